@@ -718,7 +718,7 @@ static DcsStatus pipelineCreate(DcsCtx *ctx, int depth, uint32_t flags, DcsPipel
     // worker spends a third of a millisecond on a list and then sleeps until its PCM is down; 0.70-0.77 ms per list with 6,
     // 8, 12, 16 or 24 of them (round 3: the link is what bounds it).  Round 5 (tools/thread_cpu.py, three interleaved rounds of 1 500
     // lists): TWO of them 0.59-0.63 ms per list at 0.43-0.55 CPU-ms, three 0.65 / 0.67, eight 0.63-0.66 / 0.74-0.87 -- every worker has a
-    // HIP stream of its own, the runtime spreads a process's streams over GPU_MAX_HW_QUEUES (8) hardware queues per device, and once
+    // HIP stream of its own, the runtime spreads a process's streams over GPU_MAX_HW_QUEUES hardware queues per device, and once
     // streams share queues a thread of the RUNTIME orders them on the host: two pipelines with twelve streams each on one device (two
     // contexts of a node, or two ranks, sharing a card) kept that thread 65 % busy, 0.45 CPU-ms per list; with two stage-B workers a
     // pipeline has six streams.  (The context's own pipeline, which serves one waiting caller's parts side by side, keeps eight.)

@@ -61,9 +61,9 @@ if os.environ.get("DCS_NO_RUNTIME_DEFAULTS"):
     print("optout-ok")
 else:
     L.dcs_runtime_defaults.restype = ctypes.c_int
-    assert L.dcs_runtime_defaults() == 1 and libc.getenv(b"GPU_MAX_HW_QUEUES") == b"8"
-    libc.setenv(b"GPU_MAX_HW_QUEUES", b"4", 1)
-    assert L.dcs_runtime_defaults() == 0 and libc.getenv(b"GPU_MAX_HW_QUEUES") == b"4"    # never overwritten
+    assert L.dcs_runtime_defaults() == 1 and libc.getenv(b"GPU_MAX_HW_QUEUES") == b"2"
+    libc.setenv(b"GPU_MAX_HW_QUEUES", b"1", 1)
+    assert L.dcs_runtime_defaults() == 0 and libc.getenv(b"GPU_MAX_HW_QUEUES") == b"1"    # never overwritten
     print("explicit-ok")
 '''
     lib = os.path.join(ROOT, "dcsexplorer_amd", "libdcs_hip.so")
