@@ -196,9 +196,12 @@ static uint32_t planChunks(const DcsFrameJob *jobs, uint32_t nJobs, const Src *s
         // hand-off buffer when the predecessor is the LAST frame of an EARLIER chunk (the usual case along a chain:
         // that wavefront publishes the tail, this one picks it up after its own transform; chunks are dispatched in
         // index order, so the producer is never behind the consumer), (c) otherwise by decoding the predecessor a
-        // second time in this chunk as a halo slot.
+        // second time in this chunk as a halo slot.  A hand-off row has ONE importer (the rendezvous has two sides, and
+        // the producer names its consumer in nextJob): of several successors of one frame (a fork), the first planned in a
+        // later chunk imports and the others take (a) or (c).
         auto canImport = [&](uint32_t p) {
-            return handoff && homeChunk[p] != 0xFFFFFFFFu && homeChunk[p] < chunk && lastLive[homeChunk[p]] == homePos[p];
+            return handoff && homeChunk[p] != 0xFFFFFFFFu && homeChunk[p] < chunk && lastLive[homeChunk[p]] == homePos[p]
+                   && (slots[homePos[p]].flags & DCS_SLOT_EXPORT) == 0;
         };
         uint32_t need = (link && !inChunk(prev) && !canImport(prev)) ? 2u : 1u;
         // imgCap (resident batches, dcsPlanChunksCapped): a chunk whose runs would outgrow the batch's pool image is closed early

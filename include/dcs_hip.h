@@ -194,7 +194,8 @@ typedef struct DcsFrameJob             /* one output frame = one MainLoop pass; 
     uint8_t  xform;                    /* DCS_XFORM_*: a decoder object has ONE transform (:3147-3160)  */
     uint8_t  flags;                    /* reserved, 0                                                   */
     uint32_t prev;                     /* job whose last 16 samples overlap into this frame (:569-575,
-                                          :810-812), or DCS_PREV_NONE, or DCS_PREV_EXT | k              */
+                                          :810-812), or DCS_PREV_NONE, or DCS_PREV_EXT | k.  The links may
+                                          form any graph: forks, forward links and cycles are allowed   */
     uint32_t reserved;
 } DcsFrameJob;
 

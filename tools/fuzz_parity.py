@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Seeded fuzz of the decode path on a GPU box: lists of random streams (every layout, 1..18 bands, strided from a random
 band, six symbol profiles, some with flipped payload bits or cut short) decoded with 4, 8 and 16 frames per wavefront
-and held against the oracle, the device's index pass held against the host's; every fourth seed also a multi-channel mix of 2..6 streams on one decoder, every eighth the list through dcs_pipeline.  argv[1]: seconds to run (default 120), argv[2]: first seed."""
+and held against the oracle, the device's index pass held against the host's; every fourth seed also a multi-channel mix of 2..6 streams on one decoder, every fourth (another) the list's links rewired into a random graph against tests/graph_ref.py, every eighth the list through dcs_pipeline.  argv[1]: seconds to run (default 120), argv[2]: first seed."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -10,12 +10,13 @@ import dcsexplorer_amd as D
 from oracle.dcs_oracle import Oracle
 from util import ALL_FORMATS, FORMAT_NAMES, make_stream, os_for, corrupt, splitmix
 from mixer_ref import build_mix_batch
+from graph_ref import graph_ref, rewire, permute
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 orc = Oracle()
 ctx = D.Context(0)
-t0 = t_said = time.time(); lists = frames = mixes = piped = large = 0; seed = seed0
+t0 = t_said = time.time(); lists = frames = mixes = piped = large = graphs = 0; seed = seed0
 pipes = [ctx.pipeline(3, index_on_device=m >= 1, pack_on_device=m >= 2, plan_on_device=m == 3) for m in range(4)]
 by_fmt = {f: 0 for f in ALL_FORMATS}
 while time.time() - t0 < budget:
@@ -61,6 +62,23 @@ while time.time() - t0 < budget:
             print("MISMATCH seed %d fpw %d: %s" % (seed, fpw, "shape" if bad is None else "%d samples in %d frames, first frame %d" % (len(bad), len(set(bad[:, 0])), bad[0][0])))
             sys.exit(1)
     lists += 1; frames += want.shape[0]
+    # every fourth seed (not a mix's) the list's links rewired into a random graph -- forks, links between streams and, in
+    # every other such list, the jobs in a random order (forward links) -- against the graph reference, PCM and every tail
+    if seed % 4 == 2:
+        b = D.build_stream_batch(streams, extra_frames=1)
+        rng = np.random.default_rng(seed)
+        jobs = rewire(b["jobs"], rng, 0.05 + 0.3 * rng.random())
+        if seed % 8 == 2:
+            jobs = permute(jobs, rng)
+        gwant, gtails = graph_ref(orc, streams, b, jobs)
+        for fpw in (4, 8, 16):
+            ctx.set_frames_per_wave(fpw)
+            pcm, err, tails = ctx.decode_batch(b["blob"], b["srcs"], jobs, want_tails=True)
+            if not np.array_equal(pcm, gwant) or not np.array_equal(tails, gtails):
+                bad = np.argwhere(pcm != gwant)
+                print("MISMATCH (graph) seed %d fpw %d: %d samples in %d frames%s" % (seed, fpw, len(bad), len(set(bad[:, 0])), ", tails differ" if not np.array_equal(tails, gtails) else ""))
+                sys.exit(1)
+        graphs += 1; frames += gwant.shape[0]
     # every eighth seed the list also goes through dcs_pipeline in its four modes (index pass on the host pool / on the
     # device / index pass and packer on the device / planner too), in flight twice: once with the taper frame, once without
     # (then a stream's last frame and the next one's first sit side by side in a chunk)
@@ -136,5 +154,5 @@ while time.time() - t0 < budget:
         print("  ... %d lists, %d mixes, %.0f s" % (lists, mixes, t_said - t0), flush=True)
 for pipe in pipes:
     pipe.close()
-print("fuzz: %d lists (%d of them also through the pipeline's four modes), %d large lists through dcs_decode_streams' three paths and %d multi-channel mixes (%d frames x 3 kernel variants) in %.0f s, seeds %d..%d, all bit-exact; streams by layout: %s" %
-      (lists, piped, large, mixes, frames, time.time() - t0, seed0, seed - 1, {FORMAT_NAMES[f]: n for f, n in by_fmt.items()}))
+print("fuzz: %d lists (%d of them also through the pipeline's four modes, %d also as random graphs), %d large lists through dcs_decode_streams' three paths and %d multi-channel mixes (%d frames x 3 kernel variants) in %.0f s, seeds %d..%d, all bit-exact; streams by layout: %s" %
+      (lists, piped, graphs, large, mixes, frames, time.time() - t0, seed0, seed - 1, {FORMAT_NAMES[f]: n for f, n in by_fmt.items()}))
