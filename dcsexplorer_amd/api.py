@@ -75,6 +75,19 @@ class DevicePathTimes(ctypes.Structure):
                 ("framesPerWave", ctypes.c_uint32), ("algorithmicBytes", ctypes.c_uint64)]
 
 
+class EncodeParams(ctypes.Structure):
+    _fields_ = [("formatVersion", ctypes.c_uint16), ("reserved", ctypes.c_uint16), ("streamFormatType", ctypes.c_int32),
+                ("streamFormatSubType", ctypes.c_int32), ("powerBandCutoff", ctypes.c_float), ("targetBitRate", ctypes.c_int32),
+                ("minimumDynamicRange", ctypes.c_float), ("maximumQuantizationError", ctypes.c_float)]
+
+
+ENCODE_INFO_DTYPE = np.dtype([("formatType", "<i4"), ("formatSubType", "<i4"), ("nFrames", "<i4"), ("nBytes", "<i4"),
+                              ("bandsToKeep", "<i4")])
+# the layouts encode_streams can be asked for: (type, sub-type); None = the reference's wildcard (-1, -1)
+FMT_94_T0_S3 = "94-T0-S3"
+_ENCODE_FMT = {None: (-1, -1), FMT_94_T0: (0, 0), FMT_94_T1_S0: (1, 0), FMT_94_T1_S3: (1, 3), FMT_94_T0_S3: (0, 3)}
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("format", ctypes.c_int32), ("nFrames", ctypes.c_int32),
                 ("nBands", ctypes.c_int32), ("strideFromBand", ctypes.c_int32), ("profile", ctypes.c_int32),
@@ -126,6 +139,7 @@ EXPORTS = [
     "dcs_device_path_create", "dcs_device_path_run", "dcs_device_path_run_many", "dcs_device_path_download", "dcs_device_path_destroy",
     "dcs_node_create", "dcs_node_destroy", "dcs_node_submit", "dcs_node_collect", "dcs_node_num_devices", "dcs_node_device_info",
     "dcs_node_last_error", "dcs_node_cache_release", "dcs_device_numa_node",
+    "dcs_encode_params_default", "dcs_encode_bound", "dcs_encode_header", "dcs_encode_streams",
 ]
 
 
@@ -391,6 +405,14 @@ def load_library():
     L.dcs_node_last_error.argtypes = [vp]
     L.dcs_node_cache_release.restype = None
     L.dcs_node_cache_release.argtypes = []
+    L.dcs_encode_params_default.restype = i32
+    L.dcs_encode_params_default.argtypes = [ctypes.POINTER(EncodeParams)]
+    L.dcs_encode_bound.restype = sz
+    L.dcs_encode_bound.argtypes = [ctypes.c_uint64]
+    L.dcs_encode_header.restype = i32
+    L.dcs_encode_header.argtypes = [vp, vp, vp, ctypes.POINTER(EncodeParams), i32, i32, vp, ctypes.POINTER(i32), vp]
+    L.dcs_encode_streams.restype = i32
+    L.dcs_encode_streams.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), vp, sz, vp, vp]
     L.dcs_device_numa_node.restype = ctypes.c_int
     L.dcs_device_numa_node.argtypes = [ctypes.c_int]
     L.dcs_host_threads.restype = ctypes.c_int
@@ -549,6 +571,47 @@ def synth_stream(fmt, nframes, seed, nbands=16, stride_from=16, profile=0):
     out = np.zeros(n.value, dtype=np.uint8)
     _check(L.dcs_synth_stream(ctypes.byref(p), _ptr(out), out.size, ctypes.byref(n)))
     return out.tobytes()
+
+
+def encode_params(fmt=None, **params):
+    """an EncodeParams: the reference's defaults (dcs_encode_params_default), the layout `fmt` (None = wildcard,
+    FMT_94_T0, FMT_94_T1_S0, FMT_94_T1_S3 or FMT_94_T0_S3) and any CompressionParams field by name"""
+    p = EncodeParams()
+    _check(load_library().dcs_encode_params_default(ctypes.byref(p)))
+    if fmt not in _ENCODE_FMT:
+        raise ValueError("no 1994+ encoder layout %r" % (fmt,))
+    p.streamFormatType, p.streamFormatSubType = _ENCODE_FMT[fmt]
+    for k, v in params.items():
+        if k not in dict(EncodeParams._fields_) or k == "reserved":
+            raise TypeError("unknown encoder parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def encode_bound(n_samples):
+    """dcs_encode_bound: the largest stream n_samples samples can encode to (0 = not encodable)"""
+    return int(load_library().dcs_encode_bound(int(n_samples)))
+
+
+def encode_header(power_sum, lo, hi, fmt_type, fmt_sub_type, **params):
+    """dcs_encode_header -> (16 header bytes, bandsToKeep, bitsPerBand[16])"""
+    a = [np.ascontiguousarray(x, dtype=np.float32) for x in (power_sum, lo, hi)]
+    assert all(x.shape == (16,) for x in a)
+    p = encode_params(**params)
+    hdr, bits, keep = np.zeros(16, np.uint8), np.zeros(16, np.int32), ctypes.c_int32()
+    _check(load_library().dcs_encode_header(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), ctypes.byref(p), int(fmt_type), int(fmt_sub_type),
+                                            _ptr(hdr), ctypes.byref(keep), _ptr(bits)))
+    return hdr, keep.value, bits
+
+
+def _encode_input(pcm_list):
+    parts = []
+    for x in pcm_list:
+        x = np.asarray(x)
+        parts.append(x.astype(np.float32) / np.float32(32768.0) if x.dtype == np.int16 else np.asarray(x, dtype=np.float32))
+    offs = np.zeros(len(parts) + 1, np.uint64)
+    offs[1:] = np.cumsum([len(x) for x in parts])
+    return (np.concatenate(parts) if parts else np.zeros(1, np.float32)), offs
 
 
 def format_os(fmt, prefer_95=False, prefer_93a=False):
@@ -809,6 +872,20 @@ class Context:
 
     def batch(self, blob, srcs, jobs, tails_in=None):
         return Batch(self, blob, srcs, jobs, tails_in)
+
+    def encode_streams(self, pcm_list, fmt=None, **params):
+        """dcs_encode_streams: PCM at 31 250 Hz (float32 in [-1, 1], or int16, which is divided by 32768) -> 1994+ streams,
+        byte for byte the reference DCSEncoder's.  fmt: None = the reference's wildcard, or FMT_94_T0, FMT_94_T1_S0,
+        FMT_94_T1_S3, FMT_94_T0_S3; params: CompressionParams fields by name.  Returns (list of bytes, ENCODE_INFO_DTYPE array)."""
+        p = encode_params(fmt, **params)
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        out_offs = np.zeros(n + 1, np.uint64)
+        info = np.zeros(n, ENCODE_INFO_DTYPE)
+        cap = sum(encode_bound(offs[i + 1] - offs[i]) for i in range(n))
+        out = np.zeros(max(cap, 1), np.uint8)
+        _check(self.L.dcs_encode_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info
 
     def extract_streams(self, romset, volume=255, extra_frames=2):
         """the whole `--extract-streams` pipeline: ROM set -> plan -> one launch -> PCM per stream.

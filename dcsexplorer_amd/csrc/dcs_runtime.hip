@@ -2282,3 +2282,11 @@ extern "C" DcsStatus dcs_ctx_call_floor(DcsCtx *ctx, uint32_t nFrames, int iters
 #include "dcs_pipeline.hip.h"
 #include "dcs_device_path.hip.h"
 #include "dcs_node.hip.h"
+
+// What the encoder's translation unit (dcs_encode.hip: compiled apart so that its floating-point contract applies to it
+// alone) needs of a context: its device, its stream, its error text and its buffer cache.
+int dcsCtxDevice(DcsCtx *ctx) { return ctx->device; }
+hipStream_t dcsCtxStream(DcsCtx *ctx) { return ctx->stream; }
+void dcsCtxSetError(DcsCtx *ctx, const char *text) { setError(ctx, text); }
+hipError_t dcsCtxAlloc(DcsCtx *ctx, void **out, size_t bytes) { return cacheAlloc(ctx, false, out, bytes); }
+void dcsCtxFree(DcsCtx *ctx, void *p, size_t bytes) { cacheFree(ctx, false, p, bytes); }

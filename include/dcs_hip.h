@@ -31,7 +31,10 @@
 extern "C" {
 #endif
 
-#define DCS_ABI_VERSION 9              /* 9: dcs_decode_batch_live, dcs_seq_decode_view, dcs_seq_plan_ahead, dcs_seq_stream_playing_at (round 6) */
+#define DCS_ABI_VERSION 9              /* 9: dcs_decode_batch_live, dcs_seq_decode_view, dcs_seq_plan_ahead, dcs_seq_stream_playing_at (round 6);
+                                          additions since, which change no existing layout or entry point: the 1994+ encoder
+                                          (DcsEncodeParams, DcsEncodeInfo, dcs_encode_params_default, dcs_encode_bound,
+                                          dcs_encode_header, dcs_encode_streams) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -753,6 +756,53 @@ DcsStatus dcs_pack_chunks(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcD
 DcsStatus dcs_pack_chunks_device(DcsCtx *ctx, const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, uint32_t nSrcs,
                                  const uint8_t *blob, size_t blobLen, int fpw,
                                  uint8_t *out, size_t cap, uint32_t *nChunksOut, uint32_t *packageBytesOut);
+
+/* ------------------------------------------------------------------------------------------------
+ * Encoder: PCM at 31 250 Hz -> 1994+ DCS streams, byte for byte what the reference's DCSEncoder writes for the same
+ * samples and CompressionParams (OpenStream(31250) / WriteStream(const float *, n) / CloseStream, DCSEncoder.cpp:520-960,
+ * :1623-2050, with its resampler at ratio 1).  Three departures, where the reference is undefined or wrong
+ * ("Encoding"): the rate model's 1 << bitsPerBand is 1 << (bitsPerBand & 31) (what its x86 build
+ * computes); a Type-1 candidate code whose scale index exceeds 0x3f is not eligible (the reference reads past its
+ * table); empty streams and streams of more than 65 535 frames are rejected.  Only formatVersion 0x9400 for now.
+ */
+typedef struct DcsEncodeParams         /* DCSEncoder::CompressionParams (DCSEncoder.h:70-180)                         */
+{
+    uint16_t formatVersion;            /* 0x9400 (the 1994+ format; the OS93 encoders are not built)                     */
+    uint16_t reserved;
+    int32_t  streamFormatType;         /* 0, 1, or -1: try both                                                          */
+    int32_t  streamFormatSubType;      /* 0, 3, or -1: try both                                                          */
+    float    powerBandCutoff;          /* 0.97                                                                           */
+    int32_t  targetBitRate;            /* bits per second, 1 .. 100 000 000; 128 000                                     */
+    float    minimumDynamicRange;      /* 10 / 32768                                                                     */
+    float    maximumQuantizationError; /* 10 / 32768                                                                     */
+} DcsEncodeParams;
+
+typedef struct DcsEncodeInfo
+{
+    int32_t formatType;                /* the layout written: type 0 or 1 ...                                            */
+    int32_t formatSubType;             /* ... and sub-type 0 or 3 (a wildcard picks the first strictly smallest of        */
+                                       /*     (0,0), (0,3), (1,0), (1,3), as CloseStream does)                            */
+    int32_t nFrames;                   /* ceil(nSamples / 240)                                                            */
+    int32_t nBytes;                    /* stream length: 2-byte frame count, 16-byte header, the frames' bits             */
+    int32_t bandsToKeep;               /* bands the power cutoff keeps (0..16)                                            */
+} DcsEncodeInfo;
+
+DcsStatus dcs_encode_params_default(DcsEncodeParams *params);
+/* the largest stream nSamples samples can encode to (0 when nSamples is 0 or more than 65 535 frames) */
+size_t    dcs_encode_bound(uint64_t nSamples);
+/* The stream header of one layout from a stream's statistics (CloseStream :740-770, CompressStream :859-960):
+ * powerSum[16] = per-band power summed over the frames in frame order, lo/hi[16] = per-band sample range over the
+ * stream.  Writes the 16 header bytes, the bands kept and the rate model's bits per band (0 for dropped bands). */
+DcsStatus dcs_encode_header(const float *powerSum, const float *lo, const float *hi, const DcsEncodeParams *params,
+                            int formatType, int formatSubType, uint8_t *headerOut, int32_t *bandsToKeepOut, int32_t *bitsPerBandOut);
+/* Encode nStreams streams on the GPU.  pcm = float samples in [-1, 1]; stream i is pcm[sampleOffsets[i] ..
+ * sampleOffsets[i+1]).  Stream i is written to out + outOffsets[i] (outOffsets[nStreams] = total bytes).
+ * DCS_ERR_CAPACITY: outCap is too small; outOffsets is filled all the same, so outOffsets[nStreams] is the size needed.
+ * DCS_ERR_INVALID_ARG: bad params, an empty stream, more than 65 535 frames.  DCS_ERR_BAD_STREAM: a sample that is
+ * not finite or has |x| > 1.  No CPU fallback.  info (optional) = nStreams records. */
+DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                             const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                             DcsEncodeInfo *info);
 
 uint32_t dcs_abi_version(void);
 /* a digest of the sources and compiler flags this library was built from (16 hex digits).  Counter profiles under

@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""Encoder throughput on one GPU (dcs_encode_streams, host buffers in and out, timed to the call's return, which
+synchronises the device): frames per second and the real-time factor (seconds of 31 250 Hz audio per second) for
+256 streams x 256 frames and for one stream of 65 535 frames (the format's longest), in the reference's wildcard layout
+(three layouts searched).  --rocprof: per-kernel times from `rocprofv3 --kernel-trace --stats`, in a run of their own.
+Prints one JSON line."""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def signal(n, seed):
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) / 31250.0
+    x = 0.3 * np.sin(2 * np.pi * 220.0 * (1 + seed % 7) * t) + 0.1 * np.sin(2 * np.pi * 3100.0 * t) + 0.05 * rng.standard_normal(n)
+    return np.clip(np.rint(x * 32767), -32768, 32767).astype(np.int16)
+
+
+def measure(ctx, pcm, iters):
+    ctx.encode_streams(pcm)                     # warm-up: buffers, code objects
+    times = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        streams, _ = ctx.encode_streams(pcm)
+        times.append(time.perf_counter() - t0)
+    frames = sum((len(x) + 239) // 240 for x in pcm)
+    med = float(np.median(times))
+    return dict(streams=len(pcm), frames=frames, iters=iters, median_ms=round(med * 1e3, 3), min_ms=round(min(times) * 1e3, 3),
+                frames_per_s=round(frames / med), realtime_factor=round(frames * 240 / 31250.0 / med, 1),
+                bytes_out=sum(len(s) for s in streams))
+
+
+def rocprof(iters):
+    with tempfile.TemporaryDirectory() as d:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "enc", "--", sys.executable, os.path.abspath(__file__),
+               "--iters", str(iters)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        if r.returncode != 0:
+            return dict(error="rocprofv3 exit %d" % r.returncode, stderr=r.stderr[-800:])
+        out = {}
+        for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+            for row in csv.DictReader(open(path)):
+                name = row.get("Name", "")
+                if "enc" in name:
+                    short = name.replace("(anonymous namespace)::", "").split("(")[0].split("::")[-1]
+                    out[short] = dict(calls=int(row["Calls"]), total_ms=round(float(row["TotalDurationNs"]) / 1e6, 3),
+                                      avg_us=round(float(row["AverageNs"]) / 1e3, 1))
+        return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--rocprof", action="store_true")
+    a = ap.parse_args()
+    if a.rocprof:
+        print(json.dumps(dict(kernels=rocprof(3))))
+        return
+    import dcsexplorer_amd as D
+    ctx = D.Context(0)
+    batch = [signal(256 * 240, k) for k in range(256)]
+    res = dict(batch_256x256=measure(ctx, batch, a.iters), stream_65535=measure(ctx, [signal(65535 * 240, 999)], max(2, a.iters // 3)))
+    ctx.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
