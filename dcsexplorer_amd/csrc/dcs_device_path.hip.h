@@ -17,10 +17,10 @@ struct DcsDevicePath
 {
     DcsCtx *ctx = nullptr;
     uint32_t nStreams = 0, extraFrames = 0;
-    uint64_t totalRec = 0, nJobs = 0;
+    uint64_t nJobs = 0;
     std::vector<uint32_t> firstJob;
-    void *dBlob = nullptr, *dRec = nullptr, *dInfo = nullptr, *dLocs = nullptr;
-    size_t blobCap = 0, recBytes = 0, infoBytes = 0, locBytes = 0, blobLen = 0;
+    CacheBuf dBlob, dRec, dInfo, dLocs;
+    size_t blobLen = 0;
     DcsBatch *batch = nullptr;
     hipEvent_t ev[6] = { nullptr };
 };
@@ -33,10 +33,8 @@ extern "C" void dcs_device_path_destroy(DcsDevicePath *d)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     if (d->batch) dcs_batch_destroy(d->batch);
-    if (d->dBlob) cacheFree(ctx, false, d->dBlob, d->blobCap);
-    if (d->dRec) cacheFree(ctx, false, d->dRec, d->recBytes);
-    if (d->dInfo) cacheFree(ctx, false, d->dInfo, d->infoBytes);
-    if (d->dLocs) cacheFree(ctx, false, d->dLocs, d->locBytes);
+    for (CacheBuf *c : { &d->dBlob, &d->dRec, &d->dInfo, &d->dLocs })       // (in this order: the cache evicts what came back first)
+        c->release();
     for (hipEvent_t e : d->ev)
         if (e) (void)hipEventDestroy(e);
     delete d;
@@ -47,81 +45,53 @@ extern "C" DcsStatus dcs_device_path_create(DcsCtx *ctx, const DcsStreamRef *str
     if (ctx == nullptr || streams == nullptr || nStreams == 0 || out == nullptr)
         return DCS_ERR_INVALID_ARG;
     *out = nullptr;
+    // the streams end to end, as pipelineUpload lays them out per list
+    std::vector<DcsStreamLoc> locs;
+    std::vector<uint64_t> firstRecord;
+    size_t blobLen = 0;
+    uint64_t totalRec = 0;
+    DcsStatus st = layoutStreams(streams, nStreams, locs, firstRecord, &blobLen, &totalRec);
+    if (st != DCS_OK)
+        return st;
     DcsDevicePath *d = new (std::nothrow) DcsDevicePath;
     if (d == nullptr)
         return DCS_ERR_NO_MEMORY;
     d->ctx = ctx; d->nStreams = nStreams; d->extraFrames = extraFrames;
-    // the streams end to end, each on a 4-byte boundary (what pipelineUpload lays out per list)
-    std::vector<DcsStreamLoc> locs(nStreams);
-    std::vector<uint64_t> firstRecord(nStreams);
-    size_t blobLen = 0;
-    uint64_t totalRec = 0;
-    for (uint32_t k = 0 ; k < nStreams ; ++k)
-    {
-        const DcsStreamRef &sr = streams[k];
-        if (sr.data == nullptr || sr.len < 3 || sr.os < DCS_OS93A || sr.os > DCS_OS95)
-        {
-            delete d;
-            return DCS_ERR_INVALID_ARG;
-        }
-        const uint32_t nFrames = (static_cast<uint32_t>(sr.data[0]) << 8) | sr.data[1];
-        if (nFrames == 0)
-        {
-            delete d;
-            return DCS_ERR_BAD_STREAM;
-        }
-        const size_t most = 2 + 16 + (static_cast<size_t>(nFrames) * DCS_MAX_FRAME_BITS + 7) / 8 + 8;
-        const size_t len = sr.len < most ? sr.len : most;
-        blobLen = (blobLen + 3) & ~size_t(3);
-        locs[k].off = blobLen; locs[k].len = static_cast<uint32_t>(len); locs[k].os = sr.os; locs[k].firstRecord = totalRec;
-        firstRecord[k] = totalRec;
-        blobLen += len;
-        totalRec += nFrames;
-    }
-    d->totalRec = totalRec;
     d->blobLen = blobLen;
-    d->blobCap = ((blobLen + 3) & ~size_t(3)) + 64;
-    std::vector<DcsPlanStream> table;
-    uint64_t nJobs = 0, payload = 0;
-    bool all94 = true, has93a = false;
-    DcsStatus st = planTableFor(streams, nStreams, extraFrames, locs.data(), firstRecord.data(), table, d->firstJob, &nJobs, &payload, &all94, &has93a);
-    if (st == DCS_OK && (nJobs > 0xFFFFFFFFull || totalRec > 0xFFFFFFFFull))
-        st = DCS_ERR_CAPACITY;
+    DcsPlanTable table;
+    st = planTableFor(streams, nStreams, extraFrames, locs.data(), firstRecord.data(), totalRec, table, d->firstJob);
     if (st != DCS_OK)
     {
         delete d;
         return st;
     }
-    d->nJobs = nJobs;
-    std::vector<uint8_t> blob(d->blobCap, 0);
+    d->nJobs = table.nJobs;
+    std::vector<uint8_t> blob(deviceBlobBytes(blobLen), 0);
     for (uint32_t k = 0 ; k < nStreams ; ++k)
         memcpy(blob.data() + locs[k].off, streams[k].data, locs[k].len);
     st = [&]() -> DcsStatus {
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        d->recBytes = sizeof(DcsFrameIndex) * (totalRec ? totalRec : 1);
-        d->infoBytes = sizeof(DcsStreamInfo) * nStreams;
-        d->locBytes = sizeof(DcsStreamLoc) * nStreams;
-        HIPCHK(ctx, cacheAlloc(ctx, false, &d->dBlob, d->blobCap));
-        HIPCHK(ctx, cacheAlloc(ctx, false, &d->dRec, d->recBytes));
-        HIPCHK(ctx, cacheAlloc(ctx, false, &d->dInfo, d->infoBytes));
-        HIPCHK(ctx, cacheAlloc(ctx, false, &d->dLocs, d->locBytes));
-        HIPCHK(ctx, hipMemcpyAsync(d->dBlob, blob.data(), d->blobCap, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d->dLocs, locs.data(), d->locBytes, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(d->dRec, 0, d->recBytes, ctx->stream));
+        HIPCHK(ctx, d->dBlob.alloc(ctx, false, blob.size()));
+        HIPCHK(ctx, d->dRec.alloc(ctx, false, sizeof(DcsFrameIndex) * (totalRec ? totalRec : 1)));
+        HIPCHK(ctx, d->dInfo.alloc(ctx, false, sizeof(DcsStreamInfo) * nStreams));
+        HIPCHK(ctx, d->dLocs.alloc(ctx, false, sizeof(DcsStreamLoc) * nStreams));
+        HIPCHK(ctx, hipMemcpyAsync(d->dBlob.as(), blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d->dLocs.as(), locs.data(), d->dLocs.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(d->dRec.as(), 0, d->dRec.bytes(), ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         for (hipEvent_t &e : d->ev)
             HIPCHK(ctx, hipEventCreate(&e));
         // the first pass: index walk, then the batch (which queues planner and packer behind it) and its decode launch
-        HIPCHK(ctx, launchIndexWave(ctx->stream, reinterpret_cast<uintptr_t>(d->dBlob), static_cast<const DcsStreamLoc *>(d->dLocs), nStreams, ctx->dTables,
-                                    static_cast<DcsFrameIndex *>(d->dRec), static_cast<DcsStreamInfo *>(d->dInfo), nullptr));
+        HIPCHK(ctx, launchIndexWave(ctx->stream, reinterpret_cast<uintptr_t>(d->dBlob.as()), d->dLocs.as<const DcsStreamLoc>(), nStreams, ctx->dTables,
+                                    d->dRec.as<DcsFrameIndex>(), d->dInfo.as<DcsStreamInfo>(), nullptr));
         return DCS_OK;
     }();
+    BatchOptions o(ctx);
+    o.xcdRanges = pipeXcdRanges();
     if (st == DCS_OK)
-        st = createBatchPlannedOnDevice(ctx, table.data(), nStreams, extraFrames, static_cast<uint32_t>(nJobs), static_cast<uint32_t>(totalRec), all94, has93a,
-                                        payload, static_cast<const DcsFrameIndex *>(d->dRec), static_cast<const DcsStreamInfo *>(d->dInfo),
-                                        static_cast<const uint8_t *>(d->dBlob), d->blobLen, ctx->stream, &d->batch);
+        st = createBatchPlannedOnDevice(ctx, o, table, extraFrames, static_cast<uint32_t>(totalRec), d->dRec.as<const DcsFrameIndex>(),
+                                        d->dInfo.as<const DcsStreamInfo>(), d->dBlob.as<const uint8_t>(), d->blobLen, &d->batch);
     if (st == DCS_OK) st = dcs_batch_run(d->batch, nullptr);
-    if (st == DCS_OK) st = batchQueuePlanFlag(d->batch);
     if (st == DCS_OK) st = dcs_batch_sync(d->batch);
     if (st == DCS_OK && batchPlanFlag(d->batch) != 0)
     {
@@ -143,11 +113,11 @@ static DcsStatus devicePathPass(DcsDevicePath *d, hipEvent_t *e)
     DcsCtx *ctx = d->ctx;
     DcsBatch *b = d->batch;
     if (e) HIPCHK(ctx, hipEventRecord(e[0], ctx->stream));
-    HIPCHK(ctx, launchIndexWave(ctx->stream, reinterpret_cast<uintptr_t>(d->dBlob), static_cast<const DcsStreamLoc *>(d->dLocs), d->nStreams, ctx->dTables,
-                                static_cast<DcsFrameIndex *>(d->dRec), static_cast<DcsStreamInfo *>(d->dInfo), nullptr));
+    HIPCHK(ctx, launchIndexWave(ctx->stream, reinterpret_cast<uintptr_t>(d->dBlob.as()), d->dLocs.as<const DcsStreamLoc>(), d->nStreams, ctx->dTables,
+                                d->dRec.as<DcsFrameIndex>(), d->dInfo.as<DcsStreamInfo>(), nullptr));
     if (e) HIPCHK(ctx, hipEventRecord(e[1], ctx->stream));
-    DcsStatus st = queuePlanAndPack(b, d->nStreams, d->extraFrames, static_cast<const DcsFrameIndex *>(d->dRec), static_cast<const DcsStreamInfo *>(d->dInfo),
-                                    static_cast<const uint8_t *>(d->dBlob), d->blobLen, e ? e[2] : nullptr);
+    DcsStatus st = queuePlanAndPack(b, d->nStreams, d->extraFrames, d->dRec.as<const DcsFrameIndex>(), d->dInfo.as<const DcsStreamInfo>(),
+                                    d->dBlob.as<const uint8_t>(), d->blobLen, e ? e[2] : nullptr);
     if (st != DCS_OK)
         return st;
     if (e) HIPCHK(ctx, hipEventRecord(e[3], ctx->stream));
@@ -196,8 +166,7 @@ extern "C" DcsStatus dcs_device_path_run(DcsDevicePath *d, int iters, DcsDeviceP
         if (st != DCS_OK)
             return st;
     }
-    DcsStatus st = batchQueuePlanFlag(d->batch);
-    if (st == DCS_OK) st = dcs_batch_sync(d->batch);
+    const DcsStatus st = dcs_batch_sync(d->batch);
     if (st != DCS_OK)
         return st;
     t->planFlags = batchPlanFlag(d->batch);

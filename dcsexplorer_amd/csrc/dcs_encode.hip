@@ -27,12 +27,11 @@
 #include "../../include/dcs_hip.h"
 #include "dcs_tables.h"
 #include "dcs_enc_tables.h"
+#include "dcs_cache.h"
 
 int dcsCtxDevice(DcsCtx *ctx);
 hipStream_t dcsCtxStream(DcsCtx *ctx);
 void dcsCtxSetError(DcsCtx *ctx, const char *text);
-hipError_t dcsCtxAlloc(DcsCtx *ctx, void **out, size_t bytes);
-void dcsCtxFree(DcsCtx *ctx, void *p, size_t bytes);
 
 namespace {
 
@@ -806,11 +805,11 @@ extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uin
     const uint64_t nSamples = sampleOffsets[nStreams] - sampleOffsets[0];
 
     const hipStream_t st = dcsCtxStream(ctx);
-    std::vector<std::pair<void *, size_t>> held;
+    std::vector<CacheBuf> held;
     auto alloc = [&](void **p, size_t bytes) -> hipError_t {
-        bytes = (bytes + 255) & ~size_t(255);
-        const hipError_t e = dcsCtxAlloc(ctx, p, bytes);
-        if (e == hipSuccess) held.emplace_back(*p, bytes);
+        held.emplace_back();
+        const hipError_t e = held.back().alloc(ctx, false, (bytes + 255) & ~size_t(255));
+        *p = held.back().as();
         return e;
     };
     EncTabs *dT; float *dPcm, *dSpec, *dPw, *dLo, *dHi; EncStream *dStr; uint32_t *dFS, *dBad, *dFrameBits, *dFrameOff, *dW;
@@ -892,7 +891,7 @@ extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uin
         return DCS_OK;
     }();
     (void)hipStreamSynchronize(st);
-    for (auto &h : held)
-        dcsCtxFree(ctx, h.first, h.second);
+    for (CacheBuf &h : held)
+        h.release();
     return status;
 }

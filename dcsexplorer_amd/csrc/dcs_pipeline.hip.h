@@ -47,15 +47,14 @@ struct DcsPipeline
         // ---- index pass on the device
         bool onDevice = false;                  // records came from the device; the streams lie in hBlob
         uint32_t path = 0;                      // DCS_PIPE_*: the stages of THIS list that ran on the device
-        uint8_t *hBlob = nullptr;               // the streams as uploaded, end to end (pinned); the packer reads them
-        size_t hBlobCap = 0, hBlobLen = 0;
-        void *dBlob = nullptr;                  // the same on the device, for the walk only
-        size_t dBlobCap = 0;
+        CacheBuf hBlob;                         // the streams as uploaded, end to end (pinned); the packer reads them
+        size_t hBlobLen = 0;
+        CacheBuf dBlob;                         // the same on the device, for the walk only
         std::vector<DcsStreamLoc> locs;         // offsets relative to the list's blob
         std::vector<uint64_t> firstRecord, streamOff;
         uint64_t totalRec = 0;
-        void *hRec = nullptr, *hInfo = nullptr; // records (or, packing on the device, their digests) and stream summaries
-        size_t recBytes = 0, infoBytes = 0;     //   as they come back (pinned)
+        CacheBuf hRec, hInfo;                   // records (or, packing on the device, their digests) and stream summaries
+                                                //   as they come back (pinned)
         hipEvent_t uploaded = nullptr;
         // results copied into caller memory by the worker (dcs_decode_streams in parts): optional
         int16_t *pcmDst = nullptr;
@@ -67,8 +66,7 @@ struct DcsPipeline
         double tSubmit = 0, tTaken = 0, tQueuedForIndex = 0, tIndexStart = 0, tIndexed = 0, tStageB = 0, tDone = 0;     // (DCS_PIPE_TRACE)
         // what the index round writes for this list (device; fixed sizes per list, so the context's cache serves them): the
         // records -- which stay resident for the device packer --, their digests, the stream summaries
-        void *dRec = nullptr, *dDigest = nullptr, *dInfo = nullptr;
-        size_t dRecBytes = 0, dDigestBytes = 0;
+        CacheBuf dRec, dDigest, dInfo;
         const DcsFrameIndex *dRecords = nullptr;    // = dRec once the round has run
         // planner on the device: the list's stream locations and result addresses as the index kernel takes them
     };
@@ -110,17 +108,12 @@ static void pipeLog(const char *who, int id, const char *what, double t0, double
         fprintf(stderr, "pipe thread: %s %d %s %.3f %.3f %zu %zu\n", who, id, what, t0, t1, q1, q2);
 }
 
-static void pipelineFreeIndexBuffers(DcsPipeline *p, DcsPipeline::Job *job, bool keepHostBlob)
+static void pipelineFreeIndexBuffers(DcsPipeline::Job *job)
 {
-    DcsCtx *ctx = p->ctx;
     job->dRecords = nullptr;
-    if (job->dRec) { cacheFree(ctx, false, job->dRec, job->dRecBytes); job->dRec = nullptr; }
-    if (job->dDigest) { cacheFree(ctx, false, job->dDigest, job->dDigestBytes); job->dDigest = nullptr; }
-    if (job->dInfo) { cacheFree(ctx, false, job->dInfo, job->infoBytes); job->dInfo = nullptr; }
-    if (job->dBlob) { cacheFree(ctx, false, job->dBlob, job->dBlobCap); job->dBlob = nullptr; }
-    if (job->hRec) { cacheFree(ctx, true, job->hRec, job->recBytes); job->hRec = nullptr; }
-    if (job->hInfo) { cacheFree(ctx, true, job->hInfo, job->infoBytes); job->hInfo = nullptr; }
-    if (job->hBlob && !keepHostBlob) { cacheFree(ctx, true, job->hBlob, job->hBlobCap); job->hBlob = nullptr; }
+    // (in this order, not the members': the cache evicts what came back first)
+    for (CacheBuf *c : { &job->dRec, &job->dDigest, &job->dInfo, &job->dBlob, &job->hRec, &job->hInfo, &job->hBlob })
+        c->release();
     if (job->uploaded) { (void)hipEventDestroy(job->uploaded); job->uploaded = nullptr; }
 }
 
@@ -133,7 +126,7 @@ static void pipelineRelease(DcsPipeline *p, DcsPipeline::JobPtr &job)
             dcs_batch_destroy(job->batch);
             job->batch = nullptr;
         }
-        pipelineFreeIndexBuffers(p, job.get(), false);
+        pipelineFreeIndexBuffers(job.get());
     }
     job.reset();
 }
@@ -149,62 +142,72 @@ static void pipelineFinish(DcsPipeline *p, const DcsPipeline::JobPtr &job, DcsSt
     p->finished.notify_all();
 }
 
-// stage A (device index pass): lay the list's streams end to end in pinned memory and send them up
-static DcsStatus pipelineUpload(DcsPipeline *p, DcsPipeline::Job *job, hipStream_t stream)
+// The streams of a list end to end, each on a 4-byte boundary and no longer than its header plus nFrames maximal frames (the
+// caller's buffer may be the rest of a ROM): where each lies in the list's blob and where its index records go.
+static DcsStatus layoutStreams(const DcsStreamRef *streams, uint32_t n, std::vector<DcsStreamLoc> &locs, std::vector<uint64_t> &firstRecord,
+                              size_t *blobLenOut, uint64_t *totalRecOut)
 {
-    DcsCtx *ctx = p->ctx;
-    const uint32_t n = job->nStreams;
-    job->locs.resize(n); job->firstRecord.resize(n); job->streamOff.resize(n);
+    locs.resize(n); firstRecord.resize(n);
     size_t blobLen = 0;
     uint64_t totalRec = 0;
     for (uint32_t k = 0 ; k < n ; ++k)
     {
-        const DcsStreamRef &sr = job->streams[k];
+        const DcsStreamRef &sr = streams[k];
         if (sr.data == nullptr || sr.len < 3 || sr.os < DCS_OS93A || sr.os > DCS_OS95)
             return DCS_ERR_INVALID_ARG;
         const uint32_t nFrames = (static_cast<uint32_t>(sr.data[0]) << 8) | sr.data[1];
         if (nFrames == 0)
             return DCS_ERR_BAD_STREAM;
-        // no stream is longer than its header plus nFrames maximal frames (the caller's buffer may be the rest of a ROM)
         const size_t most = 2 + 16 + (static_cast<size_t>(nFrames) * DCS_MAX_FRAME_BITS + 7) / 8 + 8;
         const size_t len = sr.len < most ? sr.len : most;
         blobLen = (blobLen + 3) & ~size_t(3);
-        job->locs[k].off = blobLen; job->locs[k].len = static_cast<uint32_t>(len); job->locs[k].os = sr.os;
-        job->locs[k].firstRecord = totalRec;
-        job->streamOff[k] = blobLen;
-        job->firstRecord[k] = totalRec;
+        locs[k].off = blobLen; locs[k].len = static_cast<uint32_t>(len); locs[k].os = sr.os; locs[k].firstRecord = totalRec;
+        firstRecord[k] = totalRec;
         blobLen += len;
         totalRec += nFrames;
     }
-    job->totalRec = totalRec;
-    job->hBlobLen = blobLen;
-    job->hBlobCap = ((blobLen + 3) & ~size_t(3)) + 64;          // zero tail: the walk prefetches, the packer copies whole dwords
-    job->dBlobCap = job->hBlobCap;
-    job->recBytes = ((p->flags & DCS_PIPE_PACK_ON_DEVICE) ? sizeof(DcsFrameDigest) : sizeof(DcsFrameIndex)) * totalRec;
-    job->infoBytes = sizeof(DcsStreamInfo) * n;
+    *blobLenOut = blobLen;
+    *totalRecOut = totalRec;
+    return DCS_OK;
+}
+
+// stage A (device index pass): lay the list's streams end to end in pinned memory and send them up
+static DcsStatus pipelineUpload(DcsPipeline *p, DcsPipeline::Job *job, hipStream_t stream)
+{
+    DcsCtx *ctx = p->ctx;
+    const uint32_t n = job->nStreams;
+    {
+        const DcsStatus st = layoutStreams(job->streams, n, job->locs, job->firstRecord, &job->hBlobLen, &job->totalRec);
+        if (st != DCS_OK)
+            return st;
+    }
+    job->streamOff.resize(n);
+    for (uint32_t k = 0 ; k < n ; ++k)
+        job->streamOff[k] = job->locs[k].off;
+    const size_t blobLen = job->hBlobLen, blobBytes = deviceBlobBytes(blobLen);
+    const uint64_t totalRec = job->totalRec;
     const double tu0 = nowMs();
-    HIPCHK(ctx, cacheAlloc(ctx, true, reinterpret_cast<void **>(&job->hBlob), job->hBlobCap));
+    HIPCHK(ctx, job->hBlob.alloc(ctx, true, blobBytes));
     const bool planOnDevice = (p->flags & DCS_PIPE_PLAN_ON_DEVICE) != 0;       // (then nothing of the index pass comes back to the host)
     if (!planOnDevice)
     {
-        HIPCHK(ctx, cacheAlloc(ctx, true, &job->hRec, job->recBytes));
-        HIPCHK(ctx, cacheAlloc(ctx, true, &job->hInfo, job->infoBytes));
+        HIPCHK(ctx, job->hRec.alloc(ctx, true, ((p->flags & DCS_PIPE_PACK_ON_DEVICE) ? sizeof(DcsFrameDigest) : sizeof(DcsFrameIndex)) * totalRec));
+        HIPCHK(ctx, job->hInfo.alloc(ctx, true, sizeof(DcsStreamInfo) * n));
     }
-    HIPCHK(ctx, cacheAlloc(ctx, false, &job->dBlob, job->dBlobCap));
-    job->dRecBytes = sizeof(DcsFrameIndex) * (totalRec ? totalRec : 1);
-    job->dDigestBytes = sizeof(DcsFrameDigest) * (totalRec ? totalRec : 1);
-    HIPCHK(ctx, cacheAlloc(ctx, false, &job->dRec, job->dRecBytes));
+    HIPCHK(ctx, job->dBlob.alloc(ctx, false, blobBytes));
+    HIPCHK(ctx, job->dRec.alloc(ctx, false, sizeof(DcsFrameIndex) * (totalRec ? totalRec : 1)));
     if ((p->flags & DCS_PIPE_PACK_ON_DEVICE) && !planOnDevice)
-        HIPCHK(ctx, cacheAlloc(ctx, false, &job->dDigest, job->dDigestBytes));
-    HIPCHK(ctx, cacheAlloc(ctx, false, &job->dInfo, job->infoBytes));
+        HIPCHK(ctx, job->dDigest.alloc(ctx, false, sizeof(DcsFrameDigest) * (totalRec ? totalRec : 1)));
+    HIPCHK(ctx, job->dInfo.alloc(ctx, false, sizeof(DcsStreamInfo) * n));
     const double tu1 = nowMs();
-    memset(job->hBlob + blobLen, 0, job->hBlobCap - blobLen);
+    uint8_t *hBlob = job->hBlob.as<uint8_t>();
+    memset(hBlob + blobLen, 0, blobBytes - blobLen);
     for (uint32_t k = 0 ; k < n ; ++k)
     {
         const DcsStreamLoc &l = job->locs[k];
         if (k + 1 < n)          // (the alignment gap in front of the next stream)
-            memset(job->hBlob + l.off + l.len, 0, static_cast<size_t>(job->locs[k + 1].off - l.off) - l.len);
-        memcpy(job->hBlob + l.off, job->streams[k].data, l.len);
+            memset(hBlob + l.off + l.len, 0, static_cast<size_t>(job->locs[k + 1].off - l.off) - l.len);
+        memcpy(hBlob + l.off, job->streams[k].data, l.len);
     }
     const double tu2 = nowMs();
     HIPCHK(ctx, hipEventCreateWithFlags(&job->uploaded, hipEventDisableTiming));
@@ -214,8 +217,8 @@ static DcsStatus pipelineUpload(DcsPipeline *p, DcsPipeline::Job *job, hipStream
     // workgroups (an upload then takes 0.15 ms instead of 0.05) the link runs at 93-97 %: 0.74 -> 0.58 ms per list sustained (round 4).
     // (a list far larger than those measured gets more of them, one per 300 KB up to 32, so that its upload stays shorter than its PCM's way down)
     static const unsigned upBlocksEnv = getenv("DCS_PIPE_UP_BLOCKS") != nullptr ? static_cast<unsigned>(std::max(1, atoi(getenv("DCS_PIPE_UP_BLOCKS")))) : 0u;
-    const unsigned upBlocks = upBlocksEnv != 0 ? upBlocksEnv : static_cast<unsigned>(std::min<size_t>(32, std::max<size_t>(8, job->hBlobCap / (300u << 10))));
-    HIPCHK(ctx, copyByKernel(stream, job->dBlob, job->hBlob, job->hBlobCap, (p->flags & kPipeLatency) ? 1024u : upBlocks));
+    const unsigned upBlocks = upBlocksEnv != 0 ? upBlocksEnv : static_cast<unsigned>(std::min<size_t>(32, std::max<size_t>(8, blobBytes / (300u << 10))));
+    HIPCHK(ctx, copyByKernel(stream, job->dBlob.as(), hBlob, blobBytes, (p->flags & kPipeLatency) ? 1024u : upBlocks));
     HIPCHK(ctx, hipEventRecord(job->uploaded, stream));
     if (getenv("DCS_PIPE_TRACE"))
         fprintf(stderr, "pipe upload: allocs %.2f, memcpy %.2f, hip calls %.2f\n", tu1 - tu0, tu2 - tu1, nowMs() - tu2);
@@ -290,10 +293,10 @@ static void pipelineIndexer(DcsPipeline *p, int which)
                 {
                     const DcsStreamLoc &l = j->locs[i];
                     locs[k] = l;
-                    locs[k].off = reinterpret_cast<uint64_t>(j->dBlob) + l.off;
-                    outs[k].records = static_cast<DcsFrameIndex *>(j->dRec) + l.firstRecord;
-                    outs[k].digest = j->dDigest != nullptr ? static_cast<DcsFrameDigest *>(j->dDigest) + l.firstRecord : nullptr;
-                    outs[k].info = static_cast<DcsStreamInfo *>(j->dInfo) + i;
+                    locs[k].off = reinterpret_cast<uint64_t>(j->dBlob.as()) + l.off;
+                    outs[k].records = j->dRec.as<DcsFrameIndex>() + l.firstRecord;
+                    outs[k].digest = j->dDigest ? j->dDigest.as<DcsFrameDigest>() + l.firstRecord : nullptr;
+                    outs[k].info = j->dInfo.as<DcsStreamInfo>() + i;
                 }
             for (const DcsPipeline::JobPtr &j : jobs)
                 HIPCHK(ctx, hipStreamWaitEvent(stream, j->uploaded, 0));
@@ -301,10 +304,10 @@ static void pipelineIndexer(DcsPipeline *p, int which)
             HIPCHK(ctx, launchIndexWave(stream, 0, static_cast<const DcsStreamLoc *>(dTable), nStreams, ctx->dTables, nullptr, nullptr, nullptr,
                                         reinterpret_cast<const dcsidx::StreamOut *>(static_cast<const uint8_t *>(dTable) + locBytes)));
             for (const DcsPipeline::JobPtr &j : jobs)
-                if (j->hRec != nullptr)         // (planner on the device: the records stay where they are)
+                if (j->hRec)                    // (planner on the device: the records stay where they are)
                 {
-                    HIPCHK(ctx, hipMemcpyAsync(j->hRec, packOnDevice ? j->dDigest : j->dRec, j->recBytes, hipMemcpyDeviceToHost, stream));
-                    HIPCHK(ctx, hipMemcpyAsync(j->hInfo, j->dInfo, j->infoBytes, hipMemcpyDeviceToHost, stream));
+                    HIPCHK(ctx, hipMemcpyAsync(j->hRec.as(), (packOnDevice ? j->dDigest : j->dRec).as(), j->hRec.bytes(), hipMemcpyDeviceToHost, stream));
+                    HIPCHK(ctx, hipMemcpyAsync(j->hInfo.as(), j->dInfo.as(), j->hInfo.bytes(), hipMemcpyDeviceToHost, stream));
                 }
             HIPCHK(ctx, streamWait(ctx, stream));
             return DCS_OK;
@@ -313,7 +316,7 @@ static void pipelineIndexer(DcsPipeline *p, int which)
             (void)streamWait(ctx, stream);
         if (packOnDevice && st == DCS_OK)
             for (const DcsPipeline::JobPtr &j : jobs)
-                j->dRecords = static_cast<const DcsFrameIndex *>(j->dRec);      // (they stay until the list has packed)
+                j->dRecords = j->dRec.as<const DcsFrameIndex>();      // (they stay until the list has packed)
         const double dt = nowMs() - t0;
         pipeLog("indexer", which, "round", t0, nowMs(), jobs.size(), nStreams);
         {
@@ -342,6 +345,13 @@ static void pipelineIndexer(DcsPipeline *p, int which)
 // is dispatched before it on the consumer's own XCD, so no wait depends on a place becoming free.  (ONE decode stream per device,
 // which also rules the circle out, was measured first: 0.92 ms per list instead of 0.60 -- lists waiting behind each other's packers.)
 
+// (DCS_PIPE_XCD_RANGES=0, an experiment switch: the pipelines' batches are made without them)
+static bool pipeXcdRanges()
+{
+    static const bool on = getenv("DCS_PIPE_XCD_RANGES") == nullptr || atoi(getenv("DCS_PIPE_XCD_RANGES")) != 0;
+    return on;
+}
+
 // How a list's PCM comes down: by the runtime's copy (hipMemcpyAsync into pinned memory, which this runtime does with a blit
 // kernel of its own), or -- DCS_PIPE_DOWN_BLOCKS=n, and always for a pipeline with ONE waiting caller (the context's own), where
 // hipMemcpyAsync now and then holds the calling thread for 7 ms (profiles/NOTES.md 17) -- by dcsCopyKernel with at most n workgroups.
@@ -366,24 +376,24 @@ static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream
     DcsBuiltStreams &built = scratch;
     const bool packOnDevice = (p->flags & DCS_PIPE_PACK_ON_DEVICE) != 0 && job->dRecords != nullptr;
     thread_local DcsBuiltPlan planScratch;
-    if (job->hRec != nullptr)
+    if (job->hRec)
     {
         // a stream whose frames run past its buffer reads the missing bytes as zero, which streams laid end to end
         // cannot express: such a list (truncated input) takes the host path.  What counts is the bits the frames
         // occupy, not nBytes, which includes the reference reader's look-ahead of up to three bytes (:1509).
-        const DcsStreamInfo *infos = static_cast<const DcsStreamInfo *>(job->hInfo);
+        const DcsStreamInfo *infos = job->hInfo.as<const DcsStreamInfo>();
         fromDevice = true;
         for (uint32_t k = 0 ; k < job->nStreams && fromDevice ; ++k)
             fromDevice = infos[k].nFrames != 0
                       && 2u + static_cast<size_t>(infos[k].hdrLen) + (static_cast<size_t>(infos[k].payloadBits) + 7) / 8 <= job->locs[k].len;
         if (fromDevice && packOnDevice)
         {
-            const DcsDigested in{ static_cast<const DcsFrameDigest *>(job->hRec), job->firstRecord.data(), infos, job->streamOff.data(), 0 };
+            const DcsDigested in{ job->hRec.as<const DcsFrameDigest>(), job->firstRecord.data(), infos, job->streamOff.data(), 0 };
             st = dcsBuildPlanFromDigest(job->streams, job->nStreams, job->extraFrames, in, planScratch);
         }
         else if (fromDevice)
         {
-            const DcsPreIndexed pre{ static_cast<const DcsFrameIndex *>(job->hRec), job->firstRecord.data(), infos, job->streamOff.data() };
+            const DcsPreIndexed pre{ job->hRec.as<const DcsFrameIndex>(), job->firstRecord.data(), infos, job->streamOff.data() };
             st = dcsBuildStreams(job->streams, job->nStreams, job->extraFrames, built, false, false, &pre);
         }
     }
@@ -402,20 +412,21 @@ static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream
     job->path = fromDevice ? (DCS_PIPE_INDEX_ON_DEVICE | (devicePacked ? DCS_PIPE_PACK_ON_DEVICE : 0u)) : 0u;
     job->firstJob = devicePacked ? planScratch.firstJob : built.firstJob;
     const size_t nJobsBuilt = devicePacked ? planScratch.jobs.size() : built.jobs.size();
-    const uint8_t *blob = fromDevice ? job->hBlob : built.blob.data();
+    const uint8_t *blob = fromDevice ? job->hBlob.as<const uint8_t>() : built.blob.data();
     const size_t blobLen = fromDevice ? job->hBlobLen : built.blob.size();
     double t1 = nowMs(), t2 = t1;
     if (st == DCS_OK)
     {
-        const bool handoff = p->ctx->handoff;
+        BatchOptions o(p->ctx, stream);
+        o.xcdRanges = pipeXcdRanges();
         const DcsBuiltStreams &B = built;
         if (devicePacked)
-            st = createBatchOnDevice(p->ctx, planScratch.jobs.data(), static_cast<uint32_t>(planScratch.jobs.size()), planScratch.srcs.data(),
-                                     static_cast<uint32_t>(planScratch.srcs.size()), job->dRecords, static_cast<const uint8_t *>(job->dBlob),
-                                     job->hBlobLen, stream, handoff, &job->batch);
+            st = createBatchOnDevice(p->ctx, o, planScratch.jobs.data(), static_cast<uint32_t>(planScratch.jobs.size()), planScratch.srcs.data(),
+                                     static_cast<uint32_t>(planScratch.srcs.size()), job->dRecords, job->dBlob.as<const uint8_t>(),
+                                     job->hBlobLen, &job->batch);
         else
-            st = createBatch(p->ctx, blob, blobLen, B.srcs.data(), static_cast<uint32_t>(B.srcs.size()),
-                             B.jobs.data(), static_cast<uint32_t>(B.jobs.size()), nullptr, 0, stream, handoff, &job->batch);
+            st = createBatch(p->ctx, o, blob, blobLen, B.srcs.data(), static_cast<uint32_t>(B.srcs.size()),
+                             B.jobs.data(), static_cast<uint32_t>(B.jobs.size()), nullptr, 0, &job->batch);
         t2 = nowMs();
         if (st == DCS_OK) st = dcs_batch_run(job->batch, nullptr);
         // (DCS_PIPE_TRACE=3 waits for the kernels first, so that the thread log tells them from the copies)
@@ -436,7 +447,7 @@ static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream
         if (job->batch != nullptr) { dcs_batch_destroy(job->batch); job->batch = nullptr; }
         (void)streamWait(p->ctx, stream);
     }
-    pipelineFreeIndexBuffers(p, job, false);        // (the packages are on the device: the streams are no longer needed)
+    pipelineFreeIndexBuffers(job);        // (the packages are on the device: the streams are no longer needed)
     if (st == DCS_OK && job->pcmDst != nullptr)
     {
         memcpy(job->pcmDst, job->pcm, sizeof(int16_t) * DCS_FRAME_SAMPLES * nJobsBuilt);
@@ -453,54 +464,6 @@ static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream
     return st;
 }
 
-// The device planner's stream table (DcsPlanStream, 40 bytes a stream): what the host knows of every stream of a list of
-// whole streams without walking it -- where it lies in the list's blob, its layout, frame count, and the mixing parameters
-// of frame 0 and of every later frame.  Also the first output frame of every stream (n + 1 entries) and the list's totals.
-static DcsStatus planTableFor(const DcsStreamRef *streams, uint32_t n, uint32_t extraFrames, const DcsStreamLoc *locs, const uint64_t *firstRecord,
-                              std::vector<DcsPlanStream> &table, std::vector<uint32_t> &firstJob, uint64_t *nJobsOut, uint64_t *payloadOut,
-                              bool *all94Out, bool *has93aOut)
-{
-    table.resize(n);
-    firstJob.resize(static_cast<size_t>(n) + 1);
-    uint64_t nJobs = 0, payload = 0;
-    bool all94 = true, has93a = false;
-    for (uint32_t k = 0 ; k < n ; ++k)
-    {
-        const DcsStreamRef &sr = streams[k];
-        const uint8_t *d = sr.data;
-        const uint32_t len = locs[k].len;
-        const uint32_t nFrames = (static_cast<uint32_t>(d[0]) << 8) | d[1];
-        const bool typeBit = (d[2] & 0x80) != 0;
-        const uint32_t h12 = (len > 3 ? d[3] : 0u) | (len > 4 ? d[4] : 0u);
-        const DcsOsVersion os = static_cast<DcsOsVersion>(sr.os);
-        DcsPlanStream &t = table[k];
-        t = DcsPlanStream{};
-        t.hdrLen = (os == DCS_OS93A && typeBit) ? 1 : 16;
-        t.format = static_cast<uint8_t>(os == DCS_OS93A ? (typeBit ? DCS_FMT_93A_T1 : DCS_FMT_93_T0)
-                                      : os == DCS_OS93B ? (typeBit ? DCS_FMT_93B_T1 : DCS_FMT_93_T0)
-                                      : !typeBit ? DCS_FMT_94_T0 : (h12 & 0x80) == 0 ? DCS_FMT_94_T1_S0 : DCS_FMT_94_T1_S3);
-        t.xform = (os == DCS_OS93A || os == DCS_OS93B) ? DCS_XFORM_93 : DCS_XFORM_94;
-        all94 = all94 && t.xform == DCS_XFORM_94;
-        has93a = has93a || t.format == DCS_FMT_93A_T1;
-        t.streamOff = locs[k].off;
-        t.len = len;
-        t.firstRecord = static_cast<uint32_t>(firstRecord[k]);
-        t.firstJob = static_cast<uint32_t>(nJobs);
-        t.nFrames = nFrames;
-        uint16_t mm[2]; uint8_t vs[2];
-        const DcsStatus st = dcs_stream_params_from(os, sr.volume, sr.level, sr.channelVolume, 0x7FFF, 2, mm, vs);    // frame 0, and every later frame
-        if (st != DCS_OK)
-            return st;
-        t.mixMul0 = mm[0]; t.mixMulN = mm[1]; t.volShift0 = vs[0]; t.volShiftN = vs[1];
-        firstJob[k] = static_cast<uint32_t>(nJobs);
-        nJobs += nFrames + extraFrames;
-        payload += len;
-    }
-    firstJob[n] = static_cast<uint32_t>(nJobs);
-    *nJobsOut = nJobs; *payloadOut = payload; *all94Out = all94; *has93aOut = has93a;
-    return DCS_OK;
-}
-
 // Planner on the device (DCS_PIPE_PLAN_ON_DEVICE), stage B: the list's index records are on the device (an indexer's round
 // put them there); planner, packer and decode kernels and the PCM's way down are queued on the worker's stream, and the one
 // wait is for the PCM.  Returns DCS_OK with *served = false when the arithmetic plan cannot serve the list (DCS_PLAN_*):
@@ -510,34 +473,29 @@ static DcsStatus pipelineDecodePlanned(DcsPipeline *p, DcsPipeline::Job *job, hi
     DcsCtx *ctx = p->ctx;
     *served = false;
     const double t0 = nowMs();
-    DcsStatus st = DCS_OK;
-    const uint32_t n = job->nStreams;
     // what the host knows of every stream without walking it
-    thread_local std::vector<DcsPlanStream> table;
-    uint64_t nJobs = 0, payload = 0;
-    bool all94 = true, has93a = false;
-    st = planTableFor(job->streams, n, job->extraFrames, job->locs.data(), job->firstRecord.data(), table, job->firstJob, &nJobs, &payload, &all94, &has93a);
+    thread_local DcsPlanTable table;
+    DcsStatus st = planTableFor(job->streams, job->nStreams, job->extraFrames, job->locs.data(), job->firstRecord.data(), job->totalRec, table, job->firstJob);
     if (st != DCS_OK)
         return st;
-    if (nJobs > 0xFFFFFFFFull || job->totalRec > 0xFFFFFFFFull)
-        return DCS_ERR_CAPACITY;
+    const uint64_t nJobs = table.nJobs;
     // A chunk whose frames' compressed bytes overflow the kernel's bit pool (224 bytes per slot) is what the arithmetic plan cannot
     // close early as the host planner does: the list is planned again with fewer frames per chunk -- three quarters, then half of the
     // slots -- before the host path gets it (one stream of large frames among 600 would otherwise cost the whole list the device).
     double t1 = t0, t2 = t0;
     uint32_t flag = 0;
-    const int fullFpw = chooseFpw(ctx, static_cast<uint32_t>(nJobs), all94);
+    const int fullFpw = chooseFpw(ctx, static_cast<uint32_t>(nJobs), table.all94);
     const int tries[3] = { 0, fullFpw * 3 / 4, fullFpw / 2 };
+    BatchOptions o(ctx, stream);
+    o.xcdRanges = pipeXcdRanges();
     for (int attempt = 0 ; attempt < 3 ; ++attempt)
     {
         if (job->batch != nullptr) { dcs_batch_destroy(job->batch); job->batch = nullptr; }
-        st = createBatchPlannedOnDevice(ctx, table.data(), n, job->extraFrames, static_cast<uint32_t>(nJobs), static_cast<uint32_t>(job->totalRec), all94,
-                                        has93a, payload, static_cast<const DcsFrameIndex *>(job->dRec), static_cast<const DcsStreamInfo *>(job->dInfo),
-                                        static_cast<const uint8_t *>(job->dBlob), job->hBlobLen, stream, &job->batch, tries[attempt]);
+        st = createBatchPlannedOnDevice(ctx, o, table, job->extraFrames, static_cast<uint32_t>(job->totalRec), job->dRec.as<const DcsFrameIndex>(),
+                                        job->dInfo.as<const DcsStreamInfo>(), job->dBlob.as<const uint8_t>(), job->hBlobLen, &job->batch, tries[attempt]);
         t1 = nowMs();
         pipeLog("worker", 0, "plan-queue", t0, t1);
         if (st == DCS_OK) st = dcs_batch_run(job->batch, nullptr);
-        if (st == DCS_OK) st = batchQueuePlanFlag(job->batch);
         t2 = nowMs();
         pipeLog("worker", 0, "run-queue", t1, t2);
         if (st == DCS_OK) pipelineDownPolicy(p, job->batch);
@@ -557,12 +515,12 @@ static DcsStatus pipelineDecodePlanned(DcsPipeline *p, DcsPipeline::Job *job, hi
         // not served (or failed): nothing of this attempt stays
         if (job->batch != nullptr) { dcs_batch_destroy(job->batch); job->batch = nullptr; }
         (void)streamWait(ctx, stream);
-        pipelineFreeIndexBuffers(p, job, false);
+        pipelineFreeIndexBuffers(job);
         return st;
     }
     job->onDevice = true;
     job->path = DCS_PIPE_INDEX_ON_DEVICE | DCS_PIPE_PACK_ON_DEVICE | DCS_PIPE_PLAN_ON_DEVICE;
-    pipelineFreeIndexBuffers(p, job, false);
+    pipelineFreeIndexBuffers(job);
     if (job->pcmDst != nullptr)
     {
         memcpy(job->pcmDst, job->pcm, sizeof(int16_t) * DCS_FRAME_SAMPLES * nJobs);
@@ -576,8 +534,6 @@ static DcsStatus pipelineDecodePlanned(DcsPipeline *p, DcsPipeline::Job *job, hi
 static void pipelineWorker(DcsPipeline *p, int id)
 {
     pthread_setname_np(pthread_self(), "dcs-worker");
-    static const bool xcdRanges = getenv("DCS_PIPE_XCD_RANGES") == nullptr || atoi(getenv("DCS_PIPE_XCD_RANGES")) != 0;     // (0: an experiment switch)
-    tlsXcdRanges = xcdRanges;                               // (this thread's batches: chain order, launched in XCD ranges; see above)
     tlsBlockingWaits = (p->flags & kPipeLatency) == 0;      // (the context's own pipeline serves ONE waiting caller: its threads poll)
     (void)hipSetDevice(p->ctx->device);
     const hipStream_t stream = p->streams[id];
@@ -616,7 +572,7 @@ static void pipelineWorker(DcsPipeline *p, int id)
             pipeLog("worker", id, "upload", t0, nowMs());
             if (st != DCS_OK)
             {
-                pipelineFreeIndexBuffers(p, job.get(), false);
+                pipelineFreeIndexBuffers(job.get());
                 pipelineFinish(p, job, st);
                 continue;
             }
@@ -628,15 +584,15 @@ static void pipelineWorker(DcsPipeline *p, int id)
                 // indexer waits for its round, because stage B runs on another stream.)
                 DcsStatus s2 = [&]() -> DcsStatus {
                     DcsCtx *ctx = p->ctx;
-                    HIPCHK(ctx, copyByKernel(stream, job->dRec, job->preRecords + job->preFirstRecord[0], sizeof(DcsFrameIndex) * job->totalRec, 64u));
-                    HIPCHK(ctx, copyByKernel(stream, job->dInfo, job->preInfos, job->infoBytes, 1u));
+                    HIPCHK(ctx, copyByKernel(stream, job->dRec.as(), job->preRecords + job->preFirstRecord[0], sizeof(DcsFrameIndex) * job->totalRec, 64u));
+                    HIPCHK(ctx, copyByKernel(stream, job->dInfo.as(), job->preInfos, job->dInfo.bytes(), 1u));
                     HIPCHK(ctx, streamWait(ctx, stream));
                     return DCS_OK;
                 }();
                 const double t1 = nowMs();
                 {
                     std::lock_guard<std::mutex> lk(p->m);
-                    job->dRecords = static_cast<const DcsFrameIndex *>(job->dRec);
+                    job->dRecords = job->dRec.as<const DcsFrameIndex>();
                     job->status = s2;
                     job->tQueuedForIndex = job->tIndexStart = job->tIndexed = t1;
                     p->indexed.push_back(job);
@@ -674,7 +630,7 @@ static void pipelineWorker(DcsPipeline *p, int id)
                     job->tTaken - job->tSubmit, job->tQueuedForIndex - job->tTaken, job->tIndexStart - job->tQueuedForIndex,
                     job->tIndexed - job->tIndexStart, job->tStageB - job->tIndexed, job->tDone - job->tStageB);
         }
-        pipelineFreeIndexBuffers(p, job.get(), false);      // (a list whose indexer failed still holds them)
+        pipelineFreeIndexBuffers(job.get());      // (a list whose indexer failed still holds them)
         pipelineFinish(p, job, st);
     }
 }
@@ -978,8 +934,7 @@ DcsStatus dcsDecodeStreamsInParts(DcsCtx *ctx, const DcsStreamRef *streams, uint
         }
     };
     const int idxThreads = 0;        // (all of the pool: leaving a quarter of the CPUs to the workers was measured, 6.8 against 5.8 ms)
-    void *sharedPinned = nullptr;
-    size_t sharedPinnedBytes = 0;
+    CacheBuf sharedPinned;
     uint32_t hostParts = 0;
     double tCall0 = nowMs();
     if (onDevice)
@@ -1007,17 +962,15 @@ DcsStatus dcsDecodeStreamsInParts(DcsCtx *ctx, const DcsStreamRef *streams, uint
         DcsStreamInfo *hInfos = nullptr;
         if (hostParts != 0)
         {
-            sharedPinnedBytes = sizeof(DcsFrameIndex) * hostRecs + sizeof(DcsStreamInfo) * hostStreams + 64;
-            if (cacheAlloc(ctx, true, &sharedPinned, sharedPinnedBytes) != hipSuccess)
+            if (sharedPinned.alloc(ctx, true, sizeof(DcsFrameIndex) * hostRecs + sizeof(DcsStreamInfo) * hostStreams + 64) != hipSuccess)
             {
                 (void)hipGetLastError();
-                sharedPinned = nullptr;
                 hostParts = 0;
             }
             else
             {
-                hRecs = static_cast<DcsFrameIndex *>(sharedPinned);
-                hInfos = reinterpret_cast<DcsStreamInfo *>(static_cast<uint8_t *>(sharedPinned) + ((sizeof(DcsFrameIndex) * hostRecs + 15) & ~size_t(15)));
+                hRecs = sharedPinned.as<DcsFrameIndex>();
+                hInfos = reinterpret_cast<DcsStreamInfo *>(sharedPinned.as<uint8_t>() + ((sizeof(DcsFrameIndex) * hostRecs + 15) & ~size_t(15)));
                 firstRecord.resize(hostStreams);
                 uint64_t nRec = 0;
                 for (uint32_t k = 0 ; k < hostStreams ; ++k)
@@ -1100,8 +1053,7 @@ DcsStatus dcsDecodeStreamsInParts(DcsCtx *ctx, const DcsStreamRef *streams, uint
             fprintf(stderr, "decode in parts: %u of %u parts walked by the host pool, done at %.2f ms; the device's at %.2f ms; next call %d\n",
                     hostParts, kParts, tHost, tDev, ctx->sharedHostParts);
     }
-    if (sharedPinned != nullptr)
-        cacheFree(ctx, true, sharedPinned, sharedPinnedBytes);
+    sharedPinned.release();
     if (getenv("DCS_PIPE_TRACE"))
         fprintf(stderr, "decode in parts: index %.2f ms, parts %.2f ms\n", tI1 - tI0, nowMs() - tI1);
     if (frameOffsets != nullptr)

@@ -258,7 +258,7 @@ static uint32_t planChunks(const DcsFrameJob *jobs, uint32_t nJobs, const Src *s
 
     // The chunks stay in chain order.  (Rounds 2-5 reordered them by depth in the hand-off graph, so that a consumer did not reach
     // its wait before the tail was there; consumers no longer wait -- the rendezvous, dcs_kernels.hip.h -- and the order measures
-    // the same either way: 33.15 us for 65 536 frames, tools/ab_order.sh.)
+    // the same either way: 33.15 us for 65 536 frames, measured A/B.)
     (void)depthOrder;
     return chunk;
 }

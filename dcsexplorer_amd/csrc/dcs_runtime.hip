@@ -12,11 +12,13 @@
 #include <new>
 #include <chrono>
 #include <algorithm>
+#include <type_traits>
 #include <mutex>
 #include <atomic>
 #include <unordered_set>
 #include <unordered_map>
 #include "dcs_common.h"
+#include "dcs_cache.h"
 #include "dcs_kernels.hip.h"
 #include "dcs_scan.h"
 #include "dcs_index_wave.hip.h"
@@ -145,7 +147,7 @@ static hipError_t cacheAlloc(DcsCtx *ctx, bool pinned, void **out, size_t bytes)
     return e;
 }
 
-static void cacheFree(DcsCtx *ctx, bool pinned, void *p, size_t cap)
+static void cacheFree(DcsCtx *ctx, bool pinned, void *p)
 {
     if (p == nullptr)
         return;
@@ -155,6 +157,7 @@ static void cacheFree(DcsCtx *ctx, bool pinned, void *p, size_t cap)
     // hipHostMalloc per list, 0.34 s for a job that takes 0.22.)
     std::vector<DcsCtx::Cached> victims;
     bool keep = true;
+    size_t cap = 0;
     {
         std::lock_guard<std::mutex> lock(ctx->cacheMutex);
         const auto live = ctx->liveCap.find(p);
@@ -194,11 +197,6 @@ static double hipchkNow() { return std::chrono::duration<double, std::micro>(std
 // short look first (the kernels of a small list are done in microseconds), then naps of 50 us, which the kernel's timer slack
 // makes ~110.  DCS_WAIT_RUNTIME=1 restores hipEventSynchronize.  Everybody else polls inside the runtime (shortest latency).
 static thread_local bool tlsBlockingWaits = false;
-// Batches made by THIS thread keep their chunks in chain order and are launched in XCD ranges (DCS_BATCH_XCD_RANGES): set by the
-// pipelines' workers, whose decode kernels run next to each other's.
-static thread_local bool tlsXcdRanges = false;
-static thread_local bool tlsResidentBatch = false;   // dcs_batch_create: a batch that is run many times is planned twice for the shortest packages (dcsPlanChunksCapped)
-static thread_local bool tlsKeepAllTails = false;   // dcs_decode_batch with a tailsOut array: every frame's tail (the sequencer resumes from any tick)
 
 // DCS_WAIT_STATS=1: what the host's waits cost, summed over all threads, printed when a pipeline is destroyed
 static std::atomic<uint64_t> g_waitCalls{0}, g_waitPolls{0}, g_waitCpuNs{0}, g_waitWallNs{0};
@@ -315,26 +313,26 @@ struct DcsBatch
     uint64_t abiBytes = 0;                  // the same with the records as the ABI has them (160 B per source, 16 per job)
     hipStream_t stream = nullptr;           // uploads, default launches and downloads (the context's, or the batch's own)
     // device buffers
-    uint8_t *dBlob = nullptr;
-    DcsSrcDesc *dSrcs = nullptr;
-    int16_t *dTailsIn = nullptr;
-    int16_t *dPcm = nullptr;
-    uint32_t *dErr = nullptr;
-    int16_t *dTailsOut = nullptr;
-    unsigned long long *dDebug = nullptr;   // DCS_STAMPS builds only
-    unsigned long long *dHandoff = nullptr; // nChunks x 16 words (DcsKernelArgs.handoff)
-    uint8_t *dPackages = nullptr;           // nChunks x dcsPkgBytes(fpw) (DcsKernelArgs.packages)
+    CacheBuf dBlob;                         // the streams (only frames with a second source read them)
+    CacheBuf dSrcs;                         // DcsSrcDesc[nSrcs] (likewise)
+    CacheBuf dTable;                        // the device planner's stream table (DcsPlanStream)
+    CacheBuf dTailsIn;
+    CacheBuf dPcm;                          // nJobs x 240 samples (and the error words behind them when they are joined)
+    CacheBuf dErrOwn;                       // the error words, when they are not joined to the PCM
+    CacheBuf dTailsOut;
+    CacheBuf dDebug;                        // DCS_STAMPS builds only
+    CacheBuf dHandoff;                      // (nChunks + 1) x 16 words (DcsKernelArgs.handoff)
+    CacheBuf dPackages;                     // nChunks x dcsPkgStride(fpw, imgDw) (DcsKernelArgs.packages)
+    uint32_t *dErr = nullptr;               // nJobs error words: in dErrOwn or behind the PCM in dPcm
     uint32_t epoch = 0;                     // launches of this batch so far
     uint32_t flags = 0;                     // DCS_BATCH_*
     uint32_t imgDw = 0;                     // the packages' LAYOUT word (dcs_common.h): dwords of pool image | DCS_PKG_SPLIT4; packages at dcsPkgStride(fpw, imgDw)
-    size_t cap[10] = { 0 };                 // allocated bytes of the buffers above, in that order
-    // packages assembled on the device: the plan and the source digests as uploaded for the pack kernel
-    void *dPlanSlots = nullptr, *dPlanSrcs = nullptr, *hStage = nullptr, *dTable = nullptr;      // (dTable: the stream table of the device planner; cap[2])
-    size_t planSlotsCap = 0, planSrcsCap = 0, hStageCap = 0;
+    // packages assembled on the device: the plan and the source digests as uploaded for the pack kernel, and the pinned staging
+    // they (or the device planner's stream table, behind its flag word) went up through
+    CacheBuf dPlanSlots, dPlanSrcs, hStage;
     // pinned host mirror of (pcm, err), filled by dcs_batch_download_view
-    int16_t *hPcm = nullptr;
-    uint32_t *hErr = nullptr;
-    size_t hCap[2] = { 0 };
+    CacheBuf hPcm, hErrOwn;
+    uint32_t *hErr = nullptr;               // in hErrOwn or behind the PCM in hPcm, like dErr
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // recorded behind the last launch on whatever stream the caller launched on (a caller's stream is not ordered
     // against the context's non-blocking one): sync, download, download_view and destroy wait for it
@@ -344,7 +342,7 @@ struct DcsBatch
     unsigned downBlocks = 1024; // ... with at most this many workgroups
     bool settled = false;       // a wait has covered everything enqueued for this batch and nothing was enqueued since
     uint32_t planFpc = 0;       // frames per chunk of a plan made on the device (dcsPlanKernel)
-    bool errJoined = false;     // dErr lies behind dPcm in ONE allocation (and hErr behind hPcm): the two come down in one copy
+    bool errJoined = false;     // dErr lies behind the PCM in dPcm (and hErr in hPcm): the two come down in one copy
 };
 
 // the device work of the batch's last launch has finished (host-side wait)
@@ -640,6 +638,17 @@ static int chooseFpw(const DcsCtx *ctx, uint32_t nJobs, bool all94)
     return nJobs > simds * (all94 ? 10 : 32) ? 8 : 4;
 }
 
+// f(std::integral_constant<int, FPW>()): the kernel variant for `fpw` frames per wavefront (4 unless 8 or 16)
+template <class F>
+static auto withFpw(int fpw, F &&f)
+{
+    if (fpw == 16)
+        return f(std::integral_constant<int, 16>());
+    if (fpw == 8)
+        return f(std::integral_constant<int, 8>());
+    return f(std::integral_constant<int, 4>());
+}
+
 extern "C" void dcs_batch_destroy(DcsBatch *b)
 {
     if (b == nullptr)
@@ -653,15 +662,10 @@ extern "C" void dcs_batch_destroy(DcsBatch *b)
         if (b->evDone) (void)waitLaunched(b);
         (void)streamWait(b->ctx, b->stream);
     }
-    void *ptrs[] = { b->dBlob, b->dSrcs, b->dTable, b->dTailsIn, b->dPcm, b->errJoined ? nullptr : b->dErr, b->dTailsOut, b->dDebug, b->dHandoff, b->dPackages };
-    for (int i = 0 ; i < 10 ; ++i)
-        cacheFree(b->ctx, false, ptrs[i], b->cap[i]);
-    cacheFree(b->ctx, false, b->dPlanSlots, b->planSlotsCap);
-    cacheFree(b->ctx, false, b->dPlanSrcs, b->planSrcsCap);
-    cacheFree(b->ctx, true, b->hStage, b->hStageCap);
-    cacheFree(b->ctx, true, b->hPcm, b->hCap[0]);
-    if (!b->errJoined || b->hCap[1] != 0)
-        cacheFree(b->ctx, true, b->hErr, b->hCap[1]);
+    // (in this order, not the members': the cache evicts what came back first)
+    for (CacheBuf *c : { &b->dBlob, &b->dSrcs, &b->dTable, &b->dTailsIn, &b->dPcm, &b->dErrOwn, &b->dTailsOut, &b->dDebug, &b->dHandoff,
+                         &b->dPackages, &b->dPlanSlots, &b->dPlanSrcs, &b->hStage, &b->hPcm, &b->hErrOwn })
+        c->release();
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->evDone) (void)hipEventDestroy(b->evDone);
@@ -671,19 +675,19 @@ extern "C" void dcs_batch_destroy(DcsBatch *b)
 static DcsKernelArgs kernelArgs(const DcsBatch *b)
 {
     DcsKernelArgs args;
-    args.blob = b->dBlob;
+    args.blob = b->dBlob.as<uint8_t>();
     args.blobLen = b->blobOnDevice;
-    args.srcs = b->dSrcs;
-    args.packages = b->dPackages;
+    args.srcs = b->dSrcs.as<DcsSrcDesc>();
+    args.packages = b->dPackages.as<uint8_t>();
     args.nChunks = b->nChunks;
     args.nJobs = b->nJobs;
-    args.pcm = b->dPcm;
+    args.pcm = b->dPcm.as<int16_t>();
     args.err = b->dErr;
-    args.tailsIn = b->dTailsIn;
-    args.tailsOut = b->dTailsOut;
+    args.tailsIn = b->dTailsIn.as<int16_t>();
+    args.tailsOut = b->dTailsOut.as<int16_t>();
     args.tables = b->ctx->dTables;
-    args.debug = b->dDebug;
-    args.handoff = b->dHandoff;
+    args.debug = b->dDebug.as<unsigned long long>();
+    args.handoff = b->dHandoff.as<unsigned long long>();
     args.epoch = b->epoch;
     args.flags = b->flags | ((dcsPkgImgDw(b->imgDw) != 0 ? b->imgDw : (b->imgDw | dcsPoolCapacity(b->fpw))) << DCS_BATCH_IMG_SHIFT);
     return args;
@@ -761,16 +765,130 @@ static DcsStatus validateBatch(DcsCtx *ctx, size_t blobLen, const DcsSrcDesc *sr
     return DCS_OK;
 }
 
-// stream: where the batch's uploads, default launches and downloads run (nullptr: the context's); handoff: how tails
-// cross chunk boundaries (DcsCtx::handoff, or forced off for the second attempt after a lost tail)
-static DcsStatus createBatch(DcsCtx *ctx,
+// How a batch is made besides its jobs: what the callers of the three constructors below choose
+struct BatchOptions
+{
+    hipStream_t stream;             // uploads, default launches and downloads (the context's, or the caller's)
+    bool handoff;                   // tails cross chunk boundaries through the hand-off buffer (else: halo re-decode)
+    bool xcdRanges = false;         // chunks in chain order, launched in XCD ranges (DCS_BATCH_XCD_RANGES): the pipelines' batches,
+                                    // whose decode kernels run next to each other's
+    bool resident = false;          // dcs_batch_create: a batch that is run many times is planned twice for the shortest packages
+    bool keepAllTails = false;      // every frame's tail is stored (dcs_decode_batch with tailsOut: the sequencer resumes from any tick)
+    explicit BatchOptions(const DcsCtx *ctx, hipStream_t s = nullptr) : stream(s ? s : ctx->stream), handoff(ctx->handoff) {}
+    // chain order and XCD ranges for a batch planned on the host (the context's setting counts too, its test hook overrules)
+    bool ranges(const DcsCtx *ctx) const { return (xcdRanges || ctx->xcdRanges) && !ctx->noXcdRanges; }
+};
+
+static bool allXform94(const DcsFrameJob *jobs, uint32_t nJobs)
+{
+    bool all94 = nJobs != 0;
+    for (uint32_t j = 0 ; j < nJobs && all94 ; ++j)
+        all94 = jobs[j].xform == DCS_XFORM_94;
+    return all94;
+}
+
+// bytes of the device copy of a blob: whole dwords and a zero tail (the bit reader prefetches past the end, the packers copy whole dwords)
+static size_t deviceBlobBytes(size_t len) { return ((len + 3) & ~size_t(3)) + 64; }
+
+// The first step of every batch: the object, its stream, frames per wavefront and flags
+static DcsBatch *newBatch(DcsCtx *ctx, const BatchOptions &o, uint32_t nJobs, uint32_t nSrcs, bool all94, bool has93aT1, bool ranges)
+{
+    DcsBatch *b = new (std::nothrow) DcsBatch;
+    if (b == nullptr)
+        return nullptr;
+    b->ctx = ctx;
+    b->stream = o.stream;
+    b->nJobs = nJobs;
+    b->nSrcs = nSrcs;
+    b->fpw = chooseFpw(ctx, nJobs, all94);
+    b->flags = (has93aT1 ? DCS_BATCH_HAS_93A_T1 : 0u) | (ranges && o.handoff ? DCS_BATCH_XCD_RANGES : 0u);
+    return b;
+}
+
+// Algorithmic bytes per launch: the exact compressed payload, the header (and U16 frame count) of every stream the
+// batch draws on, a 56-byte frame descriptor per source, 480 bytes of PCM per output frame.  abiBytes counts the descriptors as
+// this ABI has them instead: 160-byte DcsSrcDesc, 16-byte DcsFrameJob.
+static void batchBytes(DcsBatch *b, uint64_t payloadBytes, uint64_t headerBytes)
+{
+    const uint64_t pcm = static_cast<uint64_t>(b->nJobs) * DCS_FRAME_SAMPLES * 2;
+    b->algoBytes = payloadBytes + headerBytes + static_cast<uint64_t>(b->nSrcs) * 56u + pcm;
+    b->abiBytes = payloadBytes + static_cast<uint64_t>(b->nSrcs) * sizeof(DcsSrcDesc) + static_cast<uint64_t>(b->nJobs) * sizeof(DcsFrameJob) + pcm;
+}
+
+// the headers of the distinct streams the sources (DcsSrcDesc or DcsPlanSrc) lie in
+template <class Src>
+static uint64_t streamHeaderBytes(const Src *srcs, uint32_t nSrcs)
+{
+    uint64_t bytes = 0, lastOff = ~0ull;
+    std::unordered_set<uint64_t> seen;
+    for (uint32_t k = 0 ; k < nSrcs ; ++k)
+        if (srcs[k].streamOff != lastOff)               // (the frames of a stream are normally consecutive sources)
+        {
+            lastOff = srcs[k].streamOff;
+            if (seen.insert(lastOff).second)
+                bytes += 2u + srcs[k].hdrLen;
+        }
+    return bytes;
+}
+
+// The last step of every batch: where its results go -- PCM, error words, every frame's tail (`tails`), hand-off words, phase
+// stamps -- and its events.  A batch planned on the device has its error words behind the PCM (one copy brings both down) and
+// leaves clearing them and the hand-off words to queuePlanAndPack, which does it in front of every pass.
+static DcsStatus batchOutputs(DcsBatch *b, bool tails, bool plannedOnDevice)
+{
+    DcsCtx *ctx = b->ctx;
+    const size_t pcmBytes = sizeof(int16_t) * DCS_FRAME_SAMPLES * b->nJobs, errBytes = sizeof(uint32_t) * b->nJobs;
+    b->errJoined = plannedOnDevice;
+    HIPCHK(ctx, b->dPcm.alloc(ctx, false, b->errJoined ? pcmBytes + errBytes : pcmBytes));
+    if (b->errJoined)
+        b->dErr = reinterpret_cast<uint32_t *>(b->dPcm.as<uint8_t>() + pcmBytes);
+    else
+    {
+        HIPCHK(ctx, b->dErrOwn.alloc(ctx, false, errBytes));
+        b->dErr = b->dErrOwn.as<uint32_t>();
+    }
+    // (without `tails` none are kept: nothing reads them, and a buffer from the recycling cache would carry another list's -- ADVICE r5)
+    if (tails)
+    {
+        HIPCHK(ctx, b->dTailsOut.alloc(ctx, false, sizeof(int16_t) * 16 * b->nJobs));
+        HIPCHK(ctx, hipMemsetAsync(b->dTailsOut.as(), 0, b->dTailsOut.bytes(), b->stream));   // (rows of frames whose tail is not kept read as zero)
+    }
+    if (!plannedOnDevice)
+        HIPCHK(ctx, hipMemsetAsync(b->dErr, 0, errBytes, b->stream));
+    HIPCHK(ctx, b->dHandoff.alloc(ctx, false, sizeof(unsigned long long) * 16 * (b->nChunks + 1)));
+    if (!plannedOnDevice)
+        HIPCHK(ctx, hipMemsetAsync(b->dHandoff.as(), 0, b->dHandoff.bytes(), b->stream));     // epoch 0 = never written
+#ifdef DCS_STAMPS
+    HIPCHK(ctx, b->dDebug.alloc(ctx, false, sizeof(unsigned long long) * 16 * (b->nChunks + 4)));
+    HIPCHK(ctx, hipMemsetAsync(b->dDebug.as(), 0, b->dDebug.bytes(), b->stream));
+#endif
+    HIPCHK(ctx, hipEventCreate(&b->ev0));
+    HIPCHK(ctx, hipEventCreate(&b->ev1));
+    HIPCHK(ctx, hipEventCreateWithFlags(&b->evDone, hipEventDisableTiming | (tlsBlockingWaits ? hipEventBlockingSync : 0u)));
+    return DCS_OK;
+}
+
+// The end of every constructor: the batch is handed out, or -- once nothing queued for it runs any more -- destroyed
+static DcsStatus batchDone(DcsBatch *b, DcsStatus st, DcsBatch **out)
+{
+    if (st != DCS_OK)
+    {
+        (void)streamWait(b->ctx, b->stream);
+        dcs_batch_destroy(b);
+        return st;
+    }
+    *out = b;
+    return DCS_OK;
+}
+
+// Plan and pack on the host: the chunk packages are built in pinned memory and uploaded
+static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
                              const uint8_t *blob, size_t blobLen,
                              const DcsSrcDesc *srcs, uint32_t nSrcs,
                              const DcsFrameJob *jobs, uint32_t nJobs,
-                             const int16_t *tailsIn, uint32_t nTailsIn,
-                             hipStream_t stream, bool handoff, DcsBatch **out)
+                             const int16_t *tailsIn, uint32_t nTailsIn, DcsBatch **out)
 {
-    if (ctx == nullptr || out == nullptr || jobs == nullptr || nJobs == 0 || (nSrcs != 0 && (srcs == nullptr || blob == nullptr)))
+    if (out == nullptr || jobs == nullptr || nJobs == 0 || (nSrcs != 0 && (srcs == nullptr || blob == nullptr)))
         return DCS_ERR_INVALID_ARG;
     *out = nullptr;
 
@@ -781,63 +899,28 @@ static DcsStatus createBatch(DcsCtx *ctx,
         if (vst != DCS_OK)
             return vst;
     }
-
-    DcsBatch *b = new (std::nothrow) DcsBatch;
+    const bool ranges = o.ranges(ctx);
+    DcsBatch *b = newBatch(ctx, o, nJobs, nSrcs, allXform94(jobs, nJobs), (batchFlags & DCS_BATCH_HAS_93A_T1) != 0, ranges);
     if (b == nullptr)
         return DCS_ERR_NO_MEMORY;
-    b->ctx = ctx;
-    b->stream = stream ? stream : ctx->stream;
-    b->nJobs = nJobs; b->nSrcs = nSrcs; b->nTailsIn = nTailsIn; b->blobLen = blobLen;
-    {
-        bool all94 = nJobs != 0;
-        for (uint32_t j = 0 ; j < nJobs && all94 ; ++j)
-            all94 = jobs[j].xform == DCS_XFORM_94;
-        b->fpw = chooseFpw(ctx, nJobs, all94);
-    }
-    b->flags = batchFlags;
+    b->nTailsIn = nTailsIn; b->blobLen = blobLen;
+    batchBytes(b, (payloadBits + 7) / 8, streamHeaderBytes(srcs, nSrcs));
 
     thread_local std::vector<DcsSlot> slots;    // (kept from batch to batch: see the pipeline's scratch)
-    uint8_t *hPackages = nullptr;           // pinned staging for the chunk packages
-    size_t pkgBytes = 0;
-    static const bool forceRanges = getenv("DCS_BATCH_XCD_RANGES") != nullptr && atoi(getenv("DCS_BATCH_XCD_RANGES")) != 0;     // (experiment switch)
-    const bool ranges = (tlsXcdRanges || ctx->xcdRanges || forceRanges) && !ctx->noXcdRanges;
-    static const bool chainOrder = getenv("DCS_EXP_CHAIN_ORDER") != nullptr && atoi(getenv("DCS_EXP_CHAIN_ORDER")) != 0;      // (experiment switch)
-    // (experiment switch, for A/B runs on one binary: round 4's packages -- the full pool image, every frame's tail stored)
-    static const bool fullImage = getenv("DCS_EXP_FULL_IMAGE") != nullptr && atoi(getenv("DCS_EXP_FULL_IMAGE")) != 0;
-    const bool allTails = ctx->keepAllTails || tlsKeepAllTails || fullImage;
-    if (tlsResidentBatch && !fullImage)
-        b->nChunks = dcsPlanChunksCapped(jobs, nJobs, srcs, b->fpw, slots, handoff, ctx->framesPerChunk, !ranges && !chainOrder, allTails, &b->imgDw,
+    const bool allTails = ctx->keepAllTails || o.keepAllTails;
+    if (o.resident)
+        b->nChunks = dcsPlanChunksCapped(jobs, nJobs, srcs, b->fpw, slots, o.handoff, ctx->framesPerChunk, !ranges, allTails, &b->imgDw,
                                           static_cast<uint32_t>(ctx->numCUs) * 16u);
     else
     {
-        b->nChunks = dcsPlanChunks(jobs, nJobs, srcs, b->fpw, slots, handoff, ctx->framesPerChunk, !ranges && !chainOrder, allTails);
-        b->imgDw = fullImage ? dcsPoolCapacity(b->fpw) : dcsImageDwords(slots.data(), b->nChunks, b->fpw);
+        b->nChunks = dcsPlanChunks(jobs, nJobs, srcs, b->fpw, slots, o.handoff, ctx->framesPerChunk, !ranges, allTails);
+        b->imgDw = dcsImageDwords(slots.data(), b->nChunks, b->fpw);
     }
     dcsShuffleChunks(slots, b->nChunks, b->fpw, ctx->shuffleSeed);          // (test hook)
-    if (!fullImage && dcsAllSources94(jobs, nJobs, srcs))
+    if (dcsAllSources94(jobs, nJobs, srcs))
         b->imgDw |= DCS_PKG_SPLIT4;             // (the layout word: every source a 1994+ frame -> 4-byte split records)
-    if (ranges && handoff)
-        b->flags |= DCS_BATCH_XCD_RANGES;
 
-    // algorithmic bytes per launch: the exact compressed payload, the header (and U16 frame count) of every
-    // stream the batch draws on, a 56-byte frame descriptor per source, 480 bytes of PCM per output frame.  abiBytes
-    // counts the descriptors as this ABI has them instead: 160-byte DcsSrcDesc, 16-byte DcsFrameJob.
-    {
-        uint64_t hdrBytes = 0;
-        uint64_t lastOff = ~0ull;
-        std::unordered_set<uint64_t> seen;
-        for (uint32_t k = 0 ; k < nSrcs ; ++k)
-            if (srcs[k].streamOff != lastOff)               // (the frames of a stream are normally consecutive sources)
-            {
-                lastOff = srcs[k].streamOff;
-                if (seen.insert(lastOff).second)
-                    hdrBytes += 2u + srcs[k].hdrLen;
-            }
-        const uint64_t payload = (payloadBits + 7) / 8, pcm = static_cast<uint64_t>(nJobs) * DCS_FRAME_SAMPLES * 2;
-        b->algoBytes = payload + hdrBytes + static_cast<uint64_t>(nSrcs) * 56u + pcm;
-        b->abiBytes = payload + static_cast<uint64_t>(nSrcs) * sizeof(DcsSrcDesc) + static_cast<uint64_t>(nJobs) * sizeof(DcsFrameJob) + pcm;
-    }
-
+    CacheBuf hPackages;                         // pinned staging for the chunk packages
     DcsStatus st = [&]() -> DcsStatus {
         HIPCHK(ctx, hipSetDevice(ctx->device));
         // Round 0 of every frame reads the chunk packages only; the streams and the full descriptors are needed on the
@@ -848,55 +931,36 @@ static DcsStatus createBatch(DcsCtx *ctx,
         b->blobOnDevice = multi ? blobLen : 0;
         if (multi)
         {
-            const size_t blobAlloc = ((blobLen + 3) & ~size_t(3)) + 64;     // zero tail: the bit reader prefetches past the end
-            b->cap[0] = blobAlloc; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dBlob), b->cap[0]));
-            HIPCHK(ctx, hipMemsetAsync(b->dBlob, 0, blobAlloc, b->stream));
+            HIPCHK(ctx, b->dBlob.alloc(ctx, false, deviceBlobBytes(blobLen)));
+            HIPCHK(ctx, hipMemsetAsync(b->dBlob.as(), 0, b->dBlob.bytes(), b->stream));
             if (blobLen)
-                HIPCHK(ctx, hipMemcpyAsync(b->dBlob, blob, blobLen, hipMemcpyHostToDevice, b->stream));
+                HIPCHK(ctx, hipMemcpyAsync(b->dBlob.as(), blob, blobLen, hipMemcpyHostToDevice, b->stream));
         }
         if (multi && nSrcs)
         {
-            b->cap[1] = sizeof(DcsSrcDesc) * nSrcs; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dSrcs), b->cap[1]));
-            HIPCHK(ctx, hipMemcpyAsync(b->dSrcs, srcs, sizeof(DcsSrcDesc) * nSrcs, hipMemcpyHostToDevice, b->stream));
+            HIPCHK(ctx, b->dSrcs.alloc(ctx, false, sizeof(DcsSrcDesc) * nSrcs));
+            HIPCHK(ctx, hipMemcpyAsync(b->dSrcs.as(), srcs, b->dSrcs.bytes(), hipMemcpyHostToDevice, b->stream));
         }
         // built in pinned host memory (recycled by the context like the device buffers): the upload runs at link speed
-        pkgBytes = static_cast<size_t>(b->nChunks) * dcsPkgStride(b->fpw, b->imgDw);
-        HIPCHK(ctx, cacheAlloc(ctx, true, reinterpret_cast<void **>(&hPackages), pkgBytes));
-        dcsBuildPackages(slots.data(), b->nChunks, b->fpw, srcs, blob, blobLen, hPackages, b->imgDw);
-        b->cap[9] = pkgBytes; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dPackages), b->cap[9]));
-        HIPCHK(ctx, hipMemcpyAsync(b->dPackages, hPackages, pkgBytes, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(ctx, hPackages.alloc(ctx, true, static_cast<size_t>(b->nChunks) * dcsPkgStride(b->fpw, b->imgDw)));
+        dcsBuildPackages(slots.data(), b->nChunks, b->fpw, srcs, blob, blobLen, hPackages.as<uint8_t>(), b->imgDw);
+        HIPCHK(ctx, b->dPackages.alloc(ctx, false, hPackages.bytes()));
+        HIPCHK(ctx, hipMemcpyAsync(b->dPackages.as(), hPackages.as(), hPackages.bytes(), hipMemcpyHostToDevice, b->stream));
         if (nTailsIn)
         {
-            b->cap[3] = sizeof(int16_t) * 16 * nTailsIn; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dTailsIn), b->cap[3]));
-            HIPCHK(ctx, hipMemcpyAsync(b->dTailsIn, tailsIn, sizeof(int16_t) * 16 * nTailsIn, hipMemcpyHostToDevice, b->stream));
+            HIPCHK(ctx, b->dTailsIn.alloc(ctx, false, sizeof(int16_t) * 16 * nTailsIn));
+            HIPCHK(ctx, hipMemcpyAsync(b->dTailsIn.as(), tailsIn, b->dTailsIn.bytes(), hipMemcpyHostToDevice, b->stream));
         }
-        b->cap[4] = sizeof(int16_t) * DCS_FRAME_SAMPLES * nJobs; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dPcm), b->cap[4]));
-        b->cap[5] = sizeof(uint32_t) * nJobs; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dErr), b->cap[5]));
-        b->cap[6] = sizeof(int16_t) * 16 * nJobs; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dTailsOut), b->cap[6]));
-        HIPCHK(ctx, hipMemsetAsync(b->dTailsOut, 0, b->cap[6], b->stream));   // (rows of frames whose tail is not kept read as zero)
-        HIPCHK(ctx, hipMemsetAsync(b->dErr, 0, sizeof(uint32_t) * nJobs, b->stream));
-        b->cap[8] = sizeof(unsigned long long) * 16 * (b->nChunks + 1); HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dHandoff), b->cap[8]));
-        HIPCHK(ctx, hipMemsetAsync(b->dHandoff, 0, b->cap[8], b->stream));     // epoch 0 = never written
-#ifdef DCS_STAMPS
-        b->cap[7] = sizeof(unsigned long long) * 16 * (b->nChunks + 4); HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dDebug), b->cap[7]));
-        HIPCHK(ctx, hipMemsetAsync(b->dDebug, 0, sizeof(unsigned long long) * 16 * (b->nChunks + 4), b->stream));
-#endif
-        HIPCHK(ctx, hipEventCreate(&b->ev0));
-        HIPCHK(ctx, hipEventCreate(&b->ev1));
-        HIPCHK(ctx, hipEventCreateWithFlags(&b->evDone, hipEventDisableTiming | (tlsBlockingWaits ? hipEventBlockingSync : 0u)));
+        const DcsStatus so = batchOutputs(b, true, false);
+        if (so != DCS_OK)
+            return so;
         HIPCHK(ctx, streamWait(b->ctx, b->stream));
         return DCS_OK;
     }();
     if (st != DCS_OK)
         (void)streamWait(b->ctx, b->stream);    // (on success the lambda has already waited for the uploads)
-    cacheFree(ctx, true, hPackages, pkgBytes);
-    if (st != DCS_OK)
-    {
-        dcs_batch_destroy(b);
-        return st;
-    }
-    *out = b;
-    return DCS_OK;
+    hPackages.release();
+    return batchDone(b, st, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1180,104 +1244,64 @@ __global__ __launch_bounds__(256) void dcsPlanKernel(const DcsPlanStream *stream
 }
 }   // namespace
 
-// plan on the host from source digests, pack on the device: `dRecords` (the index records as the device index pass
+// one wavefront per chunk, four to a workgroup (dcsPackKernel above)
+static hipError_t launchPack(int fpw, hipStream_t stream, const DcsSlot *slots, uint32_t nChunks, const DcsPlanSrc *srcs, const DcsFrameIndex *records,
+                             const uint8_t *blob, uint64_t blobLen, uint8_t *packages, uint32_t layout)
+{
+    withFpw(fpw, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL(dcsPackKernel<W>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, slots, nChunks, srcs, records, blob, blobLen, packages, layout);
+    });
+    return hipGetLastError();
+}
+
+// Plan on the host from source digests, pack on the device: `dRecords` (the index records as the device index pass
 // wrote them) and `dBlob` (the streams as uploaded for it) must stay valid until the pack kernel has run, i.e. until the
 // batch's stream has been waited for once
-static DcsStatus createBatchOnDevice(DcsCtx *ctx, const DcsFrameJob *jobs, uint32_t nJobs, const DcsPlanSrc *srcs, uint32_t nSrcs,
-                                     const DcsFrameIndex *dRecords, const uint8_t *dBlob, uint64_t blobLen,
-                                     hipStream_t stream, bool handoff, DcsBatch **out)
+static DcsStatus createBatchOnDevice(DcsCtx *ctx, const BatchOptions &o, const DcsFrameJob *jobs, uint32_t nJobs, const DcsPlanSrc *srcs, uint32_t nSrcs,
+                                     const DcsFrameIndex *dRecords, const uint8_t *dBlob, uint64_t blobLen, DcsBatch **out)
 {
     *out = nullptr;
-    DcsBatch *b = new (std::nothrow) DcsBatch;
-    if (b == nullptr)
-        return DCS_ERR_NO_MEMORY;
-    b->ctx = ctx;
-    b->stream = stream ? stream : ctx->stream;
-    b->nJobs = nJobs; b->nSrcs = nSrcs;
-    bool all94 = nJobs != 0;
-    for (uint32_t j = 0 ; j < nJobs && all94 ; ++j)
-        all94 = jobs[j].xform == DCS_XFORM_94;
-    b->fpw = chooseFpw(ctx, nJobs, all94);
-    uint64_t payloadBits = 0, hdrBytes = 0, lastOff = ~0ull;
+    uint64_t payloadBits = 0;
+    bool has93aT1 = false, all94 = nSrcs != 0;
     for (uint32_t k = 0 ; k < nSrcs ; ++k)
     {
         payloadBits += srcs[k].nBits;
-        if (srcs[k].format == DCS_FMT_93A_T1)
-            b->flags |= DCS_BATCH_HAS_93A_T1;
-        if (srcs[k].streamOff != lastOff)       // (a list's frames come stream by stream)
-        {
-            lastOff = srcs[k].streamOff;
-            hdrBytes += 2u + srcs[k].hdrLen;
-        }
+        has93aT1 = has93aT1 || srcs[k].format == DCS_FMT_93A_T1;
+        all94 = all94 && srcs[k].format >= DCS_FMT_94_T0;
     }
-    const uint64_t payload = (payloadBits + 7) / 8, pcm = static_cast<uint64_t>(nJobs) * DCS_FRAME_SAMPLES * 2;
-    b->algoBytes = payload + hdrBytes + static_cast<uint64_t>(nSrcs) * 56u + pcm;
-    b->abiBytes = payload + static_cast<uint64_t>(nSrcs) * sizeof(DcsSrcDesc) + static_cast<uint64_t>(nJobs) * sizeof(DcsFrameJob) + pcm;
+    const bool ranges = o.ranges(ctx);
+    DcsBatch *b = newBatch(ctx, o, nJobs, nSrcs, allXform94(jobs, nJobs), has93aT1, ranges);
+    if (b == nullptr)
+        return DCS_ERR_NO_MEMORY;
+    batchBytes(b, (payloadBits + 7) / 8, streamHeaderBytes(srcs, nSrcs));
 
     thread_local std::vector<DcsSlot> slots;
-    const bool ranges = (tlsXcdRanges || ctx->xcdRanges) && !ctx->noXcdRanges;
-    b->nChunks = dcsPlanChunksLite(jobs, nJobs, srcs, b->fpw, slots, handoff, ctx->framesPerChunk, !ranges);
-    b->imgDw = dcsImageDwords(slots.data(), b->nChunks, b->fpw);
-    {
-        bool all94 = nSrcs != 0;
-        for (uint32_t k = 0 ; k < nSrcs && all94 ; ++k)
-            all94 = srcs[k].format >= DCS_FMT_94_T0;
-        if (all94)
-            b->imgDw |= DCS_PKG_SPLIT4;
-    }
-    if (ranges && handoff)
-        b->flags |= DCS_BATCH_XCD_RANGES;
+    b->nChunks = dcsPlanChunksLite(jobs, nJobs, srcs, b->fpw, slots, o.handoff, ctx->framesPerChunk, !ranges);
+    b->imgDw = dcsImageDwords(slots.data(), b->nChunks, b->fpw) | (all94 ? DCS_PKG_SPLIT4 : 0u);
     dcsShuffleChunks(slots, b->nChunks, b->fpw, ctx->shuffleSeed);          // (test hook)
-    const size_t pkgBytes = static_cast<size_t>(b->nChunks) * dcsPkgStride(b->fpw, b->imgDw);
-    void *stage = nullptr;
-    size_t stageBytes = 0;
-    DcsStatus st = [&]() -> DcsStatus {
+    const DcsStatus st = [&]() -> DcsStatus {
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        b->planSlotsCap = sizeof(DcsSlot) * slots.size();
-        b->planSrcsCap = sizeof(DcsPlanSrc) * (nSrcs ? nSrcs : 1);
-        HIPCHK(ctx, cacheAlloc(ctx, false, &b->dPlanSlots, b->planSlotsCap));
-        HIPCHK(ctx, cacheAlloc(ctx, false, &b->dPlanSrcs, b->planSrcsCap));
-        // (through pinned staging: a copy from pageable memory holds the calling thread until the stream gets to it)
-        stageBytes = b->planSlotsCap + sizeof(DcsPlanSrc) * nSrcs;
-        HIPCHK(ctx, cacheAlloc(ctx, true, &stage, stageBytes));
-        memcpy(stage, slots.data(), b->planSlotsCap);
+        const size_t slotBytes = sizeof(DcsSlot) * slots.size(), srcBytes = sizeof(DcsPlanSrc) * nSrcs;
+        HIPCHK(ctx, b->dPlanSlots.alloc(ctx, false, slotBytes));
+        HIPCHK(ctx, b->dPlanSrcs.alloc(ctx, false, sizeof(DcsPlanSrc) * (nSrcs ? nSrcs : 1)));
+        // (through pinned staging, in use until the uploads have run: a copy from pageable memory holds the calling thread until the
+        // stream gets to it)
+        HIPCHK(ctx, b->hStage.alloc(ctx, true, slotBytes + srcBytes));
+        memcpy(b->hStage.as(), slots.data(), slotBytes);
         if (nSrcs)
-            memcpy(static_cast<uint8_t *>(stage) + b->planSlotsCap, srcs, sizeof(DcsPlanSrc) * nSrcs);
-        HIPCHK(ctx, copyByKernel(b->stream, b->dPlanSlots, stage, b->planSlotsCap));
+            memcpy(b->hStage.as<uint8_t>() + slotBytes, srcs, srcBytes);
+        HIPCHK(ctx, copyByKernel(b->stream, b->dPlanSlots.as(), b->hStage.as(), slotBytes));
         if (nSrcs)
-            HIPCHK(ctx, copyByKernel(b->stream, b->dPlanSrcs, static_cast<uint8_t *>(stage) + b->planSlotsCap, sizeof(DcsPlanSrc) * nSrcs));
-        b->cap[9] = pkgBytes; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dPackages), b->cap[9]));
-        const uint32_t blocks = (b->nChunks + 3) / 4;       // (the pack kernel writes every byte of the packages: nothing to clear)
-        const DcsSlot *dS = static_cast<const DcsSlot *>(b->dPlanSlots);
-        const DcsPlanSrc *dP = static_cast<const DcsPlanSrc *>(b->dPlanSrcs);
-        if (b->fpw == 16)
-            hipLaunchKernelGGL(dcsPackKernel<16>, dim3(blocks), dim3(256), 0, b->stream, dS, b->nChunks, dP, dRecords, dBlob, blobLen, b->dPackages, b->imgDw);
-        else if (b->fpw == 8)
-            hipLaunchKernelGGL(dcsPackKernel<8>, dim3(blocks), dim3(256), 0, b->stream, dS, b->nChunks, dP, dRecords, dBlob, blobLen, b->dPackages, b->imgDw);
-        else
-            hipLaunchKernelGGL(dcsPackKernel<4>, dim3(blocks), dim3(256), 0, b->stream, dS, b->nChunks, dP, dRecords, dBlob, blobLen, b->dPackages, b->imgDw);
-        HIPCHK(ctx, hipGetLastError());
-        b->cap[4] = sizeof(int16_t) * DCS_FRAME_SAMPLES * nJobs; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dPcm), b->cap[4]));
-        b->cap[5] = sizeof(uint32_t) * nJobs; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dErr), b->cap[5]));
-        // (no tails kept: nothing reads them on this path, and a buffer from the recycling cache would carry another list's -- ADVICE r5)
-        HIPCHK(ctx, hipMemsetAsync(b->dErr, 0, sizeof(uint32_t) * nJobs, b->stream));
-        b->cap[8] = sizeof(unsigned long long) * 16 * (b->nChunks + 1); HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dHandoff), b->cap[8]));
-        HIPCHK(ctx, hipMemsetAsync(b->dHandoff, 0, b->cap[8], b->stream));
-        HIPCHK(ctx, hipEventCreate(&b->ev0));
-        HIPCHK(ctx, hipEventCreate(&b->ev1));
-        HIPCHK(ctx, hipEventCreateWithFlags(&b->evDone, hipEventDisableTiming | (tlsBlockingWaits ? hipEventBlockingSync : 0u)));
+            HIPCHK(ctx, copyByKernel(b->stream, b->dPlanSrcs.as(), b->hStage.as<uint8_t>() + slotBytes, srcBytes));
+        // (the pack kernel writes every byte of the packages: nothing to clear)
+        HIPCHK(ctx, b->dPackages.alloc(ctx, false, static_cast<size_t>(b->nChunks) * dcsPkgStride(b->fpw, b->imgDw)));
+        HIPCHK(ctx, launchPack(b->fpw, b->stream, b->dPlanSlots.as<const DcsSlot>(), b->nChunks, b->dPlanSrcs.as<const DcsPlanSrc>(), dRecords,
+                               dBlob, blobLen, b->dPackages.as<uint8_t>(), b->imgDw));
         // (nothing is waited for here: the decode launch follows the pack kernel on the same stream)
-        return DCS_OK;
+        return batchOutputs(b, false, false);
     }();
-    b->hStage = stage; b->hStageCap = stageBytes;       // (in use until the uploads have run: released with the batch)
-    if (st != DCS_OK)
-    {
-        (void)streamWait(ctx, b->stream);
-        dcs_batch_destroy(b);
-        return st;
-    }
-    *out = b;
-    return DCS_OK;
+    return batchDone(b, st, out);
 }
 
 namespace {
@@ -1304,65 +1328,102 @@ static DcsStatus queuePlanAndPack(DcsBatch *b, uint32_t nStreams, uint32_t extra
     // ten per list; epoch 0 = never written; the planner's flag word lies behind the last chunk's hand-off words)
     {
         // (the packages are no longer among them: the pack kernel writes every byte of a package itself)
-        const size_t errBytes = sizeof(uint32_t) * nJobs, hoBytes = b->cap[8];
+        const size_t errBytes = sizeof(uint32_t) * nJobs, hoBytes = b->dHandoff.bytes();
         const size_t total16 = (errBytes + 15) / 16 + hoBytes / 16;
         const unsigned blocks = static_cast<unsigned>(std::min<size_t>((total16 + 255) / 256, 2048));
         hipLaunchKernelGGL(dcsClear3Kernel, dim3(blocks), dim3(256), 0, b->stream, static_cast<uint4 *>(nullptr), static_cast<size_t>(0),
-                           reinterpret_cast<uint32_t *>(b->dErr), errBytes / 4, reinterpret_cast<uint4 *>(b->dHandoff), hoBytes / 16);
+                           b->dErr, errBytes / 4, b->dHandoff.as<uint4>(), hoBytes / 16);
         HIPCHK(ctx, hipGetLastError());
     }
-    uint32_t *flagWord = reinterpret_cast<uint32_t *>(b->dHandoff + static_cast<size_t>(b->nChunks) * 16) + 2;
+    uint32_t *flagWord = reinterpret_cast<uint32_t *>(b->dHandoff.as<unsigned long long>() + static_cast<size_t>(b->nChunks) * 16) + 2;
     const uint32_t planBlocks = (b->nChunks + 63) / 64;         // (one wavefront per workgroup: a thread's work is serial, the chunks should spread over the CUs)
-    DcsSlot *dS = static_cast<DcsSlot *>(b->dPlanSlots);
-    DcsPlanSrc *dP = static_cast<DcsPlanSrc *>(b->dPlanSrcs);
-    const DcsPlanStream *dT = static_cast<const DcsPlanStream *>(b->dTable);
-    const uint32_t blocks = (b->nChunks + 3) / 4;
-    if (b->fpw == 16)
-        hipLaunchKernelGGL(dcsPlanKernel<16>, dim3(planBlocks), dim3(64), 0, b->stream, dT, nStreams, extraFrames, nJobs, dRecords, dInfos, dS, dP, flagWord, static_cast<uint32_t *>(b->hStage), b->planFpc);
-    else if (b->fpw == 8)
-        hipLaunchKernelGGL(dcsPlanKernel<8>, dim3(planBlocks), dim3(64), 0, b->stream, dT, nStreams, extraFrames, nJobs, dRecords, dInfos, dS, dP, flagWord, static_cast<uint32_t *>(b->hStage), b->planFpc);
-    else
-        hipLaunchKernelGGL(dcsPlanKernel<4>, dim3(planBlocks), dim3(64), 0, b->stream, dT, nStreams, extraFrames, nJobs, dRecords, dInfos, dS, dP, flagWord, static_cast<uint32_t *>(b->hStage), b->planFpc);
+    DcsSlot *dS = b->dPlanSlots.as<DcsSlot>();
+    DcsPlanSrc *dP = b->dPlanSrcs.as<DcsPlanSrc>();
+    withFpw(b->fpw, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL(dcsPlanKernel<W>, dim3(planBlocks), dim3(64), 0, b->stream, b->dTable.as<const DcsPlanStream>(), nStreams, extraFrames, nJobs,
+                           dRecords, dInfos, dS, dP, flagWord, b->hStage.as<uint32_t>(), b->planFpc);
+    });
     HIPCHK(ctx, hipGetLastError());
     if (between != nullptr)
         HIPCHK(ctx, hipEventRecord(between, b->stream));
-    if (b->fpw == 16)
-        hipLaunchKernelGGL(dcsPackKernel<16>, dim3(blocks), dim3(256), 0, b->stream, dS, b->nChunks, dP, dRecords, dBlob, blobLen, b->dPackages, b->imgDw);
-    else if (b->fpw == 8)
-        hipLaunchKernelGGL(dcsPackKernel<8>, dim3(blocks), dim3(256), 0, b->stream, dS, b->nChunks, dP, dRecords, dBlob, blobLen, b->dPackages, b->imgDw);
-    else
-        hipLaunchKernelGGL(dcsPackKernel<4>, dim3(blocks), dim3(256), 0, b->stream, dS, b->nChunks, dP, dRecords, dBlob, blobLen, b->dPackages, b->imgDw);
-    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, launchPack(b->fpw, b->stream, dS, b->nChunks, dP, dRecords, dBlob, blobLen, b->dPackages.as<uint8_t>(), b->imgDw));
     return DCS_OK;
 }
 
-// Plan AND pack on the device (dcsPlanKernel above): nothing of the list's index results is needed on the host.  `table`
+// The device planner's stream table (DcsPlanStream, 40 bytes a stream): what the host knows of every stream of a list of
+// whole streams without walking it -- where it lies in the list's blob, its layout, frame count, and the mixing parameters
+// of frame 0 and of every later frame -- and the list's totals.
+struct DcsPlanTable
+{
+    std::vector<DcsPlanStream> streams;
+    uint64_t nJobs = 0;                 // output frames
+    uint64_t payload = 0;               // bytes of the streams, headers included
+    bool all94 = true, has93aT1 = false;
+};
+// ... made from the streams as laid out in the list's blob (layoutStreams); also the first output frame of every stream (n + 1 entries)
+static DcsStatus planTableFor(const DcsStreamRef *streams, uint32_t n, uint32_t extraFrames, const DcsStreamLoc *locs, const uint64_t *firstRecord,
+                              uint64_t totalRec, DcsPlanTable &table, std::vector<uint32_t> &firstJob)
+{
+    table.streams.resize(n);
+    firstJob.resize(static_cast<size_t>(n) + 1);
+    uint64_t nJobs = 0, payload = 0;
+    bool all94 = true, has93a = false;
+    for (uint32_t k = 0 ; k < n ; ++k)
+    {
+        const DcsStreamRef &sr = streams[k];
+        const uint8_t *d = sr.data;
+        const uint32_t len = locs[k].len;
+        const uint32_t nFrames = (static_cast<uint32_t>(d[0]) << 8) | d[1];
+        const bool typeBit = (d[2] & 0x80) != 0;
+        const uint32_t h12 = (len > 3 ? d[3] : 0u) | (len > 4 ? d[4] : 0u);
+        const DcsOsVersion os = static_cast<DcsOsVersion>(sr.os);
+        DcsPlanStream &t = table.streams[k];
+        t = DcsPlanStream{};
+        t.hdrLen = (os == DCS_OS93A && typeBit) ? 1 : 16;
+        t.format = static_cast<uint8_t>(os == DCS_OS93A ? (typeBit ? DCS_FMT_93A_T1 : DCS_FMT_93_T0)
+                                      : os == DCS_OS93B ? (typeBit ? DCS_FMT_93B_T1 : DCS_FMT_93_T0)
+                                      : !typeBit ? DCS_FMT_94_T0 : (h12 & 0x80) == 0 ? DCS_FMT_94_T1_S0 : DCS_FMT_94_T1_S3);
+        t.xform = (os == DCS_OS93A || os == DCS_OS93B) ? DCS_XFORM_93 : DCS_XFORM_94;
+        all94 = all94 && t.xform == DCS_XFORM_94;
+        has93a = has93a || t.format == DCS_FMT_93A_T1;
+        t.streamOff = locs[k].off;
+        t.len = len;
+        t.firstRecord = static_cast<uint32_t>(firstRecord[k]);
+        t.firstJob = static_cast<uint32_t>(nJobs);
+        t.nFrames = nFrames;
+        uint16_t mm[2]; uint8_t vs[2];
+        const DcsStatus st = dcs_stream_params_from(os, sr.volume, sr.level, sr.channelVolume, 0x7FFF, 2, mm, vs);    // frame 0, and every later frame
+        if (st != DCS_OK)
+            return st;
+        t.mixMul0 = mm[0]; t.mixMulN = mm[1]; t.volShift0 = vs[0]; t.volShiftN = vs[1];
+        firstJob[k] = static_cast<uint32_t>(nJobs);
+        nJobs += nFrames + extraFrames;
+        payload += len;
+    }
+    firstJob[n] = static_cast<uint32_t>(nJobs);
+    table.nJobs = nJobs; table.payload = payload; table.all94 = all94; table.has93aT1 = has93a;
+    return nJobs > 0xFFFFFFFFull || totalRec > 0xFFFFFFFFull ? DCS_ERR_CAPACITY : DCS_OK;
+}
+
+// Plan AND pack on the device (dcsPlanKernel above): nothing of the list's index results is needed on the host.  `t`
 // describes the streams (host memory; copied), dRecords / dInfos are what the index kernel wrote or is still writing on
-// `stream`, dBlob the streams as uploaded.  The planner's flag word (DCS_PLAN_*) is copied to *flagOut (pinned memory of the
-// batch) behind the decode launch by batchQueuePlanFlag; a non-zero flag means the PCM of this batch is not to be used.
-static DcsStatus createBatchPlannedOnDevice(DcsCtx *ctx, const DcsPlanStream *table, uint32_t nStreams, uint32_t extraFrames, uint32_t nJobs,
-                                            uint32_t nRecords, bool all94, bool has93aT1, uint64_t payloadBytes, const DcsFrameIndex *dRecords,
-                                            const DcsStreamInfo *dInfos, const uint8_t *dBlob, uint64_t blobLen, hipStream_t stream, DcsBatch **out,
-                                            int framesPerChunk = 0)
+// `o.stream`, dBlob the streams as uploaded.  The planner stores its flag word (DCS_PLAN_*) into the batch's pinned staging
+// itself (batchPlanFlag); a non-zero flag means the PCM of this batch is not to be used.
+static DcsStatus createBatchPlannedOnDevice(DcsCtx *ctx, BatchOptions o, const DcsPlanTable &t, uint32_t extraFrames, uint32_t nRecords,
+                                            const DcsFrameIndex *dRecords, const DcsStreamInfo *dInfos, const uint8_t *dBlob, uint64_t blobLen,
+                                            DcsBatch **out, int framesPerChunk = 0)
 {
     *out = nullptr;
+    const uint32_t nStreams = static_cast<uint32_t>(t.streams.size()), nJobs = static_cast<uint32_t>(t.nJobs);
     if (nStreams == 0 || nJobs == 0)
         return DCS_ERR_INVALID_ARG;
-    DcsBatch *b = new (std::nothrow) DcsBatch;
+    // (the arithmetic plan always hands tails over, and it IS chain order: chunk c takes its tail from chunk c - 1)
+    o.handoff = true;
+    DcsBatch *b = newBatch(ctx, o, nJobs, nRecords, t.all94, t.has93aT1, o.xcdRanges && !ctx->noXcdRanges);
     if (b == nullptr)
         return DCS_ERR_NO_MEMORY;
-    b->ctx = ctx;
-    b->stream = stream ? stream : ctx->stream;
-    b->nJobs = nJobs; b->nSrcs = nRecords;
-    b->fpw = chooseFpw(ctx, nJobs, all94);
-    if (has93aT1)
-        b->flags |= DCS_BATCH_HAS_93A_T1;
-    static const bool xcdRanges = getenv("DCS_PIPE_XCD_RANGES") == nullptr || atoi(getenv("DCS_PIPE_XCD_RANGES")) != 0;
-    if (xcdRanges && !ctx->noXcdRanges)
-        b->flags |= DCS_BATCH_XCD_RANGES;       // (the arithmetic plan IS chain order: chunk c takes its tail from chunk c - 1)
-    const uint64_t pcm = static_cast<uint64_t>(nJobs) * DCS_FRAME_SAMPLES * 2;
-    b->algoBytes = payloadBytes + static_cast<uint64_t>(nRecords) * 56u + pcm;
-    b->abiBytes = payloadBytes + static_cast<uint64_t>(nRecords) * sizeof(DcsSrcDesc) + static_cast<uint64_t>(nJobs) * sizeof(DcsFrameJob) + pcm;
+    batchBytes(b, t.payload, 0);                // (the payload here is the streams' bytes, headers included)
     // (framesPerChunk: fewer frames per chunk than the kernel variant has slots -- the pipeline's second attempt for a list whose
     // frames are too large for a full chunk's bit pool; the context's diagnostic setting applies as well)
     {
@@ -1370,64 +1431,30 @@ static DcsStatus createBatchPlannedOnDevice(DcsCtx *ctx, const DcsPlanStream *ta
         b->planFpc = static_cast<uint32_t>(fpc >= 1 && fpc < b->fpw ? fpc : b->fpw);
     }
     b->nChunks = (nJobs + b->planFpc - 1) / b->planFpc;
-    b->imgDw = dcsPoolCapacity(b->fpw) | (all94 ? DCS_PKG_SPLIT4 : 0u);     // (a plan made on the device: the full image, dcs_common.h)
-    const size_t pkgBytes = static_cast<size_t>(b->nChunks) * dcsPkgStride(b->fpw, b->imgDw);
-    void *dTable = nullptr;
+    b->imgDw = dcsPoolCapacity(b->fpw) | (t.all94 ? DCS_PKG_SPLIT4 : 0u);   // (a plan made on the device: the full image, dcs_common.h)
     const size_t tableBytes = sizeof(DcsPlanStream) * nStreams;
-    DcsStatus st = [&]() -> DcsStatus {
+    const DcsStatus st = [&]() -> DcsStatus {
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        b->planSlotsCap = sizeof(DcsSlot) * static_cast<size_t>(b->nChunks) * static_cast<size_t>(b->fpw);
-        b->planSrcsCap = sizeof(DcsPlanSrc) * (nRecords ? nRecords : 1);
-        HIPCHK(ctx, cacheAlloc(ctx, false, &b->dPlanSlots, b->planSlotsCap));
-        HIPCHK(ctx, cacheAlloc(ctx, false, &b->dPlanSrcs, b->planSrcsCap));
-        // the stream table through pinned staging (a copy from pageable memory holds the calling thread), its device copy
-        // behind it in the same allocation is not needed: the table is small, it rides in the slots' buffer's neighbour
-        b->hStageCap = tableBytes + 16;
-        HIPCHK(ctx, cacheAlloc(ctx, true, &b->hStage, b->hStageCap));
-        memcpy(static_cast<uint8_t *>(b->hStage) + 16, table, tableBytes);
-        memset(b->hStage, 0, 16);
-        b->cap[2] = tableBytes;
-        HIPCHK(ctx, cacheAlloc(ctx, false, &dTable, tableBytes));
-        b->dTable = dTable;
-        HIPCHK(ctx, copyByKernel(b->stream, dTable, static_cast<uint8_t *>(b->hStage) + 16, tableBytes));
-        b->cap[9] = pkgBytes; HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dPackages), b->cap[9]));
-        // (PCM and error words in one allocation: one copy brings both down)
-        b->errJoined = true;
-        b->cap[4] = sizeof(int16_t) * DCS_FRAME_SAMPLES * nJobs + sizeof(uint32_t) * nJobs; b->cap[5] = 0;
-        HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dPcm), b->cap[4]));
-        b->dErr = reinterpret_cast<uint32_t *>(b->dPcm + static_cast<size_t>(DCS_FRAME_SAMPLES) * nJobs);
-        // (no tails kept: nothing reads them on this path, and a buffer from the recycling cache would carry another list's -- ADVICE r5)
-        b->cap[8] = sizeof(unsigned long long) * 16 * (b->nChunks + 1); HIPCHK(ctx, cacheAlloc(ctx, false, reinterpret_cast<void **>(&b->dHandoff), b->cap[8]));
-        {
-            const DcsStatus sq = queuePlanAndPack(b, nStreams, extraFrames, dRecords, dInfos, dBlob, blobLen, nullptr);
-            if (sq != DCS_OK)
-                return sq;
-        }
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipEventCreate(&b->ev0));
-        HIPCHK(ctx, hipEventCreate(&b->ev1));
-        HIPCHK(ctx, hipEventCreateWithFlags(&b->evDone, hipEventDisableTiming | (tlsBlockingWaits ? hipEventBlockingSync : 0u)));
-        return DCS_OK;
+        HIPCHK(ctx, b->dPlanSlots.alloc(ctx, false, sizeof(DcsSlot) * static_cast<size_t>(b->nChunks) * static_cast<size_t>(b->fpw)));
+        HIPCHK(ctx, b->dPlanSrcs.alloc(ctx, false, sizeof(DcsPlanSrc) * (nRecords ? nRecords : 1)));
+        // the stream table through pinned staging (a copy from pageable memory holds the calling thread), behind the 16 bytes
+        // that hold the planner's flag word
+        HIPCHK(ctx, b->hStage.alloc(ctx, true, tableBytes + 16));
+        memcpy(b->hStage.as<uint8_t>() + 16, t.streams.data(), tableBytes);
+        memset(b->hStage.as(), 0, 16);
+        HIPCHK(ctx, b->dTable.alloc(ctx, false, tableBytes));
+        HIPCHK(ctx, copyByKernel(b->stream, b->dTable.as(), b->hStage.as<uint8_t>() + 16, tableBytes));
+        HIPCHK(ctx, b->dPackages.alloc(ctx, false, static_cast<size_t>(b->nChunks) * dcsPkgStride(b->fpw, b->imgDw)));
+        const DcsStatus so = batchOutputs(b, false, true);
+        if (so != DCS_OK)
+            return so;
+        return queuePlanAndPack(b, nStreams, extraFrames, dRecords, dInfos, dBlob, blobLen, nullptr);
     }();
-    if (st != DCS_OK)
-    {
-        (void)streamWait(ctx, b->stream);
-        dcs_batch_destroy(b);
-        return st;
-    }
-    *out = b;
-    return DCS_OK;
+    return batchDone(b, st, out);
 }
 
-// queue the copy of the planner's flag word into the batch's pinned staging (behind whatever runs on the batch's stream);
-// read it with batchPlanFlag once the stream has been waited for
-static DcsStatus batchQueuePlanFlag(DcsBatch *b)
-{
-    // (nothing to queue since round 4: the planner stores a non-zero flag into the pinned word itself)
-    (void)b;
-    return DCS_OK;
-}
-static uint32_t batchPlanFlag(const DcsBatch *b) { return *static_cast<const volatile uint32_t *>(b->hStage); }
+// the planner's flag word of a batch planned on the device, once its stream has been waited for
+static uint32_t batchPlanFlag(const DcsBatch *b) { return *b->hStage.as<const volatile uint32_t>(); }
 
 // Diagnostic / test entry: the packages of `jobs` as the DEVICE packer lays them out (plan from source digests on the
 // host, pack kernel on the device), for comparison with dcs_pack_chunks, the host packer.  out = NULL to size.
@@ -1460,7 +1487,7 @@ extern "C" DcsStatus dcs_pack_chunks_device(DcsCtx *ctx, const DcsFrameJob *jobs
         return DCS_ERR_CAPACITY;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     void *dSlots = nullptr, *dPs = nullptr, *dRecs = nullptr, *dBlob = nullptr, *dPkg = nullptr;
-    const size_t blobAlloc = ((blobLen + 3) & ~size_t(3)) + 64;
+    const size_t blobAlloc = deviceBlobBytes(blobLen);
     DcsStatus st = [&]() -> DcsStatus {
         HIPCHK(ctx, hipMalloc(&dSlots, sizeof(DcsSlot) * slots.size()));
         HIPCHK(ctx, hipMalloc(&dPs, sizeof(DcsPlanSrc) * (nSrcs ? nSrcs : 1)));
@@ -1473,16 +1500,8 @@ extern "C" DcsStatus dcs_pack_chunks_device(DcsCtx *ctx, const DcsFrameJob *jobs
         HIPCHK(ctx, hipMemcpyAsync(dPs, ps.data(), sizeof(DcsPlanSrc) * nSrcs, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(dRecs, recs.data(), sizeof(DcsFrameIndex) * nSrcs, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(dBlob, blob, blobLen, hipMemcpyHostToDevice, ctx->stream));
-        const uint32_t blocks = (nChunks + 3) / 4;
-        const DcsSlot *dS = static_cast<const DcsSlot *>(dSlots);
-        const DcsPlanSrc *dP = static_cast<const DcsPlanSrc *>(dPs);
-        const DcsFrameIndex *dR = static_cast<const DcsFrameIndex *>(dRecs);
-        const uint8_t *dB = static_cast<const uint8_t *>(dBlob);
-        uint8_t *dO = static_cast<uint8_t *>(dPkg);
-        if (fpw == 16)     hipLaunchKernelGGL(dcsPackKernel<16>, dim3(blocks), dim3(256), 0, ctx->stream, dS, nChunks, dP, dR, dB, blobLen, dO, imgDw);
-        else if (fpw == 8) hipLaunchKernelGGL(dcsPackKernel<8>, dim3(blocks), dim3(256), 0, ctx->stream, dS, nChunks, dP, dR, dB, blobLen, dO, imgDw);
-        else               hipLaunchKernelGGL(dcsPackKernel<4>, dim3(blocks), dim3(256), 0, ctx->stream, dS, nChunks, dP, dR, dB, blobLen, dO, imgDw);
-        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, launchPack(fpw, ctx->stream, static_cast<const DcsSlot *>(dSlots), nChunks, static_cast<const DcsPlanSrc *>(dPs),
+                               static_cast<const DcsFrameIndex *>(dRecs), static_cast<const uint8_t *>(dBlob), blobLen, static_cast<uint8_t *>(dPkg), imgDw));
         HIPCHK(ctx, hipMemcpyAsync(out, dPkg, pkgBytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return DCS_OK;
@@ -1502,8 +1521,9 @@ extern "C" DcsStatus dcs_batch_create(DcsCtx *ctx,
 {
     if (ctx == nullptr)
         return DCS_ERR_INVALID_ARG;
-    struct Resident { bool old; Resident() : old(tlsResidentBatch) { tlsResidentBatch = true; } ~Resident() { tlsResidentBatch = old; } } resident;
-    return createBatch(ctx, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, nullptr, ctx->handoff, out);
+    BatchOptions o(ctx);
+    o.resident = true;
+    return createBatch(ctx, o, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, out);
 }
 
 template <int FPW>
@@ -1532,8 +1552,7 @@ static DcsStatus launchOnce(DcsBatch *b, hipStream_t stream)
     if (++b->epoch > DCS_EPOCH_MAX)
         b->epoch = 1;                   // (0 marks words no launch has written; after 2^31 launches of ONE batch the count starts over)
     const DcsKernelArgs args = kernelArgs(b);
-    hipError_t e;
-    e = (b->fpw == 16) ? launch<16>(args, stream, ctx->numCUs) : (b->fpw == 8) ? launch<8>(args, stream, ctx->numCUs) : launch<4>(args, stream, ctx->numCUs);
+    const hipError_t e = withFpw(b->fpw, [&](auto w) { return launch<decltype(w)::value>(args, stream, ctx->numCUs); });
     if (e != hipSuccess)
     {
         setError(ctx, std::string("kernel launch failed: ") + hipGetErrorString(e));
@@ -1661,11 +1680,11 @@ extern "C" DcsStatus dcs_batch_download(DcsBatch *b, int16_t *pcmOut, uint32_t *
     HIPCHK(ctx, streamWait(b->ctx, b->stream));
     b->settled = true;          // (the copies below are synchronous)
     if (pcmOut)
-        HIPCHK(ctx, hipMemcpy(pcmOut, b->dPcm, sizeof(int16_t) * DCS_FRAME_SAMPLES * b->nJobs, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(pcmOut, b->dPcm.as(), sizeof(int16_t) * DCS_FRAME_SAMPLES * b->nJobs, hipMemcpyDeviceToHost));
     if (errOut)
         HIPCHK(ctx, hipMemcpy(errOut, b->dErr, sizeof(uint32_t) * b->nJobs, hipMemcpyDeviceToHost));
     if (tailsOut && b->dTailsOut)
-        HIPCHK(ctx, hipMemcpy(tailsOut, b->dTailsOut, sizeof(int16_t) * 16 * b->nJobs, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(tailsOut, b->dTailsOut.as(), sizeof(int16_t) * 16 * b->nJobs, hipMemcpyDeviceToHost));
     return DCS_OK;
 }
 
@@ -1678,58 +1697,52 @@ extern "C" DcsStatus dcs_batch_download_view(DcsBatch *b, const int16_t **pcmOut
     DcsCtx *ctx = b->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t pcmBytes = sizeof(int16_t) * DCS_FRAME_SAMPLES * b->nJobs, errBytes = sizeof(uint32_t) * b->nJobs;
-    // (the error words lie behind the PCM on the device: mirror that in pinned memory and bring both down in one copy -- unless
-    // dcs_batch_download has given this batch separate host buffers before)
-    const bool joined = b->errJoined && (b->hPcm == nullptr
-                                         || b->hErr == reinterpret_cast<uint32_t *>(b->hPcm + static_cast<size_t>(DCS_FRAME_SAMPLES) * b->nJobs));
-    if (b->hPcm == nullptr)
+    // (the error words lie behind the PCM on the device: mirror that in pinned memory and bring both down in one copy)
+    const bool joined = b->errJoined;
+    if (!b->hPcm)
     {
-        b->hCap[0] = joined ? pcmBytes + errBytes : pcmBytes;
-        HIPCHK(ctx, cacheAlloc(ctx, true, reinterpret_cast<void **>(&b->hPcm), b->hCap[0]));
+        HIPCHK(ctx, b->hPcm.alloc(ctx, true, joined ? pcmBytes + errBytes : pcmBytes));
         if (joined)
-        {
-            b->hErr = reinterpret_cast<uint32_t *>(b->hPcm + static_cast<size_t>(DCS_FRAME_SAMPLES) * b->nJobs);
-            b->hCap[1] = 0;
-        }
+            b->hErr = reinterpret_cast<uint32_t *>(b->hPcm.as<uint8_t>() + pcmBytes);
     }
     if (b->hErr == nullptr && errOut != nullptr)
     {
-        b->hCap[1] = errBytes;
-        HIPCHK(ctx, cacheAlloc(ctx, true, reinterpret_cast<void **>(&b->hErr), errBytes));
+        HIPCHK(ctx, b->hErrOwn.alloc(ctx, true, errBytes));
+        b->hErr = b->hErrOwn.as<uint32_t>();
     }
     if (b->launched)
         HIPCHK(ctx, hipStreamWaitEvent(b->stream, b->evDone, 0));      // the copies follow the last launch, whatever stream it ran on
     const size_t firstBytes = joined ? pcmBytes + errBytes : pcmBytes;
     if (b->downByKernel)
     {
-        HIPCHK(ctx, copyByKernel(b->stream, b->hPcm, b->dPcm, firstBytes, b->downBlocks));
+        HIPCHK(ctx, copyByKernel(b->stream, b->hPcm.as(), b->dPcm.as(), firstBytes, b->downBlocks));
         if (errOut != nullptr && !joined)
             HIPCHK(ctx, copyByKernel(b->stream, b->hErr, b->dErr, errBytes, b->downBlocks));
     }
     else
     {
-        HIPCHK(ctx, hipMemcpyAsync(b->hPcm, b->dPcm, firstBytes, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(ctx, hipMemcpyAsync(b->hPcm.as(), b->dPcm.as(), firstBytes, hipMemcpyDeviceToHost, b->stream));
         if (errOut != nullptr && !joined)
             HIPCHK(ctx, hipMemcpyAsync(b->hErr, b->dErr, errBytes, hipMemcpyDeviceToHost, b->stream));
     }
     HIPCHK(ctx, streamWait(b->ctx, b->stream));
     b->settled = true;          // (uploads and pack kernels ran on b->stream before, the launches are behind evDone)
-    *pcmOut = b->hPcm;
+    *pcmOut = b->hPcm.as<int16_t>();
     if (errOut != nullptr)
         *errOut = b->hErr;
     return DCS_OK;
 }
 
-extern "C" void *dcs_batch_device_pcm(DcsBatch *b) { return b ? b->dPcm : nullptr; }
+extern "C" void *dcs_batch_device_pcm(DcsBatch *b) { return b ? b->dPcm.as() : nullptr; }
 
 #ifdef DCS_STAMPS
 // diagnostic builds only: copy the per-chunk phase stamps (16 x uint64 per chunk) to the host
 extern "C" int dcs_debug_stamps(DcsBatch *b, unsigned long long *out, uint32_t capChunks)
 {
-    if (b == nullptr || b->dDebug == nullptr) return -1;
+    if (b == nullptr || !b->dDebug) return -1;
     (void)streamWait(b->ctx, b->stream);
     const uint32_t n = b->nChunks < capChunks ? b->nChunks : capChunks;
-    (void)hipMemcpy(out, b->dDebug, sizeof(unsigned long long) * 16 * n, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(out, b->dDebug.as(), sizeof(unsigned long long) * 16 * n, hipMemcpyDeviceToHost);
     return static_cast<int>(n);
 }
 #endif
@@ -1745,7 +1758,8 @@ extern "C" uint32_t dcs_batch_num_jobs(const DcsBatch *b) { return b ? b->nJobs 
 // borrowed buffers, three events, three memsets, an upload, the launch and two synchronous downloads -- 80 us for ONE frame, when
 // the reference's whole pump takes 4 us a frame.  Here everything that can outlive a call does:
 //   * one pinned arena for what goes up (the external tails, the descriptors of multi-channel frames, the chunk packages) and one
-//     for what comes down (PCM, error words, every frame's tail), grown geometrically, never given back before the context goes;
+//     for what comes down (PCM, error words, every frame's tail), both first made for a look-ahead of 4 096 frames, replaced by
+//     one of the size a call needs (rounded up to 64 KiB) when that is more, never given back before the context goes;
 //   * small batches are not copied at all: the kernel reads its packages from the pinned arena and writes its PCM into the
 //     pinned arena over the link (a package is read once, 16 bytes per lane; the PCM of a few dozen frames is a few kilobytes),
 //     so a call is ONE launch and ONE wait.  Larger ones get one copy up, one copy down (PCM, error words and tails are one
@@ -1794,7 +1808,7 @@ static void liveDestroy(DcsCtx *ctx)
     ctx->live = nullptr;
 }
 
-// room for `bytes` in one of the live arenas (pinned or device); what it held is not kept
+// room for `bytes` in one of the live arenas (pinned or device), rounded up to 64 KiB; what it held is not kept
 static hipError_t liveRoom(uint8_t **buf, size_t *cap, size_t bytes, bool pinned, size_t first = 0)
 {
     if (bytes <= *cap)
@@ -1809,14 +1823,9 @@ static hipError_t liveRoom(uint8_t **buf, size_t *cap, size_t bytes, bool pinned
         *buf = nullptr;
         *cap = 0;
     }
-    const size_t want = std::max((bytes + 65535) & ~size_t(65535), *cap * 2);
+    const size_t want = (bytes + 65535) & ~size_t(65535);
     void *p = nullptr;
-    hipError_t e = pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
-    if (e != hipSuccess && want != ((bytes + 65535) & ~size_t(65535)))
-    {
-        (void)hipGetLastError();
-        e = pinned ? hipHostMalloc(&p, (bytes + 65535) & ~size_t(65535), hipHostMallocDefault) : hipMalloc(&p, (bytes + 65535) & ~size_t(65535));
-    }
+    const hipError_t e = pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
     if (e != hipSuccess)
         return e;
     *buf = static_cast<uint8_t *>(p);
@@ -1865,7 +1874,7 @@ static DcsStatus decodeLive(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, ui
     // the streams behind further sources: resident under the caller's name for the blob, else uploaded for this call
     if (multi)
     {
-        const size_t need = ((blobLen + 3) & ~size_t(3)) + 64;          // zero tail: the bit reader looks past the end
+        const size_t need = deviceBlobBytes(blobLen);
         const bool reuse = blobId != 0 && blobId == l->blobId && blobLen >= l->blobResident && need <= l->blobCap;
         if (!reuse)
         {
@@ -1875,7 +1884,7 @@ static DcsStatus decodeLive(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, ui
                 HIPCHK(ctx, hipMemsetAsync(l->dBlob, 0, l->blobCap, ctx->stream));
             }
             else if (l->blobDirty != 0)                                 // (what another blob left there must not show behind this one's end)
-                HIPCHK(ctx, hipMemsetAsync(l->dBlob, 0, std::min(l->blobCap, ((l->blobDirty + 3) & ~size_t(3)) + 64), ctx->stream));
+                HIPCHK(ctx, hipMemsetAsync(l->dBlob, 0, std::min(l->blobCap, deviceBlobBytes(l->blobDirty)), ctx->stream));
             l->blobDirty = 0;
             l->blobResident = 0;
             l->blobId = blobId;
@@ -1925,11 +1934,14 @@ static DcsStatus decodeLive(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, ui
         }
         if (nChunks + 1 > l->handoffChunks)
         {
+            // (the size is recorded once the words are there and cleared: a failed call leaves none, and the next one tries again)
+            const size_t chunks = std::max<size_t>(size_t(nChunks) + 1, std::max<size_t>(l->handoffChunks * 2, 1024));
             if (l->dHandoff) (void)hipFree(l->dHandoff);
             l->dHandoff = nullptr;
-            l->handoffChunks = std::max<size_t>(size_t(nChunks) + 1, std::max<size_t>(l->handoffChunks * 2, 1024));
-            HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&l->dHandoff), l->handoffChunks * 16 * sizeof(unsigned long long)));
-            HIPCHK(ctx, hipMemsetAsync(l->dHandoff, 0, l->handoffChunks * 16 * sizeof(unsigned long long), ctx->stream));
+            l->handoffChunks = 0;
+            HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&l->dHandoff), chunks * 16 * sizeof(unsigned long long)));
+            HIPCHK(ctx, hipMemsetAsync(l->dHandoff, 0, chunks * 16 * sizeof(unsigned long long), ctx->stream));
+            l->handoffChunks = chunks;
         }
         if (++l->epoch > DCS_EPOCH_MAX)
         {
@@ -1954,7 +1966,7 @@ static DcsStatus decodeLive(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, ui
         args.handoff = l->dHandoff;
         args.epoch = l->epoch;
         args.flags = batchFlags | (layout << DCS_BATCH_IMG_SHIFT);
-        const hipError_t e = fpw == 16 ? launch<16>(args, ctx->stream, ctx->numCUs) : fpw == 8 ? launch<8>(args, ctx->stream, ctx->numCUs) : launch<4>(args, ctx->stream, ctx->numCUs);
+        const hipError_t e = withFpw(fpw, [&](auto w) { return launch<decltype(w)::value>(args, ctx->stream, ctx->numCUs); });
         if (e != hipSuccess)
         {
             setError(ctx, std::string("kernel launch failed: ") + hipGetErrorString(e));
@@ -2016,9 +2028,10 @@ extern "C" DcsStatus dcs_decode_batch(DcsCtx *ctx,
     }
     // more than the live decoder takes: a batch object with buffers from the context's bounded cache, run once
     // a caller that asks for tailsOut gets the tail EVERY frame leaves (the sequencer resumes from any tick of a batch)
-    struct Tails { bool old; explicit Tails(bool all) : old(tlsKeepAllTails) { tlsKeepAllTails = all; } ~Tails() { tlsKeepAllTails = old; } } tails(tailsOut != nullptr);
+    BatchOptions o(ctx);
+    o.keepAllTails = tailsOut != nullptr;
     DcsBatch *b = nullptr;
-    DcsStatus st = createBatch(ctx, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, nullptr, ctx->handoff, &b);
+    DcsStatus st = createBatch(ctx, o, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, &b);
     if (st != DCS_OK)
         return st;
     st = dcs_batch_run(b, nullptr);
@@ -2211,18 +2224,18 @@ extern "C" DcsStatus dcs_ctx_link_rate(DcsCtx *ctx, float *gbpsOut)
         return DCS_ERR_INVALID_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t bytes = size_t(64) << 20;
-    void *d = nullptr, *h = nullptr;
+    CacheBuf d, h;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     DcsStatus st = [&]() -> DcsStatus {
-        HIPCHK(ctx, cacheAlloc(ctx, false, &d, bytes));
-        HIPCHK(ctx, cacheAlloc(ctx, true, &h, bytes));
+        HIPCHK(ctx, d.alloc(ctx, false, bytes));
+        HIPCHK(ctx, h.alloc(ctx, true, bytes));
         HIPCHK(ctx, hipEventCreate(&e0));
         HIPCHK(ctx, hipEventCreate(&e1));
-        HIPCHK(ctx, hipMemsetAsync(d, 0x5A, bytes, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));       // (first use of the path)
+        HIPCHK(ctx, hipMemsetAsync(d.as(), 0x5A, bytes, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h.as(), d.as(), bytes, hipMemcpyDeviceToHost, ctx->stream));       // (first use of the path)
         HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
         for (int i = 0 ; i < 5 ; ++i)
-            HIPCHK(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(h.as(), d.as(), bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
         HIPCHK(ctx, hipEventSynchronize(e1));
         float ms = 0;
@@ -2234,8 +2247,8 @@ extern "C" DcsStatus dcs_ctx_link_rate(DcsCtx *ctx, float *gbpsOut)
         (void)hipStreamSynchronize(ctx->stream);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (d) cacheFree(ctx, false, d, bytes);
-    if (h) cacheFree(ctx, true, h, bytes);
+    d.release();
+    h.release();
     return st;
 }
 
@@ -2251,10 +2264,10 @@ extern "C" DcsStatus dcs_ctx_call_floor(DcsCtx *ctx, uint32_t nFrames, int iters
         return DCS_ERR_INVALID_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t bytes = static_cast<size_t>(nFrames) * 516;
-    void *d = nullptr, *h = nullptr;
+    CacheBuf d, h;
     DcsStatus st = [&]() -> DcsStatus {
-        HIPCHK(ctx, cacheAlloc(ctx, false, &d, bytes));
-        HIPCHK(ctx, cacheAlloc(ctx, true, &h, bytes));
+        HIPCHK(ctx, d.alloc(ctx, false, bytes));
+        HIPCHK(ctx, h.alloc(ctx, true, bytes));
         std::vector<double> a, b;
         for (int i = 0 ; i < iters + 3 ; ++i)
         {
@@ -2263,7 +2276,7 @@ extern "C" DcsStatus dcs_ctx_call_floor(DcsCtx *ctx, uint32_t nFrames, int iters
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             const double t1 = hipchkNow();
             hipLaunchKernelGGL(dcsEmptyKernel, dim3(1), dim3(64), 0, ctx->stream, static_cast<uint32_t *>(nullptr));
-            HIPCHK(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(h.as(), d.as(), bytes, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             const double t2 = hipchkNow();
             if (i >= 3) { a.push_back(t1 - t0); b.push_back(t2 - t1); }
@@ -2274,8 +2287,8 @@ extern "C" DcsStatus dcs_ctx_call_floor(DcsCtx *ctx, uint32_t nFrames, int iters
         if (launchCopyWaitUs) *launchCopyWaitUs = static_cast<float>(b[b.size() / 2]);
         return DCS_OK;
     }();
-    if (d) cacheFree(ctx, false, d, bytes);
-    if (h) cacheFree(ctx, true, h, bytes);
+    d.release();
+    h.release();
     return st;
 }
 
@@ -2284,9 +2297,9 @@ extern "C" DcsStatus dcs_ctx_call_floor(DcsCtx *ctx, uint32_t nFrames, int iters
 #include "dcs_node.hip.h"
 
 // What the encoder's translation unit (dcs_encode.hip: compiled apart so that its floating-point contract applies to it
-// alone) needs of a context: its device, its stream, its error text and its buffer cache.
+// alone) needs of a context: its device, its stream, its error text and its buffer cache (CacheBuf, dcs_cache.h).
 int dcsCtxDevice(DcsCtx *ctx) { return ctx->device; }
 hipStream_t dcsCtxStream(DcsCtx *ctx) { return ctx->stream; }
 void dcsCtxSetError(DcsCtx *ctx, const char *text) { setError(ctx, text); }
-hipError_t dcsCtxAlloc(DcsCtx *ctx, void **out, size_t bytes) { return cacheAlloc(ctx, false, out, bytes); }
-void dcsCtxFree(DcsCtx *ctx, void *p, size_t bytes) { cacheFree(ctx, false, p, bytes); }
+hipError_t dcsCtxAlloc(DcsCtx *ctx, bool pinned, void **out, size_t bytes) { return cacheAlloc(ctx, pinned, out, bytes); }
+void dcsCtxFree(DcsCtx *ctx, bool pinned, void *p) { cacheFree(ctx, pinned, p); }

@@ -314,6 +314,56 @@ def test_batch_is_idempotent_and_resident(gpu_ctx):
     bt.close()
 
 
+def survey_bytes(srcs, n_jobs):
+    """SURVEY 8(d) restated for a batch description: (algorithmic, ABI) bytes of one launch.  Algorithmic: the compressed
+    payload (the sources' bits, rounded up to bytes), the header and U16 frame count of each distinct stream, 56 B per
+    source, 480 B of PCM per frame.  ABI: the payload, the descriptors as the ABI lays them out (160 B a source, 16 B a
+    job) and the PCM."""
+    payload = (int(srcs["idx"]["nBits"].astype(np.int64).sum()) + 7) // 8
+    headers = {}
+    for off, hdr_len in zip(srcs["streamOff"].tolist(), srcs["hdrLen"].tolist()):
+        headers.setdefault(off, 2 + hdr_len)
+    pcm = 480 * n_jobs
+    return payload + sum(headers.values()) + 56 * len(srcs) + pcm, payload + 160 * len(srcs) + 16 * n_jobs + pcm
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", [0x8D01, 0x8D02, 0x8D03])
+def test_batch_bytes_follow_survey_formula(gpu_ctx, seed):
+    """dcs_batch_algorithmic_bytes / dcs_batch_abi_bytes of a resident batch and the device path's algorithmicBytes equal
+    the SURVEY 8(d) formula exactly, for seeded lists of every layout (bench.py's roofline fraction divides by them)"""
+    rng = np.random.default_rng(seed)
+    streams = []
+    for i in range(int(rng.integers(6, 14))):
+        fmt = ALL_FORMATS[int(rng.integers(len(ALL_FORMATS)))]
+        # (no profile 4: its large frames overflow a chunk's bit pool, which the device path's planner does not plan around)
+        s = make_stream(fmt, int(rng.integers(1, 40)), seed=seed + i, profile=int(rng.choice([0, 1, 2, 3, 5])))
+        streams.append((os_for(fmt, i), s, 0xE0, 0x64))
+    extra = int(rng.integers(0, 3))
+    b = D.build_stream_batch(streams, extra_frames=extra)
+    n_jobs = len(b["jobs"])
+    # the sources once in stream order, once shuffled (a stream's frames no longer consecutive sources: its header still counts once)
+    perm = rng.permutation(len(b["srcs"]))
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(perm.size)
+    jobs = b["jobs"].copy()
+    has_src = jobs["nSrc"] != 0
+    jobs["firstSrc"][has_src] = inv[jobs["firstSrc"][has_src]]
+    for srcs, jb in ((b["srcs"], b["jobs"]), (b["srcs"][perm], jobs)):
+        bt = gpu_ctx.batch(b["blob"], srcs, jb)
+        assert (bt.algorithmic_bytes, bt.abi_bytes) == survey_bytes(srcs, n_jobs)
+        bt.close()
+    # the device path: the streams' bytes as laid out in its blob (at most the header and nFrames maximal frames: headers
+    # included, so no separate header term), 56 B per frame record, 480 B per output frame
+    n_rec = sum((s[0] << 8) | s[1] for _, s, _, _ in streams)
+    payload = sum(min(len(s), 2 + 16 + (((s[0] << 8) | s[1]) * 4480 + 7) // 8 + 8) for _, s, _, _ in streams)
+    path = gpu_ctx.device_path(streams, extra_frames=extra)
+    t = path.run(1)
+    assert t["planFlags"] == 0 and t["nFrames"] == n_jobs
+    assert t["algorithmicBytes"] == payload + 56 * n_rec + 480 * n_jobs
+    path.close()
+
+
 @pytest.mark.gpu
 def test_gpu_index_pass_equals_host_index_pass(gpu_ctx, oracle):
     """dcs_index_streams_gpu (one wavefront per stream) must return the host walker's records bit for bit --
