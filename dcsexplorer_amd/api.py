@@ -140,6 +140,7 @@ EXPORTS = [
     "dcs_node_create", "dcs_node_destroy", "dcs_node_submit", "dcs_node_collect", "dcs_node_num_devices", "dcs_node_device_info",
     "dcs_node_last_error", "dcs_node_cache_release", "dcs_device_numa_node",
     "dcs_encode_params_default", "dcs_encode_bound", "dcs_encode_header", "dcs_encode_streams",
+    "dcs_encode93_bound", "dcs_encode93_header", "dcs_encode93_streams",
 ]
 
 
@@ -413,6 +414,12 @@ def load_library():
     L.dcs_encode_header.argtypes = [vp, vp, vp, ctypes.POINTER(EncodeParams), i32, i32, vp, ctypes.POINTER(i32), vp]
     L.dcs_encode_streams.restype = i32
     L.dcs_encode_streams.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), vp, sz, vp, vp]
+    L.dcs_encode93_bound.restype = sz
+    L.dcs_encode93_bound.argtypes = [ctypes.c_uint64]
+    L.dcs_encode93_header.restype = i32
+    L.dcs_encode93_header.argtypes = [vp, vp, vp, ctypes.POINTER(EncodeParams), i32, vp, ctypes.POINTER(i32), vp]
+    L.dcs_encode93_streams.restype = i32
+    L.dcs_encode93_streams.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), vp, sz, vp, vp]
     L.dcs_device_numa_node.restype = ctypes.c_int
     L.dcs_device_numa_node.argtypes = [ctypes.c_int]
     L.dcs_host_threads.restype = ctypes.c_int
@@ -601,6 +608,38 @@ def encode_header(power_sum, lo, hi, fmt_type, fmt_sub_type, **params):
     hdr, bits, keep = np.zeros(16, np.uint8), np.zeros(16, np.int32), ctypes.c_int32()
     _check(load_library().dcs_encode_header(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), ctypes.byref(p), int(fmt_type), int(fmt_sub_type),
                                             _ptr(hdr), ctypes.byref(keep), _ptr(bits)))
+    return hdr, keep.value, bits
+
+
+# OS93: the format version per OS, and the layouts encode93_streams can be asked for (streamFormatType; None = wildcard)
+_ENCODE93_VERSION = {OS93A: 0x9301, OS93B: 0x9302}
+_ENCODE93_FMT = {None: -1, FMT_93_T0: 0, FMT_93B_T1: 1, FMT_93A_T1: 1}
+
+
+def encode93_params(os_=OS93B, fmt=None, **params):
+    """an EncodeParams for the OS93 encoder: the reference's defaults, formatVersion 0x9301 (OS93A) or 0x9302 (OS93B), the
+    layout `fmt` (None = wildcard, FMT_93_T0, FMT_93B_T1 with OS93B, FMT_93A_T1 with OS93A) and CompressionParams by name"""
+    if os_ not in _ENCODE93_VERSION:
+        raise ValueError("no OS93 encoder for OS %r" % (os_,))
+    if fmt not in _ENCODE93_FMT or (fmt == FMT_93B_T1 and os_ != OS93B) or (fmt == FMT_93A_T1 and os_ != OS93A):
+        raise ValueError("no OS93 layout %r for OS %r" % (fmt, os_))
+    return encode_params(None, **dict(dict(formatVersion=_ENCODE93_VERSION[os_], streamFormatType=_ENCODE93_FMT[fmt],
+                                           streamFormatSubType=-1), **params))
+
+
+def encode93_bound(n_samples):
+    """dcs_encode93_bound: the largest OS93 stream n_samples samples can encode to (0 = not encodable)"""
+    return int(load_library().dcs_encode93_bound(int(n_samples)))
+
+
+def encode93_header(power_sum, lo, hi, fmt_type, os_=OS93B, **params):
+    """dcs_encode93_header -> (16 header bytes, bandsToKeep, bitsPerBand[16])"""
+    a = [np.ascontiguousarray(x, dtype=np.float32) for x in (power_sum, lo, hi)]
+    assert all(x.shape == (16,) for x in a)
+    p = encode93_params(os_, **params)
+    hdr, bits, keep = np.zeros(16, np.uint8), np.zeros(16, np.int32), ctypes.c_int32()
+    _check(load_library().dcs_encode93_header(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), ctypes.byref(p), int(fmt_type), _ptr(hdr),
+                                              ctypes.byref(keep), _ptr(bits)))
     return hdr, keep.value, bits
 
 
@@ -885,6 +924,21 @@ class Context:
         cap = sum(encode_bound(offs[i + 1] - offs[i]) for i in range(n))
         out = np.zeros(max(cap, 1), np.uint8)
         _check(self.L.dcs_encode_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info
+
+    def encode93_streams(self, pcm_list, os_=OS93B, fmt=None, **params):
+        """dcs_encode93_streams: PCM at 31 250 Hz (as encode_streams) -> OS93 streams, byte for byte the reference DCSEncoder's
+        with formatVersion 0x9301 (os_=OS93A) or 0x9302 (OS93B).  fmt: None = the reference's wildcard, FMT_93_T0, FMT_93B_T1
+        (OS93B only) or FMT_93A_T1 (OS93A only; the library refuses it, as the reference does).  Returns (list of bytes,
+        ENCODE_INFO_DTYPE array)."""
+        p = encode93_params(os_, fmt, **params)
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        out_offs = np.zeros(n + 1, np.uint64)
+        info = np.zeros(n, ENCODE_INFO_DTYPE)
+        cap = sum(encode93_bound(offs[i + 1] - offs[i]) for i in range(n))
+        out = np.zeros(max(cap, 1), np.uint8)
+        _check(self.L.dcs_encode93_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info
 
     def extract_streams(self, romset, volume=255, extra_frames=2):

@@ -1,6 +1,7 @@
-// dcs_encode.hip -- the 1994+ DCS encoder on the GPU: PCM at 31 250 Hz in, streams byte-identical to the reference's
+// dcs_encode.hip -- the DCS encoder on the GPU: PCM at 31 250 Hz in, streams byte-identical to the reference's
 // DCSEncoder out (DCSEncoder.cpp: TransformFrame :1001-1069, DFTAlgorithmOrig :1218-1358, DualFFT :1360-1500,
-// Frame::Frame :2535-2571, CloseStream :717-850, CompressStream :859-960, CompressFrame94 :1623-2050, BitWriter :2573-2704).
+// Frame::Frame :2535-2571, CloseStream :717-850, CompressStream :859-960, CompressFrame94 :1623-2050, CompressFrame93b
+// :2053-2470, BitWriter :2573-2704), for the 1994+ format and for OS93 (0x9301 / 0x9302).
 //
 // A translation unit of its own because of the floating-point contract below: the reference is plain x86-64 code that
 // rounds every multiply and add separately, and byte-exact streams need the same here, in device AND host code.  The
@@ -16,6 +17,14 @@
 //   E4 encChainKernel     one lane per (stream, layout, band): the walk over frames through those per-frame choices
 //   E5 encBitsKernel / encSizeKernel / encHeadKernel / encPackKernel: bits per band and frame, stream sizes, the winner,
 //                         frame bit offsets, and the bits themselves OR-ed into a zeroed buffer of big-endian words
+//
+// OS93 shares E1, E2 and the E5 size / head / swap steps (with the OS93 tables: 16 bands of 16 for the statistics, band
+// norms 1.0, the layouts' own counts in the rate model) and replaces E3-E5a and the pack:
+//   O3 enc93SearchKernel  one thread per (frame, band, layout): the scaled integers, the sub-type 0 search, and what the
+//                         band's delta codes need that does not depend on the previous band (Enc93Rec)
+//   O4 enc93WalkKernel    CompressFrame93b's band loop: Type 0 one lane per frame (no state crosses frames), Type 1 one lane
+//                         per stream, frame after frame (the band-type codes carried from frame to frame)
+//   O5 enc93PackKernel    one lane per (frame, band): the band's flag and type bits, then its samples
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -36,11 +45,14 @@ void dcsCtxSetError(DcsCtx *ctx, const char *text);
 namespace {
 
 // Everything the encoder looks up, in one block that is built on the host (from dcs_tables.h and dcs_enc_tables.h) and
-// copied to the device per call.
+// copied to the device per call.  One instance per format family: count / first / bandNorm are the statistics' bands
+// (Frame::Frame, CloseStream), shareCount[type] the bands the rate model weighs (CompressStream :866-868).
 struct EncTabs
 {
     float window[16], twiddle[128], fft[896], bandNorm[16];
     int32_t share[16], count[16], first[16], scale[64];
+    int32_t os93;                      // OS93: no Type-1 scale adjust, no sub-type bits in the header
+    int32_t shareCount[2][16];
     uint8_t preAdj[2][16];             // sub-type 0, sub-type 3
     uint8_t xw[3][16], xa[3][16];      // Type 1 band-type code -> bit width / scale adjust, for bands 0-2, 3-5, 6-15
     uint32_t hdrCode[31];              // frame-header band-type delta codes, index delta + 16
@@ -49,24 +61,29 @@ struct EncTabs
     uint8_t smpLen[7][64];
     uint16_t dzCode[7];                // the codebooks' two-zeros code
     uint8_t dzLen[7];
+    uint32_t btCode[2][32];            // OS93 Type 1 band-type delta codes, [Invert][delta + 16] (Keep: -15..14, Invert: -16..15)
+    uint8_t btLen[2][32];
 };
 
 float fromBits(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
 
-EncTabs buildTabs()
+EncTabs buildTabs(bool os93)
 {
     EncTabs t;
     memset(&t, 0, sizeof(t));
+    t.os93 = os93;
     for (int i = 0 ; i < 16 ; ++i) t.window[i] = fromBits(kEncWindowBits[i]);
     for (int i = 0 ; i < 128 ; ++i) t.twiddle[i] = fromBits(kEncTwiddleBits[i]);
     for (int i = 0 ; i < 896 ; ++i) t.fft[i] = fromBits(kEncFftBits[i]);
     for (int b = 0, first = 0 ; b < 16 ; ++b)
     {
-        t.bandNorm[b] = fromBits(kEncBandNormBits[b]);
+        t.bandNorm[b] = os93 ? 1.0f : fromBits(kEncBandNormBits[b]);
         t.share[b] = kEncBandShare[b];
-        t.count[b] = kBandCount94[b];
+        t.count[b] = os93 ? 16 : kBandCount94[b];
         t.first[b] = first;
-        first += kBandCount94[b];
+        first += t.count[b];
+        t.shareCount[0][b] = t.count[b];
+        t.shareCount[1][b] = os93 && b == 0 ? 15 : t.count[b];       // OS93b Type 1: 15 samples in band 0
     }
     // the scaling factors are the decoder's mantissas at the code's octave (tools/extract_enc_tables.py checks this equal
     // to the reference's table)
@@ -88,12 +105,21 @@ EncTabs buildTabs()
             if (v.val & 0x80) { t.dzCode[w] = static_cast<uint16_t>(v.code); t.dzLen[w] = v.len; }
             else { t.smpCode[w][v.val] = static_cast<uint16_t>(v.code); t.smpLen[w][v.val] = v.len; }
         }
+    // the decoder's leaf: < 0x1E keeps the band sub-type (delta = leaf - 0x0F), else inverts it (delta = leaf - 0x2E)
+    for (const DcsVlc &v : kVlc93BandType)
+    {
+        const int inv = v.val >= 0x1E ? 1 : 0;
+        const int d = v.val - (inv ? 0x2E : 0x0F);
+        t.btCode[inv][d + 16] = v.code;
+        t.btLen[inv][d + 16] = v.len;
+    }
     return t;
 }
 
-const EncTabs &encTabs() { static const EncTabs t = buildTabs(); return t; }
+const EncTabs &encTabs() { static const EncTabs t = buildTabs(false); return t; }
+const EncTabs &encTabs93() { static const EncTabs t = buildTabs(true); return t; }
 
-// CloseStream's band cutoff and CompressStream's header (the rate model), for one layout.  The reference computes
+// CloseStream's band cutoff and CompressStream's header (the rate model), for one layout of either family.  The reference computes
 // 1 << bitsPerBand[band] with counts above 31 at its default settings (few bands kept); its x86 build masks the count,
 // and that is the rule here, written out.
 __host__ __device__ void encHeader(const EncTabs &T, const float *ps, const float *lo, const float *hi, float cutoff, int rate,
@@ -120,7 +146,7 @@ __host__ __device__ void encHeader(const EncTabs &T, const float *ps, const floa
     const float bitsPerFrame = static_cast<float>(rate) / framesPerSecond;
     float shareNorm = 0.0f;
     for (int i = 0 ; i < keep ; ++i)
-        shareNorm += static_cast<float>(T.share[i] * T.count[i]);
+        shareNorm += static_cast<float>(T.share[i] * T.shareCount[typ][i]);
     for (int b = 0 ; b < 16 ; ++b) { hdr[b] = 0xFF; bits[b] = 0; }
     for (int b = 0 ; b < keep ; ++b)
     {
@@ -137,7 +163,7 @@ __host__ __device__ void encHeader(const EncTabs &T, const float *ps, const floa
             if (T.scale[j] < target) code = j;
             else break;
         }
-        if (typ == 1)
+        if (typ == 1 && !T.os93)
         {
             const int adjust = (b < 3 ? 0x0d : 0x17) + (sub == 0 ? 1 : 3);
             code = code > adjust ? code - adjust : 0;
@@ -145,8 +171,11 @@ __host__ __device__ void encHeader(const EncTabs &T, const float *ps, const floa
         hdr[b] = static_cast<uint8_t>(code);
     }
     if (typ != 0) hdr[0] |= 0x80;
-    hdr[1] |= static_cast<uint8_t>((sub & 2) << 6);
-    hdr[2] |= static_cast<uint8_t>((sub & 1) << 7);
+    if (!T.os93)
+    {
+        hdr[1] |= static_cast<uint8_t>((sub & 2) << 6);
+        hdr[2] |= static_cast<uint8_t>((sub & 1) << 7);
+    }
     *keepOut = keep;
 }
 
@@ -158,6 +187,32 @@ __device__ inline void encInterpret(const EncTabs &T, int typ, int band, int cod
     const int k = band < 3 ? 0 : band < 6 ? 1 : 2;
     *w = T.xw[k][code];
     *sc = hscale + T.xa[k][code] + (band < 3 ? pre : 0);
+}
+
+// FindBestResult over codes 1..15 and over 1..14: the narrowest passing width, then the smallest error among the codes of
+// that width (of all codes when none passes), the first on a tie -> best | bestWithout15 << 4
+__device__ inline uint8_t encPick(const float *err, const int *width, const bool *elig, const bool *pass)
+{
+    int best[2];
+#pragma unroll
+    for (int set = 0 ; set < 2 ; ++set)
+    {
+        const int last = set == 0 ? 15 : 14;
+        int narrow = -1;
+        for (int c = 1 ; c <= last ; ++c)
+            if (elig[c - 1] && pass[c - 1] && (narrow == -1 || width[c - 1] < narrow))
+                narrow = width[c - 1];
+        float minErr = -1.0f;
+        int b = 0;
+        for (int c = 1 ; c <= last ; ++c)
+            if (elig[c - 1] && (narrow == -1 || width[c - 1] == narrow) && (minErr < 0 || err[c - 1] < minErr))
+            {
+                b = c;
+                minErr = err[c - 1];
+            }
+        best[set] = b;
+    }
+    return static_cast<uint8_t>(best[0] | (best[1] << 4));
 }
 
 // FindBestBandEncoding + FindBestResult (:1502-1621) over codes 1..15 at one pre-adjust; returns best | bestWithout15 << 4.
@@ -194,26 +249,7 @@ __device__ uint8_t encSearch(const EncTabs &T, const float *smp, int n, int typ,
         err[c - 1] = sum;
         pass[c - 1] = sum <= errMax;
     }
-    int best[2];
-#pragma unroll
-    for (int set = 0 ; set < 2 ; ++set)
-    {
-        const int last = set == 0 ? 15 : 14;
-        int narrow = -1;
-        for (int c = 1 ; c <= last ; ++c)
-            if (elig[c - 1] && pass[c - 1] && (narrow == -1 || width[c - 1] < narrow))
-                narrow = width[c - 1];
-        float minErr = -1.0f;
-        int b = 0;
-        for (int c = 1 ; c <= last ; ++c)
-            if (elig[c - 1] && (narrow == -1 || width[c - 1] == narrow) && (minErr < 0 || err[c - 1] < minErr))
-            {
-                b = c;
-                minErr = err[c - 1];
-            }
-        best[set] = b;
-    }
-    return static_cast<uint8_t>(best[0] | (best[1] << 4));
+    return encPick(err, width, elig, pass);
 }
 
 // MSB-first bits into big-endian words (byte-swapped at the end); frames and streams share boundary words, hence the OR
@@ -710,15 +746,313 @@ __global__ __launch_bounds__(256) void encSwapKernel(uint32_t *W, size_t n)
         W[i] = __builtin_bswap32(W[i]);
 }
 
-bool paramsValid(const DcsEncodeParams *p)
+// ---------------------------------------------------------------------------------------------------- OS93 (CompressFrame93b)
+
+// a band of an OS93 layout: 16 bands of 16 samples over f[0..255]; Type 1 has 15 in band 0 and ends at f[254] (:2144)
+__device__ inline void enc93Band(int typ, int band, int *first, int *n)
 {
-    return p != nullptr && p->formatVersion == 0x9400 && p->streamFormatType >= -1 && p->streamFormatType <= 1
-        && (p->streamFormatSubType == -1 || p->streamFormatSubType == 0 || p->streamFormatSubType == 3)
-        && p->targetBitRate >= 1 && p->targetBitRate <= 100000000 && isfinite(p->powerBandCutoff)
-        && isfinite(p->minimumDynamicRange) && isfinite(p->maximumQuantizationError);
+    *n = typ == 1 && band == 0 ? 15 : 16;
+    *first = band * 16 - (typ == 1 && band > 0 ? 1 : 0);
+}
+
+// what the band loop needs of one (frame, band, layout) that does not depend on the bands before it: the sub-type 0
+// code (pick = best | best without 15 << 4), the bit lengths of max |buf1[i]| for i >= 1 and of max |buf2[i]| for i >= 2
+// (<< 8, << 16), and the scaled integers the incoming prvSample / prvDelta meet: the first two and the last sample and delta
+struct Enc93Rec { int32_t s0, s1, sLast, dLast; uint32_t pick; };
+
+// the band loop's output per (layout, frame, band): the flag and type-code bits (value, length), the incoming prvSample /
+// prvDelta, and meta = flag/type length | code << 8 | band sub-type << 12 | sample bits << 16
+struct Enc93Band { uint32_t hdr; int32_t P, D; uint32_t meta; };
+
+__device__ inline uint32_t bitLen(uint32_t x) { return x ? 32u - static_cast<uint32_t>(__builtin_clz(x)) : 0u; }
+
+__device__ inline uint32_t absI(int x) { return x < 0 ? 0u - static_cast<uint32_t>(x) : static_cast<uint32_t>(x); }
+
+// O3: four frames per block, one thread per (frame, band, layout)
+__global__ __launch_bounds__(128) void enc93SearchKernel(const EncTabs *__restrict__ Tp, const float *__restrict__ spec,
+    const uint32_t *__restrict__ frameStream, const uint8_t *__restrict__ hdr, const int32_t *__restrict__ keepArr,
+    uint32_t vmask, uint32_t F, float maxQE, Enc93Rec *__restrict__ rec)
+{
+    const EncTabs &T = *Tp;
+    __shared__ float smp[4][256];
+    const int t = threadIdx.x;
+    for (int q = 0 ; q < 8 ; ++q)
+    {
+        const int idx = t + 128 * q;
+        const uint32_t ff = blockIdx.x * 4 + (idx >> 8);
+        smp[idx >> 8][idx & 255] = ff < F ? spec[static_cast<size_t>(ff) * 256 + (idx & 255)] : 0.0f;
+    }
+    __syncthreads();
+    const uint32_t f = blockIdx.x * 4 + (t >> 5);
+    const int v = (t >> 4) & 1, band = t & 15;
+    if (f >= F || !((vmask >> v) & 1))
+        return;
+    const uint32_t si = frameStream[f];
+    if (band >= keepArr[si])
+        return;
+    int first, n;
+    enc93Band(v, band, &first, &n);
+    const float *x = smp[t >> 5] + first;
+    const float scaleFactor = static_cast<float>(T.scale[hdr[(static_cast<size_t>(si) * 3 + v) * 16 + band] & 0x3f]);
+    // FindBestBandEncoding: every code shares the band's scale, so each sample is scaled once; each code's error sum
+    // stays serial in sample order
+    float err[15];
+    int width[15];
+    bool elig[15], pass[15];
+#pragma unroll
+    for (int c = 1 ; c <= 15 ; ++c)
+    {
+        err[c - 1] = 0.0f;
+        width[c - 1] = c + (v == 0 ? 1 : 0);
+        elig[c - 1] = true;
+    }
+    int s0 = 0, s1 = 0, prv = 0, prvD = 0;
+    uint32_t m1 = 0, m2 = 0;
+    for (int i = 0 ; i < n ; ++i)
+    {
+        const float orig = x[i];
+        const int s = static_cast<int>(roundf(orig * 32768.0f / scaleFactor));
+#pragma unroll
+        for (int c = 1 ; c <= 15 ; ++c)
+        {
+            const int w = width[c - 1];
+            const int refVal = 1 << (w - 1);
+            const int stored = (s + refVal) & (0xFFFF >> (16 - w));
+            const float reconstructed = (static_cast<float>(stored - refVal) * scaleFactor) / 32768.0f;
+            const float q = reconstructed - orig;
+            err[c - 1] += q * q;
+        }
+        if (i == 0) s0 = s;
+        if (i == 1) s1 = s;
+        if (i >= 1)
+        {
+            const int d = s - prv;
+            m1 = max(m1, absI(d));
+            if (i >= 2) m2 = max(m2, absI(d - prvD));
+            prvD = d;
+        }
+        prv = s;
+    }
+    const float errMax = (maxQE * maxQE) * static_cast<float>(n);
+#pragma unroll
+    for (int c = 0 ; c < 15 ; ++c)
+        pass[c] = err[c] <= errMax;
+    rec[(static_cast<size_t>(v) * F + f) * 16 + band] = Enc93Rec{ s0, s1, prv, prvD, encPick(err, width, elig, pass) | (bitLen(m1) << 8) | (bitLen(m2) << 16) };
+}
+
+// GetDeltaBandCode from the bit length of max |delta|: bit width = length + 1, code = width - 1 in Type 0, = width in Type 1
+__device__ inline int enc93DeltaCode(int typ, uint32_t len) { return len == 0 ? 0 : static_cast<int>(len) + typ; }
+
+// one frame of CompressFrame93b's band loop (:2196-2466); btc = the band-type codes carried from frame to frame (Type 1),
+// btCode / btLen = EncTabs' Keep / Invert codebooks, copied to LDS (a global load per band would put a memory latency on
+// every step of the Type-1 walk)
+template <int TYP>
+__device__ inline uint32_t enc93Frame(const uint32_t (*btCode)[32], const uint8_t (*btLen)[32], int keep, const Enc93Rec (&r)[16],
+                                      int (&btc)[16], Enc93Band *out)
+{
+    int lastCode = -1, lastSub = TYP == 1 ? 0 : 2, P = 0, D = 0;
+    uint32_t bits = 0;
+#pragma unroll
+    for (int b = 0 ; b < 16 ; ++b)
+    {
+        if (b >= keep)
+            continue;                           // (not break: the loop stays fully unrolled, r[] and btc[] in registers)
+        const Enc93Rec &x = r[b];
+        const int old = TYP == 1 ? btc[b] : 0;
+        // the sub-type 0 search leaves out code 15 when it is out of the Keep codebook's reach (delta > 14)
+        const int c0 = (TYP == 1 && lastSub == 0 && old == 0) ? static_cast<int>((x.pick >> 4) & 15) : static_cast<int>(x.pick & 15);
+        const int c1 = enc93DeltaCode(TYP, max(bitLen(absI(x.s0 - P)), (x.pick >> 8) & 0xFF));
+        int code = c0, sub = 0;
+        // a sub-type 1 candidate the chosen codebook cannot express is not eligible (Keep has no +15 code)
+        if ((c1 < code || (c1 == code && lastSub == 1)) && !(TYP == 1 && lastSub == 1 && c1 - old > 14))
+        {
+            code = c1;
+            sub = 1;
+        }
+        if (TYP == 0)
+        {
+            const int c2 = enc93DeltaCode(0, max(max(bitLen(absI(x.s0 - P - D)), bitLen(absI(x.s1 - 2 * x.s0 + P))), x.pick >> 16));
+            if (c2 < code)
+            {
+                code = c2;
+                sub = 2;
+            }
+        }
+        uint32_t hv, hl, sb = 0;
+        const int inP = P, inD = D;
+        if (lastCode == 0 && code == 0 && lastSub == sub)
+        {
+            hv = 1;                             // repeat the zero band; prvSample / prvDelta follow the scaled samples
+            hl = 1;
+            P = x.sLast;
+            D = x.dLast;
+        }
+        else
+        {
+            if (TYP == 0)
+            {
+                const bool keepSub = sub == lastSub;
+                hv = keepSub ? static_cast<uint32_t>(code) : (2u | (sub == (lastSub + 1) % 3 ? 1u : 0u)) << 4 | static_cast<uint32_t>(code);
+                hl = keepSub ? 5 : 6;
+            }
+            else
+            {
+                const int inv = sub != lastSub ? 1 : 0;
+                hv = btCode[inv][code - old + 16];
+                hl = btLen[inv][code - old + 16];
+                btc[b] = code;
+            }
+            hl += lastCode == 0 ? 1 : 0;          // the 0 bit: not a repeat
+            if (code == 0)
+            {
+                if (sub == 0) { P = 0; D = 0; }
+                else if (sub == 1) D = 0;
+            }
+            else
+            {
+                sb = static_cast<uint32_t>((b == 0 && TYP == 1 ? 15 : 16) * (code + (TYP == 0 ? 1 : 0)));
+                P = x.sLast;
+                D = x.dLast;
+            }
+        }
+        out[b] = Enc93Band{ hv, inP, inD, hl | static_cast<uint32_t>(code) << 8 | static_cast<uint32_t>(sub) << 12 | sb << 16 };
+        bits += hl + sb;
+        lastCode = code;
+        lastSub = sub;
+    }
+    return bits;
+}
+
+template <int TYP>
+__device__ inline void enc93Load(const Enc93Rec *__restrict__ rec, size_t row, int keep, Enc93Rec (&r)[16])
+{
+#pragma unroll
+    for (int b = 0 ; b < 16 ; ++b)
+        if (b < keep)
+            r[b] = rec[row + b];
+}
+
+// O4: Type 0 (TYP 0): one lane per frame.  Type 1: one lane per stream, frame after frame, the next frame's records loaded
+// while the current one is walked.  Writes each band's Enc93Band and each frame's bit count.
+template <int TYP>
+__global__ __launch_bounds__(64) void enc93WalkKernel(const EncTabs *__restrict__ Tp, const EncStream *__restrict__ streams,
+    const uint32_t *__restrict__ frameStream, const int32_t *__restrict__ keepArr, uint32_t F, uint32_t nUnits,
+    const Enc93Rec *__restrict__ rec, Enc93Band *__restrict__ out, uint32_t *__restrict__ frameBits)
+{
+    __shared__ uint32_t btCode[2][32];
+    __shared__ uint8_t btLen[2][32];
+    btCode[threadIdx.x >> 5][threadIdx.x & 31] = Tp->btCode[threadIdx.x >> 5][threadIdx.x & 31];
+    btLen[threadIdx.x >> 5][threadIdx.x & 31] = Tp->btLen[threadIdx.x >> 5][threadIdx.x & 31];
+    __syncthreads();
+    const uint32_t u = blockIdx.x * 64 + threadIdx.x;
+    if (u >= nUnits)
+        return;
+    Enc93Rec r[16];
+    int btc[16];
+#pragma unroll
+    for (int b = 0 ; b < 16 ; ++b)
+        btc[b] = 0;
+    if (TYP == 0)
+    {
+        const int keep = keepArr[frameStream[u]];
+        enc93Load<TYP>(rec, static_cast<size_t>(u) * 16, keep, r);
+        frameBits[u] = enc93Frame<TYP>(btCode, btLen, keep, r, btc, out + static_cast<size_t>(u) * 16);
+        return;
+    }
+    const EncStream s = streams[u];
+    const int keep = keepArr[u];
+    const size_t base = static_cast<size_t>(F) * 16;          // layout 1's rows
+    enc93Load<TYP>(rec, base + static_cast<size_t>(s.firstFrame) * 16, keep, r);
+    for (uint32_t j = 0 ; j < s.nFrames ; ++j)
+    {
+        const uint32_t f = s.firstFrame + j;
+        Enc93Rec nx[16];
+        enc93Load<TYP>(rec, base + static_cast<size_t>(j + 1 < s.nFrames ? f + 1 : f) * 16, keep, nx);
+        frameBits[F + f] = enc93Frame<TYP>(btCode, btLen, keep, r, btc, out + base + static_cast<size_t>(f) * 16);
+#pragma unroll
+        for (int b = 0 ; b < 16 ; ++b)
+            r[b] = nx[b];
+    }
+}
+
+// O5: four frames per block, one lane per band: the winner's flag and type bits, then the samples of its band sub-type
+__global__ __launch_bounds__(64) void enc93PackKernel(const EncTabs *__restrict__ Tp, const float *__restrict__ spec,
+    const uint32_t *__restrict__ frameStream, const uint8_t *__restrict__ hdr, const int32_t *__restrict__ keepArr,
+    const int32_t *__restrict__ win, uint32_t F, const Enc93Band *__restrict__ bands, const uint32_t *__restrict__ frameOff,
+    const uint64_t *__restrict__ outOff, uint32_t *__restrict__ W)
+{
+    const EncTabs &T = *Tp;
+    __shared__ float smp[4][256];
+    const int l = threadIdx.x;
+    for (int q = 0 ; q < 16 ; ++q)
+    {
+        const int idx = l + 64 * q;
+        const uint32_t ff = blockIdx.x * 4 + (idx >> 8);
+        smp[idx >> 8][idx & 255] = ff < F ? spec[static_cast<size_t>(ff) * 256 + (idx & 255)] : 0.0f;
+    }
+    __syncthreads();
+    const uint32_t f = blockIdx.x * 4 + (l >> 4);
+    const int band = l & 15;
+    if (f >= F)
+        return;
+    const uint32_t si = frameStream[f];
+    if (band >= keepArr[si])
+        return;
+    const int v = win[si] < 2 ? 0 : 1;                          // (0,0) -> Type 0, (1,0) -> Type 1
+    const size_t row = (static_cast<size_t>(v) * F + f) * 16;
+    uint64_t pos = (outOff[si] + 18) * 8 + frameOff[f];
+    for (int b = 0 ; b < band ; ++b)
+    {
+        const uint32_t m = bands[row + b].meta;
+        pos += (m & 0xFF) + (m >> 16);
+    }
+    const Enc93Band x = bands[row + band];
+    encPut(W, pos, x.hdr, static_cast<int>(x.meta & 0xFF));
+    if ((x.meta >> 16) == 0)
+        return;
+    pos += x.meta & 0xFF;
+    int first, n;
+    enc93Band(v, band, &first, &n);
+    const float scaleFactor = static_cast<float>(T.scale[hdr[(static_cast<size_t>(si) * 3 + v) * 16 + band] & 0x3f]);
+    const int sub = static_cast<int>((x.meta >> 12) & 3);
+    const int nBits = static_cast<int>((x.meta >> 8) & 15) + (v == 0 ? 1 : 0);
+    const uint32_t mask = (1u << nBits) - 1;
+    int prv = x.P, prvD = x.D;
+    for (int i = 0 ; i < n ; ++i)
+    {
+        const int s = static_cast<int>(roundf(smp[l >> 4][first + i] * 32768.0f / scaleFactor));
+        const int val = sub == 0 ? s : sub == 1 ? s - prv : s - prv - prvD;
+        prvD = s - prv;
+        prv = s;
+        encPut(W, pos + static_cast<uint64_t>(i) * nBits, static_cast<uint32_t>(val) & mask, nBits);
+    }
+}
+
+bool paramsValid(const DcsEncodeParams *p, bool os93)
+{
+    if (p == nullptr || p->streamFormatType < -1 || p->streamFormatType > 1 || p->targetBitRate < 1 || p->targetBitRate > 100000000
+        || !isfinite(p->powerBandCutoff) || !isfinite(p->minimumDynamicRange) || !isfinite(p->maximumQuantizationError))
+        return false;
+    if (!os93)
+        return p->formatVersion == 0x9400
+            && (p->streamFormatSubType == -1 || p->streamFormatSubType == 0 || p->streamFormatSubType == 3);
+    // OS93 has no sub-types: CloseStream forces 0 (:777-782); OS93a Type 1 has no encoder (CompressFrame93a :2485-2531)
+    return (p->formatVersion == 0x9301 || p->formatVersion == 0x9302) && p->streamFormatSubType >= -1 && p->streamFormatSubType <= 3
+        && !(p->formatVersion == 0x9301 && p->streamFormatType == 1);
 }
 
 const uint32_t kMaxBitsPerFrame = 16 * 23 + 255 * 15;      // every band at its longest header code and widest samples
+// OS93, every band at its longest flag and type code and widest samples: Type 1 (1 + 30 bits, 15-bit samples, 15 in
+// band 0) = 4 321 bits, more than Type 0 (1 + 2 + 4 bits, 16 x 16-bit samples) = 4 208
+const uint32_t kMaxBitsPerFrame93 = 16 * (1 + 30) + (15 + 15 * 16) * 15;
+
+size_t boundOf(uint64_t nSamples, uint32_t bitsPerFrame)
+{
+    const uint64_t nFrames = (nSamples + 239) / 240;
+    if (nFrames == 0 || nFrames > 65535)
+        return 0;
+    return static_cast<size_t>(18 + (nFrames * bitsPerFrame + 7) / 8);
+}
 
 }  // namespace
 
@@ -732,20 +1066,36 @@ extern "C" DcsStatus dcs_encode_params_default(DcsEncodeParams *p)
 
 extern "C" size_t dcs_encode_bound(uint64_t nSamples)
 {
-    const uint64_t nFrames = (nSamples + 239) / 240;
-    if (nFrames == 0 || nFrames > 65535)
-        return 0;
-    return static_cast<size_t>(18 + (nFrames * kMaxBitsPerFrame + 7) / 8);
+    return boundOf(nSamples, kMaxBitsPerFrame);
+}
+
+extern "C" size_t dcs_encode93_bound(uint64_t nSamples)
+{
+    return boundOf(nSamples, kMaxBitsPerFrame93);
 }
 
 extern "C" DcsStatus dcs_encode_header(const float *powerSum, const float *lo, const float *hi, const DcsEncodeParams *params,
                                        int formatType, int formatSubType, uint8_t *headerOut, int32_t *bandsToKeepOut, int32_t *bitsPerBandOut)
 {
-    if (powerSum == nullptr || lo == nullptr || hi == nullptr || headerOut == nullptr || !paramsValid(params)
+    if (powerSum == nullptr || lo == nullptr || hi == nullptr || headerOut == nullptr || !paramsValid(params, false)
         || (formatType != 0 && formatType != 1) || (formatSubType != 0 && formatSubType != 3))
         return DCS_ERR_INVALID_ARG;
     int bits[16], keep;
     encHeader(encTabs(), powerSum, lo, hi, params->powerBandCutoff, params->targetBitRate, formatType, formatSubType, headerOut, &keep, bits);
+    if (bandsToKeepOut != nullptr) *bandsToKeepOut = keep;
+    if (bitsPerBandOut != nullptr)
+        for (int b = 0 ; b < 16 ; ++b) bitsPerBandOut[b] = bits[b];
+    return DCS_OK;
+}
+
+extern "C" DcsStatus dcs_encode93_header(const float *powerSum, const float *lo, const float *hi, const DcsEncodeParams *params,
+                                         int formatType, uint8_t *headerOut, int32_t *bandsToKeepOut, int32_t *bitsPerBandOut)
+{
+    if (powerSum == nullptr || lo == nullptr || hi == nullptr || headerOut == nullptr || !paramsValid(params, true)
+        || (formatType != 0 && formatType != 1) || (params->formatVersion == 0x9301 && formatType == 1))
+        return DCS_ERR_INVALID_ARG;
+    int bits[16], keep;
+    encHeader(encTabs93(), powerSum, lo, hi, params->powerBandCutoff, params->targetBitRate, formatType, 0, headerOut, &keep, bits);
     if (bandsToKeepOut != nullptr) *bandsToKeepOut = keep;
     if (bitsPerBandOut != nullptr)
         for (int b = 0 ; b < 16 ; ++b) bitsPerBandOut[b] = bits[b];
@@ -763,12 +1113,22 @@ extern "C" DcsStatus dcs_encode_header(const float *powerSum, const float *lo, c
         }                                                                                            \
     } while (0)
 
-extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
-                                        const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
-                                        DcsEncodeInfo *info)
+namespace {
+
+// The one host driver behind dcs_encode_streams (os93 = false) and dcs_encode93_streams (os93 = true): validation,
+// buffers, E1 / E2, the family's band stages, the sizes and the capacity check, then the header, pack and swap.
+DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                        const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info,
+                        bool os93)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || !paramsValid(params) || (nStreams != 0 && pcm == nullptr))
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
         return DCS_ERR_INVALID_ARG;
+    if (!paramsValid(params, os93))
+    {
+        if (os93 && params != nullptr && params->formatVersion == 0x9301 && params->streamFormatType == 1)
+            dcsCtxSetError(ctx, "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0");
+        return DCS_ERR_INVALID_ARG;
+    }
     std::vector<EncStream> hs(nStreams);
     std::vector<uint32_t> frameStream;
     uint32_t F = 0;
@@ -795,14 +1155,15 @@ extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uin
         outOffsets[0] = 0;
         return DCS_OK;
     }
-    const int typ = params->streamFormatType, sub = params->streamFormatSubType;
+    const int typ = params->streamFormatType, sub = os93 ? 0 : params->streamFormatSubType;
     uint32_t cmask = 0;                 // candidates in CloseStream's order (0,0), (0,3), (1,0), (1,3)
     const int ct[4] = { 0, 0, 1, 1 }, cs[4] = { 0, 3, 0, 3 };
     for (int c = 0 ; c < 4 ; ++c)
-        if ((typ < 0 || typ == ct[c]) && (sub < 0 || sub == cs[c]))
+        if ((typ < 0 || typ == ct[c]) && (sub < 0 || sub == cs[c]) && !(os93 && params->formatVersion == 0x9301 && ct[c] == 1))
             cmask |= 1u << c;
     const uint32_t vmask = ((cmask & 3) ? 1u : 0u) | ((cmask & 4) ? 2u : 0u) | ((cmask & 8) ? 4u : 0u);
     const uint64_t nSamples = sampleOffsets[nStreams] - sampleOffsets[0];
+    const EncTabs &tabs = os93 ? encTabs93() : encTabs();
 
     const hipStream_t st = dcsCtxStream(ctx);
     std::vector<CacheBuf> held;
@@ -813,7 +1174,8 @@ extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uin
         return e;
     };
     EncTabs *dT; float *dPcm, *dSpec, *dPw, *dLo, *dHi; EncStream *dStr; uint32_t *dFS, *dBad, *dFrameBits, *dFrameOff, *dW;
-    uint8_t *dHdr, *dBest, *dCodes, *dHdrBits; uint16_t *dSmpBits; int32_t *dKeep, *dWin; uint64_t *dSize, *dOutOff;
+    uint8_t *dHdr, *dBest = nullptr, *dCodes = nullptr, *dHdrBits = nullptr; uint16_t *dSmpBits = nullptr;
+    Enc93Rec *dRec = nullptr; Enc93Band *dBand = nullptr; int32_t *dKeep, *dWin; uint64_t *dSize, *dOutOff;
     std::vector<int32_t> win(nStreams), keep(nStreams);
     std::vector<uint64_t> size(nStreams);
     std::vector<uint32_t> bad(nStreams);
@@ -830,31 +1192,52 @@ extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uin
         ENCCHK(alloc(reinterpret_cast<void **>(&dBad), sizeof(uint32_t) * nStreams));
         ENCCHK(alloc(reinterpret_cast<void **>(&dHdr), 48 * size_t(nStreams)));
         ENCCHK(alloc(reinterpret_cast<void **>(&dKeep), sizeof(int32_t) * nStreams));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dBest), size_t(128) * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dCodes), size_t(48) * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dHdrBits), size_t(48) * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dSmpBits), sizeof(uint16_t) * 48 * F));
+        if (os93)
+        {
+            ENCCHK(alloc(reinterpret_cast<void **>(&dRec), sizeof(Enc93Rec) * 32 * size_t(F)));
+            ENCCHK(alloc(reinterpret_cast<void **>(&dBand), sizeof(Enc93Band) * 32 * size_t(F)));
+        }
+        else
+        {
+            ENCCHK(alloc(reinterpret_cast<void **>(&dBest), size_t(128) * F));
+            ENCCHK(alloc(reinterpret_cast<void **>(&dCodes), size_t(48) * F));
+            ENCCHK(alloc(reinterpret_cast<void **>(&dHdrBits), size_t(48) * F));
+            ENCCHK(alloc(reinterpret_cast<void **>(&dSmpBits), sizeof(uint16_t) * 48 * F));
+        }
         ENCCHK(alloc(reinterpret_cast<void **>(&dFrameBits), sizeof(uint32_t) * 3 * F));
         ENCCHK(alloc(reinterpret_cast<void **>(&dFrameOff), sizeof(uint32_t) * F));
         ENCCHK(alloc(reinterpret_cast<void **>(&dWin), sizeof(int32_t) * nStreams));
         ENCCHK(alloc(reinterpret_cast<void **>(&dSize), sizeof(uint64_t) * nStreams));
         ENCCHK(alloc(reinterpret_cast<void **>(&dOutOff), sizeof(uint64_t) * nStreams));
-        ENCCHK(hipMemcpyAsync(dT, &encTabs(), sizeof(EncTabs), hipMemcpyHostToDevice, st));
+        ENCCHK(hipMemcpyAsync(dT, &tabs, sizeof(EncTabs), hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dPcm, pcm + sampleOffsets[0], sizeof(float) * nSamples, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(EncStream) * nStreams, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dFS, frameStream.data(), sizeof(uint32_t) * F, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * nStreams, st));
-        ENCCHK(hipMemsetAsync(dBest, 0, size_t(128) * F, st));
-        ENCCHK(hipMemsetAsync(dCodes, 0, size_t(48) * F, st));
         ENCCHK(hipMemsetAsync(dFrameBits, 0, sizeof(uint32_t) * 3 * F, st));
         hipLaunchKernelGGL(encAnalyseKernel, dim3((F + 3) / 4), dim3(256), 0, st, dT, dPcm, dStr, dFS, F, dSpec, dPw, dLo, dHi, dBad);
         hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, dT, dStr, dPw, dLo, dHi, params->powerBandCutoff,
                            params->targetBitRate, vmask, dHdr, dKeep);
-        hipLaunchKernelGGL(encSearchKernel, dim3(F), dim3(128), 0, st, dT, dSpec, dLo, dHi, dFS, dHdr, dKeep, vmask,
-                           params->minimumDynamicRange, params->maximumQuantizationError, dBest);
-        hipLaunchKernelGGL(encChainKernel, dim3(nStreams), dim3(64), 0, st, dT, dStr, dKeep, vmask, F,
-                           reinterpret_cast<const uint64_t *>(dBest), dCodes);
-        hipLaunchKernelGGL(encBitsKernel, dim3(F), dim3(64), 0, st, dT, dSpec, dStr, dFS, dHdr, dKeep, vmask, F, dCodes, dHdrBits, dSmpBits, dFrameBits);
+        if (os93)
+        {
+            hipLaunchKernelGGL(enc93SearchKernel, dim3((F + 3) / 4), dim3(128), 0, st, dT, dSpec, dFS, dHdr, dKeep, vmask, F,
+                               params->maximumQuantizationError, dRec);
+            if (vmask & 1)
+                hipLaunchKernelGGL(enc93WalkKernel<0>, dim3((F + 63) / 64), dim3(64), 0, st, dT, dStr, dFS, dKeep, F, F, dRec, dBand, dFrameBits);
+            if (vmask & 2)
+                hipLaunchKernelGGL(enc93WalkKernel<1>, dim3((nStreams + 63) / 64), dim3(64), 0, st, dT, dStr, dFS, dKeep, F, nStreams, dRec,
+                                   dBand, dFrameBits);
+        }
+        else
+        {
+            ENCCHK(hipMemsetAsync(dBest, 0, size_t(128) * F, st));
+            ENCCHK(hipMemsetAsync(dCodes, 0, size_t(48) * F, st));
+            hipLaunchKernelGGL(encSearchKernel, dim3(F), dim3(128), 0, st, dT, dSpec, dLo, dHi, dFS, dHdr, dKeep, vmask,
+                               params->minimumDynamicRange, params->maximumQuantizationError, dBest);
+            hipLaunchKernelGGL(encChainKernel, dim3(nStreams), dim3(64), 0, st, dT, dStr, dKeep, vmask, F,
+                               reinterpret_cast<const uint64_t *>(dBest), dCodes);
+            hipLaunchKernelGGL(encBitsKernel, dim3(F), dim3(64), 0, st, dT, dSpec, dStr, dFS, dHdr, dKeep, vmask, F, dCodes, dHdrBits, dSmpBits, dFrameBits);
+        }
         hipLaunchKernelGGL(encSizeKernel, dim3(nStreams), dim3(256), 0, st, dStr, F, cmask, dFrameBits, dWin, dSize, dFrameOff);
         ENCCHK(hipGetLastError());
         ENCCHK(hipMemcpyAsync(bad.data(), dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
@@ -882,8 +1265,12 @@ extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uin
         ENCCHK(hipMemsetAsync(dW, 0, sizeof(uint32_t) * nWords, st));
         ENCCHK(hipMemcpyAsync(dOutOff, outOffsets, sizeof(uint64_t) * nStreams, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(encHeadKernel, dim3(nStreams), dim3(64), 0, st, dStr, dHdr, dWin, dOutOff, dW);
-        hipLaunchKernelGGL(encPackKernel, dim3((F + 3) / 4), dim3(64), 0, st, dT, dSpec, dStr, dFS, dHdr, dKeep, dWin, F, dCodes,
-                           dHdrBits, dSmpBits, dFrameOff, dOutOff, dW);
+        if (os93)
+            hipLaunchKernelGGL(enc93PackKernel, dim3((F + 3) / 4), dim3(64), 0, st, dT, dSpec, dFS, dHdr, dKeep, dWin, F, dBand,
+                               dFrameOff, dOutOff, dW);
+        else
+            hipLaunchKernelGGL(encPackKernel, dim3((F + 3) / 4), dim3(64), 0, st, dT, dSpec, dStr, dFS, dHdr, dKeep, dWin, F, dCodes,
+                               dHdrBits, dSmpBits, dFrameOff, dOutOff, dW);
         hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
         ENCCHK(hipGetLastError());
         ENCCHK(hipMemcpyAsync(out, dW, total, hipMemcpyDeviceToHost, st));
@@ -894,4 +1281,20 @@ extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uin
     for (CacheBuf &h : held)
         h.release();
     return status;
+}
+
+}  // namespace
+
+extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                        const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                                        DcsEncodeInfo *info)
+{
+    return encodeStreams(ctx, pcm, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, false);
+}
+
+extern "C" DcsStatus dcs_encode93_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                          const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                                          DcsEncodeInfo *info)
+{
+    return encodeStreams(ctx, pcm, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, true);
 }

@@ -34,7 +34,8 @@ extern "C" {
 #define DCS_ABI_VERSION 9              /* 9: dcs_decode_batch_live, dcs_seq_decode_view, dcs_seq_plan_ahead, dcs_seq_stream_playing_at (round 6);
                                           additions since, which change no existing layout or entry point: the 1994+ encoder
                                           (DcsEncodeParams, DcsEncodeInfo, dcs_encode_params_default, dcs_encode_bound,
-                                          dcs_encode_header, dcs_encode_streams) */
+                                          dcs_encode_header, dcs_encode_streams); the OS93 encoder (dcs_encode93_bound,
+                                          dcs_encode93_header, dcs_encode93_streams) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -763,11 +764,12 @@ DcsStatus dcs_pack_chunks_device(DcsCtx *ctx, const DcsFrameJob *jobs, uint32_t 
  * :1623-2050, with its resampler at ratio 1).  Three departures, where the reference is undefined or wrong
  * ("Encoding"): the rate model's 1 << bitsPerBand is 1 << (bitsPerBand & 31) (what its x86 build
  * computes); a Type-1 candidate code whose scale index exceeds 0x3f is not eligible (the reference reads past its
- * table); empty streams and streams of more than 65 535 frames are rejected.  Only formatVersion 0x9400 for now.
+ * table); empty streams and streams of more than 65 535 frames are rejected.  dcs_encode_* take formatVersion 0x9400
+ * only; the OS93 versions have entry points of their own (dcs_encode93_*, below).
  */
 typedef struct DcsEncodeParams         /* DCSEncoder::CompressionParams (DCSEncoder.h:70-180)                         */
 {
-    uint16_t formatVersion;            /* 0x9400 (the 1994+ format; the OS93 encoders are not built)                     */
+    uint16_t formatVersion;            /* 0x9400 (the 1994+ format); dcs_encode93_*: 0x9302 (OS93b) or 0x9301 (OS93a)   */
     uint16_t reserved;
     int32_t  streamFormatType;         /* 0, 1, or -1: try both                                                          */
     int32_t  streamFormatSubType;      /* 0, 3, or -1: try both                                                          */
@@ -803,6 +805,22 @@ DcsStatus dcs_encode_header(const float *powerSum, const float *lo, const float 
 DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
                              const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
                              DcsEncodeInfo *info);
+
+/* OS93: PCM at 31 250 Hz -> OS93a / OS93b streams, byte for byte what the reference's DCSEncoder writes with
+ * formatVersion 0x9301 / 0x9302 (CompressFrame93b, DCSEncoder.cpp:2053-2470).  streamFormatType 0, 1, or -1 (0x9302: the
+ * first strictly smallest of Type 0 and Type 1; 0x9301: Type 0 only, as CloseStream :812 does).  0x9301 Type 1 has no
+ * encoder (CompressFrame93a) and is DCS_ERR_INVALID_ARG, with the reason in dcs_last_error.  OS93 has no sub-types:
+ * streamFormatSubType -1..3 is accepted and ignored; DcsEncodeInfo.formatSubType is 0.  One departure where the
+ * reference writes a corrupt stream ("Encoding"): a Type-1 band sub-type 1 candidate whose delta the
+ * chosen codebook cannot express (Keep: -15..+14) is not eligible.  Everything else as dcs_encode_streams. */
+/* the largest OS93 stream (either layout) nSamples samples can encode to (0 when nSamples is 0 or more than 65 535 frames) */
+size_t    dcs_encode93_bound(uint64_t nSamples);
+/* the stream header of one OS93 layout (formatType 0 or 1) from a stream's statistics over 16 bands of 16 samples */
+DcsStatus dcs_encode93_header(const float *powerSum, const float *lo, const float *hi, const DcsEncodeParams *params,
+                              int formatType, uint8_t *headerOut, int32_t *bandsToKeepOut, int32_t *bitsPerBandOut);
+DcsStatus dcs_encode93_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                               const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                               DcsEncodeInfo *info);
 
 uint32_t dcs_abi_version(void);
 /* a digest of the sources and compiler flags this library was built from (16 hex digits).  Counter profiles under

@@ -2,7 +2,8 @@
 """Encoder throughput on one GPU (dcs_encode_streams, host buffers in and out, timed to the call's return, which
 synchronises the device): frames per second and the real-time factor (seconds of 31 250 Hz audio per second) for
 256 streams x 256 frames and for one stream of 65 535 frames (the format's longest), in the reference's wildcard layout
-(three layouts searched).  --rocprof: per-kernel times from `rocprofv3 --kernel-trace --stats`, in a run of their own.
+(three layouts searched).  --version 9301 / 9302: the OS93 encoder (dcs_encode93_streams) in its wildcard (0x9302: Type 0
+and Type 1; 0x9301: Type 0).  --rocprof: per-kernel times from `rocprofv3 --kernel-trace --stats`, in a run of their own.
 Prints one JSON line."""
 import argparse
 import csv
@@ -27,12 +28,12 @@ def signal(n, seed):
     return np.clip(np.rint(x * 32767), -32768, 32767).astype(np.int16)
 
 
-def measure(ctx, pcm, iters):
-    ctx.encode_streams(pcm)                     # warm-up: buffers, code objects
+def measure(encode, pcm, iters):
+    encode(pcm)                                 # warm-up: buffers, code objects
     times = []
     for _ in range(iters):
         t0 = time.perf_counter()
-        streams, _ = ctx.encode_streams(pcm)
+        streams, _ = encode(pcm)
         times.append(time.perf_counter() - t0)
     frames = sum((len(x) + 239) // 240 for x in pcm)
     med = float(np.median(times))
@@ -41,10 +42,10 @@ def measure(ctx, pcm, iters):
                 bytes_out=sum(len(s) for s in streams))
 
 
-def rocprof(iters):
+def rocprof(iters, version):
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "enc", "--", sys.executable, os.path.abspath(__file__),
-               "--iters", str(iters)]
+               "--iters", str(iters), "--version", version]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             return dict(error="rocprofv3 exit %d" % r.returncode, stderr=r.stderr[-800:])
@@ -63,14 +64,22 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rocprof", action="store_true")
+    ap.add_argument("--version", choices=["9400", "9301", "9302"], default="9400")
     a = ap.parse_args()
     if a.rocprof:
-        print(json.dumps(dict(kernels=rocprof(3))))
+        print(json.dumps(dict(version=a.version, kernels=rocprof(3, a.version))))
         return
     import dcsexplorer_amd as D
     ctx = D.Context(0)
+    if a.version == "9400":
+        encode = ctx.encode_streams
+    else:
+        os_ = D.OS93A if a.version == "9301" else D.OS93B
+        encode = lambda pcm: ctx.encode93_streams(pcm, os_)        # noqa: E731
     batch = [signal(256 * 240, k) for k in range(256)]
-    res = dict(batch_256x256=measure(ctx, batch, a.iters), stream_65535=measure(ctx, [signal(65535 * 240, 999)], max(2, a.iters // 3)))
+    res = dict(batch_256x256=measure(encode, batch, a.iters), stream_65535=measure(encode, [signal(65535 * 240, 999)], max(2, a.iters // 3)))
+    if a.version != "9400":
+        res = dict(version=a.version, **res)
     ctx.close()
     print(json.dumps(res))
 
