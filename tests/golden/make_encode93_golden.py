@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generates tests/golden/encode93_golden.npz + encode93_golden.json: the reference ENCODER's OS93 streams
 (formatVersion 0x9301 / 0x9302, CompressFrame93b) for the inputs of encode_golden.npz, through the same driver
-(encoder/enc_pcm_driver.cpp) and the same builds as make_encode_golden.py: g++ -O2, and a second time with
+(encoder/enc_pcm_driver.cpp) and the same builds as make_encode_golden.py (`make -C oracle encref`): g++ -O2, and a second time with
 -fsanitize=bounds,shift,float-cast-overflow to screen every case (a bounds or float-cast report drops the case; shift
 reports are kept, the library's masked-shift rule covers them).
 
@@ -75,7 +75,7 @@ def main():
         return src[key + "/pcm"]
 
     with tempfile.TemporaryDirectory() as tmp:
-        exe, san = G.build(tmp, False), G.build(tmp, True)
+        exe, san = G.build(False), G.build(True)
         for name, key, fk, over in cases():
             p = dict(G.DEFAULTS, **over)
             version, typ = FMTS[fk]

@@ -3,9 +3,9 @@
 (DCSEncoder::OpenStream(31250) / WriteStream(float) / CloseStream through encoder/enc_pcm_driver.cpp), for the 1994+
 format in every fixed layout and the wildcard, over a sweep of CompressionParams and a set of edge signals.
 
-Build container only.  The encoder is compiled from where it lies under /root/reference exactly as
-make_encoder_golden.py compiles it (g++ -O2, encoder/enc_shim.h, the pass-through resampler encoder/enc_resample_stub.c)
-in a temporary directory, and a second time with -fsanitize=bounds,shift,float-cast-overflow to screen every case:
+Build container only.  The encoder is the checker `make -C oracle encref` builds from where it lies under /root/reference
+(oracle/_ref/dcs_encref: g++ -O2, encoder/enc_shim.h, the pass-through resampler encoder/enc_resample_stub.c), and
+its second build with -fsanitize=bounds,shift,float-cast-overflow (oracle/_ref/dcs_encref_san) screens every case:
 a case with a bounds or float-cast report is DROPPED (the reference's bytes then depend on its binary layout); shift
 reports are kept -- the 1 << bitsPerBand of CompressStream runs as x86 shl, which masks the count, and the library
 defines that rule ("Encoding").  Outputs are data and travel to the GPU box.
@@ -24,22 +24,18 @@ import tempfile
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-REF = "/root/reference"
 HERE = os.path.join(ROOT, "tests", "golden", "encoder")
 FMTS = {"wild": (-1, -1), "T0s0": (0, 0), "T0s3": (0, 3), "T1s0": (1, 0), "T1s3": (1, 3)}
 KEEP_BYTES = 4096
 DEFAULTS = dict(powerBandCutoff=0.97, targetBitRate=128000, minimumDynamicRange=10 / 32768, maximumQuantizationError=10 / 32768)
 
 
-def build(tmp, sanitize):
-    exe = os.path.join(tmp, "enc_san" if sanitize else "enc")
-    san = ["-fsanitize=bounds,shift,float-cast-overflow"] if sanitize else []
-    stub = os.path.join(tmp, "stub.o")
-    subprocess.check_call(["gcc", "-O2", "-w", "-I%s/libsamplerate/src" % REF, "-c", os.path.join(HERE, "enc_resample_stub.c"), "-o", stub])
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-w"] + san + ["-include", os.path.join(HERE, "enc_shim.h"),
-                           "-I%s/DCSEncoder" % REF, "-I%s/libsamplerate/src" % REF, "-o", exe,
-                           os.path.join(HERE, "enc_pcm_driver.cpp"), "%s/DCSEncoder/DCSEncoder.cpp" % REF,
-                           "%s/DCSDecoder/DCSDecoder.cpp" % REF, "%s/DCSDecoder/DCSDecoderNative.cpp" % REF, stub, "-lpthread"])
+def build(sanitize):
+    """the reference encoder (sanitize=False) or its UBSan build, as oracle/Makefile's `encref` target makes them"""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "encref"])
+    exe = os.path.join(ROOT, "oracle", "_ref", "dcs_encref_san" if sanitize else "dcs_encref")
+    if not os.path.exists(exe):
+        raise RuntimeError("%s was not built (the reference encoder sources are missing)" % exe)
     return exe
 
 
@@ -124,7 +120,7 @@ def main():
     signals.update(edge_signals())
     arrays, meta, dropped = {}, [], []
     with tempfile.TemporaryDirectory() as tmp:
-        exe, san = build(tmp, False), build(tmp, True)
+        exe, san = build(False), build(True)
         for name, key, fk, over in cases():
             p = dict(DEFAULTS, **over)
             _, report = run(san, signals[key], fk, p, tmp)
