@@ -16,4 +16,5 @@ from .api import (  # noqa: F401
     host_threads, partition_streams, decode_streams_sharded, Pipeline, make_refs, FRAME_TAIL_LOST, Node, DevicePath, node_cache_release, device_numa_node, bind_process_to_device_numa,
     FMT_94_T0_S3, ENCODE_INFO_DTYPE, EncodeParams, encode_params, encode_bound, encode_header,
     encode93_params, encode93_bound, encode93_header,
+    TRANSCODE_COPIED, TRANSCODE_REENCODED, TRANSCODE_REENCODE_ALL, TRANSCODE_INFO_DTYPE, TRANSCODE_OS, transcode_params, transcode_plan,
 )

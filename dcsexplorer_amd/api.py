@@ -88,6 +88,14 @@ FMT_94_T0_S3 = "94-T0-S3"
 _ENCODE_FMT = {None: (-1, -1), FMT_94_T0: (0, 0), FMT_94_T1_S0: (1, 0), FMT_94_T1_S3: (1, 3), FMT_94_T0_S3: (0, 3)}
 
 
+# dcs_transcode_*: what happens to a source, and its record (DcsTranscodeInfo)
+TRANSCODE_COPIED, TRANSCODE_REENCODED = 0, 1
+TRANSCODE_REENCODE_ALL = 1
+TRANSCODE_INFO_DTYPE = np.dtype([("action", "<i4"), ("srcFrames", "<i4"), ("enc", ENCODE_INFO_DTYPE)])
+# a target format version -> the OS its streams play under (and the DCSa container names)
+TRANSCODE_OS = {0x9301: 0, 0x9302: 1, 0x9400: 2}
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("format", ctypes.c_int32), ("nFrames", ctypes.c_int32),
                 ("nBands", ctypes.c_int32), ("strideFromBand", ctypes.c_int32), ("profile", ctypes.c_int32),
@@ -141,6 +149,7 @@ EXPORTS = [
     "dcs_node_last_error", "dcs_node_cache_release", "dcs_device_numa_node",
     "dcs_encode_params_default", "dcs_encode_bound", "dcs_encode_header", "dcs_encode_streams",
     "dcs_encode93_bound", "dcs_encode93_header", "dcs_encode93_streams",
+    "dcs_transcode_plan", "dcs_transcode_streams",
 ]
 
 
@@ -420,6 +429,10 @@ def load_library():
     L.dcs_encode93_header.argtypes = [vp, vp, vp, ctypes.POINTER(EncodeParams), i32, vp, ctypes.POINTER(i32), vp]
     L.dcs_encode93_streams.restype = i32
     L.dcs_encode93_streams.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), vp, sz, vp, vp]
+    L.dcs_transcode_plan.restype = i32
+    L.dcs_transcode_plan.argtypes = [vp, u32, ctypes.POINTER(EncodeParams), u32, vp, vp]
+    L.dcs_transcode_streams.restype = i32
+    L.dcs_transcode_streams.argtypes = [vp, vp, u32, ctypes.POINTER(EncodeParams), u32, vp, sz, vp, vp]
     L.dcs_device_numa_node.restype = ctypes.c_int
     L.dcs_device_numa_node.argtypes = [ctypes.c_int]
     L.dcs_host_threads.restype = ctypes.c_int
@@ -641,6 +654,45 @@ def encode93_header(power_sum, lo, hi, fmt_type, os_=OS93B, **params):
     _check(load_library().dcs_encode93_header(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), ctypes.byref(p), int(fmt_type), _ptr(hdr),
                                               ctypes.byref(keep), _ptr(bits)))
     return hdr, keep.value, bits
+
+
+def transcode_params(version=0x9400, fmt=None, **params):
+    """the EncodeParams of a transcode target: formatVersion 0x9400 (fmt as encode_params) or 0x9301 / 0x9302 (fmt as
+    encode93_params), CompressionParams by name"""
+    if version == 0x9400:
+        return encode_params(fmt, **params)
+    if version in (0x9301, 0x9302):
+        return encode93_params(TRANSCODE_OS[version], fmt, **params)
+    raise ValueError("no encoder for formatVersion %#x" % version)
+
+
+def _transcode_refs(streams, os_list, volume, level, channel_volume):
+    streams = [bytes(s) for s in streams]
+    os_list = list(os_list)
+    if len(os_list) != len(streams):
+        raise ValueError("%d streams, %d OS versions" % (len(streams), len(os_list)))
+    keep = [np.frombuffer(s, dtype=np.uint8) if s else np.zeros(1, np.uint8) for s in streams]
+    refs = (StreamRef * max(1, len(streams)))()
+    for k, s in enumerate(streams):
+        refs[k].data = keep[k].ctypes.data
+        refs[k].len = len(s)
+        refs[k].os = os_list[k]
+        refs[k].volume = volume
+        refs[k].level = level
+        refs[k].channelVolume = channel_volume
+    return refs, keep
+
+
+def transcode_plan(streams, os_list, version=0x9400, fmt=None, reencode_all=False, volume=0x67, level=0xFF, channel_volume=0xFF,
+                   **params):
+    """dcs_transcode_plan (host only): -> (action per stream, TRANSCODE_COPIED / _REENCODED; the bytes its output can take)"""
+    p = transcode_params(version, fmt, **params)
+    refs, keep = _transcode_refs(streams, os_list, volume, level, channel_volume)
+    n = len(keep) if streams else 0
+    action, bound = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64)
+    _check(load_library().dcs_transcode_plan(refs, n, ctypes.byref(p), TRANSCODE_REENCODE_ALL if reencode_all else 0,
+                                             _ptr(action), _ptr(bound)))
+    return action[:n], bound[:n]
 
 
 def _encode_input(pcm_list):
@@ -940,6 +992,34 @@ class Context:
         out = np.zeros(max(cap, 1), np.uint8)
         _check(self.L.dcs_encode93_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info
+
+    def transcode_streams(self, streams, os_list, version=0x9400, fmt=None, reencode_all=False, volume=0x67, level=0xFF,
+                          channel_volume=0xFF, **params):
+        """dcs_transcode_streams: DCS streams (bytes; os_list[i] = the OS stream i plays under) into the family of `version`
+        (0x9400, 0x9301 or 0x9302), as the reference's EncodeDCSFile does it: a stream that fits is copied, any other one is
+        decoded (volume / level / channel_volume: the reference's 0x67 / 0xFF / 0xFF) and encoded again on the device.
+        fmt and params: the target layout and CompressionParams (transcode_params).  Returns (list of bytes,
+        TRANSCODE_INFO_DTYPE array)."""
+        p = transcode_params(version, fmt, **params)
+        flags = TRANSCODE_REENCODE_ALL if reencode_all else 0
+        refs, keep = _transcode_refs(streams, os_list, volume, level, channel_volume)
+        n = len(keep) if streams else 0
+        bound = np.zeros(max(n, 1), np.uint64)
+        # (a source the plan refuses: the call below refuses it too, and names the reason in dcs_last_error)
+        st = self.L.dcs_transcode_plan(refs, n, ctypes.byref(p), flags, None, _ptr(bound))
+        cap = int(bound[:n].sum()) if st == 0 else 0
+        out = np.zeros(max(cap, 1), np.uint8)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info = np.zeros(max(n, 1), TRANSCODE_INFO_DTYPE)
+        _check(self.L.dcs_transcode_streams(self.h, refs, n, ctypes.byref(p), flags, _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n]
+
+    def transcode_dcsa(self, containers, version=0x9400, fmt=None, reencode_all=False, **kw):
+        """transcode_streams on "DCSa" containers (what EncodeDCSFile reads; the source OS from the container, 0x9400 as
+        OS94) -> (list of containers in the target's version, TRANSCODE_INFO_DTYPE array)"""
+        parsed = [dcsa_parse(c) for c in containers]
+        out, info = self.transcode_streams([s for _, s in parsed], [o for o, _ in parsed], version, fmt, reencode_all, **kw)
+        return [dcsa_header(TRANSCODE_OS[version], len(s)) + s for s in out], info
 
     def extract_streams(self, romset, volume=255, extra_frames=2):
         """the whole `--extract-streams` pipeline: ROM set -> plan -> one launch -> PCM per stream.

@@ -31,7 +31,9 @@
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
+#include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/dcs_hip.h"
 #include "dcs_tables.h"
@@ -300,7 +302,8 @@ __device__ uint32_t encBandSamples(const EncTabs &T, const float *smp, int n, in
     return bits;
 }
 
-struct EncStream { uint64_t sampleOff; uint32_t nSamples, firstFrame, nFrames, pad; };
+// errFrame: the decoder's error word of the stream's first frame (int16 input from a decode batch; 0 for float input)
+struct EncStream { uint64_t sampleOff; uint32_t nSamples, firstFrame, nFrames, errFrame; };
 
 // layouts computed: v0 = Type 0 (sub-types 0 and 3 differ only in two header bits), v1 = Type 1 sub-type 0, v2 = Type 1
 // sub-type 3.  Search slots per (frame, band): 0 = v0; 1, 2 = v1 at pre-adjust 0, 1; 3..7 = v2 at pre-adjust 0..4.
@@ -317,11 +320,16 @@ __device__ inline int encPre(const EncTabs &T, int v, int band, int old)
 
 __device__ inline int rev7(int i) { return static_cast<int>(__builtin_bitreverse32(static_cast<uint32_t>(i)) >> 25); }
 
-// E1: one wavefront per frame, four frames per block
-__global__ __launch_bounds__(256) void encAnalyseKernel(const EncTabs *__restrict__ Tp, const float *__restrict__ pcm,
+// E1: one wavefront per frame, four frames per block.  S = float: the caller's samples, |x| <= 1 checked.  S = int16_t: a
+// decode batch's resident PCM, x / 32768 (a power of two: exact, the same value as the float path's x / 32768.0f); frame
+// k of the stream reads decoded frames k - 1 and k, and lane 0 ORs decoded frame k's error word into the stream's flag.
+template <typename S>
+__global__ __launch_bounds__(256) void encAnalyseKernel(const EncTabs *__restrict__ Tp, const S *__restrict__ pcm,
     const EncStream *__restrict__ streams, const uint32_t *__restrict__ frameStream, uint32_t F, float *__restrict__ spec,
-    float *__restrict__ pw, float *__restrict__ flo, float *__restrict__ fhi, uint32_t *__restrict__ bad)
+    float *__restrict__ pw, float *__restrict__ flo, float *__restrict__ fhi, uint32_t *__restrict__ bad,
+    const uint32_t *__restrict__ err)
 {
+    constexpr bool kPcm16 = std::is_same<S, int16_t>::value;
     const EncTabs &T = *Tp;
     __shared__ float lds[4][260];
     const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -338,13 +346,23 @@ __global__ __launch_bounds__(256) void encAnalyseKernel(const EncTabs *__restric
         {
             const int i = l + 64 * q;
             const int64_t idx = base + i;
-            float x = (idx >= 0 && idx < static_cast<int64_t>(s.nSamples)) ? pcm[s.sampleOff + static_cast<uint64_t>(idx)] : 0.0f;
-            if (!(fabsf(x) <= 1.0f))
-                isBad = true;
+            const S raw = (idx >= 0 && idx < static_cast<int64_t>(s.nSamples)) ? pcm[s.sampleOff + static_cast<uint64_t>(idx)] : S(0);
+            float x;
+            if constexpr (kPcm16)
+                x = static_cast<float>(raw) * (1.0f / 32768.0f);
+            else
+            {
+                x = raw;
+                if (!(fabsf(x) <= 1.0f))
+                    isBad = true;
+            }
             if (i < 16) x *= T.window[i];
             else if (i >= 240) x *= T.window[255 - i];
             b[(rev7(i >> 1) << 1) | (i & 1)] = x;
         }
+        if constexpr (kPcm16)
+            if (l == 0 && err[s.errFrame + (f - s.firstFrame)] != 0)
+                isBad = true;
         if (isBad)
             atomicOr(&bad[si], 1u);
     }
@@ -1115,13 +1133,31 @@ extern "C" DcsStatus dcs_encode93_header(const float *powerSum, const float *lo,
 
 namespace {
 
-// The one host driver behind dcs_encode_streams (os93 = false) and dcs_encode93_streams (os93 = true): validation,
-// buffers, E1 / E2, the family's band stages, the sizes and the capacity check, then the header, pack and swap.
-DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
-                        const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info,
-                        bool os93)
+// Where the driver reads its samples: the caller's float PCM on the host (dcs_encode_streams, dcs_encode93_streams), or a
+// decode batch's int16 PCM and error words, resident on the device (dcs_transcode_streams, dcs_transcode.hip.h)
+struct EncInput
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
+    const float *hostPcm = nullptr;
+    const int16_t *devPcm = nullptr;        // stream i starts at sample sampleOffsets[i], a multiple of 240 ...
+    const uint32_t *devErr = nullptr;       // ... and its frames' error words at sampleOffsets[i] / 240
+    const uint32_t *label = nullptr;        // the number a message gives stream i (null: i)
+    const volatile uint32_t *planFlag = nullptr;    // a word the device writes before the PCM is final: not 0 = the PCM is not to be used
+    bool unusable = false;                  // (out) planFlag was set: DCS_ERR_BAD_STREAM, and nothing was written
+};
+
+// after the sizes are known: the host memory that takes the `total` bytes (stream i at outOffsets[i]), or null for DCS_ERR_CAPACITY
+using EncPlace = std::function<uint8_t *(const uint64_t *outOffsets, uint64_t total)>;
+
+// The one host driver behind dcs_encode_streams (os93 = false), dcs_encode93_streams (os93 = true) and the re-encodes of
+// dcs_transcode_streams: validation, buffers, E1 / E2, the family's band stages, the sizes and the capacity check, then
+// the header, pack and swap.  Returns after the stream is idle: device input may be released then.
+DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets, uint32_t nStreams,
+                        const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info,
+                        bool os93, const EncPlace &place = nullptr)
+{
+    const bool dev = in.devPcm != nullptr;
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && in.hostPcm == nullptr && !dev)
+        || (dev && in.devErr == nullptr))
         return DCS_ERR_INVALID_ARG;
     if (!paramsValid(params, os93))
     {
@@ -1129,6 +1165,7 @@ DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOff
             dcsCtxSetError(ctx, "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0");
         return DCS_ERR_INVALID_ARG;
     }
+    auto name = [&](uint32_t i) { return "stream " + std::to_string(in.label ? in.label[i] : i); };
     std::vector<EncStream> hs(nStreams);
     std::vector<uint32_t> frameStream;
     uint32_t F = 0;
@@ -1136,17 +1173,18 @@ DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOff
     {
         if (sampleOffsets[i + 1] <= sampleOffsets[i])
         {
-            dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": empty").c_str());
+            dcsCtxSetError(ctx, (name(i) + ": empty").c_str());
             return DCS_ERR_INVALID_ARG;
         }
         const uint64_t n = sampleOffsets[i + 1] - sampleOffsets[i];
         const uint64_t nF = (n + 239) / 240;
         if (nF > 65535)
         {
-            dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": more than 65 535 frames").c_str());
+            dcsCtxSetError(ctx, (name(i) + ": more than 65 535 frames").c_str());
             return DCS_ERR_INVALID_ARG;
         }
-        hs[i] = EncStream{ sampleOffsets[i] - sampleOffsets[0], static_cast<uint32_t>(n), F, static_cast<uint32_t>(nF), 0 };
+        hs[i] = EncStream{ sampleOffsets[i] - sampleOffsets[0], static_cast<uint32_t>(n), F, static_cast<uint32_t>(nF),
+                           dev ? static_cast<uint32_t>(sampleOffsets[i] / 240) : 0u };
         frameStream.insert(frameStream.end(), static_cast<size_t>(nF), i);
         F += static_cast<uint32_t>(nF);
     }
@@ -1173,7 +1211,7 @@ DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOff
         *p = held.back().as();
         return e;
     };
-    EncTabs *dT; float *dPcm, *dSpec, *dPw, *dLo, *dHi; EncStream *dStr; uint32_t *dFS, *dBad, *dFrameBits, *dFrameOff, *dW;
+    EncTabs *dT; float *dPcm = nullptr, *dSpec, *dPw, *dLo, *dHi; EncStream *dStr; uint32_t *dFS, *dBad, *dFrameBits, *dFrameOff, *dW;
     uint8_t *dHdr, *dBest = nullptr, *dCodes = nullptr, *dHdrBits = nullptr; uint16_t *dSmpBits = nullptr;
     Enc93Rec *dRec = nullptr; Enc93Band *dBand = nullptr; int32_t *dKeep, *dWin; uint64_t *dSize, *dOutOff;
     std::vector<int32_t> win(nStreams), keep(nStreams);
@@ -1182,7 +1220,8 @@ DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOff
     DcsStatus status = [&]() -> DcsStatus {
         ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
         ENCCHK(alloc(reinterpret_cast<void **>(&dT), sizeof(EncTabs)));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dPcm), sizeof(float) * nSamples));
+        if (!dev)
+            ENCCHK(alloc(reinterpret_cast<void **>(&dPcm), sizeof(float) * nSamples));
         ENCCHK(alloc(reinterpret_cast<void **>(&dStr), sizeof(EncStream) * nStreams));
         ENCCHK(alloc(reinterpret_cast<void **>(&dFS), sizeof(uint32_t) * F));
         ENCCHK(alloc(reinterpret_cast<void **>(&dSpec), sizeof(float) * 256 * F));
@@ -1210,12 +1249,18 @@ DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOff
         ENCCHK(alloc(reinterpret_cast<void **>(&dSize), sizeof(uint64_t) * nStreams));
         ENCCHK(alloc(reinterpret_cast<void **>(&dOutOff), sizeof(uint64_t) * nStreams));
         ENCCHK(hipMemcpyAsync(dT, &tabs, sizeof(EncTabs), hipMemcpyHostToDevice, st));
-        ENCCHK(hipMemcpyAsync(dPcm, pcm + sampleOffsets[0], sizeof(float) * nSamples, hipMemcpyHostToDevice, st));
+        if (!dev)
+            ENCCHK(hipMemcpyAsync(dPcm, in.hostPcm + sampleOffsets[0], sizeof(float) * nSamples, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(EncStream) * nStreams, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dFS, frameStream.data(), sizeof(uint32_t) * F, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * nStreams, st));
         ENCCHK(hipMemsetAsync(dFrameBits, 0, sizeof(uint32_t) * 3 * F, st));
-        hipLaunchKernelGGL(encAnalyseKernel, dim3((F + 3) / 4), dim3(256), 0, st, dT, dPcm, dStr, dFS, F, dSpec, dPw, dLo, dHi, dBad);
+        if (dev)
+            hipLaunchKernelGGL(encAnalyseKernel<int16_t>, dim3((F + 3) / 4), dim3(256), 0, st, dT, in.devPcm + sampleOffsets[0], dStr, dFS, F,
+                               dSpec, dPw, dLo, dHi, dBad, in.devErr);
+        else
+            hipLaunchKernelGGL(encAnalyseKernel<float>, dim3((F + 3) / 4), dim3(256), 0, st, dT, dPcm, dStr, dFS, F, dSpec, dPw, dLo, dHi, dBad,
+                               static_cast<const uint32_t *>(nullptr));
         hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, dT, dStr, dPw, dLo, dHi, params->powerBandCutoff,
                            params->targetBitRate, vmask, dHdr, dKeep);
         if (os93)
@@ -1245,10 +1290,16 @@ DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOff
         ENCCHK(hipMemcpyAsync(keep.data(), dKeep, sizeof(int32_t) * nStreams, hipMemcpyDeviceToHost, st));
         ENCCHK(hipMemcpyAsync(size.data(), dSize, sizeof(uint64_t) * nStreams, hipMemcpyDeviceToHost, st));
         ENCCHK(hipStreamSynchronize(st));
+        if (in.planFlag != nullptr && *in.planFlag != 0)
+        {
+            in.unusable = true;
+            return DCS_ERR_BAD_STREAM;
+        }
         for (uint32_t i = 0 ; i < nStreams ; ++i)
             if (bad[i])
             {
-                dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": a sample is not finite or |x| > 1").c_str());
+                dcsCtxSetError(ctx, (name(i) + (dev ? ": the decoder reports an error in a frame (DCS_FRAME_STOP / DCS_FRAME_FATAL)"
+                                                    : ": a sample is not finite or |x| > 1")).c_str());
                 return DCS_ERR_BAD_STREAM;
             }
         outOffsets[0] = 0;
@@ -1258,7 +1309,8 @@ DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOff
             for (uint32_t i = 0 ; i < nStreams ; ++i)
                 info[i] = DcsEncodeInfo{ ct[win[i]], cs[win[i]], static_cast<int32_t>(hs[i].nFrames), static_cast<int32_t>(size[i]), keep[i] };
         const uint64_t total = outOffsets[nStreams];
-        if (out == nullptr || outCap < total)
+        uint8_t *dst = place ? place(outOffsets, total) : (out != nullptr && outCap >= total ? out : nullptr);
+        if (dst == nullptr)
             return DCS_ERR_CAPACITY;
         const size_t nWords = static_cast<size_t>((total + 3) / 4) + 1;
         ENCCHK(alloc(reinterpret_cast<void **>(&dW), sizeof(uint32_t) * nWords));
@@ -1273,7 +1325,7 @@ DcsStatus encodeStreams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOff
                                dHdrBits, dSmpBits, dFrameOff, dOutOff, dW);
         hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
         ENCCHK(hipGetLastError());
-        ENCCHK(hipMemcpyAsync(out, dW, total, hipMemcpyDeviceToHost, st));
+        ENCCHK(hipMemcpyAsync(dst, dW, total, hipMemcpyDeviceToHost, st));
         ENCCHK(hipStreamSynchronize(st));
         return DCS_OK;
     }();
@@ -1289,12 +1341,95 @@ extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uin
                                         const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
                                         DcsEncodeInfo *info)
 {
-    return encodeStreams(ctx, pcm, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, false);
+    EncInput in;
+    in.hostPcm = pcm;
+    return encodeStreams(ctx, in, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, false);
 }
 
 extern "C" DcsStatus dcs_encode93_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
                                           const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
                                           DcsEncodeInfo *info)
 {
-    return encodeStreams(ctx, pcm, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, true);
+    EncInput in;
+    in.hostPcm = pcm;
+    return encodeStreams(ctx, in, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, true);
+}
+
+// ----------------------------------------------------------------------------------------- transcoding (dcs_transcode.hip.h)
+
+namespace {
+
+uint16_t sourceVersion(int32_t os) { return os == DCS_OS93A ? 0x9301 : os == DCS_OS93B ? 0x9302 : 0x9400; }
+
+}  // namespace
+
+// EncodeDCSFile's rule (DCSEncoder.cpp:498-517): a source is copied when its version is the target's, or when both are OS93
+// and the source is Type 0; every other source is decoded for nFrames + 1 frames and encoded again.  why = the reason of a
+// failure, for dcs_last_error.
+DcsStatus dcsTranscodePlan(const DcsStreamRef *src, uint32_t nStreams, const DcsEncodeParams *target, uint32_t flags,
+                           int32_t *actionOut, uint64_t *boundOut, std::string &why)
+{
+    if ((nStreams != 0 && src == nullptr) || target == nullptr || (flags & ~DCS_TRANSCODE_REENCODE_ALL) != 0)
+        return DCS_ERR_INVALID_ARG;
+    const bool os93 = target->formatVersion != 0x9400;
+    if (!paramsValid(target, os93))
+    {
+        char text[96];
+        snprintf(text, sizeof(text), "target: not a valid DcsEncodeParams for formatVersion 0x%x", target->formatVersion);
+        why = os93 && target->formatVersion == 0x9301 && target->streamFormatType == 1
+            ? "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0" : text;
+        return DCS_ERR_INVALID_ARG;
+    }
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+    {
+        const DcsStreamRef &s = src[i];
+        const std::string name = "stream " + std::to_string(i);
+        if (s.data == nullptr || s.os < DCS_OS93A || s.os > DCS_OS95)
+        {
+            why = name + ": no data, or not a DcsOsVersion";
+            return DCS_ERR_INVALID_ARG;
+        }
+        if (s.len < 3)
+        {
+            why = name + ": shorter than 3 bytes (no type bit)";
+            return DCS_ERR_BAD_STREAM;
+        }
+        const uint16_t v = sourceVersion(s.os);
+        const uint32_t nFrames = (static_cast<uint32_t>(s.data[0]) << 8) | s.data[1];
+        const bool copy = (flags & DCS_TRANSCODE_REENCODE_ALL) == 0
+                          && (v == target->formatVersion || (os93 && v != 0x9400 && (s.data[2] & 0x80) == 0));
+        if (!copy && nFrames == 0)
+        {
+            why = name + ": zero frames";
+            return DCS_ERR_BAD_STREAM;
+        }
+        if (!copy && nFrames + 1 > 65535)
+        {
+            why = name + ": 65 535 frames; re-encoded with the extra frame it would need 65 536, more than the frame count holds";
+            return DCS_ERR_INVALID_ARG;
+        }
+        if (actionOut != nullptr)
+            actionOut[i] = copy ? DCS_TRANSCODE_COPIED : DCS_TRANSCODE_REENCODED;
+        if (boundOut != nullptr)
+            boundOut[i] = copy ? static_cast<uint64_t>(s.len) : boundOf(static_cast<uint64_t>(nFrames + 1) * 240, os93 ? kMaxBitsPerFrame93 : kMaxBitsPerFrame);
+    }
+    return DCS_OK;
+}
+
+// The re-encodes of dcs_transcode_streams: encodeStreams on a decode batch's resident PCM (stream k from sample
+// sampleOffsets[k]) and error words.  label[k] = the source's index, for messages.  *unusable: planFlag was set after the
+// first wait (nothing written).  place: as EncPlace.
+DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *dErr, const volatile uint32_t *planFlag,
+                              const uint64_t *sampleOffsets, const uint32_t *label, uint32_t nStreams, const DcsEncodeParams *target,
+                              bool *unusable, uint64_t *encOffsets, DcsEncodeInfo *info, const EncPlace &place)
+{
+    EncInput in;
+    in.devPcm = dPcm;
+    in.devErr = dErr;
+    in.label = label;
+    in.planFlag = planFlag;
+    const DcsStatus st = encodeStreams(ctx, in, sampleOffsets, nStreams, target, nullptr, 0, encOffsets, info,
+                                       target->formatVersion != 0x9400, place);
+    *unusable = in.unusable;
+    return st;
 }

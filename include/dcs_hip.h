@@ -35,7 +35,8 @@ extern "C" {
                                           additions since, which change no existing layout or entry point: the 1994+ encoder
                                           (DcsEncodeParams, DcsEncodeInfo, dcs_encode_params_default, dcs_encode_bound,
                                           dcs_encode_header, dcs_encode_streams); the OS93 encoder (dcs_encode93_bound,
-                                          dcs_encode93_header, dcs_encode93_streams) */
+                                          dcs_encode93_header, dcs_encode93_streams); transcoding (DcsTranscodeInfo,
+                                          dcs_transcode_plan, dcs_transcode_streams) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -821,6 +822,40 @@ DcsStatus dcs_encode93_header(const float *powerSum, const float *lo, const floa
 DcsStatus dcs_encode93_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
                                const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
                                DcsEncodeInfo *info);
+
+/* ------------------------------------------------------------------------------------------------
+ * Transcoding: DCS streams of any family into the family of `target` (formatVersion 0x9400: the 1994+ encoder; 0x9301 /
+ * 0x9302: the OS93 encoder; checked as those encoders check it), the reference's DCSEncoder::EncodeDCSFile
+ * (DCSEncoder.cpp:402-587).  A source's version comes from its `os` (OS93A 0x9301, OS93B 0x9302, OS94 / OS95 0x9400).
+ * It is COPIED (its len bytes verbatim, nothing decoded) when its version is the target's, or when both are 0x93xx and its
+ * type bit (data[2] & 0x80) is 0; every other source is RE-ENCODED: decoded as dcs_decode_streams decodes it with
+ * extraFrames = 1 (the ref's volume, level and channelVolume as given; the reference plays 0x67 / 0xFF / 0xFF), and those
+ * samples, x / 32768, encoded with `target`.  The PCM stays on the device between the two.  DCS_TRANSCODE_REENCODE_ALL
+ * re-encodes every source.  Errors, with the stream's index in dcs_last_error ("Transcoding"): a source
+ * shorter than 3 bytes, a re-encoded source of zero frames, or one whose decode reports an error word in any frame, is
+ * DCS_ERR_BAD_STREAM; a re-encoded source of 65 535 frames (65 536 with the extra frame) is DCS_ERR_INVALID_ARG.
+ * outOffsets (nStreams + 1) is filled whenever the encodes ran: DCS_ERR_CAPACITY means outCap < outOffsets[nStreams].
+ */
+#define DCS_TRANSCODE_COPIED        0
+#define DCS_TRANSCODE_REENCODED     1
+#define DCS_TRANSCODE_REENCODE_ALL  1u     /* flags */
+
+typedef struct DcsTranscodeInfo
+{
+    int32_t action;                    /* DCS_TRANSCODE_COPIED / DCS_TRANSCODE_REENCODED                                  */
+    int32_t srcFrames;                 /* the source's frame count                                                        */
+    DcsEncodeInfo enc;                 /* re-encoded: as the encoder reports it; copied: nFrames, nBytes = len, formatType
+                                          from the type bit, formatSubType from the 1994+ sub-type bits, bandsToKeep -1   */
+} DcsTranscodeInfo;
+
+/* host only, no GPU: each source's action (actionOut) and the bytes its output can take (boundOut: len for a copy,
+ * dcs_encode_bound / dcs_encode93_bound of (nFrames + 1) * 240 for a re-encode); either may be NULL.  The same checks
+ * as dcs_transcode_streams, but no decode: a decode error is found only there. */
+DcsStatus dcs_transcode_plan(const DcsStreamRef *src, uint32_t nStreams, const DcsEncodeParams *target, uint32_t flags,
+                             int32_t *actionOut, uint64_t *boundOut);
+/* Stream i is written to out + outOffsets[i], in input order; info (optional) = nStreams records. */
+DcsStatus dcs_transcode_streams(DcsCtx *ctx, const DcsStreamRef *src, uint32_t nStreams, const DcsEncodeParams *target,
+                                uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsTranscodeInfo *info);
 
 uint32_t dcs_abi_version(void);
 /* a digest of the sources and compiler flags this library was built from (16 hex digits).  Counter profiles under
