@@ -2,10 +2,15 @@
 """bench.py -- throughput of the batched DCS frame decode on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload survey3_65536|dcs94_65536|dcs93_4096|mixed_16384|realistic_65536|corpus]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (one kernel launch) over one resident batch of synthetic frames.
 Metric (BASELINE.json): bit-exact int16 PCM samples/s; value = samples of all ranks / max-over-ranks time.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, --dump-outputs, the line.  --full
+adds everything else, after the timed steps and in this order: kernel time by HIP events and the roofline, every rank's PCM
+against the reference's committed hashes (bit_exact), end_to_end over the ranks, and the optional sections (other workloads,
+cold inputs, the whole device path, end to end, class surface, CPU baseline; the --no-* options leave single ones out).
 
 Multi-GPU: one process per GPU.  Started as one process with --gpus N > 1 (no RANK in the environment) this script
 starts the N ranks itself (python -m torch.distributed.run ... bench.py, rendezvous on 127.0.0.1) and relays rank 0's
@@ -53,6 +58,8 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD)
+    ap.add_argument("--full", action="store_true", help="besides the headline: kernel time and roofline, the PCM against the reference's "
+                    "hashes (bit_exact), end to end, the other workloads and the CPU baseline (a plain run times the steps and nothing else)")
     ap.add_argument("--fpw", type=int, default=0, help="frames per wavefront override (4/8/16)")
     ap.add_argument("--frames-per-chunk", type=int, default=0, help="diagnostic: frames a wavefront decodes (1 = one wavefront "
                     "per frame with the lanes of the other slots idle); 0 = every slot of the kernel variant")
@@ -1016,6 +1023,61 @@ def run_rank(args):
     if args.dump_outputs and rank == 0:
         dumped = dump_outputs(args.dump_outputs, batch)      # (outside the timed region; a failure here fails the run)
 
+    def headline():
+        """the keys of the line that a plain run prints too: the rate of the K steps and what was timed"""
+        line = {
+            "metric": "bit_exact_int16_pcm_samples_per_sec",
+            "value": total_frames * 240 * args.steps / dt,
+            "unit": "samples/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": "int16",
+            "data": "synthetic",
+            "config": {"workload": args.workload, "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "rank0_bound_to_numa_node": args.numa_node,
+                       "workload_is": {"survey3_65536": "BASELINE configs[2] as SURVEY.md 8(d) Config 3 specifies it: 256 streams x 256 1994+ frames, 80 % Type 1 "
+                                                        "sub-type 3, 10 % Type 1 sub-type 0, 10 % Type 0, 12 populated bands, 120 B/frame",
+                                       "dcs94_65536": "BASELINE configs[2], the form of rounds 1 and 2: 16 populated bands, 96 B/frame"}.get(args.workload, args.workload),
+                       "frames_rank0_per_step": n_frames, "frames_all_ranks_per_step": total_frames,
+                       "samples_per_frame": 240, "frames_per_wave": batch.frames_per_wave, "wavefronts_per_launch": batch.num_chunks,
+                       "arithmetic": "ADSP-2105 1.15 fixed point, 32-bit integer intermediates",
+                       "partition": "range over streams%s, no collective" % (", balanced by frames" if corpus else ""),
+                       "scale": args.scale, "inflight": args.inflight, "clock_settle_ms": args.clock_settle_ms, "frames_per_chunk": args.frames_per_chunk or "all",
+                       "full": args.full},
+            **({"share_gpu": "all ranks on GPU 0 (test of the N-rank path on a one-GPU box): not a scaling measurement"} if args.share_gpu else {}),
+            **({"force_dist": "one rank through the N-rank code: process group of one, NUMA bind, the exchanges on the device"} if args.force_dist else {}),
+            "dist": dist_info,
+        }
+        if corpus:
+            line["config"]["corpus"] = golden_range[0]
+            line["config"]["rank0_stream_range"] = [golden_range[1], golden_range[2]]
+        return line
+
+    def release():
+        for bt, _ in extra:
+            bt.close()
+        batch.close()
+        ctx.close()
+        try:
+            comm.barrier()                  # (rank 0 has printed before any rank leaves)
+        except Exception:
+            pass
+        comm.close()
+
+    if not args.full:
+        # a plain run ends here: the line is the headline and what was timed; checks and further figures are --full's
+        if rank == 0:
+            out = headline()
+            if dumped is not None:
+                out["dump_outputs"] = dumped
+            emit(out)
+        release()
+        return
+
     # From here on nothing may take the line away: everything below is guarded, and every rank reaches every exchange.
     # kernel-only average duration by HIP events on the launch stream (roofline denominator)
     # (three runs of K launches, the median: the host now and then falls behind 8-us kernels and an average over one
@@ -1055,8 +1117,7 @@ def run_rank(args):
     hard_exit = bool(e2e_ranks and e2e_ranks.get("abandoned"))
 
     if rank == 0:
-        samples = total_frames * 240 * args.steps
-        achieved = None if kern_ms is None else algo_bytes / (kern_ms * 1e-3) / 1e9
+        achieved =None if kern_ms is None else algo_bytes / (kern_ms * 1e-3) / 1e9
         # HBM traffic per launch: FETCH_SIZE + WRITE_SIZE of the rocprofv3 --pmc passes of this same command
         # (tools/prof.sh), committed under profiles/; null when no profile of this workload exists
         traffic, traffic_note, valu = None, None, None
@@ -1089,31 +1150,7 @@ def run_rank(args):
                                         "VOP1/VOP2 complete in 2.2, so this is an upper estimate of the SIMDs' VALU occupancy and "
                                         "reaches 1.0 on launches long enough for ramp and tail not to count",
                         "lds_bank_conflict_cycles": t.get("SQ_LDS_BANK_CONFLICT"), "lds_idx_active": t.get("SQ_LDS_IDX_ACTIVE")}
-        out = {
-            "metric": "bit_exact_int16_pcm_samples_per_sec",
-            "value": samples / dt,
-            "unit": "samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "int16",
-            "data": "synthetic",
-            "config": {"workload": args.workload, "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "rank0_bound_to_numa_node": args.numa_node,
-                       "workload_is": {"survey3_65536": "BASELINE configs[2] as SURVEY.md 8(d) Config 3 specifies it: 256 streams x 256 1994+ frames, 80 % Type 1 "
-                                                        "sub-type 3, 10 % Type 1 sub-type 0, 10 % Type 0, 12 populated bands, 120 B/frame",
-                                       "dcs94_65536": "BASELINE configs[2], the form of rounds 1 and 2: 16 populated bands, 96 B/frame"}.get(args.workload, args.workload),
-                       "frames_rank0_per_step": n_frames, "frames_all_ranks_per_step": total_frames,
-                       "samples_per_frame": 240, "frames_per_wave": batch.frames_per_wave, "wavefronts_per_launch": batch.num_chunks,
-                       "arithmetic": "ADSP-2105 1.15 fixed point, 32-bit integer intermediates",
-                       "partition": "range over streams%s, no collective" % (", balanced by frames" if corpus else ""),
-                       "scale": args.scale, "inflight": args.inflight, "clock_settle_ms": args.clock_settle_ms, "frames_per_chunk": args.frames_per_chunk or "all"},
-            **({"share_gpu": "all ranks on GPU 0 (test of the N-rank path on a one-GPU box): not a scaling measurement"} if args.share_gpu else {}),
-            **({"force_dist": "one rank through the N-rank code: process group of one, NUMA bind, the exchanges on the device"} if args.force_dist else {}),
-            "dist": dist_info,
+        out = dict(headline(), **{
             "bit_exact": bit_exact,
             "bit_exact_ranks": bit_exact_ranks,
             "bit_exact_note": bit_exact_note,
@@ -1124,14 +1161,11 @@ def run_rank(args):
                          "algorithmic_bytes_note": "SURVEY 8(d): exact payload + stream headers + 56 B descriptor and 480 B PCM per frame "
                                                    "(x %d frames per launch)" % n_frames,
                          "abi_bytes_per_launch": batch.abi_bytes, "valu_issue": valu},
-        }
+        })
         if core_notes:
             out["notes"] = core_notes
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if corpus:
-            out["config"]["corpus"] = golden_range[0]
-            out["config"]["rank0_stream_range"] = [golden_range[1], golden_range[2]]
         if e2e_ranks is not None:
             out["end_to_end"] = e2e_ranks
 
@@ -1229,15 +1263,7 @@ def run_rank(args):
         # (the line is out and `value` is whole; an optional section was given up, which the line says.  Exit code 0 by default -- a
         # harness that reads the line must not take the run for failed --, DCS_BENCH_STRICT_EXIT=1 turns it into 3 for a CI: ADVICE r5)
         os._exit(3 if os.environ.get("DCS_BENCH_STRICT_EXIT", "0") not in ("", "0") else 0)
-    for bt, _ in extra:
-        bt.close()
-    batch.close()
-    ctx.close()
-    try:
-        comm.barrier()                      # (rank 0 has printed before any rank leaves)
-    except Exception:
-        pass
-    comm.close()
+    release()
 
 
 def main():

@@ -2,7 +2,7 @@
 """Generates tests/golden/rank_golden_hashes.json: per-stream FNV-1a-64 hashes of the PCM the UNMODIFIED reference
 decoder (oracle/_ref/libdcsref.so) produces for the share of every rank 0..7 of the weak-scaling bench workloads
 (rank r decodes streams [r*n, (r+1)*n) of the seeded corpus: dcsexplorer_amd/sharding.py rank_streams), so that
-`bench.py --gpus N` can hold EVERY rank's PCM against the reference, not rank 0's only.  Each stream is played alone
+`bench.py --full --gpus N` can hold EVERY rank's PCM against the reference, not rank 0's only.  Each stream is played alone
 from a fresh decoder, as --extract-streams plays them (DCSExplorer.cpp:1900-1907).  Build container only; the output is
 data and travels to the GPU box."""
 import json

@@ -394,7 +394,7 @@ def test_bench_two_ranks_on_one_gpu_runs_launcher_ranks_and_kernel(tmp_path):
     says n_gpus 2, carries per-rank host figures, and EVERY rank's PCM equals the reference's hashes of its range"""
     import subprocess
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--steps", "3", "--warmup", "1",
                         "--e2e-device-depth", "8", "--e2e-lists", "16"], capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

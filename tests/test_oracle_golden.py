@@ -111,7 +111,7 @@ def test_oracle_matches_reference_hashes_of_the_realistic_workload(oracle, encod
 
 
 def test_rank_goldens_cover_eight_ranks_and_rank_0_is_the_workload_golden():
-    """tests/golden/rank_golden_hashes.json (make_rank_golden.py): what bench.py --gpus N holds every rank's PCM against.
+    """tests/golden/rank_golden_hashes.json (make_rank_golden.py): what bench.py --full --gpus N holds every rank's PCM against.
     Rank 0's streams are the workload itself, so its hashes must be the committed workload hashes; ranks differ."""
     import json, os
     G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")

@@ -19,6 +19,7 @@ for wl in survey3_65536 dcs94_65536 dcs93_4096 mixed_16384 realistic_65536 corpu
 done
 for wl in survey3_65536 dcs94_65536 dcs93_4096 mixed_16384 realistic_65536 corpus; do
   # (the class surface is timed once, with the default workload's line)
-  python bench.py --workload $wl $([ $wl = survey3_65536 ] || echo --no-class-surface) > $NEW/${TAG}_bench_$wl.json 2> gpurun_out/bench_${TAG}_$wl.err || { echo "bench $wl failed"; tail -5 gpurun_out/bench_${TAG}_$wl.err; exit 1; }
+  ERR=$(dirname $NEW)/bench_${TAG}_$wl.err
+  python bench.py --full --workload $wl $([ $wl = survey3_65536 ] || echo --no-class-surface) > $NEW/${TAG}_bench_$wl.json 2> $ERR || { echo "bench $wl failed"; tail -5 $ERR; exit 1; }
   echo "benched $wl"
 done
