@@ -17,4 +17,5 @@ from .api import (  # noqa: F401
     FMT_94_T0_S3, ENCODE_INFO_DTYPE, EncodeParams, encode_params, encode_bound, encode_header,
     encode93_params, encode93_bound, encode93_header,
     TRANSCODE_COPIED, TRANSCODE_REENCODED, TRANSCODE_REENCODE_ALL, TRANSCODE_INFO_DTYPE, TRANSCODE_OS, transcode_params, transcode_plan,
+    ResampleFilter, RESAMPLE_AT_UNITY, resample_filter_default, resample_count,
 )

@@ -96,6 +96,14 @@ TRANSCODE_INFO_DTYPE = np.dtype([("action", "<i4"), ("srcFrames", "<i4"), ("enc"
 TRANSCODE_OS = {0x9301: 0, 0x9302: 1, 0x9400: 2}
 
 
+# dcs_resample_*: libsamplerate's coefficient layout, and the flag that runs the converter at 31 250 Hz too
+class ResampleFilter(ctypes.Structure):
+    _fields_ = [("coeffs", ctypes.c_void_p), ("nCoeffs", ctypes.c_int32), ("increment", ctypes.c_int32)]
+
+
+RESAMPLE_AT_UNITY = 1
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("format", ctypes.c_int32), ("nFrames", ctypes.c_int32),
                 ("nBands", ctypes.c_int32), ("strideFromBand", ctypes.c_int32), ("profile", ctypes.c_int32),
@@ -150,6 +158,7 @@ EXPORTS = [
     "dcs_encode_params_default", "dcs_encode_bound", "dcs_encode_header", "dcs_encode_streams",
     "dcs_encode93_bound", "dcs_encode93_header", "dcs_encode93_streams",
     "dcs_transcode_plan", "dcs_transcode_streams",
+    "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
 ]
 
 
@@ -433,6 +442,15 @@ def load_library():
     L.dcs_transcode_plan.argtypes = [vp, u32, ctypes.POINTER(EncodeParams), u32, vp, vp]
     L.dcs_transcode_streams.restype = i32
     L.dcs_transcode_streams.argtypes = [vp, vp, u32, ctypes.POINTER(EncodeParams), u32, vp, sz, vp, vp]
+    L.dcs_resample_filter_default.restype = i32
+    L.dcs_resample_filter_default.argtypes = [ctypes.POINTER(ResampleFilter)]
+    L.dcs_resample_count.restype = i32
+    L.dcs_resample_count.argtypes = [ctypes.c_uint64, u32, i32, ctypes.POINTER(ResampleFilter), u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.dcs_resample_streams.restype = i32
+    L.dcs_resample_streams.argtypes = [vp, vp, vp, u32, vp, vp, ctypes.POINTER(ResampleFilter), u32, vp, sz, vp]
+    L.dcs_encode_streams_at.restype = i32
+    L.dcs_encode_streams_at.argtypes = [vp, vp, vp, u32, vp, vp, ctypes.POINTER(ResampleFilter), u32, ctypes.POINTER(EncodeParams),
+                                        vp, sz, vp, vp]
     L.dcs_device_numa_node.restype = ctypes.c_int
     L.dcs_device_numa_node.argtypes = [ctypes.c_int]
     L.dcs_host_threads.restype = ctypes.c_int
@@ -703,6 +721,50 @@ def _encode_input(pcm_list):
     offs = np.zeros(len(parts) + 1, np.uint64)
     offs[1:] = np.cumsum([len(x) for x in parts])
     return (np.concatenate(parts) if parts else np.zeros(1, np.float32)), offs
+
+
+def resample_filter_default():
+    """dcs_resample_filter_default -> (float32 coefficients, increment): the library's own Kaiser-windowed sinc table"""
+    f = ResampleFilter()
+    _check(load_library().dcs_resample_filter_default(ctypes.byref(f)))
+    c = np.ctypeslib.as_array(ctypes.cast(f.coeffs, ctypes.POINTER(ctypes.c_float)), shape=(f.nCoeffs,)).copy()
+    return c, int(f.increment)
+
+
+def _resample_filter(filter):
+    """(ResampleFilter or None, the array it points into): filter = None (the default table) or (coefficients, increment)"""
+    if filter is None:
+        return None, None
+    coeffs, increment = filter
+    c = np.ascontiguousarray(coeffs, dtype=np.float32)
+    return ResampleFilter(c.ctypes.data, len(c), int(increment)), c
+
+
+def _per_stream(v, n, dtype, name):
+    a = np.full(n, v, dtype) if np.ndim(v) == 0 else np.ascontiguousarray(v, dtype=dtype)
+    if len(a) != n:
+        raise ValueError("%d streams, %d %s" % (n, len(a), name))
+    return a if n else np.zeros(1, dtype)
+
+
+def _resample_bound(n_values, rate, channels, at_unity):
+    """at least the resampled length of a stream (host arithmetic, no walk): its mono samples x 31250 / rate and a margin,
+    which the end rule keeps the position chain inside"""
+    m = (n_values + 1) // 2 if channels == 2 else n_values
+    if rate == 31250 and not at_unity:
+        return m
+    return m * 31250 // max(rate, 1) + m // (1 << 20) + 8
+
+
+def resample_count(n_values, rate, channels=1, filter=None, at_unity=False):
+    """dcs_resample_count (host only): the number of 31 250 Hz samples n_values input values (interleaved when
+    channels == 2) at `rate` Hz resample to; filter as Context.resample_streams"""
+    f, keep = _resample_filter(filter)
+    out = ctypes.c_uint64()
+    _check(load_library().dcs_resample_count(int(n_values), int(rate), int(channels), ctypes.byref(f) if f is not None else None,
+                                             RESAMPLE_AT_UNITY if at_unity else 0, ctypes.byref(out)))
+    del keep
+    return int(out.value)
 
 
 def format_os(fmt, prefer_95=False, prefer_93a=False):
@@ -992,6 +1054,51 @@ class Context:
         out = np.zeros(max(cap, 1), np.uint8)
         _check(self.L.dcs_encode93_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info
+
+    def resample_streams(self, pcm_list, rates, channels=1, filter=None, at_unity=False):
+        """dcs_resample_streams: PCM at `rates` Hz (one rate, or one per stream; 4 000 .. 384 000) -> float32 at 31 250 Hz,
+        what the reference's encoder feeds itself.  pcm_list: float32 arrays, or int16 arrays, which are divided by 32768;
+        channels: 1 or 2 (interleaved, averaged), one value or one per stream; filter: None = the library's table, or
+        (float32 coefficients, increment) in libsamplerate's layout; at_unity: run the converter at 31 250 Hz too.
+        Returns a list of float32 arrays."""
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        r, ch = _per_stream(rates, n, np.uint32, "rates"), _per_stream(channels, n, np.int32, "channel counts")
+        f, keep = _resample_filter(filter)
+        flags = RESAMPLE_AT_UNITY if at_unity else 0
+        fp = ctypes.byref(f) if f is not None else None
+        out_offs = np.zeros(n + 1, np.uint64)
+        out = np.zeros(max(sum(_resample_bound(int(offs[i + 1] - offs[i]), int(r[i]), int(ch[i]), at_unity) for i in range(n)), 1),
+                       np.float32)
+        _check(self.L.dcs_resample_streams(self.h, _ptr(pcm), _ptr(offs), n, _ptr(r), _ptr(ch), fp, flags, _ptr(out), out.size,
+                                           _ptr(out_offs)), self.h)
+        del keep
+        return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)]
+
+    def encode_streams_at(self, pcm_list, rates, version=0x9400, fmt=None, channels=1, filter=None, at_unity=False, **params):
+        """dcs_encode_streams_at: resample (as resample_streams), then encode on the device (version 0x9400: fmt as
+        encode_streams; 0x9301 / 0x9302: fmt as encode93_streams), as the reference's EncodeFile does it for float input.
+        Returns (list of bytes, ENCODE_INFO_DTYPE array)."""
+        p = transcode_params(version, fmt, **params)
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        r, ch = _per_stream(rates, n, np.uint32, "rates"), _per_stream(channels, n, np.int32, "channel counts")
+        f, keep = _resample_filter(filter)
+        flags = RESAMPLE_AT_UNITY if at_unity else 0
+        bound = encode_bound if version == 0x9400 else encode93_bound
+        # no walk here: a bound on each stream's resampled length, and the encoder's bound of that (of the longest stream it
+        # takes where the bound passes 65 535 frames: a longer stream is refused before its bytes are placed)
+        cap = 0
+        for i in range(n):
+            m = _resample_bound(int(offs[i + 1] - offs[i]), int(r[i]), int(ch[i]), at_unity)
+            cap += bound(m) or bound(65535 * 240)
+        out = np.zeros(max(cap, 1), np.uint8)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info = np.zeros(max(n, 1), ENCODE_INFO_DTYPE)
+        _check(self.L.dcs_encode_streams_at(self.h, _ptr(pcm), _ptr(offs), n, _ptr(r), _ptr(ch), ctypes.byref(f) if f is not None else None,
+                                            flags, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
+        del keep
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n]
 
     def transcode_streams(self, streams, os_list, version=0x9400, fmt=None, reencode_all=False, volume=0x67, level=0xFF,
                           channel_volume=0xFF, **params):

@@ -1133,11 +1133,13 @@ extern "C" DcsStatus dcs_encode93_header(const float *powerSum, const float *lo,
 
 namespace {
 
-// Where the driver reads its samples: the caller's float PCM on the host (dcs_encode_streams, dcs_encode93_streams), or a
-// decode batch's int16 PCM and error words, resident on the device (dcs_transcode_streams, dcs_transcode.hip.h)
+// Where the driver reads its samples: the caller's float PCM on the host (dcs_encode_streams, dcs_encode93_streams), a
+// decode batch's int16 PCM and error words, resident on the device (dcs_transcode_streams, dcs_transcode.hip.h), or the
+// resampler's float output, resident on the device (dcs_encode_streams_at, dcs_resample.hip.h)
 struct EncInput
 {
     const float *hostPcm = nullptr;
+    const float *devFloat = nullptr;        // stream i starts at sample sampleOffsets[i]
     const int16_t *devPcm = nullptr;        // stream i starts at sample sampleOffsets[i], a multiple of 240 ...
     const uint32_t *devErr = nullptr;       // ... and its frames' error words at sampleOffsets[i] / 240
     const uint32_t *label = nullptr;        // the number a message gives stream i (null: i)
@@ -1155,8 +1157,8 @@ DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets
                         const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info,
                         bool os93, const EncPlace &place = nullptr)
 {
-    const bool dev = in.devPcm != nullptr;
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && in.hostPcm == nullptr && !dev)
+    const bool dev = in.devPcm != nullptr, devF = in.devFloat != nullptr;
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && in.hostPcm == nullptr && !dev && !devF)
         || (dev && in.devErr == nullptr))
         return DCS_ERR_INVALID_ARG;
     if (!paramsValid(params, os93))
@@ -1220,7 +1222,7 @@ DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets
     DcsStatus status = [&]() -> DcsStatus {
         ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
         ENCCHK(alloc(reinterpret_cast<void **>(&dT), sizeof(EncTabs)));
-        if (!dev)
+        if (!dev && !devF)
             ENCCHK(alloc(reinterpret_cast<void **>(&dPcm), sizeof(float) * nSamples));
         ENCCHK(alloc(reinterpret_cast<void **>(&dStr), sizeof(EncStream) * nStreams));
         ENCCHK(alloc(reinterpret_cast<void **>(&dFS), sizeof(uint32_t) * F));
@@ -1249,7 +1251,7 @@ DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets
         ENCCHK(alloc(reinterpret_cast<void **>(&dSize), sizeof(uint64_t) * nStreams));
         ENCCHK(alloc(reinterpret_cast<void **>(&dOutOff), sizeof(uint64_t) * nStreams));
         ENCCHK(hipMemcpyAsync(dT, &tabs, sizeof(EncTabs), hipMemcpyHostToDevice, st));
-        if (!dev)
+        if (!dev && !devF)
             ENCCHK(hipMemcpyAsync(dPcm, in.hostPcm + sampleOffsets[0], sizeof(float) * nSamples, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(EncStream) * nStreams, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dFS, frameStream.data(), sizeof(uint32_t) * F, hipMemcpyHostToDevice, st));
@@ -1259,8 +1261,8 @@ DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets
             hipLaunchKernelGGL(encAnalyseKernel<int16_t>, dim3((F + 3) / 4), dim3(256), 0, st, dT, in.devPcm + sampleOffsets[0], dStr, dFS, F,
                                dSpec, dPw, dLo, dHi, dBad, in.devErr);
         else
-            hipLaunchKernelGGL(encAnalyseKernel<float>, dim3((F + 3) / 4), dim3(256), 0, st, dT, dPcm, dStr, dFS, F, dSpec, dPw, dLo, dHi, dBad,
-                               static_cast<const uint32_t *>(nullptr));
+            hipLaunchKernelGGL(encAnalyseKernel<float>, dim3((F + 3) / 4), dim3(256), 0, st, dT, devF ? in.devFloat + sampleOffsets[0] : dPcm,
+                               dStr, dFS, F, dSpec, dPw, dLo, dHi, dBad, static_cast<const uint32_t *>(nullptr));
         hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, dT, dStr, dPw, dLo, dHi, params->powerBandCutoff,
                            params->targetBitRate, vmask, dHdr, dKeep);
         if (os93)
@@ -1433,3 +1435,7 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
     *unusable = in.unusable;
     return st;
 }
+
+// ------------------------------------------------------------------------------- resampling (dcs_resample.hip.h)
+
+#include "dcs_resample.hip.h"

@@ -1,0 +1,647 @@
+// dcs_resample.hip.h -- the reference's input resampler on the GPU: libsamplerate's sinc converter, mono, at the fixed
+// ratio 31250 / rate (DCSEncoder::OpenStream, DCSEncoder.cpp:165-185; src_sinc.c:280-424 sinc_mono_vari_process and
+// calc_output_single; common.h:147-155 fmod_one), and EncodeFile's stereo downmix (DCSEncodeFile.cpp:81-102).  Included at
+// the end of dcs_encode.hip: it shares that translation unit's floating-point contract (no contraction, f64 and f32 rounded
+// at every step, denormals kept) and hands its output to the encoder's driver where it lies.
+//
+//   R1 stage    rsStageKernel     one thread per mono sample: (L + R) / 2.0f for stereo, a copy for mono; a non-finite value
+//                                 flags its stream
+//   R2 walk     rsWalkKernel      one lane per stream: the serial position chain (input_index += 1 / ratio, fmod_one), the
+//                                 end rule and the 512-sample cap of the end-of-input flush; per output the integer input
+//                                 position and start_filter_index, per stream the count
+//   R3 convolve rsConvolveKernel  one thread per output: the left half, the right half, each summed in f64 in the reference's
+//                                 order, scaled and rounded to f32; the stream's peak |y|
+//
+// Each output's value depends only on the whole input and the output's position.  How many outputs there are depends on the
+// reference's calls as well: the end-of-input call runs once with a 512-float buffer (CloseStream, DCSEncoder.cpp:717-721),
+// and the end rule is an f64 sum in the converter's buffer indices, so the walk replays the buffer's bookkeeping (rsWalk).
+#pragma once
+
+namespace {
+
+const int kRsFlushCap = 512;            // CloseStream's one end-of-input call: WriteStream's outbuf[512]
+const uint32_t kRsMinRate = 4000, kRsMaxRate = 384000;
+
+// what the walk needs of one stream, fixed before it runs (src_sinc.c:359-405)
+struct RsStream
+{
+    uint64_t inOff;         // first mono sample in the staged buffer
+    uint64_t nIn;           // mono samples
+    uint64_t slotOff;       // first slot of its walk records ...
+    uint64_t nSlots;        // ... and their number (rsSlots)
+    uint64_t outOff;        // first output sample (set after the walk)
+    double step;            // 1.0 / ratio
+    double terminate;       // 1.0 / ratio + 1e-20
+    double floatInc;        // increment * min(ratio, 1)
+    int64_t half;           // half_filter_chan_len
+    int32_t increment;      // lrint(floatInc * 4096)
+    int32_t bLen;           // the converter's buffer length (sinc_set_converter)
+    int32_t passThrough;    // rate 31 250 without DCS_RESAMPLE_AT_UNITY: the samples as they are
+};
+
+__host__ __device__ inline double rsFmodOne(double x)
+{
+    const double res = x - rint(x);
+    return res < 0.0 ? res + 1.0 : res;
+}
+
+// The position chain of sinc_mono_vari_process (src_sinc.c:342-413) over the reference encoder's calls: 16 samples per
+// src_process, a 512-float output buffer, then one zero-length end-of-input call (WriteStream / CloseStream,
+// DCSEncoder.cpp:650-721).  sink(k, pos, start_filter_index) per output, with pos the absolute input position; returns the
+// count.  The converter's buffer is restated in its own indices (prepare_data's loads and moves, src_sinc.c:1156-1226):
+// the end rule compares b_current + input_index + terminate with b_real_end there, and that f64 sum rounds by the size of
+// b_current, so absolute positions would keep an extra sample at the end of some whole-second streams.  Indices are 32-bit
+// (f64 <-> i32 are single instructions on the device; streams are shorter than 2^31 samples, rsCheck).
+template <class Sink>
+__host__ __device__ inline uint64_t rsWalk(const RsStream &s, Sink sink)
+{
+    if (s.passThrough)
+    {
+        for (uint64_t k = 0 ; k < s.nIn ; ++k)
+            sink(k, static_cast<int64_t>(k), 0);
+        return s.nIn;
+    }
+    const int32_t n = static_cast<int32_t>(s.nIn), half = static_cast<int32_t>(s.half), bLen = s.bLen;
+    int32_t bCur = 0, bEnd = 0, bRealEnd = -1, fed = 0, pos = 0;
+    double idx = 0.0;
+    uint64_t k = 0;
+    // (bEnd - bCur + bLen) % bLen and (bCur + adv) % bLen for operands in (-bLen, 2 bLen): a compare instead of a division
+    auto inHand = [&]() { const int32_t d = bEnd - bCur; return d < 0 ? d + bLen : d >= bLen ? d - bLen : d; };
+    auto advance = [&]() {
+        const double rem = rsFmodOne(idx);
+        const int32_t adv = static_cast<int32_t>(rint(idx - rem));
+        bCur += adv;
+        bCur = bCur >= bLen ? bCur - bLen : bCur;
+        pos += adv;
+        idx = rem;
+    };
+    while (bRealEnd < 0)
+    {
+        const int32_t inCount = n - fed < 16 ? n - fed : 16;
+        const bool eof = inCount == 0;
+        fed += inCount;
+        int32_t inUsed = 0, outGen = 0;
+        advance();                                          // the call's opening fmod_one (no move: idx is in [0, 1))
+        while (outGen < kRsFlushCap)
+        {
+            if (inHand() <= half)
+            {
+                if (bRealEnd < 0)                           // prepare_data
+                {
+                    int32_t len;
+                    if (bCur == 0)
+                    {
+                        len = bLen - 2 * half;
+                        bCur = bEnd = half;
+                    }
+                    else if (bEnd + half + 1 < bLen)
+                        len = bLen - bCur - half > 0 ? bLen - bCur - half : 0;
+                    else
+                    {
+                        len = bEnd - bCur;
+                        bCur = half;
+                        bEnd = half + len;
+                        len = bLen - bCur - half > 0 ? bLen - bCur - half : 0;
+                    }
+                    len = inCount - inUsed < len ? inCount - inUsed : len;
+                    bEnd += len;
+                    inUsed += len;
+                    if (inUsed == inCount && bEnd - bCur < 2 * half && eof)
+                    {
+                        if (bLen - bEnd < half + 5)
+                        {
+                            len = bEnd - bCur;
+                            bCur = half;
+                            bEnd = half + len;
+                        }
+                        bRealEnd = bEnd;
+                        len = bEnd + half + 5 > bLen ? bLen - bEnd : half + 5;
+                        bEnd += len;
+                    }
+                }
+                if (inHand() <= half)
+                    break;
+            }
+            if (bRealEnd >= 0 && static_cast<double>(bCur) + idx + s.terminate > static_cast<double>(bRealEnd))
+                break;
+            sink(k, pos, static_cast<int32_t>(rint(idx * s.floatInc * 4096.0)));
+            ++k;
+            ++outGen;
+            idx += s.step;
+            advance();
+        }
+    }
+    return k;
+}
+
+// walk records the stream may fill (none for a pass-through): the end rule keeps pos + 1 / ratio <= n, so k <= n * ratio;
+// the margin covers the chain's rounding
+uint64_t rsSlots(const RsStream &s)
+{
+    return s.passThrough ? 0 : static_cast<uint64_t>(static_cast<double>(s.nIn) / s.step) + 4;
+}
+
+bool rsFilterValid(const DcsResampleFilter *f)
+{
+    if (f == nullptr || f->coeffs == nullptr || f->increment < 1 || f->increment > (1 << 18) || f->nCoeffs < 3)
+        return false;
+    // sinc_set_converter's check (src_sinc.c:229-234), and what keeps int_to_fp (coeff_half_len) and the first tap's
+    // coeff_count in range: a half length below 2^19 and at least one input sample wide
+    const int32_t half = f->nCoeffs - 2;
+    int32_t count = half, bits = 0;
+    for (bits = 0 ; (int32_t(1) << bits) < count ; bits++)
+        count |= int32_t(1) << bits;
+    if (bits + 12 - 1 >= 32 || half >= (1 << 19) || half < f->increment)
+        return false;
+    for (int32_t i = 0 ; i < f->nCoeffs ; ++i)
+        if (!isfinite(f->coeffs[i]))
+            return false;
+    return true;
+}
+
+// the fixed quantities of one stream (mono samples nIn at `rate`)
+RsStream rsStreamOf(uint64_t nIn, uint32_t rate, const DcsResampleFilter &f, uint32_t flags)
+{
+    RsStream s{};
+    s.nIn = nIn;
+    s.passThrough = rate == 31250 && (flags & DCS_RESAMPLE_AT_UNITY) == 0;
+    const double ratio = 31250.0 / static_cast<double>(rate);
+    double count = (f.nCoeffs - 2 + 2.0) / f.increment;
+    if (ratio < 1.0)
+        count /= ratio;
+    s.half = static_cast<int64_t>(lrint(count)) + 1;
+    s.step = 1.0 / ratio;
+    s.terminate = 1.0 / ratio + 1e-20;
+    s.floatInc = f.increment * (ratio < 1.0 ? ratio : 1.0);
+    s.increment = static_cast<int32_t>(lrint(s.floatInc * 4096.0));
+    // src_sinc.c:215-217: lrint(2.5 * coeff_half_len / index_inc * SRC_MAX_RATIO), at least 4096, times the channels (1)
+    const int32_t bLen = static_cast<int32_t>(lrint(2.5 * (f.nCoeffs - 2) / (f.increment * 1.0) * 256));
+    s.bLen = bLen > 4096 ? bLen : 4096;
+    return s;
+}
+
+uint64_t rsMonoLength(uint64_t nValues, int32_t channels) { return channels == 2 ? (nValues + 1) / 2 : nValues; }
+
+// R1: blockIdx.y strides over the streams, the x dimension over a stream's mono samples
+__global__ __launch_bounds__(256) void rsStageKernel(const float *__restrict__ in, const uint64_t *__restrict__ inOffsets,
+                                                     const int32_t *__restrict__ channels, const RsStream *__restrict__ streams,
+                                                     uint32_t nStreams, float *__restrict__ mono, uint32_t *__restrict__ bad)
+{
+    for (uint32_t si = blockIdx.y ; si < nStreams ; si += gridDim.y)
+    {
+        const RsStream &s = streams[si];
+        const uint64_t base = inOffsets[si] - inOffsets[0], nValues = inOffsets[si + 1] - inOffsets[si];
+        const bool stereo = channels[si] == 2;
+        bool isBad = false;
+        for (uint64_t j = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x ; j < s.nIn ; j += uint64_t(gridDim.x) * blockDim.x)
+        {
+            float x;
+            if (stereo && 2 * j + 1 < nValues)
+                x = (in[base + 2 * j] + in[base + 2 * j + 1]) / 2.0f;
+            else
+                x = in[base + (stereo ? 2 * j : j)];
+            if (!isfinite(x))
+                isBad = true;
+            mono[s.inOff + j] = x;
+        }
+        if (isBad)
+            atomicOr(&bad[si], 1u);
+    }
+}
+
+// R2: one lane per stream; out-of-range lanes do nothing
+__global__ __launch_bounds__(64) void rsWalkKernel(const RsStream *__restrict__ streams, uint32_t nStreams, int2 *__restrict__ slots,
+                                                   uint64_t *__restrict__ counts)
+{
+    const uint32_t si = blockIdx.x * blockDim.x + threadIdx.x;
+    if (si >= nStreams)
+        return;
+    const RsStream s = streams[si];
+    if (s.passThrough)
+    {
+        counts[si] = s.nIn;
+        return;
+    }
+    int2 *dst = slots + s.slotOff;
+    // (rsSlots bounds the count; the guard keeps a stream that broke the bound inside its own records, and the host refuses it)
+    const uint64_t count = rsWalk(s, [&](uint64_t k, int64_t pos, int32_t sfi) {
+        if (k < s.nSlots)
+            dst[k] = make_int2(static_cast<int32_t>(pos), sfi);
+    });
+    counts[si] = count;
+}
+
+// One output of calc_output_single (src_sinc.c:280-333): coefficient i + fraction * (coefficient i+1 - i), the difference a
+// float subtraction, each half summed in f64 in the loop's order, then left + right.  x: the stream's mono samples, zero
+// outside [0, n).
+__device__ inline double rsOutput(const float *__restrict__ c, int32_t maxFilterIndex, int32_t increment, int32_t sfi,
+                                  const float *__restrict__ x, int64_t n, int64_t pos)
+{
+    int32_t fi = sfi;
+    int32_t cc = (maxFilterIndex - fi) / increment;
+    fi = fi + cc * increment;
+    int64_t d = pos - cc;
+    double left = 0.0;
+    do
+    {
+        const double fraction = static_cast<double>(fi & 4095) * (1.0 / 4096.0);
+        const int32_t indx = fi >> 12;
+        const float c0 = c[indx], c1 = c[indx + 1];
+        const double icoeff = static_cast<double>(c0) + fraction * static_cast<double>(c1 - c0);
+        const float v = (d >= 0 && d < n) ? x[d] : 0.0f;
+        left += icoeff * static_cast<double>(v);
+        fi -= increment;
+        ++d;
+    } while (fi >= 0);
+
+    fi = increment - sfi;
+    cc = (maxFilterIndex - fi) / increment;
+    fi = fi + cc * increment;
+    d = pos + 1 + cc;
+    double right = 0.0;
+    do
+    {
+        const double fraction = static_cast<double>(fi & 4095) * (1.0 / 4096.0);
+        const int32_t indx = fi >> 12;
+        const float c0 = c[indx], c1 = c[indx + 1];
+        const double icoeff = static_cast<double>(c0) + fraction * static_cast<double>(c1 - c0);
+        const float v = (d >= 0 && d < n) ? x[d] : 0.0f;
+        right += icoeff * static_cast<double>(v);
+        fi -= increment;
+        --d;
+    } while (fi > 0);
+    return left + right;
+}
+
+// R3: blockIdx.y strides over the streams, x over a stream's outputs.  LDS: the table is copied to LDS once per block
+// (tables up to kRsLdsMaxCoeffs); otherwise it is read through the caches.
+const int32_t kRsLdsMaxCoeffs = 16384;          // 64 KiB
+template <bool LDS>
+__global__ __launch_bounds__(256) void rsConvolveKernel(const float *__restrict__ coeffs, int32_t nCoeffs, int32_t tableInc,
+                                                        const RsStream *__restrict__ streams, uint32_t nStreams,
+                                                        const uint64_t *__restrict__ counts, const int2 *__restrict__ slots,
+                                                        const float *__restrict__ mono, float *__restrict__ out,
+                                                        uint32_t *__restrict__ peak)
+{
+    extern __shared__ float ldsCoeffs[];
+    const float *c = coeffs;
+    if constexpr (LDS)
+    {
+        for (int32_t i = threadIdx.x ; i < nCoeffs ; i += blockDim.x)
+            ldsCoeffs[i] = coeffs[i];
+        __syncthreads();
+        c = ldsCoeffs;
+    }
+    const int32_t maxFilterIndex = (nCoeffs - 2) << 12;
+    for (uint32_t si = blockIdx.y ; si < nStreams ; si += gridDim.y)
+    {
+        const RsStream &s = streams[si];
+        const uint64_t count = counts[si];
+        const float *x = mono + s.inOff;
+        const int64_t n = static_cast<int64_t>(s.nIn);
+        uint32_t top = 0;
+        for (uint64_t k = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x ; k < count ; k += uint64_t(gridDim.x) * blockDim.x)
+        {
+            float y;
+            if (s.passThrough)
+                y = x[k];
+            else
+            {
+                const int2 r = slots[s.slotOff + k];
+                y = static_cast<float>((s.floatInc / tableInc) * rsOutput(c, maxFilterIndex, s.increment, r.y, x, n, r.x));
+            }
+            out[s.outOff + k] = y;
+            const uint32_t b = __float_as_uint(fabsf(y));
+            top = b > top ? b : top;
+        }
+        if (top != 0)
+            atomicMax(&peak[si], top);
+    }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------- host side
+
+namespace {
+
+// The library's own table (dcs_resample_filter_default), in libsamplerate's layout: coeffs[i] = h(i / 128) for a
+// Kaiser-windowed sinc h(t) = fc sinc(fc t) w(t / 48), fc = 0.91 of the input Nyquist, beta = 11, zero from t = 48 on.
+// Computed once in f64 and rounded to f32.
+const int32_t kRsDefaultIncrement = 128, kRsDefaultHalfWidth = 48;
+const double kRsDefaultCutoff = 0.91, kRsDefaultBeta = 11.0;
+
+double rsBesselI0(double x)
+{
+    double sum = 1.0, term = 1.0;
+    for (int k = 1 ; k < 200 ; ++k)
+    {
+        const double q = x / (2.0 * k);
+        term *= q * q;
+        sum += term;
+        if (term < sum * 1e-18)
+            break;
+    }
+    return sum;
+}
+
+const std::vector<float> &rsDefaultTable()
+{
+    static const std::vector<float> table = [] {
+        const int32_t half = kRsDefaultIncrement * kRsDefaultHalfWidth;
+        std::vector<float> c(static_cast<size_t>(half) + 2, 0.0f);
+        const double i0b = rsBesselI0(kRsDefaultBeta), pi = 3.14159265358979323846;
+        for (int32_t i = 0 ; i < half ; ++i)
+        {
+            const double t = static_cast<double>(i) / kRsDefaultIncrement, x = kRsDefaultCutoff * t;
+            const double sinc = i == 0 ? 1.0 : sin(pi * x) / (pi * x);
+            const double r = t / kRsDefaultHalfWidth;
+            const double w = rsBesselI0(kRsDefaultBeta * sqrt(1.0 - r * r)) / i0b;
+            c[static_cast<size_t>(i)] = static_cast<float>(kRsDefaultCutoff * sinc * w);
+        }
+        return c;
+    }();
+    return table;
+}
+
+DcsResampleFilter rsDefaultFilter()
+{
+    const std::vector<float> &t = rsDefaultTable();
+    return DcsResampleFilter{ t.data(), static_cast<int32_t>(t.size()), kRsDefaultIncrement };
+}
+
+// the checks every entry point shares: the filter (null = the default), flags, rate, channels; why = the message
+DcsStatus rsCheck(uint32_t n, const uint64_t *sampleOffsets, const uint32_t *rates, const int32_t *channels,
+                  const DcsResampleFilter *filter, uint32_t flags, DcsResampleFilter &f, std::string &why)
+{
+    if ((flags & ~DCS_RESAMPLE_AT_UNITY) != 0)
+    {
+        why = "unknown flags";
+        return DCS_ERR_INVALID_ARG;
+    }
+    f = filter != nullptr ? *filter : rsDefaultFilter();
+    if (!rsFilterValid(&f))
+    {
+        why = "filter: not a valid libsamplerate table (increment >= 1, increment <= nCoeffs - 2 < 2^19, finite coefficients)";
+        return DCS_ERR_INVALID_ARG;
+    }
+    for (uint32_t i = 0 ; i < n ; ++i)
+    {
+        const std::string name = "stream " + std::to_string(i);
+        if (rates[i] < kRsMinRate || rates[i] > kRsMaxRate)
+        {
+            why = name + ": rate " + std::to_string(rates[i]) + " Hz is outside 4 000 .. 384 000";
+            return DCS_ERR_INVALID_ARG;
+        }
+        const int32_t ch = channels != nullptr ? channels[i] : 1;
+        if (ch != 1 && ch != 2)
+        {
+            why = name + ": " + std::to_string(ch) + " channels (1 or 2)";
+            return DCS_ERR_INVALID_ARG;
+        }
+        if (sampleOffsets[i + 1] <= sampleOffsets[i])
+        {
+            why = name + ": empty";
+            return DCS_ERR_INVALID_ARG;
+        }
+        if (rsMonoLength(sampleOffsets[i + 1] - sampleOffsets[i], ch) >= (uint64_t(1) << 31))
+        {
+            why = name + ": 2^31 samples or more";
+            return DCS_ERR_INVALID_ARG;
+        }
+    }
+    return DCS_OK;
+}
+
+// The converter on the device: stage, walk, counts back, convolve.  On DCS_OK, *dOut holds the outputs (stream i from
+// outOffsets[i], outOffsets[n] in all) and peak[i] the bits of the stream's largest |y|; the buffers belong to `held`.
+DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t n, const uint32_t *rates,
+                           const int32_t *channels, const DcsResampleFilter &f, uint32_t flags, std::vector<CacheBuf> &held,
+                           float **dOut, uint64_t *outOffsets, std::vector<uint32_t> &peak)
+{
+    std::vector<RsStream> hs(n);
+    std::vector<int32_t> ch(n);
+    std::vector<uint64_t> counts(n);
+    std::vector<uint32_t> bad(n);
+    uint64_t nMono = 0, nSlots = 0, maxMono = 0;
+    for (uint32_t i = 0 ; i < n ; ++i)
+    {
+        ch[i] = channels != nullptr ? channels[i] : 1;
+        const uint64_t m = rsMonoLength(sampleOffsets[i + 1] - sampleOffsets[i], ch[i]);
+        hs[i] = rsStreamOf(m, rates[i], f, flags);
+        hs[i].inOff = nMono;
+        hs[i].slotOff = nSlots;
+        hs[i].nSlots = rsSlots(hs[i]);
+        nMono += m;
+        nSlots += hs[i].nSlots;
+        maxMono = m > maxMono ? m : maxMono;
+    }
+    const uint64_t nValues = sampleOffsets[n] - sampleOffsets[0];
+    const hipStream_t st = dcsCtxStream(ctx);
+    auto alloc = [&](void **p, size_t bytes) -> hipError_t {
+        held.emplace_back();
+        const hipError_t e = held.back().alloc(ctx, false, (bytes + 255) & ~size_t(255));
+        *p = held.back().as();
+        return e;
+    };
+    float *dIn, *dMono, *dCoeffs, *dRes;
+    uint64_t *dInOff, *dCounts;
+    int32_t *dCh;
+    RsStream *dStr;
+    uint32_t *dBad, *dPeak;
+    int2 *dSlots;
+    ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dIn), sizeof(float) * nValues));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dMono), sizeof(float) * nMono));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dCoeffs), sizeof(float) * f.nCoeffs));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dInOff), sizeof(uint64_t) * (n + 1)));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dCounts), sizeof(uint64_t) * n));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dCh), sizeof(int32_t) * n));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dStr), sizeof(RsStream) * n));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dBad), sizeof(uint32_t) * n));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dPeak), sizeof(uint32_t) * n));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dSlots), sizeof(int2) * (nSlots ? nSlots : 1)));
+    ENCCHK(hipMemcpyAsync(dIn, pcm + sampleOffsets[0], sizeof(float) * nValues, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dCoeffs, f.coeffs, sizeof(float) * f.nCoeffs, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dInOff, sampleOffsets, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dCh, ch.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * n, st));
+    ENCCHK(hipMemsetAsync(dPeak, 0, sizeof(uint32_t) * n, st));
+    const unsigned gy = n < 65535 ? n : 65535;
+    const uint64_t stageBlocks = (maxMono + 255) / 256;
+    hipLaunchKernelGGL(rsStageKernel, dim3(static_cast<unsigned>(stageBlocks < 1024 ? stageBlocks : 1024), gy), dim3(256), 0, st,
+                       dIn, dInOff, dCh, dStr, n, dMono, dBad);
+    hipLaunchKernelGGL(rsWalkKernel, dim3((n + 63) / 64), dim3(64), 0, st, dStr, n, dSlots, dCounts);
+    ENCCHK(hipGetLastError());
+    ENCCHK(hipMemcpyAsync(counts.data(), dCounts, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipMemcpyAsync(bad.data(), dBad, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipStreamSynchronize(st));
+    for (uint32_t i = 0 ; i < n ; ++i)
+        if (bad[i])
+        {
+            dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": an input sample (or a stereo pair's mean) is not finite").c_str());
+            return DCS_ERR_BAD_STREAM;
+        }
+    for (uint32_t i = 0 ; i < n ; ++i)
+        if (!hs[i].passThrough && counts[i] > hs[i].nSlots)
+        {
+            // a defect of this library, not of the input: the walk made more outputs than rsSlots allows (nothing is truncated)
+            dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": internal error: the resampler's walk made " + std::to_string(counts[i])
+                                 + " outputs, more than its bound " + std::to_string(hs[i].nSlots)).c_str());
+            return DCS_ERR_HIP;
+        }
+    outOffsets[0] = 0;
+    uint64_t maxCount = 0;
+    for (uint32_t i = 0 ; i < n ; ++i)
+    {
+        hs[i].outOff = outOffsets[i];
+        outOffsets[i + 1] = outOffsets[i] + counts[i];
+        maxCount = counts[i] > maxCount ? counts[i] : maxCount;
+    }
+    ENCCHK(alloc(reinterpret_cast<void **>(&dRes), sizeof(float) * (outOffsets[n] ? outOffsets[n] : 1)));
+    ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
+    // about 4 096 blocks in all: each block of the LDS variant copies the table once and then strides over its outputs
+    const uint64_t want = (maxCount + 255) / 256, perStream = (4096 + gy - 1) / gy;
+    const unsigned gx = static_cast<unsigned>(want < 1 ? 1 : want < perStream ? want : perStream);
+    if (f.nCoeffs <= kRsLdsMaxCoeffs)
+        hipLaunchKernelGGL(rsConvolveKernel<true>, dim3(gx, gy), dim3(256), sizeof(float) * f.nCoeffs, st, dCoeffs, f.nCoeffs,
+                           f.increment, dStr, n, dCounts, dSlots, dMono, dRes, dPeak);
+    else
+        hipLaunchKernelGGL(rsConvolveKernel<false>, dim3(gx, gy), dim3(256), 0, st, dCoeffs, f.nCoeffs, f.increment, dStr, n,
+                           dCounts, dSlots, dMono, dRes, dPeak);
+    ENCCHK(hipGetLastError());
+    peak.assign(n, 0);
+    ENCCHK(hipMemcpyAsync(peak.data(), dPeak, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipStreamSynchronize(st));
+    *dOut = dRes;
+    return DCS_OK;
+}
+
+float fromBitsU(uint32_t b) { float x; memcpy(&x, &b, 4); return x; }
+
+}  // namespace
+
+extern "C" DcsStatus dcs_resample_filter_default(DcsResampleFilter *filter)
+{
+    if (filter == nullptr)
+        return DCS_ERR_INVALID_ARG;
+    *filter = rsDefaultFilter();
+    return DCS_OK;
+}
+
+extern "C" DcsStatus dcs_resample_count(uint64_t nValues, uint32_t rate, int32_t channels, const DcsResampleFilter *filter,
+                                        uint32_t flags, uint64_t *countOut)
+{
+    if (countOut == nullptr)
+        return DCS_ERR_INVALID_ARG;
+    const uint64_t offs[2] = { 0, nValues };
+    DcsResampleFilter f;
+    std::string why;
+    const DcsStatus st = rsCheck(1, offs, &rate, &channels, filter, flags, f, why);
+    if (st != DCS_OK)
+        return st;
+    *countOut = rsWalk(rsStreamOf(rsMonoLength(nValues, channels), rate, f, flags), [](uint64_t, int64_t, int32_t) {});
+    return DCS_OK;
+}
+
+extern "C" DcsStatus dcs_resample_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                          const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                                          uint32_t flags, float *out, size_t outCap, uint64_t *outOffsets)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
+        return DCS_ERR_INVALID_ARG;
+    DcsResampleFilter f;
+    std::string why;
+    DcsStatus status = rsCheck(nStreams, sampleOffsets, rates, channels, filter, flags, f, why);
+    if (status != DCS_OK)
+    {
+        dcsCtxSetError(ctx, why.c_str());
+        return status;
+    }
+    outOffsets[0] = 0;
+    if (nStreams == 0)
+        return DCS_OK;
+    const hipStream_t st = dcsCtxStream(ctx);
+    std::vector<CacheBuf> held;
+    status = [&]() -> DcsStatus {
+        float *dRes = nullptr;
+        std::vector<uint32_t> peak;
+        const DcsStatus s = resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, outOffsets, peak);
+        if (s != DCS_OK)
+            return s;
+        if (out == nullptr || outCap < outOffsets[nStreams])
+            return DCS_ERR_CAPACITY;
+        ENCCHK(hipMemcpyAsync(out, dRes, sizeof(float) * outOffsets[nStreams], hipMemcpyDeviceToHost, st));
+        ENCCHK(hipStreamSynchronize(st));
+        return DCS_OK;
+    }();
+    (void)hipStreamSynchronize(st);
+    for (CacheBuf &h : held)
+        h.release();
+    return status;
+}
+
+extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                           const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                                           uint32_t flags, const DcsEncodeParams *params, uint8_t *out, size_t outCap,
+                                           uint64_t *outOffsets, DcsEncodeInfo *info)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
+        return DCS_ERR_INVALID_ARG;
+    const bool os93 = params != nullptr && params->formatVersion != 0x9400;
+    if (!paramsValid(params, os93))
+    {
+        if (os93 && params->formatVersion == 0x9301 && params->streamFormatType == 1)
+            dcsCtxSetError(ctx, "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0");
+        return DCS_ERR_INVALID_ARG;
+    }
+    DcsResampleFilter f;
+    std::string why;
+    DcsStatus status = rsCheck(nStreams, sampleOffsets, rates, channels, filter, flags, f, why);
+    if (status != DCS_OK)
+    {
+        dcsCtxSetError(ctx, why.c_str());
+        return status;
+    }
+    if (nStreams == 0)
+    {
+        outOffsets[0] = 0;
+        return DCS_OK;
+    }
+    const hipStream_t st = dcsCtxStream(ctx);
+    std::vector<CacheBuf> held;
+    status = [&]() -> DcsStatus {
+        float *dRes = nullptr;
+        std::vector<uint32_t> peak;
+        std::vector<uint64_t> resOffsets(static_cast<size_t>(nStreams) + 1);
+        DcsStatus s = resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, resOffsets.data(), peak);
+        if (s != DCS_OK)
+            return s;
+        for (uint32_t i = 0 ; i < nStreams ; ++i)
+        {
+            const std::string name = "stream " + std::to_string(i);
+            const uint64_t m = resOffsets[i + 1] - resOffsets[i];
+            if (m == 0 || (m + 239) / 240 > 65535)
+            {
+                dcsCtxSetError(ctx, (name + (m == 0 ? ": resamples to no samples" : ": resamples to more than 65 535 frames")).c_str());
+                return DCS_ERR_INVALID_ARG;
+            }
+            if (peak[i] > 0x3f800000u)          // |y| > 1, or not a number
+            {
+                char text[160];
+                snprintf(text, sizeof(text), "%s: the resampled signal peaks at |x| = %.9g, outside [-1, 1] (attenuate the input)",
+                         name.c_str(), static_cast<double>(fromBitsU(peak[i])));
+                dcsCtxSetError(ctx, text);
+                return DCS_ERR_BAD_STREAM;
+            }
+        }
+        EncInput in;
+        in.devFloat = dRes;
+        return encodeStreams(ctx, in, resOffsets.data(), nStreams, params, out, outCap, outOffsets, info, os93);
+    }();
+    (void)hipStreamSynchronize(st);
+    for (CacheBuf &h : held)
+        h.release();
+    return status;
+}

@@ -36,7 +36,9 @@ extern "C" {
                                           (DcsEncodeParams, DcsEncodeInfo, dcs_encode_params_default, dcs_encode_bound,
                                           dcs_encode_header, dcs_encode_streams); the OS93 encoder (dcs_encode93_bound,
                                           dcs_encode93_header, dcs_encode93_streams); transcoding (DcsTranscodeInfo,
-                                          dcs_transcode_plan, dcs_transcode_streams) */
+                                          dcs_transcode_plan, dcs_transcode_streams); resampling (DcsResampleFilter,
+                                          DCS_RESAMPLE_AT_UNITY, dcs_resample_filter_default, dcs_resample_count,
+                                          dcs_resample_streams, dcs_encode_streams_at) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -856,6 +858,52 @@ DcsStatus dcs_transcode_plan(const DcsStreamRef *src, uint32_t nStreams, const D
 /* Stream i is written to out + outOffsets[i], in input order; info (optional) = nStreams records. */
 DcsStatus dcs_transcode_streams(DcsCtx *ctx, const DcsStreamRef *src, uint32_t nStreams, const DcsEncodeParams *target,
                                 uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsTranscodeInfo *info);
+
+/* ------------------------------------------------------------------------------------------------
+ * Resampling: PCM at any rate from 4 000 to 384 000 Hz, mono or interleaved stereo -> mono float PCM at 31 250 Hz, bit for
+ * bit what the reference's encoder feeds itself (DCSEncoder::EncodeFile, DCSEncodeFile.cpp:81-102: the channels' mean
+ * (L + R) / 2.0f, a final unpaired value alone; OpenStream(rate) / WriteStream / CloseStream, DCSEncoder.cpp:165-185,
+ * :650-721: libsamplerate's sinc converter at the ratio 31250.0 / rate, src_sinc.c:280-424) when it is given the same
+ * filter table.  The reference uses libsamplerate's SRC_SINC_BEST_QUALITY table, which this library does not ship:
+ * a NULL filter means the library's own table (dcs_resample_filter_default); a caller that has the reference's table
+ * passes it in ("Resampling").  A rate of 31 250 is a pass-through (the encoders' contract) unless
+ * DCS_RESAMPLE_AT_UNITY asks for the converter at ratio 1, as the reference runs it.
+ */
+typedef struct DcsResampleFilter       /* libsamplerate's coefficient layout (src_sinc.c, *_coeffs.h)                     */
+{
+    const float *coeffs;               /* the right half of the prototype, coeffs[i] = h(i / increment) ...               */
+    int32_t nCoeffs;                   /* ... i = 0 .. nCoeffs - 1; coeff_half_len = nCoeffs - 2                          */
+    int32_t increment;                 /* table entries per input sample: 1 <= increment <= nCoeffs - 2 < 2^19           */
+} DcsResampleFilter;
+
+#define DCS_RESAMPLE_AT_UNITY 1u       /* flags: run the converter at 31 250 Hz too (default: the samples as they are)    */
+
+/* the library's own table: a Kaiser-windowed sinc, increment 128, 48 input samples each side; the
+ * coefficients are the library's and live as long as it is loaded */
+DcsStatus dcs_resample_filter_default(DcsResampleFilter *filter);
+/* host only: the exact number of 31 250 Hz samples nValues input values (interleaved when channels == 2) resample to.
+ * filter NULL = the default.  DCS_ERR_INVALID_ARG: rate outside 4 000 .. 384 000, channels not 1 or 2, nValues 0, an
+ * invalid filter, unknown flags. */
+DcsStatus dcs_resample_count(uint64_t nValues, uint32_t rate, int32_t channels, const DcsResampleFilter *filter,
+                             uint32_t flags, uint64_t *countOut);
+/* The converter on its own, on the GPU.  Stream i is pcm[sampleOffsets[i] .. sampleOffsets[i+1]) at rates[i] Hz with
+ * channels[i] (1 or 2; channels NULL = all mono) channels; its outputs land at out + outOffsets[i] (outOffsets[nStreams]
+ * in all; a stream may resample to no samples).  DCS_ERR_CAPACITY: outCap (floats) is too small; outOffsets is filled all
+ * the same.  DCS_ERR_BAD_STREAM: an input value, or a stereo pair's mean, is not finite.  (DCS_ERR_HIP also reports an
+ * internal inconsistency of the resampler, named in dcs_last_error, rather than return a short stream.)  Errors name the stream in
+ * dcs_last_error.  Outputs are not clipped: the converter can overshoot a full-scale input. */
+DcsStatus dcs_resample_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                               const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                               uint32_t flags, float *out, size_t outCap, uint64_t *outOffsets);
+/* Resample, then encode on the device with params (formatVersion 0x9400: dcs_encode_streams; 0x9301 / 0x9302:
+ * dcs_encode93_streams): the reference's EncodeFile for float input.  The encoders' rules apply to the resampled signal:
+ * a stream that resamples to no samples or to more than 65 535 frames is DCS_ERR_INVALID_ARG, one whose resampled signal
+ * leaves [-1, 1] is DCS_ERR_BAD_STREAM (dcs_last_error names the stream and its peak: attenuate loud input, nothing is
+ * clipped).  The capacity protocol is dcs_encode_streams': dcs_encode_bound of dcs_resample_count per stream is enough. */
+DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                                uint32_t flags, const DcsEncodeParams *params, uint8_t *out, size_t outCap,
+                                uint64_t *outOffsets, DcsEncodeInfo *info);
 
 uint32_t dcs_abi_version(void);
 /* a digest of the sources and compiler flags this library was built from (16 hex digits).  Counter profiles under
