@@ -104,6 +104,23 @@ class ResampleFilter(ctypes.Structure):
 RESAMPLE_AT_UNITY = 1
 
 
+# dcs_wav_parse / dcs_encode_files: the reader's record of one WAV file, and what each file became
+class WavInfo(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("formatCode", ctypes.c_int32), ("sampleFormat", ctypes.c_int32),
+                ("bitDepth", ctypes.c_int32), ("channels", ctypes.c_int32), ("rate", ctypes.c_uint32),
+                ("blockAlign", ctypes.c_int32), ("reserved", ctypes.c_int32), ("dataOffset", ctypes.c_uint64),
+                ("dataSize", ctypes.c_uint64), ("nValues", ctypes.c_uint64), ("nBlocks", ctypes.c_uint64),
+                ("reason", ctypes.c_char * 96)]
+
+
+WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32, WAV_F64, WAV_IMA = range(7)
+FILE_WAV, FILE_DCSA_COPY, FILE_DCSA_REENCODE = 0, 1, 2
+FILE_WALK_NONE, FILE_WALK_DEVICE, FILE_WALK_HOST = 0, 1, 2
+ENCODE_FILE_INFO_DTYPE = np.dtype([("kind", "<i4"), ("sourceFormat", "<i4"), ("rate", "<u4"), ("channels", "<i4"),
+                                   ("nValues", "<u8"), ("nSamples", "<u8"), ("walk", "<i4"), ("srcFrames", "<i4"),
+                                   ("enc", ENCODE_INFO_DTYPE)], align=True)
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("format", ctypes.c_int32), ("nFrames", ctypes.c_int32),
                 ("nBands", ctypes.c_int32), ("strideFromBand", ctypes.c_int32), ("profile", ctypes.c_int32),
@@ -159,6 +176,7 @@ EXPORTS = [
     "dcs_encode93_bound", "dcs_encode93_header", "dcs_encode93_streams",
     "dcs_transcode_plan", "dcs_transcode_streams",
     "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
+    "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
 ]
 
 
@@ -451,6 +469,15 @@ def load_library():
     L.dcs_encode_streams_at.restype = i32
     L.dcs_encode_streams_at.argtypes = [vp, vp, vp, u32, vp, vp, ctypes.POINTER(ResampleFilter), u32, ctypes.POINTER(EncodeParams),
                                         vp, sz, vp, vp]
+    L.dcs_wav_parse.restype = i32
+    L.dcs_wav_parse.argtypes = [vp, sz, ctypes.POINTER(WavInfo)]
+    L.dcs_encode_files_plan.restype = i32
+    L.dcs_encode_files_plan.argtypes = [vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32, vp, vp, vp]
+    L.dcs_wav_decode.restype = i32
+    L.dcs_wav_decode.argtypes = [vp, vp, vp, u32, vp, sz, vp]
+    L.dcs_encode_files.restype = i32
+    L.dcs_encode_files.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32, vp, sz,
+                                   vp, vp]
     L.dcs_device_numa_node.restype = ctypes.c_int
     L.dcs_device_numa_node.argtypes = [ctypes.c_int]
     L.dcs_host_threads.restype = ctypes.c_int
@@ -765,6 +792,45 @@ def resample_count(n_values, rate, channels=1, filter=None, at_unity=False):
                                              RESAMPLE_AT_UNITY if at_unity else 0, ctypes.byref(out)))
     del keep
     return int(out.value)
+
+
+def _files_blob(files):
+    """files (bytes, or paths) -> (uint8 blob, uint64 offsets)"""
+    parts = []
+    for f in files:
+        if isinstance(f, (str, os.PathLike)):
+            with open(f, "rb") as fh:
+                f = fh.read()
+        parts.append(np.frombuffer(bytes(f), dtype=np.uint8))
+    offs = np.zeros(len(parts) + 1, np.uint64)
+    offs[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+    blob = np.concatenate(parts) if parts and offs[-1] else np.zeros(1, np.uint8)
+    return blob, offs
+
+
+def wav_parse(data):
+    """dcs_wav_parse (host only): one WAV file as libnyquist's WavDecoder reads it -> dict of the WavInfo fields (status 0 =
+    accepted; otherwise the DcsStatus and `reason`)"""
+    b = bytes(data)
+    buf = np.frombuffer(b, dtype=np.uint8) if b else np.zeros(1, np.uint8)
+    w = WavInfo()
+    load_library().dcs_wav_parse(_ptr(buf), len(b), ctypes.byref(w))
+    d = {k: getattr(w, k) for k, _ in WavInfo._fields_ if k != "reserved"}
+    d["reason"] = w.reason.decode()
+    return d
+
+
+def encode_files_plan(files, version=0x9400, fmt=None, filter=None, at_unity=False, **params):
+    """dcs_encode_files_plan (host only): -> (kind per file, FILE_* or -1; the bytes its output can take; DcsStatus per file)"""
+    p = transcode_params(version, fmt, **params)
+    blob, offs = _files_blob(files)
+    n = len(offs) - 1
+    f, keep = _resample_filter(filter)
+    kind, bound, status = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.int32)
+    load_library().dcs_encode_files_plan(_ptr(blob), _ptr(offs), n, ctypes.byref(p), ctypes.byref(f) if f is not None else None,
+                                         RESAMPLE_AT_UNITY if at_unity else 0, _ptr(kind), _ptr(bound), _ptr(status))
+    del keep
+    return kind[:n], bound[:n], status[:n]
 
 
 def format_os(fmt, prefer_95=False, prefer_93a=False):
@@ -1097,6 +1163,42 @@ class Context:
         info = np.zeros(max(n, 1), ENCODE_INFO_DTYPE)
         _check(self.L.dcs_encode_streams_at(self.h, _ptr(pcm), _ptr(offs), n, _ptr(r), _ptr(ch), ctypes.byref(f) if f is not None else None,
                                             flags, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
+        del keep
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n]
+
+    def wav_decode(self, files):
+        """dcs_wav_decode: WAV files (bytes or paths) -> list of mono float32 arrays at each file's own rate, as libnyquist
+        converts the samples and EncodeFile averages a stereo pair"""
+        blob, offs = _files_blob(files)
+        n = len(offs) - 1
+        out_offs = np.zeros(n + 1, np.uint64)
+        total = 0
+        for i in range(n):
+            w = wav_parse(blob[int(offs[i]):int(offs[i + 1])].tobytes())
+            total += (w["nValues"] + 1) // 2 if w["channels"] == 2 else w["nValues"]
+        out = np.zeros(max(total, 1), np.float32)
+        _check(self.L.dcs_wav_decode(self.h, _ptr(blob), _ptr(offs), n, _ptr(out), out.size, _ptr(out_offs)), self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)]
+
+    def encode_files(self, files, version=0x9400, fmt=None, filter=None, at_unity=False, **params):
+        """dcs_encode_files: DCSEncoder::EncodeFile on each file (bytes or paths): a DCSa container is copied or re-encoded as
+        transcode_dcsa does it, a WAV file is read as libnyquist reads it, resampled and encoded (version, fmt, params as
+        encode_streams_at).  Returns (list of stream bytes, ENCODE_FILE_INFO_DTYPE array)."""
+        p = transcode_params(version, fmt, **params)
+        blob, offs = _files_blob(files)
+        n = len(offs) - 1
+        f, keep = _resample_filter(filter)
+        fp = ctypes.byref(f) if f is not None else None
+        flags = RESAMPLE_AT_UNITY if at_unity else 0
+        bound = np.zeros(max(n, 1), np.uint64)
+        # (a file the plan refuses: the call below refuses it too, and names the reason in dcs_last_error)
+        st = self.L.dcs_encode_files_plan(_ptr(blob), _ptr(offs), n, ctypes.byref(p), fp, flags, None, _ptr(bound), None)
+        cap = int(bound[:n].sum()) if st == 0 else 0
+        out = np.zeros(max(cap, 1), np.uint8)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info = np.zeros(max(n, 1), ENCODE_FILE_INFO_DTYPE)
+        _check(self.L.dcs_encode_files(self.h, _ptr(blob), _ptr(offs), n, ctypes.byref(p), fp, flags, _ptr(out), cap, _ptr(out_offs),
+                                       _ptr(info)), self.h)
         del keep
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n]
 

@@ -32,7 +32,9 @@
 #include <string.h>
 #include <stdio.h>
 #include <functional>
+#include <atomic>
 #include <string>
+#include <thread>
 #include <type_traits>
 #include <vector>
 #include "../../include/dcs_hip.h"
@@ -303,7 +305,7 @@ __device__ uint32_t encBandSamples(const EncTabs &T, const float *smp, int n, in
 }
 
 // errFrame: the decoder's error word of the stream's first frame (int16 input from a decode batch; 0 for float input)
-struct EncStream { uint64_t sampleOff; uint32_t nSamples, firstFrame, nFrames, errFrame; };
+struct EncStream { uint64_t sampleOff; uint32_t nSamples, firstFrame, nFrames, errFrame; float bound; };   // bound: largest |x|
 
 // layouts computed: v0 = Type 0 (sub-types 0 and 3 differ only in two header bits), v1 = Type 1 sub-type 0, v2 = Type 1
 // sub-type 3.  Search slots per (frame, band): 0 = v0; 1, 2 = v1 at pre-adjust 0, 1; 3..7 = v2 at pre-adjust 0..4.
@@ -353,7 +355,7 @@ __global__ __launch_bounds__(256) void encAnalyseKernel(const EncTabs *__restric
             else
             {
                 x = raw;
-                if (!(fabsf(x) <= 1.0f))
+                if (!(fabsf(x) <= s.bound))
                     isBad = true;
             }
             if (i < 16) x *= T.window[i];
@@ -1143,6 +1145,7 @@ struct EncInput
     const int16_t *devPcm = nullptr;        // stream i starts at sample sampleOffsets[i], a multiple of 240 ...
     const uint32_t *devErr = nullptr;       // ... and its frames' error words at sampleOffsets[i] / 240
     const uint32_t *label = nullptr;        // the number a message gives stream i (null: i)
+    const float *bound = nullptr;           // the largest |x| stream i may hold (null: 1; dcs_encode_files, INTEGRATION rule 12)
     const volatile uint32_t *planFlag = nullptr;    // a word the device writes before the PCM is final: not 0 = the PCM is not to be used
     bool unusable = false;                  // (out) planFlag was set: DCS_ERR_BAD_STREAM, and nothing was written
 };
@@ -1186,7 +1189,7 @@ DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets
             return DCS_ERR_INVALID_ARG;
         }
         hs[i] = EncStream{ sampleOffsets[i] - sampleOffsets[0], static_cast<uint32_t>(n), F, static_cast<uint32_t>(nF),
-                           dev ? static_cast<uint32_t>(sampleOffsets[i] / 240) : 0u };
+                           dev ? static_cast<uint32_t>(sampleOffsets[i] / 240) : 0u, in.bound != nullptr ? in.bound[i] : 1.0f };
         frameStream.insert(frameStream.end(), static_cast<size_t>(nF), i);
         F += static_cast<uint32_t>(nF);
     }
@@ -1301,6 +1304,7 @@ DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets
             if (bad[i])
             {
                 dcsCtxSetError(ctx, (name(i) + (dev ? ": the decoder reports an error in a frame (DCS_FRAME_STOP / DCS_FRAME_FATAL)"
+                                                    : in.bound != nullptr ? ": a sample is not finite or beyond its format's full scale"
                                                     : ": a sample is not finite or |x| > 1")).c_str());
                 return DCS_ERR_BAD_STREAM;
             }
@@ -1439,3 +1443,7 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
 // ------------------------------------------------------------------------------- resampling (dcs_resample.hip.h)
 
 #include "dcs_resample.hip.h"
+
+// ---------------------------------------------------------------------- encoding files (dcs_wav.hip.h)
+
+#include "dcs_wav.hip.h"

@@ -37,6 +37,7 @@ struct RsStream
     int32_t increment;      // lrint(floatInc * 4096)
     int32_t bLen;           // the converter's buffer length (sinc_set_converter)
     int32_t passThrough;    // rate 31 250 without DCS_RESAMPLE_AT_UNITY: the samples as they are
+    int32_t hostWalk;       // walked by the host pool, not by a device lane (rsHostRoute; dcs_encode_files only)
 };
 
 __host__ __device__ inline double rsFmodOne(double x)
@@ -217,6 +218,8 @@ __global__ __launch_bounds__(64) void rsWalkKernel(const RsStream *__restrict__ 
     if (si >= nStreams)
         return;
     const RsStream s = streams[si];
+    if (s.hostWalk)
+        return;
     if (s.passThrough)
     {
         counts[si] = s.nIn;
@@ -413,30 +416,46 @@ DcsStatus rsCheck(uint32_t n, const uint64_t *sampleOffsets, const uint32_t *rat
     return DCS_OK;
 }
 
-// The converter on the device: stage, walk, counts back, convolve.  On DCS_OK, *dOut holds the outputs (stream i from
-// outOffsets[i], outOffsets[n] in all) and peak[i] the bits of the stream's largest |y|; the buffers belong to `held`.
-DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t n, const uint32_t *rates,
-                           const int32_t *channels, const DcsResampleFilter &f, uint32_t flags, std::vector<CacheBuf> &held,
-                           float **dOut, uint64_t *outOffsets, std::vector<uint32_t> &peak)
+// Walk the files' position chains on the host rather than on device lanes where one or a few long ones dominate the list:
+// a file whose walk makes more than kRsHostWalkMin outputs and at least 1 / kRsHostWalkShare of the list's.  A device lane
+// takes about 263 ns an output, the host about 5 ns, so such a file is walked about 50 times faster
+// on the host while the device walks the rest; a batch of comparable files stays on the device lanes, which walk in parallel.
+const uint64_t kRsHostWalkMin = 65536;
+const uint64_t kRsHostWalkShare = 4;
+void rsHostRoute(std::vector<RsStream> &hs)
 {
-    std::vector<RsStream> hs(n);
-    std::vector<int32_t> ch(n);
+    uint64_t total = 0;
+    for (const RsStream &s : hs)
+        total += s.passThrough ? 0 : rsSlots(s);
+    for (RsStream &s : hs)
+    {
+        const uint64_t est = s.passThrough ? 0 : rsSlots(s);
+        s.hostWalk = est > kRsHostWalkMin && est * kRsHostWalkShare >= total;
+    }
+}
+
+// After staging: the walk (device lanes, and the host pool for streams marked hostWalk, at the same time), the counts back,
+// the convolution.  hs[i].inOff locates stream i in dMono; dBad (optional) holds R1's flags.  Messages name stream i as
+// "<unit> label[i]".  On DCS_OK, *dOut holds the outputs (stream i from outOffsets[i], outOffsets[n] in all) and peak[i] the
+// bits of the stream's largest |y|; the buffers belong to `held`.
+DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dMono, const uint32_t *dBad, const DcsResampleFilter &f,
+                         const uint32_t *label, const char *unit, std::vector<CacheBuf> &held, float **dOut, uint64_t *outOffsets,
+                         std::vector<uint32_t> &peak)
+{
+    const uint32_t n = static_cast<uint32_t>(hs.size());
     std::vector<uint64_t> counts(n);
     std::vector<uint32_t> bad(n);
-    uint64_t nMono = 0, nSlots = 0, maxMono = 0;
+    uint64_t nSlots = 0;
+    std::vector<uint32_t> onHost;
     for (uint32_t i = 0 ; i < n ; ++i)
     {
-        ch[i] = channels != nullptr ? channels[i] : 1;
-        const uint64_t m = rsMonoLength(sampleOffsets[i + 1] - sampleOffsets[i], ch[i]);
-        hs[i] = rsStreamOf(m, rates[i], f, flags);
-        hs[i].inOff = nMono;
         hs[i].slotOff = nSlots;
         hs[i].nSlots = rsSlots(hs[i]);
-        nMono += m;
         nSlots += hs[i].nSlots;
-        maxMono = m > maxMono ? m : maxMono;
+        if (hs[i].hostWalk)
+            onHost.push_back(i);
     }
-    const uint64_t nValues = sampleOffsets[n] - sampleOffsets[0];
+    auto name = [&](uint32_t i) { return std::string(unit) + " " + std::to_string(label != nullptr ? label[i] : i); };
     const hipStream_t st = dcsCtxStream(ctx);
     auto alloc = [&](void **p, size_t bytes) -> hipError_t {
         held.emplace_back();
@@ -444,53 +463,77 @@ DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sample
         *p = held.back().as();
         return e;
     };
-    float *dIn, *dMono, *dCoeffs, *dRes;
-    uint64_t *dInOff, *dCounts;
-    int32_t *dCh;
+    float *dCoeffs, *dRes;
+    uint64_t *dCounts;
     RsStream *dStr;
-    uint32_t *dBad, *dPeak;
+    uint32_t *dPeak;
     int2 *dSlots;
-    ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dIn), sizeof(float) * nValues));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dMono), sizeof(float) * nMono));
     ENCCHK(alloc(reinterpret_cast<void **>(&dCoeffs), sizeof(float) * f.nCoeffs));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dInOff), sizeof(uint64_t) * (n + 1)));
     ENCCHK(alloc(reinterpret_cast<void **>(&dCounts), sizeof(uint64_t) * n));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dCh), sizeof(int32_t) * n));
     ENCCHK(alloc(reinterpret_cast<void **>(&dStr), sizeof(RsStream) * n));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dBad), sizeof(uint32_t) * n));
     ENCCHK(alloc(reinterpret_cast<void **>(&dPeak), sizeof(uint32_t) * n));
     ENCCHK(alloc(reinterpret_cast<void **>(&dSlots), sizeof(int2) * (nSlots ? nSlots : 1)));
-    ENCCHK(hipMemcpyAsync(dIn, pcm + sampleOffsets[0], sizeof(float) * nValues, hipMemcpyHostToDevice, st));
     ENCCHK(hipMemcpyAsync(dCoeffs, f.coeffs, sizeof(float) * f.nCoeffs, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(dInOff, sampleOffsets, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(dCh, ch.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
     ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * n, st));
     ENCCHK(hipMemsetAsync(dPeak, 0, sizeof(uint32_t) * n, st));
-    const unsigned gy = n < 65535 ? n : 65535;
-    const uint64_t stageBlocks = (maxMono + 255) / 256;
-    hipLaunchKernelGGL(rsStageKernel, dim3(static_cast<unsigned>(stageBlocks < 1024 ? stageBlocks : 1024), gy), dim3(256), 0, st,
-                       dIn, dInOff, dCh, dStr, n, dMono, dBad);
     hipLaunchKernelGGL(rsWalkKernel, dim3((n + 63) / 64), dim3(64), 0, st, dStr, n, dSlots, dCounts);
     ENCCHK(hipGetLastError());
-    ENCCHK(hipMemcpyAsync(counts.data(), dCounts, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
-    ENCCHK(hipMemcpyAsync(bad.data(), dBad, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    // the host pool walks its streams while the lanes walk theirs (dcs_host_threads, at most one thread a stream)
+    std::vector<std::vector<int2>> hostRec(onHost.size());
+    if (!onHost.empty())
+    {
+        std::atomic<size_t> next{0};
+        auto worker = [&]() {
+            for (size_t j = next++ ; j < onHost.size() ; j = next++)
+            {
+                const RsStream &s = hs[onHost[j]];
+                std::vector<int2> &rec = hostRec[j];
+                rec.reserve(s.nSlots);
+                counts[onHost[j]] = rsWalk(s, [&](uint64_t k, int64_t pos, int32_t sfi) {
+                    if (k < s.nSlots)
+                        rec.push_back(make_int2(static_cast<int32_t>(pos), sfi));
+                });
+            }
+        };
+        int nThreads = dcs_host_threads();
+        nThreads = nThreads < 1 ? 1 : nThreads > static_cast<int>(onHost.size()) ? static_cast<int>(onHost.size()) : nThreads;
+        std::vector<std::thread> pool;
+        for (int t = 1 ; t < nThreads ; ++t)
+            pool.emplace_back(worker);
+        worker();
+        for (std::thread &t : pool)
+            t.join();
+    }
+    std::vector<uint64_t> devCounts(n);
+    ENCCHK(hipMemcpyAsync(devCounts.data(), dCounts, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    if (dBad != nullptr)
+        ENCCHK(hipMemcpyAsync(bad.data(), dBad, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
     ENCCHK(hipStreamSynchronize(st));
+    for (uint32_t i = 0 ; i < n ; ++i)
+        if (!hs[i].hostWalk)
+            counts[i] = devCounts[i];
     for (uint32_t i = 0 ; i < n ; ++i)
         if (bad[i])
         {
-            dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": an input sample (or a stereo pair's mean) is not finite").c_str());
+            dcsCtxSetError(ctx, (name(i) + ": an input sample (or a stereo pair's mean) is not finite").c_str());
             return DCS_ERR_BAD_STREAM;
         }
     for (uint32_t i = 0 ; i < n ; ++i)
         if (!hs[i].passThrough && counts[i] > hs[i].nSlots)
         {
             // a defect of this library, not of the input: the walk made more outputs than rsSlots allows (nothing is truncated)
-            dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": internal error: the resampler's walk made " + std::to_string(counts[i])
+            dcsCtxSetError(ctx, (name(i) + ": internal error: the resampler's walk made " + std::to_string(counts[i])
                                  + " outputs, more than its bound " + std::to_string(hs[i].nSlots)).c_str());
             return DCS_ERR_HIP;
         }
+    if (!onHost.empty())
+    {
+        for (size_t j = 0 ; j < onHost.size() ; ++j)
+            if (!hostRec[j].empty())
+                ENCCHK(hipMemcpyAsync(dSlots + hs[onHost[j]].slotOff, hostRec[j].data(), sizeof(int2) * hostRec[j].size(),
+                                      hipMemcpyHostToDevice, st));
+        ENCCHK(hipMemcpyAsync(dCounts, counts.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
+    }
     outOffsets[0] = 0;
     uint64_t maxCount = 0;
     for (uint32_t i = 0 ; i < n ; ++i)
@@ -502,6 +545,7 @@ DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sample
     ENCCHK(alloc(reinterpret_cast<void **>(&dRes), sizeof(float) * (outOffsets[n] ? outOffsets[n] : 1)));
     ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
     // about 4 096 blocks in all: each block of the LDS variant copies the table once and then strides over its outputs
+    const unsigned gy = n < 65535 ? n : 65535;
     const uint64_t want = (maxCount + 255) / 256, perStream = (4096 + gy - 1) / gy;
     const unsigned gx = static_cast<unsigned>(want < 1 ? 1 : want < perStream ? want : perStream);
     if (f.nCoeffs <= kRsLdsMaxCoeffs)
@@ -516,6 +560,56 @@ DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sample
     ENCCHK(hipStreamSynchronize(st));
     *dOut = dRes;
     return DCS_OK;
+}
+
+// The converter on the device for float input: stage (R1), then rsWalkConvolve, every stream on the device lanes.
+DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t n, const uint32_t *rates,
+                           const int32_t *channels, const DcsResampleFilter &f, uint32_t flags, std::vector<CacheBuf> &held,
+                           float **dOut, uint64_t *outOffsets, std::vector<uint32_t> &peak)
+{
+    std::vector<RsStream> hs(n);
+    std::vector<int32_t> ch(n);
+    uint64_t nMono = 0, maxMono = 0;
+    for (uint32_t i = 0 ; i < n ; ++i)
+    {
+        ch[i] = channels != nullptr ? channels[i] : 1;
+        const uint64_t m = rsMonoLength(sampleOffsets[i + 1] - sampleOffsets[i], ch[i]);
+        hs[i] = rsStreamOf(m, rates[i], f, flags);
+        hs[i].inOff = nMono;
+        nMono += m;
+        maxMono = m > maxMono ? m : maxMono;
+    }
+    const uint64_t nValues = sampleOffsets[n] - sampleOffsets[0];
+    const hipStream_t st = dcsCtxStream(ctx);
+    auto alloc = [&](void **p, size_t bytes) -> hipError_t {
+        held.emplace_back();
+        const hipError_t e = held.back().alloc(ctx, false, (bytes + 255) & ~size_t(255));
+        *p = held.back().as();
+        return e;
+    };
+    float *dIn, *dMono;
+    uint64_t *dInOff;
+    int32_t *dCh;
+    RsStream *dStr;
+    uint32_t *dBad;
+    ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dIn), sizeof(float) * nValues));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dMono), sizeof(float) * nMono));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dInOff), sizeof(uint64_t) * (n + 1)));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dCh), sizeof(int32_t) * n));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dStr), sizeof(RsStream) * n));
+    ENCCHK(alloc(reinterpret_cast<void **>(&dBad), sizeof(uint32_t) * n));
+    ENCCHK(hipMemcpyAsync(dIn, pcm + sampleOffsets[0], sizeof(float) * nValues, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dInOff, sampleOffsets, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dCh, ch.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * n, st));
+    const unsigned gy = n < 65535 ? n : 65535;
+    const uint64_t stageBlocks = (maxMono + 255) / 256;
+    hipLaunchKernelGGL(rsStageKernel, dim3(static_cast<unsigned>(stageBlocks < 1024 ? stageBlocks : 1024), gy), dim3(256), 0, st,
+                       dIn, dInOff, dCh, dStr, n, dMono, dBad);
+    ENCCHK(hipGetLastError());
+    return rsWalkConvolve(ctx, hs, dMono, dBad, f, nullptr, "stream", held, dOut, outOffsets, peak);
 }
 
 float fromBitsU(uint32_t b) { float x; memcpy(&x, &b, 4); return x; }

@@ -38,7 +38,9 @@ extern "C" {
                                           dcs_encode93_header, dcs_encode93_streams); transcoding (DcsTranscodeInfo,
                                           dcs_transcode_plan, dcs_transcode_streams); resampling (DcsResampleFilter,
                                           DCS_RESAMPLE_AT_UNITY, dcs_resample_filter_default, dcs_resample_count,
-                                          dcs_resample_streams, dcs_encode_streams_at) */
+                                          dcs_resample_streams, dcs_encode_streams_at); encoding files (DcsWavInfo,
+                                          DcsEncodeFileInfo, DCS_WAV_*, DCS_FILE_*, dcs_wav_parse, dcs_wav_decode,
+                                          dcs_encode_files_plan, dcs_encode_files) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -904,6 +906,77 @@ DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const uint64_t *s
                                 const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
                                 uint32_t flags, const DcsEncodeParams *params, uint8_t *out, size_t outCap,
                                 uint64_t *outOffsets, DcsEncodeInfo *info);
+
+/* ------------------------------------------------------------------------------------------------
+ * Encoding files: DCSEncoder::EncodeFile (DCSEncodeFile.cpp:29-105) on files held in memory.  A "DCSa" container (IsDCSFile's
+ * test) is copied or re-encoded as dcs_transcode_streams does it (EncodeDCSFile); a RIFF/WAVE file is read as libnyquist's
+ * WavDecoder::LoadFromBuffer reads it, downmixed ((L + R) / 2.0f), resampled and encoded as dcs_encode_streams_at does it;
+ * anything else is DCS_ERR_INVALID_ARG.  The numbered rules where libnyquist is undefined or departs from the format are in
+ * INTEGRATION.md, "Encoding files".  Files i is files[fileOffsets[i] .. fileOffsets[i+1]).
+ */
+#define DCS_WAV_U8   0                 /* sample formats (DcsWavInfo.sampleFormat): unsigned 8-bit ...                     */
+#define DCS_WAV_S16  1                 /* ... signed 16-bit (also 4-bit PCM, which libnyquist reads as 16-bit) ...         */
+#define DCS_WAV_S24  2                 /* ... packed signed 24-bit ...                                                     */
+#define DCS_WAV_S32  3                 /* ... signed 32-bit ...                                                            */
+#define DCS_WAV_F32  4                 /* ... IEEE float ...                                                               */
+#define DCS_WAV_F64  5                 /* ... IEEE double ...                                                              */
+#define DCS_WAV_IMA  6                 /* ... IMA ADPCM, 4 bits                                                            */
+
+typedef struct DcsWavInfo
+{
+    int32_t  status;                   /* DCS_OK, or why the file is refused (DCS_ERR_INVALID_ARG / DCS_ERR_BAD_STREAM)    */
+    int32_t  formatCode;               /* the fmt chunk's format code: 1, 3, 0x11, 0xFFFE                                  */
+    int32_t  sampleFormat;             /* DCS_WAV_*                                                                        */
+    int32_t  bitDepth;
+    int32_t  channels;                 /* 1 or 2                                                                           */
+    uint32_t rate;                     /* Hz, as the file says                                                             */
+    int32_t  blockAlign;               /* the fmt chunk's block align (libnyquist's frame_size)                            */
+    int32_t  reserved;
+    uint64_t dataOffset;               /* the data payload's first byte in the file ...                                    */
+    uint64_t dataSize;                 /* ... and its size as the chunk header says                                        */
+    uint64_t nValues;                  /* float values libnyquist produces (interleaved)                                   */
+    uint64_t nBlocks;                  /* IMA ADPCM: whole blocks decoded                                                  */
+    char     reason[96];               /* a refusal's reason                                                               */
+} DcsWavInfo;
+
+#define DCS_FILE_WAV            0      /* DcsEncodeFileInfo.kind: a RIFF/WAVE file, encoded ...                            */
+#define DCS_FILE_DCSA_COPY      1      /* ... a DCSa container whose stream is copied ...                                  */
+#define DCS_FILE_DCSA_REENCODE  2      /* ... a DCSa container whose stream is decoded and encoded again                   */
+#define DCS_FILE_WALK_NONE      0      /* DcsEncodeFileInfo.walk: no resampling (31 250 Hz, or a DCSa file) ...           */
+#define DCS_FILE_WALK_DEVICE    1      /* ... the position walk ran on a device lane ...                                   */
+#define DCS_FILE_WALK_HOST      2      /* ... on the host (a file that dominates the list)                */
+
+typedef struct DcsEncodeFileInfo
+{
+    int32_t  kind;                     /* DCS_FILE_*                                                                       */
+    int32_t  sourceFormat;             /* WAV: the format code; DCSa: the container's DcsOsVersion                         */
+    uint32_t rate;                     /* WAV: the file's rate; DCSa: 31 250                                               */
+    int32_t  channels;
+    uint64_t nValues;                  /* WAV: values read (interleaved); DCSa: the stream's bytes                         */
+    uint64_t nSamples;                 /* WAV: 31 250 Hz samples encoded; DCSa: the source's frames x 240                  */
+    int32_t  walk;                     /* DCS_FILE_WALK_*                                                                  */
+    int32_t  srcFrames;                /* DCSa: DcsTranscodeInfo.srcFrames; WAV: 0                                         */
+    DcsEncodeInfo enc;                 /* WAV: the encoder's; DCSa: DcsTranscodeInfo.enc                                   */
+} DcsEncodeFileInfo;
+
+/* host only: one file as LoadFromBuffer reads it.  Returns info->status; info->reason says why a file is refused. */
+DcsStatus dcs_wav_parse(const uint8_t *file, size_t len, DcsWavInfo *info);
+/* host only: each file's kind (DCS_FILE_*, -1 when refused), the bytes its output can take, and the errors that need no GPU
+ * (statusOut); any of the three may be NULL.  Returns the first file's error, or DCS_OK. */
+DcsStatus dcs_encode_files_plan(const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles, const DcsEncodeParams *params,
+                                const DcsResampleFilter *filter, uint32_t flags, int32_t *kindOut, uint64_t *boundOut,
+                                int32_t *statusOut);
+/* WAV files -> mono float PCM at each file's own rate (the device unpack alone, W0 and W1): file i's samples at
+ * out + outOffsets[i].  DCS_ERR_CAPACITY: outCap (floats) is too small; outOffsets is filled all the same. */
+DcsStatus dcs_wav_decode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles, float *out,
+                         size_t outCap, uint64_t *outOffsets);
+/* EncodeFile for each file with params (formatVersion 0x9400, 0x9301, 0x9302), filter and flags as dcs_encode_streams_at.
+ * Outputs are stream bytes in input order with the encoders' capacity protocol; errors name the file's index in
+ * dcs_last_error.  A DCSa file's bytes, info and errors are dcs_transcode_streams' for its stream (decode volume 0x67, level
+ * 0xFF, channel volume 0xFF). */
+DcsStatus dcs_encode_files(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
+                           const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out,
+                           size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info);
 
 uint32_t dcs_abi_version(void);
 /* a digest of the sources and compiler flags this library was built from (16 hex digits).  Counter profiles under

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""dcs_encode_files throughput on one GPU, against the host composition it replaces: the WAV files read on the host
+(wav_parse + tests/wav_ref.py's conversion and downmix), then dcs_encode_streams_at on the float PCM.  Workloads:
+256 x 10 s 16-bit stereo 44.1 kHz (each walk on a device lane), one 180 s 16-bit stereo 44.1 kHz file (the walk on the
+host), 256 x 10 s IMA ADPCM mono 22.05 kHz (its composition decodes with dcs_wav_decode, because the numpy ADPCM restatement
+is a Python loop).  Each path is timed to the call's return, median of --iters after a warm-up call, the two paths
+alternating; both must give the same bytes.  Prints one JSON line.  Per-kernel times: run this under
+`rocprofv3 --kernel-trace --stats -- python tools/encode_files_bench.py --iters 1`."""
+import argparse
+import json
+import os
+import struct
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import dcsexplorer_amd as D                     # noqa: E402
+import wav_cases as W                           # noqa: E402
+import wav_ref as R                             # noqa: E402
+
+
+def stereo16(seconds, rate, seed):
+    n = seconds * rate
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) / rate
+    lr = np.stack([0.3 * np.sin(2 * np.pi * (220 + seed) * t), 0.3 * np.sin(2 * np.pi * (330 + seed) * t)], axis=1)
+    v = np.round((lr + 0.05 * rng.uniform(-1, 1, lr.shape)).reshape(-1) * 32767).astype("<i2")
+    return W.riff([W.fmt_chunk(1, 2, rate, 16), W.chunk("data", v.tobytes())])
+
+
+def ima_mono(seconds, rate, seed, block_align=1024):
+    """IMA ADPCM blocks with seeded headers and small nibbles (codes 0, 1, 8, 9: the step index settles at 0)"""
+    rng = np.random.default_rng(seed)
+    per = 2 * (block_align - 4)
+    nb = -(-seconds * rate // (per + 1))
+    nib = rng.choice(np.array([0, 1, 8, 9], np.uint8), size=(nb, per))
+    body = (nib[:, 0::2] | (nib[:, 1::2] << 4)).astype(np.uint8)
+    hdr = np.zeros((nb, 4), np.uint8)
+    hdr[:, 0:2] = np.frombuffer(struct.pack("<h", 0) * nb, np.uint8).reshape(nb, 2)
+    data = np.concatenate([hdr, body], axis=1).tobytes()
+    fact = W.chunk("fact", struct.pack("<I", seconds * rate))
+    return W.riff([W.fmt_chunk(0x11, 1, rate, 4, block_align=block_align, size=20), fact, W.chunk("data", data)])
+
+
+def workload(name):
+    if name == "256x10s_s16_stereo_44k":
+        return [stereo16(10, 44100, k) for k in range(256)]
+    if name == "1x180s_s16_stereo_44k":
+        return [W.long_wav()]
+    return [ima_mono(10, 22050, k) for k in range(256)]
+
+
+def host_composition(ctx, files):
+    mono, rates = [], []
+    if R.parse(files[0])[1].get("sampleFormat") == R.IMA:
+        mono = ctx.wav_decode(files)
+        rates = [D.wav_parse(f)["rate"] for f in files]
+    else:
+        for f in files:
+            st, m, d = R.decode(f)
+            mono.append(m)
+            rates.append(d["rate"])
+    return ctx.encode_streams_at(mono, rates)[0]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--workloads", default="256x10s_s16_stereo_44k,1x180s_s16_stereo_44k,256x10s_ima_mono_22k")
+    a = ap.parse_args()
+    ctx = D.Context(0)
+    res = {}
+    for w in a.workloads.split(","):
+        files = workload(w)
+        fused = lambda: ctx.encode_files(files)                          # noqa: E731
+        host = lambda: host_composition(ctx, files)                      # noqa: E731
+        out, info = fused()
+        want = host()
+        tf, th = [], []
+        for _ in range(a.iters):
+            t = time.perf_counter(); out, info = fused(); tf.append(time.perf_counter() - t)
+            t = time.perf_counter(); want = host(); th.append(time.perf_counter() - t)
+        n_out = int(info["nSamples"].sum())
+        res[w] = dict(files=len(files), mb_in=sum(len(f) for f in files) / 1e6, out_samples=n_out,
+                      walk=sorted(set(int(x) for x in info["walk"])), encode_files_s=float(np.median(tf)),
+                      host_composition_s=float(np.median(th)), speedup=float(np.median(th) / np.median(tf)),
+                      encode_files_out_per_s=n_out / float(np.median(tf)), bytes_equal=out == want)
+    ctx.close()
+    print(json.dumps(dict(tool="encode_files_bench", results=res)))
+
+
+if __name__ == "__main__":
+    sys.exit(main())
