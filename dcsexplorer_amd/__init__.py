@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     host_threads, partition_streams, decode_streams_sharded, Pipeline, make_refs, FRAME_TAIL_LOST, Node, DevicePath, node_cache_release, device_numa_node, bind_process_to_device_numa,
     FMT_94_T0_S3, ENCODE_INFO_DTYPE, EncodeParams, encode_params, encode_bound, encode_header,
     encode93_params, encode93_bound, encode93_header,
+    SWEEP_RESULT_DTYPE, SWEEP_JOB_DTYPE, SWEEP_MEASURE, sweep_sq_err, encode_sweep_group_frames, encode_fit_choose,
     TRANSCODE_COPIED, TRANSCODE_REENCODED, TRANSCODE_REENCODE_ALL, TRANSCODE_INFO_DTYPE, TRANSCODE_OS, transcode_params, transcode_plan,
     ResampleFilter, RESAMPLE_AT_UNITY, resample_filter_default, resample_count,
     WavInfo, ENCODE_FILE_INFO_DTYPE, WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32, WAV_F64, WAV_IMA, FILE_WAV, FILE_DCSA_COPY,

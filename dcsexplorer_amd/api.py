@@ -88,6 +88,13 @@ FMT_94_T0_S3 = "94-T0-S3"
 _ENCODE_FMT = {None: (-1, -1), FMT_94_T0: (0, 0), FMT_94_T1_S0: (1, 0), FMT_94_T1_S3: (1, 3), FMT_94_T0_S3: (0, 3)}
 
 
+# dcs_encode_sweep: a job's record (DcsSweepResult), the job list's entries (DcsSweepJob) and the flag that measures
+SWEEP_RESULT_DTYPE = np.dtype([("enc", ENCODE_INFO_DTYPE), ("measured", "<u4"), ("peakErr", "<i4"), ("nCompared", "<u8"),
+                               ("sumSrcSq", "<i8"), ("sumDecSq", "<i8"), ("sumCross", "<i8")], align=True)
+SWEEP_JOB_DTYPE = np.dtype([("stream", "<u4"), ("paramSet", "<u4")])
+SWEEP_MEASURE = 1
+
+
 # dcs_transcode_*: what happens to a source, and its record (DcsTranscodeInfo)
 TRANSCODE_COPIED, TRANSCODE_REENCODED = 0, 1
 TRANSCODE_REENCODE_ALL = 1
@@ -177,6 +184,7 @@ EXPORTS = [
     "dcs_transcode_plan", "dcs_transcode_streams",
     "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
     "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
+    "dcs_encode_sweep", "dcs_encode_sweep_group_frames", "dcs_encode_fit",
 ]
 
 
@@ -471,6 +479,12 @@ def load_library():
                                         vp, sz, vp, vp]
     L.dcs_wav_parse.restype = i32
     L.dcs_wav_parse.argtypes = [vp, sz, ctypes.POINTER(WavInfo)]
+    L.dcs_encode_sweep.restype = i32
+    L.dcs_encode_sweep.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, sz, vp]
+    L.dcs_encode_sweep_group_frames.restype = None
+    L.dcs_encode_sweep_group_frames.argtypes = [ctypes.c_uint64]
+    L.dcs_encode_fit.restype = i32
+    L.dcs_encode_fit.argtypes = [vp, vp, u32, u32, ctypes.c_uint64, vp, vp]
     L.dcs_encode_files_plan.restype = i32
     L.dcs_encode_files_plan.argtypes = [vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32, vp, vp, vp]
     L.dcs_wav_decode.restype = i32
@@ -738,6 +752,37 @@ def transcode_plan(streams, os_list, version=0x9400, fmt=None, reencode_all=Fals
     _check(load_library().dcs_transcode_plan(refs, n, ctypes.byref(p), TRANSCODE_REENCODE_ALL if reencode_all else 0,
                                              _ptr(action), _ptr(bound)))
     return action[:n], bound[:n]
+
+
+def sweep_sq_err(results):
+    """the squared error at unity of measured SWEEP_RESULT_DTYPE records, sumDecSq - 2 sumCross + sumSrcSq (Python ints)"""
+    return [int(r["sumDecSq"]) - 2 * int(r["sumCross"]) + int(r["sumSrcSq"]) for r in np.atleast_1d(results)]
+
+
+def encode_sweep_group_frames(max_job_frames):
+    """dcs_encode_sweep_group_frames: the most job-frames a group of an encode may hold (0: what the memory takes)"""
+    load_library().dcs_encode_sweep_group_frames(int(max_job_frames))
+
+
+def encode_fit_choose(n_bytes, sq_err, budget):
+    """dcs_encode_fit (host only): tables [nStreams][nSets], the sets in order of preference -> (choice per stream, total
+    bytes).  Raises DcsError with status -5 when no set fits as a whole; its `needed` is the smallest column total and its
+    `choice` that column."""
+    nb = np.ascontiguousarray(n_bytes, dtype=np.uint64)
+    se = np.ascontiguousarray(sq_err, dtype=np.uint64)
+    if nb.ndim != 2 or nb.shape != se.shape:
+        raise ValueError("n_bytes and sq_err are [nStreams][nSets] tables of one shape")
+    choice = np.zeros(max(nb.shape[0], 1), np.int32)
+    total = ctypes.c_uint64(0)
+    st = load_library().dcs_encode_fit(_ptr(nb) if nb.size else None, _ptr(se) if se.size else None, nb.shape[0], nb.shape[1],
+                                       int(budget), _ptr(choice), ctypes.byref(total))
+    if st == -5:
+        e = DcsError(st, "no parameter set fits %d bytes: the smallest needs %d" % (int(budget), total.value))
+        e.needed = int(total.value)
+        e.choice = choice[:nb.shape[0]].copy()
+        raise e
+    _check(st)
+    return choice[:nb.shape[0]].copy(), int(total.value)
 
 
 def _encode_input(pcm_list):
@@ -1105,6 +1150,52 @@ class Context:
         out = np.zeros(max(cap, 1), np.uint8)
         _check(self.L.dcs_encode_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info
+
+    def encode_sweep(self, pcm_list, sets, jobs=None, measure=True, streams=True):
+        """dcs_encode_sweep: jobs = (stream, set) pairs encoded in one call; sets = EncodeParams of one encoder (encode_params /
+        encode93_params / transcode_params); jobs None = every pair, stream-major.  PCM as encode_streams.  measure: each
+        job's stream is decoded on the device and compared with its source (SWEEP_RESULT_DTYPE's sums; sweep_sq_err).
+        Returns (list of bytes per job, or None when streams is false; SWEEP_RESULT_DTYPE array)."""
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        arr = (EncodeParams * max(len(sets), 1))(*sets)
+        if jobs is None:
+            jl, n_jobs = None, n * len(sets)
+        else:
+            jl = np.zeros(max(len(jobs), 1), SWEEP_JOB_DTYPE)
+            for k, (s, p) in enumerate(jobs):
+                jl[k] = (s, p)
+            n_jobs = len(jobs)
+        res = np.zeros(max(n_jobs, 1), SWEEP_RESULT_DTYPE)
+        out_offs = np.zeros(n_jobs + 1, np.uint64)
+        flags = SWEEP_MEASURE if measure else 0
+        args = (self.h, _ptr(pcm), _ptr(offs), n, arr, len(sets), _ptr(jl) if jl is not None else None, n_jobs, flags, _ptr(res))
+        if not streams:
+            _check(self.L.dcs_encode_sweep(*args, None, 0, _ptr(out_offs)), self.h)
+            return None, res[:n_jobs]
+        # sizes first would cost a second pass: the encoders' bound of every job's stream instead
+        bound = encode_bound if len(sets) and sets[0].formatVersion == 0x9400 else encode93_bound
+        each = [bound(int(offs[i + 1] - offs[i])) for i in range(n)]
+        cap = sum(each) * len(sets) if jobs is None else sum(each[s] for s, _ in jobs if 0 <= s < n)
+        out = np.zeros(max(cap, 1), np.uint8)
+        _check(self.L.dcs_encode_sweep(*args, _ptr(out), cap, _ptr(out_offs)), self.h)
+        return [out[out_offs[j]:out_offs[j + 1]].tobytes() for j in range(n_jobs)], res[:n_jobs]
+
+    def encode_fit(self, pcm_list, sets, budget):
+        """the best of `sets` (in order of preference) per stream within `budget` bytes: a measuring sweep without bytes,
+        encode_fit_choose on its sizes and squared errors, then one job per stream for the bytes.  Returns (list of bytes,
+        choice per stream, SWEEP_RESULT_DTYPE records of the chosen jobs, total bytes); raises DcsError status -5 (with
+        `needed`) when no set fits as a whole."""
+        n, k = len(pcm_list), len(sets)
+        _, res = self.encode_sweep(pcm_list, sets, None, measure=True, streams=False)
+        if not res["measured"].all():
+            j = int(np.flatnonzero(res["measured"] == 0)[0])
+            raise DcsError(-6, "stream %d, set %d: an OS93a stream with no band kept cannot be decoded, so not measured" % (j // k, j % k))
+        n_bytes = res["enc"]["nBytes"].astype(np.uint64).reshape(n, k)
+        sq_err = np.array(sweep_sq_err(res), dtype=np.uint64).reshape(n, k)
+        choice, total = encode_fit_choose(n_bytes, sq_err, budget)
+        out, _ = self.encode_sweep(pcm_list, sets, [(i, int(choice[i])) for i in range(n)], measure=False, streams=True)
+        return out, choice, res.reshape(n, k)[np.arange(n), choice], total
 
     def encode93_streams(self, pcm_list, os_=OS93B, fmt=None, **params):
         """dcs_encode93_streams: PCM at 31 250 Hz (as encode_streams) -> OS93 streams, byte for byte the reference DCSEncoder's

@@ -11,7 +11,8 @@
 //
 //   E1 encAnalyseKernel   one wavefront per frame: window, bit-reversed load, 6 radix-2 stages, the odd-coefficient pass,
 //                         the folds, the twiddle, the sign fix (each stage element-parallel over LDS); per-band power / lo / hi
-//   E2 encStreamKernel    one wavefront per stream: powerSum in frame order and the range, then the header of each layout
+//   E2 encStreamKernel    one wavefront per stream: powerSum in frame order and the range
+//      encHeaderKernel    one wavefront per job: the header of each layout
 //   E3 encSearchKernel    one thread per (frame, band, layout, pre-adjust): the 15 candidate codes' error sums, the best code
 //                         with and without code 15 (the only things the previous frame's code can change)
 //   E4 encChainKernel     one lane per (stream, layout, band): the walk over frames through those per-frame choices
@@ -25,12 +26,19 @@
 //   O4 enc93WalkKernel    CompressFrame93b's band loop: Type 0 one lane per frame (no state crosses frames), Type 1 one lane
 //                         per stream, frame after frame (the band-type codes carried from frame to frame)
 //   O5 enc93PackKernel    one lane per (frame, band): the band's flag and type bits, then its samples
+//
+// E1 and encStreamKernel run per stream and do not read the parameters.  Everything behind them runs per JOB, a stream
+// encoded with one parameter set (EncJob, EncSet): its rows in the per-frame buffers are the job's own, the spectrum it reads
+// is its stream's.  dcs_encode_streams and its kin are one job per stream with one set; dcs_encode_sweep is any list of jobs,
+// and with DCS_SWEEP_MEASURE decodes every job's stream where the pack step left it and reduces the round trip's error
+// (encMeasureKernel).
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
+#include <algorithm>
 #include <functional>
 #include <atomic>
 #include <string>
@@ -307,6 +315,16 @@ __device__ uint32_t encBandSamples(const EncTabs &T, const float *smp, int n, in
 // errFrame: the decoder's error word of the stream's first frame (int16 input from a decode batch; 0 for float input)
 struct EncStream { uint64_t sampleOff; uint32_t nSamples, firstFrame, nFrames, errFrame; float bound; };   // bound: largest |x|
 
+// A job: stream `stream` encoded with parameter set `set`.  Its nFrames rows in the per-job-frame buffers (best, codes, bits,
+// frame offsets) start at firstFrame; row k reads frame specFirst + k of E1's output (specFirst = its stream's firstFrame).
+struct EncJob { uint32_t stream, set, firstFrame, nFrames, specFirst; };
+
+// what the kernels read of a DcsEncodeParams: vmask = the layouts to compute, cmask = CloseStream's candidates (encodeJobs)
+struct EncSet { float cutoff, minDR, maxQE; int32_t rate; uint32_t vmask, cmask; };
+
+// the frame of E1's output that row f of the per-job-frame buffers reads
+__device__ inline uint32_t encSpecFrame(const EncJob &j, uint32_t f) { return j.specFirst + (f - j.firstFrame); }
+
 // layouts computed: v0 = Type 0 (sub-types 0 and 3 differ only in two header bits), v1 = Type 1 sub-type 0, v2 = Type 1
 // sub-type 3.  Search slots per (frame, band): 0 = v0; 1, 2 = v1 at pre-adjust 0, 1; 3..7 = v2 at pre-adjust 0..4.
 __device__ inline int encSlot(const EncTabs &T, int v, int band, int old)
@@ -475,12 +493,10 @@ __global__ __launch_bounds__(256) void encAnalyseKernel(const EncTabs *__restric
     }
 }
 
-// E2: one wavefront per stream
-__global__ __launch_bounds__(64) void encStreamKernel(const EncTabs *__restrict__ Tp, const EncStream *__restrict__ streams,
-    const float *__restrict__ pw, const float *__restrict__ flo, const float *__restrict__ fhi, float cutoff, int rate,
-    uint32_t vmask, uint8_t *__restrict__ hdrOut, int32_t *__restrict__ keepOut)
+// E2: one wavefront per stream: sums[stream][0 / 1 / 2][band] = powerSum in frame order, the lowest and the highest sample
+__global__ __launch_bounds__(64) void encStreamKernel(const EncStream *__restrict__ streams, const float *__restrict__ pw,
+    const float *__restrict__ flo, const float *__restrict__ fhi, float *__restrict__ sums)
 {
-    __shared__ float sPs[16], sLo[16], sHi[16];
     const EncStream s = streams[blockIdx.x];
     const int l = threadIdx.x;
     if (l < 16)
@@ -506,58 +522,76 @@ __global__ __launch_bounds__(64) void encStreamKernel(const EncTabs *__restrict_
                 if (j0 + u == 0 || c[u] > hi) hi = c[u];
             }
         }
-        sPs[l] = ps; sLo[l] = lo; sHi[l] = hi;
+        float *o = sums + static_cast<size_t>(blockIdx.x) * 48 + l;
+        o[0] = ps; o[16] = lo; o[32] = hi;
     }
+}
+
+// E2, the header half: one wavefront per job, one lane per layout
+__global__ __launch_bounds__(64) void encHeaderKernel(const EncTabs *__restrict__ Tp, const EncJob *__restrict__ jobs,
+    const EncSet *__restrict__ sets, const float *__restrict__ sums, uint8_t *__restrict__ hdrOut, int32_t *__restrict__ keepOut)
+{
+    __shared__ float sSum[48];
+    const EncJob j = jobs[blockIdx.x];
+    const EncSet p = sets[j.set];
+    const int l = threadIdx.x;
+    if (l < 48)
+        sSum[l] = sums[static_cast<size_t>(j.stream) * 48 + l];
     __syncthreads();
-    if (l < 3 && ((vmask >> l) & 1))
+    if (l < 3 && ((p.vmask >> l) & 1))
     {
         uint8_t hdr[16];
         int bits[16], keep;
-        encHeader(*Tp, sPs, sLo, sHi, cutoff, rate, l == 0 ? 0 : 1, l == 2 ? 3 : 0, hdr, &keep, bits);
+        encHeader(*Tp, sSum, sSum + 16, sSum + 32, p.cutoff, p.rate, l == 0 ? 0 : 1, l == 2 ? 3 : 0, hdr, &keep, bits);
         for (int b = 0 ; b < 16 ; ++b)
             hdrOut[(static_cast<size_t>(blockIdx.x) * 3 + l) * 16 + b] = hdr[b];
         keepOut[blockIdx.x] = keep;                         // (the same for every layout)
     }
 }
 
-// E3: one block per frame, one thread per (band, slot)
+// E3: one block per job-frame, one thread per (band, slot)
 __global__ __launch_bounds__(128) void encSearchKernel(const EncTabs *__restrict__ Tp, const float *__restrict__ spec,
-    const float *__restrict__ flo, const float *__restrict__ fhi, const uint32_t *__restrict__ frameStream,
-    const uint8_t *__restrict__ hdr, const int32_t *__restrict__ keepArr, uint32_t vmask, float minDR, float maxQE,
-    uint8_t *__restrict__ best)
+    const float *__restrict__ flo, const float *__restrict__ fhi, const uint32_t *__restrict__ frameJob,
+    const EncJob *__restrict__ jobs, const EncSet *__restrict__ sets, const uint8_t *__restrict__ hdr,
+    const int32_t *__restrict__ keepArr, uint8_t *__restrict__ best)
 {
     const EncTabs &T = *Tp;
     __shared__ float smp[256];
     const uint32_t f = blockIdx.x;
     const int t = threadIdx.x;
-    smp[t] = spec[static_cast<size_t>(f) * 256 + t];
-    smp[t + 128] = spec[static_cast<size_t>(f) * 256 + 128 + t];
+    const uint32_t ji = frameJob[f];
+    const EncJob job = jobs[ji];
+    const uint32_t sf = encSpecFrame(job, f);
+    smp[t] = spec[static_cast<size_t>(sf) * 256 + t];
+    smp[t + 128] = spec[static_cast<size_t>(sf) * 256 + 128 + t];
     __syncthreads();
     const int band = t >> 3, slot = t & 7;
-    const uint32_t si = frameStream[f];
-    if (band >= keepArr[si])
+    if (band >= keepArr[ji])
         return;
+    const EncSet p = sets[job.set];
     const int v = slot == 0 ? 0 : slot < 3 ? 1 : 2;
     const int pre = slot == 0 ? 0 : slot < 3 ? slot - 1 : slot - 3;
-    if (!((vmask >> v) & 1) || (band >= 3 && pre != 0))
+    if (!((p.vmask >> v) & 1) || (band >= 3 && pre != 0))
         return;
-    const size_t fb = static_cast<size_t>(f) * 16 + band;
+    const size_t sb = static_cast<size_t>(sf) * 16 + band;
     uint8_t out = 0;
-    if (!(fhi[fb] - flo[fb] < minDR))
+    if (!(fhi[sb] - flo[sb] < p.minDR))
     {
         const int n = T.count[band];
-        const float errMax = (maxQE * maxQE) * static_cast<float>(n);
-        out = encSearch(T, smp + T.first[band], n, v == 0 ? 0 : 1, band, hdr[(static_cast<size_t>(si) * 3 + v) * 16 + band] & 0x3f, pre, errMax);
+        const float errMax = (p.maxQE * p.maxQE) * static_cast<float>(n);
+        out = encSearch(T, smp + T.first[band], n, v == 0 ? 0 : 1, band, hdr[(static_cast<size_t>(ji) * 3 + v) * 16 + band] & 0x3f, pre, errMax);
     }
-    best[fb * 8 + slot] = out;
+    best[(static_cast<size_t>(f) * 16 + band) * 8 + slot] = out;
 }
 
-// E4: one block per stream, one lane per (layout, band): the band-type codes, frame after frame
-__global__ __launch_bounds__(64) void encChainKernel(const EncTabs *__restrict__ Tp, const EncStream *__restrict__ streams,
-    const int32_t *__restrict__ keepArr, uint32_t vmask, uint32_t F, const uint64_t *__restrict__ best, uint8_t *__restrict__ codes)
+// E4: one block per job, one lane per (layout, band): the band-type codes, frame after frame
+__global__ __launch_bounds__(64) void encChainKernel(const EncTabs *__restrict__ Tp, const EncJob *__restrict__ jobs,
+    const EncSet *__restrict__ sets, const int32_t *__restrict__ keepArr, uint32_t F, const uint64_t *__restrict__ best,
+    uint8_t *__restrict__ codes)
 {
     const EncTabs &T = *Tp;
-    const EncStream s = streams[blockIdx.x];
+    const EncJob s = jobs[blockIdx.x];
+    const uint32_t vmask = sets[s.set].vmask;
     const int v = threadIdx.x >> 4, band = threadIdx.x & 15;
     if (v >= 3 || !((vmask >> v) & 1) || band >= keepArr[blockIdx.x])
         return;
@@ -584,10 +618,10 @@ __global__ __launch_bounds__(64) void encChainKernel(const EncTabs *__restrict__
     }
 }
 
-// E5a: one block per frame, one lane per (layout, band): header-code and sample bits
+// E5a: one block per job-frame, one lane per (layout, band): header-code and sample bits
 __global__ __launch_bounds__(64) void encBitsKernel(const EncTabs *__restrict__ Tp, const float *__restrict__ spec,
-    const EncStream *__restrict__ streams, const uint32_t *__restrict__ frameStream, const uint8_t *__restrict__ hdr,
-    const int32_t *__restrict__ keepArr, uint32_t vmask, uint32_t F, const uint8_t *__restrict__ codes,
+    const uint32_t *__restrict__ frameJob, const EncJob *__restrict__ jobs, const EncSet *__restrict__ sets,
+    const uint8_t *__restrict__ hdr, const int32_t *__restrict__ keepArr, uint32_t F, const uint8_t *__restrict__ codes,
     uint8_t *__restrict__ hdrBits, uint16_t *__restrict__ smpBits, uint32_t *__restrict__ frameBits)
 {
     const EncTabs &T = *Tp;
@@ -595,17 +629,19 @@ __global__ __launch_bounds__(64) void encBitsKernel(const EncTabs *__restrict__ 
     __shared__ uint32_t fb[3][16];
     const uint32_t f = blockIdx.x;
     const int l = threadIdx.x;
+    const uint32_t si = frameJob[f];
+    const EncJob job = jobs[si];
+    const uint32_t sf = encSpecFrame(job, f), vmask = sets[job.set].vmask;
     for (int q = 0 ; q < 4 ; ++q)
-        smp[l + 64 * q] = spec[static_cast<size_t>(f) * 256 + l + 64 * q];
+        smp[l + 64 * q] = spec[static_cast<size_t>(sf) * 256 + l + 64 * q];
     __syncthreads();
     const int v = l >> 4, band = l & 15;
-    const uint32_t si = frameStream[f];
     uint32_t hb = 0, sb = 0;
     if (v < 3 && ((vmask >> v) & 1) && band < keepArr[si])
     {
         const size_t at = (static_cast<size_t>(v) * F + f) * 16 + band;
         const int code = codes[at];
-        const int old = f == streams[si].firstFrame ? 0 : codes[at - 16];
+        const int old = f == job.firstFrame ? 0 : codes[at - 16];
         hb = T.hdrLen[code - old + 16];
         int w, sc;
         encInterpret(T, v == 0 ? 0 : 1, band, code, hdr[(static_cast<size_t>(si) * 3 + v) * 16 + band] & 0x3f, encPre(T, v, band, old), &w, &sc);
@@ -625,16 +661,17 @@ __global__ __launch_bounds__(64) void encBitsKernel(const EncTabs *__restrict__ 
     }
 }
 
-// E5b: one block per stream: sizes of the layouts, the winner (the first strictly smallest, CloseStream :805), and the
+// E5b: one block per job: sizes of the layouts, the winner (the first strictly smallest, CloseStream :805), and the
 // exclusive scan of the winner's frame bits
-__global__ __launch_bounds__(256) void encSizeKernel(const EncStream *__restrict__ streams, uint32_t F, uint32_t cmask,
+__global__ __launch_bounds__(256) void encSizeKernel(const EncJob *__restrict__ jobs, const EncSet *__restrict__ sets, uint32_t F,
     const uint32_t *__restrict__ frameBits, int32_t *__restrict__ winOut, uint64_t *__restrict__ sizeOut, uint32_t *__restrict__ frameOff)
 {
     __shared__ uint64_t red[3][256];
     __shared__ uint32_t scan[256];
     __shared__ int sWin;
     __shared__ uint32_t carry;
-    const EncStream s = streams[blockIdx.x];
+    const EncJob s = jobs[blockIdx.x];
+    const uint32_t cmask = sets[s.set].cmask;
     const int t = threadIdx.x;
     uint64_t tot[3] = { 0, 0, 0 };
     for (uint32_t j = t ; j < s.nFrames ; j += 256)
@@ -691,8 +728,8 @@ __global__ __launch_bounds__(256) void encSizeKernel(const EncStream *__restrict
     }
 }
 
-// E5c: the 2-byte frame count and the 16-byte header of each stream's winner
-__global__ __launch_bounds__(64) void encHeadKernel(const EncStream *__restrict__ streams, const uint8_t *__restrict__ hdr,
+// E5c: the 2-byte frame count and the 16-byte header of each job's winner
+__global__ __launch_bounds__(64) void encHeadKernel(const EncJob *__restrict__ jobs, const uint8_t *__restrict__ hdr,
     const int32_t *__restrict__ win, const uint64_t *__restrict__ outOff, uint32_t *__restrict__ W)
 {
     const uint32_t si = blockIdx.x;
@@ -700,7 +737,7 @@ __global__ __launch_bounds__(64) void encHeadKernel(const EncStream *__restrict_
     if (k >= 18)
         return;
     const int c = win[si], v = c < 2 ? 0 : c - 1;
-    const uint32_t nF = streams[si].nFrames;
+    const uint32_t nF = jobs[si].nFrames;
     uint32_t byte;
     if (k < 2)
         byte = k == 0 ? nF >> 8 : nF & 0xFF;
@@ -713,9 +750,9 @@ __global__ __launch_bounds__(64) void encHeadKernel(const EncStream *__restrict_
     encPut(W, outOff[si] * 8 + k * 8, byte, 8);
 }
 
-// E5d: four frames per block, one lane per band: the winner's header codes and samples
+// E5d: four job-frames per block, one lane per band: the winner's header codes and samples
 __global__ __launch_bounds__(64) void encPackKernel(const EncTabs *__restrict__ Tp, const float *__restrict__ spec,
-    const EncStream *__restrict__ streams, const uint32_t *__restrict__ frameStream, const uint8_t *__restrict__ hdr,
+    const uint32_t *__restrict__ frameJob, const EncJob *__restrict__ jobs, const uint8_t *__restrict__ hdr,
     const int32_t *__restrict__ keepArr, const int32_t *__restrict__ win, uint32_t F, const uint8_t *__restrict__ codes,
     const uint8_t *__restrict__ hdrBits, const uint16_t *__restrict__ smpBits, const uint32_t *__restrict__ frameOff,
     const uint64_t *__restrict__ outOff, uint32_t *__restrict__ W)
@@ -727,14 +764,14 @@ __global__ __launch_bounds__(64) void encPackKernel(const EncTabs *__restrict__ 
     {
         const int idx = l + 64 * q;
         const uint32_t ff = blockIdx.x * 4 + (idx >> 8);
-        smp[idx >> 8][idx & 255] = ff < F ? spec[static_cast<size_t>(ff) * 256 + (idx & 255)] : 0.0f;
+        smp[idx >> 8][idx & 255] = ff < F ? spec[static_cast<size_t>(encSpecFrame(jobs[frameJob[ff]], ff)) * 256 + (idx & 255)] : 0.0f;
     }
     __syncthreads();
     const uint32_t f = blockIdx.x * 4 + (l >> 4);
     const int band = l & 15;
     if (f >= F)
         return;
-    const uint32_t si = frameStream[f];
+    const uint32_t si = frameJob[f];
     const int keep = keepArr[si];
     if (band >= keep)
         return;
@@ -752,7 +789,7 @@ __global__ __launch_bounds__(64) void encPackKernel(const EncTabs *__restrict__ 
     }
     const uint64_t base = (outOff[si] + 18) * 8 + frameOff[f];
     const int code = codes[row + band];
-    const int old = f == streams[si].firstFrame ? 0 : codes[row - 16 + band];
+    const int old = f == jobs[si].firstFrame ? 0 : codes[row - 16 + band];
     encPut(W, base + hOff, T.hdrCode[code - old + 16], T.hdrLen[code - old + 16]);
     int w, sc;
     encInterpret(T, v == 0 ? 0 : 1, band, code, hdr[(static_cast<size_t>(si) * 3 + v) * 16 + band] & 0x3f, encPre(T, v, band, old), &w, &sc);
@@ -788,10 +825,10 @@ __device__ inline uint32_t bitLen(uint32_t x) { return x ? 32u - static_cast<uin
 
 __device__ inline uint32_t absI(int x) { return x < 0 ? 0u - static_cast<uint32_t>(x) : static_cast<uint32_t>(x); }
 
-// O3: four frames per block, one thread per (frame, band, layout)
+// O3: four job-frames per block, one thread per (frame, band, layout)
 __global__ __launch_bounds__(128) void enc93SearchKernel(const EncTabs *__restrict__ Tp, const float *__restrict__ spec,
-    const uint32_t *__restrict__ frameStream, const uint8_t *__restrict__ hdr, const int32_t *__restrict__ keepArr,
-    uint32_t vmask, uint32_t F, float maxQE, Enc93Rec *__restrict__ rec)
+    const uint32_t *__restrict__ frameJob, const EncJob *__restrict__ jobs, const EncSet *__restrict__ sets,
+    const uint8_t *__restrict__ hdr, const int32_t *__restrict__ keepArr, uint32_t F, Enc93Rec *__restrict__ rec)
 {
     const EncTabs &T = *Tp;
     __shared__ float smp[4][256];
@@ -800,15 +837,16 @@ __global__ __launch_bounds__(128) void enc93SearchKernel(const EncTabs *__restri
     {
         const int idx = t + 128 * q;
         const uint32_t ff = blockIdx.x * 4 + (idx >> 8);
-        smp[idx >> 8][idx & 255] = ff < F ? spec[static_cast<size_t>(ff) * 256 + (idx & 255)] : 0.0f;
+        smp[idx >> 8][idx & 255] = ff < F ? spec[static_cast<size_t>(encSpecFrame(jobs[frameJob[ff]], ff)) * 256 + (idx & 255)] : 0.0f;
     }
     __syncthreads();
     const uint32_t f = blockIdx.x * 4 + (t >> 5);
     const int v = (t >> 4) & 1, band = t & 15;
-    if (f >= F || !((vmask >> v) & 1))
+    if (f >= F)
         return;
-    const uint32_t si = frameStream[f];
-    if (band >= keepArr[si])
+    const uint32_t si = frameJob[f];
+    const EncSet p = sets[jobs[si].set];
+    if (!((p.vmask >> v) & 1) || band >= keepArr[si])
         return;
     int first, n;
     enc93Band(v, band, &first, &n);
@@ -853,7 +891,7 @@ __global__ __launch_bounds__(128) void enc93SearchKernel(const EncTabs *__restri
         }
         prv = s;
     }
-    const float errMax = (maxQE * maxQE) * static_cast<float>(n);
+    const float errMax = (p.maxQE * p.maxQE) * static_cast<float>(n);
 #pragma unroll
     for (int c = 0 ; c < 15 ; ++c)
         pass[c] = err[c] <= errMax;
@@ -952,11 +990,11 @@ __device__ inline void enc93Load(const Enc93Rec *__restrict__ rec, size_t row, i
             r[b] = rec[row + b];
 }
 
-// O4: Type 0 (TYP 0): one lane per frame.  Type 1: one lane per stream, frame after frame, the next frame's records loaded
+// O4: Type 0 (TYP 0): one lane per job-frame.  Type 1: one lane per job that computes Type 1, frame after frame, the next frame's records loaded
 // while the current one is walked.  Writes each band's Enc93Band and each frame's bit count.
 template <int TYP>
-__global__ __launch_bounds__(64) void enc93WalkKernel(const EncTabs *__restrict__ Tp, const EncStream *__restrict__ streams,
-    const uint32_t *__restrict__ frameStream, const int32_t *__restrict__ keepArr, uint32_t F, uint32_t nUnits,
+__global__ __launch_bounds__(64) void enc93WalkKernel(const EncTabs *__restrict__ Tp, const EncJob *__restrict__ jobs,
+    const EncSet *__restrict__ sets, const uint32_t *__restrict__ frameJob, const int32_t *__restrict__ keepArr, uint32_t F, uint32_t nUnits,
     const Enc93Rec *__restrict__ rec, Enc93Band *__restrict__ out, uint32_t *__restrict__ frameBits)
 {
     __shared__ uint32_t btCode[2][32];
@@ -974,12 +1012,17 @@ __global__ __launch_bounds__(64) void enc93WalkKernel(const EncTabs *__restrict_
         btc[b] = 0;
     if (TYP == 0)
     {
-        const int keep = keepArr[frameStream[u]];
+        const uint32_t ji = frameJob[u];
+        if (!(sets[jobs[ji].set].vmask & 1))
+            return;
+        const int keep = keepArr[ji];
         enc93Load<TYP>(rec, static_cast<size_t>(u) * 16, keep, r);
         frameBits[u] = enc93Frame<TYP>(btCode, btLen, keep, r, btc, out + static_cast<size_t>(u) * 16);
         return;
     }
-    const EncStream s = streams[u];
+    const EncJob s = jobs[u];
+    if (!(sets[s.set].vmask & 2))
+        return;
     const int keep = keepArr[u];
     const size_t base = static_cast<size_t>(F) * 16;          // layout 1's rows
     enc93Load<TYP>(rec, base + static_cast<size_t>(s.firstFrame) * 16, keep, r);
@@ -995,9 +1038,9 @@ __global__ __launch_bounds__(64) void enc93WalkKernel(const EncTabs *__restrict_
     }
 }
 
-// O5: four frames per block, one lane per band: the winner's flag and type bits, then the samples of its band sub-type
+// O5: four job-frames per block, one lane per band: the winner's flag and type bits, then the samples of its band sub-type
 __global__ __launch_bounds__(64) void enc93PackKernel(const EncTabs *__restrict__ Tp, const float *__restrict__ spec,
-    const uint32_t *__restrict__ frameStream, const uint8_t *__restrict__ hdr, const int32_t *__restrict__ keepArr,
+    const uint32_t *__restrict__ frameJob, const EncJob *__restrict__ jobs, const uint8_t *__restrict__ hdr, const int32_t *__restrict__ keepArr,
     const int32_t *__restrict__ win, uint32_t F, const Enc93Band *__restrict__ bands, const uint32_t *__restrict__ frameOff,
     const uint64_t *__restrict__ outOff, uint32_t *__restrict__ W)
 {
@@ -1008,14 +1051,14 @@ __global__ __launch_bounds__(64) void enc93PackKernel(const EncTabs *__restrict_
     {
         const int idx = l + 64 * q;
         const uint32_t ff = blockIdx.x * 4 + (idx >> 8);
-        smp[idx >> 8][idx & 255] = ff < F ? spec[static_cast<size_t>(ff) * 256 + (idx & 255)] : 0.0f;
+        smp[idx >> 8][idx & 255] = ff < F ? spec[static_cast<size_t>(encSpecFrame(jobs[frameJob[ff]], ff)) * 256 + (idx & 255)] : 0.0f;
     }
     __syncthreads();
     const uint32_t f = blockIdx.x * 4 + (l >> 4);
     const int band = l & 15;
     if (f >= F)
         return;
-    const uint32_t si = frameStream[f];
+    const uint32_t si = frameJob[f];
     if (band >= keepArr[si])
         return;
     const int v = win[si] < 2 ? 0 : 1;                          // (0,0) -> Type 0, (1,0) -> Type 1
@@ -1133,7 +1176,78 @@ extern "C" DcsStatus dcs_encode93_header(const float *powerSum, const float *lo,
         }                                                                                            \
     } while (0)
 
+// ------------------------------------------------------------------------ measuring a job's round trip (dcs_sweep.hip.h)
+
+// what the encoder knows of a stream it has sized, enough for the device path's stream table (dcs_sweep.hip.h)
+struct DcsSweepStream { uint32_t nFrames, nBytes; int32_t os, formatType, formatSubType, bandsToKeep; };
+struct DcsSweepDecode;
+DcsStatus dcsSweepLayout(const DcsSweepStream *s, uint32_t n, uint64_t *offs, size_t *blobLen, size_t *blobBytes);
+DcsStatus dcsSweepDecodeStart(DcsCtx *ctx, const DcsSweepStream *s, uint32_t n, const uint64_t *offs, const uint8_t *dBlob, size_t blobLen,
+                              const uint8_t *hostBlob, DcsSweepDecode **out, const int16_t **dPcm, const uint32_t **dErr,
+                              const volatile uint32_t **planFlag, const uint32_t **firstFrame);
+void dcsSweepDecodeRelease(DcsSweepDecode *d);
+
 namespace {
+
+// the sums of one job (DcsSweepResult's, as the kernel adds them up), and the OR of its frames' decode error words
+struct EncMeasure { unsigned long long srcSq, decSq, cross; int32_t peak; uint32_t err; };
+
+const uint32_t kMeasureFrames = 32;         // frames of a job per block of encMeasureKernel
+const uint32_t kNotDecoded = 0xFFFFFFFFu;   // firstDec of a job whose stream was not decoded
+
+__device__ inline long long waveSum(long long v)
+{
+    for (int o = 32 ; o > 0 ; o >>= 1)
+        v += __shfl_down(v, o);
+    return v;
+}
+
+// M1: block (j, y) compares samples [y * 7 680, (y + 1) * 7 680) of job j's source, q = clamp(rint(x * 32768)), with the
+// decoded stream 16 samples on (the decoder's overlap; it was decoded for nFrames + 1 frames, so the last 16 exist), and
+// ORs the error words of decoded frames [y * 32, (y + 1) * 32).  All sums are integers: any order of adding is exact.
+__global__ __launch_bounds__(256) void encMeasureKernel(const float *__restrict__ pcm, const EncStream *__restrict__ streams,
+    const EncJob *__restrict__ jobs, const uint32_t *__restrict__ firstDec, const int16_t *__restrict__ dec,
+    const uint32_t *__restrict__ decErr, EncMeasure *__restrict__ res)
+{
+    const EncJob j = jobs[blockIdx.x];
+    const EncStream s = streams[j.stream];
+    const uint32_t t = threadIdx.x;
+    const uint32_t fr = blockIdx.y * kMeasureFrames + t;
+    if (firstDec[blockIdx.x] == kNotDecoded)
+        return;
+    if (t < kMeasureFrames && fr <= j.nFrames && decErr[firstDec[blockIdx.x] + fr] != 0)
+        atomicOr(&res[blockIdx.x].err, 1u);
+    const uint32_t k0 = blockIdx.y * kMeasureFrames * 240;
+    if (k0 >= s.nSamples)
+        return;
+    const uint32_t k1 = min(k0 + kMeasureFrames * 240, s.nSamples);
+    const float *x = pcm + s.sampleOff;
+    const int16_t *d = dec + static_cast<size_t>(firstDec[blockIdx.x]) * 240 + 16;
+    long long a = 0, b = 0, c = 0;
+    int peak = 0;
+    for (uint32_t k = k0 + t ; k < k1 ; k += 256)
+    {
+        int q = static_cast<int>(rintf(x[k] * 32768.0f));
+        q = q > 32767 ? 32767 : q < -32768 ? -32768 : q;
+        const int y = d[k];
+        a += static_cast<long long>(q * q);
+        b += static_cast<long long>(y * y);
+        c += static_cast<long long>(y * q);
+        const int e = y > q ? y - q : q - y;
+        peak = e > peak ? e : peak;
+    }
+    a = waveSum(a); b = waveSum(b); c = waveSum(c);
+    for (int o = 32 ; o > 0 ; o >>= 1)
+        peak = max(peak, __shfl_down(peak, o));
+    if ((t & 63) == 0)
+    {
+        EncMeasure &r = res[blockIdx.x];
+        atomicAdd(&r.srcSq, static_cast<unsigned long long>(a));
+        atomicAdd(&r.decSq, static_cast<unsigned long long>(b));
+        atomicAdd(&r.cross, static_cast<unsigned long long>(c));      // (two's complement: the signed sum)
+        atomicMax(&r.peak, peak);
+    }
+}
 
 // Where the driver reads its samples: the caller's float PCM on the host (dcs_encode_streams, dcs_encode93_streams), a
 // decode batch's int16 PCM and error words, resident on the device (dcs_transcode_streams, dcs_transcode.hip.h), or the
@@ -1153,23 +1267,28 @@ struct EncInput
 // after the sizes are known: the host memory that takes the `total` bytes (stream i at outOffsets[i]), or null for DCS_ERR_CAPACITY
 using EncPlace = std::function<uint8_t *(const uint64_t *outOffsets, uint64_t total)>;
 
-// The one host driver behind dcs_encode_streams (os93 = false), dcs_encode93_streams (os93 = true) and the re-encodes of
-// dcs_transcode_streams: validation, buffers, E1 / E2, the family's band stages, the sizes and the capacity check, then
-// the header, pack and swap.  Returns after the stream is idle: device input may be released then.
-DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets, uint32_t nStreams,
-                        const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info,
-                        bool os93, const EncPlace &place = nullptr)
+// what dcs_encode_sweep asks of the driver beyond a list of jobs
+struct EncSweep
+{
+    DcsSweepResult *results = nullptr;
+    bool measure = false;
+    bool sizesOnly = false;                 // out == NULL && outCap == 0: nothing is packed for the host
+};
+
+// most job-frames a group may hold (0: what the memory takes); dcs_encode_sweep_group_frames
+std::atomic<uint64_t> gGroupFrames{ 0 };
+
+// The one host driver behind every encode.  A job is (stream, parameter set); dcs_encode_streams and its kin are one job per
+// stream with one set.  Validation of the streams, E1 and the sums of E2 once per stream; then the jobs in groups, runs of the
+// job list whose per-job-frame buffers fit the memory (one group unless an allocation fails or a cap is set): the header
+// half of E2, the family's band stages and the sizes per group, the capacity check once every size is known, then header,
+// pack and swap per group (a group that is no longer resident is computed again), and with sweep.measure the group's
+// streams decoded where the pack step left them and compared with their sources.  Returns after the stream is idle.
+DcsStatus encodeJobs(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets, uint32_t nStreams, const DcsEncodeParams *sets,
+                     uint32_t nSets, const DcsSweepJob *jobList, uint32_t nJobs, bool os93, uint8_t *out, size_t outCap,
+                     uint64_t *outOffsets, DcsEncodeInfo *info, const EncSweep &sweep, const EncPlace &place)
 {
     const bool dev = in.devPcm != nullptr, devF = in.devFloat != nullptr;
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && in.hostPcm == nullptr && !dev && !devF)
-        || (dev && in.devErr == nullptr))
-        return DCS_ERR_INVALID_ARG;
-    if (!paramsValid(params, os93))
-    {
-        if (os93 && params != nullptr && params->formatVersion == 0x9301 && params->streamFormatType == 1)
-            dcsCtxSetError(ctx, "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0");
-        return DCS_ERR_INVALID_ARG;
-    }
     auto name = [&](uint32_t i) { return "stream " + std::to_string(in.label ? in.label[i] : i); };
     std::vector<EncStream> hs(nStreams);
     std::vector<uint32_t> frameStream;
@@ -1188,157 +1307,431 @@ DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets
             dcsCtxSetError(ctx, (name(i) + ": more than 65 535 frames").c_str());
             return DCS_ERR_INVALID_ARG;
         }
+        if (sweep.measure && nF == 65535)
+        {
+            dcsCtxSetError(ctx, (name(i) + ": 65 535 frames; measured with the extra frame its decode would need 65 536, more than the frame count holds").c_str());
+            return DCS_ERR_INVALID_ARG;
+        }
         hs[i] = EncStream{ sampleOffsets[i] - sampleOffsets[0], static_cast<uint32_t>(n), F, static_cast<uint32_t>(nF),
                            dev ? static_cast<uint32_t>(sampleOffsets[i] / 240) : 0u, in.bound != nullptr ? in.bound[i] : 1.0f };
         frameStream.insert(frameStream.end(), static_cast<size_t>(nF), i);
         F += static_cast<uint32_t>(nF);
     }
-    if (nStreams == 0)
+    outOffsets[0] = 0;
+    if (nStreams == 0 || nJobs == 0)
     {
-        outOffsets[0] = 0;
+        for (uint32_t j = 0 ; j < nJobs ; ++j)
+            outOffsets[j + 1] = 0;
         return DCS_OK;
     }
-    const int typ = params->streamFormatType, sub = os93 ? 0 : params->streamFormatSubType;
-    uint32_t cmask = 0;                 // candidates in CloseStream's order (0,0), (0,3), (1,0), (1,3)
-    const int ct[4] = { 0, 0, 1, 1 }, cs[4] = { 0, 3, 0, 3 };
-    for (int c = 0 ; c < 4 ; ++c)
-        if ((typ < 0 || typ == ct[c]) && (sub < 0 || sub == cs[c]) && !(os93 && params->formatVersion == 0x9301 && ct[c] == 1))
-            cmask |= 1u << c;
-    const uint32_t vmask = ((cmask & 3) ? 1u : 0u) | ((cmask & 4) ? 2u : 0u) | ((cmask & 8) ? 4u : 0u);
+    const int ct[4] = { 0, 0, 1, 1 }, cs[4] = { 0, 3, 0, 3 };      // candidates in CloseStream's order (0,0), (0,3), (1,0), (1,3)
+    std::vector<EncSet> hsets(nSets);
+    uint32_t anyV = 0;
+    for (uint32_t k = 0 ; k < nSets ; ++k)
+    {
+        const DcsEncodeParams &p = sets[k];
+        const int typ = p.streamFormatType, sub = os93 ? 0 : p.streamFormatSubType;
+        uint32_t cmask = 0;
+        for (int c = 0 ; c < 4 ; ++c)
+            if ((typ < 0 || typ == ct[c]) && (sub < 0 || sub == cs[c]) && !(os93 && p.formatVersion == 0x9301 && ct[c] == 1))
+                cmask |= 1u << c;
+        const uint32_t vmask = ((cmask & 3) ? 1u : 0u) | ((cmask & 4) ? 2u : 0u) | ((cmask & 8) ? 4u : 0u);
+        hsets[k] = EncSet{ p.powerBandCutoff, p.minimumDynamicRange, p.maximumQuantizationError, p.targetBitRate, vmask, cmask };
+        anyV |= vmask;
+    }
+    // the groups: runs of the job list of at most `limit` job-frames, a job never split
+    uint64_t allFrames = 0, largest = 0;
+    for (uint32_t j = 0 ; j < nJobs ; ++j)
+    {
+        const uint64_t nF = hs[jobList[j].stream].nFrames;
+        allFrames += nF;
+        largest = nF > largest ? nF : largest;
+    }
+    std::vector<uint32_t> groupFirst;           // group g = jobs [groupFirst[g], groupFirst[g + 1])
+    uint64_t groupFrames = 0;                   // the largest group's job-frames ...
+    uint32_t groupJobs = 0;                     // ... and the most jobs in a group
+    auto makeGroups = [&](uint64_t limit) {
+        groupFirst.assign(1, 0);
+        groupFrames = 0; groupJobs = 0;
+        uint64_t inGroup = 0;
+        for (uint32_t j = 0 ; j < nJobs ; ++j)
+        {
+            const uint64_t nF = hs[jobList[j].stream].nFrames;
+            if ((inGroup != 0 && inGroup + nF > limit) || inGroup + nF > 0xFFFFFFFFull)
+            {
+                groupFirst.push_back(j);
+                inGroup = 0;
+            }
+            inGroup += nF;
+            groupFrames = inGroup > groupFrames ? inGroup : groupFrames;
+            groupJobs = std::max(groupJobs, j + 1 - groupFirst.back());
+        }
+        groupFirst.push_back(nJobs);
+    };
     const uint64_t nSamples = sampleOffsets[nStreams] - sampleOffsets[0];
     const EncTabs &tabs = os93 ? encTabs93() : encTabs();
 
     const hipStream_t st = dcsCtxStream(ctx);
-    std::vector<CacheBuf> held;
-    auto alloc = [&](void **p, size_t bytes) -> hipError_t {
-        held.emplace_back();
-        const hipError_t e = held.back().alloc(ctx, false, (bytes + 255) & ~size_t(255));
-        *p = held.back().as();
+    std::vector<CacheBuf> held, group;
+    auto allocIn = [&](std::vector<CacheBuf> &own, void **p, size_t bytes) -> hipError_t {
+        own.emplace_back();
+        const hipError_t e = own.back().alloc(ctx, false, (bytes + 255) & ~size_t(255));
+        *p = own.back().as();
         return e;
     };
-    EncTabs *dT; float *dPcm = nullptr, *dSpec, *dPw, *dLo, *dHi; EncStream *dStr; uint32_t *dFS, *dBad, *dFrameBits, *dFrameOff, *dW;
-    uint8_t *dHdr, *dBest = nullptr, *dCodes = nullptr, *dHdrBits = nullptr; uint16_t *dSmpBits = nullptr;
-    Enc93Rec *dRec = nullptr; Enc93Band *dBand = nullptr; int32_t *dKeep, *dWin; uint64_t *dSize, *dOutOff;
-    std::vector<int32_t> win(nStreams), keep(nStreams);
-    std::vector<uint64_t> size(nStreams);
+    auto alloc = [&](void **p, size_t bytes) -> hipError_t { return allocIn(held, p, bytes); };
+    EncTabs *dT; float *dPcm = nullptr, *dSpec, *dPw, *dLo, *dHi, *dSums; EncStream *dStr; EncSet *dSets; uint32_t *dFS, *dBad;
+    EncJob *dJobs = nullptr; uint32_t *dFJ = nullptr, *dFrameBits = nullptr, *dFrameOff = nullptr, *dFirstDec = nullptr;
+    uint8_t *dHdr = nullptr, *dBest = nullptr, *dCodes = nullptr, *dHdrBits = nullptr; uint16_t *dSmpBits = nullptr;
+    Enc93Rec *dRec = nullptr; Enc93Band *dBand = nullptr; int32_t *dKeep = nullptr, *dWin = nullptr; uint64_t *dSize = nullptr, *dOutOff = nullptr;
+    EncMeasure *dMeas = nullptr;
+    // every buffer of a group, sized for the largest one
+    auto allocGroup = [&]() -> hipError_t {
+        const size_t JF = static_cast<size_t>(groupFrames), NJ = groupJobs;
+        struct { void **p; size_t bytes; } want[] = {
+            { reinterpret_cast<void **>(&dJobs), sizeof(EncJob) * NJ }, { reinterpret_cast<void **>(&dFJ), sizeof(uint32_t) * JF },
+            { reinterpret_cast<void **>(&dHdr), 48 * NJ }, { reinterpret_cast<void **>(&dKeep), sizeof(int32_t) * NJ },
+            { reinterpret_cast<void **>(&dWin), sizeof(int32_t) * NJ }, { reinterpret_cast<void **>(&dSize), sizeof(uint64_t) * NJ },
+            { reinterpret_cast<void **>(&dOutOff), sizeof(uint64_t) * NJ },
+            { reinterpret_cast<void **>(&dFrameBits), sizeof(uint32_t) * 3 * JF }, { reinterpret_cast<void **>(&dFrameOff), sizeof(uint32_t) * JF },
+            { reinterpret_cast<void **>(&dRec), os93 ? sizeof(Enc93Rec) * 32 * JF : 0 }, { reinterpret_cast<void **>(&dBand), os93 ? sizeof(Enc93Band) * 32 * JF : 0 },
+            { reinterpret_cast<void **>(&dBest), os93 ? 0 : 128 * JF }, { reinterpret_cast<void **>(&dCodes), os93 ? 0 : 48 * JF },
+            { reinterpret_cast<void **>(&dHdrBits), os93 ? 0 : 48 * JF }, { reinterpret_cast<void **>(&dSmpBits), os93 ? 0 : sizeof(uint16_t) * 48 * JF },
+            { reinterpret_cast<void **>(&dMeas), sweep.measure ? sizeof(EncMeasure) * NJ : 0 },
+            { reinterpret_cast<void **>(&dFirstDec), sweep.measure ? sizeof(uint32_t) * NJ : 0 },
+        };
+        for (const auto &w : want)
+            if (w.bytes != 0)
+            {
+                const hipError_t e = allocIn(group, w.p, w.bytes);
+                if (e != hipSuccess)
+                    return e;
+            }
+        return hipSuccess;
+    };
+    std::vector<int32_t> win(nJobs), keep(nJobs);
+    std::vector<uint64_t> size(nJobs);
     std::vector<uint32_t> bad(nStreams);
+    std::vector<EncJob> hj;                     // the resident group's jobs and rows
+    std::vector<uint32_t> frameJob;
+    uint32_t resident = ~0u, residentFrames = 0;
+    // E2's header half to the sizes for group g, and a wait: win, keep and size of its jobs are on the host after it
+    auto runGroup = [&](uint32_t g) -> DcsStatus {
+        const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
+        hj.resize(n);
+        frameJob.clear();
+        uint32_t JF = 0;
+        for (uint32_t k = 0 ; k < n ; ++k)
+        {
+            const EncStream &s = hs[jobList[j0 + k].stream];
+            hj[k] = EncJob{ jobList[j0 + k].stream, jobList[j0 + k].paramSet, JF, s.nFrames, s.firstFrame };
+            frameJob.insert(frameJob.end(), s.nFrames, k);
+            JF += s.nFrames;
+        }
+        ENCCHK(hipMemcpyAsync(dJobs, hj.data(), sizeof(EncJob) * n, hipMemcpyHostToDevice, st));
+        ENCCHK(hipMemcpyAsync(dFJ, frameJob.data(), sizeof(uint32_t) * JF, hipMemcpyHostToDevice, st));
+        ENCCHK(hipMemsetAsync(dFrameBits, 0, sizeof(uint32_t) * 3 * JF, st));
+        hipLaunchKernelGGL(encHeaderKernel, dim3(n), dim3(64), 0, st, dT, dJobs, dSets, dSums, dHdr, dKeep);
+        if (os93)
+        {
+            hipLaunchKernelGGL(enc93SearchKernel, dim3((JF + 3) / 4), dim3(128), 0, st, dT, dSpec, dFJ, dJobs, dSets, dHdr, dKeep, JF, dRec);
+            if (anyV & 1)
+                hipLaunchKernelGGL(enc93WalkKernel<0>, dim3((JF + 63) / 64), dim3(64), 0, st, dT, dJobs, dSets, dFJ, dKeep, JF, JF, dRec, dBand, dFrameBits);
+            if (anyV & 2)
+                hipLaunchKernelGGL(enc93WalkKernel<1>, dim3((n + 63) / 64), dim3(64), 0, st, dT, dJobs, dSets, dFJ, dKeep, JF, n, dRec,
+                                   dBand, dFrameBits);
+        }
+        else
+        {
+            ENCCHK(hipMemsetAsync(dBest, 0, size_t(128) * JF, st));
+            ENCCHK(hipMemsetAsync(dCodes, 0, size_t(48) * JF, st));
+            hipLaunchKernelGGL(encSearchKernel, dim3(JF), dim3(128), 0, st, dT, dSpec, dLo, dHi, dFJ, dJobs, dSets, dHdr, dKeep, dBest);
+            hipLaunchKernelGGL(encChainKernel, dim3(n), dim3(64), 0, st, dT, dJobs, dSets, dKeep, JF,
+                               reinterpret_cast<const uint64_t *>(dBest), dCodes);
+            hipLaunchKernelGGL(encBitsKernel, dim3(JF), dim3(64), 0, st, dT, dSpec, dFJ, dJobs, dSets, dHdr, dKeep, JF, dCodes, dHdrBits, dSmpBits, dFrameBits);
+        }
+        hipLaunchKernelGGL(encSizeKernel, dim3(n), dim3(256), 0, st, dJobs, dSets, JF, dFrameBits, dWin, dSize, dFrameOff);
+        ENCCHK(hipGetLastError());
+        ENCCHK(hipMemcpyAsync(win.data() + j0, dWin, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        ENCCHK(hipMemcpyAsync(keep.data() + j0, dKeep, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        ENCCHK(hipMemcpyAsync(size.data() + j0, dSize, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+        ENCCHK(hipStreamSynchronize(st));
+        resident = g;
+        residentFrames = JF;
+        return DCS_OK;
+    };
+    CacheBuf wBuf;
+    std::vector<uint64_t> offs;
+    std::vector<uint8_t> stage;
+    std::vector<DcsSweepStream> ss, selS;
+    std::vector<uint32_t> sel, firstDec;
+    std::vector<uint64_t> selOff;
+    std::vector<EncMeasure> meas;
+    uint8_t *dst = nullptr;
+    // header, pack and swap of the resident group; its bytes to dst; with sweep.measure its decode and the comparison
+    auto packGroup = [&](uint32_t g) -> DcsStatus {
+        const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0, JF = residentFrames;
+        offs.resize(n);
+        size_t blobLen, nWords;
+        if (sweep.measure)
+        {
+            // where the device path's stream layout wants them (each stream on a 4-byte boundary, the blob's zeroed tail)
+            ss.resize(n);
+            for (uint32_t k = 0 ; k < n ; ++k)
+            {
+                const int c = win[j0 + k];
+                const uint16_t ver = sets[hj[k].set].formatVersion;
+                ss[k] = DcsSweepStream{ hj[k].nFrames, static_cast<uint32_t>(size[j0 + k]),
+                                        ver == 0x9301 ? DCS_OS93A : ver == 0x9302 ? DCS_OS93B : cs[c] == 3 ? DCS_OS95 : DCS_OS94, ct[c], os93 ? 0 : cs[c],
+                                        keep[j0 + k] };
+            }
+            size_t blobBytes;
+            const DcsStatus ls = dcsSweepLayout(ss.data(), n, offs.data(), &blobLen, &blobBytes);
+            if (ls != DCS_OK)
+                return ls;
+            nWords = blobBytes / 4;
+        }
+        else
+        {
+            for (uint32_t k = 0 ; k < n ; ++k)
+                offs[k] = outOffsets[j0 + k] - outOffsets[j0];
+            blobLen = static_cast<size_t>(outOffsets[j0 + n] - outOffsets[j0]);
+            nWords = (blobLen + 3) / 4 + 1;
+        }
+        ENCCHK(wBuf.alloc(ctx, false, (sizeof(uint32_t) * nWords + 255) & ~size_t(255)));
+        uint32_t *dW = wBuf.as<uint32_t>();
+        ENCCHK(hipMemsetAsync(dW, 0, sizeof(uint32_t) * nWords, st));
+        ENCCHK(hipMemcpyAsync(dOutOff, offs.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(encHeadKernel, dim3(n), dim3(64), 0, st, dJobs, dHdr, dWin, dOutOff, dW);
+        if (os93)
+            hipLaunchKernelGGL(enc93PackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, dT, dSpec, dFJ, dJobs, dHdr, dKeep, dWin, JF, dBand,
+                               dFrameOff, dOutOff, dW);
+        else
+            hipLaunchKernelGGL(encPackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, dT, dSpec, dFJ, dJobs, dHdr, dKeep, dWin, JF, dCodes,
+                               dHdrBits, dSmpBits, dFrameOff, dOutOff, dW);
+        hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
+        ENCCHK(hipGetLastError());
+        if (!sweep.measure)
+        {
+            ENCCHK(hipMemcpyAsync(dst + outOffsets[j0], dW, blobLen, hipMemcpyDeviceToHost, st));
+            ENCCHK(hipStreamSynchronize(st));
+            return DCS_OK;
+        }
+        // The decode, as transcoding runs it (dcs_transcode.hip.h): the device path on the bytes where they lie; the
+        // host-planned batch, for which the bytes are read back, where the device planner cannot serve the list or one
+        // long stream dominates it (the device index walk is one wavefront per stream, serial over its frames).
+        // One kind of stream is left out: an OS93a stream with no band kept.  Its header is sixteen 0xFF bytes, the first of
+        // which carries the type bit, so every decoder reads it as OS93a Type 1 with 31 bands; its record stays measured = 0.
+        sel.clear(); selS.clear(); selOff.clear();
+        uint64_t longest = 0, selFrames = 0;
+        uint32_t mostFrames = 0;
+        for (uint32_t k = 0 ; k < n ; ++k)
+            if (!(ss[k].os == DCS_OS93A && ss[k].bandsToKeep == 0))
+            {
+                sel.push_back(k); selS.push_back(ss[k]); selOff.push_back(offs[k]);
+                longest = std::max<uint64_t>(longest, hj[k].nFrames);
+                mostFrames = std::max(mostFrames, hj[k].nFrames);
+                selFrames += hj[k].nFrames;
+            }
+        const uint32_t nSel = static_cast<uint32_t>(sel.size());
+        const bool walkOnHost = longest > 2048 && longest * 64 > selFrames;
+        bool staged = false;
+        meas.assign(n, EncMeasure{});
+        firstDec.assign(n, kNotDecoded);
+        if (nSel == 0 && dst != nullptr)
+        {
+            stage.resize(blobLen);
+            ENCCHK(hipMemcpyAsync(stage.data(), dW, blobLen, hipMemcpyDeviceToHost, st));
+            ENCCHK(hipStreamSynchronize(st));
+        }
+        for (int attempt = walkOnHost ? 1 : 0 ; attempt < 2 && nSel != 0 ; ++attempt)
+        {
+            if (attempt == 1 && !staged)
+            {
+                stage.resize(blobLen);
+                ENCCHK(hipMemcpyAsync(stage.data(), dW, blobLen, hipMemcpyDeviceToHost, st));
+                ENCCHK(hipStreamSynchronize(st));
+                staged = true;
+            }
+            DcsSweepDecode *d = nullptr;
+            const int16_t *decPcm = nullptr;
+            const uint32_t *decErr = nullptr, *firstFrame = nullptr;
+            const volatile uint32_t *flag = nullptr;
+            DcsStatus ds = dcsSweepDecodeStart(ctx, selS.data(), nSel, selOff.data(), reinterpret_cast<const uint8_t *>(dW), blobLen,
+                                               attempt == 1 ? stage.data() : nullptr, &d, &decPcm, &decErr, &flag, &firstFrame);
+            bool unusable = false;
+            if (ds == DCS_OK)
+                ds = [&]() -> DcsStatus {
+                    for (uint32_t i = 0 ; i < nSel ; ++i)
+                        firstDec[sel[i]] = firstFrame[i];
+                    ENCCHK(hipMemcpyAsync(dFirstDec, firstDec.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
+                    ENCCHK(hipMemsetAsync(dMeas, 0, sizeof(EncMeasure) * n, st));
+                    hipLaunchKernelGGL(encMeasureKernel, dim3(n, (mostFrames + 1 + kMeasureFrames - 1) / kMeasureFrames), dim3(256), 0, st,
+                                       dPcm, dStr, dJobs, dFirstDec, decPcm, decErr, dMeas);
+                    ENCCHK(hipGetLastError());
+                    ENCCHK(hipMemcpyAsync(meas.data(), dMeas, sizeof(EncMeasure) * n, hipMemcpyDeviceToHost, st));
+                    if (dst != nullptr && !staged)
+                    {
+                        stage.resize(blobLen);
+                        ENCCHK(hipMemcpyAsync(stage.data(), dW, blobLen, hipMemcpyDeviceToHost, st));
+                    }
+                    ENCCHK(hipStreamSynchronize(st));
+                    staged = staged || dst != nullptr;
+                    unusable = flag != nullptr && *flag != 0;
+                    return DCS_OK;
+                }();
+            dcsSweepDecodeRelease(d);
+            if (ds != DCS_OK)
+                return ds;
+            if (!unusable)
+                break;
+        }
+        for (uint32_t k = 0 ; k < n ; ++k)
+        {
+            const uint32_t j = j0 + k;
+            if (meas[k].err != 0)
+            {
+                dcsCtxSetError(ctx, ("job " + std::to_string(j) + " (" + name(hj[k].stream) + ", set " + std::to_string(hj[k].set)
+                                     + "): the decoder reports an error in a frame of the stream just encoded").c_str());
+                return DCS_ERR_HIP;
+            }
+            DcsSweepResult &r = sweep.results[j];
+            if (dst != nullptr)
+                memcpy(dst + outOffsets[j], stage.data() + offs[k], size[j]);
+            if (firstDec[k] == kNotDecoded)
+                continue;
+            r.measured = 1;
+            r.peakErr = meas[k].peak;
+            r.nCompared = hs[hj[k].stream].nSamples;
+            r.sumSrcSq = static_cast<int64_t>(meas[k].srcSq);
+            r.sumDecSq = static_cast<int64_t>(meas[k].decSq);
+            r.sumCross = static_cast<int64_t>(meas[k].cross);
+        }
+        return DCS_OK;
+    };
     DcsStatus status = [&]() -> DcsStatus {
         ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
         ENCCHK(alloc(reinterpret_cast<void **>(&dT), sizeof(EncTabs)));
         if (!dev && !devF)
             ENCCHK(alloc(reinterpret_cast<void **>(&dPcm), sizeof(float) * nSamples));
         ENCCHK(alloc(reinterpret_cast<void **>(&dStr), sizeof(EncStream) * nStreams));
+        ENCCHK(alloc(reinterpret_cast<void **>(&dSets), sizeof(EncSet) * nSets));
         ENCCHK(alloc(reinterpret_cast<void **>(&dFS), sizeof(uint32_t) * F));
         ENCCHK(alloc(reinterpret_cast<void **>(&dSpec), sizeof(float) * 256 * F));
         ENCCHK(alloc(reinterpret_cast<void **>(&dPw), sizeof(float) * 16 * F));
         ENCCHK(alloc(reinterpret_cast<void **>(&dLo), sizeof(float) * 16 * F));
         ENCCHK(alloc(reinterpret_cast<void **>(&dHi), sizeof(float) * 16 * F));
         ENCCHK(alloc(reinterpret_cast<void **>(&dBad), sizeof(uint32_t) * nStreams));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dHdr), 48 * size_t(nStreams)));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dKeep), sizeof(int32_t) * nStreams));
-        if (os93)
+        ENCCHK(alloc(reinterpret_cast<void **>(&dSums), sizeof(float) * 48 * nStreams));
+        // the groups: all jobs in one when that can be had; half the job-frames each time an allocation fails
+        uint64_t limit = gGroupFrames.load() != 0 ? std::max<uint64_t>(gGroupFrames.load(), largest) : allFrames;
+        for (;;)
         {
-            ENCCHK(alloc(reinterpret_cast<void **>(&dRec), sizeof(Enc93Rec) * 32 * size_t(F)));
-            ENCCHK(alloc(reinterpret_cast<void **>(&dBand), sizeof(Enc93Band) * 32 * size_t(F)));
+            makeGroups(limit);
+            const hipError_t e = allocGroup();
+            if (e == hipSuccess)
+                break;
+            group.clear();
+            if (e != hipErrorOutOfMemory || groupFrames <= largest)
+                ENCCHK(e);
+            limit = std::max<uint64_t>(largest, groupFrames / 2);
         }
-        else
-        {
-            ENCCHK(alloc(reinterpret_cast<void **>(&dBest), size_t(128) * F));
-            ENCCHK(alloc(reinterpret_cast<void **>(&dCodes), size_t(48) * F));
-            ENCCHK(alloc(reinterpret_cast<void **>(&dHdrBits), size_t(48) * F));
-            ENCCHK(alloc(reinterpret_cast<void **>(&dSmpBits), sizeof(uint16_t) * 48 * F));
-        }
-        ENCCHK(alloc(reinterpret_cast<void **>(&dFrameBits), sizeof(uint32_t) * 3 * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dFrameOff), sizeof(uint32_t) * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dWin), sizeof(int32_t) * nStreams));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dSize), sizeof(uint64_t) * nStreams));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dOutOff), sizeof(uint64_t) * nStreams));
         ENCCHK(hipMemcpyAsync(dT, &tabs, sizeof(EncTabs), hipMemcpyHostToDevice, st));
         if (!dev && !devF)
             ENCCHK(hipMemcpyAsync(dPcm, in.hostPcm + sampleOffsets[0], sizeof(float) * nSamples, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(EncStream) * nStreams, hipMemcpyHostToDevice, st));
+        ENCCHK(hipMemcpyAsync(dSets, hsets.data(), sizeof(EncSet) * nSets, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dFS, frameStream.data(), sizeof(uint32_t) * F, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * nStreams, st));
-        ENCCHK(hipMemsetAsync(dFrameBits, 0, sizeof(uint32_t) * 3 * F, st));
         if (dev)
             hipLaunchKernelGGL(encAnalyseKernel<int16_t>, dim3((F + 3) / 4), dim3(256), 0, st, dT, in.devPcm + sampleOffsets[0], dStr, dFS, F,
                                dSpec, dPw, dLo, dHi, dBad, in.devErr);
         else
             hipLaunchKernelGGL(encAnalyseKernel<float>, dim3((F + 3) / 4), dim3(256), 0, st, dT, devF ? in.devFloat + sampleOffsets[0] : dPcm,
                                dStr, dFS, F, dSpec, dPw, dLo, dHi, dBad, static_cast<const uint32_t *>(nullptr));
-        hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, dT, dStr, dPw, dLo, dHi, params->powerBandCutoff,
-                           params->targetBitRate, vmask, dHdr, dKeep);
-        if (os93)
-        {
-            hipLaunchKernelGGL(enc93SearchKernel, dim3((F + 3) / 4), dim3(128), 0, st, dT, dSpec, dFS, dHdr, dKeep, vmask, F,
-                               params->maximumQuantizationError, dRec);
-            if (vmask & 1)
-                hipLaunchKernelGGL(enc93WalkKernel<0>, dim3((F + 63) / 64), dim3(64), 0, st, dT, dStr, dFS, dKeep, F, F, dRec, dBand, dFrameBits);
-            if (vmask & 2)
-                hipLaunchKernelGGL(enc93WalkKernel<1>, dim3((nStreams + 63) / 64), dim3(64), 0, st, dT, dStr, dFS, dKeep, F, nStreams, dRec,
-                                   dBand, dFrameBits);
-        }
-        else
-        {
-            ENCCHK(hipMemsetAsync(dBest, 0, size_t(128) * F, st));
-            ENCCHK(hipMemsetAsync(dCodes, 0, size_t(48) * F, st));
-            hipLaunchKernelGGL(encSearchKernel, dim3(F), dim3(128), 0, st, dT, dSpec, dLo, dHi, dFS, dHdr, dKeep, vmask,
-                               params->minimumDynamicRange, params->maximumQuantizationError, dBest);
-            hipLaunchKernelGGL(encChainKernel, dim3(nStreams), dim3(64), 0, st, dT, dStr, dKeep, vmask, F,
-                               reinterpret_cast<const uint64_t *>(dBest), dCodes);
-            hipLaunchKernelGGL(encBitsKernel, dim3(F), dim3(64), 0, st, dT, dSpec, dStr, dFS, dHdr, dKeep, vmask, F, dCodes, dHdrBits, dSmpBits, dFrameBits);
-        }
-        hipLaunchKernelGGL(encSizeKernel, dim3(nStreams), dim3(256), 0, st, dStr, F, cmask, dFrameBits, dWin, dSize, dFrameOff);
-        ENCCHK(hipGetLastError());
+        hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, dStr, dPw, dLo, dHi, dSums);
         ENCCHK(hipMemcpyAsync(bad.data(), dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipMemcpyAsync(win.data(), dWin, sizeof(int32_t) * nStreams, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipMemcpyAsync(keep.data(), dKeep, sizeof(int32_t) * nStreams, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipMemcpyAsync(size.data(), dSize, sizeof(uint64_t) * nStreams, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipStreamSynchronize(st));
-        if (in.planFlag != nullptr && *in.planFlag != 0)
+        const uint32_t nGroups = static_cast<uint32_t>(groupFirst.size()) - 1;
+        for (uint32_t g = 0 ; g < nGroups ; ++g)
         {
-            in.unusable = true;
-            return DCS_ERR_BAD_STREAM;
-        }
-        for (uint32_t i = 0 ; i < nStreams ; ++i)
-            if (bad[i])
+            const DcsStatus gs = runGroup(g);
+            if (gs != DCS_OK)
+                return gs;
+            if (g != 0)
+                continue;
+            if (in.planFlag != nullptr && *in.planFlag != 0)
             {
-                dcsCtxSetError(ctx, (name(i) + (dev ? ": the decoder reports an error in a frame (DCS_FRAME_STOP / DCS_FRAME_FATAL)"
-                                                    : in.bound != nullptr ? ": a sample is not finite or beyond its format's full scale"
-                                                    : ": a sample is not finite or |x| > 1")).c_str());
+                in.unusable = true;
                 return DCS_ERR_BAD_STREAM;
             }
-        outOffsets[0] = 0;
-        for (uint32_t i = 0 ; i < nStreams ; ++i)
-            outOffsets[i + 1] = outOffsets[i] + size[i];
-        if (info != nullptr)
             for (uint32_t i = 0 ; i < nStreams ; ++i)
-                info[i] = DcsEncodeInfo{ ct[win[i]], cs[win[i]], static_cast<int32_t>(hs[i].nFrames), static_cast<int32_t>(size[i]), keep[i] };
-        const uint64_t total = outOffsets[nStreams];
-        uint8_t *dst = place ? place(outOffsets, total) : (out != nullptr && outCap >= total ? out : nullptr);
-        if (dst == nullptr)
-            return DCS_ERR_CAPACITY;
-        const size_t nWords = static_cast<size_t>((total + 3) / 4) + 1;
-        ENCCHK(alloc(reinterpret_cast<void **>(&dW), sizeof(uint32_t) * nWords));
-        ENCCHK(hipMemsetAsync(dW, 0, sizeof(uint32_t) * nWords, st));
-        ENCCHK(hipMemcpyAsync(dOutOff, outOffsets, sizeof(uint64_t) * nStreams, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(encHeadKernel, dim3(nStreams), dim3(64), 0, st, dStr, dHdr, dWin, dOutOff, dW);
-        if (os93)
-            hipLaunchKernelGGL(enc93PackKernel, dim3((F + 3) / 4), dim3(64), 0, st, dT, dSpec, dFS, dHdr, dKeep, dWin, F, dBand,
-                               dFrameOff, dOutOff, dW);
-        else
-            hipLaunchKernelGGL(encPackKernel, dim3((F + 3) / 4), dim3(64), 0, st, dT, dSpec, dStr, dFS, dHdr, dKeep, dWin, F, dCodes,
-                               dHdrBits, dSmpBits, dFrameOff, dOutOff, dW);
-        hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
-        ENCCHK(hipGetLastError());
-        ENCCHK(hipMemcpyAsync(dst, dW, total, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipStreamSynchronize(st));
+                if (bad[i])
+                {
+                    dcsCtxSetError(ctx, (name(i) + (dev ? ": the decoder reports an error in a frame (DCS_FRAME_STOP / DCS_FRAME_FATAL)"
+                                                        : in.bound != nullptr ? ": a sample is not finite or beyond its format's full scale"
+                                                        : ": a sample is not finite or |x| > 1")).c_str());
+                    return DCS_ERR_BAD_STREAM;
+                }
+        }
+        for (uint32_t j = 0 ; j < nJobs ; ++j)
+        {
+            outOffsets[j + 1] = outOffsets[j] + size[j];
+            const DcsEncodeInfo e{ ct[win[j]], cs[win[j]], static_cast<int32_t>(hs[jobList[j].stream].nFrames), static_cast<int32_t>(size[j]), keep[j] };
+            if (info != nullptr)
+                info[j] = e;
+            if (sweep.results != nullptr)
+            {
+                memset(&sweep.results[j], 0, sizeof(DcsSweepResult));       // (its padding too: records compare as bytes)
+                sweep.results[j].enc = e;
+            }
+        }
+        const uint64_t total = outOffsets[nJobs];
+        if (!sweep.sizesOnly)
+        {
+            dst = place ? place(outOffsets, total) : (out != nullptr && outCap >= total ? out : nullptr);
+            if (dst == nullptr)
+                return DCS_ERR_CAPACITY;
+        }
+        if (dst == nullptr && !sweep.measure)
+            return DCS_OK;
+        for (uint32_t g = 0 ; g < nGroups ; ++g)
+        {
+            DcsStatus gs = resident == g ? DCS_OK : runGroup(g);
+            if (gs == DCS_OK)
+                gs = packGroup(g);
+            if (gs != DCS_OK)
+                return gs;
+        }
         return DCS_OK;
     }();
     (void)hipStreamSynchronize(st);
+    wBuf.release();
+    for (CacheBuf &h : group)
+        h.release();
     for (CacheBuf &h : held)
         h.release();
     return status;
+}
+
+// the entry points that encode every stream with one parameter set: job i = (stream i, set 0)
+DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets, uint32_t nStreams,
+                        const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info,
+                        bool os93, const EncPlace &place = nullptr)
+{
+    const bool dev = in.devPcm != nullptr, devF = in.devFloat != nullptr;
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && in.hostPcm == nullptr && !dev && !devF)
+        || (dev && in.devErr == nullptr))
+        return DCS_ERR_INVALID_ARG;
+    if (!paramsValid(params, os93))
+    {
+        if (os93 && params != nullptr && params->formatVersion == 0x9301 && params->streamFormatType == 1)
+            dcsCtxSetError(ctx, "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0");
+        return DCS_ERR_INVALID_ARG;
+    }
+    std::vector<DcsSweepJob> jobs(nStreams);
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+        jobs[i] = DcsSweepJob{ i, 0 };
+    return encodeJobs(ctx, in, sampleOffsets, nStreams, params, 1, jobs.data(), nStreams, os93, out, outCap, outOffsets, info, EncSweep(), place);
 }
 
 }  // namespace
@@ -1359,6 +1752,108 @@ extern "C" DcsStatus dcs_encode93_streams(DcsCtx *ctx, const float *pcm, const u
     EncInput in;
     in.hostPcm = pcm;
     return encodeStreams(ctx, in, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, true);
+}
+
+// ------------------------------------------------------------------------------------------------------- sweeping and fitting
+
+extern "C" void dcs_encode_sweep_group_frames(uint64_t maxJobFrames)
+{
+    gGroupFrames.store(maxJobFrames);
+}
+
+extern "C" DcsStatus dcs_encode_sweep(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                      const DcsEncodeParams *sets, uint32_t nSets, const DcsSweepJob *jobs, uint32_t nJobs,
+                                      uint32_t flags, DcsSweepResult *results, uint8_t *out, size_t outCap, uint64_t *outOffsets)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || sets == nullptr || nSets == 0 || (nStreams != 0 && pcm == nullptr)
+        || (flags & ~DCS_SWEEP_MEASURE) != 0 || ((flags & DCS_SWEEP_MEASURE) != 0 && results == nullptr) || (out == nullptr && outCap != 0))
+        return DCS_ERR_INVALID_ARG;
+    const bool os93 = sets[0].formatVersion != 0x9400;
+    for (uint32_t k = 0 ; k < nSets ; ++k)
+    {
+        if (sets[k].formatVersion != sets[0].formatVersion)
+        {
+            dcsCtxSetError(ctx, ("set " + std::to_string(k) + ": the sets of one call belong to one encoder (all formatVersion 0x9400, all 0x9301 or all 0x9302)").c_str());
+            return DCS_ERR_INVALID_ARG;
+        }
+        if (!paramsValid(&sets[k], os93))
+        {
+            dcsCtxSetError(ctx, os93 && sets[k].formatVersion == 0x9301 && sets[k].streamFormatType == 1
+                                    ? "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0"
+                                    : ("set " + std::to_string(k) + ": not a valid DcsEncodeParams").c_str());
+            return DCS_ERR_INVALID_ARG;
+        }
+    }
+    std::vector<DcsSweepJob> all;
+    if (jobs == nullptr)
+    {
+        if (static_cast<uint64_t>(nStreams) * nSets > 0xFFFFFFFFull)
+            return DCS_ERR_INVALID_ARG;
+        nJobs = nStreams * nSets;
+        all.resize(nJobs);
+        for (uint32_t j = 0 ; j < nJobs ; ++j)
+            all[j] = DcsSweepJob{ j / nSets, j % nSets };
+        jobs = all.data();
+    }
+    for (uint32_t j = 0 ; j < nJobs ; ++j)
+        if (jobs[j].stream >= nStreams || jobs[j].paramSet >= nSets)
+        {
+            dcsCtxSetError(ctx, ("job " + std::to_string(j) + ": names stream " + std::to_string(jobs[j].stream) + " of " + std::to_string(nStreams)
+                                 + ", set " + std::to_string(jobs[j].paramSet) + " of " + std::to_string(nSets)).c_str());
+            return DCS_ERR_INVALID_ARG;
+        }
+    EncInput in;
+    in.hostPcm = pcm;
+    EncSweep sweep;
+    sweep.results = results;
+    sweep.measure = (flags & DCS_SWEEP_MEASURE) != 0;
+    sweep.sizesOnly = out == nullptr;
+    return encodeJobs(ctx, in, sampleOffsets, nStreams, sets, nSets, jobs, nJobs, os93, out, outCap, outOffsets, nullptr, sweep, nullptr);
+}
+
+extern "C" DcsStatus dcs_encode_fit(const uint64_t *nBytes, const uint64_t *sqErr, uint32_t nStreams, uint32_t nSets, uint64_t budget,
+                                    int32_t *choiceOut, uint64_t *totalOut)
+{
+    if (nBytes == nullptr || sqErr == nullptr || nStreams == 0 || nSets == 0 || choiceOut == nullptr || totalOut == nullptr)
+        return DCS_ERR_INVALID_ARG;
+    auto at = [nSets](const uint64_t *t, uint32_t i, uint32_t r) { return t[static_cast<size_t>(i) * nSets + r]; };
+    // the first set, in the caller's order of preference, that fits as a whole
+    uint32_t r = nSets, smallest = 0;
+    uint64_t total = 0, smallestTotal = 0;
+    for (uint32_t c = 0 ; c < nSets && r == nSets ; ++c)
+    {
+        uint64_t sum = 0;
+        for (uint32_t i = 0 ; i < nStreams ; ++i)
+            sum += at(nBytes, i, c);
+        if (c == 0 || sum < smallestTotal) { smallest = c; smallestTotal = sum; }
+        if (sum <= budget) { r = c; total = sum; }
+    }
+    if (r == nSets)
+    {
+        for (uint32_t i = 0 ; i < nStreams ; ++i)
+            choiceOut[i] = static_cast<int32_t>(smallest);
+        *totalOut = smallestTotal;
+        return DCS_ERR_CAPACITY;
+    }
+    // the streams by descending error at r (ties: ascending index), each moved once to the first more preferred set that
+    // lowers its error and still fits
+    std::vector<uint32_t> order(nStreams);
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+    {
+        order[i] = i;
+        choiceOut[i] = static_cast<int32_t>(r);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return at(sqErr, a, r) > at(sqErr, b, r); });
+    for (uint32_t i : order)
+        for (uint32_t c = 0 ; c < r ; ++c)
+            if (at(sqErr, i, c) < at(sqErr, i, r) && total - at(nBytes, i, r) + at(nBytes, i, c) <= budget)
+            {
+                total = total - at(nBytes, i, r) + at(nBytes, i, c);
+                choiceOut[i] = static_cast<int32_t>(c);
+                break;
+            }
+    *totalOut = total;
+    return DCS_OK;
 }
 
 // ----------------------------------------------------------------------------------------- transcoding (dcs_transcode.hip.h)

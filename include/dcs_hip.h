@@ -40,7 +40,9 @@ extern "C" {
                                           DCS_RESAMPLE_AT_UNITY, dcs_resample_filter_default, dcs_resample_count,
                                           dcs_resample_streams, dcs_encode_streams_at); encoding files (DcsWavInfo,
                                           DcsEncodeFileInfo, DCS_WAV_*, DCS_FILE_*, dcs_wav_parse, dcs_wav_decode,
-                                          dcs_encode_files_plan, dcs_encode_files) */
+                                          dcs_encode_files_plan, dcs_encode_files); sweeping and fitting (DcsSweepJob,
+                                          DcsSweepResult, DCS_SWEEP_MEASURE, dcs_encode_sweep,
+                                          dcs_encode_sweep_group_frames, dcs_encode_fit) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -977,6 +979,60 @@ DcsStatus dcs_wav_decode(DcsCtx *ctx, const uint8_t *files, const uint64_t *file
 DcsStatus dcs_encode_files(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
                            const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out,
                            size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sweeping parameters and fitting a byte budget.  A JOB is one stream encoded with one parameter set.  dcs_encode_sweep
+ * encodes a list of jobs in one call: the PCM goes up once, the analysis of a stream (its spectrum, power and range per
+ * frame) runs once however many sets it is encoded with, and everything that reads the parameters runs per job.  Job j's
+ * bytes and `enc` are exactly what dcs_encode_streams / dcs_encode93_streams return for that stream alone with that set.
+ *   sets    nSets >= 1 parameter sets of ONE encoder: all formatVersion 0x9400, or all 0x9301, or all 0x9302 (anything else
+ *           is DCS_ERR_INVALID_ARG); each is checked as that encoder's entry point checks it, wildcards included.
+ *   jobs    nJobs (stream, paramSet) pairs in any order, repeats allowed; NULL = every pair, stream-major
+ *           (job = stream * nSets + paramSet; nJobs is ignored).  One job per stream = per-stream parameters.
+ *   out     job j at out + outOffsets[j]; outOffsets has nJobs + 1 entries and is filled whenever the encodes ran.
+ *           out == NULL with outCap == 0: sizes (and measurements) only, DCS_OK, nothing is packed for the host.
+ *           Otherwise DCS_ERR_CAPACITY when outCap < outOffsets[nJobs], as dcs_encode_streams.
+ *   results nJobs records (may be NULL without DCS_SWEEP_MEASURE).
+ * DCS_SWEEP_MEASURE: every job's stream is decoded on the device where the encoder packed it (nothing PCM-sized crosses
+ * PCIe) and compared with its source.  The decode is a fresh decoder's, nFrames + 1 frames (dcs_decode_streams with
+ * extraFrames = 1), OS by the stream written (0x9400 sub-type 0: OS94, sub-type 3: OS95; 0x9301: OS93A; 0x9302: OS93B),
+ * volume, mixing level and channel volume 0xFF: the decoder's unity setting.  The decoded signal lags the source by 16
+ * samples (the frames' overlap).  With q[k] = clamp(rint(x[k] * 32768), -32768, 32767) (ties to even) and
+ * d[k] = decoded[k + 16], over k in [0, nSamples): sumSrcSq = sum q*q, sumDecSq = sum d*d, sumCross = sum d*q,
+ * peakErr = max |d - q|.  The squared error at unity is sumDecSq - 2 sumCross + sumSrcSq; the least-squares gain of the
+ * decode is sumCross / sumSrcSq.  All are exact integers.  A stream of 65 535 frames cannot be decoded with the extra frame:
+ * DCS_ERR_INVALID_ARG for the call, the stream named.  A decode error word in a frame of the library's own stream is
+ * DCS_ERR_HIP with the job named.  Stream errors are dcs_encode_streams'.  One kind of stream is not decoded and keeps
+ * measured = 0: an OS93a stream with bandsToKeep 0.  Its header is sixteen 0xFF bytes, whose first carries the type bit,
+ * so every decoder reads it as OS93a Type 1 with 31 bands (the reference encoder writes it all the same).
+ * Memory: 1.2 KB per stream-frame and about 350 bytes (1994+) or 1.2 KB (OS93) per job-frame, plus 480 bytes per job-frame
+ * while measuring.  When an allocation fails the jobs are processed in groups, runs of the job list, the analysis kept. */
+typedef struct DcsSweepJob    { uint32_t stream; uint32_t paramSet; } DcsSweepJob;
+typedef struct DcsSweepResult
+{
+    DcsEncodeInfo enc;                 /* what dcs_encode_streams / dcs_encode93_streams report for this stream and set   */
+    uint32_t measured;                 /* 1 when the sums below are valid (DCS_SWEEP_MEASURE)                             */
+    int32_t  peakErr;                  /* max |d - q|                                                                     */
+    uint64_t nCompared;                /* the stream's sample count                                                       */
+    int64_t  sumSrcSq, sumDecSq, sumCross;
+} DcsSweepResult;
+#define DCS_SWEEP_MEASURE 1u
+DcsStatus dcs_encode_sweep(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                           const DcsEncodeParams *sets, uint32_t nSets, const DcsSweepJob *jobs, uint32_t nJobs,
+                           uint32_t flags, DcsSweepResult *results, uint8_t *out, size_t outCap, uint64_t *outOffsets);
+/* Process-wide: the most job-frames a group of any encode may hold (0, the default: as many as the memory takes; a job
+ * is never split, so the longest job is the floor).  Results do not depend on it.  For callers that share a card, and for
+ * testing the grouped path without filling the memory. */
+void      dcs_encode_sweep_group_frames(uint64_t maxJobFrames);
+/* Host only, no GPU: a parameter set per stream under a byte budget, from tables [nStreams][nSets] of sizes and squared
+ * errors whose sets are in the caller's order of preference, most preferred first.  (1) r = the first set whose column
+ * total is <= budget; none: DCS_ERR_CAPACITY, *totalOut = the smallest column total, choiceOut = that column (the first on
+ * a tie).  (2) Every stream starts at r; the streams are then visited once, by descending sqErr[i][r] (ties: ascending
+ * i); stream i moves to the first r' < r with sqErr[i][r'] < sqErr[i][r] whose bytes keep the total within the budget,
+ * and the total is updated at once.  Deterministic and simple; not an optimal (knapsack) allocation.
+ * DCS_ERR_INVALID_ARG: nStreams or nSets 0, a NULL pointer. */
+DcsStatus dcs_encode_fit(const uint64_t *nBytes, const uint64_t *sqErr, uint32_t nStreams, uint32_t nSets, uint64_t budget,
+                         int32_t *choiceOut, uint64_t *totalOut);
 
 uint32_t dcs_abi_version(void);
 /* a digest of the sources and compiler flags this library was built from (16 hex digits).  Counter profiles under
