@@ -1,10 +1,13 @@
 // dcs_cache.h -- CacheBuf, the one owner of a buffer borrowed from a context's buffer cache (dcs_runtime.hip: cacheAlloc /
 // cacheFree).  The cache knows the real size of every buffer it handed out, so the owner keeps only what it asked for.
+// CacheArena, the owner of all the buffers that one call borrows for work on the context's stream.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <vector>
 
 struct DcsCtx;
+hipStream_t dcsCtxStream(DcsCtx *ctx);
 hipError_t dcsCtxAlloc(DcsCtx *ctx, bool pinned, void **out, size_t bytes);
 void dcsCtxFree(DcsCtx *ctx, bool pinned, void *p);
 
@@ -47,4 +50,48 @@ private:
     void *p_ = nullptr;
     size_t bytes_ = 0;
     bool pinned_ = false;
+};
+
+// The device buffers of one call.  Move-only.  What the type is for is how they go back: an arena that still holds
+// something when it goes waits for the context's stream (kernels and copies queued there may be using them) and then gives
+// them back in the order they were taken, which is the order the cache will evict them in.  clear() gives them back at
+// once, for buffers nothing was queued on; an owner of several arenas that must go back after ONE wait calls wait() and
+// then clear() on each, in the order it wants them back.
+class CacheArena
+{
+public:
+    explicit CacheArena(DcsCtx *ctx) : ctx_(ctx), stream_(dcsCtxStream(ctx)) {}
+    CacheArena(const CacheArena &) = delete;
+    CacheArena &operator=(const CacheArena &) = delete;
+    CacheArena(CacheArena &&) = default;            // (what it is moved from holds nothing, and goes without a wait)
+    ~CacheArena()
+    {
+        if (!bufs_.empty())
+            wait();
+        clear();
+    }
+
+    // `count` objects of T in device memory, the byte count rounded up to 256; *p is null on failure
+    template <class T> hipError_t alloc(T **p, size_t count)
+    {
+        bufs_.emplace_back();
+        const hipError_t e = bufs_.back().alloc(ctx_, false, (sizeof(T) * count + 255) & ~size_t(255));
+        *p = bufs_.back().as<T>();
+        return e;
+    }
+    void wait() const { (void)hipStreamSynchronize(stream_); }
+    void clear()
+    {
+        for (CacheBuf &b : bufs_)
+            b.release();
+        bufs_.clear();
+    }
+    bool empty() const { return bufs_.empty(); }
+    DcsCtx *ctx() const { return ctx_; }
+    hipStream_t stream() const { return stream_; }
+
+private:
+    DcsCtx *ctx_;
+    hipStream_t stream_;
+    std::vector<CacheBuf> bufs_;
 };

@@ -319,7 +319,7 @@ struct EncStream { uint64_t sampleOff; uint32_t nSamples, firstFrame, nFrames, e
 // frame offsets) start at firstFrame; row k reads frame specFirst + k of E1's output (specFirst = its stream's firstFrame).
 struct EncJob { uint32_t stream, set, firstFrame, nFrames, specFirst; };
 
-// what the kernels read of a DcsEncodeParams: vmask = the layouts to compute, cmask = CloseStream's candidates (encodeJobs)
+// what the kernels read of a DcsEncodeParams: vmask = the layouts to compute, cmask = CloseStream's candidates (EncRun::buildSets)
 struct EncSet { float cutoff, minDR, maxQE; int32_t rate; uint32_t vmask, cmask; };
 
 // the frame of E1's output that row f of the per-job-frame buffers reads
@@ -1104,6 +1104,13 @@ bool paramsValid(const DcsEncodeParams *p, bool os93)
         && !(p->formatVersion == 0x9301 && p->streamFormatType == 1);
 }
 
+// the message for a set that paramsValid refuses because it asks for OS93a Type 1 (null: it was refused for another reason)
+const char *whyOs93aType1(const DcsEncodeParams *p, bool os93)
+{
+    return os93 && p != nullptr && p->formatVersion == 0x9301 && p->streamFormatType == 1
+        ? "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0" : nullptr;
+}
+
 const uint32_t kMaxBitsPerFrame = 16 * 23 + 255 * 15;      // every band at its longest header code and widest samples
 // OS93, every band at its longest flag and type code and widest samples: Type 1 (1 + 30 bits, 15-bit samples, 15 in
 // band 0) = 4 321 bits, more than Type 0 (1 + 2 + 4 bits, 16 x 16-bit samples) = 4 208
@@ -1254,9 +1261,11 @@ __global__ __launch_bounds__(256) void encMeasureKernel(const float *__restrict_
 // resampler's float output, resident on the device (dcs_encode_streams_at, dcs_resample.hip.h)
 struct EncInput
 {
+    const uint64_t *sampleOffsets = nullptr;    // stream i = samples [sampleOffsets[i], sampleOffsets[i + 1]) of the one that is set:
+    uint32_t nStreams = 0;
     const float *hostPcm = nullptr;
-    const float *devFloat = nullptr;        // stream i starts at sample sampleOffsets[i]
-    const int16_t *devPcm = nullptr;        // stream i starts at sample sampleOffsets[i], a multiple of 240 ...
+    const float *devFloat = nullptr;
+    const int16_t *devPcm = nullptr;        // sampleOffsets[i] a multiple of 240 ...
     const uint32_t *devErr = nullptr;       // ... and its frames' error words at sampleOffsets[i] / 240
     const uint32_t *label = nullptr;        // the number a message gives stream i (null: i)
     const float *bound = nullptr;           // the largest |x| stream i may hold (null: 1; dcs_encode_files, INTEGRATION rule 12)
@@ -1264,8 +1273,28 @@ struct EncInput
     bool unusable = false;                  // (out) planFlag was set: DCS_ERR_BAD_STREAM, and nothing was written
 };
 
+// the jobs of a call: job j = (stream list[j].stream, set list[j].paramSet), every set of the one encoder `os93` names
+struct EncJobs
+{
+    const DcsEncodeParams *sets;
+    uint32_t nSets;
+    const DcsSweepJob *list;
+    uint32_t n;
+    bool os93;
+};
+
 // after the sizes are known: the host memory that takes the `total` bytes (stream i at outOffsets[i]), or null for DCS_ERR_CAPACITY
 using EncPlace = std::function<uint8_t *(const uint64_t *outOffsets, uint64_t total)>;
+
+// where a call's streams and what is known of them go
+struct EncOutput
+{
+    uint8_t *out = nullptr;                 // the caller's buffer of outCap bytes, where `place` is not given
+    size_t outCap = 0;
+    uint64_t *outOffsets = nullptr;         // nJobs + 1
+    DcsEncodeInfo *info = nullptr;          // nJobs, or null
+    const EncPlace *place = nullptr;
+};
 
 // what dcs_encode_sweep asks of the driver beyond a list of jobs
 struct EncSweep
@@ -1278,29 +1307,171 @@ struct EncSweep
 // most job-frames a group may hold (0: what the memory takes); dcs_encode_sweep_group_frames
 std::atomic<uint64_t> gGroupFrames{ 0 };
 
-// The one host driver behind every encode.  A job is (stream, parameter set); dcs_encode_streams and its kin are one job per
-// stream with one set.  Validation of the streams, E1 and the sums of E2 once per stream; then the jobs in groups, runs of the
-// job list whose per-job-frame buffers fit the memory (one group unless an allocation fails or a cap is set): the header
-// half of E2, the family's band stages and the sizes per group, the capacity check once every size is known, then header,
-// pack and swap per group (a group that is no longer resident is computed again), and with sweep.measure the group's
-// streams decoded where the pack step left them and compared with their sources.  Returns after the stream is idle.
-DcsStatus encodeJobs(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets, uint32_t nStreams, const DcsEncodeParams *sets,
-                     uint32_t nSets, const DcsSweepJob *jobList, uint32_t nJobs, bool os93, uint8_t *out, size_t outCap,
-                     uint64_t *outOffsets, DcsEncodeInfo *info, const EncSweep &sweep, const EncPlace &place)
+const int kCandType[4] = { 0, 0, 1, 1 }, kCandSub[4] = { 0, 3, 0, 3 };     // candidates in CloseStream's order (0,0), (0,3), (1,0), (1,3)
+
+#define HIPTRY(call)                                                                                 \
+    do {                                                                                             \
+        const hipError_t e_ = (call);                                                                \
+        if (e_ != hipSuccess)                                                                        \
+            return e_;                                                                               \
+    } while (0)
+#define ENCTRY(call)                                                                                 \
+    do {                                                                                             \
+        const DcsStatus s_ = (call);                                                                 \
+        if (s_ != DCS_OK)                                                                            \
+            return s_;                                                                               \
+    } while (0)
+
+// a decode queued by dcsSweepDecodeStart, released (which waits for the stream) on every way out of its scope
+struct SweepDecodeGuard
 {
-    const bool dev = in.devPcm != nullptr, devF = in.devFloat != nullptr;
-    auto name = [&](uint32_t i) { return "stream " + std::to_string(in.label ? in.label[i] : i); };
-    std::vector<EncStream> hs(nStreams);
-    std::vector<uint32_t> frameStream;
-    uint32_t F = 0;
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
+    DcsSweepDecode *d = nullptr;
+    ~SweepDecodeGuard() { dcsSweepDecodeRelease(d); }
+};
+
+// The one host driver behind every encode, as an object that lives for one call.  A job is (stream, parameter set);
+// dcs_encode_streams and its kin are one job per stream with one set.  run() strings the steps together, each a member
+// function below, in this order:
+//   checkStreams   the streams' lengths, before anything is written; then the empty call's zeros, before any HIP call
+//   buildSets      the parameter sets as the kernels read them, and which layouts any of them asks for
+//   allocCall      the buffers that live as long as the call (CallBufs)
+//   allocGroups    the jobs in groups, runs of the job list whose per-job-frame buffers (GroupBufs, sized for the largest
+//                  group) fit the memory: makeGroups + allocGroup, one group unless a cap is set or an allocation fails
+//   analyse        upload, E1 and the sums of E2, once per stream
+//   runGroup       per group: the header half of E2, the family's band stages and the sizes, and a wait, after which win,
+//                  keep and size of its jobs are on the host.  After the first group's wait, checkInput: planFlag, then bad[]
+//   placeOutput    once every size is known: outOffsets, info, results, and the memory the bytes go to (the capacity check)
+//   packGroup      per group again (one that is no longer resident is first computed again by runGroup): layout, header,
+//                  pack and swap into the group's blob on the device; then one of
+//   deliverGroup   the blob to its place in the output, or with sweep.measure
+//   measureGroup   the group's streams decoded where the pack step left them and compared with their sources (M1), the
+//                  blob staged on the host when the decode or the output needs it there (stageBlob)
+// Three lifetimes of device memory: `call`, `group` (emptied when an allocation attempt fails) and `blob` (taken anew for
+// every group).  The destructor waits for the stream once and gives back blob, group, call, in that order.
+class EncRun
+{
+public:
+    EncRun(DcsCtx *ctx, EncInput &in, const EncJobs &jobs, const EncOutput &to, const EncSweep &sweep)
+        : ctx(ctx), st(dcsCtxStream(ctx)), in(in), jobs(jobs), to(to), sweep(sweep), dev(in.devPcm != nullptr),
+          devF(in.devFloat != nullptr), call(ctx), group(ctx), blob(ctx) {}
+    ~EncRun()
     {
-        if (sampleOffsets[i + 1] <= sampleOffsets[i])
+        if (!call.empty())
+            call.wait();
+        blob.clear();
+        group.clear();
+        call.clear();
+    }
+    DcsStatus run();
+
+private:
+    DcsStatus checkStreams();
+    void buildSets();
+    DcsStatus allocCall();
+    void makeGroups(uint64_t limit);
+    hipError_t allocGroup();
+    DcsStatus allocGroups();
+    DcsStatus analyse();
+    DcsStatus runGroup(uint32_t g);
+    DcsStatus checkInput();
+    DcsStatus placeOutput();
+    DcsStatus layoutGroup(uint32_t g, size_t *nWords);
+    DcsStatus packGroup(uint32_t g);
+    DcsStatus deliverGroup(uint32_t g);
+    DcsStatus stageBlob();
+    void selectDecodes(uint32_t n);
+    DcsStatus decodeAndCompare(uint32_t n, bool onHost, bool *unusable);
+    DcsStatus reportGroup(uint32_t g);
+    DcsStatus measureGroup(uint32_t g);
+    std::string name(uint32_t i) const { return "stream " + std::to_string(in.label ? in.label[i] : i); }
+
+    // ---- fixed by the arguments
+    DcsCtx *const ctx;
+    const hipStream_t st;
+    EncInput &in;
+    const EncJobs jobs;
+    const EncOutput to;
+    const EncSweep sweep;
+    const bool dev, devF;                       // the input is a decode batch's int16 PCM / float PCM on the device
+    std::vector<EncStream> hs;                  // (checkStreams)
+    std::vector<uint32_t> frameStream;
+    uint32_t F = 0;                             // frames of all streams
+    std::vector<EncSet> hsets;                  // (buildSets)
+    uint32_t anyV = 0;                          // the layouts any set asks for: bit 0 Type 0, bit 1 (1, 0), bit 2 (1, 3)
+    uint64_t allFrames = 0, largest = 0;        // job-frames of all jobs, of the largest job
+
+    // ---- device buffers of the call: valid from allocCall to the end
+    struct CallBufs
+    {
+        EncTabs *dT;
+        float *dPcm = nullptr;                  // the host's PCM uploaded (null where the input is on the device)
+        EncStream *dStr;
+        EncSet *dSets;
+        uint32_t *dFS;                          // frame -> stream
+        float *dSpec, *dPw, *dLo, *dHi;         // E1's output per frame
+        uint32_t *dBad;                         // per stream: a sample E1 refused
+        float *dSums;                           // E2's sums per stream
+    } cb;
+    CacheArena call;
+
+    // ---- device buffers of a group, sized for the largest one: valid from allocGroups to the end, their CONTENT that of
+    // the resident group (runGroup), dOutOff of the group packed last
+    struct GroupBufs
+    {
+        EncJob *dJobs;
+        uint32_t *dFJ;                          // job-frame -> job of the group
+        uint8_t *dHdr;
+        int32_t *dKeep, *dWin;
+        uint64_t *dSize, *dOutOff;
+        uint32_t *dFrameBits, *dFrameOff;
+        struct { Enc93Rec *dRec = nullptr; Enc93Band *dBand = nullptr; } o93;                       // OS93 only (O3-O5)
+        struct { uint8_t *dBest = nullptr, *dCodes = nullptr, *dHdrBits = nullptr; uint16_t *dSmpBits = nullptr; } v94;   // 1994+ only (E3-E5)
+        struct { EncMeasure *dMeas = nullptr; uint32_t *dFirstDec = nullptr; } m;                   // sweep.measure only (M1)
+    } gb;
+    CacheArena group;
+
+    // ---- the groups, and what is known of every job once its group has run
+    std::vector<uint32_t> groupFirst;           // group g = jobs [groupFirst[g], groupFirst[g + 1])
+    uint64_t groupFrames = 0;                   // the largest group's job-frames ...
+    uint32_t groupJobs = 0;                     // ... and the most jobs in a group
+    uint32_t resident = ~0u, residentFrames = 0;    // the group whose rows the group buffers hold, and its job-frames
+    std::vector<EncJob> hj;                     // the resident group's jobs ...
+    std::vector<uint32_t> frameJob;             // ... and rows
+    std::vector<int32_t> win, keep;             // per job (runGroup)
+    std::vector<uint64_t> size;
+    std::vector<uint32_t> bad;                  // per stream, on the host after the first group's wait
+    uint8_t *dst = nullptr;                     // where the bytes go (placeOutput); null: nowhere
+
+    // ---- the packed group: valid from packGroup to the next one
+    CacheArena blob;
+    uint32_t *dW = nullptr;                     // the blob, big-endian after the swap
+    size_t blobLen = 0;
+    std::vector<uint64_t> offs;                 // job k of the group at blob byte offs[k]
+    std::vector<DcsSweepStream> ss;             // (sweep.measure) what the decoder is told of each
+    std::vector<uint8_t> stage;                 // the blob on the host ...
+    bool staged = false;                        // ... once stageBlob has run for this group
+
+    // ---- measureGroup's own
+    std::vector<uint32_t> sel, firstDec;        // the jobs of the group that are decoded; per job its first decoded frame
+    std::vector<DcsSweepStream> selS;
+    std::vector<uint64_t> selOff;
+    uint32_t mostFrames = 0;                    // of the selected jobs: the longest ...
+    uint64_t selFrames = 0;                     // ... and all of them
+    std::vector<EncMeasure> meas;
+};
+
+DcsStatus EncRun::checkStreams()
+{
+    hs.resize(in.nStreams);
+    for (uint32_t i = 0 ; i < in.nStreams ; ++i)
+    {
+        const uint64_t *so = in.sampleOffsets;
+        if (so[i + 1] <= so[i])
         {
             dcsCtxSetError(ctx, (name(i) + ": empty").c_str());
             return DCS_ERR_INVALID_ARG;
         }
-        const uint64_t n = sampleOffsets[i + 1] - sampleOffsets[i];
+        const uint64_t n = so[i + 1] - so[i];
         const uint64_t nF = (n + 239) / 240;
         if (nF > 65535)
         {
@@ -1312,426 +1483,487 @@ DcsStatus encodeJobs(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets, u
             dcsCtxSetError(ctx, (name(i) + ": 65 535 frames; measured with the extra frame its decode would need 65 536, more than the frame count holds").c_str());
             return DCS_ERR_INVALID_ARG;
         }
-        hs[i] = EncStream{ sampleOffsets[i] - sampleOffsets[0], static_cast<uint32_t>(n), F, static_cast<uint32_t>(nF),
-                           dev ? static_cast<uint32_t>(sampleOffsets[i] / 240) : 0u, in.bound != nullptr ? in.bound[i] : 1.0f };
+        hs[i] = EncStream{ so[i] - so[0], static_cast<uint32_t>(n), F, static_cast<uint32_t>(nF),
+                           dev ? static_cast<uint32_t>(so[i] / 240) : 0u, in.bound != nullptr ? in.bound[i] : 1.0f };
         frameStream.insert(frameStream.end(), static_cast<size_t>(nF), i);
         F += static_cast<uint32_t>(nF);
     }
-    outOffsets[0] = 0;
-    if (nStreams == 0 || nJobs == 0)
+    return DCS_OK;
+}
+
+void EncRun::buildSets()
+{
+    hsets.resize(jobs.nSets);
+    for (uint32_t k = 0 ; k < jobs.nSets ; ++k)
     {
-        for (uint32_t j = 0 ; j < nJobs ; ++j)
-            outOffsets[j + 1] = 0;
-        return DCS_OK;
-    }
-    const int ct[4] = { 0, 0, 1, 1 }, cs[4] = { 0, 3, 0, 3 };      // candidates in CloseStream's order (0,0), (0,3), (1,0), (1,3)
-    std::vector<EncSet> hsets(nSets);
-    uint32_t anyV = 0;
-    for (uint32_t k = 0 ; k < nSets ; ++k)
-    {
-        const DcsEncodeParams &p = sets[k];
-        const int typ = p.streamFormatType, sub = os93 ? 0 : p.streamFormatSubType;
+        const DcsEncodeParams &p = jobs.sets[k];
+        const int typ = p.streamFormatType, sub = jobs.os93 ? 0 : p.streamFormatSubType;
         uint32_t cmask = 0;
         for (int c = 0 ; c < 4 ; ++c)
-            if ((typ < 0 || typ == ct[c]) && (sub < 0 || sub == cs[c]) && !(os93 && p.formatVersion == 0x9301 && ct[c] == 1))
+            if ((typ < 0 || typ == kCandType[c]) && (sub < 0 || sub == kCandSub[c])
+                && !(jobs.os93 && p.formatVersion == 0x9301 && kCandType[c] == 1))
                 cmask |= 1u << c;
         const uint32_t vmask = ((cmask & 3) ? 1u : 0u) | ((cmask & 4) ? 2u : 0u) | ((cmask & 8) ? 4u : 0u);
         hsets[k] = EncSet{ p.powerBandCutoff, p.minimumDynamicRange, p.maximumQuantizationError, p.targetBitRate, vmask, cmask };
         anyV |= vmask;
     }
-    // the groups: runs of the job list of at most `limit` job-frames, a job never split
-    uint64_t allFrames = 0, largest = 0;
-    for (uint32_t j = 0 ; j < nJobs ; ++j)
+    for (uint32_t j = 0 ; j < jobs.n ; ++j)
     {
-        const uint64_t nF = hs[jobList[j].stream].nFrames;
+        const uint64_t nF = hs[jobs.list[j].stream].nFrames;
         allFrames += nF;
         largest = nF > largest ? nF : largest;
     }
-    std::vector<uint32_t> groupFirst;           // group g = jobs [groupFirst[g], groupFirst[g + 1])
-    uint64_t groupFrames = 0;                   // the largest group's job-frames ...
-    uint32_t groupJobs = 0;                     // ... and the most jobs in a group
-    auto makeGroups = [&](uint64_t limit) {
-        groupFirst.assign(1, 0);
-        groupFrames = 0; groupJobs = 0;
-        uint64_t inGroup = 0;
-        for (uint32_t j = 0 ; j < nJobs ; ++j)
-        {
-            const uint64_t nF = hs[jobList[j].stream].nFrames;
-            if ((inGroup != 0 && inGroup + nF > limit) || inGroup + nF > 0xFFFFFFFFull)
-            {
-                groupFirst.push_back(j);
-                inGroup = 0;
-            }
-            inGroup += nF;
-            groupFrames = inGroup > groupFrames ? inGroup : groupFrames;
-            groupJobs = std::max(groupJobs, j + 1 - groupFirst.back());
-        }
-        groupFirst.push_back(nJobs);
-    };
-    const uint64_t nSamples = sampleOffsets[nStreams] - sampleOffsets[0];
-    const EncTabs &tabs = os93 ? encTabs93() : encTabs();
+}
 
-    const hipStream_t st = dcsCtxStream(ctx);
-    std::vector<CacheBuf> held, group;
-    auto allocIn = [&](std::vector<CacheBuf> &own, void **p, size_t bytes) -> hipError_t {
-        own.emplace_back();
-        const hipError_t e = own.back().alloc(ctx, false, (bytes + 255) & ~size_t(255));
-        *p = own.back().as();
-        return e;
-    };
-    auto alloc = [&](void **p, size_t bytes) -> hipError_t { return allocIn(held, p, bytes); };
-    EncTabs *dT; float *dPcm = nullptr, *dSpec, *dPw, *dLo, *dHi, *dSums; EncStream *dStr; EncSet *dSets; uint32_t *dFS, *dBad;
-    EncJob *dJobs = nullptr; uint32_t *dFJ = nullptr, *dFrameBits = nullptr, *dFrameOff = nullptr, *dFirstDec = nullptr;
-    uint8_t *dHdr = nullptr, *dBest = nullptr, *dCodes = nullptr, *dHdrBits = nullptr; uint16_t *dSmpBits = nullptr;
-    Enc93Rec *dRec = nullptr; Enc93Band *dBand = nullptr; int32_t *dKeep = nullptr, *dWin = nullptr; uint64_t *dSize = nullptr, *dOutOff = nullptr;
-    EncMeasure *dMeas = nullptr;
-    // every buffer of a group, sized for the largest one
-    auto allocGroup = [&]() -> hipError_t {
-        const size_t JF = static_cast<size_t>(groupFrames), NJ = groupJobs;
-        struct { void **p; size_t bytes; } want[] = {
-            { reinterpret_cast<void **>(&dJobs), sizeof(EncJob) * NJ }, { reinterpret_cast<void **>(&dFJ), sizeof(uint32_t) * JF },
-            { reinterpret_cast<void **>(&dHdr), 48 * NJ }, { reinterpret_cast<void **>(&dKeep), sizeof(int32_t) * NJ },
-            { reinterpret_cast<void **>(&dWin), sizeof(int32_t) * NJ }, { reinterpret_cast<void **>(&dSize), sizeof(uint64_t) * NJ },
-            { reinterpret_cast<void **>(&dOutOff), sizeof(uint64_t) * NJ },
-            { reinterpret_cast<void **>(&dFrameBits), sizeof(uint32_t) * 3 * JF }, { reinterpret_cast<void **>(&dFrameOff), sizeof(uint32_t) * JF },
-            { reinterpret_cast<void **>(&dRec), os93 ? sizeof(Enc93Rec) * 32 * JF : 0 }, { reinterpret_cast<void **>(&dBand), os93 ? sizeof(Enc93Band) * 32 * JF : 0 },
-            { reinterpret_cast<void **>(&dBest), os93 ? 0 : 128 * JF }, { reinterpret_cast<void **>(&dCodes), os93 ? 0 : 48 * JF },
-            { reinterpret_cast<void **>(&dHdrBits), os93 ? 0 : 48 * JF }, { reinterpret_cast<void **>(&dSmpBits), os93 ? 0 : sizeof(uint16_t) * 48 * JF },
-            { reinterpret_cast<void **>(&dMeas), sweep.measure ? sizeof(EncMeasure) * NJ : 0 },
-            { reinterpret_cast<void **>(&dFirstDec), sweep.measure ? sizeof(uint32_t) * NJ : 0 },
-        };
-        for (const auto &w : want)
-            if (w.bytes != 0)
-            {
-                const hipError_t e = allocIn(group, w.p, w.bytes);
-                if (e != hipSuccess)
-                    return e;
-            }
-        return hipSuccess;
-    };
-    std::vector<int32_t> win(nJobs), keep(nJobs);
-    std::vector<uint64_t> size(nJobs);
-    std::vector<uint32_t> bad(nStreams);
-    std::vector<EncJob> hj;                     // the resident group's jobs and rows
-    std::vector<uint32_t> frameJob;
-    uint32_t resident = ~0u, residentFrames = 0;
-    // E2's header half to the sizes for group g, and a wait: win, keep and size of its jobs are on the host after it
-    auto runGroup = [&](uint32_t g) -> DcsStatus {
-        const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
-        hj.resize(n);
-        frameJob.clear();
-        uint32_t JF = 0;
+DcsStatus EncRun::allocCall()
+{
+    const uint32_t nStreams = in.nStreams;
+    ENCCHK(call.alloc(&cb.dT, 1));
+    if (!dev && !devF)
+        ENCCHK(call.alloc(&cb.dPcm, in.sampleOffsets[nStreams] - in.sampleOffsets[0]));
+    ENCCHK(call.alloc(&cb.dStr, nStreams));
+    ENCCHK(call.alloc(&cb.dSets, jobs.nSets));
+    ENCCHK(call.alloc(&cb.dFS, F));
+    ENCCHK(call.alloc(&cb.dSpec, size_t(256) * F));
+    ENCCHK(call.alloc(&cb.dPw, size_t(16) * F));
+    ENCCHK(call.alloc(&cb.dLo, size_t(16) * F));
+    ENCCHK(call.alloc(&cb.dHi, size_t(16) * F));
+    ENCCHK(call.alloc(&cb.dBad, nStreams));
+    ENCCHK(call.alloc(&cb.dSums, size_t(48) * nStreams));
+    return DCS_OK;
+}
+
+// the groups: runs of the job list of at most `limit` job-frames, a job never split
+void EncRun::makeGroups(uint64_t limit)
+{
+    groupFirst.assign(1, 0);
+    groupFrames = 0; groupJobs = 0;
+    uint64_t inGroup = 0;
+    for (uint32_t j = 0 ; j < jobs.n ; ++j)
+    {
+        const uint64_t nF = hs[jobs.list[j].stream].nFrames;
+        if ((inGroup != 0 && inGroup + nF > limit) || inGroup + nF > 0xFFFFFFFFull)
+        {
+            groupFirst.push_back(j);
+            inGroup = 0;
+        }
+        inGroup += nF;
+        groupFrames = inGroup > groupFrames ? inGroup : groupFrames;
+        groupJobs = std::max(groupJobs, j + 1 - groupFirst.back());
+    }
+    groupFirst.push_back(jobs.n);
+}
+
+// every buffer of a group, sized for the largest one; the first failure is returned, for allocGroups to judge
+hipError_t EncRun::allocGroup()
+{
+    const size_t JF = static_cast<size_t>(groupFrames), NJ = groupJobs;
+    HIPTRY(group.alloc(&gb.dJobs, NJ));
+    HIPTRY(group.alloc(&gb.dFJ, JF));
+    HIPTRY(group.alloc(&gb.dHdr, 48 * NJ));
+    HIPTRY(group.alloc(&gb.dKeep, NJ));
+    HIPTRY(group.alloc(&gb.dWin, NJ));
+    HIPTRY(group.alloc(&gb.dSize, NJ));
+    HIPTRY(group.alloc(&gb.dOutOff, NJ));
+    HIPTRY(group.alloc(&gb.dFrameBits, 3 * JF));
+    HIPTRY(group.alloc(&gb.dFrameOff, JF));
+    if (jobs.os93)
+    {
+        HIPTRY(group.alloc(&gb.o93.dRec, 32 * JF));
+        HIPTRY(group.alloc(&gb.o93.dBand, 32 * JF));
+    }
+    else
+    {
+        HIPTRY(group.alloc(&gb.v94.dBest, 128 * JF));
+        HIPTRY(group.alloc(&gb.v94.dCodes, 48 * JF));
+        HIPTRY(group.alloc(&gb.v94.dHdrBits, 48 * JF));
+        HIPTRY(group.alloc(&gb.v94.dSmpBits, 48 * JF));
+    }
+    if (sweep.measure)
+    {
+        HIPTRY(group.alloc(&gb.m.dMeas, NJ));
+        HIPTRY(group.alloc(&gb.m.dFirstDec, NJ));
+    }
+    return hipSuccess;
+}
+
+// all jobs in one group when that can be had (or the cap that is set); half the job-frames each time the memory runs out
+DcsStatus EncRun::allocGroups()
+{
+    uint64_t limit = gGroupFrames.load() != 0 ? std::max<uint64_t>(gGroupFrames.load(), largest) : allFrames;
+    for (;;)
+    {
+        makeGroups(limit);
+        const hipError_t e = allocGroup();
+        if (e == hipSuccess)
+            return DCS_OK;
+        group.clear();
+        if (e != hipErrorOutOfMemory || groupFrames <= largest)
+            ENCCHK(e);
+        limit = std::max<uint64_t>(largest, groupFrames / 2);
+    }
+}
+
+// E2's header half to the sizes for group g, and a wait: win, keep and size of its jobs are on the host after it
+DcsStatus EncRun::runGroup(uint32_t g)
+{
+    const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
+    hj.resize(n);
+    frameJob.clear();
+    uint32_t JF = 0;
+    for (uint32_t k = 0 ; k < n ; ++k)
+    {
+        const DcsSweepJob &job = jobs.list[j0 + k];
+        const EncStream &s = hs[job.stream];
+        hj[k] = EncJob{ job.stream, job.paramSet, JF, s.nFrames, s.firstFrame };
+        frameJob.insert(frameJob.end(), s.nFrames, k);
+        JF += s.nFrames;
+    }
+    ENCCHK(hipMemcpyAsync(gb.dJobs, hj.data(), sizeof(EncJob) * n, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(gb.dFJ, frameJob.data(), sizeof(uint32_t) * JF, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(gb.dFrameBits, 0, sizeof(uint32_t) * 3 * JF, st));
+    hipLaunchKernelGGL(encHeaderKernel, dim3(n), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, cb.dSums, gb.dHdr, gb.dKeep);
+    if (jobs.os93)
+    {
+        hipLaunchKernelGGL(enc93SearchKernel, dim3((JF + 3) / 4), dim3(128), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, cb.dSets, gb.dHdr,
+                           gb.dKeep, JF, gb.o93.dRec);
+        if (anyV & 1)
+            hipLaunchKernelGGL(enc93WalkKernel<0>, dim3((JF + 63) / 64), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, gb.dFJ, gb.dKeep, JF, JF,
+                               gb.o93.dRec, gb.o93.dBand, gb.dFrameBits);
+        if (anyV & 2)
+            hipLaunchKernelGGL(enc93WalkKernel<1>, dim3((n + 63) / 64), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, gb.dFJ, gb.dKeep, JF, n,
+                               gb.o93.dRec, gb.o93.dBand, gb.dFrameBits);
+    }
+    else
+    {
+        ENCCHK(hipMemsetAsync(gb.v94.dBest, 0, size_t(128) * JF, st));
+        ENCCHK(hipMemsetAsync(gb.v94.dCodes, 0, size_t(48) * JF, st));
+        hipLaunchKernelGGL(encSearchKernel, dim3(JF), dim3(128), 0, st, cb.dT, cb.dSpec, cb.dLo, cb.dHi, gb.dFJ, gb.dJobs, cb.dSets, gb.dHdr,
+                           gb.dKeep, gb.v94.dBest);
+        hipLaunchKernelGGL(encChainKernel, dim3(n), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, gb.dKeep, JF,
+                           reinterpret_cast<const uint64_t *>(gb.v94.dBest), gb.v94.dCodes);
+        hipLaunchKernelGGL(encBitsKernel, dim3(JF), dim3(64), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, cb.dSets, gb.dHdr, gb.dKeep, JF,
+                           gb.v94.dCodes, gb.v94.dHdrBits, gb.v94.dSmpBits, gb.dFrameBits);
+    }
+    hipLaunchKernelGGL(encSizeKernel, dim3(n), dim3(256), 0, st, gb.dJobs, cb.dSets, JF, gb.dFrameBits, gb.dWin, gb.dSize, gb.dFrameOff);
+    ENCCHK(hipGetLastError());
+    ENCCHK(hipMemcpyAsync(win.data() + j0, gb.dWin, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipMemcpyAsync(keep.data() + j0, gb.dKeep, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipMemcpyAsync(size.data() + j0, gb.dSize, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipStreamSynchronize(st));
+    resident = g;
+    residentFrames = JF;
+    return DCS_OK;
+}
+
+// Upload, E1 and encStreamKernel; bad[] is on its way to the host, there after the first group's wait.  (The step before
+// runGroup, written after it: the kernel templates are instantiated in the order the source first launches them, and the
+// device code object keeps the order it had.)
+DcsStatus EncRun::analyse()
+{
+    const uint32_t nStreams = in.nStreams;
+    const uint64_t first = in.sampleOffsets[0], nSamples = in.sampleOffsets[nStreams] - first;
+    const EncTabs &tabs = jobs.os93 ? encTabs93() : encTabs();
+    bad.resize(nStreams);
+    ENCCHK(hipMemcpyAsync(cb.dT, &tabs, sizeof(EncTabs), hipMemcpyHostToDevice, st));
+    if (!dev && !devF)
+        ENCCHK(hipMemcpyAsync(cb.dPcm, in.hostPcm + first, sizeof(float) * nSamples, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(cb.dStr, hs.data(), sizeof(EncStream) * nStreams, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(cb.dSets, hsets.data(), sizeof(EncSet) * jobs.nSets, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(cb.dFS, frameStream.data(), sizeof(uint32_t) * F, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(cb.dBad, 0, sizeof(uint32_t) * nStreams, st));
+    if (dev)
+        hipLaunchKernelGGL(encAnalyseKernel<int16_t>, dim3((F + 3) / 4), dim3(256), 0, st, cb.dT, in.devPcm + first, cb.dStr, cb.dFS, F,
+                           cb.dSpec, cb.dPw, cb.dLo, cb.dHi, cb.dBad, in.devErr);
+    else
+        hipLaunchKernelGGL(encAnalyseKernel<float>, dim3((F + 3) / 4), dim3(256), 0, st, cb.dT, devF ? in.devFloat + first : cb.dPcm,
+                           cb.dStr, cb.dFS, F, cb.dSpec, cb.dPw, cb.dLo, cb.dHi, cb.dBad, static_cast<const uint32_t *>(nullptr));
+    hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, cb.dStr, cb.dPw, cb.dLo, cb.dHi, cb.dSums);
+    ENCCHK(hipMemcpyAsync(bad.data(), cb.dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
+    return DCS_OK;
+}
+
+// what the first wait brings: was the input usable at all (planFlag), then did E1 refuse a sample (bad[])
+DcsStatus EncRun::checkInput()
+{
+    if (in.planFlag != nullptr && *in.planFlag != 0)
+    {
+        in.unusable = true;
+        return DCS_ERR_BAD_STREAM;
+    }
+    for (uint32_t i = 0 ; i < in.nStreams ; ++i)
+        if (bad[i])
+        {
+            dcsCtxSetError(ctx, (name(i) + (dev ? ": the decoder reports an error in a frame (DCS_FRAME_STOP / DCS_FRAME_FATAL)"
+                                                : in.bound != nullptr ? ": a sample is not finite or beyond its format's full scale"
+                                                : ": a sample is not finite or |x| > 1")).c_str());
+            return DCS_ERR_BAD_STREAM;
+        }
+    return DCS_OK;
+}
+
+// every size is known: outOffsets, info and results, then dst (null with DCS_OK: a sweep that asked for sizes only)
+DcsStatus EncRun::placeOutput()
+{
+    uint64_t *outOffsets = to.outOffsets;
+    for (uint32_t j = 0 ; j < jobs.n ; ++j)
+    {
+        outOffsets[j + 1] = outOffsets[j] + size[j];
+        const DcsEncodeInfo e{ kCandType[win[j]], kCandSub[win[j]], static_cast<int32_t>(hs[jobs.list[j].stream].nFrames),
+                               static_cast<int32_t>(size[j]), keep[j] };
+        if (to.info != nullptr)
+            to.info[j] = e;
+        if (sweep.results != nullptr)
+        {
+            memset(&sweep.results[j], 0, sizeof(DcsSweepResult));       // (its padding too: records compare as bytes)
+            sweep.results[j].enc = e;
+        }
+    }
+    if (sweep.sizesOnly)
+        return DCS_OK;
+    const uint64_t total = outOffsets[jobs.n];
+    dst = to.place != nullptr && *to.place ? (*to.place)(outOffsets, total) : (to.out != nullptr && to.outCap >= total ? to.out : nullptr);
+    return dst != nullptr ? DCS_OK : DCS_ERR_CAPACITY;
+}
+
+// Where the jobs of group g lie in its blob, and the blob's size in words.  For the output: as in the output.  For a
+// decode: where the device path's stream layout wants them (each stream on a 4-byte boundary, the blob's zeroed tail).
+DcsStatus EncRun::layoutGroup(uint32_t g, size_t *nWords)
+{
+    const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
+    offs.resize(n);
+    if (!sweep.measure)
+    {
         for (uint32_t k = 0 ; k < n ; ++k)
+            offs[k] = to.outOffsets[j0 + k] - to.outOffsets[j0];
+        blobLen = static_cast<size_t>(to.outOffsets[j0 + n] - to.outOffsets[j0]);
+        *nWords = (blobLen + 3) / 4 + 1;
+        return DCS_OK;
+    }
+    ss.resize(n);
+    for (uint32_t k = 0 ; k < n ; ++k)
+    {
+        const int c = win[j0 + k];
+        const uint16_t ver = jobs.sets[hj[k].set].formatVersion;
+        ss[k] = DcsSweepStream{ hj[k].nFrames, static_cast<uint32_t>(size[j0 + k]),
+                                ver == 0x9301 ? DCS_OS93A : ver == 0x9302 ? DCS_OS93B : kCandSub[c] == 3 ? DCS_OS95 : DCS_OS94, kCandType[c],
+                                jobs.os93 ? 0 : kCandSub[c], keep[j0 + k] };
+    }
+    size_t blobBytes;
+    ENCTRY(dcsSweepLayout(ss.data(), n, offs.data(), &blobLen, &blobBytes));
+    *nWords = blobBytes / 4;
+    return DCS_OK;
+}
+
+// header, pack and swap of the resident group g into a blob of its own
+DcsStatus EncRun::packGroup(uint32_t g)
+{
+    const uint32_t n = groupFirst[g + 1] - groupFirst[g], JF = residentFrames;
+    size_t nWords;
+    ENCTRY(layoutGroup(g, &nWords));
+    blob.clear();
+    staged = false;
+    ENCCHK(blob.alloc(&dW, nWords));
+    ENCCHK(hipMemsetAsync(dW, 0, sizeof(uint32_t) * nWords, st));
+    ENCCHK(hipMemcpyAsync(gb.dOutOff, offs.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(encHeadKernel, dim3(n), dim3(64), 0, st, gb.dJobs, gb.dHdr, gb.dWin, gb.dOutOff, dW);
+    if (jobs.os93)
+        hipLaunchKernelGGL(enc93PackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, gb.dHdr, gb.dKeep, gb.dWin,
+                           JF, gb.o93.dBand, gb.dFrameOff, gb.dOutOff, dW);
+    else
+        hipLaunchKernelGGL(encPackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, gb.dHdr, gb.dKeep, gb.dWin,
+                           JF, gb.v94.dCodes, gb.v94.dHdrBits, gb.v94.dSmpBits, gb.dFrameOff, gb.dOutOff, dW);
+    hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
+    ENCCHK(hipGetLastError());
+    return DCS_OK;
+}
+
+// the packed group g to its place in the output, and a wait
+DcsStatus EncRun::deliverGroup(uint32_t g)
+{
+    ENCCHK(hipMemcpyAsync(dst + to.outOffsets[groupFirst[g]], dW, blobLen, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipStreamSynchronize(st));
+    return DCS_OK;
+}
+
+// the packed group's blob to `stage`, queued once per group; the caller waits
+DcsStatus EncRun::stageBlob()
+{
+    if (staged)
+        return DCS_OK;
+    stage.resize(blobLen);
+    ENCCHK(hipMemcpyAsync(stage.data(), dW, blobLen, hipMemcpyDeviceToHost, st));
+    staged = true;
+    return DCS_OK;
+}
+
+// The jobs of the packed group (n of them) whose streams are decoded.  One kind is left out: an OS93a stream with no band
+// kept.  Its header is sixteen 0xFF bytes, the first of which carries the type bit, so every decoder reads it as OS93a
+// Type 1 with 31 bands; its record stays measured = 0.
+void EncRun::selectDecodes(uint32_t n)
+{
+    sel.clear(); selS.clear(); selOff.clear();
+    mostFrames = 0;
+    selFrames = 0;
+    for (uint32_t k = 0 ; k < n ; ++k)
+        if (!(ss[k].os == DCS_OS93A && ss[k].bandsToKeep == 0))
         {
-            const EncStream &s = hs[jobList[j0 + k].stream];
-            hj[k] = EncJob{ jobList[j0 + k].stream, jobList[j0 + k].paramSet, JF, s.nFrames, s.firstFrame };
-            frameJob.insert(frameJob.end(), s.nFrames, k);
-            JF += s.nFrames;
+            sel.push_back(k); selS.push_back(ss[k]); selOff.push_back(offs[k]);
+            mostFrames = std::max(mostFrames, hj[k].nFrames);
+            selFrames += hj[k].nFrames;
         }
-        ENCCHK(hipMemcpyAsync(dJobs, hj.data(), sizeof(EncJob) * n, hipMemcpyHostToDevice, st));
-        ENCCHK(hipMemcpyAsync(dFJ, frameJob.data(), sizeof(uint32_t) * JF, hipMemcpyHostToDevice, st));
-        ENCCHK(hipMemsetAsync(dFrameBits, 0, sizeof(uint32_t) * 3 * JF, st));
-        hipLaunchKernelGGL(encHeaderKernel, dim3(n), dim3(64), 0, st, dT, dJobs, dSets, dSums, dHdr, dKeep);
-        if (os93)
-        {
-            hipLaunchKernelGGL(enc93SearchKernel, dim3((JF + 3) / 4), dim3(128), 0, st, dT, dSpec, dFJ, dJobs, dSets, dHdr, dKeep, JF, dRec);
-            if (anyV & 1)
-                hipLaunchKernelGGL(enc93WalkKernel<0>, dim3((JF + 63) / 64), dim3(64), 0, st, dT, dJobs, dSets, dFJ, dKeep, JF, JF, dRec, dBand, dFrameBits);
-            if (anyV & 2)
-                hipLaunchKernelGGL(enc93WalkKernel<1>, dim3((n + 63) / 64), dim3(64), 0, st, dT, dJobs, dSets, dFJ, dKeep, JF, n, dRec,
-                                   dBand, dFrameBits);
-        }
-        else
-        {
-            ENCCHK(hipMemsetAsync(dBest, 0, size_t(128) * JF, st));
-            ENCCHK(hipMemsetAsync(dCodes, 0, size_t(48) * JF, st));
-            hipLaunchKernelGGL(encSearchKernel, dim3(JF), dim3(128), 0, st, dT, dSpec, dLo, dHi, dFJ, dJobs, dSets, dHdr, dKeep, dBest);
-            hipLaunchKernelGGL(encChainKernel, dim3(n), dim3(64), 0, st, dT, dJobs, dSets, dKeep, JF,
-                               reinterpret_cast<const uint64_t *>(dBest), dCodes);
-            hipLaunchKernelGGL(encBitsKernel, dim3(JF), dim3(64), 0, st, dT, dSpec, dFJ, dJobs, dSets, dHdr, dKeep, JF, dCodes, dHdrBits, dSmpBits, dFrameBits);
-        }
-        hipLaunchKernelGGL(encSizeKernel, dim3(n), dim3(256), 0, st, dJobs, dSets, JF, dFrameBits, dWin, dSize, dFrameOff);
-        ENCCHK(hipGetLastError());
-        ENCCHK(hipMemcpyAsync(win.data() + j0, dWin, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipMemcpyAsync(keep.data() + j0, dKeep, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipMemcpyAsync(size.data() + j0, dSize, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+}
+
+// One attempt: the selected streams decoded, on the device path from the bytes where they lie or (onHost) as a host-planned
+// batch from the staged blob, then M1 and a wait, after which meas[] is on the host, and so is the blob where the output
+// wants it.  *unusable: the device planner gave the list up (its flag); the sums are then not to be used.
+DcsStatus EncRun::decodeAndCompare(uint32_t n, bool onHost, bool *unusable)
+{
+    if (onHost && !staged)
+    {
+        ENCTRY(stageBlob());
         ENCCHK(hipStreamSynchronize(st));
-        resident = g;
-        residentFrames = JF;
+    }
+    SweepDecodeGuard dec;
+    const int16_t *decPcm = nullptr;
+    const uint32_t *decErr = nullptr, *firstFrame = nullptr;
+    const volatile uint32_t *flag = nullptr;
+    const uint32_t nSel = static_cast<uint32_t>(sel.size());
+    ENCTRY(dcsSweepDecodeStart(ctx, selS.data(), nSel, selOff.data(), reinterpret_cast<const uint8_t *>(dW), blobLen,
+                               onHost ? stage.data() : nullptr, &dec.d, &decPcm, &decErr, &flag, &firstFrame));
+    for (uint32_t i = 0 ; i < nSel ; ++i)
+        firstDec[sel[i]] = firstFrame[i];
+    ENCCHK(hipMemcpyAsync(gb.m.dFirstDec, firstDec.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(gb.m.dMeas, 0, sizeof(EncMeasure) * n, st));
+    hipLaunchKernelGGL(encMeasureKernel, dim3(n, (mostFrames + 1 + kMeasureFrames - 1) / kMeasureFrames), dim3(256), 0, st,
+                       cb.dPcm, cb.dStr, gb.dJobs, gb.m.dFirstDec, decPcm, decErr, gb.m.dMeas);
+    ENCCHK(hipGetLastError());
+    ENCCHK(hipMemcpyAsync(meas.data(), gb.m.dMeas, sizeof(EncMeasure) * n, hipMemcpyDeviceToHost, st));
+    if (dst != nullptr)
+        ENCTRY(stageBlob());
+    ENCCHK(hipStreamSynchronize(st));
+    *unusable = flag != nullptr && *flag != 0;
+    return DCS_OK;
+}
+
+// meas[] to the results of group g's jobs, and their bytes from `stage` to the output
+DcsStatus EncRun::reportGroup(uint32_t g)
+{
+    const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
+    for (uint32_t k = 0 ; k < n ; ++k)
+    {
+        const uint32_t j = j0 + k;
+        if (meas[k].err != 0)
+        {
+            dcsCtxSetError(ctx, ("job " + std::to_string(j) + " (" + name(hj[k].stream) + ", set " + std::to_string(hj[k].set)
+                                 + "): the decoder reports an error in a frame of the stream just encoded").c_str());
+            return DCS_ERR_HIP;
+        }
+        DcsSweepResult &r = sweep.results[j];
+        if (dst != nullptr)
+            memcpy(dst + to.outOffsets[j], stage.data() + offs[k], size[j]);
+        if (firstDec[k] == kNotDecoded)
+            continue;
+        r.measured = 1;
+        r.peakErr = meas[k].peak;
+        r.nCompared = hs[hj[k].stream].nSamples;
+        r.sumSrcSq = static_cast<int64_t>(meas[k].srcSq);
+        r.sumDecSq = static_cast<int64_t>(meas[k].decSq);
+        r.sumCross = static_cast<int64_t>(meas[k].cross);
+    }
+    return DCS_OK;
+}
+
+// The packed group g decoded and compared with its sources.  The decode, as transcoding runs it (dcs_transcode.hip.h): the
+// device path on the bytes where they lie; the host-planned batch, for which the bytes are read back, where the device
+// planner cannot serve the list (a second attempt) or one long stream dominates it (the only one: the device index walk is
+// one wavefront per stream, serial over its frames).
+DcsStatus EncRun::measureGroup(uint32_t g)
+{
+    const uint32_t n = groupFirst[g + 1] - groupFirst[g];
+    selectDecodes(n);
+    const bool walkOnHost = mostFrames > 2048 && uint64_t(mostFrames) * 64 > selFrames;
+    meas.assign(n, EncMeasure{});
+    firstDec.assign(n, kNotDecoded);
+    if (sel.empty() && dst != nullptr)
+    {
+        ENCTRY(stageBlob());
+        ENCCHK(hipStreamSynchronize(st));
+    }
+    for (int attempt = walkOnHost ? 1 : 0 ; attempt < 2 && !sel.empty() ; ++attempt)
+    {
+        bool unusable = false;
+        ENCTRY(decodeAndCompare(n, attempt == 1, &unusable));
+        if (!unusable)
+            break;
+    }
+    return reportGroup(g);
+}
+
+DcsStatus EncRun::run()
+{
+    ENCTRY(checkStreams());
+    to.outOffsets[0] = 0;
+    if (in.nStreams == 0 || jobs.n == 0)
+    {
+        for (uint32_t j = 0 ; j < jobs.n ; ++j)
+            to.outOffsets[j + 1] = 0;
         return DCS_OK;
-    };
-    CacheBuf wBuf;
-    std::vector<uint64_t> offs;
-    std::vector<uint8_t> stage;
-    std::vector<DcsSweepStream> ss, selS;
-    std::vector<uint32_t> sel, firstDec;
-    std::vector<uint64_t> selOff;
-    std::vector<EncMeasure> meas;
-    uint8_t *dst = nullptr;
-    // header, pack and swap of the resident group; its bytes to dst; with sweep.measure its decode and the comparison
-    auto packGroup = [&](uint32_t g) -> DcsStatus {
-        const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0, JF = residentFrames;
-        offs.resize(n);
-        size_t blobLen, nWords;
-        if (sweep.measure)
-        {
-            // where the device path's stream layout wants them (each stream on a 4-byte boundary, the blob's zeroed tail)
-            ss.resize(n);
-            for (uint32_t k = 0 ; k < n ; ++k)
-            {
-                const int c = win[j0 + k];
-                const uint16_t ver = sets[hj[k].set].formatVersion;
-                ss[k] = DcsSweepStream{ hj[k].nFrames, static_cast<uint32_t>(size[j0 + k]),
-                                        ver == 0x9301 ? DCS_OS93A : ver == 0x9302 ? DCS_OS93B : cs[c] == 3 ? DCS_OS95 : DCS_OS94, ct[c], os93 ? 0 : cs[c],
-                                        keep[j0 + k] };
-            }
-            size_t blobBytes;
-            const DcsStatus ls = dcsSweepLayout(ss.data(), n, offs.data(), &blobLen, &blobBytes);
-            if (ls != DCS_OK)
-                return ls;
-            nWords = blobBytes / 4;
-        }
-        else
-        {
-            for (uint32_t k = 0 ; k < n ; ++k)
-                offs[k] = outOffsets[j0 + k] - outOffsets[j0];
-            blobLen = static_cast<size_t>(outOffsets[j0 + n] - outOffsets[j0]);
-            nWords = (blobLen + 3) / 4 + 1;
-        }
-        ENCCHK(wBuf.alloc(ctx, false, (sizeof(uint32_t) * nWords + 255) & ~size_t(255)));
-        uint32_t *dW = wBuf.as<uint32_t>();
-        ENCCHK(hipMemsetAsync(dW, 0, sizeof(uint32_t) * nWords, st));
-        ENCCHK(hipMemcpyAsync(dOutOff, offs.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(encHeadKernel, dim3(n), dim3(64), 0, st, dJobs, dHdr, dWin, dOutOff, dW);
-        if (os93)
-            hipLaunchKernelGGL(enc93PackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, dT, dSpec, dFJ, dJobs, dHdr, dKeep, dWin, JF, dBand,
-                               dFrameOff, dOutOff, dW);
-        else
-            hipLaunchKernelGGL(encPackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, dT, dSpec, dFJ, dJobs, dHdr, dKeep, dWin, JF, dCodes,
-                               dHdrBits, dSmpBits, dFrameOff, dOutOff, dW);
-        hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
-        ENCCHK(hipGetLastError());
-        if (!sweep.measure)
-        {
-            ENCCHK(hipMemcpyAsync(dst + outOffsets[j0], dW, blobLen, hipMemcpyDeviceToHost, st));
-            ENCCHK(hipStreamSynchronize(st));
-            return DCS_OK;
-        }
-        // The decode, as transcoding runs it (dcs_transcode.hip.h): the device path on the bytes where they lie; the
-        // host-planned batch, for which the bytes are read back, where the device planner cannot serve the list or one
-        // long stream dominates it (the device index walk is one wavefront per stream, serial over its frames).
-        // One kind of stream is left out: an OS93a stream with no band kept.  Its header is sixteen 0xFF bytes, the first of
-        // which carries the type bit, so every decoder reads it as OS93a Type 1 with 31 bands; its record stays measured = 0.
-        sel.clear(); selS.clear(); selOff.clear();
-        uint64_t longest = 0, selFrames = 0;
-        uint32_t mostFrames = 0;
-        for (uint32_t k = 0 ; k < n ; ++k)
-            if (!(ss[k].os == DCS_OS93A && ss[k].bandsToKeep == 0))
-            {
-                sel.push_back(k); selS.push_back(ss[k]); selOff.push_back(offs[k]);
-                longest = std::max<uint64_t>(longest, hj[k].nFrames);
-                mostFrames = std::max(mostFrames, hj[k].nFrames);
-                selFrames += hj[k].nFrames;
-            }
-        const uint32_t nSel = static_cast<uint32_t>(sel.size());
-        const bool walkOnHost = longest > 2048 && longest * 64 > selFrames;
-        bool staged = false;
-        meas.assign(n, EncMeasure{});
-        firstDec.assign(n, kNotDecoded);
-        if (nSel == 0 && dst != nullptr)
-        {
-            stage.resize(blobLen);
-            ENCCHK(hipMemcpyAsync(stage.data(), dW, blobLen, hipMemcpyDeviceToHost, st));
-            ENCCHK(hipStreamSynchronize(st));
-        }
-        for (int attempt = walkOnHost ? 1 : 0 ; attempt < 2 && nSel != 0 ; ++attempt)
-        {
-            if (attempt == 1 && !staged)
-            {
-                stage.resize(blobLen);
-                ENCCHK(hipMemcpyAsync(stage.data(), dW, blobLen, hipMemcpyDeviceToHost, st));
-                ENCCHK(hipStreamSynchronize(st));
-                staged = true;
-            }
-            DcsSweepDecode *d = nullptr;
-            const int16_t *decPcm = nullptr;
-            const uint32_t *decErr = nullptr, *firstFrame = nullptr;
-            const volatile uint32_t *flag = nullptr;
-            DcsStatus ds = dcsSweepDecodeStart(ctx, selS.data(), nSel, selOff.data(), reinterpret_cast<const uint8_t *>(dW), blobLen,
-                                               attempt == 1 ? stage.data() : nullptr, &d, &decPcm, &decErr, &flag, &firstFrame);
-            bool unusable = false;
-            if (ds == DCS_OK)
-                ds = [&]() -> DcsStatus {
-                    for (uint32_t i = 0 ; i < nSel ; ++i)
-                        firstDec[sel[i]] = firstFrame[i];
-                    ENCCHK(hipMemcpyAsync(dFirstDec, firstDec.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
-                    ENCCHK(hipMemsetAsync(dMeas, 0, sizeof(EncMeasure) * n, st));
-                    hipLaunchKernelGGL(encMeasureKernel, dim3(n, (mostFrames + 1 + kMeasureFrames - 1) / kMeasureFrames), dim3(256), 0, st,
-                                       dPcm, dStr, dJobs, dFirstDec, decPcm, decErr, dMeas);
-                    ENCCHK(hipGetLastError());
-                    ENCCHK(hipMemcpyAsync(meas.data(), dMeas, sizeof(EncMeasure) * n, hipMemcpyDeviceToHost, st));
-                    if (dst != nullptr && !staged)
-                    {
-                        stage.resize(blobLen);
-                        ENCCHK(hipMemcpyAsync(stage.data(), dW, blobLen, hipMemcpyDeviceToHost, st));
-                    }
-                    ENCCHK(hipStreamSynchronize(st));
-                    staged = staged || dst != nullptr;
-                    unusable = flag != nullptr && *flag != 0;
-                    return DCS_OK;
-                }();
-            dcsSweepDecodeRelease(d);
-            if (ds != DCS_OK)
-                return ds;
-            if (!unusable)
-                break;
-        }
-        for (uint32_t k = 0 ; k < n ; ++k)
-        {
-            const uint32_t j = j0 + k;
-            if (meas[k].err != 0)
-            {
-                dcsCtxSetError(ctx, ("job " + std::to_string(j) + " (" + name(hj[k].stream) + ", set " + std::to_string(hj[k].set)
-                                     + "): the decoder reports an error in a frame of the stream just encoded").c_str());
-                return DCS_ERR_HIP;
-            }
-            DcsSweepResult &r = sweep.results[j];
-            if (dst != nullptr)
-                memcpy(dst + outOffsets[j], stage.data() + offs[k], size[j]);
-            if (firstDec[k] == kNotDecoded)
-                continue;
-            r.measured = 1;
-            r.peakErr = meas[k].peak;
-            r.nCompared = hs[hj[k].stream].nSamples;
-            r.sumSrcSq = static_cast<int64_t>(meas[k].srcSq);
-            r.sumDecSq = static_cast<int64_t>(meas[k].decSq);
-            r.sumCross = static_cast<int64_t>(meas[k].cross);
-        }
+    }
+    buildSets();
+    win.resize(jobs.n); keep.resize(jobs.n); size.resize(jobs.n);
+    ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
+    ENCTRY(allocCall());
+    ENCTRY(allocGroups());
+    ENCTRY(analyse());
+    const uint32_t nGroups = static_cast<uint32_t>(groupFirst.size()) - 1;
+    for (uint32_t g = 0 ; g < nGroups ; ++g)
+    {
+        ENCTRY(runGroup(g));
+        if (g == 0)
+            ENCTRY(checkInput());
+    }
+    ENCTRY(placeOutput());
+    if (dst == nullptr && !sweep.measure)
         return DCS_OK;
-    };
-    DcsStatus status = [&]() -> DcsStatus {
-        ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dT), sizeof(EncTabs)));
-        if (!dev && !devF)
-            ENCCHK(alloc(reinterpret_cast<void **>(&dPcm), sizeof(float) * nSamples));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dStr), sizeof(EncStream) * nStreams));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dSets), sizeof(EncSet) * nSets));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dFS), sizeof(uint32_t) * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dSpec), sizeof(float) * 256 * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dPw), sizeof(float) * 16 * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dLo), sizeof(float) * 16 * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dHi), sizeof(float) * 16 * F));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dBad), sizeof(uint32_t) * nStreams));
-        ENCCHK(alloc(reinterpret_cast<void **>(&dSums), sizeof(float) * 48 * nStreams));
-        // the groups: all jobs in one when that can be had; half the job-frames each time an allocation fails
-        uint64_t limit = gGroupFrames.load() != 0 ? std::max<uint64_t>(gGroupFrames.load(), largest) : allFrames;
-        for (;;)
-        {
-            makeGroups(limit);
-            const hipError_t e = allocGroup();
-            if (e == hipSuccess)
-                break;
-            group.clear();
-            if (e != hipErrorOutOfMemory || groupFrames <= largest)
-                ENCCHK(e);
-            limit = std::max<uint64_t>(largest, groupFrames / 2);
-        }
-        ENCCHK(hipMemcpyAsync(dT, &tabs, sizeof(EncTabs), hipMemcpyHostToDevice, st));
-        if (!dev && !devF)
-            ENCCHK(hipMemcpyAsync(dPcm, in.hostPcm + sampleOffsets[0], sizeof(float) * nSamples, hipMemcpyHostToDevice, st));
-        ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(EncStream) * nStreams, hipMemcpyHostToDevice, st));
-        ENCCHK(hipMemcpyAsync(dSets, hsets.data(), sizeof(EncSet) * nSets, hipMemcpyHostToDevice, st));
-        ENCCHK(hipMemcpyAsync(dFS, frameStream.data(), sizeof(uint32_t) * F, hipMemcpyHostToDevice, st));
-        ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * nStreams, st));
-        if (dev)
-            hipLaunchKernelGGL(encAnalyseKernel<int16_t>, dim3((F + 3) / 4), dim3(256), 0, st, dT, in.devPcm + sampleOffsets[0], dStr, dFS, F,
-                               dSpec, dPw, dLo, dHi, dBad, in.devErr);
-        else
-            hipLaunchKernelGGL(encAnalyseKernel<float>, dim3((F + 3) / 4), dim3(256), 0, st, dT, devF ? in.devFloat + sampleOffsets[0] : dPcm,
-                               dStr, dFS, F, dSpec, dPw, dLo, dHi, dBad, static_cast<const uint32_t *>(nullptr));
-        hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, dStr, dPw, dLo, dHi, dSums);
-        ENCCHK(hipMemcpyAsync(bad.data(), dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
-        const uint32_t nGroups = static_cast<uint32_t>(groupFirst.size()) - 1;
-        for (uint32_t g = 0 ; g < nGroups ; ++g)
-        {
-            const DcsStatus gs = runGroup(g);
-            if (gs != DCS_OK)
-                return gs;
-            if (g != 0)
-                continue;
-            if (in.planFlag != nullptr && *in.planFlag != 0)
-            {
-                in.unusable = true;
-                return DCS_ERR_BAD_STREAM;
-            }
-            for (uint32_t i = 0 ; i < nStreams ; ++i)
-                if (bad[i])
-                {
-                    dcsCtxSetError(ctx, (name(i) + (dev ? ": the decoder reports an error in a frame (DCS_FRAME_STOP / DCS_FRAME_FATAL)"
-                                                        : in.bound != nullptr ? ": a sample is not finite or beyond its format's full scale"
-                                                        : ": a sample is not finite or |x| > 1")).c_str());
-                    return DCS_ERR_BAD_STREAM;
-                }
-        }
-        for (uint32_t j = 0 ; j < nJobs ; ++j)
-        {
-            outOffsets[j + 1] = outOffsets[j] + size[j];
-            const DcsEncodeInfo e{ ct[win[j]], cs[win[j]], static_cast<int32_t>(hs[jobList[j].stream].nFrames), static_cast<int32_t>(size[j]), keep[j] };
-            if (info != nullptr)
-                info[j] = e;
-            if (sweep.results != nullptr)
-            {
-                memset(&sweep.results[j], 0, sizeof(DcsSweepResult));       // (its padding too: records compare as bytes)
-                sweep.results[j].enc = e;
-            }
-        }
-        const uint64_t total = outOffsets[nJobs];
-        if (!sweep.sizesOnly)
-        {
-            dst = place ? place(outOffsets, total) : (out != nullptr && outCap >= total ? out : nullptr);
-            if (dst == nullptr)
-                return DCS_ERR_CAPACITY;
-        }
-        if (dst == nullptr && !sweep.measure)
-            return DCS_OK;
-        for (uint32_t g = 0 ; g < nGroups ; ++g)
-        {
-            DcsStatus gs = resident == g ? DCS_OK : runGroup(g);
-            if (gs == DCS_OK)
-                gs = packGroup(g);
-            if (gs != DCS_OK)
-                return gs;
-        }
-        return DCS_OK;
-    }();
-    (void)hipStreamSynchronize(st);
-    wBuf.release();
-    for (CacheBuf &h : group)
-        h.release();
-    for (CacheBuf &h : held)
-        h.release();
-    return status;
+    for (uint32_t g = 0 ; g < nGroups ; ++g)
+    {
+        if (resident != g)
+            ENCTRY(runGroup(g));
+        ENCTRY(packGroup(g));
+        ENCTRY(sweep.measure ? measureGroup(g) : deliverGroup(g));
+    }
+    return DCS_OK;
 }
 
 // the entry points that encode every stream with one parameter set: job i = (stream i, set 0)
-DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const uint64_t *sampleOffsets, uint32_t nStreams,
-                        const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info,
-                        bool os93, const EncPlace &place = nullptr)
+DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const DcsEncodeParams *params, bool os93, const EncOutput &to)
 {
     const bool dev = in.devPcm != nullptr, devF = in.devFloat != nullptr;
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && in.hostPcm == nullptr && !dev && !devF)
-        || (dev && in.devErr == nullptr))
+    if (ctx == nullptr || in.sampleOffsets == nullptr || to.outOffsets == nullptr
+        || (in.nStreams != 0 && in.hostPcm == nullptr && !dev && !devF) || (dev && in.devErr == nullptr))
         return DCS_ERR_INVALID_ARG;
     if (!paramsValid(params, os93))
     {
-        if (os93 && params != nullptr && params->formatVersion == 0x9301 && params->streamFormatType == 1)
-            dcsCtxSetError(ctx, "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0");
+        if (const char *why = whyOs93aType1(params, os93))
+            dcsCtxSetError(ctx, why);
         return DCS_ERR_INVALID_ARG;
     }
-    std::vector<DcsSweepJob> jobs(nStreams);
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-        jobs[i] = DcsSweepJob{ i, 0 };
-    return encodeJobs(ctx, in, sampleOffsets, nStreams, params, 1, jobs.data(), nStreams, os93, out, outCap, outOffsets, info, EncSweep(), place);
+    std::vector<DcsSweepJob> list(in.nStreams);
+    for (uint32_t i = 0 ; i < in.nStreams ; ++i)
+        list[i] = DcsSweepJob{ i, 0 };
+    return EncRun(ctx, in, EncJobs{ params, 1, list.data(), in.nStreams, os93 }, to, EncSweep()).run();
+}
+
+// dcs_encode_streams and dcs_encode93_streams
+DcsStatus encodeHostPcm(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, const DcsEncodeParams *params,
+                        bool os93, const EncOutput &to)
+{
+    EncInput in;
+    in.sampleOffsets = sampleOffsets;
+    in.nStreams = nStreams;
+    in.hostPcm = pcm;
+    return encodeStreams(ctx, in, params, os93, to);
 }
 
 }  // namespace
@@ -1740,18 +1972,14 @@ extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uin
                                         const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
                                         DcsEncodeInfo *info)
 {
-    EncInput in;
-    in.hostPcm = pcm;
-    return encodeStreams(ctx, in, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, false);
+    return encodeHostPcm(ctx, pcm, sampleOffsets, nStreams, params, false, EncOutput{ out, outCap, outOffsets, info, nullptr });
 }
 
 extern "C" DcsStatus dcs_encode93_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
                                           const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
                                           DcsEncodeInfo *info)
 {
-    EncInput in;
-    in.hostPcm = pcm;
-    return encodeStreams(ctx, in, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, true);
+    return encodeHostPcm(ctx, pcm, sampleOffsets, nStreams, params, true, EncOutput{ out, outCap, outOffsets, info, nullptr });
 }
 
 // ------------------------------------------------------------------------------------------------------- sweeping and fitting
@@ -1778,9 +2006,8 @@ extern "C" DcsStatus dcs_encode_sweep(DcsCtx *ctx, const float *pcm, const uint6
         }
         if (!paramsValid(&sets[k], os93))
         {
-            dcsCtxSetError(ctx, os93 && sets[k].formatVersion == 0x9301 && sets[k].streamFormatType == 1
-                                    ? "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0"
-                                    : ("set " + std::to_string(k) + ": not a valid DcsEncodeParams").c_str());
+            const char *why = whyOs93aType1(&sets[k], os93);
+            dcsCtxSetError(ctx, why != nullptr ? why : ("set " + std::to_string(k) + ": not a valid DcsEncodeParams").c_str());
             return DCS_ERR_INVALID_ARG;
         }
     }
@@ -1803,12 +2030,14 @@ extern "C" DcsStatus dcs_encode_sweep(DcsCtx *ctx, const float *pcm, const uint6
             return DCS_ERR_INVALID_ARG;
         }
     EncInput in;
+    in.sampleOffsets = sampleOffsets;
+    in.nStreams = nStreams;
     in.hostPcm = pcm;
     EncSweep sweep;
     sweep.results = results;
     sweep.measure = (flags & DCS_SWEEP_MEASURE) != 0;
     sweep.sizesOnly = out == nullptr;
-    return encodeJobs(ctx, in, sampleOffsets, nStreams, sets, nSets, jobs, nJobs, os93, out, outCap, outOffsets, nullptr, sweep, nullptr);
+    return EncRun(ctx, in, EncJobs{ sets, nSets, jobs, nJobs, os93 }, EncOutput{ out, outCap, outOffsets, nullptr, nullptr }, sweep).run();
 }
 
 extern "C" DcsStatus dcs_encode_fit(const uint64_t *nBytes, const uint64_t *sqErr, uint32_t nStreams, uint32_t nSets, uint64_t budget,
@@ -1877,8 +2106,8 @@ DcsStatus dcsTranscodePlan(const DcsStreamRef *src, uint32_t nStreams, const Dcs
     {
         char text[96];
         snprintf(text, sizeof(text), "target: not a valid DcsEncodeParams for formatVersion 0x%x", target->formatVersion);
-        why = os93 && target->formatVersion == 0x9301 && target->streamFormatType == 1
-            ? "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0" : text;
+        const char *type1 = whyOs93aType1(target, os93);
+        why = type1 != nullptr ? type1 : text;
         return DCS_ERR_INVALID_ARG;
     }
     for (uint32_t i = 0 ; i < nStreams ; ++i)
@@ -1925,12 +2154,13 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
                               bool *unusable, uint64_t *encOffsets, DcsEncodeInfo *info, const EncPlace &place)
 {
     EncInput in;
+    in.sampleOffsets = sampleOffsets;
+    in.nStreams = nStreams;
     in.devPcm = dPcm;
     in.devErr = dErr;
     in.label = label;
     in.planFlag = planFlag;
-    const DcsStatus st = encodeStreams(ctx, in, sampleOffsets, nStreams, target, nullptr, 0, encOffsets, info,
-                                       target->formatVersion != 0x9400, place);
+    const DcsStatus st = encodeStreams(ctx, in, target, target->formatVersion != 0x9400, EncOutput{ nullptr, 0, encOffsets, info, &place });
     *unusable = in.unusable;
     return st;
 }

@@ -439,7 +439,7 @@ void rsHostRoute(std::vector<RsStream> &hs)
 // "<unit> label[i]".  On DCS_OK, *dOut holds the outputs (stream i from outOffsets[i], outOffsets[n] in all) and peak[i] the
 // bits of the stream's largest |y|; the buffers belong to `held`.
 DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dMono, const uint32_t *dBad, const DcsResampleFilter &f,
-                         const uint32_t *label, const char *unit, std::vector<CacheBuf> &held, float **dOut, uint64_t *outOffsets,
+                         const uint32_t *label, const char *unit, CacheArena &held, float **dOut, uint64_t *outOffsets,
                          std::vector<uint32_t> &peak)
 {
     const uint32_t n = static_cast<uint32_t>(hs.size());
@@ -457,22 +457,16 @@ DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dM
     }
     auto name = [&](uint32_t i) { return std::string(unit) + " " + std::to_string(label != nullptr ? label[i] : i); };
     const hipStream_t st = dcsCtxStream(ctx);
-    auto alloc = [&](void **p, size_t bytes) -> hipError_t {
-        held.emplace_back();
-        const hipError_t e = held.back().alloc(ctx, false, (bytes + 255) & ~size_t(255));
-        *p = held.back().as();
-        return e;
-    };
     float *dCoeffs, *dRes;
     uint64_t *dCounts;
     RsStream *dStr;
     uint32_t *dPeak;
     int2 *dSlots;
-    ENCCHK(alloc(reinterpret_cast<void **>(&dCoeffs), sizeof(float) * f.nCoeffs));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dCounts), sizeof(uint64_t) * n));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dStr), sizeof(RsStream) * n));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dPeak), sizeof(uint32_t) * n));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dSlots), sizeof(int2) * (nSlots ? nSlots : 1)));
+    ENCCHK(held.alloc(&dCoeffs, f.nCoeffs));
+    ENCCHK(held.alloc(&dCounts, n));
+    ENCCHK(held.alloc(&dStr, n));
+    ENCCHK(held.alloc(&dPeak, n));
+    ENCCHK(held.alloc(&dSlots, nSlots ? nSlots : 1));
     ENCCHK(hipMemcpyAsync(dCoeffs, f.coeffs, sizeof(float) * f.nCoeffs, hipMemcpyHostToDevice, st));
     ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
     ENCCHK(hipMemsetAsync(dPeak, 0, sizeof(uint32_t) * n, st));
@@ -542,7 +536,7 @@ DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dM
         outOffsets[i + 1] = outOffsets[i] + counts[i];
         maxCount = counts[i] > maxCount ? counts[i] : maxCount;
     }
-    ENCCHK(alloc(reinterpret_cast<void **>(&dRes), sizeof(float) * (outOffsets[n] ? outOffsets[n] : 1)));
+    ENCCHK(held.alloc(&dRes, outOffsets[n] ? outOffsets[n] : 1));
     ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
     // about 4 096 blocks in all: each block of the LDS variant copies the table once and then strides over its outputs
     const unsigned gy = n < 65535 ? n : 65535;
@@ -564,7 +558,7 @@ DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dM
 
 // The converter on the device for float input: stage (R1), then rsWalkConvolve, every stream on the device lanes.
 DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t n, const uint32_t *rates,
-                           const int32_t *channels, const DcsResampleFilter &f, uint32_t flags, std::vector<CacheBuf> &held,
+                           const int32_t *channels, const DcsResampleFilter &f, uint32_t flags, CacheArena &held,
                            float **dOut, uint64_t *outOffsets, std::vector<uint32_t> &peak)
 {
     std::vector<RsStream> hs(n);
@@ -581,24 +575,18 @@ DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sample
     }
     const uint64_t nValues = sampleOffsets[n] - sampleOffsets[0];
     const hipStream_t st = dcsCtxStream(ctx);
-    auto alloc = [&](void **p, size_t bytes) -> hipError_t {
-        held.emplace_back();
-        const hipError_t e = held.back().alloc(ctx, false, (bytes + 255) & ~size_t(255));
-        *p = held.back().as();
-        return e;
-    };
     float *dIn, *dMono;
     uint64_t *dInOff;
     int32_t *dCh;
     RsStream *dStr;
     uint32_t *dBad;
     ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dIn), sizeof(float) * nValues));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dMono), sizeof(float) * nMono));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dInOff), sizeof(uint64_t) * (n + 1)));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dCh), sizeof(int32_t) * n));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dStr), sizeof(RsStream) * n));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dBad), sizeof(uint32_t) * n));
+    ENCCHK(held.alloc(&dIn, nValues));
+    ENCCHK(held.alloc(&dMono, nMono));
+    ENCCHK(held.alloc(&dInOff, size_t(n) + 1));
+    ENCCHK(held.alloc(&dCh, n));
+    ENCCHK(held.alloc(&dStr, n));
+    ENCCHK(held.alloc(&dBad, n));
     ENCCHK(hipMemcpyAsync(dIn, pcm + sampleOffsets[0], sizeof(float) * nValues, hipMemcpyHostToDevice, st));
     ENCCHK(hipMemcpyAsync(dInOff, sampleOffsets, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, st));
     ENCCHK(hipMemcpyAsync(dCh, ch.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
@@ -656,24 +644,15 @@ extern "C" DcsStatus dcs_resample_streams(DcsCtx *ctx, const float *pcm, const u
     outOffsets[0] = 0;
     if (nStreams == 0)
         return DCS_OK;
-    const hipStream_t st = dcsCtxStream(ctx);
-    std::vector<CacheBuf> held;
-    status = [&]() -> DcsStatus {
-        float *dRes = nullptr;
-        std::vector<uint32_t> peak;
-        const DcsStatus s = resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, outOffsets, peak);
-        if (s != DCS_OK)
-            return s;
-        if (out == nullptr || outCap < outOffsets[nStreams])
-            return DCS_ERR_CAPACITY;
-        ENCCHK(hipMemcpyAsync(out, dRes, sizeof(float) * outOffsets[nStreams], hipMemcpyDeviceToHost, st));
-        ENCCHK(hipStreamSynchronize(st));
-        return DCS_OK;
-    }();
-    (void)hipStreamSynchronize(st);
-    for (CacheBuf &h : held)
-        h.release();
-    return status;
+    CacheArena held(ctx);
+    float *dRes = nullptr;
+    std::vector<uint32_t> peak;
+    ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, outOffsets, peak));
+    if (out == nullptr || outCap < outOffsets[nStreams])
+        return DCS_ERR_CAPACITY;
+    ENCCHK(hipMemcpyAsync(out, dRes, sizeof(float) * outOffsets[nStreams], hipMemcpyDeviceToHost, held.stream()));
+    ENCCHK(hipStreamSynchronize(held.stream()));
+    return DCS_OK;
 }
 
 extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
@@ -686,8 +665,8 @@ extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const 
     const bool os93 = params != nullptr && params->formatVersion != 0x9400;
     if (!paramsValid(params, os93))
     {
-        if (os93 && params->formatVersion == 0x9301 && params->streamFormatType == 1)
-            dcsCtxSetError(ctx, "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0");
+        if (const char *type1 = whyOs93aType1(params, os93))
+            dcsCtxSetError(ctx, type1);
         return DCS_ERR_INVALID_ARG;
     }
     DcsResampleFilter f;
@@ -703,39 +682,32 @@ extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const 
         outOffsets[0] = 0;
         return DCS_OK;
     }
-    const hipStream_t st = dcsCtxStream(ctx);
-    std::vector<CacheBuf> held;
-    status = [&]() -> DcsStatus {
-        float *dRes = nullptr;
-        std::vector<uint32_t> peak;
-        std::vector<uint64_t> resOffsets(static_cast<size_t>(nStreams) + 1);
-        DcsStatus s = resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, resOffsets.data(), peak);
-        if (s != DCS_OK)
-            return s;
-        for (uint32_t i = 0 ; i < nStreams ; ++i)
+    CacheArena held(ctx);
+    float *dRes = nullptr;
+    std::vector<uint32_t> peak;
+    std::vector<uint64_t> resOffsets(static_cast<size_t>(nStreams) + 1);
+    ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, resOffsets.data(), peak));
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+    {
+        const std::string name = "stream " + std::to_string(i);
+        const uint64_t m = resOffsets[i + 1] - resOffsets[i];
+        if (m == 0 || (m + 239) / 240 > 65535)
         {
-            const std::string name = "stream " + std::to_string(i);
-            const uint64_t m = resOffsets[i + 1] - resOffsets[i];
-            if (m == 0 || (m + 239) / 240 > 65535)
-            {
-                dcsCtxSetError(ctx, (name + (m == 0 ? ": resamples to no samples" : ": resamples to more than 65 535 frames")).c_str());
-                return DCS_ERR_INVALID_ARG;
-            }
-            if (peak[i] > 0x3f800000u)          // |y| > 1, or not a number
-            {
-                char text[160];
-                snprintf(text, sizeof(text), "%s: the resampled signal peaks at |x| = %.9g, outside [-1, 1] (attenuate the input)",
-                         name.c_str(), static_cast<double>(fromBitsU(peak[i])));
-                dcsCtxSetError(ctx, text);
-                return DCS_ERR_BAD_STREAM;
-            }
+            dcsCtxSetError(ctx, (name + (m == 0 ? ": resamples to no samples" : ": resamples to more than 65 535 frames")).c_str());
+            return DCS_ERR_INVALID_ARG;
         }
-        EncInput in;
-        in.devFloat = dRes;
-        return encodeStreams(ctx, in, resOffsets.data(), nStreams, params, out, outCap, outOffsets, info, os93);
-    }();
-    (void)hipStreamSynchronize(st);
-    for (CacheBuf &h : held)
-        h.release();
-    return status;
+        if (peak[i] > 0x3f800000u)          // |y| > 1, or not a number
+        {
+            char text[160];
+            snprintf(text, sizeof(text), "%s: the resampled signal peaks at |x| = %.9g, outside [-1, 1] (attenuate the input)",
+                     name.c_str(), static_cast<double>(fromBitsU(peak[i])));
+            dcsCtxSetError(ctx, text);
+            return DCS_ERR_BAD_STREAM;
+        }
+    }
+    EncInput in;
+    in.sampleOffsets = resOffsets.data();
+    in.nStreams = nStreams;
+    in.devFloat = dRes;
+    return encodeStreams(ctx, in, params, os93, EncOutput{ out, outCap, outOffsets, info, nullptr });
 }

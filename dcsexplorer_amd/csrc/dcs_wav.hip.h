@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256) void wavUnpackKernel(const uint8_t *__restrict
 // The parsed WAV files of one call on the device: payloads up, W0, W1.  On DCS_OK *dMono holds file k's mono samples from
 // files[k].monoOff; bad[k] is set where a value or a pair's mean is not finite.  Buffers belong to `held`.
 DcsStatus wavStageOnDevice(DcsCtx *ctx, const uint8_t *const *bytes, const DcsWavInfo *infos, uint32_t n, std::vector<WavFile> &wf,
-                           std::vector<CacheBuf> &held, float **dMonoOut, std::vector<uint32_t> &bad)
+                           CacheArena &held, float **dMonoOut, std::vector<uint32_t> &bad)
 {
     wf.assign(n, WavFile{});
     uint64_t blobBytes = 0, nStaged = 0, nMono = 0, maxMono = 0, maxLanes = 0;
@@ -326,24 +326,18 @@ DcsStatus wavStageOnDevice(DcsCtx *ctx, const uint8_t *const *bytes, const DcsWa
         byFormat[w.sampleFormat].push_back(k);
     }
     const hipStream_t st = dcsCtxStream(ctx);
-    auto alloc = [&](void **p, size_t bytes) -> hipError_t {
-        held.emplace_back();
-        const hipError_t e = held.back().alloc(ctx, false, (bytes + 255) & ~size_t(255));
-        *p = held.back().as();
-        return e;
-    };
     uint8_t *dBlob;
     int16_t *dStaged;
     float *dMono;
     WavFile *dFiles;
     uint32_t *dWhich, *dBad;
     ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dBlob), blobBytes ? blobBytes : 1));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dStaged), sizeof(int16_t) * (nStaged ? nStaged : 1)));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dMono), sizeof(float) * (nMono ? nMono : 1)));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dFiles), sizeof(WavFile) * n));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dWhich), sizeof(uint32_t) * n));
-    ENCCHK(alloc(reinterpret_cast<void **>(&dBad), sizeof(uint32_t) * n));
+    ENCCHK(held.alloc(&dBlob, blobBytes ? blobBytes : 1));
+    ENCCHK(held.alloc(&dStaged, nStaged ? nStaged : 1));
+    ENCCHK(held.alloc(&dMono, nMono ? nMono : 1));
+    ENCCHK(held.alloc(&dFiles, n));
+    ENCCHK(held.alloc(&dWhich, n));
+    ENCCHK(held.alloc(&dBad, n));
     for (uint32_t k = 0 ; k < n ; ++k)
     {
         const DcsWavInfo &w = infos[k];
@@ -564,8 +558,8 @@ DcsStatus filesArgs(const uint8_t *files, const uint64_t *fileOffsets, uint32_t 
     const bool os93 = params != nullptr && params->formatVersion != 0x9400;
     if (!paramsValid(params, os93))
     {
-        if (os93 && params->formatVersion == 0x9301 && params->streamFormatType == 1)
-            why = "OS93a Type 1 streams cannot be encoded (the reference has no encoder for them); ask for Type 0";
+        if (const char *type1 = whyOs93aType1(params, os93))
+            why = type1;
         return DCS_ERR_INVALID_ARG;
     }
     const uint64_t none[1] = { 0 };
@@ -633,26 +627,17 @@ DcsStatus wavDecode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffse
         outOffsets[i + 1] = outOffsets[i] + rsMonoLength(infos[i].nValues, infos[i].channels);
     if (nFiles == 0)
         return DCS_OK;
-    const hipStream_t st = dcsCtxStream(ctx);
-    std::vector<CacheBuf> held;
-    const DcsStatus status = [&]() -> DcsStatus {
-        std::vector<WavFile> wf;
-        std::vector<uint32_t> bad;
-        float *dMono = nullptr;
-        const DcsStatus s = wavStageOnDevice(ctx, bytes.data(), infos.data(), nFiles, wf, held, &dMono, bad);
-        if (s != DCS_OK)
-            return s;
-        if (out == nullptr || outCap < outOffsets[nFiles])
-            return DCS_ERR_CAPACITY;
-        if (outOffsets[nFiles] != 0)
-            ENCCHK(hipMemcpyAsync(out, dMono, sizeof(float) * outOffsets[nFiles], hipMemcpyDeviceToHost, st));
-        ENCCHK(hipStreamSynchronize(st));
-        return DCS_OK;
-    }();
-    (void)hipStreamSynchronize(st);
-    for (CacheBuf &h : held)
-        h.release();
-    return status;
+    CacheArena held(ctx);
+    std::vector<WavFile> wf;
+    std::vector<uint32_t> bad;
+    float *dMono = nullptr;
+    ENCTRY(wavStageOnDevice(ctx, bytes.data(), infos.data(), nFiles, wf, held, &dMono, bad));
+    if (out == nullptr || outCap < outOffsets[nFiles])
+        return DCS_ERR_CAPACITY;
+    if (outOffsets[nFiles] != 0)
+        ENCCHK(hipMemcpyAsync(out, dMono, sizeof(float) * outOffsets[nFiles], hipMemcpyDeviceToHost, held.stream()));
+    ENCCHK(hipStreamSynchronize(held.stream()));
+    return DCS_OK;
 }
 
 DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
@@ -697,98 +682,87 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
     std::vector<uint64_t> wavOffsets(static_cast<size_t>(nW) + 1, 0);
     if (nW != 0)
     {
-        const hipStream_t st = dcsCtxStream(ctx);
-        std::vector<CacheBuf> held;
-        status = [&]() -> DcsStatus {
-            std::vector<DcsWavInfo> infos(nW);
-            std::vector<const uint8_t *> bytes(nW);
-            for (uint32_t k = 0 ; k < nW ; ++k)
+        CacheArena held(ctx);               // (given back at the end of this block, before the DCSa group borrows its own)
+        std::vector<DcsWavInfo> infos(nW);
+        std::vector<const uint8_t *> bytes(nW);
+        for (uint32_t k = 0 ; k < nW ; ++k)
+        {
+            infos[k] = plan[wavIdx[k]].wav;
+            bytes[k] = files + fileOffsets[wavIdx[k]];
+        }
+        std::vector<WavFile> wf;
+        std::vector<uint32_t> bad;
+        float *dMono = nullptr;
+        ENCTRY(wavStageOnDevice(ctx, bytes.data(), infos.data(), nW, wf, held, &dMono, bad));
+        for (uint32_t k = 0 ; k < nW ; ++k)
+            if (bad[k])
             {
-                infos[k] = plan[wavIdx[k]].wav;
-                bytes[k] = files + fileOffsets[wavIdx[k]];
+                dcsCtxSetError(ctx, ("file " + std::to_string(wavIdx[k]) + ": a sample (or a stereo pair's mean) is not finite").c_str());
+                return DCS_ERR_BAD_STREAM;
             }
-            std::vector<WavFile> wf;
-            std::vector<uint32_t> bad;
-            float *dMono = nullptr;
-            DcsStatus s = wavStageOnDevice(ctx, bytes.data(), infos.data(), nW, wf, held, &dMono, bad);
-            if (s != DCS_OK)
-                return s;
-            for (uint32_t k = 0 ; k < nW ; ++k)
-                if (bad[k])
-                {
-                    dcsCtxSetError(ctx, ("file " + std::to_string(wavIdx[k]) + ": a sample (or a stereo pair's mean) is not finite").c_str());
-                    return DCS_ERR_BAD_STREAM;
-                }
-            std::vector<RsStream> hs(nW);
-            for (uint32_t k = 0 ; k < nW ; ++k)
+        std::vector<RsStream> hs(nW);
+        for (uint32_t k = 0 ; k < nW ; ++k)
+        {
+            hs[k] = rsStreamOf(wf[k].nMono, infos[k].rate, f, flags);
+            hs[k].inOff = wf[k].monoOff;
+        }
+        rsHostRoute(hs);
+        float *dRes = nullptr;
+        std::vector<uint32_t> peak;
+        std::vector<uint64_t> resOffsets(static_cast<size_t>(nW) + 1);
+        ENCTRY(rsWalkConvolve(ctx, hs, dMono, nullptr, f, wavIdx.data(), "file", held, &dRes, resOffsets.data(), peak));
+        for (uint32_t k = 0 ; k < nW ; ++k)
+        {
+            const std::string name = "file " + std::to_string(wavIdx[k]);
+            const uint64_t m = resOffsets[k + 1] - resOffsets[k];
+            if (m == 0 || (m + 239) / 240 > 65535)
             {
-                hs[k] = rsStreamOf(wf[k].nMono, infos[k].rate, f, flags);
-                hs[k].inOff = wf[k].monoOff;
+                dcsCtxSetError(ctx, (name + (m == 0 ? ": resamples to no samples" : ": resamples to more than 65 535 frames")).c_str());
+                return DCS_ERR_INVALID_ARG;
             }
-            rsHostRoute(hs);
-            float *dRes = nullptr;
-            std::vector<uint32_t> peak;
-            std::vector<uint64_t> resOffsets(static_cast<size_t>(nW) + 1);
-            s = rsWalkConvolve(ctx, hs, dMono, nullptr, f, wavIdx.data(), "file", held, &dRes, resOffsets.data(), peak);
-            if (s != DCS_OK)
-                return s;
-            for (uint32_t k = 0 ; k < nW ; ++k)
+            const float b = wavBound(infos[k].sampleFormat);
+            if (!(fromBitsU(peak[k]) <= b))
             {
-                const std::string name = "file " + std::to_string(wavIdx[k]);
-                const uint64_t m = resOffsets[k + 1] - resOffsets[k];
-                if (m == 0 || (m + 239) / 240 > 65535)
-                {
-                    dcsCtxSetError(ctx, (name + (m == 0 ? ": resamples to no samples" : ": resamples to more than 65 535 frames")).c_str());
-                    return DCS_ERR_INVALID_ARG;
-                }
-                const float b = wavBound(infos[k].sampleFormat);
-                if (!(fromBitsU(peak[k]) <= b))
-                {
-                    char text[192];
-                    snprintf(text, sizeof(text), "%s: the signal the encoder reads peaks at |x| = %.9g, beyond %.9g (attenuate the input)",
-                             name.c_str(), static_cast<double>(fromBitsU(peak[k])), static_cast<double>(b));
-                    dcsCtxSetError(ctx, text);
-                    return DCS_ERR_BAD_STREAM;
-                }
+                char text[192];
+                snprintf(text, sizeof(text), "%s: the signal the encoder reads peaks at |x| = %.9g, beyond %.9g (attenuate the input)",
+                         name.c_str(), static_cast<double>(fromBitsU(peak[k])), static_cast<double>(b));
+                dcsCtxSetError(ctx, text);
+                return DCS_ERR_BAD_STREAM;
             }
-            uint64_t cap = 0;
-            std::vector<float> bound(nW);
-            for (uint32_t k = 0 ; k < nW ; ++k)
-                bound[k] = wavBound(infos[k].sampleFormat);
-            for (uint32_t k = 0 ; k < nW ; ++k)
-                cap += (os93 ? dcs_encode93_bound : dcs_encode_bound)(resOffsets[k + 1] - resOffsets[k]);
-            wavOut.resize(cap ? cap : 1);
-            std::vector<DcsEncodeInfo> enc(nW);
-            EncInput in;
-            in.devFloat = dRes;
-            in.label = wavIdx.data();
-            in.bound = bound.data();
-            s = encodeStreams(ctx, in, resOffsets.data(), nW, params, wavOut.data(), cap, wavOffsets.data(), enc.data(), os93);
-            if (s != DCS_OK)
-            {
-                renameError(ctx, nullptr);           // (the encoder's messages give the file's own index: in.label)
-                return s;
-            }
-            for (uint32_t k = 0 ; k < nW ; ++k)
-            {
-                DcsEncodeFileInfo &t = fi[wavIdx[k]];
-                t.kind = DCS_FILE_WAV;
-                t.sourceFormat = infos[k].formatCode;
-                t.rate = infos[k].rate;
-                t.channels = infos[k].channels;
-                t.nValues = infos[k].nValues;
-                t.nSamples = resOffsets[k + 1] - resOffsets[k];
-                t.walk = hs[k].passThrough ? DCS_FILE_WALK_NONE : hs[k].hostWalk ? DCS_FILE_WALK_HOST : DCS_FILE_WALK_DEVICE;
-                t.enc = enc[k];
-                size[wavIdx[k]] = wavOffsets[k + 1] - wavOffsets[k];
-            }
-            return DCS_OK;
-        }();
-        (void)hipStreamSynchronize(st);
-        for (CacheBuf &h : held)
-            h.release();
+        }
+        uint64_t cap = 0;
+        std::vector<float> bound(nW);
+        for (uint32_t k = 0 ; k < nW ; ++k)
+            bound[k] = wavBound(infos[k].sampleFormat);
+        for (uint32_t k = 0 ; k < nW ; ++k)
+            cap += (os93 ? dcs_encode93_bound : dcs_encode_bound)(resOffsets[k + 1] - resOffsets[k]);
+        wavOut.resize(cap ? cap : 1);
+        std::vector<DcsEncodeInfo> enc(nW);
+        EncInput in;
+        in.sampleOffsets = resOffsets.data();
+        in.nStreams = nW;
+        in.devFloat = dRes;
+        in.label = wavIdx.data();
+        in.bound = bound.data();
+        status = encodeStreams(ctx, in, params, os93, EncOutput{ wavOut.data(), cap, wavOffsets.data(), enc.data(), nullptr });
         if (status != DCS_OK)
+        {
+            renameError(ctx, nullptr);           // (the encoder's messages give the file's own index: in.label)
             return status;
+        }
+        for (uint32_t k = 0 ; k < nW ; ++k)
+        {
+            DcsEncodeFileInfo &t = fi[wavIdx[k]];
+            t.kind = DCS_FILE_WAV;
+            t.sourceFormat = infos[k].formatCode;
+            t.rate = infos[k].rate;
+            t.channels = infos[k].channels;
+            t.nValues = infos[k].nValues;
+            t.nSamples = resOffsets[k + 1] - resOffsets[k];
+            t.walk = hs[k].passThrough ? DCS_FILE_WALK_NONE : hs[k].hostWalk ? DCS_FILE_WALK_HOST : DCS_FILE_WALK_DEVICE;
+            t.enc = enc[k];
+            size[wavIdx[k]] = wavOffsets[k + 1] - wavOffsets[k];
+        }
     }
     // the DCSa group: EncodeDCSFile's copy or re-encode (dcs_transcode_streams)
     const uint32_t nD = static_cast<uint32_t>(dcsaIdx.size());
