@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Generates dcs_encode_files' fixtures from the reference's own code (build container only; outputs are data):
-  encode_file_golden.{json,npz}  every case of tests/wav_cases.py (and the 180 s file, sha256 only) run through the
+  encode_file_golden.{json,npz}  every case of tests/wav_cases.py (cases(), the 180 s file with its sha256 only, then
+                                 float_edge_cases()) run through the
                                  reference's DCSEncoder::EncodeFile (encode_file/ef_driver.cpp), linked with the vendored
                                  libnyquist and libsamplerate: NyquistIO::Load's result (its float bits for the short cases,
                                  the sha256 of all of them, or its exception text) and EncodeFile's stream or error text
@@ -81,7 +82,8 @@ def run(exe, path, tmp, fv, typ, sub):
 def main():
     import dcsexplorer_amd as D
     coeffs, inc = D.resample_filter_default()
-    cases = W.cases() + [("long_180s_s16_stereo_44100", W.long_wav())]
+    # (the float-edge cases come last, so the entries before them keep their places and their bytes)
+    cases = W.cases() + [("long_180s_s16_stereo_44100", W.long_wav())] + W.float_edge_cases()
     meta, arrays = [], {}
     with tempfile.TemporaryDirectory() as tmp:
         nqb = os.path.join(tmp, "nq")

@@ -20,7 +20,6 @@ own: a bounds or float-cast report drops the case.  Everything is compiled into 
 import hashlib
 import json
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -31,6 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import resample_ref as R        # noqa: E402  (lcg_signal: the long cases' inputs, kept as a recipe)
+from oracle.rsref import build_lsr, stand_in, vendored as _vendored      # noqa: E402  (the recipe `make -C oracle rsref` uses)
 HERE = os.path.join(ROOT, "tests", "golden")
 REF = "/root/reference"
 LSR = os.path.join(REF, "libsamplerate", "src")
@@ -41,13 +41,7 @@ ENC_FMTS = {"wild": (0x9400, -1, -1), "T0": (0x9400, 0, 0), "T1s3": (0x9400, 1, 
 
 
 def vendored(name):
-    """a vendored table: (float32 coefficients, increment), read from its header as data"""
-    text = open(os.path.join(LSR, name)).read()
-    inc = int(re.search(r"increment\s*:\s*(\d+)", text).group(1))
-    body = text[text.index("=", text.index("coeffs [")):]        # "= { increment, { c0, c1, ... } }"
-    body = body[body.index("{", body.index("{") + 1) + 1:body.index("}")]
-    vals = [float(v) for v in re.findall(r"[-+]?\d*\.\d+(?:[eE][-+]?\d+)?|[-+]?\d+[eE][-+]?\d+", body)]
-    return np.array(vals, np.float32), inc
+    return _vendored(LSR, name)
 
 
 def long_table():
@@ -58,34 +52,6 @@ def long_table():
     c = fc * np.sinc(fc * t) * np.i0(8.0 * np.sqrt(np.clip(1 - (t / half) ** 2, 0, 1))) / np.i0(8.0)
     c[t >= half] = 0.0
     return c.astype(np.float32), inc
-
-
-def stand_in(coeffs, inc):
-    """high_qual_coeffs.h of ours: the best-quality slot holds `coeffs`"""
-    vals = ",\n".join(float(v).hex() for v in coeffs.astype(np.float64))
-    return ("static const struct slow_high_qual_coeffs_s\n{\tint increment ;\n\tcoeff_t coeffs [%d] ;\n} slow_high_qual_coeffs =\n"
-            "{\t%d,\n{\n%s\n}\n} ;\n" % (len(coeffs), inc, vals))
-
-
-def build_lsr(tmp, name, coeffs, inc, driver, cxx=False, extra=()):
-    d = os.path.join(tmp, name)
-    os.makedirs(d, exist_ok=True)
-    open(os.path.join(d, "high_qual_coeffs.h"), "w").write(stand_in(coeffs, inc))
-    objs = []
-    for src in ("samplerate.c", "src_sinc.c", "src_linear.c", "src_zoh.c"):
-        o = os.path.join(d, src + ".o")
-        subprocess.check_call(["gcc", "-O2", "-w", "-I" + d, "-I" + LSR, "-c", os.path.join(LSR, src), "-o", o] + list(extra))
-        objs.append(o)
-    exe = os.path.join(d, "drv")
-    if cxx:
-        enc = os.path.join(HERE, "encoder")
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-w", "-include", os.path.join(enc, "enc_shim.h"),
-                               "-I" + os.path.join(REF, "DCSEncoder"), "-I" + LSR, "-o", exe, driver,
-                               os.path.join(REF, "DCSEncoder", "DCSEncoder.cpp"), os.path.join(REF, "DCSDecoder", "DCSDecoder.cpp"),
-                               os.path.join(REF, "DCSDecoder", "DCSDecoderNative.cpp")] + objs + list(extra) + ["-lpthread", "-lm"])
-    else:
-        subprocess.check_call(["gcc", "-O2", "-w", "-I" + LSR, "-o", exe, driver] + objs + ["-lm"])
-    return exe
 
 
 def signals():

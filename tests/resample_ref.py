@@ -185,7 +185,8 @@ def convert(mono, rate, coeffs, increment, flags=0):
     p = pos + reach
     left = _half_sum(c, xp, p, sfi, inc_t, max_fi, +1)
     right = _half_sum(c, xp, p, inc_t - sfi, inc_t, max_fi, -1)
-    return ((float_inc / increment) * (left + right)).astype(np.float32)
+    with np.errstate(over="ignore"):        # a sum past FLT_MAX rounds to +-inf, as the C cast does
+        return ((float_inc / increment) * (left + right)).astype(np.float32)
 
 
 def resample(values, rate, coeffs, increment, channels=1, flags=0):

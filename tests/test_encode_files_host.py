@@ -1,5 +1,8 @@
 """dcs_wav_parse and dcs_encode_files_plan (host only) against tests/wav_ref.py on the seeded cases of tests/wav_cases.py,
 and each numbered rule of INTEGRATION.md "Encoding files" that needs no GPU."""
+import hashlib
+import json
+import os
 import struct
 
 import numpy as np
@@ -10,6 +13,9 @@ import wav_cases as W
 import wav_ref as R
 
 CASES = W.cases()
+EDGE = W.float_edge_cases()
+REF = {c["name"]: c for c in json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                                           "encode_file_golden.json")))["cases"]}
 
 
 @pytest.mark.parametrize("name,data", CASES, ids=[c[0] for c in CASES])
@@ -132,3 +138,52 @@ def test_extensible_chunk_past_the_end_is_bad_stream():
                    + bytes(2)])
     assert D.wav_parse(body)["status"] == R.BAD_STREAM
     assert R.parse(body)[0] == R.BAD_STREAM
+
+
+@pytest.mark.parametrize("name,data", EDGE, ids=[c[0] for c in EDGE])
+def test_float_edge_files_parse_and_load_as_nyquist(name, data):
+    """the float-edge files: dcs_wav_parse equals the restatement, and wav_ref's values are NyquistIO::Load's floats (sha256
+    over the bits, so NaN payloads and signed zeros count) wherever libnyquist reads the file as float (not EXTENSIBLE,
+    rule 10)"""
+    got = D.wav_parse(data)
+    st, d = R.parse(data)
+    assert got["status"] == st == 0, (name, got["reason"])
+    for k in ("formatCode", "channels", "rate", "blockAlign", "bitDepth", "sampleFormat", "dataOffset", "dataSize", "nValues"):
+        assert got[k] == d[k], (name, k)
+    ref = REF[name]
+    assert ref["file_sha256"] == hashlib.sha256(data).hexdigest()
+    assert all(r["load"].startswith("ok") for r in ref["runs"])
+    v = R.values(data, d)
+    assert len(v) == ref["n_values"]
+    if "_ext_" not in name:
+        assert hashlib.sha256(np.asarray(v, "<f4").tobytes()).hexdigest() == ref["values_sha256"], name
+    else:
+        assert hashlib.sha256(np.asarray(v, "<f4").tobytes()).hexdigest() != ref["values_sha256"], name
+
+
+def test_float_edge_files_hold_the_edges():
+    """what the list is for, read back through the restatement: no edge is lost to a change of seed"""
+    vals = {n: R.values(b, R.parse(b)[1]) for n, b in EDGE}
+    raw64 = {n: np.frombuffer(b[R.parse(b)[1]["dataOffset"]:][:8 * R.parse(b)[1]["nValues"]], "<f8") for n, b in EDGE if "_f64_" in n}
+    fmax, tiny = np.finfo(np.float32).max, 2.0 ** -126
+    assert {R.parse(b)[1]["sampleFormat"] for _, b in EDGE} == {D.WAV_F32, D.WAV_F64}
+    assert {R.parse(b)[1]["channels"] for _, b in EDGE} == {1, 2} and {R.parse(b)[1]["formatCode"] for _, b in EDGE} == {3, 0xFFFE}
+    sub = vals["fe_f32_subnormal_1ch"]
+    assert ((np.abs(sub) > 0) & (np.abs(sub) < tiny)).sum() > 700 and (sub.view(np.uint32) == 0x80000000).sum() > 100
+    v, r = vals["fe_f64_to_subnormal_1ch"], raw64["fe_f64_to_subnormal_1ch"]
+    assert (v.astype(np.float64) != r).sum() > 900 and (np.abs(v) <= tiny).all()           # every one rounds, into the range
+    assert v[0] == 0 and v[1] == np.float32(2 * 2.0 ** -149) and v[2] == np.float32(2 * 2.0 ** -149)     # ties to even
+    v, r = vals["fe_f64_to_zero_2ch"], raw64["fe_f64_to_zero_2ch"]
+    assert (v == 0).all() and (r != 0).all() and (v.view(np.uint32) == 0x80000000).any() and (v.view(np.uint32) == 0).any()
+    v, r = vals["fe_f64_to_fltmax_1ch"], raw64["fe_f64_to_fltmax_1ch"]
+    assert (np.abs(v) == fmax).sum() >= 9 and not (np.abs(r) == float(fmax)).any() and np.isfinite(v).all()
+    v, r = vals["fe_f64_overflow_1ch"], raw64["fe_f64_overflow_1ch"]
+    assert np.isinf(v).sum() >= 9 and np.isfinite(r).all()
+    assert np.isnan(vals["fe_f32_nan_1ch"]).any() and np.isposinf(vals["fe_f32_inf_2ch"]).any() and np.isneginf(vals["fe_f32_inf_2ch"]).any()
+    v = vals["fe_f32_pair_overflow_2ch"]
+    assert np.isfinite(v).all() and np.isinf(R.downmix(v, 2)).sum() >= 2
+    one = np.float32(1)
+    assert {1.0, -1.0, float(np.nextafter(one, np.float32(0)))} <= set(np.abs(vals["fe_f32_at_one_1ch"]).tolist() + vals["fe_f32_at_one_1ch"].tolist())
+    assert np.abs(vals["fe_f32_above_one_1ch"]).max() == np.nextafter(one, np.float32(2))
+    v, r = vals["fe_f64_rounds_to_one_1ch"], raw64["fe_f64_rounds_to_one_1ch"]
+    assert np.abs(v).max() == 1.0 and np.abs(r).max() > 1.0

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import dcsexplorer_amd as D
+import resample_ref as RS
 import wav_cases as W
 import wav_ref as R
 from dcsexplorer_amd.api import ERR_BAD_STREAM, ERR_CAPACITY, ERR_INVALID_ARG, DcsError, _files_blob, _ptr, transcode_params
@@ -19,6 +20,7 @@ from dcsexplorer_amd.api import ERR_BAD_STREAM, ERR_CAPACITY, ERR_INVALID_ARG, D
 pytestmark = pytest.mark.gpu
 
 CASES = W.cases()
+EDGE = W.float_edge_cases()
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = json.load(open(os.path.join(HERE, "golden", "encode_file_golden.json")))
 REF_RUN = {(c["name"], r["version"]): r for c in REF["cases"] for r in c["runs"]}
@@ -102,17 +104,25 @@ def test_full_scale_negative_is_accepted(gpu_ctx):
         gpu_ctx.encode_streams_at([np.full(500, np.float32(-32768) / np.float32(32767))], 31250)
 
 
-# Where the library departs from what the reference does with the file (INTEGRATION.md rules 8-11, and the resampler's rate
-# range): it refuses the file, or reads it differently (rule 10), so the reference's bytes are not the contract there
+# Where the library departs from what the reference does with the file (INTEGRATION.md rules 8-12 and 19, and the resampler's
+# rate range): it refuses the file, or reads it differently (rule 10), so the reference's bytes are not the contract there
 DEPARTS = {"ext_float_f32": 10, "ext_float_f64": 10, "err_mulaw": 9, "err_bits12": 9, "err_int64": 9, "err_ext_other": 10,
            "err_3ch": 9, "err_data_past_end": 8, "err_blockalign0": 8, "err_ima_no_fact": 11, "err_ima_step89": 11,
-           "err_ima_overflow": 11, "enc_err_rate_low": 0, "fullscale_s16_31250": 12, "fullscale_u8_31250": 12}
+           "err_ima_overflow": 11, "enc_err_rate_low": 0, "fullscale_s16_31250": 12, "fullscale_u8_31250": 12,
+           # float files (tests/wav_cases.py float_edge_cases): EXTENSIBLE float is read as float (rule 10); a value or a pair's
+           # mean that is not finite, and a float value above 1 that reaches the encoder, are refused (rule 19), where the
+           # reference encodes them -- the first kind through casts its sanitizer build reports; a full-scale DC level
+           # overshoots in the converter (rule 12)
+           "fe_ext_f32_subnormal_2ch": 10, "fe_ext_f64_to_subnormal_1ch": 10, "fe_ext_f32_inf_1ch": 10,
+           "fe_f64_overflow_1ch": 19, "fe_f32_nan_1ch": 19, "fe_f32_inf_2ch": 19, "fe_f64_inf_1ch": 19,
+           "fe_f32_pair_overflow_2ch": 19, "fe_f64_to_fltmax_1ch": 19, "fe_f32_fltmax_1ch": 19,
+           "fe_f32_dc_above_one_1ch": 19, "fe_f64_dc_above_one_2ch": 19, "fe_f32_dc_one_1ch": 12}
 
 
 @pytest.mark.parametrize("version", [0x9400, 0x9302])
 def test_encode_files_equals_reference_encodefile(gpu_ctx, version):
     """bytes and refusals against the reference's own EncodeFile linked with libnyquist (tests/golden/encode_file_golden.*)"""
-    by = dict(CASES)
+    by = dict(CASES + EDGE)
     acc, n_ref_refused = [], 0
     for c in REF["cases"]:
         name = c["name"]
@@ -121,7 +131,7 @@ def test_encode_files_equals_reference_encodefile(gpu_ctx, version):
         run = REF_RUN[name, version]
         ours = R.parse(by[name])[0]
         if name in DEPARTS:
-            assert ours != 0 or DEPARTS[name] in (0, 10, 12), name
+            assert ours != 0 or DEPARTS[name] in (0, 10, 12, 19), name
             continue
         if run["encode"] is None or not run["encode"].startswith("ok"):
             assert ours != 0, name                          # the reference refuses it: so does the library
@@ -142,8 +152,8 @@ def test_encode_files_equals_reference_encodefile(gpu_ctx, version):
 
 def test_wav_decode_equals_nyquist_load(gpu_ctx):
     """the values before the downmix are NyquistIO::Load's: every case's float sha256 through wav_ref, and the mono cases
-    (whose output is Load's floats themselves) through dcs_wav_decode"""
-    by = dict(CASES)
+    (whose output is Load's floats themselves) through dcs_wav_decode; the float-edge cases are among them"""
+    by = dict(CASES + EDGE)
     for c in REF["cases"]:
         name = c["name"]
         if name in DEPARTS or name.startswith("long_") or "values_sha256" not in c or R.parse(by[name])[0] != 0:
@@ -154,6 +164,87 @@ def test_wav_decode_equals_nyquist_load(gpu_ctx):
         if d["channels"] == 1:
             y = gpu_ctx.wav_decode([by[name]])[0]
             assert hashlib.sha256(np.asarray(y, "<f4").tobytes()).hexdigest() == c["values_sha256"], name
+
+
+def test_float_edges_decode_to_the_restated_bits(gpu_ctx):
+    """subnormals, -0.0, f64 values rounding into the subnormal range, to +-0, to FLT_MAX and past it, NaN and +-inf: the
+    device unpack gives wav_ref's bits (a NaN only where it is copied, so its payload is the file's), alone and in a batch"""
+    got = gpu_ctx.wav_decode([b for _, b in EDGE])
+    for (name, b), y in zip(EDGE, got):
+        want = R.decode(b)[1]
+        assert same_bits(y, want), name
+        assert same_bits(gpu_ctx.wav_decode([b])[0], want), name
+    flat = np.concatenate(got)
+    a = np.abs(flat)
+    # (-0.0: the 500 pairs of the all -0.0 file and every seventh value of the mono subnormal file, 143, at the least)
+    assert ((a > 0) & (a < 2.0 ** -126)).sum() > 3000 and (flat.view(np.uint32) == 0x80000000).sum() >= 643
+    assert np.isnan(flat).any() and np.isposinf(flat).any() and np.isneginf(flat).any() and (a == np.finfo(np.float32).max).any()
+
+
+def test_more_than_65535_files_in_one_decode(gpu_ctx):
+    """70 001 small f32 files drawn from 56 distinct ones (5 to 60 values of the float-edge kinds, mono and stereo):
+    wavUnpackKernel's blockIdx.y loop takes a second pass, and every file still decodes to its own bits"""
+    rng = np.random.default_rng(0x70001)
+    src = np.concatenate([R.values(b, R.parse(b)[1]) for n, b in EDGE if "_f32_" in n and "nan" not in n and "_ext_" not in n])
+    pool = []
+    for k in range(56):
+        n, ch = int(rng.integers(5, 61)), 1 + k % 2
+        n += n % ch
+        at = int(rng.integers(0, len(src) - n))
+        pool.append(W.wav("f32", ch, (8000, 22050, 44100, 48000)[k % 4], src[at:at + n]))
+    want = [R.decode(b)[1] for b in pool]
+    assert all(len(b) >= 64 for b in pool) and any(np.isinf(w).any() for w in want) and any((np.abs(w) < 2.0 ** -126).all() for w in want)
+    idx = rng.integers(0, len(pool), 70001)
+    idx[:len(pool)] = idx[-len(pool):] = np.arange(len(pool))
+    got = gpu_ctx.wav_decode([pool[i] for i in idx])
+    assert len(got) == 70001 > 65535
+    bad = [k for k, (i, y) in enumerate(zip(idx, got)) if not same_bits(y, want[i])]
+    assert not bad, (len(bad), bad[:5])
+
+
+def _refused(ctx, good, data, *words, **kw):
+    with pytest.raises(DcsError) as e:
+        ctx.encode_files([good, data], **kw)
+    assert e.value.status == ERR_BAD_STREAM
+    msg = ctx.L.dcs_last_error(ctx.h).decode()
+    assert msg.startswith("file 1:") and all(w in msg for w in words), msg
+    return msg
+
+
+def test_float_edges_refusals_name_the_file(gpu_ctx):
+    """rule 19: a float file with a value, or a pair's mean, that is not finite is refused as such, and one whose signal
+    passes 1 where the encoder reads it is refused with its peak -- decided by wav_ref's floats and the restated converter,
+    not by the kernel's.  Every departure listed for these files is one of the two; every other file encodes."""
+    good = dict(CASES)["s16_1ch_22050"]
+    c, inc = D.resample_filter_default()
+    n_finite = n_peak = n_ok = 0
+    for name, b in EDGE:
+        st, mono, d = R.decode(b)
+        assert st == 0, name
+        if not np.isfinite(mono).all():
+            _refused(gpu_ctx, good, b, "finite", at_unity=True)
+            _refused(gpu_ctx, good, b, "finite")
+            assert DEPARTS.get(name) in (19, 10), name
+            n_finite += 1
+            continue
+        with np.errstate(over="ignore"):
+            peak = float(np.abs(RS.convert(mono, d["rate"], c, inc, RS.AT_UNITY)).max())
+        if peak > 1.0:
+            _refused(gpu_ctx, good, b, "peaks at", at_unity=True)
+            assert DEPARTS.get(name) in (19, 12), name
+            n_peak += 1
+        else:
+            out, _ = gpu_ctx.encode_files([good, b], at_unity=True)
+            assert len(out[1]) >= 18 and (name not in DEPARTS or DEPARTS[name] == 10), name
+            n_ok += 1
+    assert n_finite >= 6 and n_peak >= 5 and n_ok >= 14
+    by = dict(EDGE)
+    # at 31 250 Hz without the converter the encoder reads the file's own values: +-1 and 1 - 2^-24 pass, 1 + 2^-23 does not
+    out, info = gpu_ctx.encode_files([by["fe_f32_at_one_1ch"], by["fe_f32_dc_one_1ch"]])
+    assert all(len(o) > 18 for o in out) and list(info["walk"]) == [D.FILE_WALK_NONE] * 2
+    for name in ("fe_f32_above_one_1ch", "fe_f32_dc_above_one_1ch", "fe_f64_dc_above_one_2ch"):
+        msg = _refused(gpu_ctx, good, by[name], "peaks at")
+        assert "1.00000012" in msg, msg
 
 
 def dcsa(fmt, frames, seed):

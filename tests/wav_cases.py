@@ -203,6 +203,80 @@ def cases():
     return out
 
 
+# ------------------------------------------------------------------------------------------------- float files' edges
+
+F32_TINY, F32_NORM_MIN, F32_MAX = 2.0 ** -149, 2.0 ** -126, float(np.finfo(np.float32).max)
+ONE_UP, ONE_DOWN = float(np.nextafter(np.float32(1), np.float32(2))), float(np.nextafter(np.float32(1), np.float32(0)))
+
+
+def _quiet(n, seed):
+    return signal("f32", n, seed, 0.3).astype(np.float32).astype(np.float64)
+
+
+def _isolated(n, seed, vals):
+    """a quiet tone with single samples of `vals`, 40 apart"""
+    x = _quiet(n, seed)
+    for k, v in enumerate(vals * 3):
+        x[100 + 40 * k] = v
+    return x
+
+
+def float_edge_cases():
+    """-> list of (name, bytes): f32 and f64 files, plain and EXTENSIBLE, mono and stereo, at the edges of the float formats.
+    A second list beside cases(), which stays as it is.  1 000 values each."""
+    rng = np.random.default_rng(0xF10A7)
+    n = 1000
+    out = []
+    sub = rng.integers(-(1 << 23) + 1, 1 << 23, n).astype(np.float64) * F32_TINY            # every f32 subnormal magnitude
+    sub[::7] = -0.0
+    sub[3::11] = 0.0
+    out.append(("fe_f32_subnormal_1ch", wav("f32", 1, 44100, sub)))
+    out.append(("fe_f32_subnormal_2ch", wav("f32", 2, 22050, np.append(sub, -F32_TINY))))    # half a frame at the end: not counted
+    out.append(("fe_f32_negzero_2ch", wav("f32", 2, 48000, np.full(n, -0.0))))
+    # f64 values that are no f32: they round into the subnormal range (ties and near-ties of 2^-149 among them), or to +-0
+    to_sub = rng.choice([-1.0, 1.0], n) * np.exp(rng.uniform(np.log(F32_TINY / 2), np.log(F32_NORM_MIN), n))
+    to_sub[:8] = np.array([0.5, 1.5, 2.5, 0.5 + 2.0 ** -30, 0.5 - 2.0 ** -30, 1.5 - 2.0 ** -30, 2.0 ** 23 - 0.5, 2.0 ** 23 - 0.25]) * F32_TINY
+    out.append(("fe_f64_to_subnormal_1ch", wav("f64", 1, 44100, to_sub)))
+    out.append(("fe_f64_to_subnormal_2ch", wav("f64", 2, 8000, -to_sub)))
+    out.append(("fe_f64_to_zero_2ch", wav("f64", 2, 44100, rng.choice([-1.0, 1.0], n) * rng.uniform(1e-47, 6e-46, n))))
+    mixed = np.where(rng.random(n) < 0.5, sub, rng.uniform(-0.25, 0.25, n).astype(np.float32))
+    out.append(("fe_f32_mixed_1ch", wav("f32", 1, 31250, mixed)))
+    out.append(("fe_f64_mixed_2ch", wav("f64", 2, 31250, np.where(rng.random(n) < 0.5, to_sub, rng.uniform(-0.25, 0.25, n)))))
+    # f64 values a hair either side of the midpoint of two neighbouring f32 values, and on it (ties to even)
+    g = rng.uniform(-0.5, 0.5, n).astype(np.float32)
+    up = np.nextafter(g, np.float32(1)).astype(np.float64)
+    mid = (g.astype(np.float64) + up) / 2
+    ties = mid + rng.choice([-1.0, 0.0, 1.0], n) * np.abs(mid) * 2.0 ** -50
+    out.append(("fe_f64_near_ties_1ch", wav("f64", 1, 22050, ties)))
+    out.append(("fe_f64_near_ties_2ch", wav("f64", 2, 44100, ties[::-1].copy())))
+    # at and around +-1: single samples in a quiet tone, then whole files
+    out.append(("fe_f32_at_one_1ch", wav("f32", 1, 31250, _isolated(n, 21, [1.0, -1.0, ONE_DOWN, -ONE_DOWN]))))
+    out.append(("fe_f64_rounds_to_one_1ch", wav("f64", 1, 44100, _isolated(n, 22, [1.0 + 2.0 ** -25, -1.0 - 2.0 ** -25, 1.0 - 2.0 ** -26]))))
+    out.append(("fe_f32_above_one_1ch", wav("f32", 1, 31250, _isolated(n, 23, [ONE_UP, -ONE_UP]))))
+    out.append(("fe_f32_dc_one_1ch", wav("f32", 1, 31250, np.full(n, 1.0))))
+    out.append(("fe_f32_dc_above_one_1ch", wav("f32", 1, 31250, np.full(n, ONE_UP))))
+    out.append(("fe_f64_dc_above_one_2ch", wav("f64", 2, 31250, np.full(n, -(1.0 + 2.0 ** -23)))))
+    # f64 values that round to exactly FLT_MAX, and ones that overflow f32
+    half_ulp = 2.0 ** 103
+    out.append(("fe_f64_to_fltmax_1ch", wav("f64", 1, 44100, _isolated(n, 24, [F32_MAX + 0.99 * half_ulp, -F32_MAX - 0.5 * half_ulp,
+                                                                                 F32_MAX - 0.99 * half_ulp]))))
+    out.append(("fe_f64_overflow_1ch", wav("f64", 1, 44100, _isolated(n, 25, [F32_MAX + half_ulp, -1e300, 3.5e38]))))
+    # not finite: a NaN, infinities, and finite pairs whose sum is not
+    out.append(("fe_f32_nan_1ch", wav("f32", 1, 44100, _isolated(n, 26, [np.nan]))))
+    out.append(("fe_f32_inf_2ch", wav("f32", 2, 44100, _isolated(n, 27, [np.inf, -np.inf]))))
+    out.append(("fe_f64_inf_1ch", wav("f64", 1, 48000, _isolated(n, 28, [-np.inf]))))
+    pair = _quiet(n, 29)
+    pair[200:202] = F32_MAX
+    pair[300:302] = [-F32_MAX, -3e38]
+    out.append(("fe_f32_pair_overflow_2ch", wav("f32", 2, 44100, pair)))
+    out.append(("fe_f32_fltmax_1ch", wav("f32", 1, 44100, _isolated(n, 30, [F32_MAX, -F32_MAX]))))
+    # EXTENSIBLE float (rule 10: the library reads float where libnyquist reads integers)
+    out.append(("fe_ext_f32_subnormal_2ch", wav("f32", 2, 44100, sub, extensible=3)))
+    out.append(("fe_ext_f64_to_subnormal_1ch", wav("f64", 1, 22050, to_sub, extensible=3)))
+    out.append(("fe_ext_f32_inf_1ch", wav("f32", 1, 44100, _isolated(n, 31, [np.inf]), extensible=3)))
+    return out
+
+
 def ima_wrap_wav():
     """one ADPCM block whose predictor overflows int16 at once: 32700 + 61 436 wraps to 28 600 (a clamp gives 32 767)"""
     data = struct.pack("<hBB", 32700, 88, 0) + bytes([0x77] * 4) * 63

@@ -161,7 +161,8 @@ def values(b, d):
         return np.frombuffer(raw, "<i4").astype(np.float32) / np.float32(2147483648.0)
     if fmt == F32:
         return np.frombuffer(raw, "<f4").copy()
-    return np.frombuffer(raw, "<f8").astype(np.float32)
+    with np.errstate(over="ignore"):        # past FLT_MAX the C cast gives +-inf
+        return np.frombuffer(raw, "<f8").astype(np.float32)
 
 
 def downmix(v, channels):
@@ -170,7 +171,8 @@ def downmix(v, channels):
     if channels != 2:
         return v
     m = len(v) // 2
-    out = (v[0:2 * m:2] + v[1:2 * m:2]) / np.float32(2.0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        out = (v[0:2 * m:2] + v[1:2 * m:2]) / np.float32(2.0)
     return np.concatenate([out, v[2 * m:]]).astype(np.float32)
 
 
