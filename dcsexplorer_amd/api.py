@@ -174,7 +174,7 @@ EXPORTS = [
     "dcs_seq_tick", "dcs_seq_fatal_tick", "dcs_seq_stream_playing",
     "dcs_decode_batch_live", "dcs_seq_decode_view", "dcs_seq_plan_ahead", "dcs_seq_stream_playing_at", "dcs_seq_tracks_active_at", "dcs_ctx_call_floor",
     "dcs_host_threads", "dcs_partition_streams", "dcs_decode_streams_sharded",
-    "dcs_ctx_set_frames_per_chunk", "dcs_index_stream_literal", "dcs_pack_chunks_device", "dcs_batch_abi_bytes", "dcs_batch_num_chunks", "dcs_batch_frames_per_wave", "dcs_ctx_clock_mhz", "dcs_ctx_link_rate", "dcs_ctx_set_test_hooks",
+    "dcs_ctx_set_frames_per_chunk", "dcs_index_stream_literal", "dcs_pack_chunks_device", "dcs_batch_abi_bytes", "dcs_batch_num_chunks", "dcs_batch_frames_per_wave", "dcs_ctx_set_chunks_per_wave", "dcs_batch_chunks_per_wave", "dcs_ctx_clock_mhz", "dcs_ctx_link_rate", "dcs_ctx_set_test_hooks",
     "dcs_pipeline_create", "dcs_pipeline_destroy", "dcs_pipeline_submit", "dcs_pipeline_collect",
     "dcs_device_path_create", "dcs_device_path_run", "dcs_device_path_run_many", "dcs_device_path_download", "dcs_device_path_destroy",
     "dcs_node_create", "dcs_node_destroy", "dcs_node_submit", "dcs_node_collect", "dcs_node_num_devices", "dcs_node_device_info",
@@ -247,6 +247,9 @@ def load_library():
     L.dcs_device_count.restype = ctypes.c_int
     L.dcs_ctx_set_frames_per_wave.restype = i32
     L.dcs_ctx_set_frames_per_wave.argtypes = [vp, ctypes.c_int]
+    if hasattr(L, "dcs_ctx_set_chunks_per_wave"):       # (DCS_HIP_LIB may name a build from before there was the setting: A/B against it)
+        L.dcs_ctx_set_chunks_per_wave.restype = i32
+        L.dcs_ctx_set_chunks_per_wave.argtypes = [vp, ctypes.c_int]
     L.dcs_ctx_set_tail_handoff.restype = i32
     L.dcs_ctx_set_tail_handoff.argtypes = [vp, ctypes.c_int]
     L.dcs_ctx_set_large_list_path.restype = i32
@@ -410,6 +413,9 @@ def load_library():
     L.dcs_runtime_defaults.argtypes = []
     L.dcs_batch_frames_per_wave.restype = ctypes.c_int
     L.dcs_batch_frames_per_wave.argtypes = [vp]
+    if hasattr(L, "dcs_batch_chunks_per_wave"):
+        L.dcs_batch_chunks_per_wave.restype = ctypes.c_int
+        L.dcs_batch_chunks_per_wave.argtypes = [vp]
     L.dcs_ctx_clock_mhz.restype = i32
     L.dcs_ctx_clock_mhz.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dcs_ctx_link_rate.restype = i32
@@ -1078,6 +1084,11 @@ class Context:
     def set_frames_per_wave(self, fpw):
         _check(self.L.dcs_ctx_set_frames_per_wave(self.h, fpw), self.h)
 
+    def set_chunks_per_wave(self, chunks):
+        """Chunks a wavefront of a decode launch takes, one after the other: 1, 2, or 0 for the library's rule (2 for batches
+        of 8 frames per wavefront that make more than one and at most two generations of the chip).  Read at every launch."""
+        _check(self.L.dcs_ctx_set_chunks_per_wave(self.h, chunks), self.h)
+
     def set_frames_per_chunk(self, frames):
         _check(self.L.dcs_ctx_set_frames_per_chunk(self.h, frames), self.h)
 
@@ -1495,6 +1506,11 @@ class Batch:
     @property
     def frames_per_wave(self):
         return int(self.L.dcs_batch_frames_per_wave(self.h))
+
+    @property
+    def chunks_per_wave(self):
+        """chunks per wavefront of the batch's next launch (1 or 2; Decoder.set_chunks_per_wave)"""
+        return int(self.L.dcs_batch_chunks_per_wave(self.h))
 
     def close(self):
         if self.h:

@@ -29,6 +29,7 @@ struct DcsCtx
     hipStream_t stream = nullptr;
     DcsDevTables *dTables = nullptr;
     int fpwOverride = 0;
+    int cpwOverride = 0;                // chunks per wavefront of a decode launch: 0 = by the launch's size (twoChunksPerWave), 1, 2
     bool handoff = true;                // tails cross chunk boundaries through the hand-off buffer (else: halo re-decode)
     uint32_t shuffleSeed = 0;           // test hook: host-planned batches get their chunks in a seeded random order (dcs_ctx_set_test_hooks)
     bool noXcdRanges = false;           // test hook: no batch of this context is launched in XCD ranges
@@ -343,6 +344,7 @@ struct DcsBatch
     bool settled = false;       // a wait has covered everything enqueued for this batch and nothing was enqueued since
     uint32_t planFpc = 0;       // frames per chunk of a plan made on the device (dcsPlanKernel)
     bool errJoined = false;     // dErr lies behind the PCM in dPcm (and hErr in hPcm): the two come down in one copy
+    bool solo = true;           // its launches have the chip to themselves (not a pipeline's batch, not one of a context of concurrent batches)
 };
 
 // the device work of the batch's last launch has finished (host-side wait)
@@ -569,6 +571,14 @@ extern "C" DcsStatus dcs_ctx_set_frames_per_wave(DcsCtx *ctx, int fpw)
     if (ctx == nullptr || !(fpw == 0 || fpw == 4 || fpw == 8 || fpw == 16))
         return DCS_ERR_INVALID_ARG;
     ctx->fpwOverride = fpw;
+    return DCS_OK;
+}
+
+extern "C" DcsStatus dcs_ctx_set_chunks_per_wave(DcsCtx *ctx, int chunks)
+{
+    if (ctx == nullptr || chunks < 0 || chunks > 2)
+        return DCS_ERR_INVALID_ARG;
+    ctx->cpwOverride = chunks;
     return DCS_OK;
 }
 
@@ -802,6 +812,7 @@ static DcsBatch *newBatch(DcsCtx *ctx, const BatchOptions &o, uint32_t nJobs, ui
     b->nSrcs = nSrcs;
     b->fpw = chooseFpw(ctx, nJobs, all94);
     b->flags = (has93aT1 ? DCS_BATCH_HAS_93A_T1 : 0u) | (ranges && o.handoff ? DCS_BATCH_XCD_RANGES : 0u);
+    b->solo = !(o.xcdRanges || ctx->xcdRanges);
     return b;
 }
 
@@ -1526,18 +1537,42 @@ extern "C" DcsStatus dcs_batch_create(DcsCtx *ctx,
     return createBatch(ctx, o, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, out);
 }
 
-template <int FPW>
-static hipError_t launch(const DcsKernelArgs &args, hipStream_t stream, int numCUs)
+// Two chunks per wavefront (dcsDecodeKernel<8, 2>) where the chunks make more than one and at most two generations of the chip's
+// CUs x 16 wavefront places: one generation of wavefronts then decodes them with every SIMD given the same share, where two
+// generations of one-chunk wavefronts leave the compute units with 7, 8 or 9 workgroups each (NOTES 36, 49).  Only for a launch
+// that has the chip to itself: a pipeline's batches and those of a context of concurrent batches keep the dynamic deal, which
+// fills whatever places the neighbours leave.  `mode`: dcs_ctx_set_chunks_per_wave (1 and 2 force the variant at any size).
+static bool twoChunksPerWave(int fpw, int mode, bool solo, uint32_t nChunks, uint32_t flags, uint32_t cus)
 {
-    uint32_t blocks = (args.nChunks + dcsk::kWavesPerBlock - 1) / dcsk::kWavesPerBlock;
+    if (fpw != 8 || mode == 1)
+        return false;                   // (the two-chunk kernel exists for 8 frames per wavefront)
+    if (mode == 2)
+        return true;
+    return solo && !(flags & DCS_BATCH_XCD_RANGES) && nChunks > cus * 16u && nChunks <= cus * 32u;
+}
+
+template <int FPW>
+static hipError_t launch(const DcsKernelArgs &args, hipStream_t stream, int numCUs, int cpwMode, bool solo)
+{
+    const bool two = twoChunksPerWave(FPW, cpwMode, solo, args.nChunks, args.flags, static_cast<uint32_t>(numCUs));
+    const uint32_t waves = two ? (args.nChunks + 1u) / 2u : args.nChunks;
+    uint32_t blocks = (waves + dcsk::kWavesPerBlock - 1) / dcsk::kWavesPerBlock;
     if (args.flags & DCS_BATCH_XCD_RANGES)
         blocks = (blocks + 7u) / 8u * 8u;           // eight ranges of equal length; the padding workgroups find no chunk and leave
     // (priorities, dcs_kernels.hip.h: four wavefronts of this kernel per SIMD, CUs x 16 resident at once; with no more than CUs x 4
     // chunks every wavefront has a SIMD to itself and there is nothing to arrange)
     const uint32_t cus = static_cast<uint32_t>(numCUs);
     uint32_t flags = args.flags;
-    if (args.nChunks > cus * 4u && cus % 8u == 0 && cus / 8u < 256u)
+    if (waves > cus * 4u && cus % 8u == 0 && cus / 8u < 256u)
         flags |= DCS_BATCH_PACED | ((cus / 8u) << DCS_BATCH_CUS8_SHIFT);
+    if constexpr (FPW == 8)
+        if (two)
+        {
+            dcsk::dcsDecodeKernel<FPW, 2><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
+                args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
+                args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
+            return hipGetLastError();
+        }
     dcsk::dcsDecodeKernel<FPW><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
         args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
         args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
@@ -1552,7 +1587,7 @@ static DcsStatus launchOnce(DcsBatch *b, hipStream_t stream)
     if (++b->epoch > DCS_EPOCH_MAX)
         b->epoch = 1;                   // (0 marks words no launch has written; after 2^31 launches of ONE batch the count starts over)
     const DcsKernelArgs args = kernelArgs(b);
-    const hipError_t e = withFpw(b->fpw, [&](auto w) { return launch<decltype(w)::value>(args, stream, ctx->numCUs); });
+    const hipError_t e = withFpw(b->fpw, [&](auto w) { return launch<decltype(w)::value>(args, stream, ctx->numCUs, ctx->cpwOverride, b->solo); });
     if (e != hipSuccess)
     {
         setError(ctx, std::string("kernel launch failed: ") + hipGetErrorString(e));
@@ -1750,6 +1785,13 @@ extern "C" uint64_t dcs_batch_algorithmic_bytes(const DcsBatch *b) { return b ? 
 extern "C" uint64_t dcs_batch_abi_bytes(const DcsBatch *b) { return b ? b->abiBytes : 0; }
 extern "C" uint32_t dcs_batch_num_chunks(const DcsBatch *b) { return b ? b->nChunks : 0; }
 extern "C" int dcs_batch_frames_per_wave(const DcsBatch *b) { return b ? b->fpw : 0; }
+extern "C" int dcs_batch_chunks_per_wave(const DcsBatch *b)
+{
+    if (b == nullptr)
+        return 0;
+    const uint32_t cus = static_cast<uint32_t>(b->ctx->numCUs);
+    return twoChunksPerWave(b->fpw, b->ctx->cpwOverride, b->solo, b->nChunks, b->flags, cus) ? 2 : 1;
+}
 extern "C" uint32_t dcs_batch_num_jobs(const DcsBatch *b) { return b ? b->nJobs : 0; }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1966,7 +2008,7 @@ static DcsStatus decodeLive(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, ui
         args.handoff = l->dHandoff;
         args.epoch = l->epoch;
         args.flags = batchFlags | (layout << DCS_BATCH_IMG_SHIFT);
-        const hipError_t e = withFpw(fpw, [&](auto w) { return launch<decltype(w)::value>(args, ctx->stream, ctx->numCUs); });
+        const hipError_t e = withFpw(fpw, [&](auto w) { return launch<decltype(w)::value>(args, ctx->stream, ctx->numCUs, ctx->cpwOverride, !ctx->xcdRanges); });
         if (e != hipSuccess)
         {
             setError(ctx, std::string("kernel launch failed: ") + hipGetErrorString(e));

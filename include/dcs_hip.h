@@ -229,6 +229,12 @@ int       dcs_runtime_defaults(void);
 
 /* tuning: frames handled per wavefront in the kernel (4, 8 or 16); 0 = choose from batch size */
 DcsStatus dcs_ctx_set_frames_per_wave(DcsCtx *ctx, int fpw);
+/* tuning: chunks decoded per wavefront, one after the other (1 or 2); 0 (default) = 2 where the chunks of a batch of 8 frames
+ * per wavefront make more than one and at most two generations of the chip's wavefront places (CUs x 16 < chunks <= CUs x 32)
+ * and the batch has the chip to itself (not a pipeline's batch, not one of dcs_ctx_set_concurrent_batches), else 1.  Forced to
+ * 2 it holds for every batch of 8 frames per wavefront, whatever its size; batches of 4 and 16 always run 1.  Read at every
+ * launch; same PCM and error words at every setting. */
+DcsStatus dcs_ctx_set_chunks_per_wave(DcsCtx *ctx, int chunks);
 /* diagnostic: frames a wavefront decodes, when fewer than the kernel variant has slots for (the lanes of the unused
  * slots idle): 1 = one wavefront per frame.  0 (default) = every slot is used.  Same PCM at every setting. */
 DcsStatus dcs_ctx_set_frames_per_chunk(DcsCtx *ctx, int frames);
@@ -348,6 +354,7 @@ uint64_t  dcs_batch_abi_bytes(const DcsBatch *batch);
 uint32_t  dcs_batch_num_jobs(const DcsBatch *batch);
 uint32_t  dcs_batch_num_chunks(const DcsBatch *batch);          /* wavefronts of one launch */
 int       dcs_batch_frames_per_wave(const DcsBatch *batch);     /* the kernel variant chosen for it */
+int       dcs_batch_chunks_per_wave(const DcsBatch *batch);     /* ... and what its next launch decodes per wavefront (1 or 2) */
 /* shader clock (MHz) the chip holds under an integer VALU load on every SIMD (a probe kernel of a few hundred
  * microseconds; not part of the decode path): turns a kernel duration into cycles */
 DcsStatus dcs_ctx_clock_mhz(DcsCtx *ctx, float *mhzOut);
