@@ -89,7 +89,14 @@ struct DcsDevTables
     // next DCS_IDX_MULTI_BITS bits, the codes that lie entirely inside them, as long as they stand for at most
     // DCS_IDX_MULTI_SAMPLES samples together (at least one code): total length | samples << 4
     uint8_t  multi94[6][1 << 10];
+    // The band plan of the decode kernel (planBand94, dcs_kernels.hip.h; 8 frames per wavefront, which stage it into LDS): what a
+    // band's record takes from its band-type code alone, [strided][key of lds.band94] -> two dwords,
+    //   [0] codebook's offset in the lds block in bytes (bits 0..15) | scale adjustment (16..22) | bytes of tile row per sample
+    //       of the band, halved count: 2, 4 for a coded strided band, 0 for a code that is none (24..26)
+    //   [1] the record's second dword but for its last byte
+    uint32_t plan94[2][72][2];
 };
+#define DCS_PLAN94_BYTES 1152
 #define DCS_IDX_MULTI_BITS 10
 #define DCS_IDX_MULTI_SAMPLES 4
 

@@ -13,6 +13,10 @@
     uint32_t exportNext;                                // where the chunk's tail for another chunk is due (a scalar: see below)
     uint4 pd0, pd1, phdr;
     uint2 pd2;
+    // (8 frames per wavefront: this lane plans bands q and q + 8 of its slot's frame, see below.  Their header and band-type bytes
+    // are read as bytes where the head lies in LDS anyway -- picking them out of the eight registers by a band number that is
+    // the lane's costs a dozen selects)
+    uint32_t planHdr0 = 0, planHdr1 = 0, planType0 = 0, planType1 = 0;
     {
         uint4 *scratch = reinterpret_cast<uint4 *>(L.pool());
         static_assert(kHeadVec * 16 <= poolDwords(FPW) * 4, "the package head fits in the bit pool");
@@ -27,6 +31,13 @@
         const uint4 d2v = sp5[3];
         pd2 = make_uint2(d2v.x, d2v.y);
         phdr = sp5[4];
+        if constexpr (bandPlanInLds(FPW))
+        {
+            // (DcsFrameIndex.bandType: bytes 4..19 of a slot's third and fourth pieces; the stream header: its fifth piece)
+            const unsigned char *bytes = reinterpret_cast<const unsigned char *>(sp5) + q;
+            planType0 = bytes[36]; planType1 = bytes[44];
+            planHdr0 = bytes[64]; planHdr1 = bytes[72];
+        }
         waveSync();
         slot.job = s0.x;
         slot.prevSlot = s0.y & 0xFFu; slot.flags = (s0.y >> 8) & 0xFFu; slot.nSrc = (s0.y >> 16) & 0xFFu; slot.shiftXform = s0.y >> 24;
@@ -37,6 +48,24 @@
         // last one, so this is the same for every lane: taken into a scalar register here, no vector register lives through phase 1)
         const unsigned long long exportSlots = __ballot(lane < FPW && !(slot.flags & DCS_SLOT_EMPTY) && (slot.flags & DCS_SLOT_EXPORT) != 0);
         exportNext = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(d2v.w), exportSlots != 0 ? static_cast<int>(__builtin_ctzll(exportSlots)) : 0));
+    }
+
+    // ---- the band plan of the first-source round (planBand94, unpack94): two records per lane, lane (s, q)'s at lane and
+    // lane + 64 of the [16][FPW] array.  Skipped where no frame of the chunk starts with a 1994+ source (a uniform branch).
+    if constexpr (bandPlanInLds(FPW))
+    {
+        const int fmt0 = static_cast<int>((pd0.z >> 16) & 0xFFu);
+        if (__any(!(slot.flags & DCS_SLOT_EMPTY) && slot.nSrc != 0 && fmt0 >= DCS_FMT_94_T0))
+        {
+            uint2 *plan = reinterpret_cast<uint2 *>(L.plan());
+            const uint2 *tmpl = reinterpret_cast<const uint2 *>(smem + planTableOffset(FPW));
+            const bool type1 = fmt0 != DCS_FMT_94_T0;
+            const uint32_t keyLim = type1 ? 16u : 17u;
+            const uint32_t cls0 = !type1 ? DCS_B94_TYPE0 : q < 3 ? 0u : q < 6 ? 17u : 34u, cls1 = type1 ? 34u : DCS_B94_TYPE0;
+            const uint32_t pre = (type1 && q < 3) ? (pd2.y >> (4 * q)) & 15u : 0u;
+            plan[lane] = planBand94(L.tables(), tmpl, planHdr0, planType0, cls0, keyLim, q < 2 ? 7u + q : 16u, pre);
+            plan[lane + 64] = planBand94(L.tables(), tmpl, planHdr1, planType1, cls1, keyLim, q == 7 ? 32u : 16u, 0u);
+        }
     }
 
     // the lane's transform constants for the chunk's first frame (the whole chunk, normally): requested now, needed in
@@ -294,7 +323,11 @@
             {
                 BR94 br;
                 br.init(brAt, brBit);
-                err |= unpack94<R0, BR94, SUB>(T, row, br, Q, format, mixMul, is94, stamp);
+                // (first source, 8 lanes per frame: the bands' set-up comes from the plan; the record of this lane's first band)
+                const uint32_t planAt = (R0 && bandPlanInLds(FPW))
+                    ? static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsBytePtr)L.plan())) + static_cast<uint32_t>(Q.bandBase * FPW + s) * kPlanRecBytes
+                    : 0u;
+                err |= unpack94<R0, BR94, SUB>(T, row, br, Q, format, mixMul, is94, stamp, planAt);
             }
             BR93 br;
             br.init(brAt, brBit);

@@ -78,16 +78,29 @@ constexpr int kRowBytes = DCS_ROW_BYTES; // 256 words + 16 bytes: 16-byte aligne
 __host__ __device__ constexpr int poolDwords(int fpw) { return static_cast<int>(dcsPoolCapacity(fpw)); }
 __host__ __device__ constexpr int subLanes(int fpw) { return 64 / fpw; }     // 16, 8 and 4 lanes per frame for fpw 4, 8, 16
 
-// per wavefront: tile rows | tails [fpw + 1][16] i16 (the last row is a sink for lane groups without a frame) | bit pool
-__host__ __device__ constexpr int waveLdsBytes(int fpw) { return fpw * kRowBytes + (fpw + 1) * 32 + poolDwords(fpw) * 4; }
+// The band plan of unpack94 (8 frames per wavefront only): one 8-byte record per (band, slot), [16][fpw], see planBand94.
+// (4 frames per wavefront: band 15's halves depend on the lane; 16: no LDS to spare, dcs_common.h)
+constexpr int kPlanRecBytes = 8;
+__host__ __device__ constexpr bool bandPlanInLds(int fpw) { return fpw == 8; }
+__host__ __device__ constexpr int planBytes(int fpw) { return bandPlanInLds(fpw) ? 16 * fpw * kPlanRecBytes : 0; }
+// per wavefront: tile rows | tails [fpw + 1][16] i16 (the last row is a sink for lane groups without a frame) | band plan | bit pool
+__host__ __device__ constexpr int waveTileBytes(int fpw) { return fpw * kRowBytes + (fpw + 1) * 32 + planBytes(fpw); }
+__host__ __device__ constexpr int waveLdsBytes(int fpw) { return waveTileBytes(fpw) + poolDwords(fpw) * 4; }
 // workgroup layout: tables | the four wavefronts' bit pools | the four wavefronts' (tile rows, tails).  The pools
 // come first on purpose, see BitReader.
 // ... | OS93a Type-1 pair table (4 KB; only where it fits next to three more workgroups: 4 and 8 frames per wavefront)
 __host__ __device__ constexpr bool pairTableInLds(int fpw) { return fpw <= 8; }
 __host__ __device__ constexpr int ldsBytes(int fpw)
 {
-    return DCS_LDS_DECODE_BYTES + kWavesPerBlock * waveLdsBytes(fpw) + (pairTableInLds(fpw) ? 4096 : 0);
+    return DCS_LDS_DECODE_BYTES + kWavesPerBlock * waveLdsBytes(fpw) + (bandPlanInLds(fpw) ? DCS_PLAN94_BYTES : 0) + (pairTableInLds(fpw) ? 4096 : 0);
 }
+// ... | the band plan's table (DcsDevTables::plan94; with a band plan only) | the pair table, from the end
+__host__ __device__ constexpr int planTableOffset(int fpw) { return ldsBytes(fpw) - (pairTableInLds(fpw) ? 4096 : 0) - DCS_PLAN94_BYTES; }
+// (gfx950: 160 KB of LDS per compute unit, handed out in pieces of 1 280 bytes)  Four workgroups share a compute unit --
+// one wavefront per SIMD each, the launch bounds' four wavefronts per SIMD -- with 4 and 8 frames per wavefront, three with 16.
+__host__ __device__ constexpr int ldsAllocBytes(int fpw) { return (ldsBytes(fpw) + 1279) / 1280 * 1280; }
+static_assert(4 * ldsAllocBytes(4) <= 163840 && 4 * ldsAllocBytes(8) <= 163840 && 3 * ldsAllocBytes(16) <= 163840,
+              "workgroups per compute unit: the band plan must not cost one");
 
 // ------------------------------------------------------------------------------------------------
 // L0 arithmetic
@@ -200,6 +213,10 @@ struct BitReader
     {
         init((const uint32_t *)reinterpret_cast<LdsDwordPtr>(static_cast<uintptr_t>((bits >> 5) << 2)), static_cast<int>(bits & 31u));
     }
+    // the same position as one instruction's worth of mark (pa is a multiple of 4, negpos below 32: the two do not overlap), for
+    // where it is taken at every band and looked at only in the error path
+    __device__ __forceinline__ uint32_t mark() const { return (pa << 3) | static_cast<uint32_t>(negpos); }
+    __device__ __forceinline__ void initAtMark(uint32_t m) { initAt((m & ~31u) - 32u - (m & 31u)); }
 };
 
 // The same reader without a window held in registers: only the position is kept, every look reads the two pool
@@ -233,6 +250,8 @@ struct DirectReader
     __device__ __forceinline__ uint32_t get(int n) { const uint32_t v = peek(n); skip(n); return v; }
     __device__ __forceinline__ uint32_t bitAddr() const { return bp + 1u; }
     __device__ __forceinline__ void initAt(uint32_t bits) { bp = bits - 1u; }
+    __device__ __forceinline__ uint32_t mark() const { return bitAddr(); }
+    __device__ __forceinline__ void initAtMark(uint32_t m) { initAt(m); }
 };
 
 // prefix code via first-level table + trie (dcs_common.h)
@@ -274,6 +293,7 @@ struct Lds
     __device__ __forceinline__ uint16_t *row(int s) const { return reinterpret_cast<uint16_t *>(base + s * kRowBytes); }
     __device__ __forceinline__ uint16_t *tails() const { return reinterpret_cast<uint16_t *>(base + FPW * kRowBytes); }      // [FPW][16]
     __device__ __forceinline__ uint32_t *pool() const { return reinterpret_cast<uint32_t *>(poolBase); }
+    __device__ __forceinline__ unsigned char *plan() const { return base + FPW * kRowBytes + (FPW + 1) * 32; }              // [16][FPW] records
 };
 
 // what one sub-lane knows about the frame quarter it unpacks
@@ -406,6 +426,41 @@ __device__ __forceinline__ void dcFixup(uint16_t *row, uint32_t saved1)
 constexpr int kDummyWord = 256;         // the pad word of a tile row: sink for predicated-off stores
 
 // ------------------------------------------------------------------------------------------------
+// The band plan (first source of a frame, 8 frames per wavefront).  What unpack94 sets up when a lane starts a band is, but
+// for the cell and the bits where the band begins, a function of things fixed per (frame, band): the header byte, the
+// band-type code, the pre-adjust nibble, the format and the band number.  In the round loop that set-up runs for the whole
+// wavefront three times per chunk with 8 to 48 of the 64 lanes in it; here it runs ONCE per chunk with every lane busy --
+// 8 frames x 16 bands = two per lane, lane (s, q) takes bands q and q + 8 of the frame in slot s -- and leaves one record per
+// (band, slot), laid out for its reader (unpack94 takes the fields with byte and half-word reads and operand selects):
+//   +0 u16  codebook, as an LDS byte address          +2 u16  scale factor (pre-adjust and the code's own adjustment in)
+//   +4 u8   shift that turns the next 32 bits into the codebook index
+//   +5 u8   sample's offset in (window's high half | entry), bits 0..4 | log2 of the bytes per sample << 5 | fatal << 7
+//   +6 u8   sample's width, bits 0..4 | band without a code << 7     (the bit-field extract looks at bits 0..4 of both only)
+//   +7 u8   bytes of tile row the band covers: a band without a code moves on by them, a coded one decodes that many, 0 if fatal
+// Slots without a 1994+ first source get records nobody reads (every table index below is in range whatever the bytes).
+// ------------------------------------------------------------------------------------------------
+typedef uint8_t __attribute__((address_space(3))) *LdsBytePtr;
+// What a record takes from the band-type code alone comes ready-made out of a table (DcsDevTables::plan94, staged behind the
+// wavefronts' areas), by the code's key in lds.band94 and whether the band is strided; the header byte adds the scale factor and
+// the band number the count.  tmpl: the table in LDS; cls: 0, 17, 34 by the band's class (Type 1) or DCS_B94_TYPE0; keyLim: 16
+// resp. 17, the band-type codes beyond which all mean the same (no such code); count0: samples of the band (:1848-1850): 7, 8,
+// 16 ... 16, 32; pre: Type 1, bands 0..2: the pre-adjust from the previous frame's codes (:1914-1961), else 0.
+__device__ __forceinline__ uint2 planBand94(const DcsLdsTables *T, const uint2 *tmpl, uint32_t hdrByte, uint32_t typeByte,
+                                            uint32_t cls, uint32_t keyLim, uint32_t count0, uint32_t pre)
+{
+    const uint32_t strided = (hdrByte >> 6) & 1u;
+    const uint2 t = tmpl[min(typeByte, keyLim) + (strided * 72u + cls)];
+    // scale = header byte + pre-adjust + the code's own adjustment (the table looks at the low six bits)
+    const uint32_t scale = scaleFactor(T, static_cast<int>(hdrByte + pre + ((t.x >> 16) & 0x7Fu)));
+    const uint32_t book = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsWordPtr)reinterpret_cast<const uint16_t *>(T))) + (t.x & 0xFFFFu);
+    // (a strided band has half the samples; one without a code moves on by the halved count, not by count * inc, :1886; no
+    // band-type code stands for sample code 0 -- dcs_tables.cpp checks it --, so the STOP of :1985-1991 cannot happen: a band is
+    // empty, in error, or has its count of samples)
+    const uint32_t span = static_cast<uint32_t>(__mul24(static_cast<int>(count0 >> strided), static_cast<int>(t.x >> 24)));
+    return make_uint2(book | (scale << 16), t.y | (span << 24));
+}
+
+// ------------------------------------------------------------------------------------------------
 // a2: 1994+ frame (DecoderImpl94x::DecompressFrame, .cpp:1679-2261)
 //
 // Each lane unpacks Q.nb consecutive header bands.  The frame header (band-type deltas, :1780-1834)
@@ -416,8 +471,13 @@ constexpr int kDummyWord = 256;         // the pad word of a tile row: sink for 
 // ------------------------------------------------------------------------------------------------
 template <bool FIRST, class BR, int SUB>
 __device__ uint32_t unpack94(const DcsLdsTables *T, uint16_t *row, BR &br, const Quarter &Q,
-                             int format, uint32_t mixMul, bool has, const Stamper &stamp)
+                             int format, uint32_t mixMul, bool has, const Stamper &stamp, uint32_t planAt = 0)
 {
+    // The first source with eight lanes per frame: the bands' set-up was done before the rounds (planBands94), a lane that
+    // starts a band reads its record.  planAt: LDS byte address of the record of (this lane's first band, its slot); the
+    // records of a slot's bands are kPlanRecBytes * 8 apart.
+    constexpr bool kPlan = FIRST && SUB == 8;
+    constexpr uint32_t kPlanBandBytes = kPlanRecBytes * 8;
     const bool type1 = format != DCS_FMT_94_T0;
     uint32_t err = 0;
     int nb = has ? Q.nb : 0;
@@ -444,6 +504,7 @@ __device__ uint32_t unpack94(const DcsLdsTables *T, uint16_t *row, BR &br, const
     // lane has 31 or 32 samples and the wavefront is through after 7 + 9 + 16 iterations; one band per lane per round
     // (round 1's form) cost 16 + 32.
     int k = 0;                                  // bands this lane has started
+    uint32_t planEnd = planAt + kPlanBandBytes * static_cast<uint32_t>(nb);     // (with a plan: the record behind this lane's last band)
     const int keyLim = type1 ? 16 : 17;         // band-type codes beyond this all mean the same (no such code)
     // (cells as LDS byte addresses: 32-bit arithmetic in the loop)
     uint32_t cell = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsWordPtr)row)) + 2u * static_cast<uint32_t>(outIdx);   // where the next sample goes
@@ -467,7 +528,10 @@ __device__ uint32_t unpack94(const DcsLdsTables *T, uint16_t *row, BR &br, const
             if (valid)
             {
                 BR r2;
-                r2.initAt(startBits);
+                if (kPlan)
+                    r2.initAtMark(startBits);
+                else
+                    r2.initAt(startBits);
                 uint32_t c2 = cellStart;
                 while (c2 + (1u << incSh) < cellEnd)            // (more than one sample left)
                 {
@@ -484,10 +548,38 @@ __device__ uint32_t unpack94(const DcsLdsTables *T, uint16_t *row, BR &br, const
             cellEnd = cell;
         }
         // ---- per-band set-up for the lanes that are between bands ---------------------------------------------
-        const bool start = cell == cellEnd && k < nb;
+        const bool start = cell == cellEnd && (kPlan ? planAt < planEnd : k < nb);
         if (!__any(start || cell < cellEnd))
             break;
-        if (start)
+        if constexpr (kPlan)
+        {
+            if (start)
+            {
+                const LdsBytePtr rec = reinterpret_cast<LdsBytePtr>(static_cast<uintptr_t>(planAt));
+                planAt += kPlanBandBytes;
+                const uint32_t bookAt = *reinterpret_cast<LdsWordPtr>(rec);
+                const uint32_t recScale = *reinterpret_cast<LdsWordPtr>(rec + 2);
+                const uint32_t recOff = rec[5], recWidth = rec[6], span = rec[7];
+                shIdx = rec[4];
+                book = (const uint16_t *)reinterpret_cast<LdsWordPtr>(static_cast<uintptr_t>(bookAt));
+                // (the bit-field extract of the symbol loop looks at bits 0..4 of its offset and width: the flags ride along)
+                valOff = recOff;
+                valWidth = recWidth;
+                incSh = __builtin_amdgcn_ubfe(recOff, 5u, 2u);
+                if (recOff > 0x7Fu)
+                {
+                    err |= DCS_FRAME_FATAL | DCS_FRAME_STOP;
+                    planEnd = 0;                    // stop: later bands contribute nothing
+                }
+                scale = valid ? static_cast<int>(recScale) : 0;    // after a STOP the band is still parsed, its samples contribute nothing
+                // a band without a code moves on by its span and is over; a coded one has its span to decode
+                cellEnd = cell + span;
+                cell = recWidth > 0x7Fu ? cellEnd : cell;
+                cellStart = cell;
+                startBits = br.mark();
+            }
+        }
+        else if (start)
         {
             const int band = Q.bandBase + k;
             ++k;
@@ -1477,7 +1569,7 @@ dcsDecodeKernel(uint8_t *kPackages, const DcsDevTables *kTables, uint32_t kNChun
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int wave = static_cast<int>(threadIdx.x) >> 6;
     const int lane = static_cast<int>(threadIdx.x) & 63;
-    constexpr int kPoolBytes = poolDwords(FPW) * 4, kTileBytes = FPW * kRowBytes + (FPW + 1) * 32;
+    constexpr int kPoolBytes = poolDwords(FPW) * 4, kTileBytes = waveTileBytes(FPW);
     static_assert(kPoolBytes % 16 == 0 && kWavesPerBlock * kTileBytes >= 8192, "LDS layout");
     const Lds<FPW> L{ smem, smem + DCS_LDS_DECODE_BYTES + kWavesPerBlock * kPoolBytes + wave * kTileBytes,
                       smem + DCS_LDS_DECODE_BYTES + wave * kPoolBytes };
@@ -1565,13 +1657,23 @@ dcsDecodeKernel(uint8_t *kPackages, const DcsDevTables *kTables, uint32_t kNChun
         if (stagePairs)
             pairPiece = reinterpret_cast<const uint4 *>(a.tables->pair93a)[threadIdx.x];
         uint4 *tile = reinterpret_cast<uint4 *>(L.base);
+        // the band plan's table, likewise (requested here, stored behind the clearing)
+        if constexpr (bandPlanInLds(FPW))
+        {
+            constexpr int kPlanVec = DCS_PLAN94_BYTES / 16;
+            const uint4 planPiece = reinterpret_cast<const uint4 *>(a.tables->plan94)[min(static_cast<int>(threadIdx.x), kPlanVec - 1)];
+            for (int i = lane ; i < FPW * kRowBytes / 16 ; i += 64)
+                tile[i] = make_uint4(0, 0, 0, 0);
+            if (static_cast<int>(threadIdx.x) < kPlanVec)
+                reinterpret_cast<uint4 *>(smem + planTableOffset(FPW))[threadIdx.x] = planPiece;
+        }
 #ifndef DCS_CLEAR_FIRST_MAX_FPW
 #define DCS_CLEAR_FIRST_MAX_FPW 8
 #endif
         // (with 16 frames per wavefront, where the clearing is four times as long and other workgroups of the CU are busy
         // anyway, tables first measured 1 % better)
         constexpr bool kClearFirst = FPW <= DCS_CLEAR_FIRST_MAX_FPW;
-        if (kClearFirst)
+        if (kClearFirst && !bandPlanInLds(FPW))
             for (int i = lane ; i < FPW * kRowBytes / 16 ; i += 64)
                 tile[i] = make_uint4(0, 0, 0, 0);
         if (static_cast<int>(threadIdx.x) < kTableVec)

@@ -174,6 +174,20 @@ DcsDevTables build()
         t.lds.band94[k] = static_cast<uint32_t>(book) | ((shPeek & 31u) << 11) | ((shIdx & 31u) << 16) | (raw ? DCS_B94_RAW : 0u)
                         | (zero ? DCS_B94_ZERO : 0u) | (stop ? DCS_B94_STOP : 0u) | (fatal ? DCS_B94_FATAL : 0u) | (adj << 25);
     }
+    // plan94: the same entries taken apart for the band plan's records
+    for (uint32_t strided = 0 ; strided < 2 ; ++strided)
+        for (int k = 0 ; k < 72 ; ++k)
+        {
+            const uint32_t e = t.lds.band94[k];
+            const uint32_t shPeek = (e >> 11) & 31u, shIdx = (e >> 16) & 31u;
+            const bool raw = (e & DCS_B94_RAW) != 0, zero = (e & DCS_B94_ZERO) != 0, fatal = (e & DCS_B94_FATAL) != 0;
+            const uint32_t valOff = raw ? shPeek : 0u, valWidth = raw ? 32u - shPeek : 8u;
+            const uint32_t perSample = fatal ? 0u : zero ? 2u : 2u << strided;
+            if (valWidth > 16 || (zero && fatal))
+                abort();
+            t.plan94[strided][k][0] = 2u * (e & 0x7FFu) | ((e >> 25) << 16) | (perSample << 24);
+            t.plan94[strided][k][1] = shIdx | ((valOff | ((1u + strided) << 5) | (fatal ? 0x80u : 0u)) << 8) | ((valWidth | (zero ? 0x80u : 0u)) << 16);
+        }
     memcpy(t.lds.bandBits93a, kBandBits93a, sizeof(t.lds.bandBits93a));
     memcpy(t.lds.scaleCb93a, kScaleCb93a, sizeof(t.lds.scaleCb93a));
     for (int i = 0 ; i < 18 ; ++i)
@@ -245,4 +259,5 @@ static_assert(offsetof(DcsSrcDesc, idx) == 12, "DcsSrcDesc layout");
 static_assert(sizeof(DcsFrameJob) == 16, "DcsFrameJob layout");
 static_assert(sizeof(DcsFrameIndex) == 148 && offsetof(DcsFrameIndex, split) == 28, "DcsFrameIndex layout");
 static_assert(sizeof(DcsSlot) == 32, "DcsSlot layout");
+static_assert(offsetof(DcsDevTables, plan94) % 16 == 0 && sizeof(DcsDevTables::plan94) == DCS_PLAN94_BYTES, "the band plan's table is staged as uint4");
 static_assert(offsetof(DcsDevTables, pair93a) % 4 == 0, "OS93a sample pairs are read as 32-bit words");
