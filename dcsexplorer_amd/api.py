@@ -120,12 +120,25 @@ class WavInfo(ctypes.Structure):
                 ("reason", ctypes.c_char * 96)]
 
 
-WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32, WAV_F64, WAV_IMA = range(7)
-FILE_WAV, FILE_DCSA_COPY, FILE_DCSA_REENCODE = 0, 1, 2
+WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32, WAV_F64, WAV_IMA, WAV_S8 = range(8)
+FILE_WAV, FILE_DCSA_COPY, FILE_DCSA_REENCODE, FILE_FLAC = 0, 1, 2, 3
 FILE_WALK_NONE, FILE_WALK_DEVICE, FILE_WALK_HOST = 0, 1, 2
 ENCODE_FILE_INFO_DTYPE = np.dtype([("kind", "<i4"), ("sourceFormat", "<i4"), ("rate", "<u4"), ("channels", "<i4"),
                                    ("nValues", "<u8"), ("nSamples", "<u8"), ("walk", "<i4"), ("srcFrames", "<i4"),
                                    ("enc", ENCODE_INFO_DTYPE)], align=True)
+
+
+# dcs_flac_parse / dcs_flac_index: the reader's record of one FLAC file and of each of its frames
+class FlacInfo(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("rate", ctypes.c_uint32), ("channels", ctypes.c_int32), ("bitDepth", ctypes.c_int32),
+                ("sampleFormat", ctypes.c_int32), ("minBlockSize", ctypes.c_uint32), ("maxBlockSize", ctypes.c_uint32),
+                ("nFrames", ctypes.c_uint32), ("totalSamples", ctypes.c_uint64), ("nValues", ctypes.c_uint64),
+                ("firstFrameOffset", ctypes.c_uint64), ("reason", ctypes.c_char * 96)]
+
+
+FLAC_FRAME_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u4"), ("blockSize", "<u4"), ("firstSample", "<u8"),
+                             ("channelAssignment", "<i4"), ("bitsPerSample", "<i4"), ("blockingStrategy", "<i4"),
+                             ("headerLength", "<i4")], align=True)
 
 
 class SynthParams(ctypes.Structure):
@@ -184,6 +197,7 @@ EXPORTS = [
     "dcs_transcode_plan", "dcs_transcode_streams",
     "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
     "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
+    "dcs_flac_parse", "dcs_flac_index", "dcs_flac_decode",
     "dcs_encode_sweep", "dcs_encode_sweep_group_frames", "dcs_encode_fit",
 ]
 
@@ -495,6 +509,12 @@ def load_library():
     L.dcs_encode_files_plan.argtypes = [vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32, vp, vp, vp]
     L.dcs_wav_decode.restype = i32
     L.dcs_wav_decode.argtypes = [vp, vp, vp, u32, vp, sz, vp]
+    L.dcs_flac_parse.restype = i32
+    L.dcs_flac_parse.argtypes = [vp, sz, ctypes.POINTER(FlacInfo)]
+    L.dcs_flac_index.restype = i32
+    L.dcs_flac_index.argtypes = [vp, sz, vp, u32, vp]
+    L.dcs_flac_decode.restype = i32
+    L.dcs_flac_decode.argtypes = [vp, vp, vp, u32, vp, sz, vp]
     L.dcs_encode_files.restype = i32
     L.dcs_encode_files.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32, vp, sz,
                                    vp, vp]
@@ -869,6 +889,32 @@ def wav_parse(data):
     d = {k: getattr(w, k) for k, _ in WavInfo._fields_ if k != "reserved"}
     d["reason"] = w.reason.decode()
     return d
+
+
+def flac_parse(data):
+    """dcs_flac_parse (host only): one FLAC file's STREAMINFO and frame count as libFLAC reads them -> dict of the FlacInfo
+    fields (status 0 = accepted; otherwise the DcsStatus and `reason`)"""
+    b = bytes(data)
+    buf = np.frombuffer(b, dtype=np.uint8) if b else np.zeros(1, np.uint8)
+    w = FlacInfo()
+    load_library().dcs_flac_parse(_ptr(buf), len(b), ctypes.byref(w))
+    d = {k: getattr(w, k) for k, _ in FlacInfo._fields_}
+    d["reason"] = w.reason.decode()
+    return d
+
+
+def flac_index(data):
+    """dcs_flac_index (host only): -> (DcsStatus, FLAC_FRAME_DTYPE array of the file's frames; empty when refused)"""
+    b = bytes(data)
+    buf = np.frombuffer(b, dtype=np.uint8) if b else np.zeros(1, np.uint8)
+    n = np.zeros(1, np.uint32)
+    L = load_library()
+    st = L.dcs_flac_index(_ptr(buf), len(b), None, 0, _ptr(n))
+    if st != ERR_CAPACITY:
+        return st, np.zeros(0, FLAC_FRAME_DTYPE)
+    frames = np.zeros(int(n[0]), FLAC_FRAME_DTYPE)
+    st = L.dcs_flac_index(_ptr(buf), len(b), _ptr(frames), frames.size, _ptr(n))
+    return st, frames
 
 
 def encode_files_plan(files, version=0x9400, fmt=None, filter=None, at_unity=False, **params):
@@ -1282,9 +1328,20 @@ class Context:
         _check(self.L.dcs_wav_decode(self.h, _ptr(blob), _ptr(offs), n, _ptr(out), out.size, _ptr(out_offs)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)]
 
+    def flac_decode(self, files):
+        """dcs_flac_decode: FLAC files (bytes or paths) -> list of mono float32 arrays at each file's own rate, as libnyquist's
+        FlacDecoder converts libFLAC's samples and EncodeFile averages a stereo pair"""
+        blob, offs = _files_blob(files)
+        n = len(offs) - 1
+        out_offs = np.zeros(n + 1, np.uint64)
+        total = sum(flac_parse(blob[int(offs[i]):int(offs[i + 1])].tobytes())["totalSamples"] for i in range(n))
+        out = np.zeros(max(total, 1), np.float32)
+        _check(self.L.dcs_flac_decode(self.h, _ptr(blob), _ptr(offs), n, _ptr(out), out.size, _ptr(out_offs)), self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)]
+
     def encode_files(self, files, version=0x9400, fmt=None, filter=None, at_unity=False, **params):
         """dcs_encode_files: DCSEncoder::EncodeFile on each file (bytes or paths): a DCSa container is copied or re-encoded as
-        transcode_dcsa does it, a WAV file is read as libnyquist reads it, resampled and encoded (version, fmt, params as
+        transcode_dcsa does it, a WAV or native FLAC file is read as libnyquist reads it, resampled and encoded (version, fmt, params as
         encode_streams_at).  Returns (list of stream bytes, ENCODE_FILE_INFO_DTYPE array)."""
         p = transcode_params(version, fmt, **params)
         blob, offs = _files_blob(files)

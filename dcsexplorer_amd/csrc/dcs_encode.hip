@@ -2172,3 +2172,7 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
 // ---------------------------------------------------------------------- encoding files (dcs_wav.hip.h)
 
 #include "dcs_wav.hip.h"
+
+// ------------------------------------------------------------------- FLAC files for encoding files (dcs_flac.hip.h)
+
+#include "dcs_flac.hip.h"

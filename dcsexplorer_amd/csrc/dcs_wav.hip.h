@@ -238,24 +238,43 @@ __global__ __launch_bounds__(64) void wavImaKernel(const uint8_t *__restrict__ b
     }
 }
 
-// ConvertToFloat32 (Common.cpp) and the *_to_float32 macros (Common.h), bit for bit
+// the *_to_float32 macros (Common.h) on an integer already read, bit for bit; shared with F3 (dcs_flac.hip.h)
+template <int F>
+__device__ inline float wavScale(int32_t x)
+{
+    if constexpr (F == DCS_WAV_U8)
+        return (static_cast<float>(x) - 128) * (1.0f / 127.0f);
+    else if constexpr (F == DCS_WAV_S8)
+        return static_cast<float>(x) * (1.0f / 127.0f);
+    else if constexpr (F == DCS_WAV_S16 || F == DCS_WAV_IMA)
+        return static_cast<float>(x) / 32767.f;
+    else if constexpr (F == DCS_WAV_S24)
+        return static_cast<float>(x) / 8388608.f;
+    else
+        return static_cast<float>(x) / 2147483648.f;
+}
+
+// EncodeFile's downmix of a stereo pair (DCSEncodeFile.cpp)
+__device__ inline float wavMean(float l, float r) { return (l + r) / 2.0f; }
+
+// ConvertToFloat32 (Common.cpp), bit for bit
 template <int F>
 __device__ inline float wavValue(const uint8_t *__restrict__ p, const int16_t *__restrict__ ima, uint64_t k)
 {
     if constexpr (F == DCS_WAV_U8)
-        return (static_cast<float>(p[k]) - 128) * (1.0f / 127.0f);
+        return wavScale<F>(p[k]);
     else if constexpr (F == DCS_WAV_S16)
-        return static_cast<float>(reinterpret_cast<const int16_t *>(p)[k]) / 32767.f;
+        return wavScale<F>(reinterpret_cast<const int16_t *>(p)[k]);
     else if constexpr (F == DCS_WAV_IMA)
-        return static_cast<float>(ima[k]) / 32767.f;
+        return wavScale<F>(ima[k]);
     else if constexpr (F == DCS_WAV_S24)
     {
         const uint8_t *q = p + 3 * k;
         const int32_t x = (static_cast<int32_t>(static_cast<int8_t>(q[2])) << 16) | (q[1] << 8) | q[0];
-        return static_cast<float>(x) / 8388608.f;
+        return wavScale<F>(x);
     }
     else if constexpr (F == DCS_WAV_S32)
-        return static_cast<float>(reinterpret_cast<const int32_t *>(p)[k]) / 2147483648.f;
+        return wavScale<F>(reinterpret_cast<const int32_t *>(p)[k]);
     else if constexpr (F == DCS_WAV_F32)
         return reinterpret_cast<const float *>(p)[k];
     else
@@ -280,7 +299,7 @@ __global__ __launch_bounds__(256) void wavUnpackKernel(const uint8_t *__restrict
         {
             float x;
             if (stereo && 2 * j + 1 < w.nValues)
-                x = (wavValue<F>(p, q, 2 * j) + wavValue<F>(p, q, 2 * j + 1)) / 2.0f;
+                x = wavMean(wavValue<F>(p, q, 2 * j), wavValue<F>(p, q, 2 * j + 1));
             else
                 x = wavValue<F>(p, q, stereo ? 2 * j : j);
             if (!isfinite(x))
@@ -294,11 +313,28 @@ __global__ __launch_bounds__(256) void wavUnpackKernel(const uint8_t *__restrict
 
 // ----------------------------------------------------------------------------------------------------------- host side
 
-// The parsed WAV files of one call on the device: payloads up, W0, W1.  On DCS_OK *dMono holds file k's mono samples from
-// files[k].monoOff; bad[k] is set where a value or a pair's mean is not finite.  Buffers belong to `held`.
-DcsStatus wavStageOnDevice(DcsCtx *ctx, const uint8_t *const *bytes, const DcsWavInfo *infos, uint32_t n, std::vector<WavFile> &wf,
-                           CacheArena &held, float **dMonoOut, std::vector<uint32_t> &bad)
+// A FLAC file among the files of a call (dcs_flac.hip.h, included after this file): its record and frame index; both null
+// for a WAV file.  Its DcsWavInfo is flacAsWav's.
+struct FlacSource
 {
+    const DcsFlacInfo *info;
+    const std::vector<DcsFlacFrame> *frames;
+};
+DcsStatus flacStage(DcsCtx *ctx, CacheArena &held, hipStream_t st, const uint8_t *const *bytes, const FlacSource *flac, uint32_t n,
+                    const std::vector<WavFile> &wf, float *dMono, std::vector<uint32_t> &errOut);
+DcsStatus flacParse(const uint8_t *f, uint64_t len, DcsFlacInfo *w, std::vector<DcsFlacFrame> *frames);
+DcsWavInfo flacAsWav(const DcsFlacInfo &w);
+bool isFlacFile(const uint8_t *f, uint64_t len);
+std::string stageWhy(uint32_t bad);
+
+// The parsed WAV and FLAC files of one call on the device: payloads up, W0, W1; frames up, F1, F2, F3 (flac null: no FLAC
+// file).  On DCS_OK *dMono holds file k's mono samples from files[k].monoOff; bad[k] is set where a value or a pair's mean is
+// not finite, or (top bit) where a FLAC frame is refused on the device: stageWhy says which.  Buffers belong to `held`.
+DcsStatus wavStageOnDevice(DcsCtx *ctx, const uint8_t *const *bytes, const DcsWavInfo *infos, const FlacSource *flac, uint32_t n,
+                           std::vector<WavFile> &wf, CacheArena &held, float **dMonoOut, std::vector<uint32_t> &bad)
+{
+    const auto isFlac = [&](uint32_t k) { return flac != nullptr && flac[k].info != nullptr; };
+    bool anyFlac = false;
     wf.assign(n, WavFile{});
     uint64_t blobBytes = 0, nStaged = 0, nMono = 0, maxMono = 0, maxLanes = 0;
     std::vector<uint32_t> byFormat[DCS_WAV_IMA + 1];
@@ -307,7 +343,7 @@ DcsStatus wavStageOnDevice(DcsCtx *ctx, const uint8_t *const *bytes, const DcsWa
         const DcsWavInfo &w = infos[k];
         WavFile &f = wf[k];
         const bool ima = w.sampleFormat == DCS_WAV_IMA;
-        const uint64_t payload = ima ? w.nBlocks * static_cast<uint64_t>(w.blockAlign) : w.nValues * wavWidth(w.sampleFormat);
+        const uint64_t payload = isFlac(k) ? 0 : ima ? w.nBlocks * static_cast<uint64_t>(w.blockAlign) : w.nValues * wavWidth(w.sampleFormat);
         f.blobOff = blobBytes;
         f.payOff = ima ? nStaged : blobBytes;
         blobBytes += (payload + 255) & ~uint64_t(255);
@@ -323,7 +359,10 @@ DcsStatus wavStageOnDevice(DcsCtx *ctx, const uint8_t *const *bytes, const DcsWa
         maxMono = f.nMono > maxMono ? f.nMono : maxMono;
         if (ima)
             maxLanes = w.nBlocks * w.channels > maxLanes ? w.nBlocks * w.channels : maxLanes;
-        byFormat[w.sampleFormat].push_back(k);
+        if (isFlac(k))
+            anyFlac = true;
+        else
+            byFormat[w.sampleFormat].push_back(k);
     }
     const hipStream_t st = dcsCtxStream(ctx);
     uint8_t *dBlob;
@@ -343,7 +382,7 @@ DcsStatus wavStageOnDevice(DcsCtx *ctx, const uint8_t *const *bytes, const DcsWa
         const DcsWavInfo &w = infos[k];
         const uint64_t payload = w.sampleFormat == DCS_WAV_IMA ? w.nBlocks * static_cast<uint64_t>(w.blockAlign)
                                                                : w.nValues * wavWidth(w.sampleFormat);
-        if (payload != 0)
+        if (payload != 0 && !isFlac(k))
             ENCCHK(hipMemcpyAsync(dBlob + wf[k].blobOff, bytes[k] + w.dataOffset, payload, hipMemcpyHostToDevice, st));
     }
     std::vector<uint32_t> which;
@@ -355,7 +394,8 @@ DcsStatus wavStageOnDevice(DcsCtx *ctx, const uint8_t *const *bytes, const DcsWa
     }
     whichOff[DCS_WAV_IMA + 1] = which.size();
     ENCCHK(hipMemcpyAsync(dFiles, wf.data(), sizeof(WavFile) * n, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(dWhich, which.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
+    if (!which.empty())
+        ENCCHK(hipMemcpyAsync(dWhich, which.data(), sizeof(uint32_t) * which.size(), hipMemcpyHostToDevice, st));
     ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * n, st));
     const uint32_t nIma = static_cast<uint32_t>(byFormat[DCS_WAV_IMA].size());
     if (nIma != 0)
@@ -390,9 +430,15 @@ DcsStatus wavStageOnDevice(DcsCtx *ctx, const uint8_t *const *bytes, const DcsWa
         }
     }
     ENCCHK(hipGetLastError());
+    std::vector<uint32_t> flacErr;
+    if (anyFlac)
+        ENCTRY(flacStage(ctx, held, st, bytes, flac, n, wf, dMono, flacErr));
     bad.assign(n, 0);
     ENCCHK(hipMemcpyAsync(bad.data(), dBad, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
     ENCCHK(hipStreamSynchronize(st));
+    for (uint32_t k = 0 ; anyFlac && k < n ; ++k)
+        if (flacErr[k] != 0xFFFFFFFFu)
+            bad[k] = 0x80000000u | flacErr[k];
     *dMonoOut = dMono;
     return DCS_OK;
 }
@@ -424,12 +470,13 @@ void renameError(DcsCtx *ctx, const std::vector<uint32_t> *map)
 }
 
 // INTEGRATION rule 12: the largest |x| the encoder accepts from a file, the most negative value of its source format as
-// libnyquist converts it: -32768 / 32767 for 16-bit PCM and ADPCM, (0 - 128) / 127 for u8; 1 for the others
+// libnyquist converts it: -32768 / 32767 for 16-bit PCM, ADPCM and FLAC, (0 - 128) / 127 for u8 and -128 / 127 for FLAC's
+// signed 8 bits (rule 25); 1 for the others
 float wavBound(int32_t fmt)
 {
     if (fmt == DCS_WAV_S16 || fmt == DCS_WAV_IMA)
         return 32768.0f / 32767.0f;
-    if (fmt == DCS_WAV_U8)
+    if (fmt == DCS_WAV_U8 || fmt == DCS_WAV_S8)
         return 128.0f / 127.0f;
     return 1.0f;
 }
@@ -440,10 +487,14 @@ struct FilePlan
     int32_t kind = -1;
     DcsStatus status = DCS_OK;
     std::string why;
-    DcsWavInfo wav{};
+    DcsWavInfo wav{};               // (a FLAC file's is flacAsWav's)
+    DcsFlacInfo flac{};
+    std::vector<DcsFlacFrame> flacFrames;
     DcsStreamRef ref{};
     uint64_t bound = 0;
 };
+
+void flacParseMany(const uint8_t *files, const uint64_t *fileOffsets, const std::vector<uint32_t> &which, std::vector<FilePlan> &plan);
 
 // The length limit, checked before anything is allocated: fewer than 2^31 mono samples (what the resampler's walk indexes,
 // as rsCheck requires of the other entry points) and, for encoding (s given), a 31 250 Hz length the encoder's 65 535 frames
@@ -474,6 +525,13 @@ DcsStatus planFiles(const uint8_t *files, const uint64_t *fileOffsets, uint32_t 
 {
     plan.assign(nFiles, FilePlan{});
     const bool os93 = params->formatVersion != 0x9400;
+    std::vector<uint32_t> flacIdx;
+    for (uint32_t i = 0 ; i < nFiles ; ++i)
+        if (!isDcsaFile(files + fileOffsets[i], fileOffsets[i + 1] - fileOffsets[i]) && !isRiffFile(files + fileOffsets[i], fileOffsets[i + 1] - fileOffsets[i])
+            && isFlacFile(files + fileOffsets[i], fileOffsets[i + 1] - fileOffsets[i]))
+            flacIdx.push_back(i);
+    if (!flacIdx.empty())
+        flacParseMany(files, fileOffsets, flacIdx, plan);
     for (uint32_t i = 0 ; i < nFiles ; ++i)
     {
         FilePlan &p = plan[i];
@@ -503,17 +561,30 @@ DcsStatus planFiles(const uint8_t *files, const uint64_t *fileOffsets, uint32_t 
             p.kind = action == DCS_TRANSCODE_COPIED ? DCS_FILE_DCSA_COPY : DCS_FILE_DCSA_REENCODE;
             continue;
         }
-        if (!isRiffFile(b, len))
+        const bool flac = !isRiffFile(b, len) && isFlacFile(b, len);
+        if (flac)
+        {
+            if (p.status != DCS_OK)                         // (flacParseMany's)
+            {
+                p.why = name + ": " + p.flac.reason;
+                continue;
+            }
+            p.wav = flacAsWav(p.flac);
+        }
+        else if (!isRiffFile(b, len))
         {
             p.status = DCS_ERR_INVALID_ARG;
-            p.why = name + ": neither a DCSa container nor a RIFF/WAVE file";
+            p.why = name + ": not a DCSa container, a RIFF/WAVE file or a FLAC file";
             continue;
         }
-        p.status = wavParse(b, len, &p.wav);
-        if (p.status != DCS_OK)
+        else
         {
-            p.why = name + ": " + p.wav.reason;
-            continue;
+            p.status = wavParse(b, len, &p.wav);
+            if (p.status != DCS_OK)
+            {
+                p.why = name + ": " + p.wav.reason;
+                continue;
+            }
         }
         const DcsWavInfo &w = p.wav;
         if (w.rate < kRsMinRate || w.rate > kRsMaxRate)
@@ -536,7 +607,7 @@ DcsStatus planFiles(const uint8_t *files, const uint64_t *fileOffsets, uint32_t 
             p.why = name + ": " + p.why;
             continue;
         }
-        p.kind = DCS_FILE_WAV;
+        p.kind = flac ? DCS_FILE_FLAC : DCS_FILE_WAV;
         const uint64_t count = s.passThrough ? m : rsSlots(s);
         const uint64_t cap = uint64_t(65535) * 240;
         p.bound = (os93 ? dcs_encode93_bound : dcs_encode_bound)(count < cap ? count : cap);
@@ -600,21 +671,37 @@ extern "C" DcsStatus dcs_encode_files_plan(const uint8_t *files, const uint64_t 
 }
 
 namespace {
+// dcs_wav_decode (flac false) and dcs_flac_decode (true): each takes its own kind of file only
 DcsStatus wavDecode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles, float *out,
-                                    size_t outCap, uint64_t *outOffsets)
+                                    size_t outCap, uint64_t *outOffsets, bool flac)
 {
     if (ctx == nullptr || fileOffsets == nullptr || outOffsets == nullptr || (nFiles != 0 && files == nullptr))
         return DCS_ERR_INVALID_ARG;
     std::vector<DcsWavInfo> infos(nFiles);
     std::vector<const uint8_t *> bytes(nFiles);
+    std::vector<DcsFlacInfo> flacInfos(flac ? nFiles : 0);
+    std::vector<std::vector<DcsFlacFrame>> flacFrames(flac ? nFiles : 0);
+    std::vector<FlacSource> sources(flac ? nFiles : 0);
     outOffsets[0] = 0;
     for (uint32_t i = 0 ; i < nFiles ; ++i)
     {
         if (fileOffsets[i + 1] < fileOffsets[i])
             return DCS_ERR_INVALID_ARG;
         bytes[i] = files + fileOffsets[i];
-        DcsStatus st = wavParse(bytes[i], fileOffsets[i + 1] - fileOffsets[i], &infos[i]);
-        std::string why = infos[i].reason;
+        DcsStatus st;
+        std::string why;
+        if (flac)
+        {
+            st = flacParse(bytes[i], fileOffsets[i + 1] - fileOffsets[i], &flacInfos[i], &flacFrames[i]);
+            why = flacInfos[i].reason;
+            infos[i] = flacAsWav(flacInfos[i]);
+            sources[i] = FlacSource{ &flacInfos[i], &flacFrames[i] };
+        }
+        else
+        {
+            st = wavParse(bytes[i], fileOffsets[i + 1] - fileOffsets[i], &infos[i]);
+            why = infos[i].reason;
+        }
         if (st == DCS_OK && !wavLengthOk(infos[i], nullptr, why))
             st = DCS_ERR_INVALID_ARG;
         if (st != DCS_OK)
@@ -631,7 +718,13 @@ DcsStatus wavDecode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffse
     std::vector<WavFile> wf;
     std::vector<uint32_t> bad;
     float *dMono = nullptr;
-    ENCTRY(wavStageOnDevice(ctx, bytes.data(), infos.data(), nFiles, wf, held, &dMono, bad));
+    ENCTRY(wavStageOnDevice(ctx, bytes.data(), infos.data(), flac ? sources.data() : nullptr, nFiles, wf, held, &dMono, bad));
+    for (uint32_t i = 0 ; flac && i < nFiles ; ++i)
+        if (bad[i])
+        {
+            dcsCtxSetError(ctx, ("file " + std::to_string(i) + ": " + stageWhy(bad[i])).c_str());
+            return DCS_ERR_BAD_STREAM;
+        }
     if (out == nullptr || outCap < outOffsets[nFiles])
         return DCS_ERR_CAPACITY;
     if (outOffsets[nFiles] != 0)
@@ -672,11 +765,11 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
         return DCS_OK;
     std::vector<uint32_t> wavIdx, dcsaIdx;
     for (uint32_t i = 0 ; i < nFiles ; ++i)
-        (plan[i].kind == DCS_FILE_WAV ? wavIdx : dcsaIdx).push_back(i);
+        (plan[i].kind == DCS_FILE_WAV || plan[i].kind == DCS_FILE_FLAC ? wavIdx : dcsaIdx).push_back(i);
     const bool os93 = params->formatVersion != 0x9400;
     std::vector<uint64_t> size(nFiles, 0);
     std::vector<DcsEncodeFileInfo> fi(nFiles);
-    // the WAV group: upload, W0 / W1, walk, convolve, encode where it lies; the stream bytes come down into wavOut
+    // the WAV and FLAC group: upload, W0 / W1 and F1 / F2 / F3, walk, convolve, encode where it lies; the stream bytes come down into wavOut
     const uint32_t nW = static_cast<uint32_t>(wavIdx.size());
     std::vector<uint8_t> wavOut;
     std::vector<uint64_t> wavOffsets(static_cast<size_t>(nW) + 1, 0);
@@ -685,19 +778,23 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
         CacheArena held(ctx);               // (given back at the end of this block, before the DCSa group borrows its own)
         std::vector<DcsWavInfo> infos(nW);
         std::vector<const uint8_t *> bytes(nW);
+        std::vector<FlacSource> sources(nW, FlacSource{ nullptr, nullptr });
         for (uint32_t k = 0 ; k < nW ; ++k)
         {
-            infos[k] = plan[wavIdx[k]].wav;
+            const FilePlan &p = plan[wavIdx[k]];
+            infos[k] = p.wav;
             bytes[k] = files + fileOffsets[wavIdx[k]];
+            if (p.kind == DCS_FILE_FLAC)
+                sources[k] = FlacSource{ &p.flac, &p.flacFrames };
         }
         std::vector<WavFile> wf;
         std::vector<uint32_t> bad;
         float *dMono = nullptr;
-        ENCTRY(wavStageOnDevice(ctx, bytes.data(), infos.data(), nW, wf, held, &dMono, bad));
+        ENCTRY(wavStageOnDevice(ctx, bytes.data(), infos.data(), sources.data(), nW, wf, held, &dMono, bad));
         for (uint32_t k = 0 ; k < nW ; ++k)
             if (bad[k])
             {
-                dcsCtxSetError(ctx, ("file " + std::to_string(wavIdx[k]) + ": a sample (or a stereo pair's mean) is not finite").c_str());
+                dcsCtxSetError(ctx, ("file " + std::to_string(wavIdx[k]) + ": " + stageWhy(bad[k])).c_str());
                 return DCS_ERR_BAD_STREAM;
             }
         std::vector<RsStream> hs(nW);
@@ -753,7 +850,7 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
         for (uint32_t k = 0 ; k < nW ; ++k)
         {
             DcsEncodeFileInfo &t = fi[wavIdx[k]];
-            t.kind = DCS_FILE_WAV;
+            t.kind = plan[wavIdx[k]].kind;
             t.sourceFormat = infos[k].formatCode;
             t.rate = infos[k].rate;
             t.channels = infos[k].channels;
@@ -821,7 +918,7 @@ extern "C" DcsStatus dcs_wav_decode(DcsCtx *ctx, const uint8_t *files, const uin
 {
     try
     {
-        return wavDecode(ctx, files, fileOffsets, nFiles, out, outCap, outOffsets);
+        return wavDecode(ctx, files, fileOffsets, nFiles, out, outCap, outOffsets, false);
     }
     catch (const std::bad_alloc &)
     {

@@ -42,7 +42,9 @@ extern "C" {
                                           DcsEncodeFileInfo, DCS_WAV_*, DCS_FILE_*, dcs_wav_parse, dcs_wav_decode,
                                           dcs_encode_files_plan, dcs_encode_files); sweeping and fitting (DcsSweepJob,
                                           DcsSweepResult, DCS_SWEEP_MEASURE, dcs_encode_sweep,
-                                          dcs_encode_sweep_group_frames, dcs_encode_fit) */
+                                          dcs_encode_sweep_group_frames, dcs_encode_fit); FLAC files (DcsFlacInfo,
+                                          DcsFlacFrame, DCS_WAV_S8, DCS_FILE_FLAC, dcs_flac_parse, dcs_flac_index,
+                                          dcs_flac_decode; dcs_encode_files and dcs_encode_files_plan take FLAC files) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -920,7 +922,8 @@ DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const uint64_t *s
  * Encoding files: DCSEncoder::EncodeFile (DCSEncodeFile.cpp:29-105) on files held in memory.  A "DCSa" container (IsDCSFile's
  * test) is copied or re-encoded as dcs_transcode_streams does it (EncodeDCSFile); a RIFF/WAVE file is read as libnyquist's
  * WavDecoder::LoadFromBuffer reads it, downmixed ((L + R) / 2.0f), resampled and encoded as dcs_encode_streams_at does it;
- * anything else is DCS_ERR_INVALID_ARG.  The numbered rules where libnyquist is undefined or departs from the format are in
+ * a native FLAC file ("fLaC" at the start, or after one ID3v2 tag) is read as libnyquist's FlacDecoder reads it through
+ * libFLAC, and from there on is treated as a WAV file is; anything else is DCS_ERR_INVALID_ARG.  The numbered rules where libnyquist is undefined or departs from the format are in
  * INTEGRATION.md, "Encoding files".  Files i is files[fileOffsets[i] .. fileOffsets[i+1]).
  */
 #define DCS_WAV_U8   0                 /* sample formats (DcsWavInfo.sampleFormat): unsigned 8-bit ...                     */
@@ -929,7 +932,8 @@ DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const uint64_t *s
 #define DCS_WAV_S32  3                 /* ... signed 32-bit ...                                                            */
 #define DCS_WAV_F32  4                 /* ... IEEE float ...                                                               */
 #define DCS_WAV_F64  5                 /* ... IEEE double ...                                                              */
-#define DCS_WAV_IMA  6                 /* ... IMA ADPCM, 4 bits                                                            */
+#define DCS_WAV_IMA  6                 /* ... IMA ADPCM, 4 bits ...                                                        */
+#define DCS_WAV_S8   7                 /* ... signed 8-bit (DcsFlacInfo.sampleFormat only: FLAC's 8-bit samples are signed) */
 
 typedef struct DcsWavInfo
 {
@@ -950,7 +954,8 @@ typedef struct DcsWavInfo
 
 #define DCS_FILE_WAV            0      /* DcsEncodeFileInfo.kind: a RIFF/WAVE file, encoded ...                            */
 #define DCS_FILE_DCSA_COPY      1      /* ... a DCSa container whose stream is copied ...                                  */
-#define DCS_FILE_DCSA_REENCODE  2      /* ... a DCSa container whose stream is decoded and encoded again                   */
+#define DCS_FILE_DCSA_REENCODE  2      /* ... a DCSa container whose stream is decoded and encoded again ...               */
+#define DCS_FILE_FLAC           3      /* ... a native FLAC file, encoded                                                  */
 #define DCS_FILE_WALK_NONE      0      /* DcsEncodeFileInfo.walk: no resampling (31 250 Hz, or a DCSa file) ...           */
 #define DCS_FILE_WALK_DEVICE    1      /* ... the position walk ran on a device lane ...                                   */
 #define DCS_FILE_WALK_HOST      2      /* ... on the host (a file that dominates the list)                */
@@ -958,7 +963,8 @@ typedef struct DcsWavInfo
 typedef struct DcsEncodeFileInfo
 {
     int32_t  kind;                     /* DCS_FILE_*                                                                       */
-    int32_t  sourceFormat;             /* WAV: the format code; DCSa: the container's DcsOsVersion                         */
+    int32_t  sourceFormat;             /* WAV: the format code; DCSa: the container's DcsOsVersion; FLAC: the sample format
+                                          (DCS_WAV_S8, DCS_WAV_S16, DCS_WAV_S24).  The other fields are a FLAC file's as a WAV file's */
     uint32_t rate;                     /* WAV: the file's rate; DCSa: 31 250                                               */
     int32_t  channels;
     uint64_t nValues;                  /* WAV: values read (interleaved); DCSa: the stream's bytes                         */
@@ -986,6 +992,46 @@ DcsStatus dcs_wav_decode(DcsCtx *ctx, const uint8_t *files, const uint64_t *file
 DcsStatus dcs_encode_files(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
                            const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out,
                            size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info);
+
+/* FLAC files (INTEGRATION.md "Encoding files", rules 20-25).  The host reads the metadata chain (STREAMINFO alone is used)
+ * and indexes the frames; the device decodes them: entropy decode per frame, predictor restore per (frame, channel), then the
+ * channel assignment, the cut to the stream's width and the WAV path's conversion and downmix. */
+typedef struct DcsFlacInfo
+{
+    int32_t  status;                   /* DCS_OK, or why the file is refused (DCS_ERR_INVALID_ARG / DCS_ERR_BAD_STREAM)    */
+    uint32_t rate;                     /* Hz, STREAMINFO's                                                                 */
+    int32_t  channels;                 /* 1 or 2                                                                           */
+    int32_t  bitDepth;                 /* 8, 16 or 24                                                                      */
+    int32_t  sampleFormat;             /* DCS_WAV_S8, DCS_WAV_S16 or DCS_WAV_S24                                           */
+    uint32_t minBlockSize;             /* STREAMINFO's block size limits                                                   */
+    uint32_t maxBlockSize;
+    uint32_t nFrames;                  /* frames indexed                                                                   */
+    uint64_t totalSamples;             /* STREAMINFO's count of samples per channel                                        */
+    uint64_t nValues;                  /* float values libnyquist produces: totalSamples x channels                        */
+    uint64_t firstFrameOffset;         /* the byte after the last metadata block                                           */
+    char     reason[96];               /* a refusal's reason                                                               */
+} DcsFlacInfo;
+
+typedef struct DcsFlacFrame
+{
+    uint64_t offset;                   /* the frame's first byte (its sync code) in the file ...                           */
+    uint32_t length;                   /* ... and its bytes, the CRC-16 included                                           */
+    uint32_t blockSize;                /* samples per channel                                                              */
+    uint64_t firstSample;              /* the running count of the samples before it                                       */
+    int32_t  channelAssignment;        /* the header's code: 0-7 independent channels, 8 left/side, 9 right/side, 10 mid/side */
+    int32_t  bitsPerSample;
+    int32_t  blockingStrategy;         /* 0 fixed (the header numbers frames), 1 variable (it numbers samples)             */
+    int32_t  headerLength;             /* the header's bytes, its CRC-8 included                                           */
+} DcsFlacFrame;
+
+/* host only: one file's metadata and frame index.  Returns info->status; info->reason says why a file is refused. */
+DcsStatus dcs_flac_parse(const uint8_t *file, size_t len, DcsFlacInfo *info);
+/* host only: the frame index itself.  *nFrames is filled always; DCS_ERR_CAPACITY when cap (frames) is too small. */
+DcsStatus dcs_flac_index(const uint8_t *file, size_t len, DcsFlacFrame *frames, uint32_t cap, uint32_t *nFrames);
+/* FLAC files -> mono float PCM at each file's own rate (the device path alone, F1 to F3), with dcs_wav_decode's arguments
+ * and capacity protocol.  A frame the device refuses is DCS_ERR_BAD_STREAM; dcs_last_error names file and frame. */
+DcsStatus dcs_flac_decode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles, float *out,
+                          size_t outCap, uint64_t *outOffsets);
 
 /* ------------------------------------------------------------------------------------------------
  * Sweeping parameters and fitting a byte budget.  A JOB is one stream encoded with one parameter set.  dcs_encode_sweep

@@ -5,7 +5,14 @@
 host), 256 x 10 s IMA ADPCM mono 22.05 kHz (its composition decodes with dcs_wav_decode, because the numpy ADPCM restatement
 is a Python loop).  Each path is timed to the call's return, median of --iters after a warm-up call, the two paths
 alternating; both must give the same bytes.  Prints one JSON line.  Per-kernel times: run this under
-`rocprofv3 --kernel-trace --stats -- python tools/encode_files_bench.py --iters 1`."""
+`rocprofv3 --kernel-trace --stats -- python tools/encode_files_bench.py --iters 1`.
+
+--flac: what reading FLAC costs.  The same audio as a FLAC file and as a 16-bit WAV file through encode_files: the 1 s
+44.1 kHz stereo shape of tests/flac_cases.py (4 096-sample frames, LPC orders 8 and 6, left/side and mid/side) repeated to
+--flac-seconds, the file replicated over --flac-files counts (1, 16, 256).  Wall time per call for each, median of --iters;
+both must give the same bytes.  The WAV run is the yardstick; the difference is the cost of F1, F2, F3 and the index.  Under
+`rocprofv3 --kernel-trace --stats -- python tools/encode_files_bench.py --flac --flac-files 256 --iters 1` the three kernels
+stand beside the resample and encode kernels."""
 import argparse
 import json
 import os
@@ -55,6 +62,41 @@ def workload(name):
     return [ima_mono(10, 22050, k) for k in range(256)]
 
 
+def flac_and_wav(seconds):
+    """-> (FLAC file, WAV file) of the same integers: flac_cases' realistic second, its frames renumbered and repeated"""
+    import flac_cases as F
+    import flac_ref as FR
+    second = dict(F.cases())["realistic_44100_stereo"]
+    ints = F.integers()["realistic_44100_stereo"][0]
+    _, frames = FR.index(second)
+    out = []
+    for c in range(seconds):
+        for j, f in enumerate(frames):
+            body = second[f["offset"] + f["headerLength"]:f["offset"] + f["length"] - 2]
+            fr = F.frame_header(c * len(frames) + j, f["blockSize"], f["channelAssignment"]) + body
+            out.append(fr + struct.pack(">H", F.crc16(fr)))
+    info = F.streaminfo(frames[-1]["blockSize"], frames[0]["blockSize"], 44100, 2, 16, 44100 * seconds)
+    flac = b"fLaC" + F.metadata_block(0, info, True) + b"".join(out)
+    return flac, W.wav("s16", 2, 44100, np.tile(ints, seconds))
+
+
+def flac_mode(ctx, a):
+    flac, wav = flac_and_wav(a.flac_seconds)
+    res = dict(seconds=a.flac_seconds, flac_mb=len(flac) / 1e6, wav_mb=len(wav) / 1e6, frames=D.flac_parse(flac)["nFrames"], counts={})
+    for n in [int(x) for x in a.flac_files.split(",")]:
+        ff, ww = [flac] * n, [wav] * n
+        out_f, info = ctx.encode_files(ff)
+        out_w, _ = ctx.encode_files(ww)
+        tf, tw = [], []
+        for _ in range(a.iters):
+            t = time.perf_counter(); ctx.encode_files(ff); tf.append(time.perf_counter() - t)
+            t = time.perf_counter(); ctx.encode_files(ww); tw.append(time.perf_counter() - t)
+        res["counts"][n] = dict(f1_lanes=n * res["frames"], flac_s=float(np.median(tf)), wav_s=float(np.median(tw)),
+                                flac_minus_wav_s=float(np.median(tf) - np.median(tw)), bytes_equal=out_f == out_w,
+                                out_samples=int(info["nSamples"].sum()))
+    return res
+
+
 def host_composition(ctx, files):
     mono, rates = [], []
     if R.parse(files[0])[1].get("sampleFormat") == R.IMA:
@@ -72,8 +114,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--workloads", default="256x10s_s16_stereo_44k,1x180s_s16_stereo_44k,256x10s_ima_mono_22k")
+    ap.add_argument("--flac", action="store_true")
+    ap.add_argument("--flac-seconds", type=int, default=60)
+    ap.add_argument("--flac-files", default="1,16,256")
     a = ap.parse_args()
     ctx = D.Context(0)
+    if a.flac:
+        res = flac_mode(ctx, a)
+        ctx.close()
+        print(json.dumps(dict(tool="encode_files_bench", mode="flac", results=res)))
+        return 0
     res = {}
     for w in a.workloads.split(","):
         files = workload(w)
