@@ -106,160 +106,8 @@ const DcsDevTables &dcsTables();
 // MainLoop's shared fixed-point scale with a per-channel master multiplier (dcs_params.cpp)
 int dcsFrameScaleV(const uint16_t *vol, uint16_t *mixMul, const uint8_t *counted, int nch);
 
-// ---------------------------------------------------------------------------------------------
-// Kernel work list.  The planner (dcs_plan.cpp) cuts the job list into chunks of at most FPW slots;
-// one wavefront decodes one chunk.  A slot is a job to decode; HALO slots are decoded only for the
-// 16-sample tail they hand to a later slot of the same chunk (the predecessor of the chunk's first
-// frame lives in another chunk).
-// ---------------------------------------------------------------------------------------------
-// LDS bit pool: the compressed bytes of the frames one wavefront unpacks in one round are staged
-// there.  The planner closes a chunk before the pool would overflow.
-#define DCS_POOL_DW_PER_FRAME 56        // 224 bytes per frame slot on average (typical frame: ~125-150 bytes)
-#define DCS_POOL_DW_MIN       320       // but never less than two maximal frames (a halo and its successor)
-#define DCS_MAX_FRAME_BITS    4480      // 16 band headers + 255 x 16-bit samples, rounded up
-
-#ifdef __cplusplus
-// dwords of pool one source occupies: whole dwords covering the frame + 3 dwords of window look-ahead
-static inline
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-uint32_t dcsPoolDwords(uint64_t streamOff, uint32_t hdrLen, uint32_t bitOff, uint32_t nBits)
-{
-    const uint32_t inDword = static_cast<uint32_t>(((streamOff + 2 + hdrLen) * 8 + bitOff) & 31);
-    return (inDword + nBits + 31) / 32 + 3;
-}
-#endif
-
-#ifdef __cplusplus
-static inline
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-constexpr uint32_t dcsPoolCapacity(int fpw)
-{
-    return static_cast<uint32_t>(fpw * DCS_POOL_DW_PER_FRAME > DCS_POOL_DW_MIN ? fpw * DCS_POOL_DW_PER_FRAME : DCS_POOL_DW_MIN);
-}
-#endif
-
-#define DCS_SLOT_HALO      0x01u        // do not write PCM / err for this slot
-#define DCS_SLOT_EXT_TAIL  0x02u        // overlap tail comes from tailsIn[job.prev & 0x7FFFFFFF]
-#define DCS_SLOT_EXPORT    0x04u        // this frame's tail meets a frame of another chunk (job nextJob) at handoff[this chunk]
-#define DCS_SLOT_IMPORT    0x08u        // overlap tail meets this frame at handoff[prevJob] (prevJob = the chunk of its predecessor)
-#define DCS_SLOT_KEEP_TAIL 0x10u        // store this frame's tail in tailsOut: the last frame of its chain in the batch (what a caller
-                                        // needs to carry a stream into its next batch), or every frame when the batch keeps all tails
-#define DCS_SLOT_EMPTY     0x80u        // padding
-#define DCS_NO_PREV_SLOT   0xFFu
-
-struct DcsSlot                          // 32 bytes: everything the kernel needs to know about a job, so
-{                                       // that the job list itself is never read on the device
-    uint32_t job;                       // output index (PCM row, err entry)
-    uint8_t  prevSlot;                  // slot index inside the chunk whose tail overlaps into this one
-    uint8_t  flags;
-    uint8_t  nSrc;
-    uint8_t  shiftXform;                // volShift | xform << 4
-    uint32_t firstSrc;
-    uint32_t prevJob;                   // DcsFrameJob.prev (external-tail index when DCS_SLOT_EXT_TAIL)
-    // Unpack round 0 (the FIRST source of every job), worked out by the planner so that nothing of it waits for
-    // the descriptor.  The compressed bytes of a chunk's frames mostly lie back to back in the blob (consecutive
-    // frames of one stream), so they are staged as RUNS of dwords, 16 bytes per lane: slot k of a chunk carries
-    // run k (runNDw == 0: no further run), which has nothing to do with slot k's own frame.
-    uint32_t runStartDw;                // first blob dword of run k
-    uint16_t runNDw;                    // its length in dwords (whole frames + 3 dwords of window look-ahead)
-    uint16_t poolOff;                   // THIS slot's frame: pool dword that holds its first bit
-    uint32_t nextJob;                   // DCS_SLOT_EXPORT: the job whose first 16 samples this frame's tail overlaps into (round 6; the
-                                        // field held the blob dword of the stream header, which both packers take from the source)
-    uint8_t  pad_;
-    uint8_t  bpl;                       // header bands per unpack lane, ceil(min(nBands, 16) / (64 / fpw)); 0: one lane
-                                        // unpacks the whole frame (DCS_IDX_SERIAL)
-    uint16_t runPoolOff;                // pool dword where run k goes (a multiple of 4)
-};
-
-// Which header bands the q-th unpack lane of a frame takes: lane q starts at dcsLaneFirstBand(q) and ends where lane
-// q + 1 starts.  The 1993 layouts (sixteen bands of sixteen samples) get bpl consecutive bands per lane.  The bands of a
-// 1994+ frame hold 7, 8, 13 x 16 and 32 samples: there bands 0 and 1 count as one and band 15 as two, which with eight
-// lanes gives {0, 1, 2} {3, 4} ... {13, 14} {15}, 31 or 32 samples for every lane (the symbol loop works through them in
-// rounds of 7, 9 and 16 samples, unpack94 in dcs_kernels.hip.h).  With sixteen lanes it is {0, 1} {2} ... {14} {15} and
-// the last lane is left for the second half of band 15, which the packers give it when the index pass recorded where
-// that half starts (dcsMid15: split[14].prv / .prvDelta, dcs_scan.h).
-#ifdef __cplusplus
-static inline
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-constexpr int dcsLaneFirstBand(int format, int q, int bpl, int nbEnd)
-{
-    // OS93a Type 1: eighteen bands of 2, 2, 2, 2, 3, 4, 5, 6, 5, 6, 7, 9, 11, 14, 12, 12, 12, 13 sample pairs
-    // (DCSDecoderNative.cpp:2865).  The lanes of a wavefront walk their k-th bands together, so what counts is the
-    // longest k-th band: {0,1,2} {3,4,5} {6,7} {8,9} ... {16,17} with eight lanes (12 + 14 + 4 pairs; two bands per
-    // lane in order cost 12 + 14 + 12 + 13), {0,1} {2,3} {4} {5} ... {17} with sixteen, {0..6} {7..10} {11..13} {14..17}
-    // with four.  (nbEnd: 18 or the stream's own band count.)
-    if (format == DCS_FMT_93A_T1)
-    {
-        const int b = bpl == 1 ? (q < 2 ? 2 * q : q + 2) : bpl == 2 ? (q < 2 ? 3 * q : 2 * q + 2) : (q == 0 ? 0 : q == 1 ? 7 : q == 2 ? 11 : 14);
-        return b < nbEnd ? b : nbEnd;
-    }
-    const int b = q * bpl + ((format >= DCS_FMT_94_T0 && q != 0) ? 1 : 0);
-    return b < nbEnd ? b : nbEnd;
-}
-// the band where the lanes' dealing ends: sixteen header bands, eighteen for OS93a Type 1
-static inline
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-constexpr int dcsDealEnd(int format, int nBands)
-{
-    return format == DCS_FMT_93A_T1 ? (nBands < 18 ? nBands : 18) : (nBands < 16 ? nBands : 16);
-}
-// OS93a Type 1: a lane's first band can be 16 or 17; then this bit of its state word is set and bits 12..15 hold band - 16
-// (the record itself comes from the frame record's bandType bytes, dcs_scan.h)
-#define DCS_SPLIT_BASE16 0x200u
-// state word of a lane that starts in the middle of band 15: output index | DCS_MID15_STRADDLE (bit 9) | this flag
-#define DCS_SPLIT_MID15 0x800u
-#define DCS_MID15_STRADDLE 0x200u
-// ... and whether the frame's last lane does: one band per lane, all sixteen bands, a recorded middle
-static inline
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-constexpr bool dcsMid15(int format, int bpl, int nb16, uint32_t midBits)
-{
-    return format >= DCS_FMT_94_T0 && bpl == 1 && nb16 == 16 && midBits != 0;
-}
-#endif
-
-// Chunk packages.  Everything unpack round 0 of a chunk needs, gathered once per batch by the host packer
-// (dcsBuildPackages, dcs_plan.cpp) or the device packer (dcsPackKernel) into one block at a fixed stride, so that a wavefront
-// requests ALL of it at its first instruction (no load depends on another load).  Round 5 layout (a wavefront reads its whole
-// package, so every byte of it counts as HBM traffic):
-//   [0, fpw x 80)   per slot five 16-byte pieces: the slot (DcsSlot bytes 0..15: job, prevSlot | flags | nSrc | shiftXform,
-//                   firstSrc, prevJob) | descriptor head bytes 0..15 | 16..31 | 32..39 followed by poolOff (u16), bpl (u8),
-//                   a spare byte and nextJob (u32) | the stream header (16 B, a 1-byte header zero-extended)
-//   [fpw x 80, ..)  the split record of every lane [64]: 8 bytes (zero for a frame's first lane; the lane's first band in bits
-//                   12..15 of its state word, bit 15 of bitDelta: no bands) -- or, when every source of the batch is a 1994+
-//                   frame, 4 bytes: bitDelta | state << 16 (those layouts carry nothing in prv / prvDelta but band 15's middle,
-//                   which the packers fold into the two halves)
-//   [dcsPkgOffPool, + imgDw x 4)  the image of the bit pool (runs placed, dwords in bit order), as long as the batch's fullest
-//                   chunk needs, a multiple of 128 bytes (a HOST-planned batch; one planned on the device has the pool's capacity:
-//                   its stride would have to come out of device memory, a dependent load in front of the package loads)
-// The layout word: image dwords | DCS_PKG_SPLIT4; it travels to the kernel in bits 16..31 of its flags.
-#ifdef __cplusplus
-#define DCS_PKG_SLOT_BYTES 80u
-#define DCS_PKG_SPLIT4     0x8000u
-#ifdef __HIPCC__
-#define DCS_HD __host__ __device__
-#else
-#define DCS_HD
-#endif
-static inline DCS_HD constexpr uint32_t dcsPkgImgDw(uint32_t layout) { return layout & 0x7FFFu; }
-static inline DCS_HD constexpr uint32_t dcsPkgSplitBytes(uint32_t layout) { return (layout & DCS_PKG_SPLIT4) ? 4u : 8u; }
-static inline DCS_HD constexpr uint32_t dcsPkgOffSplit(int fpw) { return static_cast<uint32_t>(fpw) * DCS_PKG_SLOT_BYTES; }
-static inline DCS_HD constexpr uint32_t dcsPkgOffPool(int fpw, uint32_t layout)
-{
-    return (static_cast<uint32_t>(fpw) * DCS_PKG_SLOT_BYTES + 64u * dcsPkgSplitBytes(layout) + 127u) & ~127u;
-}
-static inline DCS_HD constexpr uint32_t dcsPkgStride(int fpw, uint32_t layout) { return dcsPkgOffPool(fpw, layout) + dcsPkgImgDw(layout) * 4u; }
-#endif
+// the kernel work list (DcsSlot), the chunk plan's rules and the chunk packages
+#include "dcs_package.h"
 
 struct DcsKernelArgs
 {
@@ -297,34 +145,6 @@ struct DcsKernelArgs
 #define DCS_BATCH_IMG_SHIFT 16          // bits 16..31: the packages' layout word (image dwords | DCS_PKG_SPLIT4; dcsPkgStride)
 #define DCS_BATCH_IMG_MASK  0xFFFFu
 
-// A source as the planner and the DEVICE packer need it when the index records stay on the device (the pipeline's
-// device path): 24 bytes instead of the 160 of DcsSrcDesc.  `record` = index of the frame's DcsFrameIndex in the
-// device-resident record array.
-struct DcsPlanSrc
-{
-    uint64_t streamOff;
-    uint32_t bitOff;
-    uint16_t nBits;
-    uint8_t  hdrLen, nBands, flags, format;
-    uint16_t mixMul;
-    uint32_t record;
-};
-// What the DEVICE planner (dcsPlanKernel, dcs_runtime.hip) is told about a stream of a list of whole streams -- everything
-// the host knows without walking the stream: where it lies, its frame count, layout and mixing parameters.  40 bytes.
-struct DcsPlanStream
-{
-    uint64_t streamOff;                 // offset of the stream in the list's blob
-    uint32_t len;                       // bytes that belong to it
-    uint32_t firstRecord;               // its records in the list's record array
-    uint32_t firstJob;                  // its first output frame
-    uint32_t nFrames;                   // the stream's U16 frame count (output frames: nFrames + extraFrames)
-    uint16_t mixMul0, mixMulN;          // rescaled mixing multiplier of frame 0 / of every later frame (dcs_stream_params_from)
-    uint8_t  volShift0, volShiftN;
-    uint8_t  xform, hdrLen, format, pad_[3];
-};
-static_assert(sizeof(DcsPlanStream) == 40, "DcsPlanStream layout (uploaded by copy kernel: whole dwords)");
-#define DCS_PLAN_POOL_OVERFLOW 1u       // flag word of the device planner: some chunk's compressed bytes do not fit the bit pool
-#define DCS_PLAN_TRUNCATED     2u       // ... some stream's frames run past its buffer
 // what the index kernel writes per frame next to the full record: all the host needs for planning (8 bytes)
 struct DcsFrameDigest
 {
@@ -333,7 +153,6 @@ struct DcsFrameDigest
     uint8_t  nBands, flags;
 };
 
-// planner: returns the number of chunks; slots is resized to nChunks * fpw
 #ifdef __cplusplus
 #include <vector>
 // whole streams -> batch description (dcs_streams.cpp): index pass on the host pool, per-frame mixing parameters, the
@@ -386,23 +205,24 @@ struct DcsBuiltPlan
 };
 DcsStatus dcsBuildPlanFromDigest(const DcsStreamRef *streams, uint32_t nStreams, uint32_t extraFrames, const DcsDigested &in,
                                  DcsBuiltPlan &P);
-// (depthOrder = false: the chunks stay in chain order, for launches in XCD ranges -- DCS_BATCH_XCD_RANGES)
-// dwords of pool image the packages of a plan need: the fullest chunk's runs, rounded up to 32 dwords, at most the pool's capacity
-uint32_t dcsImageDwords(const DcsSlot *slots, uint32_t nChunks, int fpw);
+// every source the jobs draw on is a 1994+ frame (the packages then carry 4-byte split records, DCS_PKG_SPLIT4)
 bool dcsAllSources94(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs);
-// (keepAllTails: every frame's slot gets DCS_SLOT_KEEP_TAIL, else only the last frame of every chain)
-// (shuffleSeed != 0, a test hook: the chunks in a seeded random order -- the rendezvous between chunks must not care)
-uint32_t dcsPlanChunks(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff = true,
-                       int framesPerChunk = 0, bool depthOrder = true, bool keepAllTails = false, uint32_t shuffleSeed = 0);
+// The planner (dcs_plan.cpp), from either form of source record.  slots is resized to nChunks x fpw; imgDw: dwords of pool image
+// the packages of the plan need -- the fullest chunk's runs, rounded up to 32 dwords, at most the pool's capacity.
+struct DcsPlanOptions
+{
+    bool handoff = true;                // tails between chunks go through the hand-off buffer (else every chunk re-decodes a halo)
+    int framesPerChunk = 0;             // diagnostic: fewer frames per chunk than the kernel variant has slots (0: all of them)
+    bool keepAllTails = false;          // every frame's slot gets DCS_SLOT_KEEP_TAIL, else only the last frame of every chain
+    uint32_t places = 0;                // a RESIDENT batch: wavefronts of the decode kernel the chip runs at a time (CUs x 16); the plan
+                                        // is then made a second time for the shortest packages (dcs_plan.cpp).  0: planned once
+};
+struct DcsPlan { uint32_t nChunks, imgDw; };
+DcsPlan dcsPlanJobs(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, int fpw, std::vector<DcsSlot> &slots, const DcsPlanOptions &o);
+DcsPlan dcsPlanJobs(const DcsFrameJob *jobs, uint32_t nJobs, const DcsPlanSrc *srcs, int fpw, std::vector<DcsSlot> &slots, const DcsPlanOptions &o);
+// (a test hook: the chunks in a seeded random order -- the rendezvous between chunks must not care; seed 0: as planned)
 void dcsShuffleChunks(std::vector<DcsSlot> &slots, uint32_t nChunks, int fpw, uint32_t seed);
-// (places: wavefronts of the decode kernel the chip runs at a time -- CUs x 16 -- or 0; the diagnostic entries assume an MI355X)
-#define DCS_MI355X_WAVE_PLACES 4096u
-uint32_t dcsPlanChunksCapped(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff,
-                             int framesPerChunk, bool depthOrder, bool keepAllTails, uint32_t *imgDwOut, uint32_t places);
-uint32_t dcsPlanChunksCappedLite(const DcsFrameJob *jobs, uint32_t nJobs, const DcsPlanSrc *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff,
-                                 int framesPerChunk, bool depthOrder, bool keepAllTails, uint32_t *imgDwOut, uint32_t places);
-uint32_t dcsPlanChunksLite(const DcsFrameJob *jobs, uint32_t nJobs, const DcsPlanSrc *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff = true,
-                           int framesPerChunk = 0, bool depthOrder = true, bool keepAllTails = false);
+#define DCS_MI355X_WAVE_PLACES 4096u    // (the diagnostic entries assume an MI355X)
 // packer: out = nChunks x dcsPkgStride(fpw, layout) bytes (the chunk packages described above); layout = image dwords | DCS_PKG_SPLIT4
 void dcsBuildPackages(const DcsSlot *slots, uint32_t nChunks, int fpw, const DcsSrcDesc *srcs,
                       const uint8_t *blob, size_t blobLen, uint8_t *out, uint32_t layout);

@@ -16,20 +16,16 @@
 #include <thread>
 #include <vector>
 
-// What the planner needs to know about a source, from either form of source record: the full descriptor of the ABI, or
-// the digest the pipeline works from when the index records stay on the device (DcsPlanSrc).
-static inline uint64_t srcStreamOff(const DcsSrcDesc &s) { return s.streamOff; }
-static inline uint32_t srcHdrLen(const DcsSrcDesc &s) { return s.hdrLen; }
-static inline uint32_t srcBitOff(const DcsSrcDesc &s) { return s.idx.bitOff; }
-static inline uint32_t srcNBits(const DcsSrcDesc &s) { return s.idx.nBits; }
-static inline int srcNBands(const DcsSrcDesc &s) { return s.idx.nBands; }
-static inline uint32_t srcFlags(const DcsSrcDesc &s) { return s.idx.flags; }
-static inline uint64_t srcStreamOff(const DcsPlanSrc &s) { return s.streamOff; }
-static inline uint32_t srcHdrLen(const DcsPlanSrc &s) { return s.hdrLen; }
-static inline uint32_t srcBitOff(const DcsPlanSrc &s) { return s.bitOff; }
-static inline uint32_t srcNBits(const DcsPlanSrc &s) { return s.nBits; }
-static inline int srcNBands(const DcsPlanSrc &s) { return s.nBands; }
-static inline uint32_t srcFlags(const DcsPlanSrc &s) { return s.flags; }
+// What the planner needs to know about a source, from either form of source record (the full descriptor of the ABI, or the digest
+// the pipeline works from when the index records stay on the device): where its bytes lie in the blob -- first dword, dwords of
+// pool they occupy (dcs_package.h) -- its band count and the index pass's flags
+struct SrcGeom { uint32_t firstDw, nDw, nBands, flags; };
+static inline SrcGeom geom(uint64_t streamOff, uint32_t hdrLen, uint32_t bitOff, uint32_t nBits, uint32_t nBands, uint32_t flags)
+{
+    return SrcGeom{ dcsFrameFirstDword(streamOff, hdrLen, bitOff), dcsPoolDwords(streamOff, hdrLen, bitOff, nBits), nBands, flags };
+}
+static inline SrcGeom geom(const DcsSrcDesc &s) { return geom(s.streamOff, s.hdrLen, s.idx.bitOff, s.idx.nBits, s.idx.nBands, s.idx.flags); }
+static inline SrcGeom geom(const DcsPlanSrc &s) { return geom(s.streamOff, s.hdrLen, s.bitOff, s.nBits, s.nBands, s.flags); }
 
 // the slot of one job; where its first source's bytes go in the pool is filled in by placeFrame
 template <class Src>
@@ -37,19 +33,13 @@ static DcsSlot makeSlot(const DcsFrameJob &jb, uint32_t job, uint8_t prevSlot, u
 {
     DcsSlot sl{ job, prevSlot, flags, jb.nSrc, static_cast<uint8_t>(jb.volShift | (jb.xform << 4)), jb.firstSrc, jb.prev, 0, 0, 0, 0, 0, 0, 0 };
     if (srcs != nullptr && jb.nSrc != 0)
-    {
-        const Src &sd = srcs[jb.firstSrc];
-        const int sub = 64 / fpw;
-        const int nb16 = srcNBands(sd) < 16 ? srcNBands(sd) : 16;
-        const int bpl = (nb16 + sub - 1) / sub;
-        sl.bpl = (srcFlags(sd) & DCS_IDX_SERIAL) ? 0 : static_cast<uint8_t>(bpl < 1 ? 1 : bpl);
-    }
+        sl.bpl = dcsBandsPerLane(geom(srcs[jb.firstSrc]).nBands, geom(srcs[jb.firstSrc]).flags, fpw);
     return sl;
 }
 
 template <class Src>
 static uint32_t planChunks(const DcsFrameJob *jobs, uint32_t nJobs, const Src *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff,
-                           int framesPerChunk, bool depthOrder, bool keepAllTails, uint32_t imgCap)
+                           int framesPerChunk, bool keepAllTails, uint32_t imgCap)
 {
     // (diagnostic: fewer frames per chunk than the kernel variant has slots, the rest of the wavefront idles)
     const uint32_t limit = static_cast<uint32_t>(framesPerChunk >= 1 && framesPerChunk < fpw ? framesPerChunk : fpw);
@@ -73,9 +63,8 @@ static uint32_t planChunks(const DcsFrameJob *jobs, uint32_t nJobs, const Src *s
     auto poolNeed = [&](uint32_t j, uint32_t r) -> uint32_t {
         if (srcs == nullptr || r >= jobs[j].nSrc)
             return 0;
-        const Src &sd = srcs[jobs[j].firstSrc + r];
         // (rounded up to the 16-byte granule of the run staging)
-        return (dcsPoolDwords(srcStreamOff(sd), srcHdrLen(sd), srcBitOff(sd), srcNBits(sd)) + 3) & ~3u;
+        return (geom(srcs[jobs[j].firstSrc + r]).nDw + 3) & ~3u;
     };
     auto poolFits = [&](uint32_t j, uint32_t halo, bool withHalo) {
         uint32_t rounds = jobs[j].nSrc;
@@ -93,62 +82,28 @@ static uint32_t planChunks(const DcsFrameJob *jobs, uint32_t nJobs, const Src *s
 
     uint32_t chunk = 0;
     uint32_t used = 0;                  // slots filled in the current chunk
-    // unpack round 0 is staged as runs of blob dwords (DcsSlot): a frame that starts inside or right behind the
-    // chunk's last run extends it, anything else opens a new run at the next 16-byte boundary of the pool
-    struct Run { uint32_t start, n, poolOff; };
-    std::vector<Run> runs;
-    uint32_t runUse = 0;                // pool dwords the runs take (<= poolUse[0], which counts every frame in full)
-    auto placeFrame = [&](DcsSlot &sl, const DcsFrameJob &jb) {
-        if (srcs == nullptr || jb.nSrc == 0)
-            return;
-        const Src &sd = srcs[jb.firstSrc];
-        const uint64_t bitPos = (srcStreamOff(sd) + 2 + srcHdrLen(sd)) * 8 + srcBitOff(sd);
-        const uint32_t st = static_cast<uint32_t>(bitPos >> 5);
-        const uint32_t n = dcsPoolDwords(srcStreamOff(sd), srcHdrLen(sd), srcBitOff(sd), srcNBits(sd));
-        if (!runs.empty() && st >= runs.back().start && st <= runs.back().start + runs.back().n)
+    // unpack round 0 is staged as runs of blob dwords (DcsRunCursor, dcs_package.h); run k rides in slot k of the chunk
+    DcsRunCursor runs;                  // (runs.use <= poolUse[0], which counts every frame in full)
+    size_t chunkBase = 0;               // the current chunk's first slot
+    auto firstSrc = [&](const DcsFrameJob &jb) { return srcs != nullptr && jb.nSrc != 0 ? &srcs[jb.firstSrc] : nullptr; };
+    auto placeFrame = [&](const DcsFrameJob &jb) {
+        if (const Src *sd = firstSrc(jb))
         {
-            Run &r = runs.back();
-            if (st + n > r.start + r.n)
-                r.n = st + n - r.start;
-            runUse = r.poolOff + ((r.n + 3) & ~3u);
+            slots.back().poolOff = static_cast<uint16_t>(runs.place(geom(*sd).firstDw, geom(*sd).nDw));
+            runs.store(slots[chunkBase + runs.nRuns - 1]);
         }
-        else
-        {
-            runs.push_back(Run{ st, n, runUse });
-            runUse += (n + 3) & ~3u;
-        }
-        sl.poolOff = static_cast<uint16_t>(runs.back().poolOff + (st - runs.back().start));
     };
     // pool dwords the chunk's runs would take with job jb's first source added (what placeFrame will do)
     auto runUseWith = [&](const DcsFrameJob &jb, uint32_t from) -> uint32_t {
-        if (srcs == nullptr || jb.nSrc == 0)
-            return from;
-        const Src &sd = srcs[jb.firstSrc];
-        const uint64_t bitPos = (srcStreamOff(sd) + 2 + srcHdrLen(sd)) * 8 + srcBitOff(sd);
-        const uint32_t st = static_cast<uint32_t>(bitPos >> 5);
-        const uint32_t n = dcsPoolDwords(srcStreamOff(sd), srcHdrLen(sd), srcBitOff(sd), srcNBits(sd));
-        if (!runs.empty() && from == runUse && st >= runs.back().start && st <= runs.back().start + runs.back().n)
-        {
-            const Run &r = runs.back();
-            const uint32_t len = st + n > r.start + r.n ? st + n - r.start : r.n;
-            return r.poolOff + ((len + 3) & ~3u);
-        }
-        return from + ((n + 3) & ~3u);
+        const Src *sd = firstSrc(jb);
+        return sd != nullptr ? runs.useWith(geom(*sd).firstDw, geom(*sd).nDw, from) : from;
     };
     const DcsSlot empty{ 0xFFFFFFFFu, DCS_NO_PREV_SLOT, DCS_SLOT_EMPTY, 0, 0, 0, DCS_PREV_NONE, 0, 0, 0, 0, 0, 0, 0 };
     auto closeChunk = [&]() {
         lastLive.push_back(slots.size() - 1);
         while (used < static_cast<uint32_t>(fpw)) { slots.push_back(empty); ++used; }
-        // run k rides in slot k of the chunk (there are never more runs than frames)
-        DcsSlot *cs = &slots[slots.size() - static_cast<size_t>(fpw)];
-        for (size_t k = 0 ; k < runs.size() && k < static_cast<size_t>(fpw) ; ++k)
-        {
-            cs[k].runStartDw = runs[k].start;
-            cs[k].runNDw = static_cast<uint16_t>(runs[k].n);
-            cs[k].runPoolOff = static_cast<uint16_t>(runs[k].poolOff);
-        }
-        runs.clear();
-        runUse = 0;
+        chunkBase = slots.size();
+        runs = DcsRunCursor{};
         ++chunk;
         used = 0;
         for (uint32_t &u : poolUse) u = 0;
@@ -204,10 +159,10 @@ static uint32_t planChunks(const DcsFrameJob *jobs, uint32_t nJobs, const Src *s
                    && (slots[homePos[p]].flags & DCS_SLOT_EXPORT) == 0;
         };
         uint32_t need = (link && !inChunk(prev) && !canImport(prev)) ? 2u : 1u;
-        // imgCap (resident batches, dcsPlanChunksCapped): a chunk whose runs would outgrow the batch's pool image is closed early
+        // imgCap (resident batches, dcsPlanJobs): a chunk whose runs would outgrow the batch's pool image is closed early
         // as well -- a few per cent of the chunks then hold a frame less, and every package is that much shorter
         const bool imgFull = imgCap != 0 && used != 0
-                             && runUseWith(jobs[j], need == 2 ? runUseWith(jobs[prev], runUse) : runUse) > imgCap;
+                             && runUseWith(jobs[j], need == 2 ? runUseWith(jobs[prev], runs.use) : runs.use) > imgCap;
         if (used + need > (need == 2 && limit < 2 ? 2u : limit) || (used != 0 && !poolFits(j, prev, need == 2)) || imgFull)
         {
             closeChunk();
@@ -234,7 +189,7 @@ static uint32_t planChunks(const DcsFrameJob *jobs, uint32_t nJobs, const Src *s
             else
             {
                 slots.push_back(makeSlot(jobs[prev], prev, DCS_NO_PREV_SLOT, DCS_SLOT_HALO, srcs, fpw));
-                placeFrame(slots.back(), jobs[prev]);
+                placeFrame(jobs[prev]);
                 poolAdd(prev);
                 stampOf[prev] = chunk;
                 slotOf[prev] = static_cast<uint8_t>(used++);
@@ -244,7 +199,7 @@ static uint32_t planChunks(const DcsFrameJob *jobs, uint32_t nJobs, const Src *s
         slots.push_back(makeSlot(jobs[j], j, prevSlot, flags, srcs, fpw));
         if (flags & DCS_SLOT_IMPORT)
             slots.back().prevJob = importFrom;          // the chunk whose last frame publishes the tail
-        placeFrame(slots.back(), jobs[j]);
+        placeFrame(jobs[j]);
         poolAdd(j);
         stampOf[j] = chunk;
         slotOf[j] = static_cast<uint8_t>(used++);
@@ -256,10 +211,7 @@ static uint32_t planChunks(const DcsFrameJob *jobs, uint32_t nJobs, const Src *s
     if (used != 0)
         closeChunk();
 
-    // The chunks stay in chain order.  (Rounds 2-5 reordered them by depth in the hand-off graph, so that a consumer did not reach
-    // its wait before the tail was there; consumers no longer wait -- the rendezvous, dcs_kernels.hip.h -- and the order measures
-    // the same either way: 33.15 us for 65 536 frames, measured A/B.)
-    (void)depthOrder;
+    // (the chunks stay in chain order: a chunk takes its tail from a chunk before it)
     return chunk;
 }
 
@@ -290,24 +242,32 @@ void dcsShuffleChunks(std::vector<DcsSlot> &slots, uint32_t nChunks, int fpw, ui
     slots.swap(moved);
 }
 
-uint32_t dcsPlanChunks(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff,
-                       int framesPerChunk, bool depthOrder, bool keepAllTails, uint32_t shuffleSeed)
+// dwords of pool image the packages of a plan need
+static uint32_t imageDwords(const DcsSlot *slots, uint32_t nChunks, int fpw)
 {
-    const uint32_t n = planChunks(jobs, nJobs, srcs, fpw, slots, handoff, framesPerChunk, depthOrder, keepAllTails, 0);
-    dcsShuffleChunks(slots, n, fpw, shuffleSeed);
-    return n;
+    uint32_t use = 0;
+    for (size_t i = 0, n = static_cast<size_t>(nChunks) * static_cast<size_t>(fpw) ; i < n ; ++i)
+        if (slots[i].runNDw != 0)
+        {
+            const uint32_t end = static_cast<uint32_t>(slots[i].runPoolOff) + slots[i].runNDw;
+            if (end > use)
+                use = end;
+        }
+    const uint32_t cap = dcsPoolCapacity(fpw);
+    use = (use + 31u) & ~31u;
+    if (use < 32u) use = 32u;           // (the kernel's image loads clamp to imgDw - 4)
+    return use < cap ? use : cap;
 }
 
 // A resident batch is planned for the shortest packages that cost it next to nothing: the plan above, then -- when its fullest
 // chunks are outliers -- once more with the pool image capped at what 97 % of the chunks need (rounded up to 32 dwords).  The
-// chunks that would have been fuller close a frame early.  *imgDwOut = dcsImageDwords of the plan returned.
+// chunks that would have been fuller close a frame early.  (o.places == 0: the first plan is the plan.)
 template <class Src>
-static uint32_t planChunksCapped(const DcsFrameJob *jobs, uint32_t nJobs, const Src *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff,
-                                 int framesPerChunk, bool depthOrder, bool keepAllTails, uint32_t *imgDwOut, uint32_t places)
+static DcsPlan planJobs(const DcsFrameJob *jobs, uint32_t nJobs, const Src *srcs, int fpw, std::vector<DcsSlot> &slots, const DcsPlanOptions &o)
 {
-    uint32_t nChunks = planChunks(jobs, nJobs, srcs, fpw, slots, handoff, framesPerChunk, depthOrder, keepAllTails, 0);
-    uint32_t imgDw = dcsImageDwords(slots.data(), nChunks, fpw);
-    if (nChunks >= 64 && srcs != nullptr)
+    uint32_t nChunks = planChunks(jobs, nJobs, srcs, fpw, slots, o.handoff, o.framesPerChunk, o.keepAllTails, 0);
+    uint32_t imgDw = imageDwords(slots.data(), nChunks, fpw);
+    if (o.places != 0 && nChunks >= 64 && srcs != nullptr)
     {
         std::vector<uint32_t> hist(dcsPoolCapacity(fpw) / 32 + 2, 0);
         for (uint32_t c = 0 ; c < nChunks ; ++c)
@@ -332,17 +292,17 @@ static uint32_t planChunksCapped(const DcsFrameJob *jobs, uint32_t nJobs, const 
             }
         }
         // (the cap is a target, not a limit: an empty chunk takes its first frame -- and a halo with its successor -- whatever
-        // their size, and the image is sized by what the plan really holds, dcsImageDwords)
+        // their size, and the image is sized by what the plan really holds, imageDwords)
         if (cap >= 32 && cap + 32 <= imgDw)
         {
             std::vector<DcsSlot> again;
-            const uint32_t n2 = planChunks(jobs, nJobs, srcs, fpw, again, handoff, framesPerChunk, depthOrder, keepAllTails, cap);
-            const uint32_t img2 = dcsImageDwords(again.data(), n2, fpw);
-            // Taken when the packages really get shorter in total -- and the launch no longer: `places` wavefronts run at a time
-            // (0: unknown), a launch lasts as many generations of them as it has chunks, and the chunks closed early must not
+            const uint32_t n2 = planChunks(jobs, nJobs, srcs, fpw, again, o.handoff, o.framesPerChunk, o.keepAllTails, cap);
+            const uint32_t img2 = imageDwords(again.data(), n2, fpw);
+            // Taken when the packages really get shorter in total -- and the launch no longer: o.places wavefronts run at a time,
+            // a launch lasts as many generations of them as it has chunks, and the chunks closed early must not
             // open another one (measured, round 5: 65 536 frames = 8 192 chunks = exactly two generations, 33.4 us; the same
             // frames in 8 216 chunks 36.2)
-            const bool sameGenerations = places == 0 || (n2 + places - 1) / places == (nChunks + places - 1) / places;
+            const bool sameGenerations = (n2 + o.places - 1) / o.places == (nChunks + o.places - 1) / o.places;
             if (sameGenerations && static_cast<uint64_t>(n2) * dcsPkgStride(fpw, img2) < static_cast<uint64_t>(nChunks) * dcsPkgStride(fpw, imgDw))
             {
                 slots.swap(again);
@@ -351,28 +311,18 @@ static uint32_t planChunksCapped(const DcsFrameJob *jobs, uint32_t nJobs, const 
             }
         }
     }
-    if (imgDwOut != nullptr)
-        *imgDwOut = imgDw;
-    return nChunks;
+    return DcsPlan{ nChunks, imgDw };
 }
-uint32_t dcsPlanChunksCapped(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff,
-                             int framesPerChunk, bool depthOrder, bool keepAllTails, uint32_t *imgDwOut, uint32_t places)
+DcsPlan dcsPlanJobs(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, int fpw, std::vector<DcsSlot> &slots, const DcsPlanOptions &o)
 {
-    return planChunksCapped(jobs, nJobs, srcs, fpw, slots, handoff, framesPerChunk, depthOrder, keepAllTails, imgDwOut, places);
+    return planJobs(jobs, nJobs, srcs, fpw, slots, o);
 }
-uint32_t dcsPlanChunksCappedLite(const DcsFrameJob *jobs, uint32_t nJobs, const DcsPlanSrc *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff,
-                                 int framesPerChunk, bool depthOrder, bool keepAllTails, uint32_t *imgDwOut, uint32_t places)
+DcsPlan dcsPlanJobs(const DcsFrameJob *jobs, uint32_t nJobs, const DcsPlanSrc *srcs, int fpw, std::vector<DcsSlot> &slots, const DcsPlanOptions &o)
 {
-    return planChunksCapped(jobs, nJobs, srcs, fpw, slots, handoff, framesPerChunk, depthOrder, keepAllTails, imgDwOut, places);
+    return planJobs(jobs, nJobs, srcs, fpw, slots, o);
 }
 
-uint32_t dcsPlanChunksLite(const DcsFrameJob *jobs, uint32_t nJobs, const DcsPlanSrc *srcs, int fpw, std::vector<DcsSlot> &slots, bool handoff,
-                           int framesPerChunk, bool depthOrder, bool keepAllTails)
-{
-    return planChunks(jobs, nJobs, srcs, fpw, slots, handoff, framesPerChunk, depthOrder, keepAllTails, 0);
-}
-
-// every source the jobs draw on is a 1994+ frame (the packages then carry 4-byte split records, dcs_common.h)
+// every source the jobs draw on is a 1994+ frame (the packages then carry 4-byte split records, dcs_package.h)
 bool dcsAllSources94(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs)
 {
     if (srcs == nullptr)
@@ -384,22 +334,6 @@ bool dcsAllSources94(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *
     return true;
 }
 
-uint32_t dcsImageDwords(const DcsSlot *slots, uint32_t nChunks, int fpw)
-{
-    uint32_t use = 0;
-    for (size_t i = 0, n = static_cast<size_t>(nChunks) * static_cast<size_t>(fpw) ; i < n ; ++i)
-        if (slots[i].runNDw != 0)
-        {
-            const uint32_t end = static_cast<uint32_t>(slots[i].runPoolOff) + slots[i].runNDw;
-            if (end > use)
-                use = end;
-        }
-    const uint32_t cap = dcsPoolCapacity(fpw);
-    use = (use + 31u) & ~31u;
-    if (use < 32u) use = 32u;           // (the kernel's image loads clamp to imgDw - 4)
-    return use < cap ? use : cap;
-}
-
 extern "C" DcsStatus dcs_plan_chunks2(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, int fpw, int handoff,
                                       uint64_t *slotsOut, size_t cap, uint32_t *nChunksOut)
 {
@@ -407,7 +341,7 @@ extern "C" DcsStatus dcs_plan_chunks2(const DcsFrameJob *jobs, uint32_t nJobs, c
         return DCS_ERR_INVALID_ARG;
     std::vector<DcsSlot> slots;
     // (the plan of a RESIDENT batch, dcs_batch_create: planned for the shortest packages)
-    *nChunksOut = dcsPlanChunksCapped(jobs, nJobs, srcs, fpw, slots, handoff != 0, 0, true, false, nullptr, DCS_MI355X_WAVE_PLACES);
+    *nChunksOut = dcsPlanJobs(jobs, nJobs, srcs, fpw, slots, DcsPlanOptions{ handoff != 0, 0, false, DCS_MI355X_WAVE_PLACES }).nChunks;
     if (slotsOut != nullptr)
     {
         if (cap < slots.size())
@@ -426,7 +360,7 @@ extern "C" DcsStatus dcs_plan_chunks(const DcsFrameJob *jobs, uint32_t nJobs, co
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Chunk packages (dcs_common.h): everything unpack round 0 of a chunk needs, gathered next to each other on the
+// Chunk packages (dcs_package.h): everything unpack round 0 of a chunk needs, gathered next to each other on the
 // host while the batch is being prepared -- slots, descriptor heads, stream headers (aligned), the split record of
 // every lane, and the compressed bytes of the chunk's runs as an image of the LDS bit pool, dwords in bit order
 // (big-endian).  A layout change only; nothing is decoded.  The device then reads nothing else in round 0.
@@ -435,7 +369,6 @@ static void packChunks(const DcsSlot *slots, uint32_t c0, uint32_t c1, int fpw, 
                        const uint8_t *blob, size_t blobLen, uint8_t *out, uint32_t layout)
 {
     const uint32_t pkgBytes = dcsPkgStride(fpw, layout);
-    const uint32_t poolCap = dcsPkgImgDw(layout);
     const bool split4 = (layout & DCS_PKG_SPLIT4) != 0;
     const int sub = 64 / fpw;
     for (uint32_t c = c0 ; c < c1 ; ++c)
@@ -445,62 +378,20 @@ static void packChunks(const DcsSlot *slots, uint32_t c0, uint32_t c1, int fpw, 
         memset(pkg, 0, pkgBytes);
         for (int s = 0 ; s < fpw ; ++s)
         {
-            const DcsSlot &sl = cs[s];
-            uint8_t *ps = pkg + static_cast<size_t>(s) * DCS_PKG_SLOT_BYTES;
-            memcpy(ps, &sl, 16);                            // job, prevSlot | flags | nSrc | shiftXform, firstSrc, prevJob
-            memcpy(ps + 56, &sl.poolOff, 2);
-            ps[58] = sl.bpl;
-            memcpy(ps + 60, &sl.nextJob, 4);
-            if ((sl.flags & DCS_SLOT_EMPTY) || sl.nSrc == 0 || srcs == nullptr)
-                continue;
-            const DcsSrcDesc &sd = srcs[sl.firstSrc];
-            memcpy(ps + 16, &sd, 40);
-            uint8_t *hd = ps + 64;
-            const size_t hOff = static_cast<size_t>(sd.streamOff) + 2;
-            const size_t hLen = sd.hdrLen == 1 ? 1 : 16;
-            for (size_t i = 0 ; i < hLen ; ++i)
-                hd[i] = hOff + i < blobLen ? blob[hOff + i] : 0;
-            // Which header bands the frame's q-th unpack lane (lane = s + q * fpw) takes (dcsLaneFirstBand): its first band
-            // travels in bits 12..15 of the state word of the lane's split record (the record of that band's start,
-            // split[band - 1]); a lane without bands has bit 15 of bitDelta set.
-            const int bpl = sl.bpl;
-            if (bpl == 0)
-                continue;                                   // one lane unpacks the whole frame
-            const int nb16 = sd.idx.nBands < 16 ? sd.idx.nBands : 16;
-            const int nbEnd = dcsDealEnd(sd.format, sd.idx.nBands);
-            int base[17];
-            for (int q = 0 ; q <= sub ; ++q)
-                base[q] = dcsLaneFirstBand(sd.format, q, bpl, nbEnd);
-            for (int q = 1 ; q < sub ; ++q)
+            const DcsPkgSrc sd = dcsPkgSrcOf(cs[s], srcs);
+            uint32_t entry[DCS_PKG_SLOT_DWORDS];
+            dcsPkgSlotEntry(entry, cs[s], sd, blob, blobLen);
+            memcpy(pkg + static_cast<size_t>(s) * DCS_PKG_SLOT_BYTES, entry, DCS_PKG_SLOT_BYTES);
+            // the split record of the frame's q-th unpack lane (lane = s + q * fpw); the first lane's stays zero
+            for (int q = 1 ; q < sub && sd.rec != nullptr ; ++q)
             {
-                DcsSplit rec;
-                memset(&rec, 0, sizeof(rec));
-                if (q == sub - 1 && dcsMid15(sd.format, bpl, nb16, sd.idx.split[14].prv))
-                {
-                    // the second half of band 15 (1994+, one band per lane)
-                    rec.bitDelta = sd.idx.split[14].prv;
-                    rec.state = static_cast<uint16_t>((sd.idx.split[14].prvDelta & 0x3FFu) | DCS_SPLIT_MID15 | (15u << 12));
-                }
-                else if (base[q] >= nbEnd)
-                    rec.bitDelta = 0x8000u;                 // no bands for this lane
-                else if (base[q] >= 16)
-                {
-                    // OS93a Type 1, bands 16 and 17: their records travel in the frame record's bandType bytes
-                    memcpy(&rec, sd.idx.bandType + (base[q] - 16) * 8, 8);
-                    rec.state = static_cast<uint16_t>((rec.state & 0x0DFFu) | DCS_SPLIT_BASE16 | (static_cast<unsigned>(base[q] - 16) << 12));
-                }
-                else
-                {
-                    rec = sd.idx.split[base[q] - 1];
-                    rec.state = static_cast<uint16_t>((rec.state & 0x0FFFu) | (static_cast<unsigned>(base[q]) << 12));
-                }
+                uint32_t r[2];
+                dcsLaneSplit(r, sd, cs[s].bpl, q, sub);
+                const uint32_t r4 = dcsLaneSplit4(r);
                 if (split4)
-                {
-                    const uint32_t w = static_cast<uint32_t>(rec.bitDelta) | (static_cast<uint32_t>(rec.state) << 16);
-                    memcpy(pkg + dcsPkgOffSplit(fpw) + static_cast<size_t>(s + q * fpw) * 4, &w, 4);
-                }
+                    memcpy(pkg + dcsPkgOffSplit(fpw) + static_cast<size_t>(s + q * fpw) * 4, &r4, 4);
                 else
-                    memcpy(pkg + dcsPkgOffSplit(fpw) + static_cast<size_t>(s + q * fpw) * 8, &rec, 8);
+                    memcpy(pkg + dcsPkgOffSplit(fpw) + static_cast<size_t>(s + q * fpw) * 8, r, 8);
             }
         }
         uint8_t *img = pkg + dcsPkgOffPool(fpw, layout);
@@ -509,22 +400,17 @@ static void packChunks(const DcsSlot *slots, uint32_t c0, uint32_t c1, int fpw, 
             const uint32_t n = cs[k].runNDw, st = cs[k].runStartDw, o = cs[k].runPoolOff;
             if (n == 0)
                 break;
-            if (o + n > poolCap)
-                continue;                                   // cannot happen: imgDw covers every run of the plan (dcsImageDwords)
-            // dword w of the blob in bit order = its four bytes as they come; bytes past the blob read as zero
-            const size_t b0 = static_cast<size_t>(st) * 4, bytes = static_cast<size_t>(n) * 4;
-            uint8_t *dst = img + static_cast<size_t>(o) * 4;
-            const size_t avail = b0 < blobLen ? (blobLen - b0 < bytes ? blobLen - b0 : bytes) : 0;
-            // the image is an array of uint32 on a little-endian machine: byte j of the stream goes to byte (j ^ 3)
-            for (size_t j = 0 ; j + 4 <= avail ; j += 4)
+            if (o + n > dcsPkgImgDw(layout))
+                continue;                                   // cannot happen: the image covers every run of the plan (imageDwords)
+            // (the dwords that lie wholly inside the blob without a bounds check each)
+            const uint64_t blobDw = blobLen / 4;
+            const uint32_t nIn = st + static_cast<uint64_t>(n) <= blobDw ? n : st < blobDw ? static_cast<uint32_t>(blobDw - st) : 0u;
+            for (uint32_t i = 0 ; i < n ; ++i)
             {
-                uint32_t w;
-                memcpy(&w, blob + b0 + j, 4);
-                w = __builtin_bswap32(w);
-                memcpy(dst + j, &w, 4);
+                const uint64_t dw = static_cast<uint64_t>(st) + i;
+                const uint32_t w = i < nIn ? dcsImageDwordInside(blob, dw) : dcsImageDword(blob, blobLen, dw);
+                memcpy(img + (static_cast<size_t>(o) + i) * 4, &w, 4);
             }
-            for (size_t j = avail & ~static_cast<size_t>(3) ; j < avail ; ++j)
-                dst[j ^ 3] = blob[b0 + j];
         }
     }
 }
@@ -561,10 +447,9 @@ extern "C" DcsStatus dcs_pack_chunks(const DcsFrameJob *jobs, uint32_t nJobs, co
     if (jobs == nullptr || srcs == nullptr || nChunksOut == nullptr || !(fpw == 4 || fpw == 8 || fpw == 16))
         return DCS_ERR_INVALID_ARG;
     std::vector<DcsSlot> slots;
-    uint32_t imgDw = 0;
-    const uint32_t nChunks = dcsPlanChunksCapped(jobs, nJobs, srcs, fpw, slots, true, 0, true, false, &imgDw, DCS_MI355X_WAVE_PLACES);
-    *nChunksOut = nChunks;
-    const uint32_t layout = imgDw | (dcsAllSources94(jobs, nJobs, srcs) ? DCS_PKG_SPLIT4 : 0u);
+    const DcsPlan plan = dcsPlanJobs(jobs, nJobs, srcs, fpw, slots, DcsPlanOptions{ true, 0, false, DCS_MI355X_WAVE_PLACES });
+    const uint32_t nChunks = *nChunksOut = plan.nChunks;
+    const uint32_t layout = plan.imgDw | (dcsAllSources94(jobs, nJobs, srcs) ? DCS_PKG_SPLIT4 : 0u);
     if (packageBytesOut != nullptr)
         *packageBytesOut = dcsPkgStride(fpw, layout);
     if (out == nullptr)

@@ -327,7 +327,7 @@ struct DcsBatch
     uint32_t *dErr = nullptr;               // nJobs error words: in dErrOwn or behind the PCM in dPcm
     uint32_t epoch = 0;                     // launches of this batch so far
     uint32_t flags = 0;                     // DCS_BATCH_*
-    uint32_t imgDw = 0;                     // the packages' LAYOUT word (dcs_common.h): dwords of pool image | DCS_PKG_SPLIT4; packages at dcsPkgStride(fpw, imgDw)
+    uint32_t imgDw = 0;                     // the packages' LAYOUT word (dcs_package.h): dwords of pool image | DCS_PKG_SPLIT4; packages at dcsPkgStride(fpw, imgDw)
     // packages assembled on the device: the plan and the source digests as uploaded for the pack kernel, and the pinned staging
     // they (or the device planner's stream table, behind its flag word) went up through
     CacheBuf dPlanSlots, dPlanSrcs, hStage;
@@ -918,15 +918,11 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
     batchBytes(b, (payloadBits + 7) / 8, streamHeaderBytes(srcs, nSrcs));
 
     thread_local std::vector<DcsSlot> slots;    // (kept from batch to batch: see the pipeline's scratch)
-    const bool allTails = ctx->keepAllTails || o.keepAllTails;
-    if (o.resident)
-        b->nChunks = dcsPlanChunksCapped(jobs, nJobs, srcs, b->fpw, slots, o.handoff, ctx->framesPerChunk, !ranges, allTails, &b->imgDw,
-                                          static_cast<uint32_t>(ctx->numCUs) * 16u);
-    else
-    {
-        b->nChunks = dcsPlanChunks(jobs, nJobs, srcs, b->fpw, slots, o.handoff, ctx->framesPerChunk, !ranges, allTails);
-        b->imgDw = dcsImageDwords(slots.data(), b->nChunks, b->fpw);
-    }
+    // (a resident batch is planned for the shortest packages: `places`, dcs_plan.cpp)
+    const DcsPlanOptions po{ o.handoff, ctx->framesPerChunk, ctx->keepAllTails || o.keepAllTails, o.resident ? static_cast<uint32_t>(ctx->numCUs) * 16u : 0u };
+    const DcsPlan plan = dcsPlanJobs(jobs, nJobs, srcs, b->fpw, slots, po);
+    b->nChunks = plan.nChunks;
+    b->imgDw = plan.imgDw;
     dcsShuffleChunks(slots, b->nChunks, b->fpw, ctx->shuffleSeed);          // (test hook)
     if (dcsAllSources94(jobs, nJobs, srcs))
         b->imgDw |= DCS_PKG_SPLIT4;             // (the layout word: every source a 1994+ frame -> 4-byte split records)
@@ -974,297 +970,8 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
     return batchDone(b, st, out);
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// The packer on the device: the same packages dcsBuildPackages (dcs_plan.cpp) lays out on the host, assembled by one
-// wavefront per chunk from what is already resident -- the index records the device index pass left there, the streams
-// as uploaded for that pass -- and the plan the host made from an 8-byte-per-frame digest.  Byte for byte the same
-// packages (tests/test_gpu_corpus.py compares them).  The packages buffer is zeroed beforehand.
-// ---------------------------------------------------------------------------------------------------------
-namespace {
-template <int FPW>
-__global__ __launch_bounds__(256) void dcsPackKernel(const DcsSlot *slots, uint32_t nChunks, const DcsPlanSrc *srcs,
-                                                      const DcsFrameIndex *records, const uint8_t *blob, uint64_t blobLen,
-                                                      uint8_t *packages, uint32_t layout)
-{
-    const uint32_t chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = static_cast<int>(threadIdx.x & 63);
-    if (chunk >= nChunks)
-        return;
-    uint8_t *pkg = packages + static_cast<size_t>(chunk) * dcsPkgStride(FPW, layout);
-    const DcsSlot *cs = slots + static_cast<size_t>(chunk) * FPW;
-    const uint32_t imgDw = dcsPkgImgDw(layout);
-    const bool split4 = (layout & DCS_PKG_SPLIT4) != 0;
-    // (order: the image first -- its loads need nothing but the plan's slots, and a wavefront issues its loads in program order: behind the
-    // slot -> source -> record chain of the descriptors they waited for three round trips before they were even asked for)
-    // the image of the bit pool: the chunk's runs of stream dwords, in bit order; zero between them (the runs lie one behind the
-    // other, each on a 16-byte boundary: gaps of at most three dwords) and behind the last one
-    uint32_t *img = reinterpret_cast<uint32_t *>(pkg + dcsPkgOffPool(FPW, layout));
-    uint32_t end = 0;
-    for (int k = 0 ; k < FPW ; ++k)
-    {
-        const uint32_t n = cs[k].runNDw, st = cs[k].runStartDw, o = cs[k].runPoolOff;
-        if (n == 0)
-            break;
-        if (o + n > imgDw || o < end)
-            continue;                           // (cannot happen: the image covers every run of the plan, in order)
-        for (uint32_t i = end + static_cast<uint32_t>(lane) ; i < o ; i += 64)
-            img[i] = 0;
-        // (four dwords a lane where the run and the blob have them: the run starts on a 16-byte boundary of the image, the stream
-        // bytes on a dword boundary only)
-        const uint32_t n4 = (static_cast<uint64_t>(st) + n) * 4 <= blobLen ? n & ~3u : 0u;
-        for (uint32_t i = static_cast<uint32_t>(lane) * 4 ; i < n4 ; i += 256)
-        {
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(blob + (static_cast<uint64_t>(st) + i) * 4);
-            const uint32_t w0 = src[0], w1 = src[1], w2 = src[2], w3 = src[3];
-            *reinterpret_cast<uint4 *>(img + o + i) = make_uint4(__builtin_bswap32(w0), __builtin_bswap32(w1), __builtin_bswap32(w2), __builtin_bswap32(w3));
-        }
-        for (uint32_t i = n4 + static_cast<uint32_t>(lane) ; i < n ; i += 64)
-        {
-            const uint64_t b0 = (static_cast<uint64_t>(st) + i) * 4;
-            uint32_t w = 0;
-            if (b0 + 4 <= blobLen)
-                w = __builtin_bswap32(*reinterpret_cast<const uint32_t *>(blob + b0));
-            else
-                for (int j = 0 ; j < 4 ; ++j)
-                    if (b0 + j < blobLen)
-                        w |= static_cast<uint32_t>(blob[b0 + j]) << (24 - 8 * j);
-            img[o + i] = w;
-        }
-        end = o + n;
-    }
-    {
-        // (behind the last run: dwords up to the next 16-byte boundary, then sixteen bytes a lane)
-        const uint32_t end4 = (end + 3u) & ~3u;
-        for (uint32_t i = end + static_cast<uint32_t>(lane) ; i < end4 && i < imgDw ; i += 64)
-            img[i] = 0;
-        for (uint32_t i = end4 + static_cast<uint32_t>(lane) * 4 ; i + 4 <= imgDw ; i += 256)
-            *reinterpret_cast<uint4 *>(img + i) = make_uint4(0, 0, 0, 0);
-        for (uint32_t i = (imgDw & ~3u) + static_cast<uint32_t>(lane) ; i < imgDw ; i += 64)
-            if (i >= end4)
-                img[i] = 0;
-    }
-    // EVERY byte of the package is written here, once (round 5: the buffer used to be cleared first, 700 MB of writes in front of
-    // the packer for 2 M frames): what does not apply is written as zero, as the host packer's memset leaves it.
-    // slot `lane`: its first 16 bytes, the descriptor head (the first 40 bytes of what DcsSrcDesc would be) with poolOff and bpl
-    // behind it, the stream header (dcs_common.h: five 16-byte pieces per slot)
-    if (lane < FPW)
-    {
-        const DcsSlot sl = cs[lane];
-        uint4 *ps = reinterpret_cast<uint4 *>(pkg + static_cast<size_t>(lane) * DCS_PKG_SLOT_BYTES);
-        uint32_t d[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, h[4] = { 0, 0, 0, 0 };
-        if (!(sl.flags & DCS_SLOT_EMPTY) && sl.nSrc != 0)
-        {
-            const DcsPlanSrc sd = srcs[sl.firstSrc];
-            const uint32_t *rec = reinterpret_cast<const uint32_t *>(&records[sd.record]);
-            d[0] = static_cast<uint32_t>(sd.streamOff);
-            d[1] = static_cast<uint32_t>(sd.streamOff >> 32);
-            d[2] = static_cast<uint32_t>(sd.mixMul) | (static_cast<uint32_t>(sd.format) << 16) | (static_cast<uint32_t>(sd.hdrLen) << 24);
-#pragma unroll
-            for (int i = 0 ; i < 7 ; ++i)
-                d[3 + i] = rec[i];              // bitOff, nBits | hdrBits, bandType[16], preAdj | nBands | flags
-            const uint64_t hOff = sd.streamOff + 2;
-            const uint32_t hLen = sd.hdrLen == 1 ? 1u : 16u;
-#pragma unroll
-            for (uint32_t i = 0 ; i < 16 ; ++i)
-                if (i < hLen && hOff + i < blobLen)
-                    h[i >> 2] |= static_cast<uint32_t>(blob[hOff + i]) << (8 * (i & 3));
-        }
-        ps[0] = reinterpret_cast<const uint4 *>(&cs[lane])[0];
-        ps[1] = make_uint4(d[0], d[1], d[2], d[3]);
-        ps[2] = make_uint4(d[4], d[5], d[6], d[7]);
-        ps[3] = make_uint4(d[8], d[9], static_cast<uint32_t>(sl.poolOff) | (static_cast<uint32_t>(sl.bpl) << 16), sl.nextJob);
-        ps[4] = make_uint4(h[0], h[1], h[2], h[3]);
-    }
-    // the lane's own record: first band and split record of the frame's q-th unpack lane (zero where there is none)
-    {
-        constexpr int SUB = 64 / FPW;
-        const int sI = lane % FPW, q = lane / FPW;
-        const DcsSlot sl = cs[sI];
-        uint32_t r0 = 0, r1 = 0;
-        if (q >= 1 && q < SUB && !(sl.flags & DCS_SLOT_EMPTY) && sl.nSrc != 0 && sl.bpl != 0)
-        {
-            const DcsPlanSrc sd = srcs[sl.firstSrc];
-            const int nb16 = sd.nBands < 16 ? sd.nBands : 16;
-            const int nbEnd = dcsDealEnd(sd.format, sd.nBands);
-            const int base = dcsLaneFirstBand(sd.format, q, sl.bpl, nbEnd);
-            r0 = 0x8000u;                       // bitDelta bit 15: no bands for this lane
-            const uint32_t *mid = reinterpret_cast<const uint32_t *>(&records[sd.record].split[14]);
-            if (q == SUB - 1 && dcsMid15(sd.format, sl.bpl, nb16, mid[0] >> 16))
-            {
-                // the second half of band 15 (1994+, one band per lane)
-                r0 = mid[0] >> 16;
-                r1 = ((mid[1] & 0x3FFu) | DCS_SPLIT_MID15 | (15u << 12)) << 16;
-            }
-            else if (base >= nbEnd)
-                ;
-            else if (base >= 16)
-            {
-                // OS93a Type 1, bands 16 and 17: their records travel in the frame record's bandType bytes (at byte 8 of
-                // the record, so dword-aligned)
-                const uint32_t *sp = reinterpret_cast<const uint32_t *>(records[sd.record].bandType) + 2 * (base - 16);
-                r0 = sp[0];
-                r1 = (sp[1] & 0x0DFFFFFFu) | (DCS_SPLIT_BASE16 << 16) | (static_cast<uint32_t>(base - 16) << 28);
-            }
-            else
-            {
-                const uint32_t *sp = reinterpret_cast<const uint32_t *>(&records[sd.record].split[base - 1]);
-                r0 = sp[0];
-                r1 = (sp[1] & 0x0FFFFFFFu) | (static_cast<uint32_t>(base) << 28);
-            }
-        }
-        if (split4)
-            reinterpret_cast<uint32_t *>(pkg + dcsPkgOffSplit(FPW))[lane] = (r0 & 0xFFFFu) | (r1 & 0xFFFF0000u);
-        else
-            reinterpret_cast<uint2 *>(pkg + dcsPkgOffSplit(FPW))[lane] = make_uint2(r0, r1);
-    }
-    // (the bytes between the split records and the image's 128-byte boundary)
-    {
-        const uint32_t padFrom = dcsPkgOffSplit(FPW) + 64u * dcsPkgSplitBytes(layout), padTo = dcsPkgOffPool(FPW, layout);
-        for (uint32_t i = padFrom / 4 + static_cast<uint32_t>(lane) ; i < padTo / 4 ; i += 64)
-            reinterpret_cast<uint32_t *>(pkg)[i] = 0;
-    }
-}
-}   // namespace
-
-// ---------------------------------------------------------------------------------------------------------
-// The planner on the device, for lists of WHOLE STREAMS (the pipeline's third step onto the device: the index records never
-// leave it, and the host neither waits for them nor plans).  The job list of such a list is regular -- stream k's frames
-// f = 0 .. nFrames + extraFrames - 1 one after the other, each the successor of the one before -- so the chunk plan is
-// arithmetic: chunk c holds jobs c * FPW .. c * FPW + FPW - 1, a frame whose predecessor lies in the chunk before imports
-// its tail from there.  One thread per chunk writes the chunk's slots (run placement as the host planner does it,
-// dcs_plan.cpp: placeFrame) and the source digests of its frames.  What the arithmetic plan cannot express is reported in
-// a flag word and the list then takes the host planner's path: a chunk whose compressed bytes overflow the bit pool (the
-// host planner closes such a chunk early), a stream whose frames run past its buffer.  A stream the index pass stopped
-// early (nValidFrames < nFrames) needs no flag: its remaining frames are silent here as there.
-// ---------------------------------------------------------------------------------------------------------
-namespace {
-template <int FPW>
-__global__ __launch_bounds__(256) void dcsPlanKernel(const DcsPlanStream *streams, uint32_t nStreams, uint32_t extraFrames, uint32_t nJobs,
-                                                      const DcsFrameIndex *records, const DcsStreamInfo *infos,
-                                                      DcsSlot *slots, DcsPlanSrc *srcs, uint32_t *flagWord, uint32_t *hostFlag, uint32_t fpc)
-{
-    // fpc: frames a chunk holds, FPW or -- for a list whose frames are too large for FPW of them to share the bit pool -- fewer (the
-    // chunk's other slots stay empty): chunk c holds jobs c * fpc .. c * fpc + fpc - 1
-    const uint32_t nChunks = (nJobs + fpc - 1) / fpc;
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nChunks)
-        return;
-    // the stream of the chunk's first job: the last stream whose first job is not behind it
-    uint32_t lo = 0, hi = nStreams - 1;
-    const uint32_t j0 = c * fpc;
-    while (lo < hi)
-    {
-        const uint32_t mid = (lo + hi + 1) / 2;
-        if (streams[mid].firstJob <= j0) lo = mid; else hi = mid - 1;
-    }
-    uint32_t k = lo;
-    DcsPlanStream st = streams[k];
-    uint32_t nValid = min(static_cast<uint32_t>(infos[k].nValidFrames), st.nFrames);
-    uint32_t flags = 0;
-
-    DcsSlot out[FPW];
-    uint32_t nRuns = 0, runUse = 0, poolUse = 0, curStart = 0, curN = 0, curOff = 0;    // cur*: the chunk's last run
-    const DcsSlot empty{ 0xFFFFFFFFu, DCS_NO_PREV_SLOT, DCS_SLOT_EMPTY, 0, 0, 0, DCS_PREV_NONE, 0, 0, 0, 0, 0, 0, 0 };
-    for (int p = 0 ; p < FPW ; ++p)
-    {
-        const uint32_t j = j0 + static_cast<uint32_t>(p);
-        if (j >= nJobs || static_cast<uint32_t>(p) >= fpc) { out[p] = empty; continue; }
-        while (k + 1 < nStreams && j >= streams[k + 1].firstJob)
-        {
-            ++k;
-            st = streams[k];
-            nValid = min(static_cast<uint32_t>(infos[k].nValidFrames), st.nFrames);
-        }
-        const uint32_t f = j - st.firstJob, framesOut = st.nFrames + extraFrames;
-        const bool has = f < nValid;
-        if (f == 0)
-        {
-            // (what counts is the bits the frames occupy, not nBytes, which includes the reference reader's look-ahead)
-            const DcsStreamInfo in = infos[k];
-            if (in.nFrames == 0 || 2u + static_cast<uint32_t>(in.hdrLen) + (in.payloadBits + 7) / 8 > st.len)
-                flags |= DCS_PLAN_TRUNCATED;
-        }
-        DcsSlot sl{ j, DCS_NO_PREV_SLOT, 0, static_cast<uint8_t>(has ? 1 : 0),
-                    static_cast<uint8_t>((has ? (f == 0 ? st.volShift0 : st.volShiftN) : 8) | (st.xform << 4)),
-                    has ? st.firstRecord + f : 0u, f == 0 ? DCS_PREV_NONE : j - 1, 0, 0, 0, 0, 0, 0, 0 };
-        if (f != 0)
-        {
-            if (p != 0)
-                sl.prevSlot = static_cast<uint8_t>(p - 1);
-            else
-            {
-                sl.flags |= DCS_SLOT_IMPORT;            // the chunk before publishes the tail (its last frame is this one's predecessor)
-                sl.prevJob = c - 1;
-            }
-        }
-        if ((static_cast<uint32_t>(p) == fpc - 1 || j + 1 == nJobs) && f + 1 < framesOut && j + 1 < nJobs)
-        {
-            sl.flags |= DCS_SLOT_EXPORT;
-            sl.nextJob = j + 1;                     // (the stream's next frame: the first job of the next chunk)
-        }
-        if (f + 1 == framesOut)
-            sl.flags |= DCS_SLOT_KEEP_TAIL;         // the last frame of its chain (dcs_plan.cpp)
-        if (has)
-        {
-            const uint32_t *rec = reinterpret_cast<const uint32_t *>(&records[st.firstRecord + f]);
-            const uint32_t bitOff = rec[0], nBits = rec[1] & 0xFFFFu, nBands = (rec[6] >> 16) & 0xFFu, fl = rec[6] >> 24;
-            const uint32_t sub = 64 / FPW, nb16 = nBands < 16 ? nBands : 16;
-            const uint32_t bpl = (nb16 + sub - 1) / sub;
-            sl.bpl = (fl & DCS_IDX_SERIAL) ? 0 : static_cast<uint8_t>(bpl < 1 ? 1 : bpl);
-            // where the frame's bytes go in the pool: it extends the chunk's last run or opens a new one (placeFrame, dcs_plan.cpp)
-            const uint64_t bitPos = (st.streamOff + 2 + st.hdrLen) * 8 + bitOff;
-            const uint32_t s0 = static_cast<uint32_t>(bitPos >> 5);
-            const uint32_t n = dcsPoolDwords(st.streamOff, st.hdrLen, bitOff, nBits);
-            if (nRuns != 0 && s0 >= curStart && s0 <= curStart + curN)
-                curN = max(curN, s0 + n - curStart);
-            else
-            {
-                curStart = s0; curN = n; curOff = runUse;
-                ++nRuns;
-            }
-            runUse = curOff + ((curN + 3) & ~3u);
-            sl.poolOff = static_cast<uint16_t>(curOff + (s0 - curStart));
-            poolUse += (n + 3) & ~3u;
-            srcs[st.firstRecord + f] = DcsPlanSrc{ st.streamOff, bitOff, static_cast<uint16_t>(nBits), st.hdrLen, static_cast<uint8_t>(nBands),
-                                                   static_cast<uint8_t>(fl), st.format, f == 0 ? st.mixMul0 : st.mixMulN, st.firstRecord + f };
-        }
-        out[p] = sl;
-        if (has)
-            for (int r = 0 ; r <= p ; ++r)                  // slot k carries run k (constant subscripts: the slots stay in registers)
-                if (static_cast<uint32_t>(r) + 1 == nRuns)
-                {
-                    out[r].runStartDw = curStart;
-                    out[r].runNDw = static_cast<uint16_t>(curN);
-                    out[r].runPoolOff = static_cast<uint16_t>(curOff);
-                }
-    }
-    if (poolUse > dcsPoolCapacity(FPW) || runUse > dcsPoolCapacity(FPW))
-        flags |= DCS_PLAN_POOL_OVERFLOW;
-    for (int p = 0 ; p < FPW ; ++p)
-        slots[static_cast<size_t>(c) * FPW + p] = out[p];
-    if (flags != 0)
-    {
-        const uint32_t seen = atomicOr(flagWord, flags);
-        // ... and straight into the batch's pinned staging word, so that no copy kernel has to bring it down behind the decode
-        // launch.  A plain store of everything this thread knows raised (its own bits and those the device word held before):
-        // non-zero is all the host needs for the PCM to be safe; concurrent writers can still hide each other's bits, which
-        // is why the host retries only on "overflow and NOT truncated" and treats the word as "at least these" 
-        if (hostFlag != nullptr)
-            __hip_atomic_store(hostFlag, seen | flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-}   // namespace
-
-// one wavefront per chunk, four to a workgroup (dcsPackKernel above)
-static hipError_t launchPack(int fpw, hipStream_t stream, const DcsSlot *slots, uint32_t nChunks, const DcsPlanSrc *srcs, const DcsFrameIndex *records,
-                             const uint8_t *blob, uint64_t blobLen, uint8_t *packages, uint32_t layout)
-{
-    withFpw(fpw, [&](auto w) {
-        constexpr int W = decltype(w)::value;
-        hipLaunchKernelGGL(dcsPackKernel<W>, dim3((nChunks + 3) / 4), dim3(256), 0, stream, slots, nChunks, srcs, records, blob, blobLen, packages, layout);
-    });
-    return hipGetLastError();
-}
+// the planner and the packer on the device, and what queues them (dcsPackKernel, dcsPlanKernel, queuePlanAndPack, planTableFor)
+#include "dcs_plan_device.hip.h"
 
 // Plan on the host from source digests, pack on the device: `dRecords` (the index records as the device index pass
 // wrote them) and `dBlob` (the streams as uploaded for it) must stay valid until the pack kernel has run, i.e. until the
@@ -1288,8 +995,9 @@ static DcsStatus createBatchOnDevice(DcsCtx *ctx, const BatchOptions &o, const D
     batchBytes(b, (payloadBits + 7) / 8, streamHeaderBytes(srcs, nSrcs));
 
     thread_local std::vector<DcsSlot> slots;
-    b->nChunks = dcsPlanChunksLite(jobs, nJobs, srcs, b->fpw, slots, o.handoff, ctx->framesPerChunk, !ranges);
-    b->imgDw = dcsImageDwords(slots.data(), b->nChunks, b->fpw) | (all94 ? DCS_PKG_SPLIT4 : 0u);
+    const DcsPlan plan = dcsPlanJobs(jobs, nJobs, srcs, b->fpw, slots, DcsPlanOptions{ o.handoff, ctx->framesPerChunk, false, 0 });
+    b->nChunks = plan.nChunks;
+    b->imgDw = plan.imgDw | (all94 ? DCS_PKG_SPLIT4 : 0u);
     dcsShuffleChunks(slots, b->nChunks, b->fpw, ctx->shuffleSeed);          // (test hook)
     const DcsStatus st = [&]() -> DcsStatus {
         HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1313,108 +1021,6 @@ static DcsStatus createBatchOnDevice(DcsCtx *ctx, const BatchOptions &o, const D
         return batchOutputs(b, false, false);
     }();
     return batchDone(b, st, out);
-}
-
-namespace {
-// three ranges cleared by one launch: a (16-byte units), b (dwords), c (16-byte units)
-__global__ __launch_bounds__(256) void dcsClear3Kernel(uint4 *a, size_t nA16, uint32_t *b, size_t nB4, uint4 *c, size_t nC16)
-{
-    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x, t = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    for (size_t i = t ; i < nA16 ; i += stride) a[i] = z;
-    for (size_t i = t ; i < nB4 ; i += stride) b[i] = 0;
-    for (size_t i = t ; i < nC16 ; i += stride) c[i] = z;
-}
-}   // namespace
-
-// What a planned-on-device batch queues in front of its decode launch: error words and hand-off words cleared,
-// one thread per chunk plans (dcsPlanKernel), one wavefront per chunk packs (dcsPackKernel).  `between` (optional) is
-// recorded between planner and packer (the device-path timing, dcs_device_path_run).
-static DcsStatus queuePlanAndPack(DcsBatch *b, uint32_t nStreams, uint32_t extraFrames, const DcsFrameIndex *dRecords, const DcsStreamInfo *dInfos,
-                                  const uint8_t *dBlob, uint64_t blobLen, hipEvent_t between)
-{
-    DcsCtx *ctx = b->ctx;
-    const uint32_t nJobs = b->nJobs;
-    // error words and hand-off words cleared by ONE kernel (three hipMemsetAsync were three dispatches in a chain of
-    // ten per list; epoch 0 = never written; the planner's flag word lies behind the last chunk's hand-off words)
-    {
-        // (the packages are no longer among them: the pack kernel writes every byte of a package itself)
-        const size_t errBytes = sizeof(uint32_t) * nJobs, hoBytes = b->dHandoff.bytes();
-        const size_t total16 = (errBytes + 15) / 16 + hoBytes / 16;
-        const unsigned blocks = static_cast<unsigned>(std::min<size_t>((total16 + 255) / 256, 2048));
-        hipLaunchKernelGGL(dcsClear3Kernel, dim3(blocks), dim3(256), 0, b->stream, static_cast<uint4 *>(nullptr), static_cast<size_t>(0),
-                           b->dErr, errBytes / 4, b->dHandoff.as<uint4>(), hoBytes / 16);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    uint32_t *flagWord = reinterpret_cast<uint32_t *>(b->dHandoff.as<unsigned long long>() + static_cast<size_t>(b->nChunks) * 16) + 2;
-    const uint32_t planBlocks = (b->nChunks + 63) / 64;         // (one wavefront per workgroup: a thread's work is serial, the chunks should spread over the CUs)
-    DcsSlot *dS = b->dPlanSlots.as<DcsSlot>();
-    DcsPlanSrc *dP = b->dPlanSrcs.as<DcsPlanSrc>();
-    withFpw(b->fpw, [&](auto w) {
-        constexpr int W = decltype(w)::value;
-        hipLaunchKernelGGL(dcsPlanKernel<W>, dim3(planBlocks), dim3(64), 0, b->stream, b->dTable.as<const DcsPlanStream>(), nStreams, extraFrames, nJobs,
-                           dRecords, dInfos, dS, dP, flagWord, b->hStage.as<uint32_t>(), b->planFpc);
-    });
-    HIPCHK(ctx, hipGetLastError());
-    if (between != nullptr)
-        HIPCHK(ctx, hipEventRecord(between, b->stream));
-    HIPCHK(ctx, launchPack(b->fpw, b->stream, dS, b->nChunks, dP, dRecords, dBlob, blobLen, b->dPackages.as<uint8_t>(), b->imgDw));
-    return DCS_OK;
-}
-
-// The device planner's stream table (DcsPlanStream, 40 bytes a stream): what the host knows of every stream of a list of
-// whole streams without walking it -- where it lies in the list's blob, its layout, frame count, and the mixing parameters
-// of frame 0 and of every later frame -- and the list's totals.
-struct DcsPlanTable
-{
-    std::vector<DcsPlanStream> streams;
-    uint64_t nJobs = 0;                 // output frames
-    uint64_t payload = 0;               // bytes of the streams, headers included
-    bool all94 = true, has93aT1 = false;
-};
-// ... made from the streams as laid out in the list's blob (layoutStreams); also the first output frame of every stream (n + 1 entries)
-static DcsStatus planTableFor(const DcsStreamRef *streams, uint32_t n, uint32_t extraFrames, const DcsStreamLoc *locs, const uint64_t *firstRecord,
-                              uint64_t totalRec, DcsPlanTable &table, std::vector<uint32_t> &firstJob)
-{
-    table.streams.resize(n);
-    firstJob.resize(static_cast<size_t>(n) + 1);
-    uint64_t nJobs = 0, payload = 0;
-    bool all94 = true, has93a = false;
-    for (uint32_t k = 0 ; k < n ; ++k)
-    {
-        const DcsStreamRef &sr = streams[k];
-        const uint8_t *d = sr.data;
-        const uint32_t len = locs[k].len;
-        const uint32_t nFrames = (static_cast<uint32_t>(d[0]) << 8) | d[1];
-        const bool typeBit = (d[2] & 0x80) != 0;
-        const uint32_t h12 = (len > 3 ? d[3] : 0u) | (len > 4 ? d[4] : 0u);
-        const DcsOsVersion os = static_cast<DcsOsVersion>(sr.os);
-        DcsPlanStream &t = table.streams[k];
-        t = DcsPlanStream{};
-        t.hdrLen = (os == DCS_OS93A && typeBit) ? 1 : 16;
-        t.format = static_cast<uint8_t>(os == DCS_OS93A ? (typeBit ? DCS_FMT_93A_T1 : DCS_FMT_93_T0)
-                                      : os == DCS_OS93B ? (typeBit ? DCS_FMT_93B_T1 : DCS_FMT_93_T0)
-                                      : !typeBit ? DCS_FMT_94_T0 : (h12 & 0x80) == 0 ? DCS_FMT_94_T1_S0 : DCS_FMT_94_T1_S3);
-        t.xform = (os == DCS_OS93A || os == DCS_OS93B) ? DCS_XFORM_93 : DCS_XFORM_94;
-        all94 = all94 && t.xform == DCS_XFORM_94;
-        has93a = has93a || t.format == DCS_FMT_93A_T1;
-        t.streamOff = locs[k].off;
-        t.len = len;
-        t.firstRecord = static_cast<uint32_t>(firstRecord[k]);
-        t.firstJob = static_cast<uint32_t>(nJobs);
-        t.nFrames = nFrames;
-        uint16_t mm[2]; uint8_t vs[2];
-        const DcsStatus st = dcs_stream_params_from(os, sr.volume, sr.level, sr.channelVolume, 0x7FFF, 2, mm, vs);    // frame 0, and every later frame
-        if (st != DCS_OK)
-            return st;
-        t.mixMul0 = mm[0]; t.mixMulN = mm[1]; t.volShift0 = vs[0]; t.volShiftN = vs[1];
-        firstJob[k] = static_cast<uint32_t>(nJobs);
-        nJobs += nFrames + extraFrames;
-        payload += len;
-    }
-    firstJob[n] = static_cast<uint32_t>(nJobs);
-    table.nJobs = nJobs; table.payload = payload; table.all94 = all94; table.has93aT1 = has93a;
-    return nJobs > 0xFFFFFFFFull || totalRec > 0xFFFFFFFFull ? DCS_ERR_CAPACITY : DCS_OK;
 }
 
 // Plan AND pack on the device (dcsPlanKernel above): nothing of the list's index results is needed on the host.  `t`
@@ -1442,7 +1048,7 @@ static DcsStatus createBatchPlannedOnDevice(DcsCtx *ctx, BatchOptions o, const D
         b->planFpc = static_cast<uint32_t>(fpc >= 1 && fpc < b->fpw ? fpc : b->fpw);
     }
     b->nChunks = (nJobs + b->planFpc - 1) / b->planFpc;
-    b->imgDw = dcsPoolCapacity(b->fpw) | (t.all94 ? DCS_PKG_SPLIT4 : 0u);   // (a plan made on the device: the full image, dcs_common.h)
+    b->imgDw = dcsPoolCapacity(b->fpw) | (t.all94 ? DCS_PKG_SPLIT4 : 0u);   // (a plan made on the device: the full image, dcs_package.h)
     const size_t tableBytes = sizeof(DcsPlanStream) * nStreams;
     const DcsStatus st = [&]() -> DcsStatus {
         HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1466,62 +1072,6 @@ static DcsStatus createBatchPlannedOnDevice(DcsCtx *ctx, BatchOptions o, const D
 
 // the planner's flag word of a batch planned on the device, once its stream has been waited for
 static uint32_t batchPlanFlag(const DcsBatch *b) { return *b->hStage.as<const volatile uint32_t>(); }
-
-// Diagnostic / test entry: the packages of `jobs` as the DEVICE packer lays them out (plan from source digests on the
-// host, pack kernel on the device), for comparison with dcs_pack_chunks, the host packer.  out = NULL to size.
-extern "C" DcsStatus dcs_pack_chunks_device(DcsCtx *ctx, const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, uint32_t nSrcs,
-                                            const uint8_t *blob, size_t blobLen, int fpw,
-                                            uint8_t *out, size_t cap, uint32_t *nChunksOut, uint32_t *packageBytesOut)
-{
-    if (ctx == nullptr || jobs == nullptr || srcs == nullptr || blob == nullptr || nChunksOut == nullptr || !(fpw == 4 || fpw == 8 || fpw == 16))
-        return DCS_ERR_INVALID_ARG;
-    std::vector<DcsPlanSrc> ps(nSrcs);
-    std::vector<DcsFrameIndex> recs(nSrcs);
-    for (uint32_t k = 0 ; k < nSrcs ; ++k)
-    {
-        const DcsSrcDesc &sd = srcs[k];
-        ps[k] = DcsPlanSrc{ sd.streamOff, sd.idx.bitOff, sd.idx.nBits, sd.hdrLen, sd.idx.nBands, sd.idx.flags, sd.format, sd.mixMul, k };
-        recs[k] = sd.idx;
-    }
-    std::vector<DcsSlot> slots;
-    uint32_t imgDw = 0;
-    const uint32_t nChunks = dcsPlanChunksCappedLite(jobs, nJobs, ps.data(), fpw, slots, true, 0, true, false, &imgDw, DCS_MI355X_WAVE_PLACES);
-    *nChunksOut = nChunks;
-    if (dcsAllSources94(jobs, nJobs, srcs))
-        imgDw |= DCS_PKG_SPLIT4;
-    if (packageBytesOut != nullptr)
-        *packageBytesOut = dcsPkgStride(fpw, imgDw);
-    if (out == nullptr)
-        return DCS_OK;
-    const size_t pkgBytes = static_cast<size_t>(nChunks) * dcsPkgStride(fpw, imgDw);
-    if (cap < pkgBytes)
-        return DCS_ERR_CAPACITY;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    void *dSlots = nullptr, *dPs = nullptr, *dRecs = nullptr, *dBlob = nullptr, *dPkg = nullptr;
-    const size_t blobAlloc = deviceBlobBytes(blobLen);
-    DcsStatus st = [&]() -> DcsStatus {
-        HIPCHK(ctx, hipMalloc(&dSlots, sizeof(DcsSlot) * slots.size()));
-        HIPCHK(ctx, hipMalloc(&dPs, sizeof(DcsPlanSrc) * (nSrcs ? nSrcs : 1)));
-        HIPCHK(ctx, hipMalloc(&dRecs, sizeof(DcsFrameIndex) * (nSrcs ? nSrcs : 1)));
-        HIPCHK(ctx, hipMalloc(&dBlob, blobAlloc));
-        HIPCHK(ctx, hipMalloc(&dPkg, pkgBytes));
-        HIPCHK(ctx, hipMemsetAsync(dBlob, 0, blobAlloc, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(dPkg, 0xA5, pkgBytes, ctx->stream));     // (the pack kernel writes every byte: a pattern it must leave nothing of)
-        HIPCHK(ctx, hipMemcpyAsync(dSlots, slots.data(), sizeof(DcsSlot) * slots.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(dPs, ps.data(), sizeof(DcsPlanSrc) * nSrcs, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(dRecs, recs.data(), sizeof(DcsFrameIndex) * nSrcs, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(dBlob, blob, blobLen, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, launchPack(fpw, ctx->stream, static_cast<const DcsSlot *>(dSlots), nChunks, static_cast<const DcsPlanSrc *>(dPs),
-                               static_cast<const DcsFrameIndex *>(dRecs), static_cast<const uint8_t *>(dBlob), blobLen, static_cast<uint8_t *>(dPkg), imgDw));
-        HIPCHK(ctx, hipMemcpyAsync(out, dPkg, pkgBytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return DCS_OK;
-    }();
-    (void)hipStreamSynchronize(ctx->stream);
-    for (void *q : { dSlots, dPs, dRecs, dBlob, dPkg })
-        if (q) (void)hipFree(q);
-    return st;
-}
 
 extern "C" DcsStatus dcs_batch_create(DcsCtx *ctx,
                                       const uint8_t *blob, size_t blobLen,
@@ -1948,11 +1498,12 @@ static DcsStatus decodeLive(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, ui
         HIPCHK(ctx, liveRoom(&l->dDown, &l->dDownCap, downBytes, false));
 
     {
-        const bool handoff = ctx->handoff;
+        const DcsPlanOptions po{ ctx->handoff, ctx->framesPerChunk, true, 0 };         // (every frame's tail is kept)
         const double tp0 = g_liveStats ? hipchkNow() : 0.0;
-        const uint32_t nChunks = dcsPlanChunks(jobs, nJobs, srcs, fpw, l->slots, handoff, ctx->framesPerChunk, false, true, ctx->shuffleSeed);
+        const DcsPlan plan = dcsPlanJobs(jobs, nJobs, srcs, fpw, l->slots, po);
+        dcsShuffleChunks(l->slots, plan.nChunks, fpw, ctx->shuffleSeed);        // (test hook)
         const double tp1 = g_liveStats ? hipchkNow() : 0.0;
-        const uint32_t layout = dcsImageDwords(l->slots.data(), nChunks, fpw) | (split4 ? DCS_PKG_SPLIT4 : 0u);
+        const uint32_t nChunks = plan.nChunks, layout = plan.imgDw | (split4 ? DCS_PKG_SPLIT4 : 0u);
 
         // what goes up, in one block: external tails | descriptors (only multi-channel frames read them) | chunk packages
         const size_t tailBytes = static_cast<size_t>(nTailsIn) * 16 * sizeof(int16_t);

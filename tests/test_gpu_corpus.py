@@ -125,6 +125,26 @@ def test_device_packer_lays_out_the_same_packages_as_the_host_packer(gpu_ctx, fp
     assert bad.size == 0, "first difference: chunk %d byte %d" % (bad[0][0], bad[0][1])
 
 
+@pytest.mark.parametrize("t", [0, 1, 2, 3])
+@pytest.mark.parametrize("fpw", [4, 8, 16])
+def test_device_packer_runs_that_cross_the_end_of_the_blob(gpu_ctx, fpw, t):
+    """the same comparison where the two packers take different paths: the blob ends t bytes behind the last stream's data, so
+    the look-ahead dwords of the last run lie partly or wholly past it, at every byte alignment (an OS93a Type-1 stream has a
+    1-byte header).  Bytes past the end read as zero by the format's rule; neither entry validates sources against the blob"""
+    streams = [(os_for(f), make_stream(f, 9, seed=62000 + f), 240, 0x64) for f in (D.FMT_94_T1_S3, D.FMT_93A_T1)]
+    b = D.build_stream_batch(streams, extra_frames=0)
+    end = int(b["srcs"]["streamOff"][-1]) + len(streams[-1][1])
+    blob = b["blob"][:end + t]
+    last = b["srcs"][-1]
+    bit = (int(last["streamOff"]) + 2 + int(last["hdrLen"])) * 8 + int(last["idx"]["bitOff"])
+    assert 4 * ((bit >> 5) + ((bit & 31) + int(last["idx"]["nBits"]) + 31) // 32 + 3) > len(blob) >= (bit + int(last["idx"]["nBits"]) + 7) // 8
+    host = D.pack_chunks(blob, b["srcs"], b["jobs"], fpw)
+    dev = gpu_ctx.pack_chunks_device(blob, b["srcs"], b["jobs"], fpw)
+    assert host.shape == dev.shape
+    bad = np.argwhere(host != dev)
+    assert bad.size == 0, "first difference: chunk %d byte %d" % (bad[0][0], bad[0][1])
+
+
 @pytest.mark.parametrize("on_device", [0, 1, 2, 3], ids=["host-index", "device-index", "device-index-and-pack", "device-index-plan-and-pack"])
 def test_pipeline_returns_lists_in_order(gpu_ctx, corpus, on_device):
     """dcs_pipeline: several lists in flight come back in submission order with the PCM of dcs_decode_streams, whether

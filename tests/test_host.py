@@ -340,7 +340,7 @@ def test_chunk_packages_hold_exactly_what_round_0_needs(fpw, workload):
 
 
 def test_resident_plan_shortens_packages_but_opens_no_further_generation():
-    """dcsPlanChunksCapped (what dcs_batch_create plans with): the default workload's 65 536 frames stay 8 192 chunks -- exactly two
+    """the plan of a resident batch (dcsPlanJobs with `places`, what dcs_batch_create plans with): the default workload's 65 536 frames stay 8 192 chunks -- exactly two
     generations of an MI355X's 4 096 wavefront places; a plan capped at what 97 % of the chunks need would make 8 216 of them and a
     third generation (measured: 36.2 us against 33.4) -- with the image sized by the fullest chunk and 4-byte split records; a batch
     that is well inside one generation takes the capped plan: more chunks than frames / 8, shorter packages, fewer bytes in all"""
@@ -358,6 +358,19 @@ def test_resident_plan_shortens_packages_but_opens_no_further_generation():
     jobs_seen = np.sort(np.concatenate([pk2[c, 80 * s: 80 * s + 4].view("<u4") for c in range(pk2.shape[0]) for s in range(8)]))
     jobs_seen = jobs_seen[jobs_seen != 0xFFFFFFFF]
     assert np.array_equal(jobs_seen, np.arange(small["jobs"].size, dtype=np.uint32))      # every frame once, halo-free
+
+
+def test_arithmetic_planner_equals_chain_planner():
+    """tests/cpp/dcs_plan_test.cpp: the per-chunk arithmetic plan of a list of whole streams (the device planner's body, called on
+    the host) gives the slots and source digests the chain planner gives -- all six layouts, streams of 1 .. 37 frames so that
+    chunks span stream boundaries, extra frames 0 .. 2, fpw 4 / 8 / 16 full and part-filled, a damaged stream -- and flags a
+    stream cut short of its payload"""
+    import os
+    import subprocess
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dcsexplorer_amd", "dcs_plan_test")
+    assert os.path.exists(exe), "build with make -C dcsexplorer_amd/csrc"
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout + p.stderr
 
 
 def test_workload_builders_shape():

@@ -16,8 +16,8 @@ int main(int argc,char**argv){
     std::vector<DcsFrameIndex> idx((size_t)nStreams*nFrames); std::vector<DcsStreamInfo> infos(nStreams); std::vector<uint64_t> first(nStreams); for(int k=0;k<nStreams;k++) first[k]=(uint64_t)k*nFrames;
     double t2=now(); dcs_index_streams(refs.data(),nStreams,0,idx.data(),first.data(),infos.data()); double t3=now();
     dcs_index_streams(refs.data(),nStreams,1,idx.data(),first.data(),infos.data()); double t4=now();
-    std::vector<DcsSlot> slots; double t5=now(); uint32_t nc=dcsPlanChunks(B.jobs.data(),(uint32_t)B.jobs.size(),B.srcs.data(),8,slots,true); double t6=now();
-    std::vector<uint8_t> out((size_t)nc*dcsPkgBytes(8)); double t7=now(); dcsBuildPackages(slots.data(),nc,8,B.srcs.data(),B.blob.data(),B.blob.size(),out.data()); double t8=now();
+    std::vector<DcsSlot> slots; double t5=now(); DcsPlan pl=dcsPlanJobs(B.jobs.data(),(uint32_t)B.jobs.size(),B.srcs.data(),8,slots,DcsPlanOptions()); uint32_t nc=pl.nChunks, layout=pl.imgDw|(dcsAllSources94(B.jobs.data(),(uint32_t)B.jobs.size(),B.srcs.data())?DCS_PKG_SPLIT4:0u); double t6=now();
+    std::vector<uint8_t> out((size_t)nc*dcsPkgStride(8,layout)); double t7=now(); dcsBuildPackages(slots.data(),nc,8,B.srcs.data(),B.blob.data(),B.blob.size(),out.data(),layout); double t8=now();
     // the build from records that are already there (the pipeline's device-index path)
     { DcsBuiltStreams B2; std::vector<uint64_t> off(nStreams); uint64_t o=0; for(int k=0;k<nStreams;k++){ off[k]=o; o+=(refs[k].len+3)&~size_t(3);} DcsPreIndexed pre{idx.data(), first.data(), infos.data(), off.data()};
       double a=now(); dcsBuildStreams(refs.data(),nStreams,0,B2,false,false,&pre); double b=now(); dcsBuildStreams(refs.data(),nStreams,0,B2,false,false,&pre); double c=now();
