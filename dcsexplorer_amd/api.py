@@ -141,6 +141,20 @@ FLAC_FRAME_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u4"), ("blockSize",
                              ("headerLength", "<i4")], align=True)
 
 
+# dcs_level_*: what happens to a stream's level between the converter and the encoder, and what the stage did
+class Level(ctypes.Structure):
+    """DcsLevel.  Level(LEVEL_FIT, ceiling=1.0), Level(LEVEL_GAIN, gain=0.5), Level(LEVEL_GAIN, LEVEL_CLIP, 2.0, 0.9)"""
+    _fields_ = [("mode", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("gain", ctypes.c_float), ("ceiling", ctypes.c_float)]
+
+    def __init__(self, mode=0, flags=0, gain=1.0, ceiling=1.0):
+        super().__init__(mode, flags, gain, ceiling)
+
+
+LEVEL_GAIN, LEVEL_FIT, LEVEL_NORMALIZE = 1, 2, 3
+LEVEL_CLIP = 1
+LEVEL_INFO_DTYPE = np.dtype([("peakIn", "<f4"), ("gain", "<f4"), ("peakOut", "<f4"), ("mode", "<u4"), ("nClipped", "<u8")], align=True)
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("format", ctypes.c_int32), ("nFrames", ctypes.c_int32),
                 ("nBands", ctypes.c_int32), ("strideFromBand", ctypes.c_int32), ("profile", ctypes.c_int32),
@@ -199,6 +213,7 @@ EXPORTS = [
     "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
     "dcs_flac_parse", "dcs_flac_index", "dcs_flac_decode",
     "dcs_encode_sweep", "dcs_encode_sweep_group_frames", "dcs_encode_fit",
+    "dcs_level_gain", "dcs_level_streams", "dcs_resample_streams_level", "dcs_encode_streams_at_level", "dcs_encode_files_level",
 ]
 
 
@@ -518,6 +533,18 @@ def load_library():
     L.dcs_encode_files.restype = i32
     L.dcs_encode_files.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32, vp, sz,
                                    vp, vp]
+    if hasattr(L, "dcs_level_gain"):        # (DCS_HIP_LIB may name a build from before there was the level stage: A/B against it)
+        fp = ctypes.POINTER(ctypes.c_float)
+        L.dcs_level_gain.restype = i32
+        L.dcs_level_gain.argtypes = [ctypes.c_float, ctypes.POINTER(Level), ctypes.c_float, fp, fp]
+        L.dcs_level_streams.restype = i32
+        L.dcs_level_streams.argtypes = [vp, vp, vp, u32, vp, u32, vp, sz, vp, vp]
+        L.dcs_resample_streams_level.restype = i32
+        L.dcs_resample_streams_level.argtypes = L.dcs_resample_streams.argtypes + [vp, u32, vp]
+        L.dcs_encode_streams_at_level.restype = i32
+        L.dcs_encode_streams_at_level.argtypes = L.dcs_encode_streams_at.argtypes + [vp, u32, vp]
+        L.dcs_encode_files_level.restype = i32
+        L.dcs_encode_files_level.argtypes = L.dcs_encode_files.argtypes + [vp, u32, vp]
     L.dcs_device_numa_node.restype = ctypes.c_int
     L.dcs_device_numa_node.argtypes = [ctypes.c_int]
     L.dcs_host_threads.restype = ctypes.c_int
@@ -863,6 +890,27 @@ def resample_count(n_values, rate, channels=1, filter=None, at_unity=False):
                                              RESAMPLE_AT_UNITY if at_unity else 0, ctypes.byref(out)))
     del keep
     return int(out.value)
+
+
+def _levels(level, n):
+    """level: a Level, or a list of n of them -> (DcsLevel array, its length)"""
+    ls = [level] if isinstance(level, Level) else list(level)
+    if len(ls) != 1 and len(ls) != n:
+        raise ValueError("%d streams, %d levels (one, or one per stream)" % (n, len(ls)))
+    return (Level * max(len(ls), 1))(*ls), len(ls)
+
+
+def level_gain(peak, level, bound=1.0):
+    """dcs_level_gain (host only): the gain `level` gives a stream whose peak is `peak`, and the peak after it, as float32.
+    Raises DcsError -1 for a bad level, peak or bound, and -6 (with .gain and .peak_out) when the peak comes out above bound."""
+    g, p = ctypes.c_float(), ctypes.c_float()
+    st = load_library().dcs_level_gain(float(peak), ctypes.byref(level), float(bound), ctypes.byref(g), ctypes.byref(p))
+    if st != 0:
+        e = DcsError(st)
+        if st == ERR_BAD_STREAM:
+            e.gain, e.peak_out = np.float32(g.value), np.float32(p.value)
+        raise e
+    return np.float32(g.value), np.float32(p.value)
 
 
 def _files_blob(files):
@@ -1269,12 +1317,26 @@ class Context:
         _check(self.L.dcs_encode93_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info
 
-    def resample_streams(self, pcm_list, rates, channels=1, filter=None, at_unity=False):
+    def level_streams(self, pcm_list, level):
+        """dcs_level_streams: the level stage alone on PCM at 31 250 Hz (as encode_streams; a stream may be empty).  level: a
+        Level for every stream, or a list with one per stream.  Returns (list of float32 arrays, LEVEL_INFO_DTYPE array)."""
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        lv, n_lv = _levels(level, n)
+        out = np.zeros(max(int(offs[-1]), 1), np.float32)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info = np.zeros(max(n, 1), LEVEL_INFO_DTYPE)
+        _check(self.L.dcs_level_streams(self.h, _ptr(pcm), _ptr(offs), n, lv, n_lv, _ptr(out), out.size, _ptr(out_offs), _ptr(info)),
+               self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)], info[:n]
+
+    def resample_streams(self, pcm_list, rates, channels=1, filter=None, at_unity=False, level=None):
         """dcs_resample_streams: PCM at `rates` Hz (one rate, or one per stream; 4 000 .. 384 000) -> float32 at 31 250 Hz,
         what the reference's encoder feeds itself.  pcm_list: float32 arrays, or int16 arrays, which are divided by 32768;
         channels: 1 or 2 (interleaved, averaged), one value or one per stream; filter: None = the library's table, or
         (float32 coefficients, increment) in libsamplerate's layout; at_unity: run the converter at 31 250 Hz too.
-        Returns a list of float32 arrays."""
+        Returns a list of float32 arrays.  level: None, or a Level or a list of one per stream applied to the resampled
+        signal (dcs_resample_streams_level); then the LEVEL_INFO_DTYPE array is returned as well, as the last element."""
         pcm, offs = _encode_input(pcm_list)
         n = len(offs) - 1
         r, ch = _per_stream(rates, n, np.uint32, "rates"), _per_stream(channels, n, np.int32, "channel counts")
@@ -1284,15 +1346,21 @@ class Context:
         out_offs = np.zeros(n + 1, np.uint64)
         out = np.zeros(max(sum(_resample_bound(int(offs[i + 1] - offs[i]), int(r[i]), int(ch[i]), at_unity) for i in range(n)), 1),
                        np.float32)
-        _check(self.L.dcs_resample_streams(self.h, _ptr(pcm), _ptr(offs), n, _ptr(r), _ptr(ch), fp, flags, _ptr(out), out.size,
-                                           _ptr(out_offs)), self.h)
+        args = (self.h, _ptr(pcm), _ptr(offs), n, _ptr(r), _ptr(ch), fp, flags, _ptr(out), out.size, _ptr(out_offs))
+        if level is None:
+            _check(self.L.dcs_resample_streams(*args), self.h)
+            return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)]
+        lv, n_lv = _levels(level, n)
+        linfo = np.zeros(max(n, 1), LEVEL_INFO_DTYPE)
+        _check(self.L.dcs_resample_streams_level(*args, lv, n_lv, _ptr(linfo)), self.h)
         del keep
-        return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)]
+        return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)], linfo[:n]
 
-    def encode_streams_at(self, pcm_list, rates, version=0x9400, fmt=None, channels=1, filter=None, at_unity=False, **params):
+    def encode_streams_at(self, pcm_list, rates, version=0x9400, fmt=None, channels=1, filter=None, at_unity=False, level=None,
+                          **params):
         """dcs_encode_streams_at: resample (as resample_streams), then encode on the device (version 0x9400: fmt as
         encode_streams; 0x9301 / 0x9302: fmt as encode93_streams), as the reference's EncodeFile does it for float input.
-        Returns (list of bytes, ENCODE_INFO_DTYPE array)."""
+        Returns (list of bytes, ENCODE_INFO_DTYPE array); with level (as resample_streams) also the LEVEL_INFO_DTYPE array."""
         p = transcode_params(version, fmt, **params)
         pcm, offs = _encode_input(pcm_list)
         n = len(offs) - 1
@@ -1309,10 +1377,16 @@ class Context:
         out = np.zeros(max(cap, 1), np.uint8)
         out_offs = np.zeros(n + 1, np.uint64)
         info = np.zeros(max(n, 1), ENCODE_INFO_DTYPE)
-        _check(self.L.dcs_encode_streams_at(self.h, _ptr(pcm), _ptr(offs), n, _ptr(r), _ptr(ch), ctypes.byref(f) if f is not None else None,
-                                            flags, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
+        args = (self.h, _ptr(pcm), _ptr(offs), n, _ptr(r), _ptr(ch), ctypes.byref(f) if f is not None else None, flags, ctypes.byref(p),
+                _ptr(out), cap, _ptr(out_offs), _ptr(info))
+        if level is None:
+            _check(self.L.dcs_encode_streams_at(*args), self.h)
+            return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n]
+        lv, n_lv = _levels(level, n)
+        linfo = np.zeros(max(n, 1), LEVEL_INFO_DTYPE)
+        _check(self.L.dcs_encode_streams_at_level(*args, lv, n_lv, _ptr(linfo)), self.h)
         del keep
-        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n]
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n], linfo[:n]
 
     def wav_decode(self, files):
         """dcs_wav_decode: WAV files (bytes or paths) -> list of mono float32 arrays at each file's own rate, as libnyquist
@@ -1339,10 +1413,11 @@ class Context:
         _check(self.L.dcs_flac_decode(self.h, _ptr(blob), _ptr(offs), n, _ptr(out), out.size, _ptr(out_offs)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)]
 
-    def encode_files(self, files, version=0x9400, fmt=None, filter=None, at_unity=False, **params):
+    def encode_files(self, files, version=0x9400, fmt=None, filter=None, at_unity=False, level=None, **params):
         """dcs_encode_files: DCSEncoder::EncodeFile on each file (bytes or paths): a DCSa container is copied or re-encoded as
         transcode_dcsa does it, a WAV or native FLAC file is read as libnyquist reads it, resampled and encoded (version, fmt, params as
-        encode_streams_at).  Returns (list of stream bytes, ENCODE_FILE_INFO_DTYPE array)."""
+        encode_streams_at).  Returns (list of stream bytes, ENCODE_FILE_INFO_DTYPE array); with level (a Level, or a list of
+        one per file; WAV and FLAC files only) also the LEVEL_INFO_DTYPE array."""
         p = transcode_params(version, fmt, **params)
         blob, offs = _files_blob(files)
         n = len(offs) - 1
@@ -1356,10 +1431,15 @@ class Context:
         out = np.zeros(max(cap, 1), np.uint8)
         out_offs = np.zeros(n + 1, np.uint64)
         info = np.zeros(max(n, 1), ENCODE_FILE_INFO_DTYPE)
-        _check(self.L.dcs_encode_files(self.h, _ptr(blob), _ptr(offs), n, ctypes.byref(p), fp, flags, _ptr(out), cap, _ptr(out_offs),
-                                       _ptr(info)), self.h)
+        args = (self.h, _ptr(blob), _ptr(offs), n, ctypes.byref(p), fp, flags, _ptr(out), cap, _ptr(out_offs), _ptr(info))
+        if level is None:
+            _check(self.L.dcs_encode_files(*args), self.h)
+            return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n]
+        lv, n_lv = _levels(level, n)
+        linfo = np.zeros(max(n, 1), LEVEL_INFO_DTYPE)
+        _check(self.L.dcs_encode_files_level(*args, lv, n_lv, _ptr(linfo)), self.h)
         del keep
-        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n]
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n], linfo[:n]
 
     def transcode_streams(self, streams, os_list, version=0x9400, fmt=None, reencode_all=False, volume=0x67, level=0xFF,
                           channel_volume=0xFF, **params):

@@ -2169,6 +2169,10 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
 
 #include "dcs_resample.hip.h"
 
+// -------------------------------------------------------------------- level control (dcs_level.hip.h)
+
+#include "dcs_level.hip.h"
+
 // ---------------------------------------------------------------------- encoding files (dcs_wav.hip.h)
 
 #include "dcs_wav.hip.h"

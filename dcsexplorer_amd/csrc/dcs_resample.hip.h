@@ -602,6 +602,13 @@ DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sample
 
 float fromBitsU(uint32_t b) { float x; memcpy(&x, &b, 4); return x; }
 
+// the level stage between the converter and whoever reads its output (dcs_level.hip.h, which follows this file)
+DcsStatus lvCheckLevels(DcsCtx *ctx, const DcsLevel *levels, uint32_t nLevels, uint32_t n, const char *unit);
+void lvPlan(const DcsLevel *levels, uint32_t nLevels, const uint32_t *which, const std::vector<uint32_t> &peak, std::vector<DcsLevelInfo> &li);
+DcsStatus lvScale(DcsCtx *ctx, CacheArena &held, float *dBuf, const uint64_t *offsets, const DcsLevel *levels, uint32_t nLevels,
+                  const uint32_t *which, const std::vector<DcsLevelInfo> &li, unsigned long long **dClipped);
+DcsStatus lvCollect(DcsCtx *ctx, const unsigned long long *dClipped, std::vector<DcsLevelInfo> &li);
+
 }  // namespace
 
 extern "C" DcsStatus dcs_resample_filter_default(DcsResampleFilter *filter)
@@ -631,6 +638,15 @@ extern "C" DcsStatus dcs_resample_streams(DcsCtx *ctx, const float *pcm, const u
                                           const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
                                           uint32_t flags, float *out, size_t outCap, uint64_t *outOffsets)
 {
+    return dcs_resample_streams_level(ctx, pcm, sampleOffsets, nStreams, rates, channels, filter, flags, out, outCap, outOffsets,
+                                      nullptr, 0, nullptr);
+}
+
+extern "C" DcsStatus dcs_resample_streams_level(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                                const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                                                uint32_t flags, float *out, size_t outCap, uint64_t *outOffsets,
+                                                const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
+{
     if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
         return DCS_ERR_INVALID_ARG;
     DcsResampleFilter f;
@@ -641,6 +657,9 @@ extern "C" DcsStatus dcs_resample_streams(DcsCtx *ctx, const float *pcm, const u
         dcsCtxSetError(ctx, why.c_str());
         return status;
     }
+    const bool level = levels != nullptr || nLevels != 0;
+    if (level)
+        ENCTRY(lvCheckLevels(ctx, levels, nLevels, nStreams, "stream"));
     outOffsets[0] = 0;
     if (nStreams == 0)
         return DCS_OK;
@@ -648,10 +667,33 @@ extern "C" DcsStatus dcs_resample_streams(DcsCtx *ctx, const float *pcm, const u
     float *dRes = nullptr;
     std::vector<uint32_t> peak;
     ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, outOffsets, peak));
+    std::vector<DcsLevelInfo> li;
+    unsigned long long *dClipped = nullptr;
+    if (level)
+    {
+        lvPlan(levels, nLevels, nullptr, peak, li);
+        for (uint32_t i = 0 ; i < nStreams ; ++i)
+            if (!isfinite(li[i].peakOut))
+            {
+                dcsCtxSetError(ctx, ("stream " + std::to_string(i) + (isfinite(li[i].peakIn) ? ": the levelled signal is not finite (the gain overflows)"
+                                                                                              : ": the resampled signal is not finite")).c_str());
+                return DCS_ERR_BAD_STREAM;
+            }
+        if (levelInfo != nullptr)
+            memcpy(levelInfo, li.data(), sizeof(DcsLevelInfo) * nStreams);
+    }
     if (out == nullptr || outCap < outOffsets[nStreams])
         return DCS_ERR_CAPACITY;
+    if (level)
+        ENCTRY(lvScale(ctx, held, dRes, outOffsets, levels, nLevels, nullptr, li, &dClipped));
     ENCCHK(hipMemcpyAsync(out, dRes, sizeof(float) * outOffsets[nStreams], hipMemcpyDeviceToHost, held.stream()));
     ENCCHK(hipStreamSynchronize(held.stream()));
+    if (dClipped != nullptr)
+    {
+        ENCTRY(lvCollect(ctx, dClipped, li));
+        if (levelInfo != nullptr)
+            memcpy(levelInfo, li.data(), sizeof(DcsLevelInfo) * nStreams);
+    }
     return DCS_OK;
 }
 
@@ -659,6 +701,16 @@ extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const 
                                            const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
                                            uint32_t flags, const DcsEncodeParams *params, uint8_t *out, size_t outCap,
                                            uint64_t *outOffsets, DcsEncodeInfo *info)
+{
+    return dcs_encode_streams_at_level(ctx, pcm, sampleOffsets, nStreams, rates, channels, filter, flags, params, out, outCap, outOffsets,
+                                       info, nullptr, 0, nullptr);
+}
+
+extern "C" DcsStatus dcs_encode_streams_at_level(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                                 const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                                                 uint32_t flags, const DcsEncodeParams *params, uint8_t *out, size_t outCap,
+                                                 uint64_t *outOffsets, DcsEncodeInfo *info,
+                                                 const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
 {
     if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
         return DCS_ERR_INVALID_ARG;
@@ -677,6 +729,9 @@ extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const 
         dcsCtxSetError(ctx, why.c_str());
         return status;
     }
+    const bool level = levels != nullptr || nLevels != 0;
+    if (level)
+        ENCTRY(lvCheckLevels(ctx, levels, nLevels, nStreams, "stream"));
     if (nStreams == 0)
     {
         outOffsets[0] = 0;
@@ -687,6 +742,9 @@ extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const 
     std::vector<uint32_t> peak;
     std::vector<uint64_t> resOffsets(static_cast<size_t>(nStreams) + 1);
     ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, resOffsets.data(), peak));
+    std::vector<DcsLevelInfo> li;
+    if (level)
+        lvPlan(levels, nLevels, nullptr, peak, li);
     for (uint32_t i = 0 ; i < nStreams ; ++i)
     {
         const std::string name = "stream " + std::to_string(i);
@@ -696,18 +754,33 @@ extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const 
             dcsCtxSetError(ctx, (name + (m == 0 ? ": resamples to no samples" : ": resamples to more than 65 535 frames")).c_str());
             return DCS_ERR_INVALID_ARG;
         }
-        if (peak[i] > 0x3f800000u)          // |y| > 1, or not a number
+        const float top = level ? li[i].peakOut : fromBitsU(peak[i]);       // what the encoder would read
+        if (!(top <= 1.0f))                 // |y| > 1, or not a number
         {
             char text[160];
             snprintf(text, sizeof(text), "%s: the resampled signal peaks at |x| = %.9g, outside [-1, 1] (attenuate the input)",
-                     name.c_str(), static_cast<double>(fromBitsU(peak[i])));
+                     name.c_str(), static_cast<double>(top));
             dcsCtxSetError(ctx, text);
             return DCS_ERR_BAD_STREAM;
         }
+    }
+    unsigned long long *dClipped = nullptr;
+    if (level)
+    {
+        if (levelInfo != nullptr)
+            memcpy(levelInfo, li.data(), sizeof(DcsLevelInfo) * nStreams);
+        ENCTRY(lvScale(ctx, held, dRes, resOffsets.data(), levels, nLevels, nullptr, li, &dClipped));
     }
     EncInput in;
     in.sampleOffsets = resOffsets.data();
     in.nStreams = nStreams;
     in.devFloat = dRes;
-    return encodeStreams(ctx, in, params, os93, EncOutput{ out, outCap, outOffsets, info, nullptr });
+    ENCTRY(encodeStreams(ctx, in, params, os93, EncOutput{ out, outCap, outOffsets, info, nullptr }));
+    if (dClipped != nullptr)
+    {
+        ENCTRY(lvCollect(ctx, dClipped, li));
+        if (levelInfo != nullptr)
+            memcpy(levelInfo, li.data(), sizeof(DcsLevelInfo) * nStreams);
+    }
+    return DCS_OK;
 }

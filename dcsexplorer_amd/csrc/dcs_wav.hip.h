@@ -735,7 +735,8 @@ DcsStatus wavDecode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffse
 
 DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
                                       const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out,
-                                      size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info)
+                                      size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info,
+                                      const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
 {
     if (ctx == nullptr || outOffsets == nullptr)
         return DCS_ERR_INVALID_ARG;
@@ -748,6 +749,9 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
             dcsCtxSetError(ctx, why.c_str());
         return status;
     }
+    const bool level = levels != nullptr || nLevels != 0;
+    if (level)
+        ENCTRY(lvCheckLevels(ctx, levels, nLevels, nFiles, "file"));
     std::vector<FilePlan> plan;
     status = planFiles(files, fileOffsets, nFiles, params, f, flags, plan);
     if (status != DCS_OK)
@@ -763,6 +767,8 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
     outOffsets[0] = 0;
     if (nFiles == 0)
         return DCS_OK;
+    // (a DCSa container keeps this record: the stage is for the signal the converter hands the encoder)
+    std::vector<DcsLevelInfo> fileLevel(level ? nFiles : 0, DcsLevelInfo{ 0.0f, 1.0f, 0.0f, 0, 0 });
     std::vector<uint32_t> wavIdx, dcsaIdx;
     for (uint32_t i = 0 ; i < nFiles ; ++i)
         (plan[i].kind == DCS_FILE_WAV || plan[i].kind == DCS_FILE_FLAC ? wavIdx : dcsaIdx).push_back(i);
@@ -808,6 +814,9 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
         std::vector<uint32_t> peak;
         std::vector<uint64_t> resOffsets(static_cast<size_t>(nW) + 1);
         ENCTRY(rsWalkConvolve(ctx, hs, dMono, nullptr, f, wavIdx.data(), "file", held, &dRes, resOffsets.data(), peak));
+        std::vector<DcsLevelInfo> li;
+        if (level)
+            lvPlan(levels, nLevels, wavIdx.data(), peak, li);
         for (uint32_t k = 0 ; k < nW ; ++k)
         {
             const std::string name = "file " + std::to_string(wavIdx[k]);
@@ -818,11 +827,12 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
                 return DCS_ERR_INVALID_ARG;
             }
             const float b = wavBound(infos[k].sampleFormat);
-            if (!(fromBitsU(peak[k]) <= b))
+            const float top = level ? li[k].peakOut : fromBitsU(peak[k]);
+            if (!(top <= b))
             {
                 char text[192];
                 snprintf(text, sizeof(text), "%s: the signal the encoder reads peaks at |x| = %.9g, beyond %.9g (attenuate the input)",
-                         name.c_str(), static_cast<double>(fromBitsU(peak[k])), static_cast<double>(b));
+                         name.c_str(), static_cast<double>(top), static_cast<double>(b));
                 dcsCtxSetError(ctx, text);
                 return DCS_ERR_BAD_STREAM;
             }
@@ -841,11 +851,20 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
         in.devFloat = dRes;
         in.label = wavIdx.data();
         in.bound = bound.data();
+        unsigned long long *dClipped = nullptr;
+        if (level)
+            ENCTRY(lvScale(ctx, held, dRes, resOffsets.data(), levels, nLevels, wavIdx.data(), li, &dClipped));
         status = encodeStreams(ctx, in, params, os93, EncOutput{ wavOut.data(), cap, wavOffsets.data(), enc.data(), nullptr });
         if (status != DCS_OK)
         {
             renameError(ctx, nullptr);           // (the encoder's messages give the file's own index: in.label)
             return status;
+        }
+        if (level)
+        {
+            ENCTRY(lvCollect(ctx, dClipped, li));
+            for (uint32_t k = 0 ; k < nW ; ++k)
+                fileLevel[wavIdx[k]] = li[k];
         }
         for (uint32_t k = 0 ; k < nW ; ++k)
         {
@@ -901,6 +920,8 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
         outOffsets[i + 1] = outOffsets[i] + size[i];
     if (info != nullptr)
         memcpy(info, fi.data(), sizeof(DcsEncodeFileInfo) * nFiles);
+    if (level && levelInfo != nullptr)
+        memcpy(levelInfo, fileLevel.data(), sizeof(DcsLevelInfo) * nFiles);
     if (out == nullptr || outCap < outOffsets[nFiles])
         return DCS_ERR_CAPACITY;
     for (uint32_t k = 0 ; k < nW ; ++k)
@@ -930,9 +951,17 @@ extern "C" DcsStatus dcs_encode_files(DcsCtx *ctx, const uint8_t *files, const u
                                       const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out,
                                       size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info)
 {
+    return dcs_encode_files_level(ctx, files, fileOffsets, nFiles, params, filter, flags, out, outCap, outOffsets, info, nullptr, 0, nullptr);
+}
+
+extern "C" DcsStatus dcs_encode_files_level(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
+                                            const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out,
+                                            size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info,
+                                            const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
+{
     try
     {
-        return encodeFiles(ctx, files, fileOffsets, nFiles, params, filter, flags, out, outCap, outOffsets, info);
+        return encodeFiles(ctx, files, fileOffsets, nFiles, params, filter, flags, out, outCap, outOffsets, info, levels, nLevels, levelInfo);
     }
     catch (const std::bad_alloc &)
     {

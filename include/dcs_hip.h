@@ -44,7 +44,9 @@ extern "C" {
                                           DcsSweepResult, DCS_SWEEP_MEASURE, dcs_encode_sweep,
                                           dcs_encode_sweep_group_frames, dcs_encode_fit); FLAC files (DcsFlacInfo,
                                           DcsFlacFrame, DCS_WAV_S8, DCS_FILE_FLAC, dcs_flac_parse, dcs_flac_index,
-                                          dcs_flac_decode; dcs_encode_files and dcs_encode_files_plan take FLAC files) */
+                                          dcs_flac_decode; dcs_encode_files and dcs_encode_files_plan take FLAC files); level
+                                          control (DcsLevel, DcsLevelInfo, DCS_LEVEL_*, dcs_level_gain, dcs_level_streams,
+                                          dcs_resample_streams_level, dcs_encode_streams_at_level, dcs_encode_files_level) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -1032,6 +1034,73 @@ DcsStatus dcs_flac_index(const uint8_t *file, size_t len, DcsFlacFrame *frames, 
  * and capacity protocol.  A frame the device refuses is DCS_ERR_BAD_STREAM; dcs_last_error names file and frame. */
 DcsStatus dcs_flac_decode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles, float *out,
                           size_t outCap, uint64_t *outOffsets);
+
+/* ------------------------------------------------------------------------------------------------
+ * Level: what happens to a signal's level between the converter and the encoder ("Level", rules 26-33).
+ * The stage works on the float samples y the encoder would read, after downmix and resampling or after the 31 250 Hz
+ * pass-through.  P = max |y| of a stream, an exact float.  The stream's gain g:
+ *   DCS_LEVEL_GAIN       g = gain (finite, > 0)
+ *   DCS_LEVEL_FIT        g = 1 when P <= ceiling, and the samples are not touched; otherwise g = fit(P, ceiling)
+ *   DCS_LEVEL_NORMALIZE  g = 1 when P == 0, otherwise g = fit(P, ceiling): up as well as down
+ * fit(P, c) in f32: g = c / P, correctly rounded; FLT_MAX where that is infinite; then g steps towards 0
+ * (nextafterf) while (float)(P * g) > c.  Every sample becomes (float)(y * g), one multiply with one rounding, denormals
+ * kept, so the new peak is (float)(P * g) exactly.  With DCS_LEVEL_CLIP the product is then clamped to [-ceiling, ceiling]
+ * and the samples the clamp changed are counted; without it nothing is ever clipped, and a GAIN that leaves the peak beyond
+ * what the entry point accepts is refused as the unlevelled signal would be.  ceiling: 0 < ceiling <= 1, in every mode.
+ * levels: one DcsLevel for all streams (nLevels 1) or one per stream (nLevels == nStreams); anything else, an unknown mode
+ * or flag, a bad gain or ceiling is DCS_ERR_INVALID_ARG with the stream named in dcs_last_error.
+ */
+#define DCS_LEVEL_GAIN       1u        /* DcsLevel.mode                                                                    */
+#define DCS_LEVEL_FIT        2u
+#define DCS_LEVEL_NORMALIZE  3u
+#define DCS_LEVEL_CLIP       1u        /* DcsLevel.flags: clamp to [-ceiling, ceiling] after the multiply                   */
+
+typedef struct DcsLevel
+{
+    uint32_t mode;                     /* DCS_LEVEL_GAIN, DCS_LEVEL_FIT or DCS_LEVEL_NORMALIZE                             */
+    uint32_t flags;                    /* 0 or DCS_LEVEL_CLIP                                                              */
+    float    gain;                     /* DCS_LEVEL_GAIN's factor (the other modes do not read it)                         */
+    float    ceiling;                  /* the largest |y| FIT and NORMALIZE leave, and the clamp's bound                   */
+} DcsLevel;
+
+typedef struct DcsLevelInfo
+{
+    float    peakIn;                   /* P, before the stage                                                              */
+    float    gain;                     /* g as applied                                                                     */
+    float    peakOut;                  /* the largest |y| after it: (float)(P * g), or ceiling where the clamp cut it      */
+    uint32_t mode;                     /* the DcsLevel's mode; 0 for a file the stage does not touch (a DCSa container)    */
+    uint64_t nClipped;                 /* samples the clamp changed                                                        */
+} DcsLevelInfo;
+
+/* host only: the gain and the resulting peak of a stream whose peak is `peak` (finite, >= 0).  DCS_ERR_INVALID_ARG: a bad
+ * level, peak or bound (bound > 0); DCS_ERR_BAD_STREAM, with both outputs filled: the peak comes out above bound. */
+DcsStatus dcs_level_gain(float peak, const DcsLevel *level, float bound, float *gainOut, float *peakOut);
+/* The stage on its own, on the GPU: float PCM at 31 250 Hz in, the same number of floats out (stream i of out at
+ * outOffsets[i] = sampleOffsets[i] - sampleOffsets[0]; a stream may be empty: P = 0, g = 1).  levelInfo: nStreams records,
+ * or NULL.  DCS_ERR_CAPACITY: outCap (floats) is too small; outOffsets is filled all the same.  DCS_ERR_BAD_STREAM: a sample
+ * is not finite, or the levelled peak is (a GAIN without DCS_LEVEL_CLIP that overflows). */
+DcsStatus dcs_level_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                            const DcsLevel *levels, uint32_t nLevels, float *out, size_t outCap, uint64_t *outOffsets,
+                            DcsLevelInfo *levelInfo);
+/* dcs_resample_streams, dcs_encode_streams_at and dcs_encode_files with the stage between converter and output or encoder.
+ * levels NULL (nLevels 0): exactly the call without _level.  levelInfo: one record per stream or file, or NULL.
+ * dcs_resample_streams_level refuses (DCS_ERR_BAD_STREAM) a stream whose resampled or levelled peak is not finite; the two
+ * encoders check the levelled peak where the plain calls check the resampled one (1, or the source format's own full scale
+ * for a file), with the same message and status.  In dcs_encode_files_level the levels count per file; a DCSa container is
+ * copied or re-encoded as ever, and its record is mode 0, gain 1, peaks 0. */
+DcsStatus dcs_resample_streams_level(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                     const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                                     uint32_t flags, float *out, size_t outCap, uint64_t *outOffsets,
+                                     const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo);
+DcsStatus dcs_encode_streams_at_level(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                      const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                                      uint32_t flags, const DcsEncodeParams *params, uint8_t *out, size_t outCap,
+                                      uint64_t *outOffsets, DcsEncodeInfo *info,
+                                      const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo);
+DcsStatus dcs_encode_files_level(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
+                                 const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out,
+                                 size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info,
+                                 const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo);
 
 /* ------------------------------------------------------------------------------------------------
  * Sweeping parameters and fitting a byte budget.  A JOB is one stream encoded with one parameter set.  dcs_encode_sweep

@@ -12,7 +12,13 @@ alternating; both must give the same bytes.  Prints one JSON line.  Per-kernel t
 --flac-seconds, the file replicated over --flac-files counts (1, 16, 256).  Wall time per call for each, median of --iters;
 both must give the same bytes.  The WAV run is the yardstick; the difference is the cost of F1, F2, F3 and the index.  Under
 `rocprofv3 --kernel-trace --stats -- python tools/encode_files_bench.py --flac --flac-files 256 --iters 1` the three kernels
-stand beside the resample and encode kernels."""
+stand beside the resample and encode kernels.
+
+--level fit|gain: what the level stage costs.  The files of each workload through encode_files without a level and with one
+that scales every file (fit: DCS_LEVEL_FIT to --ceiling, below the files' peaks; gain: DCS_LEVEL_GAIN of 0.5), the two calls
+alternating, median and range of --iters each; beside them a device-to-device copy of the resampled floats (the stage reads
+and writes them once), timed in the same run.  With a library from before the stage (DCS_HIP_LIB) only the call without a
+level runs: the same command on two builds compares their unlevelled paths."""
 import argparse
 import json
 import os
@@ -97,6 +103,44 @@ def flac_mode(ctx, a):
     return res
 
 
+def d2d_copy_s(n_floats, iters):
+    """median seconds of one device-to-device copy of n_floats float32 values"""
+    import torch
+    a = torch.zeros(n_floats, dtype=torch.float32, device="cuda")
+    b = torch.empty_like(a)
+    b.copy_(a)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(max(iters, 5)):
+        t = time.perf_counter(); b.copy_(a); torch.cuda.synchronize(); ts.append(time.perf_counter() - t)
+    return float(np.median(ts))
+
+
+def level_mode(ctx, a):
+    have = hasattr(ctx.L, "dcs_encode_files_level")
+    level = D.Level(D.LEVEL_FIT, ceiling=a.ceiling) if a.level == "fit" else D.Level(D.LEVEL_GAIN, gain=0.5)
+    res = {}
+    for w in a.workloads.split(","):
+        files = workload(w)
+        out, info = ctx.encode_files(files)
+        row = dict(files=len(files), out_samples=int(info["nSamples"].sum()))
+        if have:
+            out_l, _, li = ctx.encode_files(files, level=level)
+            row.update(scaled=int((li["gain"] != 1).sum()), peak_in_max=float(li["peakIn"].max()), peak_out_max=float(li["peakOut"].max()))
+        tp, tl = [], []
+        for _ in range(a.iters):
+            t = time.perf_counter(); ctx.encode_files(files); tp.append(time.perf_counter() - t)
+            if have:
+                t = time.perf_counter(); ctx.encode_files(files, level=level); tl.append(time.perf_counter() - t)
+        row.update(plain_s=float(np.median(tp)), plain_min_s=min(tp), plain_max_s=max(tp))
+        if have:
+            row.update(level_s=float(np.median(tl)), level_min_s=min(tl), level_max_s=max(tl),
+                       level_minus_plain_s=float(np.median(tl) - np.median(tp)))
+        row["d2d_copy_s"] = d2d_copy_s(row["out_samples"], a.iters)
+        res[w] = row
+    return res
+
+
 def host_composition(ctx, files):
     mono, rates = [], []
     if R.parse(files[0])[1].get("sampleFormat") == R.IMA:
@@ -117,8 +161,15 @@ def main():
     ap.add_argument("--flac", action="store_true")
     ap.add_argument("--flac-seconds", type=int, default=60)
     ap.add_argument("--flac-files", default="1,16,256")
+    ap.add_argument("--level", choices=["fit", "gain"])
+    ap.add_argument("--ceiling", type=float, default=0.25)
     a = ap.parse_args()
     ctx = D.Context(0)
+    if a.level:
+        res = level_mode(ctx, a)
+        ctx.close()
+        print(json.dumps(dict(tool="encode_files_bench", mode="level", level=a.level, lib=os.path.basename(D.lib_path()), results=res)))
+        return 0
     if a.flac:
         res = flac_mode(ctx, a)
         ctx.close()
