@@ -2165,18 +2165,24 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
     return st;
 }
 
-// ------------------------------------------------------------------------------- resampling (dcs_resample.hip.h)
-
-#include "dcs_resample.hip.h"
+// The chain in front of the encoder, each header using only those before it.
 
 // -------------------------------------------------------------------- level control (dcs_level.hip.h)
 
 #include "dcs_level.hip.h"
 
-// ---------------------------------------------------------------------- encoding files (dcs_wav.hip.h)
+// ------------------------------------------------------------------------------- resampling (dcs_resample.hip.h)
+
+#include "dcs_resample.hip.h"
+
+// ------------------------------------------------------------------------------------ the WAV reader (dcs_wav.hip.h)
 
 #include "dcs_wav.hip.h"
 
-// ------------------------------------------------------------------- FLAC files for encoding files (dcs_flac.hip.h)
+// ---------------------------------------------------------------------------------- the FLAC reader (dcs_flac.hip.h)
 
 #include "dcs_flac.hip.h"
+
+// ------------------------------------------------------------------------ encoding files (dcs_encode_files.hip.h)
+
+#include "dcs_encode_files.hip.h"

@@ -1,8 +1,9 @@
 // dcs_flac.hip.h -- native FLAC files for dcs_encode_files, read as the reference reads them: NyquistIO::Load picks
 // FlacDecoder (FlacDecoder.cpp), which runs libFLAC 1.3.1 (stream_decoder.c), copies the low 1, 2 or 3 bytes of every decoded
-// int32 and converts them with ConvertToFloat32 (Common.cpp: PCM_S8, PCM_16, PCM_24).  Included in dcs_encode.hip after
-// dcs_wav.hip.h, whose driver (wavStageOnDevice, planFiles, encodeFiles) calls into this file; it shares that translation
-// unit's floating-point contract and W1's conversion helpers (wavScale, wavMean).
+// int32 and converts them with ConvertToFloat32 (Common.cpp: PCM_S8, PCM_16, PCM_24).  The FLAC reader only: included in
+// dcs_encode.hip after dcs_wav.hip.h, whose WavFile and conversion helpers (wavScale, wavMean) it uses, and before
+// dcs_encode_files.hip.h, whose driver (wavStageOnDevice, planFiles, encodeFiles) calls into this file; it shares that
+// translation unit's floating-point contract.
 //
 //   F1 walk     flacWalkKernel     one lane per frame: the frame's subframes, serially, through a 64-bit bit window refilled
 //                                  by dword loads (MSB first): headers, warm-ups, LPC parameters, Rice and escape coded
@@ -670,6 +671,13 @@ std::string stageWhy(uint32_t bad)
     return "frame " + std::to_string((bad & 0x7FFFFFFFu) >> 4) + ": " + flacErrText(bad & 15u);
 }
 
+// A FLAC file among the files of a call: its record and frame index; both null for a WAV file.  Its DcsWavInfo is flacAsWav's.
+struct FlacSource
+{
+    const DcsFlacInfo *info;
+    const std::vector<DcsFlacFrame> *frames;
+};
+
 // The FLAC files of a call's group on the device: frame bytes up, F1, F2, F3 into dMono (zeroed first where no frame writes).
 // errOut[k] (one word per file of the group, 0xFFFFFFFF = none) is copied back on the stream; the caller synchronises.
 DcsStatus flacStage(DcsCtx *ctx, CacheArena &held, hipStream_t st, const uint8_t *const *bytes, const FlacSource *flac, uint32_t n,
@@ -757,53 +765,26 @@ DcsWavInfo flacAsWav(const DcsFlacInfo &w)
     return v;
 }
 
-// the index of every FLAC file of a list, on the host pool (files are independent)
-void flacParseMany(const uint8_t *files, const uint64_t *fileOffsets, const std::vector<uint32_t> &which, std::vector<FilePlan> &plan)
-{
-    std::atomic<size_t> next{ 0 };
-    const auto worker = [&] {
-        for (size_t j ; (j = next.fetch_add(1)) < which.size() ; )
-        {
-            FilePlan &p = plan[which[j]];
-            p.status = flacParse(files + fileOffsets[which[j]], fileOffsets[which[j] + 1] - fileOffsets[which[j]], &p.flac, &p.flacFrames);
-        }
-    };
-    int nThreads = dcs_host_threads();
-    nThreads = nThreads < 1 ? 1 : nThreads > static_cast<int>(which.size()) ? static_cast<int>(which.size()) : nThreads;
-    std::vector<std::thread> pool;
-    for (int t = 1 ; t < nThreads ; ++t)
-        pool.emplace_back(worker);
-    worker();
-    for (std::thread &t : pool)
-        t.join();
-}
-
 }  // namespace
 
 extern "C" DcsStatus dcs_flac_parse(const uint8_t *file, size_t len, DcsFlacInfo *info)
 {
     if (info == nullptr || (file == nullptr && len != 0))
         return DCS_ERR_INVALID_ARG;
-    try
-    {
+    return encGuard([&] {
         DcsFlacInfo w;
         const DcsStatus st = flacParse(file, file == nullptr ? 0 : len, &w, nullptr);
         w.status = st;
         *info = w;
         return st;
-    }
-    catch (const std::bad_alloc &)
-    {
-        return DCS_ERR_NO_MEMORY;
-    }
+    });
 }
 
 extern "C" DcsStatus dcs_flac_index(const uint8_t *file, size_t len, DcsFlacFrame *frames, uint32_t cap, uint32_t *nFrames)
 {
     if (nFrames == nullptr || (file == nullptr && len != 0))
         return DCS_ERR_INVALID_ARG;
-    try
-    {
+    return encGuard([&]() -> DcsStatus {
         DcsFlacInfo w;
         std::vector<DcsFlacFrame> ff;
         const DcsStatus st = flacParse(file, file == nullptr ? 0 : len, &w, &ff);
@@ -814,22 +795,5 @@ extern "C" DcsStatus dcs_flac_index(const uint8_t *file, size_t len, DcsFlacFram
             return DCS_ERR_CAPACITY;
         memcpy(frames, ff.data(), sizeof(DcsFlacFrame) * ff.size());
         return DCS_OK;
-    }
-    catch (const std::bad_alloc &)
-    {
-        return DCS_ERR_NO_MEMORY;
-    }
-}
-
-extern "C" DcsStatus dcs_flac_decode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles, float *out,
-                                     size_t outCap, uint64_t *outOffsets)
-{
-    try
-    {
-        return wavDecode(ctx, files, fileOffsets, nFiles, out, outCap, outOffsets, true);
-    }
-    catch (const std::bad_alloc &)
-    {
-        return DCS_ERR_NO_MEMORY;
-    }
+    });
 }

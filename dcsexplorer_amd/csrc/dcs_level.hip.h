@@ -2,20 +2,43 @@
 // (DCS_LEVEL_GAIN) or from the stream's peak (DCS_LEVEL_FIT, DCS_LEVEL_NORMALIZE), and an optional clamp (DCS_LEVEL_CLIP).
 // The reference has no such stage: it encodes whatever the converter gives, overshoot included; this library refuses what
 // leaves the encoder's range (INTEGRATION.md rules 3, 12, 19) and here lets the caller say what should happen instead
-// (rules 26-33).  Included at the end of dcs_encode.hip after dcs_resample.hip.h: it shares that translation unit's
-// floating-point contract (no contraction, f32 rounded at every step, denormals kept), which makes y * g one multiply with
-// one rounding on the device as in a numpy restatement.
+// (rules 26-33).  Included at the end of dcs_encode.hip, the first of the headers of the chain in front of the encoder
+// (dcs_resample.hip.h, dcs_wav.hip.h, dcs_flac.hip.h and dcs_encode_files.hip.h follow and use it): it shares that
+// translation unit's floating-point contract (no contraction, f32 rounded at every step, denormals kept), which makes y * g
+// one multiply with one rounding on the device as in a numpy restatement.
 //
 //   L0 peak   lvPeakKernel    the largest |y| of each stream as bits (dcs_level_streams only: the converter's R3 already
 //                             gives the peak of what it writes, the pass-through included)
 //   L1 scale  lvScaleKernel   y = y * g in place, then the clamp and its count; a stream with g == 1 and no clamp is left alone
 //
-// Everything between is host arithmetic on one float per stream: lvFitGain and lvPlan.  Rounding is monotone, so the peak
-// after the multiply is (float)(P * g) and needs no second reduction.
+// Everything between is host arithmetic on one float per stream: lvFitGain and LevelStage::plan.  Rounding is monotone, so
+// the peak after the multiply is (float)(P * g) and needs no second reduction.  LevelStage is the stage of one call, the
+// one object every driver of the chain runs it through.
 #pragma once
 #include <float.h>
 
 namespace {
+
+float fromBitsU(uint32_t b) { float x; memcpy(&x, &b, 4); return x; }
+
+// The one guard at the C boundary of the chain's headers: a host allocation that fails is DCS_ERR_NO_MEMORY, and no
+// exception leaves the C interface
+template <class Body>
+DcsStatus encGuard(Body body)
+{
+    try { return body(); }
+    catch (const std::bad_alloc &) { return DCS_ERR_NO_MEMORY; }
+}
+
+// The grid of a streaming launch of 256-thread blocks: y strides over the n streams (n >= 1), x over the `items` of the
+// longest one, at least one block a stream and at most blocksPerStream, or, where blocksInAll is given, as many as make
+// about blocksInAll in the whole grid
+dim3 streamGrid(uint32_t n, uint64_t items, uint64_t blocksInAll, uint64_t blocksPerStream)
+{
+    const unsigned gy = n < 65535 ? n : 65535;
+    const uint64_t want = (items + 255) / 256, most = blocksInAll != 0 ? (blocksInAll + gy - 1) / gy : blocksPerStream;
+    return dim3(static_cast<unsigned>(want < 1 ? 1 : want < most ? want : most), gy);
+}
 
 // the correctly rounded c / P, stepped towards 0 until (float)(P * g) <= c (P > 0, 0 < c <= 1)
 __host__ __device__ inline float lvFitGain(float P, float c)
@@ -70,20 +93,6 @@ DcsStatus lvCheckLevels(DcsCtx *ctx, const DcsLevel *levels, uint32_t nLevels, u
             return DCS_ERR_INVALID_ARG;
         }
     return DCS_OK;
-}
-
-// The records of a call's streams from their peaks' bits (rsWalkConvolve's, lvPeakKernel's).  A peak that is not finite
-// gives the neutral record with that peak in and out: every caller refuses it by the check it makes of peakOut.
-void lvPlan(const DcsLevel *levels, uint32_t nLevels, const uint32_t *which, const std::vector<uint32_t> &peak, std::vector<DcsLevelInfo> &li)
-{
-    const uint32_t n = static_cast<uint32_t>(peak.size());
-    li.resize(n);
-    for (uint32_t i = 0 ; i < n ; ++i)
-    {
-        const DcsLevel &l = levels[nLevels == 1 ? 0 : which != nullptr ? which[i] : i];
-        const float P = fromBitsU(peak[i]);
-        li[i] = isfinite(P) ? lvInfoOf(P, l) : DcsLevelInfo{ P, 1.0f, P, l.mode, 0 };
-    }
 }
 
 // what L1 reads of one stream
@@ -161,59 +170,133 @@ __global__ __launch_bounds__(256) void lvScaleKernel(float *__restrict__ buf, co
     }
 }
 
-// L1 on the streams of dBuf (stream i = [offsets[i], offsets[i + 1])) with the gains of li; nothing is launched where every
-// stream keeps its samples.  No wait: the launch is ordered before whatever reads dBuf next on the context's stream.
-// *dClipped: the clamp's counts per stream, on the device (held's), or null where no stream clamps.
-DcsStatus lvScale(DcsCtx *ctx, CacheArena &held, float *dBuf, const uint64_t *offsets, const DcsLevel *levels, uint32_t nLevels,
-                  const uint32_t *which, const std::vector<DcsLevelInfo> &li, unsigned long long **dClipped)
+// The level stage of one call.  levels == null && nLevels == 0: the call has none, and every step below does nothing.
+// `which` (encodeFiles): stream i of the call's group is the caller's unit which[i], whose level it takes and whose record
+// it fills; null: i itself.
+struct LevelStage
 {
-    const uint32_t n = static_cast<uint32_t>(li.size());
-    std::vector<LvStream> hs(n);
-    bool any = false, anyClip = false;
-    uint64_t maxN = 0;
-    for (uint32_t i = 0 ; i < n ; ++i)
-    {
-        const DcsLevel &l = levels[nLevels == 1 ? 0 : which != nullptr ? which[i] : i];
-        // FIT and NORMALIZE end at or below the ceiling, and a stream of no samples has nothing to clamp
-        const bool clip = (l.flags & DCS_LEVEL_CLIP) != 0 && l.mode == DCS_LEVEL_GAIN && offsets[i + 1] > offsets[i];
-        hs[i] = LvStream{ offsets[i], offsets[i + 1] - offsets[i], li[i].gain, clip ? l.ceiling : 0.0f };
-        any = any || clip || li[i].gain != 1.0f;
-        anyClip = anyClip || clip;
-        maxN = hs[i].n > maxN ? hs[i].n : maxN;
-    }
-    *dClipped = nullptr;
-    if (!any || maxN == 0)
-        return DCS_OK;
-    const hipStream_t st = dcsCtxStream(ctx);
-    LvStream *dStr;
-    ENCCHK(held.alloc(&dStr, n));
-    ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(LvStream) * n, hipMemcpyHostToDevice, st));
-    if (anyClip)
-    {
-        ENCCHK(held.alloc(dClipped, n));
-        ENCCHK(hipMemsetAsync(*dClipped, 0, sizeof(unsigned long long) * n, st));
-    }
-    // about 2 048 blocks in all, each thread four samples a step
-    const unsigned gy = n < 65535 ? n : 65535;
-    const uint64_t want = (maxN / 4 + 255) / 256, perStream = (2048 + gy - 1) / gy;
-    const unsigned gx = static_cast<unsigned>(want < 1 ? 1 : want < perStream ? want : perStream);
-    hipLaunchKernelGGL(lvScaleKernel, dim3(gx, gy), dim3(256), 0, st, dBuf, dStr, n, *dClipped);
-    ENCCHK(hipGetLastError());
-    return DCS_OK;
-}
+    DcsCtx *ctx;
+    const DcsLevel *levels;
+    uint32_t nLevels;
+    const uint32_t *which = nullptr;
+    std::vector<DcsLevelInfo> li = {};              // one record per stream, from plan() on
+    unsigned long long *dClipped = nullptr;         // the clamp's counts per stream on the device, or null where no stream clamps
 
-// the clamp's counts into li: one small copy and a wait, only where a stream clamps
-DcsStatus lvCollect(DcsCtx *ctx, const unsigned long long *dClipped, std::vector<DcsLevelInfo> &li)
-{
-    if (dClipped == nullptr)
+    bool on() const { return levels != nullptr || nLevels != 0; }
+    const DcsLevel &of(uint32_t i) const { return levels[nLevels == 1 ? 0 : which != nullptr ? which[i] : i]; }
+
+    // the levels of a call of n units, before anything runs
+    DcsStatus check(uint32_t n, const char *unit) const { return on() ? lvCheckLevels(ctx, levels, nLevels, n, unit) : DCS_OK; }
+
+    // The records from the streams' peaks' bits (rsWalkConvolve's, lvPeakKernel's).  A peak that is not finite gives the
+    // neutral record with that peak in and out: every caller refuses it by the check it makes of peakOut (finite, rsGate).
+    void plan(const std::vector<uint32_t> &peak)
+    {
+        li.resize(on() ? peak.size() : 0);
+        for (uint32_t i = 0 ; i < li.size() ; ++i)
+        {
+            const float P = fromBitsU(peak[i]);
+            li[i] = isfinite(P) ? lvInfoOf(P, of(i)) : DcsLevelInfo{ P, 1.0f, P, of(i).mode, 0 };
+        }
+    }
+
+    // the largest |x| whoever reads stream i next will see
+    float top(uint32_t i, const std::vector<uint32_t> &peak) const { return on() ? li[i].peakOut : fromBitsU(peak[i]); }
+
+    // the refusal of the entry points that hand floats back: a levelled peak that is not finite; `phrase` says what it means
+    // where the peak was not finite to begin with
+    DcsStatus finite(const char *phrase) const
+    {
+        for (uint32_t i = 0 ; i < li.size() ; ++i)
+            if (!isfinite(li[i].peakOut))
+            {
+                dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": "
+                                     + (isfinite(li[i].peakIn) ? "the levelled signal is not finite (the gain overflows)" : phrase)).c_str());
+                return DCS_ERR_BAD_STREAM;
+            }
         return DCS_OK;
-    const hipStream_t st = dcsCtxStream(ctx);
-    std::vector<unsigned long long> c(li.size());
-    ENCCHK(hipMemcpyAsync(c.data(), dClipped, sizeof(unsigned long long) * c.size(), hipMemcpyDeviceToHost, st));
-    ENCCHK(hipStreamSynchronize(st));
-    for (size_t i = 0 ; i < c.size() ; ++i)
-        li[i].nClipped = c[i];
-    return DCS_OK;
+    }
+
+    // L1 on the streams of dBuf (stream i = [offsets[i], offsets[i + 1])) with the gains of li; nothing is launched where
+    // every stream keeps its samples.  No wait: the launch is ordered before whatever reads dBuf next on the context's stream.
+    DcsStatus scale(CacheArena &held, float *dBuf, const uint64_t *offsets)
+    {
+        const uint32_t n = static_cast<uint32_t>(li.size());
+        std::vector<LvStream> hs(n);
+        bool any = false, anyClip = false;
+        uint64_t maxN = 0;
+        for (uint32_t i = 0 ; i < n ; ++i)
+        {
+            const DcsLevel &l = of(i);
+            // FIT and NORMALIZE end at or below the ceiling, and a stream of no samples has nothing to clamp
+            const bool clip = (l.flags & DCS_LEVEL_CLIP) != 0 && l.mode == DCS_LEVEL_GAIN && offsets[i + 1] > offsets[i];
+            hs[i] = LvStream{ offsets[i], offsets[i + 1] - offsets[i], li[i].gain, clip ? l.ceiling : 0.0f };
+            any = any || clip || li[i].gain != 1.0f;
+            anyClip = anyClip || clip;
+            maxN = hs[i].n > maxN ? hs[i].n : maxN;
+        }
+        if (!any || maxN == 0)
+            return DCS_OK;
+        const hipStream_t st = dcsCtxStream(ctx);
+        LvStream *dStr;
+        ENCCHK(held.alloc(&dStr, n));
+        ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(LvStream) * n, hipMemcpyHostToDevice, st));
+        if (anyClip)
+        {
+            ENCCHK(held.alloc(&dClipped, n));
+            ENCCHK(hipMemsetAsync(dClipped, 0, sizeof(unsigned long long) * n, st));
+        }
+        // about 2 048 blocks in all, each thread four samples a step
+        hipLaunchKernelGGL(lvScaleKernel, streamGrid(n, maxN / 4, 2048, 0), dim3(256), 0, st, dBuf, dStr, n, dClipped);
+        ENCCHK(hipGetLastError());
+        return DCS_OK;
+    }
+
+    // the records as they stand into the caller's array (null: nowhere)
+    void publish(DcsLevelInfo *to) const
+    {
+        for (uint32_t i = 0 ; to != nullptr && i < li.size() ; ++i)
+            to[which != nullptr ? which[i] : i] = li[i];
+    }
+
+    // after the last reader of the scaled signal is queued: the clamp's counts into li (one small copy and a wait, only where
+    // a stream clamps), then publish
+    DcsStatus finish(DcsLevelInfo *to)
+    {
+        if (dClipped != nullptr)
+        {
+            const hipStream_t st = dcsCtxStream(ctx);
+            std::vector<unsigned long long> c(li.size());
+            ENCCHK(hipMemcpyAsync(c.data(), dClipped, sizeof(unsigned long long) * c.size(), hipMemcpyDeviceToHost, st));
+            ENCCHK(hipStreamSynchronize(st));
+            for (size_t i = 0 ; i < c.size() ; ++i)
+                li[i].nClipped = c[i];
+        }
+        publish(to);
+        return DCS_OK;
+    }
+};
+
+// From floats on the device to the caller's buffer, for the entry points that hand floats back (dcs_resample_streams_level,
+// dcs_level_streams): plan the level from the peaks, refuse what is not finite (`phrase`: what a peak that was not finite
+// to begin with means), look at the capacity, scale, copy down, collect the clamp's counts, publish.  publishEarly: the
+// records (no clamp counted yet) stand before the capacity is looked at, so DCS_ERR_CAPACITY tells the caller what the
+// level would do; nothing is published where the signal is refused.
+DcsStatus lvToHost(LevelStage &lv, CacheArena &held, float *dBuf, const uint64_t *offsets, const std::vector<uint32_t> &peak,
+                   const char *phrase, bool publishEarly, float *out, size_t outCap, DcsLevelInfo *levelInfo)
+{
+    DcsCtx *ctx = lv.ctx;
+    lv.plan(peak);
+    ENCTRY(lv.finite(phrase));
+    if (publishEarly)
+        lv.publish(levelInfo);
+    const uint64_t total = offsets[peak.size()] - offsets[0];
+    if (out == nullptr || outCap < total)
+        return DCS_ERR_CAPACITY;
+    ENCTRY(lv.scale(held, dBuf, offsets));
+    ENCCHK(hipMemcpyAsync(out, dBuf, sizeof(float) * total, hipMemcpyDeviceToHost, held.stream()));
+    ENCCHK(hipStreamSynchronize(held.stream()));
+    return lv.finish(levelInfo);
 }
 
 }  // namespace
@@ -233,23 +316,29 @@ extern "C" DcsStatus dcs_level_streams(DcsCtx *ctx, const float *pcm, const uint
                                        const DcsLevel *levels, uint32_t nLevels, float *out, size_t outCap, uint64_t *outOffsets,
                                        DcsLevelInfo *levelInfo)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr)
-        return DCS_ERR_INVALID_ARG;
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-        if (sampleOffsets[i + 1] < sampleOffsets[i])
+    return encGuard([&]() -> DcsStatus {
+        if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr)
             return DCS_ERR_INVALID_ARG;
-    const uint64_t total = nStreams != 0 ? sampleOffsets[nStreams] - sampleOffsets[0] : 0;
-    if (total != 0 && pcm == nullptr)
-        return DCS_ERR_INVALID_ARG;
-    ENCTRY(lvCheckLevels(ctx, levels, nLevels, nStreams, "stream"));
-    for (uint32_t i = 0 ; i <= nStreams ; ++i)
-        outOffsets[i] = nStreams != 0 ? sampleOffsets[i] - sampleOffsets[0] : 0;
-    if (total != 0 && (out == nullptr || outCap < total))
-        return DCS_ERR_CAPACITY;
-    std::vector<uint32_t> peak(nStreams, 0);
-    std::vector<DcsLevelInfo> li;
-    if (total != 0)
-    {
+        for (uint32_t i = 0 ; i < nStreams ; ++i)
+            if (sampleOffsets[i + 1] < sampleOffsets[i])
+                return DCS_ERR_INVALID_ARG;
+        const uint64_t total = nStreams != 0 ? sampleOffsets[nStreams] - sampleOffsets[0] : 0;
+        if (total != 0 && pcm == nullptr)
+            return DCS_ERR_INVALID_ARG;
+        ENCTRY(lvCheckLevels(ctx, levels, nLevels, nStreams, "stream"));        // (here the levels are not optional)
+        for (uint32_t i = 0 ; i <= nStreams ; ++i)
+            outOffsets[i] = nStreams != 0 ? sampleOffsets[i] - sampleOffsets[0] : 0;
+        // the capacity is known before anything runs, and is refused before anything runs: no record is published then,
+        // and a sample that is not finite goes unseen
+        if (total != 0 && (out == nullptr || outCap < total))
+            return DCS_ERR_CAPACITY;
+        LevelStage lv{ ctx, levels, nLevels };
+        std::vector<uint32_t> peak(nStreams, 0);
+        if (total == 0)
+        {
+            lv.plan(peak);
+            return lv.finish(levelInfo);
+        }
         CacheArena held(ctx);
         const hipStream_t st = dcsCtxStream(ctx);
         std::vector<LvStream> hs(nStreams);
@@ -269,30 +358,10 @@ extern "C" DcsStatus dcs_level_streams(DcsCtx *ctx, const float *pcm, const uint
         ENCCHK(hipMemcpyAsync(dBuf, pcm + sampleOffsets[0], sizeof(float) * total, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(LvStream) * nStreams, hipMemcpyHostToDevice, st));
         ENCCHK(hipMemsetAsync(dPeak, 0, sizeof(uint32_t) * nStreams, st));
-        const unsigned gy = nStreams < 65535 ? nStreams : 65535;
-        const uint64_t want = (maxN + 255) / 256, perStream = (2048 + gy - 1) / gy;
-        hipLaunchKernelGGL(lvPeakKernel, dim3(static_cast<unsigned>(want < perStream ? want : perStream), gy), dim3(256), 0, st, dBuf, dStr,
-                           nStreams, dPeak);
+        hipLaunchKernelGGL(lvPeakKernel, streamGrid(nStreams, maxN, 2048, 0), dim3(256), 0, st, dBuf, dStr, nStreams, dPeak);
         ENCCHK(hipGetLastError());
         ENCCHK(hipMemcpyAsync(peak.data(), dPeak, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
         ENCCHK(hipStreamSynchronize(st));
-        lvPlan(levels, nLevels, nullptr, peak, li);
-        for (uint32_t i = 0 ; i < nStreams ; ++i)
-            if (!isfinite(li[i].peakOut))
-            {
-                dcsCtxSetError(ctx, ("stream " + std::to_string(i) + (isfinite(li[i].peakIn) ? ": the levelled signal is not finite (the gain overflows)"
-                                                                                              : ": a sample is not finite")).c_str());
-                return DCS_ERR_BAD_STREAM;
-            }
-        unsigned long long *dClipped = nullptr;
-        ENCTRY(lvScale(ctx, held, dBuf, outOffsets, levels, nLevels, nullptr, li, &dClipped));
-        ENCCHK(hipMemcpyAsync(out, dBuf, sizeof(float) * total, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipStreamSynchronize(st));
-        ENCTRY(lvCollect(ctx, dClipped, li));
-    }
-    else
-        lvPlan(levels, nLevels, nullptr, peak, li);
-    if (levelInfo != nullptr && nStreams != 0)
-        memcpy(levelInfo, li.data(), sizeof(DcsLevelInfo) * nStreams);
-    return DCS_OK;
+        return lvToHost(lv, held, dBuf, outOffsets, peak, "a sample is not finite", false, out, outCap, levelInfo);
+    });
 }

@@ -1,8 +1,10 @@
 // dcs_resample.hip.h -- the reference's input resampler on the GPU: libsamplerate's sinc converter, mono, at the fixed
 // ratio 31250 / rate (DCSEncoder::OpenStream, DCSEncoder.cpp:165-185; src_sinc.c:280-424 sinc_mono_vari_process and
 // calc_output_single; common.h:147-155 fmod_one), and EncodeFile's stereo downmix (DCSEncodeFile.cpp:81-102).  Included at
-// the end of dcs_encode.hip: it shares that translation unit's floating-point contract (no contraction, f64 and f32 rounded
-// at every step, denormals kept) and hands its output to the encoder's driver where it lies.
+// the end of dcs_encode.hip after dcs_level.hip.h: it shares that translation unit's floating-point contract (no
+// contraction, f64 and f32 rounded at every step, denormals kept) and hands its output to the encoder's driver where it
+// lies.  The way from the converted signal to the encoder (the level stage, the gate, the hand-over) is stated once, in
+// rsEncodeConverted, for the streams of this file and the files of dcs_encode_files.hip.h.
 //
 //   R1 stage    rsStageKernel     one thread per mono sample: (L + R) / 2.0f for stereo, a copy for mono; a non-finite value
 //                                 flags its stream
@@ -416,6 +418,21 @@ DcsStatus rsCheck(uint32_t n, const uint64_t *sampleOffsets, const uint32_t *rat
     return DCS_OK;
 }
 
+// what the converter produced: the outputs on the device (stream i = [offsets[i], offsets[i + 1]), offsets[n] in all) and
+// the bits of each stream's largest |y|
+struct RsConverted
+{
+    float *d = nullptr;
+    std::vector<uint64_t> offsets;
+    std::vector<uint32_t> peak;
+};
+
+// how a message names stream i of a call: "<unit> label[i]" (label null: i)
+std::string rsName(const char *unit, const uint32_t *label, uint32_t i)
+{
+    return std::string(unit) + " " + std::to_string(label != nullptr ? label[i] : i);
+}
+
 // Walk the files' position chains on the host rather than on device lanes where one or a few long ones dominate the list:
 // a file whose walk makes more than kRsHostWalkMin outputs and at least 1 / kRsHostWalkShare of the list's.  A device lane
 // takes about 263 ns an output, the host about 5 ns, so such a file is walked about 50 times faster
@@ -436,13 +453,13 @@ void rsHostRoute(std::vector<RsStream> &hs)
 
 // After staging: the walk (device lanes, and the host pool for streams marked hostWalk, at the same time), the counts back,
 // the convolution.  hs[i].inOff locates stream i in dMono; dBad (optional) holds R1's flags.  Messages name stream i as
-// "<unit> label[i]".  On DCS_OK, *dOut holds the outputs (stream i from outOffsets[i], outOffsets[n] in all) and peak[i] the
-// bits of the stream's largest |y|; the buffers belong to `held`.
+// "<unit> label[i]" (rsName).  On DCS_OK `c` is filled; the buffers belong to `held`.
 DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dMono, const uint32_t *dBad, const DcsResampleFilter &f,
-                         const uint32_t *label, const char *unit, CacheArena &held, float **dOut, uint64_t *outOffsets,
-                         std::vector<uint32_t> &peak)
+                         const uint32_t *label, const char *unit, CacheArena &held, RsConverted &c)
 {
     const uint32_t n = static_cast<uint32_t>(hs.size());
+    std::vector<uint64_t> &outOffsets = c.offsets;
+    outOffsets.assign(static_cast<size_t>(n) + 1, 0);
     std::vector<uint64_t> counts(n);
     std::vector<uint32_t> bad(n);
     uint64_t nSlots = 0;
@@ -455,7 +472,7 @@ DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dM
         if (hs[i].hostWalk)
             onHost.push_back(i);
     }
-    auto name = [&](uint32_t i) { return std::string(unit) + " " + std::to_string(label != nullptr ? label[i] : i); };
+    auto name = [&](uint32_t i) { return rsName(unit, label, i); };
     const hipStream_t st = dcsCtxStream(ctx);
     float *dCoeffs, *dRes;
     uint64_t *dCounts;
@@ -528,7 +545,6 @@ DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dM
                                       hipMemcpyHostToDevice, st));
         ENCCHK(hipMemcpyAsync(dCounts, counts.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
     }
-    outOffsets[0] = 0;
     uint64_t maxCount = 0;
     for (uint32_t i = 0 ; i < n ; ++i)
     {
@@ -539,27 +555,24 @@ DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dM
     ENCCHK(held.alloc(&dRes, outOffsets[n] ? outOffsets[n] : 1));
     ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
     // about 4 096 blocks in all: each block of the LDS variant copies the table once and then strides over its outputs
-    const unsigned gy = n < 65535 ? n : 65535;
-    const uint64_t want = (maxCount + 255) / 256, perStream = (4096 + gy - 1) / gy;
-    const unsigned gx = static_cast<unsigned>(want < 1 ? 1 : want < perStream ? want : perStream);
+    const dim3 grid = streamGrid(n, maxCount, 4096, 0);
     if (f.nCoeffs <= kRsLdsMaxCoeffs)
-        hipLaunchKernelGGL(rsConvolveKernel<true>, dim3(gx, gy), dim3(256), sizeof(float) * f.nCoeffs, st, dCoeffs, f.nCoeffs,
+        hipLaunchKernelGGL(rsConvolveKernel<true>, grid, dim3(256), sizeof(float) * f.nCoeffs, st, dCoeffs, f.nCoeffs,
                            f.increment, dStr, n, dCounts, dSlots, dMono, dRes, dPeak);
     else
-        hipLaunchKernelGGL(rsConvolveKernel<false>, dim3(gx, gy), dim3(256), 0, st, dCoeffs, f.nCoeffs, f.increment, dStr, n,
+        hipLaunchKernelGGL(rsConvolveKernel<false>, grid, dim3(256), 0, st, dCoeffs, f.nCoeffs, f.increment, dStr, n,
                            dCounts, dSlots, dMono, dRes, dPeak);
     ENCCHK(hipGetLastError());
-    peak.assign(n, 0);
-    ENCCHK(hipMemcpyAsync(peak.data(), dPeak, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    c.peak.assign(n, 0);
+    ENCCHK(hipMemcpyAsync(c.peak.data(), dPeak, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
     ENCCHK(hipStreamSynchronize(st));
-    *dOut = dRes;
+    c.d = dRes;
     return DCS_OK;
 }
 
 // The converter on the device for float input: stage (R1), then rsWalkConvolve, every stream on the device lanes.
 DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t n, const uint32_t *rates,
-                           const int32_t *channels, const DcsResampleFilter &f, uint32_t flags, CacheArena &held,
-                           float **dOut, uint64_t *outOffsets, std::vector<uint32_t> &peak)
+                           const int32_t *channels, const DcsResampleFilter &f, uint32_t flags, CacheArena &held, RsConverted &c)
 {
     std::vector<RsStream> hs(n);
     std::vector<int32_t> ch(n);
@@ -592,22 +605,61 @@ DcsStatus resampleOnDevice(DcsCtx *ctx, const float *pcm, const uint64_t *sample
     ENCCHK(hipMemcpyAsync(dCh, ch.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
     ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
     ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * n, st));
-    const unsigned gy = n < 65535 ? n : 65535;
-    const uint64_t stageBlocks = (maxMono + 255) / 256;
-    hipLaunchKernelGGL(rsStageKernel, dim3(static_cast<unsigned>(stageBlocks < 1024 ? stageBlocks : 1024), gy), dim3(256), 0, st,
-                       dIn, dInOff, dCh, dStr, n, dMono, dBad);
+    hipLaunchKernelGGL(rsStageKernel, streamGrid(n, maxMono, 0, 1024), dim3(256), 0, st, dIn, dInOff, dCh, dStr, n, dMono, dBad);
     ENCCHK(hipGetLastError());
-    return rsWalkConvolve(ctx, hs, dMono, dBad, f, nullptr, "stream", held, dOut, outOffsets, peak);
+    return rsWalkConvolve(ctx, hs, dMono, dBad, f, nullptr, "stream", held, c);
 }
 
-float fromBitsU(uint32_t b) { float x; memcpy(&x, &b, 4); return x; }
+// The gate in front of the encoder: per stream and in stream order, first the length the encoder can take, then the range
+// of what it would read (the levelled peak where the call has a level).  bound[i]: the largest |x| stream i may hold (null:
+// 1); rangeFormat: the caller's message for the range, a format of the stream's name (%s), the peak and the bound (%.9g).
+DcsStatus rsGate(DcsCtx *ctx, const RsConverted &c, const LevelStage &lv, const uint32_t *label, const char *unit, const float *bound,
+                 const char *rangeFormat)
+{
+    for (uint32_t i = 0 ; i + 1 < c.offsets.size() ; ++i)
+    {
+        const std::string name = rsName(unit, label, i);
+        const uint64_t m = c.offsets[i + 1] - c.offsets[i];
+        if (m == 0 || (m + 239) / 240 > 65535)
+        {
+            dcsCtxSetError(ctx, (name + (m == 0 ? ": resamples to no samples" : ": resamples to more than 65 535 frames")).c_str());
+            return DCS_ERR_INVALID_ARG;
+        }
+        const float top = lv.top(i, c.peak), b = bound != nullptr ? bound[i] : 1.0f;
+        if (!(top <= b))                    // |y| beyond the bound, or not a number
+        {
+            char text[192];
+            snprintf(text, sizeof(text), rangeFormat, name.c_str(), static_cast<double>(top), static_cast<double>(b));
+            dcsCtxSetError(ctx, text);
+            return DCS_ERR_BAD_STREAM;
+        }
+    }
+    return DCS_OK;
+}
 
-// the level stage between the converter and whoever reads its output (dcs_level.hip.h, which follows this file)
-DcsStatus lvCheckLevels(DcsCtx *ctx, const DcsLevel *levels, uint32_t nLevels, uint32_t n, const char *unit);
-void lvPlan(const DcsLevel *levels, uint32_t nLevels, const uint32_t *which, const std::vector<uint32_t> &peak, std::vector<DcsLevelInfo> &li);
-DcsStatus lvScale(DcsCtx *ctx, CacheArena &held, float *dBuf, const uint64_t *offsets, const DcsLevel *levels, uint32_t nLevels,
-                  const uint32_t *which, const std::vector<DcsLevelInfo> &li, unsigned long long **dClipped);
-DcsStatus lvCollect(DcsCtx *ctx, const unsigned long long *dClipped, std::vector<DcsLevelInfo> &li);
+// From the converted signal on the device to the encoder, for streams (dcs_encode_streams_at_level) and files
+// (encodeFiles): plan the level from the peaks, gate, scale (queued, no wait), encode where the floats lie, collect the
+// clamp's counts, publish the records to levelOut.  Nothing is published where the gate refuses.  publishEarly: the
+// records go to levelOut as soon as the gate has passed, so they stand where the encoder then refuses (its
+// DCS_ERR_CAPACITY); without it they are written only once everything has succeeded.
+DcsStatus rsEncodeConverted(DcsCtx *ctx, CacheArena &held, const RsConverted &c, LevelStage &lv, const uint32_t *label, const char *unit,
+                            const float *bound, const char *rangeFormat, bool publishEarly, DcsLevelInfo *levelOut,
+                            const DcsEncodeParams *params, bool os93, const EncOutput &to)
+{
+    lv.plan(c.peak);
+    ENCTRY(rsGate(ctx, c, lv, label, unit, bound, rangeFormat));
+    if (publishEarly)
+        lv.publish(levelOut);
+    ENCTRY(lv.scale(held, c.d, c.offsets.data()));
+    EncInput in;
+    in.sampleOffsets = c.offsets.data();
+    in.nStreams = static_cast<uint32_t>(c.peak.size());
+    in.devFloat = c.d;
+    in.label = label;
+    in.bound = bound;
+    ENCTRY(encodeStreams(ctx, in, params, os93, to));
+    return lv.finish(levelOut);
+}
 
 }  // namespace
 
@@ -615,8 +667,10 @@ extern "C" DcsStatus dcs_resample_filter_default(DcsResampleFilter *filter)
 {
     if (filter == nullptr)
         return DCS_ERR_INVALID_ARG;
-    *filter = rsDefaultFilter();
-    return DCS_OK;
+    return encGuard([&] {
+        *filter = rsDefaultFilter();
+        return DCS_OK;
+    });
 }
 
 extern "C" DcsStatus dcs_resample_count(uint64_t nValues, uint32_t rate, int32_t channels, const DcsResampleFilter *filter,
@@ -624,14 +678,15 @@ extern "C" DcsStatus dcs_resample_count(uint64_t nValues, uint32_t rate, int32_t
 {
     if (countOut == nullptr)
         return DCS_ERR_INVALID_ARG;
-    const uint64_t offs[2] = { 0, nValues };
-    DcsResampleFilter f;
-    std::string why;
-    const DcsStatus st = rsCheck(1, offs, &rate, &channels, filter, flags, f, why);
-    if (st != DCS_OK)
+    return encGuard([&] {
+        const uint64_t offs[2] = { 0, nValues };
+        DcsResampleFilter f;
+        std::string why;
+        const DcsStatus st = rsCheck(1, offs, &rate, &channels, filter, flags, f, why);
+        if (st == DCS_OK)
+            *countOut = rsWalk(rsStreamOf(rsMonoLength(nValues, channels), rate, f, flags), [](uint64_t, int64_t, int32_t) {});
         return st;
-    *countOut = rsWalk(rsStreamOf(rsMonoLength(nValues, channels), rate, f, flags), [](uint64_t, int64_t, int32_t) {});
-    return DCS_OK;
+    });
 }
 
 extern "C" DcsStatus dcs_resample_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
@@ -647,54 +702,29 @@ extern "C" DcsStatus dcs_resample_streams_level(DcsCtx *ctx, const float *pcm, c
                                                 uint32_t flags, float *out, size_t outCap, uint64_t *outOffsets,
                                                 const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
-        return DCS_ERR_INVALID_ARG;
-    DcsResampleFilter f;
-    std::string why;
-    DcsStatus status = rsCheck(nStreams, sampleOffsets, rates, channels, filter, flags, f, why);
-    if (status != DCS_OK)
-    {
-        dcsCtxSetError(ctx, why.c_str());
-        return status;
-    }
-    const bool level = levels != nullptr || nLevels != 0;
-    if (level)
-        ENCTRY(lvCheckLevels(ctx, levels, nLevels, nStreams, "stream"));
-    outOffsets[0] = 0;
-    if (nStreams == 0)
-        return DCS_OK;
-    CacheArena held(ctx);
-    float *dRes = nullptr;
-    std::vector<uint32_t> peak;
-    ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, outOffsets, peak));
-    std::vector<DcsLevelInfo> li;
-    unsigned long long *dClipped = nullptr;
-    if (level)
-    {
-        lvPlan(levels, nLevels, nullptr, peak, li);
-        for (uint32_t i = 0 ; i < nStreams ; ++i)
-            if (!isfinite(li[i].peakOut))
-            {
-                dcsCtxSetError(ctx, ("stream " + std::to_string(i) + (isfinite(li[i].peakIn) ? ": the levelled signal is not finite (the gain overflows)"
-                                                                                              : ": the resampled signal is not finite")).c_str());
-                return DCS_ERR_BAD_STREAM;
-            }
-        if (levelInfo != nullptr)
-            memcpy(levelInfo, li.data(), sizeof(DcsLevelInfo) * nStreams);
-    }
-    if (out == nullptr || outCap < outOffsets[nStreams])
-        return DCS_ERR_CAPACITY;
-    if (level)
-        ENCTRY(lvScale(ctx, held, dRes, outOffsets, levels, nLevels, nullptr, li, &dClipped));
-    ENCCHK(hipMemcpyAsync(out, dRes, sizeof(float) * outOffsets[nStreams], hipMemcpyDeviceToHost, held.stream()));
-    ENCCHK(hipStreamSynchronize(held.stream()));
-    if (dClipped != nullptr)
-    {
-        ENCTRY(lvCollect(ctx, dClipped, li));
-        if (levelInfo != nullptr)
-            memcpy(levelInfo, li.data(), sizeof(DcsLevelInfo) * nStreams);
-    }
-    return DCS_OK;
+    return encGuard([&]() -> DcsStatus {
+        if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
+            return DCS_ERR_INVALID_ARG;
+        DcsResampleFilter f;
+        std::string why;
+        const DcsStatus status = rsCheck(nStreams, sampleOffsets, rates, channels, filter, flags, f, why);
+        if (status != DCS_OK)
+        {
+            dcsCtxSetError(ctx, why.c_str());
+            return status;
+        }
+        LevelStage lv{ ctx, levels, nLevels };
+        ENCTRY(lv.check(nStreams, "stream"));
+        outOffsets[0] = 0;
+        if (nStreams == 0)
+            return DCS_OK;
+        CacheArena held(ctx);
+        RsConverted c;
+        ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, c));
+        memcpy(outOffsets, c.offsets.data(), sizeof(uint64_t) * c.offsets.size());
+        // (the offsets stand, and with publishEarly the records, where DCS_ERR_CAPACITY then says the buffer is too small)
+        return lvToHost(lv, held, c.d, outOffsets, c.peak, "the resampled signal is not finite", true, out, outCap, levelInfo);
+    });
 }
 
 extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
@@ -712,75 +742,36 @@ extern "C" DcsStatus dcs_encode_streams_at_level(DcsCtx *ctx, const float *pcm, 
                                                  uint64_t *outOffsets, DcsEncodeInfo *info,
                                                  const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
-        return DCS_ERR_INVALID_ARG;
-    const bool os93 = params != nullptr && params->formatVersion != 0x9400;
-    if (!paramsValid(params, os93))
-    {
-        if (const char *type1 = whyOs93aType1(params, os93))
-            dcsCtxSetError(ctx, type1);
-        return DCS_ERR_INVALID_ARG;
-    }
-    DcsResampleFilter f;
-    std::string why;
-    DcsStatus status = rsCheck(nStreams, sampleOffsets, rates, channels, filter, flags, f, why);
-    if (status != DCS_OK)
-    {
-        dcsCtxSetError(ctx, why.c_str());
-        return status;
-    }
-    const bool level = levels != nullptr || nLevels != 0;
-    if (level)
-        ENCTRY(lvCheckLevels(ctx, levels, nLevels, nStreams, "stream"));
-    if (nStreams == 0)
-    {
-        outOffsets[0] = 0;
-        return DCS_OK;
-    }
-    CacheArena held(ctx);
-    float *dRes = nullptr;
-    std::vector<uint32_t> peak;
-    std::vector<uint64_t> resOffsets(static_cast<size_t>(nStreams) + 1);
-    ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, &dRes, resOffsets.data(), peak));
-    std::vector<DcsLevelInfo> li;
-    if (level)
-        lvPlan(levels, nLevels, nullptr, peak, li);
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-    {
-        const std::string name = "stream " + std::to_string(i);
-        const uint64_t m = resOffsets[i + 1] - resOffsets[i];
-        if (m == 0 || (m + 239) / 240 > 65535)
+    return encGuard([&]() -> DcsStatus {
+        if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
+            return DCS_ERR_INVALID_ARG;
+        const bool os93 = params != nullptr && params->formatVersion != 0x9400;
+        if (!paramsValid(params, os93))
         {
-            dcsCtxSetError(ctx, (name + (m == 0 ? ": resamples to no samples" : ": resamples to more than 65 535 frames")).c_str());
+            if (const char *type1 = whyOs93aType1(params, os93))
+                dcsCtxSetError(ctx, type1);
             return DCS_ERR_INVALID_ARG;
         }
-        const float top = level ? li[i].peakOut : fromBitsU(peak[i]);       // what the encoder would read
-        if (!(top <= 1.0f))                 // |y| > 1, or not a number
+        DcsResampleFilter f;
+        std::string why;
+        const DcsStatus status = rsCheck(nStreams, sampleOffsets, rates, channels, filter, flags, f, why);
+        if (status != DCS_OK)
         {
-            char text[160];
-            snprintf(text, sizeof(text), "%s: the resampled signal peaks at |x| = %.9g, outside [-1, 1] (attenuate the input)",
-                     name.c_str(), static_cast<double>(top));
-            dcsCtxSetError(ctx, text);
-            return DCS_ERR_BAD_STREAM;
+            dcsCtxSetError(ctx, why.c_str());
+            return status;
         }
-    }
-    unsigned long long *dClipped = nullptr;
-    if (level)
-    {
-        if (levelInfo != nullptr)
-            memcpy(levelInfo, li.data(), sizeof(DcsLevelInfo) * nStreams);
-        ENCTRY(lvScale(ctx, held, dRes, resOffsets.data(), levels, nLevels, nullptr, li, &dClipped));
-    }
-    EncInput in;
-    in.sampleOffsets = resOffsets.data();
-    in.nStreams = nStreams;
-    in.devFloat = dRes;
-    ENCTRY(encodeStreams(ctx, in, params, os93, EncOutput{ out, outCap, outOffsets, info, nullptr }));
-    if (dClipped != nullptr)
-    {
-        ENCTRY(lvCollect(ctx, dClipped, li));
-        if (levelInfo != nullptr)
-            memcpy(levelInfo, li.data(), sizeof(DcsLevelInfo) * nStreams);
-    }
-    return DCS_OK;
+        LevelStage lv{ ctx, levels, nLevels };
+        ENCTRY(lv.check(nStreams, "stream"));
+        if (nStreams == 0)
+        {
+            outOffsets[0] = 0;
+            return DCS_OK;
+        }
+        CacheArena held(ctx);
+        RsConverted c;
+        ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, c));
+        return rsEncodeConverted(ctx, held, c, lv, nullptr, "stream", nullptr,
+                                 "%s: the resampled signal peaks at |x| = %.9g, outside [-1, 1] (attenuate the input)", true, levelInfo,
+                                 params, os93, EncOutput{ out, outCap, outOffsets, info, nullptr });
+    });
 }
