@@ -1,6 +1,8 @@
 // dcs_cache.h -- CacheBuf, the one owner of a buffer borrowed from a context's buffer cache (dcs_runtime.hip: cacheAlloc /
 // cacheFree).  The cache knows the real size of every buffer it handed out, so the owner keeps only what it asked for.
 // CacheArena, the owner of all the buffers that one call borrows for work on the context's stream.
+// GrowBuf, the one owner of a buffer that lives OUTSIDE the cache: one that is kept and only ever grows (the live decoder's
+// arenas, an indexer's tables, the resident index inputs), or a diagnostic entry's temporary that the cache should not keep.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -94,4 +96,49 @@ private:
     DcsCtx *ctx_;
     hipStream_t stream_;
     std::vector<CacheBuf> bufs_;
+};
+
+// One allocation of pinned host or device memory made with the runtime directly, never through the context's cache (whose byte
+// counts it leaves alone).  Move-only; an owner that goes frees.  Nothing here waits: whoever lets a buffer go or grow while work
+// queued on a stream may still use it waits for that stream first.
+class GrowBuf
+{
+public:
+    explicit GrowBuf(bool pinned = false) : pinned_(pinned) {}
+    GrowBuf(const GrowBuf &) = delete;
+    GrowBuf &operator=(const GrowBuf &) = delete;
+    GrowBuf(GrowBuf &&o) noexcept : p_(o.p_), cap_(o.cap_), pinned_(o.pinned_) { o.p_ = nullptr; o.cap_ = 0; }
+    ~GrowBuf() { release(); }
+
+    // room for `bytes`: nothing happens when the capacity suffices; else the old allocation is freed -- what it held is NOT kept --
+    // and one of `bytes` rounded up to 64 KiB is made; on failure it owns nothing.  `first`: the least a buffer that holds nothing
+    // yet starts with (a decoder's look-ahead grows 64 -> 512 -> 4 096 frames within its first three calls, and every step used to
+    // free and pin the live arenas again -- 0.7-1.5 ms of a new context's first stream, NOTES 44).
+    hipError_t room(size_t bytes, size_t first = 0)
+    {
+        if (bytes <= cap_)
+            return hipSuccess;
+        const size_t want = ((p_ == nullptr && bytes < first ? first : bytes) + 65535) & ~size_t(65535);
+        release();
+        const hipError_t e = pinned_ ? hipHostMalloc(&p_, want, hipHostMallocDefault) : hipMalloc(&p_, want);
+        if (e == hipSuccess)
+            cap_ = want;
+        else
+            p_ = nullptr;
+        return e;
+    }
+    void release()
+    {
+        if (p_ != nullptr)
+            (void)(pinned_ ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    template <class T = void> T *as() const { return static_cast<T *>(p_); }
+    size_t capacity() const { return cap_; }        // what it really holds
+
+private:
+    void *p_ = nullptr;
+    size_t cap_ = 0;
+    bool pinned_;
 };

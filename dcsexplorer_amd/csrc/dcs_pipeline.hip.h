@@ -239,8 +239,7 @@ static void pipelineIndexer(DcsPipeline *p, int which)
     size_t maxRoundStreams = static_cast<size_t>(ctx->numCUs) * 8;
     if (const char *e = getenv("DCS_PIPE_ROUND_STREAMS"))
         maxRoundStreams = static_cast<size_t>(std::max(1, atoi(e)));
-    void *hTable = nullptr, *dTable = nullptr;      // the round's stream locations and result addresses, as uploaded
-    size_t tableCap = 0;
+    GrowBuf hTable(true), dTable;       // the round's stream locations and result addresses, as uploaded; freed when the thread ends
     for (;;)
     {
         std::vector<DcsPipeline::JobPtr> jobs;
@@ -251,11 +250,7 @@ static void pipelineIndexer(DcsPipeline *p, int which)
             if (p->roundGather > 1 && !p->quit)
                 p->indexWork.wait_for(lk, std::chrono::microseconds(400), [&] { return p->quit || p->toIndex.size() >= p->roundGather; });
             if (p->quit && p->toIndex.empty())
-            {
-                if (hTable) (void)hipHostFree(hTable);
-                if (dTable) (void)hipFree(dTable);
                 return;
-            }
             size_t roundStreams = 0;
             while (!p->toIndex.empty() && (jobs.empty() || roundStreams + p->toIndex.front()->nStreams <= maxRoundStreams))
             {
@@ -275,18 +270,13 @@ static void pipelineIndexer(DcsPipeline *p, int which)
         const size_t locBytes = sizeof(DcsStreamLoc) * nStreams, tableBytes = locBytes + sizeof(dcsidx::StreamOut) * nStreams;
         const bool packOnDevice = (p->flags & DCS_PIPE_PACK_ON_DEVICE) != 0;
         DcsStatus st = [&]() -> DcsStatus {
-            if (tableCap < tableBytes)
+            if (std::min(hTable.capacity(), dTable.capacity()) < tableBytes)        // (twice what the round needs, for the rounds to come)
             {
-                if (hTable) (void)hipHostFree(hTable);
-                if (dTable) (void)hipFree(dTable);
-                hTable = nullptr; dTable = nullptr; tableCap = 0;
-                const size_t want = tableBytes * 2;
-                HIPCHK(ctx, hipHostMalloc(&hTable, want, hipHostMallocDefault));
-                HIPCHK(ctx, hipMalloc(&dTable, want));
-                tableCap = want;
+                HIPCHK(ctx, hTable.room(tableBytes * 2));
+                HIPCHK(ctx, dTable.room(tableBytes * 2));
             }
-            DcsStreamLoc *locs = static_cast<DcsStreamLoc *>(hTable);
-            dcsidx::StreamOut *outs = reinterpret_cast<dcsidx::StreamOut *>(static_cast<uint8_t *>(hTable) + locBytes);
+            DcsStreamLoc *locs = hTable.as<DcsStreamLoc>();
+            dcsidx::StreamOut *outs = reinterpret_cast<dcsidx::StreamOut *>(hTable.as<uint8_t>() + locBytes);
             uint32_t k = 0;
             for (const DcsPipeline::JobPtr &j : jobs)
                 for (uint32_t i = 0 ; i < j->nStreams ; ++i, ++k)
@@ -300,9 +290,9 @@ static void pipelineIndexer(DcsPipeline *p, int which)
                 }
             for (const DcsPipeline::JobPtr &j : jobs)
                 HIPCHK(ctx, hipStreamWaitEvent(stream, j->uploaded, 0));
-            HIPCHK(ctx, copyByKernel(stream, dTable, hTable, tableBytes));
-            HIPCHK(ctx, launchIndexWave(stream, 0, static_cast<const DcsStreamLoc *>(dTable), nStreams, ctx->dTables, nullptr, nullptr, nullptr,
-                                        reinterpret_cast<const dcsidx::StreamOut *>(static_cast<const uint8_t *>(dTable) + locBytes)));
+            HIPCHK(ctx, copyByKernel(stream, dTable.as(), hTable.as(), tableBytes));
+            HIPCHK(ctx, launchIndexWave(stream, 0, dTable.as<const DcsStreamLoc>(), nStreams, ctx->dTables, nullptr, nullptr, nullptr,
+                                        reinterpret_cast<const dcsidx::StreamOut *>(dTable.as<const uint8_t>() + locBytes)));
             for (const DcsPipeline::JobPtr &j : jobs)
                 if (j->hRec)                    // (planner on the device: the records stay where they are)
                 {

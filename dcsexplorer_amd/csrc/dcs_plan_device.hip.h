@@ -269,28 +269,26 @@ extern "C" DcsStatus dcs_pack_chunks_device(DcsCtx *ctx, const DcsFrameJob *jobs
     if (cap < pkgBytes)
         return DCS_ERR_CAPACITY;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    void *dSlots = nullptr, *dPs = nullptr, *dRecs = nullptr, *dBlob = nullptr, *dPkg = nullptr;
+    GrowBuf dSlots, dPs, dRecs, dBlob, dPkg;    // (outside the cache: a diagnostic entry's temporaries, freed when they go)
     const size_t blobAlloc = deviceBlobBytes(blobLen);
-    DcsStatus st = [&]() -> DcsStatus {
-        HIPCHK(ctx, hipMalloc(&dSlots, sizeof(DcsSlot) * slots.size()));
-        HIPCHK(ctx, hipMalloc(&dPs, sizeof(DcsPlanSrc) * (nSrcs ? nSrcs : 1)));
-        HIPCHK(ctx, hipMalloc(&dRecs, sizeof(DcsFrameIndex) * (nSrcs ? nSrcs : 1)));
-        HIPCHK(ctx, hipMalloc(&dBlob, blobAlloc));
-        HIPCHK(ctx, hipMalloc(&dPkg, pkgBytes));
-        HIPCHK(ctx, hipMemsetAsync(dBlob, 0, blobAlloc, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(dPkg, 0xA5, pkgBytes, ctx->stream));     // (the pack kernel writes every byte: a pattern it must leave nothing of)
-        HIPCHK(ctx, hipMemcpyAsync(dSlots, slots.data(), sizeof(DcsSlot) * slots.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(dPs, ps.data(), sizeof(DcsPlanSrc) * nSrcs, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(dRecs, recs.data(), sizeof(DcsFrameIndex) * nSrcs, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(dBlob, blob, blobLen, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, launchPack(fpw, ctx->stream, static_cast<const DcsSlot *>(dSlots), nChunks, static_cast<const DcsPlanSrc *>(dPs),
-                               static_cast<const DcsFrameIndex *>(dRecs), static_cast<const uint8_t *>(dBlob), blobLen, static_cast<uint8_t *>(dPkg), imgDw));
-        HIPCHK(ctx, hipMemcpyAsync(out, dPkg, pkgBytes, hipMemcpyDeviceToHost, ctx->stream));
+    const DcsStatus st = [&]() -> DcsStatus {
+        HIPCHK(ctx, dSlots.room(sizeof(DcsSlot) * slots.size()));
+        HIPCHK(ctx, dPs.room(sizeof(DcsPlanSrc) * (nSrcs ? nSrcs : 1)));
+        HIPCHK(ctx, dRecs.room(sizeof(DcsFrameIndex) * (nSrcs ? nSrcs : 1)));
+        HIPCHK(ctx, dBlob.room(blobAlloc));
+        HIPCHK(ctx, dPkg.room(pkgBytes));
+        HIPCHK(ctx, hipMemsetAsync(dBlob.as(), 0, blobAlloc, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(dPkg.as(), 0xA5, pkgBytes, ctx->stream));    // (the pack kernel writes every byte: a pattern it must leave nothing of)
+        HIPCHK(ctx, hipMemcpyAsync(dSlots.as(), slots.data(), sizeof(DcsSlot) * slots.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(dPs.as(), ps.data(), sizeof(DcsPlanSrc) * nSrcs, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(dRecs.as(), recs.data(), sizeof(DcsFrameIndex) * nSrcs, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(dBlob.as(), blob, blobLen, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, launchPack(fpw, ctx->stream, dSlots.as<const DcsSlot>(), nChunks, dPs.as<const DcsPlanSrc>(), dRecs.as<const DcsFrameIndex>(),
+                               dBlob.as<const uint8_t>(), blobLen, dPkg.as<uint8_t>(), imgDw));
+        HIPCHK(ctx, hipMemcpyAsync(out, dPkg.as(), pkgBytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return DCS_OK;
     }();
-    (void)hipStreamSynchronize(ctx->stream);
-    for (void *q : { dSlots, dPs, dRecs, dBlob, dPkg })
-        if (q) (void)hipFree(q);
+    (void)hipStreamSynchronize(ctx->stream);    // (on failure too: queued copies may still be using the buffers that now go)
     return st;
 }

@@ -46,11 +46,8 @@ struct DcsCtx
     int numCUs = 256;
     std::string lastError;              // written through setError only (the pipeline's threads fail concurrently)
     std::mutex errMutex;
-    // inputs of the last dcs_index_streams_gpu call, resident for dcs_index_streams_gpu_time
-    uint32_t *dIdxBlob = nullptr;
-    DcsStreamLoc *dIdxLocs = nullptr;
-    DcsFrameIndex *dIdxOut = nullptr;
-    DcsStreamInfo *dIdxInfos = nullptr;
+    // inputs of the last dcs_index_streams_gpu call, resident for dcs_index_streams_gpu_time (idxStreams is 0 unless all four are there)
+    GrowBuf dIdxBlob, dIdxLocs, dIdxOut, dIdxInfos;
     size_t idxBlobLen = 0, idxBlobDw = 0;
     uint32_t idxStreams = 0;
     uint64_t idxCap = 0;
@@ -513,10 +510,6 @@ extern "C" void dcs_ctx_destroy(DcsCtx *ctx)
     if (ctx->internalPipe) dcs_pipeline_destroy(ctx->internalPipe);
     liveDestroy(ctx);
     if (ctx->dTables) (void)hipFree(ctx->dTables);
-    if (ctx->dIdxBlob) (void)hipFree(ctx->dIdxBlob);
-    if (ctx->dIdxLocs) (void)hipFree(ctx->dIdxLocs);
-    if (ctx->dIdxOut) (void)hipFree(ctx->dIdxOut);
-    if (ctx->dIdxInfos) (void)hipFree(ctx->dIdxInfos);
     for (const DcsCtx::Cached &c : ctx->devCache) (void)hipFree(c.p);
     for (const DcsCtx::Cached &c : ctx->pinCache) (void)hipHostFree(c.p);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -789,12 +782,34 @@ struct BatchOptions
     bool ranges(const DcsCtx *ctx) const { return (xcdRanges || ctx->xcdRanges) && !ctx->noXcdRanges; }
 };
 
-static bool allXform94(const DcsFrameJob *jobs, uint32_t nJobs)
+// What the host plan of a job list turns on, asked once for resident batches and for the live decoder
+struct JobKinds
 {
-    bool all94 = nJobs != 0;
-    for (uint32_t j = 0 ; j < nJobs && all94 ; ++j)
-        all94 = jobs[j].xform == DCS_XFORM_94;
-    return all94;
+    bool all94;                     // every job a 1994+ transform (chooseFpw)
+    bool multi;                     // some job has a second source: only then are the streams and the full descriptors read on the device
+    bool split4;                    // every source a 1994+ frame: the packages carry 4-byte split records (DCS_PKG_SPLIT4)
+};
+// (an empty list is no list of 1994+ transforms -- no caller gets here with one: createBatch and the live entries refuse it first.
+// srcs = NULL for a caller that has digests instead of descriptors and settles split4 itself)
+static JobKinds classifyJobs(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs)
+{
+    JobKinds k{ nJobs != 0, false, dcsAllSources94(jobs, nJobs, srcs) };
+    for (uint32_t j = 0 ; j < nJobs ; ++j)
+    {
+        k.all94 = k.all94 && jobs[j].xform == DCS_XFORM_94;
+        k.multi = k.multi || jobs[j].nSrc > 1;
+    }
+    return k;
+}
+
+// The host plan of a job list: the chunks in `slots`, in the test hook's order if one is set, and -- in imgDw -- the packages'
+// LAYOUT word (dcs_package.h).  What dcsBuildPackages is then called with, for resident batches and live calls alike.
+static DcsPlan planOnHost(const DcsCtx *ctx, const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, int fpw, bool split4,
+                          std::vector<DcsSlot> &slots, const DcsPlanOptions &po)
+{
+    const DcsPlan plan = dcsPlanJobs(jobs, nJobs, srcs, fpw, slots, po);
+    dcsShuffleChunks(slots, plan.nChunks, fpw, ctx->shuffleSeed);           // (test hook)
+    return DcsPlan{ plan.nChunks, plan.imgDw | (split4 ? DCS_PKG_SPLIT4 : 0u) };
 }
 
 // bytes of the device copy of a blob: whole dwords and a zero tail (the bit reader prefetches past the end, the packers copy whole dwords)
@@ -911,7 +926,8 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
             return vst;
     }
     const bool ranges = o.ranges(ctx);
-    DcsBatch *b = newBatch(ctx, o, nJobs, nSrcs, allXform94(jobs, nJobs), (batchFlags & DCS_BATCH_HAS_93A_T1) != 0, ranges);
+    const JobKinds kinds = classifyJobs(jobs, nJobs, srcs);
+    DcsBatch *b = newBatch(ctx, o, nJobs, nSrcs, kinds.all94, (batchFlags & DCS_BATCH_HAS_93A_T1) != 0, ranges);
     if (b == nullptr)
         return DCS_ERR_NO_MEMORY;
     b->nTailsIn = nTailsIn; b->blobLen = blobLen;
@@ -920,21 +936,16 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
     thread_local std::vector<DcsSlot> slots;    // (kept from batch to batch: see the pipeline's scratch)
     // (a resident batch is planned for the shortest packages: `places`, dcs_plan.cpp)
     const DcsPlanOptions po{ o.handoff, ctx->framesPerChunk, ctx->keepAllTails || o.keepAllTails, o.resident ? static_cast<uint32_t>(ctx->numCUs) * 16u : 0u };
-    const DcsPlan plan = dcsPlanJobs(jobs, nJobs, srcs, b->fpw, slots, po);
+    const DcsPlan plan = planOnHost(ctx, jobs, nJobs, srcs, b->fpw, kinds.split4, slots, po);
     b->nChunks = plan.nChunks;
     b->imgDw = plan.imgDw;
-    dcsShuffleChunks(slots, b->nChunks, b->fpw, ctx->shuffleSeed);          // (test hook)
-    if (dcsAllSources94(jobs, nJobs, srcs))
-        b->imgDw |= DCS_PKG_SPLIT4;             // (the layout word: every source a 1994+ frame -> 4-byte split records)
 
     CacheBuf hPackages;                         // pinned staging for the chunk packages
     DcsStatus st = [&]() -> DcsStatus {
         HIPCHK(ctx, hipSetDevice(ctx->device));
         // Round 0 of every frame reads the chunk packages only; the streams and the full descriptors are needed on the
         // device just for the further sources of multi-channel frames.
-        bool multi = false;
-        for (uint32_t j = 0 ; j < nJobs && !multi ; ++j)
-            multi = jobs[j].nSrc > 1;
+        const bool multi = kinds.multi;
         b->blobOnDevice = multi ? blobLen : 0;
         if (multi)
         {
@@ -989,7 +1000,7 @@ static DcsStatus createBatchOnDevice(DcsCtx *ctx, const BatchOptions &o, const D
         all94 = all94 && srcs[k].format >= DCS_FMT_94_T0;
     }
     const bool ranges = o.ranges(ctx);
-    DcsBatch *b = newBatch(ctx, o, nJobs, nSrcs, allXform94(jobs, nJobs), has93aT1, ranges);
+    DcsBatch *b = newBatch(ctx, o, nJobs, nSrcs, classifyJobs(jobs, nJobs, nullptr).all94, has93aT1, ranges);
     if (b == nullptr)
         return DCS_ERR_NO_MEMORY;
     batchBytes(b, (payloadBits + 7) / 8, streamHeaderBytes(srcs, nSrcs));
@@ -1346,28 +1357,42 @@ extern "C" uint32_t dcs_batch_num_jobs(const DcsBatch *b) { return b ? b->nJobs 
 
 // ---------------------------------------------------------------------------------------------------------
 // The context's LIVE decoder: dcs_decode_batch for a caller that comes back every few frames (DCSDecoderHIP's sample pump, the
-// sequencer, small one-shot calls).  Round 5's one-shot call made a batch object per call: a planner and packer run into freshly
-// borrowed buffers, three events, three memsets, an upload, the launch and two synchronous downloads -- 80 us for ONE frame, when
-// the reference's whole pump takes 4 us a frame.  Here everything that can outlive a call does:
-//   * one pinned arena for what goes up (the external tails, the descriptors of multi-channel frames, the chunk packages) and one
-//     for what comes down (PCM, error words, every frame's tail), both first made for a look-ahead of 4 096 frames, replaced by
-//     one of the size a call needs (rounded up to 64 KiB) when that is more, never given back before the context goes;
-//   * small batches are not copied at all: the kernel reads its packages from the pinned arena and writes its PCM into the
-//     pinned arena over the link (a package is read once, 16 bytes per lane; the PCM of a few dozen frames is a few kilobytes),
-//     so a call is ONE launch and ONE wait.  Larger ones get one copy up, one copy down (PCM, error words and tails are one
-//     block), queued with the launch and waited for once;
-//   * the hand-off words live as long as the context and are told apart by a launch counter (epoch) that only grows, so nothing
-//     is cleared per call; the kernel writes every error word itself;
-//   * the streams behind the SECOND and later sources of multi-channel frames stay resident: a caller that names its blob
-//     (blobId != 0, append-only under that name) has every byte of it uploaded once, when it first appears.
-// Results are handed out as pointers into the pinned arena, valid until the context's next live call.
+// sequencer, small one-shot calls).  DcsLive is its object, made by the context's first live call and gone with the context.  It
+// owns what outlives a call, each buffer a GrowBuf outside the context's cache that is never given back before the context goes:
+//   hUp, hDown     the pinned arenas: what goes up in one block (external tails | descriptors of multi-channel frames | chunk
+//                  packages) and what comes down in one (PCM | error words | every frame's tail).  A small call is not copied at
+//                  all: the kernel reads its packages from hUp and writes into hDown over the link, ONE launch and ONE wait;
+//   dUp, dDown     their device copies, for calls over the zero-copy thresholds: one copy up, one down, queued with the launch;
+//   dHandoff       the hand-off words, told apart by a launch counter (epoch) that only grows, so nothing is cleared per call;
+//   dBlob          the streams behind the SECOND and later sources of multi-channel frames: a caller that names its blob
+//                  (blobId != 0, append-only under that name) has every byte of it uploaded once, when it first appears.
+// A call is a LiveCall that borrows it, and decodeLive the list of its steps, in the order their work is queued on the stream:
+//   validate       before anything is touched: a refused call leaves the device and DcsLive alone
+//   attach         the device, and DcsLive on first use (the two DCS_LIVE_ZC_* variables are read there, once per context)
+//   classifyJobs   and with it the frames per wavefront
+//   residentBlob   (DcsLive) the reuse test, the clear of what another blob left, the upload of what is new
+//   roomDown       hDown, and dDown over the threshold
+//   planAndPack    planOnHost, the up block laid out and filled in hUp, copied to dUp over the threshold
+//   handoffWords   (DcsLive) more words, cleared, for more chunks than any call before had; the epoch and its roll-over
+//   launchKernel   DcsKernelArgs from the arenas, the launch
+//   finish         the copy down over the threshold, the wait, pointers into hDown: valid until the context's next live call
+// (How it came to this: profiles/NOTES.md items 44 and 54.)
 // ---------------------------------------------------------------------------------------------------------
+// DCS_LIVE_STATS=1: where the calls' time went, printed when the context goes.  A call's stopwatch: lap() gives the time since
+// start() or the last lap() to one of the call's sums; a call that gets through adds them to the context's.  Unset: no clock is read.
+static const bool g_liveStats = getenv("DCS_LIVE_STATS") != nullptr && atoi(getenv("DCS_LIVE_STATS")) != 0;
+enum { kLiveValidate, kLivePlan, kLivePack, kLiveQueue, kLiveWait, kLiveLaps };
+struct LiveWatch
+{
+    double us[kLiveLaps] = {}, t = 0;
+    void start() { if (g_liveStats) t = hipchkNow(); }
+    void lap(int k) { if (g_liveStats) { const double now = hipchkNow(); us[k] += now - t; t = now; } }
+};
+
 struct DcsLive
 {
-    uint8_t *hUp = nullptr, *dUp = nullptr, *hDown = nullptr, *dDown = nullptr, *dBlob = nullptr;
-    size_t hUpCap = 0, dUpCap = 0, hDownCap = 0, dDownCap = 0, blobCap = 0;
-    unsigned long long *dHandoff = nullptr;
-    size_t handoffChunks = 0;
+    GrowBuf hUp{ true }, hDown{ true }, dUp, dDown, dBlob, dHandoff;
+    size_t handoffChunks = 0;           // chunks the hand-off words are there AND cleared for
     uint32_t epoch = 0;
     size_t blobResident = 0;            // bytes of the named blob that are on the device
     size_t blobDirty = 0;               // bytes of the device blob written since it was last cleared
@@ -1378,10 +1403,12 @@ struct DcsLive
     // (1 frame 21 us, 64 frames 26.5 against 36-39 with copies, 2 000 frames 176 against 187); beyond a megabyte the copy engines take over.
     size_t zcUpBytes = size_t(1) << 20;
     uint32_t zcDownFrames = 2048;
-    // DCS_LIVE_STATS=1: where the calls' time went, printed when the context goes
-    struct { double validateUs = 0, planUs = 0, packUs = 0, queueUs = 0, waitUs = 0; unsigned long long calls = 0, frames = 0; } stats;
+    double statsUs[kLiveLaps] = {};
+    unsigned long long calls = 0, frames = 0;
+
+    DcsStatus residentBlob(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, uint64_t id);
+    DcsStatus handoffWords(DcsCtx *ctx, uint32_t nChunks);
 };
-static const bool g_liveStats = getenv("DCS_LIVE_STATS") != nullptr && atoi(getenv("DCS_LIVE_STATS")) != 0;
 
 static void liveDestroy(DcsCtx *ctx)
 {
@@ -1391,38 +1418,9 @@ static void liveDestroy(DcsCtx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     if (g_liveStats)
         fprintf(stderr, "live decoder of context %p: %llu calls, %llu frames; validate %.1f us, plan %.1f, pack %.1f, queue %.1f, wait %.1f\n", static_cast<void *>(ctx),
-                l->stats.calls, l->stats.frames, l->stats.validateUs, l->stats.planUs, l->stats.packUs, l->stats.queueUs, l->stats.waitUs);
-    if (l->hUp) (void)hipHostFree(l->hUp);
-    if (l->hDown) (void)hipHostFree(l->hDown);
-    for (void *p : { static_cast<void *>(l->dUp), static_cast<void *>(l->dDown), static_cast<void *>(l->dBlob), static_cast<void *>(l->dHandoff) })
-        if (p) (void)hipFree(p);
+                l->calls, l->frames, l->statsUs[kLiveValidate], l->statsUs[kLivePlan], l->statsUs[kLivePack], l->statsUs[kLiveQueue], l->statsUs[kLiveWait]);
     delete l;
     ctx->live = nullptr;
-}
-
-// room for `bytes` in one of the live arenas (pinned or device), rounded up to 64 KiB; what it held is not kept
-static hipError_t liveRoom(uint8_t **buf, size_t *cap, size_t bytes, bool pinned, size_t first = 0)
-{
-    if (bytes <= *cap)
-        return hipSuccess;
-    // (`first`: what the arena starts with.  A decoder's look-ahead grows 64 -> 512 -> 4 096 frames within its first three calls, and
-    // every step used to free and pin the arenas again -- 0.7-1.5 ms of a new context's first stream, NOTES 44)
-    if (*buf == nullptr && bytes < first)
-        bytes = first;
-    if (*buf != nullptr)
-    {
-        (void)(pinned ? hipHostFree(*buf) : hipFree(*buf));
-        *buf = nullptr;
-        *cap = 0;
-    }
-    const size_t want = (bytes + 65535) & ~size_t(65535);
-    void *p = nullptr;
-    const hipError_t e = pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
-    if (e != hipSuccess)
-        return e;
-    *buf = static_cast<uint8_t *>(p);
-    *cap = want;
-    return hipSuccess;
 }
 
 // the pinned arenas' first size: what a look-ahead of 4 096 frames needs (packages up ~ 340 B a frame, PCM + error word + tail down)
@@ -1430,123 +1428,138 @@ static const size_t kLiveFirstUp = size_t(3) << 19, kLiveFirstDown = size_t(9) <
 // batches beyond this go the resident-batch way (buffers from the context's bounded cache): the live arenas never shrink
 static const uint32_t kLiveMaxJobs = 1u << 17;
 
-static DcsStatus decodeLive(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, uint64_t blobId,
-                            const DcsSrcDesc *srcs, uint32_t nSrcs, const DcsFrameJob *jobs, uint32_t nJobs,
-                            const int16_t *tailsIn, uint32_t nTailsIn,
-                            const int16_t **pcmOut, const uint32_t **errOut, const int16_t **tailsOut)
+// the streams behind further sources: resident under the caller's name for the blob, else uploaded for this call
+DcsStatus DcsLive::residentBlob(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, uint64_t id)
 {
-    uint64_t payloadBits = 0;
-    uint32_t batchFlags = 0;
-    const double tv0 = g_liveStats ? hipchkNow() : 0.0;
+    const size_t need = deviceBlobBytes(blobLen);
+    const bool reuse = id != 0 && id == blobId && blobLen >= blobResident && need <= dBlob.capacity();
+    if (!reuse)
     {
-        const DcsStatus vst = validateBatch(ctx, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, &payloadBits, &batchFlags);
-        if (vst != DCS_OK)
-            return vst;
+        if (need > dBlob.capacity())
+        {
+            HIPCHK(ctx, dBlob.room(id != 0 ? need * 2 : need));
+            HIPCHK(ctx, hipMemsetAsync(dBlob.as(), 0, dBlob.capacity(), ctx->stream));
+        }
+        else if (blobDirty != 0)                                    // (what another blob left there must not show behind this one's end)
+            HIPCHK(ctx, hipMemsetAsync(dBlob.as(), 0, std::min(dBlob.capacity(), deviceBlobBytes(blobDirty)), ctx->stream));
+        blobDirty = 0;
+        blobResident = 0;
+        blobId = id;
     }
-    const double tv1 = g_liveStats ? hipchkNow() : 0.0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->live == nullptr)
+    if (blobLen > blobResident)
     {
-        ctx->live = new (std::nothrow) DcsLive;
+        HIPCHK(ctx, hipMemcpyAsync(dBlob.as<uint8_t>() + blobResident, blob + blobResident, blobLen - blobResident, hipMemcpyHostToDevice, ctx->stream));
+        blobDirty = std::max(blobDirty, blobLen);
+        if (id != 0)
+            blobResident = blobLen;                                 // (an unnamed blob is nobody's next time)
+    }
+    return DCS_OK;
+}
+
+DcsStatus DcsLive::handoffWords(DcsCtx *ctx, uint32_t nChunks)
+{
+    const size_t chunkBytes = 16 * sizeof(unsigned long long);
+    if (nChunks + 1 > handoffChunks)
+    {
+        // (the size is recorded once the words are there and cleared: a failed call leaves none, and the next one tries again)
+        const size_t chunks = std::max<size_t>(size_t(nChunks) + 1, std::max<size_t>(handoffChunks * 2, 1024));
+        handoffChunks = 0;
+        HIPCHK(ctx, dHandoff.room(chunks * chunkBytes));
+        HIPCHK(ctx, hipMemsetAsync(dHandoff.as(), 0, chunks * chunkBytes, ctx->stream));
+        handoffChunks = chunks;
+    }
+    if (++epoch > DCS_EPOCH_MAX)
+    {
+        // the launch counter has come round: words of 2^32 launches ago must not pass for this launch's
+        HIPCHK(ctx, hipMemsetAsync(dHandoff.as(), 0, handoffChunks * chunkBytes, ctx->stream));
+        epoch = 1;
+    }
+    return DCS_OK;
+}
+
+// One call of the live decoder: its arguments, what its steps work out for the steps behind them, and the steps
+struct LiveCall
+{
+    DcsCtx *ctx;
+    const uint8_t *blob; size_t blobLen; uint64_t blobId;
+    const DcsSrcDesc *srcs; uint32_t nSrcs; const DcsFrameJob *jobs; uint32_t nJobs; const int16_t *tailsIn; uint32_t nTailsIn;
+    DcsLive *l = nullptr;
+    LiveWatch watch;
+    uint32_t batchFlags = 0;                                                    // (validate)
+    JobKinds kinds{}; int fpw = 0;                                              // (decodeLive)
+    size_t pcmBytes = 0, errBytes = 0, downBytes = 0; bool zcDown = false;      // (roomDown) the down block: PCM | error words | tails
+    uint32_t nChunks = 0, layout = 0;                                           // (planAndPack)
+    size_t offSrcs = 0, offPkg = 0, upBytes = 0; bool zcUp = false;             // the up block: tails | descriptors at offSrcs | packages at offPkg
+
+    DcsStatus validate()
+    {
+        uint64_t payloadBits = 0;
+        watch.start();
+        const DcsStatus st = validateBatch(ctx, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, &payloadBits, &batchFlags);
+        watch.lap(kLiveValidate);
+        return st;
+    }
+    DcsStatus attach()
+    {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
         if (ctx->live == nullptr)
-            return DCS_ERR_NO_MEMORY;
-        if (const char *v = getenv("DCS_LIVE_ZC_UP_KB")) ctx->live->zcUpBytes = static_cast<size_t>(atol(v)) << 10;
-        if (const char *v = getenv("DCS_LIVE_ZC_DOWN_FRAMES")) ctx->live->zcDownFrames = static_cast<uint32_t>(atol(v));
-    }
-    DcsLive *l = ctx->live;
-    bool all94 = true, multi = false;
-    for (uint32_t j = 0 ; j < nJobs ; ++j)
-    {
-        all94 = all94 && jobs[j].xform == DCS_XFORM_94;
-        multi = multi || jobs[j].nSrc > 1;
-    }
-    const int fpw = chooseFpw(ctx, nJobs, all94);
-    const bool split4 = dcsAllSources94(jobs, nJobs, srcs);
-
-    // the streams behind further sources: resident under the caller's name for the blob, else uploaded for this call
-    if (multi)
-    {
-        const size_t need = deviceBlobBytes(blobLen);
-        const bool reuse = blobId != 0 && blobId == l->blobId && blobLen >= l->blobResident && need <= l->blobCap;
-        if (!reuse)
         {
-            if (need > l->blobCap)
-            {
-                HIPCHK(ctx, liveRoom(&l->dBlob, &l->blobCap, blobId != 0 ? need * 2 : need, false));
-                HIPCHK(ctx, hipMemsetAsync(l->dBlob, 0, l->blobCap, ctx->stream));
-            }
-            else if (l->blobDirty != 0)                                 // (what another blob left there must not show behind this one's end)
-                HIPCHK(ctx, hipMemsetAsync(l->dBlob, 0, std::min(l->blobCap, deviceBlobBytes(l->blobDirty)), ctx->stream));
-            l->blobDirty = 0;
-            l->blobResident = 0;
-            l->blobId = blobId;
+            ctx->live = new (std::nothrow) DcsLive;
+            if (ctx->live == nullptr)
+                return DCS_ERR_NO_MEMORY;
+            if (const char *v = getenv("DCS_LIVE_ZC_UP_KB")) ctx->live->zcUpBytes = static_cast<size_t>(atol(v)) << 10;
+            if (const char *v = getenv("DCS_LIVE_ZC_DOWN_FRAMES")) ctx->live->zcDownFrames = static_cast<uint32_t>(atol(v));
         }
-        if (blobLen > l->blobResident)
-        {
-            HIPCHK(ctx, hipMemcpyAsync(l->dBlob + l->blobResident, blob + l->blobResident, blobLen - l->blobResident, hipMemcpyHostToDevice, ctx->stream));
-            l->blobDirty = std::max(l->blobDirty, blobLen);
-            if (blobId != 0)
-                l->blobResident = blobLen;                              // (an unnamed blob is nobody's next time)
-        }
+        l = ctx->live;
+        return DCS_OK;
     }
-
-    const size_t pcmBytes = static_cast<size_t>(nJobs) * DCS_FRAME_SAMPLES * sizeof(int16_t), errBytes = static_cast<size_t>(nJobs) * sizeof(uint32_t);
-    const size_t downBytes = pcmBytes + errBytes + static_cast<size_t>(nJobs) * 16 * sizeof(int16_t);
-    const bool zcDown = nJobs <= l->zcDownFrames;
-    HIPCHK(ctx, liveRoom(&l->hDown, &l->hDownCap, downBytes, true, kLiveFirstDown));
-    if (!zcDown)
-        HIPCHK(ctx, liveRoom(&l->dDown, &l->dDownCap, downBytes, false));
-
+    DcsStatus roomDown()
     {
-        const DcsPlanOptions po{ ctx->handoff, ctx->framesPerChunk, true, 0 };         // (every frame's tail is kept)
-        const double tp0 = g_liveStats ? hipchkNow() : 0.0;
-        const DcsPlan plan = dcsPlanJobs(jobs, nJobs, srcs, fpw, l->slots, po);
-        dcsShuffleChunks(l->slots, plan.nChunks, fpw, ctx->shuffleSeed);        // (test hook)
-        const double tp1 = g_liveStats ? hipchkNow() : 0.0;
-        const uint32_t nChunks = plan.nChunks, layout = plan.imgDw | (split4 ? DCS_PKG_SPLIT4 : 0u);
-
-        // what goes up, in one block: external tails | descriptors (only multi-channel frames read them) | chunk packages
+        pcmBytes = static_cast<size_t>(nJobs) * DCS_FRAME_SAMPLES * sizeof(int16_t);
+        errBytes = static_cast<size_t>(nJobs) * sizeof(uint32_t);
+        downBytes = pcmBytes + errBytes + static_cast<size_t>(nJobs) * 16 * sizeof(int16_t);
+        zcDown = nJobs <= l->zcDownFrames;
+        HIPCHK(ctx, l->hDown.room(downBytes, kLiveFirstDown));
+        if (!zcDown)
+            HIPCHK(ctx, l->dDown.room(downBytes));
+        return DCS_OK;
+    }
+    DcsStatus planAndPack()
+    {
+        watch.start();
+        const DcsPlanOptions po{ ctx->handoff, ctx->framesPerChunk, true, 0 };         // (every frame's tail is kept, no places)
+        const DcsPlan plan = planOnHost(ctx, jobs, nJobs, srcs, fpw, kinds.split4, l->slots, po);
+        watch.lap(kLivePlan);
+        nChunks = plan.nChunks;
+        layout = plan.imgDw;
         const size_t tailBytes = static_cast<size_t>(nTailsIn) * 16 * sizeof(int16_t);
-        const size_t offSrcs = (tailBytes + 255) & ~size_t(255);
-        const size_t srcBytes = multi ? static_cast<size_t>(nSrcs) * sizeof(DcsSrcDesc) : 0;
-        const size_t offPkg = (offSrcs + srcBytes + 255) & ~size_t(255);
-        const size_t pkgBytes = static_cast<size_t>(nChunks) * dcsPkgStride(fpw, layout);
-        const size_t upBytes = offPkg + pkgBytes;
-        HIPCHK(ctx, liveRoom(&l->hUp, &l->hUpCap, upBytes, true, kLiveFirstUp));
+        offSrcs = (tailBytes + 255) & ~size_t(255);
+        const size_t srcBytes = kinds.multi ? static_cast<size_t>(nSrcs) * sizeof(DcsSrcDesc) : 0;     // (only multi-channel frames read them)
+        offPkg = (offSrcs + srcBytes + 255) & ~size_t(255);
+        upBytes = offPkg + static_cast<size_t>(nChunks) * dcsPkgStride(fpw, layout);
+        HIPCHK(ctx, l->hUp.room(upBytes, kLiveFirstUp));
+        uint8_t *hUp = l->hUp.as<uint8_t>();
         if (tailBytes)
-            memcpy(l->hUp, tailsIn, tailBytes);
+            memcpy(hUp, tailsIn, tailBytes);
         if (srcBytes)
-            memcpy(l->hUp + offSrcs, srcs, srcBytes);
-        dcsBuildPackages(l->slots.data(), nChunks, fpw, srcs, blob, blobLen, l->hUp + offPkg, layout);
-        const double tp2 = g_liveStats ? hipchkNow() : 0.0;
-        const bool zcUp = upBytes <= l->zcUpBytes;
+            memcpy(hUp + offSrcs, srcs, srcBytes);
+        dcsBuildPackages(l->slots.data(), nChunks, fpw, srcs, blob, blobLen, hUp + offPkg, layout);
+        watch.lap(kLivePack);
+        zcUp = upBytes <= l->zcUpBytes;
         if (!zcUp)
         {
-            HIPCHK(ctx, liveRoom(&l->dUp, &l->dUpCap, upBytes, false));
-            HIPCHK(ctx, hipMemcpyAsync(l->dUp, l->hUp, upBytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, l->dUp.room(upBytes));
+            HIPCHK(ctx, hipMemcpyAsync(l->dUp.as(), hUp, upBytes, hipMemcpyHostToDevice, ctx->stream));
         }
-        if (nChunks + 1 > l->handoffChunks)
-        {
-            // (the size is recorded once the words are there and cleared: a failed call leaves none, and the next one tries again)
-            const size_t chunks = std::max<size_t>(size_t(nChunks) + 1, std::max<size_t>(l->handoffChunks * 2, 1024));
-            if (l->dHandoff) (void)hipFree(l->dHandoff);
-            l->dHandoff = nullptr;
-            l->handoffChunks = 0;
-            HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&l->dHandoff), chunks * 16 * sizeof(unsigned long long)));
-            HIPCHK(ctx, hipMemsetAsync(l->dHandoff, 0, chunks * 16 * sizeof(unsigned long long), ctx->stream));
-            l->handoffChunks = chunks;
-        }
-        if (++l->epoch > DCS_EPOCH_MAX)
-        {
-            // the launch counter has come round: words of 2^32 launches ago must not pass for this launch's
-            HIPCHK(ctx, hipMemsetAsync(l->dHandoff, 0, l->handoffChunks * 16 * sizeof(unsigned long long), ctx->stream));
-            l->epoch = 1;
-        }
-        uint8_t *up = zcUp ? l->hUp : l->dUp, *down = zcDown ? l->hDown : l->dDown;
+        return DCS_OK;
+    }
+    DcsStatus launchKernel()
+    {
+        uint8_t *up = (zcUp ? l->hUp : l->dUp).as<uint8_t>(), *down = (zcDown ? l->hDown : l->dDown).as<uint8_t>();
         DcsKernelArgs args;
-        args.blob = multi ? l->dBlob : nullptr;
-        args.blobLen = multi ? blobLen : 0;
-        args.srcs = multi ? reinterpret_cast<const DcsSrcDesc *>(up + offSrcs) : nullptr;
+        args.blob = kinds.multi ? l->dBlob.as<uint8_t>() : nullptr;
+        args.blobLen = kinds.multi ? blobLen : 0;
+        args.srcs = kinds.multi ? reinterpret_cast<const DcsSrcDesc *>(up + offSrcs) : nullptr;
         args.packages = up + offPkg;
         args.nChunks = nChunks;
         args.nJobs = nJobs;
@@ -1556,30 +1569,53 @@ static DcsStatus decodeLive(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, ui
         args.tailsOut = reinterpret_cast<int16_t *>(down + pcmBytes + errBytes);
         args.tables = ctx->dTables;
         args.debug = nullptr;
-        args.handoff = l->dHandoff;
+        args.handoff = l->dHandoff.as<unsigned long long>();
         args.epoch = l->epoch;
         args.flags = batchFlags | (layout << DCS_BATCH_IMG_SHIFT);
         const hipError_t e = withFpw(fpw, [&](auto w) { return launch<decltype(w)::value>(args, ctx->stream, ctx->numCUs, ctx->cpwOverride, !ctx->xcdRanges); });
-        if (e != hipSuccess)
-        {
-            setError(ctx, std::string("kernel launch failed: ") + hipGetErrorString(e));
-            (void)streamWait(ctx, ctx->stream);
-            return DCS_ERR_HIP;
-        }
-        if (!zcDown)
-            HIPCHK(ctx, hipMemcpyAsync(l->hDown, l->dDown, downBytes, hipMemcpyDeviceToHost, ctx->stream));
-        const double tp3 = g_liveStats ? hipchkNow() : 0.0;
-        HIPCHK(ctx, streamWait(ctx, ctx->stream));
-        if (g_liveStats)
-        {
-            l->stats.planUs += tp1 - tp0; l->stats.packUs += tp2 - tp1; l->stats.queueUs += tp3 - tp2; l->stats.waitUs += hipchkNow() - tp3;
-            l->stats.validateUs += tv1 - tv0; l->stats.calls += 1; l->stats.frames += nJobs;
-        }
+        if (e == hipSuccess)
+            return DCS_OK;
+        setError(ctx, std::string("kernel launch failed: ") + hipGetErrorString(e));
+        (void)streamWait(ctx, ctx->stream);
+        return DCS_ERR_HIP;
     }
-    if (pcmOut) *pcmOut = reinterpret_cast<const int16_t *>(l->hDown);
-    if (errOut) *errOut = reinterpret_cast<const uint32_t *>(l->hDown + pcmBytes);
-    if (tailsOut) *tailsOut = reinterpret_cast<const int16_t *>(l->hDown + pcmBytes + errBytes);
-    return DCS_OK;
+    DcsStatus finish(const int16_t **pcmOut, const uint32_t **errOut, const int16_t **tailsOut)
+    {
+        const uint8_t *hDown = l->hDown.as<uint8_t>();
+        if (!zcDown)
+            HIPCHK(ctx, hipMemcpyAsync(l->hDown.as(), l->dDown.as(), downBytes, hipMemcpyDeviceToHost, ctx->stream));
+        watch.lap(kLiveQueue);
+        HIPCHK(ctx, streamWait(ctx, ctx->stream));
+        watch.lap(kLiveWait);
+        for (int k = 0 ; g_liveStats && k < kLiveLaps ; ++k)
+            l->statsUs[k] += watch.us[k];
+        l->calls += 1;                  // (the two counts are printed with the sums only)
+        l->frames += nJobs;
+        if (pcmOut) *pcmOut = reinterpret_cast<const int16_t *>(hDown);
+        if (errOut) *errOut = reinterpret_cast<const uint32_t *>(hDown + pcmBytes);
+        if (tailsOut) *tailsOut = reinterpret_cast<const int16_t *>(hDown + pcmBytes + errBytes);
+        return DCS_OK;
+    }
+};
+
+static DcsStatus decodeLive(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, uint64_t blobId,
+                            const DcsSrcDesc *srcs, uint32_t nSrcs, const DcsFrameJob *jobs, uint32_t nJobs,
+                            const int16_t *tailsIn, uint32_t nTailsIn,
+                            const int16_t **pcmOut, const uint32_t **errOut, const int16_t **tailsOut)
+{
+    LiveCall c{ ctx, blob, blobLen, blobId, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn };
+    DcsStatus st = c.validate();
+    if (st == DCS_OK) st = c.attach();
+    if (st != DCS_OK)
+        return st;
+    c.kinds = classifyJobs(jobs, nJobs, srcs);
+    c.fpw = chooseFpw(ctx, nJobs, c.kinds.all94);
+    if (c.kinds.multi) st = c.l->residentBlob(ctx, blob, blobLen, blobId);
+    if (st == DCS_OK) st = c.roomDown();
+    if (st == DCS_OK) st = c.planAndPack();
+    if (st == DCS_OK) st = c.l->handoffWords(ctx, c.nChunks);
+    if (st == DCS_OK) st = c.launchKernel();
+    return st == DCS_OK ? c.finish(pcmOut, errOut, tailsOut) : st;
 }
 
 extern "C" DcsStatus dcs_decode_batch_live(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, uint64_t blobId,
@@ -1653,8 +1689,8 @@ static hipError_t launchIndexWave(hipStream_t stream, uintptr_t blobBase, const 
 
 static hipError_t launchIndex(DcsCtx *ctx)
 {
-    return launchIndexWave(ctx->stream, reinterpret_cast<uintptr_t>(ctx->dIdxBlob), ctx->dIdxLocs, ctx->idxStreams, ctx->dTables, ctx->dIdxOut,
-                           ctx->dIdxInfos, nullptr);
+    return launchIndexWave(ctx->stream, reinterpret_cast<uintptr_t>(ctx->dIdxBlob.as()), ctx->dIdxLocs.as<DcsStreamLoc>(), ctx->idxStreams, ctx->dTables,
+                           ctx->dIdxOut.as<DcsFrameIndex>(), ctx->dIdxInfos.as<DcsStreamInfo>(), nullptr);
 }
 
 extern "C" DcsStatus dcs_index_streams_gpu(DcsCtx *ctx, const uint8_t *blob, size_t blobLen,
@@ -1685,27 +1721,24 @@ extern "C" DcsStatus dcs_index_streams_gpu(DcsCtx *ctx, const uint8_t *blob, siz
         }
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (void *p : { static_cast<void *>(ctx->dIdxBlob), static_cast<void *>(ctx->dIdxLocs),
-                     static_cast<void *>(ctx->dIdxOut), static_cast<void *>(ctx->dIdxInfos) })
-        if (p) (void)hipFree(p);
-    ctx->dIdxBlob = nullptr; ctx->dIdxLocs = nullptr; ctx->dIdxOut = nullptr; ctx->dIdxInfos = nullptr;
+    // (every call's inputs replace the last one's whole; nothing counts as resident until all four buffers are there again)
     ctx->idxStreams = 0;
     const size_t blobAlloc = (blobLen + 3 + 4) & ~size_t(3);
-    HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dIdxBlob), blobAlloc));
-    HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dIdxLocs), sizeof(DcsStreamLoc) * nStreams));
-    HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dIdxOut), sizeof(DcsFrameIndex) * (outCap ? outCap : 1)));
-    HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dIdxInfos), sizeof(DcsStreamInfo) * nStreams));
-    HIPCHK(ctx, hipMemsetAsync(reinterpret_cast<uint8_t *>(ctx->dIdxBlob) + (blobAlloc - 8), 0, 8, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dIdxBlob, blob, blobLen, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dIdxLocs, streams, sizeof(DcsStreamLoc) * nStreams, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->dIdxOut, 0, sizeof(DcsFrameIndex) * (outCap ? outCap : 1), ctx->stream));
+    HIPCHK(ctx, ctx->dIdxBlob.room(blobAlloc));
+    HIPCHK(ctx, ctx->dIdxLocs.room(sizeof(DcsStreamLoc) * nStreams));
+    HIPCHK(ctx, ctx->dIdxOut.room(sizeof(DcsFrameIndex) * (outCap ? outCap : 1)));
+    HIPCHK(ctx, ctx->dIdxInfos.room(sizeof(DcsStreamInfo) * nStreams));
+    HIPCHK(ctx, hipMemsetAsync(ctx->dIdxBlob.as<uint8_t>() + (blobAlloc - 8), 0, 8, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dIdxBlob.as(), blob, blobLen, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dIdxLocs.as(), streams, sizeof(DcsStreamLoc) * nStreams, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->dIdxOut.as(), 0, sizeof(DcsFrameIndex) * (outCap ? outCap : 1), ctx->stream));
     ctx->idxBlobLen = blobLen;
     ctx->idxBlobDw = blobAlloc / 4;
     ctx->idxStreams = nStreams;
     ctx->idxCap = outCap;
     HIPCHK(ctx, launchIndex(ctx));
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->dIdxOut, sizeof(DcsFrameIndex) * outCap, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(infos, ctx->dIdxInfos, sizeof(DcsStreamInfo) * nStreams, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->dIdxOut.as(), sizeof(DcsFrameIndex) * outCap, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(infos, ctx->dIdxInfos.as(), sizeof(DcsStreamInfo) * nStreams, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return DCS_OK;
 }
@@ -1731,18 +1764,20 @@ extern "C" DcsStatus dcs_index_streams_gpu_time(DcsCtx *ctx, int iters, float *a
         return DCS_ERR_INVALID_ARG;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipEvent_t e0, e1;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    HIPCHK(ctx, hipEventCreate(&e1));
-    HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+    struct Events                       // (destroyed on every way out)
+    {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    HIPCHK(ctx, hipEventCreate(&ev.e0));
+    HIPCHK(ctx, hipEventCreate(&ev.e1));
+    HIPCHK(ctx, hipEventRecord(ev.e0, ctx->stream));
     for (int i = 0 ; i < iters ; ++i)
         HIPCHK(ctx, launchIndex(ctx));
-    HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(e1));
+    HIPCHK(ctx, hipEventRecord(ev.e1, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(ev.e1));
     float ms = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ev.e0, ev.e1));
     *avgMs = ms / static_cast<float>(iters);
     return DCS_OK;
 }
@@ -1780,18 +1815,17 @@ extern "C" DcsStatus dcs_ctx_clock_mhz(DcsCtx *ctx, float *mhzOut)
         return DCS_ERR_INVALID_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const uint32_t blocks = static_cast<uint32_t>(ctx->numCUs) * 4;
-    unsigned long long *d = nullptr;
-    HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&d), sizeof(unsigned long long) * 2 * blocks));
+    GrowBuf d;                          // (freed on every way out; a free waits for the device)
+    HIPCHK(ctx, d.room(sizeof(unsigned long long) * 2 * blocks));
     std::vector<unsigned long long> h(2 * static_cast<size_t>(blocks));
     hipError_t e = hipSuccess;
     for (int rep = 0 ; rep < 2 && e == hipSuccess ; ++rep)      // (the first launch only warms the chip up)
     {
-        hipLaunchKernelGGL(dcsClockKernel, dim3(blocks), dim3(256), 0, ctx->stream, d, 8000, 12345u + rep);
+        hipLaunchKernelGGL(dcsClockKernel, dim3(blocks), dim3(256), 0, ctx->stream, d.as<unsigned long long>(), 8000, 12345u + rep);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d.as(), sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     if (e != hipSuccess)
     {
         setError(ctx, std::string("clock probe failed: ") + hipGetErrorString(e));
