@@ -141,6 +141,13 @@ FLAC_FRAME_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u4"), ("blockSize",
                              ("headerLength", "<i4")], align=True)
 
 
+# dcs_flac_write_streams, dcs_decode_streams_flac: flags, and what was written per stream
+FLAC_MD5 = 1
+FLAC_SEQUENCE = 2
+FLAC_WRITE_INFO_DTYPE = np.dtype([("nSamples", "<u8"), ("nBytes", "<u8"), ("nBlocks", "<u4"), ("nConstant", "<u4"), ("nVerbatim", "<u4"),
+                                  ("nFixed", "<u4"), ("minFrame", "<u4"), ("maxFrame", "<u4")], align=True)
+
+
 # dcs_level_*: what happens to a stream's level between the converter and the encoder, and what the stage did
 class Level(ctypes.Structure):
     """DcsLevel.  Level(LEVEL_FIT, ceiling=1.0), Level(LEVEL_GAIN, gain=0.5), Level(LEVEL_GAIN, LEVEL_CLIP, 2.0, 0.9)"""
@@ -212,6 +219,7 @@ EXPORTS = [
     "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
     "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
     "dcs_flac_parse", "dcs_flac_index", "dcs_flac_decode",
+    "dcs_flac_write_bound", "dcs_flac_write_check", "dcs_flac_write_streams", "dcs_decode_streams_flac",
     "dcs_encode_sweep", "dcs_encode_sweep_group_frames", "dcs_encode_fit",
     "dcs_level_gain", "dcs_level_streams", "dcs_resample_streams_level", "dcs_encode_streams_at_level", "dcs_encode_files_level",
 ]
@@ -530,6 +538,14 @@ def load_library():
     L.dcs_flac_index.argtypes = [vp, sz, vp, u32, vp]
     L.dcs_flac_decode.restype = i32
     L.dcs_flac_decode.argtypes = [vp, vp, vp, u32, vp, sz, vp]
+    L.dcs_flac_write_bound.restype = ctypes.c_uint64
+    L.dcs_flac_write_bound.argtypes = [ctypes.c_uint64]
+    L.dcs_flac_write_check.restype = i32
+    L.dcs_flac_write_check.argtypes = [vp, u32, u32, u32, vp]
+    L.dcs_flac_write_streams.restype = i32
+    L.dcs_flac_write_streams.argtypes = [vp, vp, vp, u32, u32, u32, vp, sz, vp, vp]
+    L.dcs_decode_streams_flac.restype = i32
+    L.dcs_decode_streams_flac.argtypes = [vp, vp, u32, u32, u32, vp, sz, vp, vp, vp]
     L.dcs_encode_files.restype = i32
     L.dcs_encode_files.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32, vp, sz,
                                    vp, vp]
@@ -963,6 +979,19 @@ def flac_index(data):
     frames = np.zeros(int(n[0]), FLAC_FRAME_DTYPE)
     st = L.dcs_flac_index(_ptr(buf), len(b), _ptr(frames), frames.size, _ptr(n))
     return st, frames
+
+
+def flac_write_bound(n_samples):
+    """dcs_flac_write_bound: the largest FLAC stream n_samples samples can be written to"""
+    return int(load_library().dcs_flac_write_bound(int(n_samples)))
+
+
+def flac_write_check(lengths, rate=31250, flags=0):
+    """dcs_flac_write_check on streams of `lengths` samples -> (status, the stream at fault)"""
+    offs = np.concatenate(([0], np.cumsum(np.asarray(lengths, np.uint64)))).astype(np.uint64)
+    bad = ctypes.c_uint32()
+    st = load_library().dcs_flac_write_check(_ptr(offs), offs.size - 1, int(rate) & 0xFFFFFFFF, flags, ctypes.byref(bad))
+    return st, bad.value
 
 
 def encode_files_plan(files, version=0x9400, fmt=None, filter=None, at_unity=False, **params):
@@ -1412,6 +1441,59 @@ class Context:
         out = np.zeros(max(total, 1), np.float32)
         _check(self.L.dcs_flac_decode(self.h, _ptr(blob), _ptr(offs), n, _ptr(out), out.size, _ptr(out_offs)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].copy() for i in range(n)]
+
+    def _flac_written(self, call, n, cap):
+        """the writer's capacity protocol: one call with the bound's capacity -> (list of bytes, FLAC_WRITE_INFO_DTYPE array)"""
+        out = np.zeros(max(cap, 1), np.uint8)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info = np.zeros(max(n, 1), FLAC_WRITE_INFO_DTYPE)
+        _check(call(_ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
+        return [out[int(out_offs[i]):int(out_offs[i + 1])].tobytes() for i in range(n)], info[:n]
+
+    def flac_write_streams(self, pcm_list, rate=31250, md5=True):
+        """dcs_flac_write_streams: int16 PCM streams (whole frames of 240 samples) -> (list of FLAC streams as bytes,
+        FLAC_WRITE_INFO_DTYPE array); mono, 16 bits, block size 4096, the MD5 of the samples in STREAMINFO if md5"""
+        arrs = [np.ascontiguousarray(p, np.int16).ravel() for p in pcm_list]
+        n = len(arrs)
+        offs = np.zeros(n + 1, np.uint64)
+        offs[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+        pcm = np.concatenate(arrs) if n else np.zeros(1, np.int16)
+        cap = sum(flac_write_bound(a.size) for a in arrs)
+        flags = FLAC_MD5 if md5 else 0
+        return self._flac_written(lambda *o: self.L.dcs_flac_write_streams(self.h, _ptr(pcm), _ptr(offs), n, rate, flags, *o), n, cap)
+
+    def _decode_refs_flac(self, refs, n, frames, extra_frames, flags):
+        total = int(sum(frames)) + n * extra_frames
+        err = np.zeros(max(total, 1), np.uint32)
+        first = np.zeros(n + 1, np.uint32)
+        first[1:] = np.cumsum([f + extra_frames for f in frames])
+        cap = sum(flac_write_bound((f + extra_frames) * FRAME_SAMPLES) for f in frames)
+        out, info = self._flac_written(lambda *o: self.L.dcs_decode_streams_flac(self.h, refs, n, extra_frames, flags, *o, _ptr(err)), n, cap)
+        return out, info, err[:total], first
+
+    def decode_streams_flac(self, streams, extra_frames=0, md5=True):
+        """dcs_decode_streams_flac: (os, bytes, volume, level) streams decoded as decode_streams decodes them, the PCM kept on
+        the device and written as FLAC at 31 250 Hz there -> (list of FLAC streams as bytes, FLAC_WRITE_INFO_DTYPE array, err,
+        first_job)"""
+        streams = list(streams)
+        refs, keep = _stream_refs(streams)
+        frames = [(int(k[0]) << 8) | int(k[1]) for k in keep]
+        return self._decode_refs_flac(refs, len(streams), frames, extra_frames, FLAC_MD5 if md5 else 0)
+
+    def extract_streams_flac(self, romset, volume=255, extra_frames=2, md5=True):
+        """extract_streams whose PCM leaves the device as FLAC: -> (plan items, list of FLAC streams as bytes,
+        FLAC_WRITE_INFO_DTYPE array, first frame of each stream)"""
+        items = romset.extract_plan()
+        refs = romset.stream_refs(items, volume)
+        frames = []
+        for k in range(len(items)):
+            one = ctypes.c_uint64()
+            st = self.L.dcs_count_stream_frames(ctypes.byref(refs[k]), 1, 0, ctypes.byref(one))
+            if st != 0:
+                raise DcsError(st)
+            frames.append(one.value)
+        out, info, _, first = self._decode_refs_flac(refs, len(items), frames, extra_frames, FLAC_SEQUENCE | (FLAC_MD5 if md5 else 0))
+        return items, out, info, first
 
     def encode_files(self, files, version=0x9400, fmt=None, filter=None, at_unity=False, level=None, **params):
         """dcs_encode_files: DCSEncoder::EncodeFile on each file (bytes or paths): a DCSa container is copied or re-encoded as

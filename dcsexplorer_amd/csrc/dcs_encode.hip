@@ -2183,6 +2183,10 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
 
 #include "dcs_flac.hip.h"
 
+// ------------------------------------------------------------------------------ the FLAC writer (dcs_flac_write.hip.h)
+
+#include "dcs_flac_write.hip.h"
+
 // ------------------------------------------------------------------------ encoding files (dcs_encode_files.hip.h)
 
 #include "dcs_encode_files.hip.h"

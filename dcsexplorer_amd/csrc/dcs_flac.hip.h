@@ -139,7 +139,7 @@ struct FlacBits
             {
                 const int32_t z = __builtin_clzll(win);
                 count += static_cast<uint32_t>(z);
-                win <<= z + 1;
+                win = z == 63 ? 0 : win << (z + 1);             // (the run's one in the window's last bit: no shift by 64)
                 n -= z + 1;
                 left -= z + 1;
                 if (left >= 0)

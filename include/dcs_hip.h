@@ -46,7 +46,9 @@ extern "C" {
                                           DcsFlacFrame, DCS_WAV_S8, DCS_FILE_FLAC, dcs_flac_parse, dcs_flac_index,
                                           dcs_flac_decode; dcs_encode_files and dcs_encode_files_plan take FLAC files); level
                                           control (DcsLevel, DcsLevelInfo, DCS_LEVEL_*, dcs_level_gain, dcs_level_streams,
-                                          dcs_resample_streams_level, dcs_encode_streams_at_level, dcs_encode_files_level) */
+                                          dcs_resample_streams_level, dcs_encode_streams_at_level, dcs_encode_files_level);
+                                          writing FLAC (DcsFlacWriteInfo, DCS_FLAC_MD5, DCS_FLAC_SEQUENCE, dcs_flac_write_bound,
+                                          dcs_flac_write_check, dcs_flac_write_streams, dcs_decode_streams_flac) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -1034,6 +1036,41 @@ DcsStatus dcs_flac_index(const uint8_t *file, size_t len, DcsFlacFrame *frames, 
  * and capacity protocol.  A frame the device refuses is DCS_ERR_BAD_STREAM; dcs_last_error names file and frame. */
 DcsStatus dcs_flac_decode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles, float *out,
                           size_t outCap, uint64_t *outOffsets);
+
+/* ------------------------------------------------------------------------------------------------
+ * Writing FLAC (INTEGRATION.md "Writing FLAC"): int16 PCM -> one native FLAC stream per PCM stream, written on the device
+ * (W1 to W4, dcs_flac_write.hip.h).  Mono, 16 bits, fixed block size 4096, "fLaC" and one STREAMINFO block in front; each
+ * block is a CONSTANT, a VERBATIM or a FIXED subframe (orders 0..4, partitioned Rice coding with 4-bit parameters) by the
+ * rule stated there, so a stream's bytes are a function of its samples, the rate and the flag alone.  A stream is whole
+ * DCS frames: 240 x nFrames samples, nFrames >= 1. */
+#define DCS_FLAC_MD5      1u           /* STREAMINFO carries the MD5 of the samples (else 16 zero bytes: "not computed")     */
+#define DCS_FLAC_SEQUENCE 2u           /* dcs_decode_streams_flac only: decode as dcs_decode_stream_sequence does             */
+typedef struct DcsFlacWriteInfo       /* one per stream */
+{
+    uint64_t nSamples, nBytes;         /* nBytes: the whole stream, its 42 header bytes included                           */
+    uint32_t nBlocks, nConstant, nVerbatim, nFixed;         /* blocks, and how many of each kind of subframe                */
+    uint32_t minFrame, maxFrame;       /* the smallest and the largest frame in bytes, as STREAMINFO says them             */
+} DcsFlacWriteInfo;
+/* host only: 42 + blocks x (16 + 1 + 2 x 4096 + 2), blocks = ceil(nSamples / 4096).  Always enough: a block that FIXED
+ * would not make smaller is written VERBATIM. */
+uint64_t  dcs_flac_write_bound(uint64_t nSamples);
+/* host only: the check dcs_flac_write_streams makes before any device work.  DCS_ERR_INVALID_ARG: a stream that is not
+ * whole frames (empty, or not a multiple of 240 samples) or has 2^36 samples or more, falling offsets, a rate outside
+ * 1 .. 65 535, an unknown flag, more than 2^31 - 1 blocks in all.  *badStream (optional): the stream at fault, else 0. */
+DcsStatus dcs_flac_write_check(const uint64_t *sampleOffsets, uint32_t nStreams, uint32_t rate, uint32_t flags, uint32_t *badStream);
+/* Stream k = pcm[sampleOffsets[k] .. sampleOffsets[k + 1]) (host memory) at `rate` Hz; its FLAC stream goes to
+ * out + outOffsets[k].  flags: DCS_FLAC_MD5 or 0.  outOffsets (nStreams + 1) is filled, and info (optional, nStreams),
+ * whenever the sizes are known: DCS_ERR_CAPACITY means outCap < outOffsets[nStreams], and nothing was written.
+ * DCS_ERR_INVALID_ARG: see dcs_flac_write_check; dcs_last_error names the stream. */
+DcsStatus dcs_flac_write_streams(DcsCtx *ctx, const int16_t *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, uint32_t rate,
+                                 uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsFlacWriteInfo *info);
+/* dcs_decode_streams (with DCS_FLAC_SEQUENCE: dcs_decode_stream_sequence, and its argument rules) whose PCM stays on the
+ * device and leaves it as FLAC at 31 250 Hz: stream k's nFrames + extraFrames frames are one FLAC stream at
+ * out + outOffsets[k].  Only the FLAC bytes and the per-frame error words (errOut, optional, one per decoded frame as
+ * dcs_decode_streams gives them) come down.  A stream with a fatal frame is written all the same: it is the PCM the
+ * decoder produced.  Capacity protocol and info as dcs_flac_write_streams. */
+DcsStatus dcs_decode_streams_flac(DcsCtx *ctx, const DcsStreamRef *streams, uint32_t nStreams, uint32_t extraFrames, uint32_t flags,
+                                  uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsFlacWriteInfo *info, uint32_t *errOut);
 
 /* ------------------------------------------------------------------------------------------------
  * Level: what happens to a signal's level between the converter and the encoder ("Level", rules 26-33).
