@@ -69,6 +69,16 @@ class PipelineResult(ctypes.Structure):
                 ("hostMs", ctypes.c_float), ("deviceMs", ctypes.c_float), ("path", ctypes.c_uint32)]
 
 
+# DcsPipelineFlacResult: what dcs_pipeline_collect_flac fills for a list of a FLAC pipeline (PIPE_FLAC, PIPE_FLAC_MD5)
+PIPE_FLAC, PIPE_FLAC_MD5 = 8, 16
+
+
+class PipelineFlacResult(ctypes.Structure):
+    _fields_ = [("flac", ctypes.c_void_p), ("flacOffsets", ctypes.c_void_p), ("info", ctypes.c_void_p), ("err", ctypes.c_void_p),
+                ("frameOffsets", ctypes.c_void_p), ("nFrames", ctypes.c_uint32), ("nStreams", ctypes.c_uint32),
+                ("status", ctypes.c_int32), ("hostMs", ctypes.c_float), ("deviceMs", ctypes.c_float), ("path", ctypes.c_uint32)]
+
+
 class DevicePathTimes(ctypes.Structure):
     _fields_ = [("passMs", ctypes.c_float), ("indexMs", ctypes.c_float), ("planMs", ctypes.c_float), ("packMs", ctypes.c_float),
                 ("decodeMs", ctypes.c_float), ("planFlags", ctypes.c_uint32), ("nStreams", ctypes.c_uint32), ("nFrames", ctypes.c_uint32),
@@ -209,7 +219,7 @@ EXPORTS = [
     "dcs_decode_batch_live", "dcs_seq_decode_view", "dcs_seq_plan_ahead", "dcs_seq_stream_playing_at", "dcs_seq_tracks_active_at", "dcs_ctx_call_floor",
     "dcs_host_threads", "dcs_partition_streams", "dcs_decode_streams_sharded",
     "dcs_ctx_set_frames_per_chunk", "dcs_index_stream_literal", "dcs_pack_chunks_device", "dcs_batch_abi_bytes", "dcs_batch_num_chunks", "dcs_batch_frames_per_wave", "dcs_ctx_set_chunks_per_wave", "dcs_batch_chunks_per_wave", "dcs_ctx_clock_mhz", "dcs_ctx_link_rate", "dcs_ctx_set_test_hooks",
-    "dcs_pipeline_create", "dcs_pipeline_destroy", "dcs_pipeline_submit", "dcs_pipeline_collect",
+    "dcs_pipeline_create", "dcs_pipeline_destroy", "dcs_pipeline_submit", "dcs_pipeline_collect", "dcs_pipeline_collect_flac",
     "dcs_device_path_create", "dcs_device_path_run", "dcs_device_path_run_many", "dcs_device_path_download", "dcs_device_path_destroy",
     "dcs_node_create", "dcs_node_destroy", "dcs_node_submit", "dcs_node_collect", "dcs_node_num_devices", "dcs_node_device_info",
     "dcs_node_last_error", "dcs_node_cache_release", "dcs_device_numa_node",
@@ -467,6 +477,8 @@ def load_library():
     L.dcs_pipeline_submit.argtypes = [vp, vp, u32, u32]
     L.dcs_pipeline_collect.restype = i32
     L.dcs_pipeline_collect.argtypes = [vp, ctypes.POINTER(PipelineResult)]
+    L.dcs_pipeline_collect_flac.restype = i32
+    L.dcs_pipeline_collect_flac.argtypes = [vp, ctypes.POINTER(PipelineFlacResult)]
     L.dcs_device_path_create.restype = i32
     L.dcs_device_path_create.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.dcs_device_path_run.restype = i32
@@ -1610,8 +1622,8 @@ class Context:
     def device_path(self, streams, extra_frames=0):
         return DevicePath(self, streams, extra_frames)
 
-    def pipeline(self, depth=3, index_on_device=False, pack_on_device=False, plan_on_device=False):
-        return Pipeline(self, depth, index_on_device, pack_on_device, plan_on_device)
+    def pipeline(self, depth=3, index_on_device=False, pack_on_device=False, plan_on_device=False, flac=False, md5=True):
+        return Pipeline(self, depth, index_on_device, pack_on_device, plan_on_device, flac, md5)
 
     def pack_chunks_device(self, blob, srcs, jobs, fpw):
         """dcs_pack_chunks_device -> uint8 array [nChunks, packageBytes], assembled by the device packer"""
@@ -1745,13 +1757,15 @@ class Batch:
 
 
 class Pipeline:
-    """DcsPipeline: lists of whole streams in, PCM out in submission order, `depth` lists in flight"""
+    """DcsPipeline: lists of whole streams in, PCM out in submission order, `depth` lists in flight.  flac=True: the lists
+    leave the device as FLAC at 31 250 Hz (with the samples' MD5 if md5) and are collected with collect_flac()"""
 
-    def __init__(self, ctx, depth=3, index_on_device=False, pack_on_device=False, plan_on_device=False):
+    def __init__(self, ctx, depth=3, index_on_device=False, pack_on_device=False, plan_on_device=False, flac=False, md5=True):
         self.ctx = ctx
         self.L = ctx.L
         h = ctypes.c_void_p()
         flags = (1 if index_on_device else 0) | (2 if pack_on_device else 0) | (4 if plan_on_device else 0)
+        flags |= (PIPE_FLAC | (PIPE_FLAC_MD5 if md5 else 0)) if flac else 0
         _check(self.L.dcs_pipeline_create(ctx.h, depth, flags, ctypes.byref(h)), ctx.h)
         self.h = h
         self._keep = []                         # (refs, byte buffers) of submitted lists, oldest first
@@ -1774,13 +1788,31 @@ class Pipeline:
         r = PipelineResult()
         st = self.L.dcs_pipeline_collect(self.h, ctypes.byref(r))
         self.last_path = int(r.path)
-        if self._keep:
+        if self._keep and st != ERR_INVALID_ARG:        # (refused: the list is still the pipeline's, and its streams stay)
             self._keep.pop(0)
         _check(st, self.ctx.h)
         pcm = _view(r.pcm, ctypes.c_int16, np.int16, (r.nFrames, FRAME_SAMPLES))
         err = _view(r.err, ctypes.c_uint32, np.uint32, (r.nFrames,))
         first = _view(r.frameOffsets, ctypes.c_uint32, np.uint32, (r.nStreams + 1,))
         return pcm, err, first, r.hostMs, r.deviceMs
+
+    def collect_flac(self):
+        """a FLAC pipeline's collect -> (list of FLAC streams as bytes, FLAC_WRITE_INFO_DTYPE array, err, first frame of each
+        stream, hostMs, deviceMs): copies of the pipeline's pinned memory.  self.last_path as collect() sets it"""
+        r = PipelineFlacResult()
+        st = self.L.dcs_pipeline_collect_flac(self.h, ctypes.byref(r))
+        self.last_path = int(r.path)
+        if self._keep and st != ERR_INVALID_ARG:
+            self._keep.pop(0)
+        _check(st, self.ctx.h)
+        n = int(r.nStreams)
+        offs = _view(r.flacOffsets, ctypes.c_uint64, np.uint64, (n + 1,))
+        flac = _view(r.flac, ctypes.c_uint8, np.uint8, (int(offs[n]),))
+        out = [flac[int(offs[k]):int(offs[k + 1])].tobytes() for k in range(n)]
+        info = np.frombuffer(ctypes.string_at(r.info, FLAC_WRITE_INFO_DTYPE.itemsize * n), FLAC_WRITE_INFO_DTYPE).copy()
+        err = _view(r.err, ctypes.c_uint32, np.uint32, (r.nFrames,)).copy()
+        first = _view(r.frameOffsets, ctypes.c_uint32, np.uint32, (n + 1,)).copy()
+        return out, info, err, first, r.hostMs, r.deviceMs
 
     def close(self):
         if self.h:

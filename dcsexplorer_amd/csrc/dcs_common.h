@@ -190,6 +190,7 @@ DcsStatus dcsIndexStreamsNotify(const DcsStreamRef *streams, uint32_t nStreams, 
                                 DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos,
                                 const std::function<void(uint32_t)> *done);
 bool dcsIndexPoolBusy();
+void dcsHostPoolRun(uint32_t n, int threads, const std::function<void(uint32_t)> &fn);
 // the host walk with its records handed over frame by frame, and the container part of it alone (dcs_index.cpp)
 DcsStatus dcsIndexStreamProgressive(DcsOsVersion os, const uint8_t *stream, size_t len, DcsStreamInfo *info,
                                     const std::function<void(uint32_t, const DcsFrameIndex &)> &onFrame);

@@ -3,8 +3,9 @@
 // dcs_encode.hip's unit) where it lies in HBM, as dcs_transcode_streams hands it to the encoder.  Included at the end of
 // dcs_runtime.hip.  The FLAC bytes and the error words come down; the PCM does not.
 #pragma once
+#include "dcs_flac_held.h"
 
-// dcs_flac_write.hip.h
+// dcs_flac_write.hip.h (dcsFlacWriteQueue, which a pipeline's lists go through, is declared in dcs_flac_held.h)
 DcsStatus dcsFlacWriteFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint64_t *sampleOffsets, uint32_t n, uint32_t rate,
                                  uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsFlacWriteInfo *info);
 

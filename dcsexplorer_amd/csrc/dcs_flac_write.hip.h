@@ -12,10 +12,19 @@
 //                       only a code's one and low bits, the unary zeros are the buffer's), both CRCs from per-lane parts
 //                       moved to their place by powers of x (a CRC is linear), and the copy out, dwords where aligned
 //   W4 fwMd5Kernel      DCS_FLAC_MD5 only: one lane per stream walks its samples in 64-byte blocks (the chain is serial)
-// The host sits between W2 and W3 once, as the encoders' size-then-place step does: it reads the streams' sizes, fills
-// outOffsets, checks the capacity and borrows the output buffer.  It also writes the 42 bytes in front of each stream
-// ("fLaC" and STREAMINFO), from FwSum and W4's digests.
+// Nothing comes back to the host between them.  Three more kernels stand where the host's size-then-place step would:
+//      fwBaseKernel     one workgroup: the exclusive scan of the streams' sizes (rounds of 256 with a carried total: a scan in
+//                       each wavefront, the wavefronts' totals through LDS, as W2's within a stream), which is W3's dBase and,
+//                       with FwSum and the block table, the result table as the ABI lays it out (outOffsets, DcsFlacWriteInfo)
+//                       and the total in a word of its own
+//      fwHeadKernel     the 42 bytes in front of each stream ("fLaC" and STREAMINFO, from FwSum and W4's digests), one lane
+//                       per byte: stream bases fall at every alignment, and a lane stores nothing but its own byte
+//      fwDownKernel     16-byte copies in a grid-stride loop whose length is read from a word on the DEVICE: the FLAC bytes go
+//                       to pinned host memory without the host knowing, when it queues the copy, how many there are
+// dcsFlacWriteQueue (dcs_flac_held.h) is the one statement of the order they are queued in; the output in HBM and its pinned
+// staging are sized by a bound the host knows beforehand (fwBound: every block VERBATIM).
 #pragma once
+#include "dcs_flac_held.h"
 
 namespace {
 
@@ -609,6 +618,101 @@ __global__ __launch_bounds__(64) void fwMd5Kernel(const int16_t *pcm, const uint
         digest[4 * k + i] = h[i];
 }
 
+// ------------------------------------------------------------------------------------------------------------ base
+// byte i of the 42 in front of a stream: "fLaC", the header of STREAMINFO as the last metadata block, STREAMINFO
+__host__ __device__ inline uint32_t fwHeadByte(uint32_t i, uint32_t rate, uint64_t nSamples, uint32_t minFrame, uint32_t maxFrame,
+                                               const uint32_t *digest)
+{
+    if (i < 4) return i == 0 ? 'f' : i == 1 ? 'L' : i == 2 ? 'a' : 'C';
+    if (i < 8) return i == 4 ? 0x80u : i == 7 ? 34u : 0u;
+    if (i < 12) return (i & 1) == 0 ? kFwBlock >> 8 : kFwBlock & 0xFF;
+    if (i < 15) return (minFrame >> (16 - 8 * (i - 12))) & 0xFF;
+    if (i < 18) return (maxFrame >> (16 - 8 * (i - 15))) & 0xFF;
+    if (i < 26)
+    {
+        const uint64_t v = (static_cast<uint64_t>(rate) << 44) | (0ull << 41) | (15ull << 36) | nSamples;
+        return static_cast<uint32_t>(v >> (56 - 8 * (i - 18))) & 0xFF;
+    }
+    // (the digest's words are little-endian)
+    return digest != nullptr ? (digest[(i - 26) >> 2] >> (8 * ((i - 26) & 3))) & 0xFF : 0u;
+}
+
+__global__ __launch_bounds__(kFwThreads) void fwBaseKernel(const FwSum *sums, const uint64_t *offs, const uint32_t *blockFirst, uint32_t nStreams,
+                                                           unsigned long long *base, uint64_t *outOffsets, uint64_t *total,
+                                                           DcsFlacWriteInfo *info)
+{
+    __shared__ unsigned long long waveTotal[kFwThreads / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    unsigned long long carry = 0;
+    for (uint32_t first = 0 ; first < nStreams ; first += kFwThreads)   // (the same rounds for every lane: the barriers below)
+    {
+        const uint32_t k = first + t;
+        FwSum s = {};
+        if (k < nStreams)
+            s = sums[k];
+        unsigned long long incl = s.bytes;
+        for (int d = 1 ; d < 64 ; d <<= 1)
+        {
+            const unsigned long long up = __shfl_up(incl, d, 64);
+            if (lane >= static_cast<uint32_t>(d))
+                incl += up;
+        }
+        if (lane == 63)
+            waveTotal[wave] = incl;
+        __syncthreads();
+        unsigned long long before = carry;
+        for (uint32_t v = 0 ; v < kFwThreads / 64 ; ++v)
+        {
+            if (v < wave)
+                before += waveTotal[v];
+            carry += waveTotal[v];
+        }
+        if (k < nStreams)
+        {
+            const unsigned long long at = before + incl - s.bytes;
+            base[k] = at;
+            outOffsets[k] = at;
+            info[k] = DcsFlacWriteInfo{ offs[k + 1] - offs[k], s.bytes, blockFirst[k + 1] - blockFirst[k], s.nConstant, s.nVerbatim, s.nFixed,
+                                        s.minFrame, s.maxFrame };
+        }
+        __syncthreads();                                // (waveTotal is the next round's)
+    }
+    if (t == 0)
+    {
+        outOffsets[nStreams] = carry;
+        *total = carry;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ head
+__global__ __launch_bounds__(kFwThreads) void fwHeadKernel(const FwSum *sums, const uint64_t *offs, const unsigned long long *base,
+                                                           const uint32_t *digest, uint32_t nStreams, uint32_t rate, uint8_t *out)
+{
+    const uint64_t at = static_cast<uint64_t>(blockIdx.x) * kFwThreads + threadIdx.x;
+    const uint64_t k = at / kFwHeadBytes;
+    if (k >= nStreams)
+        return;
+    const uint32_t i = static_cast<uint32_t>(at - k * kFwHeadBytes);
+    out[base[k] + i] = static_cast<uint8_t>(fwHeadByte(i, rate, offs[k + 1] - offs[k], sums[k].minFrame, sums[k].maxFrame,
+                                                       digest != nullptr ? digest + 4 * k : nullptr));
+}
+
+// ------------------------------------------------------------------------------------------------------------ down
+// *count bytes (null: all of cap16 x 16), rounded up to 16 and never more than cap16 x 16, from src to dst: both 16-byte aligned,
+// both at least cap16 x 16 bytes long
+__global__ __launch_bounds__(kFwThreads) void fwDownKernel(uint4 *dst, const uint4 *src, const uint64_t *count, uint64_t cap16)
+{
+    uint64_t n16 = cap16;
+    if (count != nullptr)
+    {
+        const uint64_t want = (*count + 15) / 16;
+        n16 = want < cap16 ? want : cap16;
+    }
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kFwThreads;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kFwThreads + threadIdx.x ; i < n16 ; i += stride)
+        dst[i] = src[i];
+}
+
 // ------------------------------------------------------------------------------------------------------------ host
 // what dcs_flac_write_streams checks before any device work; *bad = the stream at fault
 DcsStatus fwCheck(const uint64_t *offs, uint32_t n, uint32_t rate, uint32_t flags, uint32_t *bad, std::string &why)
@@ -636,23 +740,23 @@ DcsStatus fwCheck(const uint64_t *offs, uint32_t n, uint32_t rate, uint32_t flag
     return DCS_OK;
 }
 
-void fwStreamHead(uint8_t *p, uint32_t rate, uint64_t nSamples, const FwSum &sum, const uint32_t *digest)
+// what the streams of a call can come to at most: 42 bytes a stream, and every block VERBATIM behind the longest frame header
+// (16 + 1 + 2 n + 2 for a block of n samples; W1 writes a block so where FIXED would not make it smaller)
+uint64_t fwBound(const uint64_t *offs, uint32_t n, uint32_t nBlocks)
 {
-    memcpy(p, "fLaC", 4);
-    p[4] = 0x80; p[5] = 0; p[6] = 0; p[7] = 34;                 // STREAMINFO, the last metadata block
-    p[8] = p[10] = kFwBlock >> 8; p[9] = p[11] = kFwBlock & 0xFF;
-    for (int i = 0 ; i < 3 ; ++i)
-    {
-        p[12 + i] = static_cast<uint8_t>(sum.minFrame >> (16 - 8 * i));
-        p[15 + i] = static_cast<uint8_t>(sum.maxFrame >> (16 - 8 * i));
-    }
-    const uint64_t v = (static_cast<uint64_t>(rate) << 44) | (0ull << 41) | (15ull << 36) | nSamples;
-    for (int i = 0 ; i < 8 ; ++i)
-        p[18 + i] = static_cast<uint8_t>(v >> (56 - 8 * i));
-    if (digest != nullptr)
-        memcpy(p + 26, digest, 16);                             // (the digest's words are little-endian, as the host is)
-    else
-        memset(p + 26, 0, 16);
+    return static_cast<uint64_t>(kFwHeadBytes) * n + 19ull * nBlocks + 2 * (offs[n] - offs[0]);
+}
+
+hipError_t fwCopy16(hipStream_t stream, void *dst, const void *src, const uint64_t *count, uint64_t capBytes, unsigned blockCap)
+{
+    const uint64_t cap16 = capBytes / 16;
+    if (cap16 == 0)
+        return hipSuccess;
+    if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) != 0)
+        return hipErrorInvalidValue;
+    const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((cap16 + kFwThreads - 1) / kFwThreads, std::max(1u, blockCap)));
+    hipLaunchKernelGGL(fwDownKernel, dim3(blocks), dim3(kFwThreads), 0, stream, static_cast<uint4 *>(dst), static_cast<const uint4 *>(src), count, cap16);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -672,9 +776,108 @@ extern "C" DcsStatus dcs_flac_write_check(const uint64_t *sampleOffsets, uint32_
     return st;
 }
 
+// dcs_index.cpp: the host pool
+void dcsHostPoolRun(uint32_t n, int threads, const std::function<void(uint32_t)> &fn);
+bool dcsIndexPoolBusy();
+
+// the one copy from pinned staging into the caller's (pageable) buffer: megabytes of it go in parts on the host pool's threads,
+// since one thread moves them slower than the link brought them down
+static void fwCopyOut(uint8_t *dst, const uint8_t *src, size_t bytes)
+{
+    constexpr size_t kPart = size_t(1) << 20;
+    const uint32_t parts = static_cast<uint32_t>((bytes + kPart - 1) / kPart);
+    const int threads = std::min<int>({ static_cast<int>(parts / 2), dcs_host_threads(), 8 });
+    if (threads < 2 || dcsIndexPoolBusy())
+    {
+        memcpy(dst, src, bytes);
+        return;
+    }
+    dcsHostPoolRun(parts, threads, [&](uint32_t k) {
+        const size_t from = static_cast<size_t>(k) * kPart;
+        memcpy(dst + from, src + from, std::min(kPart, bytes - from));
+    });
+}
+
+DcsStatus dcsFlacWriteQueue(DcsCtx *ctx, hipStream_t stream, const int16_t *dPcm, const uint64_t *sampleOffsets, uint32_t n, uint32_t rate,
+                            uint32_t flags, FlacHeld &held, unsigned downBlocks)
+{
+    if (ctx == nullptr || n == 0)
+        return DCS_ERR_INVALID_ARG;
+    uint32_t bad = 0;
+    std::string why;
+    const DcsStatus checked = fwCheck(sampleOffsets, n, rate, flags, &bad, why);
+    if (checked != DCS_OK)
+    {
+        dcsCtxSetError(ctx, why.c_str());
+        return checked;
+    }
+    const bool md5 = (flags & DCS_FLAC_MD5) != 0;
+    auto blocksOf = [&](uint32_t k) { return static_cast<uint32_t>((sampleOffsets[k + 1] - sampleOffsets[k] + kFwBlock - 1) / kFwBlock); };
+    uint32_t nBlocks = 0;
+    for (uint32_t k = 0 ; k < n ; ++k)
+        nBlocks += blocksOf(k);
+
+    // the device's working memory, every part on a 256-byte boundary: what goes up first, the table that comes down last
+    size_t need = 0;
+    auto part = [&](size_t bytes) { const size_t at = need; need += (bytes + 255) & ~size_t(255); return at; };
+    const size_t nn = static_cast<size_t>(n);
+    const size_t offsAt = part(sizeof(uint64_t) * (nn + 1) + sizeof(uint32_t) * (nn + 1)), firstAt = offsAt + sizeof(uint64_t) * (nn + 1);
+    const size_t upBytes = need;
+    const size_t recAt = part(sizeof(FwRec) * nBlocks), relAt = part(sizeof(unsigned long long) * nBlocks), sumsAt = part(sizeof(FwSum) * nn),
+                 baseAt = part(sizeof(unsigned long long) * nn), digestAt = part(sizeof(uint32_t) * 4 * nn);
+    const size_t tableAt = part(FlacHeld::tableBytes(n)), tableBytes = need - tableAt;
+    held.n = n;
+    held.bound = fwBound(sampleOffsets, n, nBlocks);
+    const size_t outBytes = (static_cast<size_t>(held.bound) + 255) & ~size_t(255);
+    ENCCHK(held.dWork.alloc(ctx, false, need));
+    ENCCHK(held.dOut.alloc(ctx, false, outBytes));
+    ENCCHK(held.hUp.alloc(ctx, true, upBytes));
+    ENCCHK(held.hTable.alloc(ctx, true, tableBytes));
+    ENCCHK(held.hOut.alloc(ctx, true, outBytes));
+
+    uint8_t *dWork = held.dWork.as<uint8_t>(), *dOut = held.dOut.as<uint8_t>();
+    uint64_t *hOffs = held.hUp.as<uint64_t>();
+    uint32_t *hFirst = reinterpret_cast<uint32_t *>(held.hUp.as<uint8_t>() + firstAt);
+    memcpy(hOffs, sampleOffsets, sizeof(uint64_t) * (nn + 1));
+    hFirst[0] = 0;
+    for (uint32_t k = 0 ; k < n ; ++k)
+        hFirst[k + 1] = hFirst[k] + blocksOf(k);
+    const uint64_t *dOffs = reinterpret_cast<const uint64_t *>(dWork + offsAt);
+    const uint32_t *dBlockFirst = reinterpret_cast<const uint32_t *>(dWork + firstAt);
+    FwRec *dRec = reinterpret_cast<FwRec *>(dWork + recAt);
+    unsigned long long *dRel = reinterpret_cast<unsigned long long *>(dWork + relAt), *dBase = reinterpret_cast<unsigned long long *>(dWork + baseAt);
+    FwSum *dSums = reinterpret_cast<FwSum *>(dWork + sumsAt);
+    uint32_t *dDigest = md5 ? reinterpret_cast<uint32_t *>(dWork + digestAt) : nullptr;
+    uint64_t *dOutOffsets = reinterpret_cast<uint64_t *>(dWork + tableAt), *dTotal = dOutOffsets + nn + 1;
+    DcsFlacWriteInfo *dInfo = reinterpret_cast<DcsFlacWriteInfo *>(dOutOffsets + nn + 2);
+
+    ENCCHK(fwCopy16(stream, dWork + offsAt, hOffs, nullptr, upBytes, 64));
+    hipLaunchKernelGGL(fwChooseKernel, dim3(nBlocks), dim3(kFwThreads), 0, stream, dPcm, dOffs, dBlockFirst, n, nBlocks, dRec);
+    ENCCHK(hipGetLastError());
+    hipLaunchKernelGGL(fwPlaceKernel, dim3((n + kFwThreads / 64 - 1) / (kFwThreads / 64)), dim3(kFwThreads), 0, stream, dBlockFirst, n,
+                       dRec, dRel, dSums);
+    ENCCHK(hipGetLastError());
+    hipLaunchKernelGGL(fwBaseKernel, dim3(1), dim3(kFwThreads), 0, stream, dSums, dOffs, dBlockFirst, n, dBase, dOutOffsets, dTotal, dInfo);
+    ENCCHK(hipGetLastError());
+    if (md5)
+    {
+        hipLaunchKernelGGL(fwMd5Kernel, dim3((n + 63) / 64), dim3(64), 0, stream, dPcm, dOffs, n, dDigest);
+        ENCCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(fwHeadKernel, dim3(static_cast<uint32_t>((nn * kFwHeadBytes + kFwThreads - 1) / kFwThreads)), dim3(kFwThreads), 0, stream,
+                       dSums, dOffs, dBase, dDigest, n, rate, dOut);
+    ENCCHK(hipGetLastError());
+    hipLaunchKernelGGL(fwWriteKernel, dim3(nBlocks), dim3(kFwThreads), 0, stream, dPcm, dOffs, dBlockFirst, n, nBlocks, dRec, dRel, dBase,
+                       rate, dOut);
+    ENCCHK(hipGetLastError());
+    ENCCHK(fwCopy16(stream, held.hTable.as(), dWork + tableAt, nullptr, tableBytes, 64));
+    ENCCHK(fwCopy16(stream, held.hOut.as(), dOut, dTotal, outBytes, downBlocks));
+    return DCS_OK;
+}
+
 // The writer on PCM that lies in HBM (stream k = dPcm[sampleOffsets[k] .. sampleOffsets[k + 1]), offsets on the host): the body of
 // dcs_flac_write_streams, and what dcs_decode_streams_flac (dcs_decode_flac.hip.h) hands a batch's PCM to.  Everything is
-// queued on the context's stream; the PCM has to stay until this returns.
+// queued on the context's stream and waited for once; the PCM has to stay until this returns.
 DcsStatus dcsFlacWriteFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint64_t *sampleOffsets, uint32_t n, uint32_t rate,
                                  uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsFlacWriteInfo *info)
 {
@@ -691,69 +894,30 @@ DcsStatus dcsFlacWriteFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint64_
     outOffsets[0] = 0;
     if (n == 0)
         return DCS_OK;
-    std::vector<uint32_t> blockFirst(static_cast<size_t>(n) + 1, 0);
-    for (uint32_t k = 0 ; k < n ; ++k)
-        blockFirst[k + 1] = blockFirst[k] + static_cast<uint32_t>((sampleOffsets[k + 1] - sampleOffsets[k] + kFwBlock - 1) / kFwBlock);
-    const uint32_t nBlocks = blockFirst[n];
-    const bool md5 = (flags & DCS_FLAC_MD5) != 0;
-
-    // (host ends of the copies below: they outlive the arena, whose going waits for the stream)
-    std::vector<FwSum> sums(n);
-    std::vector<uint32_t> digest(md5 ? static_cast<size_t>(n) * 4 : 0);
-    std::vector<unsigned long long> base(n);
-
     ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
-    CacheArena held(ctx);
-    hipStream_t stream = held.stream();
-    uint64_t *dOffs = nullptr;
-    uint32_t *dBlockFirst = nullptr, *dDigest = nullptr;
-    FwRec *dRec = nullptr;
-    unsigned long long *dRel = nullptr, *dBase = nullptr;
-    FwSum *dSums = nullptr;
-    ENCCHK(held.alloc(&dOffs, static_cast<size_t>(n) + 1));
-    ENCCHK(held.alloc(&dBlockFirst, static_cast<size_t>(n) + 1));
-    ENCCHK(held.alloc(&dRec, nBlocks));
-    ENCCHK(held.alloc(&dRel, nBlocks));
-    ENCCHK(held.alloc(&dSums, n));
-    ENCCHK(held.alloc(&dBase, n));
-    ENCCHK(held.alloc(&dDigest, static_cast<size_t>(n) * 4));
-    ENCCHK(hipMemcpyAsync(dOffs, sampleOffsets, sizeof(uint64_t) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice, stream));
-    ENCCHK(hipMemcpyAsync(dBlockFirst, blockFirst.data(), sizeof(uint32_t) * blockFirst.size(), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(fwChooseKernel, dim3(nBlocks), dim3(kFwThreads), 0, stream, dPcm, dOffs, dBlockFirst, n, nBlocks, dRec);
-    ENCCHK(hipGetLastError());
-    hipLaunchKernelGGL(fwPlaceKernel, dim3((n + kFwThreads / 64 - 1) / (kFwThreads / 64)), dim3(kFwThreads), 0, stream, dBlockFirst, n,
-                       dRec, dRel, dSums);
-    ENCCHK(hipGetLastError());
-    ENCCHK(hipMemcpyAsync(sums.data(), dSums, sizeof(FwSum) * n, hipMemcpyDeviceToHost, stream));
-    if (md5)
-    {
-        hipLaunchKernelGGL(fwMd5Kernel, dim3((n + 63) / 64), dim3(64), 0, stream, dPcm, dOffs, n, dDigest);
-        ENCCHK(hipGetLastError());
-        ENCCHK(hipMemcpyAsync(digest.data(), dDigest, sizeof(uint32_t) * digest.size(), hipMemcpyDeviceToHost, stream));
-    }
-    ENCCHK(hipStreamSynchronize(stream));
-
-    for (uint32_t k = 0 ; k < n ; ++k)
-    {
-        base[k] = outOffsets[k];
-        outOffsets[k + 1] = outOffsets[k] + sums[k].bytes;
-        if (info != nullptr)
-            info[k] = DcsFlacWriteInfo{ sampleOffsets[k + 1] - sampleOffsets[k], sums[k].bytes, blockFirst[k + 1] - blockFirst[k],
-                                        sums[k].nConstant, sums[k].nVerbatim, sums[k].nFixed, sums[k].minFrame, sums[k].maxFrame };
-    }
-    const uint64_t total = outOffsets[n];
+    hipStream_t stream = dcsCtxStream(ctx);
+    FlacHeld held;
+    // (DCS_FLAC_TRACE: where a call's time goes, on stderr)
+    static const bool trace = getenv("DCS_FLAC_TRACE") != nullptr;
+    const auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = trace ? now() : 0;
+    const DcsStatus queued = dcsFlacWriteQueue(ctx, stream, dPcm, sampleOffsets, n, rate, flags, held, 1024);
+    const double t1 = trace ? now() : 0;
+    const hipError_t waited = hipStreamSynchronize(stream);         // (also for a run that failed half queued: its buffers go back)
+    const double t2 = trace ? now() : 0;
+    if (queued != DCS_OK)
+        return queued;
+    ENCCHK(waited);
+    memcpy(outOffsets, held.offsets(), sizeof(uint64_t) * (static_cast<size_t>(n) + 1));
+    if (info != nullptr)
+        memcpy(info, held.info(), sizeof(DcsFlacWriteInfo) * n);
+    const uint64_t total = held.total();
     if (out == nullptr || outCap < total)
         return DCS_ERR_CAPACITY;
-    uint8_t *dOut = nullptr;
-    ENCCHK(held.alloc(&dOut, total));
-    ENCCHK(hipMemcpyAsync(dBase, base.data(), sizeof(unsigned long long) * n, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(fwWriteKernel, dim3(nBlocks), dim3(kFwThreads), 0, stream, dPcm, dOffs, dBlockFirst, n, nBlocks, dRec, dRel, dBase,
-                       rate, dOut);
-    ENCCHK(hipGetLastError());
-    ENCCHK(hipMemcpyAsync(out, dOut, total, hipMemcpyDeviceToHost, stream));
-    ENCCHK(hipStreamSynchronize(stream));
-    for (uint32_t k = 0 ; k < n ; ++k)
-        fwStreamHead(out + base[k], rate, sampleOffsets[k + 1] - sampleOffsets[k], sums[k], md5 ? digest.data() + 4 * static_cast<size_t>(k) : nullptr);
+    fwCopyOut(out, held.bytes(), total);
+    if (trace)
+        fprintf(stderr, "flac write: queue %.3f ms, wait %.3f ms, copy out %.3f ms (%llu bytes)\n", t1 - t0, t2 - t1, now() - t2,
+                static_cast<unsigned long long>(total));
     return DCS_OK;
 }
 

@@ -353,6 +353,12 @@ private:
 // (dcs_node, dcs_decode_streams_sharded: a thread per device) would otherwise walk their lists one after the other on it
 bool dcsIndexPoolBusy() { return IndexPool::get().busy() > 0; }
 
+// fn(k) for k in [0, n) on up to `threads` threads of that pool, the caller among them (one parallel region at a time)
+void dcsHostPoolRun(uint32_t n, int threads, const std::function<void(uint32_t)> &fn)
+{
+    IndexPool::get().run(n, threads < 1 ? 1 : threads > 64 ? 64 : threads, fn);
+}
+
 // Host threads this process may actually run at once: the CPUs of its affinity mask, further limited by a cgroup
 // CPU quota when there is one (a container given 16 CPUs of a 256-thread host reports 256 hardware threads).
 static long long readNumber(const char *path, bool *isMax = nullptr)

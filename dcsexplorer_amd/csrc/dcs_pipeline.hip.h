@@ -22,7 +22,13 @@
 //     decode kernel and the copy down behind the indexers' round and sleeps until the PCM is there.  Lists the arithmetic
 //     plan cannot serve are decoded by the host-planned path (DcsPipelineResult.path).
 // The context keeps a pipeline of its own for dcs_decode_streams on a large list (dcsDecodeStreamsInParts below).
+//
+// Output, chosen at creation too: PCM (default), or FLAC (DCS_PIPE_FLAC, with DCS_PIPE_FLAC_MD5 the samples' MD5 in it).  Stage B of
+// a FLAC pipeline ends, on each of its exits, in pipelineFlacDown instead of the batch's download: the writer (dcs_flac_held.h)
+// is queued behind the batch's launch on the worker's stream, the FLAC bytes, their table and the error words come down into
+// pinned memory the list keeps until it is collected, and the worker waits once.  The PCM never leaves the device.
 #pragma once
+#include "dcs_flac_held.h"
 #include <condition_variable>
 #include <deque>
 #include <memory>
@@ -68,6 +74,9 @@ struct DcsPipeline
         // records -- which stay resident for the device packer --, their digests, the stream summaries
         CacheBuf dRec, dDigest, dInfo;
         const DcsFrameIndex *dRecords = nullptr;    // = dRec once the round has run
+        // ---- FLAC out: the writer's buffers and the error words' pinned copy, the list's until it is collected
+        FlacHeld flac;
+        CacheBuf hErrFlac;
         // planner on the device: the list's stream locations and result addresses as the index kernel takes them
     };
     typedef std::shared_ptr<Job> JobPtr;
@@ -127,6 +136,8 @@ static void pipelineRelease(DcsPipeline *p, DcsPipeline::JobPtr &job)
             job->batch = nullptr;
         }
         pipelineFreeIndexBuffers(job.get());
+        job->flac.release();
+        job->hErrFlac.release();
     }
     job.reset();
 }
@@ -354,6 +365,45 @@ static void pipelineDownPolicy(const DcsPipeline *p, DcsBatch *b)
     b->downBlocks = latency ? 1024u : static_cast<unsigned>(std::max(1, downBlocksEnv));
 }
 
+// The FLAC ending of stage B (DCS_PIPE_FLAC), in place of dcs_batch_download_view: the writer queued behind the batch's launch,
+// the error words' copy behind it, ONE wait.  job->firstJob has the streams' first frames whatever planned the list.  The batch
+// (its dPcm) outlives the wait; after a failure the caller waits for the stream and lets the list's buffers go.
+static DcsStatus pipelineFlacDown(DcsPipeline *p, DcsPipeline::Job *job)
+{
+    DcsCtx *ctx = p->ctx;
+    DcsBatch *b = job->batch;
+    const uint32_t n = job->nStreams;
+    if (job->firstJob.size() != static_cast<size_t>(n) + 1)
+        return DCS_ERR_INVALID_ARG;
+    thread_local std::vector<uint64_t> sampleOffsets;
+    sampleOffsets.resize(static_cast<size_t>(n) + 1);
+    for (uint32_t k = 0 ; k <= n ; ++k)
+        sampleOffsets[k] = static_cast<uint64_t>(job->firstJob[k]) * DCS_FRAME_SAMPLES;
+    pipelineDownPolicy(p, b);
+    const unsigned blocks = b->downByKernel ? b->downBlocks : 1024u;
+    const size_t errBytes = sizeof(uint32_t) * b->nJobs;
+    if (b->launched)
+        HIPCHK(ctx, hipStreamWaitEvent(b->stream, b->evDone, 0));
+    const DcsStatus st = dcsFlacWriteQueue(ctx, b->stream, b->dPcm.as<const int16_t>(), sampleOffsets.data(), n, 31250,
+                                           (p->flags & DCS_PIPE_FLAC_MD5) ? DCS_FLAC_MD5 : 0u, job->flac, blocks);
+    if (st != DCS_OK)
+        return st;
+    HIPCHK(ctx, job->hErrFlac.alloc(ctx, true, errBytes));
+    HIPCHK(ctx, copyByKernel(b->stream, job->hErrFlac.as(), b->dErr, errBytes, 64u));
+    HIPCHK(ctx, streamWait(ctx, b->stream));
+    b->settled = true;
+    job->pcm = nullptr;
+    job->err = job->hErrFlac.as<const uint32_t>();
+    return DCS_OK;
+}
+
+// what a list that failed or was not served leaves behind, once its stream has been waited for
+static void pipelineDropFlac(DcsPipeline::Job *job)
+{
+    job->flac.release();
+    job->hErrFlac.release();
+}
+
 // stage B: from index records (device path) or from scratch (host pool) to PCM in pinned memory
 static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream_t stream)
 {
@@ -424,8 +474,10 @@ static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream
         static const bool splitWait = getenv("DCS_PIPE_TRACE") != nullptr && atoi(getenv("DCS_PIPE_TRACE")) >= 3;
         if (st == DCS_OK && splitWait) st = dcs_batch_sync(job->batch);
         const double tk1 = nowMs();
-        if (st == DCS_OK) pipelineDownPolicy(p, job->batch);
-        if (st == DCS_OK) st = dcs_batch_download_view(job->batch, &job->pcm, &job->err);
+        const bool flac = (p->flags & DCS_PIPE_FLAC) != 0;
+        if (st == DCS_OK && flac) st = pipelineFlacDown(p, job);
+        if (st == DCS_OK && !flac) pipelineDownPolicy(p, job->batch);
+        if (st == DCS_OK && !flac) st = dcs_batch_download_view(job->batch, &job->pcm, &job->err);
         pipeLog("worker", 0, "kernels", tk0, tk1);
         pipeLog("worker", 0, "download", tk1, nowMs());
     }
@@ -436,9 +488,10 @@ static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream
     {
         if (job->batch != nullptr) { dcs_batch_destroy(job->batch); job->batch = nullptr; }
         (void)streamWait(p->ctx, stream);
+        pipelineDropFlac(job);
     }
     pipelineFreeIndexBuffers(job);        // (the packages are on the device: the streams are no longer needed)
-    if (st == DCS_OK && job->pcmDst != nullptr)
+    if (st == DCS_OK && job->pcmDst != nullptr && job->pcm != nullptr)
     {
         memcpy(job->pcmDst, job->pcm, sizeof(int16_t) * DCS_FRAME_SAMPLES * nJobsBuilt);
         if (job->errDst != nullptr)
@@ -488,8 +541,11 @@ static DcsStatus pipelineDecodePlanned(DcsPipeline *p, DcsPipeline::Job *job, hi
         if (st == DCS_OK) st = dcs_batch_run(job->batch, nullptr);
         t2 = nowMs();
         pipeLog("worker", 0, "run-queue", t1, t2);
-        if (st == DCS_OK) pipelineDownPolicy(p, job->batch);
-        if (st == DCS_OK) st = dcs_batch_download_view(job->batch, &job->pcm, &job->err);
+        const bool flac = (p->flags & DCS_PIPE_FLAC) != 0;
+        if (flac) pipelineDropFlac(job);        // (an attempt before this one was waited for: what it queued is through)
+        if (st == DCS_OK && flac) st = pipelineFlacDown(p, job);
+        if (st == DCS_OK && !flac) pipelineDownPolicy(p, job->batch);
+        if (st == DCS_OK && !flac) st = dcs_batch_download_view(job->batch, &job->pcm, &job->err);
         pipeLog("worker", 0, "download", t2, nowMs());
         flag = 0;
         if (st == DCS_OK)
@@ -505,13 +561,14 @@ static DcsStatus pipelineDecodePlanned(DcsPipeline *p, DcsPipeline::Job *job, hi
         // not served (or failed): nothing of this attempt stays
         if (job->batch != nullptr) { dcs_batch_destroy(job->batch); job->batch = nullptr; }
         (void)streamWait(ctx, stream);
+        pipelineDropFlac(job);
         pipelineFreeIndexBuffers(job);
         return st;
     }
     job->onDevice = true;
     job->path = DCS_PIPE_INDEX_ON_DEVICE | DCS_PIPE_PACK_ON_DEVICE | DCS_PIPE_PLAN_ON_DEVICE;
     pipelineFreeIndexBuffers(job);
-    if (job->pcmDst != nullptr)
+    if (job->pcmDst != nullptr && job->pcm != nullptr)
     {
         memcpy(job->pcmDst, job->pcm, sizeof(int16_t) * DCS_FRAME_SAMPLES * nJobs);
         if (job->errDst != nullptr)
@@ -629,7 +686,9 @@ static DcsStatus pipelineCreate(DcsCtx *ctx, int depth, uint32_t flags, DcsPipel
 
 extern "C" DcsStatus dcs_pipeline_create(DcsCtx *ctx, int depth, uint32_t flags, DcsPipeline **out)
 {
-    if ((flags & ~(DCS_PIPE_INDEX_ON_DEVICE | DCS_PIPE_PACK_ON_DEVICE | DCS_PIPE_PLAN_ON_DEVICE)) != 0)
+    if ((flags & ~(DCS_PIPE_INDEX_ON_DEVICE | DCS_PIPE_PACK_ON_DEVICE | DCS_PIPE_PLAN_ON_DEVICE | DCS_PIPE_FLAC | DCS_PIPE_FLAC_MD5)) != 0)
+        return DCS_ERR_INVALID_ARG;
+    if ((flags & DCS_PIPE_FLAC_MD5) != 0 && (flags & DCS_PIPE_FLAC) == 0)
         return DCS_ERR_INVALID_ARG;
     return pipelineCreate(ctx, depth, flags, out);
 }
@@ -671,6 +730,11 @@ static DcsStatus pipelineCreate(DcsCtx *ctx, int depth, uint32_t flags, DcsPipel
     int nWorkers = (flags & DCS_PIPE_PLAN_ON_DEVICE)  ? std::min(depth, (flags & kPipeLatency) ? 8 : 2)
                  : (flags & DCS_PIPE_PACK_ON_DEVICE)  ? std::min(depth, std::max(4, dcs_host_threads() / 3))
                  : (flags & DCS_PIPE_INDEX_ON_DEVICE) ? std::min(depth, dcs_host_threads() + 4) : depth;
+    // FLAC out, planner on the device: stage B holds a worker longer (the writer's kernels and, with the MD5, W4's serial walk run
+    // behind the decode before anything comes down), so four of them: realistic_65536 at depth 32, two / three / four workers 0.81 /
+    // 0.76 / 0.75 ms per list, with the MD5 1.66 / 1.32 / 1.16 (tools/flac_write_bench.py --pipeline).
+    if ((flags & DCS_PIPE_FLAC) != 0 && (flags & DCS_PIPE_PLAN_ON_DEVICE) != 0 && (flags & kPipeLatency) == 0)
+        nWorkers = std::min(depth, 4);
     if (const char *w = getenv("DCS_PIPE_WORKERS"))
         nWorkers = std::max(1, std::min(64, atoi(w)));
     int nUploaders = 0;
@@ -774,17 +838,15 @@ extern "C" DcsStatus dcs_pipeline_submit(DcsPipeline *p, const DcsStreamRef *str
     return pipelineSubmit(p, streams, nStreams, extraFrames, nullptr, nullptr);
 }
 
-extern "C" DcsStatus dcs_pipeline_collect(DcsPipeline *p, DcsPipelineResult *out)
+// the oldest list, once it is finished, becomes the one the caller reads (the previous one's buffers go back to the context's cache)
+static DcsStatus pipelineTakeOldest(DcsPipeline *p, DcsPipeline::JobPtr &job)
 {
-    if (p == nullptr || out == nullptr)
-        return DCS_ERR_INVALID_ARG;
     const double tc0 = nowMs();
     (void)hipSetDevice(p->ctx->device);
     const double tc1 = nowMs();
-    pipelineRelease(p, p->held);                    // the previous result's buffers go back to the context's cache
+    pipelineRelease(p, p->held);
     pipeLog("caller", 0, "set-device", tc0, tc1);
     pipeLog("caller", 0, "release", tc1, nowMs());
-    DcsPipeline::JobPtr job;
     {
         std::unique_lock<std::mutex> lk(p->m);
         if (p->order.empty())
@@ -795,6 +857,17 @@ extern "C" DcsStatus dcs_pipeline_collect(DcsPipeline *p, DcsPipelineResult *out
     }
     p->room.notify_one();
     p->held = job;
+    return DCS_OK;
+}
+
+extern "C" DcsStatus dcs_pipeline_collect(DcsPipeline *p, DcsPipelineResult *out)
+{
+    if (p == nullptr || out == nullptr || (p->flags & DCS_PIPE_FLAC) != 0)     // (a FLAC pipeline's lists are dcs_pipeline_collect_flac's)
+        return DCS_ERR_INVALID_ARG;
+    DcsPipeline::JobPtr job;
+    const DcsStatus taken = pipelineTakeOldest(p, job);
+    if (taken != DCS_OK)
+        return taken;
     memset(out, 0, sizeof(*out));
     out->status = job->status;
     out->nStreams = job->nStreams;
@@ -804,6 +877,32 @@ extern "C" DcsStatus dcs_pipeline_collect(DcsPipeline *p, DcsPipelineResult *out
     if (job->status == DCS_OK)
     {
         out->pcm = job->pcm;
+        out->err = job->err;
+        out->frameOffsets = job->firstJob.data();
+        out->nFrames = job->firstJob.empty() ? 0u : job->firstJob.back();
+    }
+    return job->status;
+}
+
+extern "C" DcsStatus dcs_pipeline_collect_flac(DcsPipeline *p, DcsPipelineFlacResult *out)
+{
+    if (p == nullptr || out == nullptr || (p->flags & DCS_PIPE_FLAC) == 0)
+        return DCS_ERR_INVALID_ARG;
+    DcsPipeline::JobPtr job;
+    const DcsStatus taken = pipelineTakeOldest(p, job);
+    if (taken != DCS_OK)
+        return taken;
+    memset(out, 0, sizeof(*out));
+    out->status = job->status;
+    out->nStreams = job->nStreams;
+    out->hostMs = static_cast<float>(job->hostMs);
+    out->path = job->path;
+    out->deviceMs = static_cast<float>(job->deviceMs);
+    if (job->status == DCS_OK)
+    {
+        out->flac = job->flac.bytes();
+        out->flacOffsets = job->flac.offsets();
+        out->info = job->flac.info();
         out->err = job->err;
         out->frameOffsets = job->firstJob.data();
         out->nFrames = job->firstJob.empty() ? 0u : job->firstJob.back();

@@ -48,7 +48,9 @@ extern "C" {
                                           control (DcsLevel, DcsLevelInfo, DCS_LEVEL_*, dcs_level_gain, dcs_level_streams,
                                           dcs_resample_streams_level, dcs_encode_streams_at_level, dcs_encode_files_level);
                                           writing FLAC (DcsFlacWriteInfo, DCS_FLAC_MD5, DCS_FLAC_SEQUENCE, dcs_flac_write_bound,
-                                          dcs_flac_write_check, dcs_flac_write_streams, dcs_decode_streams_flac) */
+                                          dcs_flac_write_check, dcs_flac_write_streams, dcs_decode_streams_flac); FLAC out of the
+                                          pipeline (DCS_PIPE_FLAC, DCS_PIPE_FLAC_MD5, DcsPipelineFlacResult,
+                                          dcs_pipeline_collect_flac) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -482,6 +484,12 @@ typedef struct DcsPipelineResult
  * the frames per chunk) is decoded by the host-planned path instead, same PCM (DcsPipelineResult.path tells). */
 #define DCS_PIPE_PLAN_ON_DEVICE  4u
 #define DCS_PIPE_ALL_ON_DEVICE   7u      /* the three together: what a caller with many lists in flight wants */
+/* DCS_PIPE_FLAC -- the lists leave the device as FLAC, not as PCM: see dcs_pipeline_collect_flac under "Writing FLAC" below.
+ * DCS_PIPE_FLAC_MD5 (only together with the former) -- with the samples' MD5 in STREAMINFO.  Both combine with every shape
+ * above; any other bit, and DCS_PIPE_FLAC_MD5 alone, is DCS_ERR_INVALID_ARG.  dcs_node_create accepts the three shape flags
+ * alone: FLAC through dcs_node is not offered. */
+#define DCS_PIPE_FLAC            8u
+#define DCS_PIPE_FLAC_MD5        16u
 DcsStatus dcs_pipeline_create(DcsCtx *ctx, int depth /* 1..64 lists in flight */, uint32_t flags, DcsPipeline **out);
 void      dcs_pipeline_destroy(DcsPipeline *p);
 DcsStatus dcs_pipeline_submit(DcsPipeline *p, const DcsStreamRef *streams, uint32_t nStreams, uint32_t extraFrames);
@@ -1071,6 +1079,29 @@ DcsStatus dcs_flac_write_streams(DcsCtx *ctx, const int16_t *pcm, const uint64_t
  * decoder produced.  Capacity protocol and info as dcs_flac_write_streams. */
 DcsStatus dcs_decode_streams_flac(DcsCtx *ctx, const DcsStreamRef *streams, uint32_t nStreams, uint32_t extraFrames, uint32_t flags,
                                   uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsFlacWriteInfo *info, uint32_t *errOut);
+/* FLAC as a pipeline's output (dcs_pipeline_create with DCS_PIPE_FLAC, and DCS_PIPE_FLAC_MD5 for the MD5): every submitted list
+ * is decoded as dcs_decode_streams decodes it and written at 31 250 Hz by the writer's kernels, queued behind the list's decode
+ * on its worker's HIP stream; the FLAC bytes, this table and the error words are all that crosses the link, and the worker
+ * waits once.  The bytes are dcs_decode_streams_flac's of the same list (there is no counterpart of DCS_FLAC_SEQUENCE).
+ * dcs_pipeline_collect_flac is such a pipeline's collect call, with dcs_pipeline_collect's rules: submission order, pointers
+ * into pinned memory of the pipeline that stay valid until the next collect or destroy, a failed list reported through
+ * status (the pointers are then null) without harm to the next.  The wrong collect call for the kind of pipeline --
+ * dcs_pipeline_collect on a FLAC pipeline, this one on a PCM pipeline -- is DCS_ERR_INVALID_ARG and leaves the oldest list where
+ * it is, for the right call to collect.  Pinned staging is sized by what the list's streams can come to at most (every block
+ * VERBATIM), slightly more than its PCM. */
+typedef struct DcsPipelineFlacResult            /* 64 bytes */
+{
+    const uint8_t          *flac;               /* stream k: flac + flacOffsets[k] .. flacOffsets[k + 1]        */
+    const uint64_t         *flacOffsets;        /* nStreams + 1                                                 */
+    const DcsFlacWriteInfo *info;               /* nStreams                                                     */
+    const uint32_t         *err;                /* nFrames x DCS_FRAME_*                                        */
+    const uint32_t         *frameOffsets;       /* nStreams + 1                                                 */
+    uint32_t                nFrames, nStreams;
+    DcsStatus               status;
+    float                   hostMs, deviceMs;
+    uint32_t                path;
+} DcsPipelineFlacResult;
+DcsStatus dcs_pipeline_collect_flac(DcsPipeline *p, DcsPipelineFlacResult *out);
 
 /* ------------------------------------------------------------------------------------------------
  * Level: what happens to a signal's level between the converter and the encoder ("Level", rules 26-33).
