@@ -195,7 +195,7 @@ void dcsHostPoolRun(uint32_t n, int threads, const std::function<void(uint32_t)>
 DcsStatus dcsIndexStreamProgressive(DcsOsVersion os, const uint8_t *stream, size_t len, DcsStreamInfo *info,
                                     const std::function<void(uint32_t, const DcsFrameIndex &)> &onFrame);
 DcsStatus dcsStreamContainer(DcsOsVersion os, const uint8_t *stream, size_t len, DcsStreamInfo *info);
-// large lists through the context's own pipeline, in parts (dcs_pipeline.hip.h); *handled = false: take the direct path
+// large lists through the context's own pipeline, in parts (dcs_large_list.hip.h); *handled = false: take the direct path
 DcsStatus dcsDecodeStreamsInParts(DcsCtx *ctx, const DcsStreamRef *streams, uint32_t nStreams, uint32_t extraFrames,
                                   int16_t *pcmOut, size_t pcmCapFrames, uint32_t *frameOffsets, uint32_t *errOut, bool *handled);
 struct DcsBuiltPlan

@@ -38,9 +38,8 @@ extern "C" DcsStatus dcs_decode_streams_flac(DcsCtx *ctx, const DcsStreamRef *st
         st = dcs_batch_run(d.batch, nullptr);
     if (st == DCS_OK)
     {
-        std::vector<uint64_t> sampleOffsets(static_cast<size_t>(nStreams) + 1);
-        for (uint32_t k = 0 ; k <= nStreams ; ++k)
-            sampleOffsets[k] = static_cast<uint64_t>(d.built.firstJob[k]) * DCS_FRAME_SAMPLES;
+        std::vector<uint64_t> sampleOffsets;
+        dcsFlacSampleOffsets(d.built.firstJob.data(), nStreams, sampleOffsets);
         st = dcsFlacWriteFromDevice(ctx, d.batch->dPcm.as<const int16_t>(), sampleOffsets.data(), nStreams, 31250, flags & DCS_FLAC_MD5,
                                     out, outCap, outOffsets, info);
         // (the writer has waited for the stream: the error words are final)

@@ -39,3 +39,11 @@ struct FlacHeld
 // may have been queued all the same: wait for the stream before `held` goes.
 DcsStatus dcsFlacWriteQueue(DcsCtx *ctx, hipStream_t stream, const int16_t *dPcm, const uint64_t *sampleOffsets, uint32_t nStreams,
                             uint32_t rate, uint32_t flags, FlacHeld &held, unsigned downBlocks);
+
+// ... and its sampleOffsets for decoded streams: from the first output frame of every stream and their total (nStreams + 1 entries)
+inline void dcsFlacSampleOffsets(const uint32_t *firstJob, uint32_t nStreams, std::vector<uint64_t> &sampleOffsets)
+{
+    sampleOffsets.resize(static_cast<size_t>(nStreams) + 1);
+    for (uint32_t k = 0 ; k <= nStreams ; ++k)
+        sampleOffsets[k] = static_cast<uint64_t>(firstJob[k]) * DCS_FRAME_SAMPLES;
+}

@@ -21,12 +21,17 @@
 //     regular job list, so one thread per chunk works the chunk plan out (dcsPlanKernel); a worker queues planner, packer,
 //     decode kernel and the copy down behind the indexers' round and sleeps until the PCM is there.  Lists the arithmetic
 //     plan cannot serve are decoded by the host-planned path (DcsPipelineResult.path).
-// The context keeps a pipeline of its own for dcs_decode_streams on a large list (dcsDecodeStreamsInParts below).
+// The context keeps a pipeline of its own for dcs_decode_streams on a large list (dcsDecodeStreamsInParts, dcs_large_list.hip.h).
 //
-// Output, chosen at creation too: PCM (default), or FLAC (DCS_PIPE_FLAC, with DCS_PIPE_FLAC_MD5 the samples' MD5 in it).  Stage B of
-// a FLAC pipeline ends, on each of its exits, in pipelineFlacDown instead of the batch's download: the writer (dcs_flac_held.h)
-// is queued behind the batch's launch on the worker's stream, the FLAC bytes, their table and the error words come down into
-// pinned memory the list keeps until it is collected, and the worker waits once.  The PCM never leaves the device.
+// Output, chosen at creation too: PCM (default), or FLAC (DCS_PIPE_FLAC, with DCS_PIPE_FLAC_MD5 the samples' MD5 in it): the writer
+// (dcs_flac_held.h) is queued behind the batch's launch on the worker's stream, the FLAC bytes, their table and the error words come
+// down into pinned memory the list keeps until it is collected, and the worker waits once.  The PCM never leaves the device.
+//
+// Stage B is made of steps that the host-planned path (pipelineDecode) and the device-planned one (pipelineDecodePlanned, up to
+// three attempts) share: pipelinePrepare (host-planned only: where the records come from), pipelineLaunch (options, the batch, its
+// run), pipelineBringDown (the ending, PCM or FLAC: the one place that knows there are two), and then either pipelineDeliver
+// (into a caller's memory) or pipelineAbandon.  What a list holds is the Job's: Job::releaseInputs() gives back what the index
+// pass and the packer read, Job::releaseResults() the batch and the FLAC buffers; the environment's switches are PipeSwitches.
 #pragma once
 #include "dcs_flac_held.h"
 #include <condition_variable>
@@ -34,16 +39,24 @@
 #include <memory>
 #include <thread>
 #include <atomic>
+#include <climits>
 #include <pthread.h>
 
 struct DcsPipeline
 {
+    struct BatchDeleter { void operator()(DcsBatch *b) const { dcs_batch_destroy(b); } };
+    struct EventDeleter { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+
+    // A list and everything it holds.  Nothing here waits, and the cache (which knows nothing of streams) hands a buffer that came
+    // back to the next who asks: whoever lets go of something that work queued on a stream may still use waits for that stream first
+    // (dcs_cache.h, dcs_flac_held.h), and the list's device is the current one.  A list that succeeded has waited for its PCM or FLAC,
+    // which its stream delivers after everything else.
     struct Job
     {
         const DcsStreamRef *streams = nullptr;
         uint32_t nStreams = 0, extraFrames = 0;
         std::vector<uint32_t> firstJob;         // first output frame of each stream, and the total
-        DcsBatch *batch = nullptr;
+        std::unique_ptr<DcsBatch, BatchDeleter> batch;
         const int16_t *pcm = nullptr;
         const uint32_t *err = nullptr;
         DcsStatus status = DCS_OK;
@@ -61,7 +74,7 @@ struct DcsPipeline
         uint64_t totalRec = 0;
         CacheBuf hRec, hInfo;                   // records (or, packing on the device, their digests) and stream summaries
                                                 //   as they come back (pinned)
-        hipEvent_t uploaded = nullptr;
+        std::unique_ptr<std::remove_pointer<hipEvent_t>::type, EventDeleter> uploaded;
         // results copied into caller memory by the worker (dcs_decode_streams in parts): optional
         int16_t *pcmDst = nullptr;
         uint32_t *errDst = nullptr;
@@ -77,7 +90,26 @@ struct DcsPipeline
         // ---- FLAC out: the writer's buffers and the error words' pinned copy, the list's until it is collected
         FlacHeld flac;
         CacheBuf hErrFlac;
-        // planner on the device: the list's stream locations and result addresses as the index kernel takes them
+
+        // The two releases, each in the order in which its buffers go back (not the members': the cache evicts what came back first).
+        // What the index pass and the packer read: given back once the packages are on the device, or once the list is given up.
+        void releaseInputs()
+        {
+            dRecords = nullptr;
+            for (CacheBuf *c : { &dRec, &dDigest, &dInfo, &dBlob, &hRec, &hInfo, &hBlob })
+                c->release();
+            uploaded.reset();
+        }
+        // What the caller reads: given back when the next list is collected, or between the attempts of a list planned again.
+        void releaseResults()
+        {
+            batch.reset();
+            flac.release();
+            hErrFlac.release();
+            pcm = nullptr;
+            err = nullptr;
+        }
+        ~Job() { releaseInputs(); releaseResults(); }      // (a backstop: every path through the pipeline has called both by now)
     };
     typedef std::shared_ptr<Job> JobPtr;
 
@@ -106,38 +138,62 @@ static double nowMs()
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// DCS_PIPE_TRACE=2: what every pipeline thread did and when (tools/pipe_threads.py reads it from stderr)
 // internal flag: the pipeline's threads wait by polling inside the runtime (shortest latency) instead of napping
 static constexpr uint32_t kPipeLatency = 0x100u;
 
+// The environment's switches, read ONCE, with the first pipeline of the process (or the first batch made as a pipeline makes them).
+// Experiment switches all: 0 or null means "not set", and the rule next to the use holds.
+struct PipeSwitches
+{
+    int trace = 0;                  // DCS_PIPE_TRACE: set at all, a line or two per list; 2, what every thread did and when; 3, stage B waits
+                                    //   for its kernels before the copies
+    unsigned upBlocks = 0;          // DCS_PIPE_UP_BLOCKS: workgroups of a list's upload
+    int downBlocks = 0;             // DCS_PIPE_DOWN_BLOCKS: the PCM comes down by copy kernel, with at most so many workgroups
+    size_t roundStreams = 0;        // DCS_PIPE_ROUND_STREAMS: the most streams an index round takes
+    int workers = 0, uploaders = 0; // DCS_PIPE_WORKERS (1 to 64; stage-B workers where there are uploaders), DCS_PIPE_UPLOADERS (1 to 8)
+    char indexerPrio[2] = { 0, 0 }; // DCS_PIPE_INDEXER_PRIO=ab, a / b one of l(east) g(reatest) n(ormal): the two indexers' stream priorities
+    bool xcdRanges = true;          // DCS_PIPE_XCD_RANGES=0: the pipelines' batches are made without XCD ranges
+};
+
+static const PipeSwitches &pipeSwitches()
+{
+    static const PipeSwitches switches = [] {
+        PipeSwitches s;
+        const auto number = [](const char *name, int lo, int hi, int unset) {
+            const char *e = getenv(name);
+            return e == nullptr ? unset : std::max(lo, std::min(hi, atoi(e)));
+        };
+        s.trace = number("DCS_PIPE_TRACE", 1, INT_MAX, 0);
+        s.upBlocks = static_cast<unsigned>(number("DCS_PIPE_UP_BLOCKS", 1, INT_MAX, 0));
+        s.downBlocks = number("DCS_PIPE_DOWN_BLOCKS", INT_MIN, INT_MAX, 0);
+        s.roundStreams = static_cast<size_t>(number("DCS_PIPE_ROUND_STREAMS", 1, INT_MAX, 0));
+        s.workers = number("DCS_PIPE_WORKERS", 1, 64, 0);
+        s.uploaders = number("DCS_PIPE_UPLOADERS", 1, 8, 0);
+        if (const char *e = getenv("DCS_PIPE_INDEXER_PRIO"))
+        {
+            s.indexerPrio[0] = e[0];
+            s.indexerPrio[1] = e[0] ? e[1] : 0;
+        }
+        s.xcdRanges = number("DCS_PIPE_XCD_RANGES", INT_MIN, INT_MAX, 1) != 0;
+        return s;
+    }();
+    return switches;
+}
+
+// DCS_PIPE_TRACE=2: what every pipeline thread did and when (tools/pipe_threads.py reads it from stderr)
 static void pipeLog(const char *who, int id, const char *what, double t0, double t1, size_t q1 = 0, size_t q2 = 0)
 {
-    static const bool on = getenv("DCS_PIPE_TRACE") != nullptr && atoi(getenv("DCS_PIPE_TRACE")) >= 2;
-    if (on)
+    if (pipeSwitches().trace >= 2)
         fprintf(stderr, "pipe thread: %s %d %s %.3f %.3f %zu %zu\n", who, id, what, t0, t1, q1, q2);
 }
 
-static void pipelineFreeIndexBuffers(DcsPipeline::Job *job)
-{
-    job->dRecords = nullptr;
-    // (in this order, not the members': the cache evicts what came back first)
-    for (CacheBuf *c : { &job->dRec, &job->dDigest, &job->dInfo, &job->dBlob, &job->hRec, &job->hInfo, &job->hBlob })
-        c->release();
-    if (job->uploaded) { (void)hipEventDestroy(job->uploaded); job->uploaded = nullptr; }
-}
-
-static void pipelineRelease(DcsPipeline *p, DcsPipeline::JobPtr &job)
+// the list a caller has read, or one that was never collected, goes (the caller has set the device)
+static void pipelineRelease(DcsPipeline::JobPtr &job)
 {
     if (job)
     {
-        if (job->batch)
-        {
-            dcs_batch_destroy(job->batch);
-            job->batch = nullptr;
-        }
-        pipelineFreeIndexBuffers(job.get());
-        job->flac.release();
-        job->hErrFlac.release();
+        job->releaseInputs();
+        job->releaseResults();
     }
     job.reset();
 }
@@ -221,17 +277,19 @@ static DcsStatus pipelineUpload(DcsPipeline *p, DcsPipeline::Job *job, hipStream
         memcpy(hBlob + l.off, job->streams[k].data, l.len);
     }
     const double tu2 = nowMs();
-    HIPCHK(ctx, hipEventCreateWithFlags(&job->uploaded, hipEventDisableTiming));
+    hipEvent_t uploaded = nullptr;
+    HIPCHK(ctx, hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+    job->uploaded.reset(uploaded);
     // The streams go up through EIGHT workgroups (DCS_PIPE_UP_BLOCKS overrides).  A copy kernel that reads pinned host memory with hundreds of
     // workgroups -- 2.4 MB a list: 586 of them -- keeps that many wavefronts stalled on PCIe reads whose completions travel the
     // direction the PCM's writes need: the PCM of the lists further along came down at 70-75 % of the link's rate.  With 4 to 20
     // workgroups (an upload then takes 0.15 ms instead of 0.05) the link runs at 93-97 %: 0.74 -> 0.58 ms per list sustained (round 4).
     // (a list far larger than those measured gets more of them, one per 300 KB up to 32, so that its upload stays shorter than its PCM's way down)
-    static const unsigned upBlocksEnv = getenv("DCS_PIPE_UP_BLOCKS") != nullptr ? static_cast<unsigned>(std::max(1, atoi(getenv("DCS_PIPE_UP_BLOCKS")))) : 0u;
+    const unsigned upBlocksEnv = pipeSwitches().upBlocks;
     const unsigned upBlocks = upBlocksEnv != 0 ? upBlocksEnv : static_cast<unsigned>(std::min<size_t>(32, std::max<size_t>(8, blobBytes / (300u << 10))));
     HIPCHK(ctx, copyByKernel(stream, job->dBlob.as(), hBlob, blobBytes, (p->flags & kPipeLatency) ? 1024u : upBlocks));
-    HIPCHK(ctx, hipEventRecord(job->uploaded, stream));
-    if (getenv("DCS_PIPE_TRACE"))
+    HIPCHK(ctx, hipEventRecord(uploaded, stream));
+    if (pipeSwitches().trace)
         fprintf(stderr, "pipe upload: allocs %.2f, memcpy %.2f, hip calls %.2f\n", tu1 - tu0, tu2 - tu1, nowMs() - tu2);
     return DCS_OK;
 }
@@ -247,9 +305,7 @@ static void pipelineIndexer(DcsPipeline *p, int which)
     // A round takes the lists that are waiting, up to about an eighth of the chip's wavefront slots (one wavefront walks one
     // stream, for milliseconds): the decode kernels of the lists further along must find room next to it, and beyond that
     // size a round's time grows with its streams anyway (2 048 streams x 256 frames 2.7 ms, 8 192 6.0 ms).
-    size_t maxRoundStreams = static_cast<size_t>(ctx->numCUs) * 8;
-    if (const char *e = getenv("DCS_PIPE_ROUND_STREAMS"))
-        maxRoundStreams = static_cast<size_t>(std::max(1, atoi(e)));
+    const size_t maxRoundStreams = pipeSwitches().roundStreams != 0 ? pipeSwitches().roundStreams : static_cast<size_t>(ctx->numCUs) * 8;
     GrowBuf hTable(true), dTable;       // the round's stream locations and result addresses, as uploaded; freed when the thread ends
     for (;;)
     {
@@ -300,7 +356,7 @@ static void pipelineIndexer(DcsPipeline *p, int which)
                     outs[k].info = j->dInfo.as<DcsStreamInfo>() + i;
                 }
             for (const DcsPipeline::JobPtr &j : jobs)
-                HIPCHK(ctx, hipStreamWaitEvent(stream, j->uploaded, 0));
+                HIPCHK(ctx, hipStreamWaitEvent(stream, j->uploaded.get(), 0));
             HIPCHK(ctx, copyByKernel(stream, dTable.as(), hTable.as(), tableBytes));
             HIPCHK(ctx, launchIndexWave(stream, 0, dTable.as<const DcsStreamLoc>(), nStreams, ctx->dTables, nullptr, nullptr, nullptr,
                                         reinterpret_cast<const dcsidx::StreamOut *>(dTable.as<const uint8_t>() + locBytes)));
@@ -347,11 +403,7 @@ static void pipelineIndexer(DcsPipeline *p, int which)
 // which also rules the circle out, was measured first: 0.92 ms per list instead of 0.60 -- lists waiting behind each other's packers.)
 
 // (DCS_PIPE_XCD_RANGES=0, an experiment switch: the pipelines' batches are made without them)
-static bool pipeXcdRanges()
-{
-    static const bool on = getenv("DCS_PIPE_XCD_RANGES") == nullptr || atoi(getenv("DCS_PIPE_XCD_RANGES")) != 0;
-    return on;
-}
+static bool pipeXcdRanges() { return pipeSwitches().xcdRanges; }
 
 // How a list's PCM comes down: by the runtime's copy (hipMemcpyAsync into pinned memory, which this runtime does with a blit
 // kernel of its own), or -- DCS_PIPE_DOWN_BLOCKS=n, and always for a pipeline with ONE waiting caller (the context's own), where
@@ -359,7 +411,7 @@ static bool pipeXcdRanges()
 // Measured in round 4 (NOTES 24): with the uploads throttled (pipelineUpload) both ways down run at 93-97 % of the link.
 static void pipelineDownPolicy(const DcsPipeline *p, DcsBatch *b)
 {
-    static const int downBlocksEnv = getenv("DCS_PIPE_DOWN_BLOCKS") != nullptr ? atoi(getenv("DCS_PIPE_DOWN_BLOCKS")) : 0;
+    const int downBlocksEnv = pipeSwitches().downBlocks;
     const bool latency = (p->flags & kPipeLatency) != 0;
     b->downByKernel = latency || downBlocksEnv > 0;
     b->downBlocks = latency ? 1024u : static_cast<unsigned>(std::max(1, downBlocksEnv));
@@ -367,18 +419,16 @@ static void pipelineDownPolicy(const DcsPipeline *p, DcsBatch *b)
 
 // The FLAC ending of stage B (DCS_PIPE_FLAC), in place of dcs_batch_download_view: the writer queued behind the batch's launch,
 // the error words' copy behind it, ONE wait.  job->firstJob has the streams' first frames whatever planned the list.  The batch
-// (its dPcm) outlives the wait; after a failure the caller waits for the stream and lets the list's buffers go.
+// (its dPcm) outlives the wait.
 static DcsStatus pipelineFlacDown(DcsPipeline *p, DcsPipeline::Job *job)
 {
     DcsCtx *ctx = p->ctx;
-    DcsBatch *b = job->batch;
+    DcsBatch *b = job->batch.get();
     const uint32_t n = job->nStreams;
     if (job->firstJob.size() != static_cast<size_t>(n) + 1)
         return DCS_ERR_INVALID_ARG;
     thread_local std::vector<uint64_t> sampleOffsets;
-    sampleOffsets.resize(static_cast<size_t>(n) + 1);
-    for (uint32_t k = 0 ; k <= n ; ++k)
-        sampleOffsets[k] = static_cast<uint64_t>(job->firstJob[k]) * DCS_FRAME_SAMPLES;
+    dcsFlacSampleOffsets(job->firstJob.data(), n, sampleOffsets);
     pipelineDownPolicy(p, b);
     const unsigned blocks = b->downByKernel ? b->downBlocks : 1024u;
     const size_t errBytes = sizeof(uint32_t) * b->nJobs;
@@ -397,113 +447,143 @@ static DcsStatus pipelineFlacDown(DcsPipeline *p, DcsPipeline::Job *job)
     return DCS_OK;
 }
 
-// what a list that failed or was not served leaves behind, once its stream has been waited for
-static void pipelineDropFlac(DcsPipeline::Job *job)
+// ---- stage B's steps, shared by the host-planned and the device-planned path
+
+// Launch: a batch as the pipelines make them (XCD ranges, see above) from whatever `create` has planned, and its run queued on the
+// worker's stream.  *tCreated: when the batch was there (host work before, device work behind).
+template <class Create>
+static DcsStatus pipelineLaunch(DcsPipeline *p, DcsPipeline::Job *job, hipStream_t stream, double *tCreated, Create &&create)
 {
-    job->flac.release();
-    job->hErrFlac.release();
+    BatchOptions o(p->ctx, stream);
+    o.xcdRanges = pipeXcdRanges();
+    DcsBatch *b = nullptr;
+    DcsStatus st = create(o, &b);
+    job->batch.reset(b);
+    *tCreated = nowMs();
+    if (st == DCS_OK) st = dcs_batch_run(b, nullptr);
+    return st;
 }
 
-// stage B: from index records (device path) or from scratch (host pool) to PCM in pinned memory
-static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream_t stream)
+// Bring down: the ending, with its one wait -- the PCM into the batch's pinned memory, or the FLAC written from it into the list's.
+// The only place that knows there are two kinds of output.
+static DcsStatus pipelineBringDown(DcsPipeline *p, DcsPipeline::Job *job)
 {
-    const double t0 = nowMs();
-    DcsStatus st = DCS_OK;
-    bool fromDevice = false;
-    // the batch description is needed only until the batch exists: one per worker thread, its memory kept from list to
-    // list (fresh multi-megabyte vectors for every list cost more in page faults than everything else the host does)
-    thread_local DcsBuiltStreams scratch;
-    DcsBuiltStreams &built = scratch;
-    const bool packOnDevice = (p->flags & DCS_PIPE_PACK_ON_DEVICE) != 0 && job->dRecords != nullptr;
-    thread_local DcsBuiltPlan planScratch;
+    if ((p->flags & DCS_PIPE_FLAC) != 0)
+        return pipelineFlacDown(p, job);
+    pipelineDownPolicy(p, job->batch.get());
+    return dcs_batch_download_view(job->batch.get(), &job->pcm, &job->err);
+}
+
+// Abandon: a list that failed, or that the device planner could not serve, may have left kernels in flight that read its inputs
+// (the pack kernel reads dBlob and the round's records) and write its results: the batch goes (it waits for what it launched), the
+// worker's stream is waited for, and then nothing of the attempt stays.
+static void pipelineAbandon(DcsPipeline *p, DcsPipeline::Job *job, hipStream_t stream)
+{
+    job->batch.reset();
+    (void)streamWait(p->ctx, stream);
+    job->releaseResults();
+    job->releaseInputs();
+}
+
+// Deliver: the results copied into caller memory by the worker (dcs_decode_streams in parts)
+static void pipelineDeliver(DcsPipeline::Job *job, size_t nFrames)
+{
+    if (job->pcmDst == nullptr || job->pcm == nullptr)
+        return;
+    memcpy(job->pcmDst, job->pcm, sizeof(int16_t) * DCS_FRAME_SAMPLES * nFrames);
+    if (job->errDst != nullptr)
+        memcpy(job->errDst, job->err, sizeof(uint32_t) * nFrames);
+}
+
+// Prepare (host-planned path): where the list's index records come from, in this order of preference, and the plan made from them
+enum PlanSource
+{
+    kPlanFromDigests,       // digests back from the device: the plan is in `planned`, the packer runs on the device
+    kPlanFromRecords,       // records back from the device: `built`, over the streams as uploaded (hBlob)
+    kPlanFromHost           // the submitter's records, or the host index pass: `built`, with a blob of its own
+};
+
+static DcsStatus pipelinePrepare(DcsPipeline *p, DcsPipeline::Job *job, DcsBuiltStreams &built, DcsBuiltPlan &planned, PlanSource *source)
+{
+    *source = kPlanFromHost;
     if (job->hRec)
     {
         // a stream whose frames run past its buffer reads the missing bytes as zero, which streams laid end to end
         // cannot express: such a list (truncated input) takes the host path.  What counts is the bits the frames
         // occupy, not nBytes, which includes the reference reader's look-ahead of up to three bytes (:1509).
         const DcsStreamInfo *infos = job->hInfo.as<const DcsStreamInfo>();
-        fromDevice = true;
+        bool fromDevice = true;
         for (uint32_t k = 0 ; k < job->nStreams && fromDevice ; ++k)
             fromDevice = infos[k].nFrames != 0
                       && 2u + static_cast<size_t>(infos[k].hdrLen) + (static_cast<size_t>(infos[k].payloadBits) + 7) / 8 <= job->locs[k].len;
-        if (fromDevice && packOnDevice)
+        if (fromDevice && (p->flags & DCS_PIPE_PACK_ON_DEVICE) != 0 && job->dRecords != nullptr)
         {
+            *source = kPlanFromDigests;
             const DcsDigested in{ job->hRec.as<const DcsFrameDigest>(), job->firstRecord.data(), infos, job->streamOff.data(), 0 };
-            st = dcsBuildPlanFromDigest(job->streams, job->nStreams, job->extraFrames, in, planScratch);
+            return dcsBuildPlanFromDigest(job->streams, job->nStreams, job->extraFrames, in, planned);
         }
-        else if (fromDevice)
+        if (fromDevice)
         {
+            *source = kPlanFromRecords;
             const DcsPreIndexed pre{ job->hRec.as<const DcsFrameIndex>(), job->firstRecord.data(), infos, job->streamOff.data() };
-            st = dcsBuildStreams(job->streams, job->nStreams, job->extraFrames, built, false, false, &pre);
+            return dcsBuildStreams(job->streams, job->nStreams, job->extraFrames, built, false, false, &pre);
         }
     }
-    if (st == DCS_OK && !fromDevice)
+    if (job->preRecords != nullptr)
     {
-        if (job->preRecords != nullptr)
-        {
-            const DcsPreIndexed pre{ job->preRecords, job->preFirstRecord, job->preInfos, nullptr };
-            st = dcsBuildStreams(job->streams, job->nStreams, job->extraFrames, built, false, false, &pre);
-        }
-        else
-            st = dcsBuildStreams(job->streams, job->nStreams, job->extraFrames, built, false, false);
+        const DcsPreIndexed pre{ job->preRecords, job->preFirstRecord, job->preInfos, nullptr };
+        return dcsBuildStreams(job->streams, job->nStreams, job->extraFrames, built, false, false, &pre);
     }
-    const bool devicePacked = fromDevice && packOnDevice;
+    return dcsBuildStreams(job->streams, job->nStreams, job->extraFrames, built, false, false);
+}
+
+// stage B, planned on the host: from index records (device path) or from scratch (host pool) to PCM or FLAC in pinned memory
+static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream_t stream, int id)
+{
+    const double t0 = nowMs();
+    // the batch description is needed only until the batch exists: one per worker thread, its memory kept from list to
+    // list (fresh multi-megabyte vectors for every list cost more in page faults than everything else the host does)
+    thread_local DcsBuiltStreams built;
+    thread_local DcsBuiltPlan planned;
+    PlanSource source;
+    DcsStatus st = pipelinePrepare(p, job, built, planned, &source);
+    const bool fromDevice = source != kPlanFromHost, devicePacked = source == kPlanFromDigests;
     job->onDevice = fromDevice;
     job->path = fromDevice ? (DCS_PIPE_INDEX_ON_DEVICE | (devicePacked ? DCS_PIPE_PACK_ON_DEVICE : 0u)) : 0u;
-    job->firstJob = devicePacked ? planScratch.firstJob : built.firstJob;
-    const size_t nJobsBuilt = devicePacked ? planScratch.jobs.size() : built.jobs.size();
-    const uint8_t *blob = fromDevice ? job->hBlob.as<const uint8_t>() : built.blob.data();
-    const size_t blobLen = fromDevice ? job->hBlobLen : built.blob.size();
+    job->firstJob = devicePacked ? planned.firstJob : built.firstJob;
+    const size_t nJobs = devicePacked ? planned.jobs.size() : built.jobs.size();
     double t1 = nowMs(), t2 = t1;
     if (st == DCS_OK)
     {
-        BatchOptions o(p->ctx, stream);
-        o.xcdRanges = pipeXcdRanges();
-        const DcsBuiltStreams &B = built;
-        if (devicePacked)
-            st = createBatchOnDevice(p->ctx, o, planScratch.jobs.data(), static_cast<uint32_t>(planScratch.jobs.size()), planScratch.srcs.data(),
-                                     static_cast<uint32_t>(planScratch.srcs.size()), job->dRecords, job->dBlob.as<const uint8_t>(),
-                                     job->hBlobLen, &job->batch);
-        else
-            st = createBatch(p->ctx, o, blob, blobLen, B.srcs.data(), static_cast<uint32_t>(B.srcs.size()),
-                             B.jobs.data(), static_cast<uint32_t>(B.jobs.size()), nullptr, 0, &job->batch);
-        t2 = nowMs();
-        if (st == DCS_OK) st = dcs_batch_run(job->batch, nullptr);
+        st = pipelineLaunch(p, job, stream, &t2, [&](const BatchOptions &o, DcsBatch **out) {
+            if (devicePacked)
+                return createBatchOnDevice(p->ctx, o, planned.jobs.data(), static_cast<uint32_t>(nJobs), planned.srcs.data(),
+                                           static_cast<uint32_t>(planned.srcs.size()), job->dRecords, job->dBlob.as<const uint8_t>(),
+                                           job->hBlobLen, out);
+            return createBatch(p->ctx, o, fromDevice ? job->hBlob.as<const uint8_t>() : built.blob.data(), fromDevice ? job->hBlobLen : built.blob.size(),
+                               built.srcs.data(), static_cast<uint32_t>(built.srcs.size()), built.jobs.data(), static_cast<uint32_t>(nJobs), nullptr, 0, out);
+        });
         // (DCS_PIPE_TRACE=3 waits for the kernels first, so that the thread log tells them from the copies)
         const double tk0 = nowMs();
-        static const bool splitWait = getenv("DCS_PIPE_TRACE") != nullptr && atoi(getenv("DCS_PIPE_TRACE")) >= 3;
-        if (st == DCS_OK && splitWait) st = dcs_batch_sync(job->batch);
+        if (st == DCS_OK && pipeSwitches().trace >= 3) st = dcs_batch_sync(job->batch.get());
         const double tk1 = nowMs();
-        const bool flac = (p->flags & DCS_PIPE_FLAC) != 0;
-        if (st == DCS_OK && flac) st = pipelineFlacDown(p, job);
-        if (st == DCS_OK && !flac) pipelineDownPolicy(p, job->batch);
-        if (st == DCS_OK && !flac) st = dcs_batch_download_view(job->batch, &job->pcm, &job->err);
-        pipeLog("worker", 0, "kernels", tk0, tk1);
-        pipeLog("worker", 0, "download", tk1, nowMs());
+        if (st == DCS_OK) st = pipelineBringDown(p, job);
+        pipeLog("worker", id, "kernels", tk0, tk1);
+        pipeLog("worker", id, "download", tk1, nowMs());
     }
-    // A failed list may have left its pack kernel (which reads dBlob and the round's records) in flight: nothing of it
-    // runs any more when those buffers go back to the cache, which knows nothing of streams.  (A list that succeeded has
-    // waited for its PCM, which the worker's stream delivers after everything else.)
     if (st != DCS_OK)
+        pipelineAbandon(p, job, stream);
+    else
     {
-        if (job->batch != nullptr) { dcs_batch_destroy(job->batch); job->batch = nullptr; }
-        (void)streamWait(p->ctx, stream);
-        pipelineDropFlac(job);
-    }
-    pipelineFreeIndexBuffers(job);        // (the packages are on the device: the streams are no longer needed)
-    if (st == DCS_OK && job->pcmDst != nullptr && job->pcm != nullptr)
-    {
-        memcpy(job->pcmDst, job->pcm, sizeof(int16_t) * DCS_FRAME_SAMPLES * nJobsBuilt);
-        if (job->errDst != nullptr)
-            memcpy(job->errDst, job->err, sizeof(uint32_t) * nJobsBuilt);
+        job->releaseInputs();           // (the packages are on the device: the streams are no longer needed)
+        pipelineDeliver(job, nJobs);
     }
     const double t3 = nowMs();
-    if (getenv("DCS_PIPE_TRACE"))
+    if (pipeSwitches().trace)
         fprintf(stderr, "pipe list: upload %.2f ms, index launch %.2f ms (records from the %s) | build %.2f create %.2f run+download %.2f\n",
                 job->hostMs, job->deviceMs, fromDevice ? "device" : "host pool", t1 - t0, t2 - t1, t3 - t2);
     job->hostMs += t2 - t0;
     job->deviceMs += t3 - t2;
-    (void)t1;
     return st;
 }
 
@@ -511,7 +591,7 @@ static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream
 // put them there); planner, packer and decode kernels and the PCM's way down are queued on the worker's stream, and the one
 // wait is for the PCM.  Returns DCS_OK with *served = false when the arithmetic plan cannot serve the list (DCS_PLAN_*):
 // the caller then takes the host-planned path.
-static DcsStatus pipelineDecodePlanned(DcsPipeline *p, DcsPipeline::Job *job, hipStream_t stream, bool *served)
+static DcsStatus pipelineDecodePlanned(DcsPipeline *p, DcsPipeline::Job *job, hipStream_t stream, int id, bool *served)
 {
     DcsCtx *ctx = p->ctx;
     *served = false;
@@ -521,35 +601,26 @@ static DcsStatus pipelineDecodePlanned(DcsPipeline *p, DcsPipeline::Job *job, hi
     DcsStatus st = planTableFor(job->streams, job->nStreams, job->extraFrames, job->locs.data(), job->firstRecord.data(), job->totalRec, table, job->firstJob);
     if (st != DCS_OK)
         return st;
-    const uint64_t nJobs = table.nJobs;
     // A chunk whose frames' compressed bytes overflow the kernel's bit pool (224 bytes per slot) is what the arithmetic plan cannot
     // close early as the host planner does: the list is planned again with fewer frames per chunk -- three quarters, then half of the
     // slots -- before the host path gets it (one stream of large frames among 600 would otherwise cost the whole list the device).
     double t1 = t0, t2 = t0;
     uint32_t flag = 0;
-    const int fullFpw = chooseFpw(ctx, static_cast<uint32_t>(nJobs), table.all94);
+    const int fullFpw = chooseFpw(ctx, static_cast<uint32_t>(table.nJobs), table.all94);
     const int tries[3] = { 0, fullFpw * 3 / 4, fullFpw / 2 };
-    BatchOptions o(ctx, stream);
-    o.xcdRanges = pipeXcdRanges();
     for (int attempt = 0 ; attempt < 3 ; ++attempt)
     {
-        if (job->batch != nullptr) { dcs_batch_destroy(job->batch); job->batch = nullptr; }
-        st = createBatchPlannedOnDevice(ctx, o, table, job->extraFrames, static_cast<uint32_t>(job->totalRec), job->dRec.as<const DcsFrameIndex>(),
-                                        job->dInfo.as<const DcsStreamInfo>(), job->dBlob.as<const uint8_t>(), job->hBlobLen, &job->batch, tries[attempt]);
-        t1 = nowMs();
-        pipeLog("worker", 0, "plan-queue", t0, t1);
-        if (st == DCS_OK) st = dcs_batch_run(job->batch, nullptr);
+        job->releaseResults();          // (an attempt before this one was waited for: what it queued is through)
+        st = pipelineLaunch(p, job, stream, &t1, [&](const BatchOptions &o, DcsBatch **out) {
+            return createBatchPlannedOnDevice(ctx, o, table, job->extraFrames, static_cast<uint32_t>(job->totalRec), job->dRec.as<const DcsFrameIndex>(),
+                                              job->dInfo.as<const DcsStreamInfo>(), job->dBlob.as<const uint8_t>(), job->hBlobLen, out, tries[attempt]);
+        });
         t2 = nowMs();
-        pipeLog("worker", 0, "run-queue", t1, t2);
-        const bool flac = (p->flags & DCS_PIPE_FLAC) != 0;
-        if (flac) pipelineDropFlac(job);        // (an attempt before this one was waited for: what it queued is through)
-        if (st == DCS_OK && flac) st = pipelineFlacDown(p, job);
-        if (st == DCS_OK && !flac) pipelineDownPolicy(p, job->batch);
-        if (st == DCS_OK && !flac) st = dcs_batch_download_view(job->batch, &job->pcm, &job->err);
-        pipeLog("worker", 0, "download", t2, nowMs());
-        flag = 0;
-        if (st == DCS_OK)
-            flag = batchPlanFlag(job->batch);
+        pipeLog("worker", id, "plan-queue", t0, t1);
+        pipeLog("worker", id, "run-queue", t1, t2);
+        if (st == DCS_OK) st = pipelineBringDown(p, job);
+        pipeLog("worker", id, "download", t2, nowMs());
+        flag = st == DCS_OK ? batchPlanFlag(job->batch.get()) : 0;
         // again with fewer slots only for an overflow, and not when the list is (also) truncated: that one is the host's whatever the plan
         if (st != DCS_OK || (flag & DCS_PLAN_POOL_OVERFLOW) == 0 || (flag & DCS_PLAN_TRUNCATED) != 0)
             break;
@@ -558,22 +629,13 @@ static DcsStatus pipelineDecodePlanned(DcsPipeline *p, DcsPipeline::Job *job, hi
     job->deviceMs += nowMs() - t1;
     if (st != DCS_OK || flag != 0)
     {
-        // not served (or failed): nothing of this attempt stays
-        if (job->batch != nullptr) { dcs_batch_destroy(job->batch); job->batch = nullptr; }
-        (void)streamWait(ctx, stream);
-        pipelineDropFlac(job);
-        pipelineFreeIndexBuffers(job);
+        pipelineAbandon(p, job, stream);        // not served (or failed): nothing of this attempt stays
         return st;
     }
     job->onDevice = true;
     job->path = DCS_PIPE_INDEX_ON_DEVICE | DCS_PIPE_PACK_ON_DEVICE | DCS_PIPE_PLAN_ON_DEVICE;
-    pipelineFreeIndexBuffers(job);
-    if (job->pcmDst != nullptr && job->pcm != nullptr)
-    {
-        memcpy(job->pcmDst, job->pcm, sizeof(int16_t) * DCS_FRAME_SAMPLES * nJobs);
-        if (job->errDst != nullptr)
-            memcpy(job->errDst, job->err, sizeof(uint32_t) * nJobs);
-    }
+    job->releaseInputs();
+    pipelineDeliver(job, table.nJobs);
     *served = true;
     return DCS_OK;
 }
@@ -619,7 +681,7 @@ static void pipelineWorker(DcsPipeline *p, int id)
             pipeLog("worker", id, "upload", t0, nowMs());
             if (st != DCS_OK)
             {
-                pipelineFreeIndexBuffers(job.get());
+                pipelineAbandon(p, job.get(), stream);
                 pipelineFinish(p, job, st);
                 continue;
             }
@@ -636,6 +698,8 @@ static void pipelineWorker(DcsPipeline *p, int id)
                     HIPCHK(ctx, streamWait(ctx, stream));
                     return DCS_OK;
                 }();
+                if (s2 != DCS_OK)
+                    (void)streamWait(p->ctx, stream);
                 const double t1 = nowMs();
                 {
                     std::lock_guard<std::mutex> lk(p->m);
@@ -657,27 +721,32 @@ static void pipelineWorker(DcsPipeline *p, int id)
         }
         DcsStatus st = job->status;             // (the indexer's)
         job->tStageB = nowMs();
-        if (st == DCS_OK && (p->flags & DCS_PIPE_PLAN_ON_DEVICE))
+        if (st != DCS_OK)
+        {
+            // the index round failed (its thread has waited for its own stream; the streams' upload may not have been reached)
+            if (job->uploaded) (void)hipEventSynchronize(job->uploaded.get());
+            pipelineAbandon(p, job.get(), stream);
+        }
+        else
         {
             bool served = false;
-            st = pipelineDecodePlanned(p, job.get(), stream, &served);
-            if (st == DCS_OK && !served)
+            if (p->flags & DCS_PIPE_PLAN_ON_DEVICE)
             {
-                pipeLog("worker", id, "not-served", job->tStageB, nowMs());
-                st = pipelineDecode(p, job.get(), stream);       // (host index pass, host planner: serves every list)
+                st = pipelineDecodePlanned(p, job.get(), stream, id, &served);
+                if (st == DCS_OK && !served)
+                    pipeLog("worker", id, "not-served", job->tStageB, nowMs());
             }
+            if (st == DCS_OK && !served)
+                st = pipelineDecode(p, job.get(), stream, id);      // (host index pass, host planner: serves every list)
         }
-        else if (st == DCS_OK)
-            st = pipelineDecode(p, job.get(), stream);
         pipeLog("worker", id, "stageB", job->tStageB, nowMs());
         job->tDone = nowMs();
-        if (getenv("DCS_PIPE_TRACE") && job->tIndexed != 0)
+        if (pipeSwitches().trace && job->tIndexed != 0)
         {
             fprintf(stderr, "pipe life: submit->taken %.2f, upload %.2f, wait for indexer %.2f, index round %.2f, wait for worker %.2f, stage B %.2f\n",
                     job->tTaken - job->tSubmit, job->tQueuedForIndex - job->tTaken, job->tIndexStart - job->tQueuedForIndex,
                     job->tIndexed - job->tIndexStart, job->tStageB - job->tIndexed, job->tDone - job->tStageB);
         }
-        pipelineFreeIndexBuffers(job.get());      // (a list whose indexer failed still holds them)
         pipelineFinish(p, job, st);
     }
 }
@@ -735,15 +804,15 @@ static DcsStatus pipelineCreate(DcsCtx *ctx, int depth, uint32_t flags, DcsPipel
     // 0.76 / 0.75 ms per list, with the MD5 1.66 / 1.32 / 1.16 (tools/flac_write_bench.py --pipeline).
     if ((flags & DCS_PIPE_FLAC) != 0 && (flags & DCS_PIPE_PLAN_ON_DEVICE) != 0 && (flags & kPipeLatency) == 0)
         nWorkers = std::min(depth, 4);
-    if (const char *w = getenv("DCS_PIPE_WORKERS"))
-        nWorkers = std::max(1, std::min(64, atoi(w)));
+    if (pipeSwitches().workers != 0)
+        nWorkers = pipeSwitches().workers;
     int nUploaders = 0;
     if (flags & DCS_PIPE_INDEX_ON_DEVICE)
     {
         // stage A costs a worker a quarter to half a millisecond per list: two of them keep up with any rate the link allows
         nUploaders = (flags & kPipeLatency) ? std::min(depth, 4) : depth >= 4 ? 2 : 1;      // (one waiting caller: its parts go up side by side)
-        if (const char *u = getenv("DCS_PIPE_UPLOADERS"))
-            nUploaders = std::max(1, std::min(8, atoi(u)));
+        if (pipeSwitches().uploaders != 0)
+            nUploaders = pipeSwitches().uploaders;
         nWorkers += nUploaders;
     }
     p->nUploaders = nUploaders;
@@ -760,10 +829,8 @@ static DcsStatus pipelineCreate(DcsCtx *ctx, int depth, uint32_t flags, DcsPipel
         // stream, on a handful of lanes), and neither a worker's copies and 40-microsecond kernels nor the other
         // indexer's launch must queue up behind one.
         // (DCS_PIPE_INDEXER_PRIO=ab, a / b one of l(east) g(reatest) n(ormal): the two indexers' priorities, an experiment switch)
-        static const char *prioEnv = getenv("DCS_PIPE_INDEXER_PRIO");
         auto prioOf = [&](char c, int dflt) { return c == 'l' ? prioLeast : c == 'g' ? prioGreatest : c == 'n' ? (prioLeast + prioGreatest) / 2 : dflt; };
-        const int idxPrio = i == nWorkers ? prioOf(prioEnv && prioEnv[0] ? prioEnv[0] : 0, prioLeast)
-                                          : prioOf(prioEnv && prioEnv[0] && prioEnv[1] ? prioEnv[1] : 0, prioGreatest);
+        const int idxPrio = i == nWorkers ? prioOf(pipeSwitches().indexerPrio[0], prioLeast) : prioOf(pipeSwitches().indexerPrio[1], prioGreatest);
         const hipError_t e = i >= nWorkers ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, idxPrio)
                                            : hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
         if (e != hipSuccess)
@@ -801,9 +868,9 @@ extern "C" void dcs_pipeline_destroy(DcsPipeline *p)
     for (std::thread &t : p->indexers)
         t.join();
     (void)hipSetDevice(p->ctx->device);
-    pipelineRelease(p, p->held);
+    pipelineRelease(p->held);
     for (DcsPipeline::JobPtr &j : p->order)
-        pipelineRelease(p, j);
+        pipelineRelease(j);
     for (hipStream_t s : p->streams)
         (void)hipStreamDestroy(s);
     delete p;
@@ -844,7 +911,7 @@ static DcsStatus pipelineTakeOldest(DcsPipeline *p, DcsPipeline::JobPtr &job)
     const double tc0 = nowMs();
     (void)hipSetDevice(p->ctx->device);
     const double tc1 = nowMs();
-    pipelineRelease(p, p->held);
+    pipelineRelease(p->held);
     pipeLog("caller", 0, "set-device", tc0, tc1);
     pipeLog("caller", 0, "release", tc1, nowMs());
     {
@@ -860,11 +927,10 @@ static DcsStatus pipelineTakeOldest(DcsPipeline *p, DcsPipeline::JobPtr &job)
     return DCS_OK;
 }
 
-extern "C" DcsStatus dcs_pipeline_collect(DcsPipeline *p, DcsPipelineResult *out)
+// collect: the oldest list becomes the held one, and what both kinds of result have in common is filled in
+template <class Result>
+static DcsStatus pipelineCollect(DcsPipeline *p, Result *out, DcsPipeline::JobPtr &job)
 {
-    if (p == nullptr || out == nullptr || (p->flags & DCS_PIPE_FLAC) != 0)     // (a FLAC pipeline's lists are dcs_pipeline_collect_flac's)
-        return DCS_ERR_INVALID_ARG;
-    DcsPipeline::JobPtr job;
     const DcsStatus taken = pipelineTakeOldest(p, job);
     if (taken != DCS_OK)
         return taken;
@@ -876,12 +942,22 @@ extern "C" DcsStatus dcs_pipeline_collect(DcsPipeline *p, DcsPipelineResult *out
     out->deviceMs = static_cast<float>(job->deviceMs);
     if (job->status == DCS_OK)
     {
-        out->pcm = job->pcm;
         out->err = job->err;
         out->frameOffsets = job->firstJob.data();
         out->nFrames = job->firstJob.empty() ? 0u : job->firstJob.back();
     }
     return job->status;
+}
+
+extern "C" DcsStatus dcs_pipeline_collect(DcsPipeline *p, DcsPipelineResult *out)
+{
+    if (p == nullptr || out == nullptr || (p->flags & DCS_PIPE_FLAC) != 0)     // (a FLAC pipeline's lists are dcs_pipeline_collect_flac's)
+        return DCS_ERR_INVALID_ARG;
+    DcsPipeline::JobPtr job;
+    const DcsStatus st = pipelineCollect(p, out, job);
+    if (job && st == DCS_OK)
+        out->pcm = job->pcm;
+    return st;
 }
 
 extern "C" DcsStatus dcs_pipeline_collect_flac(DcsPipeline *p, DcsPipelineFlacResult *out)
@@ -889,264 +965,15 @@ extern "C" DcsStatus dcs_pipeline_collect_flac(DcsPipeline *p, DcsPipelineFlacRe
     if (p == nullptr || out == nullptr || (p->flags & DCS_PIPE_FLAC) == 0)
         return DCS_ERR_INVALID_ARG;
     DcsPipeline::JobPtr job;
-    const DcsStatus taken = pipelineTakeOldest(p, job);
-    if (taken != DCS_OK)
-        return taken;
-    memset(out, 0, sizeof(*out));
-    out->status = job->status;
-    out->nStreams = job->nStreams;
-    out->hostMs = static_cast<float>(job->hostMs);
-    out->path = job->path;
-    out->deviceMs = static_cast<float>(job->deviceMs);
-    if (job->status == DCS_OK)
+    const DcsStatus st = pipelineCollect(p, out, job);
+    if (job && st == DCS_OK)
     {
         out->flac = job->flac.bytes();
         out->flacOffsets = job->flac.offsets();
         out->info = job->flac.info();
-        out->err = job->err;
-        out->frameOffsets = job->firstJob.data();
-        out->nFrames = job->firstJob.empty() ? 0u : job->firstJob.back();
     }
-    return job->status;
-}
-
-// dcs_decode_streams for a LARGE list: cut into parts (contiguous stream ranges balanced by frames) that go through a
-// pipeline the context keeps for the purpose (index pass on the host pool), so that the planner, packer and upload of
-// one part run while another part is indexed and a third decodes and comes back; every worker copies its part's PCM
-// straight into the caller's buffer.  One synchronous call for the caller, the same PCM -- 15 ms become 5 for 65 536
-// frames.  *handled = false: the list is small, the caller takes the direct path.
-DcsStatus dcsDecodeStreamsInParts(DcsCtx *ctx, const DcsStreamRef *streams, uint32_t nStreams, uint32_t extraFrames,
-                                  int16_t *pcmOut, size_t pcmCapFrames, uint32_t *frameOffsets, uint32_t *errOut, bool *handled)
-{
-    *handled = false;
-    constexpr uint32_t kParts = 8;
-    if (nStreams < 4 * kParts)
-        return DCS_OK;
-    std::vector<uint32_t> frames(nStreams);
-    std::vector<uint64_t> first(static_cast<size_t>(nStreams) + 1, 0);
-    for (uint32_t k = 0 ; k < nStreams ; ++k)
-    {
-        if (streams[k].data == nullptr || streams[k].len < 3)
-            return DCS_OK;                          // (the direct path reports it)
-        const uint32_t nf = (static_cast<uint32_t>(streams[k].data[0]) << 8) | streams[k].data[1];
-        if (nf == 0)
-            return DCS_OK;
-        frames[k] = nf + extraFrames;
-        first[k + 1] = first[k] + frames[k];
-    }
-    if (first[nStreams] < 32768 || first[nStreams] > pcmCapFrames || first[nStreams] > 0xFFFFFFFFull)
-        return DCS_OK;
-    const bool onDevice = ctx->largeListOnDevice;
-    if (ctx->internalPipe == nullptr)
-    {
-        const DcsStatus st = pipelineCreate(ctx, static_cast<int>(kParts), (onDevice ? DCS_PIPE_ALL_ON_DEVICE : 0u) | kPipeLatency, &ctx->internalPipe);
-        if (st != DCS_OK)
-            return DCS_OK;                          // (no pipeline: the direct path still works)
-        if (onDevice)
-            ctx->internalPipe->roundGather = kParts;
-    }
-    *handled = true;
-    // The parts taper: the call ends one part's latency (build, create, upload, kernel, download) after the index pass
-    // has reached the list's last stream, so the last parts are small -- 4 4 4 4 3 2 2 1 twenty-fourths of the frames
-    // (equal parts: 4.6 ms for 65 536 frames, of which 1.45 behind the index pass).
-    // (the walk shared with the device: the device walks the LAST part(s), and what it does behind its walk -- planner, packer,
-    // decode, the PCM's way down -- is the call's tail: those parts are the small ones)
-    static const uint32_t kWeightHost[kParts] = { 4, 4, 4, 4, 3, 2, 2, 1 }, kWeightDevice[kParts] = { 3, 3, 3, 3, 3, 3, 3, 3 },
-                          kWeightShared[kParts] = { 4, 4, 4, 3, 3, 3, 2, 1 };
-    const uint32_t *kWeight = !onDevice ? kWeightHost : ctx->largeListShared ? kWeightShared : kWeightDevice;
-    uint32_t cut[kParts + 1];
-    {
-        uint32_t wSum = 0, wAcc = 0;
-        for (uint32_t r = 0 ; r < kParts ; ++r)
-            wSum += kWeight[r];
-        cut[0] = 0;
-        for (uint32_t r = 1 ; r < kParts ; ++r)
-        {
-            wAcc += kWeight[r - 1];
-            const uint64_t target = first[nStreams] * wAcc / wSum;
-            uint32_t k = static_cast<uint32_t>(std::lower_bound(first.begin(), first.end(), target) - first.begin());
-            // every part keeps at least one stream (nStreams >= 4 * kParts)
-            k = std::max(k, cut[r - 1] + 1);
-            k = std::min(k, nStreams - (kParts - r));
-            cut[r] = k;
-        }
-        cut[kParts] = nStreams;
-    }
-    DcsStatus st = DCS_OK;
-    // the index pass over the WHOLE list in one region of the host pool (eight regions of 32 streams each would balance
-    // badly over the pool's threads), then the parts go to the workers with their records
-    // (only the host-index path needs them: 148 B per frame, kept per calling thread; the device path leaves them empty)
-    thread_local std::vector<DcsFrameIndex> records;
-    std::vector<DcsStreamInfo> infos;
-    std::vector<uint64_t> firstRecord;
-    if (!onDevice)
-    {
-        infos.resize(nStreams);
-        firstRecord.resize(nStreams);
-        uint64_t nRec = 0;
-        for (uint32_t k = 0 ; k < nStreams ; ++k)
-        {
-            firstRecord[k] = nRec;
-            nRec += frames[k] - extraFrames;
-        }
-        if (records.size() < nRec)
-            records.resize(nRec);
-    }
-    const double tI0 = nowMs();
-    // a part goes to the workers the moment the last of its streams has been indexed (by whichever pool thread that was):
-    // planner, packer, upload and decode of the early parts run under the index pass of the late ones
-    std::atomic<uint32_t> left[kParts];
-    std::atomic<uint32_t> submitted{ 0 };
-    std::atomic<int> submitError{ DCS_OK };
-    std::vector<uint8_t> partOf(nStreams);
-    for (uint32_t r = 0 ; r < kParts ; ++r)
-    {
-        left[r].store(cut[r + 1] - cut[r]);
-        for (uint32_t k = cut[r] ; k < cut[r + 1] ; ++k)
-            partOf[k] = static_cast<uint8_t>(r);
-    }
-    DcsFrameIndex *const recs = records.data();     // (`records` is thread-local: the pool threads must not name it)
-    const std::function<void(uint32_t)> done = [&, recs](uint32_t k) {
-        const uint32_t r = partOf[k];
-        if (left[r].fetch_sub(1) != 1)
-            return;
-        const uint64_t f0 = first[cut[r]];
-        const DcsStatus s1 = pipelineSubmit(ctx->internalPipe, streams + cut[r], cut[r + 1] - cut[r], extraFrames,
-                                            pcmOut + f0 * DCS_FRAME_SAMPLES, errOut ? errOut + f0 : nullptr,
-                                            recs, firstRecord.data() + cut[r], infos.data() + cut[r]);
-        if (s1 == DCS_OK)
-            submitted.fetch_add(1);
-        else
-        {
-            int expected = DCS_OK;
-            submitError.compare_exchange_strong(expected, s1);
-        }
-    };
-    const int idxThreads = 0;        // (all of the pool: leaving a quarter of the CPUs to the workers was measured, 6.8 against 5.8 ms)
-    CacheBuf sharedPinned;
-    uint32_t hostParts = 0;
-    double tCall0 = nowMs();
-    if (onDevice)
-    {
-        // The walk SHARED between host and device (dcs_ctx_set_large_list_path 2, the default; round 5).  The index kernel takes as
-        // long as its longest stream whatever the number of streams (a lone wavefront per stream: 1.9 ms for 256 frames), and until
-        // it is through nothing of the list can be decoded; the host pool walks a stream fourteen times faster and delivers the
-        // list's FIRST parts while the device walks the last ones: their planner, packer, decode and -- what counts -- their PCM's
-        // way down run under the index kernel.  The host's records are the index kernel's, byte for byte (tests/test_gpu_parity.py),
-        // so they go up and take its place (pipelineWorker).  How many parts the host takes follows what was measured: the side
-        // that finished later in the last call gets less in the next.
-        hostParts = ctx->largeListShared ? static_cast<uint32_t>(std::max(0, std::min(static_cast<int>(kParts) - 1, ctx->sharedHostParts))) : 0u;
-        //  The pool runs ONE parallel region at a time: with several contexts decoding large lists at once (dcs_node,
-        // dcs_decode_streams_sharded: a thread per device) the shared walks would queue up one behind the other, the last device
-        // waiting (N - 1) host walks before its first part is even submitted.  A context that finds the pool taken walks its whole
-        // list on its own device (mode 1's 3.3 ms, whatever the others do).  A share that has fallen to nothing is tried again
-        // with one part every sixteenth call.
-        if (hostParts != 0 && dcsIndexPoolBusy())
-            hostParts = 0;
-        if (ctx->largeListShared && ctx->sharedHostParts == 0 && (++ctx->sharedProbe & 15) == 0 && !dcsIndexPoolBusy())
-            hostParts = 1;
-        const uint32_t hostStreams = cut[hostParts];
-        const uint64_t hostRecs = first[hostStreams] - static_cast<uint64_t>(hostStreams) * extraFrames;
-        DcsFrameIndex *hRecs = nullptr;
-        DcsStreamInfo *hInfos = nullptr;
-        if (hostParts != 0)
-        {
-            if (sharedPinned.alloc(ctx, true, sizeof(DcsFrameIndex) * hostRecs + sizeof(DcsStreamInfo) * hostStreams + 64) != hipSuccess)
-            {
-                (void)hipGetLastError();
-                hostParts = 0;
-            }
-            else
-            {
-                hRecs = sharedPinned.as<DcsFrameIndex>();
-                hInfos = reinterpret_cast<DcsStreamInfo *>(sharedPinned.as<uint8_t>() + ((sizeof(DcsFrameIndex) * hostRecs + 15) & ~size_t(15)));
-                firstRecord.resize(hostStreams);
-                uint64_t nRec = 0;
-                for (uint32_t k = 0 ; k < hostStreams ; ++k)
-                {
-                    firstRecord[k] = nRec;
-                    nRec += frames[k] - extraFrames;
-                }
-            }
-        }
-        {
-            std::lock_guard<std::mutex> lk(ctx->internalPipe->m);
-            ctx->internalPipe->roundGather = kParts - hostParts;           // (the index round waits until its parts are all there)
-            ctx->internalPipe->lastHostWalkedDone = ctx->internalPipe->lastDeviceWalkedDone = 0;
-        }
-        tCall0 = nowMs();
-        // the device's parts first: index walk, planner, packer and decode on the device, the workers copy the PCM out
-        for (uint32_t r = hostParts ; r < kParts && st == DCS_OK ; ++r)
-        {
-            const uint64_t f0 = first[cut[r]];
-            st = pipelineSubmit(ctx->internalPipe, streams + cut[r], cut[r + 1] - cut[r], extraFrames,
-                                pcmOut + f0 * DCS_FRAME_SAMPLES, errOut ? errOut + f0 : nullptr);
-            if (st == DCS_OK)
-                submitted.fetch_add(1);
-        }
-        if (hostParts != 0 && st == DCS_OK)
-        {
-            // ... and the host's: a part goes to the pipeline the moment the pool has walked the last of its streams
-            const std::function<void(uint32_t)> walked = [&, hRecs, hInfos](uint32_t k) {
-                const uint32_t r = partOf[k];
-                if (left[r].fetch_sub(1) != 1)
-                    return;
-                const uint64_t f0 = first[cut[r]];
-                const DcsStatus s1 = pipelineSubmit(ctx->internalPipe, streams + cut[r], cut[r + 1] - cut[r], extraFrames,
-                                                    pcmOut + f0 * DCS_FRAME_SAMPLES, errOut ? errOut + f0 : nullptr,
-                                                    hRecs, firstRecord.data() + cut[r], hInfos + cut[r]);
-                if (s1 == DCS_OK)
-                    submitted.fetch_add(1);
-                else
-                {
-                    int expected = DCS_OK;
-                    submitError.compare_exchange_strong(expected, s1);
-                }
-            };
-            st = dcsIndexStreamsNotify(streams, hostStreams, idxThreads, hRecs, firstRecord.data(), hInfos, &walked);
-            if (st == DCS_OK)
-                st = static_cast<DcsStatus>(submitError.load());
-        }
-    }
-    else
-    {
-        st = dcsIndexStreamsNotify(streams, nStreams, idxThreads, recs, firstRecord.data(), infos.data(), &done);
-        if (st == DCS_OK)
-            st = static_cast<DcsStatus>(submitError.load());
-    }
-    const double tI1 = nowMs();
-    for (uint32_t r = 0, n = submitted.load() ; r < n ; ++r)
-    {
-        DcsPipelineResult res;
-        const DcsStatus s1 = dcs_pipeline_collect(ctx->internalPipe, &res);
-        if (st == DCS_OK)
-            st = s1;
-    }
-    if (onDevice && hostParts != 0)
-    {
-        // who finished later?  (the pool's parts are submitted as they are walked, so both times are of lists of this call)
-        double tHost, tDev;
-        {
-            std::lock_guard<std::mutex> lk(ctx->internalPipe->m);
-            tHost = ctx->internalPipe->lastHostWalkedDone - tCall0;
-            tDev = ctx->internalPipe->lastDeviceWalkedDone - tCall0;
-        }
-        if (st == DCS_OK && tHost > 0 && tDev > 0)
-        {
-            if (tHost > tDev + 0.15 && ctx->sharedHostParts > 0)
-                ctx->sharedHostParts -= 1;
-            else if (tDev > tHost + 0.15 && ctx->sharedHostParts < static_cast<int>(kParts) - 1)
-                ctx->sharedHostParts += 1;
-        }
-        if (getenv("DCS_PIPE_TRACE"))
-            fprintf(stderr, "decode in parts: %u of %u parts walked by the host pool, done at %.2f ms; the device's at %.2f ms; next call %d\n",
-                    hostParts, kParts, tHost, tDev, ctx->sharedHostParts);
-    }
-    sharedPinned.release();
-    if (getenv("DCS_PIPE_TRACE"))
-        fprintf(stderr, "decode in parts: index %.2f ms, parts %.2f ms\n", tI1 - tI0, nowMs() - tI1);
-    if (frameOffsets != nullptr)
-        for (uint32_t k = 0 ; k <= nStreams ; ++k)
-            frameOffsets[k] = static_cast<uint32_t>(first[k]);
     return st;
 }
+
+// dcs_decode_streams for a LARGE list, in parts through the context's own pipeline
+#include "dcs_large_list.hip.h"

@@ -14,6 +14,7 @@ import flac_write_cases as C
 import flac_write_ref as R
 from dcsexplorer_amd.api import (ERR_BAD_STREAM, ERR_INVALID_ARG, FLAC_WRITE_INFO_DTYPE, DcsError, PipelineFlacResult, PipelineResult,
                                  _ptr, _stream_refs)
+from util import ALL_FORMATS, make_stream, os_for
 
 pytestmark = pytest.mark.gpu
 
@@ -243,6 +244,57 @@ def test_bad_list_and_the_one_behind_it(gpu_ctx, want, flags):
     check_list(pipe.collect_flac(), want[2], True, "behind the bad list")
     check_list(first_result, want[0], True, "copied before two more collects")
     pipe.close()
+
+
+def flac_behind_attempts(gpu_ctx, oracle, hard, behind):
+    """`hard` (extra_frames=2), then `behind`, through a FLAC pipeline with the planner on the device and 8 frames per wavefront:
+    hard's FLAC bytes against decode_streams_flac on the same list and against the restatement of the oracle's PCM, its error
+    words zero -> (hard's path, behind's result with its path last)"""
+    files = [R.write(oracle.decode(o, v, [s], [l], ((s[0] << 8) | s[1]) + 2), 31250, True)[0] for o, s, v, l in hard]
+    try:
+        gpu_ctx.set_frames_per_wave(8)
+        sync_out, sync_info, sync_err, sync_first = gpu_ctx.decode_streams_flac(hard, extra_frames=2)
+        pipe = pipeline(gpu_ctx, 7, flac=True)
+        pipe.submit(hard, extra_frames=2)
+        pipe.submit(behind[0], extra_frames=behind[1])
+        out, info, err, first = pipe.collect_flac()[:4]
+        path = pipe.last_path
+        got_behind = pipe.collect_flac() + (pipe.last_path,)
+        pipe.close()
+    finally:
+        gpu_ctx.set_frames_per_wave(0)
+    assert len(out) == len(hard) and np.array_equal(first, sync_first) and np.array_equal(info, sync_info)
+    for k, (a, b, c) in enumerate(zip(out, sync_out, files)):
+        assert a == b, (k, "decode_streams_flac", len(a), len(b))
+        assert a == c, (k, "restatement", len(a), len(c))
+    assert not err.any() and not sync_err.any()
+    return path, got_behind
+
+
+def test_flac_ending_behind_a_list_planned_again(gpu_ctx, oracle, want):
+    """the list of test_large_frames_are_planned_again_on_the_device_with_fewer_frames_per_chunk (tests/test_gpu_corpus.py): the
+    first attempt's FLAC buffers are dropped, the list is planned again on the device and its FLAC ending queued a second time;
+    the ordinary list behind it is what it is alone"""
+    hard = [(os_for(f, f & 1), make_stream(f, 60 + f, seed=67000 + f, profile=4, nbands=10), 255, 0x64) for f in (0, 1, 3)]
+    hard += [(os_for(f, 1), make_stream(f, 40, seed=67100 + f), 255, 0x64) for f in ALL_FORMATS]
+    path, behind = flac_behind_attempts(gpu_ctx, oracle, hard, LISTS[0])
+    assert path == 7
+    check_list(behind, want[0], True, "behind the list planned again")
+    assert behind[-1] == 7
+
+
+def test_flac_ending_behind_a_list_handed_back(gpu_ctx, oracle):
+    """the saturated list of tests/test_gpu_corpus.py, which overflows the bit pool with six and with four frames per chunk too:
+    three attempts' FLAC endings are abandoned, then the host-planned path writes the list's FLAC; the easy list behind it stays
+    on the device"""
+    hard = [(os_for(f, f & 1), make_stream(f, 48 + f, seed=66000 + f, profile=4), 255, 0x64) for f in ALL_FORMATS]
+    easy = [(os_for(f, f & 1), make_stream(f, 48 + f, seed=66100 + f), 255, 0x64) for f in ALL_FORMATS]
+    path, behind = flac_behind_attempts(gpu_ctx, oracle, hard, (easy, 2))
+    assert path == 0
+    assert behind[-1] == 7
+    alone_out, alone_info, alone_err, alone_first = gpu_ctx.decode_streams_flac(easy, extra_frames=2)
+    assert behind[0] == alone_out and np.array_equal(behind[1], alone_info)
+    assert np.array_equal(behind[2], alone_err) and np.array_equal(behind[3], alone_first)
 
 
 def test_destroy_with_uncollected_lists(gpu_ctx):

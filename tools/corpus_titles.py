@@ -1,5 +1,6 @@
 """BASELINE configs[4] at SURVEY's size (29 titles x 600 streams) through dcs_pipeline, one title per list: seconds per pass for several
-numbers of titles in flight, and where a title's time goes (DCS_PIPE_TRACE=1 on the last pass, or on pass TRACE_PASS: the pipeline's "pipe life" lines, averaged).
+numbers of titles in flight, and where a title's time goes (DCS_PIPE_TRACE=1, which the library reads once, for the whole child; the "pipe life"
+lines of the last pass, or of pass TRACE_PASS, averaged).
 argv[1:]: titles in flight to try (default 4 8)"""
 import sys, os, time, re, subprocess
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,10 +20,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     ctx = D.Context(0)
     pipe = ctx.pipeline(depth, index_on_device=True, pack_on_device=True, plan_on_device=True)
     for p in range(3):
-        if p == int(os.environ.get("TRACE_PASS", "2")):
-            os.environ["DCS_PIPE_TRACE"] = "1"
-        else:
-            os.environ.pop("DCS_PIPE_TRACE", None)
+        sys.stderr.write("==== pass %d\n" % p); sys.stderr.flush()
         done = 0; t0 = time.perf_counter(); lat = []; sub = []
         for i, (refs, keep) in enumerate(lists):
             sub.append(time.perf_counter()); pipe.submit_refs(refs, titles[i][1] - titles[i][0])
@@ -36,10 +34,11 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     pipe.close(); ctx.close()
     sys.exit(0)
 for depth in (sys.argv[1:] or ["4", "8"]):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", depth], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", depth], capture_output=True, text=True, env=dict(os.environ, DCS_PIPE_TRACE="1"))
     print(r.stdout, end="")
-    life = [list(map(float, re.findall(r"-?\d+\.\d+", l.split(":", 1)[1]))) for l in r.stderr.splitlines() if l.startswith("pipe life:")]
-    up = [list(map(float, re.findall(r"-?\d+\.\d+", l.split(":", 1)[1]))) for l in r.stderr.splitlines() if l.startswith("pipe upload:")]
+    traced = r.stderr.split("==== pass %d\n" % int(os.environ.get("TRACE_PASS", "2")), 1)[-1].split("==== pass", 1)[0].splitlines()
+    life = [list(map(float, re.findall(r"-?\d+\.\d+", l.split(":", 1)[1]))) for l in traced if l.startswith("pipe life:")]
+    up = [list(map(float, re.findall(r"-?\d+\.\d+", l.split(":", 1)[1]))) for l in traced if l.startswith("pipe upload:")]
     if life:
         names = ["submit->taken", "upload", "wait for indexer", "index round", "wait for worker", "stage B"]
         print("  per title, ms (mean / max): " + ", ".join("%s %.1f / %.1f" % (n, sum(x[i] for x in life) / len(life), max(x[i] for x in life)) for i, n in enumerate(names)))
