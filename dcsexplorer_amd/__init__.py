@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     SWEEP_RESULT_DTYPE, SWEEP_JOB_DTYPE, SWEEP_MEASURE, sweep_sq_err, encode_sweep_group_frames, encode_fit_choose,
     TRANSCODE_COPIED, TRANSCODE_REENCODED, TRANSCODE_REENCODE_ALL, TRANSCODE_INFO_DTYPE, TRANSCODE_OS, transcode_params, transcode_plan,
     ResampleFilter, RESAMPLE_AT_UNITY, resample_filter_default, resample_count,
+    OUT_SEQUENCE, RATE_INFO_DTYPE, resample_out_count, resample_out_walk,
     WavInfo, ENCODE_FILE_INFO_DTYPE, WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32, WAV_F64, WAV_IMA, FILE_WAV, FILE_DCSA_COPY,
     FILE_DCSA_REENCODE, FILE_WALK_NONE, FILE_WALK_DEVICE, FILE_WALK_HOST, wav_parse, encode_files_plan,
     FlacInfo, FLAC_FRAME_DTYPE, WAV_S8, FILE_FLAC, flac_parse, flac_index,

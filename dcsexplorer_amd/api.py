@@ -157,6 +157,10 @@ FLAC_SEQUENCE = 2
 FLAC_WRITE_INFO_DTYPE = np.dtype([("nSamples", "<u8"), ("nBytes", "<u8"), ("nBlocks", "<u4"), ("nConstant", "<u4"), ("nVerbatim", "<u4"),
                                   ("nFixed", "<u4"), ("minFrame", "<u4"), ("maxFrame", "<u4")], align=True)
 
+# dcs_resample_out_streams, dcs_decode_streams_at: the decode call's flag, and what the converter made of each stream
+OUT_SEQUENCE = 2
+RATE_INFO_DTYPE = np.dtype([("nIn", "<u8"), ("nOut", "<u8"), ("nClipped", "<u8"), ("peak", "<f4"), ("reserved", "<u4")], align=True)
+
 
 # dcs_level_*: what happens to a stream's level between the converter and the encoder, and what the stage did
 class Level(ctypes.Structure):
@@ -232,6 +236,7 @@ EXPORTS = [
     "dcs_flac_write_bound", "dcs_flac_write_check", "dcs_flac_write_streams", "dcs_decode_streams_flac",
     "dcs_encode_sweep", "dcs_encode_sweep_group_frames", "dcs_encode_fit",
     "dcs_level_gain", "dcs_level_streams", "dcs_resample_streams_level", "dcs_encode_streams_at_level", "dcs_encode_files_level",
+    "dcs_resample_out_count", "dcs_resample_out_walk", "dcs_resample_out_streams", "dcs_decode_streams_at",
 ]
 
 
@@ -561,6 +566,16 @@ def load_library():
     L.dcs_encode_files.restype = i32
     L.dcs_encode_files.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32, vp, sz,
                                    vp, vp]
+    if hasattr(L, "dcs_decode_streams_at"):     # (DCS_HIP_LIB may name a build from before there was an output rate)
+        L.dcs_resample_out_count.restype = i32
+        L.dcs_resample_out_count.argtypes = [ctypes.c_uint64, u32, ctypes.POINTER(ResampleFilter), u32, ctypes.POINTER(ctypes.c_uint64)]
+        L.dcs_resample_out_walk.restype = i32
+        L.dcs_resample_out_walk.argtypes = [ctypes.c_uint64, u32, ctypes.POINTER(ResampleFilter), u32, vp, vp, ctypes.c_uint64,
+                                            ctypes.POINTER(ctypes.c_uint64)]
+        L.dcs_resample_out_streams.restype = i32
+        L.dcs_resample_out_streams.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(ResampleFilter), u32, vp, sz, vp, vp]
+        L.dcs_decode_streams_at.restype = i32
+        L.dcs_decode_streams_at.argtypes = [vp, vp, u32, u32, u32, ctypes.POINTER(ResampleFilter), u32, vp, sz, vp, vp, vp]
     if hasattr(L, "dcs_level_gain"):        # (DCS_HIP_LIB may name a build from before there was the level stage: A/B against it)
         fp = ctypes.POINTER(ctypes.c_float)
         L.dcs_level_gain.restype = i32
@@ -918,6 +933,42 @@ def resample_count(n_values, rate, channels=1, filter=None, at_unity=False):
                                              RESAMPLE_AT_UNITY if at_unity else 0, ctypes.byref(out)))
     del keep
     return int(out.value)
+
+
+def _resample_out_bound(n_samples, rate, at_unity):
+    """at least the converted length of n_samples samples at 31 250 Hz (host arithmetic, no walk): the end rule keeps the
+    position chain inside n_samples x rate / 31250, and the margin covers its rounding (INTEGRATION.md rule 40; the library's own
+    bound on a walk, rsSlots, is n_samples x ratio + 4)"""
+    if rate == 31250 and not at_unity:
+        return n_samples
+    return n_samples * max(rate, 0) // 31250 + 8
+
+
+def resample_out_count(n_samples, rate, filter=None, at_unity=False):
+    """dcs_resample_out_count (host only): the number of samples at `rate` Hz (4 000 .. 65 535) that n_samples samples at
+    31 250 Hz convert to; filter as Context.resample_streams"""
+    f, keep = _resample_filter(filter)
+    out = ctypes.c_uint64()
+    _check(load_library().dcs_resample_out_count(int(n_samples), int(rate), ctypes.byref(f) if f is not None else None,
+                                                 RESAMPLE_AT_UNITY if at_unity else 0, ctypes.byref(out)))
+    del keep
+    return int(out.value)
+
+
+def resample_out_walk(n_samples, rate, filter=None, at_unity=False):
+    """dcs_resample_out_walk (host only, a diagnostic): the converter's walk of such a stream -> (int64 input positions,
+    int32 start_filter_index values), one pair per output"""
+    f, keep = _resample_filter(filter)
+    fp = ctypes.byref(f) if f is not None else None
+    flags = RESAMPLE_AT_UNITY if at_unity else 0
+    cap = _resample_out_bound(int(n_samples), int(rate), at_unity)
+    pos, sfi = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int32)
+    count = ctypes.c_uint64()
+    _check(load_library().dcs_resample_out_walk(int(n_samples), int(rate), fp, flags, _ptr(pos), _ptr(sfi), cap, ctypes.byref(count)))
+    del keep
+    if count.value > cap:
+        raise DcsError(-1, "the walk made %d outputs, more than its bound %d" % (count.value, cap))
+    return pos[:count.value].copy(), sfi[:count.value].copy()
 
 
 def _levels(level, n):
@@ -1505,6 +1556,71 @@ class Context:
                 raise DcsError(st)
             frames.append(one.value)
         out, info, _, first = self._decode_refs_flac(refs, len(items), frames, extra_frames, FLAC_SEQUENCE | (FLAC_MD5 if md5 else 0))
+        return items, out, info, first
+
+    def resample_out_streams(self, pcm_list, rate, filter=None, at_unity=False):
+        """dcs_resample_out_streams: int16 PCM streams at 31 250 Hz (any length >= 1) -> (list of int16 arrays at `rate` Hz,
+        RATE_INFO_DTYPE array): libsamplerate's sinc converter at rate / 31250.0 between its own int16 conversions.  rate:
+        4 000 .. 65 535, one per call; filter: None = the library's table, or (float32 coefficients, increment); 31 250
+        returns the samples untouched unless at_unity."""
+        arrs = [np.ascontiguousarray(p, np.int16).ravel() for p in pcm_list]
+        n = len(arrs)
+        offs = np.zeros(n + 1, np.uint64)
+        offs[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+        pcm = np.concatenate(arrs) if n else np.zeros(1, np.int16)
+        f, keep = _resample_filter(filter)
+        fp = ctypes.byref(f) if f is not None else None
+        flags = RESAMPLE_AT_UNITY if at_unity else 0
+        cap = sum(_resample_out_bound(a.size, int(rate), at_unity) for a in arrs)
+        out = np.zeros(max(cap, 1), np.int16)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info = np.zeros(max(n, 1), RATE_INFO_DTYPE)
+        _check(self.L.dcs_resample_out_streams(self.h, _ptr(pcm), _ptr(offs), n, int(rate), fp, flags, _ptr(out), cap, _ptr(out_offs),
+                                               _ptr(info)), self.h)
+        del keep
+        return [out[int(out_offs[i]):int(out_offs[i + 1])].copy() for i in range(n)], info[:n]
+
+    def _decode_refs_at(self, refs, n, frames, rate, extra_frames, filter, flags):
+        total = int(sum(frames)) + n * extra_frames
+        err = np.zeros(max(total, 1), np.uint32)
+        first = np.zeros(n + 1, np.uint32)
+        first[1:] = np.cumsum([f + extra_frames for f in frames])
+        f, keep = _resample_filter(filter)
+        fp = ctypes.byref(f) if f is not None else None
+        cap = sum(_resample_out_bound(int(fr + extra_frames) * FRAME_SAMPLES, int(rate), bool(flags & RESAMPLE_AT_UNITY)) for fr in frames)
+        out = np.zeros(max(cap, 1), np.int16)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info = np.zeros(max(n, 1), RATE_INFO_DTYPE)
+        _check(self.L.dcs_decode_streams_at(self.h, refs, n, extra_frames, int(rate), fp, flags, _ptr(out), cap, _ptr(out_offs),
+                                            _ptr(info), _ptr(err)), self.h)
+        del keep
+        return [out[int(out_offs[i]):int(out_offs[i + 1])].copy() for i in range(n)], info[:n], err[:total], first
+
+    def decode_streams_at(self, streams, rate, extra_frames=0, filter=None, at_unity=False, sequence=False):
+        """dcs_decode_streams_at: (os, bytes, volume, level) streams decoded as decode_streams decodes them (sequence: as
+        decode_stream_sequence does, one decoder object for the list), the PCM converted to `rate` Hz where it lies on the
+        device (as resample_out_streams converts it) -> (list of int16 arrays, RATE_INFO_DTYPE array, err, first_job); err
+        and first_job count decoded frames, as decode_streams gives them"""
+        streams = list(streams)
+        refs, keep = _stream_refs(streams)
+        frames = [(int(k[0]) << 8) | int(k[1]) for k in keep]
+        flags = (RESAMPLE_AT_UNITY if at_unity else 0) | (OUT_SEQUENCE if sequence else 0)
+        return self._decode_refs_at(refs, len(streams), frames, rate, extra_frames, filter, flags)
+
+    def extract_streams_at(self, romset, rate, volume=255, extra_frames=2, filter=None, at_unity=False):
+        """extract_streams whose PCM leaves the device at `rate` Hz: -> (plan items, list of int16 arrays, RATE_INFO_DTYPE
+        array, first frame of each stream)"""
+        items = romset.extract_plan()
+        refs = romset.stream_refs(items, volume)
+        frames = []
+        for k in range(len(items)):
+            one = ctypes.c_uint64()
+            st = self.L.dcs_count_stream_frames(ctypes.byref(refs[k]), 1, 0, ctypes.byref(one))
+            if st != 0:
+                raise DcsError(st)
+            frames.append(one.value)
+        out, info, _, first = self._decode_refs_at(refs, len(items), frames, rate, extra_frames, filter,
+                                                   OUT_SEQUENCE | (RESAMPLE_AT_UNITY if at_unity else 0))
         return items, out, info, first
 
     def encode_files(self, files, version=0x9400, fmt=None, filter=None, at_unity=False, level=None, **params):

@@ -17,6 +17,9 @@
 // Each output's value depends only on the whole input and the output's position.  How many outputs there are depends on the
 // reference's calls as well: the end-of-input call runs once with a 512-float buffer (CloseStream, DCSEncoder.cpp:717-721),
 // and the end rule is an f64 sum in the converter's buffer indices, so the walk replays the buffer's bookkeeping (rsWalk).
+//
+// The same converter runs the other way behind the decoder (the end of this file): int16 at 31 250 Hz to int16 at an output
+// rate, ratio outRate / 31250.0, with R3's int16 instantiation and one walk-record table for the whole call.
 #pragma once
 
 namespace {
@@ -162,13 +165,14 @@ bool rsFilterValid(const DcsResampleFilter *f)
     return true;
 }
 
-// the fixed quantities of one stream (mono samples nIn at `rate`)
-RsStream rsStreamOf(uint64_t nIn, uint32_t rate, const DcsResampleFilter &f, uint32_t flags)
+// the fixed quantities of one stream of nIn mono samples converted at ratio = to / from, the two rates as the caller's
+// contract divides them: 31250.0 / rate in front of the encoders, outRate / 31250.0 behind the decoder (one f64 division)
+RsStream rsStreamOf(uint64_t nIn, double to, double from, bool passThrough, const DcsResampleFilter &f)
 {
     RsStream s{};
     s.nIn = nIn;
-    s.passThrough = rate == 31250 && (flags & DCS_RESAMPLE_AT_UNITY) == 0;
-    const double ratio = 31250.0 / static_cast<double>(rate);
+    s.passThrough = passThrough;
+    const double ratio = to / from;
     double count = (f.nCoeffs - 2 + 2.0) / f.increment;
     if (ratio < 1.0)
         count /= ratio;
@@ -181,6 +185,12 @@ RsStream rsStreamOf(uint64_t nIn, uint32_t rate, const DcsResampleFilter &f, uin
     const int32_t bLen = static_cast<int32_t>(lrint(2.5 * (f.nCoeffs - 2) / (f.increment * 1.0) * 256));
     s.bLen = bLen > 4096 ? bLen : 4096;
     return s;
+}
+
+// ... of mono samples nIn at `rate`, for the encoders
+RsStream rsStreamOf(uint64_t nIn, uint32_t rate, const DcsResampleFilter &f, uint32_t flags)
+{
+    return rsStreamOf(nIn, 31250.0, static_cast<double>(rate), rate == 31250 && (flags & DCS_RESAMPLE_AT_UNITY) == 0, f);
 }
 
 uint64_t rsMonoLength(uint64_t nValues, int32_t channels) { return channels == 2 ? (nValues + 1) / 2 : nValues; }
@@ -238,9 +248,14 @@ __global__ __launch_bounds__(64) void rsWalkKernel(const RsStream *__restrict__ 
 
 // One output of calc_output_single (src_sinc.c:280-333): coefficient i + fraction * (coefficient i+1 - i), the difference a
 // float subtraction, each half summed in f64 in the loop's order, then left + right.  x: the stream's mono samples, zero
-// outside [0, n).
+// outside [0, n): floats, or a decoder's int16, which enter as src_short_to_float_array makes them (samplerate.c:486-495),
+// (float)(s / 32768.0), exact for every int16 and so formed in registers.
+__device__ inline float rsSample(const float *__restrict__ x, int64_t d) { return x[d]; }
+__device__ inline float rsSample(const int16_t *__restrict__ x, int64_t d) { return static_cast<float>(x[d] / 32768.0); }
+
+template <class T>
 __device__ inline double rsOutput(const float *__restrict__ c, int32_t maxFilterIndex, int32_t increment, int32_t sfi,
-                                  const float *__restrict__ x, int64_t n, int64_t pos)
+                                  const T *__restrict__ x, int64_t n, int64_t pos)
 {
     int32_t fi = sfi;
     int32_t cc = (maxFilterIndex - fi) / increment;
@@ -253,7 +268,7 @@ __device__ inline double rsOutput(const float *__restrict__ c, int32_t maxFilter
         const int32_t indx = fi >> 12;
         const float c0 = c[indx], c1 = c[indx + 1];
         const double icoeff = static_cast<double>(c0) + fraction * static_cast<double>(c1 - c0);
-        const float v = (d >= 0 && d < n) ? x[d] : 0.0f;
+        const float v = (d >= 0 && d < n) ? rsSample(x, d) : 0.0f;
         left += icoeff * static_cast<double>(v);
         fi -= increment;
         ++d;
@@ -270,7 +285,7 @@ __device__ inline double rsOutput(const float *__restrict__ c, int32_t maxFilter
         const int32_t indx = fi >> 12;
         const float c0 = c[indx], c1 = c[indx + 1];
         const double icoeff = static_cast<double>(c0) + fraction * static_cast<double>(c1 - c0);
-        const float v = (d >= 0 && d < n) ? x[d] : 0.0f;
+        const float v = (d >= 0 && d < n) ? rsSample(x, d) : 0.0f;
         right += icoeff * static_cast<double>(v);
         fi -= increment;
         --d;
@@ -278,15 +293,36 @@ __device__ inline double rsOutput(const float *__restrict__ c, int32_t maxFilter
     return left + right;
 }
 
+// src_float_to_short_array as a build without CPU_CLIPS_* compiles it (samplerate.c:497-516): the float times 2^31 in f64,
+// the two ends clamped (and counted), else lrint and an arithmetic shift by 16.  The shift floors: -0.3 of a step is -1,
+// +0.7 of a step is 0.  That is libsamplerate's rounding and stays as it is.  (|v| < 2^31 where lrint runs: 32 bits hold it.)
+__device__ inline int16_t rsToShort(float y, uint32_t &clipped)
+{
+    const double v = static_cast<double>(y) * 2147483648.0;
+    if (v >= 2147483647.0)
+    {
+        ++clipped;
+        return 32767;
+    }
+    if (v <= -2147483648.0)
+    {
+        ++clipped;
+        return -32768;
+    }
+    return static_cast<int16_t>(static_cast<int32_t>(rint(v)) >> 16);
+}
+
 // R3: blockIdx.y strides over the streams, x over a stream's outputs.  LDS: the table is copied to LDS once per block
-// (tables up to kRsLdsMaxCoeffs); otherwise it is read through the caches.
+// (tables up to kRsLdsMaxCoeffs); otherwise it is read through the caches.  T = float: the encoders' side, floats in and
+// out.  T = int16_t: the decoder's side (rsConvertPcm16), int16 read where the decoder left it, quantised by rsToShort and
+// stored as int16; `clipped` then counts each stream's clamped outputs, and a pass-through copies the samples.
 const int32_t kRsLdsMaxCoeffs = 16384;          // 64 KiB
-template <bool LDS>
+template <bool LDS, class T>
 __global__ __launch_bounds__(256) void rsConvolveKernel(const float *__restrict__ coeffs, int32_t nCoeffs, int32_t tableInc,
                                                         const RsStream *__restrict__ streams, uint32_t nStreams,
                                                         const uint64_t *__restrict__ counts, const int2 *__restrict__ slots,
-                                                        const float *__restrict__ mono, float *__restrict__ out,
-                                                        uint32_t *__restrict__ peak)
+                                                        const T *__restrict__ mono, T *__restrict__ out,
+                                                        uint32_t *__restrict__ peak, unsigned long long *__restrict__ clipped)
 {
     extern __shared__ float ldsCoeffs[];
     const float *c = coeffs;
@@ -302,25 +338,30 @@ __global__ __launch_bounds__(256) void rsConvolveKernel(const float *__restrict_
     {
         const RsStream &s = streams[si];
         const uint64_t count = counts[si];
-        const float *x = mono + s.inOff;
+        const T *x = mono + s.inOff;
         const int64_t n = static_cast<int64_t>(s.nIn);
-        uint32_t top = 0;
+        uint32_t top = 0, nClipped = 0;
         for (uint64_t k = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x ; k < count ; k += uint64_t(gridDim.x) * blockDim.x)
         {
             float y;
             if (s.passThrough)
-                y = x[k];
+                y = rsSample(x, static_cast<int64_t>(k));
             else
             {
                 const int2 r = slots[s.slotOff + k];
                 y = static_cast<float>((s.floatInc / tableInc) * rsOutput(c, maxFilterIndex, s.increment, r.y, x, n, r.x));
             }
-            out[s.outOff + k] = y;
+            if constexpr (std::is_same<T, float>::value)
+                out[s.outOff + k] = y;
+            else
+                out[s.outOff + k] = s.passThrough ? x[k] : rsToShort(y, nClipped);
             const uint32_t b = __float_as_uint(fabsf(y));
             top = b > top ? b : top;
         }
         if (top != 0)
             atomicMax(&peak[si], top);
+        if (nClipped != 0)
+            atomicAdd(&clipped[si], static_cast<unsigned long long>(nClipped));
     }
 }
 
@@ -557,11 +598,11 @@ DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dM
     // about 4 096 blocks in all: each block of the LDS variant copies the table once and then strides over its outputs
     const dim3 grid = streamGrid(n, maxCount, 4096, 0);
     if (f.nCoeffs <= kRsLdsMaxCoeffs)
-        hipLaunchKernelGGL(rsConvolveKernel<true>, grid, dim3(256), sizeof(float) * f.nCoeffs, st, dCoeffs, f.nCoeffs,
-                           f.increment, dStr, n, dCounts, dSlots, dMono, dRes, dPeak);
+        hipLaunchKernelGGL((rsConvolveKernel<true, float>), grid, dim3(256), sizeof(float) * f.nCoeffs, st, dCoeffs, f.nCoeffs,
+                           f.increment, dStr, n, dCounts, dSlots, dMono, dRes, dPeak, static_cast<unsigned long long *>(nullptr));
     else
-        hipLaunchKernelGGL(rsConvolveKernel<false>, grid, dim3(256), 0, st, dCoeffs, f.nCoeffs, f.increment, dStr, n,
-                           dCounts, dSlots, dMono, dRes, dPeak);
+        hipLaunchKernelGGL((rsConvolveKernel<false, float>), grid, dim3(256), 0, st, dCoeffs, f.nCoeffs, f.increment, dStr, n,
+                           dCounts, dSlots, dMono, dRes, dPeak, static_cast<unsigned long long *>(nullptr));
     ENCCHK(hipGetLastError());
     c.peak.assign(n, 0);
     ENCCHK(hipMemcpyAsync(c.peak.data(), dPeak, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
@@ -773,5 +814,357 @@ extern "C" DcsStatus dcs_encode_streams_at_level(DcsCtx *ctx, const float *pcm, 
         return rsEncodeConverted(ctx, held, c, lv, nullptr, "stream", nullptr,
                                  "%s: the resampled signal peaks at |x| = %.9g, outside [-1, 1] (attenuate the input)", true, levelInfo,
                                  params, os93, EncOutput{ out, outCap, outOffsets, info, nullptr });
+    });
+}
+
+// ------------------------------------------------------------------ the other direction: 31 250 Hz int16 to an output rate
+//
+// dcs_resample_out_streams and the decode calls of dcs_decode_rate.hip.h: the same converter at ratio outRate / 31250.0,
+// int16 in (rsSample) and int16 out (rsToShort), one rate per call.  Output k's walk record (pos, start_filter_index)
+// depends on k and the ratio alone -- the chain is idx += step; advance(), the call-opening advance() does nothing to an
+// idx already in [0, 1), and a stream's length decides only where the end rule and the flush cap stop it -- so a call
+// keeps ONE record table, the longest stream's walk, of which every stream reads a prefix (slotOff 0), and walks each
+// distinct length once more without a sink for its count.
+
+namespace {
+
+const uint32_t kRsOutMinRate = 4000, kRsOutMaxRate = 65535;     // the upper end: what a FLAC frame header can say
+
+// the checks the output-rate entry points share, before any device work (sampleOffsets null: the rate, table and flags alone)
+DcsStatus rsOutCheck(uint32_t n, const uint64_t *sampleOffsets, uint32_t outRate, const DcsResampleFilter *filter, uint32_t flags,
+                     DcsResampleFilter &f, std::string &why)
+{
+    if ((flags & ~DCS_RESAMPLE_AT_UNITY) != 0)
+    {
+        why = "unknown flags";
+        return DCS_ERR_INVALID_ARG;
+    }
+    if (outRate < kRsOutMinRate || outRate > kRsOutMaxRate)
+    {
+        why = "output rate " + std::to_string(outRate) + " Hz is outside 4 000 .. 65 535";
+        return DCS_ERR_INVALID_ARG;
+    }
+    f = filter != nullptr ? *filter : rsDefaultFilter();
+    if (!rsFilterValid(&f))
+    {
+        why = "filter: not a valid libsamplerate table (increment >= 1, increment <= nCoeffs - 2 < 2^19, finite coefficients)";
+        return DCS_ERR_INVALID_ARG;
+    }
+    for (uint32_t i = 0 ; sampleOffsets != nullptr && i < n ; ++i)
+    {
+        if (sampleOffsets[i + 1] <= sampleOffsets[i])
+        {
+            why = "stream " + std::to_string(i) + ": empty";
+            return DCS_ERR_INVALID_ARG;
+        }
+        if (sampleOffsets[i + 1] - sampleOffsets[i] >= (uint64_t(1) << 31))
+        {
+            why = "stream " + std::to_string(i) + ": 2^31 samples or more";
+            return DCS_ERR_INVALID_ARG;
+        }
+    }
+    return DCS_OK;
+}
+
+RsStream rsOutStreamOf(uint64_t nIn, uint32_t outRate, const DcsResampleFilter &f, uint32_t flags)
+{
+    return rsStreamOf(nIn, static_cast<double>(outRate), 31250.0, outRate == 31250 && (flags & DCS_RESAMPLE_AT_UNITY) == 0, f);
+}
+
+// what the converter produced on the device: int16 samples, stream i = [offsets[i], offsets[i + 1])
+struct RsConverted16
+{
+    int16_t *d = nullptr;
+    std::vector<uint64_t> offsets;
+    std::vector<DcsRateInfo> info;
+};
+
+// The walks of one call whose streams hs all convert at one ratio: the shared record table (*dSlots, the longest stream's
+// walk) and counts[i].  The table is walked where rsHostRoute puts a stream of its length that is a list of its own: on
+// one device lane, or above kRsHostWalkMin outputs on the host.  Every other distinct length is walked without a sink on
+// the host pool, at the same time: device lanes, one a length, took 42.5 ms for 255 lengths of up to 511 frames, and the
+// call 56.6 ms where it takes 22.8 ms with the pool (profiles/decode_rate_bench.txt).  One wait.
+DcsStatus rsOutWalks(DcsCtx *ctx, const std::vector<RsStream> &hs, CacheArena &held, int2 **dSlots, std::vector<uint64_t> &counts)
+{
+    const hipStream_t st = dcsCtxStream(ctx);
+    const uint32_t n = static_cast<uint32_t>(hs.size());
+    // the distinct lengths, falling; the first one's walk is the table
+    std::vector<uint64_t> lengths(n);
+    for (uint32_t i = 0 ; i < n ; ++i)
+        lengths[i] = hs[i].nIn;
+    std::sort(lengths.begin(), lengths.end(), std::greater<uint64_t>());
+    lengths.erase(std::unique(lengths.begin(), lengths.end()), lengths.end());
+    const uint32_t nLen = static_cast<uint32_t>(lengths.size());
+    std::vector<RsStream> table(1, hs[0]);
+    table[0].nIn = lengths[0];
+    table[0].inOff = table[0].slotOff = 0;
+    table[0].nSlots = rsSlots(table[0]);
+    rsHostRoute(table);
+    const RsStream &tb = table[0];
+    ENCCHK(held.alloc(dSlots, tb.nSlots));
+    std::vector<uint64_t> lenCounts(nLen, 0);
+    if (!tb.hostWalk)
+    {
+        RsStream *dWalk = nullptr;
+        uint64_t *dCount = nullptr;
+        ENCCHK(held.alloc(&dWalk, 1));
+        ENCCHK(held.alloc(&dCount, 1));
+        ENCCHK(hipMemcpyAsync(dWalk, &tb, sizeof(RsStream), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(rsWalkKernel, dim3(1), dim3(64), 0, st, dWalk, 1u, *dSlots, dCount);
+        ENCCHK(hipGetLastError());
+        ENCCHK(hipMemcpyAsync(&lenCounts[0], dCount, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+    // the host pool meanwhile (dcs_host_threads, at most one thread a walk), the longest first
+    std::vector<int2> rec;                                          // the table's records, where the host walks it
+    const uint32_t firstOnHost = tb.hostWalk ? 0 : 1;
+    if (firstOnHost < nLen)
+    {
+        std::atomic<uint32_t> next{firstOnHost};
+        auto worker = [&]() {
+            for (uint32_t j = next++ ; j < nLen ; j = next++)
+            {
+                if (j == 0)
+                {
+                    rec.reserve(tb.nSlots);
+                    lenCounts[0] = rsWalk(tb, [&](uint64_t k, int64_t pos, int32_t sfi) {
+                        if (k < tb.nSlots)
+                            rec.push_back(make_int2(static_cast<int32_t>(pos), sfi));
+                    });
+                    continue;
+                }
+                RsStream s = tb;
+                s.nIn = lengths[j];
+                lenCounts[j] = rsWalk(s, [](uint64_t, int64_t, int32_t) {});
+            }
+        };
+        int nThreads = dcs_host_threads();
+        const int nWalks = static_cast<int>(nLen - firstOnHost);
+        nThreads = nThreads < 1 ? 1 : nThreads > nWalks ? nWalks : nThreads;
+        std::vector<std::thread> pool;
+        for (int t = 1 ; t < nThreads ; ++t)
+            pool.emplace_back(worker);
+        worker();
+        for (std::thread &t : pool)
+            t.join();
+    }
+    if (!rec.empty())
+        ENCCHK(hipMemcpyAsync(*dSlots, rec.data(), sizeof(int2) * rec.size(), hipMemcpyHostToDevice, st));
+    ENCCHK(hipStreamSynchronize(st));
+    for (uint32_t j = 0 ; j < nLen ; ++j)
+        if (lenCounts[j] > tb.nSlots || lenCounts[j] > lenCounts[0])
+        {
+            // a defect of this library, not of the input: a walk left the table every stream reads a prefix of
+            dcsCtxSetError(ctx, ("internal error: the resampler's walk of " + std::to_string(lengths[j]) + " samples made "
+                                 + std::to_string(lenCounts[j]) + " outputs; the table holds " + std::to_string(lenCounts[0])
+                                 + " and may hold " + std::to_string(tb.nSlots)).c_str());
+            return DCS_ERR_HIP;
+        }
+    for (uint32_t i = 0 ; i < n ; ++i)
+        counts[i] = lenCounts[std::lower_bound(lengths.begin(), lengths.end(), hs[i].nIn, std::greater<uint64_t>()) - lengths.begin()];
+    return DCS_OK;
+}
+
+// The converter on int16 PCM resident on the device (stream i = dPcm[sampleOffsets[i] .. sampleOffsets[i + 1]), offsets on
+// the host), queued on the context's stream behind whatever produces dPcm there.  It waits twice: for the counts
+// (rsOutWalks; not for a pass-through), then for the peaks and clip counts.  On DCS_OK `c` is filled; the buffers belong
+// to `held`.
+DcsStatus rsConvertPcm16(DcsCtx *ctx, const int16_t *dPcm, const uint64_t *sampleOffsets, uint32_t n, uint32_t outRate,
+                         const DcsResampleFilter &f, uint32_t flags, CacheArena &held, RsConverted16 &c)
+{
+    const hipStream_t st = dcsCtxStream(ctx);
+    std::vector<RsStream> hs(n);
+    std::vector<uint64_t> counts(n);
+    for (uint32_t i = 0 ; i < n ; ++i)
+    {
+        hs[i] = rsOutStreamOf(sampleOffsets[i + 1] - sampleOffsets[i], outRate, f, flags);
+        hs[i].inOff = sampleOffsets[i];
+        counts[i] = hs[i].nIn;
+    }
+    ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
+    int2 *dSlots = nullptr;
+    if (!hs[0].passThrough)
+        ENCTRY(rsOutWalks(ctx, hs, held, &dSlots, counts));
+    c.offsets.assign(static_cast<size_t>(n) + 1, 0);
+    uint64_t maxCount = 0;
+    for (uint32_t i = 0 ; i < n ; ++i)
+    {
+        hs[i].outOff = c.offsets[i];
+        c.offsets[i + 1] = c.offsets[i] + counts[i];
+        maxCount = counts[i] > maxCount ? counts[i] : maxCount;
+    }
+    float *dCoeffs;
+    uint64_t *dCounts;
+    RsStream *dStr;
+    uint32_t *dPeak;
+    unsigned long long *dClipped;
+    int16_t *dOut;
+    ENCCHK(held.alloc(&dCoeffs, f.nCoeffs));
+    ENCCHK(held.alloc(&dCounts, n));
+    ENCCHK(held.alloc(&dStr, n));
+    ENCCHK(held.alloc(&dPeak, n));
+    ENCCHK(held.alloc(&dClipped, n));
+    ENCCHK(held.alloc(&dOut, c.offsets[n] ? c.offsets[n] : 1));
+    ENCCHK(hipMemcpyAsync(dCoeffs, f.coeffs, sizeof(float) * f.nCoeffs, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dCounts, counts.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(dPeak, 0, sizeof(uint32_t) * n, st));
+    ENCCHK(hipMemsetAsync(dClipped, 0, sizeof(unsigned long long) * n, st));
+    // about 4 096 blocks in all, as the float side
+    const dim3 grid = streamGrid(n, maxCount, 4096, 0);
+    if (f.nCoeffs <= kRsLdsMaxCoeffs)
+        hipLaunchKernelGGL((rsConvolveKernel<true, int16_t>), grid, dim3(256), sizeof(float) * f.nCoeffs, st, dCoeffs, f.nCoeffs,
+                           f.increment, dStr, n, dCounts, dSlots, dPcm, dOut, dPeak, dClipped);
+    else
+        hipLaunchKernelGGL((rsConvolveKernel<false, int16_t>), grid, dim3(256), 0, st, dCoeffs, f.nCoeffs, f.increment, dStr, n,
+                           dCounts, dSlots, dPcm, dOut, dPeak, dClipped);
+    ENCCHK(hipGetLastError());
+    std::vector<uint32_t> peak(n);
+    std::vector<unsigned long long> clipped(n);
+    ENCCHK(hipMemcpyAsync(peak.data(), dPeak, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipMemcpyAsync(clipped.data(), dClipped, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipStreamSynchronize(st));
+    c.info.assign(n, DcsRateInfo{});
+    for (uint32_t i = 0 ; i < n ; ++i)
+    {
+        c.info[i].nIn = hs[i].nIn;
+        c.info[i].nOut = counts[i];
+        c.info[i].nClipped = clipped[i];
+        memcpy(&c.info[i].peak, &peak[i], sizeof(float));
+    }
+    c.d = dOut;
+    return DCS_OK;
+}
+
+}  // namespace
+
+// The converter on a decode batch's PCM where it lies (dcs_decode_streams_at, dcs_decode_rate.hip.h) and the body of
+// dcs_resample_out_streams: convert, fill outOffsets and info, then bring the samples down if they fit.  The PCM has to
+// stay until this returns.
+DcsStatus dcsRateFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint64_t *sampleOffsets, uint32_t n, uint32_t outRate,
+                            const DcsResampleFilter *filter, uint32_t flags, int16_t *out, size_t outCapSamples, uint64_t *outOffsets,
+                            DcsRateInfo *info)
+{
+    return encGuard([&]() -> DcsStatus {
+        if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr)
+            return DCS_ERR_INVALID_ARG;
+        DcsResampleFilter f;
+        std::string why;
+        const DcsStatus status = rsOutCheck(n, sampleOffsets, outRate, filter, flags, f, why);
+        if (status != DCS_OK)
+        {
+            dcsCtxSetError(ctx, why.c_str());
+            return status;
+        }
+        outOffsets[0] = 0;
+        if (n == 0)
+            return DCS_OK;
+        // (DCS_RATE_TRACE: where a call's time goes, on stderr; the first figure includes the wait for whatever made dPcm)
+        static const bool trace = getenv("DCS_RATE_TRACE") != nullptr;
+        const auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        const double t0 = trace ? now() : 0;
+        CacheArena held(ctx);
+        RsConverted16 c;
+        ENCTRY(rsConvertPcm16(ctx, dPcm, sampleOffsets, n, outRate, f, flags, held, c));
+        memcpy(outOffsets, c.offsets.data(), sizeof(uint64_t) * c.offsets.size());
+        if (info != nullptr)
+            memcpy(info, c.info.data(), sizeof(DcsRateInfo) * n);
+        if (out == nullptr || outCapSamples < c.offsets[n])
+            return DCS_ERR_CAPACITY;
+        const double t1 = trace ? now() : 0;
+        ENCCHK(hipMemcpyAsync(out, c.d, sizeof(int16_t) * c.offsets[n], hipMemcpyDeviceToHost, held.stream()));
+        ENCCHK(hipStreamSynchronize(held.stream()));
+        if (trace)
+            fprintf(stderr, "rate convert: walks, convolution and waits %.3f ms, download %.3f ms (%llu bytes)\n", t1 - t0, now() - t1,
+                    static_cast<unsigned long long>(sizeof(int16_t) * c.offsets[n]));
+        return DCS_OK;
+    });
+}
+
+// the output-rate entry points' argument check on its own, for a caller that has device work of its own to do first
+// (sampleOffsets null: the rate, the table and the flags alone)
+DcsStatus dcsRateCheck(DcsCtx *ctx, const uint64_t *sampleOffsets, uint32_t n, uint32_t outRate, const DcsResampleFilter *filter,
+                       uint32_t flags)
+{
+    return encGuard([&]() -> DcsStatus {
+        DcsResampleFilter f;
+        std::string why;
+        const DcsStatus status = rsOutCheck(n, sampleOffsets, outRate, filter, flags, f, why);
+        if (status != DCS_OK)
+            dcsCtxSetError(ctx, why.c_str());
+        return status;
+    });
+}
+
+extern "C" DcsStatus dcs_resample_out_count(uint64_t nSamples, uint32_t outRate, const DcsResampleFilter *filter, uint32_t flags,
+                                            uint64_t *countOut)
+{
+    if (countOut == nullptr)
+        return DCS_ERR_INVALID_ARG;
+    return encGuard([&] {
+        const uint64_t offs[2] = { 0, nSamples };
+        DcsResampleFilter f;
+        std::string why;
+        const DcsStatus st = rsOutCheck(1, offs, outRate, filter, flags, f, why);
+        if (st == DCS_OK)
+            *countOut = rsWalk(rsOutStreamOf(nSamples, outRate, f, flags), [](uint64_t, int64_t, int32_t) {});
+        return st;
+    });
+}
+
+// host only, for tests: the walk records (pos, start_filter_index) of a stream of nSamples at outRate, at most cap of them
+// into pos[] and sfi[]; *countOut = the walk's count
+extern "C" DcsStatus dcs_resample_out_walk(uint64_t nSamples, uint32_t outRate, const DcsResampleFilter *filter, uint32_t flags,
+                                           int64_t *pos, int32_t *sfi, uint64_t cap, uint64_t *countOut)
+{
+    if (countOut == nullptr || (cap != 0 && (pos == nullptr || sfi == nullptr)))
+        return DCS_ERR_INVALID_ARG;
+    return encGuard([&] {
+        const uint64_t offs[2] = { 0, nSamples };
+        DcsResampleFilter f;
+        std::string why;
+        const DcsStatus st = rsOutCheck(1, offs, outRate, filter, flags, f, why);
+        if (st == DCS_OK)
+            *countOut = rsWalk(rsOutStreamOf(nSamples, outRate, f, flags), [&](uint64_t k, int64_t p, int32_t s) {
+                if (k < cap)
+                {
+                    pos[k] = p;
+                    sfi[k] = s;
+                }
+            });
+        return st;
+    });
+}
+
+extern "C" DcsStatus dcs_resample_out_streams(DcsCtx *ctx, const int16_t *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                              uint32_t outRate, const DcsResampleFilter *filter, uint32_t flags, int16_t *out,
+                                              size_t outCapSamples, uint64_t *outOffsets, DcsRateInfo *info)
+{
+    return encGuard([&]() -> DcsStatus {
+        if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
+            return DCS_ERR_INVALID_ARG;
+        DcsResampleFilter f;
+        std::string why;
+        const DcsStatus status = rsOutCheck(nStreams, sampleOffsets, outRate, filter, flags, f, why);
+        if (status != DCS_OK)
+        {
+            dcsCtxSetError(ctx, why.c_str());
+            return status;
+        }
+        if (nStreams == 0)
+        {
+            outOffsets[0] = 0;
+            return DCS_OK;
+        }
+        // the streams as they lie in the caller's array, gaps between them included
+        const uint64_t lo = sampleOffsets[0], hi = sampleOffsets[nStreams];
+        std::vector<uint64_t> offs(static_cast<size_t>(nStreams) + 1);
+        for (uint32_t k = 0 ; k <= nStreams ; ++k)
+            offs[k] = sampleOffsets[k] - lo;
+        ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
+        CacheArena held(ctx);
+        int16_t *dPcm = nullptr;
+        ENCCHK(held.alloc(&dPcm, hi - lo));
+        ENCCHK(hipMemcpyAsync(dPcm, pcm + lo, sizeof(int16_t) * (hi - lo), hipMemcpyHostToDevice, held.stream()));
+        return dcsRateFromDevice(ctx, dPcm, offs.data(), nStreams, outRate, filter, flags, out, outCapSamples, outOffsets, info);
     });
 }

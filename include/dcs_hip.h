@@ -50,7 +50,9 @@ extern "C" {
                                           writing FLAC (DcsFlacWriteInfo, DCS_FLAC_MD5, DCS_FLAC_SEQUENCE, dcs_flac_write_bound,
                                           dcs_flac_write_check, dcs_flac_write_streams, dcs_decode_streams_flac); FLAC out of the
                                           pipeline (DCS_PIPE_FLAC, DCS_PIPE_FLAC_MD5, DcsPipelineFlacResult,
-                                          dcs_pipeline_collect_flac) */
+                                          dcs_pipeline_collect_flac); decoding at an output rate (DcsRateInfo,
+                                          DCS_OUT_SEQUENCE, dcs_resample_out_count, dcs_resample_out_walk,
+                                          dcs_resample_out_streams, dcs_decode_streams_at) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -929,6 +931,51 @@ DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const uint64_t *s
                                 const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
                                 uint32_t flags, const DcsEncodeParams *params, uint8_t *out, size_t outCap,
                                 uint64_t *outOffsets, DcsEncodeInfo *info);
+
+/* ------------------------------------------------------------------------------------------------
+ * Decoding at an output rate (INTEGRATION.md "Decoding at an output rate"): int16 PCM at the DCS rate of 31 250 Hz -> int16
+ * PCM at outRate, 4 000 .. 65 535 Hz, one rate per call.  The converter is the one above run the other way, at the ratio
+ * (double)outRate / 31250.0 with the encoder's call pattern (16 samples per src_process call, a 512-float output buffer, one
+ * zero-length end-of-input call), between libsamplerate's own conversions: a sample s enters as (float)(s / 32768.0)
+ * (src_short_to_float_array) and an output y leaves as src_float_to_short_array makes it: with v = (double)y * 2^31,
+ * v >= 2147483647.0 gives 32767, v <= -2147483648.0 gives -32768 (the two are counted, DcsRateInfo.nClipped), anything else
+ * (int16)(lrint(v) >> 16) -- an arithmetic shift, so it FLOORS: that is libsamplerate's rounding, kept as it is.
+ * outRate == 31250 returns the samples untouched unless DCS_RESAMPLE_AT_UNITY asks for the converter at ratio 1.
+ * filter NULL = the library's table.  Capacity protocol: outOffsets (nStreams + 1, in samples) and info (optional, nStreams)
+ * are filled once the counts are known; DCS_ERR_CAPACITY means outCapSamples < outOffsets[nStreams] and nothing was written;
+ * a second call with that capacity succeeds.  DCS_ERR_INVALID_ARG, before any device work and named in dcs_last_error: a
+ * rate outside 4 000 .. 65 535, an empty stream (or one of 2^31 samples or more), an invalid table, unknown flags.
+ */
+#define DCS_OUT_SEQUENCE 2u            /* dcs_decode_streams_at only: decode as dcs_decode_stream_sequence does               */
+typedef struct DcsRateInfo             /* one per stream */
+{
+    uint64_t nIn, nOut;                /* samples at 31 250 Hz in, samples at outRate out                                  */
+    uint64_t nClipped;                 /* outputs the conversion to int16 clamped to 32767 or -32768                       */
+    float    peak;                     /* the largest |y| of the converter's float output (a pass-through: of s / 32768)   */
+    uint32_t reserved;
+} DcsRateInfo;
+/* host only: the exact number of samples at outRate that nSamples samples at 31 250 Hz convert to. */
+DcsStatus dcs_resample_out_count(uint64_t nSamples, uint32_t outRate, const DcsResampleFilter *filter, uint32_t flags,
+                                 uint64_t *countOut);
+/* host only, a diagnostic: the converter's walk of such a stream, output k's integer input position and start_filter_index
+ * into pos[k] and sfi[k] for k < cap; *countOut = the count.  Output k's record depends on k and the ratio alone: the
+ * records of a stream are a prefix of a longer one's, which is why a call keeps one record table on the device. */
+DcsStatus dcs_resample_out_walk(uint64_t nSamples, uint32_t outRate, const DcsResampleFilter *filter, uint32_t flags,
+                                int64_t *pos, int32_t *sfi, uint64_t cap, uint64_t *countOut);
+/* The converter alone, on the GPU: stream i = pcm[sampleOffsets[i] .. sampleOffsets[i+1]) (host memory, any length >= 1);
+ * its outputs land at out + outOffsets[i].  flags: DCS_RESAMPLE_AT_UNITY or 0. */
+DcsStatus dcs_resample_out_streams(DcsCtx *ctx, const int16_t *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                   uint32_t outRate, const DcsResampleFilter *filter, uint32_t flags, int16_t *out,
+                                   size_t outCapSamples, uint64_t *outOffsets, DcsRateInfo *info);
+/* dcs_decode_streams (with DCS_OUT_SEQUENCE: dcs_decode_stream_sequence, and its argument rules) whose PCM is converted
+ * where it lies in device memory: stream k's (nFrames + extraFrames) x 240 samples become one stream at outRate at
+ * out + outOffsets[k].  Only the converted samples and the per-frame error words (errOut, optional, one per decoded frame
+ * as dcs_decode_streams gives them) come down.  Decode errors are reported as dcs_decode_streams reports them; a stream
+ * with a fatal frame is converted all the same: it is the PCM the decoder produced.  flags: DCS_RESAMPLE_AT_UNITY,
+ * DCS_OUT_SEQUENCE. */
+DcsStatus dcs_decode_streams_at(DcsCtx *ctx, const DcsStreamRef *streams, uint32_t nStreams, uint32_t extraFrames,
+                                uint32_t outRate, const DcsResampleFilter *filter, uint32_t flags, int16_t *out,
+                                size_t outCapSamples, uint64_t *outOffsets, DcsRateInfo *info, uint32_t *errOut);
 
 /* ------------------------------------------------------------------------------------------------
  * Encoding files: DCSEncoder::EncodeFile (DCSEncodeFile.cpp:29-105) on files held in memory.  A "DCSa" container (IsDCSFile's
