@@ -87,10 +87,14 @@ def utf8(v):
 
 # ------------------------------------------------------------------------------------------------------------ subframes
 
-def S(t, order=0, prec=0, shift=0, method=0, po=0, k=3, wasted=0, amp=None, values=None):
+def S(t, order=0, prec=0, shift=0, method=0, po=0, k=3, wasted=0, amp=None, values=None, exact=None):
     """a subframe recipe: t in const / verbatim / fixed / lpc; k: one Rice parameter for every partition or a list with one
-    entry per partition, an entry being a parameter or ('esc', raw width); values: the samples themselves (verbatim / const)"""
-    return dict(t=t, order=order, prec=prec, shift=shift, method=method, po=po, k=k, wasted=wasted, amp=amp, values=values)
+    entry per partition, an entry being a parameter or ('esc', raw width); values: the samples themselves (verbatim / const);
+    exact: (warm-ups, LPC coefficients, residuals) of a fixed or LPC subframe as the caller chose them, in the subframe's own
+    depth (after the wasted bits are taken off) -- residuals of any size, nothing drawn, nothing capped at 6 << k; the writer
+    still runs the recurrence and asserts that every sample stays inside its depth"""
+    return dict(t=t, order=order, prec=prec, shift=shift, method=method, po=po, k=k, wasted=wasted, amp=amp, values=values,
+                exact=exact)
 
 
 def _coefs(rng, order, prec, shift):
@@ -143,7 +147,7 @@ def make_subframe(rng, bs, bits, spec):
     ks = spec["k"] if isinstance(spec["k"], list) else [spec["k"]] * len(counts)
     assert len(ks) == len(counts)
     amp0 = spec["amp"] if spec["amp"] is not None else max(1, hi >> 6)
-    for attempt in range(40):
+    for attempt in range(40 if spec.get("exact") is None else 0):
         amp = max(1, amp0 >> attempt)
         if t == "lpc":
             prec, shift = spec["prec"], spec["shift"]
@@ -177,7 +181,22 @@ def make_subframe(rng, bs, bits, spec):
         if ok:
             break
     else:
-        raise AssertionError("no stable signal for %r" % (spec,))
+        if spec.get("exact") is None:
+            raise AssertionError("no stable signal for %r" % (spec,))
+        prec, shift = (spec["prec"], spec["shift"]) if t == "lpc" else (0, 0)
+        warm, coefs, res = ([int(x) for x in part] for part in spec["exact"])
+        coefs = coefs if t == "lpc" else FIXED_TAPS[order]
+        assert len(warm) == len(coefs) == order and len(res) == sum(counts)
+        assert t != "lpc" or all(-(1 << (prec - 1)) <= c < 1 << (prec - 1) for c in coefs)
+        i = 0
+        for c, k in zip(counts, ks):                       # (an escape's residuals must fit its raw width)
+            if isinstance(k, tuple):
+                assert all(-(1 << k[1]) <= 2 * r < 1 << k[1] for r in res[i:i + c]), (k, res[i:i + c])
+            i += c
+        data = list(warm)
+        for r in res:
+            data.append(r + (sum(coefs[j] * data[-1 - j] for j in range(order)) >> shift))
+        assert all(lo <= x <= hi for x in data), "an exact recipe leaves its depth"
 
     def write(bw):
         code = 8 + order if t == "fixed" else 32 + order - 1

@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 import wav_cases as W                   # noqa: E402
+from oracle import flacref                      # noqa: E402  (libnyquist's build: one recipe)
 import make_resample_golden as MR       # noqa: E402  (stand_in: the best-quality slot)
 
 HERE = os.path.join(ROOT, "tests", "golden")
@@ -86,11 +87,7 @@ def main():
     cases = W.cases() + [("long_180s_s16_stereo_44100", W.long_wav())] + W.float_edge_cases()
     meta, arrays = [], {}
     with tempfile.TemporaryDirectory() as tmp:
-        nqb = os.path.join(tmp, "nq")
-        subprocess.check_call(["cmake", "-G", "Ninja", "-S", NQ, "-B", nqb, "-DLIBNYQUIST_BUILD_EXAMPLE=OFF",
-                               "-DCMAKE_BUILD_TYPE=Release"], stdout=subprocess.DEVNULL)
-        subprocess.check_call(["ninja", "-C", nqb, "-j16"], stdout=subprocess.DEVNULL)
-        nq_lib = os.path.join(nqb, "lib", "liblibnyquist.a")
+        nq_lib = flacref.build_libnyquist(NQ, os.path.join(tmp, "nq"))
         plain = build(tmp, nq_lib, coeffs, inc)
         san = build(tmp, nq_lib, coeffs, inc, extra=["-fsanitize=bounds,shift,float-cast-overflow"])
         for name, data in cases:

@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 import flac_cases as F                          # noqa: E402
 import make_encode_file_golden as MG            # noqa: E402
+from oracle import flacref                      # noqa: E402  (libnyquist's build: one recipe)
 
 HERE = MG.HERE
 
@@ -37,11 +38,7 @@ def main():
     cases = [(n, b, "valid") for n, b in F.cases()] + [(c[0], c[1], "refused") for c in F.refused_cases()]
     meta, arrays, failed = [], {}, []
     with tempfile.TemporaryDirectory() as tmp:
-        nqb = os.path.join(tmp, "nq")
-        subprocess.check_call(["cmake", "-G", "Ninja", "-S", MG.NQ, "-B", nqb, "-DLIBNYQUIST_BUILD_EXAMPLE=OFF",
-                               "-DCMAKE_BUILD_TYPE=Release"], stdout=subprocess.DEVNULL)
-        subprocess.check_call(["ninja", "-C", nqb, "-j16"], stdout=subprocess.DEVNULL)
-        nq_lib = os.path.join(nqb, "lib", "liblibnyquist.a")
+        nq_lib = flacref.build_libnyquist(MG.NQ, os.path.join(tmp, "nq"))
         plain = MG.build(tmp, nq_lib, coeffs, inc)
         san = MG.build(tmp, nq_lib, coeffs, inc, extra=["-fsanitize=bounds,shift,float-cast-overflow"])
         for name, data, kind in cases:

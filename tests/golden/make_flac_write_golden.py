@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import flac_write_cases as C                    # noqa: E402
 import flac_write_ref as R                      # noqa: E402
 import make_encode_file_golden as MG            # noqa: E402
+from oracle import flacref                      # noqa: E402  (libnyquist's build: one recipe)
 
 HERE = MG.HERE
 KINDS = ("nBlocks", "nConstant", "nVerbatim", "nFixed")
@@ -56,11 +57,7 @@ def entries():
 def main():
     es = entries()
     with tempfile.TemporaryDirectory() as tmp:
-        nqb = os.path.join(tmp, "nq")
-        subprocess.check_call(["cmake", "-G", "Ninja", "-S", MG.NQ, "-B", nqb, "-DLIBNYQUIST_BUILD_EXAMPLE=OFF",
-                               "-DCMAKE_BUILD_TYPE=Release"], stdout=subprocess.DEVNULL)
-        subprocess.check_call(["ninja", "-C", nqb, "-j16"], stdout=subprocess.DEVNULL)
-        nq_lib = os.path.join(nqb, "lib", "liblibnyquist.a")
+        nq_lib = flacref.build_libnyquist(MG.NQ, os.path.join(tmp, "nq"))
         exe = os.path.join(tmp, "fw_driver")
         subprocess.check_call(["g++", "-O2", "-w", "-x", "c", os.path.join(HERE, "flac_write", "fw_driver.c"), "-x", "none",
                                "-I" + os.path.join(MG.NQ, "third_party"), "-o", exe, nq_lib, "-lpthread", "-lm"])
