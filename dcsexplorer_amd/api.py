@@ -203,6 +203,8 @@ _LIB = None
 ABI_VERSION = 9                 # include/dcs_hip.h DCS_ABI_VERSION these bindings are written for
 
 EXPORTS = [
+    "dcs_index_stream_mids", "dcs_index_streams_mids", "dcs_batch_create_mids", "dcs_ctx_set_even_deal", "dcs_batch_even_deal",
+    "dcs_pack_chunks_mids", "dcs_even_deal_lane",
     "dcs_abi_version", "dcs_build_id", "dcs_index_stream", "dcs_volume_multiplier", "dcs_mixing_multiplier", "dcs_frame_scale",
     "dcs_stream_params", "dcs_ctx_create", "dcs_ctx_destroy", "dcs_last_error", "dcs_device_count", "dcs_runtime_defaults", "dcs_ctx_set_batch_tails", "dcs_batch_package_bytes",
     "dcs_ctx_set_frames_per_wave", "dcs_ctx_set_tail_handoff", "dcs_ctx_set_large_list_path", "dcs_ctx_set_concurrent_batches", "dcs_ctx_set_cache_limits", "dcs_ctx_trim_cache", "dcs_ctx_cache_bytes", "dcs_plan_chunks2", "dcs_decode_batch", "dcs_batch_create", "dcs_batch_destroy", "dcs_batch_run", "dcs_batch_run_many", "dcs_pack_chunks",
@@ -323,6 +325,21 @@ def load_library():
     L.dcs_decode_batch.argtypes = [vp, vp, sz, vp, u32, vp, u32, vp, u32, vp, vp, vp]
     L.dcs_batch_create.restype = i32
     L.dcs_batch_create.argtypes = [vp, vp, sz, vp, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]
+    if hasattr(L, "dcs_batch_create_mids"):             # (DCS_HIP_LIB may name a build from before the even deal: A/B against it)
+        L.dcs_batch_create_mids.restype = i32
+        L.dcs_batch_create_mids.argtypes = [vp, vp, sz, vp, vp, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]
+        L.dcs_index_stream_mids.restype = i32
+        L.dcs_index_stream_mids.argtypes = [ctypes.c_int, vp, sz, vp, u32, ctypes.POINTER(StreamInfo), vp]
+        L.dcs_index_streams_mids.restype = i32
+        L.dcs_index_streams_mids.argtypes = [vp, u32, ctypes.c_int, vp, vp, vp, vp]
+        L.dcs_ctx_set_even_deal.restype = i32
+        L.dcs_ctx_set_even_deal.argtypes = [vp, ctypes.c_int]
+        L.dcs_batch_even_deal.restype = ctypes.c_int
+        L.dcs_batch_even_deal.argtypes = [vp]
+        L.dcs_pack_chunks_mids.restype = i32
+        L.dcs_pack_chunks_mids.argtypes = [vp, u32, vp, vp, vp, sz, ctypes.c_int, vp, sz, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.dcs_even_deal_lane.restype = None
+        L.dcs_even_deal_lane.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3
     L.dcs_batch_destroy.restype = None
     L.dcs_batch_destroy.argtypes = [vp]
     L.dcs_batch_run.restype = i32
@@ -625,6 +642,32 @@ def index_stream(os_, stream, literal=False):
     return out[:info.nValidFrames], info
 
 
+class SrcArray(np.ndarray):
+    """source descriptors with the mid records of their frames riding along (`mids`: MIDS_DTYPE [n, 16], or None), so that
+    Context.batch(blob, srcs, jobs) can hand them on.  A slice or a copy is a plain array again: the records would no longer
+    be parallel to it, and the batch keeps whole bands.  Rows edited in place are the caller's business as with any
+    descriptor; mid records that no longer fit the index records are refused when the batch is made."""
+    mids = None
+
+    def __array_finalize__(self, obj):
+        self.mids = None
+
+
+def index_stream_mids(os_, stream):
+    """dcs_index_stream_mids: (index records, StreamInfo, mid records [frames, 16] uint32) -- the middle of every 1994+ band of
+    16 or 32 samples, for the even deal of dcs_batch_create_mids"""
+    L = load_library()
+    buf = np.frombuffer(bytes(stream), dtype=np.uint8)
+    nframes = (int(buf[0]) << 8) | int(buf[1])
+    out = np.zeros(max(nframes, 1), dtype=INDEX_DTYPE)
+    mids = np.zeros((max(nframes, 1), 16), dtype=np.uint32)
+    info = StreamInfo()
+    st = L.dcs_index_stream_mids(os_, _ptr(buf), buf.size, _ptr(out), nframes, ctypes.byref(info), _ptr(mids))
+    if st != 0:
+        raise DcsError(st)
+    return out[:info.nValidFrames], info, mids[:info.nValidFrames]
+
+
 def _info_from_record(r):
     info = StreamInfo()
     ctypes.memmove(ctypes.byref(info), r.tobytes(), ctypes.sizeof(info))
@@ -640,9 +683,10 @@ def _split_records(out, infos, first):
             for k in range(len(infos))]
 
 
-def index_streams(streams, threads=0):
+def index_streams(streams, threads=0, with_mids=False):
     """dcs_index_streams: index many (os, bytes, ...) streams on `threads` host threads (0 = all).
-    Returns a list of (records, StreamInfo), one per stream, identical to index_stream on each."""
+    Returns a list of (records, StreamInfo), one per stream, identical to index_stream on each; with_mids
+    (dcs_index_streams_mids): of (records, StreamInfo, mid records) as index_stream_mids returns them."""
     L = load_library()
     streams = list(streams)
     if not streams:
@@ -657,10 +701,17 @@ def index_streams(streams, threads=0):
         refs[k].os = s[0]
     out = np.zeros(max(int(first[-1]), 1), dtype=INDEX_DTYPE)
     infos = np.zeros(len(streams), dtype=INFO_DTYPE)
-    st = L.dcs_index_streams(refs, len(streams), threads, _ptr(out), _ptr(first), _ptr(infos))
+    mids = np.zeros((out.size, 16), dtype=np.uint32) if with_mids else None
+    if with_mids:
+        st = L.dcs_index_streams_mids(refs, len(streams), threads, _ptr(out), _ptr(first), _ptr(infos), _ptr(mids))
+    else:
+        st = L.dcs_index_streams(refs, len(streams), threads, _ptr(out), _ptr(first), _ptr(infos))
     if st != 0:
         raise DcsError(st)
-    return _split_records(out, infos, first)
+    recs = _split_records(out, infos, first)
+    if with_mids:
+        return [(r, i, mids[int(first[k]):int(first[k]) + len(r)]) for k, (r, i) in enumerate(recs)]
+    return recs
 
 
 def pack_streams(streams, pad=64):
@@ -1089,12 +1140,21 @@ def build_stream_batch(streams, extra_frames=0, pad=64, indexer=None):
     callable streams -> [(records, StreamInfo)] such as index_streams or Context.index_streams_gpu.
     Returns dict(blob, srcs, jobs, first_job)."""
     blob = bytearray()
-    srcs, jobs, first = [], [], []
+    srcs, jobs, first, mids = [], [], [], []
     njobs = 0
     streams = list(streams)
-    indexed = indexer(streams) if indexer is not None else None
+    # (the host indexers also record the middles of the 1994+ bands: they ride along with the descriptors, see SrcArray)
+    with_mids = (indexer is None or indexer is index_streams) and hasattr(load_library(), "dcs_index_stream_mids")
+    if indexer is index_streams and with_mids:
+        indexed = index_streams(streams, with_mids=True)
+    else:
+        indexed = indexer(streams) if indexer is not None else None
     for k, (os_, data, volume, level) in enumerate(streams):
-        idx, info = indexed[k] if indexed is not None else index_stream(os_, data)
+        if with_mids:
+            idx, info, m = indexed[k] if indexed is not None else index_stream_mids(os_, data)
+            mids.append(m)
+        else:
+            idx, info = indexed[k] if indexed is not None else index_stream(os_, data)
         nframes = info.nFrames
         mm, vs = stream_params(os_, volume, level, nframes)
         while len(blob) & 3:
@@ -1124,8 +1184,13 @@ def build_stream_batch(streams, extra_frames=0, pad=64, indexer=None):
         first.append(njobs)
         njobs += total
     first.append(njobs)
-    return dict(blob=bytes(blob), srcs=np.concatenate(srcs) if srcs else np.zeros(0, SRC_DTYPE),
-                jobs=np.concatenate(jobs), first_job=np.array(first, dtype=np.int64))
+    all_srcs = (np.concatenate(srcs) if srcs else np.zeros(0, SRC_DTYPE)).view(SrcArray)
+    if with_mids and mids:
+        all_srcs.mids = np.ascontiguousarray(np.concatenate(mids), dtype=np.uint32)
+    # (`mids` is the explicit form -- Context.batch(blob, srcs, jobs, mids=b["mids"]) --; the attribute on `srcs` serves callers
+    # that hand on the three arrays only.  Either way dcs_batch_create_mids refuses mids that do not fit the records.)
+    return dict(blob=bytes(blob), srcs=all_srcs, jobs=np.concatenate(jobs), first_job=np.array(first, dtype=np.int64),
+                mids=all_srcs.mids)
 
 
 def plan_chunks(jobs, fpw, srcs=None, handoff=True):
@@ -1144,17 +1209,35 @@ def plan_chunks(jobs, fpw, srcs=None, handoff=True):
     return out.reshape(n.value, fpw)
 
 
-def pack_chunks(blob, srcs, jobs, fpw):
-    """dcs_pack_chunks -> uint8 array [nChunks, packageBytes] (what a batch uploads for unpack round 0)"""
+def pack_chunks(blob, srcs, jobs, fpw, mids=None):
+    """dcs_pack_chunks -> uint8 array [nChunks, packageBytes] (what a batch uploads for unpack round 0); mids: the sources' mid
+    records (index_stream_mids), for the packages of the even deal (dcs_pack_chunks_mids)"""
     L = load_library()
     blob_a = np.frombuffer(bytes(blob), dtype=np.uint8)
     srcs = np.ascontiguousarray(srcs, dtype=SRC_DTYPE)
     jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
     n, pb = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    _check(L.dcs_pack_chunks(_ptr(jobs), jobs.size, _ptr(srcs), _ptr(blob_a), blob_a.size, fpw, None, 0, ctypes.byref(n), ctypes.byref(pb)))
+    if mids is None:
+        def call(out, cap):
+            return L.dcs_pack_chunks(_ptr(jobs), jobs.size, _ptr(srcs), _ptr(blob_a), blob_a.size, fpw, out, cap, ctypes.byref(n), ctypes.byref(pb))
+    else:
+        mids = np.ascontiguousarray(mids, dtype=np.uint32)
+        assert mids.shape == (srcs.size, 16)
+
+        def call(out, cap):
+            return L.dcs_pack_chunks_mids(_ptr(jobs), jobs.size, _ptr(srcs), _ptr(mids), _ptr(blob_a), blob_a.size, fpw, out, cap,
+                                          ctypes.byref(n), ctypes.byref(pb))
+    _check(call(None, 0))
     out = np.zeros((n.value, pb.value), dtype=np.uint8)
-    _check(L.dcs_pack_chunks(_ptr(jobs), jobs.size, _ptr(srcs), _ptr(blob_a), blob_a.size, fpw, _ptr(out), out.size, ctypes.byref(n), ctypes.byref(pb)))
+    _check(call(_ptr(out), out.size))
     return out
+
+
+def even_deal_lane(n_bands, q):
+    """dcs_even_deal_lane -> (first unit, units) of lane q of a frame of n_bands header bands, and the samples the deal saves"""
+    first, count, gain = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    load_library().dcs_even_deal_lane(n_bands, q, ctypes.byref(first), ctypes.byref(count), ctypes.byref(gain))
+    return first.value, count.value, gain.value
 
 
 def device_count():
@@ -1275,6 +1358,11 @@ class Context:
         of 8 frames per wavefront that make more than one and at most two generations of the chip).  Read at every launch."""
         _check(self.L.dcs_ctx_set_chunks_per_wave(self.h, chunks), self.h)
 
+    def set_even_deal(self, mode):
+        """The deal of 1994+ frames to their unpack lanes in batches created afterwards from descriptors with mid records:
+        0 whole bands, 1 units of 8 samples wherever the batch allows it, -1 (default) units where some frame gains."""
+        _check(self.L.dcs_ctx_set_even_deal(self.h, mode), self.h)
+
     def set_frames_per_chunk(self, frames):
         _check(self.L.dcs_ctx_set_frames_per_chunk(self.h, frames), self.h)
 
@@ -1331,8 +1419,9 @@ class Context:
         pcm, err = self.decode_batch(b["blob"], b["srcs"], b["jobs"])
         return pcm, err, b["first_job"]
 
-    def batch(self, blob, srcs, jobs, tails_in=None):
-        return Batch(self, blob, srcs, jobs, tails_in)
+    def batch(self, blob, srcs, jobs, tails_in=None, mids=None):
+        """mids: the sources' mid records (build_stream_batch's "mids"; default: what `srcs` carries, if anything)"""
+        return Batch(self, blob, srcs, jobs, tails_in, mids=mids)
 
     def encode_streams(self, pcm_list, fmt=None, **params):
         """dcs_encode_streams: PCM at 31 250 Hz (float32 in [-1, 1], or int16, which is divided by 32768) -> 1994+ streams,
@@ -1779,16 +1868,23 @@ class Context:
 class Batch:
     """DcsBatch: a job list resident in HBM"""
 
-    def __init__(self, ctx, blob, srcs, jobs, tails_in=None):
+    def __init__(self, ctx, blob, srcs, jobs, tails_in=None, mids=None):
         self.ctx = ctx
         self.L = ctx.L
         blob_a = np.frombuffer(bytes(blob), dtype=np.uint8)
+        mids = getattr(srcs, "mids", None) if mids is None else mids
         srcs = np.ascontiguousarray(srcs, dtype=SRC_DTYPE)
         jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
         tin = None if tails_in is None else np.ascontiguousarray(tails_in, dtype=np.int16)
         h = ctypes.c_void_p()
-        _check(self.L.dcs_batch_create(ctx.h, _ptr(blob_a), blob_a.size, _ptr(srcs), srcs.size, _ptr(jobs), jobs.size,
-                                       _ptr(tin), 0 if tin is None else tin.shape[0], ctypes.byref(h)), ctx.h)
+        if mids is not None and hasattr(self.L, "dcs_batch_create_mids"):
+            mids = np.ascontiguousarray(mids, dtype=np.uint32)
+            assert mids.shape == (srcs.size, 16)
+            _check(self.L.dcs_batch_create_mids(ctx.h, _ptr(blob_a), blob_a.size, _ptr(srcs), _ptr(mids), srcs.size, _ptr(jobs), jobs.size,
+                                                _ptr(tin), 0 if tin is None else tin.shape[0], ctypes.byref(h)), ctx.h)
+        else:
+            _check(self.L.dcs_batch_create(ctx.h, _ptr(blob_a), blob_a.size, _ptr(srcs), srcs.size, _ptr(jobs), jobs.size,
+                                           _ptr(tin), 0 if tin is None else tin.shape[0], ctypes.byref(h)), ctx.h)
         self.h = h
         self.n_jobs = jobs.size
         ctx._batches.add(self)
@@ -1853,6 +1949,11 @@ class Batch:
     @property
     def frames_per_wave(self):
         return int(self.L.dcs_batch_frames_per_wave(self.h))
+
+    @property
+    def even_deal(self):
+        """the batch's packages deal 1994+ frames in units of 8 samples (Context.set_even_deal)"""
+        return bool(self.L.dcs_batch_even_deal(self.h))
 
     @property
     def chunks_per_wave(self):

@@ -142,6 +142,9 @@ struct DcsKernelArgs
 // dcs_kernels.hip.h); bits 8..15 then hold CUs / 8 (CUs x 4 workgroups are resident at once)
 #define DCS_BATCH_PACED 4u
 #define DCS_BATCH_CUS8_SHIFT 8
+// the packages deal 1994+ frames to their eight unpack lanes in units of 8 samples (dcs_package.h: the even deal), and the symbol
+// loop runs in rounds of 8 samples (8 frames per wavefront, first source)
+#define DCS_BATCH_EVEN_DEAL 8u
 #define DCS_BATCH_IMG_SHIFT 16          // bits 16..31: the packages' layout word (image dwords | DCS_PKG_SPLIT4; dcsPkgStride)
 #define DCS_BATCH_IMG_MASK  0xFFFFu
 
@@ -225,6 +228,9 @@ DcsPlan dcsPlanJobs(const DcsFrameJob *jobs, uint32_t nJobs, const DcsPlanSrc *s
 void dcsShuffleChunks(std::vector<DcsSlot> &slots, uint32_t nChunks, int fpw, uint32_t seed);
 #define DCS_MI355X_WAVE_PLACES 4096u    // (the diagnostic entries assume an MI355X)
 // packer: out = nChunks x dcsPkgStride(fpw, layout) bytes (the chunk packages described above); layout = image dwords | DCS_PKG_SPLIT4
+// mids: the sources' mid records, parallel to srcs, for a batch that takes the even deal (DCS_BATCH_EVEN_DEAL); null: whole bands
 void dcsBuildPackages(const DcsSlot *slots, uint32_t nChunks, int fpw, const DcsSrcDesc *srcs,
-                      const uint8_t *blob, size_t blobLen, uint8_t *out, uint32_t layout);
+                      const uint8_t *blob, size_t blobLen, uint8_t *out, uint32_t layout, const DcsFrameMids *mids = nullptr);
+// what the even deal saves the fullest unpack lane of a frame of nb header bands, in samples, against whole bands (8 lanes)
+int dcsEvenDealGain(int nb);
 #endif

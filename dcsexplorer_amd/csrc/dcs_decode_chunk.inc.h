@@ -248,6 +248,9 @@
             Q.subType = (format == DCS_FMT_93B_T1) ? 0 : 2;
             Q.reuse = false; Q.first = true;
             Q.midEnd = Q.midStart = Q.midStraddle = false;
+            Q.endIdx = 0;
+            // (the batch's packages carry the even deal, dcs_package.h: first source, eight lanes per frame)
+            constexpr bool evenDeal = R0 && SUB == 8 && EVEN;
             if (serial)
                 Q.nb = (q == 0) ? nBands : 0;
             else
@@ -274,6 +277,20 @@
                         Q.midEnd = q == SUB - 2 && nextMid;
                         if (Q.midEnd)
                             Q.nb = 16 - myBase;
+                    }
+                    if constexpr (evenDeal)
+                    {
+                        // the even deal: a lane may start with the second half of a band (its record says so), and then the lane
+                        // before it stops there -- at the output index the record names, a sample later behind a straddling code
+                        const bool mid = format >= DCS_FMT_94_T0 && !(sp.x & 0x8000u) && (sp.y & (DCS_SPLIT_MID15 << 16)) != 0;
+                        const bool nextMid = __shfl(static_cast<int>(mid), lane + FPW) != 0 && q != SUB - 1;
+                        const int nextIdx = __shfl(static_cast<int>((sp.y >> 16) & 0x1FFu), lane + FPW);
+                        Q.midStart = mid;
+                        Q.midStraddle = mid && (sp.y & (DCS_MID15_STRADDLE << 16)) != 0;
+                        Q.midEnd = nextMid;
+                        Q.endIdx = nextIdx;
+                        if (nextMid)
+                            Q.nb = min(nextBase + 1, nbEnd) - myBase;
                     }
                 }
                 else
@@ -327,7 +344,7 @@
                 const uint32_t planAt = (R0 && bandPlanInLds(FPW))
                     ? static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsBytePtr)L.plan())) + static_cast<uint32_t>(Q.bandBase * FPW + s) * kPlanRecBytes
                     : 0u;
-                err |= unpack94<R0, BR94, SUB>(T, row, br, Q, format, mixMul, is94, stamp, planAt);
+                err |= unpack94<R0, BR94, SUB, evenDeal>(T, row, br, Q, format, mixMul, is94, stamp, planAt);
             }
             BR93 br;
             br.init(brAt, brBit);

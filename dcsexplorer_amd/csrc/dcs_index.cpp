@@ -182,6 +182,85 @@ extern "C" DcsStatus dcs_index_stream(DcsOsVersion os, const uint8_t *stream, si
     return sink.overflow ? DCS_ERR_CAPACITY : DCS_OK;
 }
 
+// The mid records of a 1994+ frame (DcsFrameMids, dcs_hip.h): from the frame's record, which says where every band starts,
+// each band of 16 or 32 samples is walked again up to its middle -- the first code boundary with at least half of its samples
+// done, the rule of dcsPutMid15 (dcs_scan.h), whose record of band 15 this walk reproduces.  The walker itself, which the device
+// index kernel shares, is left as it is; the second look at half of the sample codes is host time of the batch's preparation.
+static void frameMids94(const uint8_t *stream, size_t len, const DcsStreamInfo &si, const DcsFrameIndex &fi, DcsFrameMids &out)
+{
+    out = DcsFrameMids{};
+    if (si.format < DCS_FMT_94_T0 || fi.flags != 0)
+        return;                                         // (a frame with an error flag is never split)
+    const DcsLdsTables &T = dcsTables().lds;
+    const bool type1 = si.format != DCS_FMT_94_T0;
+    const int nBands = fi.nBands < 16 ? fi.nBands : 16;
+    for (int band = 2 ; band < nBands ; ++band)
+    {
+        const DcsSplit &sp = fi.split[band - 1];
+        const int hb = si.header[band] & 0x7F;
+        int count = band == 15 ? 32 : 16, inc = 1;
+        if (hb & 0x40) { count /= 2; inc = 2; }
+        const int first = count - count / 2;            // samples in front of the middle
+        int outIdx = sp.state & 0x1FF;
+        uint32_t bits = sp.bitDelta;
+        bool straddle = false;
+        int code = fi.bandType[band];
+        if (code == 0)
+            outIdx += first;                            // (a band without a code moves on by the halved count, :1886)
+        else
+        {
+            if (type1)
+                code = code > 15 ? 17 : T.xlat94[(band < 3 ? 0 : band < 6 ? 16 : 32) + code] & 0xFF;
+            if (code == 0 || code > 16)
+            {
+                out = DcsFrameMids{};                   // (cannot happen in a frame without an error flag)
+                return;
+            }
+            if (code <= 6)
+            {
+                const int maxBits = T.cbInfo[code] & 0xF;
+                const uint16_t *book = T.cb94 + (T.cbInfo[code] >> 4);
+                WinBits r{ stream, len };
+                r.setPayload(2 + static_cast<size_t>(si.hdrLen));
+                r.skipRun(1, static_cast<int>(fi.bitOff + bits));
+                int i = count;
+                for ( ; i > count / 2 ; --i)
+                {
+                    const uint32_t e = book[r.look(maxBits)];
+                    r.consume(static_cast<int>((e >> 8) & 0x1F));
+                    if ((e >> 13) == 2 && i >= 2)
+                        --i;
+                }
+                straddle = i < count / 2;
+                bits = r.bitPos() - fi.bitOff;
+                outIdx += (count - i) * inc;
+            }
+            else
+            {
+                bits += static_cast<uint32_t>(first * code);
+                outIdx += first * inc;
+            }
+        }
+        out.mid[band] = (bits & 0xFFFFu) | (static_cast<uint32_t>((outIdx & 0x1FF) | (straddle ? DCS_MID15_STRADDLE : 0u)) << 16);
+    }
+    out.mid[0] = DCS_MIDS_VALID;
+}
+
+extern "C" DcsStatus dcs_index_stream_mids(DcsOsVersion os, const uint8_t *stream, size_t len,
+                                           DcsFrameIndex *out, uint32_t cap, DcsStreamInfo *info, DcsFrameMids *mids)
+{
+    DcsStreamInfo si;
+    const DcsStatus st = dcs_index_stream(os, stream, len, out, cap, &si);
+    if (info != nullptr)
+        *info = si;
+    if (mids == nullptr || out == nullptr || (st != DCS_OK && st != DCS_ERR_CAPACITY))
+        return st;
+    const uint32_t n = static_cast<uint32_t>(si.nValidFrames) < cap ? static_cast<uint32_t>(si.nValidFrames) : cap;
+    for (uint32_t f = 0 ; f < n ; ++f)
+        frameMids94(stream, len, si, out[f], mids[f]);
+    return st;
+}
+
 // The same walk for a caller that uses the records as they come (the sequencer's background walker, dcs_sequencer.cpp): onFrame(f,
 // record) is called for every frame, in order, on the calling thread.  Same records, same summary as dcs_index_stream.
 namespace {
@@ -456,4 +535,20 @@ extern "C" DcsStatus dcs_index_streams(const DcsStreamRef *streams, uint32_t nSt
                                        DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos)
 {
     return dcsIndexStreamsNotify(streams, nStreams, nThreads, out, firstRecord, infos, nullptr);
+}
+
+// ... with the mid records of every stream's frames as a second output (dcs_index_stream_mids), made on the thread that walked it
+extern "C" DcsStatus dcs_index_streams_mids(const DcsStreamRef *streams, uint32_t nStreams, int nThreads,
+                                            DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos, DcsFrameMids *mids)
+{
+    if (mids == nullptr)
+        return dcsIndexStreamsNotify(streams, nStreams, nThreads, out, firstRecord, infos, nullptr);
+    const std::function<void(uint32_t)> done = [&](uint32_t k) {
+        const DcsStreamRef &sr = streams[k];
+        if (sr.data == nullptr || sr.len < 3 || infos[k].nFrames == 0)
+            return;
+        for (int32_t f = 0 ; f < infos[k].nValidFrames ; ++f)
+            frameMids94(sr.data, sr.len, infos[k], out[firstRecord[k] + static_cast<uint64_t>(f)], mids[firstRecord[k] + static_cast<uint64_t>(f)]);
+    };
+    return dcsIndexStreamsNotify(streams, nStreams, nThreads, out, firstRecord, infos, &done);
 }

@@ -312,6 +312,9 @@ struct Quarter
     // 1994+, sixteen lanes per frame: band 15 shared by two lanes (dcsMid15).  midEnd: this lane's band 15 ends at the
     // middle; midStart: it starts there, midStraddle: one sample later (a two-zeros code ran across)
     bool midEnd, midStart, midStraddle;
+    // ... and eight lanes per frame under the even deal (dcs_package.h): any band of 16 samples may be shared so.  endIdx: the
+    // tile word where the next lane of the frame starts, when that is the middle of this lane's last band (midEnd)
+    int endIdx;
 };
 
 // byte b (0..15) of four registers; explicit selects so that nothing is indexed in memory
@@ -469,7 +472,7 @@ __device__ __forceinline__ uint2 planBand94(const DcsLdsTables *T, const uint2 *
 // divergent code; the symbol loop is branch-free so that lanes with Huffman-coded bands, raw bands
 // and different codebooks all execute the same instruction stream.
 // ------------------------------------------------------------------------------------------------
-template <bool FIRST, class BR, int SUB>
+template <bool FIRST, class BR, int SUB, bool EVEN = false>
 __device__ uint32_t unpack94(const DcsLdsTables *T, uint16_t *row, BR &br, const Quarter &Q,
                              int format, uint32_t mixMul, bool has, const Stamper &stamp, uint32_t planAt = 0)
 {
@@ -490,7 +493,25 @@ __device__ uint32_t unpack94(const DcsLdsTables *T, uint16_t *row, BR &br, const
     // (a lane that starts in the middle of band 15 has sixteen tile words to go at most; one sample fewer -- one word, or
     // two in a strided band, header bit 6 -- behind a straddling code)
     const int midAdvance = 16 - (Q.midStraddle ? 1 + static_cast<int>((Q.h3 >> 30) & 1u) : 0);
-    int outIdx = min(Q.outIdx, 256 - ((SUB == 16 && Q.midStart) ? midAdvance : upTo - before));
+    // The even deal (EVEN: the kernels of batches with DCS_BATCH_EVEN_DEAL; with a plan only): a lane that starts in the middle of its first
+    // band has that band's span less what the lane before it took -- half of it, and one sample more behind a straddling code --
+    // and a lane whose last band the next lane shares ends at that lane's first cell.  Both are settled here: `cut` comes off
+    // the first span, `laneEnd` bounds every band's end, and the rounds know nothing of halves.
+    uint32_t cut = 0, laneEnd = 0xFFFFFFFFu;
+    if constexpr (FIRST && SUB == 8 && EVEN)
+    {
+        {
+            if (has && Q.midStart)
+            {
+                const LdsBytePtr rec0 = reinterpret_cast<LdsBytePtr>(static_cast<uintptr_t>(planAt));
+                const uint32_t span0 = rec0[7], sh0 = __builtin_amdgcn_ubfe(static_cast<uint32_t>(rec0[5]), 5u, 2u);
+                cut = min(span0, span0 - (span0 >> 1) + (Q.midStraddle ? 1u << sh0 : 0u));
+            }
+            if (has && Q.midEnd)
+                laneEnd = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsWordPtr)row)) + 2u * static_cast<uint32_t>(min(Q.endIdx, 256));
+        }
+    }
+    int outIdx = min(Q.outIdx, 256 - ((SUB == 16 && Q.midStart) ? midAdvance : upTo - before - static_cast<int>(cut >> 1)));
     bool valid = true;
     const bool owner = has && Q.bandBase == 0;          // the lane that holds band 0 does the DC fix-up
     const uint32_t saved1 = (owner && !FIRST) ? row[1] : 0u;
@@ -574,6 +595,13 @@ __device__ uint32_t unpack94(const DcsLdsTables *T, uint16_t *row, BR &br, const
                 scale = valid ? static_cast<int>(recScale) : 0;    // after a STOP the band is still parsed, its samples contribute nothing
                 // a band without a code moves on by its span and is over; a coded one has its span to decode
                 cellEnd = cell + span;
+                if constexpr (FIRST && SUB == 8 && EVEN)
+                {
+                    // (never in front of the cell: with the library's own mid records it is not, and a caller-made one must not
+                    // send the lane into the overshoot path below, which steps back)
+                    cellEnd = max(cell, min(cellEnd - cut, laneEnd));
+                    cut = 0;
+                }
                 cell = recWidth > 0x7Fu ? cellEnd : cell;
                 cellStart = cell;
                 startBits = br.mark();
@@ -637,7 +665,8 @@ __device__ uint32_t unpack94(const DcsLdsTables *T, uint16_t *row, BR &br, const
         if (round == 0) stamp(9);
         // (the round is bounded in samples, not iterations: a symbol is at least one sample, and the loop's only test
         // stays the cell against an end)
-        const uint32_t roundLen = round == 0 ? 7u : round == 1 ? 9u : 16u;
+        // (the even deal's units are 8 samples, and so are its rounds)
+        const uint32_t roundLen = (FIRST && SUB == 8 && EVEN) ? 8u : round == 0 ? 7u : round == 1 ? 9u : 16u;
         const uint32_t roundEnd = min(cellEnd, cell + (roundLen << incSh));
         if (cell < roundEnd)
         {
@@ -1549,7 +1578,9 @@ __host__ __device__ constexpr PaceSchedule paceSchedule(int cpw, int pass)
 #endif
 }
 
-template <int FPW, int CPW = 1>
+// EVEN: the packages of the batch carry the even deal of 1994+ frames (DCS_BATCH_EVEN_DEAL, dcs_package.h; 8 frames per wavefront):
+// a kernel of its own, so that the others are what they were
+template <int FPW, int CPW = 1, bool EVEN = false>
 #ifndef DCS_MIN_WAVES
 #define DCS_MIN_WAVES 4
 #endif

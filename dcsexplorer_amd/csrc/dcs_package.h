@@ -195,6 +195,31 @@ DCS_HDI constexpr bool dcsMid15(int format, int bpl, int nb16, uint32_t midBits)
     return format >= DCS_FMT_94_T0 && bpl == 1 && nb16 == 16 && midBits != 0;
 }
 
+// The EVEN deal of a 1994+ frame to eight lanes (first source, 8 frames per wavefront, a batch with DCS_BATCH_EVEN_DEAL).
+// Whole bands cannot be dealt more evenly than 31 or 32 samples for the fullest lane, however few of the sixteen bands the
+// stream codes; UNITS of 8 samples can: band 0 (7 samples), band 1, and the two halves of every later band (a strided band's
+// halved count still makes two halves).  A frame of nb header bands has dcsEvenUnits(nb) of them; lane q takes
+// dcsLaneUnits(nb, q).count consecutive ones from .first on: ceil(units / 8) or one fewer, in order.  A lane that starts with
+// a second half needs the decoder's state in the middle of that band: the mid records (DcsFrameMids, made by the host index
+// walk, dcs_index_stream_mids).  The symbol loop then runs in rounds of 8 samples.
+// Today's deal stays for a frame with all sixteen bands (band 15's halves are 16 samples: units do no better than 32 there),
+// for one without mid records or in error, for the 1993 layouts and for the further sources of a frame.
+struct DcsUnitRange { int first, count; };
+DCS_HDI constexpr int dcsEvenUnits(int nb) { return nb < 2 ? nb : 2 * nb - 2; }
+DCS_HDI constexpr DcsUnitRange dcsLaneUnits(int nb, int q)
+{
+    const int units = dcsEvenUnits(nb), lo = units >> 3, extra = units & 7;
+    return DcsUnitRange{ q * lo + (q < extra ? q : extra), lo + (q < extra ? 1 : 0) };
+}
+DCS_HDI constexpr int dcsUnitBand(int u) { return u < 2 ? u : 1 + (u >> 1); }
+DCS_HDI constexpr int dcsUnitHalf(int u) { return u < 2 ? 0 : (u & 1); }
+// mid[0] of a frame's DcsFrameMids: set when the walk recorded the middle of every band it has
+#define DCS_MIDS_VALID 1u
+DCS_HDI constexpr bool dcsEvenDealt(int format, int bpl, int nb16, int sub, const uint32_t *mid)
+{
+    return format >= DCS_FMT_94_T0 && bpl != 0 && sub == 8 && nb16 < 16 && mid != nullptr && mid[0] == DCS_MIDS_VALID;
+}
+
 // Chunk packages.  Everything unpack round 0 of a chunk needs, gathered once per batch by the host packer
 // (dcsBuildPackages, dcs_plan.cpp) or the device packer (dcsPackKernel) into one block at a fixed stride, so that a wavefront
 // requests ALL of it at its first instruction (no load depends on another load).  Round 5 layout (a wavefront reads its whole
@@ -229,21 +254,23 @@ struct DcsPkgSrc
     uint64_t streamOff;
     uint32_t mixMul, format, hdrLen, nBands;
     const DcsFrameIndex *rec;
+    const uint32_t *mid;                // the frame's DcsFrameMids, or null: whole bands only (dcsEvenDealt)
 };
 DCS_HDI bool dcsSlotHasSrc(const DcsSlot &sl) { return !(sl.flags & DCS_SLOT_EMPTY) && sl.nSrc != 0; }
-DCS_HDI DcsPkgSrc dcsPkgSrcOf(const DcsSlot &sl, const DcsSrcDesc *srcs)
+DCS_HDI DcsPkgSrc dcsPkgSrcOf(const DcsSlot &sl, const DcsSrcDesc *srcs, const DcsFrameMids *mids = nullptr)
 {
     if (!dcsSlotHasSrc(sl) || srcs == nullptr)
-        return DcsPkgSrc{ 0, 0, 0, 0, 0, nullptr };
+        return DcsPkgSrc{ 0, 0, 0, 0, 0, nullptr, nullptr };
     const DcsSrcDesc &sd = srcs[sl.firstSrc];
-    return DcsPkgSrc{ sd.streamOff, sd.mixMul, sd.format, sd.hdrLen, sd.idx.nBands, &sd.idx };
+    return DcsPkgSrc{ sd.streamOff, sd.mixMul, sd.format, sd.hdrLen, sd.idx.nBands, &sd.idx,
+                      mids != nullptr ? mids[sl.firstSrc].mid : nullptr };
 }
 DCS_HDI DcsPkgSrc dcsPkgSrcOf(const DcsSlot &sl, const DcsPlanSrc *srcs, const DcsFrameIndex *records)
 {
     if (!dcsSlotHasSrc(sl))
-        return DcsPkgSrc{ 0, 0, 0, 0, 0, nullptr };
+        return DcsPkgSrc{ 0, 0, 0, 0, 0, nullptr, nullptr };
     const DcsPlanSrc sd = srcs[sl.firstSrc];
-    return DcsPkgSrc{ sd.streamOff, sd.mixMul, sd.format, sd.hdrLen, sd.nBands, &records[sd.record] };
+    return DcsPkgSrc{ sd.streamOff, sd.mixMul, sd.format, sd.hdrLen, sd.nBands, &records[sd.record], nullptr };
 }
 
 // The 80-byte slot entry as dwords (five 16-byte pieces): slot bytes 0..15 | the 40-byte descriptor head -- what DcsSrcDesc
@@ -293,7 +320,27 @@ DCS_HDI void dcsLaneSplit(uint32_t r[2], const DcsPkgSrc &sd, int bpl, int q, in
     const int format = static_cast<int>(sd.format), nBands = static_cast<int>(sd.nBands);
     const int nbEnd = dcsDealEnd(format, nBands), base = dcsLaneFirstBand(format, q, bpl, nbEnd);
     const DcsRecDword *split = reinterpret_cast<const DcsRecDword *>(sd.rec->split), *mid = split + 2 * 14;
-    if (q == sub - 1 && dcsMid15(format, bpl, nBands < 16 ? nBands : 16, mid[0] >> 16))
+    if (dcsEvenDealt(format, bpl, nbEnd, sub, sd.mid))
+    {
+        // the even deal: the lane's first unit is a band, whose record is the band's, or the second half of one, whose
+        // record is the mid record in the form of band 15's below
+        const DcsUnitRange u = dcsLaneUnits(nbEnd, q);
+        const int band = dcsUnitBand(u.first);
+        if (u.count == 0)
+            r[0] = 0x8000u;
+        else if (dcsUnitHalf(u.first) != 0)
+        {
+            r[0] = sd.mid[band] & 0xFFFFu;
+            r[1] = (((sd.mid[band] >> 16) & 0x3FFu) | DCS_SPLIT_MID15 | (static_cast<uint32_t>(band) << 12)) << 16;
+        }
+        else
+        {
+            const DcsRecDword *sp = split + 2 * (band - 1);
+            r[0] = sp[0];
+            r[1] = (sp[1] & 0x0FFFFFFFu) | (static_cast<uint32_t>(band) << 28);
+        }
+    }
+    else if (q == sub - 1 && dcsMid15(format, bpl, nBands < 16 ? nBands : 16, mid[0] >> 16))
     {
         // the second half of band 15 (1994+, one band per lane): split[14].prv / .prvDelta
         r[0] = mid[0] >> 16;

@@ -366,7 +366,7 @@ extern "C" DcsStatus dcs_plan_chunks(const DcsFrameJob *jobs, uint32_t nJobs, co
 // (big-endian).  A layout change only; nothing is decoded.  The device then reads nothing else in round 0.
 // ---------------------------------------------------------------------------------------------------------
 static void packChunks(const DcsSlot *slots, uint32_t c0, uint32_t c1, int fpw, const DcsSrcDesc *srcs,
-                       const uint8_t *blob, size_t blobLen, uint8_t *out, uint32_t layout)
+                       const uint8_t *blob, size_t blobLen, uint8_t *out, uint32_t layout, const DcsFrameMids *mids)
 {
     const uint32_t pkgBytes = dcsPkgStride(fpw, layout);
     const bool split4 = (layout & DCS_PKG_SPLIT4) != 0;
@@ -378,7 +378,7 @@ static void packChunks(const DcsSlot *slots, uint32_t c0, uint32_t c1, int fpw, 
         memset(pkg, 0, pkgBytes);
         for (int s = 0 ; s < fpw ; ++s)
         {
-            const DcsPkgSrc sd = dcsPkgSrcOf(cs[s], srcs);
+            const DcsPkgSrc sd = dcsPkgSrcOf(cs[s], srcs, mids);
             uint32_t entry[DCS_PKG_SLOT_DWORDS];
             dcsPkgSlotEntry(entry, cs[s], sd, blob, blobLen);
             memcpy(pkg + static_cast<size_t>(s) * DCS_PKG_SLOT_BYTES, entry, DCS_PKG_SLOT_BYTES);
@@ -415,8 +415,28 @@ static void packChunks(const DcsSlot *slots, uint32_t c0, uint32_t c1, int fpw, 
     }
 }
 
+// The fullest lane's samples of a frame of nb header bands, whole bands against units (dcs_package.h)
+int dcsEvenDealGain(int nb)
+{
+    nb = nb < 0 ? 0 : nb > 16 ? 16 : nb;
+    if (nb >= 16)
+        return 0;                                       // (such a frame keeps whole bands)
+    const int bpl = dcsBandsPerLane(static_cast<uint32_t>(nb), 0, 8);
+    int whole = 0;
+    for (int q = 0 ; q < 8 ; ++q)
+    {
+        const int b0 = dcsLaneFirstBand(DCS_FMT_94_T0, q, bpl, nb), b1 = q == 7 ? nb : dcsLaneFirstBand(DCS_FMT_94_T0, q + 1, bpl, nb);
+        int n = 0;
+        for (int b = b0 ; b < b1 ; ++b)
+            n += b == 0 ? 7 : b == 1 ? 8 : 16;
+        whole = n > whole ? n : whole;
+    }
+    // (rounds of 8 samples: the lanes that hold band 0 have one sample fewer, the round is as long as the others')
+    return whole - 8 * dcsLaneUnits(nb, 0).count;
+}
+
 void dcsBuildPackages(const DcsSlot *slots, uint32_t nChunks, int fpw, const DcsSrcDesc *srcs,
-                      const uint8_t *blob, size_t blobLen, uint8_t *out, uint32_t layout)
+                      const uint8_t *blob, size_t blobLen, uint8_t *out, uint32_t layout, const DcsFrameMids *mids)
 {
     // (measured on the 2 x EPYC host of an MI355X box, 65 536 frames: 1 thread 2.5 ms, 4 threads 1.2 ms, 8 and 16
     // threads no faster -- the work is memory traffic -- and they slow the single-threaded planner of the next batch down)
@@ -424,7 +444,7 @@ void dcsBuildPackages(const DcsSlot *slots, uint32_t nChunks, int fpw, const Dcs
     if (nt > 4) nt = 4;
     if (nt <= 1)
     {
-        packChunks(slots, 0, nChunks, fpw, srcs, blob, blobLen, out, layout);
+        packChunks(slots, 0, nChunks, fpw, srcs, blob, blobLen, out, layout, mids);
         return;
     }
     std::vector<std::thread> th;
@@ -433,16 +453,24 @@ void dcsBuildPackages(const DcsSlot *slots, uint32_t nChunks, int fpw, const Dcs
     {
         const uint32_t c0 = t * per, c1 = c0 + per < nChunks ? c0 + per : nChunks;
         if (c0 < c1)
-            th.emplace_back(packChunks, slots, c0, c1, fpw, srcs, blob, blobLen, out, layout);
+            th.emplace_back(packChunks, slots, c0, c1, fpw, srcs, blob, blobLen, out, layout, mids);
     }
     for (std::thread &t : th)
         t.join();
 }
 
+// Diagnostic / test entries: the even deal's rule (dcsLaneUnits), and the packages of dcs_batch_create_mids with the deal forced
+extern "C" void dcs_even_deal_lane(int nBands, int q, int *firstUnit, int *nUnits, int *gain)
+{
+    const DcsUnitRange u = dcsLaneUnits(nBands < 0 ? 0 : nBands > 16 ? 16 : nBands, q);
+    if (firstUnit != nullptr) *firstUnit = u.first;
+    if (nUnits != nullptr) *nUnits = u.count;
+    if (gain != nullptr) *gain = dcsEvenDealGain(nBands);
+}
 // Diagnostic / test entry: plan + pack on the host, exactly what dcs_batch_create uploads.
-extern "C" DcsStatus dcs_pack_chunks(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs,
-                                     const uint8_t *blob, size_t blobLen, int fpw,
-                                     uint8_t *out, size_t cap, uint32_t *nChunksOut, uint32_t *packageBytesOut)
+static DcsStatus packEntry(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, const DcsFrameMids *mids,
+                           const uint8_t *blob, size_t blobLen, int fpw,
+                           uint8_t *out, size_t cap, uint32_t *nChunksOut, uint32_t *packageBytesOut)
 {
     if (jobs == nullptr || srcs == nullptr || nChunksOut == nullptr || !(fpw == 4 || fpw == 8 || fpw == 16))
         return DCS_ERR_INVALID_ARG;
@@ -456,6 +484,19 @@ extern "C" DcsStatus dcs_pack_chunks(const DcsFrameJob *jobs, uint32_t nJobs, co
         return DCS_OK;
     if (cap < static_cast<size_t>(nChunks) * dcsPkgStride(fpw, layout))
         return DCS_ERR_CAPACITY;
-    dcsBuildPackages(slots.data(), nChunks, fpw, srcs, blob, blobLen, out, layout);
+    dcsBuildPackages(slots.data(), nChunks, fpw, srcs, blob, blobLen, out, layout, mids);
     return DCS_OK;
+}
+extern "C" DcsStatus dcs_pack_chunks(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs,
+                                     const uint8_t *blob, size_t blobLen, int fpw,
+                                     uint8_t *out, size_t cap, uint32_t *nChunksOut, uint32_t *packageBytesOut)
+{
+    return packEntry(jobs, nJobs, srcs, nullptr, blob, blobLen, fpw, out, cap, nChunksOut, packageBytesOut);
+}
+// ... and what dcs_batch_create_mids uploads where it takes the even deal
+extern "C" DcsStatus dcs_pack_chunks_mids(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, const DcsFrameMids *mids,
+                                          const uint8_t *blob, size_t blobLen, int fpw,
+                                          uint8_t *out, size_t cap, uint32_t *nChunksOut, uint32_t *packageBytesOut)
+{
+    return packEntry(jobs, nJobs, srcs, mids, blob, blobLen, fpw, out, cap, nChunksOut, packageBytesOut);
 }

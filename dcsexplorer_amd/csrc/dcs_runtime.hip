@@ -30,6 +30,7 @@ struct DcsCtx
     DcsDevTables *dTables = nullptr;
     int fpwOverride = 0;
     int cpwOverride = 0;                // chunks per wavefront of a decode launch: 0 = by the launch's size (twoChunksPerWave), 1, 2
+    int evenDeal = -1;                  // the deal of 1994+ frames in batches given mid records: 0 whole bands, 1 units, -1 units where a frame gains
     bool handoff = true;                // tails cross chunk boundaries through the hand-off buffer (else: halo re-decode)
     uint32_t shuffleSeed = 0;           // test hook: host-planned batches get their chunks in a seeded random order (dcs_ctx_set_test_hooks)
     bool noXcdRanges = false;           // test hook: no batch of this context is launched in XCD ranges
@@ -575,6 +576,14 @@ extern "C" DcsStatus dcs_ctx_set_chunks_per_wave(DcsCtx *ctx, int chunks)
     return DCS_OK;
 }
 
+extern "C" DcsStatus dcs_ctx_set_even_deal(DcsCtx *ctx, int mode)
+{
+    if (ctx == nullptr || mode < -1 || mode > 1)
+        return DCS_ERR_INVALID_ARG;
+    ctx->evenDeal = mode;
+    return DCS_OK;
+}
+
 extern "C" DcsStatus dcs_ctx_set_frames_per_chunk(DcsCtx *ctx, int frames)
 {
     if (ctx == nullptr || frames < 0 || frames > 16)
@@ -768,6 +777,34 @@ static DcsStatus validateBatch(DcsCtx *ctx, size_t blobLen, const DcsSrcDesc *sr
     return DCS_OK;
 }
 
+// Caller-made mid records (dcs_batch_create_mids) steer where lanes start and stop inside a band, as the band-15 middle of the
+// record does: a frame's must lie inside the frame and inside their bands -- bits between the band's start and the frame's end,
+// the output index between the band's start and the next band's (the row's end for the last band).  Frames not marked
+// DCS_MIDS_VALID are never dealt by them and are not looked at.
+static DcsStatus validateMids(DcsCtx *ctx, const DcsSrcDesc *srcs, const DcsFrameMids *mids, uint32_t nSrcs)
+{
+    for (uint32_t s = 0 ; s < nSrcs ; ++s)
+    {
+        if (mids[s].mid[0] != DCS_MIDS_VALID)
+            continue;
+        const DcsFrameIndex &ix = srcs[s].idx;
+        const int nb = ix.nBands < 16 ? ix.nBands : 16;
+        bool ok = srcs[s].format >= DCS_FMT_94_T0 && ix.flags == 0;
+        for (int band = 2 ; band < nb && ok ; ++band)
+        {
+            const uint32_t m = mids[s].mid[band], bits = m & 0xFFFFu, idx = (m >> 16) & 0x1FFu;
+            const uint32_t idx0 = ix.split[band - 1].state & 0x1FFu, idx1 = band + 1 < nb ? (ix.split[band].state & 0x1FFu) : 256u;
+            ok = bits >= ix.split[band - 1].bitDelta && bits <= ix.nBits && idx >= idx0 && idx <= idx1 && idx <= 256u;
+        }
+        if (!ok)
+        {
+            setError(ctx, "source " + std::to_string(s) + ": inconsistent mid records");
+            return DCS_ERR_INVALID_ARG;
+        }
+    }
+    return DCS_OK;
+}
+
 // How a batch is made besides its jobs: what the callers of the three constructors below choose
 struct BatchOptions
 {
@@ -912,7 +949,7 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
                              const uint8_t *blob, size_t blobLen,
                              const DcsSrcDesc *srcs, uint32_t nSrcs,
                              const DcsFrameJob *jobs, uint32_t nJobs,
-                             const int16_t *tailsIn, uint32_t nTailsIn, DcsBatch **out)
+                             const int16_t *tailsIn, uint32_t nTailsIn, DcsBatch **out, const DcsFrameMids *mids = nullptr)
 {
     if (out == nullptr || jobs == nullptr || nJobs == 0 || (nSrcs != 0 && (srcs == nullptr || blob == nullptr)))
         return DCS_ERR_INVALID_ARG;
@@ -924,6 +961,9 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
         const DcsStatus vst = validateBatch(ctx, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, &payloadBits, &batchFlags);
         if (vst != DCS_OK)
             return vst;
+        const DcsStatus mst = mids != nullptr ? validateMids(ctx, srcs, mids, nSrcs) : DCS_OK;
+        if (mst != DCS_OK)
+            return mst;
     }
     const bool ranges = o.ranges(ctx);
     const JobKinds kinds = classifyJobs(jobs, nJobs, srcs);
@@ -939,6 +979,22 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
     const DcsPlan plan = planOnHost(ctx, jobs, nJobs, srcs, b->fpw, kinds.split4, slots, po);
     b->nChunks = plan.nChunks;
     b->imgDw = plan.imgDw;
+    // The even deal (dcs_package.h): mid records, 8 frames per wavefront, every source a 1994+ frame (the first source of a job is
+    // dealt so, its further sources keep whole bands), every job the 1994+ transform -- and, unless the context
+    // forces it, some frame that gains by it (a list of streams with all sixteen bands keeps the rounds of 7, 9 and 16 samples)
+    // (By the rule: at least half of the sources gain.  A frame that does not gain -- all sixteen bands, or in error -- runs four
+    // rounds of 8 under the flag where it ran three of 7, 9 and 16, and a chunk is through when its fullest lane is, so a list of
+    // mostly such frames with a few short streams among them would only pay.  Where between "some" and "half" the balance tips
+    // has not been measured; half is the side that cannot lose more than it gains.)
+    if (mids != nullptr && ctx->evenDeal != 0 && b->fpw == 8 && kinds.split4 && kinds.all94)
+    {
+        uint32_t gaining = 0;
+        for (uint32_t k = 0 ; k < nSrcs ; ++k)
+            gaining += (mids[k].mid[0] == DCS_MIDS_VALID && dcsEvenDealGain(srcs[k].idx.nBands) > 0) ? 1u : 0u;
+        if (ctx->evenDeal == 1 || (gaining != 0 && 2u * gaining >= nSrcs))
+            b->flags |= DCS_BATCH_EVEN_DEAL;
+    }
+    const DcsFrameMids *packMids = (b->flags & DCS_BATCH_EVEN_DEAL) ? mids : nullptr;
 
     CacheBuf hPackages;                         // pinned staging for the chunk packages
     DcsStatus st = [&]() -> DcsStatus {
@@ -961,7 +1017,7 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
         }
         // built in pinned host memory (recycled by the context like the device buffers): the upload runs at link speed
         HIPCHK(ctx, hPackages.alloc(ctx, true, static_cast<size_t>(b->nChunks) * dcsPkgStride(b->fpw, b->imgDw)));
-        dcsBuildPackages(slots.data(), b->nChunks, b->fpw, srcs, blob, blobLen, hPackages.as<uint8_t>(), b->imgDw);
+        dcsBuildPackages(slots.data(), b->nChunks, b->fpw, srcs, blob, blobLen, hPackages.as<uint8_t>(), b->imgDw, packMids);
         HIPCHK(ctx, b->dPackages.alloc(ctx, false, hPackages.bytes()));
         HIPCHK(ctx, hipMemcpyAsync(b->dPackages.as(), hPackages.as(), hPackages.bytes(), hipMemcpyHostToDevice, b->stream));
         if (nTailsIn)
@@ -1098,6 +1154,20 @@ extern "C" DcsStatus dcs_batch_create(DcsCtx *ctx,
     return createBatch(ctx, o, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, out);
 }
 
+extern "C" DcsStatus dcs_batch_create_mids(DcsCtx *ctx,
+                                           const uint8_t *blob, size_t blobLen,
+                                           const DcsSrcDesc *srcs, const DcsFrameMids *mids, uint32_t nSrcs,
+                                           const DcsFrameJob *jobs, uint32_t nJobs,
+                                           const int16_t *tailsIn, uint32_t nTailsIn,
+                                           DcsBatch **out)
+{
+    if (ctx == nullptr)
+        return DCS_ERR_INVALID_ARG;
+    BatchOptions o(ctx);
+    o.resident = true;
+    return createBatch(ctx, o, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, out, mids);
+}
+
 // Two chunks per wavefront (dcsDecodeKernel<8, 2>) where the chunks make more than one and at most two generations of the chip's
 // CUs x 16 wavefront places: one generation of wavefronts then decodes them with every SIMD given the same share, where two
 // generations of one-chunk wavefronts leave the compute units with 7, 8 or 9 workgroups each (NOTES 36, 49).  Only for a launch
@@ -1127,6 +1197,19 @@ static hipError_t launch(const DcsKernelArgs &args, hipStream_t stream, int numC
     if (waves > cus * 4u && cus % 8u == 0 && cus / 8u < 256u)
         flags |= DCS_BATCH_PACED | ((cus / 8u) << DCS_BATCH_CUS8_SHIFT);
     if constexpr (FPW == 8)
+    {
+        if (flags & DCS_BATCH_EVEN_DEAL)
+        {
+            if (two)
+                dcsk::dcsDecodeKernel<FPW, 2, true><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
+                    args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
+                    args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
+            else
+                dcsk::dcsDecodeKernel<FPW, 1, true><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
+                    args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
+                    args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
+            return hipGetLastError();
+        }
         if (two)
         {
             dcsk::dcsDecodeKernel<FPW, 2><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
@@ -1134,6 +1217,7 @@ static hipError_t launch(const DcsKernelArgs &args, hipStream_t stream, int numC
                 args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
             return hipGetLastError();
         }
+    }
     dcsk::dcsDecodeKernel<FPW><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
         args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
         args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
@@ -1353,6 +1437,7 @@ extern "C" int dcs_batch_chunks_per_wave(const DcsBatch *b)
     const uint32_t cus = static_cast<uint32_t>(b->ctx->numCUs);
     return twoChunksPerWave(b->fpw, b->ctx->cpwOverride, b->solo, b->nChunks, b->flags, cus) ? 2 : 1;
 }
+extern "C" int dcs_batch_even_deal(const DcsBatch *b) { return (b != nullptr && (b->flags & DCS_BATCH_EVEN_DEAL)) ? 1 : 0; }
 extern "C" uint32_t dcs_batch_num_jobs(const DcsBatch *b) { return b ? b->nJobs : 0; }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -32,7 +32,10 @@ extern "C" {
 #endif
 
 #define DCS_ABI_VERSION 9              /* 9: dcs_decode_batch_live, dcs_seq_decode_view, dcs_seq_plan_ahead, dcs_seq_stream_playing_at (round 6);
-                                          additions since, which change no existing layout or entry point: the 1994+ encoder
+                                          additions since, which change no existing layout or entry point: the even deal
+                                          (DcsFrameMids, dcs_index_stream_mids, dcs_index_streams_mids, dcs_batch_create_mids,
+                                          dcs_ctx_set_even_deal, dcs_batch_even_deal, dcs_pack_chunks_mids, dcs_even_deal_lane);
+                                          the 1994+ encoder
                                           (DcsEncodeParams, DcsEncodeInfo, dcs_encode_params_default, dcs_encode_bound,
                                           dcs_encode_header, dcs_encode_streams); the OS93 encoder (dcs_encode93_bound,
                                           dcs_encode93_header, dcs_encode93_streams); transcoding (DcsTranscodeInfo,
@@ -159,6 +162,27 @@ typedef struct DcsStreamInfo           /* DCSDecoderNative::StreamInfo (DCSDecod
  * only fill `info`).  Returns DCS_ERR_CAPACITY if cap was too small (info is still valid). */
 DcsStatus dcs_index_stream(DcsOsVersion os, const uint8_t *stream, size_t len,
                            DcsFrameIndex *out, uint32_t cap, DcsStreamInfo *info);
+
+/* 1994+: the decoder state in the MIDDLE of every band of 16 or 32 samples, a side array next to the frame's record (the
+ * record itself keeps band 15's middle only).  mid[b], b = 2 .. nBands - 1: bits from the frame's first bit to the first code
+ * that starts with at least half of the band's samples done | (output index there | 0x200 when a two-zeros code carried one
+ * sample across the middle) << 16 -- the rule and the straddle flag of the record's split[14].prv / .prvDelta.  A band
+ * without a code has its middle where it starts, half of its advance on.  mid[0] = 1 marks a frame whose middles were all
+ * recorded; all zero: a frame in error (never split), or not a 1994+ frame.  mid[1] is unused. */
+typedef struct DcsFrameMids
+{
+    uint32_t mid[16];
+} DcsFrameMids;
+
+/* dcs_index_stream with the mid records as a second output (`mids`: cap entries, may be NULL).  Same records, same
+ * summary, same return value. */
+DcsStatus dcs_index_stream_mids(DcsOsVersion os, const uint8_t *stream, size_t len,
+                                DcsFrameIndex *out, uint32_t cap, DcsStreamInfo *info, DcsFrameMids *mids);
+
+/* ... and dcs_index_streams (below) likewise: stream k's mid records at mids + firstRecord[k] (mids may be NULL) */
+typedef struct DcsStreamRef DcsStreamRef;
+DcsStatus dcs_index_streams_mids(const DcsStreamRef *streams, uint32_t nStreams, int nThreads,
+                                 DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos, DcsFrameMids *mids);
 
 /* Diagnostic: the same scan with a reader that keeps the reference reader's byte pointer literally (Peek pulls whole
  * bytes while nBits <= n, DCSDecoderNative.h:271) and decodes one code per look.  dcs_index_stream computes that pointer
@@ -329,6 +353,23 @@ DcsStatus dcs_batch_create(DcsCtx *ctx,
                            const DcsFrameJob *jobs, uint32_t nJobs,
                            const int16_t *tailsIn, uint32_t nTailsIn,
                            DcsBatch **batch);
+/* The same with the mid records of the sources (`mids`: nSrcs entries parallel to `srcs`, dcs_index_stream_mids; NULL: none).
+ * With them a batch of 8 frames per wavefront whose sources are all 1994+ frames deals the samples of a frame's first source
+ * to its eight unpack lanes in units of 8 (the even deal, dcs_package.h) wherever that is fewer for the fullest lane than
+ * whole bands give: streams that code fewer than sixteen bands.  Same PCM and error words. */
+DcsStatus dcs_batch_create_mids(DcsCtx *ctx,
+                                const uint8_t *blob, size_t blobLen,
+                                const DcsSrcDesc *srcs, const DcsFrameMids *mids, uint32_t nSrcs,
+                                const DcsFrameJob *jobs, uint32_t nJobs,
+                                const int16_t *tailsIn, uint32_t nTailsIn,
+                                DcsBatch **batch);
+/* tuning: the deal of a 1994+ frame to its unpack lanes in batches created afterwards.  0: whole bands, always; 1: the even
+ * deal wherever the batch allows it (8 frames per wavefront, all-1994+ sources, mid records), even where no frame
+ * gains; -1 (default): the even deal where at least half of the batch's sources gain by it (a frame that does not runs a
+ * fourth round under it).  Every job of the batch must use the 1994+ transform.  Mid records that do not lie inside their
+ * frame and band (bits, output index) are refused with DCS_ERR_INVALID_ARG, like an inconsistent index record. */
+DcsStatus dcs_ctx_set_even_deal(DcsCtx *ctx, int mode);
+int       dcs_batch_even_deal(const DcsBatch *batch);           /* 1: the batch's packages carry the even deal */
 void      dcs_batch_destroy(DcsBatch *batch);
 /* Enqueue the decode on `hipStream` (a hipStream_t passed as void*; NULL = the context's stream).
  * Asynchronous: returns after the launch.  No wavefront of the launch waits for another (a frame whose predecessor is decoded by
@@ -780,6 +821,13 @@ DcsStatus dcs_plan_chunks2(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrc
 DcsStatus dcs_pack_chunks(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs,
                           const uint8_t *blob, size_t blobLen, int fpw,
                           uint8_t *out, size_t cap, uint32_t *nChunksOut, uint32_t *packageBytesOut);
+/* ... and the packages of dcs_batch_create_mids where it takes the even deal (mids = NULL: dcs_pack_chunks); the rule of that
+ * deal: the first unit and the number of units of lane q (0..7) of a frame of nBands header bands, and what the deal saves
+ * the frame's fullest lane, in samples */
+DcsStatus dcs_pack_chunks_mids(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, const DcsFrameMids *mids,
+                               const uint8_t *blob, size_t blobLen, int fpw,
+                               uint8_t *out, size_t cap, uint32_t *nChunksOut, uint32_t *packageBytesOut);
+void      dcs_even_deal_lane(int nBands, int q, int *firstUnit, int *nUnits, int *gain);
 
 /* Diagnostic: the same packages as the DEVICE packer assembles them (what a DCS_PIPE_PACK_ON_DEVICE pipeline does: plan on
  * the host from 8-byte source digests, pack kernel on the device from resident records and streams).  Byte for byte what
