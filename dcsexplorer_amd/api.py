@@ -628,18 +628,23 @@ def _check(st, ctx=None):
 
 
 # ---------------------------------------------------------------------------------------------- host side
-def index_stream(os_, stream, literal=False):
-    """dcs_index_stream (literal: dcs_index_stream_literal): returns (index records as INDEX_DTYPE array, StreamInfo)"""
-    L = load_library()
+def _index_one(entry, os_, stream, with_mids=False):
+    """one stream through `entry` of the library: (records, StreamInfo), and the mid records where the entry makes them"""
     buf = np.frombuffer(bytes(stream), dtype=np.uint8)
     nframes = (int(buf[0]) << 8) | int(buf[1])
     out = np.zeros(max(nframes, 1), dtype=INDEX_DTYPE)
+    mids = (np.zeros((max(nframes, 1), 16), dtype=np.uint32),) if with_mids else ()
     info = StreamInfo()
-    fn = L.dcs_index_stream_literal if literal else L.dcs_index_stream
-    st = fn(os_, _ptr(buf), buf.size, _ptr(out), nframes, ctypes.byref(info))
+    st = entry(os_, _ptr(buf), buf.size, _ptr(out), nframes, ctypes.byref(info), *[_ptr(m) for m in mids])
     if st != 0:
         raise DcsError(st)
-    return out[:info.nValidFrames], info
+    return (out[:info.nValidFrames], info) + tuple(m[:info.nValidFrames] for m in mids)
+
+
+def index_stream(os_, stream, literal=False):
+    """dcs_index_stream (literal: dcs_index_stream_literal): returns (index records as INDEX_DTYPE array, StreamInfo)"""
+    L = load_library()
+    return _index_one(L.dcs_index_stream_literal if literal else L.dcs_index_stream, os_, stream)
 
 
 class SrcArray(np.ndarray):
@@ -656,16 +661,7 @@ class SrcArray(np.ndarray):
 def index_stream_mids(os_, stream):
     """dcs_index_stream_mids: (index records, StreamInfo, mid records [frames, 16] uint32) -- the middle of every 1994+ band of
     16 or 32 samples, for the even deal of dcs_batch_create_mids"""
-    L = load_library()
-    buf = np.frombuffer(bytes(stream), dtype=np.uint8)
-    nframes = (int(buf[0]) << 8) | int(buf[1])
-    out = np.zeros(max(nframes, 1), dtype=INDEX_DTYPE)
-    mids = np.zeros((max(nframes, 1), 16), dtype=np.uint32)
-    info = StreamInfo()
-    st = L.dcs_index_stream_mids(os_, _ptr(buf), buf.size, _ptr(out), nframes, ctypes.byref(info), _ptr(mids))
-    if st != 0:
-        raise DcsError(st)
-    return out[:info.nValidFrames], info, mids[:info.nValidFrames]
+    return _index_one(load_library().dcs_index_stream_mids, os_, stream, with_mids=True)
 
 
 def _info_from_record(r):
@@ -701,17 +697,13 @@ def index_streams(streams, threads=0, with_mids=False):
         refs[k].os = s[0]
     out = np.zeros(max(int(first[-1]), 1), dtype=INDEX_DTYPE)
     infos = np.zeros(len(streams), dtype=INFO_DTYPE)
-    mids = np.zeros((out.size, 16), dtype=np.uint32) if with_mids else None
-    if with_mids:
-        st = L.dcs_index_streams_mids(refs, len(streams), threads, _ptr(out), _ptr(first), _ptr(infos), _ptr(mids))
-    else:
-        st = L.dcs_index_streams(refs, len(streams), threads, _ptr(out), _ptr(first), _ptr(infos))
+    mids = (np.zeros((out.size, 16), dtype=np.uint32),) if with_mids else ()
+    entry = L.dcs_index_streams_mids if with_mids else L.dcs_index_streams
+    st = entry(refs, len(streams), threads, _ptr(out), _ptr(first), _ptr(infos), *[_ptr(m) for m in mids])
     if st != 0:
         raise DcsError(st)
-    recs = _split_records(out, infos, first)
-    if with_mids:
-        return [(r, i, mids[int(first[k]):int(first[k]) + len(r)]) for k, (r, i) in enumerate(recs)]
-    return recs
+    return [(r, i) + tuple(m[int(first[k]):int(first[k]) + len(r)] for m in mids)
+            for k, (r, i) in enumerate(_split_records(out, infos, first))]
 
 
 def pack_streams(streams, pad=64):
@@ -1217,16 +1209,14 @@ def pack_chunks(blob, srcs, jobs, fpw, mids=None):
     srcs = np.ascontiguousarray(srcs, dtype=SRC_DTYPE)
     jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
     n, pb = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    if mids is None:
-        def call(out, cap):
-            return L.dcs_pack_chunks(_ptr(jobs), jobs.size, _ptr(srcs), _ptr(blob_a), blob_a.size, fpw, out, cap, ctypes.byref(n), ctypes.byref(pb))
-    else:
+    entry, with_mids = L.dcs_pack_chunks, ()
+    if mids is not None:
         mids = np.ascontiguousarray(mids, dtype=np.uint32)
         assert mids.shape == (srcs.size, 16)
+        entry, with_mids = L.dcs_pack_chunks_mids, (_ptr(mids),)
 
-        def call(out, cap):
-            return L.dcs_pack_chunks_mids(_ptr(jobs), jobs.size, _ptr(srcs), _ptr(mids), _ptr(blob_a), blob_a.size, fpw, out, cap,
-                                          ctypes.byref(n), ctypes.byref(pb))
+    def call(out, cap):
+        return entry(_ptr(jobs), jobs.size, _ptr(srcs), *with_mids, _ptr(blob_a), blob_a.size, fpw, out, cap, ctypes.byref(n), ctypes.byref(pb))
     _check(call(None, 0))
     out = np.zeros((n.value, pb.value), dtype=np.uint8)
     _check(call(_ptr(out), out.size))

@@ -190,7 +190,7 @@ struct DcsDigested
 };
 #include <functional>
 DcsStatus dcsIndexStreamsNotify(const DcsStreamRef *streams, uint32_t nStreams, int nThreads,
-                                DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos,
+                                DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos, DcsFrameMids *mids,
                                 const std::function<void(uint32_t)> *done);
 bool dcsIndexPoolBusy();
 void dcsHostPoolRun(uint32_t n, int threads, const std::function<void(uint32_t)> &fn);

@@ -47,7 +47,7 @@ static DcsStatus decodeListThen(DcsCtx *ctx, const char *call, const DcsStreamRe
     if (st == DCS_OK)
     {
         BatchOptions o(ctx);
-        st = createBatch(ctx, o, d.built.blob.data(), d.built.blob.size(), d.built.srcs.data(), static_cast<uint32_t>(d.built.srcs.size()),
+        st = createBatch(ctx, o, d.built.blob.data(), d.built.blob.size(), d.built.srcs.data(), nullptr, static_cast<uint32_t>(d.built.srcs.size()),
                          d.built.jobs.data(), static_cast<uint32_t>(d.built.jobs.size()), nullptr, 0, &d.batch);
     }
     if (st == DCS_OK)

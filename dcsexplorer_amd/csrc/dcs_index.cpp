@@ -1,5 +1,5 @@
-// dcs_index.cpp -- host entry points of the index pass (the walker itself is dcs_scan.h, shared with
-// the device index kernel).
+// dcs_index.cpp -- host entry points of the index pass (the walker itself is dcs_scan.h, instantiated here only: the
+// device index kernel has a walk of its own, dcs_index_wave.hip.h, held to the same records).
 #include "dcs_scan.h"
 #include <atomic>
 #include <condition_variable>
@@ -125,11 +125,33 @@ struct ArraySink
     uint32_t cap;
     uint32_t written = 0;
     bool overflow = false;
+    bool valid() const { return out != nullptr || cap == 0; }
+    DcsStatus status() const { return overflow ? DCS_ERR_CAPACITY : DCS_OK; }
     void operator()(uint32_t f, const DcsFrameIndex &fi)
     {
         if (f < cap) { out[f] = fi; written = f + 1; }
-        else overflow = true;
+        else overflow = out != nullptr;         // (no array at all: the caller wants the summary only)
     }
+};
+
+// ... with the frame's mid records beside its record (a MIDS walk, dcs_scan.h)
+struct MidsSink : ArraySink
+{
+    DcsFrameMids *mids;
+    void operator()(uint32_t f, const DcsFrameIndex &fi, const DcsFrameMids &m)
+    {
+        ArraySink::operator()(f, fi);
+        if (f < cap) mids[f] = m;
+    }
+};
+
+// onFrame(f, record) for every frame, in order, on the calling thread
+struct CallbackSink
+{
+    const std::function<void(uint32_t, const DcsFrameIndex &)> &fn;
+    bool valid() const { return true; }
+    DcsStatus status() const { return DCS_OK; }
+    void operator()(uint32_t f, const DcsFrameIndex &fi) { fn(f, fi); }
 };
 
 }   // namespace
@@ -163,154 +185,56 @@ static const uint16_t *multi94Table()
     return table.data();
 }
 
+// One walk of one stream, as every entry below makes it: argument check, tables (the multi-code and first-level tables go
+// with the readers that compute the reference's byte pointer), working storage, the walk, the status.
+template <bool MIDS = false, class R, class Sink>
+static DcsStatus walkStream(DcsOsVersion os, const uint8_t *stream, size_t len, R reader, Sink &sink, DcsStreamInfo *info)
+{
+    if (stream == nullptr || len < 3 || os < DCS_OS93A || os > DCS_OS95 || !sink.valid())
+        return DCS_ERR_INVALID_ARG;
+    const DcsScanTables tabs{ &dcsTables().lds, dcsTables().trie94, R::kAnalytic ? multi94Table() : nullptr,
+                              R::kAnalytic ? dcsTables().fast94 : nullptr };
+    DcsScanMem mem;
+    const DcsStreamInfo si = dcsScanStream<MIDS>(static_cast<int>(os), reader, tabs, &mem, sink);
+    if (info != nullptr)
+        *info = si;
+    return si.nFrames == 0 ? DCS_ERR_BAD_STREAM : sink.status();
+}
+
 extern "C" DcsStatus dcs_index_stream(DcsOsVersion os, const uint8_t *stream, size_t len,
                                       DcsFrameIndex *out, uint32_t cap, DcsStreamInfo *info)
 {
-    if (stream == nullptr || len < 3 || os < DCS_OS93A || os > DCS_OS95 || (out == nullptr && cap != 0))
-        return DCS_ERR_INVALID_ARG;
-    WinBits reader{ stream, len };
-    const DcsScanTables tabs{ &dcsTables().lds, dcsTables().trie94, multi94Table(), dcsTables().fast94 };
     ArraySink sink{ out, cap };
-    DcsScanMem mem;
-    const DcsStreamInfo si = dcsScanStream(static_cast<int>(os), reader, tabs, &mem, sink);
-    if (info != nullptr)
-        *info = si;
-    if (si.nFrames == 0)
-        return DCS_ERR_BAD_STREAM;
-    if (out == nullptr && cap == 0)
-        return DCS_OK;
-    return sink.overflow ? DCS_ERR_CAPACITY : DCS_OK;
+    return walkStream(os, stream, len, WinBits{ stream, len }, sink, info);
 }
 
-// The mid records of a 1994+ frame (DcsFrameMids, dcs_hip.h): from the frame's record, which says where every band starts,
-// each band of 16 or 32 samples is walked again up to its middle -- the first code boundary with at least half of its samples
-// done, the rule of dcsPutMid15 (dcs_scan.h), whose record of band 15 this walk reproduces.  The walker itself, which the device
-// index kernel shares, is left as it is; the second look at half of the sample codes is host time of the batch's preparation.
-static void frameMids94(const uint8_t *stream, size_t len, const DcsStreamInfo &si, const DcsFrameIndex &fi, DcsFrameMids &out)
-{
-    out = DcsFrameMids{};
-    if (si.format < DCS_FMT_94_T0 || fi.flags != 0)
-        return;                                         // (a frame with an error flag is never split)
-    const DcsLdsTables &T = dcsTables().lds;
-    const bool type1 = si.format != DCS_FMT_94_T0;
-    const int nBands = fi.nBands < 16 ? fi.nBands : 16;
-    for (int band = 2 ; band < nBands ; ++band)
-    {
-        const DcsSplit &sp = fi.split[band - 1];
-        const int hb = si.header[band] & 0x7F;
-        int count = band == 15 ? 32 : 16, inc = 1;
-        if (hb & 0x40) { count /= 2; inc = 2; }
-        const int first = count - count / 2;            // samples in front of the middle
-        int outIdx = sp.state & 0x1FF;
-        uint32_t bits = sp.bitDelta;
-        bool straddle = false;
-        int code = fi.bandType[band];
-        if (code == 0)
-            outIdx += first;                            // (a band without a code moves on by the halved count, :1886)
-        else
-        {
-            if (type1)
-                code = code > 15 ? 17 : T.xlat94[(band < 3 ? 0 : band < 6 ? 16 : 32) + code] & 0xFF;
-            if (code == 0 || code > 16)
-            {
-                out = DcsFrameMids{};                   // (cannot happen in a frame without an error flag)
-                return;
-            }
-            if (code <= 6)
-            {
-                const int maxBits = T.cbInfo[code] & 0xF;
-                const uint16_t *book = T.cb94 + (T.cbInfo[code] >> 4);
-                WinBits r{ stream, len };
-                r.setPayload(2 + static_cast<size_t>(si.hdrLen));
-                r.skipRun(1, static_cast<int>(fi.bitOff + bits));
-                int i = count;
-                for ( ; i > count / 2 ; --i)
-                {
-                    const uint32_t e = book[r.look(maxBits)];
-                    r.consume(static_cast<int>((e >> 8) & 0x1F));
-                    if ((e >> 13) == 2 && i >= 2)
-                        --i;
-                }
-                straddle = i < count / 2;
-                bits = r.bitPos() - fi.bitOff;
-                outIdx += (count - i) * inc;
-            }
-            else
-            {
-                bits += static_cast<uint32_t>(first * code);
-                outIdx += first * inc;
-            }
-        }
-        out.mid[band] = (bits & 0xFFFFu) | (static_cast<uint32_t>((outIdx & 0x1FF) | (straddle ? DCS_MID15_STRADDLE : 0u)) << 16);
-    }
-    out.mid[0] = DCS_MIDS_VALID;
-}
-
+// The same walk with the mid records of its frames as a second output (DcsFrameMids, dcs_hip.h): the walker records the
+// middle of every band of 16 or 32 samples as it passes it (dcsScan94<MIDS>, dcs_scan.h), the rule of band 15's own record.
 extern "C" DcsStatus dcs_index_stream_mids(DcsOsVersion os, const uint8_t *stream, size_t len,
                                            DcsFrameIndex *out, uint32_t cap, DcsStreamInfo *info, DcsFrameMids *mids)
 {
-    DcsStreamInfo si;
-    const DcsStatus st = dcs_index_stream(os, stream, len, out, cap, &si);
-    if (info != nullptr)
-        *info = si;
-    if (mids == nullptr || out == nullptr || (st != DCS_OK && st != DCS_ERR_CAPACITY))
-        return st;
-    const uint32_t n = static_cast<uint32_t>(si.nValidFrames) < cap ? static_cast<uint32_t>(si.nValidFrames) : cap;
-    for (uint32_t f = 0 ; f < n ; ++f)
-        frameMids94(stream, len, si, out[f], mids[f]);
-    return st;
+    if (mids == nullptr || out == nullptr)
+        return dcs_index_stream(os, stream, len, out, cap, info);
+    MidsSink sink{ { out, cap }, mids };
+    return walkStream<true>(os, stream, len, WinBits{ stream, len }, sink, info);
 }
 
 // The same walk for a caller that uses the records as they come (the sequencer's background walker, dcs_sequencer.cpp): onFrame(f,
 // record) is called for every frame, in order, on the calling thread.  Same records, same summary as dcs_index_stream.
-namespace {
-struct CallbackSink
-{
-    const std::function<void(uint32_t, const DcsFrameIndex &)> &fn;
-    void operator()(uint32_t f, const DcsFrameIndex &fi) { fn(f, fi); }
-};
-}   // namespace
 DcsStatus dcsIndexStreamProgressive(DcsOsVersion os, const uint8_t *stream, size_t len, DcsStreamInfo *info,
                                     const std::function<void(uint32_t, const DcsFrameIndex &)> &onFrame)
 {
-    if (stream == nullptr || len < 3 || os < DCS_OS93A || os > DCS_OS95)
-        return DCS_ERR_INVALID_ARG;
-    WinBits reader{ stream, len };
-    const DcsScanTables tabs{ &dcsTables().lds, dcsTables().trie94, multi94Table(), dcsTables().fast94 };
     CallbackSink sink{ onFrame };
-    DcsScanMem mem;
-    const DcsStreamInfo si = dcsScanStream(static_cast<int>(os), reader, tabs, &mem, sink);
-    if (info != nullptr)
-        *info = si;
-    return si.nFrames == 0 ? DCS_ERR_BAD_STREAM : DCS_OK;
+    return walkStream(os, stream, len, WinBits{ stream, len }, sink, info);
 }
 
-// What a stream says about itself before any frame is walked: frame count, header, layout (the container part of the walk,
-// InitChannelStream / InitStreamPlayback, DCSDecoderNative.cpp:1433-1463, :1595-1641).  nBytes, nValidFrames and payloadBits are 0.
+// What a stream says about itself before any frame is walked: the container part of the walk (dcsContainer, dcs_scan.h).
 DcsStatus dcsStreamContainer(DcsOsVersion os, const uint8_t *stream, size_t len, DcsStreamInfo *info)
 {
     if (stream == nullptr || len < 3 || os < DCS_OS93A || os > DCS_OS95 || info == nullptr)
         return DCS_ERR_INVALID_ARG;
-    auto byteAt = [&](size_t i) -> uint32_t { return i < len ? stream[i] : 0u; };
-    DcsStreamInfo si = {};
-    si.nFrames = static_cast<int32_t>((byteAt(0) << 8) | byteAt(1));
-    const bool typeBit = (byteAt(2) & 0x80) != 0;
-    si.hdrLen = (os == DCS_OS93A && typeBit) ? 1 : 16;
-    for (int i = 0 ; i < 16 ; ++i)
-        si.header[i] = i < si.hdrLen ? static_cast<uint8_t>(byteAt(2 + static_cast<size_t>(i))) : static_cast<uint8_t>(0);
-    si.formatType = typeBit ? 1 : 0;
-    if (os == DCS_OS94 || os == DCS_OS95)
-        si.formatSubType = ((si.header[1] & 0x80) >> 6) | ((si.header[1] & 0x80) >> 7);
-    if (os == DCS_OS93A)
-        si.format = typeBit ? DCS_FMT_93A_T1 : DCS_FMT_93_T0;
-    else if (os == DCS_OS93B)
-        si.format = typeBit ? DCS_FMT_93B_T1 : DCS_FMT_93_T0;
-    else if (!typeBit)
-        si.format = DCS_FMT_94_T0;
-    else
-        si.format = (((si.header[1] | si.header[2]) & 0x80) == 0) ? DCS_FMT_94_T1_S0 : DCS_FMT_94_T1_S3;
-    *info = si;
-    return si.nFrames == 0 ? DCS_ERR_BAD_STREAM : DCS_OK;
+    *info = dcsContainer(static_cast<int>(os), HostFetch{ stream, len });
+    return info->nFrames == 0 ? DCS_ERR_BAD_STREAM : DCS_OK;
 }
 
 // Diagnostic: the same walk with the reader that keeps the reference's byte pointer LITERALLY (DcsBits, dcs_scan.h:
@@ -319,18 +243,8 @@ DcsStatus dcsStreamContainer(DcsOsVersion os, const uint8_t *stream, size_t len,
 extern "C" DcsStatus dcs_index_stream_literal(DcsOsVersion os, const uint8_t *stream, size_t len,
                                               DcsFrameIndex *out, uint32_t cap, DcsStreamInfo *info)
 {
-    if (stream == nullptr || len < 3 || os < DCS_OS93A || os > DCS_OS95 || (out == nullptr && cap != 0))
-        return DCS_ERR_INVALID_ARG;
-    DcsBits<HostFetch> reader{ HostFetch{ stream, len } };
-    const DcsScanTables tabs{ &dcsTables().lds, dcsTables().trie94, nullptr };
     ArraySink sink{ out, cap };
-    DcsScanMem mem;
-    const DcsStreamInfo si = dcsScanStream(static_cast<int>(os), reader, tabs, &mem, sink);
-    if (info != nullptr)
-        *info = si;
-    if (si.nFrames == 0)
-        return DCS_ERR_BAD_STREAM;
-    return sink.overflow ? DCS_ERR_CAPACITY : DCS_OK;
+    return walkStream(os, stream, len, DcsBits<HostFetch>{ HostFetch{ stream, len } }, sink, info);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -487,9 +401,10 @@ extern "C" int dcs_host_threads(void)
 
 // Stream k's records go to out + firstRecord[k]; it writes at most nFrames(k) of them (the U16 prefix
 // of the stream).  nThreads 0 = dcs_host_threads(), at most 64 and at most one per stream.
+// `mids`, when given, receives the mid records of stream k's frames at mids + firstRecord[k], from the same walk.
 // `done(k)`, when given, is called (on whichever pool thread indexed it) as soon as stream k's records are complete
 DcsStatus dcsIndexStreamsNotify(const DcsStreamRef *streams, uint32_t nStreams, int nThreads,
-                                DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos,
+                                DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos, DcsFrameMids *mids,
                                 const std::function<void(uint32_t)> *done)
 {
     if (streams == nullptr || out == nullptr || firstRecord == nullptr || infos == nullptr)
@@ -511,7 +426,8 @@ DcsStatus dcsIndexStreamsNotify(const DcsStreamRef *streams, uint32_t nStreams, 
         if (sr.data != nullptr && sr.len >= 3)
         {
             const uint32_t nf = (static_cast<uint32_t>(sr.data[0]) << 8) | sr.data[1];
-            st = dcs_index_stream(static_cast<DcsOsVersion>(sr.os), sr.data, sr.len, out + firstRecord[k], nf, &infos[k]);
+            st = dcs_index_stream_mids(static_cast<DcsOsVersion>(sr.os), sr.data, sr.len, out + firstRecord[k], nf, &infos[k],
+                                       mids != nullptr ? mids + firstRecord[k] : nullptr);
             if (st == DCS_ERR_BAD_STREAM)
                 st = DCS_OK;                // reported through infos[k].nFrames == 0
         }
@@ -534,21 +450,12 @@ DcsStatus dcsIndexStreamsNotify(const DcsStreamRef *streams, uint32_t nStreams, 
 extern "C" DcsStatus dcs_index_streams(const DcsStreamRef *streams, uint32_t nStreams, int nThreads,
                                        DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos)
 {
-    return dcsIndexStreamsNotify(streams, nStreams, nThreads, out, firstRecord, infos, nullptr);
+    return dcsIndexStreamsNotify(streams, nStreams, nThreads, out, firstRecord, infos, nullptr, nullptr);
 }
 
-// ... with the mid records of every stream's frames as a second output (dcs_index_stream_mids), made on the thread that walked it
+// ... with the mid records of every stream's frames as a second output (dcs_index_stream_mids; mids may be null)
 extern "C" DcsStatus dcs_index_streams_mids(const DcsStreamRef *streams, uint32_t nStreams, int nThreads,
                                             DcsFrameIndex *out, const uint64_t *firstRecord, DcsStreamInfo *infos, DcsFrameMids *mids)
 {
-    if (mids == nullptr)
-        return dcsIndexStreamsNotify(streams, nStreams, nThreads, out, firstRecord, infos, nullptr);
-    const std::function<void(uint32_t)> done = [&](uint32_t k) {
-        const DcsStreamRef &sr = streams[k];
-        if (sr.data == nullptr || sr.len < 3 || infos[k].nFrames == 0)
-            return;
-        for (int32_t f = 0 ; f < infos[k].nValidFrames ; ++f)
-            frameMids94(sr.data, sr.len, infos[k], out[firstRecord[k] + static_cast<uint64_t>(f)], mids[firstRecord[k] + static_cast<uint64_t>(f)]);
-    };
-    return dcsIndexStreamsNotify(streams, nStreams, nThreads, out, firstRecord, infos, &done);
+    return dcsIndexStreamsNotify(streams, nStreams, nThreads, out, firstRecord, infos, mids, nullptr);
 }

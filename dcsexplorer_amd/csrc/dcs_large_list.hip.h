@@ -207,7 +207,7 @@ DcsStatus dcsDecodeStreamsInParts(DcsCtx *ctx, const DcsStreamRef *streams, uint
             if (left[r].fetch_sub(1) == 1)
                 submitPart(r, walkRecs, firstRecord.data(), walkInfos);
         };
-        st = dcsIndexStreamsNotify(streams, walkStreams, idxThreads, walkRecs, firstRecord.data(), walkInfos, &walked);
+        st = dcsIndexStreamsNotify(streams, walkStreams, idxThreads, walkRecs, firstRecord.data(), walkInfos, nullptr, &walked);
         if (st == DCS_OK)
             st = static_cast<DcsStatus>(submitError.load());
     }

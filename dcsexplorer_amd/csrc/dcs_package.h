@@ -200,8 +200,8 @@ DCS_HDI constexpr bool dcsMid15(int format, int bpl, int nb16, uint32_t midBits)
 // stream codes; UNITS of 8 samples can: band 0 (7 samples), band 1, and the two halves of every later band (a strided band's
 // halved count still makes two halves).  A frame of nb header bands has dcsEvenUnits(nb) of them; lane q takes
 // dcsLaneUnits(nb, q).count consecutive ones from .first on: ceil(units / 8) or one fewer, in order.  A lane that starts with
-// a second half needs the decoder's state in the middle of that band: the mid records (DcsFrameMids, made by the host index
-// walk, dcs_index_stream_mids).  The symbol loop then runs in rounds of 8 samples.
+// a second half needs the decoder's state in the middle of that band: the mid records (DcsFrameMids, which the host index
+// walk records as it passes each middle: dcsScan94<MIDS>, through dcs_index_stream_mids).  The symbol loop then runs in rounds of 8 samples.
 // Today's deal stays for a frame with all sixteen bands (band 15's halves are 16 samples: units do no better than 32 there),
 // for one without mid records or in error, for the 1993 layouts and for the further sources of a frame.
 struct DcsUnitRange { int first, count; };

@@ -561,7 +561,7 @@ static DcsStatus pipelineDecode(DcsPipeline *p, DcsPipeline::Job *job, hipStream
                                            static_cast<uint32_t>(planned.srcs.size()), job->dRecords, job->dBlob.as<const uint8_t>(),
                                            job->hBlobLen, out);
             return createBatch(p->ctx, o, fromDevice ? job->hBlob.as<const uint8_t>() : built.blob.data(), fromDevice ? job->hBlobLen : built.blob.size(),
-                               built.srcs.data(), static_cast<uint32_t>(built.srcs.size()), built.jobs.data(), static_cast<uint32_t>(nJobs), nullptr, 0, out);
+                               built.srcs.data(), nullptr, static_cast<uint32_t>(built.srcs.size()), built.jobs.data(), static_cast<uint32_t>(nJobs), nullptr, 0, out);
         });
         // (DCS_PIPE_TRACE=3 waits for the kernels first, so that the thread log tells them from the copies)
         const double tk0 = nowMs();

@@ -947,9 +947,9 @@ static DcsStatus batchDone(DcsBatch *b, DcsStatus st, DcsBatch **out)
 // Plan and pack on the host: the chunk packages are built in pinned memory and uploaded
 static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
                              const uint8_t *blob, size_t blobLen,
-                             const DcsSrcDesc *srcs, uint32_t nSrcs,
+                             const DcsSrcDesc *srcs, const DcsFrameMids *mids, uint32_t nSrcs,
                              const DcsFrameJob *jobs, uint32_t nJobs,
-                             const int16_t *tailsIn, uint32_t nTailsIn, DcsBatch **out, const DcsFrameMids *mids = nullptr)
+                             const int16_t *tailsIn, uint32_t nTailsIn, DcsBatch **out)
 {
     if (out == nullptr || jobs == nullptr || nJobs == 0 || (nSrcs != 0 && (srcs == nullptr || blob == nullptr)))
         return DCS_ERR_INVALID_ARG;
@@ -1140,6 +1140,17 @@ static DcsStatus createBatchPlannedOnDevice(DcsCtx *ctx, BatchOptions o, const D
 // the planner's flag word of a batch planned on the device, once its stream has been waited for
 static uint32_t batchPlanFlag(const DcsBatch *b) { return *b->hStage.as<const volatile uint32_t>(); }
 
+// a resident batch (`mids`: the sources' mid records, or null)
+static DcsStatus createResident(DcsCtx *ctx, const uint8_t *blob, size_t blobLen, const DcsSrcDesc *srcs, const DcsFrameMids *mids, uint32_t nSrcs,
+                                const DcsFrameJob *jobs, uint32_t nJobs, const int16_t *tailsIn, uint32_t nTailsIn, DcsBatch **out)
+{
+    if (ctx == nullptr)
+        return DCS_ERR_INVALID_ARG;
+    BatchOptions o(ctx);
+    o.resident = true;
+    return createBatch(ctx, o, blob, blobLen, srcs, mids, nSrcs, jobs, nJobs, tailsIn, nTailsIn, out);
+}
+
 extern "C" DcsStatus dcs_batch_create(DcsCtx *ctx,
                                       const uint8_t *blob, size_t blobLen,
                                       const DcsSrcDesc *srcs, uint32_t nSrcs,
@@ -1147,11 +1158,7 @@ extern "C" DcsStatus dcs_batch_create(DcsCtx *ctx,
                                       const int16_t *tailsIn, uint32_t nTailsIn,
                                       DcsBatch **out)
 {
-    if (ctx == nullptr)
-        return DCS_ERR_INVALID_ARG;
-    BatchOptions o(ctx);
-    o.resident = true;
-    return createBatch(ctx, o, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, out);
+    return createResident(ctx, blob, blobLen, srcs, nullptr, nSrcs, jobs, nJobs, tailsIn, nTailsIn, out);
 }
 
 extern "C" DcsStatus dcs_batch_create_mids(DcsCtx *ctx,
@@ -1161,11 +1168,7 @@ extern "C" DcsStatus dcs_batch_create_mids(DcsCtx *ctx,
                                            const int16_t *tailsIn, uint32_t nTailsIn,
                                            DcsBatch **out)
 {
-    if (ctx == nullptr)
-        return DCS_ERR_INVALID_ARG;
-    BatchOptions o(ctx);
-    o.resident = true;
-    return createBatch(ctx, o, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, out, mids);
+    return createResident(ctx, blob, blobLen, srcs, mids, nSrcs, jobs, nJobs, tailsIn, nTailsIn, out);
 }
 
 // Two chunks per wavefront (dcsDecodeKernel<8, 2>) where the chunks make more than one and at most two generations of the chip's
@@ -1182,6 +1185,16 @@ static bool twoChunksPerWave(int fpw, int mode, bool solo, uint32_t nChunks, uin
     return solo && !(flags & DCS_BATCH_XCD_RANGES) && nChunks > cus * 16u && nChunks <= cus * 32u;
 }
 
+// the launch itself, of one kernel instantiation (`flags`: the batch's with the launch's own)
+template <int FPW, int CPW, bool EVEN>
+static hipError_t launchVariant(const DcsKernelArgs &args, uint32_t flags, uint32_t blocks, hipStream_t stream)
+{
+    dcsk::dcsDecodeKernel<FPW, CPW, EVEN><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
+        args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
+        args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
+    return hipGetLastError();
+}
+
 template <int FPW>
 static hipError_t launch(const DcsKernelArgs &args, hipStream_t stream, int numCUs, int cpwMode, bool solo)
 {
@@ -1196,32 +1209,15 @@ static hipError_t launch(const DcsKernelArgs &args, hipStream_t stream, int numC
     uint32_t flags = args.flags;
     if (waves > cus * 4u && cus % 8u == 0 && cus / 8u < 256u)
         flags |= DCS_BATCH_PACED | ((cus / 8u) << DCS_BATCH_CUS8_SHIFT);
+    // (two chunks per wavefront and the even deal exist for 8 frames per wavefront only)
     if constexpr (FPW == 8)
     {
         if (flags & DCS_BATCH_EVEN_DEAL)
-        {
-            if (two)
-                dcsk::dcsDecodeKernel<FPW, 2, true><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
-                    args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
-                    args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
-            else
-                dcsk::dcsDecodeKernel<FPW, 1, true><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
-                    args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
-                    args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
-            return hipGetLastError();
-        }
+            return two ? launchVariant<8, 2, true>(args, flags, blocks, stream) : launchVariant<8, 1, true>(args, flags, blocks, stream);
         if (two)
-        {
-            dcsk::dcsDecodeKernel<FPW, 2><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
-                args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
-                args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
-            return hipGetLastError();
-        }
+            return launchVariant<8, 2, false>(args, flags, blocks, stream);
     }
-    dcsk::dcsDecodeKernel<FPW><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
-        args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
-        args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
-    return hipGetLastError();
+    return launchVariant<FPW, 1, false>(args, flags, blocks, stream);
 }
 
 // one launch, without the completion event (the callers below record it once per call)
@@ -1745,7 +1741,7 @@ extern "C" DcsStatus dcs_decode_batch(DcsCtx *ctx,
     BatchOptions o(ctx);
     o.keepAllTails = tailsOut != nullptr;
     DcsBatch *b = nullptr;
-    DcsStatus st = createBatch(ctx, o, blob, blobLen, srcs, nSrcs, jobs, nJobs, tailsIn, nTailsIn, &b);
+    DcsStatus st = createBatch(ctx, o, blob, blobLen, srcs, nullptr, nSrcs, jobs, nJobs, tailsIn, nTailsIn, &b);
     if (st != DCS_OK)
         return st;
     st = dcs_batch_run(b, nullptr);

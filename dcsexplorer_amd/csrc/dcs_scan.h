@@ -90,6 +90,7 @@ struct DcsScanMem
     uint8_t header[16];
     uint16_t bandType[16];
     DcsFrameIndex fi;
+    DcsFrameMids mids;              // the frame's mid records: written by a MIDS walk only (dcsScanStream)
 };
 
 template <class R>
@@ -168,9 +169,28 @@ DCS_HD inline void dcsPutMid15(DcsFrameIndex &fi, uint32_t frameStart, const Dcs
     sp.prvDelta = static_cast<uint16_t>((outIdx & 0x1FF) | (straddle ? DCS_MID15_STRADDLE : 0u));
 }
 
-// --- 1994+ frame (:1679-2261) -----------------------------------------------------------------
+// The same state for any band from 2 on, as a word of the frame's DcsFrameMids (dcs_hip.h): bits | (output index | straddle) << 16
 template <class R>
-DCS_HD void dcsScan94(DcsScan<R> &s, const DcsScanTables &tabs, DcsFrameIndex &fi)
+DCS_HD inline uint32_t dcsMidWord(uint32_t frameStart, const DcsScan<R> &s, int outIdx, bool straddle)
+{
+    return ((s.b.bitPos() - frameStart) & 0xFFFFu) | (static_cast<uint32_t>((outIdx & 0x1FF) | (straddle ? DCS_MID15_STRADDLE : 0u)) << 16);
+}
+
+// the middle of `band`, reached: into the record for band 15, into `mid` for every band of a MIDS walk
+template <bool MIDS, class R>
+DCS_HD inline void dcsPutMid(DcsFrameIndex &fi, uint32_t *mid, int band, uint32_t frameStart, const DcsScan<R> &s, int outIdx, bool straddle)
+{
+    if (band == 15)
+        dcsPutMid15(fi, frameStart, s, outIdx, straddle);
+    if constexpr (MIDS)
+        mid[band] = dcsMidWord(frameStart, s, outIdx, straddle);
+}
+
+// --- 1994+ frame (:1679-2261) -----------------------------------------------------------------
+// MIDS (host walks that make mid records, dcs_index_stream_mids): the middle of every band from 2 on goes into mid[band];
+// without it `mid` is not touched
+template <bool MIDS, class R>
+DCS_HD void dcsScan94(DcsScan<R> &s, const DcsScanTables &tabs, DcsFrameIndex &fi, uint32_t *mid)
 {
     const DcsLdsTables &T = *tabs.lds;
     const uint16_t *trie94 = tabs.trie94;
@@ -203,9 +223,16 @@ DCS_HD void dcsScan94(DcsScan<R> &s, const DcsScanTables &tabs, DcsFrameIndex &f
         int count = band == 0 ? 7 : band == 1 ? 8 : band == 15 ? 32 : 16;      // :1848-1850
         int inc = 1;
         if (hb & 0x40) { count /= 2; inc = 2; }
+        // Band 15 is twice as long as the others: it is walked in two halves, and where the second one starts -- the first
+        // code boundary with at least half of the samples done -- is recorded, so that two lanes can share the band
+        // (dcsPutMid15).  A MIDS walk does so for every band from 2 on (the even deal, dcs_package.h); other bands are one piece.
+        const bool halves = band == 15 || (MIDS && band >= 2);
         int code = s.bandType[band];
         if (code == 0)
         {
+            if constexpr (MIDS)
+                if (halves)
+                    mid[band] = dcsMidWord(frameStart, s, outIdx + (count - count / 2), false);
             outIdx += count;                            // the halved count (:1886)
             continue;
         }
@@ -225,10 +252,7 @@ DCS_HD void dcsScan94(DcsScan<R> &s, const DcsScanTables &tabs, DcsFrameIndex &f
             const int maxBits = T.cbInfo[code] & 0xF;
             const uint16_t *book = T.cb94 + (T.cbInfo[code] >> 4);
             int i = count;
-            // Band 15 is twice as long as the others: its samples are walked in two halves, and where the second one
-            // starts -- the first code boundary with at least half of the samples done -- is recorded, so that two lanes
-            // can share the band (dcsPutMid15).  Every other band is one piece.
-            for (int piece = band == 15 ? 0 : 1 ; piece < 2 ; ++piece)
+            for (int piece = halves ? 0 : 1 ; piece < 2 ; ++piece)
             {
                 const int lim = piece == 0 ? count / 2 : 0;         // samples left when the piece is done
                 // several codes per look while more samples remain than the look covers (so that the "two zeros with one
@@ -257,13 +281,13 @@ DCS_HD void dcsScan94(DcsScan<R> &s, const DcsScanTables &tabs, DcsFrameIndex &f
                     }
                 }
                 if (piece == 0)
-                    dcsPutMid15(fi, frameStart, s, outIdx - i * inc, i < lim);
+                    dcsPutMid<MIDS>(fi, mid, band, frameStart, s, outIdx - i * inc, i < lim);
             }
         }
-        else if (band == 15)
+        else if (halves)
         {
             s.b.skipRun(count - count / 2, code);
-            dcsPutMid15(fi, frameStart, s, outIdx - (count / 2) * inc, false);
+            dcsPutMid<MIDS>(fi, mid, band, frameStart, s, outIdx - (count / 2) * inc, false);
             s.b.skipRun(count / 2, code);
         }
         else
@@ -441,54 +465,62 @@ DCS_HD void dcsScan93a(DcsScan<R> &s, const DcsScanTables &tabs, DcsFrameIndex &
 }
 
 
+// What a stream says about itself before any frame is walked: frame count, header, layout (InitChannelStream :1433-1463,
+// InitStreamPlayback :1595-1641).  byteAt(i) = byte i of the stream (0 past its end).  nBytes, nValidFrames and payloadBits are 0.
+template <class ByteAt>
+DCS_HD DcsStreamInfo dcsContainer(int os, ByteAt byteAt)
+{
+    DcsStreamInfo si = {};
+    si.nFrames = static_cast<int32_t>((byteAt(0) << 8) | byteAt(1));
+    const bool typeBit = (byteAt(2) & 0x80) != 0;
+    si.hdrLen = (os == DCS_OS93A && typeBit) ? 1 : 16;
+    for (int i = 0 ; i < 16 ; ++i)
+        si.header[i] = i < si.hdrLen ? static_cast<uint8_t>(byteAt(2 + static_cast<size_t>(i))) : static_cast<uint8_t>(0);
+    si.formatType = typeBit ? 1 : 0;
+    if (os == DCS_OS94 || os == DCS_OS95)       // sic: GetStreamInfo tests header[1] twice (:1517)
+        si.formatSubType = ((si.header[1] & 0x80) >> 6) | ((si.header[1] & 0x80) >> 7);
+    if (os == DCS_OS93A)
+        si.format = typeBit ? DCS_FMT_93A_T1 : DCS_FMT_93_T0;
+    else if (os == DCS_OS93B)
+        si.format = typeBit ? DCS_FMT_93B_T1 : DCS_FMT_93_T0;
+    else if (!typeBit)
+        si.format = DCS_FMT_94_T0;
+    else
+        si.format = (((si.header[1] | si.header[2]) & 0x80) == 0) ? DCS_FMT_94_T1_S0 : DCS_FMT_94_T1_S3;
+    return si;
+}
+
 // Walk one stream.  `sink(f, record)` receives every indexed frame.  Returns the stream summary.
-template <class R, class Sink>
+// MIDS: the walk also records the middle of every 1994+ band from 2 on (dcsScan94) and the sink is called as
+// sink(f, record, mids): mid[0] = DCS_MIDS_VALID for a 1994+ frame without an error flag, all zero for any other frame
+// (a frame with an error flag is never split, a 1993 frame has no even deal).
+template <bool MIDS = false, class R, class Sink>
 DCS_HD DcsStreamInfo dcsScanStream(int os, R reader, const DcsScanTables &tabs, DcsScanMem *mem, Sink &sink)
 {
     DcsScan<R> s{ reader, mem->header, mem->bandType };
 
-    // container (InitChannelStream :1433-1463, InitStreamPlayback :1595-1641)
-    const int nFrames = static_cast<int>((s.b.byteAt(0) << 8) | s.b.byteAt(1));
-    const bool typeBit = (s.b.byteAt(2) & 0x80) != 0;
-    const int hdrLen = (os == DCS_OS93A && typeBit) ? 1 : 16;
+    DcsStreamInfo si = dcsContainer(os, [&s](size_t i) { return s.b.byteAt(i); });
+    const int nFrames = si.nFrames, format = si.format;
     for (int i = 0 ; i < 16 ; ++i)
     {
-        s.header[i] = i < hdrLen ? static_cast<uint8_t>(s.b.byteAt(2 + static_cast<size_t>(i))) : static_cast<uint8_t>(0);
+        s.header[i] = si.header[i];
         s.bandType[i] = 0;
     }
-    s.b.setPayload(2 + static_cast<size_t>(hdrLen));
+    s.b.setPayload(2 + static_cast<size_t>(si.hdrLen));
     s.nBands = 0;
-    if (os == DCS_OS93A && typeBit)
+    if (format == DCS_FMT_93A_T1)
         s.nBands = s.header[0] & 0x1F;
     else
         while (s.nBands < 16 && (s.header[s.nBands] & 0x7F) != 0x7F)
             ++s.nBands;
-
-    int format;
-    if (os == DCS_OS93A)
-        format = typeBit ? DCS_FMT_93A_T1 : DCS_FMT_93_T0;
-    else if (os == DCS_OS93B)
-        format = typeBit ? DCS_FMT_93B_T1 : DCS_FMT_93_T0;
-    else if (!typeBit)
-        format = DCS_FMT_94_T0;
-    else
-        format = (((s.header[1] | s.header[2]) & 0x80) == 0) ? DCS_FMT_94_T1_S0 : DCS_FMT_94_T1_S3;
-
-    DcsStreamInfo si = {};
-    si.nFrames = nFrames;
-    si.formatType = typeBit ? 1 : 0;
-    if (os == DCS_OS94 || os == DCS_OS95)       // sic: GetStreamInfo tests header[1] twice (:1517)
-        si.formatSubType = ((s.header[1] & 0x80) >> 6) | ((s.header[1] & 0x80) >> 7);
-    for (int i = 0 ; i < 16 ; ++i)
-        si.header[i] = s.header[i];
-    si.format = format;
-    si.hdrLen = hdrLen;
 
     int valid = 0;
     for (int f = 0 ; f < nFrames ; ++f)
     {
         DcsFrameIndex &fi = mem->fi;
         fi = DcsFrameIndex{};
+        if constexpr (MIDS)
+            mem->mids = DcsFrameMids{};
         const uint32_t frameBit = s.b.bitPos();
         fi.bitOff = frameBit;
         fi.nBands = static_cast<uint8_t>(s.nBands);
@@ -498,11 +530,20 @@ DCS_HD DcsStreamInfo dcsScanStream(int os, R reader, const DcsScanTables &tabs, 
         case DCS_FMT_93_T0:
         case DCS_FMT_93B_T1: dcsScan93(s, tabs, fi); break;
         case DCS_FMT_93A_T1: dcsScan93a(s, tabs, fi); break;
-        default:             dcsScan94(s, tabs, fi); break;
+        default:             dcsScan94<MIDS>(s, tabs, fi, mem->mids.mid); break;
         }
         fi.nBits = static_cast<uint16_t>(s.b.bitPos() - frameBit);
         fi.flags = static_cast<uint8_t>((s.err << 4) | (s.err != 0 ? DCS_IDX_SERIAL : 0));
-        sink(static_cast<uint32_t>(valid), fi);
+        if constexpr (MIDS)
+        {
+            if (s.err != 0)
+                mem->mids = DcsFrameMids{};
+            else if (format >= DCS_FMT_94_T0)
+                mem->mids.mid[0] = DCS_MIDS_VALID;
+            sink(static_cast<uint32_t>(valid), fi, mem->mids);
+        }
+        else
+            sink(static_cast<uint32_t>(valid), fi);
         ++valid;
         si.payloadBits = s.b.bitPos();
         if (s.err != 0)

@@ -84,7 +84,7 @@ static DcsStatus transcodeDecodeOnHost(DcsCtx *ctx, const DcsStreamRef *refs, ui
         return st;
     d.firstJob = d.built.firstJob;
     BatchOptions o(ctx);
-    st = createBatch(ctx, o, d.built.blob.data(), d.built.blob.size(), d.built.srcs.data(), static_cast<uint32_t>(d.built.srcs.size()),
+    st = createBatch(ctx, o, d.built.blob.data(), d.built.blob.size(), d.built.srcs.data(), nullptr, static_cast<uint32_t>(d.built.srcs.size()),
                      d.built.jobs.data(), static_cast<uint32_t>(d.built.jobs.size()), nullptr, 0, &d.batch);
     return st != DCS_OK ? st : dcs_batch_run(d.batch, nullptr);
 }
