@@ -204,7 +204,7 @@ ABI_VERSION = 9                 # include/dcs_hip.h DCS_ABI_VERSION these bindin
 
 EXPORTS = [
     "dcs_index_stream_mids", "dcs_index_streams_mids", "dcs_batch_create_mids", "dcs_ctx_set_even_deal", "dcs_batch_even_deal",
-    "dcs_pack_chunks_mids", "dcs_even_deal_lane",
+    "dcs_pack_chunks_mids", "dcs_even_deal_lane", "dcs_ctx_set_sole_source_kernel", "dcs_batch_sole_source_kernel",
     "dcs_abi_version", "dcs_build_id", "dcs_index_stream", "dcs_volume_multiplier", "dcs_mixing_multiplier", "dcs_frame_scale",
     "dcs_stream_params", "dcs_ctx_create", "dcs_ctx_destroy", "dcs_last_error", "dcs_device_count", "dcs_runtime_defaults", "dcs_ctx_set_batch_tails", "dcs_batch_package_bytes",
     "dcs_ctx_set_frames_per_wave", "dcs_ctx_set_tail_handoff", "dcs_ctx_set_large_list_path", "dcs_ctx_set_concurrent_batches", "dcs_ctx_set_cache_limits", "dcs_ctx_trim_cache", "dcs_ctx_cache_bytes", "dcs_plan_chunks2", "dcs_decode_batch", "dcs_batch_create", "dcs_batch_destroy", "dcs_batch_run", "dcs_batch_run_many", "dcs_pack_chunks",
@@ -340,6 +340,11 @@ def load_library():
         L.dcs_pack_chunks_mids.argtypes = [vp, u32, vp, vp, vp, sz, ctypes.c_int, vp, sz, ctypes.POINTER(u32), ctypes.POINTER(u32)]
         L.dcs_even_deal_lane.restype = None
         L.dcs_even_deal_lane.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3
+    if hasattr(L, "dcs_ctx_set_sole_source_kernel"):    # (DCS_HIP_LIB may name a build from before there were these kernels: A/B against it)
+        L.dcs_ctx_set_sole_source_kernel.restype = i32
+        L.dcs_ctx_set_sole_source_kernel.argtypes = [vp, ctypes.c_int]
+        L.dcs_batch_sole_source_kernel.restype = ctypes.c_int
+        L.dcs_batch_sole_source_kernel.argtypes = [vp]
     L.dcs_batch_destroy.restype = None
     L.dcs_batch_destroy.argtypes = [vp]
     L.dcs_batch_run.restype = i32
@@ -1353,6 +1358,11 @@ class Context:
         0 whole bands, 1 units of 8 samples wherever the batch allows it, -1 (default) units where some frame gains."""
         _check(self.L.dcs_ctx_set_even_deal(self.h, mode), self.h)
 
+    def set_sole_source_kernel(self, mode):
+        """The kernel of an even-deal batch none of whose jobs has a second source: -1 (default) the instantiation without the
+        rounds of further sources, 0 never.  Read at every launch."""
+        _check(self.L.dcs_ctx_set_sole_source_kernel(self.h, mode), self.h)
+
     def set_frames_per_chunk(self, frames):
         _check(self.L.dcs_ctx_set_frames_per_chunk(self.h, frames), self.h)
 
@@ -1944,6 +1954,11 @@ class Batch:
     def even_deal(self):
         """the batch's packages deal 1994+ frames in units of 8 samples (Context.set_even_deal)"""
         return bool(self.L.dcs_batch_even_deal(self.h))
+
+    @property
+    def sole_source_kernel(self):
+        """the batch's next launch runs the even-deal kernel without the rounds of further sources (Context.set_sole_source_kernel)"""
+        return bool(self.L.dcs_batch_sole_source_kernel(self.h))
 
     @property
     def chunks_per_wave(self):

@@ -145,6 +145,9 @@ struct DcsKernelArgs
 // the packages deal 1994+ frames to their eight unpack lanes in units of 8 samples (dcs_package.h: the even deal), and the symbol
 // loop runs in rounds of 8 samples (8 frames per wavefront, first source)
 #define DCS_BATCH_EVEN_DEAL 8u
+// no job of the batch has a second source (classifyJobs): with the even deal, the launch may take the kernels without the rounds of
+// further sources (dcsDecodeKernel<8, CPW, true, true>; dcs_ctx_set_sole_source_kernel)
+#define DCS_BATCH_SOLE_SOURCE 16u
 #define DCS_BATCH_IMG_SHIFT 16          // bits 16..31: the packages' layout word (image dwords | DCS_PKG_SPLIT4; dcsPkgStride)
 #define DCS_BATCH_IMG_MASK  0xFFFFu
 

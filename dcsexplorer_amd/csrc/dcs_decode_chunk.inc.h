@@ -72,11 +72,21 @@
     // phase 2.  (Requesting them with the first loads of the kernel, which a batch flag could allow when every job runs
     // the same transform, makes that first round trip longer: 4 % slower on the 4 096-frame batch.)
     // (a wavefront's second chunk keeps the first one's while the family stays the same)
-    const int firstXform = __builtin_amdgcn_readfirstlane(static_cast<int>(slot.shiftXform >> 4)) == DCS_XFORM_94 ? DCS_XFORM_94 : DCS_XFORM_93;
-    if (PASS == 0 || firstXform != constsXform)
+    // (SOLE, an even-deal kernel: every job of the batch runs the 1994+ transform -- createBatch sets DCS_BATCH_EVEN_DEAL for no
+    // other -- so the constants are the wavefront's, requested with its first chunk)
+    if constexpr (SOLE)
     {
-        constsXform = firstXform;
-        loadLaneConsts(a.tables, lane, constsXform, C);
+        if (PASS == 0)
+            loadLaneConsts(a.tables, lane, DCS_XFORM_94, C);
+    }
+    else
+    {
+        const int firstXform = __builtin_amdgcn_readfirstlane(static_cast<int>(slot.shiftXform >> 4)) == DCS_XFORM_94 ? DCS_XFORM_94 : DCS_XFORM_93;
+        if (PASS == 0 || firstXform != constsXform)
+        {
+            constsXform = firstXform;
+            loadLaneConsts(a.tables, lane, constsXform, C);
+        }
     }
     // the bit pool of round 0: a straight copy of the package's image
 #pragma unroll
@@ -120,7 +130,10 @@
             const int bplSlot = slot.bpl;
             if (R0)
             {
-                if (has) { d0 = pd0; d1 = pd1; d2 = pd2; sp = psplit; }
+                // (SOLE: taken as they are.  Both packers write a slot without a source -- a padding slot, a silent job -- as zeros
+                // in all of these, dcsPkgSlotEntry and dcsLaneSplit in dcs_package.h; only hdrLen below wants something else)
+                if constexpr (SOLE) { d0 = pd0; d1 = pd1; d2 = pd2; sp = psplit; }
+                else if (has) { d0 = pd0; d1 = pd1; d2 = pd2; sp = psplit; }
             }
             else if (has) { d0 = sdp[0]; d1 = sdp[1]; d2 = *reinterpret_cast<const uint2 *>(sdp + 2); }
             // DcsSrcDesc: [0] streamOff lo, [1] streamOff hi, [2] mixMul | format<<16 | hdrLen<<24,
@@ -213,7 +226,8 @@
             // the stream header: 16 bytes at streamOff + 2 (round 0: from the package, aligned and masked there)
             if (R0)
             {
-                Q.h0 = has ? phdr.x : 0u; Q.h1 = has ? phdr.y : 0u; Q.h2 = has ? phdr.z : 0u; Q.h3 = has ? phdr.w : 0u;
+                if constexpr (SOLE) { Q.h0 = phdr.x; Q.h1 = phdr.y; Q.h2 = phdr.z; Q.h3 = phdr.w; }      // (zeros, as above)
+                else { Q.h0 = has ? phdr.x : 0u; Q.h1 = has ? phdr.y : 0u; Q.h2 = has ? phdr.z : 0u; Q.h3 = has ? phdr.w : 0u; }
             }
             else
             {
@@ -346,6 +360,11 @@
                     : 0u;
                 err |= unpack94<R0, BR94, SUB, evenDeal>(T, row, br, Q, format, mixMul, is94, stamp, planAt);
             }
+            // (SOLE, an even-deal kernel: every source of the batch is a 1994+ frame, createBatch sets DCS_BATCH_EVEN_DEAL for no
+            // other; no 1993-family code.  The even-deal kernels of batches with a second source keep it: every cut of it tried
+            // sent one of them to scratch memory, profiles/NOTES.md 57)
+            if constexpr (!SOLE)
+            {
             BR93 br;
             br.init(brAt, brBit);
             if (__any(is93))
@@ -379,14 +398,17 @@
                     }
                 }
             }
+            }
             waveSync();
         };
 
         {
             if (__any(myNSrc > 0))
                 unpackRound(std::true_type{}, 0);
-            for (int r = 1 ; __any(r < myNSrc) ; ++r)
-                unpackRound(std::false_type{}, r);
+            // (SOLE: no job of the batch has a second source, and the rounds of further sources are not instantiated)
+            if constexpr (!SOLE)
+                for (int r = 1 ; __any(r < myNSrc) ; ++r)
+                    unpackRound(std::false_type{}, r);
         }
 
         DCS_STAMP(4);
@@ -399,8 +421,9 @@
         }
         if (live && q == 0)
         {
-            if (job.xform == DCS_XFORM_93)
-                dcMagnitude93(row);
+            if constexpr (!SOLE)
+                if (job.xform == DCS_XFORM_93)
+                    dcMagnitude93(row);
             if (!(slot.flags & DCS_SLOT_HALO) && a.err != nullptr)
                 a.err[slot.job] = err;
         }
@@ -420,18 +443,25 @@
     const int jobXform = job.xform, jobPrev = static_cast<int>(job.prev);
 
 
-    const unsigned long long slots94 = __ballot(live && lane < FPW && jobXform == DCS_XFORM_94);
-    const bool oneXform = slots94 == 0 || slots94 == __ballot(live && lane < FPW);
-    for (int s0 = 0 ; s0 < nSlots ; )
+    // (SOLE, an even-deal kernel: eight slots at most, all of them 1994+ transforms, are ONE pass of eight frames: the loop's body
+    // as straight-line code, no run lengths and no look at the jobs' transforms.  A chunk without a live slot -- the planner makes
+    // none -- would run it with no lane group active and store nothing.)
+    constexpr bool kOnePass = SOLE;
+    static_assert(!kOnePass || (EVEN && FPW == 8), "the even deal: 8 frames per wavefront, one transform pass of 8");
+    const unsigned long long slots94 = kOnePass ? 0ull : __ballot(live && lane < FPW && jobXform == DCS_XFORM_94);
+    const bool oneXform = kOnePass || slots94 == 0 || slots94 == __ballot(live && lane < FPW);
+    for (int s0 = 0 ; kOnePass || s0 < nSlots ; )
     {
         // a pass takes the run of slots from s0 on that want the same transform (8 frames at most for 1994+, 4 for 1993)
-        const int xf = __builtin_amdgcn_readlane(jobXform, s0);
+        const int xf = kOnePass ? DCS_XFORM_94 : __builtin_amdgcn_readlane(jobXform, s0);
         const int G = (xf == DCS_XFORM_94) ? 8 : 4;
 #ifndef DCS_RUN_BALLOT_MIN_FPW
 #define DCS_RUN_BALLOT_MIN_FPW 8
 #endif
         int n = 1;
-        if constexpr (FPW >= DCS_RUN_BALLOT_MIN_FPW)
+        if constexpr (kOnePass)
+            n = nSlots;
+        else if constexpr (FPW >= DCS_RUN_BALLOT_MIN_FPW)
         {
             // the run length as a count of trailing zeros over a ballot
             const unsigned long long sameXf = (xf == DCS_XFORM_94) ? slots94 : ~slots94;
@@ -446,11 +476,12 @@
                 ++n;
         }
 
-        if (xf != constsXform)
-        {
-            constsXform = xf;                       // a chunk that mixes decoders of both families
-            loadLaneConsts(a.tables, lane, constsXform, C);
-        }
+        if constexpr (!kOnePass)
+            if (xf != constsXform)
+            {
+                constsXform = xf;                       // a chunk that mixes decoders of both families
+                loadLaneConsts(a.tables, lane, constsXform, C);
+            }
         const int lpfShift = (xf == DCS_XFORM_94) ? 3 : 4;
         const int g = lane >> lpfShift;
         const bool active = g < n;
@@ -490,7 +521,9 @@
         R.k8000 = 0x8000u; R.k10000 = 0x10000u; R.watch = 0xFFFFu;
         R.k4000 = 0x4000u; R.watchB = 0x7FFF7FFFu;
         asm volatile("" : "+v"(R.k8000), "+v"(R.k10000), "+v"(R.k4000));    // keep them in vector registers (VOP3 takes no literal operand)
-        if (xf == DCS_XFORM_94)
+        if constexpr (kOnePass)
+            transform94x8<kPace.levels>(P, W, C, R, x);
+        else if (xf == DCS_XFORM_94)
             transform94x8<kPace.levels>(P, W, C, R, x);
         else
             transform93x4<kPace.levels>(P, W, C, R, x);
@@ -542,7 +575,7 @@
         // row first and storing 16 bytes per lane -- 2 resp. 4 store instructions -- was measured twice: 5 % slower, the
         // extra LDS round trip is on the critical path and the narrow stores are not.  Swapping registers r and r + 8
         // with lane l ^ 8 by DPP and storing sample PAIRS, 8 stores instead of 15 for a 1993 frame: no difference.)
-        if (xf == DCS_XFORM_94)
+        if (kOnePass || xf == DCS_XFORM_94)
         {
             // overlap-add on sample pair m = bitrev3(l) (register 0) (:538-555)
             uint32_t tailPair = tails[(hasPrev ? myPrevSlot : mySlot) * 8 + lr];
@@ -583,7 +616,7 @@
                           overlapMix(imC(theirs), C.k[DCS_K94_OVLA] >> 16, imC(x[15]), C.k[DCS_K94_OVLB] >> 16));
             }
         }
-        else
+        else if constexpr (!kOnePass)
         {
             // overlap-add on sample i = bitrev4(l) (register 0) (:789-802)
             int tailSample = static_cast<int16_t>(reinterpret_cast<const uint16_t *>(tails)[(hasPrev ? myPrevSlot : mySlot) * 16 + lr]);
@@ -616,6 +649,8 @@
         }
         waveSync();
         s0 += n;
+        if constexpr (kOnePass)
+            break;
     }
 
     DCS_STAMP(6);

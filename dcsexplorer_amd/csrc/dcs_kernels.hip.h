@@ -1579,8 +1579,12 @@ __host__ __device__ constexpr PaceSchedule paceSchedule(int cpw, int pass)
 }
 
 // EVEN: the packages of the batch carry the even deal of 1994+ frames (DCS_BATCH_EVEN_DEAL, dcs_package.h; 8 frames per wavefront):
-// a kernel of its own, so that the others are what they were
-template <int FPW, int CPW = 1, bool EVEN = false>
+// a kernel of its own, so that the others are what they were.
+// SOLE (with EVEN only): no job of the batch has a second source (DCS_BATCH_SOLE_SOURCE).  The unpack rounds of further sources
+// -- their staging loop, their set-up in front of the loop's first test, the registers held for them -- are not in the kernel;
+// and as an even-deal batch has 1994+ sources and 1994+ transforms only (createBatch), neither is any code of the 1993 family,
+// and the chunk's one transform pass is straight-line code (dcs_decode_chunk.inc.h).
+template <int FPW, int CPW = 1, bool EVEN = false, bool SOLE = false>
 #ifndef DCS_MIN_WAVES
 #define DCS_MIN_WAVES 4
 #endif
@@ -1609,6 +1613,7 @@ dcsDecodeKernel(uint8_t *kPackages, const DcsDevTables *kTables, uint32_t kNChun
     if (a.flags & DCS_BATCH_XCD_RANGES)
         blk = (blk & 7u) * (gridDim.x >> 3) + (blk >> 3);
     static_assert(CPW == 1 || CPW == 2, "one or two chunks per wavefront");
+    static_assert((!EVEN || FPW == 8) && (!SOLE || EVEN), "the even deal: 8 frames per wavefront; SOLE: an even-deal kernel");
     const uint32_t wv = blk * kWavesPerBlock + static_cast<uint32_t>(wave);         // this wavefront's first chunk
     const uint32_t nFirst = CPW == 2 ? (a.nChunks + 1u) >> 1 : a.nChunks;           // wavefronts that have one
     auto stamperOf = [&](uint32_t chunk, bool valid)

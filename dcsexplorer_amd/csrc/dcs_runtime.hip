@@ -30,6 +30,7 @@ struct DcsCtx
     DcsDevTables *dTables = nullptr;
     int fpwOverride = 0;
     int cpwOverride = 0;                // chunks per wavefront of a decode launch: 0 = by the launch's size (twoChunksPerWave), 1, 2
+    int soleKernel = -1;                // launches of even-deal batches without a second source: -1 the kernels without further-source rounds, 0 never
     int evenDeal = -1;                  // the deal of 1994+ frames in batches given mid records: 0 whole bands, 1 units, -1 units where a frame gains
     bool handoff = true;                // tails cross chunk boundaries through the hand-off buffer (else: halo re-decode)
     uint32_t shuffleSeed = 0;           // test hook: host-planned batches get their chunks in a seeded random order (dcs_ctx_set_test_hooks)
@@ -584,6 +585,14 @@ extern "C" DcsStatus dcs_ctx_set_even_deal(DcsCtx *ctx, int mode)
     return DCS_OK;
 }
 
+extern "C" DcsStatus dcs_ctx_set_sole_source_kernel(DcsCtx *ctx, int mode)
+{
+    if (ctx == nullptr || mode < -1 || mode > 0)
+        return DCS_ERR_INVALID_ARG;
+    ctx->soleKernel = mode;
+    return DCS_OK;
+}
+
 extern "C" DcsStatus dcs_ctx_set_frames_per_chunk(DcsCtx *ctx, int frames)
 {
     if (ctx == nullptr || frames < 0 || frames > 16)
@@ -994,6 +1003,8 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
         if (ctx->evenDeal == 1 || (gaining != 0 && 2u * gaining >= nSrcs))
             b->flags |= DCS_BATCH_EVEN_DEAL;
     }
+    if (!kinds.multi)
+        b->flags |= DCS_BATCH_SOLE_SOURCE;
     const DcsFrameMids *packMids = (b->flags & DCS_BATCH_EVEN_DEAL) ? mids : nullptr;
 
     CacheBuf hPackages;                         // pinned staging for the chunk packages
@@ -1186,17 +1197,24 @@ static bool twoChunksPerWave(int fpw, int mode, bool solo, uint32_t nChunks, uin
 }
 
 // the launch itself, of one kernel instantiation (`flags`: the batch's with the launch's own)
-template <int FPW, int CPW, bool EVEN>
+template <int FPW, int CPW, bool EVEN, bool SOLE = false>
 static hipError_t launchVariant(const DcsKernelArgs &args, uint32_t flags, uint32_t blocks, hipStream_t stream)
 {
-    dcsk::dcsDecodeKernel<FPW, CPW, EVEN><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
+    dcsk::dcsDecodeKernel<FPW, CPW, EVEN, SOLE><<<dim3(blocks), dim3(64 * dcsk::kWavesPerBlock), dcsk::ldsBytes(FPW), stream>>>(
         args.packages, args.tables, args.nChunks, flags, args.epoch, args.nJobs, args.pcm, args.handoff, args.err, args.tailsOut,
         args.blob, args.blobLen, args.srcs, args.tailsIn, args.debug);
     return hipGetLastError();
 }
 
+// The kernels without the rounds of further sources: an even-deal batch none of whose jobs has a second source, unless the context
+// forbids them (`mode`: dcs_ctx_set_sole_source_kernel)
+static bool soleSourceKernel(uint32_t flags, int mode)
+{
+    return mode != 0 && (flags & DCS_BATCH_EVEN_DEAL) != 0 && (flags & DCS_BATCH_SOLE_SOURCE) != 0;
+}
+
 template <int FPW>
-static hipError_t launch(const DcsKernelArgs &args, hipStream_t stream, int numCUs, int cpwMode, bool solo)
+static hipError_t launch(const DcsKernelArgs &args, hipStream_t stream, int numCUs, int cpwMode, int soleMode, bool solo)
 {
     const bool two = twoChunksPerWave(FPW, cpwMode, solo, args.nChunks, args.flags, static_cast<uint32_t>(numCUs));
     const uint32_t waves = two ? (args.nChunks + 1u) / 2u : args.nChunks;
@@ -1212,6 +1230,8 @@ static hipError_t launch(const DcsKernelArgs &args, hipStream_t stream, int numC
     // (two chunks per wavefront and the even deal exist for 8 frames per wavefront only)
     if constexpr (FPW == 8)
     {
+        if (soleSourceKernel(flags, soleMode))
+            return two ? launchVariant<8, 2, true, true>(args, flags, blocks, stream) : launchVariant<8, 1, true, true>(args, flags, blocks, stream);
         if (flags & DCS_BATCH_EVEN_DEAL)
             return two ? launchVariant<8, 2, true>(args, flags, blocks, stream) : launchVariant<8, 1, true>(args, flags, blocks, stream);
         if (two)
@@ -1228,7 +1248,7 @@ static DcsStatus launchOnce(DcsBatch *b, hipStream_t stream)
     if (++b->epoch > DCS_EPOCH_MAX)
         b->epoch = 1;                   // (0 marks words no launch has written; after 2^31 launches of ONE batch the count starts over)
     const DcsKernelArgs args = kernelArgs(b);
-    const hipError_t e = withFpw(b->fpw, [&](auto w) { return launch<decltype(w)::value>(args, stream, ctx->numCUs, ctx->cpwOverride, b->solo); });
+    const hipError_t e = withFpw(b->fpw, [&](auto w) { return launch<decltype(w)::value>(args, stream, ctx->numCUs, ctx->cpwOverride, ctx->soleKernel, b->solo); });
     if (e != hipSuccess)
     {
         setError(ctx, std::string("kernel launch failed: ") + hipGetErrorString(e));
@@ -1434,6 +1454,7 @@ extern "C" int dcs_batch_chunks_per_wave(const DcsBatch *b)
     return twoChunksPerWave(b->fpw, b->ctx->cpwOverride, b->solo, b->nChunks, b->flags, cus) ? 2 : 1;
 }
 extern "C" int dcs_batch_even_deal(const DcsBatch *b) { return (b != nullptr && (b->flags & DCS_BATCH_EVEN_DEAL)) ? 1 : 0; }
+extern "C" int dcs_batch_sole_source_kernel(const DcsBatch *b) { return (b != nullptr && soleSourceKernel(b->flags, b->ctx->soleKernel)) ? 1 : 0; }
 extern "C" uint32_t dcs_batch_num_jobs(const DcsBatch *b) { return b ? b->nJobs : 0; }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1653,7 +1674,7 @@ struct LiveCall
         args.handoff = l->dHandoff.as<unsigned long long>();
         args.epoch = l->epoch;
         args.flags = batchFlags | (layout << DCS_BATCH_IMG_SHIFT);
-        const hipError_t e = withFpw(fpw, [&](auto w) { return launch<decltype(w)::value>(args, ctx->stream, ctx->numCUs, ctx->cpwOverride, !ctx->xcdRanges); });
+        const hipError_t e = withFpw(fpw, [&](auto w) { return launch<decltype(w)::value>(args, ctx->stream, ctx->numCUs, ctx->cpwOverride, 0, !ctx->xcdRanges); });
         if (e == hipSuccess)
             return DCS_OK;
         setError(ctx, std::string("kernel launch failed: ") + hipGetErrorString(e));

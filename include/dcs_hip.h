@@ -370,6 +370,11 @@ DcsStatus dcs_batch_create_mids(DcsCtx *ctx,
  * frame and band (bits, output index) are refused with DCS_ERR_INVALID_ARG, like an inconsistent index record. */
 DcsStatus dcs_ctx_set_even_deal(DcsCtx *ctx, int mode);
 int       dcs_batch_even_deal(const DcsBatch *batch);           /* 1: the batch's packages carry the even deal */
+/* tuning: the kernel of an even-deal batch none of whose jobs has a second source.  -1 (default): the instantiation without the
+ * unpack rounds of further sources; 0: never, such a batch runs the even-deal kernel every other one runs.  Looked at by
+ * every launch, like dcs_ctx_set_chunks_per_wave.  Same PCM, error words and tails either way. */
+DcsStatus dcs_ctx_set_sole_source_kernel(DcsCtx *ctx, int mode);
+int       dcs_batch_sole_source_kernel(const DcsBatch *batch);  /* 1: the batch's next launch runs that instantiation */
 void      dcs_batch_destroy(DcsBatch *batch);
 /* Enqueue the decode on `hipStream` (a hipStream_t passed as void*; NULL = the context's stream).
  * Asynchronous: returns after the launch.  No wavefront of the launch waits for another (a frame whose predecessor is decoded by

@@ -22,6 +22,7 @@ bt = ctx.batch(b["blob"], b["srcs"], b["jobs"])
 bt.run_many(3000); bt.sync()
 t = sorted(bt.time(steps) for _ in range(15))
 even = int(bt.even_deal) if hasattr(bt.L, "dcs_batch_even_deal") else 0
-print("%s %-16s %.3f us (%.3f %.3f) fpw %d cpw %d even %d" % (os.environ.get("DCS_TAG", "?"), wl, t[7] * 1e3, t[0] * 1e3, t[14] * 1e3,
-      bt.frames_per_wave, bt.chunks_per_wave, even), flush=True)
+sole = int(bt.sole_source_kernel) if hasattr(bt.L, "dcs_batch_sole_source_kernel") else 0
+print("%s %-16s %.3f us (%.3f %.3f) fpw %d cpw %d even %d sole %d" % (os.environ.get("DCS_TAG", "?"), wl, t[7] * 1e3, t[0] * 1e3, t[14] * 1e3,
+      bt.frames_per_wave, bt.chunks_per_wave, even, sole), flush=True)
 bt.close(); ctx.close()

@@ -9,13 +9,14 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 BENCH="python3 $PWD/bench.py --full --workload $WL --steps 50 --warmup 5 --no-cpu-baseline --no-class-surface --no-end-to-end --no-second-workload --no-device-path --rotate 0 $*"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/bench_trace.json 2> $OUT/trace.log
+# (every run under a time limit of its own, and the first one that fails ends the script: nothing more is started on the card)
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/bench_trace.json 2> $OUT/trace.log || { echo "prof $TAG: kernel trace failed"; tail -5 $OUT/trace.log; exit 1; }
 echo "prof $TAG: kernel trace done"
 for pass in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \
             "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
             "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_INSTS_SMEM SQ_THREAD_CYCLES_VALU"; do
   name=$(echo $pass | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --pmc $pass --output-format csv -d $OUT/pmc_$name -- $BENCH > /dev/null 2> $OUT/pmc_$name.log
+  timeout -k 10 300 rocprofv3 --pmc $pass --output-format csv -d $OUT/pmc_$name -- $BENCH > /dev/null 2> $OUT/pmc_$name.log || { echo "prof $TAG: pass $name failed"; tail -5 $OUT/pmc_$name.log; exit 1; }
   echo "prof $TAG: pass $name done"
 done
 cd $OUT
