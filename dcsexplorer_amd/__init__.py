@@ -24,5 +24,6 @@ from .api import (  # noqa: F401
     FILE_DCSA_REENCODE, FILE_WALK_NONE, FILE_WALK_DEVICE, FILE_WALK_HOST, wav_parse, encode_files_plan,
     FlacInfo, FLAC_FRAME_DTYPE, WAV_S8, FILE_FLAC, flac_parse, flac_index,
     FLAC_MD5, FLAC_SEQUENCE, FLAC_WRITE_INFO_DTYPE, PIPE_FLAC, PIPE_FLAC_MD5, PipelineFlacResult, flac_write_bound, flac_write_check,
+    FLAC_AT_UNITY, flac_write_samples_check,
     Level, LEVEL_GAIN, LEVEL_FIT, LEVEL_NORMALIZE, LEVEL_CLIP, LEVEL_INFO_DTYPE, level_gain,
 )

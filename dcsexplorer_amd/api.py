@@ -154,6 +154,7 @@ FLAC_FRAME_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u4"), ("blockSize",
 # dcs_flac_write_streams, dcs_decode_streams_flac: flags, and what was written per stream
 FLAC_MD5 = 1
 FLAC_SEQUENCE = 2
+FLAC_AT_UNITY = 4               # dcs_decode_streams_flac_at only: RESAMPLE_AT_UNITY for its converter
 FLAC_WRITE_INFO_DTYPE = np.dtype([("nSamples", "<u8"), ("nBytes", "<u8"), ("nBlocks", "<u4"), ("nConstant", "<u4"), ("nVerbatim", "<u4"),
                                   ("nFixed", "<u4"), ("minFrame", "<u4"), ("maxFrame", "<u4")], align=True)
 
@@ -239,6 +240,7 @@ EXPORTS = [
     "dcs_encode_sweep", "dcs_encode_sweep_group_frames", "dcs_encode_fit",
     "dcs_level_gain", "dcs_level_streams", "dcs_resample_streams_level", "dcs_encode_streams_at_level", "dcs_encode_files_level",
     "dcs_resample_out_count", "dcs_resample_out_walk", "dcs_resample_out_streams", "dcs_decode_streams_at",
+    "dcs_flac_write_samples_check", "dcs_flac_write_samples", "dcs_decode_streams_flac_at",
 ]
 
 
@@ -598,6 +600,13 @@ def load_library():
         L.dcs_resample_out_streams.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(ResampleFilter), u32, vp, sz, vp, vp]
         L.dcs_decode_streams_at.restype = i32
         L.dcs_decode_streams_at.argtypes = [vp, vp, u32, u32, u32, ctypes.POINTER(ResampleFilter), u32, vp, sz, vp, vp, vp]
+    if hasattr(L, "dcs_decode_streams_flac_at"):    # (... or from before the writer took streams of any length)
+        L.dcs_flac_write_samples_check.restype = i32
+        L.dcs_flac_write_samples_check.argtypes = [vp, u32, u32, u32, vp]
+        L.dcs_flac_write_samples.restype = i32
+        L.dcs_flac_write_samples.argtypes = [vp, vp, vp, u32, u32, u32, vp, sz, vp, vp]
+        L.dcs_decode_streams_flac_at.restype = i32
+        L.dcs_decode_streams_flac_at.argtypes = [vp, vp, u32, u32, u32, ctypes.POINTER(ResampleFilter), u32, vp, sz, vp, vp, vp, vp]
     if hasattr(L, "dcs_level_gain"):        # (DCS_HIP_LIB may name a build from before there was the level stage: A/B against it)
         fp = ctypes.POINTER(ctypes.c_float)
         L.dcs_level_gain.restype = i32
@@ -1102,6 +1111,14 @@ def flac_write_check(lengths, rate=31250, flags=0):
     offs = np.concatenate(([0], np.cumsum(np.asarray(lengths, np.uint64)))).astype(np.uint64)
     bad = ctypes.c_uint32()
     st = load_library().dcs_flac_write_check(_ptr(offs), offs.size - 1, int(rate) & 0xFFFFFFFF, flags, ctypes.byref(bad))
+    return st, bad.value
+
+
+def flac_write_samples_check(lengths, rate, flags=0):
+    """dcs_flac_write_samples_check on streams of `lengths` samples, any length from 1 on -> (status, the stream at fault)"""
+    offs = np.concatenate(([0], np.cumsum(np.asarray(lengths, np.uint64)))).astype(np.uint64)
+    bad = ctypes.c_uint32()
+    st = load_library().dcs_flac_write_samples_check(_ptr(offs), offs.size - 1, int(rate) & 0xFFFFFFFF, flags, ctypes.byref(bad))
     return st, bad.value
 
 
@@ -1613,6 +1630,59 @@ class Context:
         cap = sum(flac_write_bound(a.size) for a in arrs)
         flags = FLAC_MD5 if md5 else 0
         return self._flac_written(lambda *o: self.L.dcs_flac_write_streams(self.h, _ptr(pcm), _ptr(offs), n, rate, flags, *o), n, cap)
+
+    def flac_write_samples(self, pcm_list, rate, md5=True):
+        """dcs_flac_write_samples: flac_write_streams for int16 PCM streams of any length from 1 sample on -> (list of FLAC
+        streams as bytes, FLAC_WRITE_INFO_DTYPE array); streams of whole frames get flac_write_streams' bytes"""
+        arrs = [np.ascontiguousarray(p, np.int16).ravel() for p in pcm_list]
+        n = len(arrs)
+        offs = np.zeros(n + 1, np.uint64)
+        offs[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+        pcm = np.concatenate(arrs) if n else np.zeros(1, np.int16)
+        cap = sum(flac_write_bound(a.size) for a in arrs)
+        flags = FLAC_MD5 if md5 else 0
+        return self._flac_written(lambda *o: self.L.dcs_flac_write_samples(self.h, _ptr(pcm), _ptr(offs), n, int(rate), flags, *o), n, cap)
+
+    def _decode_refs_flac_at(self, refs, n, frames, rate, extra_frames, filter, flags):
+        total = int(sum(frames)) + n * extra_frames
+        err = np.zeros(max(total, 1), np.uint32)
+        first = np.zeros(n + 1, np.uint32)
+        first[1:] = np.cumsum([f + extra_frames for f in frames])
+        f, keep = _resample_filter(filter)
+        fp = ctypes.byref(f) if f is not None else None
+        cap = sum(flac_write_bound(_resample_out_bound(int(fr + extra_frames) * FRAME_SAMPLES, int(rate), bool(flags & FLAC_AT_UNITY)))
+                  for fr in frames)
+        rate_info = np.zeros(max(n, 1), RATE_INFO_DTYPE)
+        out, info = self._flac_written(lambda o, c, oo, i: self.L.dcs_decode_streams_flac_at(
+            self.h, refs, n, extra_frames, int(rate), fp, flags, o, c, oo, i, _ptr(rate_info), _ptr(err)), n, cap)
+        del keep
+        return out, info, rate_info[:n], err[:total], first
+
+    def decode_streams_flac_at(self, streams, rate, extra_frames=0, md5=True, filter=None, at_unity=False, sequence=False):
+        """dcs_decode_streams_flac_at: decode_streams_at whose converted samples stay on the device and leave it as FLAC at
+        `rate` Hz -> (list of FLAC streams as bytes, FLAC_WRITE_INFO_DTYPE array, RATE_INFO_DTYPE array, err, first_job);
+        the bytes are flac_write_samples' of decode_streams_at's samples, everything else is decode_streams_at's"""
+        streams = list(streams)
+        refs, keep = _stream_refs(streams)
+        frames = [(int(k[0]) << 8) | int(k[1]) for k in keep]
+        flags = (FLAC_MD5 if md5 else 0) | (FLAC_AT_UNITY if at_unity else 0) | (FLAC_SEQUENCE if sequence else 0)
+        return self._decode_refs_flac_at(refs, len(streams), frames, rate, extra_frames, filter, flags)
+
+    def extract_streams_flac_at(self, romset, rate, volume=255, extra_frames=2, md5=True, filter=None, at_unity=False):
+        """extract_streams whose PCM leaves the device as FLAC at `rate` Hz: -> (plan items, list of FLAC streams as bytes,
+        FLAC_WRITE_INFO_DTYPE array, RATE_INFO_DTYPE array, first frame of each stream)"""
+        items = romset.extract_plan()
+        refs = romset.stream_refs(items, volume)
+        frames = []
+        for k in range(len(items)):
+            one = ctypes.c_uint64()
+            st = self.L.dcs_count_stream_frames(ctypes.byref(refs[k]), 1, 0, ctypes.byref(one))
+            if st != 0:
+                raise DcsError(st)
+            frames.append(one.value)
+        flags = FLAC_SEQUENCE | (FLAC_MD5 if md5 else 0) | (FLAC_AT_UNITY if at_unity else 0)
+        out, info, rate_info, _, first = self._decode_refs_flac_at(refs, len(items), frames, rate, extra_frames, filter, flags)
+        return items, out, info, rate_info, first
 
     def _decode_refs_flac(self, refs, n, frames, extra_frames, flags):
         total = int(sum(frames)) + n * extra_frames

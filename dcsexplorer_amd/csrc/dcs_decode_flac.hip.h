@@ -9,7 +9,8 @@
 DcsStatus dcsFlacWriteFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint64_t *sampleOffsets, uint32_t n, uint32_t rate,
                                  uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsFlacWriteInfo *info);
 
-// What dcs_decode_streams_flac and dcs_decode_streams_at (dcs_decode_rate.hip.h) share: the list decoded as
+// What dcs_decode_streams_flac, dcs_decode_streams_at (dcs_decode_rate.hip.h) and dcs_decode_streams_flac_at
+// (dcs_decode_flac_rate.hip.h) share: the list decoded as
 // dcs_decode_streams decodes it (sequence: as dcs_decode_stream_sequence does, under its argument rules) by the
 // host-planned batch on the context's stream, and the batch's PCM handed to `consume` where it lies in HBM, stream k =
 // dPcm[sampleOffsets[k] .. sampleOffsets[k + 1]).  `check` sees the sample offsets before any device work and may refuse

@@ -32,6 +32,10 @@ struct FlacHeld
     }
 };
 
+// Among dcsFlacWriteQueue's and dcsFlacWriteFromDevice's flags, beside DCS_FLAC_MD5, and no flag of the ABI: the streams are
+// of any length from 1 sample on (a converter's output), not whole frames of 240.
+constexpr uint32_t kFlacWriteAnyLength = 0x80000000u;
+
 // Queues, on `stream` and behind whatever produces dPcm there, the whole writer for stream k = dPcm[sampleOffsets[k] ..
 // sampleOffsets[k + 1]) (offsets on the host, copied before this returns): the upload of offsets and block table, W1, W2, the
 // scan across streams, W4 with DCS_FLAC_MD5, the stream heads, W3, and the table's and the FLAC bytes' way down into `held`'s

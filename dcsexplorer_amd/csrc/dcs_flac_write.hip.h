@@ -2,16 +2,24 @@
 // (INTEGRATION.md "Writing FLAC" has the format rules; tests/flac_write_ref.py restates them).  Included in dcs_encode.hip
 // behind the FLAC reader; integer arithmetic only, so that unit's floating-point contract does not touch it.
 //
-// Mono, 16 bits, fixed block size 4096; a stream is whole DCS frames, so every block is a multiple of 16 samples, at least 16.
+// Mono, 16 bits, fixed block size 4096.  A stream of whole DCS frames (dcs_flac_write_streams, dcs_decode_streams_flac, the
+// pipeline) has blocks that are multiples of 16 samples, at least 16: the hot path, every block of a decode at 31 250 Hz and
+// all but the last block of any stream.  A stream of any length from 1 sample on (dcs_flac_write_samples,
+// dcs_decode_streams_flac_at: a converter's output) ends in a block of 1 .. 4096 samples; W1 and W3 take such a block on a
+// side of their own, chosen by a branch on the block's length that every lane of the workgroup takes alike, and a block of
+// whole 16s runs what it always ran.  The finest partitions of a block of n samples are 2^P, P = min(4, trailing zero bits
+// of n) (rules 9 to 11).
 //   W1 fwChooseKernel   one workgroup per block: the samples into LDS, the five fixed predictors' |residual| sums, the
-//                       16 x 15 table of exact Rice bit counts of the best order, its merges for partition orders 4..0,
-//                       and the block's record (FwRec): CONSTANT, VERBATIM or FIXED with order, partition order, parameters
+//                       2^P x 15 table of exact Rice bit counts of the best order (16 x 15 for whole 16s), its merges for
+//                       partition orders P..0, and the block's record (FwRec): CONSTANT, VERBATIM or FIXED with order,
+//                       partition order, parameters
 //   W2 fwPlaceKernel    one wavefront per stream: the frames' byte offsets behind the stream's 42 header bytes (a scan of
 //                       the records' frame sizes), the stream's size, smallest and largest frame and kind counts (FwSum)
 //   W3 fwWriteKernel    one workgroup per block: the frame assembled in zeroed LDS as big-endian dwords (each lane ORs in
 //                       only a code's one and low bits, the unary zeros are the buffer's), both CRCs from per-lane parts
 //                       moved to their place by powers of x (a CRC is linear), and the copy out, dwords where aligned
-//   W4 fwMd5Kernel      DCS_FLAC_MD5 only: one lane per stream walks its samples in 64-byte blocks (the chain is serial)
+//   W4 fwMd5Kernel      DCS_FLAC_MD5 only: one lane per stream walks its samples in 64-byte blocks (the chain is serial), any
+//                       number of samples, odd ones included
 // Nothing comes back to the host between them.  Three more kernels stand where the host's size-then-place step would:
 //      fwBaseKernel     one workgroup: the exclusive scan of the streams' sizes (rounds of 256 with a carried total: a scan in
 //                       each wavefront, the wavefronts' totals through LDS, as W2's within a stream), which is W3's dBase and,
@@ -106,12 +114,85 @@ __device__ inline void fwLoadBlock(int32_t *s, const int16_t *pcm, const FwBlock
 }
 
 // ------------------------------------------------------------------------------------------------------------ W1
+// the first of the 2^q nodes of partition order q in W1's tables: 0, 16, 24, 28, 30 for q = 4 .. 0
+__device__ inline uint32_t fwNodeBase(uint32_t q) { return 32u - (2u << q); }
+
+// W1 from the finest partitions' B rows on (they stand at the nodes of partition order P; the caller's barrier is behind
+// them): the merges, each node's best parameter, the partition order and the block's record.  kWhole: the block is a
+// multiple of 16 samples, P is 4, and the loops have the fixed bounds they always had; else P < 4 is the block's own.
+template <bool kWhole> __device__ inline void fwChooseFrom(unsigned long long (*B)[15], unsigned long long *nodeBits, uint32_t *nodeK, uint32_t blockP,
+                                                          uint32_t n, uint32_t order, uint32_t head, FwRec *out)
+{
+    const uint32_t t = threadIdx.x, P = kWhole ? 4u : blockP, finest = fwNodeBase(P);
+    // partitions of the lower orders are sums of pairs
+    for (uint32_t from = finest, to = finest + (1u << P), count = (1u << P) / 2 ; count >= 1 ; from = to, to += count, count >>= 1)
+    {
+        if (t < count * 15)
+        {
+            const uint32_t m = t / 15, k = t % 15;
+            B[to + m][k] = B[from + 2 * m][k] + B[from + 2 * m + 1][k];
+        }
+        __syncthreads();
+    }
+    if (t >= finest && t < 31)
+    {
+        unsigned long long best = B[t][0];
+        uint32_t bestK = 0;
+        for (uint32_t k = 1 ; k < 15 ; ++k)
+            if (B[t][k] < best) { best = B[t][k]; bestK = k; }           // (ties: the lowest parameter)
+        nodeBits[t] = best;
+        nodeK[t] = bestK;
+    }
+    __syncthreads();
+    if (t == 0)
+    {
+        // a partition order is a candidate only where a partition is longer than the warm-up, (n >> q) > order, as the format
+        // asks: the first partition then holds a residual.  Order 0 always is one (the predictor's order is below n: 0 for
+        // n <= 4).  The orders above P do not divide n.
+        unsigned long long total = 0;
+        uint32_t p = 0, base = 0;
+        bool any = false;
+        for (uint32_t q = P, from = finest ; ; from += 1u << q, --q)
+        {
+            if ((n >> q) > order)
+            {
+                unsigned long long sum = 4ull << q;
+                for (uint32_t j = 0 ; j < (1u << q) ; ++j)
+                    sum += nodeBits[from + j];
+                if (!any || sum <= total) { total = sum; p = q; base = from; }  // (ties: the lowest partition order)
+                any = true;
+            }
+            if (q == 0)
+                break;
+        }
+        FwRec r = {};
+        if (6 + total >= 16ull * (n - order))
+        {
+            r.kind = FW_VERBATIM;
+            r.frameBytes = head + 1 + 2 * n + 2;
+        }
+        else
+        {
+            r.kind = FW_FIXED;
+            r.order = static_cast<uint8_t>(order);
+            r.p = static_cast<uint8_t>(p);
+            const uint32_t bits = 8 + 16 * order + 6 + static_cast<uint32_t>(total);
+            r.frameBytes = head + (bits + 7) / 8 + 2;
+        }
+        *out = r;
+        // (the parameters go straight to the record: indexing the local copy would put it in scratch)
+        for (uint32_t j = 0 ; r.kind == FW_FIXED && j < (1u << p) ; ++j)
+            out->k[j] = static_cast<uint8_t>(nodeK[base + j]);
+    }
+}
+
 __global__ __launch_bounds__(kFwThreads) void fwChooseKernel(const int16_t *pcm, const uint64_t *offs, const uint32_t *blockFirst,
                                                              uint32_t nStreams, uint32_t nBlocks, FwRec *rec)
 {
     __shared__ int32_t s[kFwBlock];
     __shared__ uint32_t part[kFwThreads / 64][6];
     __shared__ unsigned long long B[31][15];            // nodes 0..15: partition order 4; 16..23: 3; 24..27: 2; 28, 29: 1; 30: 0
+    __shared__ uint32_t halfSum[kFwThreads / 32][15];   // a block that is no multiple of 16: the half wavefronts' shift sums
     __shared__ unsigned long long nodeBits[31];
     __shared__ uint32_t nodeK[31];
     __shared__ uint32_t chosen[2];                      // differs, order
@@ -175,7 +256,12 @@ __global__ __launch_bounds__(kFwThreads) void fwChooseKernel(const int16_t *pcm,
         return;
     }
 
-    // B[j][k] of the 16 finest partitions: lane group j = t / 16 walks partition j, 15 shift-adds a residual
+    // The finest partitions: 2^P of n >> P samples, P = min(4, trailing zero bits of n).  Their B rows stand at the nodes
+    // of partition order P (fwNodeBase), so that a block of whole 16s, P = 4, fills nodes 0..15 as it always did.
+    const uint32_t P = (n & 15) == 0 ? 4u : static_cast<uint32_t>(__builtin_ctz(n)), finest = fwNodeBase(P);
+    // B[j][k] of the 16 finest partitions: lane group j = t / 16 walks partition j, 15 shift-adds a residual.  The branch is
+    // on the block's length alone: every lane of the workgroup takes the same side.
+    if (P == 4)
     {
         const uint32_t size = n / 16, j = t >> 4;
         uint32_t sum[15];
@@ -204,66 +290,47 @@ __global__ __launch_bounds__(kFwThreads) void fwChooseKernel(const int16_t *pcm,
                 B[j][k] = static_cast<unsigned long long>(sum[k]) + static_cast<unsigned long long>(k + 1) * count;
         }
     }
-    __syncthreads();
-    // partitions of the lower orders are sums of pairs
-    for (uint32_t from = 0, to = 16, count = 8 ; count >= 1 ; from = to, to += count, count >>= 1)
+    else
     {
-        if (t < count * 15)
-        {
-            const uint32_t m = t / 15, k = t % 15;
-            B[to + m][k] = B[from + 2 * m][k] + B[from + 2 * m + 1][k];
-        }
-        __syncthreads();
-    }
-    if (t < 31)
-    {
-        unsigned long long best = B[t][0];
-        uint32_t bestK = 0;
-        for (uint32_t k = 1 ; k < 15 ; ++k)
-            if (B[t][k] < best) { best = B[t][k]; bestK = k; }           // (ties: the lowest parameter)
-        nodeBits[t] = best;
-        nodeK[t] = bestK;
-    }
-    __syncthreads();
-    if (t == 0)
-    {
-        // a partition order is a candidate only where a partition is longer than the warm-up, (n >> q) > order, as the format
-        // asks: the first partition then holds a residual.  Order 0 always is one (n >= 16 > 4).
-        unsigned long long total = 0;
-        uint32_t p = 0, base = 0;
-        bool any = false;
-        for (uint32_t q = 4, from = 0 ; ; from += 1u << q, --q)
-        {
-            if ((n >> q) > order)
+        // a block that is no multiple of 16 (a stream's last one): 2^P partitions, P < 4, and 256 >> P lanes to a partition,
+        // which is 32 or more, so every half wavefront lies in one partition.  The half wavefronts' sums meet in LDS.
+        const uint32_t size = n >> P, group = kFwThreads >> P, j = t / group;
+        uint32_t sum[15];
+#pragma unroll
+        for (int k = 0 ; k < 15 ; ++k)
+            sum[k] = 0;
+        for (uint32_t i = j * size + (t & (group - 1)) ; i < (j + 1) * size ; i += group)
+            if (i >= order)
             {
-                unsigned long long sum = 4ull << q;
-                for (uint32_t j = 0 ; j < (1u << q) ; ++j)
-                    sum += nodeBits[from + j];
-                if (!any || sum <= total) { total = sum; p = q; base = from; }  // (ties: the lowest partition order)
-                any = true;
+                const uint32_t u = fwZigzag(fwResidualOf(order, s, i));
+#pragma unroll
+                for (int k = 0 ; k < 15 ; ++k)
+                    sum[k] += u >> k;
             }
-            if (q == 0)
-                break;
-        }
-        FwRec r = {};
-        if (6 + total >= 16ull * (n - order))
+#pragma unroll
+        for (int k = 0 ; k < 15 ; ++k)
+            for (int d = 16 ; d >= 1 ; d >>= 1)
+                sum[k] += __shfl_xor(sum[k], d, 64);    // (32 lanes x 16 residuals below 2^21)
+        if ((t & 31) == 0)
+#pragma unroll
+            for (int k = 0 ; k < 15 ; ++k)
+                halfSum[t >> 5][k] = sum[k];
+        __syncthreads();
+        if (t < (15u << P))
         {
-            r.kind = FW_VERBATIM;
-            r.frameBytes = head + 1 + 2 * n + 2;
+            const uint32_t m = t / 15, k = t % 15, halves = (kFwThreads / 32) >> P, last = (m + 1) * size;
+            const uint32_t count = last <= order ? 0u : last - order < size ? last - order : size;
+            unsigned long long bits = static_cast<unsigned long long>(k + 1) * count;
+            for (uint32_t h = 0 ; h < halves ; ++h)
+                bits += halfSum[m * halves + h][k];
+            B[finest + m][k] = bits;
         }
-        else
-        {
-            r.kind = FW_FIXED;
-            r.order = static_cast<uint8_t>(order);
-            r.p = static_cast<uint8_t>(p);
-            const uint32_t bits = 8 + 16 * order + 6 + static_cast<uint32_t>(total);
-            r.frameBytes = head + (bits + 7) / 8 + 2;
-        }
-        rec[b] = r;
-        // (the parameters go straight to the record: indexing the local copy would put it in scratch)
-        for (uint32_t j = 0 ; r.kind == FW_FIXED && j < (1u << p) ; ++j)
-            rec[b].k[j] = static_cast<uint8_t>(nodeK[base + j]);
     }
+    __syncthreads();
+    if (P == 4)
+        fwChooseFrom<true>(B, nodeBits, nodeK, P, n, order, head, &rec[b]);
+    else
+        fwChooseFrom<false>(B, nodeBits, nodeK, P, n, order, head, &rec[b]);
 }
 
 // ------------------------------------------------------------------------------------------------------------ W2
@@ -369,6 +436,53 @@ __device__ inline FwCode fwCodeOf(const FwRec &r, const uint32_t *params, const 
     return c;
 }
 
+// Lane t of a FIXED block codes samples 16 t .. 16 t + 15.  kWhole: the block is a multiple of 16 samples and the lane has
+// all 16; else the lane stops at n (the last lane of a block of any other length would code samples that are not there).
+template <bool kWhole> __device__ inline uint32_t fwLaneBits(const FwRec &r, const uint32_t *params, const int32_t *s, uint32_t n, uint32_t t)
+{
+    const uint32_t end = kWhole || 16 * t + 16 < n ? 16 * t + 16 : n;
+    uint32_t bits = 0;
+    for (uint32_t i = 16 * t ; i < end ; ++i)
+    {
+        if (i < r.order)
+            bits += 16;
+        else
+        {
+            const FwCode c = fwCodeOf(r, params, s, n, i);
+            bits += c.pre + c.q + 1 + c.k;
+        }
+    }
+    return bits;
+}
+// ... and writes them from bit `pos` of the frame on
+template <bool kWhole> __device__ inline void fwLanePut(uint32_t *buf, uint32_t pos, const FwRec &r, const uint32_t *params, const int32_t *s,
+                                                        uint32_t n, uint32_t t)
+{
+    const uint32_t end = kWhole || 16 * t + 16 < n ? 16 * t + 16 : n;
+    for (uint32_t i = 16 * t ; i < end ; ++i)
+    {
+        if (i < r.order)
+        {
+            if ((s[i] & 0xFFFF) != 0)
+                fwPut(buf, pos, s[i] & 0xFFFF, 16);
+            pos += 16;
+        }
+        else
+        {
+            const FwCode c = fwCodeOf(r, params, s, n, i);
+            if (c.pre == 10)
+            {
+                if (r.p != 0) fwPut(buf, pos, r.p, 6);
+                if (c.k != 0) fwPut(buf, pos + 6, c.k, 4);
+            }
+            else if (c.pre == 4 && c.k != 0)
+                fwPut(buf, pos, c.k, 4);
+            fwPut(buf, pos + c.pre + c.q, c.low, c.k + 1);
+            pos += c.pre + c.q + 1 + c.k;
+        }
+    }
+}
+
 __global__ __launch_bounds__(kFwThreads) void fwWriteKernel(const int16_t *pcm, const uint64_t *offs, const uint32_t *blockFirst,
                                                             uint32_t nStreams, uint32_t nBlocks, const FwRec *rec,
                                                             const unsigned long long *rel, const unsigned long long *streamBase,
@@ -434,18 +548,12 @@ __global__ __launch_bounds__(kFwThreads) void fwWriteKernel(const int16_t *pcm, 
             if ((s[i] & 0xFFFF) != 0)
                 fwPut(buf, body + 16 * i, s[i] & 0xFFFF, 16);
     }
-    uint32_t mine = 0;                                  // FIXED: the bits of this lane's 16 samples
+    // FIXED: the bits of this lane's 16 samples.  A block of whole 16s takes the loops of exactly 16; any other length (a
+    // stream's last block) the ones bounded by n.  The branch is on the block's length: the same side in every lane.
+    const bool whole = (n & 15) == 0;
+    uint32_t mine = 0;
     if (r.kind == FW_FIXED && 16 * t < n)
-        for (uint32_t i = 16 * t ; i < 16 * t + 16 ; ++i)
-        {
-            if (i < r.order)
-                mine += 16;
-            else
-            {
-                const FwCode c = fwCodeOf(r, params, s, n, i);
-                mine += c.pre + c.q + 1 + c.k;
-            }
-        }
+        mine = whole ? fwLaneBits<true>(r, params, s, n, t) : fwLaneBits<false>(r, params, s, n, t);
     // an exclusive scan of the lanes' bit counts: inside each wavefront, then over the wavefronts
     uint32_t incl = mine;
     for (int d = 1 ; d < 64 ; d <<= 1)
@@ -462,28 +570,10 @@ __global__ __launch_bounds__(kFwThreads) void fwWriteKernel(const int16_t *pcm, 
         uint32_t pos = body + incl - mine;
         for (uint32_t v = 0 ; v < (t >> 6) ; ++v)
             pos += waveSum[v];
-        for (uint32_t i = 16 * t ; i < 16 * t + 16 ; ++i)
-        {
-            if (i < r.order)
-            {
-                if ((s[i] & 0xFFFF) != 0)
-                    fwPut(buf, pos, s[i] & 0xFFFF, 16);
-                pos += 16;
-            }
-            else
-            {
-                const FwCode c = fwCodeOf(r, params, s, n, i);
-                if (c.pre == 10)
-                {
-                    if (r.p != 0) fwPut(buf, pos, r.p, 6);
-                    if (c.k != 0) fwPut(buf, pos + 6, c.k, 4);
-                }
-                else if (c.pre == 4 && c.k != 0)
-                    fwPut(buf, pos, c.k, 4);
-                fwPut(buf, pos + c.pre + c.q, c.low, c.k + 1);
-                pos += c.pre + c.q + 1 + c.k;
-            }
-        }
+        if (whole)
+            fwLanePut<true>(buf, pos, r, params, s, n, t);
+        else
+            fwLanePut<false>(buf, pos, r, params, s, n, t);
     }
     // CRC-8 of the header: lane i takes byte i past the bytes that follow it
     if (t < 64)
@@ -576,7 +666,9 @@ __device__ inline void fwMd5Block(uint32_t (&h)[4], const uint32_t (&M)[16])
     h[0] += a; h[1] += b; h[2] += c; h[3] += d;
 }
 
-// the MD5 of each stream's samples as little-endian int16: 16 bytes a stream
+// the MD5 of each stream's samples as little-endian int16: 16 bytes a stream.  Any number of samples: `rest`, what lies behind
+// the last whole 64-byte block, may be odd (a word of the padding block then holds one sample and the 0x80 byte), and from
+// 28 samples on the length goes into a block of its own.  A stream may start at an odd sample: the reads are 16-bit.
 __global__ __launch_bounds__(64) void fwMd5Kernel(const int16_t *pcm, const uint64_t *offs, uint32_t nStreams, uint32_t *digest)
 {
     const uint32_t k = blockIdx.x * 64 + threadIdx.x;
@@ -714,12 +806,15 @@ __global__ __launch_bounds__(kFwThreads) void fwDownKernel(uint4 *dst, const uin
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-// what dcs_flac_write_streams checks before any device work; *bad = the stream at fault
+// what the writer's calls check before any device work; *bad = the stream at fault.  kFlacWriteAnyLength (dcs_flac_held.h; no
+// caller's flag: the entry points that take whole frames only refuse it as an unknown flag before they come here) lifts
+// the rule that a stream is whole frames of 240 samples: dcs_flac_write_samples and dcs_decode_streams_flac_at.
 DcsStatus fwCheck(const uint64_t *offs, uint32_t n, uint32_t rate, uint32_t flags, uint32_t *bad, std::string &why)
 {
     *bad = 0;
+    const bool anyLength = (flags & kFlacWriteAnyLength) != 0;
     if (offs == nullptr) { why = "no sample offsets"; return DCS_ERR_INVALID_ARG; }
-    if ((flags & ~DCS_FLAC_MD5) != 0) { why = "unknown flag"; return DCS_ERR_INVALID_ARG; }
+    if ((flags & ~(DCS_FLAC_MD5 | kFlacWriteAnyLength)) != 0) { why = "unknown flag"; return DCS_ERR_INVALID_ARG; }
     if (rate < 1 || rate > 65535) { why = "rate " + std::to_string(rate) + " outside 1..65535"; return DCS_ERR_INVALID_ARG; }
     uint64_t blocks = 0;
     for (uint32_t k = 0 ; k < n ; ++k)
@@ -727,7 +822,8 @@ DcsStatus fwCheck(const uint64_t *offs, uint32_t n, uint32_t rate, uint32_t flag
         *bad = k;
         if (offs[k + 1] < offs[k]) { why = "stream " + std::to_string(k) + ": offsets fall"; return DCS_ERR_INVALID_ARG; }
         const uint64_t len = offs[k + 1] - offs[k];
-        if (len == 0 || len % DCS_FRAME_SAMPLES != 0)
+        if (len == 0 && anyLength) { why = "stream " + std::to_string(k) + ": no samples"; return DCS_ERR_INVALID_ARG; }
+        if (len == 0 || (!anyLength && len % DCS_FRAME_SAMPLES != 0))
         {
             why = "stream " + std::to_string(k) + ": " + std::to_string(len) + " samples are not whole frames of 240";
             return DCS_ERR_INVALID_ARG;
@@ -738,6 +834,14 @@ DcsStatus fwCheck(const uint64_t *offs, uint32_t n, uint32_t rate, uint32_t flag
     *bad = 0;
     if (blocks > 0x7FFFFFFFull) { why = "more than 2^31 - 1 blocks in one call"; return DCS_ERR_INVALID_ARG; }
     return DCS_OK;
+}
+
+// ... on a caller's flags, of which kFlacWriteAnyLength is none: whole frames only, or with anyLength any length from 1 on
+DcsStatus fwCheckCall(const uint64_t *offs, uint32_t n, uint32_t rate, uint32_t flags, bool anyLength, uint32_t *bad, std::string &why)
+{
+    *bad = 0;
+    if ((flags & ~DCS_FLAC_MD5) != 0) { why = "unknown flag"; return DCS_ERR_INVALID_ARG; }
+    return fwCheck(offs, n, rate, flags | (anyLength ? kFlacWriteAnyLength : 0u), bad, why);
 }
 
 // what the streams of a call can come to at most: 42 bytes a stream, and every block VERBATIM behind the longest frame header
@@ -770,7 +874,18 @@ extern "C" DcsStatus dcs_flac_write_check(const uint64_t *sampleOffsets, uint32_
 {
     uint32_t bad = 0;
     std::string why;
-    const DcsStatus st = fwCheck(sampleOffsets, nStreams, rate, flags, &bad, why);
+    const DcsStatus st = fwCheckCall(sampleOffsets, nStreams, rate, flags, false, &bad, why);
+    if (badStream != nullptr)
+        *badStream = bad;
+    return st;
+}
+
+extern "C" DcsStatus dcs_flac_write_samples_check(const uint64_t *sampleOffsets, uint32_t nStreams, uint32_t rate, uint32_t flags,
+                                                  uint32_t *badStream)
+{
+    uint32_t bad = 0;
+    std::string why;
+    const DcsStatus st = fwCheckCall(sampleOffsets, nStreams, rate, flags, true, &bad, why);
     if (badStream != nullptr)
         *badStream = bad;
     return st;
@@ -921,16 +1036,16 @@ DcsStatus dcsFlacWriteFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint64_
     return DCS_OK;
 }
 
-extern "C" DcsStatus dcs_flac_write_streams(DcsCtx *ctx, const int16_t *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
-                                            uint32_t rate, uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets,
-                                            DcsFlacWriteInfo *info)
+// dcs_flac_write_streams (whole frames only) and dcs_flac_write_samples (anyLength) on PCM in host memory
+static DcsStatus fwWriteHostPcm(DcsCtx *ctx, const int16_t *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, uint32_t rate,
+                                uint32_t flags, bool anyLength, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsFlacWriteInfo *info)
 {
     return encGuard([&]() -> DcsStatus {
         if (ctx == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
             return DCS_ERR_INVALID_ARG;
         uint32_t bad = 0;
         std::string why;
-        const DcsStatus checked = fwCheck(sampleOffsets, nStreams, rate, flags, &bad, why);
+        const DcsStatus checked = fwCheckCall(sampleOffsets, nStreams, rate, flags, anyLength, &bad, why);
         if (checked != DCS_OK)
         {
             dcsCtxSetError(ctx, why.c_str());
@@ -951,6 +1066,50 @@ extern "C" DcsStatus dcs_flac_write_streams(DcsCtx *ctx, const int16_t *pcm, con
         int16_t *dPcm = nullptr;
         ENCCHK(held.alloc(&dPcm, hi - lo));
         ENCCHK(hipMemcpyAsync(dPcm, pcm + lo, sizeof(int16_t) * (hi - lo), hipMemcpyHostToDevice, held.stream()));
-        return dcsFlacWriteFromDevice(ctx, dPcm, offs.data(), nStreams, rate, flags, out, outCap, outOffsets, info);
+        return dcsFlacWriteFromDevice(ctx, dPcm, offs.data(), nStreams, rate, flags | (anyLength ? kFlacWriteAnyLength : 0u), out, outCap,
+                                      outOffsets, info);
+    });
+}
+
+extern "C" DcsStatus dcs_flac_write_streams(DcsCtx *ctx, const int16_t *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                            uint32_t rate, uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                                            DcsFlacWriteInfo *info)
+{
+    return fwWriteHostPcm(ctx, pcm, sampleOffsets, nStreams, rate, flags, false, out, outCap, outOffsets, info);
+}
+
+extern "C" DcsStatus dcs_flac_write_samples(DcsCtx *ctx, const int16_t *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                            uint32_t rate, uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                                            DcsFlacWriteInfo *info)
+{
+    return fwWriteHostPcm(ctx, pcm, sampleOffsets, nStreams, rate, flags, true, out, outCap, outOffsets, info);
+}
+
+// The chain behind dcs_decode_streams_flac_at (dcs_decode_flac_rate.hip.h): a decode batch's PCM where it lies, through the
+// output-rate converter (rsConvertPcm16, dcs_resample.hip.h) and from there, still in HBM, through the writer at outRate.
+// The converted samples belong to `held` until the writer has returned; neither they nor the 31 250 Hz PCM come down.
+// flags: DCS_RESAMPLE_AT_UNITY for the converter, flacFlags: DCS_FLAC_MD5 for the writer.  rateInfo and info are optional;
+// rateInfo is filled as soon as the converter is through, whatever the writer then says.
+DcsStatus dcsFlacRateFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint64_t *sampleOffsets, uint32_t n, uint32_t outRate,
+                                const DcsResampleFilter *filter, uint32_t flags, uint32_t flacFlags, uint8_t *out, size_t outCap,
+                                uint64_t *outOffsets, DcsFlacWriteInfo *info, DcsRateInfo *rateInfo)
+{
+    return encGuard([&]() -> DcsStatus {
+        if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || n == 0 || (flacFlags & ~DCS_FLAC_MD5) != 0)
+            return DCS_ERR_INVALID_ARG;
+        DcsResampleFilter f;
+        std::string why;
+        const DcsStatus status = rsOutCheck(n, sampleOffsets, outRate, filter, flags, f, why);
+        if (status != DCS_OK)
+        {
+            dcsCtxSetError(ctx, why.c_str());
+            return status;
+        }
+        CacheArena held(ctx);
+        RsConverted16 c;
+        ENCTRY(rsConvertPcm16(ctx, dPcm, sampleOffsets, n, outRate, f, flags, held, c));
+        if (rateInfo != nullptr)
+            memcpy(rateInfo, c.info.data(), sizeof(DcsRateInfo) * n);
+        return dcsFlacWriteFromDevice(ctx, c.d, c.offsets.data(), n, outRate, flacFlags | kFlacWriteAnyLength, out, outCap, outOffsets, info);
     });
 }

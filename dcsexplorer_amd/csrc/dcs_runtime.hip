@@ -2028,6 +2028,7 @@ extern "C" DcsStatus dcs_ctx_call_floor(DcsCtx *ctx, uint32_t nFrames, int iters
 #include "dcs_sweep.hip.h"
 #include "dcs_decode_flac.hip.h"
 #include "dcs_decode_rate.hip.h"
+#include "dcs_decode_flac_rate.hip.h"
 
 // What the encoder's translation unit (dcs_encode.hip: compiled apart so that its floating-point contract applies to it
 // alone) needs of a context: its device, its stream, its error text and its buffer cache (CacheBuf, dcs_cache.h).

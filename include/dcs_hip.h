@@ -55,7 +55,9 @@ extern "C" {
                                           pipeline (DCS_PIPE_FLAC, DCS_PIPE_FLAC_MD5, DcsPipelineFlacResult,
                                           dcs_pipeline_collect_flac); decoding at an output rate (DcsRateInfo,
                                           DCS_OUT_SEQUENCE, dcs_resample_out_count, dcs_resample_out_walk,
-                                          dcs_resample_out_streams, dcs_decode_streams_at) */
+                                          dcs_resample_out_streams, dcs_decode_streams_at); FLAC of any length and at an
+                                          output rate (DCS_FLAC_AT_UNITY, dcs_flac_write_samples_check, dcs_flac_write_samples,
+                                          dcs_decode_streams_flac_at) */
 #define DCS_FRAME_SAMPLES 240          /* PCM samples per frame (DCSDecoder.h:123: 7.68 ms at 31250 Hz) */
 #define DCS_MAX_CHANNELS 8             /* DCSDecoderNative.h:305 */
 
@@ -1149,10 +1151,13 @@ DcsStatus dcs_flac_decode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fil
  * Writing FLAC (INTEGRATION.md "Writing FLAC"): int16 PCM -> one native FLAC stream per PCM stream, written on the device
  * (W1 to W4, dcs_flac_write.hip.h).  Mono, 16 bits, fixed block size 4096, "fLaC" and one STREAMINFO block in front; each
  * block is a CONSTANT, a VERBATIM or a FIXED subframe (orders 0..4, partitioned Rice coding with 4-bit parameters) by the
- * rule stated there, so a stream's bytes are a function of its samples, the rate and the flag alone.  A stream is whole
- * DCS frames: 240 x nFrames samples, nFrames >= 1. */
+ * rule stated there, so a stream's bytes are a function of its samples, the rate and the flag alone.  For
+ * dcs_flac_write_streams and dcs_decode_streams_flac a stream is whole DCS frames: 240 x nFrames samples, nFrames >= 1.
+ * dcs_flac_write_samples and dcs_decode_streams_flac_at take and make streams of any length from 1 sample on (rules 9 to
+ * 11 there); on whole frames their bytes are the former two's. */
 #define DCS_FLAC_MD5      1u           /* STREAMINFO carries the MD5 of the samples (else 16 zero bytes: "not computed")     */
-#define DCS_FLAC_SEQUENCE 2u           /* dcs_decode_streams_flac only: decode as dcs_decode_stream_sequence does             */
+#define DCS_FLAC_SEQUENCE 2u           /* dcs_decode_streams_flac, dcs_decode_streams_flac_at: decode as dcs_decode_stream_sequence does */
+#define DCS_FLAC_AT_UNITY 4u           /* dcs_decode_streams_flac_at only: DCS_RESAMPLE_AT_UNITY for its converter            */
 typedef struct DcsFlacWriteInfo       /* one per stream */
 {
     uint64_t nSamples, nBytes;         /* nBytes: the whole stream, its 42 header bytes included                           */
@@ -1160,7 +1165,8 @@ typedef struct DcsFlacWriteInfo       /* one per stream */
     uint32_t minFrame, maxFrame;       /* the smallest and the largest frame in bytes, as STREAMINFO says them             */
 } DcsFlacWriteInfo;
 /* host only: 42 + blocks x (16 + 1 + 2 x 4096 + 2), blocks = ceil(nSamples / 4096).  Always enough: a block that FIXED
- * would not make smaller is written VERBATIM. */
+ * would not make smaller is written VERBATIM.  It holds for any number of samples, whole frames or not: a last block of
+ * n samples comes to at most 16 + 1 + 2 n + 2 bytes. */
 uint64_t  dcs_flac_write_bound(uint64_t nSamples);
 /* host only: the check dcs_flac_write_streams makes before any device work.  DCS_ERR_INVALID_ARG: a stream that is not
  * whole frames (empty, or not a multiple of 240 samples) or has 2^36 samples or more, falling offsets, a rate outside
@@ -1179,6 +1185,25 @@ DcsStatus dcs_flac_write_streams(DcsCtx *ctx, const int16_t *pcm, const uint64_t
  * decoder produced.  Capacity protocol and info as dcs_flac_write_streams. */
 DcsStatus dcs_decode_streams_flac(DcsCtx *ctx, const DcsStreamRef *streams, uint32_t nStreams, uint32_t extraFrames, uint32_t flags,
                                   uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsFlacWriteInfo *info, uint32_t *errOut);
+/* host only: dcs_flac_write_check without the whole-frames rule, the check dcs_flac_write_samples makes before any device
+ * work.  DCS_ERR_INVALID_ARG: an empty stream, 2^36 samples or more, falling offsets, a rate outside 1 .. 65 535, an
+ * unknown flag, more than 2^31 - 1 blocks in all.  *badStream (optional): the stream at fault, else 0. */
+DcsStatus dcs_flac_write_samples_check(const uint64_t *sampleOffsets, uint32_t nStreams, uint32_t rate, uint32_t flags,
+                                       uint32_t *badStream);
+/* dcs_flac_write_streams for streams of any length >= 1 sample: the last block of a stream is 1 .. 4096 samples (rules 9
+ * to 11).  The same DcsFlacWriteInfo, capacity protocol and errors (see dcs_flac_write_samples_check); streams of whole
+ * frames get dcs_flac_write_streams' bytes. */
+DcsStatus dcs_flac_write_samples(DcsCtx *ctx, const int16_t *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, uint32_t rate,
+                                 uint32_t flags, uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsFlacWriteInfo *info);
+/* dcs_decode_streams_at whose converted samples stay on the device and leave it as FLAC at outRate Hz: the bytes are
+ * dcs_flac_write_samples' of what dcs_decode_streams_at returns for the same streams, extraFrames, outRate, filter and
+ * flags, at rate outRate.  flags: DCS_FLAC_MD5, DCS_FLAC_SEQUENCE (as DCS_OUT_SEQUENCE), DCS_FLAC_AT_UNITY (as
+ * DCS_RESAMPLE_AT_UNITY).  Refusals are dcs_decode_streams_at's, made before any device work and named in dcs_last_error.
+ * info and rateInfo (both optional, nStreams each): what the writer and the converter made of each stream.  Capacity
+ * protocol as dcs_decode_streams_flac; errOut (optional) as there, filled on DCS_OK and on DCS_ERR_CAPACITY. */
+DcsStatus dcs_decode_streams_flac_at(DcsCtx *ctx, const DcsStreamRef *streams, uint32_t nStreams, uint32_t extraFrames,
+                                     uint32_t outRate, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out, size_t outCap,
+                                     uint64_t *outOffsets, DcsFlacWriteInfo *info, DcsRateInfo *rateInfo, uint32_t *errOut);
 /* FLAC as a pipeline's output (dcs_pipeline_create with DCS_PIPE_FLAC, and DCS_PIPE_FLAC_MD5 for the MD5): every submitted list
  * is decoded as dcs_decode_streams decodes it and written at 31 250 Hz by the writer's kernels, queued behind the list's decode
  * on its worker's HIP stream; the FLAC bytes, this table and the error words are all that crosses the link, and the worker

@@ -11,7 +11,10 @@ each call, the bytes each brings over the link, and how many distinct stream len
 after a warm-up call; the library's own stderr lines (index and plan on the host, batch made and queued, the converter's
 walks, convolution and waits, the download into the caller's buffer) are read back and their medians reported.  --rocprof:
 the kernels' times (the decode kernel, rsWalkKernel where the table is walked on a device lane, rsConvolveKernel) from
-`rocprofv3 --kernel-trace --stats`, a run of its own.  Prints one JSON line."""
+`rocprofv3 --kernel-trace --stats`, a run of its own.  --flac: dcs_decode_streams_flac_at (the converted samples leave the
+device as FLAC) against dcs_decode_streams_at at both rates, without and with the MD5: the median milliseconds of each call,
+the bytes each brings over the link, the compression ratio (converted PCM bytes / FLAC bytes) and the kinds of subframe
+written.  Prints one JSON line."""
 import argparse
 import csv
 import glob
@@ -30,7 +33,7 @@ sys.path.insert(0, ROOT)
 
 import dcsexplorer_amd as D                     # noqa: E402
 from dcsexplorer_amd import workloads           # noqa: E402
-from dcsexplorer_amd.api import RATE_INFO_DTYPE, _check, _ptr, _resample_out_bound, _stream_refs   # noqa: E402
+from dcsexplorer_amd.api import FLAC_WRITE_INFO_DTYPE, RATE_INFO_DTYPE, _check, _ptr, _resample_out_bound, _stream_refs   # noqa: E402
 
 LISTS = ("realistic_65536", "survey3_65536", "ragged_65536")
 RATES = (48000, 44100)
@@ -92,6 +95,45 @@ def measure_list(ctx, name, iters):
     return res
 
 
+def measure_list_flac(ctx, name, iters):
+    """--flac: dcs_decode_streams_flac_at (the converted samples written as FLAC where they lie in HBM; FLAC bytes, the two
+    per-stream tables and the error words come down) against dcs_decode_streams_at (the converted samples come down), per
+    rate: the C calls alone into buffers made once, timed in alternating rounds"""
+    streams = streams_of(name)
+    refs, keep = _stream_refs(streams)
+    n = len(streams)
+    frames = [(int(k[0]) << 8) | int(k[1]) for k in keep]
+    total = sum(frames)
+    err = np.empty(total, np.uint32)
+    bounds = [_resample_out_bound(f * 240, max(RATES), False) for f in frames]
+    cap, flac_cap = sum(bounds), sum(D.flac_write_bound(b) for b in bounds)
+    out, offs, info = np.empty(cap, np.int16), np.empty(n + 1, np.uint64), np.empty(n, RATE_INFO_DTYPE)
+    flac, flac_offs, flac_info = np.empty(flac_cap, np.uint8), np.empty(n + 1, np.uint64), np.empty(n, FLAC_WRITE_INFO_DTYPE)
+    seen = {}
+
+    def down_at(rate):
+        _check(ctx.L.dcs_decode_streams_at(ctx.h, refs, n, 0, rate, None, 0, _ptr(out), cap, _ptr(offs), _ptr(info), _ptr(err)), ctx.h)
+        seen[rate, "samples"] = int(offs[n])
+
+    def down_flac_at(rate, flags):
+        _check(ctx.L.dcs_decode_streams_flac_at(ctx.h, refs, n, 0, rate, None, flags, _ptr(flac), flac_cap, _ptr(flac_offs), _ptr(flac_info),
+                                                _ptr(info), _ptr(err)), ctx.h)
+        seen[rate, "flac"] = int(flac_offs[n])
+        seen[rate, "kinds"] = {k: int(flac_info[k].sum()) for k in ("nConstant", "nVerbatim", "nFixed")}
+
+    fns = [f for r in RATES for f in (lambda r=r: down_at(r), lambda r=r: down_flac_at(r, 0), lambda r=r: down_flac_at(r, D.FLAC_MD5))]
+    ms = median_ms(fns, iters)
+    res = dict(frames=total, streams=n, distinct_lengths=len(set(frames)), longest_frames=max(frames))
+    for i, r in enumerate(RATES):
+        res["decode_streams_at_%d_ms" % r], res["decode_streams_flac_at_%d_ms" % r], res["decode_streams_flac_at_%d_md5_ms" % r] = ms[3 * i:3 * i + 3]
+        res["at_%d_link_bytes" % r] = 2 * seen[r, "samples"] + err.nbytes
+        res["flac_at_%d_link_bytes" % r] = (seen[r, "flac"] + 15) // 16 * 16 + 8 * (n + 2) + FLAC_WRITE_INFO_DTYPE.itemsize * n + err.nbytes
+        res["flac_at_%d_ratio" % r] = round(2 * seen[r, "samples"] / seen[r, "flac"], 4)
+        res["flac_at_%d_kinds" % r] = seen[r, "kinds"]
+    del keep
+    return res
+
+
 def rocprof():
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "dr", "--",
@@ -136,6 +178,7 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--flac", action="store_true", help="decode_streams_flac_at against decode_streams_at, per list and rate")
     ap.add_argument("--once", action="store_true", help="(the profiled run) one decode_streams_at of each list at 48 000 Hz")
     ap.add_argument("--trace-child", action="store_true", help="(the traced run) iters + 1 calls of each list at 48 000 Hz")
     a = ap.parse_args()
@@ -157,7 +200,7 @@ def main():
             del keep
         ctx.close()
         return
-    res = {name: measure_list(ctx, name, a.iters) for name in LISTS}
+    res = {name: (measure_list_flac if a.flac else measure_list)(ctx, name, a.iters) for name in LISTS}
     ctx.close()
     print(json.dumps(res))
 
