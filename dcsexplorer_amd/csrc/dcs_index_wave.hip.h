@@ -649,7 +649,7 @@ __device__ void scan93(Walk &s)
     for (int band = 0 ; band < s.nBands ; ++band)
     {
         s.putSplit(band, b.pos - frameStart, prv, prvDelta,
-                   (static_cast<uint32_t>(outIdx) & 0x1FFu) | (static_cast<uint32_t>(subType) << 9) | (reuse ? 0x800u : 0u));
+                   static_cast<uint32_t>(min(outIdx, DCS_ROW_PAD)) | (static_cast<uint32_t>(subType) << 9) | (reuse ? 0x800u : 0u));   // (dcsPutSplit)
         const uint32_t hb = rl(s.vHeader, static_cast<uint32_t>(band)) & 0x7Fu;
         const bool strided = (hb >> 6) != 0;
         int nSamples, inc = 1, fixup = 0, stride;

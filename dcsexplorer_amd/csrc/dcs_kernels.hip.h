@@ -923,7 +923,7 @@ __device__ __forceinline__ uint32_t unpack93a(const DcsLdsTables *T, uint16_t *r
         // 0x8000 times (0x9838 / 2^15)^(code & 3), each step truncated (:2986-2990): four constants
         constexpr uint32_t kS1 = (0x8000u * 0x9838u) >> 15, kS2 = (kS1 * 0x9838u) >> 15, kS3 = (kS2 * 0x9838u) >> 15;
         uint32_t sf = (scaleCode & 2) ? ((scaleCode & 1) ? kS3 : kS2) : ((scaleCode & 1) ? kS1 : 0x8000u);
-        sf <<= (scaleCode >> 2);
+        sf <<= ((scaleCode >> 2) & 31);             // (a damaged stream's code can leave 0 .. 0x7F: the count modulo 32, INTEGRATION.md "Damaged streams")
         sf = ((sf >> 16) * mixMul) >> 15;
         const int sfs = sx16(sf);                   // truncated to 16 bits, then read as signed (:2995, :3011)
 

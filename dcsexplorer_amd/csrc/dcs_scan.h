@@ -143,6 +143,9 @@ DCS_HD inline int dcsReadVlcFast(R &b, const uint16_t *fast, const uint16_t *tri
 template <class R>
 DCS_HD inline void dcsFatal(DcsScan<R> &s) { s.err |= DCS_FRAME_FATAL | DCS_FRAME_STOP; }
 
+// the word behind a frame's 256: where the kernels send every sample that lies past them, and the largest output index a record names
+#define DCS_ROW_PAD 256
+
 // split[band - 1] = the decoder state at the start of `band` (1..15)
 template <class R>
 DCS_HD inline void dcsPutSplit(DcsFrameIndex &fi, int band, uint32_t frameStart, const DcsScan<R> &s, int outIdx,
@@ -154,7 +157,9 @@ DCS_HD inline void dcsPutSplit(DcsFrameIndex &fi, int band, uint32_t frameStart,
     sp.bitDelta = static_cast<uint16_t>(s.b.bitPos() - frameStart);
     sp.prv = static_cast<uint16_t>(prv);
     sp.prvDelta = static_cast<uint16_t>(prvDelta);
-    sp.state = static_cast<uint16_t>((outIdx & 0x1FF) | (subType << 9) | (reuse ? 0x800 : 0));
+    // (an OS93 Type 0 header with enough strided bands, 32 words each, takes a frame past its 256 words -- a damaged header can --:
+    // what lies there is dropped, and a band that starts there starts at the row's pad word, DCS_ROW_PAD)
+    sp.state = static_cast<uint16_t>((outIdx > DCS_ROW_PAD ? DCS_ROW_PAD : outIdx) | (subType << 9) | (reuse ? 0x800 : 0));
 }
 
 // 1994+: the decoder state in the MIDDLE of band 15 (32 samples, twice any other band), kept in the two fields of that

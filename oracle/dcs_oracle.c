@@ -523,7 +523,9 @@ static void decompress93a(Stream *s, uint32_t mixMul, uint16_t *fb)
         uint32_t sf = 0x8000;
         for (int i = 0 ; i < (scaleCode & 3) ; ++i)
             sf = (sf * 0x9838u) >> 15;
-        sf <<= (scaleCode >> 2);
+        /* a damaged stream can drive scaleCode below 0 or past 0x7F: the shift count is taken modulo 32, as the x86 shl of
+         * the reference's build takes it (:2986-2991 shifts by uint16_t(scaleCode >> 2), which ISO C++ leaves undefined) */
+        sf <<= ((scaleCode >> 2) & 31);
         sf = ((sf >> 16) * mixMul) >> 15;                   /* then truncated to 16 bits (:2995, :3011) */
 
         const uint16_t *pairBase = &orc93a_pair[2 << bandBits];
