@@ -7,6 +7,10 @@
   oracle/_ref/dcs_encrate_ref, dcs_encrate_ref_san               tests/golden/resample/enc_rate_driver.cpp: the reference
                                   DCSEncoder over the real converter (default table); the second with
                                   -fsanitize=bounds,shift,float-cast-overflow (host code)
+  oracle/_ref/dcs_rsout_default, dcs_rsout_long, dcs_rsout_big   tests/golden/resample/out_rate_driver.c over the converter: int16
+                                  at 31 250 Hz to an output rate between libsamplerate's own int16 conversions; the default
+                                  table, the long table of tests/golden/decode_rate_golden.npz (on which the flush cap
+                                  binds) and big_table() of the default one
 
 The vendored libsamplerate lacks high_qual_coeffs.h, so every build gets a stand-in of ours, generated beside its object
 files (never committed), that puts a table of our choice in the best-quality slot; the fastest and medium slots are the
@@ -24,7 +28,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-BINARIES = ("dcs_rsref_default", "dcs_rsref_long", "dcs_rsref_big", "dcs_encrate_ref", "dcs_encrate_ref_san")
+BINARIES = ("dcs_rsref_default", "dcs_rsref_long", "dcs_rsref_big", "dcs_encrate_ref", "dcs_encrate_ref_san",
+            "dcs_rsout_default", "dcs_rsout_long", "dcs_rsout_big")
 SANITIZE = "-fsanitize=bounds,shift,float-cast-overflow"
 BIG_FACTOR = 4
 
@@ -85,6 +90,12 @@ def npz_table(name):
     return f[name + "/coeffs"], int(f[name + "/increment"])
 
 
+def out_long_table():
+    """the long table of the output-rate fixtures: 400 input samples a side, so that the flush cap binds from 44.1 kHz up"""
+    f = np.load(os.path.join(GOLDEN, "decode_rate_golden.npz"))
+    return f["long/coeffs"], int(f["long/increment"])
+
+
 def main(argv):
     if len(argv) != 3:
         sys.stderr.write(__doc__)
@@ -94,8 +105,12 @@ def main(argv):
     default = npz_table("default")
     rs = os.path.join(GOLDEN, "resample", "rs_driver.c")
     enc = os.path.join(GOLDEN, "resample", "enc_rate_driver.cpp")
+    rsout = os.path.join(GOLDEN, "resample", "out_rate_driver.c")
     jobs = [("default", default, rs, False, ()), ("long", npz_table("long"), rs, False, ()), ("big", big_table(*default), rs, False, ()),
-            ("enc", default, enc, True, ()), ("encsan", default, enc, True, (SANITIZE,))]
+            ("enc", default, enc, True, ()), ("encsan", default, enc, True, (SANITIZE,)),
+            ("out_default", default, rsout, False, ()), ("out_long", out_long_table(), rsout, False, ()),
+            ("out_big", big_table(*default), rsout, False, ())]
+    assert len(jobs) == len(BINARIES)
     for (name, table, driver, cxx, extra), exe in zip(jobs, BINARIES):
         build_lsr(work, name, table[0], table[1], driver, cxx=cxx, extra=list(extra), ref=ref, exe=os.path.join(out, exe))
     print("built oracle/_ref/%s from %s/libsamplerate" % (", ".join(BINARIES), ref))

@@ -146,6 +146,35 @@ def convert_float(pcm, out_rate, coeffs, increment):
         return ((float_inc / increment) * (left + right)).astype(np.float32)
 
 
+def convert_float_many(pcms, out_rate, coeffs, increment):
+    """convert_float of several streams at once -> a list of float32 arrays.  The streams lie one behind the other, each
+    between zeros of its own as wide as the filter reaches, and each half sum runs once over the taps for the outputs of all
+    of them: per output the products, their order and the sums are convert_float's (tests with many short streams and a
+    long filter spend their time per tap, not per output)."""
+    c = np.asarray(coeffs, dtype=np.float32)
+    n_coeffs = len(c)
+    _, _, _, float_inc, inc_t = params(n_coeffs, increment, out_rate)
+    max_fi = (n_coeffs - 2) << 12
+    reach = max_fi // inc_t + 2
+    parts, ps, sfis, counts, at = [], [], [], [], 0
+    for pcm in pcms:
+        x = short_to_float(pcm)
+        pos, sfi = walk(len(x), n_coeffs, increment, out_rate)
+        parts += [np.zeros(reach, np.float32), x, np.zeros(reach + 2, np.float32)]
+        ps.append(pos + at + reach)
+        sfis.append(sfi)
+        counts.append(len(pos))
+        at += len(x) + 2 * reach + 2
+    if sum(counts) == 0:
+        return [np.zeros(0, np.float32) for _ in pcms]
+    xp, p, sfi = np.concatenate(parts), np.concatenate(ps), np.concatenate(sfis)
+    left = R._half_sum(c, xp, p, sfi, inc_t, max_fi, +1)
+    right = R._half_sum(c, xp, p, inc_t - sfi, inc_t, max_fi, -1)
+    with np.errstate(over="ignore"):
+        y = ((float_inc / increment) * (left + right)).astype(np.float32)
+    return np.split(y, np.cumsum(counts)[:-1])
+
+
 def convert(pcm, out_rate, coeffs, increment, flags=0):
     """dcs_resample_out_streams for one stream -> (int16 samples, info) with info = dict(nIn, nOut, nClipped, peak), peak
     the float32 largest |y| of the converter's output (a pass-through: of s / 32768)"""

@@ -89,6 +89,18 @@ def test_the_conversions_floor_and_clamp():
     assert np.array_equal(out, x[:500]) and info["nClipped"] == 0 and info["peak"] == np.float32(1.0)
 
 
+def test_the_batched_restatement_is_the_restatement():
+    """convert_float_many, which tests/rate_out_cases.py runs on a call's streams at once, gives convert_float's bits"""
+    for tab, rate in (("default", 48000), ("fastest", 4000), ("long", 62500), ("default", 31250)):
+        c, inc = table(tab)
+        pcm = [Q.case_pcm(k) for k in ("noise:1:3", "square:240:0", "noise:497:4", "impulse:17:0", "dc-:33:0", "noise:2:5")]
+        many = Q.convert_float_many(pcm, rate, c, inc)
+        assert len(many) == len(pcm)
+        for x, y in zip(pcm, many):
+            want = Q.convert_float(x, rate, c, inc)
+            assert y.dtype == np.float32 and np.array_equal(y.view(np.uint32), want.view(np.uint32)), (tab, rate, len(x))
+
+
 def seeded_cases(seed=0xD7A1, n_random=12):
     """(table, rate, signal recipe): every rate of the issue's list and seeded other ones, every length, every signal"""
     rng = np.random.default_rng(seed)
