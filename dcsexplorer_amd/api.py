@@ -232,6 +232,7 @@ EXPORTS = [
     "dcs_node_last_error", "dcs_node_cache_release", "dcs_device_numa_node",
     "dcs_encode_params_default", "dcs_encode_bound", "dcs_encode_header", "dcs_encode_streams",
     "dcs_encode93_bound", "dcs_encode93_header", "dcs_encode93_streams",
+    "dcs_encode93a_bound", "dcs_encode93a_streams",
     "dcs_transcode_plan", "dcs_transcode_streams",
     "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
     "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
@@ -548,6 +549,10 @@ def load_library():
     L.dcs_encode93_header.argtypes = [vp, vp, vp, ctypes.POINTER(EncodeParams), i32, vp, ctypes.POINTER(i32), vp]
     L.dcs_encode93_streams.restype = i32
     L.dcs_encode93_streams.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), vp, sz, vp, vp]
+    L.dcs_encode93a_bound.restype = sz
+    L.dcs_encode93a_bound.argtypes = [ctypes.c_uint64]
+    L.dcs_encode93a_streams.restype = i32
+    L.dcs_encode93a_streams.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), vp, sz, vp, vp, vp]
     L.dcs_transcode_plan.restype = i32
     L.dcs_transcode_plan.argtypes = [vp, u32, ctypes.POINTER(EncodeParams), u32, vp, vp]
     L.dcs_transcode_streams.restype = i32
@@ -855,6 +860,16 @@ def encode93_params(os_=OS93B, fmt=None, **params):
 def encode93_bound(n_samples):
     """dcs_encode93_bound: the largest OS93 stream n_samples samples can encode to (0 = not encodable)"""
     return int(load_library().dcs_encode93_bound(int(n_samples)))
+
+
+# DcsEncode93aInfo: the Type-1 candidate of a stream encoded by encode93a_streams
+ENCODE93A_INFO_DTYPE = np.dtype([("selector", "<i4"), ("ladderIndex", "<i4"), ("numBands", "<i4"), ("reserved", "<i4"),
+                                 ("frameBits", "<u8"), ("budgetBits", "<u8"), ("sqErr", "<u8")])
+
+
+def encode93a_bound(n_samples):
+    """dcs_encode93a_bound: the largest stream n_samples samples can encode to through encode93a_streams, either type"""
+    return int(load_library().dcs_encode93a_bound(int(n_samples)))
 
 
 def encode93_header(power_sum, lo, hi, fmt_type, os_=OS93B, **params):
@@ -1514,6 +1529,24 @@ class Context:
         out = np.zeros(max(cap, 1), np.uint8)
         _check(self.L.dcs_encode93_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info
+
+    def encode93a_streams(self, pcm_list, fmt=None, **params):
+        """dcs_encode93a_streams: PCM at 31 250 Hz (as encode_streams) -> OS93a streams (formatVersion 0x9301).  fmt:
+        FMT_93A_T1 = the pair-table layout, which the reference cannot write (DESIGN.md 10.10 states the algorithm),
+        FMT_93_T0 = the bytes encode93_streams gives, None = both and per stream the first strictly smallest, Type 0 first.
+        Returns (list of bytes, ENCODE_INFO_DTYPE array, ENCODE93A_INFO_DTYPE array: the Type-1 candidate, zeros with FMT_93_T0)."""
+        if fmt not in (None, FMT_93_T0, FMT_93A_T1):
+            raise ValueError("no OS93a layout %r" % (fmt,))
+        p = encode_params(None, **dict(dict(formatVersion=0x9301, streamFormatType=_ENCODE93_FMT[fmt], streamFormatSubType=-1), **params))
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        out_offs = np.zeros(n + 1, np.uint64)
+        info, info_a = np.zeros(n, ENCODE_INFO_DTYPE), np.zeros(n, ENCODE93A_INFO_DTYPE)
+        cap = sum(encode93a_bound(offs[i + 1] - offs[i]) for i in range(n))
+        out = np.zeros(max(cap, 1), np.uint8)
+        _check(self.L.dcs_encode93a_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info),
+                                            _ptr(info_a)), self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info, info_a
 
     def level_streams(self, pcm_list, level):
         """dcs_level_streams: the level stage alone on PCM at 31 250 Hz (as encode_streams; a stream may be empty).  level: a

@@ -27,6 +27,9 @@
 //                         per stream, frame after frame (the band-type codes carried from frame to frame)
 //   O5 enc93PackKernel    one lane per (frame, band): the band's flag and type bits, then its samples
 //
+// OS93a Type 1, the pair-table layout no reference encoder writes, shares E1 and the swap and has an algorithm, kernels
+// (A1-A5) and a driver of its own: dcs_encode93a.hip.h, included at the end.
+//
 // E1 and encStreamKernel run per stream and do not read the parameters.  Everything behind them runs per JOB, a stream
 // encoded with one parameter set (EncJob, EncSet): its rows in the per-frame buffers are the job's own, the spectrum it reads
 // is its stream's.  dcs_encode_streams and its kin are one job per stream with one set; dcs_encode_sweep is any list of jobs,
@@ -2190,3 +2193,8 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
 // ------------------------------------------------------------------------ encoding files (dcs_encode_files.hip.h)
 
 #include "dcs_encode_files.hip.h"
+
+// ------------------------------------------------------- OS93a Type 1, the pair-table layout (dcs_encode93a.hip.h)
+// (last: its kernels follow every other one in the code object, which keeps the order it had)
+
+#include "dcs_encode93a.hip.h"

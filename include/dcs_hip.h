@@ -907,6 +907,34 @@ DcsStatus dcs_encode93_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sa
                                const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
                                DcsEncodeInfo *info);
 
+/* OS93a Type 1, the pair-table layout (DecoderImpl93a::DecompressFrame): the one layout the reference's DCSEncoder does
+ * not write, so there is nothing to be byte-equal to.  What holds instead (INTEGRATION.md "OS93a Type 1"):
+ * the reference decoder reads every stream to its last bit, the bytes are what the integer algorithm stated there gives
+ * (tests/enc93a_ref.py restates it), and the stream keeps to floor(targetBitRate * nFrames * 240 / 31250) bits of frame
+ * data whenever any candidate does (else it is the smallest the search found; size is never a reason to refuse).
+ * formatVersion must be 0x9301.  streamFormatType 1: Type 1.  0: the bytes dcs_encode93_streams gives.  -1: both, and per
+ * stream the first strictly smallest, Type 0 first.  powerBandCutoff and minimumDynamicRange do not apply to Type 1;
+ * maximumQuantizationError sets the per-band error floor below which more bits are not spent (0: none).  Input,
+ * capacity (DCS_ERR_CAPACITY with outOffsets written), ordering and errors as dcs_encode93_streams;
+ * DcsEncodeInfo.bandsToKeep of a Type-1 stream is its header's band count.  dcs_encode93_streams itself keeps refusing
+ * OS93a Type 1. */
+typedef struct DcsEncode93aInfo        /* the Type-1 candidate of a stream (zeros where streamFormatType is 0); with -1 it  */
+{                                      /* is filled even where Type 0 was the smaller and was written                      */
+    int32_t  selector;                 /* pp of the header byte 1 pp bbbbb: the prefix codebook                            */
+    int32_t  ladderIndex;              /* the entry of the lambda ladder the stream was walked with                        */
+    int32_t  numBands;                 /* bbbbb                                                                            */
+    int32_t  reserved;
+    uint64_t frameBits;                /* bits after the 3 header bytes; the stream is 3 + ceil(frameBits / 8) bytes       */
+    uint64_t budgetBits;               /* floor(targetBitRate * nFrames * 240 / 31250)                                     */
+    uint64_t sqErr;                    /* sum over frames and coefficients of (target - decoded frame-buffer word)^2, at    */
+                                       /* mixing multiplier 0xFFFE                                                         */
+} DcsEncode93aInfo;
+/* the largest stream nSamples samples can encode to through dcs_encode93a_streams, either type (0 as dcs_encode93_bound) */
+size_t    dcs_encode93a_bound(uint64_t nSamples);
+DcsStatus dcs_encode93a_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                                DcsEncodeInfo *info, DcsEncode93aInfo *info93a);
+
 /* ------------------------------------------------------------------------------------------------
  * Transcoding: DCS streams of any family into the family of `target` (formatVersion 0x9400: the 1994+ encoder; 0x9301 /
  * 0x9302: the OS93 encoder; checked as those encoders check it), the reference's DCSEncoder::EncodeDCSFile

@@ -3,7 +3,8 @@
 synchronises the device): frames per second and the real-time factor (seconds of 31 250 Hz audio per second) for
 256 streams x 256 frames and for one stream of 65 535 frames (the format's longest), in the reference's wildcard layout
 (three layouts searched).  --version 9301 / 9302: the OS93 encoder (dcs_encode93_streams) in its wildcard (0x9302: Type 0
-and Type 1; 0x9301: Type 0).  --rocprof: per-kernel times from `rocprofv3 --kernel-trace --stats`, in a run of their own.
+and Type 1; 0x9301: Type 0).  --version 9301 --type 1 / -1: the OS93a Type-1 encoder (dcs_encode93a_streams), alone or
+in its wildcard beside Type 0.  --rocprof: per-kernel times from `rocprofv3 --kernel-trace --stats`, in a run of their own.
 Prints one JSON line."""
 import argparse
 import csv
@@ -33,7 +34,7 @@ def measure(encode, pcm, iters):
     times = []
     for _ in range(iters):
         t0 = time.perf_counter()
-        streams, _ = encode(pcm)
+        streams = encode(pcm)[0]
         times.append(time.perf_counter() - t0)
     frames = sum((len(x) + 239) // 240 for x in pcm)
     med = float(np.median(times))
@@ -42,10 +43,10 @@ def measure(encode, pcm, iters):
                 bytes_out=sum(len(s) for s in streams))
 
 
-def rocprof(iters, version):
+def rocprof(iters, version, typ):
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "enc", "--", sys.executable, os.path.abspath(__file__),
-               "--iters", str(iters), "--version", version]
+               "--iters", str(iters), "--version", version] + (["--type", str(typ)] if typ is not None else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             return dict(error="rocprofv3 exit %d" % r.returncode, stderr=r.stderr[-800:])
@@ -65,14 +66,19 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--version", choices=["9400", "9301", "9302"], default="9400")
+    ap.add_argument("--type", type=int, choices=[-1, 1], default=None, help="with --version 9301: dcs_encode93a_streams, Type 1 or the wildcard")
     a = ap.parse_args()
+    if a.type is not None and a.version != "9301":
+        ap.error("--type goes with --version 9301")
     if a.rocprof:
-        print(json.dumps(dict(version=a.version, kernels=rocprof(3, a.version))))
+        print(json.dumps(dict(version=a.version, kernels=rocprof(3, a.version, a.type))))
         return
     import dcsexplorer_amd as D
     ctx = D.Context(0)
     if a.version == "9400":
         encode = ctx.encode_streams
+    elif a.type is not None:
+        encode = lambda pcm: ctx.encode93a_streams(pcm, D.FMT_93A_T1 if a.type == 1 else None)        # noqa: E731
     else:
         os_ = D.OS93A if a.version == "9301" else D.OS93B
         encode = lambda pcm: ctx.encode93_streams(pcm, os_)        # noqa: E731
@@ -80,6 +86,8 @@ def main():
     res = dict(batch_256x256=measure(encode, batch, a.iters), stream_65535=measure(encode, [signal(65535 * 240, 999)], max(2, a.iters // 3)))
     if a.version != "9400":
         res = dict(version=a.version, **res)
+    if a.type is not None:
+        res = dict(type=a.type, build_id=D.build_id(), **res)
     ctx.close()
     print(json.dumps(res))
 
