@@ -232,7 +232,7 @@ EXPORTS = [
     "dcs_node_last_error", "dcs_node_cache_release", "dcs_device_numa_node",
     "dcs_encode_params_default", "dcs_encode_bound", "dcs_encode_header", "dcs_encode_streams",
     "dcs_encode93_bound", "dcs_encode93_header", "dcs_encode93_streams",
-    "dcs_encode93a_bound", "dcs_encode93a_streams",
+    "dcs_encode93a_bound", "dcs_encode93a_streams", "dcs_encode93a_sweep",
     "dcs_transcode_plan", "dcs_transcode_streams",
     "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
     "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
@@ -570,6 +570,8 @@ def load_library():
     L.dcs_wav_parse.argtypes = [vp, sz, ctypes.POINTER(WavInfo)]
     L.dcs_encode_sweep.restype = i32
     L.dcs_encode_sweep.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, sz, vp]
+    L.dcs_encode93a_sweep.restype = i32
+    L.dcs_encode93a_sweep.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, sz, vp]
     L.dcs_encode_sweep_group_frames.restype = None
     L.dcs_encode_sweep_group_frames.argtypes = [ctypes.c_uint64]
     L.dcs_encode_fit.restype = i32
@@ -870,6 +872,14 @@ ENCODE93A_INFO_DTYPE = np.dtype([("selector", "<i4"), ("ladderIndex", "<i4"), ("
 def encode93a_bound(n_samples):
     """dcs_encode93a_bound: the largest stream n_samples samples can encode to through encode93a_streams, either type"""
     return int(load_library().dcs_encode93a_bound(int(n_samples)))
+
+
+def encode93a_params(fmt, **params):
+    """the EncodeParams of an OS93a set (formatVersion 0x9301) for encode93a_sweep / encode93a_fit: fmt FMT_93A_T1 or
+    FMT_93_T0 (None, the wildcard, is encode93a_streams' alone: a sweep refuses it), CompressionParams by name"""
+    if fmt not in (None, FMT_93_T0, FMT_93A_T1):
+        raise ValueError("no OS93a layout %r" % (fmt,))
+    return encode_params(None, **dict(dict(formatVersion=0x9301, streamFormatType=_ENCODE93_FMT[fmt], streamFormatSubType=-1), **params))
 
 
 def encode93_header(power_sum, lo, hi, fmt_type, os_=OS93B, **params):
@@ -1547,6 +1557,50 @@ class Context:
         _check(self.L.dcs_encode93a_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info),
                                             _ptr(info_a)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info, info_a
+
+    def encode93a_sweep(self, pcm_list, sets, jobs=None, measure=True, streams=True):
+        """dcs_encode93a_sweep: encode_sweep for OS93a, whose sets (encode93a_params) may mix FMT_93_T0 and FMT_93A_T1; a
+        Type-1 stream is searched once however many rates it is encoded at.  Returns (list of bytes per job, or None when
+        streams is false; SWEEP_RESULT_DTYPE array; ENCODE93A_INFO_DTYPE array: the Type-1 candidate, zeros of a Type-0 job)."""
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        arr = (EncodeParams * max(len(sets), 1))(*sets)
+        if jobs is None:
+            jl, n_jobs = None, n * len(sets)
+        else:
+            jl = np.zeros(max(len(jobs), 1), SWEEP_JOB_DTYPE)
+            for k, (s, p) in enumerate(jobs):
+                jl[k] = (s, p)
+            n_jobs = len(jobs)
+        res = np.zeros(max(n_jobs, 1), SWEEP_RESULT_DTYPE)
+        info_a = np.zeros(max(n_jobs, 1), ENCODE93A_INFO_DTYPE)
+        out_offs = np.zeros(n_jobs + 1, np.uint64)
+        flags = SWEEP_MEASURE if measure else 0
+        args = (self.h, _ptr(pcm), _ptr(offs), n, arr, len(sets), _ptr(jl) if jl is not None else None, n_jobs, flags, _ptr(res),
+                _ptr(info_a))
+        if not streams:
+            _check(self.L.dcs_encode93a_sweep(*args, None, 0, _ptr(out_offs)), self.h)
+            return None, res[:n_jobs], info_a[:n_jobs]
+        each = [encode93a_bound(int(offs[i + 1] - offs[i])) for i in range(n)]
+        cap = sum(each) * len(sets) if jobs is None else sum(each[s] for s, _ in jobs if 0 <= s < n)
+        out = np.zeros(max(cap, 1), np.uint8)
+        _check(self.L.dcs_encode93a_sweep(*args, _ptr(out), cap, _ptr(out_offs)), self.h)
+        return [out[out_offs[j]:out_offs[j + 1]].tobytes() for j in range(n_jobs)], res[:n_jobs], info_a[:n_jobs]
+
+    def encode93a_fit(self, pcm_list, sets, budget):
+        """encode_fit on encode93a_sweep: the best of `sets` (OS93a, either layout, in order of preference) per stream within
+        `budget` bytes.  Returns (list of bytes, choice per stream, SWEEP_RESULT_DTYPE records of the chosen jobs, total
+        bytes); raises DcsError status -5 (with `needed`) when no set fits as a whole."""
+        n, k = len(pcm_list), len(sets)
+        _, res, _ = self.encode93a_sweep(pcm_list, sets, None, measure=True, streams=False)
+        if not res["measured"].all():
+            j = int(np.flatnonzero(res["measured"] == 0)[0])
+            raise DcsError(-6, "stream %d, set %d: an OS93a Type-0 stream with no band kept cannot be decoded, so not measured" % (j // k, j % k))
+        n_bytes = res["enc"]["nBytes"].astype(np.uint64).reshape(n, k)
+        sq_err = np.array(sweep_sq_err(res), dtype=np.uint64).reshape(n, k)
+        choice, total = encode_fit_choose(n_bytes, sq_err, budget)
+        out, _, _ = self.encode93a_sweep(pcm_list, sets, [(i, int(choice[i])) for i in range(n)], measure=False, streams=True)
+        return out, choice, res.reshape(n, k)[np.arange(n), choice], total
 
     def level_streams(self, pcm_list, level):
         """dcs_level_streams: the level stage alone on PCM at 31 250 Hz (as encode_streams; a stream may be empty).  level: a

@@ -27,14 +27,16 @@
 //                         per stream, frame after frame (the band-type codes carried from frame to frame)
 //   O5 enc93PackKernel    one lane per (frame, band): the band's flag and type bits, then its samples
 //
-// OS93a Type 1, the pair-table layout no reference encoder writes, shares E1 and the swap and has an algorithm, kernels
-// (A1-A5) and a driver of its own: dcs_encode93a.hip.h, included at the end.
+// OS93a Type 1, the pair-table layout no reference encoder writes, shares E1 and the swap and has an algorithm and kernels
+// (A1-A5) of its own, dcs_encode93a.hip.h: a third family of the one driver, chosen per job by its set's type, so that one
+// call (dcs_encode93a_sweep) may hold Type-0 jobs on the O stages and Type-1 jobs on the A stages.
 //
-// E1 and encStreamKernel run per stream and do not read the parameters.  Everything behind them runs per JOB, a stream
+// E1 and encStreamKernel run per stream and do not read the parameters, and neither does A1's search; A1's walk reads one
+// of them, maximumQuantizationError, and runs once per distinct value.  Everything behind them runs per JOB, a stream
 // encoded with one parameter set (EncJob, EncSet): its rows in the per-frame buffers are the job's own, the spectrum it reads
-// is its stream's.  dcs_encode_streams and its kin are one job per stream with one set; dcs_encode_sweep is any list of jobs,
-// and with DCS_SWEEP_MEASURE decodes every job's stream where the pack step left it and reduces the round trip's error
-// (encMeasureKernel).
+// is its stream's.  dcs_encode_streams and its kin are one job per stream with one set; dcs_encode_sweep and
+// dcs_encode93a_sweep are any list of jobs, and with DCS_SWEEP_MEASURE decode every job's stream where the pack step left it
+// and reduce the round trip's error (encMeasureKernel).
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -740,6 +742,8 @@ __global__ __launch_bounds__(64) void encHeadKernel(const EncJob *__restrict__ j
     if (k >= 18)
         return;
     const int c = win[si], v = c < 2 ? 0 : c - 1;
+    if (c < 0)
+        return;                                 // no layout of this family is the job's (cmask 0): an OS93a Type-1 job
     const uint32_t nF = jobs[si].nFrames;
     uint32_t byte;
     if (k < 2)
@@ -1062,7 +1066,7 @@ __global__ __launch_bounds__(64) void enc93PackKernel(const EncTabs *__restrict_
     if (f >= F)
         return;
     const uint32_t si = frameJob[f];
-    if (band >= keepArr[si])
+    if (win[si] < 0 || band >= keepArr[si])                     // (win < 0: an OS93a Type-1 job, packed by enc93aPackKernel)
         return;
     const int v = win[si] < 2 ? 0 : 1;                          // (0,0) -> Type 0, (1,0) -> Type 1
     const size_t row = (static_cast<size_t>(v) * F + f) * 16;
@@ -1189,7 +1193,8 @@ extern "C" DcsStatus dcs_encode93_header(const float *powerSum, const float *lo,
 // ------------------------------------------------------------------------ measuring a job's round trip (dcs_sweep.hip.h)
 
 // what the encoder knows of a stream it has sized, enough for the device path's stream table (dcs_sweep.hip.h)
-struct DcsSweepStream { uint32_t nFrames, nBytes; int32_t os, formatType, formatSubType, bandsToKeep; };
+// (head: the third byte of an OS93a Type-1 stream, 1 pp bbbbb; not read of any other)
+struct DcsSweepStream { uint32_t nFrames, nBytes; int32_t os, formatType, formatSubType, bandsToKeep; uint32_t head; };
 struct DcsSweepDecode;
 DcsStatus dcsSweepLayout(const DcsSweepStream *s, uint32_t n, uint64_t *offs, size_t *blobLen, size_t *blobBytes);
 DcsStatus dcsSweepDecodeStart(DcsCtx *ctx, const DcsSweepStream *s, uint32_t n, const uint64_t *offs, const uint8_t *dBlob, size_t blobLen,
@@ -1259,6 +1264,16 @@ __global__ __launch_bounds__(256) void encMeasureKernel(const float *__restrict_
     }
 }
 
+}  // namespace
+
+// ------------------------------------------- OS93a Type 1, the pair-table layout: tables and kernels (dcs_encode93a.hip.h)
+// (here: behind every kernel above that is no template, so that those keep their order in the code object, and in front of
+// EncRun, which launches these; see the note above EncRun::analyse for the templates)
+
+#include "dcs_encode93a.hip.h"
+
+namespace {
+
 // Where the driver reads its samples: the caller's float PCM on the host (dcs_encode_streams, dcs_encode93_streams), a
 // decode batch's int16 PCM and error words, resident on the device (dcs_transcode_streams, dcs_transcode.hip.h), or the
 // resampler's float output, resident on the device (dcs_encode_streams_at, dcs_resample.hip.h)
@@ -1276,7 +1291,9 @@ struct EncInput
     bool unusable = false;                  // (out) planFlag was set: DCS_ERR_BAD_STREAM, and nothing was written
 };
 
-// the jobs of a call: job j = (stream list[j].stream, set list[j].paramSet), every set of the one encoder `os93` names
+// the jobs of a call: job j = (stream list[j].stream, set list[j].paramSet), every set of the one encoder `os93` names.
+// A set that asks for (0x9301, Type 1) puts its jobs into the A family (dcs_encode93a.hip.h); only dcs_encode93a_streams
+// and dcs_encode93a_sweep let one in.
 struct EncJobs
 {
     const DcsEncodeParams *sets;
@@ -1297,6 +1314,7 @@ struct EncOutput
     uint64_t *outOffsets = nullptr;         // nJobs + 1
     DcsEncodeInfo *info = nullptr;          // nJobs, or null
     const EncPlace *place = nullptr;
+    DcsEncode93aInfo *info93a = nullptr;    // nJobs, or null: the Type-1 candidate of a job of the A family, zeros of any other
 };
 
 // what dcs_encode_sweep asks of the driver beyond a list of jobs
@@ -1340,12 +1358,15 @@ struct SweepDecodeGuard
 //   allocCall      the buffers that live as long as the call (CallBufs)
 //   allocGroups    the jobs in groups, runs of the job list whose per-job-frame buffers (GroupBufs, sized for the largest
 //                  group) fit the memory: makeGroups + allocGroup, one group unless a cap is set or an allocation fails
-//   analyse        upload, E1 and the sums of E2, once per stream
-//   runGroup       per group: the header half of E2, the family's band stages and the sizes, and a wait, after which win,
-//                  keep and size of its jobs are on the host.  After the first group's wait, checkInput: planFlag, then bad[]
+//   analyse        upload, E1 and the sums of E2, once per stream; where the call has jobs of the A family, A1: the search
+//                  once per stream-frame and its walk once per distinct maximumQuantizationError (buildSets: setQ, rowOf)
+//   runGroup       per group: the header half of E2, the families' band stages (O or E on the jobs whose set has a layout
+//                  of theirs, A2 on the Type-1 jobs) and the sizes, and a wait, after which win, keep and size of its jobs
+//                  are on the host.  After the first group's wait, checkInput: planFlag, then bad[]
 //   placeOutput    once every size is known: outOffsets, info, results, and the memory the bytes go to (the capacity check)
 //   packGroup      per group again (one that is no longer resident is first computed again by runGroup): layout, header,
-//                  pack and swap into the group's blob on the device; then one of
+//                  pack (for the Type-1 jobs A3, A4, their head and A5) and swap into the group's blob on the device; then
+//                  one of
 //   deliverGroup   the blob to its place in the output, or with sweep.measure
 //   measureGroup   the group's streams decoded where the pack step left them and compared with their sources (M1), the
 //                  blob staged on the host when the decode or the output needs it there (stageBlob)
@@ -1400,8 +1421,15 @@ private:
     std::vector<uint32_t> frameStream;
     uint32_t F = 0;                             // frames of all streams
     std::vector<EncSet> hsets;                  // (buildSets)
-    uint32_t anyV = 0;                          // the layouts any set asks for: bit 0 Type 0, bit 1 (1, 0), bit 2 (1, 3)
+    uint32_t anyV = 0;                          // the layouts any set asks for: bit 0 Type 0, bit 1 (1, 0), bit 2 (1, 3);
+                                                // 0: every job is of the A family, and no O or E stage is launched
     uint64_t allFrames = 0, largest = 0;        // job-frames of all jobs, of the largest job
+    // the A family (OS93a Type 1): the distinct maximumQuantizationError values of its sets, each set's index among them
+    // (kA93None: a set of the O family), and per (q, stream) that a job names its row of A1's totals (kA93None: none does)
+    std::vector<float> qs;
+    std::vector<uint32_t> setQ, rowOf;
+    uint32_t nRows = 0;
+    std::vector<unsigned long long> floorE;     // [q][18] (analyse; the source of an asynchronous upload)
 
     // ---- device buffers of the call: valid from allocCall to the end
     struct CallBufs
@@ -1414,6 +1442,13 @@ private:
         float *dSpec, *dPw, *dLo, *dHi;         // E1's output per frame
         uint32_t *dBad;                         // per stream: a sample E1 refused
         float *dSums;                           // E2's sums per stream
+        struct                                  // the A family only (A1)
+        {
+            Enc93aTabs *dA = nullptr;
+            unsigned long long *dFloorE = nullptr;      // [q][18]
+            uint32_t *dSetQ = nullptr, *dRowOf = nullptr;
+            Enc93aTot *dTot = nullptr;          // [row][candidate]
+        } a93;
     } cb;
     CacheArena call;
 
@@ -1429,6 +1464,7 @@ private:
         uint32_t *dFrameBits, *dFrameOff;
         struct { Enc93Rec *dRec = nullptr; Enc93Band *dBand = nullptr; } o93;                       // OS93 only (O3-O5)
         struct { uint8_t *dBest = nullptr, *dCodes = nullptr, *dHdrBits = nullptr; uint16_t *dSmpBits = nullptr; } v94;   // 1994+ only (E3-E5)
+        struct { Enc93aChoice *dChoice = nullptr; Enc93aRec *dRec = nullptr; } a93;                 // OS93a Type 1 only (A2-A5)
         struct { EncMeasure *dMeas = nullptr; uint32_t *dFirstDec = nullptr; } m;                   // sweep.measure only (M1)
     } gb;
     CacheArena group;
@@ -1442,6 +1478,7 @@ private:
     std::vector<uint32_t> frameJob;             // ... and rows
     std::vector<int32_t> win, keep;             // per job (runGroup)
     std::vector<uint64_t> size;
+    std::vector<Enc93aChoice> choiceA;          // per job of the A family (runGroup)
     std::vector<uint32_t> bad;                  // per stream, on the host after the first group's wait
     uint8_t *dst = nullptr;                     // where the bytes go (placeOutput); null: nowhere
 
@@ -1510,11 +1547,30 @@ void EncRun::buildSets()
         hsets[k] = EncSet{ p.powerBandCutoff, p.minimumDynamicRange, p.maximumQuantizationError, p.targetBitRate, vmask, cmask };
         anyV |= vmask;
     }
+    // the A family's sets (cmask 0 above: no O stage touches their jobs) by their distinct maximumQuantizationError
+    setQ.assign(jobs.nSets, kA93None);
+    for (uint32_t k = 0 ; jobs.os93 && k < jobs.nSets ; ++k)
+        if (isType1Of93a(jobs.sets[k]))
+        {
+            const float q = jobs.sets[k].maximumQuantizationError;
+            const size_t at = std::find(qs.begin(), qs.end(), q) - qs.begin();
+            if (at == qs.size())
+                qs.push_back(q);
+            setQ[k] = static_cast<uint32_t>(at);
+        }
+    rowOf.assign(qs.size() * in.nStreams, kA93None);
     for (uint32_t j = 0 ; j < jobs.n ; ++j)
     {
-        const uint64_t nF = hs[jobs.list[j].stream].nFrames;
+        const DcsSweepJob &job = jobs.list[j];
+        const uint64_t nF = hs[job.stream].nFrames;
         allFrames += nF;
         largest = nF > largest ? nF : largest;
+        if (setQ[job.paramSet] != kA93None)
+        {
+            uint32_t &row = rowOf[static_cast<size_t>(setQ[job.paramSet]) * in.nStreams + job.stream];
+            if (row == kA93None)
+                row = nRows++;
+        }
     }
 }
 
@@ -1533,6 +1589,14 @@ DcsStatus EncRun::allocCall()
     ENCCHK(call.alloc(&cb.dHi, size_t(16) * F));
     ENCCHK(call.alloc(&cb.dBad, nStreams));
     ENCCHK(call.alloc(&cb.dSums, size_t(48) * nStreams));
+    if (!qs.empty())
+    {
+        ENCCHK(call.alloc(&cb.a93.dA, 1));
+        ENCCHK(call.alloc(&cb.a93.dFloorE, 18 * qs.size()));
+        ENCCHK(call.alloc(&cb.a93.dSetQ, jobs.nSets));
+        ENCCHK(call.alloc(&cb.a93.dRowOf, rowOf.size()));
+        ENCCHK(call.alloc(&cb.a93.dTot, size_t(kA93Cand) * nRows));
+    }
     return DCS_OK;
 }
 
@@ -1568,19 +1632,25 @@ hipError_t EncRun::allocGroup()
     HIPTRY(group.alloc(&gb.dWin, NJ));
     HIPTRY(group.alloc(&gb.dSize, NJ));
     HIPTRY(group.alloc(&gb.dOutOff, NJ));
-    HIPTRY(group.alloc(&gb.dFrameBits, 3 * JF));
+    if (anyV != 0)
+        HIPTRY(group.alloc(&gb.dFrameBits, 3 * JF));
     HIPTRY(group.alloc(&gb.dFrameOff, JF));
-    if (jobs.os93)
+    if (anyV != 0 && jobs.os93)
     {
         HIPTRY(group.alloc(&gb.o93.dRec, 32 * JF));
         HIPTRY(group.alloc(&gb.o93.dBand, 32 * JF));
     }
-    else
+    if (anyV != 0 && !jobs.os93)
     {
         HIPTRY(group.alloc(&gb.v94.dBest, 128 * JF));
         HIPTRY(group.alloc(&gb.v94.dCodes, 48 * JF));
         HIPTRY(group.alloc(&gb.v94.dHdrBits, 48 * JF));
         HIPTRY(group.alloc(&gb.v94.dSmpBits, 48 * JF));
+    }
+    if (!qs.empty())
+    {
+        HIPTRY(group.alloc(&gb.a93.dChoice, NJ));
+        HIPTRY(group.alloc(&gb.a93.dRec, JF));
     }
     if (sweep.measure)
     {
@@ -1624,9 +1694,12 @@ DcsStatus EncRun::runGroup(uint32_t g)
     }
     ENCCHK(hipMemcpyAsync(gb.dJobs, hj.data(), sizeof(EncJob) * n, hipMemcpyHostToDevice, st));
     ENCCHK(hipMemcpyAsync(gb.dFJ, frameJob.data(), sizeof(uint32_t) * JF, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemsetAsync(gb.dFrameBits, 0, sizeof(uint32_t) * 3 * JF, st));
-    hipLaunchKernelGGL(encHeaderKernel, dim3(n), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, cb.dSums, gb.dHdr, gb.dKeep);
-    if (jobs.os93)
+    if (anyV != 0)
+    {
+        ENCCHK(hipMemsetAsync(gb.dFrameBits, 0, sizeof(uint32_t) * 3 * JF, st));
+        hipLaunchKernelGGL(encHeaderKernel, dim3(n), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, cb.dSums, gb.dHdr, gb.dKeep);
+    }
+    if (anyV != 0 && jobs.os93)
     {
         hipLaunchKernelGGL(enc93SearchKernel, dim3((JF + 3) / 4), dim3(128), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, cb.dSets, gb.dHdr,
                            gb.dKeep, JF, gb.o93.dRec);
@@ -1637,7 +1710,7 @@ DcsStatus EncRun::runGroup(uint32_t g)
             hipLaunchKernelGGL(enc93WalkKernel<1>, dim3((n + 63) / 64), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, gb.dFJ, gb.dKeep, JF, n,
                                gb.o93.dRec, gb.o93.dBand, gb.dFrameBits);
     }
-    else
+    if (anyV != 0 && !jobs.os93)
     {
         ENCCHK(hipMemsetAsync(gb.v94.dBest, 0, size_t(128) * JF, st));
         ENCCHK(hipMemsetAsync(gb.v94.dCodes, 0, size_t(48) * JF, st));
@@ -1648,20 +1721,40 @@ DcsStatus EncRun::runGroup(uint32_t g)
         hipLaunchKernelGGL(encBitsKernel, dim3(JF), dim3(64), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, cb.dSets, gb.dHdr, gb.dKeep, JF,
                            gb.v94.dCodes, gb.v94.dHdrBits, gb.v94.dSmpBits, gb.dFrameBits);
     }
-    hipLaunchKernelGGL(encSizeKernel, dim3(n), dim3(256), 0, st, gb.dJobs, cb.dSets, JF, gb.dFrameBits, gb.dWin, gb.dSize, gb.dFrameOff);
+    // (a job of the A family has no layout here, cmask 0: encSizeKernel leaves its win at -1, which the head and pack
+    // kernels of this family pass over)
+    if (anyV != 0)
+        hipLaunchKernelGGL(encSizeKernel, dim3(n), dim3(256), 0, st, gb.dJobs, cb.dSets, JF, gb.dFrameBits, gb.dWin, gb.dSize, gb.dFrameOff);
+    if (!qs.empty())
+        hipLaunchKernelGGL(enc93aChooseKernel, dim3(n), dim3(256), 0, st, cb.a93.dTot, cb.a93.dRowOf, in.nStreams, gb.dJobs, cb.dSets,
+                           cb.a93.dSetQ, gb.a93.dChoice);
     ENCCHK(hipGetLastError());
-    ENCCHK(hipMemcpyAsync(win.data() + j0, gb.dWin, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    ENCCHK(hipMemcpyAsync(keep.data() + j0, gb.dKeep, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    ENCCHK(hipMemcpyAsync(size.data() + j0, gb.dSize, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    if (anyV != 0)
+    {
+        ENCCHK(hipMemcpyAsync(win.data() + j0, gb.dWin, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        ENCCHK(hipMemcpyAsync(keep.data() + j0, gb.dKeep, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        ENCCHK(hipMemcpyAsync(size.data() + j0, gb.dSize, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    }
+    if (!qs.empty())
+        ENCCHK(hipMemcpyAsync(choiceA.data() + j0, gb.a93.dChoice, sizeof(Enc93aChoice) * n, hipMemcpyDeviceToHost, st));
     ENCCHK(hipStreamSynchronize(st));
+    // a Type-1 job: the candidate (1, 0) of CloseStream's list, its header's band count, 3 header bytes and the frames' bits
+    for (uint32_t k = 0 ; k < n ; ++k)
+        if (setQ[hj[k].set] != kA93None)
+        {
+            win[j0 + k] = 2;
+            keep[j0 + k] = choiceA[j0 + k].numBands;
+            size[j0 + k] = 3 + (choiceA[j0 + k].frameBits + 7) / 8;
+        }
     resident = g;
     residentFrames = JF;
     return DCS_OK;
 }
 
-// Upload, E1 and encStreamKernel; bad[] is on its way to the host, there after the first group's wait.  (The step before
-// runGroup, written after it: the kernel templates are instantiated in the order the source first launches them, and the
-// device code object keeps the order it had.)
+// Upload, E1 and encStreamKernel; bad[] is on its way to the host, there after the first group's wait; then A1 for the
+// streams that jobs of the A family name.  (The step before runGroup, written after it: the kernel templates are
+// instantiated in the order the source first launches them, and the device code object keeps the order it had.  The A
+// family's two, enc93aFrameKernel<false> here and <true> in packGroup, follow E1's and precede the resampler's.)
 DcsStatus EncRun::analyse()
 {
     const uint32_t nStreams = in.nStreams;
@@ -1681,8 +1774,25 @@ DcsStatus EncRun::analyse()
     else
         hipLaunchKernelGGL(encAnalyseKernel<float>, dim3((F + 3) / 4), dim3(256), 0, st, cb.dT, devF ? in.devFloat + first : cb.dPcm,
                            cb.dStr, cb.dFS, F, cb.dSpec, cb.dPw, cb.dLo, cb.dHi, cb.dBad, static_cast<const uint32_t *>(nullptr));
-    hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, cb.dStr, cb.dPw, cb.dLo, cb.dHi, cb.dSums);
+    if (anyV != 0)
+        hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, cb.dStr, cb.dPw, cb.dLo, cb.dHi, cb.dSums);
     ENCCHK(hipMemcpyAsync(bad.data(), cb.dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
+    if (qs.empty())
+        return DCS_OK;
+    // A1: one search per stream-frame; kA93QPerLaunch of the distinct q to a launch
+    const uint32_t nQ = static_cast<uint32_t>(qs.size());
+    floorE.resize(size_t(18) * nQ);
+    for (uint32_t k = 0 ; k < nQ ; ++k)
+        floorE93a(qs[k], floorE.data() + size_t(18) * k);
+    ENCCHK(hipMemcpyAsync(cb.a93.dA, &encTabs93a(), sizeof(Enc93aTabs), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(cb.a93.dFloorE, floorE.data(), sizeof(unsigned long long) * floorE.size(), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(cb.a93.dSetQ, setQ.data(), sizeof(uint32_t) * jobs.nSets, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(cb.a93.dRowOf, rowOf.data(), sizeof(uint32_t) * rowOf.size(), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(cb.a93.dTot, 0, sizeof(Enc93aTot) * kA93Cand * nRows, st));
+    for (uint32_t q0 = 0 ; q0 < nQ ; q0 += kA93QPerLaunch)
+        hipLaunchKernelGGL(enc93aFrameKernel<false>, dim3(F), dim3(256), 0, st, cb.a93.dA, cb.a93.dFloorE, cb.dSpec, cb.dFS, cb.a93.dRowOf,
+                           nStreams, q0, std::min(kA93QPerLaunch, nQ - q0), cb.a93.dTot, static_cast<const EncJob *>(nullptr),
+                           static_cast<const uint32_t *>(nullptr), static_cast<const Enc93aChoice *>(nullptr), static_cast<Enc93aRec *>(nullptr));
     return DCS_OK;
 }
 
@@ -1716,6 +1826,14 @@ DcsStatus EncRun::placeOutput()
                                static_cast<int32_t>(size[j]), keep[j] };
         if (to.info != nullptr)
             to.info[j] = e;
+        if (to.info93a != nullptr)
+        {
+            const DcsEncodeParams &p = jobs.sets[jobs.list[j].paramSet];
+            const Enc93aChoice &c = choiceA[j];
+            const uint64_t budget = static_cast<uint64_t>(p.targetBitRate) * static_cast<uint64_t>(e.nFrames) * 240ull / 31250ull;
+            to.info93a[j] = setQ[jobs.list[j].paramSet] == kA93None ? DcsEncode93aInfo{}
+                            : DcsEncode93aInfo{ c.selector, c.ladderIndex, c.numBands, 0, c.frameBits, budget, c.sumD };
+        }
         if (sweep.results != nullptr)
         {
             memset(&sweep.results[j], 0, sizeof(DcsSweepResult));       // (its padding too: records compare as bytes)
@@ -1748,9 +1866,11 @@ DcsStatus EncRun::layoutGroup(uint32_t g, size_t *nWords)
     {
         const int c = win[j0 + k];
         const uint16_t ver = jobs.sets[hj[k].set].formatVersion;
+        const bool a93 = setQ[hj[k].set] != kA93None;
         ss[k] = DcsSweepStream{ hj[k].nFrames, static_cast<uint32_t>(size[j0 + k]),
                                 ver == 0x9301 ? DCS_OS93A : ver == 0x9302 ? DCS_OS93B : kCandSub[c] == 3 ? DCS_OS95 : DCS_OS94, kCandType[c],
-                                jobs.os93 ? 0 : kCandSub[c], keep[j0 + k] };
+                                jobs.os93 ? 0 : kCandSub[c], keep[j0 + k],
+                                a93 ? 0x80u | static_cast<uint32_t>(choiceA[j0 + k].selector) << 5 | static_cast<uint32_t>(keep[j0 + k]) : 0u };
     }
     size_t blobBytes;
     ENCTRY(dcsSweepLayout(ss.data(), n, offs.data(), &blobLen, &blobBytes));
@@ -1769,13 +1889,25 @@ DcsStatus EncRun::packGroup(uint32_t g)
     ENCCHK(blob.alloc(&dW, nWords));
     ENCCHK(hipMemsetAsync(dW, 0, sizeof(uint32_t) * nWords, st));
     ENCCHK(hipMemcpyAsync(gb.dOutOff, offs.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(encHeadKernel, dim3(n), dim3(64), 0, st, gb.dJobs, gb.dHdr, gb.dWin, gb.dOutOff, dW);
-    if (jobs.os93)
+    if (anyV != 0)
+        hipLaunchKernelGGL(encHeadKernel, dim3(n), dim3(64), 0, st, gb.dJobs, gb.dHdr, gb.dWin, gb.dOutOff, dW);
+    if (anyV != 0 && jobs.os93)
         hipLaunchKernelGGL(enc93PackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, gb.dHdr, gb.dKeep, gb.dWin,
                            JF, gb.o93.dBand, gb.dFrameOff, gb.dOutOff, dW);
-    else
+    if (anyV != 0 && !jobs.os93)
         hipLaunchKernelGGL(encPackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, gb.dHdr, gb.dKeep, gb.dWin,
                            JF, gb.v94.dCodes, gb.v94.dHdrBits, gb.v94.dSmpBits, gb.dFrameOff, gb.dOutOff, dW);
+    if (!qs.empty())
+    {
+        // the Type-1 jobs: each job-frame's choices (A3), the frames' offsets (A4), the 3-byte headers and the pack (A5)
+        hipLaunchKernelGGL(enc93aFrameKernel<true>, dim3(JF), dim3(256), 0, st, cb.a93.dA, cb.a93.dFloorE, cb.dSpec, gb.dFJ,
+                           static_cast<const uint32_t *>(nullptr), 0u, 0u, 0u, static_cast<Enc93aTot *>(nullptr), gb.dJobs, cb.a93.dSetQ,
+                           gb.a93.dChoice, gb.a93.dRec);
+        hipLaunchKernelGGL(enc93aOffsetKernel, dim3(n), dim3(256), 0, st, gb.dJobs, cb.a93.dSetQ, gb.a93.dRec, gb.dFrameOff);
+        hipLaunchKernelGGL(enc93aHeadKernel, dim3((n + 63) / 64), dim3(64), 0, st, gb.dJobs, cb.a93.dSetQ, gb.a93.dChoice, gb.dOutOff, n, dW);
+        hipLaunchKernelGGL(enc93aPackKernel, dim3(JF), dim3(128), 0, st, cb.a93.dA, cb.dSpec, gb.dFJ, gb.dJobs, cb.a93.dSetQ, gb.a93.dChoice,
+                           gb.a93.dRec, gb.dFrameOff, gb.dOutOff, dW);
+    }
     hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
     ENCCHK(hipGetLastError());
     return DCS_OK;
@@ -1800,16 +1932,16 @@ DcsStatus EncRun::stageBlob()
     return DCS_OK;
 }
 
-// The jobs of the packed group (n of them) whose streams are decoded.  One kind is left out: an OS93a stream with no band
-// kept.  Its header is sixteen 0xFF bytes, the first of which carries the type bit, so every decoder reads it as OS93a
-// Type 1 with 31 bands; its record stays measured = 0.
+// The jobs of the packed group (n of them) whose streams are decoded.  One kind is left out: an OS93a Type-0 stream with
+// no band kept.  Its header is sixteen 0xFF bytes, the first of which carries the type bit, so every decoder reads it as
+// OS93a Type 1 with 31 bands; its record stays measured = 0.  (A Type-1 stream's header says what it is: always decoded.)
 void EncRun::selectDecodes(uint32_t n)
 {
     sel.clear(); selS.clear(); selOff.clear();
     mostFrames = 0;
     selFrames = 0;
     for (uint32_t k = 0 ; k < n ; ++k)
-        if (!(ss[k].os == DCS_OS93A && ss[k].bandsToKeep == 0))
+        if (!(ss[k].os == DCS_OS93A && ss[k].formatType == 0 && ss[k].bandsToKeep == 0))
         {
             sel.push_back(k); selS.push_back(ss[k]); selOff.push_back(offs[k]);
             mostFrames = std::max(mostFrames, hj[k].nFrames);
@@ -1914,7 +2046,7 @@ DcsStatus EncRun::run()
         return DCS_OK;
     }
     buildSets();
-    win.resize(jobs.n); keep.resize(jobs.n); size.resize(jobs.n);
+    win.resize(jobs.n); keep.resize(jobs.n); size.resize(jobs.n); choiceA.resize(jobs.n);
     ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
     ENCTRY(allocCall());
     ENCTRY(allocGroups());
@@ -1992,12 +2124,58 @@ extern "C" void dcs_encode_sweep_group_frames(uint64_t maxJobFrames)
     gGroupFrames.store(maxJobFrames);
 }
 
+namespace {
+
+// what dcs_encode_sweep and dcs_encode93a_sweep refuse before they look at a set
+bool sweepArgsValid(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, const DcsEncodeParams *sets,
+                    uint32_t nSets, uint32_t flags, const DcsSweepResult *results, const uint8_t *out, size_t outCap, const uint64_t *outOffsets)
+{
+    return !(ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || sets == nullptr || nSets == 0 || (nStreams != 0 && pcm == nullptr)
+             || (flags & ~DCS_SWEEP_MEASURE) != 0 || ((flags & DCS_SWEEP_MEASURE) != 0 && results == nullptr) || (out == nullptr && outCap != 0));
+}
+
+// ... and what they do once their sets are checked: the job list (null: every pair, stream-major), then the driver on the
+// caller's PCM
+DcsStatus sweepHostPcm(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, EncJobs js, uint32_t flags,
+                       DcsSweepResult *results, const EncOutput &to)
+{
+    const uint32_t nSets = js.nSets;
+    std::vector<DcsSweepJob> all;
+    if (js.list == nullptr)
+    {
+        if (static_cast<uint64_t>(nStreams) * nSets > 0xFFFFFFFFull)
+            return DCS_ERR_INVALID_ARG;
+        js.n = nStreams * nSets;
+        all.resize(js.n);
+        for (uint32_t j = 0 ; j < js.n ; ++j)
+            all[j] = DcsSweepJob{ j / nSets, j % nSets };
+        js.list = all.data();
+    }
+    for (uint32_t j = 0 ; j < js.n ; ++j)
+        if (js.list[j].stream >= nStreams || js.list[j].paramSet >= nSets)
+        {
+            dcsCtxSetError(ctx, ("job " + std::to_string(j) + ": names stream " + std::to_string(js.list[j].stream) + " of " + std::to_string(nStreams)
+                                 + ", set " + std::to_string(js.list[j].paramSet) + " of " + std::to_string(nSets)).c_str());
+            return DCS_ERR_INVALID_ARG;
+        }
+    EncInput in;
+    in.sampleOffsets = sampleOffsets;
+    in.nStreams = nStreams;
+    in.hostPcm = pcm;
+    EncSweep sweep;
+    sweep.results = results;
+    sweep.measure = (flags & DCS_SWEEP_MEASURE) != 0;
+    sweep.sizesOnly = to.out == nullptr;
+    return EncRun(ctx, in, js, to, sweep).run();
+}
+
+}  // namespace
+
 extern "C" DcsStatus dcs_encode_sweep(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
                                       const DcsEncodeParams *sets, uint32_t nSets, const DcsSweepJob *jobs, uint32_t nJobs,
                                       uint32_t flags, DcsSweepResult *results, uint8_t *out, size_t outCap, uint64_t *outOffsets)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || sets == nullptr || nSets == 0 || (nStreams != 0 && pcm == nullptr)
-        || (flags & ~DCS_SWEEP_MEASURE) != 0 || ((flags & DCS_SWEEP_MEASURE) != 0 && results == nullptr) || (out == nullptr && outCap != 0))
+    if (!sweepArgsValid(ctx, pcm, sampleOffsets, nStreams, sets, nSets, flags, results, out, outCap, outOffsets))
         return DCS_ERR_INVALID_ARG;
     const bool os93 = sets[0].formatVersion != 0x9400;
     for (uint32_t k = 0 ; k < nSets ; ++k)
@@ -2014,33 +2192,114 @@ extern "C" DcsStatus dcs_encode_sweep(DcsCtx *ctx, const float *pcm, const uint6
             return DCS_ERR_INVALID_ARG;
         }
     }
-    std::vector<DcsSweepJob> all;
-    if (jobs == nullptr)
+    return sweepHostPcm(ctx, pcm, sampleOffsets, nStreams, EncJobs{ sets, nSets, jobs, nJobs, os93 }, flags, results,
+                        EncOutput{ out, outCap, outOffsets, nullptr, nullptr });
+}
+
+// ------------------------------------------------------------------------------------------ OS93a, Type 0 and Type 1
+
+extern "C" size_t dcs_encode93a_bound(uint64_t nSamples)
+{
+    return std::max(boundOf(nSamples, kMaxBitsPerFrame93), boundOf(nSamples, kA93MaxFrameBits));
+}
+
+extern "C" DcsStatus dcs_encode93a_sweep(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                         const DcsEncodeParams *sets, uint32_t nSets, const DcsSweepJob *jobs, uint32_t nJobs,
+                                         uint32_t flags, DcsSweepResult *results, DcsEncode93aInfo *info93a,
+                                         uint8_t *out, size_t outCap, uint64_t *outOffsets)
+{
+    if (!sweepArgsValid(ctx, pcm, sampleOffsets, nStreams, sets, nSets, flags, results, out, outCap, outOffsets))
+        return DCS_ERR_INVALID_ARG;
+    for (uint32_t k = 0 ; k < nSets ; ++k)
     {
-        if (static_cast<uint64_t>(nStreams) * nSets > 0xFFFFFFFFull)
-            return DCS_ERR_INVALID_ARG;
-        nJobs = nStreams * nSets;
-        all.resize(nJobs);
-        for (uint32_t j = 0 ; j < nJobs ; ++j)
-            all[j] = DcsSweepJob{ j / nSets, j % nSets };
-        jobs = all.data();
-    }
-    for (uint32_t j = 0 ; j < nJobs ; ++j)
-        if (jobs[j].stream >= nStreams || jobs[j].paramSet >= nSets)
+        const std::string set = "set " + std::to_string(k);
+        if (sets[k].formatVersion != 0x9301)
         {
-            dcsCtxSetError(ctx, ("job " + std::to_string(j) + ": names stream " + std::to_string(jobs[j].stream) + " of " + std::to_string(nStreams)
-                                 + ", set " + std::to_string(jobs[j].paramSet) + " of " + std::to_string(nSets)).c_str());
+            dcsCtxSetError(ctx, (set + ": dcs_encode93a_sweep takes OS93a sets only (formatVersion 0x9301)").c_str());
             return DCS_ERR_INVALID_ARG;
         }
+        if (!paramsValid93a(&sets[k]))
+        {
+            dcsCtxSetError(ctx, (set + ": not a valid DcsEncodeParams").c_str());
+            return DCS_ERR_INVALID_ARG;
+        }
+        if (sets[k].streamFormatType < 0)
+        {
+            dcsCtxSetError(ctx, (set + ": streamFormatType -1; a sweep lists Type 0 and Type 1 as sets of their own and reports both").c_str());
+            return DCS_ERR_INVALID_ARG;
+        }
+    }
+    return sweepHostPcm(ctx, pcm, sampleOffsets, nStreams, EncJobs{ sets, nSets, jobs, nJobs, true }, flags, results,
+                        EncOutput{ out, outCap, outOffsets, nullptr, nullptr, info93a });
+}
+
+namespace {
+
+// Type 1 of every stream: one job per stream through the one driver
+DcsStatus encode93aType1(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, const DcsEncodeParams *params,
+                         const EncOutput &to)
+{
+    DcsEncodeParams p1 = *params;
+    p1.streamFormatType = 1;
     EncInput in;
     in.sampleOffsets = sampleOffsets;
     in.nStreams = nStreams;
     in.hostPcm = pcm;
-    EncSweep sweep;
-    sweep.results = results;
-    sweep.measure = (flags & DCS_SWEEP_MEASURE) != 0;
-    sweep.sizesOnly = out == nullptr;
-    return EncRun(ctx, in, EncJobs{ sets, nSets, jobs, nJobs, os93 }, EncOutput{ out, outCap, outOffsets, nullptr, nullptr }, sweep).run();
+    std::vector<DcsSweepJob> list(nStreams);
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+        list[i] = DcsSweepJob{ i, 0 };
+    return EncRun(ctx, in, EncJobs{ &p1, 1, list.data(), nStreams, true }, to, EncSweep()).run();
+}
+
+}  // namespace
+
+extern "C" DcsStatus dcs_encode93a_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                           const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                                           DcsEncodeInfo *info, DcsEncode93aInfo *info93a)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr) || !paramsValid93a(params))
+        return DCS_ERR_INVALID_ARG;
+    if (info93a != nullptr)
+        memset(info93a, 0, sizeof(DcsEncode93aInfo) * nStreams);
+    if (params->streamFormatType == 0)
+        return encodeHostPcm(ctx, pcm, sampleOffsets, nStreams, params, true, EncOutput{ out, outCap, outOffsets, info, nullptr });
+    if (params->streamFormatType == 1)
+        return encode93aType1(ctx, pcm, sampleOffsets, nStreams, params, EncOutput{ out, outCap, outOffsets, info, nullptr, info93a });
+
+    // the wildcard: both types into buffers of their own, then per stream the first strictly smallest, Type 0 first (CloseStream :805)
+    DcsEncodeParams p0 = *params;
+    p0.streamFormatType = 0;
+    std::vector<uint64_t> off0(nStreams + 1), off1(nStreams + 1);
+    std::vector<DcsEncodeInfo> inf0(nStreams), inf1(nStreams);
+    size_t cap0 = 0, cap1 = 0;
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+    {
+        const uint64_t n = sampleOffsets[i + 1] > sampleOffsets[i] ? sampleOffsets[i + 1] - sampleOffsets[i] : 0;
+        cap0 += boundOf(n, kMaxBitsPerFrame93);
+        cap1 += boundOf(n, kA93MaxFrameBits);
+    }
+    std::vector<uint8_t> buf0(cap0 + 1), buf1(cap1 + 1);
+    ENCTRY(encodeHostPcm(ctx, pcm, sampleOffsets, nStreams, &p0, true, EncOutput{ buf0.data(), buf0.size(), off0.data(), inf0.data(), nullptr }));
+    ENCTRY(encode93aType1(ctx, pcm, sampleOffsets, nStreams, params, EncOutput{ buf1.data(), buf1.size(), off1.data(), inf1.data(), nullptr, info93a }));
+    outOffsets[0] = 0;
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+    {
+        const bool one = off1[i + 1] - off1[i] < off0[i + 1] - off0[i];
+        outOffsets[i + 1] = outOffsets[i] + (one ? off1[i + 1] - off1[i] : off0[i + 1] - off0[i]);
+        if (info != nullptr)
+            info[i] = one ? inf1[i] : inf0[i];
+    }
+    if (nStreams == 0)
+        return DCS_OK;
+    if (out == nullptr || outCap < outOffsets[nStreams])
+        return DCS_ERR_CAPACITY;
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+    {
+        const uint64_t n = outOffsets[i + 1] - outOffsets[i];
+        const bool one = off1[i + 1] - off1[i] < off0[i + 1] - off0[i];
+        memcpy(out + outOffsets[i], one ? buf1.data() + off1[i] : buf0.data() + off0[i], n);
+    }
+    return DCS_OK;
 }
 
 extern "C" DcsStatus dcs_encode_fit(const uint64_t *nBytes, const uint64_t *sqErr, uint32_t nStreams, uint32_t nSets, uint64_t budget,
@@ -2193,8 +2452,3 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
 // ------------------------------------------------------------------------ encoding files (dcs_encode_files.hip.h)
 
 #include "dcs_encode_files.hip.h"
-
-// ------------------------------------------------------- OS93a Type 1, the pair-table layout (dcs_encode93a.hip.h)
-// (last: its kernels follow every other one in the code object, which keeps the order it had)
-
-#include "dcs_encode93a.hip.h"

@@ -6,21 +6,31 @@
 // quarter-octave scale code s and one index per pair into the 2^w points of kPair93a.  After one f32 multiply and one
 // roundf per coefficient (the targets) every decision is an integer one, restated in tests/enc93a_ref.py.
 //
-//   E1  encAnalyseKernel  the OS93 front end, unchanged (its spectrum is all that is read of it)
-//   A1  enc93aFrameKernel<false>  a block per frame: targets and pair table in LDS; the search D(band, w, s) = sum over the
-//                         band's pairs of the squared distance to the nearest point, a lane per (w, s, pair) with the points
-//                         in a serial loop (a wavefront shares w, so the table read is one broadcast and nothing is reduced
-//                         across lanes); then the walk, a lane per (codebook pp, lambda of the ladder), over the D table in
-//                         LDS; per-stream totals by integer atomics
-//   A2  enc93aChooseKernel  a block per stream: the candidate within the budget with the least error
-//   A3  enc93aFrameKernel<true>  the chosen candidate's search and walk again, each frame's choices to a 40-byte record
-//   A4  enc93aOffsetKernel  a block per stream: the frames' bit offsets
-//   A5  enc93aPackKernel  a block per frame: prefix and delta codes, each pair's nearest point again, OR-ed into zeroed
+// These are the kernels of a family of EncRun's (dcs_encode.hip), beside the OS93 (O3-O5) and the 1994+ (E3-E5) stages: a
+// job whose set asks for (0x9301, Type 1) runs them, a job of the same call whose set asks for Type 0 runs the O stages.
+//
+//   E1  encAnalyseKernel  the OS93 front end, unchanged (its spectrum is all that is read of it), once per stream
+//   A1  enc93aFrameKernel<false>  once per STREAM-frame, whatever the jobs: targets and pair table in LDS; the search
+//                         D(band, w, s) = sum over the band's pairs of the squared distance to the nearest point, a lane per
+//                         (w, s, pair) with the points in a serial loop (a wavefront shares w, so the table read is one
+//                         broadcast and nothing is reduced across lanes).  Neither targetBitRate nor
+//                         maximumQuantizationError is read by it.  Then the walk, a lane per (codebook pp, lambda of the
+//                         ladder), over the D table in LDS, once for every distinct maximumQuantizationError q under which a
+//                         job names the stream (E_b of q: the floorE table); totals per (q, stream, candidate) by integer
+//                         atomics, at row rowOf[q][stream] of the totals table.  A launch walks at most kA93QPerLaunch
+//                         values of q; a call with more of them launches again, and a block whose stream none of the
+//                         launch's q concerns leaves before the search
+//   A2  enc93aChooseKernel  a block per job: within its own budget, the candidate of its (q, stream) row with the least error
+//   A3  enc93aFrameKernel<true>  per job-frame: the job's chosen candidate's search and walk again under its q, the frame's
+//                         choices to a 40-byte record
+//   A4  enc93aOffsetKernel  a block per job: the frames' bit offsets
+//   A5  enc93aPackKernel  a block per job-frame: prefix and delta codes, each pair's nearest point again, OR-ed into zeroed
 //                         big-endian words; encSwapKernel turns them into bytes
 //
-// Nothing per frame is kept between A1 and A3 but E1's spectrum: 1 264 device bytes per frame (spectrum 1 024, E1's band
-// statistics 192, frame -> stream 4, record 40, offset 4), so one call holds its whole batch and a 65 535-frame stream
-// takes 83 MB.
+// Nothing per frame is kept between A1 and A3 but E1's spectrum (no D table in HBM): per stream-frame 1 220 device bytes
+// (spectrum 1 024, E1's band statistics 192, frame -> stream 4), per job-frame of the resident group 48 (record 40, offset
+// 4, job-frame -> job 4; the O stages' rows beside them where Type-0 jobs share the call), and 24 KB of totals per
+// (stream, distinct q).
 
 namespace {
 
@@ -31,12 +41,13 @@ constexpr int kA93SMin = 4, kA93SMax = 0x39, kA93Prv0 = 0x1A;
 constexpr uint32_t kA93M0 = 0xFFFE;        // OS93a's mixing multiplier at mixing level 0xFF
 constexpr float kA93K = 32768.0f;          // spec 1.0 = frame-buffer 32768 at kA93M0
 constexpr uint32_t kA93MaxFrameBits = 18 * (4 + 8) + 127 * 9;
+constexpr uint32_t kA93QPerLaunch = 8;     // distinct maximumQuantizationError values one launch of A1 walks
+constexpr uint32_t kA93None = 0xFFFFFFFFu; // setQ: a set of the O family; rowOf: no job names this stream under this q
 
 struct Enc93aTabs
 {
     uint32_t pair[1024];                   // kPair93a as words: point j of width w at (1 << w) + j, first value in the low half
     uint64_t ladder[kA93KL];
-    uint64_t floorE[18];                   // E_b of this call's maximumQuantizationError
     int32_t sfs[64], pmax[10];
     uint8_t inputs[18], first[18], bandOf[127];
     uint8_t pfxLen[4][10], pfxCode[4][10], wmax[4];
@@ -59,7 +70,15 @@ inline int a93Sfs(int s)
     return static_cast<int16_t>(sf & 0xFFFF);
 }
 
-Enc93aTabs buildTabs93a(float maxQE)
+// E_b of one maximumQuantizationError: a row of the floorE table, which has one per distinct value of the call
+void floorE93a(float maxQE, unsigned long long *row)
+{
+    const double q = static_cast<double>(maxQE);
+    for (int b = 0 ; b < 18 ; ++b)
+        row[b] = static_cast<unsigned long long>(floor(((1073741824.0 * q) * q) * static_cast<double>(2 * kInputsPerBand93a[b])));
+}
+
+Enc93aTabs buildTabs93a()
 {
     Enc93aTabs t;
     memset(&t, 0, sizeof(t));
@@ -69,7 +88,6 @@ Enc93aTabs buildTabs93a(float maxQE)
     for (int k = 1 ; k < kA93KL - 1 ; ++k)
         t.ladder[k] = static_cast<uint64_t>(2 + (k & 1)) << (k >> 1);
     t.ladder[kA93KL - 1] = 1ull << 40;
-    const double q = static_cast<double>(maxQE);
     for (int b = 0, first = 0 ; b < 18 ; ++b)
     {
         t.inputs[b] = kInputsPerBand93a[b];
@@ -77,7 +95,6 @@ Enc93aTabs buildTabs93a(float maxQE)
         for (int i = 0 ; i < t.inputs[b] ; ++i)
             t.bandOf[first + i] = static_cast<uint8_t>(b);
         first += t.inputs[b];
-        t.floorE[b] = static_cast<uint64_t>(floor(((1073741824.0 * q) * q) * static_cast<double>(2 * t.inputs[b])));
     }
     for (int s = 0 ; s < 64 ; ++s)
         t.sfs[s] = a93Sfs(s);
@@ -114,6 +131,8 @@ Enc93aTabs buildTabs93a(float maxQE)
     }
     return t;
 }
+
+const Enc93aTabs &encTabs93a() { static const Enc93aTabs t = buildTabs93a(); return t; }
 
 // what a block keeps of the tables and of its frame
 struct Enc93aLds
@@ -216,35 +235,53 @@ __device__ inline Enc93aWalk a93Walk(const Enc93aLds &S, int pp, unsigned long l
     return o;
 }
 
-// what A2 leaves per stream
+// what A2 leaves per job
 struct Enc93aChoice { int32_t selector, ladderIndex, numBands, fits; unsigned long long frameBits, sumD; };
 
-// A1 (PACK = false) and A3 (PACK = true): a block per frame
+// A1 (PACK = false), a block per stream-frame: owner = frame -> stream; the walks of q0 .. q0 + nQ - 1 (nQ at most
+// kA93QPerLaunch) into the rows rowOf[q * nStreams + stream] of tot.  A3 (PACK = true), a block per job-frame of the
+// resident group: owner = job-frame -> job; the job's choice under the q of its set (setQ), to rec.
 template <bool PACK>
-__global__ __launch_bounds__(256) void enc93aFrameKernel(const Enc93aTabs *__restrict__ Tp, const float *__restrict__ spec,
-    const uint32_t *__restrict__ frameStream, Enc93aTot *__restrict__ tot, const Enc93aChoice *__restrict__ choice,
-    Enc93aRec *__restrict__ rec)
+__global__ __launch_bounds__(256) void enc93aFrameKernel(const Enc93aTabs *__restrict__ Tp, const unsigned long long *__restrict__ floorE,
+    const float *__restrict__ spec, const uint32_t *__restrict__ owner, const uint32_t *__restrict__ rowOf, uint32_t nStreams, uint32_t q0,
+    uint32_t nQ, Enc93aTot *__restrict__ tot, const EncJob *__restrict__ jobs, const uint32_t *__restrict__ setQ,
+    const Enc93aChoice *__restrict__ choice, Enc93aRec *__restrict__ rec)
 {
     const Enc93aTabs &T = *Tp;
     __shared__ Enc93aLds S;
     const int tid = threadIdx.x;
-    const uint32_t f = blockIdx.x, si = frameStream[f];
+    const uint32_t f = blockIdx.x, own = owner[f];
+    uint32_t sf = f;
     int ppOnly = 0, wLimit = 9;
     Enc93aChoice ch = {};
     if (PACK)
     {
-        ch = choice[si];
+        const EncJob job = jobs[own];
+        const uint32_t q = setQ[job.set];
+        if (q == kA93None)
+            return;                             // a job of the O family
+        sf = encSpecFrame(job, f);
+        ch = choice[own];
         ppOnly = ch.selector;
         wLimit = T.wmax[ppOnly];
+        if (tid < 18) S.floorE[tid] = floorE[static_cast<size_t>(q) * 18 + tid];
+    }
+    else
+    {
+        bool named = false;
+        for (uint32_t k = 0 ; k < nQ ; ++k)
+            named = named || rowOf[static_cast<size_t>(q0 + k) * nStreams + own] != kA93None;
+        if (!named)
+            return;                             // (the whole block: own is the block's)
     }
     for (int i = tid ; i < 1024 ; i += 256)
         S.pair[i] = T.pair[i];
-    S.t[tid] = tid < 254 ? a93Target(spec + static_cast<size_t>(f) * 256, tid) : 0;
+    S.t[tid] = tid < 254 ? a93Target(spec + static_cast<size_t>(sf) * 256, tid) : 0;
     for (int i = tid ; i < 18 * 9 * kA93NS ; i += 256)
         (&S.D[0][0][0])[i] = 0;
     if (tid < 64) S.sfs[tid] = T.sfs[tid];
     if (tid < 10) S.pmax[tid] = T.pmax[tid];
-    if (tid < 18) { S.inputs[tid] = T.inputs[tid]; S.first[tid] = T.first[tid]; S.floorE[tid] = T.floorE[tid]; }
+    if (tid < 18) { S.inputs[tid] = T.inputs[tid]; S.first[tid] = T.first[tid]; }
     if (tid < 127) S.bandOf[tid] = T.bandOf[tid];
     if (tid < 40) (&S.pfxLen[0][0])[tid] = (&T.pfxLen[0][0])[tid];
     if (tid < 4) S.wmax[tid] = T.wmax[tid];
@@ -279,13 +316,13 @@ __global__ __launch_bounds__(256) void enc93aFrameKernel(const Enc93aTabs *__res
     {
         const int w = 1 + idx / (kA93NS * 127), r = idx % (kA93NS * 127), k = r / 127, pr = r % 127;
         const int b = S.bandOf[pr];
-        const int sf = S.sfs[S.s0[b][w - 1] + k];
+        const int sfac = S.sfs[S.s0[b][w - 1] + k];
         const int t0 = S.t[2 * pr], t1 = S.t[2 * pr + 1];
         const uint32_t *pts = S.pair + (1 << w);
-        unsigned long long best = a93Dist(pts[0], sf, t0, t1);
+        unsigned long long best = a93Dist(pts[0], sfac, t0, t1);
         for (int j = 1 ; j < (1 << w) ; ++j)
         {
-            const unsigned long long d = a93Dist(pts[j], sf, t0, t1);
+            const unsigned long long d = a93Dist(pts[j], sfac, t0, t1);
             best = d < best ? d : best;
         }
         atomicAdd(&S.D[b][w - 1][k], best);
@@ -294,12 +331,23 @@ __global__ __launch_bounds__(256) void enc93aFrameKernel(const Enc93aTabs *__res
 
     if (!PACK)
     {
+        // the D table is walked once per q of the launch that a job names the stream under; only E_b changes between them
         const int pp = tid >> 6;
-        const Enc93aWalk o = a93Walk(S, pp, T.ladder[tid & 63], nullptr, nullptr);
-        Enc93aTot *p = tot + static_cast<size_t>(si) * kA93Cand + tid;
-        atomicAdd(&p->bits, static_cast<unsigned long long>(o.through));
-        atomicAdd(&p->sumD, o.sumD);
-        atomicAdd(&p->hist[o.last + 1], 1u);
+        const unsigned long long lam = T.ladder[tid & 63];
+        for (uint32_t k = 0 ; k < nQ ; ++k)
+        {
+            const uint32_t row = rowOf[static_cast<size_t>(q0 + k) * nStreams + own];
+            if (row == kA93None)
+                continue;
+            if (tid < 18) S.floorE[tid] = floorE[static_cast<size_t>(q0 + k) * 18 + tid];
+            __syncthreads();
+            const Enc93aWalk o = a93Walk(S, pp, lam, nullptr, nullptr);
+            Enc93aTot *p = tot + static_cast<size_t>(row) * kA93Cand + tid;
+            atomicAdd(&p->bits, static_cast<unsigned long long>(o.through));
+            atomicAdd(&p->sumD, o.sumD);
+            atomicAdd(&p->hist[o.last + 1], 1u);
+            __syncthreads();
+        }
     }
     else if (tid == 0)
     {
@@ -313,14 +361,21 @@ __global__ __launch_bounds__(256) void enc93aFrameKernel(const Enc93aTabs *__res
     }
 }
 
-// A2: a block per stream, a thread per candidate; thread 0 picks
-__global__ __launch_bounds__(256) void enc93aChooseKernel(const Enc93aTot *__restrict__ tot, const unsigned long long *__restrict__ budget,
+// A2: a block per job of the resident group, a thread per candidate of its (q, stream) row; thread 0 picks within the
+// job's budget, floor(targetBitRate * nFrames * 240 / 31250) bits
+__global__ __launch_bounds__(256) void enc93aChooseKernel(const Enc93aTot *__restrict__ tot, const uint32_t *__restrict__ rowOf,
+    uint32_t nStreams, const EncJob *__restrict__ jobs, const EncSet *__restrict__ sets, const uint32_t *__restrict__ setQ,
     Enc93aChoice *__restrict__ choice)
 {
     __shared__ unsigned long long sBits[kA93Cand], sD[kA93Cand];
     __shared__ int sBands[kA93Cand];
     const int c = threadIdx.x;
-    const Enc93aTot &t = tot[static_cast<size_t>(blockIdx.x) * kA93Cand + c];      // (read in place: a copy indexed by a loop would live in scratch)
+    const EncJob job = jobs[blockIdx.x];
+    const uint32_t q = setQ[job.set];
+    if (q == kA93None)
+        return;
+    const uint32_t row = rowOf[static_cast<size_t>(q) * nStreams + job.stream];
+    const Enc93aTot &t = tot[static_cast<size_t>(row) * kA93Cand + c];      // (read in place: a copy indexed by a loop would live in scratch)
     int numBands = 1;
     for (int i = 1 ; i < 19 ; ++i)
         if (t.hist[i] != 0)
@@ -334,7 +389,7 @@ __global__ __launch_bounds__(256) void enc93aChooseKernel(const Enc93aTot *__res
     __syncthreads();
     if (c != 0)
         return;
-    const unsigned long long cap = budget[blockIdx.x];
+    const unsigned long long cap = static_cast<unsigned long long>(sets[job.set].rate) * job.nFrames * 240ull / 31250ull;
     int best = -1, least = 0;
     for (int k = 0 ; k < kA93Cand ; ++k)
     {
@@ -347,13 +402,15 @@ __global__ __launch_bounds__(256) void enc93aChooseKernel(const Enc93aTot *__res
     choice[blockIdx.x] = Enc93aChoice{ win / kA93KL, win % kA93KL, sBands[win], best >= 0 ? 1 : 0, sBits[win], sD[win] };
 }
 
-// A4: a block per stream: the exclusive scan of its frames' bits
-__global__ __launch_bounds__(256) void enc93aOffsetKernel(const EncStream *__restrict__ streams, const Enc93aRec *__restrict__ rec,
-    uint32_t *__restrict__ frameOff)
+// A4: a block per job: the exclusive scan of its frames' bits
+__global__ __launch_bounds__(256) void enc93aOffsetKernel(const EncJob *__restrict__ jobs, const uint32_t *__restrict__ setQ,
+    const Enc93aRec *__restrict__ rec, uint32_t *__restrict__ frameOff)
 {
     __shared__ uint32_t scan[256];
     __shared__ uint32_t carry;
-    const EncStream s = streams[blockIdx.x];
+    const EncJob s = jobs[blockIdx.x];
+    if (setQ[s.set] == kA93None)
+        return;
     const int t = threadIdx.x;
     if (t == 0)
         carry = 0;
@@ -380,30 +437,35 @@ __global__ __launch_bounds__(256) void enc93aOffsetKernel(const EncStream *__res
     }
 }
 
-// the frame count and the header byte 1 pp bbbbb
-__global__ __launch_bounds__(64) void enc93aHeadKernel(const EncStream *__restrict__ streams, const Enc93aChoice *__restrict__ choice,
-    const uint64_t *__restrict__ outOff, uint32_t n, uint32_t *__restrict__ W)
+// the frame count and the header byte 1 pp bbbbb of each Type-1 job of the group
+__global__ __launch_bounds__(64) void enc93aHeadKernel(const EncJob *__restrict__ jobs, const uint32_t *__restrict__ setQ,
+    const Enc93aChoice *__restrict__ choice, const uint64_t *__restrict__ outOff, uint32_t n, uint32_t *__restrict__ W)
 {
     const uint32_t si = blockIdx.x * 64 + threadIdx.x;
-    if (si >= n)
+    if (si >= n || setQ[jobs[si].set] == kA93None)
         return;
-    const uint32_t nF = streams[si].nFrames;
+    const uint32_t nF = jobs[si].nFrames;
     const Enc93aChoice c = choice[si];
     encPut(W, outOff[si] * 8, (nF << 8) | 0x80u | (static_cast<uint32_t>(c.selector) << 5) | static_cast<uint32_t>(c.numBands), 24);
 }
 
-// A5: a block per frame.  Lane 0 walks the bands for their bit positions and writes the prefix and delta codes; then a
+// A5: a block per job-frame.  Lane 0 walks the bands for their bit positions and writes the prefix and delta codes; then a
 // lane per pair finds its nearest point again (the lowest index of a tie: the loop runs upwards and replaces on less only)
 __global__ __launch_bounds__(128) void enc93aPackKernel(const Enc93aTabs *__restrict__ Tp, const float *__restrict__ spec,
-    const uint32_t *__restrict__ frameStream, const Enc93aChoice *__restrict__ choice, const Enc93aRec *__restrict__ rec,
-    const uint32_t *__restrict__ frameOff, const uint64_t *__restrict__ outOff, uint32_t *__restrict__ W)
+    const uint32_t *__restrict__ frameJob, const EncJob *__restrict__ jobs, const uint32_t *__restrict__ setQ,
+    const Enc93aChoice *__restrict__ choice, const Enc93aRec *__restrict__ rec, const uint32_t *__restrict__ frameOff,
+    const uint64_t *__restrict__ outOff, uint32_t *__restrict__ W)
 {
     const Enc93aTabs &T = *Tp;
     __shared__ uint32_t pair[1024];
     __shared__ uint32_t idxPos[18];
     __shared__ Enc93aRec sr;
     const int tid = threadIdx.x;
-    const uint32_t f = blockIdx.x, si = frameStream[f];
+    const uint32_t f = blockIdx.x, si = frameJob[f];
+    const EncJob job = jobs[si];
+    if (setQ[job.set] == kA93None)
+        return;
+    const float *frame = spec + static_cast<size_t>(encSpecFrame(job, f)) * 256;
     for (int i = tid ; i < 1024 ; i += 128)
         pair[i] = T.pair[i];
     if (tid == 0)
@@ -440,7 +502,7 @@ __global__ __launch_bounds__(128) void enc93aPackKernel(const Enc93aTabs *__rest
     if (b > sr.last || sr.w[b] == 0)
         return;
     const int w = sr.w[b], sf = T.sfs[sr.s[b]];
-    const int t0 = a93Target(spec + static_cast<size_t>(f) * 256, 2 * tid), t1 = a93Target(spec + static_cast<size_t>(f) * 256, 2 * tid + 1);
+    const int t0 = a93Target(frame, 2 * tid), t1 = a93Target(frame, 2 * tid + 1);
     const uint32_t *pts = pair + (1 << w);
     unsigned long long best = a93Dist(pts[0], sf, t0, t1);
     uint32_t at = 0;
@@ -459,170 +521,7 @@ bool paramsValid93a(const DcsEncodeParams *p)
         && isfinite(p->powerBandCutoff) && isfinite(p->minimumDynamicRange) && isfinite(p->maximumQuantizationError);
 }
 
-// Type 1 of every stream: the driver of one call.  Its steps, in order: the streams' lengths; the call's buffers; upload,
-// E1, A1, A2 and a wait (the choices and E1's flags are on the host); sizes, outOffsets, info and the capacity check; A3-A5,
-// the swap, the download and a wait.
-DcsStatus encode93aType1(DcsCtx *ctx, const float *pcm, const uint64_t *so, uint32_t nStreams, const DcsEncodeParams *params,
-                         uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncode93aInfo *info93a)
-{
-    const hipStream_t st = dcsCtxStream(ctx);
-    std::vector<EncStream> hs(nStreams);
-    std::vector<uint32_t> frameStream;
-    std::vector<unsigned long long> budget(nStreams);
-    uint32_t F = 0;
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-    {
-        if (so[i + 1] <= so[i])
-        {
-            dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": empty").c_str());
-            return DCS_ERR_INVALID_ARG;
-        }
-        const uint64_t n = so[i + 1] - so[i], nF = (n + 239) / 240;
-        if (nF > 65535)
-        {
-            dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": more than 65 535 frames").c_str());
-            return DCS_ERR_INVALID_ARG;
-        }
-        hs[i] = EncStream{ so[i] - so[0], static_cast<uint32_t>(n), F, static_cast<uint32_t>(nF), 0u, 1.0f };
-        frameStream.insert(frameStream.end(), static_cast<size_t>(nF), i);
-        budget[i] = static_cast<unsigned long long>(params->targetBitRate) * nF * 240ull / 31250ull;
-        F += static_cast<uint32_t>(nF);
-    }
-    outOffsets[0] = 0;
-    if (nStreams == 0)
-        return DCS_OK;
-    ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
-
-    CacheArena call(ctx), blob(ctx);
-    EncTabs *dT; Enc93aTabs *dA; float *dPcm, *dSpec, *dPw, *dLo, *dHi; EncStream *dStr; uint32_t *dFS, *dBad, *dFrameOff;
-    Enc93aTot *dTot; Enc93aChoice *dChoice; Enc93aRec *dRec; unsigned long long *dBudget; uint64_t *dOutOff;
-    const uint64_t nSamples = so[nStreams] - so[0];
-    ENCCHK(call.alloc(&dT, 1));
-    ENCCHK(call.alloc(&dA, 1));
-    ENCCHK(call.alloc(&dPcm, nSamples));
-    ENCCHK(call.alloc(&dStr, nStreams));
-    ENCCHK(call.alloc(&dFS, F));
-    ENCCHK(call.alloc(&dSpec, size_t(256) * F));
-    ENCCHK(call.alloc(&dPw, size_t(16) * F));
-    ENCCHK(call.alloc(&dLo, size_t(16) * F));
-    ENCCHK(call.alloc(&dHi, size_t(16) * F));
-    ENCCHK(call.alloc(&dBad, nStreams));
-    ENCCHK(call.alloc(&dTot, size_t(kA93Cand) * nStreams));
-    ENCCHK(call.alloc(&dChoice, nStreams));
-    ENCCHK(call.alloc(&dBudget, nStreams));
-    ENCCHK(call.alloc(&dOutOff, nStreams));
-    ENCCHK(call.alloc(&dRec, F));
-    ENCCHK(call.alloc(&dFrameOff, F));
-
-    const Enc93aTabs tabs = buildTabs93a(params->maximumQuantizationError);
-    std::vector<uint32_t> bad(nStreams);
-    std::vector<Enc93aChoice> choice(nStreams);
-    ENCCHK(hipMemcpyAsync(dT, &encTabs93(), sizeof(EncTabs), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(dA, &tabs, sizeof(Enc93aTabs), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(dPcm, pcm + so[0], sizeof(float) * nSamples, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(EncStream) * nStreams, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(dFS, frameStream.data(), sizeof(uint32_t) * F, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(dBudget, budget.data(), sizeof(unsigned long long) * nStreams, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemsetAsync(dBad, 0, sizeof(uint32_t) * nStreams, st));
-    ENCCHK(hipMemsetAsync(dTot, 0, sizeof(Enc93aTot) * kA93Cand * nStreams, st));
-    hipLaunchKernelGGL(encAnalyseKernel<float>, dim3((F + 3) / 4), dim3(256), 0, st, dT, dPcm, dStr, dFS, F, dSpec, dPw, dLo, dHi, dBad,
-                       static_cast<const uint32_t *>(nullptr));
-    hipLaunchKernelGGL(enc93aFrameKernel<false>, dim3(F), dim3(256), 0, st, dA, dSpec, dFS, dTot, static_cast<const Enc93aChoice *>(nullptr),
-                       static_cast<Enc93aRec *>(nullptr));
-    hipLaunchKernelGGL(enc93aChooseKernel, dim3(nStreams), dim3(256), 0, st, dTot, dBudget, dChoice);
-    ENCCHK(hipGetLastError());
-    ENCCHK(hipMemcpyAsync(bad.data(), dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
-    ENCCHK(hipMemcpyAsync(choice.data(), dChoice, sizeof(Enc93aChoice) * nStreams, hipMemcpyDeviceToHost, st));
-    ENCCHK(hipStreamSynchronize(st));
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-        if (bad[i])
-        {
-            dcsCtxSetError(ctx, ("stream " + std::to_string(i) + ": a sample is not finite or |x| > 1").c_str());
-            return DCS_ERR_BAD_STREAM;
-        }
-
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-    {
-        const Enc93aChoice &c = choice[i];
-        const uint64_t size = 3 + (c.frameBits + 7) / 8;
-        outOffsets[i + 1] = outOffsets[i] + size;
-        if (info != nullptr)
-            info[i] = DcsEncodeInfo{ 1, 0, static_cast<int32_t>(hs[i].nFrames), static_cast<int32_t>(size), c.numBands };
-        if (info93a != nullptr)
-            info93a[i] = DcsEncode93aInfo{ c.selector, c.ladderIndex, c.numBands, 0, c.frameBits, budget[i], c.sumD };
-    }
-    const uint64_t total = outOffsets[nStreams];
-    if (out == nullptr || outCap < total)
-        return DCS_ERR_CAPACITY;
-
-    uint32_t *dW;
-    const size_t nWords = static_cast<size_t>(total / 4 + 2);
-    ENCCHK(blob.alloc(&dW, nWords));
-    ENCCHK(hipMemsetAsync(dW, 0, sizeof(uint32_t) * nWords, st));
-    ENCCHK(hipMemcpyAsync(dOutOff, outOffsets, sizeof(uint64_t) * nStreams, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(enc93aFrameKernel<true>, dim3(F), dim3(256), 0, st, dA, dSpec, dFS, static_cast<Enc93aTot *>(nullptr), dChoice, dRec);
-    hipLaunchKernelGGL(enc93aOffsetKernel, dim3(nStreams), dim3(256), 0, st, dStr, dRec, dFrameOff);
-    hipLaunchKernelGGL(enc93aHeadKernel, dim3((nStreams + 63) / 64), dim3(64), 0, st, dStr, dChoice, dOutOff, nStreams, dW);
-    hipLaunchKernelGGL(enc93aPackKernel, dim3(F), dim3(128), 0, st, dA, dSpec, dFS, dChoice, dRec, dFrameOff, dOutOff, dW);
-    hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
-    ENCCHK(hipGetLastError());
-    ENCCHK(hipMemcpyAsync(out, dW, total, hipMemcpyDeviceToHost, st));
-    ENCCHK(hipStreamSynchronize(st));
-    return DCS_OK;
-}
+// a set of the A family: EncRun runs the kernels above on its jobs, the O stages on every other job of an OS93 call
+inline bool isType1Of93a(const DcsEncodeParams &p) { return p.formatVersion == 0x9301 && p.streamFormatType == 1; }
 
 }  // namespace
-
-extern "C" size_t dcs_encode93a_bound(uint64_t nSamples)
-{
-    return std::max(boundOf(nSamples, kMaxBitsPerFrame93), boundOf(nSamples, kA93MaxFrameBits));
-}
-
-extern "C" DcsStatus dcs_encode93a_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
-                                           const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
-                                           DcsEncodeInfo *info, DcsEncode93aInfo *info93a)
-{
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr) || !paramsValid93a(params))
-        return DCS_ERR_INVALID_ARG;
-    if (info93a != nullptr)
-        memset(info93a, 0, sizeof(DcsEncode93aInfo) * nStreams);
-    if (params->streamFormatType == 0)
-        return encodeHostPcm(ctx, pcm, sampleOffsets, nStreams, params, true, EncOutput{ out, outCap, outOffsets, info, nullptr });
-    if (params->streamFormatType == 1)
-        return encode93aType1(ctx, pcm, sampleOffsets, nStreams, params, out, outCap, outOffsets, info, info93a);
-
-    // the wildcard: both types into buffers of their own, then per stream the first strictly smallest, Type 0 first (CloseStream :805)
-    DcsEncodeParams p0 = *params;
-    p0.streamFormatType = 0;
-    std::vector<uint64_t> off0(nStreams + 1), off1(nStreams + 1);
-    std::vector<DcsEncodeInfo> inf0(nStreams), inf1(nStreams);
-    size_t cap0 = 0, cap1 = 0;
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-    {
-        const uint64_t n = sampleOffsets[i + 1] > sampleOffsets[i] ? sampleOffsets[i + 1] - sampleOffsets[i] : 0;
-        cap0 += boundOf(n, kMaxBitsPerFrame93);
-        cap1 += boundOf(n, kA93MaxFrameBits);
-    }
-    std::vector<uint8_t> buf0(cap0 + 1), buf1(cap1 + 1);
-    ENCTRY(encodeHostPcm(ctx, pcm, sampleOffsets, nStreams, &p0, true, EncOutput{ buf0.data(), buf0.size(), off0.data(), inf0.data(), nullptr }));
-    ENCTRY(encode93aType1(ctx, pcm, sampleOffsets, nStreams, params, buf1.data(), buf1.size(), off1.data(), inf1.data(), info93a));
-    outOffsets[0] = 0;
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-    {
-        const bool one = off1[i + 1] - off1[i] < off0[i + 1] - off0[i];
-        outOffsets[i + 1] = outOffsets[i] + (one ? off1[i + 1] - off1[i] : off0[i + 1] - off0[i]);
-        if (info != nullptr)
-            info[i] = one ? inf1[i] : inf0[i];
-    }
-    if (nStreams == 0)
-        return DCS_OK;
-    if (out == nullptr || outCap < outOffsets[nStreams])
-        return DCS_ERR_CAPACITY;
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-    {
-        const uint64_t n = outOffsets[i + 1] - outOffsets[i];
-        const bool one = off1[i + 1] - off1[i] < off0[i + 1] - off0[i];
-        memcpy(out + outOffsets[i], one ? buf1.data() + off1[i] : buf0.data() + off0[i], n);
-    }
-    return DCS_OK;
-}

@@ -1,4 +1,4 @@
-// dcs_sweep.hip.h -- the decode half of dcs_encode_sweep's DCS_SWEEP_MEASURE (dcs_encode.hip): the streams the encoder has
+// dcs_sweep.hip.h -- the decode half of DCS_SWEEP_MEASURE (dcs_encode_sweep and dcs_encode93a_sweep, dcs_encode.hip): the streams the encoder has
 // just packed, decoded with one extra frame where they lie in HBM.  Included at the end of dcs_runtime.hip, behind
 // dcs_transcode.hip.h, whose two ways of queueing a decode these are: the device path (dcsIndexWaveKernel, the device
 // planner and packer, dcsDecodeKernel) on a blob that is already resident, and the host-planned batch on the same bytes
@@ -6,8 +6,14 @@
 // unity setting.
 #pragma once
 
-// what the encoder knows of a stream it has sized (dcs_encode.hip declares the same)
-struct DcsSweepStream { uint32_t nFrames, nBytes; int32_t os, formatType, formatSubType, bandsToKeep; };
+// what the encoder knows of a stream it has sized (dcs_encode.hip declares the same); head: the third byte of an OS93a
+// Type-1 stream, 1 pp bbbbb, not read of any other
+struct DcsSweepStream { uint32_t nFrames, nBytes; int32_t os, formatType, formatSubType, bandsToKeep; uint32_t head; };
+
+// an OS93a Type-1 stream: a 3-byte header (the frame count and `head`) and at least one byte of frames; every other layout
+// has the frame count and 16 header bytes
+static bool sweepIs93aType1(const DcsSweepStream &s) { return s.os == DCS_OS93A && s.formatType == 1; }
+static uint32_t sweepMinBytes(const DcsSweepStream &s) { return sweepIs93aType1(s) ? 4 : 18; }
 
 struct DcsSweepDecode
 {
@@ -20,7 +26,9 @@ struct DcsSweepDecode
 // and the 1994+ sub-type bits.  The encoder knows them before the bytes exist anywhere but in HBM: heads = those five
 // bytes per stream, refs = streams of nBytes bytes that begin with them.  The header byte of a band that is not kept is
 // 0xFF, top bit included: a stream that keeps fewer than 1 / 2 / 3 bands has the bit of header byte 0 / 1 / 2 set whatever
-// its layout, and every decoder reads it so (encHeader, dcs_encode.hip).
+// its layout, and every decoder reads it so (encHeader, dcs_encode.hip).  An OS93a Type-1 stream has no such bytes: its
+// third byte is its whole header and is given as it is; of it the stream table reads the top bit, which makes the stream
+// OS93a Type 1 with a 1-byte header (planTableFor), and nothing of bytes 3 and 4, which are frame data.
 static void sweepRefs(const DcsSweepStream *s, uint32_t n, std::vector<uint8_t> &heads, std::vector<DcsStreamRef> &refs)
 {
     heads.assign(static_cast<size_t>(n) * 8, 0);
@@ -30,9 +38,14 @@ static void sweepRefs(const DcsSweepStream *s, uint32_t n, std::vector<uint8_t> 
         uint8_t *h = heads.data() + static_cast<size_t>(k) * 8;
         h[0] = static_cast<uint8_t>(s[k].nFrames >> 8);
         h[1] = static_cast<uint8_t>(s[k].nFrames & 0xFF);
-        h[2] = (s[k].formatType != 0 || s[k].bandsToKeep < 1) ? 0x80 : 0;
-        h[3] = ((s[k].formatSubType & 2) != 0 || s[k].bandsToKeep < 2) ? 0x80 : 0;
-        h[4] = ((s[k].formatSubType & 1) != 0 || s[k].bandsToKeep < 3) ? 0x80 : 0;
+        if (sweepIs93aType1(s[k]))
+            h[2] = static_cast<uint8_t>(s[k].head);
+        else
+        {
+            h[2] = (s[k].formatType != 0 || s[k].bandsToKeep < 1) ? 0x80 : 0;
+            h[3] = ((s[k].formatSubType & 2) != 0 || s[k].bandsToKeep < 2) ? 0x80 : 0;
+            h[4] = ((s[k].formatSubType & 1) != 0 || s[k].bandsToKeep < 3) ? 0x80 : 0;
+        }
         refs[k] = DcsStreamRef{ h, s[k].nBytes, s[k].os, 0xFF, 0xFF, 0xFF };
     }
 }
@@ -91,7 +104,7 @@ DcsStatus dcsSweepDecodeStart(DcsCtx *ctx, const DcsSweepStream *s, uint32_t n, 
             d.locs.resize(n);
             for (uint32_t k = 0 ; k < n ; ++k)
             {
-                if (s[k].nFrames == 0 || s[k].nBytes < 18 || offs[k] + s[k].nBytes > blobLen)
+                if (s[k].nFrames == 0 || s[k].nBytes < sweepMinBytes(s[k]) || offs[k] + s[k].nBytes > blobLen)
                     return DCS_ERR_INVALID_ARG;
                 d.locs[k].off = offs[k]; d.locs[k].len = s[k].nBytes; d.locs[k].os = s[k].os; d.locs[k].firstRecord = totalRec;
                 firstRecord[k] = totalRec;

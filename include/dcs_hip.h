@@ -45,7 +45,8 @@ extern "C" {
                                           DcsEncodeFileInfo, DCS_WAV_*, DCS_FILE_*, dcs_wav_parse, dcs_wav_decode,
                                           dcs_encode_files_plan, dcs_encode_files); sweeping and fitting (DcsSweepJob,
                                           DcsSweepResult, DCS_SWEEP_MEASURE, dcs_encode_sweep,
-                                          dcs_encode_sweep_group_frames, dcs_encode_fit); FLAC files (DcsFlacInfo,
+                                          dcs_encode_sweep_group_frames, dcs_encode_fit, dcs_encode93a_sweep); FLAC
+                                          files (DcsFlacInfo,
                                           DcsFlacFrame, DCS_WAV_S8, DCS_FILE_FLAC, dcs_flac_parse, dcs_flac_index,
                                           dcs_flac_decode; dcs_encode_files and dcs_encode_files_plan take FLAC files); level
                                           control (DcsLevel, DcsLevelInfo, DCS_LEVEL_*, dcs_level_gain, dcs_level_streams,
@@ -1376,6 +1377,24 @@ void      dcs_encode_sweep_group_frames(uint64_t maxJobFrames);
  * DCS_ERR_INVALID_ARG: nStreams or nSets 0, a NULL pointer. */
 DcsStatus dcs_encode_fit(const uint64_t *nBytes, const uint64_t *sqErr, uint32_t nStreams, uint32_t nSets, uint64_t budget,
                          int32_t *choiceOut, uint64_t *totalOut);
+
+/* The sweep for OS93a, both of its layouts: dcs_encode_sweep's contract word for word (job list, sizes only, capacity,
+ * DCS_SWEEP_MEASURE and its sums, errors and messages, groups), except:
+ *   sets    every set has formatVersion 0x9301 and streamFormatType 0 or 1, otherwise checked as dcs_encode93a_streams
+ *           checks it; Type-0 and Type-1 sets may share a call, so that a fit can choose the layout per stream.  The
+ *           wildcard -1 is DCS_ERR_INVALID_ARG with the set named: list both types as sets of their own and both are
+ *           reported, where the wildcard would drop one.
+ *   results job j's bytes and `enc` are exactly what dcs_encode93a_streams returns for that stream alone with that set.
+ *   info93a nJobs records (may be NULL): that call's DcsEncode93aInfo, zeros for a Type-0 job.
+ * A Type-1 stream's size has one knob, targetBitRate, and nothing before the choice among a stream's 256 candidate totals
+ * reads it: the search runs once per stream-frame however many rates the stream is encoded at, its walk once per distinct
+ * maximumQuantizationError under which a job names the stream.  A Type-1 job is always measured (the
+ * exception above concerns a Type-0 header).  Memory beyond the analysis: 24 KB per (stream, distinct
+ * maximumQuantizationError) and 48 bytes per Type-1 job-frame.  dcs_encode_sweep itself keeps refusing (0x9301, Type 1). */
+DcsStatus dcs_encode93a_sweep(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                              const DcsEncodeParams *sets, uint32_t nSets, const DcsSweepJob *jobs, uint32_t nJobs,
+                              uint32_t flags, DcsSweepResult *results, DcsEncode93aInfo *info93a,
+                              uint8_t *out, size_t outCap, uint64_t *outOffsets);
 
 uint32_t dcs_abi_version(void);
 /* a digest of the sources and compiler flags this library was built from (16 hex digits).  Counter profiles under

@@ -4,8 +4,10 @@ decoded and compared with its source in one call, the PCM resident in HBM) again
 the one-set entry points only (encode_streams once per set -> decode_streams with extra_frames = 1 -> the sums in numpy),
 and the sweep without the measurement against the encode_streams calls alone.  Six bit rates, wildcard layout, for 256
 streams x 1 000 frames and for 4 streams x 20 000 frames; the two paths timed alternately in one process after a warm-up,
-each to the call's return; bytes and sums compared.  --rocprof: per-kernel times of the measuring sweep from `rocprofv3
---kernel-trace --stats`, in a run of their own.  Prints one JSON line."""
+each to the call's return; bytes and sums compared.  --version 9301 --type 1: dcs_encode93a_sweep, OS93a Type-1 sets at the
+six rates and one maximumQuantizationError (one search per stream-frame serves all six), against one encode93a_streams call
+per set, for 256 streams x 256 frames.  --rocprof: per-kernel times of the measuring sweep from `rocprofv3 --kernel-trace
+--stats`, in a run of their own.  Prints one JSON line."""
 import argparse
 import csv
 import glob
@@ -25,6 +27,8 @@ import dcsexplorer_amd as D                     # noqa: E402
 
 RATES = (256000, 192000, 128000, 96000, 64000, 48000)
 SHAPES = {"batch_256x1000": (256, 1000), "long_4x20000": (4, 20000)}
+SHAPES_93A = {"batch_256x256": (256, 256)}
+TYPE1 = False                   # --version 9301 --type 1
 KEYS = ("sumSrcSq", "sumDecSq", "sumCross", "peakErr")
 
 
@@ -41,22 +45,23 @@ def signals(n_streams, n_frames, seed):
 
 
 def sweep(ctx, pcm, sets, measure):
-    streams, res = ctx.encode_sweep(pcm, sets, measure=measure)
+    streams, res = (ctx.encode93a_sweep if TYPE1 else ctx.encode_sweep)(pcm, sets, measure=measure)[:2]
     return streams, [tuple(int(r[k]) for k in KEYS) for r in res] if measure else None
 
 
 def composed(ctx, pcm, sets, measure):
-    """one encode_streams call per set; measuring: each set's streams decoded with one extra frame, and numpy's sums"""
+    """one encode_streams (encode93a_streams) call per set; measuring: each set's streams decoded with one extra frame, and
+    numpy's sums"""
     n, k = len(pcm), len(sets)
     streams, sums = [None] * (n * k), [None] * (n * k)
     q = [x.astype(np.int64) for x in pcm] if measure else None
     for r, rate in enumerate(RATES):
-        enc, info = ctx.encode_streams(pcm, None, targetBitRate=rate)
+        enc, info = ctx.encode93a_streams(pcm, D.FMT_93A_T1, targetBitRate=rate)[:2] if TYPE1 else ctx.encode_streams(pcm, None, targetBitRate=rate)
         for i, s in enumerate(enc):
             streams[i * k + r] = s
         if not measure:
             continue
-        items = [(D.OS95 if inf["formatSubType"] == 3 else D.OS94, s, 255, 255) for s, inf in zip(enc, info)]
+        items = [(D.OS93A if TYPE1 else D.OS95 if inf["formatSubType"] == 3 else D.OS94, s, 255, 255) for s, inf in zip(enc, info)]
         dec, err, first = ctx.decode_streams(items, extra_frames=1)
         if err.any():
             raise RuntimeError("decode error in an encoded stream")
@@ -84,7 +89,7 @@ def timed(ctx, pcm, sets, measure, iters):
 def rocprof():
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "sw", "--",
-               sys.executable, os.path.abspath(__file__), "--sweep-only"]
+               sys.executable, os.path.abspath(__file__), "--sweep-only"] + (["--version", "9301", "--type", "1"] if TYPE1 else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             return dict(error="rocprofv3 exit %d" % r.returncode, stderr=r.stderr[-800:])
@@ -103,23 +108,29 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--sweep-only", action="store_true", help="(the profiled run) one measuring sweep of the 256 x 1 000 batch")
+    ap.add_argument("--version", choices=["9400", "9301"], default="9400")
+    ap.add_argument("--type", type=int, choices=[1], default=None, help="with --version 9301: dcs_encode93a_sweep over OS93a Type-1 sets")
     a = ap.parse_args()
+    if (a.version == "9301") != (a.type == 1):
+        ap.error("--version 9301 and --type 1 go together")
+    global TYPE1
+    TYPE1 = a.type == 1
     if a.rocprof:
         print(json.dumps(dict(rocprof=rocprof())))
         return
-    sets = [D.encode_params(None, targetBitRate=r) for r in RATES]
+    sets = [D.encode93a_params(D.FMT_93A_T1, targetBitRate=r) if TYPE1 else D.encode_params(None, targetBitRate=r) for r in RATES]
     ctx = D.Context(0)
     if a.sweep_only:
-        ctx.encode_sweep(signals(256, 1000, 0x5EE0), sets)
+        sweep(ctx, signals(256, 256 if TYPE1 else 1000, 0x5EE0), sets, True)
         ctx.close()
         return
     res = {}
-    for name, (n, frames) in SHAPES.items():
+    for name, (n, frames) in (SHAPES_93A if TYPE1 else SHAPES).items():
         pcm = signals(n, frames, 0x5EE0)
         res[name] = dict(job_frames=n * frames * len(sets), measured=timed(ctx, pcm, sets, True, a.iters),
                          bytes_only=timed(ctx, pcm, sets, False, a.iters))
     ctx.close()
-    print(json.dumps(dict(results=res, all_equal=all(v[m]["bytes_equal"] and v[m]["sums_equal"] for v in res.values()
+    print(json.dumps(dict(build_id=D.build_id(), results=res, all_equal=all(v[m]["bytes_equal"] and v[m]["sums_equal"] for v in res.values()
                                                      for m in ("measured", "bytes_only")))))
 
 
