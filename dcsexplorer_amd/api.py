@@ -206,6 +206,7 @@ ABI_VERSION = 9                 # include/dcs_hip.h DCS_ABI_VERSION these bindin
 EXPORTS = [
     "dcs_index_stream_mids", "dcs_index_streams_mids", "dcs_batch_create_mids", "dcs_ctx_set_even_deal", "dcs_batch_even_deal",
     "dcs_pack_chunks_mids", "dcs_even_deal_lane", "dcs_ctx_set_sole_source_kernel", "dcs_batch_sole_source_kernel",
+    "dcs_batch_filled_bands", "dcs_prepass_short",
     "dcs_abi_version", "dcs_build_id", "dcs_index_stream", "dcs_volume_multiplier", "dcs_mixing_multiplier", "dcs_frame_scale",
     "dcs_stream_params", "dcs_ctx_create", "dcs_ctx_destroy", "dcs_last_error", "dcs_device_count", "dcs_runtime_defaults", "dcs_ctx_set_batch_tails", "dcs_batch_package_bytes",
     "dcs_ctx_set_frames_per_wave", "dcs_ctx_set_tail_handoff", "dcs_ctx_set_large_list_path", "dcs_ctx_set_concurrent_batches", "dcs_ctx_set_cache_limits", "dcs_ctx_trim_cache", "dcs_ctx_cache_bytes", "dcs_plan_chunks2", "dcs_decode_batch", "dcs_batch_create", "dcs_batch_destroy", "dcs_batch_run", "dcs_batch_run_many", "dcs_pack_chunks",
@@ -348,6 +349,11 @@ def load_library():
         L.dcs_ctx_set_sole_source_kernel.argtypes = [vp, ctypes.c_int]
         L.dcs_batch_sole_source_kernel.restype = ctypes.c_int
         L.dcs_batch_sole_source_kernel.argtypes = [vp]
+    if hasattr(L, "dcs_batch_filled_bands"):            # (likewise: a build from before the short pre-pass)
+        L.dcs_batch_filled_bands.restype = ctypes.c_int
+        L.dcs_batch_filled_bands.argtypes = [vp]
+        L.dcs_prepass_short.restype = ctypes.c_int
+        L.dcs_prepass_short.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     L.dcs_batch_destroy.restype = None
     L.dcs_batch_destroy.argtypes = [vp]
     L.dcs_batch_run.restype = i32
@@ -1277,6 +1283,13 @@ def even_deal_lane(n_bands, q):
     return first.value, count.value, gain.value
 
 
+def prepass_short(n_bands):
+    """dcs_prepass_short -> (steps of the 1994+ transform's pre-pass that have no partner in a row of n_bands header bands, the last
+    tile word such a row can fill)"""
+    last = ctypes.c_int(0)
+    return load_library().dcs_prepass_short(n_bands, ctypes.byref(last)), last.value
+
+
 def device_count():
     return load_library().dcs_device_count()
 
@@ -2116,6 +2129,12 @@ class Batch:
     def sole_source_kernel(self):
         """the batch's next launch runs the even-deal kernel without the rounds of further sources (Context.set_sole_source_kernel)"""
         return bool(self.L.dcs_batch_sole_source_kernel(self.h))
+
+    @property
+    def filled_bands(self):
+        """the most header bands a source of the batch fills tile words for, as the kernel of a single-source even-deal batch is
+        told (9: that or fewer; 16: also a batch that does not qualify)"""
+        return int(self.L.dcs_batch_filled_bands(self.h))
 
     @property
     def chunks_per_wave(self):

@@ -148,6 +148,13 @@ struct DcsKernelArgs
 // no job of the batch has a second source (classifyJobs): with the even deal, the launch may take the kernels without the rounds of
 // further sources (dcsDecodeKernel<8, CPW, true, true>; dcs_ctx_set_sole_source_kernel)
 #define DCS_BATCH_SOLE_SOURCE 16u
+// bits 5..7: 16 less the most header bands any 1994+ first source of the batch fills tile words for, at most 7 (createBatch, for
+// batches that may take those kernels; 0: all sixteen, or not recorded).  Behind word 16 (nb - 1) - 1 of every row of the batch
+// nothing is ever written, and the 1994+ transform's pre-pass leaves out the partners that lie there (dcsPrepassShort,
+// dcs_package.h; transform94x8).  A source whose split or mid records start a lane later than the library's own walk would --
+// caller-made records may -- counts as sixteen bands.
+#define DCS_BATCH_BANDS_SHIFT 5
+#define DCS_BATCH_BANDS_MASK  7u
 #define DCS_BATCH_IMG_SHIFT 16          // bits 16..31: the packages' layout word (image dwords | DCS_PKG_SPLIT4; dcsPkgStride)
 #define DCS_BATCH_IMG_MASK  0xFFFFu
 

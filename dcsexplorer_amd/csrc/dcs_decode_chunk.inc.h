@@ -521,8 +521,8 @@
         R.k8000 = 0x8000u; R.k10000 = 0x10000u; R.watch = 0xFFFFu;
         R.k4000 = 0x4000u; R.watchB = 0x7FFF7FFFu;
         asm volatile("" : "+v"(R.k8000), "+v"(R.k10000), "+v"(R.k4000));    // keep them in vector registers (VOP3 takes no literal operand)
-        if constexpr (kOnePass)
-            transform94x8<kPace.levels>(P, W, C, R, x);
+        if constexpr (kOnePass)     // (the batch's rows hold its first sources' bands and nothing else: the short pre-pass)
+            transform94x8<kPace.levels, true>(P, W, C, R, x, 16u - ((a.flags >> DCS_BATCH_BANDS_SHIFT) & DCS_BATCH_BANDS_MASK));
         else if (xf == DCS_XFORM_94)
             transform94x8<kPace.levels>(P, W, C, R, x);
         else

@@ -1337,8 +1337,14 @@ __device__ __forceinline__ int swzPos(int row, int pos) { return swzQuad(row, po
 
 // 1994+ transform of 8 frames, 8 lanes each (DecoderImpl94x::TransformFrame, .cpp:397-534).
 // On return x[r'] holds point 16*l + r' = output sample pair m = 8*bitrev4(r') + bitrev3(l), shifted.
-template <int STEPS>
-__device__ __forceinline__ void transform94x8(const PassLane &P, const TwA &W, const LaneConsts &C, BflyRegs &R, uint32_t (&x)[16])
+// SHORT (the kernels of single-source batches only, where nothing but the frame's own bands fills its row): no row of the batch
+// holds more than `maxBands` header bands (DCS_BATCH_BANDS_SHIFT, dcs_common.h; wave-uniform), so the partners 128 - i of the
+// first dcsPrepassShort(maxBands) values of j are zero in every lane, and with Y = 0 both saturating operations return X and both
+// byte selects return X again: a_ = b_ = -X without a look at the partner.  Three straight-line forms of the loop -- 5, 3 or none
+// of the j short (at most 12 bands, at most 14, more) -- behind uniform branches.
+template <int STEPS, bool SHORT = false>
+__device__ __forceinline__ void transform94x8(const PassLane &P, const TwA &W, const LaneConsts &C, BflyRegs &R, uint32_t (&x)[16],
+                                              uint32_t maxBands = 16)
 {
     const int l = P.l;
     uint32_t *S = P.rowC;
@@ -1346,18 +1352,39 @@ __device__ __forceinline__ void transform94x8(const PassLane &P, const TwA &W, c
     uint32_t An[8], Bn[8];
     {
         uint32_t a_[8], b_[8];
-#pragma unroll
-        for (int j = 0 ; j < 8 ; ++j)
+        auto head = [&](auto zjTag)
         {
-            const int i = l + 8 * j;
-            const uint32_t X = P.rowC[i];
-            uint32_t Y = P.rowC[(128 - i) & 127];
-            if (i == 0) Y = 0;                                  // words 0x100/0x101 start at zero
-            // MulSS(v, 0x8000) = wrapping negate
-            const uint32_t Sm = pkAddSat(X, Y), Df = pkSubSat(X, Y);
-            a_[j] = pkSub(0u, __builtin_amdgcn_perm(Df, Sm, 0x07060100u));     // (-(x0+y0), -(x1-y1))
-            b_[j] = pkSub(0u, __builtin_amdgcn_perm(Sm, Df, 0x07060100u));     // (-(x0-y0), -(x1+y1))
+            constexpr int ZJ = decltype(zjTag)::value;
+#pragma unroll
+            for (int j = 0 ; j < 8 ; ++j)
+            {
+                const int i = l + 8 * j;
+                const uint32_t X = P.rowC[i];
+                if (j < ZJ)
+                {
+                    a_[j] = b_[j] = pkSub(0u, X);
+                    continue;
+                }
+                uint32_t Y = P.rowC[(128 - i) & 127];
+                if (i == 0) Y = 0;                                  // words 0x100/0x101 start at zero
+                // MulSS(v, 0x8000) = wrapping negate
+                const uint32_t Sm = pkAddSat(X, Y), Df = pkSubSat(X, Y);
+                a_[j] = pkSub(0u, __builtin_amdgcn_perm(Df, Sm, 0x07060100u));     // (-(x0+y0), -(x1-y1))
+                b_[j] = pkSub(0u, __builtin_amdgcn_perm(Sm, Df, 0x07060100u));     // (-(x0-y0), -(x1+y1))
+            }
+        };
+        if constexpr (SHORT)
+        {
+            static_assert(dcsPrepassShort(dcsPrepassBands(5)) >= 5 && dcsPrepassShort(dcsPrepassBands(3)) >= 3, "the short forms' band counts");
+            if (maxBands <= static_cast<uint32_t>(dcsPrepassBands(5)))
+                head(std::integral_constant<int, 5>());
+            else if (maxBands <= static_cast<uint32_t>(dcsPrepassBands(3)))
+                head(std::integral_constant<int, 3>());
+            else
+                head(std::integral_constant<int, 0>());
         }
+        else
+            head(std::integral_constant<int, 0>());
         // prod0 = b1*c1 - b0*c0 (rounding keyed on b0*c0) ; prod1 = b1*c0 + b0*c1 (keyed on b0*c1); b = (b0, b1), pre94 = (c0, c1)
         auto finish = [&](int j, uint32_t Pr)                   // Pr = (prod1, prod0)
         {

@@ -220,6 +220,31 @@ DCS_HDI constexpr bool dcsEvenDealt(int format, int bpl, int nb16, int sub, cons
     return format >= DCS_FMT_94_T0 && bpl != 0 && sub == 8 && nb16 < 16 && mid != nullptr && mid[0] == DCS_MIDS_VALID;
 }
 
+// Where a 1994+ frame's bands lie in its tile row: band 0 (7 samples) from word 1 on, band 1 (8) from word 8, bands 2..14 (16
+// each) from word 16 (b - 1), band 15 (32) up to word 255.  dcsBandFirstWord: a band's first word; dcsLastWord: the last word
+// a frame of nb header bands can fill.
+DCS_HDI constexpr int dcsBandFirstWord(int b) { return b <= 0 ? 1 : b == 1 ? 8 : 16 * (b - 1); }
+DCS_HDI constexpr int dcsLastWord(int nb) { return nb <= 0 ? 0 : nb == 1 ? 7 : nb >= 16 ? 255 : 15 + 16 * (nb - 2); }
+// The pre-pass of the 1994+ transform pairs point i = l + 8 j (lane l = 0..7 of the frame, j = 0..7) with point 128 - i, a point
+// being a dword of the row.  Where no row holds more than nb bands, the partners of the first dcsPrepassShort(nb) values of j
+// are zero in every lane: the lowest of them, 128 - (7 + 8 j), lies behind the last word filled.
+DCS_HDI constexpr int dcsPrepassShort(int nb)
+{
+    const int firstFree = (dcsLastWord(nb) + 2) / 2;        // the first point without a filled word
+    int zj = 0;
+    while (zj < 8 && 128 - (7 + 8 * zj) >= firstFree)
+        ++zj;
+    return zj;
+}
+// the most bands for which at least `zj` values of j are short (0: none)
+DCS_HDI constexpr int dcsPrepassBands(int zj)
+{
+    int nb = 16;
+    while (nb > 0 && dcsPrepassShort(nb) < zj)
+        --nb;
+    return nb;
+}
+
 // Chunk packages.  Everything unpack round 0 of a chunk needs, gathered once per batch by the host packer
 // (dcsBuildPackages, dcs_plan.cpp) or the device packer (dcsPackKernel) into one block at a fixed stride, so that a wavefront
 // requests ALL of it at its first instruction (no load depends on another load).  Round 5 layout (a wavefront reads its whole

@@ -467,6 +467,13 @@ extern "C" void dcs_even_deal_lane(int nBands, int q, int *firstUnit, int *nUnit
     if (nUnits != nullptr) *nUnits = u.count;
     if (gain != nullptr) *gain = dcsEvenDealGain(nBands);
 }
+// ... and the rule of the short pre-pass (dcsPrepassShort): of the transform's eight j, how many have no partner in any row of
+// at most nBands header bands; the last tile word such a row can fill
+extern "C" int dcs_prepass_short(int nBands, int *lastWord)
+{
+    if (lastWord != nullptr) *lastWord = dcsLastWord(nBands);
+    return dcsPrepassShort(nBands);
+}
 // Diagnostic / test entry: plan + pack on the host, exactly what dcs_batch_create uploads.
 static DcsStatus packEntry(const DcsFrameJob *jobs, uint32_t nJobs, const DcsSrcDesc *srcs, const DcsFrameMids *mids,
                            const uint8_t *blob, size_t blobLen, int fpw,

@@ -814,6 +814,35 @@ static DcsStatus validateMids(DcsCtx *ctx, const DcsSrcDesc *srcs, const DcsFram
     return DCS_OK;
 }
 
+// The header bands a 1994+ first source can fill tile words for (DCS_BATCH_BANDS_SHIFT, dcs_common.h): its own count, as long as
+// no record a packer may hand a lane starts that lane later than the band's place in the row allows.  A lane that starts band b
+// at output index x fills words below x + (what is left of b) + (the bands behind it), so with x no further on than
+// dcsBandFirstWord(b) -- for the second half of a band: half a band further, and one sample more (two words in a strided band,
+// header bit 6) behind a straddling code -- the frame ends where dcsLastWord says.  The library's own walk never records more
+// (a band without a code, or strided, only starts the next one earlier); caller-made records may, and such a source counts as
+// sixteen bands.  `mid`: the source's mid records or null.
+static int filledBands94(const DcsSrcDesc &sd, const uint32_t *mid, const uint8_t *blob, size_t blobLen)
+{
+    const DcsFrameIndex &ix = sd.idx;
+    const int nb = ix.nBands < 16 ? ix.nBands : 16;
+    if (sd.format < DCS_FMT_94_T0)
+        return 16;
+    for (int band = 1 ; band < nb ; ++band)
+        if (static_cast<int>(ix.split[band - 1].state & 0x1FFu) > dcsBandFirstWord(band))
+            return 16;
+    if (mid != nullptr && mid[0] == DCS_MIDS_VALID)
+        for (int band = 2 ; band < nb ; ++band)
+        {
+            const uint32_t st = mid[band] >> 16;
+            const uint64_t hdrAt = sd.streamOff + 2 + static_cast<uint64_t>(band);
+            const bool strided = sd.hdrLen != 1 && hdrAt < blobLen && (blob[hdrAt] & 0x40) != 0;
+            const int straddle = (st & DCS_MID15_STRADDLE) ? (strided ? 2 : 1) : 0;
+            if (static_cast<int>(st & 0x1FFu) > dcsBandFirstWord(band) + 8 + straddle)
+                return 16;
+        }
+    return nb;
+}
+
 // How a batch is made besides its jobs: what the callers of the three constructors below choose
 struct BatchOptions
 {
@@ -1005,6 +1034,14 @@ static DcsStatus createBatch(DcsCtx *ctx, const BatchOptions &o,
     }
     if (!kinds.multi)
         b->flags |= DCS_BATCH_SOLE_SOURCE;
+    // (for the kernels of such batches: how far up the fullest row of the batch is filled, dcs_common.h)
+    if ((b->flags & DCS_BATCH_EVEN_DEAL) != 0 && (b->flags & DCS_BATCH_SOLE_SOURCE) != 0)
+    {
+        int most = 0;
+        for (uint32_t k = 0 ; k < nSrcs && most < 16 ; ++k)
+            most = std::max(most, filledBands94(srcs[k], mids[k].mid, blob, blobLen));
+        b->flags |= std::min(16u - static_cast<uint32_t>(most), DCS_BATCH_BANDS_MASK) << DCS_BATCH_BANDS_SHIFT;
+    }
     const DcsFrameMids *packMids = (b->flags & DCS_BATCH_EVEN_DEAL) ? mids : nullptr;
 
     CacheBuf hPackages;                         // pinned staging for the chunk packages
@@ -1455,6 +1492,10 @@ extern "C" int dcs_batch_chunks_per_wave(const DcsBatch *b)
 }
 extern "C" int dcs_batch_even_deal(const DcsBatch *b) { return (b != nullptr && (b->flags & DCS_BATCH_EVEN_DEAL)) ? 1 : 0; }
 extern "C" int dcs_batch_sole_source_kernel(const DcsBatch *b) { return (b != nullptr && soleSourceKernel(b->flags, b->ctx->soleKernel)) ? 1 : 0; }
+extern "C" int dcs_batch_filled_bands(const DcsBatch *b)
+{
+    return b != nullptr ? 16 - static_cast<int>((b->flags >> DCS_BATCH_BANDS_SHIFT) & DCS_BATCH_BANDS_MASK) : 16;
+}
 extern "C" uint32_t dcs_batch_num_jobs(const DcsBatch *b) { return b ? b->nJobs : 0; }
 
 // ---------------------------------------------------------------------------------------------------------

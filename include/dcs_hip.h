@@ -378,6 +378,13 @@ int       dcs_batch_even_deal(const DcsBatch *batch);           /* 1: the batch'
  * every launch, like dcs_ctx_set_chunks_per_wave.  Same PCM, error words and tails either way. */
 DcsStatus dcs_ctx_set_sole_source_kernel(DcsCtx *ctx, int mode);
 int       dcs_batch_sole_source_kernel(const DcsBatch *batch);  /* 1: the batch's next launch runs that instantiation */
+/* That instantiation's transform leaves out of its pre-pass the partners no frame of the batch can have: the batch records the
+ * most header bands any of its sources fills tile words for -- 9 stands for fewer as well; 16 also for a batch that does not
+ * qualify for the instantiation, and for one with a source whose split or mid records start a lane later than the library's
+ * own index walk records (caller-made records may).  dcs_prepass_short: of the pre-pass's eight steps, how many are without a
+ * partner at that band count (*lastWord, may be NULL: the last tile word such a frame can fill). */
+int       dcs_batch_filled_bands(const DcsBatch *batch);
+int       dcs_prepass_short(int nBands, int *lastWord);
 void      dcs_batch_destroy(DcsBatch *batch);
 /* Enqueue the decode on `hipStream` (a hipStream_t passed as void*; NULL = the context's stream).
  * Asynchronous: returns after the launch.  No wavefront of the launch waits for another (a frame whose predecessor is decoded by
