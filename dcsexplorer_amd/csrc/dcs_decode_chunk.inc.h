@@ -571,10 +571,12 @@
                 metAsConsumer = __hip_atomic_exchange(a.handoff + static_cast<size_t>(myPrevJob) * 16 + lrA, handoffWord(a.epoch, 1u, mine0),
                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         };
-        // (The PCM leaves as 15 two- resp. four-byte stores per lane.  Putting a frame's samples in order in its dead tile
-        // row first and storing 16 bytes per lane -- 2 resp. 4 store instructions -- was measured twice: 5 % slower, the
-        // extra LDS round trip is on the critical path and the narrow stores are not.  Swapping registers r and r + 8
-        // with lane l ^ 8 by DPP and storing sample PAIRS, 8 stores instead of 15 for a 1993 frame: no difference.)
+        // (The PCM of every kernel but the two of single-source even-deal batches leaves as 15 two- resp. four-byte stores per lane.
+        // Putting a frame's samples in order in its dead tile row first and storing 16 bytes per lane as plain stores was measured
+        // three times: 5 % slower twice before the even deal, and 0.43 us = 1.6 % slower on dcsDecodeKernel<8, 2, true, true> over
+        // survey3_65536, profiles/NOTES.md 59 -- the extra LDS round trip is on the critical path and the narrow stores are not.
+        // What pays is the same path with WRITE-THROUGH stores, below.  Swapping registers r and r + 8 with lane l ^ 8 by DPP and
+        // storing sample PAIRS, 8 stores instead of 15 for a 1993 frame: no difference.)
         if (kOnePass || xf == DCS_XFORM_94)
         {
             // overlap-add on sample pair m = bitrev3(l) (register 0) (:538-555)
@@ -584,22 +586,72 @@
                                          overlapMix(imC(x[0]), C.k[DCS_K94_OVLA] >> 16, imC(tailPair), C.k[DCS_K94_OVLB] >> 16));
             x[0] = deferred ? x[0] : mixed;                             // (a deferred frame keeps the raw pair for the rendezvous)
             uint32_t *out = reinterpret_cast<uint32_t *>(a.pcm) + static_cast<size_t>(myJob) * (DCS_FRAME_SAMPLES / 2) + lrA;
-            if (emit)
+            if constexpr (SOLE)
             {
+                // The kernels of single-source even-deal batches write their PCM THROUGH the L2 (storePcm16, dcs_kernels.hip.h):
+                // plain stores keep their lines in the XCD's L2 until the write-back at the end of the kernel, which whatever
+                // follows the launch waits for -- 31.5 MB per launch of the headline workload, half of it from the launch's last
+                // microseconds.  A write-through store costs per instruction, not per byte, so the samples go out 16 bytes at a
+                // time: every lane puts its pairs in order into the frame's dead tile row (lane groups without a frame: into the
+                // dead bit pool), lane 0 of the group the frame's job and flags behind them (dwords 130 and 131 of the row's 132),
+                // and the chunk's 8 x 30 16-byte pieces leave in four rounds, piece g = lane + 64 t of frame g / 30.  Nothing is
+                // stored for a padding slot or a frame without a slot (g / 30 >= nSlots), for a halo slot, and for pieces 0 and 1
+                // -- samples 0..15 -- of a frame whose tail comes from another chunk: those belong to the rendezvous, which keeps
+                // its 4-byte stores, as do the tails and the error words.  The exchanges are issued between the LDS writes and the
+                // wide stores.  (The wide stores are inline assembly, outside the compiler's count of memory operations in
+                // flight: memory operations complete in order, so a wait it places can only wait for more; and the rows are not
+                // read again.)  27.12 -> 25.32 us on survey3_65536, profiles/NOTES.md 59.
+                uint32_t *rowO = P.rowC + lrA;
                 if (!deferred)
-                    out[0] = x[0];
+                    rowO[0] = x[0];
 #pragma unroll
-                for (int r = 1 ; r < kSplit ; ++r)
-                    out[8 * bitrevN(r, 4)] = x[r];                      // pair 8*bitrev4(r) + bitrev3(l)
-            }
-            rendezvous(x[0], x[15]);
-            if (emit)
-            {
+                for (int r = 1 ; r < 15 ; ++r)
+                    rowO[8 * bitrevN(r, 4)] = x[r];                     // pair 8*bitrev4(r) + bitrev3(l)
+                if (P.l == 0)
+                    *reinterpret_cast<uint2 *>(P.rowC + 130) = make_uint2(myJob, static_cast<uint32_t>(myFlags));
+                waveSync();
+                rendezvous(x[0], x[15]);
+                U32x4 piece[4];
+                char *dst[4];
+                bool put[4];
 #pragma unroll
-                for (int r = kSplit ; r < 15 ; ++r)
-                    out[8 * bitrevN(r, 4)] = x[r];
-                if (a.tailsOut != nullptr && (myFlags & DCS_SLOT_KEEP_TAIL))
+                for (int t = 0 ; t < 4 ; ++t)
+                {
+                    const int g = lane + 64 * t;
+                    const int f = min((g * 2185) >> 16, FPW - 1), p = g - 30 * f;       // (g / 30 for g < 240; lanes beyond: no store)
+                    const uint32_t *rowF = reinterpret_cast<const uint32_t *>(L.row(f));
+                    const uint2 jf = *reinterpret_cast<const uint2 *>(rowF + 130);
+                    const uint4 v = ldsRead4(rowF + 4 * (p & 31));
+                    piece[t] = U32x4{ v.x, v.y, v.z, v.w };
+                    put[t] = g < 240 && f < nSlots && !(jf.y & DCS_SLOT_HALO) && !((jf.y & DCS_SLOT_IMPORT) != 0 && p < 2);
+                    dst[t] = reinterpret_cast<char *>(a.pcm) + static_cast<size_t>(jf.x) * (DCS_FRAME_SAMPLES * 2) + p * 16;
+                }
+#pragma unroll
+                for (int t = 0 ; t < 4 ; ++t)
+                    if (put[t])
+                        storePcm16(dst[t], piece[t]);
+                if (emit && a.tailsOut != nullptr && (myFlags & DCS_SLOT_KEEP_TAIL))
                     reinterpret_cast<uint32_t *>(a.tailsOut)[static_cast<size_t>(myJob) * 8 + lrA] = x[15];
+            }
+            else
+            {
+                if (emit)
+                {
+                    if (!deferred)
+                        out[0] = x[0];
+#pragma unroll
+                    for (int r = 1 ; r < kSplit ; ++r)
+                        out[8 * bitrevN(r, 4)] = x[r];                  // pair 8*bitrev4(r) + bitrev3(l)
+                }
+                rendezvous(x[0], x[15]);
+                if (emit)
+                {
+#pragma unroll
+                    for (int r = kSplit ; r < 15 ; ++r)
+                        out[8 * bitrevN(r, 4)] = x[r];
+                    if (a.tailsOut != nullptr && (myFlags & DCS_SLOT_KEEP_TAIL))
+                        reinterpret_cast<uint32_t *>(a.tailsOut)[static_cast<size_t>(myJob) * 8 + lrA] = x[15];
+                }
             }
             // the second to arrive finishes the consumer's first sample pair
             if (deferred && handoffMeets(metAsConsumer, a.epoch, 0u))

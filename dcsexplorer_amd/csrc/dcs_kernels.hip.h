@@ -1329,6 +1329,15 @@ __device__ __forceinline__ uint4 ldsRead4(const uint32_t *p) { return *reinterpr
 __device__ __forceinline__ void ldsWrite4(uint32_t *p, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
 { *reinterpret_cast<uint4 *>(p) = make_uint4(a, b, c, d); }
 
+// 16 bytes of PCM written THROUGH the L2 (sc1): the line does not stay dirty in the XCD's L2 for the write-back at the end of the
+// kernel.  Inline assembly -- the compiler has no 16-byte store of that kind -- with one wait state behind it: a vector
+// instruction must not write the data registers of a store of more than 8 bytes in the cycle after it.
+typedef uint32_t U32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void storePcm16(void *p, U32x4 v)
+{
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 0" : : "v"(p), "v"(v) : "memory");
+}
+
 // The transposes go through the frame's own tile row viewed as 8 rows x 16 dwords.  The four quads of a
 // row are XOR-swizzled with the row number so that 128-bit accesses of the 8 lanes of a frame spread
 // over all banks: dword index of (row, pos) = row*16 + (((pos >> 2) ^ (row >> 1)) & 3)*4 + (pos & 3).
