@@ -70,12 +70,20 @@ inline int a93Sfs(int s)
     return static_cast<int16_t>(sf & 0xFFFF);
 }
 
-// E_b of one maximumQuantizationError: a row of the floorE table, which has one per distinct value of the call
+// E_b of one maximumQuantizationError: a row of the floorE table, which has one per distinct value of the call.  It
+// saturates at 2^40, compared in double before the cast (q is any finite float: the unbounded value passes 2^64 from
+// q = 24 771).  Every D is below 2^38, so from 2^38 on max(D, E_b) = E_b for every option of the band and the walk picks the
+// fewest bits, whatever E_b is; and a cost stays below 2^40 + 2^40 * 264 < 2^50.
+constexpr unsigned long long kA93FloorMax = 1ull << 40;
+
 void floorE93a(float maxQE, unsigned long long *row)
 {
     const double q = static_cast<double>(maxQE);
     for (int b = 0 ; b < 18 ; ++b)
-        row[b] = static_cast<unsigned long long>(floor(((1073741824.0 * q) * q) * static_cast<double>(2 * kInputsPerBand93a[b])));
+    {
+        const double e = floor(((1073741824.0 * q) * q) * static_cast<double>(2 * kInputsPerBand93a[b]));
+        row[b] = e >= static_cast<double>(kA93FloorMax) ? kA93FloorMax : static_cast<unsigned long long>(e);
+    }
 }
 
 Enc93aTabs buildTabs93a()

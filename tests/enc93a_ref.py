@@ -6,7 +6,8 @@ After one f32 multiply and one roundf per coefficient everything is integer (Pyt
   targets   t[i] = clamp(roundf(K * f[i - 1]), -32768, 32767) for frame-buffer word i >= 2, t[0] from f[0], t[1] = 0; K = 32768,
             f = the analysis transform's frame (enc_ref.analyse)
   search    D(b, w, s) = sum over the band's pairs of min_j |t - R(s, w, j)|^2, R the decoder's reconstruction at M0
-  walk      per frame, codebook pp and lambda of the ladder: bands in order, minimising max(D, E_b) + lambda * bits
+  walk      per frame, codebook pp and lambda of the ladder: bands in order, minimising max(D, E_b) + lambda * bits,
+            E_b = min(floor(2^30 q^2 * 2 inputs), 2^40)
   choice    per stream: the least sum of D among the (pp, lambda) within the byte budget, else the fewest bits
 """
 import math
@@ -143,16 +144,20 @@ def search(t):
     return D0, S0, D
 
 
+E_MAX = 1 << 40                 # E_b saturates here: every D is below 2^38, so from 2^38 on a band's options differ in bits alone
+
+
 def band_floor(mqe):
-    """E_b, in double: ((K^2 * q) * q) * (2 * inputs)"""
+    """E_b, in double: min(floor(((K^2 * q) * q) * (2 * inputs)), 2^40), compared before the value leaves double"""
     q = float(F32(mqe))
-    return np.array([int(math.floor(((1073741824.0 * q) * q) * float(2 * n))) for n in INPUTS], dtype=object)
+    e = [math.floor(((1073741824.0 * q) * q) * float(2 * n)) for n in INPUTS]
+    return np.array([E_MAX if v >= float(E_MAX) else int(v) for v in e], dtype=object)
 
 
 def walk(D0, S0, D, mqe):
     """every (frame, pp, lambda) at once -> dict of [F, 4*KL] arrays: L, bitsThrough, sumD, and the choices [F, 4*KL, 18]
-    w and s.  Costs are Python integers where they could pass 2^63 (object arrays are avoided: the ladder's top times the
-    widest band is below 2^48, D below 2^38)."""
+    w and s.  Costs stay in int64 (object arrays are avoided): E_b is at most 2^40, D below 2^38, and the ladder's top times
+    the most bits a band takes is 2^40 * 264, so a cost is below 2^50."""
     F = D0.shape[0]
     C = 4 * KL
     lam = np.array([LADDER[c % KL] for c in range(C)], np.int64)[None, :]

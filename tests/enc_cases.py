@@ -15,7 +15,10 @@ check() runs the reference encoder (oracle/_ref/dcs_encref, built by `make -C or
 build (dcs_encref_san), and classifies the case as the golden generators do: a bounds or float-cast report DROPS it (the
 reference's bytes then depend on its binary layout); a shift report alone keeps it (the library's masked-shift rule,
 INTEGRATION.md "Encoding").  A kept OS93 case in which the library's Keep +15 rule fired is a RULE case: its bytes are the
-library's, not the reference's.  The restatement's result (tests/enc_ref.py, tests/enc93_ref.py) comes with it."""
+library's, not the reference's.  The restatement's result (tests/enc_ref.py, tests/enc93_ref.py) comes with it.
+
+Layout `93a/T1`, the pair-table layout the reference cannot write, is not among FAMILIES: its seeded cases are
+tests/enc93a_fuzz_cases.py, which takes the signal kinds from here and has the reference DECODER as its checker."""
 import collections
 import concurrent.futures
 import multiprocessing
