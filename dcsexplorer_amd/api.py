@@ -234,6 +234,7 @@ EXPORTS = [
     "dcs_encode_params_default", "dcs_encode_bound", "dcs_encode_header", "dcs_encode_streams",
     "dcs_encode93_bound", "dcs_encode93_header", "dcs_encode93_streams",
     "dcs_encode93a_bound", "dcs_encode93a_streams", "dcs_encode93a_sweep",
+    "dcs_encode_rd_bound", "dcs_encode_rd_streams",
     "dcs_transcode_plan", "dcs_transcode_streams",
     "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
     "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
@@ -576,6 +577,10 @@ def load_library():
     L.dcs_wav_parse.argtypes = [vp, sz, ctypes.POINTER(WavInfo)]
     L.dcs_encode_sweep.restype = i32
     L.dcs_encode_sweep.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, sz, vp]
+    L.dcs_encode_rd_bound.restype = sz
+    L.dcs_encode_rd_bound.argtypes = [ctypes.c_uint64]
+    L.dcs_encode_rd_streams.restype = i32
+    L.dcs_encode_rd_streams.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), vp, vp, ctypes.c_uint64, vp, vp, vp]
     L.dcs_encode93a_sweep.restype = i32
     L.dcs_encode93a_sweep.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, sz, vp]
     L.dcs_encode_sweep_group_frames.restype = None
@@ -878,6 +883,16 @@ ENCODE93A_INFO_DTYPE = np.dtype([("selector", "<i4"), ("ladderIndex", "<i4"), ("
 def encode93a_bound(n_samples):
     """dcs_encode93a_bound: the largest stream n_samples samples can encode to through encode93a_streams, either type"""
     return int(load_library().dcs_encode93a_bound(int(n_samples)))
+
+
+# DcsEncodeRdInfo: what the rate-distortion search of encode_rd_streams chose for a stream
+ENCODE_RD_INFO_DTYPE = np.dtype([("formatType", "<i4"), ("formatSubType", "<i4"), ("ladderIndex", "<i4"), ("numBands", "<i4"),
+                                 ("frameBits", "<u8"), ("budgetBits", "<u8"), ("sqErr", "<u8"), ("fits", "<i4"), ("reserved", "<i4")])
+
+
+def encode_rd_bound(n_samples):
+    """dcs_encode_rd_bound: the largest stream n_samples samples can encode to through encode_rd_streams (0 = not encodable)"""
+    return int(load_library().dcs_encode_rd_bound(int(n_samples)))
 
 
 def encode93a_params(fmt, **params):
@@ -1491,6 +1506,25 @@ class Context:
         out = np.zeros(max(cap, 1), np.uint8)
         _check(self.L.dcs_encode_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info
+
+    def encode_rd_streams(self, pcm_list, fmt=None, budget=None, **params):
+        """dcs_encode_rd_streams: PCM at 31 250 Hz (as encode_streams) -> 1994+ streams from the rate-distortion search of
+        DESIGN.md 10.11, each held to a budget.  fmt as encode_streams (None: every layout).  budget: None = the frame bits
+        targetBitRate gives; an int = the most bytes any stream may have; a sequence = per stream.  Returns (list of bytes,
+        ENCODE_INFO_DTYPE array, ENCODE_RD_INFO_DTYPE array)."""
+        p = encode_params(fmt, **params)
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        bud = None
+        if budget is not None:
+            bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, np.int64), (n,)).clip(0, 0xFFFFFFFF), dtype=np.uint32)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info, info_rd = np.zeros(n, ENCODE_INFO_DTYPE), np.zeros(n, ENCODE_RD_INFO_DTYPE)
+        cap = sum(encode_rd_bound(offs[i + 1] - offs[i]) for i in range(n))
+        out = np.zeros(max(cap, 1), np.uint8)
+        _check(self.L.dcs_encode_rd_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(bud) if bud is not None and n else None,
+                                            _ptr(out), cap, _ptr(out_offs), _ptr(info), _ptr(info_rd)), self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info, info_rd
 
     def encode_sweep(self, pcm_list, sets, jobs=None, measure=True, streams=True):
         """dcs_encode_sweep: jobs = (stream, set) pairs encoded in one call; sets = EncodeParams of one encoder (encode_params /

@@ -31,6 +31,10 @@
 // (A1-A5) of its own, dcs_encode93a.hip.h: a third family of the one driver, chosen per job by its set's type, so that one
 // call (dcs_encode93a_sweep) may hold Type-0 jobs on the O stages and Type-1 jobs on the A stages.
 //
+// The rate-distortion 1994+ encoder (dcs_encode_rd_streams) is a fourth family, R1-R6 in dcs_encode_rd.hip.h: it shares E1,
+// the swap and the driver, writes the 1994+ format from a trellis search of its own and holds each job to a byte budget; a
+// call of it has jobs of this family only.
+//
 // E1 and encStreamKernel run per stream and do not read the parameters, and neither does A1's search; A1's walk reads one
 // of them, maximumQuantizationError, and runs once per distinct value.  Everything behind them runs per JOB, a stream
 // encoded with one parameter set (EncJob, EncSet): its rows in the per-frame buffers are the job's own, the spectrum it reads
@@ -1271,6 +1275,7 @@ __global__ __launch_bounds__(256) void encMeasureKernel(const float *__restrict_
 // EncRun, which launches these; see the note above EncRun::analyse for the templates)
 
 #include "dcs_encode93a.hip.h"
+#include "dcs_encode_rd.h"
 
 namespace {
 
@@ -1301,6 +1306,8 @@ struct EncJobs
     const DcsSweepJob *list;
     uint32_t n;
     bool os93;
+    bool rd = false;                        // the R family (dcs_encode_rd.hip.h): every set 0x9400, every job searched to a budget
+    const uint32_t *budgetBytes = nullptr;  // rd: per job, the most bytes its stream may have (null: the sets' targetBitRate)
 };
 
 // after the sizes are known: the host memory that takes the `total` bytes (stream i at outOffsets[i]), or null for DCS_ERR_CAPACITY
@@ -1315,6 +1322,7 @@ struct EncOutput
     DcsEncodeInfo *info = nullptr;          // nJobs, or null
     const EncPlace *place = nullptr;
     DcsEncode93aInfo *info93a = nullptr;    // nJobs, or null: the Type-1 candidate of a job of the A family, zeros of any other
+    DcsEncodeRdInfo *infoRd = nullptr;      // nJobs, or null: what the R family's search chose
 };
 
 // what dcs_encode_sweep asks of the driver beyond a list of jobs
@@ -1407,6 +1415,12 @@ private:
     DcsStatus decodeAndCompare(uint32_t n, bool onHost, bool *unusable);
     DcsStatus reportGroup(uint32_t g);
     DcsStatus measureGroup(uint32_t g);
+    // the R family's share of allocCall, allocGroup, analyse, runGroup and packGroup (defined behind dcs_encode_rd.hip.h)
+    DcsStatus rdAllocCall();
+    hipError_t rdAllocGroup();
+    DcsStatus rdAnalyse();
+    DcsStatus rdRunGroup(uint32_t j0, uint32_t n);
+    DcsStatus rdPackGroup(uint32_t n, uint32_t JF);
     std::string name(uint32_t i) const { return "stream " + std::to_string(in.label ? in.label[i] : i); }
 
     // ---- fixed by the arguments
@@ -1430,6 +1444,10 @@ private:
     std::vector<uint32_t> setQ, rowOf;
     uint32_t nRows = 0;
     std::vector<unsigned long long> floorE;     // [q][18] (analyse; the source of an asynchronous upload)
+    // the R family: E_b per set, and per job its budget in frame bits (-1: nothing fits) and what R3 chose
+    std::vector<unsigned long long> floorRd;    // [set][16]
+    std::vector<long long> budgetRd;
+    std::vector<EncRdChoice> choiceRd;
 
     // ---- device buffers of the call: valid from allocCall to the end
     struct CallBufs
@@ -1449,6 +1467,13 @@ private:
             uint32_t *dSetQ = nullptr, *dRowOf = nullptr;
             Enc93aTot *dTot = nullptr;          // [row][candidate]
         } a93;
+        struct                                  // the R family only (R1)
+        {
+            EncRdTabs *dR = nullptr;
+            unsigned long long *dItems = nullptr;       // [stream-frame][band][width][scale code]
+            uint32_t *dPeak = nullptr;          // [stream][band]
+            unsigned long long *dD0 = nullptr, *dFloor = nullptr;   // [stream][band], [set][band]
+        } rd;
     } cb;
     CacheArena call;
 
@@ -1466,6 +1491,14 @@ private:
         struct { uint8_t *dBest = nullptr, *dCodes = nullptr, *dHdrBits = nullptr; uint16_t *dSmpBits = nullptr; } v94;   // 1994+ only (E3-E5)
         struct { Enc93aChoice *dChoice = nullptr; Enc93aRec *dRec = nullptr; } a93;                 // OS93a Type 1 only (A2-A5)
         struct { EncMeasure *dMeas = nullptr; uint32_t *dFirstDec = nullptr; } m;                   // sweep.measure only (M1)
+        struct                                                                                      // the R family only (R2-R6)
+        {
+            EncRdTot *dTot = nullptr;           // [job][layout][band][window index][lambda]
+            EncRdChoice *dChoice = nullptr;
+            long long *dBudget = nullptr;
+            uint8_t *dSurv = nullptr, *dEnd = nullptr, *dCodes = nullptr;   // [job-frame][band][state], [job][band], [job-frame][band]
+            uint32_t *dBits = nullptr;          // [job-frame]
+        } rd;
     } gb;
     CacheArena group;
 
@@ -1545,7 +1578,8 @@ void EncRun::buildSets()
                 cmask |= 1u << c;
         const uint32_t vmask = ((cmask & 3) ? 1u : 0u) | ((cmask & 4) ? 2u : 0u) | ((cmask & 8) ? 4u : 0u);
         hsets[k] = EncSet{ p.powerBandCutoff, p.minimumDynamicRange, p.maximumQuantizationError, p.targetBitRate, vmask, cmask };
-        anyV |= vmask;
+        if (!jobs.rd)
+            anyV |= vmask;                      // (a set of the R family: no E stage touches its jobs)
     }
     // the A family's sets (cmask 0 above: no O stage touches their jobs) by their distinct maximumQuantizationError
     setQ.assign(jobs.nSets, kA93None);
@@ -1597,6 +1631,8 @@ DcsStatus EncRun::allocCall()
         ENCCHK(call.alloc(&cb.a93.dRowOf, rowOf.size()));
         ENCCHK(call.alloc(&cb.a93.dTot, size_t(kA93Cand) * nRows));
     }
+    if (jobs.rd)
+        ENCTRY(rdAllocCall());
     return DCS_OK;
 }
 
@@ -1657,6 +1693,8 @@ hipError_t EncRun::allocGroup()
         HIPTRY(group.alloc(&gb.m.dMeas, NJ));
         HIPTRY(group.alloc(&gb.m.dFirstDec, NJ));
     }
+    if (jobs.rd)
+        HIPTRY(rdAllocGroup());
     return hipSuccess;
 }
 
@@ -1728,6 +1766,8 @@ DcsStatus EncRun::runGroup(uint32_t g)
     if (!qs.empty())
         hipLaunchKernelGGL(enc93aChooseKernel, dim3(n), dim3(256), 0, st, cb.a93.dTot, cb.a93.dRowOf, in.nStreams, gb.dJobs, cb.dSets,
                            cb.a93.dSetQ, gb.a93.dChoice);
+    if (jobs.rd)
+        ENCTRY(rdRunGroup(j0, n));
     ENCCHK(hipGetLastError());
     if (anyV != 0)
     {
@@ -1746,6 +1786,13 @@ DcsStatus EncRun::runGroup(uint32_t g)
             keep[j0 + k] = choiceA[j0 + k].numBands;
             size[j0 + k] = 3 + (choiceA[j0 + k].frameBits + 7) / 8;
         }
+    // a job of the R family: the candidate of CloseStream's list it chose, its header's band count, 18 bytes and the frames' bits
+    for (uint32_t k = 0 ; jobs.rd && k < n ; ++k)
+    {
+        win[j0 + k] = choiceRd[j0 + k].variant;
+        keep[j0 + k] = choiceRd[j0 + k].numBands;
+        size[j0 + k] = 18 + (choiceRd[j0 + k].frameBits + 7) / 8;
+    }
     resident = g;
     residentFrames = JF;
     return DCS_OK;
@@ -1777,6 +1824,8 @@ DcsStatus EncRun::analyse()
     if (anyV != 0)
         hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, cb.dStr, cb.dPw, cb.dLo, cb.dHi, cb.dSums);
     ENCCHK(hipMemcpyAsync(bad.data(), cb.dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
+    if (jobs.rd)
+        return rdAnalyse();
     if (qs.empty())
         return DCS_OK;
     // A1: one search per stream-frame; kA93QPerLaunch of the distinct q to a launch
@@ -1833,6 +1882,12 @@ DcsStatus EncRun::placeOutput()
             const uint64_t budget = static_cast<uint64_t>(p.targetBitRate) * static_cast<uint64_t>(e.nFrames) * 240ull / 31250ull;
             to.info93a[j] = setQ[jobs.list[j].paramSet] == kA93None ? DcsEncode93aInfo{}
                             : DcsEncode93aInfo{ c.selector, c.ladderIndex, c.numBands, 0, c.frameBits, budget, c.sumD };
+        }
+        if (to.infoRd != nullptr)
+        {
+            const EncRdChoice &c = choiceRd[j];
+            to.infoRd[j] = DcsEncodeRdInfo{ kCandType[c.variant], kCandSub[c.variant], c.ladderIndex, c.numBands, c.frameBits,
+                                            static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
         }
         if (sweep.results != nullptr)
         {
@@ -1908,6 +1963,8 @@ DcsStatus EncRun::packGroup(uint32_t g)
         hipLaunchKernelGGL(enc93aPackKernel, dim3(JF), dim3(128), 0, st, cb.a93.dA, cb.dSpec, gb.dFJ, gb.dJobs, cb.a93.dSetQ, gb.a93.dChoice,
                            gb.a93.dRec, gb.dFrameOff, gb.dOutOff, dW);
     }
+    if (jobs.rd)
+        ENCTRY(rdPackGroup(n, JF));
     hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
     ENCCHK(hipGetLastError());
     return DCS_OK;
@@ -2047,6 +2104,8 @@ DcsStatus EncRun::run()
     }
     buildSets();
     win.resize(jobs.n); keep.resize(jobs.n); size.resize(jobs.n); choiceA.resize(jobs.n);
+    if (jobs.rd)
+        choiceRd.resize(jobs.n);
     ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
     ENCTRY(allocCall());
     ENCTRY(allocGroups());
@@ -2452,3 +2511,119 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
 // ------------------------------------------------------------------------ encoding files (dcs_encode_files.hip.h)
 
 #include "dcs_encode_files.hip.h"
+
+// ------------------------------------------------- the rate-distortion 1994+ encoder: kernels and driver (dcs_encode_rd.hip.h)
+// (behind every other kernel of the unit, templates included: those keep their place in the code object)
+
+#include "dcs_encode_rd.hip.h"
+
+namespace {
+
+DcsStatus EncRun::rdAllocCall()
+{
+    ENCCHK(call.alloc(&cb.rd.dR, 1));
+    ENCCHK(call.alloc(&cb.rd.dItems, size_t(kRdItemsPerFrame) * F));
+    ENCCHK(call.alloc(&cb.rd.dPeak, size_t(16) * in.nStreams));
+    ENCCHK(call.alloc(&cb.rd.dD0, size_t(16) * in.nStreams));
+    ENCCHK(call.alloc(&cb.rd.dFloor, size_t(16) * jobs.nSets));
+    return DCS_OK;
+}
+
+hipError_t EncRun::rdAllocGroup()
+{
+    const size_t JF = static_cast<size_t>(groupFrames), NJ = groupJobs;
+    HIPTRY(group.alloc(&gb.rd.dTot, size_t(kRdRowsPerJob) * NJ));
+    HIPTRY(group.alloc(&gb.rd.dChoice, NJ));
+    HIPTRY(group.alloc(&gb.rd.dBudget, NJ));
+    HIPTRY(group.alloc(&gb.rd.dSurv, 256 * JF));
+    HIPTRY(group.alloc(&gb.rd.dEnd, 16 * NJ));
+    HIPTRY(group.alloc(&gb.rd.dCodes, 16 * JF));
+    HIPTRY(group.alloc(&gb.rd.dBits, JF));
+    return hipSuccess;
+}
+
+// R1 over every stream-frame; the budgets of all jobs, in frame bits
+DcsStatus EncRun::rdAnalyse()
+{
+    floorRd.resize(size_t(16) * jobs.nSets);
+    for (uint32_t k = 0 ; k < jobs.nSets ; ++k)
+        floorERd(jobs.sets[k].maximumQuantizationError, floorRd.data() + size_t(16) * k);
+    budgetRd.resize(jobs.n);
+    for (uint32_t j = 0 ; j < jobs.n ; ++j)
+    {
+        const uint64_t nF = hs[jobs.list[j].stream].nFrames;
+        if (jobs.budgetBytes == nullptr)
+            budgetRd[j] = static_cast<long long>(static_cast<uint64_t>(jobs.sets[jobs.list[j].paramSet].targetBitRate) * nF * 240ull / 31250ull);
+        else
+            budgetRd[j] = jobs.budgetBytes[j] >= 18 ? (static_cast<long long>(jobs.budgetBytes[j]) - 18) * 8 : -1;
+    }
+    ENCCHK(hipMemcpyAsync(cb.rd.dR, &encTabsRd(), sizeof(EncRdTabs), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(cb.rd.dFloor, floorRd.data(), sizeof(unsigned long long) * floorRd.size(), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(cb.rd.dPeak, 0, sizeof(uint32_t) * 16 * in.nStreams, st));
+    ENCCHK(hipMemsetAsync(cb.rd.dD0, 0, sizeof(unsigned long long) * 16 * in.nStreams, st));
+    hipLaunchKernelGGL(encRdItemKernel, dim3(F), dim3(256), 0, st, cb.dT, cb.rd.dR, cb.dSpec, cb.dFS, cb.rd.dItems, cb.rd.dPeak, cb.rd.dD0);
+    return DCS_OK;
+}
+
+// R2 and R3 for the n jobs of a group from job j0; the choices are on the host after runGroup's wait
+DcsStatus EncRun::rdRunGroup(uint32_t j0, uint32_t n)
+{
+    ENCCHK(hipMemcpyAsync(gb.rd.dBudget, budgetRd.data() + j0, sizeof(long long) * n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(encRdTrellisKernel<false>, dim3(kRdRowsPerJob / 16 * n), dim3(256), 0, st, cb.dT, cb.rd.dR, cb.rd.dItems, cb.rd.dPeak,
+                       cb.rd.dFloor, gb.dJobs, cb.dSets, gb.rd.dTot, static_cast<const EncRdChoice *>(nullptr),
+                       static_cast<uint8_t *>(nullptr), static_cast<uint8_t *>(nullptr));
+    hipLaunchKernelGGL(encRdChooseKernel, dim3(n), dim3(256), 0, st, gb.rd.dTot, cb.rd.dD0, gb.dJobs, cb.dSets, gb.rd.dBudget, gb.rd.dChoice);
+    ENCCHK(hipMemcpyAsync(choiceRd.data() + j0, gb.rd.dChoice, sizeof(EncRdChoice) * n, hipMemcpyDeviceToHost, st));
+    return DCS_OK;
+}
+
+// R4 to R6 for the resident group: the chosen chains with their survivors, the frames' bits and offsets, header and pack
+DcsStatus EncRun::rdPackGroup(uint32_t n, uint32_t JF)
+{
+    ENCCHK(hipMemsetAsync(gb.rd.dCodes, 0, size_t(16) * JF, st));
+    hipLaunchKernelGGL(encRdTrellisKernel<true>, dim3(n), dim3(256), 0, st, cb.dT, cb.rd.dR, cb.rd.dItems, cb.rd.dPeak, cb.rd.dFloor,
+                       gb.dJobs, cb.dSets, static_cast<EncRdTot *>(nullptr), gb.rd.dChoice, gb.rd.dSurv, gb.rd.dEnd);
+    hipLaunchKernelGGL(encRdBackKernel, dim3((16 * n + 63) / 64), dim3(64), 0, st, gb.dJobs, gb.rd.dChoice, gb.rd.dSurv, gb.rd.dEnd, n,
+                       gb.rd.dCodes);
+    hipLaunchKernelGGL(encRdBitsKernel, dim3((JF + 63) / 64), dim3(64), 0, st, cb.dT, cb.rd.dItems, cb.rd.dPeak, gb.dFJ, gb.dJobs,
+                       gb.rd.dChoice, gb.rd.dCodes, JF, gb.rd.dBits);
+    hipLaunchKernelGGL(encRdOffsetKernel, dim3(n), dim3(256), 0, st, gb.dJobs, gb.rd.dBits, gb.dFrameOff);
+    hipLaunchKernelGGL(encRdHeadKernel, dim3((n + 63) / 64), dim3(64), 0, st, cb.dT, cb.rd.dPeak, gb.dJobs, gb.rd.dChoice, gb.dOutOff, n, dW);
+    hipLaunchKernelGGL(encRdPackKernel, dim3(JF), dim3(64), 0, st, cb.dT, cb.rd.dR, cb.dSpec, cb.rd.dItems, cb.rd.dPeak, gb.dFJ, gb.dJobs,
+                       gb.rd.dChoice, gb.rd.dCodes, gb.dFrameOff, gb.dOutOff, dW);
+    return DCS_OK;
+}
+
+}  // namespace
+
+extern "C" size_t dcs_encode_rd_bound(uint64_t nSamples)
+{
+    return boundOf(nSamples, rdMaxFrameBits());
+}
+
+extern "C" DcsStatus dcs_encode_rd_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                           const DcsEncodeParams *params, const uint32_t *budgetBytes, uint8_t *out, uint64_t outCap,
+                                           uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
+        return DCS_ERR_INVALID_ARG;
+    if (!paramsValidRd(params))
+    {
+        dcsCtxSetError(ctx, "dcs_encode_rd_streams: formatVersion 0x9400, streamFormatType 0, 1 or -1, streamFormatSubType 0, 3 or -1, "
+                            "targetBitRate 1..100 000 000 and finite parameters");
+        return DCS_ERR_INVALID_ARG;
+    }
+    EncInput in;
+    in.sampleOffsets = sampleOffsets;
+    in.nStreams = nStreams;
+    in.hostPcm = pcm;
+    std::vector<DcsSweepJob> list(nStreams);
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+        list[i] = DcsSweepJob{ i, 0 };
+    EncJobs js{ params, 1, list.data(), nStreams, false };
+    js.rd = true;
+    js.budgetBytes = budgetBytes;
+    EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
+    to.infoRd = infoRd;
+    return EncRun(ctx, in, js, to, EncSweep()).run();
+}

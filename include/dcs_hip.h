@@ -943,6 +943,40 @@ DcsStatus dcs_encode93a_streams(DcsCtx *ctx, const float *pcm, const uint64_t *s
                                 const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
                                 DcsEncodeInfo *info, DcsEncode93aInfo *info93a);
 
+/* Encoding 1994+ streams to a byte budget by rate-distortion search (INTEGRATION.md "Encoding to a budget (1994+)",
+ * DESIGN.md 10.11).  dcs_encode_streams writes what the reference's DCSEncoder writes, a heuristic no budget binds; this
+ * second encoder writes the same format with header scale codes, band count and per-frame band-type codes of its own: a
+ * trellis over the band-type codes per band, header code and Lagrangian multiplier of a ladder, on exact integer items
+ * (squared error against the DECODER's frame-buffer word at mixing multiplier 0xFEFC, exact sample bits).  There is no
+ * reference encoder to equal, so what holds is: the reference decoder reads every stream to its last bit and its frame
+ * buffers give sqErr exactly; the bytes are those of the integer algorithm stated in DESIGN.md 10.11 (tests/enc94rd_ref.py
+ * restates it); the stream keeps to its budget whenever any candidate searched does, else the candidate with the fewest
+ * bits is written and fits = 0 is reported (size is never a reason to refuse).
+ * formatVersion 0x9400 only; streamFormatType 0, 1 or -1 and streamFormatSubType 0, 3 or -1, the wildcards as
+ * dcs_encode_streams reads them (the candidates (0,0), (0,3), (1,0), (1,3) in that order; Type 0 is searched once).
+ * budgetBytes NULL: the budget is floor(targetBitRate * nFrames * 240 / 31250) frame bits; else stream i, all of it
+ * (2 + 16 + ceil(frameBits / 8) bytes), is at most budgetBytes[i].  maximumQuantizationError sets the per-band error floor
+ * below which more bits are not spent (0: none); powerBandCutoff and minimumDynamicRange do not apply.  Input, capacity
+ * (DCS_ERR_CAPACITY with outOffsets written), ordering and errors as dcs_encode_streams; DcsEncodeInfo.bandsToKeep is the
+ * header's band count. */
+typedef struct DcsEncodeRdInfo
+{
+    int32_t  formatType;               /* the layout written ...                                                           */
+    int32_t  formatSubType;            /* ... as in DcsEncodeInfo                                                          */
+    int32_t  ladderIndex;              /* the entry of the lambda ladder the stream was searched with                      */
+    int32_t  numBands;                 /* bands the header keeps (1..16; 3..16 for Type 1 sub-type 0)                      */
+    uint64_t frameBits;                /* bits after the 18 header bytes; the stream is 18 + ceil(frameBits / 8) bytes     */
+    uint64_t budgetBits;               /* the budget in frame bits (0 where budgetBytes[i] < 18)                           */
+    uint64_t sqErr;                    /* sum over frames and coefficients of (target - decoded frame-buffer word)^2       */
+    int32_t  fits;                     /* 1: frameBits <= budgetBits; 0: nothing searched fits, the fewest bits were written */
+    int32_t  reserved;
+} DcsEncodeRdInfo;
+/* the largest stream nSamples samples can encode to: every frame at the widest option (0 as dcs_encode_bound) */
+size_t    dcs_encode_rd_bound(uint64_t nSamples);
+DcsStatus dcs_encode_rd_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                const DcsEncodeParams *params, const uint32_t *budgetBytes, uint8_t *out, uint64_t outCap,
+                                uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd);
+
 /* ------------------------------------------------------------------------------------------------
  * Transcoding: DCS streams of any family into the family of `target` (formatVersion 0x9400: the 1994+ encoder; 0x9301 /
  * 0x9302: the OS93 encoder; checked as those encoders check it), the reference's DCSEncoder::EncodeDCSFile

@@ -4,7 +4,9 @@ synchronises the device): frames per second and the real-time factor (seconds of
 256 streams x 256 frames and for one stream of 65 535 frames (the format's longest), in the reference's wildcard layout
 (three layouts searched).  --version 9301 / 9302: the OS93 encoder (dcs_encode93_streams) in its wildcard (0x9302: Type 0
 and Type 1; 0x9301: Type 0).  --version 9301 --type 1 / -1: the OS93a Type-1 encoder (dcs_encode93a_streams), alone or
-in its wildcard beside Type 0.  --rocprof: per-kernel times from `rocprofv3 --kernel-trace --stats`, in a run of their own.
+in its wildcard beside Type 0.  --rd: the rate-distortion 1994+ encoder (dcs_encode_rd_streams, every layout, each stream held
+to the bytes dcs_encode_streams gave it) against dcs_encode_streams in the same run and against encode_fit over the six
+rates of tests/sweep_ref.py, which is what it replaces for a budget: medians of alternating rounds.  --rocprof: per-kernel times from `rocprofv3 --kernel-trace --stats`, in a run of their own.
 Prints one JSON line."""
 import argparse
 import csv
@@ -61,13 +63,54 @@ def rocprof(iters, version, typ):
         return out
 
 
+RATES = (256000, 192000, 128000, 96000, 64000, 48000)
+
+
+def rd_rounds(ctx, D, pcm, rounds, with_fit):
+    """alternating rounds of encode_streams, encode_rd_streams within its bytes, and encode_fit over RATES within their sum"""
+    budgets = [len(s) for s in ctx.encode_streams(pcm)[0]]
+    sets = [D.encode_params(None, targetBitRate=r) for r in RATES]
+    calls = dict(encode_streams=lambda: ctx.encode_streams(pcm), encode_rd_streams=lambda: ctx.encode_rd_streams(pcm, None, budgets))
+    if with_fit:
+        calls["encode_fit"] = lambda: ctx.encode_fit(pcm, sets, sum(budgets))
+    times = {k: [] for k in calls}
+    out = {}
+    for k, f in calls.items():
+        out[k] = f()                            # warm-up: buffers, code objects
+    for _ in range(rounds):
+        for k, f in calls.items():
+            t0 = time.perf_counter()
+            f()
+            times[k].append(time.perf_counter() - t0)
+    frames = sum((len(x) + 239) // 240 for x in pcm)
+    res = dict(streams=len(pcm), frames=frames, rounds=rounds)
+    for k in calls:
+        med = float(np.median(times[k]))
+        res[k] = dict(median_ms=round(med * 1e3, 3), min_ms=round(min(times[k]) * 1e3, 3), max_ms=round(max(times[k]) * 1e3, 3),
+                      frames_per_s=round(frames / med), bytes_out=sum(len(s) for s in out[k][0]))
+    info = out["encode_rd_streams"][2]
+    res["encode_rd_streams"].update(fits=int(info["fits"].sum()), sq_err=int(info["sqErr"].astype(object).sum()))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--version", choices=["9400", "9301", "9302"], default="9400")
     ap.add_argument("--type", type=int, choices=[-1, 1], default=None, help="with --version 9301: dcs_encode93a_streams, Type 1 or the wildcard")
+    ap.add_argument("--rd", action="store_true", help="dcs_encode_rd_streams against encode_streams and encode_fit, alternating rounds")
+    ap.add_argument("--streams", type=int, default=256, help="with --rd: streams of 256 frames in the batch")
     a = ap.parse_args()
+    if a.rd:
+        import dcsexplorer_amd as D
+        ctx = D.Context(0)
+        res = dict(build_id=D.build_id(), batch=rd_rounds(ctx, D, [signal(256 * 240, k) for k in range(a.streams)], a.iters, True),
+                   # (encode_fit measures, and a measured stream has 65 534 frames at the most: the long stream goes without it)
+                   stream_65535=rd_rounds(ctx, D, [signal(65535 * 240, 999)], max(2, a.iters // 3), False))
+        ctx.close()
+        print(json.dumps(res))
+        return
     if a.type is not None and a.version != "9301":
         ap.error("--type goes with --version 9301")
     if a.rocprof:
