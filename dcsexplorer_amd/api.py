@@ -234,7 +234,7 @@ EXPORTS = [
     "dcs_encode_params_default", "dcs_encode_bound", "dcs_encode_header", "dcs_encode_streams",
     "dcs_encode93_bound", "dcs_encode93_header", "dcs_encode93_streams",
     "dcs_encode93a_bound", "dcs_encode93a_streams", "dcs_encode93a_sweep",
-    "dcs_encode_rd_bound", "dcs_encode_rd_streams",
+    "dcs_encode_rd_bound", "dcs_encode_rd_streams", "dcs_encode93_rd_bound", "dcs_encode93_rd_streams",
     "dcs_transcode_plan", "dcs_transcode_streams",
     "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
     "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
@@ -581,6 +581,10 @@ def load_library():
     L.dcs_encode_rd_bound.argtypes = [ctypes.c_uint64]
     L.dcs_encode_rd_streams.restype = i32
     L.dcs_encode_rd_streams.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), vp, vp, ctypes.c_uint64, vp, vp, vp]
+    L.dcs_encode93_rd_bound.restype = sz
+    L.dcs_encode93_rd_bound.argtypes = [ctypes.c_uint64]
+    L.dcs_encode93_rd_streams.restype = i32
+    L.dcs_encode93_rd_streams.argtypes = L.dcs_encode_rd_streams.argtypes
     L.dcs_encode93a_sweep.restype = i32
     L.dcs_encode93a_sweep.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, sz, vp]
     L.dcs_encode_sweep_group_frames.restype = None
@@ -893,6 +897,11 @@ ENCODE_RD_INFO_DTYPE = np.dtype([("formatType", "<i4"), ("formatSubType", "<i4")
 def encode_rd_bound(n_samples):
     """dcs_encode_rd_bound: the largest stream n_samples samples can encode to through encode_rd_streams (0 = not encodable)"""
     return int(load_library().dcs_encode_rd_bound(int(n_samples)))
+
+
+def encode93_rd_bound(n_samples):
+    """dcs_encode93_rd_bound: the largest stream n_samples samples can encode to through encode93_rd_streams (0 = not encodable)"""
+    return int(load_library().dcs_encode93_rd_bound(int(n_samples)))
 
 
 def encode93a_params(fmt, **params):
@@ -1524,6 +1533,27 @@ class Context:
         out = np.zeros(max(cap, 1), np.uint8)
         _check(self.L.dcs_encode_rd_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(bud) if bud is not None and n else None,
                                             _ptr(out), cap, _ptr(out_offs), _ptr(info), _ptr(info_rd)), self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info, info_rd
+
+    def encode93_rd_streams(self, pcm_list, os_=OS93B, budget=None, **params):
+        """dcs_encode93_rd_streams: PCM at 31 250 Hz (as encode93_streams) -> OS93 Type-0 streams of os_ (OS93A or OS93B) from
+        the rate-distortion search of DESIGN.md 10.12, each held to a budget.  budget: None = the frame bits targetBitRate
+        gives; an int = the most bytes any stream may have; a sequence = per stream.  Returns (list of bytes,
+        ENCODE_INFO_DTYPE array, ENCODE_RD_INFO_DTYPE array)."""
+        if os_ not in _ENCODE93_VERSION:
+            raise ValueError("encode93_rd_streams: os_ is OS93A or OS93B")
+        p = encode_params(None, **dict(dict(formatVersion=_ENCODE93_VERSION[os_], streamFormatType=0, streamFormatSubType=0), **params))
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        bud = None
+        if budget is not None:
+            bud = np.ascontiguousarray(np.broadcast_to(np.asarray(budget, np.int64), (n,)).clip(0, 0xFFFFFFFF), dtype=np.uint32)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info, info_rd = np.zeros(n, ENCODE_INFO_DTYPE), np.zeros(n, ENCODE_RD_INFO_DTYPE)
+        cap = sum(encode93_rd_bound(offs[i + 1] - offs[i]) for i in range(n))
+        out = np.zeros(max(cap, 1), np.uint8)
+        _check(self.L.dcs_encode93_rd_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(bud) if bud is not None and n else None,
+                                              _ptr(out), cap, _ptr(out_offs), _ptr(info), _ptr(info_rd)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info, info_rd
 
     def encode_sweep(self, pcm_list, sets, jobs=None, measure=True, streams=True):

@@ -35,6 +35,9 @@
 // the swap and the driver, writes the 1994+ format from a trellis search of its own and holds each job to a byte budget; a
 // call of it has jobs of this family only.
 //
+// The rate-distortion OS93 Type-0 encoder (dcs_encode93_rd_streams) is a fifth family, S1-S8 in dcs_encode93_rd.hip.h, under the
+// same rules: E1, the swap and the driver are shared, the trellis runs over the bands of a frame, a call has jobs of this family only.
+//
 // E1 and encStreamKernel run per stream and do not read the parameters, and neither does A1's search; A1's walk reads one
 // of them, maximumQuantizationError, and runs once per distinct value.  Everything behind them runs per JOB, a stream
 // encoded with one parameter set (EncJob, EncSet): its rows in the per-frame buffers are the job's own, the spectrum it reads
@@ -1276,6 +1279,7 @@ __global__ __launch_bounds__(256) void encMeasureKernel(const float *__restrict_
 
 #include "dcs_encode93a.hip.h"
 #include "dcs_encode_rd.h"
+#include "dcs_encode93_rd.h"
 
 namespace {
 
@@ -1307,7 +1311,8 @@ struct EncJobs
     uint32_t n;
     bool os93;
     bool rd = false;                        // the R family (dcs_encode_rd.hip.h): every set 0x9400, every job searched to a budget
-    const uint32_t *budgetBytes = nullptr;  // rd: per job, the most bytes its stream may have (null: the sets' targetBitRate)
+    const uint32_t *budgetBytes = nullptr;  // rd, rd93: per job, the most bytes its stream may have (null: the sets' targetBitRate)
+    bool rd93 = false;                      // the S family (dcs_encode93_rd.hip.h): every set OS93 Type 0, every job searched to a budget
 };
 
 // after the sizes are known: the host memory that takes the `total` bytes (stream i at outOffsets[i]), or null for DCS_ERR_CAPACITY
@@ -1421,6 +1426,13 @@ private:
     DcsStatus rdAnalyse();
     DcsStatus rdRunGroup(uint32_t j0, uint32_t n);
     DcsStatus rdPackGroup(uint32_t n, uint32_t JF);
+    // the S family's share of the same steps (defined behind dcs_encode93_rd.hip.h)
+    DcsStatus rd93AllocCall();
+    hipError_t rd93AllocGroup();
+    DcsStatus rd93Analyse();
+    DcsStatus rd93RunGroup(uint32_t j0, uint32_t n, uint32_t JF);
+    DcsStatus rd93PackGroup(uint32_t n, uint32_t JF);
+    void budgetsRd();
     std::string name(uint32_t i) const { return "stream " + std::to_string(in.label ? in.label[i] : i); }
 
     // ---- fixed by the arguments
@@ -1448,6 +1460,8 @@ private:
     std::vector<unsigned long long> floorRd;    // [set][16]
     std::vector<long long> budgetRd;
     std::vector<EncRdChoice> choiceRd;
+    // the S family: E_b per set (floorRd, one value a set: every band has sixteen samples), budgetRd, and what S5 chose
+    std::vector<Enc93RdChoice> choiceRd93;
 
     // ---- device buffers of the call: valid from allocCall to the end
     struct CallBufs
@@ -1474,6 +1488,13 @@ private:
             uint32_t *dPeak = nullptr;          // [stream][band]
             unsigned long long *dD0 = nullptr, *dFloor = nullptr;   // [stream][band], [set][band]
         } rd;
+        struct                                  // the S family only (S1)
+        {
+            EncRdTabs *dR = nullptr;
+            unsigned long long *dItems = nullptr;       // [stream-frame][band][scale code][option]
+            Enc93RdRec *dRecs = nullptr;        // [stream-frame][band][scale code]
+            unsigned long long *dD0 = nullptr, *dFloor = nullptr;   // [stream][band], [set]
+        } r93;
     } cb;
     CacheArena call;
 
@@ -1499,6 +1520,17 @@ private:
             uint8_t *dSurv = nullptr, *dEnd = nullptr, *dCodes = nullptr;   // [job-frame][band][state], [job][band], [job-frame][band]
             uint32_t *dBits = nullptr;          // [job-frame]
         } rd;
+        struct                                                                                      // the S family only (S2-S8)
+        {
+            unsigned long long *dProxyJ = nullptr;      // [job][band][scale code][lambda]
+            uint32_t *dProxyB = nullptr;
+            Enc93RdHead *dHead = nullptr;       // [job][lambda]
+            Enc93RdTot *dTot = nullptr;         // [job][lambda]
+            Enc93RdChoice *dChoice = nullptr;
+            long long *dBudget = nullptr;
+            uint8_t *dCodes = nullptr;          // [job-frame][band]: the band's state
+            uint32_t *dBits = nullptr;          // [job-frame]
+        } r93;
     } gb;
     CacheArena group;
 
@@ -1578,8 +1610,8 @@ void EncRun::buildSets()
                 cmask |= 1u << c;
         const uint32_t vmask = ((cmask & 3) ? 1u : 0u) | ((cmask & 4) ? 2u : 0u) | ((cmask & 8) ? 4u : 0u);
         hsets[k] = EncSet{ p.powerBandCutoff, p.minimumDynamicRange, p.maximumQuantizationError, p.targetBitRate, vmask, cmask };
-        if (!jobs.rd)
-            anyV |= vmask;                      // (a set of the R family: no E stage touches its jobs)
+        if (!jobs.rd && !jobs.rd93)
+            anyV |= vmask;                      // (a set of the R or S family: no E or O stage touches its jobs)
     }
     // the A family's sets (cmask 0 above: no O stage touches their jobs) by their distinct maximumQuantizationError
     setQ.assign(jobs.nSets, kA93None);
@@ -1633,6 +1665,8 @@ DcsStatus EncRun::allocCall()
     }
     if (jobs.rd)
         ENCTRY(rdAllocCall());
+    if (jobs.rd93)
+        ENCTRY(rd93AllocCall());
     return DCS_OK;
 }
 
@@ -1695,6 +1729,8 @@ hipError_t EncRun::allocGroup()
     }
     if (jobs.rd)
         HIPTRY(rdAllocGroup());
+    if (jobs.rd93)
+        HIPTRY(rd93AllocGroup());
     return hipSuccess;
 }
 
@@ -1768,6 +1804,8 @@ DcsStatus EncRun::runGroup(uint32_t g)
                            cb.a93.dSetQ, gb.a93.dChoice);
     if (jobs.rd)
         ENCTRY(rdRunGroup(j0, n));
+    if (jobs.rd93)
+        ENCTRY(rd93RunGroup(j0, n, JF));
     ENCCHK(hipGetLastError());
     if (anyV != 0)
     {
@@ -1792,6 +1830,13 @@ DcsStatus EncRun::runGroup(uint32_t g)
         win[j0 + k] = choiceRd[j0 + k].variant;
         keep[j0 + k] = choiceRd[j0 + k].numBands;
         size[j0 + k] = 18 + (choiceRd[j0 + k].frameBits + 7) / 8;
+    }
+    // a job of the S family: Type 0, its header's band count, 18 bytes and the frames' bits
+    for (uint32_t k = 0 ; jobs.rd93 && k < n ; ++k)
+    {
+        win[j0 + k] = 0;
+        keep[j0 + k] = choiceRd93[j0 + k].numBands;
+        size[j0 + k] = 18 + (choiceRd93[j0 + k].frameBits + 7) / 8;
     }
     resident = g;
     residentFrames = JF;
@@ -1826,6 +1871,8 @@ DcsStatus EncRun::analyse()
     ENCCHK(hipMemcpyAsync(bad.data(), cb.dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
     if (jobs.rd)
         return rdAnalyse();
+    if (jobs.rd93)
+        return rd93Analyse();
     if (qs.empty())
         return DCS_OK;
     // A1: one search per stream-frame; kA93QPerLaunch of the distinct q to a launch
@@ -1883,7 +1930,13 @@ DcsStatus EncRun::placeOutput()
             to.info93a[j] = setQ[jobs.list[j].paramSet] == kA93None ? DcsEncode93aInfo{}
                             : DcsEncode93aInfo{ c.selector, c.ladderIndex, c.numBands, 0, c.frameBits, budget, c.sumD };
         }
-        if (to.infoRd != nullptr)
+        if (to.infoRd != nullptr && jobs.rd93)
+        {
+            const Enc93RdChoice &c = choiceRd93[j];
+            to.infoRd[j] = DcsEncodeRdInfo{ 0, 0, c.ladderIndex, c.numBands, c.frameBits,
+                                            static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
+        }
+        else if (to.infoRd != nullptr)
         {
             const EncRdChoice &c = choiceRd[j];
             to.infoRd[j] = DcsEncodeRdInfo{ kCandType[c.variant], kCandSub[c.variant], c.ladderIndex, c.numBands, c.frameBits,
@@ -1965,6 +2018,8 @@ DcsStatus EncRun::packGroup(uint32_t g)
     }
     if (jobs.rd)
         ENCTRY(rdPackGroup(n, JF));
+    if (jobs.rd93)
+        ENCTRY(rd93PackGroup(n, JF));
     hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
     ENCCHK(hipGetLastError());
     return DCS_OK;
@@ -2106,6 +2161,8 @@ DcsStatus EncRun::run()
     win.resize(jobs.n); keep.resize(jobs.n); size.resize(jobs.n); choiceA.resize(jobs.n);
     if (jobs.rd)
         choiceRd.resize(jobs.n);
+    if (jobs.rd93)
+        choiceRd93.resize(jobs.n);
     ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
     ENCTRY(allocCall());
     ENCTRY(allocGroups());
@@ -2542,12 +2599,9 @@ hipError_t EncRun::rdAllocGroup()
     return hipSuccess;
 }
 
-// R1 over every stream-frame; the budgets of all jobs, in frame bits
-DcsStatus EncRun::rdAnalyse()
+// the budgets of all jobs, in frame bits (-1: nothing fits)
+void EncRun::budgetsRd()
 {
-    floorRd.resize(size_t(16) * jobs.nSets);
-    for (uint32_t k = 0 ; k < jobs.nSets ; ++k)
-        floorERd(jobs.sets[k].maximumQuantizationError, floorRd.data() + size_t(16) * k);
     budgetRd.resize(jobs.n);
     for (uint32_t j = 0 ; j < jobs.n ; ++j)
     {
@@ -2557,6 +2611,15 @@ DcsStatus EncRun::rdAnalyse()
         else
             budgetRd[j] = jobs.budgetBytes[j] >= 18 ? (static_cast<long long>(jobs.budgetBytes[j]) - 18) * 8 : -1;
     }
+}
+
+// R1 over every stream-frame; the budgets
+DcsStatus EncRun::rdAnalyse()
+{
+    floorRd.resize(size_t(16) * jobs.nSets);
+    for (uint32_t k = 0 ; k < jobs.nSets ; ++k)
+        floorERd(jobs.sets[k].maximumQuantizationError, floorRd.data() + size_t(16) * k);
+    budgetsRd();
     ENCCHK(hipMemcpyAsync(cb.rd.dR, &encTabsRd(), sizeof(EncRdTabs), hipMemcpyHostToDevice, st));
     ENCCHK(hipMemcpyAsync(cb.rd.dFloor, floorRd.data(), sizeof(unsigned long long) * floorRd.size(), hipMemcpyHostToDevice, st));
     ENCCHK(hipMemsetAsync(cb.rd.dPeak, 0, sizeof(uint32_t) * 16 * in.nStreams, st));
@@ -2622,6 +2685,122 @@ extern "C" DcsStatus dcs_encode_rd_streams(DcsCtx *ctx, const float *pcm, const 
         list[i] = DcsSweepJob{ i, 0 };
     EncJobs js{ params, 1, list.data(), nStreams, false };
     js.rd = true;
+    js.budgetBytes = budgetBytes;
+    EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
+    to.infoRd = infoRd;
+    return EncRun(ctx, in, js, to, EncSweep()).run();
+}
+
+// ------------------------------------------ the rate-distortion OS93 Type-0 encoder: kernels and driver (dcs_encode93_rd.hip.h)
+// (behind every other kernel of the unit once more)
+
+#include "dcs_encode93_rd.hip.h"
+
+namespace {
+
+DcsStatus EncRun::rd93AllocCall()
+{
+    ENCCHK(call.alloc(&cb.r93.dR, 1));
+    ENCCHK(call.alloc(&cb.r93.dItems, size_t(kRd93ItemsPerFrame) * F));
+    ENCCHK(call.alloc(&cb.r93.dRecs, size_t(kRd93RecsPerFrame) * F));
+    ENCCHK(call.alloc(&cb.r93.dD0, size_t(16) * in.nStreams));
+    ENCCHK(call.alloc(&cb.r93.dFloor, jobs.nSets));
+    return DCS_OK;
+}
+
+hipError_t EncRun::rd93AllocGroup()
+{
+    const size_t JF = static_cast<size_t>(groupFrames), NJ = groupJobs;
+    HIPTRY(group.alloc(&gb.r93.dProxyJ, size_t(kRd93ProxyPerJob) * NJ));
+    HIPTRY(group.alloc(&gb.r93.dProxyB, size_t(kRd93ProxyPerJob) * NJ));
+    HIPTRY(group.alloc(&gb.r93.dHead, size_t(kRdKL) * NJ));
+    HIPTRY(group.alloc(&gb.r93.dTot, size_t(kRdKL) * NJ));
+    HIPTRY(group.alloc(&gb.r93.dChoice, NJ));
+    HIPTRY(group.alloc(&gb.r93.dBudget, NJ));
+    HIPTRY(group.alloc(&gb.r93.dCodes, 16 * JF));
+    HIPTRY(group.alloc(&gb.r93.dBits, JF));
+    return hipSuccess;
+}
+
+// S1 over every stream-frame; the budgets
+DcsStatus EncRun::rd93Analyse()
+{
+    const uint16_t version = jobs.sets[0].formatVersion;        // (one per call: dcs_encode93_rd_streams has one set)
+    floorRd.resize(jobs.nSets);
+    for (uint32_t k = 0 ; k < jobs.nSets ; ++k)
+        floorRd[k] = floorE93Rd(jobs.sets[k].maximumQuantizationError);
+    budgetsRd();
+    ENCCHK(hipMemcpyAsync(cb.r93.dR, &encTabs93Rd(version), sizeof(EncRdTabs), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(cb.r93.dFloor, floorRd.data(), sizeof(unsigned long long) * floorRd.size(), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(cb.r93.dD0, 0, sizeof(unsigned long long) * 16 * in.nStreams, st));
+    hipLaunchKernelGGL(enc93RdItemKernel, dim3(F), dim3(256), 0, st, cb.dT, cb.r93.dR, rd93M0(version), cb.dSpec, cb.dFS, cb.r93.dItems,
+                       cb.r93.dRecs, cb.r93.dD0);
+    return DCS_OK;
+}
+
+// S2 to S5 for the n jobs (JF job-frames) of a group from job j0; the choices are on the host after runGroup's wait
+DcsStatus EncRun::rd93RunGroup(uint32_t j0, uint32_t n, uint32_t JF)
+{
+    const uint32_t chunks = (JF + kRd93ChunkFrames - 1) / kRd93ChunkFrames;
+    ENCCHK(hipMemcpyAsync(gb.r93.dBudget, budgetRd.data() + j0, sizeof(long long) * n, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(gb.r93.dProxyJ, 0, sizeof(unsigned long long) * kRd93ProxyPerJob * n, st));
+    ENCCHK(hipMemsetAsync(gb.r93.dProxyB, 0, sizeof(uint32_t) * kRd93ProxyPerJob * n, st));
+    ENCCHK(hipMemsetAsync(gb.r93.dTot, 0, sizeof(Enc93RdTot) * kRdKL * n, st));
+    hipLaunchKernelGGL(enc93RdProxyKernel, dim3(kRd93ProxyPerJob / 256, chunks), dim3(256), 0, st, cb.r93.dR, cb.r93.dItems, cb.r93.dFloor,
+                       gb.dFJ, gb.dJobs, JF, gb.r93.dProxyJ, gb.r93.dProxyB);
+    hipLaunchKernelGGL(enc93RdHeaderKernel, dim3(n), dim3(64), 0, st, gb.r93.dProxyJ, gb.r93.dProxyB, cb.r93.dD0, gb.dJobs, gb.r93.dHead);
+    hipLaunchKernelGGL(enc93RdTrellisKernel<false>, dim3(chunks, kRdKL), dim3(256), 0, st, cb.r93.dR, cb.r93.dItems, cb.r93.dRecs,
+                       cb.r93.dFloor, gb.dFJ, gb.dJobs, JF, gb.r93.dHead, static_cast<const Enc93RdChoice *>(nullptr), gb.r93.dTot,
+                       static_cast<uint8_t *>(nullptr), static_cast<uint32_t *>(nullptr));
+    hipLaunchKernelGGL(enc93RdChooseKernel, dim3((n + 63) / 64), dim3(64), 0, st, gb.r93.dTot, gb.r93.dHead, cb.r93.dD0, gb.dJobs,
+                       gb.r93.dBudget, n, gb.r93.dChoice);
+    ENCCHK(hipMemcpyAsync(choiceRd93.data() + j0, gb.r93.dChoice, sizeof(Enc93RdChoice) * n, hipMemcpyDeviceToHost, st));
+    return DCS_OK;
+}
+
+// S6 to S8 for the resident group: the chosen lambda's trellises with their paths, the frames' offsets, header and pack
+DcsStatus EncRun::rd93PackGroup(uint32_t n, uint32_t JF)
+{
+    const uint32_t chunks = (JF + kRd93ChunkFrames - 1) / kRd93ChunkFrames;
+    const uint32_t m0 = rd93M0(jobs.sets[0].formatVersion);
+    hipLaunchKernelGGL(enc93RdTrellisKernel<true>, dim3(chunks), dim3(256), 0, st, cb.r93.dR, cb.r93.dItems, cb.r93.dRecs, cb.r93.dFloor,
+                       gb.dFJ, gb.dJobs, JF, static_cast<const Enc93RdHead *>(nullptr), gb.r93.dChoice, static_cast<Enc93RdTot *>(nullptr),
+                       gb.r93.dCodes, gb.r93.dBits);
+    hipLaunchKernelGGL(encRdOffsetKernel, dim3(n), dim3(256), 0, st, gb.dJobs, gb.r93.dBits, gb.dFrameOff);
+    hipLaunchKernelGGL(enc93RdHeadKernel, dim3((n + 63) / 64), dim3(64), 0, st, gb.dJobs, gb.r93.dChoice, gb.dOutOff, n, dW);
+    hipLaunchKernelGGL(enc93RdPackKernel, dim3(JF), dim3(64), 0, st, cb.dT, cb.r93.dR, m0, cb.dSpec, cb.r93.dRecs, gb.dFJ, gb.dJobs,
+                       gb.r93.dChoice, gb.r93.dCodes, gb.dFrameOff, gb.dOutOff, dW);
+    return DCS_OK;
+}
+
+}  // namespace
+
+extern "C" size_t dcs_encode93_rd_bound(uint64_t nSamples)
+{
+    return boundOf(nSamples, kRd93MaxFrameBits);
+}
+
+extern "C" DcsStatus dcs_encode93_rd_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                             const DcsEncodeParams *params, const uint32_t *budgetBytes, uint8_t *out, uint64_t outCap,
+                                             uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
+        return DCS_ERR_INVALID_ARG;
+    if (!paramsValid93Rd(params))
+    {
+        dcsCtxSetError(ctx, "dcs_encode93_rd_streams: formatVersion 0x9301 or 0x9302, streamFormatType 0 or -1 (OS93 Type 0; Type 1 is "
+                            "not searched), targetBitRate 1..100 000 000 and finite parameters");
+        return DCS_ERR_INVALID_ARG;
+    }
+    EncInput in;
+    in.sampleOffsets = sampleOffsets;
+    in.nStreams = nStreams;
+    in.hostPcm = pcm;
+    std::vector<DcsSweepJob> list(nStreams);
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+        list[i] = DcsSweepJob{ i, 0 };
+    EncJobs js{ params, 1, list.data(), nStreams, true };
+    js.rd93 = true;
     js.budgetBytes = budgetBytes;
     EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
     to.infoRd = infoRd;

@@ -977,6 +977,27 @@ DcsStatus dcs_encode_rd_streams(DcsCtx *ctx, const float *pcm, const uint64_t *s
                                 const DcsEncodeParams *params, const uint32_t *budgetBytes, uint8_t *out, uint64_t outCap,
                                 uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd);
 
+/* Encoding OS93 Type-0 streams to a byte budget by rate-distortion search (INTEGRATION.md "Encoding to a budget (OS93)",
+ * DESIGN.md 10.12): the layout Indiana Jones, Judge Dredd and Star Trek TNG all play, one bit stream under formatVersion
+ * 0x9301 and 0x9302.  dcs_encode93_streams writes what the reference's DCSEncoder writes; this second encoder writes the
+ * same layout with all sixteen header scale codes, the band count and every band's option (zero band, one of fifteen
+ * widths, delta or double-delta coding) of its own.  The OS93 decoder's state is reset at every frame, so the trellis runs
+ * over the bands of one frame and frames are independent.  The contract is dcs_encode_rd_streams': the reference decoder
+ * reads every stream to its last bit and its frame buffers (at mixing multiplier 0xFFFE for 0x9301, 0xFEFC for 0x9302:
+ * the two versions may write different bytes for the same PCM) give sqErr exactly, against targets that are the NEGATED
+ * spectrum: the OS93 transform turns the polarity of what the frame buffer holds, so these streams decode to the source's
+ * polarity, the opposite of dcs_encode93_streams'; the bytes are those of the integer
+ * algorithm of DESIGN.md 10.12 (tests/enc93rd_ref.py restates it); the stream keeps to its budget whenever any of the 56
+ * candidates searched does, else the candidate with the fewest bits is written and fits = 0 is reported.
+ * formatVersion 0x9301 or 0x9302; streamFormatType 0 or -1 (both mean Type 0: OS93b Type 1 is not searched, OS93a Type 1
+ * has dcs_encode93a_streams); anything else is DCS_ERR_INVALID_ARG with a message.  budgetBytes, maximumQuantizationError,
+ * input, capacity, ordering and errors as dcs_encode_rd_streams / dcs_encode93_streams; DcsEncodeRdInfo.formatType and
+ * formatSubType are 0, numBands is 1..16. */
+size_t    dcs_encode93_rd_bound(uint64_t nSamples);
+DcsStatus dcs_encode93_rd_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                  const DcsEncodeParams *params, const uint32_t *budgetBytes, uint8_t *out, uint64_t outCap,
+                                  uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd);
+
 /* ------------------------------------------------------------------------------------------------
  * Transcoding: DCS streams of any family into the family of `target` (formatVersion 0x9400: the 1994+ encoder; 0x9301 /
  * 0x9302: the OS93 encoder; checked as those encoders check it), the reference's DCSEncoder::EncodeDCSFile

@@ -6,7 +6,9 @@ synchronises the device): frames per second and the real-time factor (seconds of
 and Type 1; 0x9301: Type 0).  --version 9301 --type 1 / -1: the OS93a Type-1 encoder (dcs_encode93a_streams), alone or
 in its wildcard beside Type 0.  --rd: the rate-distortion 1994+ encoder (dcs_encode_rd_streams, every layout, each stream held
 to the bytes dcs_encode_streams gave it) against dcs_encode_streams in the same run and against encode_fit over the six
-rates of tests/sweep_ref.py, which is what it replaces for a budget: medians of alternating rounds.  --rocprof: per-kernel times from `rocprofv3 --kernel-trace --stats`, in a run of their own.
+rates of tests/sweep_ref.py, which is what it replaces for a budget: medians of alternating rounds.  --rd --version 9301 / 9302:
+the rate-distortion OS93 Type-0 encoder (dcs_encode93_rd_streams) against dcs_encode93_streams' Type 0 and encode93a_fit /
+encode_fit in the same way.  --rocprof: per-kernel times from `rocprofv3 --kernel-trace --stats`, in a run of their own.
 Prints one JSON line."""
 import argparse
 import csv
@@ -66,13 +68,23 @@ def rocprof(iters, version, typ):
 RATES = (256000, 192000, 128000, 96000, 64000, 48000)
 
 
-def rd_rounds(ctx, D, pcm, rounds, with_fit):
-    """alternating rounds of encode_streams, encode_rd_streams within its bytes, and encode_fit over RATES within their sum"""
-    budgets = [len(s) for s in ctx.encode_streams(pcm)[0]]
-    sets = [D.encode_params(None, targetBitRate=r) for r in RATES]
-    calls = dict(encode_streams=lambda: ctx.encode_streams(pcm), encode_rd_streams=lambda: ctx.encode_rd_streams(pcm, None, budgets))
+def rd_rounds(ctx, D, pcm, rounds, with_fit, version="9400"):
+    """alternating rounds of encode_streams, encode_rd_streams within its bytes, and encode_fit over RATES within their sum
+    (version 9301 / 9302: encode93_streams' Type 0, encode93_rd_streams, and encode93a_fit / encode_fit on Type-0 sets)"""
+    if version == "9400":
+        budgets = [len(s) for s in ctx.encode_streams(pcm)[0]]
+        sets = [D.encode_params(None, targetBitRate=r) for r in RATES]
+        calls = dict(encode_streams=lambda: ctx.encode_streams(pcm), encode_rd_streams=lambda: ctx.encode_rd_streams(pcm, None, budgets))
+        fit = ctx.encode_fit
+    else:
+        os_ = D.OS93A if version == "9301" else D.OS93B
+        budgets = [len(s) for s in ctx.encode93_streams(pcm, os_, D.FMT_93_T0)[0]]
+        sets = [D.encode93_params(os_, D.FMT_93_T0, targetBitRate=r) for r in RATES]
+        calls = dict(encode_streams=lambda: ctx.encode93_streams(pcm, os_, D.FMT_93_T0),
+                     encode_rd_streams=lambda: ctx.encode93_rd_streams(pcm, os_, budgets))
+        fit = ctx.encode93a_fit if version == "9301" else ctx.encode_fit
     if with_fit:
-        calls["encode_fit"] = lambda: ctx.encode_fit(pcm, sets, sum(budgets))
+        calls["encode_fit"] = lambda: fit(pcm, sets, sum(budgets))
     times = {k: [] for k in calls}
     out = {}
     for k, f in calls.items():
@@ -105,9 +117,10 @@ def main():
     if a.rd:
         import dcsexplorer_amd as D
         ctx = D.Context(0)
-        res = dict(build_id=D.build_id(), batch=rd_rounds(ctx, D, [signal(256 * 240, k) for k in range(a.streams)], a.iters, True),
+        res = dict(build_id=D.build_id(), version=a.version,
+                   batch=rd_rounds(ctx, D, [signal(256 * 240, k) for k in range(a.streams)], a.iters, True, a.version),
                    # (encode_fit measures, and a measured stream has 65 534 frames at the most: the long stream goes without it)
-                   stream_65535=rd_rounds(ctx, D, [signal(65535 * 240, 999)], max(2, a.iters // 3), False))
+                   stream_65535=rd_rounds(ctx, D, [signal(65535 * 240, 999)], max(2, a.iters // 3), False, a.version))
         ctx.close()
         print(json.dumps(res))
         return
