@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     host_threads, partition_streams, decode_streams_sharded, Pipeline, make_refs, FRAME_TAIL_LOST, Node, DevicePath, node_cache_release, device_numa_node, bind_process_to_device_numa,
     FMT_94_T0_S3, ENCODE_INFO_DTYPE, EncodeParams, encode_params, encode_bound, encode_header,
     encode93_params, encode93_bound, encode93_header, ENCODE93A_INFO_DTYPE, encode93a_bound, ENCODE_RD_INFO_DTYPE, encode_rd_bound, encode93_rd_bound, encode93a_params,
+    ENCODE_RD_FIT_INFO_DTYPE, encode_rd_allot,
     SWEEP_RESULT_DTYPE, SWEEP_JOB_DTYPE, SWEEP_MEASURE, sweep_sq_err, encode_sweep_group_frames, encode_fit_choose,
     TRANSCODE_COPIED, TRANSCODE_REENCODED, TRANSCODE_REENCODE_ALL, TRANSCODE_INFO_DTYPE, TRANSCODE_OS, transcode_params, transcode_plan,
     ResampleFilter, RESAMPLE_AT_UNITY, resample_filter_default, resample_count,

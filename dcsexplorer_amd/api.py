@@ -235,6 +235,7 @@ EXPORTS = [
     "dcs_encode93_bound", "dcs_encode93_header", "dcs_encode93_streams",
     "dcs_encode93a_bound", "dcs_encode93a_streams", "dcs_encode93a_sweep",
     "dcs_encode_rd_bound", "dcs_encode_rd_streams", "dcs_encode93_rd_bound", "dcs_encode93_rd_streams",
+    "dcs_encode_rd_fit", "dcs_encode93_rd_fit", "dcs_encode_rd_allot",
     "dcs_transcode_plan", "dcs_transcode_streams",
     "dcs_resample_filter_default", "dcs_resample_count", "dcs_resample_streams", "dcs_encode_streams_at",
     "dcs_wav_parse", "dcs_encode_files_plan", "dcs_wav_decode", "dcs_encode_files",
@@ -585,6 +586,13 @@ def load_library():
     L.dcs_encode93_rd_bound.argtypes = [ctypes.c_uint64]
     L.dcs_encode93_rd_streams.restype = i32
     L.dcs_encode93_rd_streams.argtypes = L.dcs_encode_rd_streams.argtypes
+    if hasattr(L, "dcs_encode_rd_fit"):     # (DCS_HIP_LIB may name a build from before there was a shared budget: A/B against it)
+        L.dcs_encode_rd_fit.restype = i32
+        L.dcs_encode_rd_fit.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp, vp, vp, vp]
+        L.dcs_encode93_rd_fit.restype = i32
+        L.dcs_encode93_rd_fit.argtypes = L.dcs_encode_rd_fit.argtypes
+        L.dcs_encode_rd_allot.restype = i32
+        L.dcs_encode_rd_allot.argtypes = [vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, vp]
     L.dcs_encode93a_sweep.restype = i32
     L.dcs_encode93a_sweep.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, sz, vp]
     L.dcs_encode_sweep_group_frames.restype = None
@@ -902,6 +910,35 @@ def encode_rd_bound(n_samples):
 def encode93_rd_bound(n_samples):
     """dcs_encode93_rd_bound: the largest stream n_samples samples can encode to through encode93_rd_streams (0 = not encodable)"""
     return int(load_library().dcs_encode93_rd_bound(int(n_samples)))
+
+
+# DcsEncodeRdFitInfo: the allocator's record of encode_rd_fit, encode93_rd_fit and encode_rd_allot
+ENCODE_RD_FIT_INFO_DTYPE = np.dtype([("totalBytes", "<u8"), ("leastBytes", "<u8"), ("usedBytes", "<u8"), ("sqErr", "<u8"),
+                                     ("nSteps", "<u4"), ("stepsTaken", "<u4"), ("fits", "<i4"), ("reserved", "<i4")])
+
+
+def encode_rd_allot(curves, total, caps=None, ctx=None):
+    """dcs_encode_rd_allot: the allocator of DESIGN.md 10.13 alone.  curves: per job a sequence of (size in bytes, squared
+    error) candidates; total: the bytes all jobs share; caps: per job the most bytes it may take (None: no caps).  ctx None:
+    on the host; a Context: on its device.  Returns (allotments uint32 [jobs], ENCODE_RD_FIT_INFO_DTYPE record)."""
+    n = len(curves)
+    offs = np.zeros(n + 1, np.uint64)
+    offs[1:] = np.cumsum([len(c) for c in curves], dtype=np.uint64)
+    flat = [p for c in curves for p in c]
+    size = np.array([int(p[0]) for p in flat], np.uint64)
+    err = np.array([int(p[1]) for p in flat], np.uint64)
+    cap = None if caps is None else np.ascontiguousarray(np.asarray(caps, np.int64).clip(0, 0xFFFFFFFF), dtype=np.uint32)
+    if cap is not None and cap.shape != (n,):
+        raise ValueError("encode_rd_allot: one cap per job")
+    allot, fit = np.zeros(n, np.uint32), np.zeros(1, ENCODE_RD_FIT_INFO_DTYPE)
+    L = load_library()
+    st = L.dcs_encode_rd_allot(ctx.h if ctx is not None else None, _ptr(size) if len(flat) else None, _ptr(err) if len(flat) else None,
+                               _ptr(offs), n, int(total), _ptr(cap) if cap is not None and n else None, _ptr(allot) if n else None, _ptr(fit))
+    if ctx is not None:
+        _check(st, ctx.h)
+    elif st != 0:
+        raise DcsError(st, "dcs_encode_rd_allot")
+    return allot, fit[0]
 
 
 def encode93a_params(fmt, **params):
@@ -1555,6 +1592,35 @@ class Context:
         _check(self.L.dcs_encode93_rd_streams(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), _ptr(bud) if bud is not None and n else None,
                                               _ptr(out), cap, _ptr(out_offs), _ptr(info), _ptr(info_rd)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info, info_rd
+
+    def _encode_rd_fit(self, entry, bound, p, pcm_list, total, cap):
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        caps = None
+        if cap is not None:
+            caps = np.ascontiguousarray(np.broadcast_to(np.asarray(cap, np.int64), (n,)).clip(0, 0xFFFFFFFF), dtype=np.uint32)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info, info_rd = np.zeros(n, ENCODE_INFO_DTYPE), np.zeros(n, ENCODE_RD_INFO_DTYPE)
+        fit = np.zeros(1, ENCODE_RD_FIT_INFO_DTYPE)
+        room = sum(bound(offs[i + 1] - offs[i]) for i in range(n))
+        out = np.zeros(max(room, 1), np.uint8)
+        _check(entry(self.h, _ptr(pcm), _ptr(offs), n, ctypes.byref(p), int(total), _ptr(caps) if caps is not None and n else None,
+                     _ptr(out), room, _ptr(out_offs), _ptr(info), _ptr(info_rd), _ptr(fit)), self.h)
+        return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info, info_rd, fit[0]
+
+    def encode_rd_fit(self, pcm_list, total, fmt=None, cap=None, **params):
+        """dcs_encode_rd_fit: PCM as encode_rd_streams -> 1994+ streams that together take at most `total` bytes, the bytes
+        dealt among them by the allocator of DESIGN.md 10.13.  cap: None, an int = the most bytes any stream may have, or a
+        sequence = per stream.  Stream j is what encode_rd_streams writes for budget = its allotment, which is its length.
+        Returns (list of bytes, ENCODE_INFO_DTYPE array, ENCODE_RD_INFO_DTYPE array, ENCODE_RD_FIT_INFO_DTYPE record)."""
+        return self._encode_rd_fit(self.L.dcs_encode_rd_fit, encode_rd_bound, encode_params(fmt, **params), pcm_list, total, cap)
+
+    def encode93_rd_fit(self, pcm_list, total, os_=OS93B, cap=None, **params):
+        """dcs_encode93_rd_fit: encode_rd_fit for OS93 Type-0 streams of os_ (OS93A or OS93B), over encode93_rd_streams' search"""
+        if os_ not in _ENCODE93_VERSION:
+            raise ValueError("encode93_rd_fit: os_ is OS93A or OS93B")
+        p = encode_params(None, **dict(dict(formatVersion=_ENCODE93_VERSION[os_], streamFormatType=0, streamFormatSubType=0), **params))
+        return self._encode_rd_fit(self.L.dcs_encode93_rd_fit, encode93_rd_bound, p, pcm_list, total, cap)
 
     def encode_sweep(self, pcm_list, sets, jobs=None, measure=True, streams=True):
         """dcs_encode_sweep: jobs = (stream, set) pairs encoded in one call; sets = EncodeParams of one encoder (encode_params /

@@ -1313,7 +1313,12 @@ struct EncJobs
     bool rd = false;                        // the R family (dcs_encode_rd.hip.h): every set 0x9400, every job searched to a budget
     const uint32_t *budgetBytes = nullptr;  // rd, rd93: per job, the most bytes its stream may have (null: the sets' targetBitRate)
     bool rd93 = false;                      // the S family (dcs_encode93_rd.hip.h): every set OS93 Type 0, every job searched to a budget
+    const struct EncFit *fit = nullptr;     // rd, rd93: the jobs share one budget (dcs_encode_rd_fit.hip.h); budgetBytes is then null
 };
+
+// what dcs_encode_rd_fit and dcs_encode93_rd_fit ask of the driver: all jobs' streams together at most totalBytes, job j at
+// most capBytes[j] (null: no caps); *info (or null) takes the allocator's record
+struct EncFit { uint64_t totalBytes; const uint32_t *capBytes; DcsEncodeRdFitInfo *info; };
 
 // after the sizes are known: the host memory that takes the `total` bytes (stream i at outOffsets[i]), or null for DCS_ERR_CAPACITY
 using EncPlace = std::function<uint8_t *(const uint64_t *outOffsets, uint64_t total)>;
@@ -1376,6 +1381,10 @@ struct SweepDecodeGuard
 //   runGroup       per group: the header half of E2, the families' band stages (O or E on the jobs whose set has a layout
 //                  of theirs, A2 on the Type-1 jobs) and the sizes, and a wait, after which win, keep and size of its jobs
 //                  are on the host.  After the first group's wait, checkInput: planFlag, then bad[]
+//   fitAllot       (a fit call only, dcs_encode_rd_fit.hip.h) once every group has run and left its jobs' candidates in the call's
+//                  curve table: the allocator over all jobs; the allotments become the jobs' budgets and sizes.  Each group
+//                  then chooses again before it is packed: fitRechoose where it is still resident (a call of one group runs
+//                  its trellises once), runGroup where it is not; fitReport checks the sizes and writes info and infoRd
 //   placeOutput    once every size is known: outOffsets, info, results, and the memory the bytes go to (the capacity check)
 //   packGroup      per group again (one that is no longer resident is first computed again by runGroup): layout, header,
 //                  pack (for the Type-1 jobs A3, A4, their head and A5) and swap into the group's blob on the device; then
@@ -1433,6 +1442,15 @@ private:
     DcsStatus rd93RunGroup(uint32_t j0, uint32_t n, uint32_t JF);
     DcsStatus rd93PackGroup(uint32_t n, uint32_t JF);
     void budgetsRd();
+    void sizesRd(uint32_t j0, uint32_t n);
+    void writeInfo(uint32_t j);
+    // a fit call's own steps (defined behind dcs_encode_rd_fit.hip.h)
+    DcsStatus fitAllocCall();
+    DcsStatus fitCurves(uint32_t j0, uint32_t n);
+    DcsStatus fitAllot();
+    DcsStatus fitRechoose(uint32_t g);
+    DcsStatus fitReport(uint32_t g);
+    void fitRecord();
     std::string name(uint32_t i) const { return "stream " + std::to_string(in.label ? in.label[i] : i); }
 
     // ---- fixed by the arguments
@@ -1462,6 +1480,9 @@ private:
     std::vector<EncRdChoice> choiceRd;
     // the S family: E_b per set (floorRd, one value a set: every band has sixteen samples), budgetRd, and what S5 chose
     std::vector<Enc93RdChoice> choiceRd93;
+    // a fit call: the allotments in bytes (empty until fitAllot has run) and the allocator's record
+    std::vector<uint32_t> allot;
+    DcsEncodeRdFitInfo fitRec{};
 
     // ---- device buffers of the call: valid from allocCall to the end
     struct CallBufs
@@ -1495,6 +1516,13 @@ private:
             Enc93RdRec *dRecs = nullptr;        // [stream-frame][band][scale code]
             unsigned long long *dD0 = nullptr, *dFloor = nullptr;   // [stream][band], [set]
         } r93;
+        struct                                  // a fit call only (F1-F4)
+        {
+            unsigned long long *dCurveSize = nullptr, *dCurveD = nullptr;   // [job][kFitMaxPoints]: every job's candidates
+            unsigned long long *dOff = nullptr; // [job + 1]
+            uint32_t *dCap = nullptr, *dAllot = nullptr;
+            DcsEncodeRdFitInfo *dFit = nullptr;
+        } fit;
     } cb;
     CacheArena call;
 
@@ -1667,6 +1695,8 @@ DcsStatus EncRun::allocCall()
         ENCTRY(rdAllocCall());
     if (jobs.rd93)
         ENCTRY(rd93AllocCall());
+    if (jobs.fit != nullptr)
+        ENCTRY(fitAllocCall());
     return DCS_OK;
 }
 
@@ -1806,6 +1836,8 @@ DcsStatus EncRun::runGroup(uint32_t g)
         ENCTRY(rdRunGroup(j0, n));
     if (jobs.rd93)
         ENCTRY(rd93RunGroup(j0, n, JF));
+    if (jobs.fit != nullptr && allot.empty())
+        ENCTRY(fitCurves(j0, n));
     ENCCHK(hipGetLastError());
     if (anyV != 0)
     {
@@ -1824,6 +1856,15 @@ DcsStatus EncRun::runGroup(uint32_t g)
             keep[j0 + k] = choiceA[j0 + k].numBands;
             size[j0 + k] = 3 + (choiceA[j0 + k].frameBits + 7) / 8;
         }
+    sizesRd(j0, n);
+    resident = g;
+    residentFrames = JF;
+    return DCS_OK;
+}
+
+// win, keep and size of n jobs from job j0 from what the R or the S family chose for them
+void EncRun::sizesRd(uint32_t j0, uint32_t n)
+{
     // a job of the R family: the candidate of CloseStream's list it chose, its header's band count, 18 bytes and the frames' bits
     for (uint32_t k = 0 ; jobs.rd && k < n ; ++k)
     {
@@ -1838,9 +1879,6 @@ DcsStatus EncRun::runGroup(uint32_t g)
         keep[j0 + k] = choiceRd93[j0 + k].numBands;
         size[j0 + k] = 18 + (choiceRd93[j0 + k].frameBits + 7) / 8;
     }
-    resident = g;
-    residentFrames = JF;
-    return DCS_OK;
 }
 
 // Upload, E1 and encStreamKernel; bad[] is on its way to the host, there after the first group's wait; then A1 for the
@@ -1911,42 +1949,50 @@ DcsStatus EncRun::checkInput()
     return DCS_OK;
 }
 
-// every size is known: outOffsets, info and results, then dst (null with DCS_OK: a sweep that asked for sizes only)
+// info, info93a, infoRd and the sweep's result of job j, from what its group's run left on the host
+void EncRun::writeInfo(uint32_t j)
+{
+    const DcsEncodeInfo e{ kCandType[win[j]], kCandSub[win[j]], static_cast<int32_t>(hs[jobs.list[j].stream].nFrames),
+                           static_cast<int32_t>(size[j]), keep[j] };
+    if (to.info != nullptr)
+        to.info[j] = e;
+    if (to.info93a != nullptr)
+    {
+        const DcsEncodeParams &p = jobs.sets[jobs.list[j].paramSet];
+        const Enc93aChoice &c = choiceA[j];
+        const uint64_t budget = static_cast<uint64_t>(p.targetBitRate) * static_cast<uint64_t>(e.nFrames) * 240ull / 31250ull;
+        to.info93a[j] = setQ[jobs.list[j].paramSet] == kA93None ? DcsEncode93aInfo{}
+                        : DcsEncode93aInfo{ c.selector, c.ladderIndex, c.numBands, 0, c.frameBits, budget, c.sumD };
+    }
+    if (to.infoRd != nullptr && jobs.rd93)
+    {
+        const Enc93RdChoice &c = choiceRd93[j];
+        to.infoRd[j] = DcsEncodeRdInfo{ 0, 0, c.ladderIndex, c.numBands, c.frameBits,
+                                        static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
+    }
+    else if (to.infoRd != nullptr)
+    {
+        const EncRdChoice &c = choiceRd[j];
+        to.infoRd[j] = DcsEncodeRdInfo{ kCandType[c.variant], kCandSub[c.variant], c.ladderIndex, c.numBands, c.frameBits,
+                                        static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
+    }
+    if (sweep.results != nullptr)
+    {
+        memset(&sweep.results[j], 0, sizeof(DcsSweepResult));       // (its padding too: records compare as bytes)
+        sweep.results[j].enc = e;
+    }
+}
+
+// every size is known: outOffsets, info and results, then dst (null with DCS_OK: a sweep that asked for sizes only).  (A fit
+// call knows the sizes, its allotments, before its groups have chosen: fitReport writes their info.)
 DcsStatus EncRun::placeOutput()
 {
     uint64_t *outOffsets = to.outOffsets;
     for (uint32_t j = 0 ; j < jobs.n ; ++j)
     {
         outOffsets[j + 1] = outOffsets[j] + size[j];
-        const DcsEncodeInfo e{ kCandType[win[j]], kCandSub[win[j]], static_cast<int32_t>(hs[jobs.list[j].stream].nFrames),
-                               static_cast<int32_t>(size[j]), keep[j] };
-        if (to.info != nullptr)
-            to.info[j] = e;
-        if (to.info93a != nullptr)
-        {
-            const DcsEncodeParams &p = jobs.sets[jobs.list[j].paramSet];
-            const Enc93aChoice &c = choiceA[j];
-            const uint64_t budget = static_cast<uint64_t>(p.targetBitRate) * static_cast<uint64_t>(e.nFrames) * 240ull / 31250ull;
-            to.info93a[j] = setQ[jobs.list[j].paramSet] == kA93None ? DcsEncode93aInfo{}
-                            : DcsEncode93aInfo{ c.selector, c.ladderIndex, c.numBands, 0, c.frameBits, budget, c.sumD };
-        }
-        if (to.infoRd != nullptr && jobs.rd93)
-        {
-            const Enc93RdChoice &c = choiceRd93[j];
-            to.infoRd[j] = DcsEncodeRdInfo{ 0, 0, c.ladderIndex, c.numBands, c.frameBits,
-                                            static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
-        }
-        else if (to.infoRd != nullptr)
-        {
-            const EncRdChoice &c = choiceRd[j];
-            to.infoRd[j] = DcsEncodeRdInfo{ kCandType[c.variant], kCandSub[c.variant], c.ladderIndex, c.numBands, c.frameBits,
-                                            static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
-        }
-        if (sweep.results != nullptr)
-        {
-            memset(&sweep.results[j], 0, sizeof(DcsSweepResult));       // (its padding too: records compare as bytes)
-            sweep.results[j].enc = e;
-        }
+        if (jobs.fit == nullptr)
+            writeInfo(j);
     }
     if (sweep.sizesOnly)
         return DCS_OK;
@@ -2174,16 +2220,25 @@ DcsStatus EncRun::run()
         if (g == 0)
             ENCTRY(checkInput());
     }
+    if (jobs.fit != nullptr)
+        ENCTRY(fitAllot());
     ENCTRY(placeOutput());
     if (dst == nullptr && !sweep.measure)
         return DCS_OK;
     for (uint32_t g = 0 ; g < nGroups ; ++g)
     {
-        if (resident != g)
+        if (jobs.fit != nullptr)
+        {
+            ENCTRY(nGroups == 1 ? fitRechoose(g) : runGroup(g));
+            ENCTRY(fitReport(g));
+        }
+        else if (resident != g)
             ENCTRY(runGroup(g));
         ENCTRY(packGroup(g));
         ENCTRY(sweep.measure ? measureGroup(g) : deliverGroup(g));
     }
+    if (jobs.fit != nullptr)
+        fitRecord();
     return DCS_OK;
 }
 
@@ -2805,4 +2860,230 @@ extern "C" DcsStatus dcs_encode93_rd_streams(DcsCtx *ctx, const float *pcm, cons
     EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
     to.infoRd = infoRd;
     return EncRun(ctx, in, js, to, EncSweep()).run();
+}
+
+// ------------------------------------------------------- a set of streams to one byte budget: kernels and driver (dcs_encode_rd_fit.hip.h)
+// (behind every other kernel of the unit once more)
+
+#include "dcs_encode_rd_fit.hip.h"
+
+namespace {
+
+DcsStatus EncRun::fitAllocCall()
+{
+    ENCCHK(call.alloc(&cb.fit.dCurveSize, size_t(kFitMaxPoints) * jobs.n));
+    ENCCHK(call.alloc(&cb.fit.dCurveD, size_t(kFitMaxPoints) * jobs.n));
+    ENCCHK(call.alloc(&cb.fit.dOff, size_t(jobs.n) + 1));
+    if (jobs.fit->capBytes != nullptr)
+        ENCCHK(call.alloc(&cb.fit.dCap, jobs.n));
+    ENCCHK(call.alloc(&cb.fit.dAllot, jobs.n));
+    ENCCHK(call.alloc(&cb.fit.dFit, 1));
+    return DCS_OK;
+}
+
+// F1 behind R2 or S4 of the resident group (n jobs from job j0): its jobs' candidates into the call's curve table
+DcsStatus EncRun::fitCurves(uint32_t j0, uint32_t n)
+{
+    unsigned long long *dSize = cb.fit.dCurveSize + size_t(kFitMaxPoints) * j0, *dD = cb.fit.dCurveD + size_t(kFitMaxPoints) * j0;
+    if (jobs.rd)
+        hipLaunchKernelGGL(encRdCurveKernel, dim3(n), dim3(256), 0, st, gb.rd.dTot, cb.rd.dD0, gb.dJobs, cb.dSets, dSize, dD);
+    else
+        hipLaunchKernelGGL(enc93RdCurveKernel, dim3((n * kFitMaxPoints + 63) / 64), dim3(64), 0, st, gb.r93.dTot, gb.r93.dHead, cb.r93.dD0,
+                           gb.dJobs, n, dSize, dD);
+    return DCS_OK;
+}
+
+// F2 to F4 over all jobs, and a wait: the allotments and the record are on the host after it, the curves never.  A job's
+// budget is its allotment, or its cap where even its smallest candidate is beyond that (a pinned job: fits = 0).
+DcsStatus EncRun::fitAllot()
+{
+    const EncFit &fit = *jobs.fit;
+    std::vector<unsigned long long> off(size_t(jobs.n) + 1);
+    for (uint32_t j = 0 ; j <= jobs.n ; ++j)
+        off[j] = static_cast<unsigned long long>(kFitMaxPoints) * j;
+    ENCCHK(hipMemcpyAsync(cb.fit.dOff, off.data(), sizeof(unsigned long long) * off.size(), hipMemcpyHostToDevice, st));
+    if (fit.capBytes != nullptr)
+        ENCCHK(hipMemcpyAsync(cb.fit.dCap, fit.capBytes, sizeof(uint32_t) * jobs.n, hipMemcpyHostToDevice, st));
+    ENCTRY(fitAllotDevice(ctx, call, cb.fit.dCurveSize, cb.fit.dCurveD, cb.fit.dOff, jobs.n, size_t(kFitMaxPoints) * jobs.n, fit.totalBytes,
+                          cb.fit.dCap, cb.fit.dAllot, cb.fit.dFit));
+    allot.resize(jobs.n);
+    ENCCHK(hipMemcpyAsync(allot.data(), cb.fit.dAllot, sizeof(uint32_t) * jobs.n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipMemcpyAsync(&fitRec, cb.fit.dFit, sizeof(fitRec), hipMemcpyDeviceToHost, st));
+    ENCCHK(hipStreamSynchronize(st));
+    for (uint32_t j = 0 ; j < jobs.n ; ++j)
+    {
+        const uint32_t b = fit.capBytes != nullptr ? std::min(allot[j], fit.capBytes[j]) : allot[j];
+        budgetRd[j] = b >= 18 ? (static_cast<long long>(b) - 18) * 8 : -1;
+        size[j] = allot[j];
+    }
+    if (fit.info != nullptr)
+        *fit.info = fitRec;
+    return DCS_OK;
+}
+
+// R3 or S5 again for group g, still resident, with the allotments as budgets; the choices are on the host after the wait
+DcsStatus EncRun::fitRechoose(uint32_t g)
+{
+    const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
+    if (jobs.rd)
+    {
+        ENCCHK(hipMemcpyAsync(gb.rd.dBudget, budgetRd.data() + j0, sizeof(long long) * n, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(encRdChooseKernel, dim3(n), dim3(256), 0, st, gb.rd.dTot, cb.rd.dD0, gb.dJobs, cb.dSets, gb.rd.dBudget, gb.rd.dChoice);
+        ENCCHK(hipMemcpyAsync(choiceRd.data() + j0, gb.rd.dChoice, sizeof(EncRdChoice) * n, hipMemcpyDeviceToHost, st));
+    }
+    else
+    {
+        ENCCHK(hipMemcpyAsync(gb.r93.dBudget, budgetRd.data() + j0, sizeof(long long) * n, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(enc93RdChooseKernel, dim3((n + 63) / 64), dim3(64), 0, st, gb.r93.dTot, gb.r93.dHead, cb.r93.dD0, gb.dJobs,
+                           gb.r93.dBudget, n, gb.r93.dChoice);
+        ENCCHK(hipMemcpyAsync(choiceRd93.data() + j0, gb.r93.dChoice, sizeof(Enc93RdChoice) * n, hipMemcpyDeviceToHost, st));
+    }
+    ENCCHK(hipGetLastError());
+    ENCCHK(hipStreamSynchronize(st));
+    sizesRd(j0, n);
+    return DCS_OK;
+}
+
+// group g has chosen with its allotments: every stream is as long as its allotment (a hull vertex is a candidate's size),
+// on which the output offsets already rest; then its jobs' info and infoRd
+DcsStatus EncRun::fitReport(uint32_t g)
+{
+    for (uint32_t j = groupFirst[g] ; j < groupFirst[g + 1] ; ++j)
+    {
+        if (size[j] != allot[j])
+        {
+            dcsCtxSetError(ctx, ("job " + std::to_string(j) + ": chose " + std::to_string(size[j]) + " bytes for an allotment of "
+                                 + std::to_string(allot[j])).c_str());
+            return DCS_ERR_HIP;
+        }
+        writeInfo(j);
+    }
+    return DCS_OK;
+}
+
+// the record once every stream is written: sqErr is the sum of what the streams' records say
+void EncRun::fitRecord()
+{
+    fitRec.sqErr = 0;
+    for (uint32_t j = 0 ; j < jobs.n ; ++j)
+        fitRec.sqErr += jobs.rd ? choiceRd[j].sumD : choiceRd93[j].sumD;
+    if (jobs.fit->info != nullptr)
+        *jobs.fit->info = fitRec;
+}
+
+// dcs_encode_rd_fit and dcs_encode93_rd_fit behind their parameter checks
+DcsStatus encodeRdFit(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, const DcsEncodeParams *params,
+                      bool os93, const EncFit &fit, const EncOutput &to)
+{
+    if (fit.info != nullptr)
+    {
+        *fit.info = DcsEncodeRdFitInfo{};
+        fit.info->totalBytes = fit.totalBytes;
+        fit.info->fits = 1;
+    }
+    EncInput in;
+    in.sampleOffsets = sampleOffsets;
+    in.nStreams = nStreams;
+    in.hostPcm = pcm;
+    std::vector<DcsSweepJob> list(nStreams);
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+        list[i] = DcsSweepJob{ i, 0 };
+    EncJobs js{ params, 1, list.data(), nStreams, os93 };
+    js.rd = !os93;
+    js.rd93 = os93;
+    js.fit = &fit;
+    return EncRun(ctx, in, js, to, EncSweep()).run();
+}
+
+}  // namespace
+
+extern "C" DcsStatus dcs_encode_rd_fit(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                       const DcsEncodeParams *params, uint64_t totalBytes, const uint32_t *capBytes, uint8_t *out,
+                                       uint64_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd,
+                                       DcsEncodeRdFitInfo *fit)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
+        return DCS_ERR_INVALID_ARG;
+    if (!paramsValidRd(params))
+    {
+        dcsCtxSetError(ctx, "dcs_encode_rd_fit: formatVersion 0x9400, streamFormatType 0, 1 or -1, streamFormatSubType 0, 3 or -1, "
+                            "targetBitRate 1..100 000 000 and finite parameters");
+        return DCS_ERR_INVALID_ARG;
+    }
+    EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
+    to.infoRd = infoRd;
+    return encodeRdFit(ctx, pcm, sampleOffsets, nStreams, params, false, EncFit{ totalBytes, capBytes, fit }, to);
+}
+
+extern "C" DcsStatus dcs_encode93_rd_fit(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                         const DcsEncodeParams *params, uint64_t totalBytes, const uint32_t *capBytes, uint8_t *out,
+                                         uint64_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd,
+                                         DcsEncodeRdFitInfo *fit)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
+        return DCS_ERR_INVALID_ARG;
+    if (!paramsValid93Rd(params))
+    {
+        dcsCtxSetError(ctx, "dcs_encode93_rd_fit: formatVersion 0x9301 or 0x9302, streamFormatType 0 or -1 (OS93 Type 0; Type 1 is "
+                            "not searched), targetBitRate 1..100 000 000 and finite parameters");
+        return DCS_ERR_INVALID_ARG;
+    }
+    EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
+    to.infoRd = infoRd;
+    return encodeRdFit(ctx, pcm, sampleOffsets, nStreams, params, true, EncFit{ totalBytes, capBytes, fit }, to);
+}
+
+extern "C" DcsStatus dcs_encode_rd_allot(DcsCtx *ctx, const uint64_t *sizeBytes, const uint64_t *sqErr, const uint64_t *curveOffsets,
+                                         uint32_t nJobs, uint64_t totalBytes, const uint32_t *capBytes, uint32_t *allotOut,
+                                         DcsEncodeRdFitInfo *fit)
+{
+    if (fit == nullptr || curveOffsets == nullptr || (nJobs != 0 && (sizeBytes == nullptr || sqErr == nullptr || allotOut == nullptr)))
+        return DCS_ERR_INVALID_ARG;
+    const char *why = nullptr;
+    for (uint32_t j = 0 ; j < nJobs && why == nullptr ; ++j)
+        if (curveOffsets[j + 1] <= curveOffsets[j] || curveOffsets[j + 1] - curveOffsets[j] > kFitMaxPoints)
+            why = "dcs_encode_rd_allot: a job has 1 to 168 candidates";
+    const uint64_t first = curveOffsets[0], N = why == nullptr ? curveOffsets[nJobs] - first : 0;
+    for (uint64_t i = 0 ; i < N && why == nullptr ; ++i)
+        if (sizeBytes[first + i] > 0xFFFFFFFFull || sqErr[first + i] >= kFitMaxD)
+            why = "dcs_encode_rd_allot: sizes are below 2^32 and errors below 2^62";
+    if (why != nullptr)
+    {
+        if (ctx != nullptr)
+            dcsCtxSetError(ctx, why);
+        return DCS_ERR_INVALID_ARG;
+    }
+    if (ctx == nullptr || nJobs == 0)
+    {
+        fitAllotHost(sizeBytes, sqErr, curveOffsets, nJobs, totalBytes, capBytes, allotOut, fit);
+        return DCS_OK;
+    }
+    ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
+    const hipStream_t st = dcsCtxStream(ctx);
+    CacheArena arena(ctx);
+    std::vector<unsigned long long> off(size_t(nJobs) + 1);
+    for (uint32_t j = 0 ; j <= nJobs ; ++j)
+        off[j] = curveOffsets[j] - first;
+    unsigned long long *dSize, *dD, *dOff;
+    uint32_t *dCap = nullptr, *dAllot;
+    DcsEncodeRdFitInfo *dFit;
+    ENCCHK(arena.alloc(&dSize, N));
+    ENCCHK(arena.alloc(&dD, N));
+    ENCCHK(arena.alloc(&dOff, off.size()));
+    if (capBytes != nullptr)
+        ENCCHK(arena.alloc(&dCap, nJobs));
+    ENCCHK(arena.alloc(&dAllot, nJobs));
+    ENCCHK(arena.alloc(&dFit, 1));
+    ENCCHK(hipMemcpyAsync(dSize, sizeBytes + first, sizeof(uint64_t) * N, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dD, sqErr + first, sizeof(uint64_t) * N, hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dOff, off.data(), sizeof(unsigned long long) * off.size(), hipMemcpyHostToDevice, st));
+    if (capBytes != nullptr)
+        ENCCHK(hipMemcpyAsync(dCap, capBytes, sizeof(uint32_t) * nJobs, hipMemcpyHostToDevice, st));
+    const DcsStatus s = fitAllotDevice(ctx, arena, dSize, dD, dOff, nJobs, static_cast<size_t>(N), totalBytes, dCap, dAllot, dFit);
+    if (s != DCS_OK)
+        return s;
+    ENCCHK(hipMemcpyAsync(allotOut, dAllot, sizeof(uint32_t) * nJobs, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipMemcpyAsync(fit, dFit, sizeof(*fit), hipMemcpyDeviceToHost, st));
+    ENCCHK(hipStreamSynchronize(st));
+    return DCS_OK;
 }

@@ -998,6 +998,45 @@ DcsStatus dcs_encode93_rd_streams(DcsCtx *ctx, const float *pcm, const uint64_t 
                                   const DcsEncodeParams *params, const uint32_t *budgetBytes, uint8_t *out, uint64_t outCap,
                                   uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd);
 
+/* Encoding a set of streams to ONE byte budget (INTEGRATION.md "Encoding a set to one budget"): the two
+ * encoders above, with the per-stream budgets computed instead of given.  Every stream's candidates, the (size, squared
+ * error) totals its search forms, make a curve; one allocator over all curves (lower convex hulls, their steps taken by
+ * falling error per byte, in exact integer arithmetic; tests/encrd_fit_ref.py restates it) gives stream j an allotment
+ * allot[j] with sum(allot) <= totalBytes, and stream j is then EXACTLY the stream dcs_encode_rd_streams (dcs_encode93_rd_streams)
+ * writes for budgetBytes[j] = allot[j], infoRd[j] that call's record; its length is allot[j].  capBytes (or NULL) bounds stream j by
+ * capBytes[j] as well.  A stream none of whose candidates keeps to its cap is pinned: its fewest-bits candidate is written,
+ * allot[j] is that stream's length, and its record is the per-stream call's for budgetBytes[j] = capBytes[j] (fits = 0).
+ * Size never refuses: if even the smallest candidates exceed totalBytes, every stream is written at its smallest and
+ * fit->fits is 0, with DCS_OK.  params->targetBitRate must be valid but is not read.  Input, parameter validation, capacity
+ * (DCS_ERR_CAPACITY with outOffsets and *fit written, and nothing else), ordering, errors and the bound functions are the
+ * per-stream calls'.  info, infoRd and fit may be NULL.  These entry points and DcsEncodeRdFitInfo are additions: nothing
+ * that existed changed its layout or behaviour, so DCS_ABI_VERSION stays 9. */
+typedef struct DcsEncodeRdFitInfo
+{
+    uint64_t totalBytes;               /* as given                                                                         */
+    uint64_t leastBytes;               /* the sum of every stream's smallest candidate (within its cap, where one is)      */
+    uint64_t usedBytes;                /* the sum of the allotments = the sum of the streams written                       */
+    uint64_t sqErr;                    /* the sum of the streams' DcsEncodeRdInfo.sqErr                                    */
+    uint32_t nSteps, stepsTaken;       /* hull steps of all streams; those the walk took                                   */
+    int32_t  fits;                     /* 0: leastBytes > totalBytes, every stream at its smallest                         */
+    int32_t  reserved;
+} DcsEncodeRdFitInfo;
+DcsStatus dcs_encode_rd_fit(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                            const DcsEncodeParams *params, uint64_t totalBytes, const uint32_t *capBytes, uint8_t *out,
+                            uint64_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd,
+                            DcsEncodeRdFitInfo *fit);
+DcsStatus dcs_encode93_rd_fit(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                              const DcsEncodeParams *params, uint64_t totalBytes, const uint32_t *capBytes, uint8_t *out,
+                              uint64_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd,
+                              DcsEncodeRdFitInfo *fit);
+/* The allocator alone, on curves the caller supplies: job j has the candidates [curveOffsets[j], curveOffsets[j + 1]) of
+ * sizeBytes (each < 2^32) and sqErr (each < 2^62), 1 to 168 of them; allotOut[j] is its allotment, and fit->sqErr the sum of
+ * the errors at the allotments (modulo 2^64).  A pinned job keeps the first of its smallest candidates.  ctx NULL: computed on the host
+ * (no device is touched); otherwise on the device of ctx, with the same result.  Anything else is DCS_ERR_INVALID_ARG. */
+DcsStatus dcs_encode_rd_allot(DcsCtx *ctx, const uint64_t *sizeBytes, const uint64_t *sqErr, const uint64_t *curveOffsets,
+                              uint32_t nJobs, uint64_t totalBytes, const uint32_t *capBytes, uint32_t *allotOut,
+                              DcsEncodeRdFitInfo *fit);
+
 /* ------------------------------------------------------------------------------------------------
  * Transcoding: DCS streams of any family into the family of `target` (formatVersion 0x9400: the 1994+ encoder; 0x9301 /
  * 0x9302: the OS93 encoder; checked as those encoders check it), the reference's DCSEncoder::EncodeDCSFile
