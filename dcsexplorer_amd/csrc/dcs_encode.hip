@@ -1275,1004 +1275,15 @@ __global__ __launch_bounds__(256) void encMeasureKernel(const float *__restrict_
 
 // ------------------------------------------- OS93a Type 1, the pair-table layout: tables and kernels (dcs_encode93a.hip.h)
 // (here: behind every kernel above that is no template, so that those keep their order in the code object, and in front of
-// EncRun, which launches these; see the note above EncRun::analyse for the templates)
+// the driver, which launches these)
 
 #include "dcs_encode93a.hip.h"
 #include "dcs_encode_rd.h"
 #include "dcs_encode93_rd.h"
 
-namespace {
+// ------------------------------------------------- the host driver: families O, E and A, and EncRun (dcs_encode_run.hip.h)
 
-// Where the driver reads its samples: the caller's float PCM on the host (dcs_encode_streams, dcs_encode93_streams), a
-// decode batch's int16 PCM and error words, resident on the device (dcs_transcode_streams, dcs_transcode.hip.h), or the
-// resampler's float output, resident on the device (dcs_encode_streams_at, dcs_resample.hip.h)
-struct EncInput
-{
-    const uint64_t *sampleOffsets = nullptr;    // stream i = samples [sampleOffsets[i], sampleOffsets[i + 1]) of the one that is set:
-    uint32_t nStreams = 0;
-    const float *hostPcm = nullptr;
-    const float *devFloat = nullptr;
-    const int16_t *devPcm = nullptr;        // sampleOffsets[i] a multiple of 240 ...
-    const uint32_t *devErr = nullptr;       // ... and its frames' error words at sampleOffsets[i] / 240
-    const uint32_t *label = nullptr;        // the number a message gives stream i (null: i)
-    const float *bound = nullptr;           // the largest |x| stream i may hold (null: 1; dcs_encode_files, INTEGRATION rule 12)
-    const volatile uint32_t *planFlag = nullptr;    // a word the device writes before the PCM is final: not 0 = the PCM is not to be used
-    bool unusable = false;                  // (out) planFlag was set: DCS_ERR_BAD_STREAM, and nothing was written
-};
-
-// the jobs of a call: job j = (stream list[j].stream, set list[j].paramSet), every set of the one encoder `os93` names.
-// A set that asks for (0x9301, Type 1) puts its jobs into the A family (dcs_encode93a.hip.h); only dcs_encode93a_streams
-// and dcs_encode93a_sweep let one in.
-struct EncJobs
-{
-    const DcsEncodeParams *sets;
-    uint32_t nSets;
-    const DcsSweepJob *list;
-    uint32_t n;
-    bool os93;
-    bool rd = false;                        // the R family (dcs_encode_rd.hip.h): every set 0x9400, every job searched to a budget
-    const uint32_t *budgetBytes = nullptr;  // rd, rd93: per job, the most bytes its stream may have (null: the sets' targetBitRate)
-    bool rd93 = false;                      // the S family (dcs_encode93_rd.hip.h): every set OS93 Type 0, every job searched to a budget
-    const struct EncFit *fit = nullptr;     // rd, rd93: the jobs share one budget (dcs_encode_rd_fit.hip.h); budgetBytes is then null
-};
-
-// what dcs_encode_rd_fit and dcs_encode93_rd_fit ask of the driver: all jobs' streams together at most totalBytes, job j at
-// most capBytes[j] (null: no caps); *info (or null) takes the allocator's record
-struct EncFit { uint64_t totalBytes; const uint32_t *capBytes; DcsEncodeRdFitInfo *info; };
-
-// after the sizes are known: the host memory that takes the `total` bytes (stream i at outOffsets[i]), or null for DCS_ERR_CAPACITY
-using EncPlace = std::function<uint8_t *(const uint64_t *outOffsets, uint64_t total)>;
-
-// where a call's streams and what is known of them go
-struct EncOutput
-{
-    uint8_t *out = nullptr;                 // the caller's buffer of outCap bytes, where `place` is not given
-    size_t outCap = 0;
-    uint64_t *outOffsets = nullptr;         // nJobs + 1
-    DcsEncodeInfo *info = nullptr;          // nJobs, or null
-    const EncPlace *place = nullptr;
-    DcsEncode93aInfo *info93a = nullptr;    // nJobs, or null: the Type-1 candidate of a job of the A family, zeros of any other
-    DcsEncodeRdInfo *infoRd = nullptr;      // nJobs, or null: what the R family's search chose
-};
-
-// what dcs_encode_sweep asks of the driver beyond a list of jobs
-struct EncSweep
-{
-    DcsSweepResult *results = nullptr;
-    bool measure = false;
-    bool sizesOnly = false;                 // out == NULL && outCap == 0: nothing is packed for the host
-};
-
-// most job-frames a group may hold (0: what the memory takes); dcs_encode_sweep_group_frames
-std::atomic<uint64_t> gGroupFrames{ 0 };
-
-const int kCandType[4] = { 0, 0, 1, 1 }, kCandSub[4] = { 0, 3, 0, 3 };     // candidates in CloseStream's order (0,0), (0,3), (1,0), (1,3)
-
-#define HIPTRY(call)                                                                                 \
-    do {                                                                                             \
-        const hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                        \
-            return e_;                                                                               \
-    } while (0)
-#define ENCTRY(call)                                                                                 \
-    do {                                                                                             \
-        const DcsStatus s_ = (call);                                                                 \
-        if (s_ != DCS_OK)                                                                            \
-            return s_;                                                                               \
-    } while (0)
-
-// a decode queued by dcsSweepDecodeStart, released (which waits for the stream) on every way out of its scope
-struct SweepDecodeGuard
-{
-    DcsSweepDecode *d = nullptr;
-    ~SweepDecodeGuard() { dcsSweepDecodeRelease(d); }
-};
-
-// The one host driver behind every encode, as an object that lives for one call.  A job is (stream, parameter set);
-// dcs_encode_streams and its kin are one job per stream with one set.  run() strings the steps together, each a member
-// function below, in this order:
-//   checkStreams   the streams' lengths, before anything is written; then the empty call's zeros, before any HIP call
-//   buildSets      the parameter sets as the kernels read them, and which layouts any of them asks for
-//   allocCall      the buffers that live as long as the call (CallBufs)
-//   allocGroups    the jobs in groups, runs of the job list whose per-job-frame buffers (GroupBufs, sized for the largest
-//                  group) fit the memory: makeGroups + allocGroup, one group unless a cap is set or an allocation fails
-//   analyse        upload, E1 and the sums of E2, once per stream; where the call has jobs of the A family, A1: the search
-//                  once per stream-frame and its walk once per distinct maximumQuantizationError (buildSets: setQ, rowOf)
-//   runGroup       per group: the header half of E2, the families' band stages (O or E on the jobs whose set has a layout
-//                  of theirs, A2 on the Type-1 jobs) and the sizes, and a wait, after which win, keep and size of its jobs
-//                  are on the host.  After the first group's wait, checkInput: planFlag, then bad[]
-//   fitAllot       (a fit call only, dcs_encode_rd_fit.hip.h) once every group has run and left its jobs' candidates in the call's
-//                  curve table: the allocator over all jobs; the allotments become the jobs' budgets and sizes.  Each group
-//                  then chooses again before it is packed: fitRechoose where it is still resident (a call of one group runs
-//                  its trellises once), runGroup where it is not; fitReport checks the sizes and writes info and infoRd
-//   placeOutput    once every size is known: outOffsets, info, results, and the memory the bytes go to (the capacity check)
-//   packGroup      per group again (one that is no longer resident is first computed again by runGroup): layout, header,
-//                  pack (for the Type-1 jobs A3, A4, their head and A5) and swap into the group's blob on the device; then
-//                  one of
-//   deliverGroup   the blob to its place in the output, or with sweep.measure
-//   measureGroup   the group's streams decoded where the pack step left them and compared with their sources (M1), the
-//                  blob staged on the host when the decode or the output needs it there (stageBlob)
-// Three lifetimes of device memory: `call`, `group` (emptied when an allocation attempt fails) and `blob` (taken anew for
-// every group).  The destructor waits for the stream once and gives back blob, group, call, in that order.
-class EncRun
-{
-public:
-    EncRun(DcsCtx *ctx, EncInput &in, const EncJobs &jobs, const EncOutput &to, const EncSweep &sweep)
-        : ctx(ctx), st(dcsCtxStream(ctx)), in(in), jobs(jobs), to(to), sweep(sweep), dev(in.devPcm != nullptr),
-          devF(in.devFloat != nullptr), call(ctx), group(ctx), blob(ctx) {}
-    ~EncRun()
-    {
-        if (!call.empty())
-            call.wait();
-        blob.clear();
-        group.clear();
-        call.clear();
-    }
-    DcsStatus run();
-
-private:
-    DcsStatus checkStreams();
-    void buildSets();
-    DcsStatus allocCall();
-    void makeGroups(uint64_t limit);
-    hipError_t allocGroup();
-    DcsStatus allocGroups();
-    DcsStatus analyse();
-    DcsStatus runGroup(uint32_t g);
-    DcsStatus checkInput();
-    DcsStatus placeOutput();
-    DcsStatus layoutGroup(uint32_t g, size_t *nWords);
-    DcsStatus packGroup(uint32_t g);
-    DcsStatus deliverGroup(uint32_t g);
-    DcsStatus stageBlob();
-    void selectDecodes(uint32_t n);
-    DcsStatus decodeAndCompare(uint32_t n, bool onHost, bool *unusable);
-    DcsStatus reportGroup(uint32_t g);
-    DcsStatus measureGroup(uint32_t g);
-    // the R family's share of allocCall, allocGroup, analyse, runGroup and packGroup (defined behind dcs_encode_rd.hip.h)
-    DcsStatus rdAllocCall();
-    hipError_t rdAllocGroup();
-    DcsStatus rdAnalyse();
-    DcsStatus rdRunGroup(uint32_t j0, uint32_t n);
-    DcsStatus rdPackGroup(uint32_t n, uint32_t JF);
-    // the S family's share of the same steps (defined behind dcs_encode93_rd.hip.h)
-    DcsStatus rd93AllocCall();
-    hipError_t rd93AllocGroup();
-    DcsStatus rd93Analyse();
-    DcsStatus rd93RunGroup(uint32_t j0, uint32_t n, uint32_t JF);
-    DcsStatus rd93PackGroup(uint32_t n, uint32_t JF);
-    void budgetsRd();
-    void sizesRd(uint32_t j0, uint32_t n);
-    void writeInfo(uint32_t j);
-    // a fit call's own steps (defined behind dcs_encode_rd_fit.hip.h)
-    DcsStatus fitAllocCall();
-    DcsStatus fitCurves(uint32_t j0, uint32_t n);
-    DcsStatus fitAllot();
-    DcsStatus fitRechoose(uint32_t g);
-    DcsStatus fitReport(uint32_t g);
-    void fitRecord();
-    std::string name(uint32_t i) const { return "stream " + std::to_string(in.label ? in.label[i] : i); }
-
-    // ---- fixed by the arguments
-    DcsCtx *const ctx;
-    const hipStream_t st;
-    EncInput &in;
-    const EncJobs jobs;
-    const EncOutput to;
-    const EncSweep sweep;
-    const bool dev, devF;                       // the input is a decode batch's int16 PCM / float PCM on the device
-    std::vector<EncStream> hs;                  // (checkStreams)
-    std::vector<uint32_t> frameStream;
-    uint32_t F = 0;                             // frames of all streams
-    std::vector<EncSet> hsets;                  // (buildSets)
-    uint32_t anyV = 0;                          // the layouts any set asks for: bit 0 Type 0, bit 1 (1, 0), bit 2 (1, 3);
-                                                // 0: every job is of the A family, and no O or E stage is launched
-    uint64_t allFrames = 0, largest = 0;        // job-frames of all jobs, of the largest job
-    // the A family (OS93a Type 1): the distinct maximumQuantizationError values of its sets, each set's index among them
-    // (kA93None: a set of the O family), and per (q, stream) that a job names its row of A1's totals (kA93None: none does)
-    std::vector<float> qs;
-    std::vector<uint32_t> setQ, rowOf;
-    uint32_t nRows = 0;
-    std::vector<unsigned long long> floorE;     // [q][18] (analyse; the source of an asynchronous upload)
-    // the R family: E_b per set, and per job its budget in frame bits (-1: nothing fits) and what R3 chose
-    std::vector<unsigned long long> floorRd;    // [set][16]
-    std::vector<long long> budgetRd;
-    std::vector<EncRdChoice> choiceRd;
-    // the S family: E_b per set (floorRd, one value a set: every band has sixteen samples), budgetRd, and what S5 chose
-    std::vector<Enc93RdChoice> choiceRd93;
-    // a fit call: the allotments in bytes (empty until fitAllot has run) and the allocator's record
-    std::vector<uint32_t> allot;
-    DcsEncodeRdFitInfo fitRec{};
-
-    // ---- device buffers of the call: valid from allocCall to the end
-    struct CallBufs
-    {
-        EncTabs *dT;
-        float *dPcm = nullptr;                  // the host's PCM uploaded (null where the input is on the device)
-        EncStream *dStr;
-        EncSet *dSets;
-        uint32_t *dFS;                          // frame -> stream
-        float *dSpec, *dPw, *dLo, *dHi;         // E1's output per frame
-        uint32_t *dBad;                         // per stream: a sample E1 refused
-        float *dSums;                           // E2's sums per stream
-        struct                                  // the A family only (A1)
-        {
-            Enc93aTabs *dA = nullptr;
-            unsigned long long *dFloorE = nullptr;      // [q][18]
-            uint32_t *dSetQ = nullptr, *dRowOf = nullptr;
-            Enc93aTot *dTot = nullptr;          // [row][candidate]
-        } a93;
-        struct                                  // the R family only (R1)
-        {
-            EncRdTabs *dR = nullptr;
-            unsigned long long *dItems = nullptr;       // [stream-frame][band][width][scale code]
-            uint32_t *dPeak = nullptr;          // [stream][band]
-            unsigned long long *dD0 = nullptr, *dFloor = nullptr;   // [stream][band], [set][band]
-        } rd;
-        struct                                  // the S family only (S1)
-        {
-            EncRdTabs *dR = nullptr;
-            unsigned long long *dItems = nullptr;       // [stream-frame][band][scale code][option]
-            Enc93RdRec *dRecs = nullptr;        // [stream-frame][band][scale code]
-            unsigned long long *dD0 = nullptr, *dFloor = nullptr;   // [stream][band], [set]
-        } r93;
-        struct                                  // a fit call only (F1-F4)
-        {
-            unsigned long long *dCurveSize = nullptr, *dCurveD = nullptr;   // [job][kFitMaxPoints]: every job's candidates
-            unsigned long long *dOff = nullptr; // [job + 1]
-            uint32_t *dCap = nullptr, *dAllot = nullptr;
-            DcsEncodeRdFitInfo *dFit = nullptr;
-        } fit;
-    } cb;
-    CacheArena call;
-
-    // ---- device buffers of a group, sized for the largest one: valid from allocGroups to the end, their CONTENT that of
-    // the resident group (runGroup), dOutOff of the group packed last
-    struct GroupBufs
-    {
-        EncJob *dJobs;
-        uint32_t *dFJ;                          // job-frame -> job of the group
-        uint8_t *dHdr;
-        int32_t *dKeep, *dWin;
-        uint64_t *dSize, *dOutOff;
-        uint32_t *dFrameBits, *dFrameOff;
-        struct { Enc93Rec *dRec = nullptr; Enc93Band *dBand = nullptr; } o93;                       // OS93 only (O3-O5)
-        struct { uint8_t *dBest = nullptr, *dCodes = nullptr, *dHdrBits = nullptr; uint16_t *dSmpBits = nullptr; } v94;   // 1994+ only (E3-E5)
-        struct { Enc93aChoice *dChoice = nullptr; Enc93aRec *dRec = nullptr; } a93;                 // OS93a Type 1 only (A2-A5)
-        struct { EncMeasure *dMeas = nullptr; uint32_t *dFirstDec = nullptr; } m;                   // sweep.measure only (M1)
-        struct                                                                                      // the R family only (R2-R6)
-        {
-            EncRdTot *dTot = nullptr;           // [job][layout][band][window index][lambda]
-            EncRdChoice *dChoice = nullptr;
-            long long *dBudget = nullptr;
-            uint8_t *dSurv = nullptr, *dEnd = nullptr, *dCodes = nullptr;   // [job-frame][band][state], [job][band], [job-frame][band]
-            uint32_t *dBits = nullptr;          // [job-frame]
-        } rd;
-        struct                                                                                      // the S family only (S2-S8)
-        {
-            unsigned long long *dProxyJ = nullptr;      // [job][band][scale code][lambda]
-            uint32_t *dProxyB = nullptr;
-            Enc93RdHead *dHead = nullptr;       // [job][lambda]
-            Enc93RdTot *dTot = nullptr;         // [job][lambda]
-            Enc93RdChoice *dChoice = nullptr;
-            long long *dBudget = nullptr;
-            uint8_t *dCodes = nullptr;          // [job-frame][band]: the band's state
-            uint32_t *dBits = nullptr;          // [job-frame]
-        } r93;
-    } gb;
-    CacheArena group;
-
-    // ---- the groups, and what is known of every job once its group has run
-    std::vector<uint32_t> groupFirst;           // group g = jobs [groupFirst[g], groupFirst[g + 1])
-    uint64_t groupFrames = 0;                   // the largest group's job-frames ...
-    uint32_t groupJobs = 0;                     // ... and the most jobs in a group
-    uint32_t resident = ~0u, residentFrames = 0;    // the group whose rows the group buffers hold, and its job-frames
-    std::vector<EncJob> hj;                     // the resident group's jobs ...
-    std::vector<uint32_t> frameJob;             // ... and rows
-    std::vector<int32_t> win, keep;             // per job (runGroup)
-    std::vector<uint64_t> size;
-    std::vector<Enc93aChoice> choiceA;          // per job of the A family (runGroup)
-    std::vector<uint32_t> bad;                  // per stream, on the host after the first group's wait
-    uint8_t *dst = nullptr;                     // where the bytes go (placeOutput); null: nowhere
-
-    // ---- the packed group: valid from packGroup to the next one
-    CacheArena blob;
-    uint32_t *dW = nullptr;                     // the blob, big-endian after the swap
-    size_t blobLen = 0;
-    std::vector<uint64_t> offs;                 // job k of the group at blob byte offs[k]
-    std::vector<DcsSweepStream> ss;             // (sweep.measure) what the decoder is told of each
-    std::vector<uint8_t> stage;                 // the blob on the host ...
-    bool staged = false;                        // ... once stageBlob has run for this group
-
-    // ---- measureGroup's own
-    std::vector<uint32_t> sel, firstDec;        // the jobs of the group that are decoded; per job its first decoded frame
-    std::vector<DcsSweepStream> selS;
-    std::vector<uint64_t> selOff;
-    uint32_t mostFrames = 0;                    // of the selected jobs: the longest ...
-    uint64_t selFrames = 0;                     // ... and all of them
-    std::vector<EncMeasure> meas;
-};
-
-DcsStatus EncRun::checkStreams()
-{
-    hs.resize(in.nStreams);
-    for (uint32_t i = 0 ; i < in.nStreams ; ++i)
-    {
-        const uint64_t *so = in.sampleOffsets;
-        if (so[i + 1] <= so[i])
-        {
-            dcsCtxSetError(ctx, (name(i) + ": empty").c_str());
-            return DCS_ERR_INVALID_ARG;
-        }
-        const uint64_t n = so[i + 1] - so[i];
-        const uint64_t nF = (n + 239) / 240;
-        if (nF > 65535)
-        {
-            dcsCtxSetError(ctx, (name(i) + ": more than 65 535 frames").c_str());
-            return DCS_ERR_INVALID_ARG;
-        }
-        if (sweep.measure && nF == 65535)
-        {
-            dcsCtxSetError(ctx, (name(i) + ": 65 535 frames; measured with the extra frame its decode would need 65 536, more than the frame count holds").c_str());
-            return DCS_ERR_INVALID_ARG;
-        }
-        hs[i] = EncStream{ so[i] - so[0], static_cast<uint32_t>(n), F, static_cast<uint32_t>(nF),
-                           dev ? static_cast<uint32_t>(so[i] / 240) : 0u, in.bound != nullptr ? in.bound[i] : 1.0f };
-        frameStream.insert(frameStream.end(), static_cast<size_t>(nF), i);
-        F += static_cast<uint32_t>(nF);
-    }
-    return DCS_OK;
-}
-
-void EncRun::buildSets()
-{
-    hsets.resize(jobs.nSets);
-    for (uint32_t k = 0 ; k < jobs.nSets ; ++k)
-    {
-        const DcsEncodeParams &p = jobs.sets[k];
-        const int typ = p.streamFormatType, sub = jobs.os93 ? 0 : p.streamFormatSubType;
-        uint32_t cmask = 0;
-        for (int c = 0 ; c < 4 ; ++c)
-            if ((typ < 0 || typ == kCandType[c]) && (sub < 0 || sub == kCandSub[c])
-                && !(jobs.os93 && p.formatVersion == 0x9301 && kCandType[c] == 1))
-                cmask |= 1u << c;
-        const uint32_t vmask = ((cmask & 3) ? 1u : 0u) | ((cmask & 4) ? 2u : 0u) | ((cmask & 8) ? 4u : 0u);
-        hsets[k] = EncSet{ p.powerBandCutoff, p.minimumDynamicRange, p.maximumQuantizationError, p.targetBitRate, vmask, cmask };
-        if (!jobs.rd && !jobs.rd93)
-            anyV |= vmask;                      // (a set of the R or S family: no E or O stage touches its jobs)
-    }
-    // the A family's sets (cmask 0 above: no O stage touches their jobs) by their distinct maximumQuantizationError
-    setQ.assign(jobs.nSets, kA93None);
-    for (uint32_t k = 0 ; jobs.os93 && k < jobs.nSets ; ++k)
-        if (isType1Of93a(jobs.sets[k]))
-        {
-            const float q = jobs.sets[k].maximumQuantizationError;
-            const size_t at = std::find(qs.begin(), qs.end(), q) - qs.begin();
-            if (at == qs.size())
-                qs.push_back(q);
-            setQ[k] = static_cast<uint32_t>(at);
-        }
-    rowOf.assign(qs.size() * in.nStreams, kA93None);
-    for (uint32_t j = 0 ; j < jobs.n ; ++j)
-    {
-        const DcsSweepJob &job = jobs.list[j];
-        const uint64_t nF = hs[job.stream].nFrames;
-        allFrames += nF;
-        largest = nF > largest ? nF : largest;
-        if (setQ[job.paramSet] != kA93None)
-        {
-            uint32_t &row = rowOf[static_cast<size_t>(setQ[job.paramSet]) * in.nStreams + job.stream];
-            if (row == kA93None)
-                row = nRows++;
-        }
-    }
-}
-
-DcsStatus EncRun::allocCall()
-{
-    const uint32_t nStreams = in.nStreams;
-    ENCCHK(call.alloc(&cb.dT, 1));
-    if (!dev && !devF)
-        ENCCHK(call.alloc(&cb.dPcm, in.sampleOffsets[nStreams] - in.sampleOffsets[0]));
-    ENCCHK(call.alloc(&cb.dStr, nStreams));
-    ENCCHK(call.alloc(&cb.dSets, jobs.nSets));
-    ENCCHK(call.alloc(&cb.dFS, F));
-    ENCCHK(call.alloc(&cb.dSpec, size_t(256) * F));
-    ENCCHK(call.alloc(&cb.dPw, size_t(16) * F));
-    ENCCHK(call.alloc(&cb.dLo, size_t(16) * F));
-    ENCCHK(call.alloc(&cb.dHi, size_t(16) * F));
-    ENCCHK(call.alloc(&cb.dBad, nStreams));
-    ENCCHK(call.alloc(&cb.dSums, size_t(48) * nStreams));
-    if (!qs.empty())
-    {
-        ENCCHK(call.alloc(&cb.a93.dA, 1));
-        ENCCHK(call.alloc(&cb.a93.dFloorE, 18 * qs.size()));
-        ENCCHK(call.alloc(&cb.a93.dSetQ, jobs.nSets));
-        ENCCHK(call.alloc(&cb.a93.dRowOf, rowOf.size()));
-        ENCCHK(call.alloc(&cb.a93.dTot, size_t(kA93Cand) * nRows));
-    }
-    if (jobs.rd)
-        ENCTRY(rdAllocCall());
-    if (jobs.rd93)
-        ENCTRY(rd93AllocCall());
-    if (jobs.fit != nullptr)
-        ENCTRY(fitAllocCall());
-    return DCS_OK;
-}
-
-// the groups: runs of the job list of at most `limit` job-frames, a job never split
-void EncRun::makeGroups(uint64_t limit)
-{
-    groupFirst.assign(1, 0);
-    groupFrames = 0; groupJobs = 0;
-    uint64_t inGroup = 0;
-    for (uint32_t j = 0 ; j < jobs.n ; ++j)
-    {
-        const uint64_t nF = hs[jobs.list[j].stream].nFrames;
-        if ((inGroup != 0 && inGroup + nF > limit) || inGroup + nF > 0xFFFFFFFFull)
-        {
-            groupFirst.push_back(j);
-            inGroup = 0;
-        }
-        inGroup += nF;
-        groupFrames = inGroup > groupFrames ? inGroup : groupFrames;
-        groupJobs = std::max(groupJobs, j + 1 - groupFirst.back());
-    }
-    groupFirst.push_back(jobs.n);
-}
-
-// every buffer of a group, sized for the largest one; the first failure is returned, for allocGroups to judge
-hipError_t EncRun::allocGroup()
-{
-    const size_t JF = static_cast<size_t>(groupFrames), NJ = groupJobs;
-    HIPTRY(group.alloc(&gb.dJobs, NJ));
-    HIPTRY(group.alloc(&gb.dFJ, JF));
-    HIPTRY(group.alloc(&gb.dHdr, 48 * NJ));
-    HIPTRY(group.alloc(&gb.dKeep, NJ));
-    HIPTRY(group.alloc(&gb.dWin, NJ));
-    HIPTRY(group.alloc(&gb.dSize, NJ));
-    HIPTRY(group.alloc(&gb.dOutOff, NJ));
-    if (anyV != 0)
-        HIPTRY(group.alloc(&gb.dFrameBits, 3 * JF));
-    HIPTRY(group.alloc(&gb.dFrameOff, JF));
-    if (anyV != 0 && jobs.os93)
-    {
-        HIPTRY(group.alloc(&gb.o93.dRec, 32 * JF));
-        HIPTRY(group.alloc(&gb.o93.dBand, 32 * JF));
-    }
-    if (anyV != 0 && !jobs.os93)
-    {
-        HIPTRY(group.alloc(&gb.v94.dBest, 128 * JF));
-        HIPTRY(group.alloc(&gb.v94.dCodes, 48 * JF));
-        HIPTRY(group.alloc(&gb.v94.dHdrBits, 48 * JF));
-        HIPTRY(group.alloc(&gb.v94.dSmpBits, 48 * JF));
-    }
-    if (!qs.empty())
-    {
-        HIPTRY(group.alloc(&gb.a93.dChoice, NJ));
-        HIPTRY(group.alloc(&gb.a93.dRec, JF));
-    }
-    if (sweep.measure)
-    {
-        HIPTRY(group.alloc(&gb.m.dMeas, NJ));
-        HIPTRY(group.alloc(&gb.m.dFirstDec, NJ));
-    }
-    if (jobs.rd)
-        HIPTRY(rdAllocGroup());
-    if (jobs.rd93)
-        HIPTRY(rd93AllocGroup());
-    return hipSuccess;
-}
-
-// all jobs in one group when that can be had (or the cap that is set); half the job-frames each time the memory runs out
-DcsStatus EncRun::allocGroups()
-{
-    uint64_t limit = gGroupFrames.load() != 0 ? std::max<uint64_t>(gGroupFrames.load(), largest) : allFrames;
-    for (;;)
-    {
-        makeGroups(limit);
-        const hipError_t e = allocGroup();
-        if (e == hipSuccess)
-            return DCS_OK;
-        group.clear();
-        if (e != hipErrorOutOfMemory || groupFrames <= largest)
-            ENCCHK(e);
-        limit = std::max<uint64_t>(largest, groupFrames / 2);
-    }
-}
-
-// E2's header half to the sizes for group g, and a wait: win, keep and size of its jobs are on the host after it
-DcsStatus EncRun::runGroup(uint32_t g)
-{
-    const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
-    hj.resize(n);
-    frameJob.clear();
-    uint32_t JF = 0;
-    for (uint32_t k = 0 ; k < n ; ++k)
-    {
-        const DcsSweepJob &job = jobs.list[j0 + k];
-        const EncStream &s = hs[job.stream];
-        hj[k] = EncJob{ job.stream, job.paramSet, JF, s.nFrames, s.firstFrame };
-        frameJob.insert(frameJob.end(), s.nFrames, k);
-        JF += s.nFrames;
-    }
-    ENCCHK(hipMemcpyAsync(gb.dJobs, hj.data(), sizeof(EncJob) * n, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(gb.dFJ, frameJob.data(), sizeof(uint32_t) * JF, hipMemcpyHostToDevice, st));
-    if (anyV != 0)
-    {
-        ENCCHK(hipMemsetAsync(gb.dFrameBits, 0, sizeof(uint32_t) * 3 * JF, st));
-        hipLaunchKernelGGL(encHeaderKernel, dim3(n), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, cb.dSums, gb.dHdr, gb.dKeep);
-    }
-    if (anyV != 0 && jobs.os93)
-    {
-        hipLaunchKernelGGL(enc93SearchKernel, dim3((JF + 3) / 4), dim3(128), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, cb.dSets, gb.dHdr,
-                           gb.dKeep, JF, gb.o93.dRec);
-        if (anyV & 1)
-            hipLaunchKernelGGL(enc93WalkKernel<0>, dim3((JF + 63) / 64), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, gb.dFJ, gb.dKeep, JF, JF,
-                               gb.o93.dRec, gb.o93.dBand, gb.dFrameBits);
-        if (anyV & 2)
-            hipLaunchKernelGGL(enc93WalkKernel<1>, dim3((n + 63) / 64), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, gb.dFJ, gb.dKeep, JF, n,
-                               gb.o93.dRec, gb.o93.dBand, gb.dFrameBits);
-    }
-    if (anyV != 0 && !jobs.os93)
-    {
-        ENCCHK(hipMemsetAsync(gb.v94.dBest, 0, size_t(128) * JF, st));
-        ENCCHK(hipMemsetAsync(gb.v94.dCodes, 0, size_t(48) * JF, st));
-        hipLaunchKernelGGL(encSearchKernel, dim3(JF), dim3(128), 0, st, cb.dT, cb.dSpec, cb.dLo, cb.dHi, gb.dFJ, gb.dJobs, cb.dSets, gb.dHdr,
-                           gb.dKeep, gb.v94.dBest);
-        hipLaunchKernelGGL(encChainKernel, dim3(n), dim3(64), 0, st, cb.dT, gb.dJobs, cb.dSets, gb.dKeep, JF,
-                           reinterpret_cast<const uint64_t *>(gb.v94.dBest), gb.v94.dCodes);
-        hipLaunchKernelGGL(encBitsKernel, dim3(JF), dim3(64), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, cb.dSets, gb.dHdr, gb.dKeep, JF,
-                           gb.v94.dCodes, gb.v94.dHdrBits, gb.v94.dSmpBits, gb.dFrameBits);
-    }
-    // (a job of the A family has no layout here, cmask 0: encSizeKernel leaves its win at -1, which the head and pack
-    // kernels of this family pass over)
-    if (anyV != 0)
-        hipLaunchKernelGGL(encSizeKernel, dim3(n), dim3(256), 0, st, gb.dJobs, cb.dSets, JF, gb.dFrameBits, gb.dWin, gb.dSize, gb.dFrameOff);
-    if (!qs.empty())
-        hipLaunchKernelGGL(enc93aChooseKernel, dim3(n), dim3(256), 0, st, cb.a93.dTot, cb.a93.dRowOf, in.nStreams, gb.dJobs, cb.dSets,
-                           cb.a93.dSetQ, gb.a93.dChoice);
-    if (jobs.rd)
-        ENCTRY(rdRunGroup(j0, n));
-    if (jobs.rd93)
-        ENCTRY(rd93RunGroup(j0, n, JF));
-    if (jobs.fit != nullptr && allot.empty())
-        ENCTRY(fitCurves(j0, n));
-    ENCCHK(hipGetLastError());
-    if (anyV != 0)
-    {
-        ENCCHK(hipMemcpyAsync(win.data() + j0, gb.dWin, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipMemcpyAsync(keep.data() + j0, gb.dKeep, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        ENCCHK(hipMemcpyAsync(size.data() + j0, gb.dSize, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
-    }
-    if (!qs.empty())
-        ENCCHK(hipMemcpyAsync(choiceA.data() + j0, gb.a93.dChoice, sizeof(Enc93aChoice) * n, hipMemcpyDeviceToHost, st));
-    ENCCHK(hipStreamSynchronize(st));
-    // a Type-1 job: the candidate (1, 0) of CloseStream's list, its header's band count, 3 header bytes and the frames' bits
-    for (uint32_t k = 0 ; k < n ; ++k)
-        if (setQ[hj[k].set] != kA93None)
-        {
-            win[j0 + k] = 2;
-            keep[j0 + k] = choiceA[j0 + k].numBands;
-            size[j0 + k] = 3 + (choiceA[j0 + k].frameBits + 7) / 8;
-        }
-    sizesRd(j0, n);
-    resident = g;
-    residentFrames = JF;
-    return DCS_OK;
-}
-
-// win, keep and size of n jobs from job j0 from what the R or the S family chose for them
-void EncRun::sizesRd(uint32_t j0, uint32_t n)
-{
-    // a job of the R family: the candidate of CloseStream's list it chose, its header's band count, 18 bytes and the frames' bits
-    for (uint32_t k = 0 ; jobs.rd && k < n ; ++k)
-    {
-        win[j0 + k] = choiceRd[j0 + k].variant;
-        keep[j0 + k] = choiceRd[j0 + k].numBands;
-        size[j0 + k] = 18 + (choiceRd[j0 + k].frameBits + 7) / 8;
-    }
-    // a job of the S family: Type 0, its header's band count, 18 bytes and the frames' bits
-    for (uint32_t k = 0 ; jobs.rd93 && k < n ; ++k)
-    {
-        win[j0 + k] = 0;
-        keep[j0 + k] = choiceRd93[j0 + k].numBands;
-        size[j0 + k] = 18 + (choiceRd93[j0 + k].frameBits + 7) / 8;
-    }
-}
-
-// Upload, E1 and encStreamKernel; bad[] is on its way to the host, there after the first group's wait; then A1 for the
-// streams that jobs of the A family name.  (The step before runGroup, written after it: the kernel templates are
-// instantiated in the order the source first launches them, and the device code object keeps the order it had.  The A
-// family's two, enc93aFrameKernel<false> here and <true> in packGroup, follow E1's and precede the resampler's.)
-DcsStatus EncRun::analyse()
-{
-    const uint32_t nStreams = in.nStreams;
-    const uint64_t first = in.sampleOffsets[0], nSamples = in.sampleOffsets[nStreams] - first;
-    const EncTabs &tabs = jobs.os93 ? encTabs93() : encTabs();
-    bad.resize(nStreams);
-    ENCCHK(hipMemcpyAsync(cb.dT, &tabs, sizeof(EncTabs), hipMemcpyHostToDevice, st));
-    if (!dev && !devF)
-        ENCCHK(hipMemcpyAsync(cb.dPcm, in.hostPcm + first, sizeof(float) * nSamples, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(cb.dStr, hs.data(), sizeof(EncStream) * nStreams, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(cb.dSets, hsets.data(), sizeof(EncSet) * jobs.nSets, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(cb.dFS, frameStream.data(), sizeof(uint32_t) * F, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemsetAsync(cb.dBad, 0, sizeof(uint32_t) * nStreams, st));
-    if (dev)
-        hipLaunchKernelGGL(encAnalyseKernel<int16_t>, dim3((F + 3) / 4), dim3(256), 0, st, cb.dT, in.devPcm + first, cb.dStr, cb.dFS, F,
-                           cb.dSpec, cb.dPw, cb.dLo, cb.dHi, cb.dBad, in.devErr);
-    else
-        hipLaunchKernelGGL(encAnalyseKernel<float>, dim3((F + 3) / 4), dim3(256), 0, st, cb.dT, devF ? in.devFloat + first : cb.dPcm,
-                           cb.dStr, cb.dFS, F, cb.dSpec, cb.dPw, cb.dLo, cb.dHi, cb.dBad, static_cast<const uint32_t *>(nullptr));
-    if (anyV != 0)
-        hipLaunchKernelGGL(encStreamKernel, dim3(nStreams), dim3(64), 0, st, cb.dStr, cb.dPw, cb.dLo, cb.dHi, cb.dSums);
-    ENCCHK(hipMemcpyAsync(bad.data(), cb.dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
-    if (jobs.rd)
-        return rdAnalyse();
-    if (jobs.rd93)
-        return rd93Analyse();
-    if (qs.empty())
-        return DCS_OK;
-    // A1: one search per stream-frame; kA93QPerLaunch of the distinct q to a launch
-    const uint32_t nQ = static_cast<uint32_t>(qs.size());
-    floorE.resize(size_t(18) * nQ);
-    for (uint32_t k = 0 ; k < nQ ; ++k)
-        floorE93a(qs[k], floorE.data() + size_t(18) * k);
-    ENCCHK(hipMemcpyAsync(cb.a93.dA, &encTabs93a(), sizeof(Enc93aTabs), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(cb.a93.dFloorE, floorE.data(), sizeof(unsigned long long) * floorE.size(), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(cb.a93.dSetQ, setQ.data(), sizeof(uint32_t) * jobs.nSets, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(cb.a93.dRowOf, rowOf.data(), sizeof(uint32_t) * rowOf.size(), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemsetAsync(cb.a93.dTot, 0, sizeof(Enc93aTot) * kA93Cand * nRows, st));
-    for (uint32_t q0 = 0 ; q0 < nQ ; q0 += kA93QPerLaunch)
-        hipLaunchKernelGGL(enc93aFrameKernel<false>, dim3(F), dim3(256), 0, st, cb.a93.dA, cb.a93.dFloorE, cb.dSpec, cb.dFS, cb.a93.dRowOf,
-                           nStreams, q0, std::min(kA93QPerLaunch, nQ - q0), cb.a93.dTot, static_cast<const EncJob *>(nullptr),
-                           static_cast<const uint32_t *>(nullptr), static_cast<const Enc93aChoice *>(nullptr), static_cast<Enc93aRec *>(nullptr));
-    return DCS_OK;
-}
-
-// what the first wait brings: was the input usable at all (planFlag), then did E1 refuse a sample (bad[])
-DcsStatus EncRun::checkInput()
-{
-    if (in.planFlag != nullptr && *in.planFlag != 0)
-    {
-        in.unusable = true;
-        return DCS_ERR_BAD_STREAM;
-    }
-    for (uint32_t i = 0 ; i < in.nStreams ; ++i)
-        if (bad[i])
-        {
-            dcsCtxSetError(ctx, (name(i) + (dev ? ": the decoder reports an error in a frame (DCS_FRAME_STOP / DCS_FRAME_FATAL)"
-                                                : in.bound != nullptr ? ": a sample is not finite or beyond its format's full scale"
-                                                : ": a sample is not finite or |x| > 1")).c_str());
-            return DCS_ERR_BAD_STREAM;
-        }
-    return DCS_OK;
-}
-
-// info, info93a, infoRd and the sweep's result of job j, from what its group's run left on the host
-void EncRun::writeInfo(uint32_t j)
-{
-    const DcsEncodeInfo e{ kCandType[win[j]], kCandSub[win[j]], static_cast<int32_t>(hs[jobs.list[j].stream].nFrames),
-                           static_cast<int32_t>(size[j]), keep[j] };
-    if (to.info != nullptr)
-        to.info[j] = e;
-    if (to.info93a != nullptr)
-    {
-        const DcsEncodeParams &p = jobs.sets[jobs.list[j].paramSet];
-        const Enc93aChoice &c = choiceA[j];
-        const uint64_t budget = static_cast<uint64_t>(p.targetBitRate) * static_cast<uint64_t>(e.nFrames) * 240ull / 31250ull;
-        to.info93a[j] = setQ[jobs.list[j].paramSet] == kA93None ? DcsEncode93aInfo{}
-                        : DcsEncode93aInfo{ c.selector, c.ladderIndex, c.numBands, 0, c.frameBits, budget, c.sumD };
-    }
-    if (to.infoRd != nullptr && jobs.rd93)
-    {
-        const Enc93RdChoice &c = choiceRd93[j];
-        to.infoRd[j] = DcsEncodeRdInfo{ 0, 0, c.ladderIndex, c.numBands, c.frameBits,
-                                        static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
-    }
-    else if (to.infoRd != nullptr)
-    {
-        const EncRdChoice &c = choiceRd[j];
-        to.infoRd[j] = DcsEncodeRdInfo{ kCandType[c.variant], kCandSub[c.variant], c.ladderIndex, c.numBands, c.frameBits,
-                                        static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
-    }
-    if (sweep.results != nullptr)
-    {
-        memset(&sweep.results[j], 0, sizeof(DcsSweepResult));       // (its padding too: records compare as bytes)
-        sweep.results[j].enc = e;
-    }
-}
-
-// every size is known: outOffsets, info and results, then dst (null with DCS_OK: a sweep that asked for sizes only).  (A fit
-// call knows the sizes, its allotments, before its groups have chosen: fitReport writes their info.)
-DcsStatus EncRun::placeOutput()
-{
-    uint64_t *outOffsets = to.outOffsets;
-    for (uint32_t j = 0 ; j < jobs.n ; ++j)
-    {
-        outOffsets[j + 1] = outOffsets[j] + size[j];
-        if (jobs.fit == nullptr)
-            writeInfo(j);
-    }
-    if (sweep.sizesOnly)
-        return DCS_OK;
-    const uint64_t total = outOffsets[jobs.n];
-    dst = to.place != nullptr && *to.place ? (*to.place)(outOffsets, total) : (to.out != nullptr && to.outCap >= total ? to.out : nullptr);
-    return dst != nullptr ? DCS_OK : DCS_ERR_CAPACITY;
-}
-
-// Where the jobs of group g lie in its blob, and the blob's size in words.  For the output: as in the output.  For a
-// decode: where the device path's stream layout wants them (each stream on a 4-byte boundary, the blob's zeroed tail).
-DcsStatus EncRun::layoutGroup(uint32_t g, size_t *nWords)
-{
-    const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
-    offs.resize(n);
-    if (!sweep.measure)
-    {
-        for (uint32_t k = 0 ; k < n ; ++k)
-            offs[k] = to.outOffsets[j0 + k] - to.outOffsets[j0];
-        blobLen = static_cast<size_t>(to.outOffsets[j0 + n] - to.outOffsets[j0]);
-        *nWords = (blobLen + 3) / 4 + 1;
-        return DCS_OK;
-    }
-    ss.resize(n);
-    for (uint32_t k = 0 ; k < n ; ++k)
-    {
-        const int c = win[j0 + k];
-        const uint16_t ver = jobs.sets[hj[k].set].formatVersion;
-        const bool a93 = setQ[hj[k].set] != kA93None;
-        ss[k] = DcsSweepStream{ hj[k].nFrames, static_cast<uint32_t>(size[j0 + k]),
-                                ver == 0x9301 ? DCS_OS93A : ver == 0x9302 ? DCS_OS93B : kCandSub[c] == 3 ? DCS_OS95 : DCS_OS94, kCandType[c],
-                                jobs.os93 ? 0 : kCandSub[c], keep[j0 + k],
-                                a93 ? 0x80u | static_cast<uint32_t>(choiceA[j0 + k].selector) << 5 | static_cast<uint32_t>(keep[j0 + k]) : 0u };
-    }
-    size_t blobBytes;
-    ENCTRY(dcsSweepLayout(ss.data(), n, offs.data(), &blobLen, &blobBytes));
-    *nWords = blobBytes / 4;
-    return DCS_OK;
-}
-
-// header, pack and swap of the resident group g into a blob of its own
-DcsStatus EncRun::packGroup(uint32_t g)
-{
-    const uint32_t n = groupFirst[g + 1] - groupFirst[g], JF = residentFrames;
-    size_t nWords;
-    ENCTRY(layoutGroup(g, &nWords));
-    blob.clear();
-    staged = false;
-    ENCCHK(blob.alloc(&dW, nWords));
-    ENCCHK(hipMemsetAsync(dW, 0, sizeof(uint32_t) * nWords, st));
-    ENCCHK(hipMemcpyAsync(gb.dOutOff, offs.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
-    if (anyV != 0)
-        hipLaunchKernelGGL(encHeadKernel, dim3(n), dim3(64), 0, st, gb.dJobs, gb.dHdr, gb.dWin, gb.dOutOff, dW);
-    if (anyV != 0 && jobs.os93)
-        hipLaunchKernelGGL(enc93PackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, gb.dHdr, gb.dKeep, gb.dWin,
-                           JF, gb.o93.dBand, gb.dFrameOff, gb.dOutOff, dW);
-    if (anyV != 0 && !jobs.os93)
-        hipLaunchKernelGGL(encPackKernel, dim3((JF + 3) / 4), dim3(64), 0, st, cb.dT, cb.dSpec, gb.dFJ, gb.dJobs, gb.dHdr, gb.dKeep, gb.dWin,
-                           JF, gb.v94.dCodes, gb.v94.dHdrBits, gb.v94.dSmpBits, gb.dFrameOff, gb.dOutOff, dW);
-    if (!qs.empty())
-    {
-        // the Type-1 jobs: each job-frame's choices (A3), the frames' offsets (A4), the 3-byte headers and the pack (A5)
-        hipLaunchKernelGGL(enc93aFrameKernel<true>, dim3(JF), dim3(256), 0, st, cb.a93.dA, cb.a93.dFloorE, cb.dSpec, gb.dFJ,
-                           static_cast<const uint32_t *>(nullptr), 0u, 0u, 0u, static_cast<Enc93aTot *>(nullptr), gb.dJobs, cb.a93.dSetQ,
-                           gb.a93.dChoice, gb.a93.dRec);
-        hipLaunchKernelGGL(enc93aOffsetKernel, dim3(n), dim3(256), 0, st, gb.dJobs, cb.a93.dSetQ, gb.a93.dRec, gb.dFrameOff);
-        hipLaunchKernelGGL(enc93aHeadKernel, dim3((n + 63) / 64), dim3(64), 0, st, gb.dJobs, cb.a93.dSetQ, gb.a93.dChoice, gb.dOutOff, n, dW);
-        hipLaunchKernelGGL(enc93aPackKernel, dim3(JF), dim3(128), 0, st, cb.a93.dA, cb.dSpec, gb.dFJ, gb.dJobs, cb.a93.dSetQ, gb.a93.dChoice,
-                           gb.a93.dRec, gb.dFrameOff, gb.dOutOff, dW);
-    }
-    if (jobs.rd)
-        ENCTRY(rdPackGroup(n, JF));
-    if (jobs.rd93)
-        ENCTRY(rd93PackGroup(n, JF));
-    hipLaunchKernelGGL(encSwapKernel, dim3(static_cast<unsigned>((nWords + 255) / 256)), dim3(256), 0, st, dW, nWords);
-    ENCCHK(hipGetLastError());
-    return DCS_OK;
-}
-
-// the packed group g to its place in the output, and a wait
-DcsStatus EncRun::deliverGroup(uint32_t g)
-{
-    ENCCHK(hipMemcpyAsync(dst + to.outOffsets[groupFirst[g]], dW, blobLen, hipMemcpyDeviceToHost, st));
-    ENCCHK(hipStreamSynchronize(st));
-    return DCS_OK;
-}
-
-// the packed group's blob to `stage`, queued once per group; the caller waits
-DcsStatus EncRun::stageBlob()
-{
-    if (staged)
-        return DCS_OK;
-    stage.resize(blobLen);
-    ENCCHK(hipMemcpyAsync(stage.data(), dW, blobLen, hipMemcpyDeviceToHost, st));
-    staged = true;
-    return DCS_OK;
-}
-
-// The jobs of the packed group (n of them) whose streams are decoded.  One kind is left out: an OS93a Type-0 stream with
-// no band kept.  Its header is sixteen 0xFF bytes, the first of which carries the type bit, so every decoder reads it as
-// OS93a Type 1 with 31 bands; its record stays measured = 0.  (A Type-1 stream's header says what it is: always decoded.)
-void EncRun::selectDecodes(uint32_t n)
-{
-    sel.clear(); selS.clear(); selOff.clear();
-    mostFrames = 0;
-    selFrames = 0;
-    for (uint32_t k = 0 ; k < n ; ++k)
-        if (!(ss[k].os == DCS_OS93A && ss[k].formatType == 0 && ss[k].bandsToKeep == 0))
-        {
-            sel.push_back(k); selS.push_back(ss[k]); selOff.push_back(offs[k]);
-            mostFrames = std::max(mostFrames, hj[k].nFrames);
-            selFrames += hj[k].nFrames;
-        }
-}
-
-// One attempt: the selected streams decoded, on the device path from the bytes where they lie or (onHost) as a host-planned
-// batch from the staged blob, then M1 and a wait, after which meas[] is on the host, and so is the blob where the output
-// wants it.  *unusable: the device planner gave the list up (its flag); the sums are then not to be used.
-DcsStatus EncRun::decodeAndCompare(uint32_t n, bool onHost, bool *unusable)
-{
-    if (onHost && !staged)
-    {
-        ENCTRY(stageBlob());
-        ENCCHK(hipStreamSynchronize(st));
-    }
-    SweepDecodeGuard dec;
-    const int16_t *decPcm = nullptr;
-    const uint32_t *decErr = nullptr, *firstFrame = nullptr;
-    const volatile uint32_t *flag = nullptr;
-    const uint32_t nSel = static_cast<uint32_t>(sel.size());
-    ENCTRY(dcsSweepDecodeStart(ctx, selS.data(), nSel, selOff.data(), reinterpret_cast<const uint8_t *>(dW), blobLen,
-                               onHost ? stage.data() : nullptr, &dec.d, &decPcm, &decErr, &flag, &firstFrame));
-    for (uint32_t i = 0 ; i < nSel ; ++i)
-        firstDec[sel[i]] = firstFrame[i];
-    ENCCHK(hipMemcpyAsync(gb.m.dFirstDec, firstDec.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemsetAsync(gb.m.dMeas, 0, sizeof(EncMeasure) * n, st));
-    hipLaunchKernelGGL(encMeasureKernel, dim3(n, (mostFrames + 1 + kMeasureFrames - 1) / kMeasureFrames), dim3(256), 0, st,
-                       cb.dPcm, cb.dStr, gb.dJobs, gb.m.dFirstDec, decPcm, decErr, gb.m.dMeas);
-    ENCCHK(hipGetLastError());
-    ENCCHK(hipMemcpyAsync(meas.data(), gb.m.dMeas, sizeof(EncMeasure) * n, hipMemcpyDeviceToHost, st));
-    if (dst != nullptr)
-        ENCTRY(stageBlob());
-    ENCCHK(hipStreamSynchronize(st));
-    *unusable = flag != nullptr && *flag != 0;
-    return DCS_OK;
-}
-
-// meas[] to the results of group g's jobs, and their bytes from `stage` to the output
-DcsStatus EncRun::reportGroup(uint32_t g)
-{
-    const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
-    for (uint32_t k = 0 ; k < n ; ++k)
-    {
-        const uint32_t j = j0 + k;
-        if (meas[k].err != 0)
-        {
-            dcsCtxSetError(ctx, ("job " + std::to_string(j) + " (" + name(hj[k].stream) + ", set " + std::to_string(hj[k].set)
-                                 + "): the decoder reports an error in a frame of the stream just encoded").c_str());
-            return DCS_ERR_HIP;
-        }
-        DcsSweepResult &r = sweep.results[j];
-        if (dst != nullptr)
-            memcpy(dst + to.outOffsets[j], stage.data() + offs[k], size[j]);
-        if (firstDec[k] == kNotDecoded)
-            continue;
-        r.measured = 1;
-        r.peakErr = meas[k].peak;
-        r.nCompared = hs[hj[k].stream].nSamples;
-        r.sumSrcSq = static_cast<int64_t>(meas[k].srcSq);
-        r.sumDecSq = static_cast<int64_t>(meas[k].decSq);
-        r.sumCross = static_cast<int64_t>(meas[k].cross);
-    }
-    return DCS_OK;
-}
-
-// The packed group g decoded and compared with its sources.  The decode, as transcoding runs it (dcs_transcode.hip.h): the
-// device path on the bytes where they lie; the host-planned batch, for which the bytes are read back, where the device
-// planner cannot serve the list (a second attempt) or one long stream dominates it (the only one: the device index walk is
-// one wavefront per stream, serial over its frames).
-DcsStatus EncRun::measureGroup(uint32_t g)
-{
-    const uint32_t n = groupFirst[g + 1] - groupFirst[g];
-    selectDecodes(n);
-    const bool walkOnHost = mostFrames > 2048 && uint64_t(mostFrames) * 64 > selFrames;
-    meas.assign(n, EncMeasure{});
-    firstDec.assign(n, kNotDecoded);
-    if (sel.empty() && dst != nullptr)
-    {
-        ENCTRY(stageBlob());
-        ENCCHK(hipStreamSynchronize(st));
-    }
-    for (int attempt = walkOnHost ? 1 : 0 ; attempt < 2 && !sel.empty() ; ++attempt)
-    {
-        bool unusable = false;
-        ENCTRY(decodeAndCompare(n, attempt == 1, &unusable));
-        if (!unusable)
-            break;
-    }
-    return reportGroup(g);
-}
-
-DcsStatus EncRun::run()
-{
-    ENCTRY(checkStreams());
-    to.outOffsets[0] = 0;
-    if (in.nStreams == 0 || jobs.n == 0)
-    {
-        for (uint32_t j = 0 ; j < jobs.n ; ++j)
-            to.outOffsets[j + 1] = 0;
-        return DCS_OK;
-    }
-    buildSets();
-    win.resize(jobs.n); keep.resize(jobs.n); size.resize(jobs.n); choiceA.resize(jobs.n);
-    if (jobs.rd)
-        choiceRd.resize(jobs.n);
-    if (jobs.rd93)
-        choiceRd93.resize(jobs.n);
-    ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
-    ENCTRY(allocCall());
-    ENCTRY(allocGroups());
-    ENCTRY(analyse());
-    const uint32_t nGroups = static_cast<uint32_t>(groupFirst.size()) - 1;
-    for (uint32_t g = 0 ; g < nGroups ; ++g)
-    {
-        ENCTRY(runGroup(g));
-        if (g == 0)
-            ENCTRY(checkInput());
-    }
-    if (jobs.fit != nullptr)
-        ENCTRY(fitAllot());
-    ENCTRY(placeOutput());
-    if (dst == nullptr && !sweep.measure)
-        return DCS_OK;
-    for (uint32_t g = 0 ; g < nGroups ; ++g)
-    {
-        if (jobs.fit != nullptr)
-        {
-            ENCTRY(nGroups == 1 ? fitRechoose(g) : runGroup(g));
-            ENCTRY(fitReport(g));
-        }
-        else if (resident != g)
-            ENCTRY(runGroup(g));
-        ENCTRY(packGroup(g));
-        ENCTRY(sweep.measure ? measureGroup(g) : deliverGroup(g));
-    }
-    if (jobs.fit != nullptr)
-        fitRecord();
-    return DCS_OK;
-}
-
-// the entry points that encode every stream with one parameter set: job i = (stream i, set 0)
-DcsStatus encodeStreams(DcsCtx *ctx, EncInput &in, const DcsEncodeParams *params, bool os93, const EncOutput &to)
-{
-    const bool dev = in.devPcm != nullptr, devF = in.devFloat != nullptr;
-    if (ctx == nullptr || in.sampleOffsets == nullptr || to.outOffsets == nullptr
-        || (in.nStreams != 0 && in.hostPcm == nullptr && !dev && !devF) || (dev && in.devErr == nullptr))
-        return DCS_ERR_INVALID_ARG;
-    if (!paramsValid(params, os93))
-    {
-        if (const char *why = whyOs93aType1(params, os93))
-            dcsCtxSetError(ctx, why);
-        return DCS_ERR_INVALID_ARG;
-    }
-    std::vector<DcsSweepJob> list(in.nStreams);
-    for (uint32_t i = 0 ; i < in.nStreams ; ++i)
-        list[i] = DcsSweepJob{ i, 0 };
-    return EncRun(ctx, in, EncJobs{ params, 1, list.data(), in.nStreams, os93 }, to, EncSweep()).run();
-}
-
-// dcs_encode_streams and dcs_encode93_streams
-DcsStatus encodeHostPcm(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, const DcsEncodeParams *params,
-                        bool os93, const EncOutput &to)
-{
-    EncInput in;
-    in.sampleOffsets = sampleOffsets;
-    in.nStreams = nStreams;
-    in.hostPcm = pcm;
-    return encodeStreams(ctx, in, params, os93, to);
-}
-
-}  // namespace
+#include "dcs_encode_run.hip.h"
 
 extern "C" DcsStatus dcs_encode_streams(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
                                         const DcsEncodeParams *params, uint8_t *out, size_t outCap, uint64_t *outOffsets,
@@ -2412,14 +1423,8 @@ DcsStatus encode93aType1(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOf
 {
     DcsEncodeParams p1 = *params;
     p1.streamFormatType = 1;
-    EncInput in;
-    in.sampleOffsets = sampleOffsets;
-    in.nStreams = nStreams;
-    in.hostPcm = pcm;
-    std::vector<DcsSweepJob> list(nStreams);
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-        list[i] = DcsSweepJob{ i, 0 };
-    return EncRun(ctx, in, EncJobs{ &p1, 1, list.data(), nStreams, true }, to, EncSweep()).run();
+    EncOneSet one(pcm, sampleOffsets, nStreams);
+    return EncRun(ctx, one.in, one.jobs(&p1, true), to, EncSweep()).run();
 }
 
 }  // namespace
@@ -2624,92 +1629,112 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
 
 #include "dcs_encode_files.hip.h"
 
-// ------------------------------------------------- the rate-distortion 1994+ encoder: kernels and driver (dcs_encode_rd.hip.h)
+// ----------------------------------------- the rate-distortion 1994+ encoder: kernels (dcs_encode_rd.hip.h) and the R family
 // (behind every other kernel of the unit, templates included: those keep their place in the code object)
 
 #include "dcs_encode_rd.hip.h"
 
 namespace {
 
-DcsStatus EncRun::rdAllocCall()
+bool EncRdFamily::select()
 {
-    ENCCHK(call.alloc(&cb.rd.dR, 1));
-    ENCCHK(call.alloc(&cb.rd.dItems, size_t(kRdItemsPerFrame) * F));
-    ENCCHK(call.alloc(&cb.rd.dPeak, size_t(16) * in.nStreams));
-    ENCCHK(call.alloc(&cb.rd.dD0, size_t(16) * in.nStreams));
-    ENCCHK(call.alloc(&cb.rd.dFloor, size_t(16) * jobs.nSets));
+    choice.resize(jobs.n);
+    return selectSearch(false);
+}
+
+DcsStatus EncRdFamily::allocCall()
+{
+    ENCCHK(s.call.alloc(&dR, 1));
+    ENCCHK(s.call.alloc(&dItems, size_t(kRdItemsPerFrame) * s.F));
+    ENCCHK(s.call.alloc(&dPeak, size_t(16) * in.nStreams));
+    ENCCHK(s.call.alloc(&dD0, size_t(16) * in.nStreams));
+    ENCCHK(s.call.alloc(&dFloor, size_t(16) * jobs.nSets));
     return DCS_OK;
 }
 
-hipError_t EncRun::rdAllocGroup()
+hipError_t EncRdFamily::allocGroup()
 {
-    const size_t JF = static_cast<size_t>(groupFrames), NJ = groupJobs;
-    HIPTRY(group.alloc(&gb.rd.dTot, size_t(kRdRowsPerJob) * NJ));
-    HIPTRY(group.alloc(&gb.rd.dChoice, NJ));
-    HIPTRY(group.alloc(&gb.rd.dBudget, NJ));
-    HIPTRY(group.alloc(&gb.rd.dSurv, 256 * JF));
-    HIPTRY(group.alloc(&gb.rd.dEnd, 16 * NJ));
-    HIPTRY(group.alloc(&gb.rd.dCodes, 16 * JF));
-    HIPTRY(group.alloc(&gb.rd.dBits, JF));
+    const size_t JF = static_cast<size_t>(s.groupFrames), NJ = s.groupJobs;
+    HIPTRY(s.group.alloc(&dTot, size_t(kRdRowsPerJob) * NJ));
+    HIPTRY(s.group.alloc(&dChoice, NJ));
+    HIPTRY(s.group.alloc(&dBudget, NJ));
+    HIPTRY(s.group.alloc(&dSurv, 256 * JF));
+    HIPTRY(s.group.alloc(&dEnd, 16 * NJ));
+    HIPTRY(s.group.alloc(&dCodes, 16 * JF));
+    HIPTRY(s.group.alloc(&dBits, JF));
     return hipSuccess;
 }
 
-// the budgets of all jobs, in frame bits (-1: nothing fits)
-void EncRun::budgetsRd()
-{
-    budgetRd.resize(jobs.n);
-    for (uint32_t j = 0 ; j < jobs.n ; ++j)
-    {
-        const uint64_t nF = hs[jobs.list[j].stream].nFrames;
-        if (jobs.budgetBytes == nullptr)
-            budgetRd[j] = static_cast<long long>(static_cast<uint64_t>(jobs.sets[jobs.list[j].paramSet].targetBitRate) * nF * 240ull / 31250ull);
-        else
-            budgetRd[j] = jobs.budgetBytes[j] >= 18 ? (static_cast<long long>(jobs.budgetBytes[j]) - 18) * 8 : -1;
-    }
-}
-
 // R1 over every stream-frame; the budgets
-DcsStatus EncRun::rdAnalyse()
+DcsStatus EncRdFamily::analyse()
 {
     floorRd.resize(size_t(16) * jobs.nSets);
     for (uint32_t k = 0 ; k < jobs.nSets ; ++k)
         floorERd(jobs.sets[k].maximumQuantizationError, floorRd.data() + size_t(16) * k);
-    budgetsRd();
-    ENCCHK(hipMemcpyAsync(cb.rd.dR, &encTabsRd(), sizeof(EncRdTabs), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(cb.rd.dFloor, floorRd.data(), sizeof(unsigned long long) * floorRd.size(), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemsetAsync(cb.rd.dPeak, 0, sizeof(uint32_t) * 16 * in.nStreams, st));
-    ENCCHK(hipMemsetAsync(cb.rd.dD0, 0, sizeof(unsigned long long) * 16 * in.nStreams, st));
-    hipLaunchKernelGGL(encRdItemKernel, dim3(F), dim3(256), 0, st, cb.dT, cb.rd.dR, cb.dSpec, cb.dFS, cb.rd.dItems, cb.rd.dPeak, cb.rd.dD0);
+    budgets();
+    ENCCHK(hipMemcpyAsync(dR, &encTabsRd(), sizeof(EncRdTabs), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dFloor, floorRd.data(), sizeof(unsigned long long) * floorRd.size(), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(dPeak, 0, sizeof(uint32_t) * 16 * in.nStreams, st));
+    ENCCHK(hipMemsetAsync(dD0, 0, sizeof(unsigned long long) * 16 * in.nStreams, st));
+    hipLaunchKernelGGL(encRdItemKernel, dim3(s.F), dim3(256), 0, st, cb.dT, dR, cb.dSpec, cb.dFS, dItems, dPeak, dD0);
     return DCS_OK;
 }
 
-// R2 and R3 for the n jobs of a group from job j0; the choices are on the host after runGroup's wait
-DcsStatus EncRun::rdRunGroup(uint32_t j0, uint32_t n)
+// R2 and R3 for the n jobs of a group from job j0; the choices are on the host after the group's wait
+DcsStatus EncRdFamily::runGroup(uint32_t j0, uint32_t n, uint32_t)
 {
-    ENCCHK(hipMemcpyAsync(gb.rd.dBudget, budgetRd.data() + j0, sizeof(long long) * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(encRdTrellisKernel<false>, dim3(kRdRowsPerJob / 16 * n), dim3(256), 0, st, cb.dT, cb.rd.dR, cb.rd.dItems, cb.rd.dPeak,
-                       cb.rd.dFloor, gb.dJobs, cb.dSets, gb.rd.dTot, static_cast<const EncRdChoice *>(nullptr),
+    ENCTRY(uploadBudgets(j0, n));
+    hipLaunchKernelGGL(encRdTrellisKernel<false>, dim3(kRdRowsPerJob / 16 * n), dim3(256), 0, st, cb.dT, dR, dItems, dPeak,
+                       dFloor, gb.dJobs, cb.dSets, dTot, static_cast<const EncRdChoice *>(nullptr),
                        static_cast<uint8_t *>(nullptr), static_cast<uint8_t *>(nullptr));
-    hipLaunchKernelGGL(encRdChooseKernel, dim3(n), dim3(256), 0, st, gb.rd.dTot, cb.rd.dD0, gb.dJobs, cb.dSets, gb.rd.dBudget, gb.rd.dChoice);
-    ENCCHK(hipMemcpyAsync(choiceRd.data() + j0, gb.rd.dChoice, sizeof(EncRdChoice) * n, hipMemcpyDeviceToHost, st));
+    launchChoose(n);
+    return fetchChoice(j0, n);
+}
+
+void EncRdFamily::launchChoose(uint32_t n)
+{
+    hipLaunchKernelGGL(encRdChooseKernel, dim3(n), dim3(256), 0, st, dTot, dD0, gb.dJobs, cb.dSets, dBudget, dChoice);
+}
+
+DcsStatus EncRdFamily::fetchChoice(uint32_t j0, uint32_t n)
+{
+    ENCCHK(hipMemcpyAsync(choice.data() + j0, dChoice, sizeof(EncRdChoice) * n, hipMemcpyDeviceToHost, st));
     return DCS_OK;
+}
+
+// a job of the R family: the candidate of CloseStream's list it chose, its header's band count, 18 bytes and the frames' bits
+void EncRdFamily::sizeJobs(uint32_t j0, uint32_t n)
+{
+    for (uint32_t j = j0 ; j < j0 + n ; ++j)
+    {
+        s.win[j] = choice[j].variant;
+        s.keep[j] = choice[j].numBands;
+        s.size[j] = 18 + (choice[j].frameBits + 7) / 8;
+    }
 }
 
 // R4 to R6 for the resident group: the chosen chains with their survivors, the frames' bits and offsets, header and pack
-DcsStatus EncRun::rdPackGroup(uint32_t n, uint32_t JF)
+DcsStatus EncRdFamily::packGroup(uint32_t n, uint32_t JF)
 {
-    ENCCHK(hipMemsetAsync(gb.rd.dCodes, 0, size_t(16) * JF, st));
-    hipLaunchKernelGGL(encRdTrellisKernel<true>, dim3(n), dim3(256), 0, st, cb.dT, cb.rd.dR, cb.rd.dItems, cb.rd.dPeak, cb.rd.dFloor,
-                       gb.dJobs, cb.dSets, static_cast<EncRdTot *>(nullptr), gb.rd.dChoice, gb.rd.dSurv, gb.rd.dEnd);
-    hipLaunchKernelGGL(encRdBackKernel, dim3((16 * n + 63) / 64), dim3(64), 0, st, gb.dJobs, gb.rd.dChoice, gb.rd.dSurv, gb.rd.dEnd, n,
-                       gb.rd.dCodes);
-    hipLaunchKernelGGL(encRdBitsKernel, dim3((JF + 63) / 64), dim3(64), 0, st, cb.dT, cb.rd.dItems, cb.rd.dPeak, gb.dFJ, gb.dJobs,
-                       gb.rd.dChoice, gb.rd.dCodes, JF, gb.rd.dBits);
-    hipLaunchKernelGGL(encRdOffsetKernel, dim3(n), dim3(256), 0, st, gb.dJobs, gb.rd.dBits, gb.dFrameOff);
-    hipLaunchKernelGGL(encRdHeadKernel, dim3((n + 63) / 64), dim3(64), 0, st, cb.dT, cb.rd.dPeak, gb.dJobs, gb.rd.dChoice, gb.dOutOff, n, dW);
-    hipLaunchKernelGGL(encRdPackKernel, dim3(JF), dim3(64), 0, st, cb.dT, cb.rd.dR, cb.dSpec, cb.rd.dItems, cb.rd.dPeak, gb.dFJ, gb.dJobs,
-                       gb.rd.dChoice, gb.rd.dCodes, gb.dFrameOff, gb.dOutOff, dW);
+    ENCCHK(hipMemsetAsync(dCodes, 0, size_t(16) * JF, st));
+    hipLaunchKernelGGL(encRdTrellisKernel<true>, dim3(n), dim3(256), 0, st, cb.dT, dR, dItems, dPeak, dFloor,
+                       gb.dJobs, cb.dSets, static_cast<EncRdTot *>(nullptr), dChoice, dSurv, dEnd);
+    hipLaunchKernelGGL(encRdBackKernel, dim3((16 * n + 63) / 64), dim3(64), 0, st, gb.dJobs, dChoice, dSurv, dEnd, n, dCodes);
+    hipLaunchKernelGGL(encRdBitsKernel, dim3((JF + 63) / 64), dim3(64), 0, st, cb.dT, dItems, dPeak, gb.dFJ, gb.dJobs,
+                       dChoice, dCodes, JF, dBits);
+    hipLaunchKernelGGL(encRdOffsetKernel, dim3(n), dim3(256), 0, st, gb.dJobs, dBits, gb.dFrameOff);
+    hipLaunchKernelGGL(encRdHeadKernel, dim3((n + 63) / 64), dim3(64), 0, st, cb.dT, dPeak, gb.dJobs, dChoice, gb.dOutOff, n, s.dW);
+    hipLaunchKernelGGL(encRdPackKernel, dim3(JF), dim3(64), 0, st, cb.dT, dR, cb.dSpec, dItems, dPeak, gb.dFJ, gb.dJobs,
+                       dChoice, dCodes, gb.dFrameOff, gb.dOutOff, s.dW);
     return DCS_OK;
+}
+
+void EncRdFamily::writeInfo(uint32_t j)
+{
+    const EncRdChoice &c = choice[j];
+    if (to.infoRd != nullptr)
+        to.infoRd[j] = DcsEncodeRdInfo{ kCandType[c.variant], kCandSub[c.variant], c.ladderIndex, c.numBands, c.frameBits,
+                                        static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
 }
 
 }  // namespace
@@ -2723,109 +1748,123 @@ extern "C" DcsStatus dcs_encode_rd_streams(DcsCtx *ctx, const float *pcm, const 
                                            const DcsEncodeParams *params, const uint32_t *budgetBytes, uint8_t *out, uint64_t outCap,
                                            uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
-        return DCS_ERR_INVALID_ARG;
-    if (!paramsValidRd(params))
-    {
-        dcsCtxSetError(ctx, "dcs_encode_rd_streams: formatVersion 0x9400, streamFormatType 0, 1 or -1, streamFormatSubType 0, 3 or -1, "
-                            "targetBitRate 1..100 000 000 and finite parameters");
-        return DCS_ERR_INVALID_ARG;
-    }
-    EncInput in;
-    in.sampleOffsets = sampleOffsets;
-    in.nStreams = nStreams;
-    in.hostPcm = pcm;
-    std::vector<DcsSweepJob> list(nStreams);
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-        list[i] = DcsSweepJob{ i, 0 };
-    EncJobs js{ params, 1, list.data(), nStreams, false };
-    js.rd = true;
-    js.budgetBytes = budgetBytes;
-    EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
-    to.infoRd = infoRd;
-    return EncRun(ctx, in, js, to, EncSweep()).run();
+    return encodeSearched(ctx, "dcs_encode_rd_streams", pcm, sampleOffsets, nStreams, params, false, budgetBytes, nullptr, out, outCap,
+                          outOffsets, info, infoRd);
 }
 
-// ------------------------------------------ the rate-distortion OS93 Type-0 encoder: kernels and driver (dcs_encode93_rd.hip.h)
+// --------------------------------- the rate-distortion OS93 Type-0 encoder: kernels (dcs_encode93_rd.hip.h) and the S family
 // (behind every other kernel of the unit once more)
 
 #include "dcs_encode93_rd.hip.h"
 
 namespace {
 
-DcsStatus EncRun::rd93AllocCall()
+bool Enc93RdFamily::select()
 {
-    ENCCHK(call.alloc(&cb.r93.dR, 1));
-    ENCCHK(call.alloc(&cb.r93.dItems, size_t(kRd93ItemsPerFrame) * F));
-    ENCCHK(call.alloc(&cb.r93.dRecs, size_t(kRd93RecsPerFrame) * F));
-    ENCCHK(call.alloc(&cb.r93.dD0, size_t(16) * in.nStreams));
-    ENCCHK(call.alloc(&cb.r93.dFloor, jobs.nSets));
+    choice.resize(jobs.n);
+    return selectSearch(true);
+}
+
+DcsStatus Enc93RdFamily::allocCall()
+{
+    ENCCHK(s.call.alloc(&dR, 1));
+    ENCCHK(s.call.alloc(&dItems, size_t(kRd93ItemsPerFrame) * s.F));
+    ENCCHK(s.call.alloc(&dRecs, size_t(kRd93RecsPerFrame) * s.F));
+    ENCCHK(s.call.alloc(&dD0, size_t(16) * in.nStreams));
+    ENCCHK(s.call.alloc(&dFloor, jobs.nSets));
     return DCS_OK;
 }
 
-hipError_t EncRun::rd93AllocGroup()
+hipError_t Enc93RdFamily::allocGroup()
 {
-    const size_t JF = static_cast<size_t>(groupFrames), NJ = groupJobs;
-    HIPTRY(group.alloc(&gb.r93.dProxyJ, size_t(kRd93ProxyPerJob) * NJ));
-    HIPTRY(group.alloc(&gb.r93.dProxyB, size_t(kRd93ProxyPerJob) * NJ));
-    HIPTRY(group.alloc(&gb.r93.dHead, size_t(kRdKL) * NJ));
-    HIPTRY(group.alloc(&gb.r93.dTot, size_t(kRdKL) * NJ));
-    HIPTRY(group.alloc(&gb.r93.dChoice, NJ));
-    HIPTRY(group.alloc(&gb.r93.dBudget, NJ));
-    HIPTRY(group.alloc(&gb.r93.dCodes, 16 * JF));
-    HIPTRY(group.alloc(&gb.r93.dBits, JF));
+    const size_t JF = static_cast<size_t>(s.groupFrames), NJ = s.groupJobs;
+    HIPTRY(s.group.alloc(&dProxyJ, size_t(kRd93ProxyPerJob) * NJ));
+    HIPTRY(s.group.alloc(&dProxyB, size_t(kRd93ProxyPerJob) * NJ));
+    HIPTRY(s.group.alloc(&dHead, size_t(kRdKL) * NJ));
+    HIPTRY(s.group.alloc(&dTot, size_t(kRdKL) * NJ));
+    HIPTRY(s.group.alloc(&dChoice, NJ));
+    HIPTRY(s.group.alloc(&dBudget, NJ));
+    HIPTRY(s.group.alloc(&dCodes, 16 * JF));
+    HIPTRY(s.group.alloc(&dBits, JF));
     return hipSuccess;
 }
 
 // S1 over every stream-frame; the budgets
-DcsStatus EncRun::rd93Analyse()
+DcsStatus Enc93RdFamily::analyse()
 {
     const uint16_t version = jobs.sets[0].formatVersion;        // (one per call: dcs_encode93_rd_streams has one set)
     floorRd.resize(jobs.nSets);
     for (uint32_t k = 0 ; k < jobs.nSets ; ++k)
         floorRd[k] = floorE93Rd(jobs.sets[k].maximumQuantizationError);
-    budgetsRd();
-    ENCCHK(hipMemcpyAsync(cb.r93.dR, &encTabs93Rd(version), sizeof(EncRdTabs), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemcpyAsync(cb.r93.dFloor, floorRd.data(), sizeof(unsigned long long) * floorRd.size(), hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemsetAsync(cb.r93.dD0, 0, sizeof(unsigned long long) * 16 * in.nStreams, st));
-    hipLaunchKernelGGL(enc93RdItemKernel, dim3(F), dim3(256), 0, st, cb.dT, cb.r93.dR, rd93M0(version), cb.dSpec, cb.dFS, cb.r93.dItems,
-                       cb.r93.dRecs, cb.r93.dD0);
+    budgets();
+    ENCCHK(hipMemcpyAsync(dR, &encTabs93Rd(version), sizeof(EncRdTabs), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dFloor, floorRd.data(), sizeof(unsigned long long) * floorRd.size(), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemsetAsync(dD0, 0, sizeof(unsigned long long) * 16 * in.nStreams, st));
+    hipLaunchKernelGGL(enc93RdItemKernel, dim3(s.F), dim3(256), 0, st, cb.dT, dR, rd93M0(version), cb.dSpec, cb.dFS, dItems, dRecs, dD0);
     return DCS_OK;
 }
 
-// S2 to S5 for the n jobs (JF job-frames) of a group from job j0; the choices are on the host after runGroup's wait
-DcsStatus EncRun::rd93RunGroup(uint32_t j0, uint32_t n, uint32_t JF)
+// S2 to S5 for the n jobs (JF job-frames) of a group from job j0; the choices are on the host after the group's wait
+DcsStatus Enc93RdFamily::runGroup(uint32_t j0, uint32_t n, uint32_t JF)
 {
     const uint32_t chunks = (JF + kRd93ChunkFrames - 1) / kRd93ChunkFrames;
-    ENCCHK(hipMemcpyAsync(gb.r93.dBudget, budgetRd.data() + j0, sizeof(long long) * n, hipMemcpyHostToDevice, st));
-    ENCCHK(hipMemsetAsync(gb.r93.dProxyJ, 0, sizeof(unsigned long long) * kRd93ProxyPerJob * n, st));
-    ENCCHK(hipMemsetAsync(gb.r93.dProxyB, 0, sizeof(uint32_t) * kRd93ProxyPerJob * n, st));
-    ENCCHK(hipMemsetAsync(gb.r93.dTot, 0, sizeof(Enc93RdTot) * kRdKL * n, st));
-    hipLaunchKernelGGL(enc93RdProxyKernel, dim3(kRd93ProxyPerJob / 256, chunks), dim3(256), 0, st, cb.r93.dR, cb.r93.dItems, cb.r93.dFloor,
-                       gb.dFJ, gb.dJobs, JF, gb.r93.dProxyJ, gb.r93.dProxyB);
-    hipLaunchKernelGGL(enc93RdHeaderKernel, dim3(n), dim3(64), 0, st, gb.r93.dProxyJ, gb.r93.dProxyB, cb.r93.dD0, gb.dJobs, gb.r93.dHead);
-    hipLaunchKernelGGL(enc93RdTrellisKernel<false>, dim3(chunks, kRdKL), dim3(256), 0, st, cb.r93.dR, cb.r93.dItems, cb.r93.dRecs,
-                       cb.r93.dFloor, gb.dFJ, gb.dJobs, JF, gb.r93.dHead, static_cast<const Enc93RdChoice *>(nullptr), gb.r93.dTot,
+    ENCTRY(uploadBudgets(j0, n));
+    ENCCHK(hipMemsetAsync(dProxyJ, 0, sizeof(unsigned long long) * kRd93ProxyPerJob * n, st));
+    ENCCHK(hipMemsetAsync(dProxyB, 0, sizeof(uint32_t) * kRd93ProxyPerJob * n, st));
+    ENCCHK(hipMemsetAsync(dTot, 0, sizeof(Enc93RdTot) * kRdKL * n, st));
+    hipLaunchKernelGGL(enc93RdProxyKernel, dim3(kRd93ProxyPerJob / 256, chunks), dim3(256), 0, st, dR, dItems, dFloor,
+                       gb.dFJ, gb.dJobs, JF, dProxyJ, dProxyB);
+    hipLaunchKernelGGL(enc93RdHeaderKernel, dim3(n), dim3(64), 0, st, dProxyJ, dProxyB, dD0, gb.dJobs, dHead);
+    hipLaunchKernelGGL(enc93RdTrellisKernel<false>, dim3(chunks, kRdKL), dim3(256), 0, st, dR, dItems, dRecs,
+                       dFloor, gb.dFJ, gb.dJobs, JF, dHead, static_cast<const Enc93RdChoice *>(nullptr), dTot,
                        static_cast<uint8_t *>(nullptr), static_cast<uint32_t *>(nullptr));
-    hipLaunchKernelGGL(enc93RdChooseKernel, dim3((n + 63) / 64), dim3(64), 0, st, gb.r93.dTot, gb.r93.dHead, cb.r93.dD0, gb.dJobs,
-                       gb.r93.dBudget, n, gb.r93.dChoice);
-    ENCCHK(hipMemcpyAsync(choiceRd93.data() + j0, gb.r93.dChoice, sizeof(Enc93RdChoice) * n, hipMemcpyDeviceToHost, st));
+    launchChoose(n);
+    return fetchChoice(j0, n);
+}
+
+void Enc93RdFamily::launchChoose(uint32_t n)
+{
+    hipLaunchKernelGGL(enc93RdChooseKernel, dim3((n + 63) / 64), dim3(64), 0, st, dTot, dHead, dD0, gb.dJobs, dBudget, n, dChoice);
+}
+
+DcsStatus Enc93RdFamily::fetchChoice(uint32_t j0, uint32_t n)
+{
+    ENCCHK(hipMemcpyAsync(choice.data() + j0, dChoice, sizeof(Enc93RdChoice) * n, hipMemcpyDeviceToHost, st));
     return DCS_OK;
+}
+
+// a job of the S family: Type 0, its header's band count, 18 bytes and the frames' bits
+void Enc93RdFamily::sizeJobs(uint32_t j0, uint32_t n)
+{
+    for (uint32_t j = j0 ; j < j0 + n ; ++j)
+    {
+        s.win[j] = 0;
+        s.keep[j] = choice[j].numBands;
+        s.size[j] = 18 + (choice[j].frameBits + 7) / 8;
+    }
 }
 
 // S6 to S8 for the resident group: the chosen lambda's trellises with their paths, the frames' offsets, header and pack
-DcsStatus EncRun::rd93PackGroup(uint32_t n, uint32_t JF)
+DcsStatus Enc93RdFamily::packGroup(uint32_t n, uint32_t JF)
 {
     const uint32_t chunks = (JF + kRd93ChunkFrames - 1) / kRd93ChunkFrames;
     const uint32_t m0 = rd93M0(jobs.sets[0].formatVersion);
-    hipLaunchKernelGGL(enc93RdTrellisKernel<true>, dim3(chunks), dim3(256), 0, st, cb.r93.dR, cb.r93.dItems, cb.r93.dRecs, cb.r93.dFloor,
-                       gb.dFJ, gb.dJobs, JF, static_cast<const Enc93RdHead *>(nullptr), gb.r93.dChoice, static_cast<Enc93RdTot *>(nullptr),
-                       gb.r93.dCodes, gb.r93.dBits);
-    hipLaunchKernelGGL(encRdOffsetKernel, dim3(n), dim3(256), 0, st, gb.dJobs, gb.r93.dBits, gb.dFrameOff);
-    hipLaunchKernelGGL(enc93RdHeadKernel, dim3((n + 63) / 64), dim3(64), 0, st, gb.dJobs, gb.r93.dChoice, gb.dOutOff, n, dW);
-    hipLaunchKernelGGL(enc93RdPackKernel, dim3(JF), dim3(64), 0, st, cb.dT, cb.r93.dR, m0, cb.dSpec, cb.r93.dRecs, gb.dFJ, gb.dJobs,
-                       gb.r93.dChoice, gb.r93.dCodes, gb.dFrameOff, gb.dOutOff, dW);
+    hipLaunchKernelGGL(enc93RdTrellisKernel<true>, dim3(chunks), dim3(256), 0, st, dR, dItems, dRecs, dFloor,
+                       gb.dFJ, gb.dJobs, JF, static_cast<const Enc93RdHead *>(nullptr), dChoice, static_cast<Enc93RdTot *>(nullptr),
+                       dCodes, dBits);
+    hipLaunchKernelGGL(encRdOffsetKernel, dim3(n), dim3(256), 0, st, gb.dJobs, dBits, gb.dFrameOff);
+    hipLaunchKernelGGL(enc93RdHeadKernel, dim3((n + 63) / 64), dim3(64), 0, st, gb.dJobs, dChoice, gb.dOutOff, n, s.dW);
+    hipLaunchKernelGGL(enc93RdPackKernel, dim3(JF), dim3(64), 0, st, cb.dT, dR, m0, cb.dSpec, dRecs, gb.dFJ, gb.dJobs,
+                       dChoice, dCodes, gb.dFrameOff, gb.dOutOff, s.dW);
     return DCS_OK;
+}
+
+void Enc93RdFamily::writeInfo(uint32_t j)
+{
+    const Enc93RdChoice &c = choice[j];
+    if (to.infoRd != nullptr)
+        to.infoRd[j] = DcsEncodeRdInfo{ 0, 0, c.ladderIndex, c.numBands, c.frameBits,
+                                        static_cast<uint64_t>(std::max<long long>(budgetRd[j], 0)), c.sumD, c.fits, 0 };
 }
 
 }  // namespace
@@ -2839,160 +1878,105 @@ extern "C" DcsStatus dcs_encode93_rd_streams(DcsCtx *ctx, const float *pcm, cons
                                              const DcsEncodeParams *params, const uint32_t *budgetBytes, uint8_t *out, uint64_t outCap,
                                              uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
-        return DCS_ERR_INVALID_ARG;
-    if (!paramsValid93Rd(params))
-    {
-        dcsCtxSetError(ctx, "dcs_encode93_rd_streams: formatVersion 0x9301 or 0x9302, streamFormatType 0 or -1 (OS93 Type 0; Type 1 is "
-                            "not searched), targetBitRate 1..100 000 000 and finite parameters");
-        return DCS_ERR_INVALID_ARG;
-    }
-    EncInput in;
-    in.sampleOffsets = sampleOffsets;
-    in.nStreams = nStreams;
-    in.hostPcm = pcm;
-    std::vector<DcsSweepJob> list(nStreams);
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-        list[i] = DcsSweepJob{ i, 0 };
-    EncJobs js{ params, 1, list.data(), nStreams, true };
-    js.rd93 = true;
-    js.budgetBytes = budgetBytes;
-    EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
-    to.infoRd = infoRd;
-    return EncRun(ctx, in, js, to, EncSweep()).run();
+    return encodeSearched(ctx, "dcs_encode93_rd_streams", pcm, sampleOffsets, nStreams, params, true, budgetBytes, nullptr, out, outCap,
+                          outOffsets, info, infoRd);
 }
 
-// ------------------------------------------------------- a set of streams to one byte budget: kernels and driver (dcs_encode_rd_fit.hip.h)
+// --------------------------------------- a set of streams to one byte budget: kernels (dcs_encode_rd_fit.hip.h) and EncFitRun
 // (behind every other kernel of the unit once more)
 
 #include "dcs_encode_rd_fit.hip.h"
 
 namespace {
 
-DcsStatus EncRun::fitAllocCall()
+DcsStatus EncFitRun::allocCall()
 {
-    ENCCHK(call.alloc(&cb.fit.dCurveSize, size_t(kFitMaxPoints) * jobs.n));
-    ENCCHK(call.alloc(&cb.fit.dCurveD, size_t(kFitMaxPoints) * jobs.n));
-    ENCCHK(call.alloc(&cb.fit.dOff, size_t(jobs.n) + 1));
+    ENCCHK(s.call.alloc(&dCurveSize, size_t(kFitMaxPoints) * jobs.n));
+    ENCCHK(s.call.alloc(&dCurveD, size_t(kFitMaxPoints) * jobs.n));
+    ENCCHK(s.call.alloc(&dOff, size_t(jobs.n) + 1));
     if (jobs.fit->capBytes != nullptr)
-        ENCCHK(call.alloc(&cb.fit.dCap, jobs.n));
-    ENCCHK(call.alloc(&cb.fit.dAllot, jobs.n));
-    ENCCHK(call.alloc(&cb.fit.dFit, 1));
+        ENCCHK(s.call.alloc(&dCap, jobs.n));
+    ENCCHK(s.call.alloc(&dAllot, jobs.n));
+    ENCCHK(s.call.alloc(&dFit, 1));
     return DCS_OK;
 }
 
 // F1 behind R2 or S4 of the resident group (n jobs from job j0): its jobs' candidates into the call's curve table
-DcsStatus EncRun::fitCurves(uint32_t j0, uint32_t n)
+void EncRdFamily::launchCurves(uint32_t n, unsigned long long *dSize, unsigned long long *dD)
 {
-    unsigned long long *dSize = cb.fit.dCurveSize + size_t(kFitMaxPoints) * j0, *dD = cb.fit.dCurveD + size_t(kFitMaxPoints) * j0;
-    if (jobs.rd)
-        hipLaunchKernelGGL(encRdCurveKernel, dim3(n), dim3(256), 0, st, gb.rd.dTot, cb.rd.dD0, gb.dJobs, cb.dSets, dSize, dD);
-    else
-        hipLaunchKernelGGL(enc93RdCurveKernel, dim3((n * kFitMaxPoints + 63) / 64), dim3(64), 0, st, gb.r93.dTot, gb.r93.dHead, cb.r93.dD0,
-                           gb.dJobs, n, dSize, dD);
-    return DCS_OK;
+    hipLaunchKernelGGL(encRdCurveKernel, dim3(n), dim3(256), 0, st, dTot, dD0, gb.dJobs, cb.dSets, dSize, dD);
+}
+
+void Enc93RdFamily::launchCurves(uint32_t n, unsigned long long *dSize, unsigned long long *dD)
+{
+    hipLaunchKernelGGL(enc93RdCurveKernel, dim3((n * kFitMaxPoints + 63) / 64), dim3(64), 0, st, dTot, dHead, dD0, gb.dJobs, n, dSize, dD);
+}
+
+void EncFitRun::launchCurves(uint32_t j0, uint32_t n)
+{
+    s.searched->launchCurves(n, dCurveSize + size_t(kFitMaxPoints) * j0, dCurveD + size_t(kFitMaxPoints) * j0);
 }
 
 // F2 to F4 over all jobs, and a wait: the allotments and the record are on the host after it, the curves never.  A job's
 // budget is its allotment, or its cap where even its smallest candidate is beyond that (a pinned job: fits = 0).
-DcsStatus EncRun::fitAllot()
+DcsStatus EncFitRun::allot()
 {
     const EncFit &fit = *jobs.fit;
     std::vector<unsigned long long> off(size_t(jobs.n) + 1);
     for (uint32_t j = 0 ; j <= jobs.n ; ++j)
         off[j] = static_cast<unsigned long long>(kFitMaxPoints) * j;
-    ENCCHK(hipMemcpyAsync(cb.fit.dOff, off.data(), sizeof(unsigned long long) * off.size(), hipMemcpyHostToDevice, st));
+    ENCCHK(hipMemcpyAsync(dOff, off.data(), sizeof(unsigned long long) * off.size(), hipMemcpyHostToDevice, st));
     if (fit.capBytes != nullptr)
-        ENCCHK(hipMemcpyAsync(cb.fit.dCap, fit.capBytes, sizeof(uint32_t) * jobs.n, hipMemcpyHostToDevice, st));
-    ENCTRY(fitAllotDevice(ctx, call, cb.fit.dCurveSize, cb.fit.dCurveD, cb.fit.dOff, jobs.n, size_t(kFitMaxPoints) * jobs.n, fit.totalBytes,
-                          cb.fit.dCap, cb.fit.dAllot, cb.fit.dFit));
-    allot.resize(jobs.n);
-    ENCCHK(hipMemcpyAsync(allot.data(), cb.fit.dAllot, sizeof(uint32_t) * jobs.n, hipMemcpyDeviceToHost, st));
-    ENCCHK(hipMemcpyAsync(&fitRec, cb.fit.dFit, sizeof(fitRec), hipMemcpyDeviceToHost, st));
+        ENCCHK(hipMemcpyAsync(dCap, fit.capBytes, sizeof(uint32_t) * jobs.n, hipMemcpyHostToDevice, st));
+    ENCTRY(fitAllotDevice(ctx, s.call, dCurveSize, dCurveD, dOff, jobs.n, size_t(kFitMaxPoints) * jobs.n, fit.totalBytes, dCap, dAllot, dFit));
+    allotBytes.resize(jobs.n);
+    ENCCHK(hipMemcpyAsync(allotBytes.data(), dAllot, sizeof(uint32_t) * jobs.n, hipMemcpyDeviceToHost, st));
+    ENCCHK(hipMemcpyAsync(&rec, dFit, sizeof(rec), hipMemcpyDeviceToHost, st));
     ENCCHK(hipStreamSynchronize(st));
     for (uint32_t j = 0 ; j < jobs.n ; ++j)
     {
-        const uint32_t b = fit.capBytes != nullptr ? std::min(allot[j], fit.capBytes[j]) : allot[j];
-        budgetRd[j] = b >= 18 ? (static_cast<long long>(b) - 18) * 8 : -1;
-        size[j] = allot[j];
+        const uint32_t b = fit.capBytes != nullptr ? std::min(allotBytes[j], fit.capBytes[j]) : allotBytes[j];
+        s.searched->budgetRd[j] = b >= 18 ? (static_cast<long long>(b) - 18) * 8 : -1;
+        s.size[j] = allotBytes[j];
     }
     if (fit.info != nullptr)
-        *fit.info = fitRec;
+        *fit.info = rec;
+    allotted = true;
     return DCS_OK;
 }
 
 // R3 or S5 again for group g, still resident, with the allotments as budgets; the choices are on the host after the wait
-DcsStatus EncRun::fitRechoose(uint32_t g)
+DcsStatus EncFitRun::rechoose(uint32_t g)
 {
-    const uint32_t j0 = groupFirst[g], n = groupFirst[g + 1] - j0;
-    if (jobs.rd)
-    {
-        ENCCHK(hipMemcpyAsync(gb.rd.dBudget, budgetRd.data() + j0, sizeof(long long) * n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(encRdChooseKernel, dim3(n), dim3(256), 0, st, gb.rd.dTot, cb.rd.dD0, gb.dJobs, cb.dSets, gb.rd.dBudget, gb.rd.dChoice);
-        ENCCHK(hipMemcpyAsync(choiceRd.data() + j0, gb.rd.dChoice, sizeof(EncRdChoice) * n, hipMemcpyDeviceToHost, st));
-    }
-    else
-    {
-        ENCCHK(hipMemcpyAsync(gb.r93.dBudget, budgetRd.data() + j0, sizeof(long long) * n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(enc93RdChooseKernel, dim3((n + 63) / 64), dim3(64), 0, st, gb.r93.dTot, gb.r93.dHead, cb.r93.dD0, gb.dJobs,
-                           gb.r93.dBudget, n, gb.r93.dChoice);
-        ENCCHK(hipMemcpyAsync(choiceRd93.data() + j0, gb.r93.dChoice, sizeof(Enc93RdChoice) * n, hipMemcpyDeviceToHost, st));
-    }
+    const uint32_t j0 = s.groupFirst[g], n = s.groupFirst[g + 1] - j0;
+    ENCTRY(s.searched->chooseAgain(j0, n));
     ENCCHK(hipGetLastError());
     ENCCHK(hipStreamSynchronize(st));
-    sizesRd(j0, n);
+    s.searched->sizeJobs(j0, n);
     return DCS_OK;
 }
 
-// group g has chosen with its allotments: every stream is as long as its allotment (a hull vertex is a candidate's size),
-// on which the output offsets already rest; then its jobs' info and infoRd
-DcsStatus EncRun::fitReport(uint32_t g)
+// job j's group has chosen with its allotments: its stream is as long as its allotment (a hull vertex is a candidate's
+// size), on which the output offsets already rest
+DcsStatus EncFitRun::report(uint32_t j)
 {
-    for (uint32_t j = groupFirst[g] ; j < groupFirst[g + 1] ; ++j)
+    if (s.size[j] != allotBytes[j])
     {
-        if (size[j] != allot[j])
-        {
-            dcsCtxSetError(ctx, ("job " + std::to_string(j) + ": chose " + std::to_string(size[j]) + " bytes for an allotment of "
-                                 + std::to_string(allot[j])).c_str());
-            return DCS_ERR_HIP;
-        }
-        writeInfo(j);
+        dcsCtxSetError(ctx, ("job " + std::to_string(j) + ": chose " + std::to_string(s.size[j]) + " bytes for an allotment of "
+                             + std::to_string(allotBytes[j])).c_str());
+        return DCS_ERR_HIP;
     }
     return DCS_OK;
 }
 
 // the record once every stream is written: sqErr is the sum of what the streams' records say
-void EncRun::fitRecord()
+void EncFitRun::record()
 {
-    fitRec.sqErr = 0;
+    rec.sqErr = 0;
     for (uint32_t j = 0 ; j < jobs.n ; ++j)
-        fitRec.sqErr += jobs.rd ? choiceRd[j].sumD : choiceRd93[j].sumD;
+        rec.sqErr += s.searched->sumD(j);
     if (jobs.fit->info != nullptr)
-        *jobs.fit->info = fitRec;
-}
-
-// dcs_encode_rd_fit and dcs_encode93_rd_fit behind their parameter checks
-DcsStatus encodeRdFit(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams, const DcsEncodeParams *params,
-                      bool os93, const EncFit &fit, const EncOutput &to)
-{
-    if (fit.info != nullptr)
-    {
-        *fit.info = DcsEncodeRdFitInfo{};
-        fit.info->totalBytes = fit.totalBytes;
-        fit.info->fits = 1;
-    }
-    EncInput in;
-    in.sampleOffsets = sampleOffsets;
-    in.nStreams = nStreams;
-    in.hostPcm = pcm;
-    std::vector<DcsSweepJob> list(nStreams);
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-        list[i] = DcsSweepJob{ i, 0 };
-    EncJobs js{ params, 1, list.data(), nStreams, os93 };
-    js.rd = !os93;
-    js.rd93 = os93;
-    js.fit = &fit;
-    return EncRun(ctx, in, js, to, EncSweep()).run();
+        *jobs.fit->info = rec;
 }
 
 }  // namespace
@@ -3002,17 +1986,9 @@ extern "C" DcsStatus dcs_encode_rd_fit(DcsCtx *ctx, const float *pcm, const uint
                                        uint64_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd,
                                        DcsEncodeRdFitInfo *fit)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
-        return DCS_ERR_INVALID_ARG;
-    if (!paramsValidRd(params))
-    {
-        dcsCtxSetError(ctx, "dcs_encode_rd_fit: formatVersion 0x9400, streamFormatType 0, 1 or -1, streamFormatSubType 0, 3 or -1, "
-                            "targetBitRate 1..100 000 000 and finite parameters");
-        return DCS_ERR_INVALID_ARG;
-    }
-    EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
-    to.infoRd = infoRd;
-    return encodeRdFit(ctx, pcm, sampleOffsets, nStreams, params, false, EncFit{ totalBytes, capBytes, fit }, to);
+    const EncFit f{ totalBytes, capBytes, fit };
+    return encodeSearched(ctx, "dcs_encode_rd_fit", pcm, sampleOffsets, nStreams, params, false, nullptr, &f, out, outCap, outOffsets,
+                          info, infoRd);
 }
 
 extern "C" DcsStatus dcs_encode93_rd_fit(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
@@ -3020,17 +1996,9 @@ extern "C" DcsStatus dcs_encode93_rd_fit(DcsCtx *ctx, const float *pcm, const ui
                                          uint64_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd,
                                          DcsEncodeRdFitInfo *fit)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
-        return DCS_ERR_INVALID_ARG;
-    if (!paramsValid93Rd(params))
-    {
-        dcsCtxSetError(ctx, "dcs_encode93_rd_fit: formatVersion 0x9301 or 0x9302, streamFormatType 0 or -1 (OS93 Type 0; Type 1 is "
-                            "not searched), targetBitRate 1..100 000 000 and finite parameters");
-        return DCS_ERR_INVALID_ARG;
-    }
-    EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
-    to.infoRd = infoRd;
-    return encodeRdFit(ctx, pcm, sampleOffsets, nStreams, params, true, EncFit{ totalBytes, capBytes, fit }, to);
+    const EncFit f{ totalBytes, capBytes, fit };
+    return encodeSearched(ctx, "dcs_encode93_rd_fit", pcm, sampleOffsets, nStreams, params, true, nullptr, &f, out, outCap, outOffsets,
+                          info, infoRd);
 }
 
 extern "C" DcsStatus dcs_encode_rd_allot(DcsCtx *ctx, const uint64_t *sizeBytes, const uint64_t *sqErr, const uint64_t *curveOffsets,

@@ -7,7 +7,7 @@
 // frames are independent.  After one f32 multiply and one roundf per coefficient (the targets) every decision is an integer
 // one, restated in tests/enc93rd_ref.py.
 //
-// These are the kernels of a family of EncRun's (dcs_encode.hip), beside the E, O, A and R stages:
+// These are the kernels of a family of EncRun's (Enc93RdFamily, dcs_encode_run.hip.h), beside the E, O, A and R stages:
 //
 //   E1  encAnalyseKernel       the front end, unchanged (its spectrum is all that is read of it), once per stream
 //   S1  enc93RdItemKernel      a block per STREAM-frame, the frame's targets and their nearest values in LDS: per band, scale

@@ -6,7 +6,7 @@
 // quarter-octave scale code s and one index per pair into the 2^w points of kPair93a.  After one f32 multiply and one
 // roundf per coefficient (the targets) every decision is an integer one, restated in tests/enc93a_ref.py.
 //
-// These are the kernels of a family of EncRun's (dcs_encode.hip), beside the OS93 (O3-O5) and the 1994+ (E3-E5) stages: a
+// These are the kernels of a family of EncRun's (Enc93aFamily, dcs_encode_run.hip.h), beside the OS93 (O3-O5) and the 1994+ (E3-E5) stages: a
 // job whose set asks for (0x9301, Type 1) runs them, a job of the same call whose set asks for Type 0 runs the O stages.
 //
 //   E1  encAnalyseKernel  the OS93 front end, unchanged (its spectrum is all that is read of it), once per stream

@@ -5,7 +5,7 @@
 // outside is the decoder (DecoderImpl94, unpack94 in dcs_kernels.hip.h).  After one f32 multiply and one roundf per
 // coefficient (the targets) every decision is an integer one, restated in tests/enc94rd_ref.py.
 //
-// These are the kernels of a family of EncRun's (dcs_encode.hip), beside the E, O and A stages:
+// These are the kernels of a family of EncRun's (EncRdFamily, dcs_encode_run.hip.h), beside the E, O and A stages:
 //
 //   E1  encAnalyseKernel     the 1994+ front end, unchanged (its spectrum is all that is read of it), once per stream
 //   R1  encRdItemKernel      a block per STREAM-frame, the frame's targets and their nearest sample values in LDS: for every

@@ -133,6 +133,18 @@ def test_calling_rules(gpu_ctx):
     want, _, _ = gpu_ctx.encode93_rd_streams([ok, C.SIGNALS["noise_m40"]])
     assert [int(v) for v in out_offs] == [0, len(want[0]), len(want[0]) + len(want[1])] and not out.any()
     gpu_ctx.encode93_rd_streams([np.array([1.0, -1.0] * 300, np.float32)])      # exactly 1.0 and -1.0 are in range
+    # the null arguments the entry refuses, and the whole of its parameter message
+    one = np.zeros(240, np.float32)
+    x, offs = _encode_input([one])
+    out_offs = np.zeros(2, np.uint64)
+    entry = gpu_ctx.L.dcs_encode93_rd_streams
+    assert entry(gpu_ctx.h, _ptr(x), None, 1, ctypes.byref(p), None, _ptr(out), 8, _ptr(out_offs), None, None) == -1
+    assert entry(gpu_ctx.h, None, _ptr(offs), 1, ctypes.byref(p), None, _ptr(out), 8, _ptr(out_offs), None, None) == -1
+    assert entry(None, _ptr(x), _ptr(offs), 1, ctypes.byref(p), None, _ptr(out), 8, _ptr(out_offs), None, None) == -1
+    with pytest.raises(D.DcsError) as e:
+        gpu_ctx.encode93_rd_streams([one], D.OS93B, None, targetBitRate=0)
+    assert str(e.value) == ("libdcs_hip status -1 dcs_encode93_rd_streams: formatVersion 0x9301 or 0x9302, streamFormatType 0 or -1 "
+                            "(OS93 Type 0; Type 1 is not searched), targetBitRate 1..100 000 000 and finite parameters")
 
 
 def _errors(gpu_ctx, os_, x, streams):

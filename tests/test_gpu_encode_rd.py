@@ -140,3 +140,15 @@ def test_calling_rules(gpu_ctx):
         assert wild["sqErr"] <= one["sqErr"] and one["fits"]
     assert gpu_ctx.encode_rd_streams([x], D.FMT_94_T0_S3, 600)[0][0][5:] == gpu_ctx.encode_rd_streams([x], D.FMT_94_T0, 600)[0][0][5:]
     gpu_ctx.encode_rd_streams([np.array([1.0, -1.0] * 300, np.float32)])        # exactly 1.0 and -1.0 are in range
+    # the null arguments the entry refuses, and the whole of its parameter message
+    one = np.zeros(240, np.float32)
+    x, offs = _encode_input([one])
+    out_offs = np.zeros(2, np.uint64)
+    entry = gpu_ctx.L.dcs_encode_rd_streams
+    assert entry(gpu_ctx.h, _ptr(x), None, 1, ctypes.byref(p), None, _ptr(out), 8, _ptr(out_offs), None, None) == -1
+    assert entry(gpu_ctx.h, None, _ptr(offs), 1, ctypes.byref(p), None, _ptr(out), 8, _ptr(out_offs), None, None) == -1
+    assert entry(None, _ptr(x), _ptr(offs), 1, ctypes.byref(p), None, _ptr(out), 8, _ptr(out_offs), None, None) == -1
+    with pytest.raises(D.DcsError) as e:
+        gpu_ctx.encode_rd_streams([one], None, None, targetBitRate=0)
+    assert str(e.value) == ("libdcs_hip status -1 dcs_encode_rd_streams: formatVersion 0x9400, streamFormatType 0, 1 or -1, "
+                            "streamFormatSubType 0, 3 or -1, targetBitRate 1..100 000 000 and finite parameters")

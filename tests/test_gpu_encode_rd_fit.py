@@ -178,3 +178,20 @@ def test_calling_rules(gpu_ctx):
         assert [int(v) for v in out_offs] == [0, len(want[0][0]), len(want[0][0]) + len(want[0][1])]
         assert not out.any() and not info.tobytes().strip(b"\0") and not infr.tobytes().strip(b"\0")
         assert int(fit[0]["usedBytes"]) == int(out_offs[2]) == int(want[3]["usedBytes"])
+    # the null arguments the entries refuse, and the whole of their parameter messages
+    one = np.zeros(240, np.float32)
+    x, offs = _encode_input([one])
+    out_offs = np.zeros(2, np.uint64)
+    for entry, p in [(gpu_ctx.L.dcs_encode_rd_fit, D.encode_params(None)),
+                     (gpu_ctx.L.dcs_encode93_rd_fit, D.encode_params(None, formatVersion=0x9302, streamFormatType=0, streamFormatSubType=0))]:
+        assert entry(gpu_ctx.h, _ptr(x), None, 1, ctypes.byref(p), 700, None, _ptr(out), 8, _ptr(out_offs), None, None, None) == -1
+        assert entry(gpu_ctx.h, None, _ptr(offs), 1, ctypes.byref(p), 700, None, _ptr(out), 8, _ptr(out_offs), None, None, None) == -1
+        assert entry(None, _ptr(x), _ptr(offs), 1, ctypes.byref(p), 700, None, _ptr(out), 8, _ptr(out_offs), None, None, None) == -1
+    with pytest.raises(D.DcsError) as e:
+        gpu_ctx.encode_rd_fit([one], 1000, targetBitRate=0)
+    assert str(e.value) == ("libdcs_hip status -1 dcs_encode_rd_fit: formatVersion 0x9400, streamFormatType 0, 1 or -1, "
+                            "streamFormatSubType 0, 3 or -1, targetBitRate 1..100 000 000 and finite parameters")
+    with pytest.raises(D.DcsError) as e:
+        gpu_ctx.encode93_rd_fit([one], 1000, targetBitRate=0)
+    assert str(e.value) == ("libdcs_hip status -1 dcs_encode93_rd_fit: formatVersion 0x9301 or 0x9302, streamFormatType 0 or -1 "
+                            "(OS93 Type 0; Type 1 is not searched), targetBitRate 1..100 000 000 and finite parameters")
