@@ -18,7 +18,7 @@ from .api import (  # noqa: F401
     encode93_params, encode93_bound, encode93_header, ENCODE93A_INFO_DTYPE, encode93a_bound, ENCODE_RD_INFO_DTYPE, encode_rd_bound, encode93_rd_bound, encode93a_params,
     ENCODE_RD_FIT_INFO_DTYPE, encode_rd_allot,
     SWEEP_RESULT_DTYPE, SWEEP_JOB_DTYPE, SWEEP_MEASURE, sweep_sq_err, encode_sweep_group_frames, encode_fit_choose,
-    TRANSCODE_COPIED, TRANSCODE_REENCODED, TRANSCODE_REENCODE_ALL, TRANSCODE_INFO_DTYPE, TRANSCODE_OS, transcode_params, transcode_plan,
+    TRANSCODE_COPIED, TRANSCODE_REENCODED, TRANSCODE_REENCODE_ALL, TRANSCODE_INFO_DTYPE, TRANSCODE_OS, transcode_params, transcode_plan, transcode_plan_budget, Budget, FILES_REENCODE_ALL,
     ResampleFilter, RESAMPLE_AT_UNITY, resample_filter_default, resample_count,
     OUT_SEQUENCE, RATE_INFO_DTYPE, resample_out_count, resample_out_walk,
     WavInfo, ENCODE_FILE_INFO_DTYPE, WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32, WAV_F64, WAV_IMA, FILE_WAV, FILE_DCSA_COPY,

@@ -91,6 +91,13 @@ class EncodeParams(ctypes.Structure):
                 ("minimumDynamicRange", ctypes.c_float), ("maximumQuantizationError", ctypes.c_float)]
 
 
+class Budget(ctypes.Structure):
+    """DcsBudget: what the budget calls on any source hold their jobs to (_budget builds one)"""
+    _fields_ = [("budgetBytes", ctypes.c_void_p), ("totalBytes", ctypes.c_uint64), ("capBytes", ctypes.c_void_p),
+                ("shared", ctypes.c_uint32), ("fit", ctypes.c_void_p)]
+
+
+FILES_REENCODE_ALL = 0x100
 ENCODE_INFO_DTYPE = np.dtype([("formatType", "<i4"), ("formatSubType", "<i4"), ("nFrames", "<i4"), ("nBytes", "<i4"),
                               ("bandsToKeep", "<i4")])
 # the layouts encode_streams can be asked for: (type, sub-type); None = the reference's wildcard (-1, -1)
@@ -245,6 +252,8 @@ EXPORTS = [
     "dcs_level_gain", "dcs_level_streams", "dcs_resample_streams_level", "dcs_encode_streams_at_level", "dcs_encode_files_level",
     "dcs_resample_out_count", "dcs_resample_out_walk", "dcs_resample_out_streams", "dcs_decode_streams_at",
     "dcs_flac_write_samples_check", "dcs_flac_write_samples", "dcs_decode_streams_flac_at",
+    "dcs_encode_streams_at_budget", "dcs_transcode_plan_budget", "dcs_transcode_streams_budget", "dcs_encode_files_plan_budget",
+    "dcs_encode_files_budget",
 ]
 
 
@@ -593,6 +602,20 @@ def load_library():
         L.dcs_encode93_rd_fit.argtypes = L.dcs_encode_rd_fit.argtypes
         L.dcs_encode_rd_allot.restype = i32
         L.dcs_encode_rd_allot.argtypes = [vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, vp]
+    if hasattr(L, "dcs_encode_files_budget"):   # (as above: a build from before the budget calls took other sources)
+        L.dcs_encode_streams_at_budget.restype = i32
+        L.dcs_encode_streams_at_budget.argtypes = [vp, vp, vp, u32, vp, vp, ctypes.POINTER(ResampleFilter), u32, ctypes.POINTER(EncodeParams),
+                                                   ctypes.POINTER(Budget), vp, sz, vp, vp, vp, vp, u32, vp]
+        L.dcs_transcode_plan_budget.restype = i32
+        L.dcs_transcode_plan_budget.argtypes = [vp, u32, ctypes.POINTER(EncodeParams), u32, ctypes.POINTER(Budget), vp, vp]
+        L.dcs_transcode_streams_budget.restype = i32
+        L.dcs_transcode_streams_budget.argtypes = [vp, vp, u32, ctypes.POINTER(EncodeParams), u32, ctypes.POINTER(Budget), vp, sz, vp, vp, vp]
+        L.dcs_encode_files_plan_budget.restype = i32
+        L.dcs_encode_files_plan_budget.argtypes = [vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32,
+                                                   ctypes.POINTER(Budget), vp, vp]
+        L.dcs_encode_files_budget.restype = i32
+        L.dcs_encode_files_budget.argtypes = [vp, vp, vp, u32, ctypes.POINTER(EncodeParams), ctypes.POINTER(ResampleFilter), u32,
+                                              ctypes.POINTER(Budget), vp, sz, vp, vp, vp, vp, u32, vp]
     L.dcs_encode93a_sweep.restype = i32
     L.dcs_encode93a_sweep.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, sz, vp]
     L.dcs_encode_sweep_group_frames.restype = None
@@ -996,6 +1019,38 @@ def transcode_plan(streams, os_list, version=0x9400, fmt=None, reencode_all=Fals
     action, bound = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64)
     _check(load_library().dcs_transcode_plan(refs, n, ctypes.byref(p), TRANSCODE_REENCODE_ALL if reencode_all else 0,
                                              _ptr(action), _ptr(bound)))
+    return action[:n], bound[:n]
+
+
+def _budget(n, budget, total, cap):
+    """the DcsBudget of n jobs: budget None, an int or a sequence = per job; total not None = the shared form, with cap None,
+    an int or a sequence.  -> (Budget, the ENCODE_RD_FIT_INFO_DTYPE array of one record it points to, what it keeps alive)"""
+    def per_job(v):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int64), (n,)).clip(0, 0xFFFFFFFF), dtype=np.uint32)
+    b = Budget()
+    fit = np.zeros(1, ENCODE_RD_FIT_INFO_DTYPE)
+    bud = per_job(budget) if budget is not None and n else None
+    caps = per_job(cap) if cap is not None and n else None
+    b.budgetBytes = bud.ctypes.data if bud is not None else None
+    b.capBytes = caps.ctypes.data if caps is not None else None
+    b.shared = 0 if total is None else 1
+    b.totalBytes = 0 if total is None else int(total)
+    b.fit = fit.ctypes.data
+    return b, fit, (bud, caps)
+
+
+def transcode_plan_budget(streams, os_list, version=0x9400, fmt=None, reencode_all=False, budget=None, total=None, cap=None,
+                          volume=0x67, level=0xFF, channel_volume=0xFF, **params):
+    """dcs_transcode_plan_budget (host only): transcode_plan under the copy rule of transcode_streams_budget -> (action per
+    stream, the bytes its output can take)"""
+    p = transcode_params(version, fmt, **params)
+    refs, keep = _transcode_refs(streams, os_list, volume, level, channel_volume)
+    n = len(keep) if streams else 0
+    b, _, alive = _budget(n, budget, total, cap)
+    action, bound = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64)
+    _check(load_library().dcs_transcode_plan_budget(refs, n, ctypes.byref(p), TRANSCODE_REENCODE_ALL if reencode_all else 0,
+                                                    ctypes.byref(b), _ptr(action), _ptr(bound)))
+    del alive
     return action[:n], bound[:n]
 
 
@@ -2060,6 +2115,93 @@ class Context:
         info = np.zeros(max(n, 1), TRANSCODE_INFO_DTYPE)
         _check(self.L.dcs_transcode_streams(self.h, refs, n, ctypes.byref(p), flags, _ptr(out), cap, _ptr(out_offs), _ptr(info)), self.h)
         return [out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n]
+
+    # ---- budgets from any source.  budget: None = the frame bits targetBitRate gives, an int or a sequence =
+    # the most bytes per job; total: not None selects the shared form, all jobs together at most `total` bytes, with cap None,
+    # an int or a sequence.  The shared form returns the ENCODE_RD_FIT_INFO_DTYPE record as well, as the last element.
+
+    def encode_streams_at_budget(self, pcm_list, rates, version=0x9400, fmt=None, budget=None, total=None, cap=None, channels=1,
+                                 filter=None, at_unity=False, level=None, **params):
+        """dcs_encode_streams_at_budget: encode_streams_at with the searched encoder (encode_rd_streams / encode93_rd_streams,
+        or encode_rd_fit / encode93_rd_fit with total) behind the level stage.  Returns (list of bytes, ENCODE_INFO_DTYPE
+        array, ENCODE_RD_INFO_DTYPE array[, LEVEL_INFO_DTYPE array with level][, the fit record with total])."""
+        p = transcode_params(version, fmt, **params)
+        pcm, offs = _encode_input(pcm_list)
+        n = len(offs) - 1
+        r, ch = _per_stream(rates, n, np.uint32, "rates"), _per_stream(channels, n, np.int32, "channel counts")
+        f, keep = _resample_filter(filter)
+        flags = RESAMPLE_AT_UNITY if at_unity else 0
+        bound = encode_rd_bound if version == 0x9400 else encode93_rd_bound
+        room = 0
+        for i in range(n):
+            m = _resample_bound(int(offs[i + 1] - offs[i]), int(r[i]), int(ch[i]), at_unity)
+            room += bound(m) or bound(65535 * 240)
+        b, fit, alive = _budget(n, budget, total, cap)
+        out = np.zeros(max(room, 1), np.uint8)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info, info_rd = np.zeros(max(n, 1), ENCODE_INFO_DTYPE), np.zeros(max(n, 1), ENCODE_RD_INFO_DTYPE)
+        lv, n_lv = _levels(level, n) if level is not None else (None, 0)
+        linfo = np.zeros(max(n, 1), LEVEL_INFO_DTYPE)
+        _check(self.L.dcs_encode_streams_at_budget(self.h, _ptr(pcm), _ptr(offs), n, _ptr(r), _ptr(ch), ctypes.byref(f) if f is not None else None,
+                                                   flags, ctypes.byref(p), ctypes.byref(b), _ptr(out), room, _ptr(out_offs), _ptr(info),
+                                                   _ptr(info_rd), lv, n_lv, _ptr(linfo) if level is not None else None), self.h)
+        del keep, alive
+        res = ([out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n], info_rd[:n])
+        return res + ((linfo[:n],) if level is not None else ()) + ((fit[0],) if total is not None else ())
+
+    def transcode_streams_budget(self, streams, os_list, version=0x9400, fmt=None, reencode_all=False, budget=None, total=None,
+                                 cap=None, volume=0x67, level=0xFF, channel_volume=0xFF, **params):
+        """dcs_transcode_streams_budget: transcode_streams with the searched encoder behind the decode; a source that fits the
+        target's family is still copied where it keeps to its own budget (or cap).  Returns (list of bytes,
+        TRANSCODE_INFO_DTYPE array, ENCODE_RD_INFO_DTYPE array[, the fit record with total])."""
+        p = transcode_params(version, fmt, **params)
+        flags = TRANSCODE_REENCODE_ALL if reencode_all else 0
+        refs, keep = _transcode_refs(streams, os_list, volume, level, channel_volume)
+        n = len(keep) if streams else 0
+        b, fit, alive = _budget(n, budget, total, cap)
+        bound = np.zeros(max(n, 1), np.uint64)
+        # (a source the plan refuses: the call below refuses it too, and names the reason in dcs_last_error)
+        st = self.L.dcs_transcode_plan_budget(refs, n, ctypes.byref(p), flags, ctypes.byref(b), None, _ptr(bound))
+        room = int(bound[:n].sum()) if st == 0 else 0
+        out = np.zeros(max(room, 1), np.uint8)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info, info_rd = np.zeros(max(n, 1), TRANSCODE_INFO_DTYPE), np.zeros(max(n, 1), ENCODE_RD_INFO_DTYPE)
+        _check(self.L.dcs_transcode_streams_budget(self.h, refs, n, ctypes.byref(p), flags, ctypes.byref(b), _ptr(out), room, _ptr(out_offs),
+                                                   _ptr(info), _ptr(info_rd)), self.h)
+        del alive
+        res = ([out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n], info_rd[:n])
+        return res + ((fit[0],) if total is not None else ())
+
+    def encode_files_budget(self, files, version=0x9400, fmt=None, reencode_all=False, budget=None, total=None, cap=None,
+                            filter=None, at_unity=False, level=None, **params):
+        """dcs_encode_files_budget: encode_files with the searched encoder: WAV and FLAC files as encode_streams_at_budget,
+        DCSa containers as transcode_streams_budget (reencode_all: every container is searched), the whole list in one
+        search.  Returns (list of stream bytes, ENCODE_FILE_INFO_DTYPE array, ENCODE_RD_INFO_DTYPE array[, LEVEL_INFO_DTYPE
+        array with level][, the fit record with total])."""
+        p = transcode_params(version, fmt, **params)
+        blob, offs = _files_blob(files)
+        n = len(offs) - 1
+        f, keep = _resample_filter(filter)
+        fp = ctypes.byref(f) if f is not None else None
+        rs_flags = RESAMPLE_AT_UNITY if at_unity else 0
+        flags = rs_flags | (FILES_REENCODE_ALL if reencode_all else 0)
+        b, fit, alive = _budget(n, budget, total, cap)
+        bound = np.zeros(max(n, 1), np.uint64)
+        # (a file the plan refuses: the call below refuses it too, and names the reason in dcs_last_error)
+        st = self.L.dcs_encode_files_plan_budget(_ptr(blob), _ptr(offs), n, ctypes.byref(p), fp, flags, ctypes.byref(b), None, _ptr(bound))
+        room = int(bound[:n].sum()) if st == 0 else 0
+        out = np.zeros(max(room, 1), np.uint8)
+        out_offs = np.zeros(n + 1, np.uint64)
+        info, info_rd = np.zeros(max(n, 1), ENCODE_FILE_INFO_DTYPE), np.zeros(max(n, 1), ENCODE_RD_INFO_DTYPE)
+        lv, n_lv = _levels(level, n) if level is not None else (None, 0)
+        linfo = np.zeros(max(n, 1), LEVEL_INFO_DTYPE)
+        _check(self.L.dcs_encode_files_budget(self.h, _ptr(blob), _ptr(offs), n, ctypes.byref(p), fp,
+                                              flags, ctypes.byref(b), _ptr(out), room,
+                                              _ptr(out_offs), _ptr(info), _ptr(info_rd), lv, n_lv,
+                                              _ptr(linfo) if level is not None else None), self.h)
+        del keep, alive
+        res = ([out[out_offs[i]:out_offs[i + 1]].tobytes() for i in range(n)], info[:n], info_rd[:n])
+        return res + ((linfo[:n],) if level is not None else ()) + ((fit[0],) if total is not None else ())
 
     def transcode_dcsa(self, containers, version=0x9400, fmt=None, reencode_all=False, **kw):
         """transcode_streams on "DCSa" containers (what EncodeDCSFile reads; the source OS from the container, 0x9400 as

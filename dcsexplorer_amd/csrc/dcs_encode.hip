@@ -1529,6 +1529,49 @@ namespace {
 
 uint16_t sourceVersion(int32_t os) { return os == DCS_OS93A ? 0x9301 : os == DCS_OS93B ? 0x9302 : 0x9400; }
 
+// the sources of either plan, behind the check of the target: `version` the target's, bitsPerFrame its encoder's most
+DcsStatus transcodePlanSources(const DcsStreamRef *src, uint32_t nStreams, uint16_t version, uint32_t flags, const DcsBudget *budget,
+                               uint32_t bitsPerFrame, int32_t *actionOut, uint64_t *boundOut, std::string &why)
+{
+    const bool os93 = version != 0x9400;
+    for (uint32_t i = 0 ; i < nStreams ; ++i)
+    {
+        const DcsStreamRef &s = src[i];
+        const std::string name = "stream " + std::to_string(i);
+        if (s.data == nullptr || s.os < DCS_OS93A || s.os > DCS_OS95)
+        {
+            why = name + ": no data, or not a DcsOsVersion";
+            return DCS_ERR_INVALID_ARG;
+        }
+        if (s.len < 3)
+        {
+            why = name + ": shorter than 3 bytes (no type bit)";
+            return DCS_ERR_BAD_STREAM;
+        }
+        const uint16_t v = sourceVersion(s.os);
+        const uint32_t nFrames = (static_cast<uint32_t>(s.data[0]) << 8) | s.data[1];
+        bool copy = (flags & DCS_TRANSCODE_REENCODE_ALL) == 0
+                          && (v == version || (os93 && v != 0x9400 && (s.data[2] & 0x80) == 0));
+        if (copy && budget != nullptr)
+            copy = budgetCopies(*budget, i, s.len);
+        if (!copy && nFrames == 0)
+        {
+            why = name + ": zero frames";
+            return DCS_ERR_BAD_STREAM;
+        }
+        if (!copy && nFrames + 1 > 65535)
+        {
+            why = name + ": 65 535 frames; re-encoded with the extra frame it would need 65 536, more than the frame count holds";
+            return DCS_ERR_INVALID_ARG;
+        }
+        if (actionOut != nullptr)
+            actionOut[i] = copy ? DCS_TRANSCODE_COPIED : DCS_TRANSCODE_REENCODED;
+        if (boundOut != nullptr)
+            boundOut[i] = copy ? static_cast<uint64_t>(s.len) : boundOf(static_cast<uint64_t>(nFrames + 1) * 240, bitsPerFrame);
+    }
+    return DCS_OK;
+}
+
 }  // namespace
 
 // EncodeDCSFile's rule (DCSEncoder.cpp:498-517): a source is copied when its version is the target's, or when both are OS93
@@ -1548,40 +1591,23 @@ DcsStatus dcsTranscodePlan(const DcsStreamRef *src, uint32_t nStreams, const Dcs
         why = type1 != nullptr ? type1 : text;
         return DCS_ERR_INVALID_ARG;
     }
-    for (uint32_t i = 0 ; i < nStreams ; ++i)
-    {
-        const DcsStreamRef &s = src[i];
-        const std::string name = "stream " + std::to_string(i);
-        if (s.data == nullptr || s.os < DCS_OS93A || s.os > DCS_OS95)
-        {
-            why = name + ": no data, or not a DcsOsVersion";
-            return DCS_ERR_INVALID_ARG;
-        }
-        if (s.len < 3)
-        {
-            why = name + ": shorter than 3 bytes (no type bit)";
-            return DCS_ERR_BAD_STREAM;
-        }
-        const uint16_t v = sourceVersion(s.os);
-        const uint32_t nFrames = (static_cast<uint32_t>(s.data[0]) << 8) | s.data[1];
-        const bool copy = (flags & DCS_TRANSCODE_REENCODE_ALL) == 0
-                          && (v == target->formatVersion || (os93 && v != 0x9400 && (s.data[2] & 0x80) == 0));
-        if (!copy && nFrames == 0)
-        {
-            why = name + ": zero frames";
-            return DCS_ERR_BAD_STREAM;
-        }
-        if (!copy && nFrames + 1 > 65535)
-        {
-            why = name + ": 65 535 frames; re-encoded with the extra frame it would need 65 536, more than the frame count holds";
-            return DCS_ERR_INVALID_ARG;
-        }
-        if (actionOut != nullptr)
-            actionOut[i] = copy ? DCS_TRANSCODE_COPIED : DCS_TRANSCODE_REENCODED;
-        if (boundOut != nullptr)
-            boundOut[i] = copy ? static_cast<uint64_t>(s.len) : boundOf(static_cast<uint64_t>(nFrames + 1) * 240, os93 ? kMaxBitsPerFrame93 : kMaxBitsPerFrame);
-    }
-    return DCS_OK;
+    return transcodePlanSources(src, nStreams, target->formatVersion, flags, nullptr, os93 ? kMaxBitsPerFrame93 : kMaxBitsPerFrame,
+                                actionOut, boundOut, why);
+}
+
+// The same for dcs_transcode_streams_budget: a target of a searched family, and a source that would be copied is searched
+// all the same where it does not keep to its own bound (budgetCopies)
+DcsStatus dcsTranscodePlanBudget(const DcsStreamRef *src, uint32_t nStreams, const DcsEncodeParams *target, uint32_t flags,
+                                 const DcsBudget *budget, int32_t *actionOut, uint64_t *boundOut, std::string &why)
+{
+    if ((nStreams != 0 && src == nullptr) || target == nullptr || (flags & ~DCS_TRANSCODE_REENCODE_ALL) != 0)
+        return DCS_ERR_INVALID_ARG;
+    const bool os93 = budgetOs93(target);
+    const auto say = [&](const char *text) { why = text; };
+    if (!searchedParams("dcs_transcode_streams_budget", target, os93, say) || !budgetValid("dcs_transcode_streams_budget", budget, say))
+        return DCS_ERR_INVALID_ARG;
+    return transcodePlanSources(src, nStreams, target->formatVersion, flags, budget, os93 ? kRd93MaxFrameBits : rdMaxFrameBits(),
+                                actionOut, boundOut, why);
 }
 
 // The re-encodes of dcs_transcode_streams: encodeStreams on a decode batch's resident PCM (stream k from sample
@@ -1602,6 +1628,9 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
     *unusable = in.unusable;
     return st;
 }
+
+// the decode of transcoding, which the budget calls run their searches on (defined in the runtime's unit)
+#include "dcs_transcode_decoded.h"
 
 // The chain in front of the encoder, each header using only those before it.
 
@@ -1628,6 +1657,10 @@ DcsStatus dcsEncodeFromDevice(DcsCtx *ctx, const int16_t *dPcm, const uint32_t *
 // ------------------------------------------------------------------------ encoding files (dcs_encode_files.hip.h)
 
 #include "dcs_encode_files.hip.h"
+
+// ------------------------------------------------ existing streams to a budget (dcs_encode_budget.hip.h; no kernel)
+
+#include "dcs_encode_budget.hip.h"
 
 // ----------------------------------------- the rate-distortion 1994+ encoder: kernels (dcs_encode_rd.hip.h) and the R family
 // (behind every other kernel of the unit, templates included: those keep their place in the code object)
@@ -2055,3 +2088,8 @@ extern "C" DcsStatus dcs_encode_rd_allot(DcsCtx *ctx, const uint64_t *sizeBytes,
     ENCCHK(hipStreamSynchronize(st));
     return DCS_OK;
 }
+
+// ------------------------------------------ the join of dcs_encode_files_budget's one input (dcs_encode_join.hip.h)
+// (behind every other kernel of the unit once more)
+
+#include "dcs_encode_join.hip.h"

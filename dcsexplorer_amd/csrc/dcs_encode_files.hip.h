@@ -171,6 +171,7 @@ struct FilePlan
     std::vector<DcsFlacFrame> flacFrames;
     DcsStreamRef ref{};
     uint64_t bound = 0;
+    uint64_t maxSamples = 0;        // a WAV or FLAC file: the most samples it can convert to (what `bound` was taken of)
 };
 
 // the index of every FLAC file of a list, on the host pool (files are independent)
@@ -308,7 +309,8 @@ DcsStatus planFiles(const uint8_t *files, const uint64_t *fileOffsets, uint32_t 
         p.kind = flac ? DCS_FILE_FLAC : DCS_FILE_WAV;
         const uint64_t count = s.passThrough ? m : rsSlots(s);
         const uint64_t cap = uint64_t(65535) * 240;
-        p.bound = (os93 ? dcs_encode93_bound : dcs_encode_bound)(count < cap ? count : cap);
+        p.maxSamples = count < cap ? count : cap;
+        p.bound = (os93 ? dcs_encode93_bound : dcs_encode_bound)(p.maxSamples);
     }
     for (uint32_t i = 0 ; i < nFiles ; ++i)
         if (plan[i].status != DCS_OK)
@@ -422,6 +424,81 @@ DcsStatus wavDecode(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffse
     return DCS_OK;
 }
 
+// The WAV and FLAC files of a list (wavIdx, in input order) up to the converter's output, for encodeFiles and
+// encodeFilesBudget: upload, W0 / W1 and F1 / F2 / F3, walk, convolve; the floats lie in `held`, c.room more behind them.
+struct FilesConverted
+{
+    std::vector<DcsWavInfo> infos;
+    std::vector<RsStream> hs;
+    RsConverted c;
+    std::vector<float> bound;               // the source format's full scale per file (INTEGRATION rule 12)
+};
+DcsStatus filesConvert(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, const std::vector<FilePlan> &plan,
+                       const std::vector<uint32_t> &wavIdx, const DcsResampleFilter &f, uint32_t flags, CacheArena &held, FilesConverted &w)
+{
+    const uint32_t nW = static_cast<uint32_t>(wavIdx.size());
+    w.infos.resize(nW);
+    std::vector<const uint8_t *> bytes(nW);
+    std::vector<FlacSource> sources(nW, FlacSource{ nullptr, nullptr });
+    for (uint32_t k = 0 ; k < nW ; ++k)
+    {
+        const FilePlan &p = plan[wavIdx[k]];
+        w.infos[k] = p.wav;
+        bytes[k] = files + fileOffsets[wavIdx[k]];
+        if (p.kind == DCS_FILE_FLAC)
+            sources[k] = FlacSource{ &p.flac, &p.flacFrames };
+    }
+    std::vector<WavFile> wf;
+    std::vector<uint32_t> bad;
+    float *dMono = nullptr;
+    ENCTRY(wavStageOnDevice(ctx, bytes.data(), w.infos.data(), sources.data(), nW, wf, held, &dMono, bad));
+    for (uint32_t k = 0 ; k < nW ; ++k)
+        if (bad[k])
+        {
+            dcsCtxSetError(ctx, ("file " + std::to_string(wavIdx[k]) + ": " + stageWhy(bad[k])).c_str());
+            return DCS_ERR_BAD_STREAM;
+        }
+    w.hs.resize(nW);
+    for (uint32_t k = 0 ; k < nW ; ++k)
+    {
+        w.hs[k] = rsStreamOf(wf[k].nMono, w.infos[k].rate, f, flags);
+        w.hs[k].inOff = wf[k].monoOff;
+    }
+    rsHostRoute(w.hs);
+    ENCTRY(rsWalkConvolve(ctx, w.hs, dMono, nullptr, f, wavIdx.data(), "file", held, w.c));
+    w.bound.resize(nW);
+    for (uint32_t k = 0 ; k < nW ; ++k)
+        w.bound[k] = wavBound(w.infos[k].sampleFormat);
+    return DCS_OK;
+}
+
+// file k of the converted group in the caller's record (enc: the encoder's own)
+void filesWavInfo(const FilePlan &p, const FilesConverted &w, uint32_t k, const DcsEncodeInfo &enc, DcsEncodeFileInfo &t)
+{
+    t.kind = p.kind;
+    t.sourceFormat = w.infos[k].formatCode;
+    t.rate = w.infos[k].rate;
+    t.channels = w.infos[k].channels;
+    t.nValues = w.infos[k].nValues;
+    t.nSamples = w.c.offsets[k + 1] - w.c.offsets[k];
+    t.walk = w.hs[k].passThrough ? DCS_FILE_WALK_NONE : w.hs[k].hostWalk ? DCS_FILE_WALK_HOST : DCS_FILE_WALK_DEVICE;
+    t.enc = enc;
+}
+
+// a DCSa container in the caller's record (ti: what transcoding says of its stream)
+void filesDcsaInfo(const DcsStreamRef &ref, const DcsTranscodeInfo &ti, DcsEncodeFileInfo &t)
+{
+    t.kind = ti.action == DCS_TRANSCODE_COPIED ? DCS_FILE_DCSA_COPY : DCS_FILE_DCSA_REENCODE;
+    t.sourceFormat = ref.os;
+    t.rate = 31250;
+    t.channels = 1;
+    t.nValues = ref.len;
+    t.nSamples = static_cast<uint64_t>(ti.srcFrames) * DCS_FRAME_SAMPLES;
+    t.walk = DCS_FILE_WALK_NONE;
+    t.srcFrames = ti.srcFrames;
+    t.enc = ti.enc;
+}
+
 DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
                                       const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out,
                                       size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info,
@@ -470,49 +547,17 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
     if (nW != 0)
     {
         CacheArena held(ctx);               // (given back at the end of this block, before the DCSa group borrows its own)
-        std::vector<DcsWavInfo> infos(nW);
-        std::vector<const uint8_t *> bytes(nW);
-        std::vector<FlacSource> sources(nW, FlacSource{ nullptr, nullptr });
-        for (uint32_t k = 0 ; k < nW ; ++k)
-        {
-            const FilePlan &p = plan[wavIdx[k]];
-            infos[k] = p.wav;
-            bytes[k] = files + fileOffsets[wavIdx[k]];
-            if (p.kind == DCS_FILE_FLAC)
-                sources[k] = FlacSource{ &p.flac, &p.flacFrames };
-        }
-        std::vector<WavFile> wf;
-        std::vector<uint32_t> bad;
-        float *dMono = nullptr;
-        ENCTRY(wavStageOnDevice(ctx, bytes.data(), infos.data(), sources.data(), nW, wf, held, &dMono, bad));
-        for (uint32_t k = 0 ; k < nW ; ++k)
-            if (bad[k])
-            {
-                dcsCtxSetError(ctx, ("file " + std::to_string(wavIdx[k]) + ": " + stageWhy(bad[k])).c_str());
-                return DCS_ERR_BAD_STREAM;
-            }
-        std::vector<RsStream> hs(nW);
-        for (uint32_t k = 0 ; k < nW ; ++k)
-        {
-            hs[k] = rsStreamOf(wf[k].nMono, infos[k].rate, f, flags);
-            hs[k].inOff = wf[k].monoOff;
-        }
-        rsHostRoute(hs);
-        RsConverted c;
-        ENCTRY(rsWalkConvolve(ctx, hs, dMono, nullptr, f, wavIdx.data(), "file", held, c));
-        const std::vector<uint64_t> &resOffsets = c.offsets;
+        FilesConverted w;
+        ENCTRY(filesConvert(ctx, files, fileOffsets, plan, wavIdx, f, flags, held, w));
+        const std::vector<uint64_t> &resOffsets = w.c.offsets;
         uint64_t cap = 0;
-        std::vector<float> bound(nW);
         for (uint32_t k = 0 ; k < nW ; ++k)
-        {
-            bound[k] = wavBound(infos[k].sampleFormat);
             cap += (os93 ? dcs_encode93_bound : dcs_encode_bound)(resOffsets[k + 1] - resOffsets[k]);
-        }
         wavOut.resize(cap ? cap : 1);
         std::vector<DcsEncodeInfo> enc(nW);
         // (the records reach fileLevel, and from there the caller, only once the group is encoded)
         lv.which = wavIdx.data();
-        status = rsEncodeConverted(ctx, held, c, lv, wavIdx.data(), "file", bound.data(),
+        status = rsEncodeConverted(ctx, held, w.c, lv, wavIdx.data(), "file", w.bound.data(),
                                    "%s: the signal the encoder reads peaks at |x| = %.9g, beyond %.9g (attenuate the input)", false,
                                    fileLevel.data(), params, os93, EncOutput{ wavOut.data(), cap, wavOffsets.data(), enc.data(), nullptr });
         if (status != DCS_OK)
@@ -522,15 +567,7 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
         }
         for (uint32_t k = 0 ; k < nW ; ++k)
         {
-            DcsEncodeFileInfo &t = fi[wavIdx[k]];
-            t.kind = plan[wavIdx[k]].kind;
-            t.sourceFormat = infos[k].formatCode;
-            t.rate = infos[k].rate;
-            t.channels = infos[k].channels;
-            t.nValues = infos[k].nValues;
-            t.nSamples = resOffsets[k + 1] - resOffsets[k];
-            t.walk = hs[k].passThrough ? DCS_FILE_WALK_NONE : hs[k].hostWalk ? DCS_FILE_WALK_HOST : DCS_FILE_WALK_DEVICE;
-            t.enc = enc[k];
+            filesWavInfo(plan[wavIdx[k]], w, k, enc[k], fi[wavIdx[k]]);
             size[wavIdx[k]] = wavOffsets[k + 1] - wavOffsets[k];
         }
     }
@@ -557,16 +594,7 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
         }
         for (uint32_t k = 0 ; k < nD ; ++k)
         {
-            DcsEncodeFileInfo &t = fi[dcsaIdx[k]];
-            t.kind = ti[k].action == DCS_TRANSCODE_COPIED ? DCS_FILE_DCSA_COPY : DCS_FILE_DCSA_REENCODE;
-            t.sourceFormat = refs[k].os;
-            t.rate = 31250;
-            t.channels = 1;
-            t.nValues = refs[k].len;
-            t.nSamples = static_cast<uint64_t>(ti[k].srcFrames) * DCS_FRAME_SAMPLES;
-            t.walk = DCS_FILE_WALK_NONE;
-            t.srcFrames = ti[k].srcFrames;
-            t.enc = ti[k].enc;
+            filesDcsaInfo(refs[k], ti[k], fi[dcsaIdx[k]]);
             size[dcsaIdx[k]] = dOffsets[k + 1] - dOffsets[k];
         }
     }
@@ -583,6 +611,215 @@ DcsStatus encodeFiles(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOff
     for (uint32_t k = 0 ; k < nD ; ++k)
         memcpy(out + outOffsets[dcsaIdx[k]], dOut.data() + dOffsets[k], dOffsets[k + 1] - dOffsets[k]);
     return DCS_OK;
+}
+
+// J1 (dcs_encode_join.hip.h, behind every other kernel of the unit): n decoded streams' int16 PCM, stream k from sample
+// srcOffsets[k] of dPcm, as floats into `arena` from float dstOffsets[k]; their frames' error words ORed into dStreamErr[k]
+DcsStatus encJoinPcm(DcsCtx *ctx, CacheArena &held, const int16_t *dPcm, const uint32_t *dErr, const uint64_t *srcOffsets, uint32_t n,
+                     float *arena, const uint64_t *dstOffsets, uint32_t *dStreamErr);
+
+// What dcs_encode_files_budget knows of its list before any device work, and dcs_encode_files_plan_budget's whole answer:
+// the arguments checked, the files planned as encodeFiles plans them, and the units in file order: a WAV or FLAC file is
+// searched (stream w of the converter's, in wavIdx), a container copied or searched by the budget's rule (searched: stream
+// nW + its place in refs / conIdx).  A refusal's message is in `why`.
+struct FilesBudgetPlan
+{
+    DcsResampleFilter f;
+    uint32_t rsFlags = 0;
+    std::vector<FilePlan> plan;
+    std::vector<int32_t> action;            // a container's DCS_TRANSCODE_COPIED / _REENCODED
+    std::vector<uint64_t> bound;            // per file: a copy's length, the searched encoder's bound of any other
+    std::vector<uint32_t> wavIdx, conIdx;
+    std::vector<DcsStreamRef> refs;
+    BudgetUnits u;
+};
+DcsStatus planFilesBudget(const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles, const DcsEncodeParams *params,
+                          const DcsResampleFilter *filter, uint32_t flags, const DcsBudget *budget, FilesBudgetPlan &b, std::string &why)
+{
+    const bool os93 = budgetOs93(params);
+    const auto say = [&](const char *text) { why = text; };
+    if (!searchedParams("dcs_encode_files_budget", params, os93, say) || !budgetValid("dcs_encode_files_budget", budget, say))
+        return DCS_ERR_INVALID_ARG;
+    // (the plan reads the set as the reference-equal encoders do, which know no OS93 sub-type but 0 .. 3; the search reads none)
+    DcsEncodeParams planned = *params;
+    if (os93)
+        planned.streamFormatSubType = 0;
+    b.rsFlags = flags & ~DCS_FILES_REENCODE_ALL;
+    ENCTRY(filesArgs(files, fileOffsets, nFiles, &planned, filter, b.rsFlags, b.f, why));
+    const DcsStatus status = planFiles(files, fileOffsets, nFiles, &planned, b.f, b.rsFlags, b.plan);
+    if (status != DCS_OK)
+    {
+        for (const FilePlan &p : b.plan)
+            if (p.status != DCS_OK)
+            {
+                why = p.why;
+                break;
+            }
+        return status;
+    }
+    const std::vector<FilePlan> &plan = b.plan;
+    b.action.assign(nFiles, DCS_TRANSCODE_REENCODED);
+    b.bound.assign(nFiles, 0);
+    for (uint32_t i = 0 ; i < nFiles ; ++i)
+        if (plan[i].kind == DCS_FILE_WAV || plan[i].kind == DCS_FILE_FLAC)
+            b.wavIdx.push_back(i);
+    const uint32_t nW = static_cast<uint32_t>(b.wavIdx.size());
+    for (uint32_t i = 0, w = 0 ; i < nFiles ; ++i)
+    {
+        if (plan[i].kind == DCS_FILE_WAV || plan[i].kind == DCS_FILE_FLAC)
+        {
+            b.u.search(w++);
+            b.bound[i] = (os93 ? dcs_encode93_rd_bound : dcs_encode_rd_bound)(plan[i].maxSamples);
+            continue;
+        }
+        DcsBudget own = *budget;                // (the file's own bound, where the call has bounds)
+        own.budgetBytes = budget->budgetBytes != nullptr ? budget->budgetBytes + i : nullptr;
+        own.capBytes = budget->capBytes != nullptr ? budget->capBytes + i : nullptr;
+        std::string text;
+        const DcsStatus st = dcsTranscodePlanBudget(&plan[i].ref, 1, params, (flags & DCS_FILES_REENCODE_ALL) != 0 ? DCS_TRANSCODE_REENCODE_ALL : 0,
+                                                    &own, &b.action[i], &b.bound[i], text);
+        if (st != DCS_OK)
+        {
+            why = text.compare(0, 9, "stream 0:") == 0 ? "file " + std::to_string(i) + text.substr(8) : "file " + std::to_string(i) + ": " + text;
+            return st;
+        }
+        if (b.action[i] == DCS_TRANSCODE_COPIED)
+            b.u.keep(plan[i].ref.data, plan[i].ref.len);
+        else
+        {
+            b.u.search(nW + static_cast<uint32_t>(b.refs.size()));
+            b.refs.push_back(plan[i].ref);
+            b.conIdx.push_back(i);
+        }
+    }
+    return DCS_OK;
+}
+
+// dcs_encode_files_budget: encodeFiles' front half, then ONE searched EncRun over every file that is not
+// a copy.  Its input is one float arena of the call's lifetime: the converter's output for the WAV and FLAC files (streams
+// 0 .. nW - 1, as the converter lays them), and behind it the searched containers' decoded PCM (streams nW .., J1); the
+// jobs name those streams in file order.  A list without searched containers launches no join; a list of searched
+// containers only has an arena of their samples alone.
+DcsStatus encodeFilesBudget(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
+                            const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, const DcsBudget *budget,
+                            uint8_t *out, size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info, DcsEncodeRdInfo *infoRd,
+                            const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
+{
+    if (ctx == nullptr || outOffsets == nullptr || budget == nullptr)
+        return DCS_ERR_INVALID_ARG;
+    FilesBudgetPlan fb;
+    std::string why;
+    DcsStatus status = planFilesBudget(files, fileOffsets, nFiles, params, filter, flags, budget, fb, why);
+    if (status != DCS_OK)
+    {
+        if (!why.empty())
+            dcsCtxSetError(ctx, why.c_str());
+        return status;
+    }
+    LevelStage lv{ ctx, levels, nLevels };
+    ENCTRY(lv.check(nFiles, "file"));
+    outOffsets[0] = 0;
+    if (nFiles == 0)
+        return DCS_OK;
+    const bool os93 = budgetOs93(params);
+    const DcsResampleFilter &f = fb.f;
+    const uint32_t rsFlags = fb.rsFlags;
+    const std::vector<FilePlan> &plan = fb.plan;
+    const std::vector<uint32_t> &wavIdx = fb.wavIdx, &conIdx = fb.conIdx;
+    const std::vector<DcsStreamRef> &refs = fb.refs;
+    const std::vector<int32_t> &action = fb.action;
+    const BudgetUnits &u = fb.u;
+    const uint32_t nW = static_cast<uint32_t>(wavIdx.size());
+    const uint32_t nC = static_cast<uint32_t>(refs.size());
+    uint64_t conSamples = 0;
+    for (const DcsStreamRef &r : refs)
+        conSamples += (((static_cast<uint64_t>(r.data[0]) << 8) | r.data[1]) + 1) * DCS_FRAME_SAMPLES;
+    // (a DCSa container keeps this record: the stage is for the signal the converter hands the encoder)
+    std::vector<DcsLevelInfo> fileLevel(lv.on() ? nFiles : 0, DcsLevelInfo{ 0.0f, 1.0f, 0.0f, 0, 0 });
+    CacheArena held(ctx);                   // the input arena: of the call, so that it outlives every group of the search
+    FilesConverted w;
+    w.c.room = conSamples;
+    if (nW != 0)
+        ENCTRY(filesConvert(ctx, files, fileOffsets, plan, wavIdx, f, rsFlags, held, w));
+    else
+    {
+        w.c.offsets.assign(1, 0);
+        if (conSamples != 0)
+        {
+            ENCCHK(hipSetDevice(dcsCtxDevice(ctx)));
+            ENCCHK(held.alloc(&w.c.d, conSamples));
+        }
+    }
+    // the streams of the one input: the converter's, then the containers'
+    std::vector<uint32_t> label(wavIdx);
+    label.insert(label.end(), conIdx.begin(), conIdx.end());
+    std::vector<float> bound(w.bound);
+    bound.resize(nW + nC, 1.0f);
+    std::vector<DcsEncodeInfo> enc;
+    const auto search = [&](EncInput &in) { return encodeBudgeted(ctx, in, u, params, os93, *budget, out, outCap, outOffsets, enc, infoRd); };
+    const RsEncode joined = [&](EncInput &in) -> DcsStatus {
+        in.label = label.data();
+        in.bound = bound.data();
+        if (nC == 0)
+            return search(in);
+        // (a message of the decode itself counts the searched containers; the encoder's gives the file's own index, in.label)
+        bool encoding = false;
+        const DcsStatus joinedStatus = dcsTranscodeDecoded(ctx, refs.data(), nC, [&](const int16_t *dPcm, const uint32_t *dErr, const volatile uint32_t *planFlag,
+                                                             const uint64_t *srcOffsets, bool *unusable) -> DcsStatus {
+            std::vector<uint64_t> offsets(w.c.offsets);
+            for (uint32_t k = 0 ; k < nC ; ++k)
+                offsets.push_back(offsets.back() + (srcOffsets[k + 1] - srcOffsets[k]));
+            if (offsets.back() - w.c.offsets.back() != conSamples)
+            {
+                dcsCtxSetError(ctx, "internal error: the decode of the containers is not as long as their frame counts say");
+                return DCS_ERR_HIP;
+            }
+            uint32_t *dStreamErr;
+            ENCCHK(held.alloc(&dStreamErr, size_t(nW) + nC));
+            ENCCHK(hipMemsetAsync(dStreamErr, 0, sizeof(uint32_t) * (size_t(nW) + nC), held.stream()));
+            ENCTRY(encJoinPcm(ctx, held, dPcm, dErr, srcOffsets, nC, w.c.d, offsets.data() + nW, dStreamErr + nW));
+            EncInput all = in;
+            all.sampleOffsets = offsets.data();
+            all.nStreams = nW + nC;
+            all.devFloat = w.c.d;
+            all.devStreamErr = dStreamErr;
+            all.planFlag = planFlag;
+            encoding = true;
+            const DcsStatus st = search(all);
+            *unusable = all.unusable;
+            encoding = !all.unusable;
+            return st;
+        });
+        if (joinedStatus != DCS_OK && joinedStatus != DCS_ERR_CAPACITY && !encoding)
+            renameError(ctx, &conIdx);
+        return joinedStatus;
+    };
+    lv.which = wavIdx.data();
+    status = rsEncodeConverted(ctx, held, w.c, lv, wavIdx.data(), "file", w.bound.data(),
+                               "%s: the signal the encoder reads peaks at |x| = %.9g, beyond %.9g (attenuate the input)", true,
+                               fileLevel.data(), params, os93, EncOutput{}, &joined);    // (early into fileLevel, which is the call's own)
+    if (status != DCS_OK && status != DCS_ERR_CAPACITY)
+    {
+        renameError(ctx, nullptr);           // (the encoder's messages give the file's own index: in.label)
+        return status;
+    }
+    if (info != nullptr)
+        for (uint32_t i = 0, k = 0 ; i < nFiles ; ++i)
+        {
+            DcsEncodeFileInfo t{};
+            if (plan[i].kind == DCS_FILE_WAV || plan[i].kind == DCS_FILE_FLAC)
+                filesWavInfo(plan[i], w, k++, enc[i], t);
+            else
+            {
+                const DcsStreamRef &r = plan[i].ref;
+                const int32_t srcFrames = static_cast<int32_t>((static_cast<uint32_t>(r.data[0]) << 8) | r.data[1]);
+                filesDcsaInfo(r, DcsTranscodeInfo{ action[i], srcFrames, action[i] == DCS_TRANSCODE_COPIED ? dcsTranscodeCopyInfo(r) : enc[i] }, t);
+            }
+            info[i] = t;
+        }
+    if (lv.on() && levelInfo != nullptr)
+        memcpy(levelInfo, fileLevel.data(), sizeof(DcsLevelInfo) * nFiles);
+    return status;
 }
 
 }  // namespace
@@ -613,5 +850,40 @@ extern "C" DcsStatus dcs_encode_files_level(DcsCtx *ctx, const uint8_t *files, c
 {
     return encGuard([&] {
         return encodeFiles(ctx, files, fileOffsets, nFiles, params, filter, flags, out, outCap, outOffsets, info, levels, nLevels, levelInfo);
+    });
+}
+
+extern "C" DcsStatus dcs_encode_files_budget(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
+                                             const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags,
+                                             const DcsBudget *budget, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                                             DcsEncodeFileInfo *info, DcsEncodeRdInfo *infoRd,
+                                             const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
+{
+    return encGuard([&] {
+        return encodeFilesBudget(ctx, files, fileOffsets, nFiles, params, filter, flags, budget, out, outCap, outOffsets, info, infoRd,
+                                 levels, nLevels, levelInfo);
+    });
+}
+
+extern "C" DcsStatus dcs_encode_files_plan_budget(const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
+                                                  const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags,
+                                                  const DcsBudget *budget, int32_t *kindOut, uint64_t *boundOut)
+{
+    return encGuard([&]() -> DcsStatus {
+        if (budget == nullptr)
+            return DCS_ERR_INVALID_ARG;
+        FilesBudgetPlan fb;
+        std::string why;
+        ENCTRY(planFilesBudget(files, fileOffsets, nFiles, params, filter, flags, budget, fb, why));
+        for (uint32_t i = 0 ; i < nFiles ; ++i)
+        {
+            const int32_t kind = fb.plan[i].kind;
+            if (kindOut != nullptr)
+                kindOut[i] = kind == DCS_FILE_WAV || kind == DCS_FILE_FLAC ? kind
+                             : fb.action[i] == DCS_TRANSCODE_COPIED ? DCS_FILE_DCSA_COPY : DCS_FILE_DCSA_REENCODE;
+            if (boundOut != nullptr)
+                boundOut[i] = fb.bound[i];
+        }
+        return DCS_OK;
     });
 }

@@ -29,6 +29,8 @@ struct EncInput
     const uint32_t *devErr = nullptr;       // ... and its frames' error words at sampleOffsets[i] / 240
     const uint32_t *label = nullptr;        // the number a message gives stream i (null: i)
     const float *bound = nullptr;           // the largest |x| stream i may hold (null: 1; dcs_encode_files, INTEGRATION rule 12)
+    const uint32_t *devStreamErr = nullptr; // devFloat: per stream, the error words of the decode its floats came from, ORed
+                                            // (null: none did; encJoinPcmKernel, dcs_encode_join.hip.h)
     const volatile uint32_t *planFlag = nullptr;    // a word the device writes before the PCM is final: not 0 = the PCM is not to be used
     bool unusable = false;                  // (out) planFlag was set: DCS_ERR_BAD_STREAM, and nothing was written
 };
@@ -684,6 +686,7 @@ private:
     uint32_t resident = ~0u, residentFrames = 0;    // the group whose rows the group buffers hold, and its job-frames
     std::vector<uint32_t> frameJob;             // the resident group's rows
     std::vector<uint32_t> bad;                  // per stream, on the host after the first group's wait
+    std::vector<uint32_t> decodeErr;            // in.devStreamErr beside it (empty: the input has none)
     uint8_t *dst = nullptr;                     // where the bytes go (placeOutput); null: nowhere
 
     // ---- the packed group: valid from packGroup to the next one
@@ -869,6 +872,11 @@ DcsStatus EncRun::analyse()
     for (EncFamily *f : fams)
         ENCTRY(f->streamSums());
     ENCCHK(hipMemcpyAsync(bad.data(), cb.dBad, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
+    if (in.devStreamErr != nullptr)
+    {
+        decodeErr.resize(nStreams);
+        ENCCHK(hipMemcpyAsync(decodeErr.data(), in.devStreamErr, sizeof(uint32_t) * nStreams, hipMemcpyDeviceToHost, st));
+    }
     for (EncFamily *f : fams)
         ENCTRY(f->analyse());
     return DCS_OK;
@@ -915,9 +923,9 @@ DcsStatus EncRun::checkInput()
         return DCS_ERR_BAD_STREAM;
     }
     for (uint32_t i = 0 ; i < in.nStreams ; ++i)
-        if (bad[i])
+        if (bad[i] || (!decodeErr.empty() && decodeErr[i]))
         {
-            dcsCtxSetError(ctx, (name(i) + (dev ? ": the decoder reports an error in a frame (DCS_FRAME_STOP / DCS_FRAME_FATAL)"
+            dcsCtxSetError(ctx, (name(i) + (dev || (!decodeErr.empty() && decodeErr[i]) ? ": the decoder reports an error in a frame (DCS_FRAME_STOP / DCS_FRAME_FATAL)"
                                                 : in.bound != nullptr ? ": a sample is not finite or beyond its format's full scale"
                                                 : ": a sample is not finite or |x| > 1")).c_str());
             return DCS_ERR_BAD_STREAM;
@@ -1235,37 +1243,189 @@ DcsStatus encodeHostPcm(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOff
     return encodeStreams(ctx, in, params, os93, to);
 }
 
-// dcs_encode_rd_streams, dcs_encode93_rd_streams, dcs_encode_rd_fit and dcs_encode93_rd_fit (`fn`: which, for the message):
-// the null arguments they refuse, then a set that is not one of the family that `os93` names; then the call, every stream
-// searched with the one set, to budgetBytes or to `fit`
-DcsStatus encodeSearched(DcsCtx *ctx, const char *fn, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
-                         const DcsEncodeParams *params, bool os93, const uint32_t *budgetBytes, const EncFit *fit, uint8_t *out,
-                         uint64_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd)
+// a set of the searched family that `os93` names (R or S); `say` takes the message of one that is not, `fn` the call's name
+bool searchedParams(const char *fn, const DcsEncodeParams *params, bool os93, const std::function<void(const char *)> &say)
 {
-    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
-        return DCS_ERR_INVALID_ARG;
-    if (!(os93 ? paramsValid93Rd(params) : paramsValidRd(params)))
-    {
-        dcsCtxSetError(ctx, (std::string(fn) + (os93 ? ": formatVersion 0x9301 or 0x9302, streamFormatType 0 or -1 (OS93 Type 0; Type 1 is "
-                                                       "not searched), targetBitRate 1..100 000 000 and finite parameters"
-                                                     : ": formatVersion 0x9400, streamFormatType 0, 1 or -1, streamFormatSubType 0, 3 or -1, "
-                                                       "targetBitRate 1..100 000 000 and finite parameters")).c_str());
-        return DCS_ERR_INVALID_ARG;
-    }
+    if (os93 ? paramsValid93Rd(params) : paramsValidRd(params))
+        return true;
+    say((std::string(fn) + (os93 ? ": formatVersion 0x9301 or 0x9302, streamFormatType 0 or -1 (OS93 Type 0; Type 1 is "
+                                   "not searched), targetBitRate 1..100 000 000 and finite parameters"
+                                 : ": formatVersion 0x9400, streamFormatType 0, 1 or -1, streamFormatSubType 0, 3 or -1, "
+                                   "targetBitRate 1..100 000 000 and finite parameters")).c_str());
+    return false;
+}
+
+// The search on any input, the one place that makes a searched EncJobs: job j = (stream list[j].stream, the one set), searched
+// to budgetBytes[j] (null: the set's targetBitRate) or, all jobs together, to `fit`.  The set has passed searchedParams.
+DcsStatus searchInput(DcsCtx *ctx, EncInput &in, const std::vector<DcsSweepJob> &list, const DcsEncodeParams *params, bool os93,
+                      const uint32_t *budgetBytes, const EncFit *fit, const EncOutput &to)
+{
     if (fit != nullptr && fit->info != nullptr)
     {
         *fit->info = DcsEncodeRdFitInfo{};
         fit->info->totalBytes = fit->totalBytes;
         fit->info->fits = 1;
     }
-    EncOneSet one(pcm, sampleOffsets, nStreams);
-    EncJobs js = one.jobs(params, os93);
+    EncJobs js{ params, 1, list.data(), static_cast<uint32_t>(list.size()), os93 };
     js.search = true;
     js.budgetBytes = budgetBytes;
     js.fit = fit;
+    return EncRun(ctx, in, js, to, EncSweep()).run();
+}
+
+// dcs_encode_rd_streams, dcs_encode93_rd_streams, dcs_encode_rd_fit and dcs_encode93_rd_fit (`fn`: which, for the message):
+// the null arguments they refuse, then a set that is not one of the family that `os93` names; then the call, every stream
+// of the caller's host PCM searched with the one set, to budgetBytes or to `fit`
+DcsStatus encodeSearched(DcsCtx *ctx, const char *fn, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                         const DcsEncodeParams *params, bool os93, const uint32_t *budgetBytes, const EncFit *fit, uint8_t *out,
+                         uint64_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && pcm == nullptr))
+        return DCS_ERR_INVALID_ARG;
+    if (!searchedParams(fn, params, os93, [&](const char *why) { dcsCtxSetError(ctx, why); }))
+        return DCS_ERR_INVALID_ARG;
+    EncOneSet one(pcm, sampleOffsets, nStreams);
     EncOutput to{ out, static_cast<size_t>(outCap), outOffsets, info, nullptr, nullptr };
     to.infoRd = infoRd;
-    return EncRun(ctx, one.in, js, to, EncSweep()).run();
+    return searchInput(ctx, one.in, one.list, params, os93, budgetBytes, fit, to);
+}
+
+// ---------------------------------------------------------------------- budgets from any source
+
+// os93 as the calls that take any target read it
+bool budgetOs93(const DcsEncodeParams *params) { return params != nullptr && params->formatVersion != 0x9400; }
+
+// the DcsBudget of a call: there, and budgetBytes only in the per-job form
+bool budgetValid(const char *fn, const DcsBudget *b, const std::function<void(const char *)> &say)
+{
+    if (b == nullptr)
+        return false;
+    if (b->shared > 1 || (b->shared != 0 && b->budgetBytes != nullptr))
+    {
+        say((std::string(fn) + (b->shared > 1 ? ": budget->shared is 0 (one budget per job) or 1 (one budget for the set)"
+                                              : ": budget->budgetBytes is for the per-job form; the shared form takes totalBytes and capBytes")).c_str());
+        return false;
+    }
+    return true;
+}
+
+// is a source that fits the target's family copied under `b`?  Unit i of the call.
+bool budgetCopies(const DcsBudget &b, uint32_t i, uint64_t len)
+{
+    const uint32_t *most = b.shared != 0 ? b.capBytes : b.budgetBytes;
+    return most == nullptr || len <= most[i];
+}
+
+// The units of a budget call (streams or files, in input order): each is a job that is searched, or a copy of bytes that
+// exist.  copy[i] null: searched, and stream[i] is its stream of the EncInput.
+struct BudgetUnits
+{
+    std::vector<const uint8_t *> copy;
+    std::vector<uint64_t> copyLen;
+    std::vector<uint32_t> stream;
+    uint32_t n() const { return static_cast<uint32_t>(copy.size()); }
+    void search(uint32_t s) { copy.push_back(nullptr); copyLen.push_back(0); stream.push_back(s); }
+    void keep(const uint8_t *p, uint64_t len) { copy.push_back(p); copyLen.push_back(len); stream.push_back(0); }
+};
+
+// What the three budget calls share behind their sources: the searched units of `u` as the jobs of ONE EncRun on `in`, with
+// their share of `b` (per job: their own budgets; shared: the total less the copies, their own caps), then the units' layout
+// in input order, the capacity, the copies' bytes and the records.  enc[i]: unit i's DcsEncodeInfo where it was searched
+// (the caller's own record type takes it).  On DCS_ERR_CAPACITY outOffsets, infoRd (per-job form) and *b.fit stand.
+DcsStatus encodeBudgeted(DcsCtx *ctx, EncInput &in, const BudgetUnits &u, const DcsEncodeParams *params, bool os93, const DcsBudget &b,
+                         uint8_t *out, size_t outCap, uint64_t *outOffsets, std::vector<DcsEncodeInfo> &enc, DcsEncodeRdInfo *infoRd)
+{
+    const uint32_t n = u.n();
+    std::vector<DcsSweepJob> list;
+    std::vector<uint32_t> unitOf, budgets, caps;
+    uint64_t copied = 0;
+    for (uint32_t i = 0 ; i < n ; ++i)
+        if (u.copy[i] == nullptr)
+        {
+            list.push_back(DcsSweepJob{ u.stream[i], 0 });
+            unitOf.push_back(i);
+            if (b.budgetBytes != nullptr)
+                budgets.push_back(b.budgetBytes[i]);
+            if (b.capBytes != nullptr)
+                caps.push_back(b.capBytes[i]);
+        }
+        else
+            copied += u.copyLen[i];
+    const uint32_t nS = static_cast<uint32_t>(list.size());
+    // (a shared total that the copies alone exceed leaves the searched jobs nothing: 10.13's rule 4 on what is left)
+    DcsEncodeRdFitInfo rec{};
+    const EncFit fit{ b.totalBytes > copied ? b.totalBytes - copied : 0, b.capBytes != nullptr ? caps.data() : nullptr, &rec };
+    std::vector<DcsEncodeInfo> encS(nS);
+    std::vector<DcsEncodeRdInfo> rdS(nS);
+    std::vector<uint64_t> offS(static_cast<size_t>(nS) + 1, 0);
+    std::vector<uint8_t> bytes;
+    const auto layout = [&](const uint64_t *offs) -> uint64_t {
+        outOffsets[0] = 0;
+        for (uint32_t i = 0, k = 0 ; i < n ; ++i)
+        {
+            outOffsets[i + 1] = outOffsets[i] + (u.copy[i] != nullptr ? u.copyLen[i] : offs[k + 1] - offs[k]);
+            k += u.copy[i] == nullptr ? 1 : 0;
+        }
+        return outOffsets[n];
+    };
+    const EncPlace place = [&](const uint64_t *offs, uint64_t total) -> uint8_t * {
+        if (layout(offs) > outCap || out == nullptr)
+            return nullptr;
+        if (nS == n)                            // no copy: the searched streams' layout is the call's, straight into `out`
+            return out;
+        bytes.resize(total ? total : 1);
+        return bytes.data();
+    };
+    DcsStatus st = DCS_OK;
+    if (nS != 0)
+    {
+        EncOutput to{ nullptr, 0, offS.data(), encS.data(), &place, nullptr };
+        to.infoRd = rdS.data();
+        st = searchInput(ctx, in, list, params, os93, b.shared == 0 && b.budgetBytes != nullptr ? budgets.data() : nullptr,
+                         b.shared != 0 ? &fit : nullptr, to);
+    }
+    else
+    {
+        rec.fits = 1;
+        if (layout(offS.data()) > outCap || (n != 0 && out == nullptr))
+            st = DCS_ERR_CAPACITY;
+    }
+    if (st != DCS_OK && st != DCS_ERR_CAPACITY)
+        return st;
+    if (b.shared != 0 && b.fit != nullptr)
+    {
+        rec.totalBytes = b.totalBytes;
+        rec.leastBytes += copied;
+        rec.usedBytes += copied;
+        rec.fits = rec.leastBytes <= b.totalBytes ? 1 : 0;
+        *b.fit = rec;
+    }
+    // (the searched records as far as the driver wrote them: all of them in the per-job form, none before a shared call's
+    // capacity was looked at)
+    enc.assign(n, DcsEncodeInfo{});
+    for (uint32_t i = 0, k = 0 ; i < n ; ++i)
+    {
+        DcsEncodeRdInfo r{};
+        r.fits = 1;
+        if (u.copy[i] == nullptr)
+        {
+            enc[i] = encS[k];
+            r = rdS[k++];
+        }
+        if (infoRd != nullptr)
+            infoRd[i] = r;
+    }
+    if (st != DCS_OK)
+        return st;
+    for (uint32_t i = 0, k = 0 ; nS != n && i < n ; ++i)
+        if (u.copy[i] != nullptr)
+            memcpy(out + outOffsets[i], u.copy[i], u.copyLen[i]);
+        else
+        {
+            memcpy(out + outOffsets[i], bytes.data() + offS[k], offS[k + 1] - offS[k]);
+            ++k;
+        }
+    return DCS_OK;
 }
 
 }  // namespace

@@ -466,6 +466,7 @@ struct RsConverted
     float *d = nullptr;
     std::vector<uint64_t> offsets;
     std::vector<uint32_t> peak;
+    uint64_t room = 0;                      // (in) floats the buffer is to hold behind the last stream, for the caller to fill
 };
 
 // how a message names stream i of a call: "<unit> label[i]" (label null: i)
@@ -593,7 +594,7 @@ DcsStatus rsWalkConvolve(DcsCtx *ctx, std::vector<RsStream> &hs, const float *dM
         outOffsets[i + 1] = outOffsets[i] + counts[i];
         maxCount = counts[i] > maxCount ? counts[i] : maxCount;
     }
-    ENCCHK(held.alloc(&dRes, outOffsets[n] ? outOffsets[n] : 1));
+    ENCCHK(held.alloc(&dRes, outOffsets[n] + c.room ? outOffsets[n] + c.room : 1));
     ENCCHK(hipMemcpyAsync(dStr, hs.data(), sizeof(RsStream) * n, hipMemcpyHostToDevice, st));
     // about 4 096 blocks in all: each block of the LDS variant copies the table once and then strides over its outputs
     const dim3 grid = streamGrid(n, maxCount, 4096, 0);
@@ -682,10 +683,12 @@ DcsStatus rsGate(DcsCtx *ctx, const RsConverted &c, const LevelStage &lv, const 
 // (encodeFiles): plan the level from the peaks, gate, scale (queued, no wait), encode where the floats lie, collect the
 // clamp's counts, publish the records to levelOut.  Nothing is published where the gate refuses.  publishEarly: the
 // records go to levelOut as soon as the gate has passed, so they stand where the encoder then refuses (its
-// DCS_ERR_CAPACITY); without it they are written only once everything has succeeded.
+// DCS_ERR_CAPACITY); without it they are written only once everything has succeeded.  `encode` (or null: encodeStreams
+// with params, os93 and `to`) takes the EncInput in the encoder's place: the budget calls' way to a searched EncJobs.
+using RsEncode = std::function<DcsStatus(EncInput &in)>;
 DcsStatus rsEncodeConverted(DcsCtx *ctx, CacheArena &held, const RsConverted &c, LevelStage &lv, const uint32_t *label, const char *unit,
                             const float *bound, const char *rangeFormat, bool publishEarly, DcsLevelInfo *levelOut,
-                            const DcsEncodeParams *params, bool os93, const EncOutput &to)
+                            const DcsEncodeParams *params, bool os93, const EncOutput &to, const RsEncode *encode = nullptr)
 {
     lv.plan(c.peak);
     ENCTRY(rsGate(ctx, c, lv, label, unit, bound, rangeFormat));
@@ -698,7 +701,7 @@ DcsStatus rsEncodeConverted(DcsCtx *ctx, CacheArena &held, const RsConverted &c,
     in.devFloat = c.d;
     in.label = label;
     in.bound = bound;
-    ENCTRY(encodeStreams(ctx, in, params, os93, to));
+    ENCTRY(encode != nullptr ? (*encode)(in) : encodeStreams(ctx, in, params, os93, to));
     return lv.finish(levelOut);
 }
 
@@ -777,6 +780,67 @@ extern "C" DcsStatus dcs_encode_streams_at(DcsCtx *ctx, const float *pcm, const 
                                        info, nullptr, 0, nullptr);
 }
 
+namespace {
+
+// dcs_encode_streams_at_level (budget null) and dcs_encode_streams_at_budget: the argument checks, the converter, and
+// rsEncodeConverted with the reference-equal encoder or the searched one behind it
+DcsStatus encodeStreamsAt(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                          const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                          uint32_t flags, const DcsEncodeParams *params, const DcsBudget *budget, uint8_t *out, size_t outCap,
+                          uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd,
+                          const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
+{
+    if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
+        return DCS_ERR_INVALID_ARG;
+    const bool os93 = budgetOs93(params);
+    if (budget != nullptr)
+    {
+        const auto say = [&](const char *why) { dcsCtxSetError(ctx, why); };
+        if (!searchedParams("dcs_encode_streams_at_budget", params, os93, say) || !budgetValid("dcs_encode_streams_at_budget", budget, say))
+            return DCS_ERR_INVALID_ARG;
+    }
+    else if (!paramsValid(params, os93))
+    {
+        if (const char *type1 = whyOs93aType1(params, os93))
+            dcsCtxSetError(ctx, type1);
+        return DCS_ERR_INVALID_ARG;
+    }
+    DcsResampleFilter f;
+    std::string why;
+    const DcsStatus status = rsCheck(nStreams, sampleOffsets, rates, channels, filter, flags, f, why);
+    if (status != DCS_OK)
+    {
+        dcsCtxSetError(ctx, why.c_str());
+        return status;
+    }
+    LevelStage lv{ ctx, levels, nLevels };
+    ENCTRY(lv.check(nStreams, "stream"));
+    if (nStreams == 0)
+    {
+        outOffsets[0] = 0;
+        return DCS_OK;
+    }
+    CacheArena held(ctx);
+    RsConverted c;
+    ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, c));
+    // (the budget call: every stream a searched job, its record the caller's own)
+    const RsEncode searched = [&](EncInput &in) -> DcsStatus {
+        BudgetUnits u;
+        for (uint32_t i = 0 ; i < nStreams ; ++i)
+            u.search(i);
+        std::vector<DcsEncodeInfo> enc;
+        const DcsStatus st = encodeBudgeted(ctx, in, u, params, os93, *budget, out, outCap, outOffsets, enc, infoRd);
+        if (info != nullptr && (st == DCS_OK || st == DCS_ERR_CAPACITY))
+            memcpy(info, enc.data(), sizeof(DcsEncodeInfo) * nStreams);
+        return st;
+    };
+    return rsEncodeConverted(ctx, held, c, lv, nullptr, "stream", nullptr,
+                             "%s: the resampled signal peaks at |x| = %.9g, outside [-1, 1] (attenuate the input)", true, levelInfo,
+                             params, os93, EncOutput{ out, outCap, outOffsets, info, nullptr }, budget != nullptr ? &searched : nullptr);
+}
+
+}  // namespace
+
 extern "C" DcsStatus dcs_encode_streams_at_level(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
                                                  const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
                                                  uint32_t flags, const DcsEncodeParams *params, uint8_t *out, size_t outCap,
@@ -784,36 +848,22 @@ extern "C" DcsStatus dcs_encode_streams_at_level(DcsCtx *ctx, const float *pcm, 
                                                  const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
 {
     return encGuard([&]() -> DcsStatus {
-        if (ctx == nullptr || sampleOffsets == nullptr || outOffsets == nullptr || (nStreams != 0 && (pcm == nullptr || rates == nullptr)))
+        return encodeStreamsAt(ctx, pcm, sampleOffsets, nStreams, rates, channels, filter, flags, params, nullptr, out, outCap, outOffsets,
+                               info, nullptr, levels, nLevels, levelInfo);
+    });
+}
+
+extern "C" DcsStatus dcs_encode_streams_at_budget(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                                  const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                                                  uint32_t flags, const DcsEncodeParams *params, const DcsBudget *budget, uint8_t *out,
+                                                  size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd,
+                                                  const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo)
+{
+    return encGuard([&]() -> DcsStatus {
+        if (budget == nullptr)
             return DCS_ERR_INVALID_ARG;
-        const bool os93 = params != nullptr && params->formatVersion != 0x9400;
-        if (!paramsValid(params, os93))
-        {
-            if (const char *type1 = whyOs93aType1(params, os93))
-                dcsCtxSetError(ctx, type1);
-            return DCS_ERR_INVALID_ARG;
-        }
-        DcsResampleFilter f;
-        std::string why;
-        const DcsStatus status = rsCheck(nStreams, sampleOffsets, rates, channels, filter, flags, f, why);
-        if (status != DCS_OK)
-        {
-            dcsCtxSetError(ctx, why.c_str());
-            return status;
-        }
-        LevelStage lv{ ctx, levels, nLevels };
-        ENCTRY(lv.check(nStreams, "stream"));
-        if (nStreams == 0)
-        {
-            outOffsets[0] = 0;
-            return DCS_OK;
-        }
-        CacheArena held(ctx);
-        RsConverted c;
-        ENCTRY(resampleOnDevice(ctx, pcm, sampleOffsets, nStreams, rates, channels, f, flags, held, c));
-        return rsEncodeConverted(ctx, held, c, lv, nullptr, "stream", nullptr,
-                                 "%s: the resampled signal peaks at |x| = %.9g, outside [-1, 1] (attenuate the input)", true, levelInfo,
-                                 params, os93, EncOutput{ out, outCap, outOffsets, info, nullptr });
+        return encodeStreamsAt(ctx, pcm, sampleOffsets, nStreams, rates, channels, filter, flags, params, budget, out, outCap, outOffsets,
+                               info, infoRd, levels, nLevels, levelInfo);
     });
 }
 

@@ -11,6 +11,8 @@
 
 #include <functional>
 
+#include "dcs_transcode_decoded.h"
+
 // dcs_encode.hip
 DcsStatus dcsTranscodePlan(const DcsStreamRef *src, uint32_t nStreams, const DcsEncodeParams *target, uint32_t flags,
                            int32_t *actionOut, uint64_t *boundOut, std::string &why);
@@ -92,6 +94,49 @@ static DcsStatus transcodeDecodeOnHost(DcsCtx *ctx, const DcsStreamRef *refs, ui
 // a source longer than this that has less than 1/64 of the list's frames beside it is walked on the host (see below)
 static const uint64_t kTranscodeHostWalkFrames = 2048;
 
+// dcs_transcode_decoded.h states what this is, for this unit and the encoder's
+DcsStatus dcsTranscodeDecoded(DcsCtx *ctx, const DcsStreamRef *refs, uint32_t nRe, const TranscodeEncode &encode)
+{
+    // The device index walk is one wavefront per stream, serial over its frames (about 7.6 us a frame on MI355X): a list
+    // that one long source dominates is walked faster by the host pool, and then planned on the host as well.
+    uint64_t total = 0, longest = 0;
+    for (uint32_t k = 0 ; k < nRe ; ++k)
+    {
+        const uint64_t n = (static_cast<uint64_t>(refs[k].data[0]) << 8) | refs[k].data[1];
+        total += n;
+        longest = n > longest ? n : longest;
+    }
+    const bool walkOnHost = longest > kTranscodeHostWalkFrames && longest * 64 > total;
+    DcsStatus st = DCS_OK;
+    for (int attempt = walkOnHost ? 1 : 0 ; attempt < 2 ; ++attempt)
+    {
+        TranscodeDecode d;
+        d.ctx = ctx;
+        st = attempt == 0 ? transcodeDecodeOnDevice(ctx, refs, nRe, d) : transcodeDecodeOnHost(ctx, refs, nRe, d);
+        bool unusable = false;
+        if (st == DCS_OK)
+        {
+            std::vector<uint64_t> sampleOffsets(static_cast<size_t>(nRe) + 1);
+            for (uint32_t k = 0 ; k <= nRe ; ++k)
+                sampleOffsets[k] = static_cast<uint64_t>(d.firstJob[k]) * DCS_FRAME_SAMPLES;
+            st = encode(d.batch->dPcm.as<const int16_t>(), d.batch->dErr,
+                        attempt == 0 ? d.batch->hStage.as<const volatile uint32_t>() : nullptr, sampleOffsets.data(), &unusable);
+        }
+        d.release();
+        if (!unusable)
+            break;
+    }
+    return st;
+}
+
+DcsEncodeInfo dcsTranscodeCopyInfo(const DcsStreamRef &s)
+{
+    const uint8_t *p = s.data;
+    const bool is94 = s.os == DCS_OS94 || s.os == DCS_OS95;
+    const int sub = is94 ? (s.len > 3 ? (p[3] >> 7) << 1 : 0) | (s.len > 4 ? p[4] >> 7 : 0) : 0;
+    return DcsEncodeInfo{ p[2] >> 7, sub, static_cast<int32_t>((static_cast<uint32_t>(p[0]) << 8) | p[1]), static_cast<int32_t>(s.len), -1 };
+}
+
 extern "C" DcsStatus dcs_transcode_plan(const DcsStreamRef *src, uint32_t nStreams, const DcsEncodeParams *target, uint32_t flags,
                                         int32_t *actionOut, uint64_t *boundOut)
 {
@@ -145,41 +190,16 @@ extern "C" DcsStatus dcs_transcode_streams(DcsCtx *ctx, const DcsStreamRef *src,
     }
     else
     {
-        // The device index walk is one wavefront per stream, serial over its frames (about 7.6 us a frame on MI355X): a list
-        // that one long source dominates is walked faster by the host pool, and then planned on the host as well.
-        uint64_t total = 0, longest = 0;
-        for (const DcsStreamRef &r : refs)
-        {
-            const uint64_t n = (static_cast<uint64_t>(r.data[0]) << 8) | r.data[1];
-            total += n;
-            longest = n > longest ? n : longest;
-        }
-        const bool walkOnHost = longest > kTranscodeHostWalkFrames && longest * 64 > total;
-        for (int attempt = walkOnHost ? 1 : 0 ; attempt < 2 ; ++attempt)
-        {
-            TranscodeDecode d;
-            d.ctx = ctx;
-            st = attempt == 0 ? transcodeDecodeOnDevice(ctx, refs.data(), nRe, d) : transcodeDecodeOnHost(ctx, refs.data(), nRe, d);
-            bool unusable = false;
-            if (st == DCS_OK)
-            {
-                std::vector<uint64_t> sampleOffsets(static_cast<size_t>(nRe) + 1);
-                for (uint32_t k = 0 ; k <= nRe ; ++k)
-                    sampleOffsets[k] = static_cast<uint64_t>(d.firstJob[k]) * DCS_FRAME_SAMPLES;
-                st = dcsEncodeFromDevice(ctx, d.batch->dPcm.as<const int16_t>(), d.batch->dErr,
-                                         attempt == 0 ? d.batch->hStage.as<const volatile uint32_t>() : nullptr,
-                                         sampleOffsets.data(), label.data(), nRe, target, &unusable, encOffsets.data(), encInfo.data(),
-                                         [&](const uint64_t *encOffs, uint64_t total) -> uint8_t * {
-                                             if (layout(encOffs) > outCap || out == nullptr)
-                                                 return nullptr;
-                                             encoded.resize(total);
-                                             return encoded.data();
-                                         });
-            }
-            d.release();
-            if (!unusable)
-                break;
-        }
+        st = dcsTranscodeDecoded(ctx, refs.data(), nRe, [&](const int16_t *dPcm, const uint32_t *dErr, const volatile uint32_t *planFlag,
+                                                            const uint64_t *sampleOffsets, bool *unusable) {
+            return dcsEncodeFromDevice(ctx, dPcm, dErr, planFlag, sampleOffsets, label.data(), nRe, target, unusable, encOffsets.data(),
+                                       encInfo.data(), [&](const uint64_t *encOffs, uint64_t total) -> uint8_t * {
+                                           if (layout(encOffs) > outCap || out == nullptr)
+                                               return nullptr;
+                                           encoded.resize(total);
+                                           return encoded.data();
+                                       });
+        });
         if (st != DCS_OK && st != DCS_ERR_CAPACITY)
             return st;
     }
@@ -193,12 +213,7 @@ extern "C" DcsStatus dcs_transcode_streams(DcsCtx *ctx, const DcsStreamRef *src,
             if (action[i] == DCS_TRANSCODE_REENCODED)
                 t.enc = encInfo[r++];
             else
-            {
-                // what the copy's header says: the type bit, the 1994+ sub-type bits (header bytes 1 and 2), no cutoff known
-                const bool is94 = src[i].os == DCS_OS94 || src[i].os == DCS_OS95;
-                const int sub = is94 ? (src[i].len > 3 ? (p[3] >> 7) << 1 : 0) | (src[i].len > 4 ? p[4] >> 7 : 0) : 0;
-                t.enc = DcsEncodeInfo{ p[2] >> 7, sub, t.srcFrames, static_cast<int32_t>(src[i].len), -1 };
-            }
+                t.enc = dcsTranscodeCopyInfo(src[i]);
         }
     if (st != DCS_OK)
         return st;

@@ -1010,7 +1010,9 @@ DcsStatus dcs_encode93_rd_streams(DcsCtx *ctx, const float *pcm, const uint64_t 
  * fit->fits is 0, with DCS_OK.  params->targetBitRate must be valid but is not read.  Input, parameter validation, capacity
  * (DCS_ERR_CAPACITY with outOffsets and *fit written, and nothing else), ordering, errors and the bound functions are the
  * per-stream calls'.  info, infoRd and fit may be NULL.  These entry points and DcsEncodeRdFitInfo are additions: nothing
- * that existed changed its layout or behaviour, so DCS_ABI_VERSION stays 9. */
+ * that existed changed its layout or behaviour, so DCS_ABI_VERSION stays 9.  The same holds for the budget calls on other
+ * sources further down (DcsBudget, dcs_encode_streams_at_budget, dcs_transcode_plan_budget, dcs_transcode_streams_budget,
+ * dcs_encode_files_plan_budget, dcs_encode_files_budget). */
 typedef struct DcsEncodeRdFitInfo
 {
     uint64_t totalBytes;               /* as given                                                                         */
@@ -1424,6 +1426,73 @@ DcsStatus dcs_encode_files_level(DcsCtx *ctx, const uint8_t *files, const uint64
                                  const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags, uint8_t *out,
                                  size_t outCap, uint64_t *outOffsets, DcsEncodeFileInfo *info,
                                  const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo);
+
+/* ------------------------------------------------------------------------------------------------
+ * Budgets from any source (INTEGRATION.md "Budgets from any source"): the searched encoders
+ * (dcs_encode_rd_streams, dcs_encode93_rd_streams and their _fit calls) behind the three other kinds of source that the
+ * reference-equal encoders take.  params->formatVersion picks the family: 0x9400 the 1994+ search, 0x9301 / 0x9302 the OS93
+ * Type-0 search, each checked as its per-stream call checks it (OS93 Type 1 is refused with that call's message).  A JOB is
+ * one stream or file of the call, in input order; budgetBytes and capBytes are indexed by job.
+ *   shared == 0   one budget per job: budgetBytes[j], or with budgetBytes NULL the frame bits the set's targetBitRate gives,
+ *                 as dcs_encode_rd_streams reads them; totalBytes, capBytes and fit are not read
+ *   shared == 1   one budget for the set: all jobs' streams together at most totalBytes, job j at most capBytes[j] (or NULL),
+ *                 *fit (or NULL) the allocator's record, as dcs_encode_rd_fit; budgetBytes must be NULL
+ * What is written keeps the searched calls' contract word for word: every stream decodes to its last bit, infoRd[j].sqErr is
+ * exact, in the shared form a searched job's stream is as long as its allotment, size never refuses and fits = 0 reports a
+ * budget that cannot be kept.  A job that is COPIED (an existing stream that already is of the target's family, below) is
+ * not searched: its infoRd is zeros with fits = 1.  In the shared form the copies are taken first and their bytes come off
+ * totalBytes; the searched jobs share what is left (nothing, where the copies alone exceed the total: every searched job is
+ * then written at its smallest and fit->fits is 0).  fit->totalBytes is the caller's total; fit->leastBytes and
+ * fit->usedBytes count copies and searched streams TOGETHER; fit->sqErr, nSteps and stepsTaken are the searched jobs'.
+ * These entry points and DcsBudget are additions as well: DCS_ABI_VERSION stays 9. */
+typedef struct DcsBudget
+{
+    const uint32_t *budgetBytes;       /* per job, or NULL: the set's targetBitRate, as dcs_encode_rd_streams              */
+    uint64_t        totalBytes;        /* shared != 0: all jobs' streams together, as dcs_encode_rd_fit                    */
+    const uint32_t *capBytes;          /* shared != 0: per job or NULL, as dcs_encode_rd_fit                               */
+    uint32_t        shared;            /* 0: one budget per job; 1: one budget for the set                                 */
+    DcsEncodeRdFitInfo *fit;           /* shared != 0: the allocator's record, or NULL                                     */
+} DcsBudget;
+/* dcs_encode_streams_at_level with the searched encoder behind the level stage: arguments, resampling, level, gate and
+ * levelInfo are that call's (INTEGRATION "Resampling" and "Level").  Stream i's bytes, info and infoRd (and *budget->fit)
+ * are those of dcs_encode_rd_streams / dcs_encode93_rd_streams / the _fit call on the floats dcs_resample_streams_level
+ * returns for the same arguments.  The bound of a stream is dcs_encode_rd_bound / dcs_encode93_rd_bound of its resampled
+ * length. */
+DcsStatus dcs_encode_streams_at_budget(DcsCtx *ctx, const float *pcm, const uint64_t *sampleOffsets, uint32_t nStreams,
+                                       const uint32_t *rates, const int32_t *channels, const DcsResampleFilter *filter,
+                                       uint32_t flags, const DcsEncodeParams *params, const DcsBudget *budget, uint8_t *out,
+                                       size_t outCap, uint64_t *outOffsets, DcsEncodeInfo *info, DcsEncodeRdInfo *infoRd,
+                                       const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo);
+/* dcs_transcode_streams with the searched encoder behind the decode.  A source that dcs_transcode_plan would copy is
+ * still COPIED (verbatim) when it keeps to its own bound: per job, len <= budgetBytes[i] (always, with budgetBytes NULL);
+ * shared, capBytes NULL or len <= capBytes[i].  Every other source, and every source with DCS_TRANSCODE_REENCODE_ALL, is
+ * decoded as dcs_transcode_streams decodes it and SEARCHED (action DCS_TRANSCODE_REENCODED).  Errors as
+ * dcs_transcode_streams.  dcs_transcode_plan_budget (host only): the actions, and boundOut = len for a copy,
+ * dcs_encode_rd_bound / dcs_encode93_rd_bound of (nFrames + 1) * 240 for a searched source. */
+DcsStatus dcs_transcode_plan_budget(const DcsStreamRef *src, uint32_t nStreams, const DcsEncodeParams *target, uint32_t flags,
+                                    const DcsBudget *budget, int32_t *actionOut, uint64_t *boundOut);
+DcsStatus dcs_transcode_streams_budget(DcsCtx *ctx, const DcsStreamRef *src, uint32_t nStreams, const DcsEncodeParams *target,
+                                       uint32_t flags, const DcsBudget *budget, uint8_t *out, size_t outCap,
+                                       uint64_t *outOffsets, DcsTranscodeInfo *info, DcsEncodeRdInfo *infoRd);
+/* dcs_encode_files_level with the searched encoder: sniffing, planning, reading, conversion, level and error naming are
+ * that call's.  Jobs are the files in input order.  flags: the resampler's, and DCS_FILES_REENCODE_ALL, which searches every
+ * DCSa container; without it a container follows dcs_transcode_streams_budget's copy rule.  The searched containers' PCM
+ * joins the converted WAV and FLAC signals on the device, and ONE search (one allocation, in the shared form) covers the
+ * list.  A WAV or FLAC file's bytes are those of dcs_encode_streams_at_budget on its decoded samples, a container's those
+ * of dcs_transcode_streams_budget. */
+#define DCS_FILES_REENCODE_ALL  0x100u     /* flags of dcs_encode_files_budget */
+/* host only, no GPU: dcs_encode_files_plan under the budget's rules.  kindOut[i]: DCS_FILE_WAV, DCS_FILE_FLAC, or what the
+ * copy rule makes of a container (DCS_FILE_DCSA_COPY / DCS_FILE_DCSA_REENCODE); boundOut[i]: the bytes file i's stream can
+ * take (a copy's length, dcs_encode_rd_bound / dcs_encode93_rd_bound of any other).  Either may be NULL.  A refusal is the
+ * first file's that dcs_encode_files_budget would refuse before it decodes anything. */
+DcsStatus dcs_encode_files_plan_budget(const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
+                                       const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags,
+                                       const DcsBudget *budget, int32_t *kindOut, uint64_t *boundOut);
+DcsStatus dcs_encode_files_budget(DcsCtx *ctx, const uint8_t *files, const uint64_t *fileOffsets, uint32_t nFiles,
+                                  const DcsEncodeParams *params, const DcsResampleFilter *filter, uint32_t flags,
+                                  const DcsBudget *budget, uint8_t *out, size_t outCap, uint64_t *outOffsets,
+                                  DcsEncodeFileInfo *info, DcsEncodeRdInfo *infoRd,
+                                  const DcsLevel *levels, uint32_t nLevels, DcsLevelInfo *levelInfo);
 
 /* ------------------------------------------------------------------------------------------------
  * Sweeping parameters and fitting a byte budget.  A JOB is one stream encoded with one parameter set.  dcs_encode_sweep
